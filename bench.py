@@ -33,14 +33,15 @@ HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    # (defaults: 100 steps of ~0.43 ms are a 43-ms timed region, three of them; regions of 20 steps spread by 4 % on one box)
-    ap.add_argument("--steps", type=int, default=100)
+    # (defaults: 100 steps of ~0.43 ms are a 43-ms timed region; regions of 20 steps spread by 4 % on one box)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (with --repeat R > 1: R timed regions of this many steps)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shard", choices=["auto", "tiles", "chroms"], default="auto",
                     help="N > 1, strong scaling: equal TILE RANGES of the genome per rank + one all-reduce(sum) of the per-chromosome rows "
                          "(max_shift <= 1023: pmx_cc_batch_ranges_dev), or whole chromosomes by LPT + all-gather; auto: tiles where supported")
-    ap.add_argument("--repeat", type=int, default=3,
-                    help="repetitions of the timed region of --steps steps; the line reports the median one (min / median / max in `repetitions`)")
+    ap.add_argument("--repeat", type=int, default=1,
+                    help="timed regions of --steps steps (default 1: --steps is the number of timed steps); the line reports the "
+                         "median one (min / median / max in `repetitions`)")
     ap.add_argument("--workload", choices=["hg38", "stress"], default="hg38",
                     help="hg38: BASELINE config 4 (default, the metric's configuration); stress: config 5, one "
                          "synthetic 10 Gbp / 200-chromosome genome sharded over the ranks, max_shift 5000")
@@ -72,7 +73,40 @@ def parse():
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-positions -> rows leg (SURVEY 8d)")
     ap.add_argument("--no-ingest", action="store_true", help="skip the BAM-file leg (SURVEY 8 row f1: device ingest against the host reader)")
     ap.add_argument("--ingest-reads", type=int, default=2_000_000, help="reads of the synthetic BAM file of that leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the exchanged per-chromosome rows and totals) "
+                         "as DIR/<name>.npy, float64, at most 64 MB in all; the inputs are seeded, so two builds compare output for output")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rows, totals):
+    """The timed path's result of one step, as its caller receives it: `rows` [jobs, PMX_NROWS, S+1] (one block per chromosome
+    job, all ranks' after the exchange) and `totals` [PMX_NROWS, S+1], int64 on the device -> float64 .npy (exact: every count is
+    below 2**53).  The scalar row's kernel-path marker (column 3) says which kernel ran, not what it computed, and is left out:
+      rows.npy     [jobs, 5, S+1]  NCC ccbins, MSCC forward sum, reverse sum, ccbins, mappable length (PMX_ROW_NCC_CCBINS..MLEN)
+      scalars.npy  [jobs, 3]       popcount of F, R, M (PMX_ROW_SCALARS[0:3])
+      totals.npy   [5, S+1], totals_scalars.npy [3]   the same summed over the jobs
+    jobs.npy lists the job indices dumped (bench's job order: genome sample, then chromosome): all of them, or above 64 MB in all a
+    fixed, seeded sample."""
+    from pymasc_amd import ffi
+    rows = rows.cpu().numpy()
+    totals = totals.cpu().numpy()
+    nd = ffi.PMX_ROW_SCALARS
+    jobs = np.arange(rows.shape[0])
+    per_job = 8 * (nd * rows.shape[2] + 3 + 1)                  # rows + scalars + its entry in jobs.npy
+    fit = max((DUMP_LIMIT_BYTES - 8 * (nd * rows.shape[2] + 3)) // per_job, 1)
+    if jobs.size > fit:
+        jobs = np.sort(np.random.default_rng(20240611).choice(jobs.size, size=fit, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"rows": rows[jobs, :nd], "scalars": rows[jobs, nd, :3], "totals": totals[:nd], "totals_scalars": totals[nd, :3],
+              "jobs": jobs}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays),
+            "bytes": int(sum(8 * a.size for a in arrays.values())), "jobs": int(jobs.size), "jobs_total": int(rows.shape[0])}
 
 
 def ingest_leg(n_reads, mapq=10):
@@ -457,8 +491,13 @@ def main():
     # (two empty launches take 10-20 us together, whatever the shard size; real work on dense tiles takes milliseconds)
     prof_level = 2 if (probe[ffi.PMX_KERNEL_CC_EVENTS] > 0 and fallback_ms > 0.04) else 1
     ctx.set_profiling(prof_level)
+    # One untimed region of args.steps steps first, at the profiling level of the timed one: a region that follows only the short
+    # warm-up reads up to 5 % slower per step, kernel time included, than one that follows a region of its own length (same box,
+    # 20-step regions); the timed region below sees what the second and third of three back-to-back regions see.
+    for _ in range(args.steps):
+        step()
     # The timed region: EXACTLY args.steps steps between two fences (barrier + synchronize on both sides), max over ranks.
-    # It is run `args.repeat` times (default 3) and the line reports the MEDIAN repetition -- elapsed, ms_per_step, value and
+    # It is run `args.repeat` times (default 1) and the line reports the MEDIAN repetition -- elapsed, ms_per_step, value and
     # the live kernel times all belong to that one repetition of args.steps steps; min / median / max go into `repetitions`
     # (a 10-ms region on one box spreads by a few per cent, more than some of the A/B differences DESIGN.md books).
     reps = []
@@ -483,6 +522,10 @@ def main():
 
     # consistency of the exchange: all-reduced totals == sum of gathered rows (integers, exact)
     assert torch.equal(rows.sum(dim=0), totals), "result exchange mismatch"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed (every rank holds every job's rows after the exchange; rank 0 writes them)
+        dumped = dump_outputs(args.dump_outputs, rows, totals)
     if shard_tiles:
         # the shares must add up to whole chromosomes: every block carries ONE path marker (the share that holds tile 0 writes
         # it), and this rank's whole chromosomes must equal a plain pmx_cc_batch_dev run of them
@@ -839,6 +882,7 @@ def main():
         "end_to_end": end_to_end,
         "end_to_end_calculator": calc_leg,
         "gen_seconds": round(t_gen, 2),
+        "dumped_outputs": dumped,
     }
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
