@@ -76,6 +76,20 @@ int pmx_dbam_fetch(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref_id, int32
  * written.  More than 65536 runs (an unsorted file): PMX_DBAM_ERR_INVALID -- take the arrays through pmx_dbam_fetch then. */
 int64_t pmx_dbam_runs(pmx_dbam *b, int64_t cap, int64_t *start, int32_t *ref_id, int32_t *first_pos1, int32_t *last_pos1);
 
+/* Read-length histogram with the ESTIMATOR's filter (PyMaSC core/readlen.pyx:139-162; not the filter of pmx_dbam_decode):
+ * exactly what pmx_bam_readlen_hist (pymasc_amd_io.h) gives -- records with ref_id < 0 invisible; nreads, npaired, nread2;
+ * unmapped ones in nunmapped only; the others counted at their query length when not duplicates and mapq >= mapq_min (read2,
+ * secondary, supplementary, QC-fail included); query length 0 in nnoqlen.  One more walk over the verified record chain already
+ * in HBM (no second inflate), with tables of its own: the arrays of the last pmx_dbam_decode are left as they are, and the
+ * order of the two calls does not matter.  Malformed records: the error codes and messages of pmx_dbam_decode.
+ * Two-call protocol like pmx_dbam_runs: lengths == NULL returns the number of distinct counted lengths; otherwise fills up to
+ * cap entries sorted by length -- counts[i], first[i] = byte offset in the inflated stream (header included) of the first
+ * counted record of that length (the file-order key MODE's tie rule needs; the same key as pmx_bam_readlen_hist's).
+ * The result is kept for the next call with the same mapq_min. */
+int64_t pmx_dbam_readlen_hist(pmx_dbam *b, uint32_t mapq_min, int64_t cap, int32_t *lengths, uint64_t *counts, uint64_t *first);
+/* c = {nreads, nunmapped, ncounted, npaired, nread2, nnoqlen} of the last pmx_dbam_readlen_hist */
+int pmx_dbam_readlen_counters(const pmx_dbam *b, uint64_t c[6]);
+
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
  * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong. */
 int pmx_dbam_counters(const pmx_dbam *b, uint64_t *records, uint64_t *kept, uint64_t *bytes_out, uint64_t *bytes_in,

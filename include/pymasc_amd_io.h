@@ -78,6 +78,23 @@ int pmx_bam_fetch_ref(pmx_bam *b, int32_t ref_id);
  * compressed bytes consumed. */
 int pmx_bam_counters(const pmx_bam *b, uint64_t *records, uint64_t *kept, uint64_t *bytes_out, uint64_t *bytes_in);
 
+/* Read-length histogram with the ESTIMATOR's filter, which is not the one above (PyMaSC core/readlen.pyx:estimate_readlen,
+ * readlen.pyx:139-162), over every alignment record of the file in file order:
+ *   ref_id < 0                        skipped, not counted anywhere                     (readlen.pyx:140-142)
+ *   otherwise nreads; flag & 0x1 -> npaired, and with flag & 0x80 also nread2      (readlen.pyx:144-148)
+ *   flag & 0x4                        nunmapped, nothing else                           (readlen.pyx:155-156)
+ *   !(flag & 0x400), mapq >= mapq_min counted at its query length (as read_len above; read2, secondary, supplementary
+ *                                     and QC-fail records included)                     (readlen.pyx:157-162)
+ *   ... query length 0 or no CIGAR    nnoqlen instead (infer_query_length() is None; the reference fails on it)
+ * One pass on the reader's threads with buffers of its own: a pmx_bam_next_batch iteration in progress is not disturbed.
+ * Two-call protocol like pmx_bigwig_fetch: lengths == NULL returns the number of distinct counted lengths; otherwise fills up
+ * to cap entries sorted by length -- counts[i], first[i] = offset in the uncompressed stream (header included) of the first
+ * counted record of that length: the same key as pmx_dbam_readlen_hist's.  The result is kept for the next call with the same
+ * mapq_min. */
+int64_t pmx_bam_readlen_hist(pmx_bam *b, uint32_t mapq_min, int64_t cap, int32_t *lengths, uint64_t *counts, uint64_t *first);
+/* c = {nreads, nunmapped, ncounted, npaired, nread2, nnoqlen} of the last pmx_bam_readlen_hist */
+int pmx_bam_readlen_counters(const pmx_bam *b, uint64_t c[6]);
+
 /* ---- BigWig (bbi) ----------------------------------------------------------------------------------------- */
 typedef struct pmx_bigwig pmx_bigwig;
 

@@ -32,6 +32,7 @@ IO_EXPORTS = [
     "pmx_io_last_error", "pmx_io_version",
     "pmx_bam_open", "pmx_bam_close", "pmx_bam_nref", "pmx_bam_ref_name", "pmx_bam_ref_len", "pmx_bam_header_text",
     "pmx_bam_next_batch", "pmx_bam_counters", "pmx_bam_index_load", "pmx_bam_has_index", "pmx_bam_fetch_ref",
+    "pmx_bam_readlen_hist", "pmx_bam_readlen_counters",
     "pmx_bigwig_open", "pmx_bigwig_close", "pmx_bigwig_nchrom", "pmx_bigwig_chrom_name", "pmx_bigwig_chrom_len",
     "pmx_bigwig_fetch",
 ]
@@ -86,6 +87,10 @@ def load_io_library():
     L.pmx_bam_has_index.restype = ctypes.c_int
     L.pmx_bam_fetch_ref.argtypes = [vp, i32]
     L.pmx_bam_fetch_ref.restype = ctypes.c_int
+    L.pmx_bam_readlen_hist.argtypes = [vp, u32, i64, vp, vp, vp]
+    L.pmx_bam_readlen_hist.restype = i64
+    L.pmx_bam_readlen_counters.argtypes = [vp, ctypes.POINTER(u64)]
+    L.pmx_bam_readlen_counters.restype = ctypes.c_int
     L.pmx_bigwig_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pmx_bigwig_open.restype = ctypes.c_int
     L.pmx_bigwig_close.argtypes = [vp]
@@ -170,6 +175,16 @@ class BamReader:
         if rc:
             _raise(rc)
         return dict(zip(("records", "kept", "bytes_out", "bytes_in"), (int(x.value) for x in v)))
+
+    def read_length_histogram(self, mapq_criteria: int = 0):
+        """The read-length histogram with the estimator's filter (PyMaSC core/readlen.pyx:estimate_readlen): one pass over the
+        whole file on the reader's threads, beside (not inside) a ``batches`` iteration.  Returns a
+        ``pymasc_amd.readlen.ReadLengthHistogram``; its first-occurrence keys are offsets in the uncompressed stream."""
+        from .readlen import histogram_from_library
+        if self._h is None:
+            raise ValueError("I/O operation on closed BAM reader")
+        return histogram_from_library(self._L.pmx_bam_readlen_hist, self._L.pmx_bam_readlen_counters, self._h, mapq_criteria,
+                                      _raise)
 
     def fetch(self, reference: str, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE,
               batch: int = 1 << 22) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:

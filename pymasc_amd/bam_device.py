@@ -23,7 +23,8 @@ _LIB_NAME = "libpymasc_ingest.so"
 INGEST_EXPORTS = [
     "pmx_dbam_last_error", "pmx_dbam_version", "pmx_dbam_open", "pmx_dbam_close", "pmx_dbam_nref", "pmx_dbam_ref_name",
     "pmx_dbam_ref_len", "pmx_dbam_header_text", "pmx_dbam_decode", "pmx_dbam_device_arrays", "pmx_dbam_fetch",
-    "pmx_dbam_runs", "pmx_dbam_counters", "pmx_dbam_timings", "pmx_dbam_inflated",
+    "pmx_dbam_runs", "pmx_dbam_counters", "pmx_dbam_timings", "pmx_dbam_inflated", "pmx_dbam_readlen_hist",
+    "pmx_dbam_readlen_counters",
     "pmx_dbw_open", "pmx_dbw_close", "pmx_dbw_nchrom", "pmx_dbw_chrom_name", "pmx_dbw_chrom_len", "pmx_dbw_fetch", "pmx_dbw_device_arrays",
     "pmx_dbw_sorted", "pmx_dbw_copy",
 ]
@@ -73,6 +74,10 @@ def load_ingest_library():
     L.pmx_dbam_timings.restype = ctypes.c_int
     L.pmx_dbam_inflated.argtypes = [vp, u64, u64, vp]
     L.pmx_dbam_inflated.restype = ctypes.c_int
+    L.pmx_dbam_readlen_hist.argtypes = [vp, u32, i64, vp, vp, vp]
+    L.pmx_dbam_readlen_hist.restype = i64
+    L.pmx_dbam_readlen_counters.argtypes = [vp, ctypes.POINTER(u64)]
+    L.pmx_dbam_readlen_counters.restype = ctypes.c_int
     L.pmx_dbw_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     L.pmx_dbw_open.restype = ctypes.c_int
     L.pmx_dbw_close.argtypes = [vp]
@@ -179,6 +184,16 @@ class DeviceBamReader:
         if n < 0:
             _raise(n)
         return int(n)
+
+    def read_length_histogram(self, mapq_criteria: int = 0):
+        """The read-length histogram with the estimator's filter (PyMaSC core/readlen.pyx:estimate_readlen), built by one more
+        walk over the record chain already in HBM; the arrays of the last ``decode`` are left as they are.  Returns a
+        ``pymasc_amd.readlen.ReadLengthHistogram``; its first-occurrence keys are byte offsets in the inflated stream."""
+        from .readlen import histogram_from_library
+        if self._h is None:
+            raise ValueError("I/O operation on closed BAM reader")
+        return histogram_from_library(self._L.pmx_dbam_readlen_hist, self._L.pmx_dbam_readlen_counters, self._h, mapq_criteria,
+                                      _raise)
 
     def device_arrays(self) -> Tuple[int, int, int, int]:
         """Device addresses of (ref_id int32, pos1 int32, read_len int32, reverse uint8) of the last decode."""

@@ -806,6 +806,147 @@ __global__ void __launch_bounds__(64) k_bam_walk(const WalkArgs A)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Read-length histogram with the ESTIMATOR's filter (PyMaSC core/readlen.pyx:139-162), which is not the calculation's: over
+// the verified chain, records with ref_id < 0 are invisible, the rest counted in nreads (/ npaired / nread2), unmapped ones in
+// nunmapped only, and of the others those that are no duplicate and reach mapq_min are counted at their query length -- read2,
+// secondary, supplementary and QC-fail records included; a query length of 0 goes to nnoqlen instead.  Every distinct length
+// gets its count and its first counted occurrence (the smallest byte offset in the inflated stream: a file-order key).
+//
+// Contention is the point: in short-read data nearly every record has ONE length, and an atomic per record on one address would
+// serialise ~20 M of them at L2.  So a lane keeps the RUN it is in (length, count, first offset) in registers and flushes only
+// when the length changes; flushes of lengths < RL_SHORT go to a per-workgroup LDS table (count u32, first u64), merged into HBM
+// with one atomic pair per non-empty bin per workgroup; longer lengths (long-read data: many values, little contention) are only
+// counted in pass 0 and inserted in pass 1, into a global open-addressing table of 2x as many slots as there were such flushes
+// (so its size is bounded by the number of records, never by the largest length).  Pass 1 runs only when pass 0 saw one.
+#define RL_SHORT 1024u
+#define RL_NCNT 7u               // nreads, nunmapped, ncounted, npaired, nread2, nnoqlen, (long-length flushes)
+struct RlArgs {
+    const u8 *D;
+    u64 N, base;                 // D = the inflated stream from its first record on, at offset `base`
+    int nref;
+    u32 mapq_min;
+    u64 npieces;
+    const u64 *spec;             // verified start of every piece (the closed chain)
+    unsigned long long *bins;    // [RL_SHORT] counts, [RL_SHORT] first offsets, [RL_NCNT] counters, first error
+    u32 *hkey;                   // (pass 1) open-addressing table: key = length (0 = empty), count, first offset
+    unsigned long long *hcnt, *hfirst;
+    u32 hmask;
+};
+
+template <int PASS>
+__global__ void __launch_bounds__(256) k_bam_readlen(const RlArgs A)
+{
+    __shared__ u32 s_cnt[PASS == 0 ? RL_SHORT : 1];
+    __shared__ unsigned long long s_first[PASS == 0 ? RL_SHORT : 1];
+    __shared__ u32 s_c[RL_NCNT];
+    const u32 t = threadIdx.x;
+    if (PASS == 0) {
+        for (u32 i = t; i < RL_SHORT; i += 256u) {
+            s_cnt[i] = 0;
+            s_first[i] = ~0ull;
+        }
+        if (t < RL_NCNT) s_c[t] = 0;
+        __syncthreads();
+    }
+    u32 c_[RL_NCNT] = {0, 0, 0, 0, 0, 0, 0};
+    u32 run_len = 0, run_cnt = 0;
+    u64 run_first = 0;
+    auto flush = [&]() {
+        if (!run_cnt) return;
+        if (run_len < RL_SHORT) {
+            if (PASS == 0) {
+                atomicAdd(&s_cnt[run_len], run_cnt);
+                atomicMin(&s_first[run_len], (unsigned long long)run_first);
+            }
+        } else if (PASS == 0) {
+            c_[6]++;
+        } else {
+            u32 h = (run_len * 0x9E3779B1u) & A.hmask;
+            for (u32 probe = 0; probe <= A.hmask; probe++, h = (h + 1u) & A.hmask) {   // (2x the slots of keys: always found)
+                const u32 k = atomicCAS(&A.hkey[h], 0u, run_len);
+                if (k == 0u || k == run_len) {
+                    atomicAdd(&A.hcnt[h], (unsigned long long)run_cnt);
+                    atomicMin(&A.hfirst[h], (unsigned long long)run_first);
+                    break;
+                }
+            }
+        }
+    };
+    const u64 c = (u64)blockIdx.x * 256u + t;
+    if (c < A.npieces) {
+        const u8 *__restrict__ D = A.D;
+        const u64 cend = (c + 1u) * WALK_PIECE;
+        u64 s = A.spec[c];
+        while (s < cend && s < A.N) {
+            u32 err = 0, bs = 0;
+            if (s + 4u > A.N) {
+                err = REC_ERR_EOF;
+            } else {
+                bs = ld32u(D + s);
+                if (bs < 32u) err = REC_ERR_BS;
+                else if (s + 4u + bs > A.N) err = REC_ERR_EOF;
+            }
+            const u8 *rec = D + s + 4;
+            u32 l_name = 0, n_cig = 0;
+            int ref = -1;
+            if (!err) {
+                ref = (int)ld32u(rec);
+                l_name = rec[8];
+                n_cig = ld16u(rec + 12);
+                if (32ull + l_name + 4ull * n_cig > bs) err = REC_ERR_SHORT;
+                else if (ref >= A.nref) err = REC_ERR_REF;
+            }
+            if (err) {                   // reported as pmx_dbam_decode reports it
+                if (PASS == 0) atomicMin(&A.bins[2u * RL_SHORT + RL_NCNT], (unsigned long long)((s << 4) | err));
+                break;
+            }
+            if (ref >= 0) {
+                const u32 mapq = rec[9], flag = ld16u(rec + 14);
+                c_[0]++;
+                if (flag & 0x1u) {
+                    c_[3]++;
+                    if (flag & 0x80u) c_[4]++;
+                }
+                if (flag & 0x4u) {
+                    c_[1]++;
+                } else if (!(flag & 0x400u) && mapq >= A.mapq_min) {
+                    const u32 l_seq = ld32u(rec + 16);
+                    const u8 *cig = rec + 32u + l_name;
+                    u32 n = n_cig;
+                    long_cigar(rec, bs, l_name, n_cig, l_seq, cig, n);
+                    const u32 q = cigar_qlen(cig, n);
+                    if (q == 0u || q > 0x7fffffffu) {
+                        c_[5]++;
+                    } else {
+                        c_[2]++;
+                        if (q != run_len) {
+                            flush();
+                            run_len = q;
+                            run_cnt = 0;
+                            run_first = A.base + s;
+                        }
+                        run_cnt++;
+                    }
+                }
+            }
+            s += 4ull + bs;
+        }
+    }
+    flush();
+    if (PASS == 0) {
+        for (u32 k = 0; k < RL_NCNT; k++)
+            if (c_[k]) atomicAdd(&s_c[k], c_[k]);
+        __syncthreads();
+        for (u32 i = t; i < RL_SHORT; i += 256u)
+            if (s_cnt[i]) {
+                atomicAdd(&A.bins[i], (unsigned long long)s_cnt[i]);
+                atomicMin(&A.bins[RL_SHORT + i], s_first[i]);
+            }
+        if (t < RL_NCNT && s_c[t]) atomicAdd(&A.bins[2u * RL_SHORT + t], (unsigned long long)s_c[t]);
+    }
+}
+
 // exclusive prefix sums of kept[] (one workgroup: a few hundred thousand pieces at most per GB), totals of kept[] and cnt[]
 __global__ void __launch_bounds__(1024) k_bam_scan(const u32 *__restrict__ kept, const u32 *__restrict__ cnt, u64 n,
                                                   u64 *__restrict__ kept_base, u64 *__restrict__ totals)
@@ -947,6 +1088,16 @@ struct pmx_dbam {
     u8 *d_rev = nullptr;
     u64 out_cap = 0, n_kept = 0, n_records = 0, n_rewalked = 0;
     double t[6] = {0, 0, 0, 0, 0, 0};
+    // read-length histogram (pmx_dbam_readlen_hist): its own device tables, so that the arrays of the last decode stay as they are
+    unsigned long long *d_rl = nullptr;   // [RL_SHORT] counts, [RL_SHORT] first offsets, [RL_NCNT] counters, first error
+    struct LenBin {
+        int32_t len;
+        u64 count, first;
+    };
+    std::vector<LenBin> rl_hist;
+    u64 rl_c[6] = {0, 0, 0, 0, 0, 0};
+    bool rl_valid = false;
+    u32 rl_mapq = 0;
 };
 
 namespace {
@@ -1380,6 +1531,7 @@ void pmx_dbam_close(pmx_dbam *b)
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     if (b->kstream) (void)sync_kernels(*b);
     free_chain(*b);
+    if (b->d_rl) (void)hipFree(b->d_rl);
     for (hipStream_t x : b->kmore)
         if (x) (void)hipStreamDestroy(x);
     if (b->h_mem) (void)hipHostFree(b->h_mem);
@@ -1416,16 +1568,12 @@ int64_t pmx_dbam_decode(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, i
         return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_decode: ") + e.what());
     }
 }
-static int64_t dbam_decode_impl(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref)
+// The record chain of the inflated stream, built (k_bam_spec) or reused, and closed: k_bam_walk<0> from every piece's start,
+// counting with A's filter into A.end / A.cnt / A.kept, then k_bam_walk<1> until every piece starts where its neighbour ended.
+// After it b->d_spec holds the verified start of every piece (b->chain_ready); the counts belong to A's filter only.
+static int walk_chain(pmx_dbam *b, WalkArgs &A)
 {
-    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
-    HIPOK(hipSetDevice(b->device));
-    b->n_kept = b->n_records = 0;
-    if (b->npieces == 0) return 0;
     const u64 np = b->npieces;
-    const u64 N = b->N - b->data_beg;
-    const u8 *D = b->d_out + b->data_beg;
-    double t0 = now_s();
     if (!b->d_spec) {
         // (all of the chain's tables or none: a failed allocation must not leave a handle that skips this block next time)
         struct Undo {
@@ -1445,26 +1593,17 @@ static int64_t dbam_decode_impl(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_ex
         HIPOK(hipMalloc((void **)&b->d_first_error, 8));
         HIPOK(hipMalloc((void **)&b->d_spec, 8 * np));
         undo.keep = true;
-        hipLaunchKernelGGL(k_bam_spec, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, b->stream, D, N, (int)b->ref_names.size(), np, b->d_spec);
+        hipLaunchKernelGGL(k_bam_spec, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, b->stream, A.D, A.N, A.nref, np, b->d_spec);
         HIPOK(hipGetLastError());
         b->chain_ready = false;
         b->n_rewalked = 0;
     }
-    WalkArgs A;
-    A.D = D;
-    A.N = N;
-    A.nref = (int)b->ref_names.size();
-    A.mapq_min = mapq_min;
-    A.flag_exclude = flag_exclude;
-    A.want_ref = want_ref;
     A.npieces = np;
     A.spec = b->d_spec;
     A.end = b->d_end;
     A.cnt = b->d_cnt;
     A.kept = b->d_kept;
     A.kept_base = b->d_kept_base;
-    A.o_ref = A.o_pos = A.o_len = nullptr;
-    A.o_rev = nullptr;
     A.first_error = b->d_first_error;
     A.nmis = b->d_nmis;
     const dim3 wg((unsigned)((np + 63) / 64));
@@ -1483,6 +1622,41 @@ static int64_t dbam_decode_impl(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_ex
         b->n_rewalked += nmis;
         if (nmis == 0) b->chain_ready = true;
     }
+    return 0;
+}
+
+// the first malformed record a walk met (min over offset << 4 | REC_ERR_*), as pmx_dbam_decode reports it
+static int record_error(unsigned long long fe)
+{
+    switch (fe & 15ull) {
+    case REC_ERR_BS: return fail(PMX_DBAM_ERR_FORMAT, "BAM record with block_size < 32");
+    case REC_ERR_EOF: return fail(PMX_DBAM_ERR_FORMAT, "file ends inside an alignment record");
+    case REC_ERR_SHORT: return fail(PMX_DBAM_ERR_FORMAT, "BAM record shorter than its name and CIGAR");
+    default: return fail(PMX_DBAM_ERR_FORMAT, "BAM record refers to an unknown reference id");
+    }
+}
+
+static int64_t dbam_decode_impl(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref)
+{
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    HIPOK(hipSetDevice(b->device));
+    b->n_kept = b->n_records = 0;
+    if (b->npieces == 0) return 0;
+    const u64 np = b->npieces;
+    const u64 N = b->N - b->data_beg;
+    const u8 *D = b->d_out + b->data_beg;
+    double t0 = now_s();
+    WalkArgs A;
+    A.D = D;
+    A.N = N;
+    A.nref = (int)b->ref_names.size();
+    A.mapq_min = mapq_min;
+    A.flag_exclude = flag_exclude;
+    A.want_ref = want_ref;
+    A.o_ref = A.o_pos = A.o_len = nullptr;
+    A.o_rev = nullptr;
+    if (int rc = walk_chain(b, A)) return rc;
+    const dim3 wg((unsigned)((np + 63) / 64));
     hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, b->stream, b->d_kept, b->d_cnt, np, b->d_kept_base, b->d_totals);
     HIPOK(hipGetLastError());
     u64 totals[2] = {0, 0};
@@ -1513,14 +1687,7 @@ static int64_t dbam_decode_impl(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_ex
     HIPOK(hipMemcpyAsync(&fe, b->d_first_error, 8, hipMemcpyDeviceToHost, b->stream));
     HIPOK(hipStreamSynchronize(b->stream));
     b->t[5] = now_s() - t1;
-    if (fe != ~0ull) {
-        switch (fe & 15ull) {
-        case REC_ERR_BS: return fail(PMX_DBAM_ERR_FORMAT, "BAM record with block_size < 32");
-        case REC_ERR_EOF: return fail(PMX_DBAM_ERR_FORMAT, "file ends inside an alignment record");
-        case REC_ERR_SHORT: return fail(PMX_DBAM_ERR_FORMAT, "BAM record shorter than its name and CIGAR");
-        default: return fail(PMX_DBAM_ERR_FORMAT, "BAM record refers to an unknown reference id");
-        }
-    }
+    if (fe != ~0ull) return record_error(fe);
     b->n_kept = totals[0];
     b->n_records = totals[1];
     b->chain_mapq = mapq_min;
@@ -1598,6 +1765,131 @@ static int64_t dbam_runs_impl(pmx_dbam *b, int64_t cap, int64_t *start, int32_t 
         if (last_pos1) last_pos1[r] = (size_t)r + 1 < runs.size() ? runs[(size_t)r + 1].prev_pos : last;
     }
     return m;
+}
+
+static int64_t dbam_readlen_impl(pmx_dbam *b, uint32_t mapq_min);
+int64_t pmx_dbam_readlen_hist(pmx_dbam *b, uint32_t mapq_min, int64_t cap, int32_t *lengths, uint64_t *counts, uint64_t *first)
+{
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    if (lengths && (cap < 0 || !counts || !first)) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_readlen_hist: null argument or cap < 0");
+    if (!b->rl_valid || b->rl_mapq != mapq_min) {
+        b->rl_valid = false;
+        int64_t rc;
+        try {
+            rc = dbam_readlen_impl(b, mapq_min);
+        } catch (const std::exception &e) {
+            return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_readlen_hist: ") + e.what());
+        }
+        if (rc < 0) return rc;
+    }
+    if (!lengths) return (int64_t)b->rl_hist.size();
+    const int64_t m = std::min<int64_t>(cap, (int64_t)b->rl_hist.size());
+    for (int64_t i = 0; i < m; i++) {
+        lengths[i] = b->rl_hist[(size_t)i].len;
+        counts[i] = b->rl_hist[(size_t)i].count;
+        first[i] = b->rl_hist[(size_t)i].first;
+    }
+    return m;
+}
+static int64_t dbam_readlen_impl(pmx_dbam *b, uint32_t mapq_min)
+{
+    HIPOK(hipSetDevice(b->device));
+    b->rl_hist.clear();
+    for (u64 &x : b->rl_c) x = 0;
+    if (b->npieces > 0) {
+        const u64 np = b->npieces;
+        const u64 N = b->N - b->data_beg;
+        const u8 *D = b->d_out + b->data_beg;
+        if (!b->chain_ready) {          // (its counts are decode's scratch: the next decode walks with its own filter again)
+            WalkArgs W;
+            W.D = D;
+            W.N = N;
+            W.nref = (int)b->ref_names.size();
+            W.mapq_min = 0;
+            W.flag_exclude = 0;
+            W.want_ref = -1;
+            W.o_ref = W.o_pos = W.o_len = nullptr;
+            W.o_rev = nullptr;
+            if (int rc = walk_chain(b, W)) return rc;
+        }
+        const size_t nb = 2u * RL_SHORT + RL_NCNT + 1u;
+        if (!b->d_rl) HIPOK(hipMalloc((void **)&b->d_rl, 8 * nb));
+        HIPOK(hipMemsetAsync(b->d_rl, 0, 8 * RL_SHORT, b->stream));
+        HIPOK(hipMemsetAsync(b->d_rl + RL_SHORT, 0xff, 8 * RL_SHORT, b->stream));
+        HIPOK(hipMemsetAsync(b->d_rl + 2u * RL_SHORT, 0, 8 * RL_NCNT, b->stream));
+        HIPOK(hipMemsetAsync(b->d_rl + 2u * RL_SHORT + RL_NCNT, 0xff, 8, b->stream));
+        RlArgs A;
+        A.D = D;
+        A.N = N;
+        A.base = b->data_beg;
+        A.nref = (int)b->ref_names.size();
+        A.mapq_min = mapq_min;
+        A.npieces = np;
+        A.spec = b->d_spec;
+        A.bins = b->d_rl;
+        A.hkey = nullptr;
+        A.hcnt = A.hfirst = nullptr;
+        A.hmask = 0;
+        const dim3 wg((unsigned)((np + 255) / 256));
+        hipLaunchKernelGGL(k_bam_readlen<0>, wg, dim3(256), 0, b->stream, A);
+        HIPOK(hipGetLastError());
+        std::vector<unsigned long long> h(nb);
+        HIPOK(hipMemcpyAsync(h.data(), b->d_rl, 8 * nb, hipMemcpyDeviceToHost, b->stream));
+        HIPOK(hipStreamSynchronize(b->stream));
+        if (h[nb - 1] != ~0ull) return record_error(h[nb - 1]);
+        for (u32 i = 0; i < RL_SHORT; i++)
+            if (h[i]) b->rl_hist.push_back({(int32_t)i, (u64)h[i], (u64)h[RL_SHORT + i]});
+        for (u32 k = 0; k < 6; k++) b->rl_c[k] = h[2u * RL_SHORT + k];
+        const u64 nlong = h[2u * RL_SHORT + 6u];
+        if (nlong) {                    // pass 1: the lengths >= RL_SHORT, into a table of >= 2 slots per flush of pass 0
+            u64 slots = 2;
+            while (slots < 2u * nlong) slots <<= 1;
+            if (slots > (1ull << 31)) return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_readlen_hist: too many distinct long lengths");
+            u32 *d_key = nullptr;
+            unsigned long long *d_cf = nullptr;
+            hipError_t e = hipMalloc((void **)&d_key, 4 * slots);
+            if (e == hipSuccess) e = hipMalloc((void **)&d_cf, 16 * slots);
+            if (e == hipSuccess) e = hipMemsetAsync(d_key, 0, 4 * slots, b->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(d_cf, 0, 8 * slots, b->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(d_cf + slots, 0xff, 8 * slots, b->stream);
+            std::vector<u32> key;
+            std::vector<unsigned long long> cf;
+            if (e == hipSuccess) {
+                A.hkey = d_key;
+                A.hcnt = d_cf;
+                A.hfirst = d_cf + slots;
+                A.hmask = (u32)(slots - 1);
+                hipLaunchKernelGGL(k_bam_readlen<1>, wg, dim3(256), 0, b->stream, A);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) {
+                key.resize(slots);
+                cf.resize(2 * slots);
+                e = hipMemcpyAsync(key.data(), d_key, 4 * slots, hipMemcpyDeviceToHost, b->stream);
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(cf.data(), d_cf, 16 * slots, hipMemcpyDeviceToHost, b->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+            if (d_key) (void)hipFree(d_key);
+            if (d_cf) (void)hipFree(d_cf);
+            if (e != hipSuccess) return fail(PMX_DBAM_ERR_DEVICE, std::string("pmx_dbam_readlen_hist: ") + hipGetErrorString(e));
+            const size_t nshort = b->rl_hist.size();
+            for (u64 i = 0; i < slots; i++)
+                if (key[i]) b->rl_hist.push_back({(int32_t)key[i], (u64)cf[i], (u64)cf[slots + i]});
+            std::sort(b->rl_hist.begin() + (std::ptrdiff_t)nshort, b->rl_hist.end(),
+                      [](const pmx_dbam::LenBin &x, const pmx_dbam::LenBin &y) { return x.len < y.len; });
+        }
+    }
+    b->rl_mapq = mapq_min;
+    b->rl_valid = true;
+    return (int64_t)b->rl_hist.size();
+}
+
+int pmx_dbam_readlen_counters(const pmx_dbam *b, uint64_t c[6])
+{
+    if (!b || !c) return fail(PMX_DBAM_ERR_INVALID, "null argument");
+    if (!b->rl_valid) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_readlen_counters: no pmx_dbam_readlen_hist yet");
+    for (int k = 0; k < 6; k++) c[k] = b->rl_c[k];
+    return 0;
 }
 
 int pmx_dbam_counters(const pmx_dbam *b, uint64_t *records, uint64_t *kept, uint64_t *bytes_out, uint64_t *bytes_in,

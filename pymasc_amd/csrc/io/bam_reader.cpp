@@ -30,6 +30,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -124,6 +125,16 @@ struct pmx_bam {
     uint64_t data_beg = 0;          // virtual offset of the first alignment record (rewind target)
     bool pristine = true;           // nothing read since open: a rewind has nothing to do
     std::atomic<uint64_t> n_records{0}, n_kept{0}, bytes_out{0}, bytes_in{0};
+    size_t hdr_len = 0;             // bytes of the BAM header at the front of the uncompressed stream
+    // read-length histogram of the last pmx_bam_readlen_hist (length, count, first key), sorted by length, and its counters
+    struct LenBin {
+        int32_t len;
+        uint64_t count, first;
+    };
+    std::vector<LenBin> rl_hist;
+    uint64_t rl_counters[6] = {0, 0, 0, 0, 0, 0};
+    bool rl_valid = false;
+    uint32_t rl_mapq = 0;
     double t_scan = 0, t_alloc = 0, t_inflate = 0, t_walk = 0, t_decode = 0, t_concat = 0;   // PMX_IO_TIMING=1
 };
 
@@ -436,6 +447,7 @@ void parse_header(pmx_bam &b)
         b.ref_lens.push_back((int64_t)le32(b.buf.data() + p + 4 + l_name));
         p += 4 + (size_t)l_name + 4;
     }
+    b.hdr_len = p;
     for (const auto &blk : loaded)
         if (blk.second <= p) b.data_beg = ((uint64_t)blk.first << 16) | (uint64_t)(p - blk.second);
     // what follows the header stays in buf as the carry of the first record window
@@ -443,6 +455,133 @@ void parse_header(pmx_bam &b)
     if (rest) memmove(b.buf.data(), b.buf.data() + p, rest);
     b.buf.resize(rest);
     b.carry = rest;
+}
+
+// ---- read-length histogram with the estimator's filter (PyMaSC core/readlen.pyx:estimate_readlen) ----------------
+struct LenAcc {
+    uint64_t count, first;
+};
+struct ReadlenPart {
+    std::unordered_map<int32_t, LenAcc> h;
+    uint64_t c[6] = {0, 0, 0, 0, 0, 0};   // nreads, nunmapped, ncounted, npaired, nread2, nnoqlen
+};
+
+// records [lo, hi) of rec_off (offsets into buf, whose first byte is at `base` of the uncompressed stream)
+void readlen_range(const pmx_bam &b, const uint8_t *buf, const std::vector<size_t> &rec_off, uint64_t base, uint32_t mapq_min,
+                   size_t lo, size_t hi, ReadlenPart &out)
+{
+    const int32_t nref = (int32_t)b.ref_names.size();
+    int32_t last_q = -1;
+    LenAcc *last = nullptr;
+    for (size_t i = lo; i < hi; i++) {
+        const uint8_t *rec = buf + rec_off[i] + 4;
+        const uint32_t rec_len = le32(rec - 4);
+        const int32_t ref = le32s(rec);
+        const uint32_t l_name = rec[8], mapq = rec[9];
+        const uint32_t n_cig = le16(rec + 12), flag = le16(rec + 14);
+        const uint32_t l_seq = le32(rec + 16);
+        if (32 + (size_t)l_name + 4 * (size_t)n_cig > rec_len)
+            throw pmx_io::Error(PMX_IO_ERR_FORMAT, "BAM record shorter than its name and CIGAR");
+        if (ref >= nref) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "BAM record refers to an unknown reference id");
+        if (ref < 0) continue;                                    // reference_name is None: not even counted (readlen.pyx)
+        out.c[0]++;
+        if (flag & 0x1u) {
+            out.c[3]++;
+            if (flag & PMX_BAM_FLAG_READ2) out.c[4]++;
+        }
+        if (flag & PMX_BAM_FLAG_UNMAPPED) {
+            out.c[1]++;
+            continue;
+        }
+        if ((flag & PMX_BAM_FLAG_DUPLICATE) || mapq < mapq_min) continue;
+        const uint8_t *cig = rec + 32 + l_name;
+        uint32_t n = n_cig;
+        long_cigar(rec, rec_len, l_name, n_cig, l_seq, cig, n);
+        const uint32_t q = query_length(cig, n);
+        if (q == 0 || q > 0x7fffffffu) {                          // infer_query_length() is None: kept apart
+            out.c[5]++;
+            continue;
+        }
+        out.c[2]++;
+        const uint64_t key = base + rec_off[i];
+        if ((int32_t)q != last_q) {
+            auto it = out.h.emplace((int32_t)q, LenAcc{0, key}).first;   // (node-based: the pointer survives a rehash)
+            last = &it->second;
+            last_q = (int32_t)q;
+        }
+        last->count++;
+        if (key < last->first) last->first = key;
+    }
+}
+
+// One pass over the whole file with buffers of its own: the state of a pmx_bam_next_batch iteration is not touched.
+void readlen_pass(pmx_bam &b, uint32_t mapq_min)
+{
+    RawBuf buf;
+    std::vector<Block> blocks;
+    std::vector<size_t> rec_off;
+    std::unordered_map<int32_t, LenAcc> hist;
+    uint64_t c[6] = {0, 0, 0, 0, 0, 0};
+    size_t off = 0, carry = 0, skip = b.hdr_len;
+    uint64_t base = 0;                                            // stream offset of buf[0]
+    for (bool eof = false; !eof;) {
+        blocks.clear();
+        size_t out = carry;
+        while (blocks.size() < WINDOW_BLOCKS) {
+            Block blk;
+            size_t next;
+            if (!scan_block(b, off, blk, next)) {
+                eof = true;
+                break;
+            }
+            blk.out_off = out;
+            out += blk.isize;
+            off = next;
+            blocks.push_back(blk);
+        }
+        buf.resize(out);
+        uint8_t *dst = buf.data();
+        parallel_for(b.nthreads, blocks.size(), 16, [&](size_t lo, size_t hi, size_t) {
+            for (size_t i = lo; i < hi; i++) inflate_block(blocks[i], dst + blocks[i].out_off);
+        });
+        size_t p = skip < out ? skip : out;                       // the header (it may span windows)
+        skip -= p;
+        rec_off.clear();
+        while (p + 4 <= out) {
+            const uint32_t bs = le32(dst + p);
+            if (bs < 32) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "BAM record with block_size < 32");
+            if (p + 4 + (size_t)bs > out) break;
+            rec_off.push_back(p);
+            p += 4 + (size_t)bs;
+        }
+        const size_t grain = 1 << 16;
+        std::vector<ReadlenPart> parts((rec_off.size() + grain - 1) / grain);
+        parallel_for(b.nthreads, rec_off.size(), grain, [&](size_t lo, size_t hi, size_t k) {
+            readlen_range(b, dst, rec_off, base, mapq_min, lo, hi, parts[k]);
+        });
+        for (const ReadlenPart &part : parts) {
+            for (int k = 0; k < 6; k++) c[k] += part.c[k];
+            for (const auto &kv : part.h) {
+                auto it = hist.emplace(kv.first, kv.second);
+                if (!it.second) {
+                    it.first->second.count += kv.second.count;
+                    if (kv.second.first < it.first->second.first) it.first->second.first = kv.second.first;
+                }
+            }
+        }
+        carry = out - p;
+        if (eof && carry) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "file ends inside an alignment record");
+        if (carry) memmove(dst, dst + p, carry);
+        buf.resize(carry);
+        base += p;
+    }
+    b.rl_hist.clear();
+    b.rl_hist.reserve(hist.size());
+    for (const auto &kv : hist) b.rl_hist.push_back({kv.first, kv.second.count, kv.second.first});
+    std::sort(b.rl_hist.begin(), b.rl_hist.end(), [](const pmx_bam::LenBin &x, const pmx_bam::LenBin &y) { return x.len < y.len; });
+    memcpy(b.rl_counters, c, sizeof c);
+    b.rl_mapq = mapq_min;
+    b.rl_valid = true;
 }
 
 }  // namespace
@@ -666,6 +805,39 @@ int pmx_bam_counters(const pmx_bam *b, uint64_t *records, uint64_t *kept, uint64
     if (kept) *kept = b->n_kept.load();
     if (bytes_out) *bytes_out = b->bytes_out.load();
     if (bytes_in) *bytes_in = b->bytes_in.load();
+    return PMX_IO_OK;
+}
+
+int64_t pmx_bam_readlen_hist(pmx_bam *b, uint32_t mapq_min, int64_t cap, int32_t *lengths, uint64_t *counts, uint64_t *first)
+{
+    if (!b) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bam_readlen_hist: NULL handle");
+    if (lengths && (cap < 0 || !counts || !first))
+        return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bam_readlen_hist: NULL argument or cap < 0");
+    if (!b->rl_valid || b->rl_mapq != mapq_min) {
+        b->rl_valid = false;
+        try {
+            readlen_pass(*b, mapq_min);
+        } catch (const pmx_io::Error &e) {
+            return pmx_io::fail(e.code, e.msg);
+        } catch (const std::exception &e) {
+            return pmx_io::fail(PMX_IO_ERR_OPEN, std::string("pmx_bam_readlen_hist: ") + e.what());
+        }
+    }
+    if (!lengths) return (int64_t)b->rl_hist.size();
+    const int64_t m = std::min<int64_t>(cap, (int64_t)b->rl_hist.size());
+    for (int64_t i = 0; i < m; i++) {
+        lengths[i] = b->rl_hist[(size_t)i].len;
+        counts[i] = b->rl_hist[(size_t)i].count;
+        first[i] = b->rl_hist[(size_t)i].first;
+    }
+    return m;
+}
+
+int pmx_bam_readlen_counters(const pmx_bam *b, uint64_t c[6])
+{
+    if (!b || !c) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bam_readlen_counters: NULL argument");
+    if (!b->rl_valid) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bam_readlen_counters: no pmx_bam_readlen_hist yet");
+    memcpy(c, b->rl_counters, sizeof b->rl_counters);
     return PMX_IO_OK;
 }
 

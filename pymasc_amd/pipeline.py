@@ -3,7 +3,8 @@
 What `pymasc sample.bam -m track.bw -d MAX_SHIFT -q MAPQ -r READ_LEN -o OUTDIR` does between argument parsing and the
 statistics / plots (PyMaSC/pymasc.py:90-160, handler/calc.py:100-161): open the BAM, open the mappability track,
 load or compute the mappable-length cache, run the calculator over the reads, write the `_cc` / `_mscc` / `_nreads`
-tables.  No CLI, no read-length estimation, no statistics: those stay the reference's.
+tables.  Without READ_LEN the read length is estimated from the BAM file first (pymasc.py:187-227, handler/calc.py:74-98;
+pymasc_amd.readlen).  No CLI, no statistics: those stay the reference's.
 Under `torch.distributed` (one process per GPU) the chromosomes are sharded over the ranks and rank 0 writes.
 """
 from __future__ import annotations
@@ -17,19 +18,78 @@ from .mappability import MappabilityStats
 from .sharding import run_sharded
 
 
-def run(bam_path, outdir, max_shift: int, read_len: int, mapq_criteria: int = 1, mappability_path=None,
+def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_criteria: int = 1, mappability_path=None,
         mappability_stats_path=None, skip_ncc: bool = False, references: Optional[Sequence[str]] = None,
         device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
-        device_ingest: Optional[bool] = None):
+        device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN"):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
-    when there is one rank on a real GPU)."""
+    when there is one rank on a real GPU).  ``read_len`` None: estimated from the BAM file with ``readlen_estimator``
+    (MEAN / MEDIAN / MODE / MIN / MAX) at ``mapq_criteria``, as ``pymasc`` does without -r; longer than ``max_shift`` is a
+    ValueError (handler/calc.py:93-98)."""
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
+    world = dist.get_world_size(group) if on else 1
     if device is None:
         device = int(os.environ.get("LOCAL_RANK", "0")) if on else 0
+    bam = None                      # a reader opened here for the estimate and handed on: the file is inflated once per run
+    try:
+        if read_len is None:
+            read_len, bam = _estimate_read_len(bam_path, max_shift, mapq_criteria, readlen_estimator, device, group,
+                                               context, device_ingest, rank, world)
+        return _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path,
+                    skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank)
+    finally:
+        if bam is not None:
+            bam.close()
+
+
+def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, group, context, device_ingest, rank, world):
+    """(read length, the DeviceBamReader it was estimated on or None).  One rank: on the device reader that the run then
+    feeds from when the BAM file goes through the GPU, on the host reader otherwise.  Several ranks: rank 0 estimates on the
+    host reader and broadcasts the value or its error; every rank raises on an error, none waits."""
+    import torch.distributed as dist
+    from . import readlen
+    from .sharding import _collective_device_setup, default_device_ingest
+    readlen._check_esttype(esttype)                     # (every rank: a wrong name fails before any collective)
+    if world == 1:
+        if device_ingest is None:
+            device_ingest = default_device_ingest(world, context)
+        if device_ingest:
+            from .bam_device import DeviceBamReader
+            bam = DeviceBamReader(bam_path, device=(context.device if context is not None else device))
+            try:
+                return readlen.estimate_from_reader(bam, esttype, mapq_criteria, max_shift), bam
+            except BaseException:
+                bam.close()
+                raise
+        from .bam import BamReader
+        with BamReader(bam_path, index=False) as b:
+            return readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift), None
+    _collective_device_setup(device, group)
+    box = [None, None]              # [read length, error]
+    err = None
+    if rank == 0:
+        try:
+            from .bam import BamReader
+            with BamReader(bam_path, index=False) as b:
+                box[0] = readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift)
+        except Exception as e:      # every rank must learn about it (no hang below)
+            err = e
+            box[1] = "{}: {}".format(type(e).__name__, e)
+    dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    if err is not None:
+        raise err                   # rank 0 re-raises its own exception (type kept)
+    if box[1] is not None:
+        raise RuntimeError("read length estimation failed on rank 0 [{}]".format(box[1]))
+    return int(box[0]), None
+
+
+def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path, skip_ncc,
+         references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank):
+    import torch.distributed as dist
 
     # The mappable-length cache (handler/mappability.py:239-309): loaded when valid; otherwise computed ONCE, on rank 0,
     # written atomically, and broadcast -- the other ranks neither recompute it per chromosome nor read a file that is
@@ -65,7 +125,7 @@ def run(bam_path, outdir, max_shift: int, read_len: int, mapq_criteria: int = 1,
         known = box[0]
     result = run_sharded(bam_path, max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
                          references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
-                         group=group, context=context, device_ingest=device_ingest)
+                         group=group, context=context, device_ingest=device_ingest, bam=bam)
     written: List[Path] = []
     if rank == 0:
         out = Path(outdir)

@@ -129,8 +129,18 @@ class EmptyBothChromResult(EmptyResult, BothChromResult):
                    mappable_chrom=EmptyMSCCResult.create_empty(genome_length, max_shift, read_len))
 
 
+class _RunReadLen:
+    @property
+    def read_len(self) -> Optional[int]:
+        """The read length the run was calculated with (given, or estimated by pipeline.run): that of its chromosomes."""
+        for rows in (self.chroms, getattr(self, "mappable_chroms", {})):
+            for r in rows.values():
+                return r.read_len
+        return None
+
+
 @dataclass
-class NCCGenomeWideResult:
+class NCCGenomeWideResult(_RunReadLen):
     genomelen: int
     forward_read_len_sum: int
     reverse_read_len_sum: int
@@ -140,7 +150,7 @@ class NCCGenomeWideResult:
 
 
 @dataclass
-class MSCCGenomeWideResult:
+class MSCCGenomeWideResult(_RunReadLen):
     genomelen: int
     forward_read_len_sum: int
     reverse_read_len_sum: int
@@ -148,7 +158,7 @@ class MSCCGenomeWideResult:
 
 
 @dataclass
-class BothGenomeWideResult:
+class BothGenomeWideResult(_RunReadLen):
     genomelen: int
     forward_read_len_sum: int
     reverse_read_len_sum: int

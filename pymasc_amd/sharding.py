@@ -177,9 +177,16 @@ def reconcile_chromosome_sizes(bam_sizes: Dict[str, int], external_sizes: Dict[s
     return out
 
 
+def default_device_ingest(world: int, context=None) -> bool:
+    """The default of ``device_ingest``: the BAM file is inflated and decoded on the GPU when this is the only rank and it runs
+    on a real GPU."""
+    from . import ffi
+    return world == 1 and (context is None or isinstance(context, ffi.Context)) and ffi.device_count() > 0
+
+
 def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, bigwig_path=None,
                 references: Sequence[str] = None, skip_ncc: bool = False, device: int = None, context=None,
-                chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None):
+                chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None):
     """BAM (+ BigWig) -> genome-wide result on every rank; chromosomes LPT-sharded over the ranks by length.
 
     Launch: one process per GPU under ``torch.distributed`` (torchrun, or pymasc_amd.launch.spawn_ranks), the process
@@ -191,7 +198,10 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     A rank that fails reports through that same all-gather, so every rank raises instead of hanging.
     ``device_ingest``: inflate, walk and filter the BAM file on the GPU and hand the records to the feeders in HBM
     (pymasc_amd.bam_device) -- default: when this is the only rank and it runs on a real GPU; with several
-    ranks each takes its own chromosomes through the host reader and the .bai instead of inflating the whole file N times."""
+    ranks each takes its own chromosomes through the host reader and the .bai instead of inflating the whole file N times.
+    ``bam``: a reader of ``bam_path`` the caller has already opened (pipeline.run opens the DeviceBamReader to estimate the read
+    length on it, so that the file is inflated once per run); it is used instead of opening one and is left open.  A
+    DeviceBamReader implies ``device_ingest``."""
     from .bam import BamReader, feed_bam
     from .bigwig import BigWigReader
     from .calculator import CCHipCalculator
@@ -207,9 +217,11 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     local: Dict[str, object] = {}
     names: List[str] = []
     error = None
-    if device_ingest is None:
-        from . import ffi
-        device_ingest = world == 1 and (context is None or isinstance(context, ffi.Context)) and ffi.device_count() > 0
+    if bam is not None:
+        from .bam_device import DeviceBamReader
+        device_ingest = isinstance(bam, DeviceBamReader)
+    elif device_ingest is None:
+        device_ingest = default_device_ingest(world, context)
     if device_ingest:
         from .bam_device import DeviceBamReader
 
@@ -224,6 +236,12 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
 
         def feed(calc, bam, mine):
             return feed_bam(calc, bam, mapq_criteria, references=mine)
+    if bam is not None:             # the caller's reader: used, not closed
+        import contextlib
+        given = bam
+
+        def open_bam():             # noqa: F811
+            return contextlib.nullcontext(given)
     try:
         with open_bam() as bam:
             names = [n for n in bam.references if references is None or n in set(references)]

@@ -27,7 +27,9 @@ from pymasc_amd.synth import HG38  # noqa: E402
 from tests import io_writers as W  # noqa: E402
 
 
-def synth_bam(path, n_reads, seed=1, readlen=36, chroms=None):
+def synth_bam(path, n_reads, seed=1, readlen=36, chroms=None, cigar_lengths=None):
+    """cigar_lengths(k): query lengths of the next k records' one M operation (default: all readlen; the record layout, sequence
+    and qualities stay those of readlen bases, so the file has the same size and records either way)."""
     rng = np.random.default_rng(seed)
     refs = [(n, l) for n, l in HG38] if chroms is None else [(n, l) for n, l in HG38][:chroms]
     total = sum(l for _, l in refs)
@@ -64,7 +66,7 @@ def synth_bam(path, n_reads, seed=1, readlen=36, chroms=None):
             rec["nref"] = -1
             rec["npos"] = -1
             rec["name"] = b"read0000000"
-            rec["cigar"] = (readlen << 4) | 0
+            rec["cigar"] = ((readlen if cigar_lengths is None else cigar_lengths(k)) << 4) | 0
             rec["seq"] = rng.integers(0, 256, size=(k, (readlen + 1) // 2), dtype=np.uint8)
             rec["qual"] = rng.integers(20, 41, size=(k, readlen), dtype=np.uint8)
             pending += rec.tobytes()
