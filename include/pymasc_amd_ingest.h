@@ -49,6 +49,22 @@ int pmx_dbam_version(void);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out);
 void pmx_dbam_close(pmx_dbam *b);
 
+/* Indexed reading (version >= 2): only the chromosomes a caller chooses are read, copied and inflated.
+ * pmx_dbam_open_indexed reads, copies and inflates only the BGZF members that hold the BAM header (from offset 0 until the
+ * parsed header is complete) and loads the .bai index (bai_path, or NULL: <path>.bai, then <stem>.bai), checked against the
+ * header.  nref / ref_name / ref_len / header_text work as after pmx_dbam_open; pmx_dbam_decode finds no records until
+ * pmx_dbam_select.  A missing or truncated index, a bad magic or another number of references: PMX_DBAM_ERR_FORMAT. */
+int pmx_dbam_open_indexed(const char *path, const char *bai_path, int device, int nthreads, pmx_dbam **out);
+/* Reads, copies and inflates only the members that hold the records of refs[0..n) (their [beg, end) virtual offsets from the
+ * index, SAM spec 5.2: the pseudo-bin 37450 when present, else min / max over the chunks of all bins -- the rule of
+ * pmx_bam_index_load); afterwards the handle behaves like a pmx_dbam_open handle of a file that holds the header and just those
+ * records, in file order (decode, fetch, runs, readlen_hist, inflated: over that stream).  May be called again with another
+ * set: the stream is replaced.  A reference id out of range: PMX_DBAM_ERR_INVALID; a chosen reference without records
+ * contributes nothing.  PMX_DBAM_ERR_FORMAT, and a handle without records, for an offset outside the file or not at a member
+ * start, a range that begins after it ends or inside the header, a range start the verified record chain does not pass through
+ * (stale or shifted index), and a record of a reference that was not chosen. */
+int pmx_dbam_select(pmx_dbam *b, const int32_t *refs, int32_t n);
+
 /* Reference dictionary = pysam's AlignmentFile.references / .lengths (reader/bam.py:137-153). */
 int32_t pmx_dbam_nref(const pmx_dbam *b);
 const char *pmx_dbam_ref_name(const pmx_dbam *b, int32_t i);
@@ -91,7 +107,9 @@ int64_t pmx_dbam_readlen_hist(pmx_dbam *b, uint32_t mapq_min, int64_t cap, int32
 int pmx_dbam_readlen_counters(const pmx_dbam *b, uint64_t c[6]);
 
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
- * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong. */
+ * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong.  An indexed
+ * handle: bytes_out is the length of its stream (header + selected records), bytes_in and members count only the members
+ * that were read (the header's and the selected references', each once). */
 int pmx_dbam_counters(const pmx_dbam *b, uint64_t *records, uint64_t *kept, uint64_t *bytes_out, uint64_t *bytes_in,
                       uint64_t *members, uint64_t *rewalked);
 /* Wall-clock seconds of the phases of open + the last decode: [0] file -> HBM (read + copies + member scan), [1] inflate,

@@ -5,6 +5,7 @@ BAMFileProcessor the calculation touches, PyMaSC/reader/bam.py:84-165) -- ``refe
 ``fetch``, ``close`` -- so ``pymasc_amd.bam.feed_bam`` takes either; the difference is where the work happens: the whole
 file is copied to HBM compressed, and BGZF inflate, CRC32, the record chain and the reference's read filter
 (handler/read.py:62-155) run as HIP kernels.  There is no host fallback: without a GPU ``DeviceBamReader`` raises.
+With ``references`` and a .bai, only the BGZF members of those references are read, copied and inflated.
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ INGEST_EXPORTS = [
     "pmx_dbam_last_error", "pmx_dbam_version", "pmx_dbam_open", "pmx_dbam_close", "pmx_dbam_nref", "pmx_dbam_ref_name",
     "pmx_dbam_ref_len", "pmx_dbam_header_text", "pmx_dbam_decode", "pmx_dbam_device_arrays", "pmx_dbam_fetch",
     "pmx_dbam_runs", "pmx_dbam_counters", "pmx_dbam_timings", "pmx_dbam_inflated", "pmx_dbam_readlen_hist",
-    "pmx_dbam_readlen_counters",
+    "pmx_dbam_readlen_counters", "pmx_dbam_open_indexed", "pmx_dbam_select",
     "pmx_dbw_open", "pmx_dbw_close", "pmx_dbw_nchrom", "pmx_dbw_chrom_name", "pmx_dbw_chrom_len", "pmx_dbw_fetch", "pmx_dbw_device_arrays",
     "pmx_dbw_sorted", "pmx_dbw_copy",
 ]
@@ -50,6 +51,10 @@ def load_ingest_library():
     L.pmx_dbam_version.restype = ctypes.c_int
     L.pmx_dbam_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     L.pmx_dbam_open.restype = ctypes.c_int
+    L.pmx_dbam_open_indexed.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+    L.pmx_dbam_open_indexed.restype = ctypes.c_int
+    L.pmx_dbam_select.argtypes = [vp, ctypes.POINTER(i32), i32]
+    L.pmx_dbam_select.restype = ctypes.c_int
     L.pmx_dbam_close.argtypes = [vp]
     L.pmx_dbam_close.restype = None
     L.pmx_dbam_nref.argtypes = [vp]
@@ -104,24 +109,95 @@ def _raise(code: int):
     raise PmxIOError(int(code), load_ingest_library().pmx_dbam_last_error().decode("utf-8", "replace"))
 
 
-class DeviceBamReader:
-    """A BAM file inflated and decoded on the GPU; batches of filtered read arrays like ``BamReader``."""
+class UnknownReferenceError(ValueError, KeyError):
+    """A reference name the BAM header does not hold (a ValueError; a KeyError too, as ``fetch`` raised before)."""
 
-    def __init__(self, path, device: int = 0, threads: int = 0):
+
+def find_index(path):
+    """``<path>.bai`` or ``<stem>.bai``, as pysam and ``pymasc_amd.bam.BamReader`` look for it; None when neither exists."""
+    path = os.fspath(path)
+    for cand in (path + ".bai", os.path.splitext(path)[0] + ".bai"):
+        if os.path.exists(cand):
+            return cand
+    return None
+
+
+class DeviceBamReader:
+    """A BAM file inflated and decoded on the GPU; batches of filtered read arrays like ``BamReader``.
+
+    ``references``: None reads the whole file (every reference selected).  A list of names with an index present (``index``:
+    its path; None: ``<path>.bai`` / ``<stem>.bai``; False: none) reads only the BGZF members of those references
+    (``pmx_dbam_open_indexed`` + ``pmx_dbam_select``); without an index the whole file is read and the selection is applied to
+    the records.  ``select(names)`` replaces the selection (the two-step use: open with ``references=[]``, read the header,
+    choose).  ``references`` / ``lengths`` always list the whole header; ``selected`` the chosen names in header order."""
+
+    def __init__(self, path, device: int = 0, threads: int = 0, references=None, index=None):
         self._L = load_ingest_library()
         self.path = os.fspath(path)
         self._h = None
+        if references is not None and index is not False:
+            index = find_index(self.path) if index is None else os.fspath(index)
+        else:
+            index = None
+        self.indexed = index is not None
         h = ctypes.c_void_p()
-        rc = self._L.pmx_dbam_open(self.path.encode(), int(device), int(threads), ctypes.byref(h))
+        if self.indexed:
+            rc = self._L.pmx_dbam_open_indexed(self.path.encode(), index.encode(), int(device), int(threads), ctypes.byref(h))
+        else:
+            rc = self._L.pmx_dbam_open(self.path.encode(), int(device), int(threads), ctypes.byref(h))
         if rc:
             _raise(rc)
         self._h = h
         n = self._L.pmx_dbam_nref(h)
         self.references: Tuple[str, ...] = tuple(self._L.pmx_dbam_ref_name(h, i).decode() for i in range(n))
         self.lengths: Tuple[int, ...] = tuple(int(self._L.pmx_dbam_ref_len(h, i)) for i in range(n))
+        self._selected = frozenset(range(n))
+        if references is not None:
+            references = [references] if isinstance(references, str) else list(references)
+            try:
+                if self.indexed and not references:
+                    self._selected = frozenset()     # (the open read the header only: nothing to select yet)
+                else:
+                    self.select(references)
+            except BaseException:
+                self.close()
+                raise
+
+    def _ids(self, names):
+        if isinstance(names, str):
+            names = [names]
+        ids = []
+        for name in names:
+            if name not in self.references:
+                raise UnknownReferenceError(name)
+            ids.append(self.references.index(name))
+        return ids
+
+    def select(self, names) -> None:
+        """Only the records of ``names`` from now on.  An indexed reader reads, copies and inflates just their BGZF members
+        (the stream is replaced; ``counters()`` counts what was read); an unknown name raises ValueError."""
+        if self._h is None:
+            raise ValueError("I/O operation on closed BAM reader")
+        ids = sorted(set(self._ids(names)))
+        if self.indexed:
+            arr = (ctypes.c_int32 * max(len(ids), 1))(*ids)
+            rc = self._L.pmx_dbam_select(self._h, arr, len(ids))
+            if rc:
+                self._selected = frozenset()
+                _raise(rc)
+        self._selected = frozenset(ids)
+
+    @property
+    def selected(self) -> Tuple[str, ...]:
+        return tuple(n for i, n in enumerate(self.references) if i in self._selected)
+
+    def _check_selected(self, names):
+        for i, name in zip(self._ids(names), names):
+            if i not in self._selected:
+                raise ValueError("reference {} was not selected".format(name))
 
     def has_index(self) -> bool:
-        """Every reference can be fetched on its own (the whole stream is resident): no .bai needed."""
+        """Every selected reference can be fetched on its own (its records are resident): no .bai needed for that."""
         return True
 
     @property
@@ -228,7 +304,9 @@ class DeviceBamReader:
         applied by the device feeders).  Falls back to ``pymasc_amd.bam.feed_bam`` (host arrays) for an unsorted file or a
         calculator without the device entry point.  Returns the number of reads fed."""
         from .bam import feed_bam
-        wanted = set(calculator.references if references is None else references)
+        wanted = list(calculator.references if references is None else references)
+        self._check_selected(wanted)
+        wanted = set(wanted)
         if not hasattr(calculator, "feed_reads_device"):
             return feed_bam(calculator, self, mapq_criteria, references, finish, use_index=False)
         self.decode(mapq_criteria)
@@ -264,12 +342,19 @@ class DeviceBamReader:
         """Yields (ref_id, pos_1based, read_len, is_reverse) of the reads that pass the reference's filter
         (handler/read.py:62-90,131-141), in file order, at most ``batch`` per round -- as ``BamReader.batches``."""
         total = self.decode(mapq_criteria, flag_exclude, _reference)
+        keep = None
+        if not self.indexed and len(self._selected) < len(self.references):
+            keep = np.zeros(max(len(self.references), 1), dtype=bool)
+            keep[list(self._selected)] = True
         for first in range(0, total, batch):
-            yield self._fetch(first, min(batch, total - first))
+            ref, pos, rlen, rev = self._fetch(first, min(batch, total - first))
+            if keep is not None:
+                m = keep[ref]
+                ref, pos, rlen, rev = ref[m], pos[m], rlen[m], rev[m]
+            yield ref, pos, rlen, rev
 
     def fetch(self, reference: str, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE,
               batch: int = 1 << 22):
         """The reads of ONE reference (handler/worker.py:106-132: what a worker gets from ``AlignmentFile.fetch(chrom)``)."""
-        if reference not in self.references:
-            raise KeyError(reference)
+        self._check_selected([reference])
         return self.batches(mapq_criteria, flag_exclude, batch, _reference=self.references.index(reference))

@@ -33,6 +33,7 @@
 #include <unistd.h>
 
 #include "../../../include/pymasc_amd_ingest.h"
+#include "../io/bai_index.h"
 
 typedef uint8_t u8;
 typedef uint16_t u16;
@@ -1006,6 +1007,78 @@ __global__ void __launch_bounds__(256) k_ref_runs(const int *__restrict__ ref, c
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Indexed reading (pmx_dbam_select): the members of the chosen references are inflated whole (a member's far matches read
+// its own output in HBM, so the bytes in front of a range's start cannot be skipped), then k_stream_gather copies the header
+// and every segment's slice behind one another: the stream the record chain walks.  One workgroup per tile of <= 64 KB.
+struct GatherTile {
+    u64 src, dst;
+    u32 len, pad;
+};
+#define GATHER_TILE 65536u
+__global__ void __launch_bounds__(256) k_stream_gather(const u8 *__restrict__ src, u8 *__restrict__ dst, const GatherTile *__restrict__ tiles,
+                                                       u32 ntiles)
+{
+    if (blockIdx.x >= ntiles) return;
+    const GatherTile t = tiles[blockIdx.x];
+    const u8 *s = src + t.src;
+    u8 *d = dst + t.dst;
+    for (u32 i = threadIdx.x; i < t.len; i += 256u) d[i] = s[i];
+}
+
+// The proof that the index told the truth, over the verified chain of the gathered stream (D = the stream from its first
+// record on): every slice start (bnd[], sorted, relative to D) must be a position the chain passes through and look like a
+// record, and every record must belong to a chosen reference (ref_ok[ref_id] != 0).  One thread per piece, as k_bam_walk;
+// the first failure is reported as min over (offset << 4 | code).
+enum { SLICE_ERR_START = 5, SLICE_ERR_REF = 6 };
+__global__ void __launch_bounds__(64) k_slice_check(const u8 *__restrict__ D, u64 N, int nref, u64 npieces, const u64 *__restrict__ spec,
+                                                    const u8 *__restrict__ ref_ok, const u64 *__restrict__ bnd, u32 nb,
+                                                    unsigned long long *__restrict__ first_error)
+{
+    const u64 c = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (c >= npieces) return;
+    const u64 cbeg = c * WALK_PIECE, cend = cbeg + WALK_PIECE;
+    u32 lo = 0, hi = nb;   // first boundary >= cbeg
+    while (lo < hi) {
+        const u32 mid = (lo + hi) / 2u;
+        if (bnd[mid] < cbeg) lo = mid + 1u;
+        else hi = mid;
+    }
+    u64 s = spec[c];
+    while (s < cend && s < N) {
+        u32 err = 0, bs = 0;
+        if (s + 4u > N) {
+            err = REC_ERR_EOF;
+        } else {
+            bs = ld32u(D + s);
+            if (bs < 32u) err = REC_ERR_BS;
+            else if (s + 4u + bs > N) err = REC_ERR_EOF;
+        }
+        if (!err && 32ull + D[s + 12] + 4ull * ld16u(D + s + 16) > bs) err = REC_ERR_SHORT;
+        if (err) {
+            atomicMin(first_error, (unsigned long long)((s << 4) | err));
+            return;
+        }
+        if (lo < nb && bnd[lo] < s) break;   // a slice start the chain stepped over
+        if (lo < nb && bnd[lo] == s) {
+            if (!rec_plausible(D, s, N, nref)) {
+                atomicMin(first_error, (unsigned long long)((s << 4) | SLICE_ERR_START));
+                return;
+            }
+            lo++;
+        }
+        const int ref = (int)ld32u(D + s + 4);
+        if (ref < 0 || ref >= nref || !ref_ok[ref]) {
+            atomicMin(first_error, (unsigned long long)((s << 4) | SLICE_ERR_REF));
+            return;
+        }
+        s += 4ull + bs;
+    }
+    // boundaries of this piece the walk did not stop at (it stepped over them, or no record starts in the piece)
+    if (lo < nb && bnd[lo] < cend && bnd[lo] < N) atomicMin(first_error, (unsigned long long)((bnd[lo] << 4) | SLICE_ERR_START));
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 namespace {
@@ -1098,6 +1171,12 @@ struct pmx_dbam {
     u64 rl_c[6] = {0, 0, 0, 0, 0, 0};
     bool rl_valid = false;
     u32 rl_mapq = 0;
+    // indexed reading (pmx_dbam_open_indexed / pmx_dbam_select): the stream holds the header and the selected references only
+    bool indexed = false;
+    std::string path;
+    std::vector<pmx_bai::RefRange> index;
+    u64 hdr_end = 0;                 // file offset behind the last member that holds part of the header
+    u64 bytes_read = 0, members_read = 0;   // compressed bytes and members behind the current stream (counters)
 };
 
 namespace {
@@ -1412,11 +1491,15 @@ int inflate_all(pmx_dbam &b)
     return check_members(b);
 }
 
-int parse_header(pmx_dbam &b)
+// partial: the stream holds only the first members of the file -- returns 1 when the header runs past them (read more)
+int parse_header(pmx_dbam &b, bool partial = false)
 {
     std::vector<u8> h;
+    b.text.clear();
+    b.ref_names.clear();
+    b.ref_lens.clear();
     auto need = [&](u64 upto) -> int {
-        if (upto > b.N) return fail(PMX_DBAM_ERR_FORMAT, "file ends inside the BAM header");
+        if (upto > b.N) return partial ? 1 : fail(PMX_DBAM_ERR_FORMAT, "file ends inside the BAM header");
         if (h.size() >= upto) return 0;
         const u64 want = std::min<u64>(b.N, std::max<u64>(upto, std::max<u64>(1u << 20, 2 * h.size())));
         h.resize(want);
@@ -1461,12 +1544,188 @@ int free_chain(pmx_dbam &b)
     return 0;
 }
 
+// ---- indexed reading: host helpers -----------------------------------------------------------------------------
+struct DevAlloc {   // a device allocation freed on every way out
+    void *p = nullptr;
+    ~DevAlloc()
+    {
+        if (p) (void)hipFree(p);
+    }
+    template <class T> T *as() const { return (T *)p; }
+};
+
+struct FileMember {
+    u64 coff;          // file offset of the member
+    u32 total, hlen;   // bytes of the whole member, of its gzip header (12 + XLEN)
+    u32 isize, crc;
+};
+
+// the BGZF member at p[0, avail) (SAM spec 4.1); nullptr or what is wrong with it
+const char *parse_member(const u8 *p, u64 avail, FileMember &m)
+{
+    if (avail < 18) return "truncated BGZF block header";
+    if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return "not a BGZF block (bad gzip magic / no extra field)";
+    const u32 xlen = h16(p + 10);
+    if (12 + (u64)xlen + 8 > avail) return "truncated BGZF extra field";
+    u32 bsize = 0;
+    bool found = false;
+    for (u32 x = 0; x + 4 <= xlen;) {
+        const u8 *s = p + 12 + x;
+        const u32 slen = h16(s + 2);
+        if (s[0] == 'B' && s[1] == 'C' && slen == 2 && x + 6 <= xlen) {
+            bsize = h16(s + 4);
+            found = true;
+            break;
+        }
+        x += 4 + slen;
+    }
+    if (!found) return "gzip member without the BGZF 'BC' subfield";
+    const u64 total = (u64)bsize + 1;
+    if (total < 12 + (u64)xlen + 8 || total > avail) return "truncated BGZF block";
+    m.total = (u32)total;
+    m.hlen = 12 + xlen;
+    m.crc = h32(p + total - 8);
+    m.isize = h32(p + total - 4);
+    if (m.isize > 65536) return "BGZF block larger than 64 KiB";
+    return nullptr;
+}
+
+// len bytes of the file at off -> dst, on up to nthreads threads (a pread from the page cache is a kernel memcpy)
+bool pread_all(int fd, u8 *dst, u64 off, u64 len, int nthreads)
+{
+    const int T = (int)std::max<u64>(1, std::min<u64>((u64)nthreads, len >> 20));
+    std::vector<int> bad((size_t)T, 0);
+    auto part = [&](int ti) {
+        const u64 lo = len * (u64)ti / (u64)T, hi = len * (u64)(ti + 1) / (u64)T;
+        for (u64 done = lo; done < hi;) {
+            const ssize_t r = pread(fd, dst + done, (size_t)(hi - done), (off_t)(off + done));
+            if (r <= 0) {
+                bad[(size_t)ti] = 1;
+                return;
+            }
+            done += (u64)r;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int ti = 1; ti < T; ti++) th.emplace_back(part, ti);
+    part(0);
+    for (auto &x : th) x.join();
+    for (int v : bad)
+        if (v) return false;
+    return true;
+}
+
+struct OpenFile {
+    int fd = -1;
+    u64 size = 0;
+    ~OpenFile()
+    {
+        if (fd >= 0) close(fd);
+    }
+};
+int open_file(const std::string &path, OpenFile &f)
+{
+    f.fd = open(path.c_str(), O_RDONLY);
+    if (f.fd < 0) return fail(PMX_DBAM_ERR_OPEN, "cannot open " + path);
+    struct stat st;
+    if (fstat(f.fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(PMX_DBAM_ERR_OPEN, "not a regular file: " + path);
+    f.size = (u64)st.st_size;
+    return 0;
+}
+
+// The members lying whole in the file ranges runs[] (disjoint, ascending, each starting at a member): read, hopped over,
+// copied to HBM and inflated + CRC-checked there.  out: the members in file order, *d_out their outputs back to back
+// (sum of ISIZE + padding), *N that sum.  stop_short: the last range may end inside a member (the header's prefix reads):
+// its members up to the last whole one are taken.
+int read_inflate_runs(pmx_dbam &b, const OpenFile &f, const std::vector<std::pair<u64, u64>> &runs, int nthreads, bool stop_short,
+                      std::vector<FileMember> &out, DevAlloc &d_out, u64 &N)
+{
+    u64 total = 0;
+    for (const auto &r : runs) total += r.second - r.first;
+    std::vector<u8> host((size_t)total);
+    std::vector<DMember> dm;
+    out.clear();
+    u64 at = 0, out_off = 0;
+    double t0 = now_s();
+    for (const auto &r : runs) {
+        const u64 len = r.second - r.first;
+        if (!pread_all(f.fd, host.data() + at, r.first, len, nthreads)) return fail(PMX_DBAM_ERR_OPEN, "read error on " + b.path);
+        for (u64 p = 0; p < len;) {
+            FileMember m;
+            m.coff = r.first + p;
+            if (const char *err = parse_member(host.data() + at + p, len - p, m)) {
+                if (stop_short && &r == &runs.back() && !dm.empty()) break;
+                char where[64];
+                snprintf(where, sizeof where, " (file offset %llu)", (unsigned long long)m.coff);
+                return fail(PMX_DBAM_ERR_FORMAT, std::string(err) + where);
+            }
+            DMember d;
+            d.in_off = at + p + m.hlen;
+            d.clen = m.total - m.hlen - 8;
+            d.isize = m.isize;
+            d.crc = m.crc;
+            d.out_off = out_off;
+            d.open_size = 0;
+            out_off += m.isize;
+            dm.push_back(d);
+            out.push_back(m);
+            p += m.total;
+        }
+        at += len;
+    }
+    N = out_off;
+    const u32 n = (u32)dm.size();
+    DevAlloc d_in, d_mem, d_status;
+    HIPOK(hipMalloc(&d_in.p, total + IN_PAD));
+    HIPOK(hipMalloc(&d_out.p, N + IN_PAD));   // (the CRC kernel reads whole 16-byte groups)
+    HIPOK(hipMemsetAsync(d_in.as<u8>() + total, 0, IN_PAD, b.stream));
+    if (total) HIPOK(hipMemcpyAsync(d_in.p, host.data(), total, hipMemcpyHostToDevice, b.stream));
+    HIPOK(hipStreamSynchronize(b.stream));
+    b.t[0] += now_s() - t0;
+    if (!n) return 0;
+    HIPOK(hipMalloc(&d_mem.p, sizeof(DMember) * n));
+    HIPOK(hipMalloc(&d_status.p, sizeof(u32) * n));
+    HIPOK(hipMemcpyAsync(d_mem.p, dm.data(), sizeof(DMember) * n, hipMemcpyHostToDevice, b.stream));
+    HIPOK(hipMemsetAsync(d_status.p, 0, sizeof(u32) * n, b.stream));
+    t0 = now_s();
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3(n), dim3(64), 0, b.stream, d_in.as<u8>(), d_out.as<u8>(), d_mem.as<DMember>(), n,
+                       d_status.as<u32>(), (u32 *)nullptr);
+    HIPOK(hipGetLastError());
+    HIPOK(hipStreamSynchronize(b.stream));
+    const double t1 = now_s();
+    b.t[1] += t1 - t0;
+    hipLaunchKernelGGL(k_bgzf_crc, dim3((n + 3) / 4), dim3(256), 0, b.stream, d_out.as<u8>(), d_mem.as<DMember>(), n, d_status.as<u32>());
+    HIPOK(hipGetLastError());
+    std::vector<u32> status(n);
+    HIPOK(hipMemcpyAsync(status.data(), d_status.p, sizeof(u32) * n, hipMemcpyDeviceToHost, b.stream));
+    HIPOK(hipStreamSynchronize(b.stream));
+    b.t[2] += now_s() - t1;
+    for (u32 i = 0; i < n; i++)
+        if (status[i]) {
+            char where[96];
+            snprintf(where, sizeof where, " (member at file offset %llu)", (unsigned long long)out[i].coff);
+            return fail(PMX_DBAM_ERR_FORMAT, std::string(inf_err_text(status[i])) + where);
+        }
+    return 0;
+}
+
+// The stream of an indexed handle back to "header only": no records until the next pmx_dbam_select
+void reset_stream(pmx_dbam &b)
+{
+    free_chain(b);
+    b.chain_ready = false;
+    b.rl_valid = false;
+    b.n_kept = b.n_records = b.n_rewalked = 0;
+    b.N = b.data_beg;
+    b.npieces = 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 1; }
+int pmx_dbam_version(void) { return 2; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1899,8 +2158,8 @@ int pmx_dbam_counters(const pmx_dbam *b, uint64_t *records, uint64_t *kept, uint
     if (records) *records = b->n_records;
     if (kept) *kept = b->n_kept;
     if (bytes_out) *bytes_out = b->N;
-    if (bytes_in) *bytes_in = b->fsize;
-    if (members) *members = b->members.size();
+    if (bytes_in) *bytes_in = b->indexed ? b->bytes_read : b->fsize;
+    if (members) *members = b->indexed ? b->members_read : b->members.size();
     if (rewalked) *rewalked = b->n_rewalked;
     return 0;
 }
@@ -1919,6 +2178,287 @@ int pmx_dbam_inflated(pmx_dbam *b, uint64_t first, uint64_t n, uint8_t *dst)
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipMemcpy(dst, b->d_out + first, n, hipMemcpyDeviceToHost));
     return 0;
+}
+
+static int dbam_open_indexed_impl(const char *path, const char *bai_path, int device, int nthreads, pmx_dbam **out);
+int pmx_dbam_open_indexed(const char *path, const char *bai_path, int device, int nthreads, pmx_dbam **out)
+{
+    try {
+        return dbam_open_indexed_impl(path, bai_path, device, nthreads, out);
+    } catch (const std::exception &e) {
+        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_open_indexed: ") + e.what());
+    }
+}
+// The header: members from offset 0, read in prefixes of growing length and inflated on the device until the parsed header is
+// complete; then the index, checked against it.
+static int open_indexed_body(pmx_dbam *b, const char *bai_path, int nthreads)
+{
+    OpenFile f;
+    if (int rc = open_file(b->path, f)) return rc;
+    b->fsize = f.size;
+    if (b->fsize < 28) return fail(PMX_DBAM_ERR_FORMAT, "truncated BGZF block header");
+    std::vector<FileMember> mem;
+    for (u64 L = std::min<u64>(b->fsize, 1u << 18);; L = std::min<u64>(b->fsize, 2 * L)) {
+        DevAlloc d;
+        u64 N = 0;
+        if (int rc = read_inflate_runs(*b, f, {{0, L}}, nthreads, L < b->fsize, mem, d, N)) return rc;
+        if (b->d_out) HIPOK(hipFree(b->d_out));
+        b->d_out = d.as<u8>();
+        d.p = nullptr;
+        b->N = N;
+        const double t0 = now_s();
+        const int rc = parse_header(*b, true);
+        b->t[3] += now_s() - t0;
+        if (rc < 0) return rc;
+        if (rc == 0) break;
+        if (L == b->fsize) return fail(PMX_DBAM_ERR_FORMAT, "file ends inside the BAM header");
+    }
+    // the members that hold a part of the header (the last one usually holds the first records too)
+    u64 o = 0;
+    b->bytes_read = b->members_read = 0;
+    for (const FileMember &m : mem) {
+        if (o >= b->data_beg) break;
+        o += m.isize;
+        b->hdr_end = m.coff + m.total;
+        b->bytes_read += m.total;
+        b->members_read++;
+    }
+    // the index: bai_path, else <path>.bai, else <stem>.bai (as pysam and pymasc_amd.bam.BamReader look for it)
+    std::vector<std::string> cands;
+    if (bai_path) {
+        cands.push_back(bai_path);
+    } else {
+        cands.push_back(b->path + ".bai");
+        const size_t slash = b->path.find_last_of('/'), dot = b->path.find_last_of('.');
+        if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) cands.push_back(b->path.substr(0, dot) + ".bai");
+    }
+    std::string ipath;
+    for (const std::string &c : cands)
+        if (access(c.c_str(), R_OK) == 0) {
+            ipath = c;
+            break;
+        }
+    if (ipath.empty()) return fail(PMX_DBAM_ERR_FORMAT, "no BAM index: " + cands[0] + " not found");
+    OpenFile fi;
+    if (open_file(ipath, fi)) return fail(PMX_DBAM_ERR_FORMAT, ipath + ": cannot read the BAM index");
+    std::vector<u8> raw((size_t)fi.size);
+    if (fi.size && !pread_all(fi.fd, raw.data(), 0, fi.size, 1)) return fail(PMX_DBAM_ERR_FORMAT, ipath + ": cannot read the BAM index");
+    std::string err;
+    if (!pmx_bai::parse(raw.data(), raw.size(), b->ref_names.size(), b->index, err)) return fail(PMX_DBAM_ERR_FORMAT, ipath + ": " + err);
+    reset_stream(*b);
+    return 0;
+}
+static int dbam_open_indexed_impl(const char *path, const char *bai_path, int device, int nthreads, pmx_dbam **out)
+{
+    if (!path || !out) return fail(PMX_DBAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PMX_DBAM_ERR_DEVICE, "no HIP device: the device ingest needs a GPU");
+    if (device < 0 || device >= ndev) return fail(PMX_DBAM_ERR_INVALID, "no such device");
+    HIPOK(hipSetDevice(device));
+    if (nthreads <= 0) nthreads = (int)std::min<unsigned>(16, std::max<unsigned>(1, std::thread::hardware_concurrency()));
+    pmx_dbam *b = new pmx_dbam;
+    b->device = device;
+    b->indexed = true;
+    b->path = path;
+    b->pipelined = false;
+    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete b;
+        return fail(PMX_DBAM_ERR_DEVICE, "hipStreamCreate failed");
+    }
+    const int rc = open_indexed_body(b, bai_path, nthreads);
+    if (rc) {
+        const std::string keep = g_err;
+        pmx_dbam_close(b);
+        g_err = keep;
+        return rc;
+    }
+    *out = b;
+    return 0;
+}
+
+static int dbam_select_impl(pmx_dbam *b, const int32_t *refs, int32_t n);
+int pmx_dbam_select(pmx_dbam *b, const int32_t *refs, int32_t n)
+{
+    try {
+        return dbam_select_impl(b, refs, n);
+    } catch (const std::exception &e) {
+        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_select: ") + e.what());
+    }
+}
+static int select_body(pmx_dbam *b, const std::vector<u8> &chosen);
+static int dbam_select_impl(pmx_dbam *b, const int32_t *refs, int32_t n)
+{
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    if (!b->indexed) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_select: the handle was not opened by pmx_dbam_open_indexed");
+    if (n < 0 || (n > 0 && !refs)) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_select: null argument or n < 0");
+    const int32_t nref = (int32_t)b->ref_names.size();
+    std::vector<u8> chosen((size_t)nref, 0);
+    for (int32_t i = 0; i < n; i++) {
+        if (refs[i] < 0 || refs[i] >= nref) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_select: reference id out of range");
+        chosen[(size_t)refs[i]] = 1;
+    }
+    HIPOK(hipSetDevice(b->device));
+    for (double &x : b->t) x = 0;
+    reset_stream(*b);
+    const int rc = select_body(b, chosen);
+    if (rc) {   // no arrays from a stream that failed a check
+        const std::string keep = g_err;
+        reset_stream(*b);
+        g_err = keep;
+    }
+    return rc;
+}
+static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
+{
+    auto bad = [&](const char *what, size_t r) {
+        return fail(PMX_DBAM_ERR_FORMAT, std::string("BAM index: ") + what + " (reference " + b->ref_names[r] + ")");
+    };
+    // planning: the chosen ranges sorted by their start, merged where they touch into segments
+    struct Seg {
+        u64 beg, end;
+        size_t ref;
+    };
+    std::vector<Seg> segs;
+    for (size_t r = 0; r < chosen.size(); r++) {
+        if (!chosen[r]) continue;
+        const pmx_bai::RefRange &rr = b->index[r];
+        if (rr.beg > rr.end) return bad("range begins after it ends", r);
+        if (rr.has) segs.push_back({rr.beg, rr.end, r});
+    }
+    std::sort(segs.begin(), segs.end(), [](const Seg &x, const Seg &y) { return x.beg < y.beg; });
+    std::vector<Seg> merged;
+    for (const Seg &s : segs) {
+        if (!merged.empty() && s.beg <= merged.back().end) merged.back().end = std::max(merged.back().end, s.end);
+        else merged.push_back(s);
+    }
+    OpenFile f;
+    if (int rc = open_file(b->path, f)) return rc;
+    if (f.size != b->fsize) return fail(PMX_DBAM_ERR_FORMAT, "the BAM file changed since it was opened");
+    // the file ranges to read: the header's members, then per segment [coffset(beg), coffset(end)) and the member at
+    // coffset(end) when the segment ends inside it
+    std::vector<std::pair<u64, u64>> ranges{{0, b->hdr_end}};
+    for (const Seg &s : merged) {
+        const u64 cb = s.beg >> 16, ce = s.end >> 16, ue = s.end & 0xffff;
+        if (cb >= b->fsize || ce > b->fsize || (ce == b->fsize && ue)) return bad("virtual offset outside the file", s.ref);
+        u64 hi = ce;
+        if (ue) {
+            std::vector<u8> head((size_t)std::min<u64>(65536, b->fsize - ce));   // (a member is at most 64 KB)
+            if (!pread_all(f.fd, head.data(), ce, head.size(), 1)) return fail(PMX_DBAM_ERR_OPEN, "read error on " + b->path);
+            FileMember m;
+            if (parse_member(head.data(), head.size(), m)) return bad("virtual offset that is not the start of a BGZF block", s.ref);
+            hi = ce + m.total;
+        }
+        ranges.push_back({cb, hi});
+    }
+    std::sort(ranges.begin(), ranges.end());
+    std::vector<std::pair<u64, u64>> runs;
+    for (const auto &r : ranges) {
+        if (r.first >= r.second) continue;
+        if (!runs.empty() && r.first <= runs.back().second) runs.back().second = std::max(runs.back().second, r.second);
+        else runs.push_back(r);
+    }
+    std::vector<FileMember> mem;
+    DevAlloc d_full;
+    u64 Nfull = 0;
+    {
+        const int nthreads = (int)std::min<unsigned>(16, std::max<unsigned>(1, std::thread::hardware_concurrency()));
+        if (int rc = read_inflate_runs(*b, f, runs, nthreads, false, mem, d_full, Nfull)) return rc;
+    }
+    std::vector<u64> out_off(mem.size());
+    for (size_t i = 0, o = 0; i < mem.size(); o += mem[i].isize, i++) out_off[i] = o;
+    auto find = [&](u64 coff) -> long {
+        const auto it = std::lower_bound(mem.begin(), mem.end(), coff, [](const FileMember &m, u64 c) { return m.coff < c; });
+        return (it != mem.end() && it->coff == coff) ? (long)(it - mem.begin()) : -1;
+    };
+    // the stream: the header, then every segment's slice from uoffset(beg) in its first member to uoffset(end) in its last
+    std::vector<GatherTile> tiles;
+    std::vector<u64> bnd;   // slice starts, relative to the first record
+    u64 dst = 0;
+    auto piece = [&](u64 src, u64 len) {
+        for (u64 k = 0; k < len; k += GATHER_TILE) tiles.push_back({src + k, dst + k, (u32)std::min<u64>(GATHER_TILE, len - k), 0});
+        dst += len;
+    };
+    piece(0, b->data_beg);
+    for (const Seg &s : merged) {
+        const long jb = find(s.beg >> 16);
+        const u64 ub = s.beg & 0xffff, ce = s.end >> 16, ue = s.end & 0xffff;
+        if (jb < 0) return bad("virtual offset that is not the start of a BGZF block", s.ref);
+        if (ub > mem[(size_t)jb].isize) return bad("virtual offset beyond the data of its BGZF block", s.ref);
+        const u64 src_b = out_off[(size_t)jb] + ub;
+        if (src_b < b->data_beg) return bad("range starts inside the BAM header", s.ref);
+        u64 src_e;
+        const long je = find(ce);
+        if (je >= 0) {
+            if (ue > mem[(size_t)je].isize) return bad("virtual offset beyond the data of its BGZF block", s.ref);
+            src_e = out_off[(size_t)je] + ue;
+        } else {
+            const auto it = std::lower_bound(mem.begin(), mem.end(), ce, [](const FileMember &m, u64 c) { return m.coff + m.total < c; });
+            if (ue || it == mem.end() || it->coff + it->total != ce) return bad("virtual offset that is not the start of a BGZF block", s.ref);
+            src_e = out_off[(size_t)(it - mem.begin())] + it->isize;
+        }
+        if (src_e < src_b) return bad("range begins after it ends", s.ref);
+        if (src_e == src_b) continue;
+        bnd.push_back(dst - b->data_beg);
+        piece(src_b, src_e - src_b);
+    }
+    const u64 N = dst;
+    for (const GatherTile &t : tiles)   // (every copy inside both buffers: checked here, not trusted in the kernel)
+        if (t.src + t.len > Nfull || t.dst + t.len > N) return fail(PMX_DBAM_ERR_DEVICE, "pmx_dbam_select: gather plan out of bounds");
+    DevAlloc d_stream, d_tiles;
+    HIPOK(hipMalloc(&d_stream.p, N + IN_PAD));
+    HIPOK(hipMemsetAsync(d_stream.as<u8>() + N, 0, IN_PAD, b->stream));
+    if (!tiles.empty()) {
+        HIPOK(hipMalloc(&d_tiles.p, sizeof(GatherTile) * tiles.size()));
+        HIPOK(hipMemcpyAsync(d_tiles.p, tiles.data(), sizeof(GatherTile) * tiles.size(), hipMemcpyHostToDevice, b->stream));
+        hipLaunchKernelGGL(k_stream_gather, dim3((unsigned)tiles.size()), dim3(256), 0, b->stream, d_full.as<u8>(), d_stream.as<u8>(),
+                           d_tiles.as<GatherTile>(), (u32)tiles.size());
+        HIPOK(hipGetLastError());
+    }
+    HIPOK(hipStreamSynchronize(b->stream));
+    HIPOK(hipFree(d_full.p));   // the whole members are not needed any more
+    d_full.p = nullptr;
+    if (b->d_out) HIPOK(hipFree(b->d_out));
+    b->d_out = d_stream.as<u8>();
+    d_stream.p = nullptr;
+    b->N = N;
+    b->npieces = N > b->data_beg ? (N - b->data_beg + WALK_PIECE - 1) / WALK_PIECE : 0;
+    b->bytes_read = b->members_read = 0;
+    for (const FileMember &m : mem) b->bytes_read += m.total;
+    b->members_read = mem.size();
+    if (!b->npieces) return 0;
+    // the record chain of the stream, and the proof that the index told the truth
+    const double t0 = now_s();
+    WalkArgs W;
+    W.D = b->d_out + b->data_beg;
+    W.N = N - b->data_beg;
+    W.nref = (int)b->ref_names.size();
+    W.mapq_min = 0;
+    W.flag_exclude = 0;
+    W.want_ref = -1;
+    W.o_ref = W.o_pos = W.o_len = nullptr;
+    W.o_rev = nullptr;
+    if (int rc = walk_chain(b, W)) return rc;
+    DevAlloc d_ok, d_bnd, d_fe;
+    HIPOK(hipMalloc(&d_ok.p, chosen.size() + 1));
+    HIPOK(hipMalloc(&d_bnd.p, 8 * bnd.size()));
+    HIPOK(hipMalloc(&d_fe.p, 8));
+    HIPOK(hipMemcpyAsync(d_ok.p, chosen.data(), chosen.size(), hipMemcpyHostToDevice, b->stream));
+    HIPOK(hipMemcpyAsync(d_bnd.p, bnd.data(), 8 * bnd.size(), hipMemcpyHostToDevice, b->stream));
+    HIPOK(hipMemsetAsync(d_fe.p, 0xff, 8, b->stream));
+    hipLaunchKernelGGL(k_slice_check, dim3((unsigned)((b->npieces + 63) / 64)), dim3(64), 0, b->stream, W.D, W.N, W.nref, b->npieces,
+                       b->d_spec, d_ok.as<u8>(), d_bnd.as<u64>(), (u32)bnd.size(), d_fe.as<unsigned long long>());
+    HIPOK(hipGetLastError());
+    unsigned long long fe = 0;
+    HIPOK(hipMemcpyAsync(&fe, d_fe.p, 8, hipMemcpyDeviceToHost, b->stream));
+    HIPOK(hipStreamSynchronize(b->stream));
+    b->t[4] = now_s() - t0;
+    if (fe == ~0ull) return 0;
+    switch (fe & 15ull) {
+    case SLICE_ERR_START: return fail(PMX_DBAM_ERR_FORMAT, "BAM index: a range starts where no alignment record starts (stale or corrupt index)");
+    case SLICE_ERR_REF: return fail(PMX_DBAM_ERR_FORMAT, "BAM index: a range holds records of a reference that was not selected (stale or corrupt index)");
+    default: return record_error(fe);
+    }
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 // image; what they would have returned for the fields used here is fixed by the spec, and the parity test replays
 // the reference's own BAM <-> SAM twin (tests/data/ENCFF000RMB-test.{bam,sam}).
 #include "../../../include/pymasc_amd_io.h"
+#include "bai_index.h"
 #include "io_common.h"
 
 #include <zlib.h>
@@ -112,10 +113,7 @@ struct pmx_bam {
     uint32_t mapq_min = 0, flag_exclude = 0;
 
     // .bai index: per reference the virtual file offsets [beg, end) of its records (SAM spec 5.2)
-    struct RefRange {
-        bool has = false;
-        uint64_t beg = 0, end = 0;
-    };
+    using RefRange = pmx_bai::RefRange;
     std::vector<RefRange> index;
     bool have_index = false;
     // region mode (pmx_bam_fetch_ref): only records of want_ref, blocks up to the one holding the range's end
@@ -690,54 +688,9 @@ int pmx_bam_index_load(pmx_bam *b, const char *bai_path)
         f.open(bai_path);
         const uint8_t *d = f.data;
         const size_t n = f.size;
-        auto need = [&](size_t p, size_t k) {
-            if (p > n || k > n - p) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "truncated BAM index");
-        };
-        need(0, 8);
-        if (memcmp(d, "BAI\1", 4) != 0) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "not a BAM index (bad magic)");
-        const uint32_t n_ref = le32(d + 4);
-        if (n_ref != b->ref_names.size())
-            throw pmx_io::Error(PMX_IO_ERR_FORMAT, "BAM index lists a different number of references than the BAM header");
-        std::vector<pmx_bam::RefRange> idx(n_ref);
-        size_t p = 8;
-        auto le64 = [&](size_t q) { return (uint64_t)le32(d + q) | ((uint64_t)le32(d + q + 4) << 32); };
-        for (uint32_t r = 0; r < n_ref; r++) {
-            need(p, 4);
-            const uint32_t n_bin = le32(d + p);
-            p += 4;
-            uint64_t lo = UINT64_MAX, hi = 0;
-            bool pseudo = false;
-            for (uint32_t k = 0; k < n_bin; k++) {
-                need(p, 8);
-                const uint32_t bin = le32(d + p), n_chunk = le32(d + p + 4);
-                p += 8;
-                need(p, (size_t)n_chunk * 16);
-                if (bin == 37450 && n_chunk >= 1) {          // pseudo-bin: [ref_beg, ref_end) then the read counts
-                    idx[r].beg = le64(p);
-                    idx[r].end = le64(p + 8);
-                    pseudo = true;
-                } else {
-                    for (uint32_t c = 0; c < n_chunk; c++) {
-                        const uint64_t cb = le64(p + 16 * (size_t)c), ce = le64(p + 16 * (size_t)c + 8);
-                        if (cb < lo) lo = cb;
-                        if (ce > hi) hi = ce;
-                    }
-                }
-                p += (size_t)n_chunk * 16;
-            }
-            need(p, 4);
-            const uint32_t n_intv = le32(d + p);
-            p += 4;
-            need(p, (size_t)n_intv * 8);
-            p += (size_t)n_intv * 8;
-            if (pseudo) {
-                idx[r].has = idx[r].end > idx[r].beg;
-            } else if (hi > lo) {
-                idx[r].has = true;
-                idx[r].beg = lo;
-                idx[r].end = hi;
-            }
-        }
+        std::vector<pmx_bai::RefRange> idx;
+        std::string err;
+        if (!pmx_bai::parse(d, n, b->ref_names.size(), idx, err)) throw pmx_io::Error(PMX_IO_ERR_FORMAT, err);
         b->index.swap(idx);
         b->have_index = true;
     } catch (const pmx_io::Error &e) {

@@ -21,13 +21,19 @@ from .sharding import run_sharded
 def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_criteria: int = 1, mappability_path=None,
         mappability_stats_path=None, skip_ncc: bool = False, references: Optional[Sequence[str]] = None,
         device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
-        device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN"):
+        device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
     when there is one rank on a real GPU).  ``read_len`` None: estimated from the BAM file with ``readlen_estimator``
     (MEAN / MEDIAN / MODE / MIN / MAX) at ``mapq_criteria``, as ``pymasc`` does without -r; longer than ``max_shift`` is a
-    ValueError (handler/calc.py:93-98)."""
+    ValueError (handler/calc.py:93-98).  The estimate is taken over the whole file, as PyMaSC takes it, and on one rank it
+    reuses the device reader that then feeds the run: with ``read_len`` None the whole file is opened even when
+    ``references`` or ``chromfilter`` choose some chromosomes; with ``read_len`` given and a .bai present, the device reader
+    reads only the chosen chromosomes' BGZF members (sharding.run_sharded).  ``chromfilter``: PyMaSC's -i / -e filter as
+    ``[(include, [patterns]), ...]`` (pymasc_amd.chromfilter), not together with ``references``."""
+    if references is not None and chromfilter is not None:
+        raise ValueError("give references or chromfilter, not both")
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
@@ -40,7 +46,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
             read_len, bam = _estimate_read_len(bam_path, max_shift, mapq_criteria, readlen_estimator, device, group,
                                                context, device_ingest, rank, world)
         return _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path,
-                    skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank)
+                    skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank,
+                    chromfilter)
     finally:
         if bam is not None:
             bam.close()
@@ -88,7 +95,7 @@ def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, grou
 
 
 def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path, skip_ncc,
-         references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank):
+         references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank, chromfilter=None):
     import torch.distributed as dist
 
     # The mappable-length cache (handler/mappability.py:239-309): loaded when valid; otherwise computed ONCE, on rank 0,
@@ -125,7 +132,7 @@ def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path,
         known = box[0]
     result = run_sharded(bam_path, max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
                          references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
-                         group=group, context=context, device_ingest=device_ingest, bam=bam)
+                         group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter)
     written: List[Path] = []
     if rank == 0:
         out = Path(outdir)

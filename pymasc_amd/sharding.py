@@ -186,7 +186,7 @@ def default_device_ingest(world: int, context=None) -> bool:
 
 def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, bigwig_path=None,
                 references: Sequence[str] = None, skip_ncc: bool = False, device: int = None, context=None,
-                chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None):
+                chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None, chromfilter=None):
     """BAM (+ BigWig) -> genome-wide result on every rank; chromosomes LPT-sharded over the ranks by length.
 
     Launch: one process per GPU under ``torch.distributed`` (torchrun, or pymasc_amd.launch.spawn_ranks), the process
@@ -201,9 +201,16 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     ranks each takes its own chromosomes through the host reader and the .bai instead of inflating the whole file N times.
     ``bam``: a reader of ``bam_path`` the caller has already opened (pipeline.run opens the DeviceBamReader to estimate the read
     length on it, so that the file is inflated once per run); it is used instead of opening one and is left open.  A
-    DeviceBamReader implies ``device_ingest``."""
+    DeviceBamReader implies ``device_ingest``.
+    ``chromfilter``: PyMaSC's -i / -e chromosome filter, an ordered list of ``(include, [patterns])``
+    (pymasc_amd.chromfilter); not together with ``references``.  A filter that leaves nothing raises on every rank.
+    With the device reader and a .bai next to the BAM file, a rank of several -- or the only rank when ``references`` or
+    ``chromfilter`` choose the chromosomes -- reads the header, takes its share and reads, copies and inflates only the BGZF
+    members of that share (DeviceBamReader.select); without an index, or with a ``bam`` given, the path is the
+    whole-file one above."""
     from .bam import BamReader, feed_bam
     from .bigwig import BigWigReader
+    from .chromfilter import filter_references
     from .calculator import CCHipCalculator
     from .result import aggregate_results
 
@@ -222,11 +229,18 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
         device_ingest = isinstance(bam, DeviceBamReader)
     elif device_ingest is None:
         device_ingest = default_device_ingest(world, context)
+    if references is not None and chromfilter is not None:
+        raise ValueError("give references or chromfilter, not both")
+    indexed = False
     if device_ingest:
-        from .bam_device import DeviceBamReader
+        from .bam_device import DeviceBamReader, find_index
+        indexed = (bam is None and (world > 1 or references is not None or chromfilter is not None)
+                   and find_index(bam_path) is not None)
 
         def open_bam():
-            return DeviceBamReader(bam_path, device=(context.device if context is not None else (device or 0)))
+            # indexed: the header only, the rank's share is selected below
+            return DeviceBamReader(bam_path, device=(context.device if context is not None else (device or 0)),
+                                   references=[] if indexed else None)
 
         def feed(calc, bam, mine):
             return bam.feed(calc, mapq_criteria, references=mine)
@@ -244,7 +258,10 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
             return contextlib.nullcontext(given)
     try:
         with open_bam() as bam:
-            names = [n for n in bam.references if references is None or n in set(references)]
+            if chromfilter is not None:
+                names = filter_references(bam.references, chromfilter)
+            else:
+                names = [n for n in bam.references if references is None or n in set(references)]
             lengths = dict(zip(bam.references, bam.lengths))
             if bigwig_path is None:
                 bw = None
@@ -257,6 +274,8 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
                 if bw is not None:      # the track's chromosome sizes win where they are longer (handler/calc.py:100-115)
                     lengths.update(reconcile_chromosome_sizes({n: lengths[n] for n in names}, bw.chromsizes))
                 mine = [names[i] for i in sorted(lpt_assign([lengths[n] for n in names], world)[rank])]
+                if indexed:
+                    bam.select(mine)
                 kw = {}
                 if context is not None:
                     kw["context"] = context

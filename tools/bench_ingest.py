@@ -27,9 +27,10 @@ from pymasc_amd.synth import HG38  # noqa: E402
 from tests import io_writers as W  # noqa: E402
 
 
-def synth_bam(path, n_reads, seed=1, readlen=36, chroms=None, cigar_lengths=None):
+def synth_bam(path, n_reads, seed=1, readlen=36, chroms=None, cigar_lengths=None, index=False):
     """cigar_lengths(k): query lengths of the next k records' one M operation (default: all readlen; the record layout, sequence
-    and qualities stay those of readlen bases, so the file has the same size and records either way)."""
+    and qualities stay those of readlen bases, so the file has the same size and records either way).  index: also write
+    <path>.bai (one chunk per reference and the pseudo-bin 37450, as samtools puts it)."""
     rng = np.random.default_rng(seed)
     refs = [(n, l) for n, l in HG38] if chroms is None else [(n, l) for n, l in HG38][:chroms]
     total = sum(l for _, l in refs)
@@ -41,16 +42,20 @@ def synth_bam(path, n_reads, seed=1, readlen=36, chroms=None, cigar_lengths=None
                           ("seq", "u1", ((readlen + 1) // 2,)), ("qual", "u1", (readlen,))])
     header = W.bam_header(refs)
     t0 = time.time()
+    zsizes, spans, u = [], {}, len(header)      # (for the index: compressed block sizes, uncompressed [beg, end) per reference)
     with open(path, "wb") as fp, ThreadPoolExecutor(8) as pool:
         def flush(data):
             blocks = [data[i:i + 0xff00] for i in range(0, len(data), 0xff00)]
             for z in pool.map(lambda b: W.bgzf_block(b, 1), blocks):
                 fp.write(z)
+                zsizes.append(len(z))
         pending = header
         for rid, (_n, ln) in enumerate(refs):
             k = int(round(n_reads * ln / total))
             if k == 0:
                 continue
+            spans[rid] = (u, u + k * (rec_dtype.itemsize))
+            u += k * rec_dtype.itemsize
             rec = np.zeros(k, dtype=rec_dtype)
             rec["block_size"] = rec_dtype.itemsize - 4
             rec["ref"] = rid
@@ -75,7 +80,63 @@ def synth_bam(path, n_reads, seed=1, readlen=36, chroms=None, cigar_lengths=None
             pending = pending[cut:]
         flush(pending)
         fp.write(W.BGZF_EOF)
+    if index:
+        import struct
+        coff = np.concatenate(([0], np.cumsum(zsizes))).tolist()
+
+        def voff(x):      # (a position at a block end belongs to the next block)
+            k, r = divmod(x, 0xff00)
+            return (coff[k] << 16) | r
+        out = [b"BAI\1", struct.pack("<i", len(refs))]
+        for rid in range(len(refs)):
+            if rid not in spans:
+                out.append(struct.pack("<ii", 0, 0))
+                continue
+            vb, ve = voff(spans[rid][0]), voff(spans[rid][1])
+            n = (spans[rid][1] - spans[rid][0]) // rec_dtype.itemsize
+            out.append(struct.pack("<iIiQQ", 2, 4681, 1, vb, ve) + struct.pack("<IiQQQQ", 37450, 2, vb, ve, n, 0)
+                       + struct.pack("<i", 0))
+        with open(path + ".bai", "wb") as fp:
+            fp.write(b"".join(out))
     return refs, time.time() - t0
+
+
+def time_subsets(path, refs, mapq, reps=5):
+    """Indexed device reads (DeviceBamReader(references=...): pmx_dbam_open_indexed + pmx_dbam_select) against the whole-file
+    open: open + decode wall-clock and the compressed bytes read, for the whole file, the largest chromosome alone and one LPT
+    share of 8 ranks.  The kept records of every case are checked against the host reader's per-chromosome counts."""
+    from pymasc_amd import bam_device as D
+    from pymasc_amd.sharding import lpt_assign
+    names = [n for n, _ in refs]
+    with B.BamReader(path, threads=16) as r:
+        per = np.zeros(len(names), dtype=np.int64)
+        for ref, _pos, _rl, _rev in r.batches(mapq):
+            per += np.bincount(ref, minlength=len(names))
+    largest = max(refs, key=lambda x: x[1])[0]
+    share = [names[i] for i in sorted(lpt_assign([l for _, l in refs], 8)[0])]
+    cases = [("whole_file", None), ("largest_chromosome", [largest]), ("lpt_share_of_8", share)]
+    out = {}
+    for label, sel in cases:
+        want = int(per.sum()) if sel is None else int(sum(per[names.index(n)] for n in sel))
+        runs = []
+        for rep in range(reps + 1):      # (rep 0: warm-up, not in the statistics)
+            t0 = time.time()
+            with D.DeviceBamReader(path, references=sel) as r:
+                t1 = time.time()
+                kept = r.decode(mapq)
+                t2 = time.time()
+                c = r.counters()
+            assert kept == want, (label, kept, want)
+            if rep:
+                runs.append((t1 - t0, t2 - t0, c["bytes_in"], c["members"]))
+        tot = np.array([x[1] for x in runs])
+        out[label] = {"chromosomes": len(names) if sel is None else len(sel), "kept": want, "bytes_in": runs[0][2],
+                      "members": runs[0][3], "file_bytes": os.path.getsize(path),
+                      "open_s": [round(x[0], 4) for x in runs], "open_decode_s": [round(x, 4) for x in tot.tolist()],
+                      "open_decode_median_s": round(float(np.median(tot)), 4), "open_decode_min_s": round(float(tot.min()), 4),
+                      "open_decode_max_s": round(float(tot.max()), 4)}
+        print(json.dumps({label: out[label]}), flush=True)
+    return out
 
 
 def time_reader(path, threads, mapq):
@@ -171,10 +232,11 @@ def main():
     ap.add_argument("--device", action="store_true", help="time the device-side reader (BGZF inflate + decode as HIP kernels)")
     ap.add_argument("--bigwig", action="store_true", help="also time the mappability track: host reader against device reader")
     ap.add_argument("--pyloop", type=int, default=0, help="time a per-read Python feeding loop over this many reads")
+    ap.add_argument("--subsets", action="store_true", help="write a .bai and time indexed device reads of chromosome subsets")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
-    refs, gen_s = synth_bam(a.path, a.reads, chroms=a.chroms)
+    refs, gen_s = synth_bam(a.path, a.reads, chroms=a.chroms, index=a.subsets)
     res = {"reads": a.reads, "bam_bytes": os.path.getsize(a.path), "generate_s": round(gen_s, 1), "reader": []}
     for t in a.threads:
         if t <= (os.cpu_count() or 1):
@@ -238,6 +300,8 @@ def main():
                 calc.close()
                 res["end_to_end_device"].append({"seconds": round(dt2, 3), "reads_fed": fed2, "reads_per_s": round(fed2 / dt2)})
                 print(json.dumps(res["end_to_end_device"][-1]), flush=True)
+    if a.subsets:
+        res["subsets"] = time_subsets(a.path, refs, a.mapq)
     if a.bigwig:
         res["bigwig"] = time_bigwig(a.path + ".bw")
         print(json.dumps(res["bigwig"]), flush=True)
@@ -245,6 +309,8 @@ def main():
         with open(a.out, "w") as fp:
             json.dump(res, fp, indent=1)
     os.unlink(a.path)
+    if a.subsets:
+        os.unlink(a.path + ".bai")
 
 
 if __name__ == "__main__":
