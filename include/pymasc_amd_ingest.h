@@ -65,6 +65,18 @@ int pmx_dbam_open_indexed(const char *path, const char *bai_path, int device, in
  * (stale or shifted index), and a record of a reference that was not chosen. */
 int pmx_dbam_select(pmx_dbam *b, const int32_t *refs, int32_t n);
 
+/* SAM text (version >= 3): `path` is a SAM file, plain or BGZF-compressed (bgzip; a gzip file that is not BGZF is
+ * PMX_DBAM_ERR_FORMAT).  The text goes to HBM as the BAM open sends the file (BGZF: the same member scan, k_bgzf_inflate and
+ * k_bgzf_crc); the header is parsed on the host from the stream's prefix; k_sam_count / k_sam_lines index the lines and
+ * k_sam_parse parses every record line into a table in HBM by the rules of DESIGN.md 7.4 (the rules of pmx_sam_open,
+ * pymasc_amd_io.h, which is its checker).  A malformed line: PMX_DBAM_ERR_FORMAT, "line N: <reason>" as pmx_sam_open words it.
+ * The handle is a pmx_dbam whose stream is the text: nref / ref_name / ref_len / header_text, decode (a filter + compaction
+ * over the table: the records, fields and order of the BAM twin), device_arrays, fetch, runs, readlen_hist (first[i] = byte
+ * offset in the text of the line of the first counted record), readlen_counters, counters (records = alignment lines,
+ * bytes_out = text bytes, bytes_in = file bytes, members = 0 for plain SAM, rewalked = 0), timings ([4] line index,
+ * [5] parse + the last filter) and inflated (the text) work on it; pmx_dbam_select returns PMX_DBAM_ERR_INVALID (no index). */
+int pmx_dsam_open(const char *path, int device, int nthreads, pmx_dbam **out);
+
 /* Reference dictionary = pysam's AlignmentFile.references / .lengths (reader/bam.py:137-153). */
 int32_t pmx_dbam_nref(const pmx_dbam *b);
 const char *pmx_dbam_ref_name(const pmx_dbam *b, int32_t i);

@@ -95,6 +95,31 @@ int64_t pmx_bam_readlen_hist(pmx_bam *b, uint32_t mapq_min, int64_t cap, int32_t
 /* c = {nreads, nunmapped, ncounted, npaired, nread2, nnoqlen} of the last pmx_bam_readlen_hist */
 int pmx_bam_readlen_counters(const pmx_bam *b, uint64_t c[6]);
 
+/* ---- SAM text (SAM spec v1 section 1), plain or BGZF-compressed (bgzip) ---------------------------------------
+ * The host twin of pmx_dsam_open (pymasc_amd_ingest.h) and its checker: the same parsing rules, the same
+ * records, read-length histogram and counters as that reader, and as the BAM readers give for the BAM twin of the file.
+ * pmx_sam_open reads the whole text (a BGZF file inflated on the reader's threads; a gzip file that is not BGZF is refused),
+ * parses the header ('@' lines before the first record; @SQ SN / LN in header order = the references) and every record line
+ * (FLAG, RNAME, POS, MAPQ, CIGAR; >= 11 fields); a malformed line is PMX_IO_ERR_FORMAT with "line N: <reason>" (1-based).
+ * nthreads <= 0: one per core (max 16).  There is no index: a SAM file is read whole. */
+typedef struct pmx_sam pmx_sam;
+int pmx_sam_open(const char *path, int nthreads, pmx_sam **out);
+void pmx_sam_close(pmx_sam *s);
+int32_t pmx_sam_nref(const pmx_sam *s);
+const char *pmx_sam_ref_name(const pmx_sam *s, int32_t i);
+int64_t pmx_sam_ref_len(const pmx_sam *s, int32_t i);
+const char *pmx_sam_header_text(const pmx_sam *s, uint32_t *len);
+/* The records that pass pmx_bam_next_batch's filter (want_ref >= 0: that reference only), in file order: returns their number;
+ * pmx_sam_fetch copies records [first, first + n) of them.  May be called again with another filter. */
+int64_t pmx_sam_decode(pmx_sam *s, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref);
+int pmx_sam_fetch(pmx_sam *s, int64_t first, int64_t n, int32_t *ref_id, int32_t *pos1, int32_t *read_len, uint8_t *reverse);
+/* alignment lines, records kept by the last decode, text bytes, file bytes, BGZF members (0 for plain SAM) */
+int pmx_sam_counters(const pmx_sam *s, uint64_t *records, uint64_t *kept, uint64_t *bytes_out, uint64_t *bytes_in,
+                     uint64_t *members);
+/* pmx_bam_readlen_hist's rules and protocol; first[i] = byte offset in the text of the line of the first counted record */
+int64_t pmx_sam_readlen_hist(pmx_sam *s, uint32_t mapq_min, int64_t cap, int32_t *lengths, uint64_t *counts, uint64_t *first);
+int pmx_sam_readlen_counters(const pmx_sam *s, uint64_t c[6]);
+
 /* ---- BigWig (bbi) ----------------------------------------------------------------------------------------- */
 typedef struct pmx_bigwig pmx_bigwig;
 

@@ -33,6 +33,8 @@ IO_EXPORTS = [
     "pmx_bam_open", "pmx_bam_close", "pmx_bam_nref", "pmx_bam_ref_name", "pmx_bam_ref_len", "pmx_bam_header_text",
     "pmx_bam_next_batch", "pmx_bam_counters", "pmx_bam_index_load", "pmx_bam_has_index", "pmx_bam_fetch_ref",
     "pmx_bam_readlen_hist", "pmx_bam_readlen_counters",
+    "pmx_sam_open", "pmx_sam_close", "pmx_sam_nref", "pmx_sam_ref_name", "pmx_sam_ref_len", "pmx_sam_header_text",
+    "pmx_sam_decode", "pmx_sam_fetch", "pmx_sam_counters", "pmx_sam_readlen_hist", "pmx_sam_readlen_counters",
     "pmx_bigwig_open", "pmx_bigwig_close", "pmx_bigwig_nchrom", "pmx_bigwig_chrom_name", "pmx_bigwig_chrom_len",
     "pmx_bigwig_fetch",
 ]
@@ -91,6 +93,28 @@ def load_io_library():
     L.pmx_bam_readlen_hist.restype = i64
     L.pmx_bam_readlen_counters.argtypes = [vp, ctypes.POINTER(u64)]
     L.pmx_bam_readlen_counters.restype = ctypes.c_int
+    L.pmx_sam_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(vp)]
+    L.pmx_sam_open.restype = ctypes.c_int
+    L.pmx_sam_close.argtypes = [vp]
+    L.pmx_sam_close.restype = None
+    L.pmx_sam_nref.argtypes = [vp]
+    L.pmx_sam_nref.restype = i32
+    L.pmx_sam_ref_name.argtypes = [vp, i32]
+    L.pmx_sam_ref_name.restype = ctypes.c_char_p
+    L.pmx_sam_ref_len.argtypes = [vp, i32]
+    L.pmx_sam_ref_len.restype = i64
+    L.pmx_sam_header_text.argtypes = [vp, ctypes.POINTER(u32)]
+    L.pmx_sam_header_text.restype = ctypes.c_char_p
+    L.pmx_sam_decode.argtypes = [vp, u32, u32, i32]
+    L.pmx_sam_decode.restype = i64
+    L.pmx_sam_fetch.argtypes = [vp, i64, i64, vp, vp, vp, vp]
+    L.pmx_sam_fetch.restype = ctypes.c_int
+    L.pmx_sam_counters.argtypes = [vp] + [ctypes.POINTER(u64)] * 5
+    L.pmx_sam_counters.restype = ctypes.c_int
+    L.pmx_sam_readlen_hist.argtypes = [vp, u32, i64, vp, vp, vp]
+    L.pmx_sam_readlen_hist.restype = i64
+    L.pmx_sam_readlen_counters.argtypes = [vp, ctypes.POINTER(u64)]
+    L.pmx_sam_readlen_counters.restype = ctypes.c_int
     L.pmx_bigwig_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pmx_bigwig_open.restype = ctypes.c_int
     L.pmx_bigwig_close.argtypes = [vp]

@@ -25,7 +25,7 @@ INGEST_EXPORTS = [
     "pmx_dbam_last_error", "pmx_dbam_version", "pmx_dbam_open", "pmx_dbam_close", "pmx_dbam_nref", "pmx_dbam_ref_name",
     "pmx_dbam_ref_len", "pmx_dbam_header_text", "pmx_dbam_decode", "pmx_dbam_device_arrays", "pmx_dbam_fetch",
     "pmx_dbam_runs", "pmx_dbam_counters", "pmx_dbam_timings", "pmx_dbam_inflated", "pmx_dbam_readlen_hist",
-    "pmx_dbam_readlen_counters", "pmx_dbam_open_indexed", "pmx_dbam_select",
+    "pmx_dbam_readlen_counters", "pmx_dbam_open_indexed", "pmx_dbam_select", "pmx_dsam_open",
     "pmx_dbw_open", "pmx_dbw_close", "pmx_dbw_nchrom", "pmx_dbw_chrom_name", "pmx_dbw_chrom_len", "pmx_dbw_fetch", "pmx_dbw_device_arrays",
     "pmx_dbw_sorted", "pmx_dbw_copy",
 ]
@@ -53,6 +53,8 @@ def load_ingest_library():
     L.pmx_dbam_open.restype = ctypes.c_int
     L.pmx_dbam_open_indexed.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     L.pmx_dbam_open_indexed.restype = ctypes.c_int
+    L.pmx_dsam_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+    L.pmx_dsam_open.restype = ctypes.c_int
     L.pmx_dbam_select.argtypes = [vp, ctypes.POINTER(i32), i32]
     L.pmx_dbam_select.restype = ctypes.c_int
     L.pmx_dbam_close.argtypes = [vp]
@@ -147,6 +149,10 @@ class DeviceBamReader:
             rc = self._L.pmx_dbam_open(self.path.encode(), int(device), int(threads), ctypes.byref(h))
         if rc:
             _raise(rc)
+        self._attach(h, references)
+
+    def _attach(self, h, references) -> None:
+        """The handle of an open: the header's references, then the selection."""
         self._h = h
         n = self._L.pmx_dbam_nref(h)
         self.references: Tuple[str, ...] = tuple(self._L.pmx_dbam_ref_name(h, i).decode() for i in range(n))

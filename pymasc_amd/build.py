@@ -86,6 +86,7 @@ def build_ingest(force=False, verbose=False):
     A library of its own: libpymasc_hip.so's build id (source_hash) covers the cross-correlation kernels only."""
     deps = ingest_sources() + glob.glob(os.path.join(CSRC, "ingest", "*.inc")) + [os.path.join(HERE, "..", "include", "pymasc_amd_ingest.h"),
                                                                                      os.path.join(CSRC, "io", "bai_index.h"),
+                                                                                     os.path.join(CSRC, "io", "sam_parse.h"),
                                                                                      os.path.abspath(__file__)]
     if not force and os.path.exists(INGEST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(INGEST_LIB) for d in deps):
         return INGEST_LIB

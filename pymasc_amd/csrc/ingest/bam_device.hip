@@ -835,8 +835,11 @@ struct RlArgs {
     u32 hmask;
 };
 
-template <int PASS>
-__global__ void __launch_bounds__(256) k_bam_readlen(const RlArgs A)
+// The body of the histogram kernels (k_bam_readlen; k_sam_readlen in sam_device.inc): the tables, a lane's counters and run,
+// the merge.  walk(add) calls add(flag, mapq, qlen, key) for every record with ref_id >= 0 of the lane's share, in file order;
+// qlen() and key() are evaluated only for a record that is counted.
+template <int PASS, class Walk>
+__device__ __forceinline__ void readlen_lane(const RlArgs &A, Walk walk)
 {
     __shared__ u32 s_cnt[PASS == 0 ? RL_SHORT : 1];
     __shared__ unsigned long long s_first[PASS == 0 ? RL_SHORT : 1];
@@ -874,8 +877,50 @@ __global__ void __launch_bounds__(256) k_bam_readlen(const RlArgs A)
             }
         }
     };
-    const u64 c = (u64)blockIdx.x * 256u + t;
-    if (c < A.npieces) {
+    walk([&](u32 flag, u32 mapq, auto qlen, auto key) {
+        c_[0]++;
+        if (flag & 0x1u) {
+            c_[3]++;
+            if (flag & 0x80u) c_[4]++;
+        }
+        if (flag & 0x4u) {
+            c_[1]++;
+        } else if (!(flag & 0x400u) && mapq >= A.mapq_min) {
+            const u32 q = qlen();
+            if (q == 0u || q > 0x7fffffffu) {
+                c_[5]++;
+            } else {
+                c_[2]++;
+                if (q != run_len) {
+                    flush();
+                    run_len = q;
+                    run_cnt = 0;
+                    run_first = key();
+                }
+                run_cnt++;
+            }
+        }
+    });
+    flush();
+    if (PASS == 0) {
+        for (u32 k = 0; k < RL_NCNT; k++)
+            if (c_[k]) atomicAdd(&s_c[k], c_[k]);
+        __syncthreads();
+        for (u32 i = t; i < RL_SHORT; i += 256u)
+            if (s_cnt[i]) {
+                atomicAdd(&A.bins[i], (unsigned long long)s_cnt[i]);
+                atomicMin(&A.bins[RL_SHORT + i], s_first[i]);
+            }
+        if (t < RL_NCNT && s_c[t]) atomicAdd(&A.bins[2u * RL_SHORT + t], (unsigned long long)s_c[t]);
+    }
+}
+
+template <int PASS>
+__global__ void __launch_bounds__(256) k_bam_readlen(const RlArgs A)
+{
+    readlen_lane<PASS>(A, [&](auto add) {
+        const u64 c = (u64)blockIdx.x * 256u + threadIdx.x;
+        if (c >= A.npieces) return;
         const u8 *__restrict__ D = A.D;
         const u64 cend = (c + 1u) * WALK_PIECE;
         u64 s = A.spec[c];
@@ -902,50 +947,17 @@ __global__ void __launch_bounds__(256) k_bam_readlen(const RlArgs A)
                 if (PASS == 0) atomicMin(&A.bins[2u * RL_SHORT + RL_NCNT], (unsigned long long)((s << 4) | err));
                 break;
             }
-            if (ref >= 0) {
-                const u32 mapq = rec[9], flag = ld16u(rec + 14);
-                c_[0]++;
-                if (flag & 0x1u) {
-                    c_[3]++;
-                    if (flag & 0x80u) c_[4]++;
-                }
-                if (flag & 0x4u) {
-                    c_[1]++;
-                } else if (!(flag & 0x400u) && mapq >= A.mapq_min) {
+            if (ref >= 0)
+                add(ld16u(rec + 14), (u32)rec[9], [&]() {
                     const u32 l_seq = ld32u(rec + 16);
                     const u8 *cig = rec + 32u + l_name;
                     u32 n = n_cig;
                     long_cigar(rec, bs, l_name, n_cig, l_seq, cig, n);
-                    const u32 q = cigar_qlen(cig, n);
-                    if (q == 0u || q > 0x7fffffffu) {
-                        c_[5]++;
-                    } else {
-                        c_[2]++;
-                        if (q != run_len) {
-                            flush();
-                            run_len = q;
-                            run_cnt = 0;
-                            run_first = A.base + s;
-                        }
-                        run_cnt++;
-                    }
-                }
-            }
+                    return cigar_qlen(cig, n);
+                }, [&]() { return A.base + s; });
             s += 4ull + bs;
         }
-    }
-    flush();
-    if (PASS == 0) {
-        for (u32 k = 0; k < RL_NCNT; k++)
-            if (c_[k]) atomicAdd(&s_c[k], c_[k]);
-        __syncthreads();
-        for (u32 i = t; i < RL_SHORT; i += 256u)
-            if (s_cnt[i]) {
-                atomicAdd(&A.bins[i], (unsigned long long)s_cnt[i]);
-                atomicMin(&A.bins[RL_SHORT + i], s_first[i]);
-            }
-        if (t < RL_NCNT && s_c[t]) atomicAdd(&A.bins[2u * RL_SHORT + t], (unsigned long long)s_c[t]);
-    }
+    });
 }
 
 // exclusive prefix sums of kept[] (one workgroup: a few hundred thousand pieces at most per GB), totals of kept[] and cnt[]
@@ -1113,6 +1125,17 @@ struct Staging {
 };
 Staging g_stage;
 
+// the buffers' events are recorded on the stream of the handle being opened, which does not outlive the handle: whatever way the
+// open is left, the copies are waited for and the buffers are marked free (an event of a destroyed stream cannot be waited on)
+struct StageReset {
+    hipStream_t st;
+    ~StageReset()
+    {
+        (void)hipStreamSynchronize(st);
+        for (bool &u : g_stage.used) u = false;
+    }
+};
+
 const char *inf_err_text(u32 code)
 {
     switch (code) {
@@ -1177,6 +1200,13 @@ struct pmx_dbam {
     std::vector<pmx_bai::RefRange> index;
     u64 hdr_end = 0;                 // file offset behind the last member that holds part of the header
     u64 bytes_read = 0, members_read = 0;   // compressed bytes and members behind the current stream (counters)
+    // SAM text (pmx_dsam_open, sam_device.inc): the stream is the text, a table of its record lines replaces the record chain
+    bool sam = false;
+    u64 sam_lines = 0, sam_hdr_lines = 0;
+    u64 *d_nl = nullptr;             // end of every record line ('\n' or the end of the text)
+    int *d_sref = nullptr, *d_spos = nullptr;
+    u32 *d_sqlen = nullptr, *d_sfm = nullptr;   // query length; flag | mapq << 16
+    double sam_parse_t = 0;          // seconds of the parse at open (timings [5] = it + the last filter)
 };
 
 namespace {
@@ -1249,6 +1279,19 @@ int launch_members(pmx_dbam &b, hipEvent_t after, u64 out_end)
     return 0;
 }
 
+// the staging buffers, page-locked once per process (g_stage_mu held)
+int stage_setup()
+{
+    if (!g_stage.ready) {
+        for (int i = 0; i < NSTAGE; i++) {
+            HIPOK(hipHostMalloc((void **)&g_stage.buf[i], STAGE_HEAD + STAGE_PAYLOAD, hipHostMallocDefault));
+            HIPOK(hipEventCreateWithFlags(&g_stage.ev[i], hipEventDisableTiming));
+        }
+        g_stage.ready = true;
+    }
+    return 0;
+}
+
 int read_and_upload(pmx_dbam &b, const char *path, int nthreads)
 {
     const int fd = open(path, O_RDONLY);
@@ -1265,23 +1308,8 @@ int read_and_upload(pmx_dbam &b, const char *path, int nthreads)
     } closer{fd};
     if (b.fsize < 28) return fail(PMX_DBAM_ERR_FORMAT, "truncated BGZF block header");
     std::lock_guard<std::mutex> stage_guard(g_stage_mu);
-    // the buffers' events are recorded on THIS handle's stream, which does not outlive the handle: whatever way this function is
-    // left, the copies are waited for and the buffers are marked free (an event of a destroyed stream cannot be waited on)
-    struct StageReset {
-        hipStream_t st;
-        ~StageReset()
-        {
-            (void)hipStreamSynchronize(st);
-            for (bool &u : g_stage.used) u = false;
-        }
-    } stage_reset{b.stream};
-    if (!g_stage.ready) {
-        for (int i = 0; i < NSTAGE; i++) {
-            HIPOK(hipHostMalloc((void **)&g_stage.buf[i], STAGE_HEAD + STAGE_PAYLOAD, hipHostMallocDefault));
-            HIPOK(hipEventCreateWithFlags(&g_stage.ev[i], hipEventDisableTiming));
-        }
-        g_stage.ready = true;
-    }
+    StageReset stage_reset{b.stream};
+    if (int rc = stage_setup()) return rc;
     const double tq0 = now_s();
     HIPOK(hipMalloc((void **)&b.d_in, b.fsize + IN_PAD));
     HIPOK(hipMemsetAsync(b.d_in + b.fsize, 0, IN_PAD, b.stream));
@@ -1725,7 +1753,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 2; }
+int pmx_dbam_version(void) { return 3; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1791,6 +1819,8 @@ void pmx_dbam_close(pmx_dbam *b)
     if (b->kstream) (void)sync_kernels(*b);
     free_chain(*b);
     if (b->d_rl) (void)hipFree(b->d_rl);
+    for (void *p : {(void *)b->d_nl, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
+        if (p) (void)hipFree(p);
     for (hipStream_t x : b->kmore)
         if (x) (void)hipStreamDestroy(x);
     if (b->h_mem) (void)hipHostFree(b->h_mem);
@@ -1895,10 +1925,14 @@ static int record_error(unsigned long long fe)
     }
 }
 
+static int64_t dsam_decode(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref);   // sam_device.inc
+static hipError_t dsam_launch_readlen(const pmx_dbam *b, int pass, const RlArgs &A);
+
 static int64_t dbam_decode_impl(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref)
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     HIPOK(hipSetDevice(b->device));
+    if (b->sam) return dsam_decode(b, mapq_min, flag_exclude, want_ref);
     b->n_kept = b->n_records = 0;
     if (b->npieces == 0) return 0;
     const u64 np = b->npieces;
@@ -2055,11 +2089,19 @@ static int64_t dbam_readlen_impl(pmx_dbam *b, uint32_t mapq_min)
     HIPOK(hipSetDevice(b->device));
     b->rl_hist.clear();
     for (u64 &x : b->rl_c) x = 0;
-    if (b->npieces > 0) {
+    if (b->npieces > 0 || b->sam_lines > 0) {
         const u64 np = b->npieces;
         const u64 N = b->N - b->data_beg;
         const u8 *D = b->d_out + b->data_beg;
-        if (!b->chain_ready) {          // (its counts are decode's scratch: the next decode walks with its own filter again)
+        // one pass of the histogram kernel: over the record chain, or over the line table of a SAM handle
+        auto launch = [&](int pass, const RlArgs &A) -> hipError_t {
+            if (b->sam) return dsam_launch_readlen(b, pass, A);
+            const dim3 wg((unsigned)((np + 255) / 256));
+            if (pass == 0) hipLaunchKernelGGL(k_bam_readlen<0>, wg, dim3(256), 0, b->stream, A);
+            else hipLaunchKernelGGL(k_bam_readlen<1>, wg, dim3(256), 0, b->stream, A);
+            return hipGetLastError();
+        };
+        if (!b->sam && !b->chain_ready) {          // (its counts are decode's scratch: the next decode walks with its own filter again)
             WalkArgs W;
             W.D = D;
             W.N = N;
@@ -2089,9 +2131,7 @@ static int64_t dbam_readlen_impl(pmx_dbam *b, uint32_t mapq_min)
         A.hkey = nullptr;
         A.hcnt = A.hfirst = nullptr;
         A.hmask = 0;
-        const dim3 wg((unsigned)((np + 255) / 256));
-        hipLaunchKernelGGL(k_bam_readlen<0>, wg, dim3(256), 0, b->stream, A);
-        HIPOK(hipGetLastError());
+        HIPOK(launch(0, A));
         std::vector<unsigned long long> h(nb);
         HIPOK(hipMemcpyAsync(h.data(), b->d_rl, 8 * nb, hipMemcpyDeviceToHost, b->stream));
         HIPOK(hipStreamSynchronize(b->stream));
@@ -2118,8 +2158,7 @@ static int64_t dbam_readlen_impl(pmx_dbam *b, uint32_t mapq_min)
                 A.hcnt = d_cf;
                 A.hfirst = d_cf + slots;
                 A.hmask = (u32)(slots - 1);
-                hipLaunchKernelGGL(k_bam_readlen<1>, wg, dim3(256), 0, b->stream, A);
-                e = hipGetLastError();
+                e = launch(1, A);
             }
             if (e == hipSuccess) {
                 key.resize(slots);
@@ -2464,3 +2503,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 }  // extern "C"
 
 #include "bigwig_device.inc"
+#include "sam_device.inc"

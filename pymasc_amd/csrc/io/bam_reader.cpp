@@ -144,10 +144,8 @@ inline double now_s()
 }
 
 // Parses the BGZF member at `off`; false at a clean end of file.  Throws on a malformed member.
-bool scan_block(const pmx_bam &b, size_t off, Block &blk, size_t &next)
+bool scan_block(const uint8_t *base, size_t size, size_t off, Block &blk, size_t &next)
 {
-    const uint8_t *base = b.file.data;
-    const size_t size = b.file.size;
     if (off == size) return false;
     if (off + BGZF_HEADER + BGZF_FOOTER > size) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "truncated BGZF block header");
     const uint8_t *p = base + off;
@@ -209,7 +207,7 @@ bool load_window(pmx_bam &b, uint32_t max_blocks)
     while (b.blocks.size() < max_blocks) {
         Block blk;
         size_t next;
-        if (b.next_off > b.stop_block || !scan_block(b, b.next_off, blk, next)) {
+        if (b.next_off > b.stop_block || !scan_block(b.file.data, b.file.size, b.next_off, blk, next)) {
             b.eof = true;
             break;
         }
@@ -528,7 +526,7 @@ void readlen_pass(pmx_bam &b, uint32_t mapq_min)
         while (blocks.size() < WINDOW_BLOCKS) {
             Block blk;
             size_t next;
-            if (!scan_block(b, off, blk, next)) {
+            if (!scan_block(b.file.data, b.file.size, off, blk, next)) {
                 eof = true;
                 break;
             }
@@ -583,6 +581,26 @@ void readlen_pass(pmx_bam &b, uint32_t mapq_min)
 }
 
 }  // namespace
+
+// Every BGZF member of data[0, size) inflated (and CRC-checked) on nthreads threads into `out`; for the SAM reader.
+void pmx_io::bgzf_inflate_all(const uint8_t *data, size_t size, int nthreads, std::vector<uint8_t> &out, uint64_t &members)
+{
+    std::vector<Block> blocks;
+    size_t off = 0, next, total = 0;
+    Block blk;
+    while (scan_block(data, size, off, blk, next)) {
+        blk.out_off = total;
+        total += blk.isize;
+        blocks.push_back(blk);
+        off = next;
+    }
+    out.resize(total);
+    uint8_t *dst = out.data();
+    parallel_for(nthreads, blocks.size(), 16, [&](size_t lo, size_t hi, size_t) {
+        for (size_t i = lo; i < hi; i++) inflate_block(blocks[i], dst + blocks[i].out_off);
+    });
+    members = blocks.size();
+}
 
 extern "C" {
 

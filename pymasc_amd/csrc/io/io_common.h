@@ -84,5 +84,8 @@ void parallel_for(int nthreads, size_t n, size_t grain, F fn)
     if (failed.load()) throw first;
 }
 
+// Every BGZF member of data[0, size) inflated into out (bam_reader.cpp); throws Error on a malformed or corrupt member.
+void bgzf_inflate_all(const uint8_t *data, size_t size, int nthreads, std::vector<uint8_t> &out, uint64_t &members);
+
 }  // namespace pmx_io
 #endif

@@ -31,7 +31,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     reuses the device reader that then feeds the run: with ``read_len`` None the whole file is opened even when
     ``references`` or ``chromfilter`` choose some chromosomes; with ``read_len`` given and a .bai present, the device reader
     reads only the chosen chromosomes' BGZF members (sharding.run_sharded).  ``chromfilter``: PyMaSC's -i / -e filter as
-    ``[(include, [patterns]), ...]`` (pymasc_amd.chromfilter), not together with ``references``."""
+    ``[(include, [patterns]), ...]`` (pymasc_amd.chromfilter), not together with ``references``.  ``bam_path`` may be a SAM
+    file, plain or BGZF (pymasc_amd.sam); the tables are named after ``Path(bam_path).stem`` as PyMaSC names them."""
     if references is not None and chromfilter is not None:
         raise ValueError("give references or chromfilter, not both")
     import torch.distributed as dist
@@ -53,35 +54,40 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
             bam.close()
 
 
+def _host_reader(path):
+    """The host reader of the file, without its index (a read-length estimate reads the whole file)."""
+    from .bam import BamReader
+    from .sam import SamReader, is_sam
+    return SamReader(path) if is_sam(path) else BamReader(path, index=False)
+
+
 def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, group, context, device_ingest, rank, world):
     """(read length, the DeviceBamReader it was estimated on or None).  One rank: on the device reader that the run then
     feeds from when the BAM file goes through the GPU, on the host reader otherwise.  Several ranks: rank 0 estimates on the
     host reader and broadcasts the value or its error; every rank raises on an error, none waits."""
     import torch.distributed as dist
     from . import readlen
+    from .sam import open_reader
     from .sharding import _collective_device_setup, default_device_ingest
     readlen._check_esttype(esttype)                     # (every rank: a wrong name fails before any collective)
     if world == 1:
         if device_ingest is None:
             device_ingest = default_device_ingest(world, context)
         if device_ingest:
-            from .bam_device import DeviceBamReader
-            bam = DeviceBamReader(bam_path, device=(context.device if context is not None else device))
+            bam = open_reader(bam_path, True, device=(context.device if context is not None else device))
             try:
                 return readlen.estimate_from_reader(bam, esttype, mapq_criteria, max_shift), bam
             except BaseException:
                 bam.close()
                 raise
-        from .bam import BamReader
-        with BamReader(bam_path, index=False) as b:
+        with _host_reader(bam_path) as b:
             return readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift), None
     _collective_device_setup(device, group)
     box = [None, None]              # [read length, error]
     err = None
     if rank == 0:
         try:
-            from .bam import BamReader
-            with BamReader(bam_path, index=False) as b:
+            with _host_reader(bam_path) as b:
                 box[0] = readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift)
         except Exception as e:      # every rank must learn about it (no hang below)
             err = e

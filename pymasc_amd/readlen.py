@@ -126,7 +126,7 @@ def estimate_from_reader(reader, esttype="MEDIAN", mapq_criteria: int = 0, max_s
 
 def estimate_readlen(path, esttype, mapq_criteria, max_shift: Optional[int] = None, device: Optional[int] = None) -> int:
     """Drop-in for PyMaSC.core.readlen.estimate_readlen(path, esttype, mapq_criteria) (handler/calc.py:87): the file is read
-    by the device reader when there is a GPU, by the host reader otherwise.  ``max_shift``: also the check of
+    by the device reader when there is a GPU, by the host reader otherwise; a SAM file (pymasc_amd.sam) by the SAM readers.  ``max_shift``: also the check of
     handler/calc.py:93-98 (ValueError when the estimate is longer).  ``device``: the GPU (default 0); None with no GPU."""
     from . import ffi
     name = _check_esttype(esttype)
@@ -134,9 +134,15 @@ def estimate_readlen(path, esttype, mapq_criteria, max_shift: Optional[int] = No
         gpu = ffi.device_count() > 0
     except Exception:
         gpu = False
+    from .sam import is_sam
     if gpu:
         from .bam_device import DeviceBamReader
-        opener = lambda: DeviceBamReader(path, device=device or 0)      # noqa: E731
+        from .sam import DeviceSamReader
+        cls = DeviceSamReader if is_sam(path) else DeviceBamReader
+        opener = lambda: cls(path, device=device or 0)                  # noqa: E731
+    elif is_sam(path):
+        from .sam import SamReader
+        opener = lambda: SamReader(path)                               # noqa: E731
     else:
         from .bam import BamReader
         opener = lambda: BamReader(path, index=False)                  # noqa: E731

@@ -1,0 +1,188 @@
+"""SAM input (SAM spec v1 section 1), plain or BGZF-compressed (``bgzip``): what PyMaSC accepts besides BAM.
+
+* ``detect_format(path)`` tells BAM from SAM text without reading more than the first BGZF member (or 64 KB);
+* ``SamReader`` (host, libpymasc_io.so ``pmx_sam_*``) has ``BamReader``'s surface: the whole text is indexed and parsed at open
+  on the reader's threads; it is the checker of the device reader, the path without a GPU and the path of a rank of several;
+* ``DeviceSamReader`` (libpymasc_ingest.so ``pmx_dsam_open``) is a ``DeviceBamReader`` whose stream is the text: the line index,
+  the parse, the filter and the read-length histogram are HIP kernels over the text in HBM.
+
+Both give for a SAM file exactly what the BAM readers give for its BAM twin: the same records, runs, read-length histogram and
+counters; only the first-occurrence keys differ (byte offsets of lines in the text instead of records in the BAM stream).
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import zlib
+from typing import Iterator, Tuple
+
+import numpy as np
+
+from .bam import PMX_BAM_DEFAULT_EXCLUDE, PmxIOError, _raise, load_io_library
+from .bam_device import DeviceBamReader, _raise as _raise_device
+
+_PROBE = 65536
+
+
+def _is_bgzf(head: bytes) -> bool:
+    """The gzip member at the front of ``head`` has the BGZF 'BC' subfield in its extra field (SAM spec 4.1)."""
+    if len(head) < 18 or not head[3] & 4:
+        return False
+    x, end = 12, min(12 + (head[10] | head[11] << 8), len(head))
+    while x + 4 <= end:
+        if head[x:x + 2] == b"BC":
+            return True
+        x += 4 + (head[x + 2] | head[x + 3] << 8)
+    return False
+
+
+def detect_format(path) -> str:
+    """``"bam"``, ``"sam"`` (plain text) or ``"sam.bgzf"`` (bgzip'd text).  Text whose first byte is '@' is SAM; a BGZF file whose
+    first member inflates to text starting with '@' is BGZF SAM; everything else is ``"bam"`` and goes to the BAM readers, which
+    report what is wrong with it as before.  A plain-gzip SAM file raises ``PmxIOError``: htslib reads it, this project asks
+    for ``bgzip``."""
+    try:
+        with open(os.fspath(path), "rb") as fh:
+            head = fh.read(_PROBE)
+    except OSError:
+        return "bam"                # (the BAM reader reports it, as before)
+    if head[:1] == b"@":
+        return "sam"
+    if head[:3] != b"\x1f\x8b\x08":
+        return "bam"
+    try:                            # the first byte of the first member (a BGZF member is a gzip member)
+        text = zlib.decompressobj(16 + 15).decompress(head, 1)
+    except zlib.error:
+        return "bam"
+    if text[:1] != b"@":
+        return "bam"
+    if not _is_bgzf(head):
+        raise PmxIOError(-2, "{}: gzip-compressed SAM that is not BGZF: recompress it with bgzip".format(os.fspath(path)))
+    return "sam.bgzf"
+
+
+def is_sam(path) -> bool:
+    return detect_format(path) != "bam"
+
+
+class SamReader:
+    """A SAM file (plain or BGZF) as batches of filtered read arrays, like ``pymasc_amd.bam.BamReader``; no index."""
+
+    def __init__(self, path, threads: int = 0):
+        self._L = load_io_library()
+        self.path = os.fspath(path)
+        self._h = None
+        h = ctypes.c_void_p()
+        rc = self._L.pmx_sam_open(self.path.encode(), int(threads), ctypes.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        n = self._L.pmx_sam_nref(h)
+        self.references: Tuple[str, ...] = tuple(self._L.pmx_sam_ref_name(h, i).decode() for i in range(n))
+        self.lengths: Tuple[int, ...] = tuple(int(self._L.pmx_sam_ref_len(h, i)) for i in range(n))
+
+    def has_index(self) -> bool:
+        return False
+
+    @property
+    def closed(self) -> bool:
+        return self._h is None
+
+    @property
+    def header_text(self) -> str:
+        ln = ctypes.c_uint32()
+        t = self._L.pmx_sam_header_text(self._h, ctypes.byref(ln))
+        return (t or b"").decode("utf-8", "replace")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            self._L.pmx_sam_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def counters(self) -> dict:
+        """records (alignment lines), kept (last decode), bytes_out (text), bytes_in (file), members (BGZF), rewalked (0):
+        the keys of ``DeviceBamReader.counters``."""
+        v = [ctypes.c_uint64() for _ in range(5)]
+        rc = self._L.pmx_sam_counters(self._h, *[ctypes.byref(x) for x in v])
+        if rc:
+            _raise(rc)
+        out = dict(zip(("records", "kept", "bytes_out", "bytes_in", "members"), (int(x.value) for x in v)))
+        out["rewalked"] = 0
+        return out
+
+    def read_length_histogram(self, mapq_criteria: int = 0):
+        """As ``BamReader.read_length_histogram``; the first-occurrence keys are byte offsets of lines in the text."""
+        from .readlen import histogram_from_library
+        if self._h is None:
+            raise ValueError("I/O operation on closed SAM reader")
+        return histogram_from_library(self._L.pmx_sam_readlen_hist, self._L.pmx_sam_readlen_counters, self._h, mapq_criteria,
+                                      _raise)
+
+    def decode(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, reference: int = -1) -> int:
+        if self._h is None:
+            raise ValueError("I/O operation on closed SAM reader")
+        n = self._L.pmx_sam_decode(self._h, int(mapq_criteria), int(flag_exclude), int(reference))
+        if n < 0:
+            _raise(n)
+        return int(n)
+
+    def _fetch(self, first: int, n: int):
+        ref = np.empty(n, dtype=np.int32)
+        pos = np.empty(n, dtype=np.int32)
+        rlen = np.empty(n, dtype=np.int32)
+        rev = np.empty(n, dtype=np.uint8)
+        rc = self._L.pmx_sam_fetch(self._h, first, n, ref.ctypes.data, pos.ctypes.data, rlen.ctypes.data, rev.ctypes.data)
+        if rc:
+            _raise(rc)
+        return ref, pos, rlen, rev.astype(bool)
+
+    def batches(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE,
+                batch: int = 1 << 22) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+        """Yields (ref_id, pos_1based, read_len, is_reverse) of the reads that pass the reference's filter, in file order."""
+        total = self.decode(mapq_criteria, flag_exclude)
+        for first in range(0, total, batch):
+            yield self._fetch(first, min(batch, total - first))
+
+    def fetch(self, reference: str, *args, **kwargs):
+        raise ValueError("fetch() needs an index: {} is a SAM file".format(self.path))
+
+
+class DeviceSamReader(DeviceBamReader):
+    """A SAM file (plain or BGZF) copied to HBM and parsed there; the surface of ``DeviceBamReader`` (its stream is the text).
+    ``references`` selects records as for a BAM file without an index; ``select`` works the same way."""
+
+    def __init__(self, path, device: int = 0, threads: int = 0, references=None, index=None):
+        from .bam_device import load_ingest_library
+        self._L = load_ingest_library()
+        self.path = os.fspath(path)
+        self._h = None
+        self.indexed = False
+        h = ctypes.c_void_p()
+        rc = self._L.pmx_dsam_open(self.path.encode(), int(device), int(threads), ctypes.byref(h))
+        if rc:
+            _raise_device(rc)
+        self._attach(h, references)
+
+
+def open_reader(path, device_ingest: bool, device: int = 0, references=None):
+    """The reader of ``path`` for a run: a SAM file through ``DeviceSamReader`` / ``SamReader``, a BAM file through
+    ``DeviceBamReader`` / ``BamReader``."""
+    from . import bam_device
+    from .bam import BamReader
+    sam = is_sam(path)
+    if device_ingest:
+        return (DeviceSamReader if sam else bam_device.DeviceBamReader)(path, device=device, references=references)
+    return SamReader(path) if sam else BamReader(path)

@@ -202,6 +202,8 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     ``bam``: a reader of ``bam_path`` the caller has already opened (pipeline.run opens the DeviceBamReader to estimate the read
     length on it, so that the file is inflated once per run); it is used instead of opening one and is left open.  A
     DeviceBamReader implies ``device_ingest``.
+    A SAM file (plain or BGZF, ``pymasc_amd.sam.detect_format``) is read whole, as a BAM file without an index: through
+    ``DeviceSamReader`` with ``device_ingest``, else ``SamReader``; ``bam`` may be an open reader of either.
     ``chromfilter``: PyMaSC's -i / -e chromosome filter, an ordered list of ``(include, [patterns])``
     (pymasc_amd.chromfilter); not together with ``references``.  A filter that leaves nothing raises on every rank.
     With the device reader and a .bai next to the BAM file, a rank of several -- or the only rank when ``references`` or
@@ -232,21 +234,23 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     if references is not None and chromfilter is not None:
         raise ValueError("give references or chromfilter, not both")
     indexed = False
+    from .sam import DeviceSamReader, SamReader, is_sam
+    sam = bam is None and is_sam(bam_path)      # SAM text: the unindexed-BAM rules
     if device_ingest:
         from .bam_device import DeviceBamReader, find_index
-        indexed = (bam is None and (world > 1 or references is not None or chromfilter is not None)
+        indexed = (bam is None and not sam and (world > 1 or references is not None or chromfilter is not None)
                    and find_index(bam_path) is not None)
 
         def open_bam():
             # indexed: the header only, the rank's share is selected below
-            return DeviceBamReader(bam_path, device=(context.device if context is not None else (device or 0)),
-                                   references=[] if indexed else None)
+            return (DeviceSamReader if sam else DeviceBamReader)(
+                bam_path, device=(context.device if context is not None else (device or 0)), references=[] if indexed else None)
 
         def feed(calc, bam, mine):
             return bam.feed(calc, mapq_criteria, references=mine)
     else:
         def open_bam():
-            return BamReader(bam_path)
+            return SamReader(bam_path) if sam else BamReader(bam_path)
 
         def feed(calc, bam, mine):
             return feed_bam(calc, bam, mapq_criteria, references=mine)

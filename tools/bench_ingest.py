@@ -182,6 +182,93 @@ def time_device_reader(path, mapq, check=None):
     return out
 
 
+def synth_sam(path, n_reads, bgzf=False, seed=1, readlen=36):
+    """The synthetic file of synth_bam as SAM text (bgzf: BGZF-compressed at level 1, as `bgzip -l 1` writes it), one fixed-width
+    layout per reference built with numpy (zero-padded decimals are decimals): flags 0 / 16 with 2 % duplicates, MAPQ 0..60."""
+    rng = np.random.default_rng(seed)
+    refs = [(n, l) for n, l in HG38]
+    total = sum(l for _, l in refs)
+    header = ("@HD\tVN:1.0\tSO:coordinate\n" + "".join("@SQ\tSN:{}\tLN:{}\n".format(n, l) for n, l in refs)).encode()
+    t0 = time.time()
+
+    def digits(v, w):
+        return (np.asarray(v, dtype=np.int64)[:, None] // (10 ** np.arange(w - 1, -1, -1, dtype=np.int64)) % 10 + 48).astype(np.uint8)
+
+    with open(path, "wb") as fp, ThreadPoolExecutor(8) as pool:
+        def flush(data, last=False):
+            if not bgzf:
+                fp.write(data)
+                return b""
+            n = len(data) if last else len(data) // 0xff00 * 0xff00
+            for z in pool.map(lambda i: W.bgzf_block(data[i:i + 0xff00], 1), range(0, n, 0xff00)):
+                fp.write(z)
+            return data[n:]
+
+        rest = flush(header)
+        k0 = 0
+        for _name, ln in refs:
+            k = int(round(n_reads * ln / total))
+            for a in range(0, k, 1 << 20):
+                m = min(1 << 20, k - a)
+                cols = [b"r", digits(np.arange(k0, k0 + m), 9), b"\t", None, b"\t" + _name.encode() + b"\t", None, b"\t", None,
+                        ("\t%dM\t*\t0\t0\t" % readlen).encode() + b"A" * readlen + b"\t" + b"I" * readlen + b"\n"]
+                flag = np.where(rng.random(m) < 0.5, 16, 0) | np.where(rng.random(m) < 0.02, 1024, 0)
+                cols[3] = digits(flag, 4)
+                cols[5] = digits(np.sort(rng.integers(1, ln - readlen, size=m)), 9)
+                cols[7] = digits(rng.integers(0, 61, size=m), 2)
+                parts = [np.broadcast_to(np.frombuffer(c, np.uint8), (m, len(c))) if isinstance(c, bytes) else c for c in cols]
+                rest = flush(rest + np.concatenate(parts, axis=1).tobytes())
+                k0 += m
+        if bgzf:
+            flush(rest, last=True)
+            fp.write(W.BGZF_EOF)
+    return refs, time.time() - t0
+
+
+def time_sam(path, threads, mapq):
+    """SamReader (host, threads) against DeviceSamReader (open + decode + runs, resident in HBM); the same records either way."""
+    from pymasc_amd import sam as S
+    out = {"sam_bytes": os.path.getsize(path), "host": [], "device": []}
+    check = None
+    for t in threads:
+        t0 = time.time()
+        with S.SamReader(path, threads=t) as r:
+            t1 = time.time()
+            n = cs = 0
+            for _ref, pos, _rl, rev in r.batches(mapq):
+                n += pos.size
+                cs += int(pos.astype(np.int64).sum()) + int(rev.sum())
+            c = r.counters()
+        dt = time.time() - t0
+        check = (n, cs)
+        out["host"].append({"threads": t, "open_s": round(t1 - t0, 3), "seconds": round(dt, 3), "records": c["records"], "kept": n,
+                            "text_GBps": round(c["bytes_out"] / dt / 1e9, 3)})
+        print(json.dumps(out["host"][-1]), flush=True)
+    for rep in range(3):      # the first open also page-locks the staging buffers and loads the code object
+        t0 = time.time()
+        with S.DeviceSamReader(path) as r:
+            t1 = time.time()
+            kept = r.decode(mapq)
+            runs = r.device_runs()
+            t2 = time.time()
+            n = cs = 0
+            for _ref, pos, _rl, rev in r.batches(mapq):
+                n += pos.size
+                cs += int(pos.astype(np.int64).sum()) + int(rev.sum())
+            c, tm = r.counters(), r.timings()
+        assert (n, cs) == check and kept == n, ((n, cs), check)
+        out["device"].append({"rep": rep, "open_s": round(t1 - t0, 4), "decode_and_runs_s": round(t2 - t1, 4),
+                              "resident_total_s": round(t2 - t0, 4), "runs": len(runs), "records": c["records"], "kept": kept,
+                              "members": c["members"], "phases_s": {k: round(v, 4) for k, v in tm.items()},
+                              "text_GBps": round(c["bytes_out"] / (t2 - t0) / 1e9, 3)})
+        print(json.dumps(out["device"][-1]), flush=True)
+    best_dev = min(x["resident_total_s"] for x in out["device"])
+    best_host = min(x["seconds"] for x in out["host"])
+    out["device_vs_host"] = {"device_resident_s": best_dev, "host_best_s": best_host, "speedup": round(best_host / best_dev, 2)}
+    print(json.dumps(out["device_vs_host"]), flush=True)
+    return out
+
+
 def time_bigwig(path_bw, chroms_per_call=None):
     """A synthetic hg38-shaped mappability track (runs of ~500 bp every ~1250 bp, bedGraph sections of 1024 items, zlib) read
     chromosome by chromosome: the host reader (zlib on threads) against the device reader (intervals left in HBM), same intervals."""
@@ -233,8 +320,23 @@ def main():
     ap.add_argument("--bigwig", action="store_true", help="also time the mappability track: host reader against device reader")
     ap.add_argument("--pyloop", type=int, default=0, help="time a per-read Python feeding loop over this many reads")
     ap.add_argument("--subsets", action="store_true", help="write a .bai and time indexed device reads of chromosome subsets")
+    ap.add_argument("--sam", choices=["plain", "bgzf"], default=None,
+                    help="write the synthetic reads as SAM text (plain or BGZF) and time SamReader against DeviceSamReader")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+
+    if a.sam:
+        path = a.path + (".sam" if a.sam == "plain" else ".sam.gz")
+        _refs, gen_s = synth_sam(path, a.reads, bgzf=(a.sam == "bgzf"))
+        res = {"reads": a.reads, "format": a.sam, "generate_s": round(gen_s, 1)}
+        try:
+            res.update(time_sam(path, [t for t in a.threads if t <= (os.cpu_count() or 1)], a.mapq))
+        finally:
+            os.unlink(path)
+        if a.out:
+            with open(a.out, "w") as fp:
+                json.dump(res, fp, indent=1)
+        return
 
     refs, gen_s = synth_bam(a.path, a.reads, chroms=a.chroms, index=a.subsets)
     res = {"reads": a.reads, "bam_bytes": os.path.getsize(a.path), "generate_s": round(gen_s, 1), "reader": []}
