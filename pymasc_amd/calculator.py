@@ -654,7 +654,8 @@ class CCHipCalculator:
         self._buff_flashed = True
 
     def finishup_calculation(self) -> None:
-        self.flush(self._chr)
+        # no read fed at all (a rank whose chromosomes have none): nothing to flush, every chromosome is filled empty below
+        self.flush(self._chr if self._chr != "" else None)
         for chrom in self.references:
             self._fill_result(chrom)
         self._materialize()

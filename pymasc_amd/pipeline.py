@@ -3,8 +3,9 @@
 What `pymasc sample.bam -m track.bw -d MAX_SHIFT -q MAPQ -r READ_LEN -o OUTDIR` does between argument parsing and the
 statistics / plots (PyMaSC/pymasc.py:90-160, handler/calc.py:100-161): open the BAM, open the mappability track,
 load or compute the mappable-length cache, run the calculator over the reads, write the `_cc` / `_mscc` / `_nreads`
-tables.  Without READ_LEN the read length is estimated from the BAM file first (pymasc.py:187-227, handler/calc.py:74-98;
-pymasc_amd.readlen).  No CLI, no statistics: those stay the reference's.
+tables and, with ``stats=True``, the `_stats.tab` of the fragment-length estimate and the quality scores (pymasc_amd.stats).
+Without READ_LEN the read length is estimated from the BAM file first (pymasc.py:187-227, handler/calc.py:74-98;
+pymasc_amd.readlen).  No CLI and no figures.
 Under `torch.distributed` (one process per GPU) the chromosomes are sharded over the ranks and rank 0 writes.
 """
 from __future__ import annotations
@@ -21,7 +22,9 @@ from .sharding import run_sharded
 def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_criteria: int = 1, mappability_path=None,
         mappability_stats_path=None, skip_ncc: bool = False, references: Optional[Sequence[str]] = None,
         device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
-        device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None):
+        device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
+        library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
+        chi2_pval: float = 0.05):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -32,9 +35,19 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     ``references`` or ``chromfilter`` choose some chromosomes; with ``read_len`` given and a .bai present, the device reader
     reads only the chosen chromosomes' BGZF members (sharding.run_sharded).  ``chromfilter``: PyMaSC's -i / -e filter as
     ``[(include, [patterns]), ...]`` (pymasc_amd.chromfilter), not together with ``references``.  ``bam_path`` may be a SAM
-    file, plain or BGZF (pymasc_amd.sam); the tables are named after ``Path(bam_path).stem`` as PyMaSC names them."""
+    file, plain or BGZF (pymasc_amd.sam); the tables are named after ``Path(bam_path).stem`` as PyMaSC names them.
+    ``stats``: rank 0 also writes ``<stem>_stats.tab`` (pymasc_amd.stats.genome_wide_stats / write_stats) with PyMaSC's
+    options -l ``library_length``, -w ``smooth_window``, --mask-size ``mask_size``, --bg-avr-width ``bg_avr_width`` and
+    --chi2-pval ``chi2_pval``.  A ``library_length`` longer than ``max_shift`` or below 1, or a ``smooth_window`` below 1, is
+    a ValueError before any GPU work (PyMaSC logs a too long ``library_length`` and ignores it)."""
     if references is not None and chromfilter is not None:
         raise ValueError("give references or chromfilter, not both")
+    from .stats import check_params
+    check_params(None, library_length, smooth_window, max_shift)
+    stat_opts = None
+    if stats:
+        stat_opts = dict(library_length=library_length, smooth_window=smooth_window, mask_size=mask_size,
+                         bg_avr_width=bg_avr_width, chi2_pval=chi2_pval)
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
@@ -48,7 +61,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
                                                context, device_ingest, rank, world)
         return _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path,
                     skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank,
-                    chromfilter)
+                    chromfilter, stat_opts)
     finally:
         if bam is not None:
             bam.close()
@@ -101,7 +114,8 @@ def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, grou
 
 
 def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path, skip_ncc,
-         references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank, chromfilter=None):
+         references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank, chromfilter=None,
+         stat_opts=None):
     import torch.distributed as dist
 
     # The mappable-length cache (handler/mappability.py:239-309): loaded when valid; otherwise computed ONCE, on rank 0,
@@ -144,4 +158,8 @@ def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path,
         out = Path(outdir)
         out.mkdir(parents=True, exist_ok=True)
         written = tables.write_tables(out / Path(bam_path).name, result)
+        if stat_opts is not None:   # every rank holds the same result: the statistics are rank 0's alone
+            from . import stats
+            written.append(stats.write_stats(out / Path(bam_path).stem,
+                                             stats.genome_wide_stats(result, read_len, **stat_opts)))
     return result, written
