@@ -18,6 +18,8 @@ from typing import Iterator, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .inputs import find_index
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libpymasc_io.so"
 
@@ -135,49 +137,19 @@ def _raise(code: int):
     raise PmxIOError(int(code), load_io_library().pmx_io_last_error().decode("utf-8", "replace"))
 
 
-class BamReader:
-    """A coordinate-sorted BAM file as batches of filtered read arrays."""
-
-    def __init__(self, path, threads: int = 0, index=None):
-        """``index``: path of the .bai; None: ``<path>.bai`` or ``<stem>.bai`` when present (like pysam); False: none."""
-        self._L = load_io_library()
-        self.path = os.fspath(path)
-        h = ctypes.c_void_p()
-        rc = self._L.pmx_bam_open(self.path.encode(), int(threads), ctypes.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
-        n = self._L.pmx_bam_nref(h)
-        self.references: Tuple[str, ...] = tuple(self._L.pmx_bam_ref_name(h, i).decode() for i in range(n))
-        self.lengths: Tuple[int, ...] = tuple(int(self._L.pmx_bam_ref_len(h, i)) for i in range(n))
-        if index is None:
-            for cand in (self.path + ".bai", os.path.splitext(self.path)[0] + ".bai"):
-                if os.path.exists(cand):
-                    index = cand
-                    break
-        if index:
-            rc = self._L.pmx_bam_index_load(h, os.fspath(index).encode())
-            if rc:
-                self.close()
-                _raise(rc)
-
-    def has_index(self) -> bool:
-        """reader/bam.py:128-135."""
-        return bool(self._L.pmx_bam_has_index(self._h))
+class NativeReader:
+    """What every reader over a library handle shares: ``closed``, ``close()``, the context manager and ``__del__``.
+    ``_h`` is the handle (None until the open succeeds and after close), ``_CLOSE`` the name of the library's close function."""
+    _h = None
+    _CLOSE = ""
 
     @property
     def closed(self) -> bool:
         return self._h is None
 
-    @property
-    def header_text(self) -> str:
-        ln = ctypes.c_uint32()
-        t = self._L.pmx_bam_header_text(self._h, ctypes.byref(ln))
-        return (t or b"").decode("utf-8", "replace")
-
     def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._L.pmx_bam_close(self._h)
+        if self._h is not None:
+            getattr(self._L, self._CLOSE)(self._h)
             self._h = None
 
     def __enter__(self):
@@ -192,6 +164,41 @@ class BamReader:
             self.close()
         except Exception:
             pass
+
+
+class BamReader(NativeReader):
+    """A coordinate-sorted BAM file as batches of filtered read arrays."""
+    _CLOSE = "pmx_bam_close"
+
+    def __init__(self, path, threads: int = 0, index=None):
+        """``index``: path of the .bai; None: ``<path>.bai`` or ``<stem>.bai`` when present (like pysam); False: none."""
+        self._L = load_io_library()
+        self.path = os.fspath(path)
+        h = ctypes.c_void_p()
+        rc = self._L.pmx_bam_open(self.path.encode(), int(threads), ctypes.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        n = self._L.pmx_bam_nref(h)
+        self.references: Tuple[str, ...] = tuple(self._L.pmx_bam_ref_name(h, i).decode() for i in range(n))
+        self.lengths: Tuple[int, ...] = tuple(int(self._L.pmx_bam_ref_len(h, i)) for i in range(n))
+        if index is None:
+            index = find_index(self.path)
+        if index:
+            rc = self._L.pmx_bam_index_load(h, os.fspath(index).encode())
+            if rc:
+                self.close()
+                _raise(rc)
+
+    def has_index(self) -> bool:
+        """reader/bam.py:128-135."""
+        return bool(self._L.pmx_bam_has_index(self._h))
+
+    @property
+    def header_text(self) -> str:
+        ln = ctypes.c_uint32()
+        t = self._L.pmx_bam_header_text(self._h, ctypes.byref(ln))
+        return (t or b"").decode("utf-8", "replace")
 
     def counters(self) -> dict:
         v = [ctypes.c_uint64() for _ in range(4)]
@@ -224,6 +231,10 @@ class BamReader:
         if rc:
             _raise(rc)
         return self.batches(mapq_criteria, flag_exclude, batch, _region=True)
+
+    def feed(self, calculator, mapq_criteria: int, references: Optional[Sequence[str]] = None, finish: bool = True) -> int:
+        """``feed_bam`` over this reader, as ``DeviceBamReader.feed`` is over the device reader."""
+        return feed_bam(calculator, self, mapq_criteria, references, finish)
 
     def batches(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, batch: int = 1 << 22,
                 _region: bool = False) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:

@@ -15,7 +15,8 @@ from typing import Iterator, Tuple
 
 import numpy as np
 
-from .bam import PMX_BAM_DEFAULT_EXCLUDE, PmxIOError
+from .bam import PMX_BAM_DEFAULT_EXCLUDE, NativeReader, PmxIOError
+from .inputs import find_index
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libpymasc_ingest.so"
@@ -115,16 +116,7 @@ class UnknownReferenceError(ValueError, KeyError):
     """A reference name the BAM header does not hold (a ValueError; a KeyError too, as ``fetch`` raised before)."""
 
 
-def find_index(path):
-    """``<path>.bai`` or ``<stem>.bai``, as pysam and ``pymasc_amd.bam.BamReader`` look for it; None when neither exists."""
-    path = os.fspath(path)
-    for cand in (path + ".bai", os.path.splitext(path)[0] + ".bai"):
-        if os.path.exists(cand):
-            return cand
-    return None
-
-
-class DeviceBamReader:
+class DeviceBamReader(NativeReader):
     """A BAM file inflated and decoded on the GPU; batches of filtered read arrays like ``BamReader``.
 
     ``references``: None reads the whole file (every reference selected).  A list of names with an index present (``index``:
@@ -132,11 +124,11 @@ class DeviceBamReader:
     (``pmx_dbam_open_indexed`` + ``pmx_dbam_select``); without an index the whole file is read and the selection is applied to
     the records.  ``select(names)`` replaces the selection (the two-step use: open with ``references=[]``, read the header,
     choose).  ``references`` / ``lengths`` always list the whole header; ``selected`` the chosen names in header order."""
+    _CLOSE = "pmx_dbam_close"
 
     def __init__(self, path, device: int = 0, threads: int = 0, references=None, index=None):
         self._L = load_ingest_library()
         self.path = os.fspath(path)
-        self._h = None
         if references is not None and index is not False:
             index = find_index(self.path) if index is None else os.fspath(index)
         else:
@@ -207,32 +199,10 @@ class DeviceBamReader:
         return True
 
     @property
-    def closed(self) -> bool:
-        return self._h is None
-
-    @property
     def header_text(self) -> str:
         ln = ctypes.c_uint32()
         t = self._L.pmx_dbam_header_text(self._h, ctypes.byref(ln))
         return (t or b"").decode("utf-8", "replace")
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._L.pmx_dbam_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def counters(self) -> dict:
         v = [ctypes.c_uint64() for _ in range(6)]

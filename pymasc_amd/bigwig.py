@@ -14,12 +14,14 @@ from typing import Dict, Iterator, Tuple
 
 import numpy as np
 
-from .bam import PmxIOError, _raise, load_io_library  # noqa: F401  (PmxIOError re-exported)
+from .bam import NativeReader, PmxIOError, _raise, load_io_library  # noqa: F401  (PmxIOError re-exported)
 
 PMX_IO_ERR_NOTFOUND = -4
 
 
-class BigWigReader:
+class BigWigReader(NativeReader):
+    _CLOSE = "pmx_bigwig_close"
+
     def __init__(self, path):
         path_str = os.fspath(path)
         if not os.path.exists(path_str):
@@ -31,7 +33,6 @@ class BigWigReader:
         if rc:
             _raise(rc)
         self._h = h
-        self.closed = False
         n = self._L.pmx_bigwig_nchrom(h)
         self.chromsizes: Dict[str, int] = {
             self._L.pmx_bigwig_chrom_name(h, i).decode(): int(self._L.pmx_bigwig_chrom_len(h, i)) for i in range(n)}
@@ -65,22 +66,3 @@ class BigWigReader:
 
     def disable_progress_bar(self) -> None:
         pass
-
-    def close(self) -> None:
-        if not getattr(self, "closed", True):
-            self._L.pmx_bigwig_close(self._h)
-            self._h = None
-            self.closed = True
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

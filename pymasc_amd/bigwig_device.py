@@ -14,7 +14,7 @@ from typing import Dict, Iterator, Tuple
 
 import numpy as np
 
-from .bam import PmxIOError
+from .bam import NativeReader, PmxIOError
 from .bam_device import load_ingest_library
 
 PMX_DBAM_ERR_NOTFOUND = -4
@@ -24,20 +24,20 @@ def _raise(code: int):
     raise PmxIOError(int(code), load_ingest_library().pmx_dbam_last_error().decode("utf-8", "replace"))
 
 
-class DeviceBigWigReader:
+class DeviceBigWigReader(NativeReader):
+    _CLOSE = "pmx_dbw_close"
+
     def __init__(self, path, device: int = 0, threads: int = 0):
         path_str = os.fspath(path)
         if not os.path.exists(path_str):
             raise IOError("input file '{0}' dose not exist.".format(path_str))     # bigwig.pyx:127-128
         self._L = load_ingest_library()
         self.path = path_str
-        self._h = None
         h = ctypes.c_void_p()
         rc = self._L.pmx_dbw_open(path_str.encode(), int(device), int(threads), ctypes.byref(h))
         if rc:
             _raise(rc)
         self._h = h
-        self.closed = False
         n = self._L.pmx_dbw_nchrom(h)
         self.chromsizes: Dict[str, int] = {self._L.pmx_dbw_chrom_name(h, i).decode(): int(self._L.pmx_dbw_chrom_len(h, i))
                                            for i in range(n)}
@@ -78,22 +78,3 @@ class DeviceBigWigReader:
 
     def disable_progress_bar(self) -> None:
         pass
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._L.pmx_dbw_close(self._h)
-            self._h = None
-        self.closed = True
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

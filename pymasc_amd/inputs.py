@@ -1,0 +1,51 @@
+"""Which reader a run reads its input through: the one place that chooses between the host readers (libpymasc_io.so) and
+the device readers (libpymasc_ingest.so) of an alignment file -- BAM, or SAM (pymasc_amd.sam) -- and of a BigWig track.
+
+The reader modules import ``find_index`` from here, so they are imported inside the openers, and the device classes are
+looked up through their module each time (a test may replace ``bam_device.DeviceBamReader``).
+"""
+from __future__ import annotations
+
+import os
+
+
+def find_index(path):
+    """``<path>.bai`` or ``<stem>.bai``, as pysam looks for it; None when neither exists."""
+    path = os.fspath(path)
+    for cand in (path + ".bai", os.path.splitext(path)[0] + ".bai"):
+        if os.path.exists(cand):
+            return cand
+    return None
+
+
+def default_device_ingest(world: int, context=None) -> bool:
+    """The default of ``device_ingest``: the input is inflated and decoded on the GPU when this is the only rank and it runs
+    on a real GPU (``context`` None or a pymasc_amd.ffi.Context).  False when the device count cannot be read."""
+    from . import ffi
+    if world != 1 or not (context is None or isinstance(context, ffi.Context)):
+        return False
+    try:
+        return ffi.device_count() > 0
+    except Exception:
+        return False
+
+
+def open_alignments(path, device_ingest: bool, device: int = 0, references=None, index=None):
+    """The reader of an alignment file: ``DeviceSamReader`` / ``DeviceBamReader`` on ``device`` with ``device_ingest``, else
+    ``SamReader`` / ``BamReader``.  ``references`` and ``index`` as ``DeviceBamReader`` takes them (the host readers read the
+    whole file and leave the choice of chromosomes to ``feed``); ``index=False`` also opens the host BAM reader without its
+    .bai, as a read-length estimate over the whole file wants it."""
+    from . import bam, bam_device, sam
+    is_sam = sam.is_sam(path)
+    if device_ingest:
+        cls = sam.DeviceSamReader if is_sam else bam_device.DeviceBamReader
+        return cls(path, device=device, references=references, index=index)
+    return sam.SamReader(path) if is_sam else bam.BamReader(path, index=index)
+
+
+def open_track(path, device_ingest: bool, device: int = 0):
+    """The reader of a BigWig track: ``DeviceBigWigReader`` on ``device`` with ``device_ingest``, else ``BigWigReader``."""
+    from . import bigwig, bigwig_device
+    if device_ingest:
+        return bigwig_device.DeviceBigWigReader(path, device=device)
+    return bigwig.BigWigReader(path)

@@ -14,9 +14,10 @@ import os
 from pathlib import Path
 from typing import List, Optional, Sequence
 
-from . import tables
+from . import readlen, tables
+from .inputs import default_device_ingest, open_alignments, open_track
 from .mappability import MappabilityStats
-from .sharding import run_sharded
+from .sharding import _collective_device_setup, on_rank0, rank_and_world, run_sharded
 
 
 def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_criteria: int = 1, mappability_path=None,
@@ -48,108 +49,63 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     if stats:
         stat_opts = dict(library_length=library_length, smooth_window=smooth_window, mask_size=mask_size,
                          bg_avr_width=bg_avr_width, chi2_pval=chi2_pval)
-    import torch.distributed as dist
-    on = dist.is_available() and dist.is_initialized()
-    rank = dist.get_rank(group) if on else 0
-    world = dist.get_world_size(group) if on else 1
+    on, rank, world = rank_and_world(group)
     if device is None:
         device = int(os.environ.get("LOCAL_RANK", "0")) if on else 0
+    _collective_device_setup(device, group)
     bam = None                      # a reader opened here for the estimate and handed on: the file is inflated once per run
     try:
         if read_len is None:
             read_len, bam = _estimate_read_len(bam_path, max_shift, mapq_criteria, readlen_estimator, device, group,
-                                               context, device_ingest, rank, world)
+                                               context, device_ingest, world)
         return _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path,
-                    skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank,
+                    skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, rank,
                     chromfilter, stat_opts)
     finally:
         if bam is not None:
             bam.close()
 
 
-def _host_reader(path):
-    """The host reader of the file, without its index (a read-length estimate reads the whole file)."""
-    from .bam import BamReader
-    from .sam import SamReader, is_sam
-    return SamReader(path) if is_sam(path) else BamReader(path, index=False)
-
-
-def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, group, context, device_ingest, rank, world):
-    """(read length, the DeviceBamReader it was estimated on or None).  One rank: on the device reader that the run then
+def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, group, context, device_ingest, world):
+    """(read length, the device reader it was estimated on or None).  One rank: on the device reader that the run then
     feeds from when the BAM file goes through the GPU, on the host reader otherwise.  Several ranks: rank 0 estimates on the
-    host reader and broadcasts the value or its error; every rank raises on an error, none waits."""
-    import torch.distributed as dist
-    from . import readlen
-    from .sam import open_reader
-    from .sharding import _collective_device_setup, default_device_ingest
+    host reader and broadcasts the value or its error (sharding.on_rank0); every rank raises on an error, none waits."""
     readlen._check_esttype(esttype)                     # (every rank: a wrong name fails before any collective)
-    if world == 1:
-        if device_ingest is None:
-            device_ingest = default_device_ingest(world, context)
-        if device_ingest:
-            bam = open_reader(bam_path, True, device=(context.device if context is not None else device))
-            try:
-                return readlen.estimate_from_reader(bam, esttype, mapq_criteria, max_shift), bam
-            except BaseException:
-                bam.close()
-                raise
-        with _host_reader(bam_path) as b:
-            return readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift), None
-    _collective_device_setup(device, group)
-    box = [None, None]              # [read length, error]
-    err = None
-    if rank == 0:
+    if world == 1 and (default_device_ingest(world, context) if device_ingest is None else device_ingest):
+        bam = open_alignments(bam_path, True, device=(context.device if context is not None else device))
         try:
-            with _host_reader(bam_path) as b:
-                box[0] = readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift)
-        except Exception as e:      # every rank must learn about it (no hang below)
-            err = e
-            box[1] = "{}: {}".format(type(e).__name__, e)
-    dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
-    if err is not None:
-        raise err                   # rank 0 re-raises its own exception (type kept)
-    if box[1] is not None:
-        raise RuntimeError("read length estimation failed on rank 0 [{}]".format(box[1]))
-    return int(box[0]), None
+            return readlen.estimate_from_reader(bam, esttype, mapq_criteria, max_shift), bam
+        except BaseException:
+            bam.close()
+            raise
+
+    def estimate():                 # the whole file: the host reader without its index
+        with open_alignments(bam_path, False, index=False) as b:
+            return readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift)
+    return int(on_rank0(estimate, group, "read length estimation")), None
 
 
 def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path, skip_ncc,
-         references, device, save_mappability_stats, group, context, device_ingest, bam, on, rank, chromfilter=None,
+         references, device, save_mappability_stats, group, context, device_ingest, bam, rank, chromfilter=None,
          stat_opts=None):
-    import torch.distributed as dist
-
     # The mappable-length cache (handler/mappability.py:239-309): loaded when valid; otherwise computed ONCE, on rank 0,
     # written atomically, and broadcast -- the other ranks neither recompute it per chromosome nor read a file that is
     # being rewritten.
-    known = None
-    if mappability_path is not None:
-        from .bigwig import BigWigReader
-        from .sharding import _collective_device_setup
-        _collective_device_setup(device, group)
-        box = [None, None]          # [chrom2mappable_len, error message]
-        if rank == 0:
+    def mappable_lengths():
+        with open_track(mappability_path, False) as bw:
+            stats = MappabilityStats(bw, max_shift, read_len, map_path=mappability_stats_path, track_path=mappability_path,
+                                     device=device, context=context)
             try:
-                with BigWigReader(mappability_path) as bw:
-                    stats = MappabilityStats(bw, max_shift, read_len, map_path=mappability_stats_path,
-                                             track_path=mappability_path, device=device, context=context)
-                    try:
-                        if stats.is_called:                      # a valid cache: the autocorrelation pass is skipped
-                            box[0] = stats.chrom2mappable_len
-                        elif save_mappability_stats:
-                            stats.calc_mappability()
-                            stats.save_mappability_stats()
-                            box[0] = stats.chrom2mappable_len
-                    finally:
-                        stats.close()
-            except Exception as e:                               # every rank must learn about it (no hang below)
-                box[1] = "{}: {}".format(type(e).__name__, e)
-                if not on or dist.get_world_size(group) == 1:
-                    raise
-        if on and dist.get_world_size(group) > 1:
-            dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
-        if box[1] is not None:
-            raise RuntimeError("mappability statistics failed on rank 0 [{}]".format(box[1]))
-        known = box[0]
+                if stats.is_called:                          # a valid cache: the autocorrelation pass is skipped
+                    return stats.chrom2mappable_len
+                if save_mappability_stats:
+                    stats.calc_mappability()
+                    stats.save_mappability_stats()
+                    return stats.chrom2mappable_len
+                return None
+            finally:
+                stats.close()
+    known = None if mappability_path is None else on_rank0(mappable_lengths, group, "mappability statistics")
     result = run_sharded(bam_path, max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
                          references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
                          group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter)

@@ -3,8 +3,8 @@
 What ``pymasc`` does when ``-r/--read-length`` is left out: a histogram of the query lengths of the file's records under the
 ESTIMATOR's filter (not the calculation's: read2, secondary, supplementary and QC-fail records count here), reduced to one
 integer by ``--readlen-estimator`` (MEAN / MEDIAN / MODE / MIN / MAX).  The histogram is built natively -- on the GPU by one
-more walk over the record chain ``DeviceBamReader`` keeps in HBM (include/pymasc_amd_ingest.h, pmx_dbam_readlen_hist), on host
-threads by ``BamReader`` (include/pymasc_amd_io.h, pmx_bam_readlen_hist) -- and reduced here with Python's own arithmetic,
+more walk over the record chain the device reader keeps in HBM (include/pymasc_amd_ingest.h, pmx_dbam_readlen_hist), on host
+threads by the host reader (include/pymasc_amd_io.h, pmx_bam_readlen_hist) -- and reduced here with Python's own arithmetic,
 so the result is the reference's bit for bit.  One deliberate divergence: a record without a query length
 (no CIGAR, or only H/D/N/P operations) is not counted but reported in ``nnoqlen``; the reference puts None in its counter and
 fails on it.
@@ -102,8 +102,8 @@ def histogram_from_library(fn_hist, fn_counters, handle, mapq_criteria: int, rai
 
 
 def estimate_from_reader(reader, esttype="MEDIAN", mapq_criteria: int = 0, max_shift: Optional[int] = None) -> int:
-    """The estimate on an open ``BamReader`` / ``DeviceBamReader``, with the reference's log lines (readlen.pyx:167-175) and
-    its check against the shift size (handler/calc.py:93-98)."""
+    """The estimate on an open alignment reader (pymasc_amd.inputs.open_alignments), with the reference's log lines
+    (readlen.pyx:167-175) and its check against the shift size (handler/calc.py:93-98)."""
     name = _check_esttype(esttype)
     hist = reader.read_length_histogram(mapq_criteria)
     length = hist.estimate(name)
@@ -128,24 +128,8 @@ def estimate_readlen(path, esttype, mapq_criteria, max_shift: Optional[int] = No
     """Drop-in for PyMaSC.core.readlen.estimate_readlen(path, esttype, mapq_criteria) (handler/calc.py:87): the file is read
     by the device reader when there is a GPU, by the host reader otherwise; a SAM file (pymasc_amd.sam) by the SAM readers.  ``max_shift``: also the check of
     handler/calc.py:93-98 (ValueError when the estimate is longer).  ``device``: the GPU (default 0); None with no GPU."""
-    from . import ffi
+    from .inputs import default_device_ingest, open_alignments
     name = _check_esttype(esttype)
-    try:
-        gpu = ffi.device_count() > 0
-    except Exception:
-        gpu = False
-    from .sam import is_sam
-    if gpu:
-        from .bam_device import DeviceBamReader
-        from .sam import DeviceSamReader
-        cls = DeviceSamReader if is_sam(path) else DeviceBamReader
-        opener = lambda: cls(path, device=device or 0)                  # noqa: E731
-    elif is_sam(path):
-        from .sam import SamReader
-        opener = lambda: SamReader(path)                               # noqa: E731
-    else:
-        from .bam import BamReader
-        opener = lambda: BamReader(path, index=False)                  # noqa: E731
     logger.info("Check read length... : {}".format(path))
-    with opener() as reader:
+    with open_alignments(path, default_device_ingest(1), device=device or 0, index=False) as reader:
         return estimate_from_reader(reader, name, int(mapq_criteria), max_shift)

@@ -18,7 +18,7 @@ from typing import Iterator, Tuple
 
 import numpy as np
 
-from .bam import PMX_BAM_DEFAULT_EXCLUDE, PmxIOError, _raise, load_io_library
+from .bam import PMX_BAM_DEFAULT_EXCLUDE, NativeReader, PmxIOError, _raise, feed_bam, load_io_library
 from .bam_device import DeviceBamReader, _raise as _raise_device
 
 _PROBE = 65536
@@ -65,13 +65,13 @@ def is_sam(path) -> bool:
     return detect_format(path) != "bam"
 
 
-class SamReader:
+class SamReader(NativeReader):
     """A SAM file (plain or BGZF) as batches of filtered read arrays, like ``pymasc_amd.bam.BamReader``; no index."""
+    _CLOSE = "pmx_sam_close"
 
     def __init__(self, path, threads: int = 0):
         self._L = load_io_library()
         self.path = os.fspath(path)
-        self._h = None
         h = ctypes.c_void_p()
         rc = self._L.pmx_sam_open(self.path.encode(), int(threads), ctypes.byref(h))
         if rc:
@@ -85,32 +85,10 @@ class SamReader:
         return False
 
     @property
-    def closed(self) -> bool:
-        return self._h is None
-
-    @property
     def header_text(self) -> str:
         ln = ctypes.c_uint32()
         t = self._L.pmx_sam_header_text(self._h, ctypes.byref(ln))
         return (t or b"").decode("utf-8", "replace")
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            self._L.pmx_sam_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def counters(self) -> dict:
         """records (alignment lines), kept (last decode), bytes_out (text), bytes_in (file), members (BGZF), rewalked (0):
@@ -149,6 +127,10 @@ class SamReader:
             _raise(rc)
         return ref, pos, rlen, rev.astype(bool)
 
+    def feed(self, calculator, mapq_criteria: int, references=None, finish: bool = True) -> int:
+        """``pymasc_amd.bam.feed_bam`` over this reader."""
+        return feed_bam(calculator, self, mapq_criteria, references, finish)
+
     def batches(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE,
                 batch: int = 1 << 22) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
         """Yields (ref_id, pos_1based, read_len, is_reverse) of the reads that pass the reference's filter, in file order."""
@@ -168,21 +150,9 @@ class DeviceSamReader(DeviceBamReader):
         from .bam_device import load_ingest_library
         self._L = load_ingest_library()
         self.path = os.fspath(path)
-        self._h = None
         self.indexed = False
         h = ctypes.c_void_p()
         rc = self._L.pmx_dsam_open(self.path.encode(), int(device), int(threads), ctypes.byref(h))
         if rc:
             _raise_device(rc)
         self._attach(h, references)
-
-
-def open_reader(path, device_ingest: bool, device: int = 0, references=None):
-    """The reader of ``path`` for a run: a SAM file through ``DeviceSamReader`` / ``SamReader``, a BAM file through
-    ``DeviceBamReader`` / ``BamReader``."""
-    from . import bam_device
-    from .bam import BamReader
-    sam = is_sam(path)
-    if device_ingest:
-        return (DeviceSamReader if sam else bam_device.DeviceBamReader)(path, device=device, references=references)
-    return SamReader(path) if sam else BamReader(path)

@@ -112,6 +112,12 @@ def exchange_results(local_rows: torch.Tensor, assignment: List[List[int]], njob
 # process per GPU instead of one per chromosome task.
 # ---------------------------------------------------------------------------------------------------------------
 
+def rank_and_world(group=None) -> Tuple[bool, int, int]:
+    """(is torch.distributed initialised, this rank in ``group``, the number of ranks in it); (False, 0, 1) without it."""
+    on = dist.is_available() and dist.is_initialized()
+    return on, (dist.get_rank(group) if on else 0), (dist.get_world_size(group) if on else 1)
+
+
 def _collective_device_setup(device, group=None):
     """With a GPU backend (nccl = RCCL) object collectives stage their payload on torch's CURRENT device, which is
     cuda:0 in every fresh process: bind it to this rank's GPU first, or two ranks collide on one device."""
@@ -123,6 +129,30 @@ def _collective_device_setup(device, group=None):
         return
     if "nccl" in backend and torch.cuda.is_available():
         torch.cuda.set_device(int(device))
+
+
+def on_rank0(fn, group, what: str):
+    """``fn()`` computed on rank 0 alone and its value returned on every rank.  One rank: ``fn()``, its exception propagates.
+    Several: rank 0 broadcasts the value or its error, re-raises its own exception (type kept), and every other rank raises
+    ``RuntimeError("<what> failed on rank 0 [...]")`` -- none waits for a value that never comes.  A GPU backend needs
+    ``_collective_device_setup`` first."""
+    _on, rank, world = rank_and_world(group)
+    if world == 1:
+        return fn()
+    box = [None, None]              # [value, error message]
+    err = None
+    if rank == 0:
+        try:
+            box[0] = fn()
+        except Exception as e:      # every rank must learn about it (no hang below)
+            err = e
+            box[1] = "{}: {}".format(type(e).__name__, e)
+    dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    if err is not None:
+        raise err
+    if box[1] is not None:
+        raise RuntimeError("{} failed on rank 0 [{}]".format(what, box[1]))
+    return box[0]
 
 
 def gather_chromosome_results(local: Dict[str, object], order: Sequence[str], group=None,
@@ -177,13 +207,6 @@ def reconcile_chromosome_sizes(bam_sizes: Dict[str, int], external_sizes: Dict[s
     return out
 
 
-def default_device_ingest(world: int, context=None) -> bool:
-    """The default of ``device_ingest``: the BAM file is inflated and decoded on the GPU when this is the only rank and it runs
-    on a real GPU."""
-    from . import ffi
-    return world == 1 and (context is None or isinstance(context, ffi.Context)) and ffi.device_count() > 0
-
-
 def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, bigwig_path=None,
                 references: Sequence[str] = None, skip_ncc: bool = False, device: int = None, context=None,
                 chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None, chromfilter=None):
@@ -199,26 +222,25 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     ``device_ingest``: inflate, walk and filter the BAM file on the GPU and hand the records to the feeders in HBM
     (pymasc_amd.bam_device) -- default: when this is the only rank and it runs on a real GPU; with several
     ranks each takes its own chromosomes through the host reader and the .bai instead of inflating the whole file N times.
-    ``bam``: a reader of ``bam_path`` the caller has already opened (pipeline.run opens the DeviceBamReader to estimate the read
+    ``bam``: a reader of ``bam_path`` the caller has already opened (pipeline.run opens the device reader to estimate the read
     length on it, so that the file is inflated once per run); it is used instead of opening one and is left open.  A
-    DeviceBamReader implies ``device_ingest``.
-    A SAM file (plain or BGZF, ``pymasc_amd.sam.detect_format``) is read whole, as a BAM file without an index: through
-    ``DeviceSamReader`` with ``device_ingest``, else ``SamReader``; ``bam`` may be an open reader of either.
+    device reader implies ``device_ingest``.
+    A SAM file (plain or BGZF, ``pymasc_amd.sam.detect_format``) is read whole, as a BAM file without an index: through the
+    device SAM reader with ``device_ingest``, else the host one (pymasc_amd.inputs.open_alignments); ``bam`` may be an open
+    reader of either.
     ``chromfilter``: PyMaSC's -i / -e chromosome filter, an ordered list of ``(include, [patterns])``
     (pymasc_amd.chromfilter); not together with ``references``.  A filter that leaves nothing raises on every rank.
     With the device reader and a .bai next to the BAM file, a rank of several -- or the only rank when ``references`` or
     ``chromfilter`` choose the chromosomes -- reads the header, takes its share and reads, copies and inflates only the BGZF
-    members of that share (DeviceBamReader.select); without an index, or with a ``bam`` given, the path is the
-    whole-file one above."""
-    from .bam import BamReader, feed_bam
-    from .bigwig import BigWigReader
-    from .chromfilter import filter_references
+    members of that share (the device reader's ``select``); without an index, or with a ``bam`` given, the path
+    is the whole-file one above."""
     from .calculator import CCHipCalculator
+    from .chromfilter import filter_references
+    from .inputs import default_device_ingest, find_index, open_alignments, open_track
     from .result import aggregate_results
+    from .sam import is_sam
 
-    on = dist.is_available() and dist.is_initialized()
-    rank = dist.get_rank(group) if on else 0
-    world = dist.get_world_size(group) if on else 1
+    on, rank, world = rank_and_world(group)
     if device is None and context is None and on:
         import os
         device = int(os.environ.get("LOCAL_RANK", "0"))
@@ -233,73 +255,49 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
         device_ingest = default_device_ingest(world, context)
     if references is not None and chromfilter is not None:
         raise ValueError("give references or chromfilter, not both")
-    indexed = False
-    from .sam import DeviceSamReader, SamReader, is_sam
-    sam = bam is None and is_sam(bam_path)      # SAM text: the unindexed-BAM rules
-    if device_ingest:
-        from .bam_device import DeviceBamReader, find_index
-        indexed = (bam is None and not sam and (world > 1 or references is not None or chromfilter is not None)
-                   and find_index(bam_path) is not None)
-
-        def open_bam():
-            # indexed: the header only, the rank's share is selected below
-            return (DeviceSamReader if sam else DeviceBamReader)(
-                bam_path, device=(context.device if context is not None else (device or 0)), references=[] if indexed else None)
-
-        def feed(calc, bam, mine):
-            return bam.feed(calc, mapq_criteria, references=mine)
-    else:
-        def open_bam():
-            return SamReader(bam_path) if sam else BamReader(bam_path)
-
-        def feed(calc, bam, mine):
-            return feed_bam(calc, bam, mapq_criteria, references=mine)
-    if bam is not None:             # the caller's reader: used, not closed
-        import contextlib
-        given = bam
-
-        def open_bam():             # noqa: F811
-            return contextlib.nullcontext(given)
+    dev = (context.device if context is not None else (device or 0)) if device_ingest else 0     # the device readers' GPU
+    # indexed: the open reads the header only, the rank's share is selected below.  SAM text: the unindexed-BAM rules
+    # 
+    indexed = (device_ingest and bam is None and (world > 1 or references is not None or chromfilter is not None)
+               and not is_sam(bam_path) and find_index(bam_path) is not None)
+    reader, bw = bam, None          # the caller's reader is used, not closed
     try:
-        with open_bam() as bam:
-            if chromfilter is not None:
-                names = filter_references(bam.references, chromfilter)
-            else:
-                names = [n for n in bam.references if references is None or n in set(references)]
-            lengths = dict(zip(bam.references, bam.lengths))
-            if bigwig_path is None:
-                bw = None
-            elif device_ingest:      # the track decoded on the GPU too: its intervals reach the calculator in HBM
-                from .bigwig_device import DeviceBigWigReader
-                bw = DeviceBigWigReader(bigwig_path, device=(context.device if context is not None else (device or 0)))
-            else:
-                bw = BigWigReader(bigwig_path)
+        if reader is None:
+            reader = open_alignments(bam_path, device_ingest, dev, references=[] if indexed else None)
+        if chromfilter is not None:
+            names = filter_references(reader.references, chromfilter)
+        else:
+            names = [n for n in reader.references if references is None or n in set(references)]
+        lengths = dict(zip(reader.references, reader.lengths))
+        if bigwig_path is not None:     # with device ingest the track is decoded on the GPU too: its intervals stay in HBM
+            bw = open_track(bigwig_path, device_ingest, dev)
+            # the track's chromosome sizes win where they are longer (handler/calc.py:100-115)
+            lengths.update(reconcile_chromosome_sizes({n: lengths[n] for n in names}, bw.chromsizes))
+        mine = [names[i] for i in sorted(lpt_assign([lengths[n] for n in names], world)[rank])]
+        if indexed:
+            reader.select(mine)
+        kw = {}
+        if context is not None:
+            kw["context"] = context
+        elif device is not None:
+            kw["device"] = device
+        if mine:
+            calc = CCHipCalculator(max_shift, read_len, mine, [lengths[n] for n in mine], bwfeeder=bw,
+                                   skip_ncc=skip_ncc, chrom2mappable_len=chrom2mappable_len, **kw)
             try:
-                if bw is not None:      # the track's chromosome sizes win where they are longer (handler/calc.py:100-115)
-                    lengths.update(reconcile_chromosome_sizes({n: lengths[n] for n in names}, bw.chromsizes))
-                mine = [names[i] for i in sorted(lpt_assign([lengths[n] for n in names], world)[rank])]
-                if indexed:
-                    bam.select(mine)
-                kw = {}
-                if context is not None:
-                    kw["context"] = context
-                elif device is not None:
-                    kw["device"] = device
-                if mine:
-                    calc = CCHipCalculator(max_shift, read_len, mine, [lengths[n] for n in mine], bwfeeder=bw,
-                                           skip_ncc=skip_ncc, chrom2mappable_len=chrom2mappable_len, **kw)
-                    try:
-                        feed(calc, bam, mine)
-                        local = {c: calc.get_result(c) for c in mine}
-                    finally:
-                        if context is None:
-                            calc.close()
+                reader.feed(calc, mapq_criteria, references=mine)
+                local = {c: calc.get_result(c) for c in mine}
             finally:
-                if bw is not None:
-                    bw.close()
+                if context is None:
+                    calc.close()
     except Exception as e:              # surfaced on every rank by the gather below
         if not on or world == 1:
             raise
         error = e
+    finally:
+        if bw is not None:
+            bw.close()
+        if reader is not bam:
+            reader.close()
     merged = gather_chromosome_results(local, names, group, error=error)
     return aggregate_results(merged)

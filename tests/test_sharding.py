@@ -232,7 +232,13 @@ def _pipeline_worker(rank, world, port, q, bam, bw, tmp, tag):
         res, written = pipeline.run(bam, os.path.join(tmp, "out_%s_%d" % (tag, rank)), 120, 36, 10, mappability_path=bw,
                                     context=FakeContext())
         tabs = [open(p, "rb").read() for p in written]
-        q.put((rank, tabs, len(calls), [os.path.basename(str(p)) for p in written]))
+        try:                                               # the cache fails on rank 0: every rank raises, none waits
+            pipeline.run(bam, os.path.join(tmp, "bad_%s_%d" % (tag, rank)), 120, 36, 10,
+                         mappability_path=os.path.join(tmp, "missing.bw"), context=FakeContext())
+            err = "no error"
+        except Exception as e:
+            err = "{}: {}".format(type(e).__name__, e)
+        q.put((rank, tabs, len(calls), [os.path.basename(str(p)) for p in written], err))
     finally:
         dist.destroy_process_group()
 
@@ -264,6 +270,8 @@ def test_two_rank_pipeline_computes_the_lag_cache_once(tmp_path):
         assert got[1][1] == [] and got[1][3] == []         # rank 0 writes the tables
         assert [g[2] for g in got] == ([1, 0] if tag == "cold" else [0, 0])   # computed once, on rank 0 only / loaded
         assert os.path.exists(cache) and not [f for f in os.listdir(tmp) if ".tmp." in f]
+        assert got[0][4].startswith("OSError") and "missing.bw" in got[0][4]        # rank 0 re-raises its own exception
+        assert got[1][4].startswith("RuntimeError: mappability statistics failed on rank 0 [OSError")
         json_ok = __import__("json").load(open(cache))
         assert set(json_ok) == {"max_shift", "__whole__", "references"}
 
