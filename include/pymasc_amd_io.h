@@ -104,6 +104,10 @@ int pmx_bam_readlen_counters(const pmx_bam *b, uint64_t c[6]);
  * nthreads <= 0: one per core (max 16).  There is no index: a SAM file is read whole. */
 typedef struct pmx_sam pmx_sam;
 int pmx_sam_open(const char *path, int nthreads, pmx_sam **out);
+/* The header only: the '@' lines of plain text, or of the BGZF members inflated in order until the first record line, parsed
+ * with pmx_sam_open's rules; no record is read.  nref / ref_name / ref_len / header_text answer as after pmx_sam_open;
+ * pmx_sam_decode and pmx_sam_readlen_hist are PMX_IO_ERR_INVALID on such a handle. */
+int pmx_sam_open_header(const char *path, pmx_sam **out);
 void pmx_sam_close(pmx_sam *s);
 int32_t pmx_sam_nref(const pmx_sam *s);
 const char *pmx_sam_ref_name(const pmx_sam *s, int32_t i);

@@ -35,7 +35,7 @@ IO_EXPORTS = [
     "pmx_bam_open", "pmx_bam_close", "pmx_bam_nref", "pmx_bam_ref_name", "pmx_bam_ref_len", "pmx_bam_header_text",
     "pmx_bam_next_batch", "pmx_bam_counters", "pmx_bam_index_load", "pmx_bam_has_index", "pmx_bam_fetch_ref",
     "pmx_bam_readlen_hist", "pmx_bam_readlen_counters",
-    "pmx_sam_open", "pmx_sam_close", "pmx_sam_nref", "pmx_sam_ref_name", "pmx_sam_ref_len", "pmx_sam_header_text",
+    "pmx_sam_open", "pmx_sam_open_header", "pmx_sam_close", "pmx_sam_nref", "pmx_sam_ref_name", "pmx_sam_ref_len", "pmx_sam_header_text",
     "pmx_sam_decode", "pmx_sam_fetch", "pmx_sam_counters", "pmx_sam_readlen_hist", "pmx_sam_readlen_counters",
     "pmx_bigwig_open", "pmx_bigwig_close", "pmx_bigwig_nchrom", "pmx_bigwig_chrom_name", "pmx_bigwig_chrom_len",
     "pmx_bigwig_fetch",
@@ -48,6 +48,10 @@ class PmxIOError(IOError):
     def __init__(self, code: int, msg: str):
         super().__init__("[pmx_io {}] {}".format(code, msg))
         self.code = code
+        self.msg = msg
+
+    def __reduce__(self):           # (pickled as its two arguments: the ranks of a run pass it to each other)
+        return type(self), (self.code, self.msg)
 
 
 _lib = None
@@ -97,6 +101,8 @@ def load_io_library():
     L.pmx_bam_readlen_counters.restype = ctypes.c_int
     L.pmx_sam_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(vp)]
     L.pmx_sam_open.restype = ctypes.c_int
+    L.pmx_sam_open_header.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
+    L.pmx_sam_open_header.restype = ctypes.c_int
     L.pmx_sam_close.argtypes = [vp]
     L.pmx_sam_close.restype = None
     L.pmx_sam_nref.argtypes = [vp]

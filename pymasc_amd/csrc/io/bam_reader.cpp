@@ -602,6 +602,19 @@ void pmx_io::bgzf_inflate_all(const uint8_t *data, size_t size, int nthreads, st
     members = blocks.size();
 }
 
+size_t pmx_io::bgzf_inflate_prefix(const uint8_t *data, size_t size, size_t off, size_t want, std::vector<uint8_t> &out)
+{
+    Block blk;
+    size_t next;
+    while (out.size() < want && scan_block(data, size, off, blk, next)) {
+        const size_t at = out.size();
+        out.resize(at + blk.isize);
+        inflate_block(blk, out.data() + at);
+        off = next;
+    }
+    return off;
+}
+
 extern "C" {
 
 int pmx_bam_open(const char *path, int nthreads, pmx_bam **out)

@@ -87,5 +87,9 @@ void parallel_for(int nthreads, size_t n, size_t grain, F fn)
 // Every BGZF member of data[0, size) inflated into out (bam_reader.cpp); throws Error on a malformed or corrupt member.
 void bgzf_inflate_all(const uint8_t *data, size_t size, int nthreads, std::vector<uint8_t> &out, uint64_t &members);
 
+// The BGZF members of data[0, size) from offset `off` on, one after the other, inflated and appended to out until it holds at
+// least `want` bytes or no member is left; returns the offset of the next member (size when none is left).  Throws as above.
+size_t bgzf_inflate_prefix(const uint8_t *data, size_t size, size_t off, size_t want, std::vector<uint8_t> &out);
+
 }  // namespace pmx_io
 #endif

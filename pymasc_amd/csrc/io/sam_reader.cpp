@@ -22,6 +22,7 @@ struct pmx_sam {
     const uint8_t *t = nullptr;     // the text
     uint64_t N = 0, members = 0;
     int nthreads = 1;
+    bool header_only = false;       // pmx_sam_open_header: no record was read
     samtext::Header h;
     std::vector<uint64_t> nl;       // end ('\n' or the end of the text) of every record line
     uint64_t nrec = 0;
@@ -151,6 +152,46 @@ int pmx_sam_open(const char *path, int nthreads, pmx_sam **out)
     return PMX_IO_OK;
 }
 
+int pmx_sam_open_header(const char *path, pmx_sam **out)
+{
+    if (!path || !out) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_open_header: NULL argument");
+    *out = nullptr;
+    pmx_sam *s = new pmx_sam();
+    s->header_only = true;
+    try {
+        s->file.open(path);
+        const uint8_t *d = s->file.data;
+        const size_t n = s->file.size;
+        std::string err;
+        int rc;
+        if (n >= 2 && d[0] == 0x1f && d[1] == 0x8b) {
+            if (n < 4 || d[2] != 8 || !(d[3] & 4))
+                throw pmx_io::Error(PMX_IO_ERR_FORMAT, "gzip-compressed SAM that is not BGZF: recompress it with bgzip");
+            // members inflated in order until the text holds the first record line (or the file ends), as pmx_dsam_open
+            // reads its header from a growing prefix
+            size_t off = 0;
+            for (size_t want = (size_t)1 << 20;; want *= 2) {
+                off = pmx_io::bgzf_inflate_prefix(d, n, off, want, s->inflated);
+                rc = samtext::parse_header((const char *)s->inflated.data(), s->inflated.size(), off == n, s->h, err);
+                if (rc != 1) break;
+            }
+            std::vector<uint8_t>().swap(s->inflated);
+        } else {
+            rc = samtext::parse_header((const char *)d, n, true, s->h, err);     // reads the '@' lines only
+        }
+        if (rc != 0) throw pmx_io::Error(PMX_IO_ERR_FORMAT, err);
+        s->file.close();
+    } catch (const pmx_io::Error &e) {
+        delete s;
+        return pmx_io::fail(e.code, std::string(path) + ": " + e.msg);
+    } catch (const std::exception &e) {
+        delete s;
+        return pmx_io::fail(PMX_IO_ERR_OPEN, std::string(path) + ": " + e.what());
+    }
+    *out = s;
+    return PMX_IO_OK;
+}
+
 void pmx_sam_close(pmx_sam *s) { delete s; }
 
 int32_t pmx_sam_nref(const pmx_sam *s) { return s ? (int32_t)s->h.names.size() : 0; }
@@ -177,6 +218,7 @@ const char *pmx_sam_header_text(const pmx_sam *s, uint32_t *len)
 int64_t pmx_sam_decode(pmx_sam *s, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref)
 {
     if (!s) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_decode: NULL handle");
+    if (s->header_only) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_decode: the file was opened for its header only");
     try {
         const size_t n = s->nrec, grain = 1 << 16, chunks = (n + grain - 1) / grain;
         std::vector<uint64_t> base(chunks + 1, 0);
@@ -237,6 +279,7 @@ int pmx_sam_counters(const pmx_sam *s, uint64_t *records, uint64_t *kept, uint64
 int64_t pmx_sam_readlen_hist(pmx_sam *s, uint32_t mapq_min, int64_t cap, int32_t *lengths, uint64_t *counts, uint64_t *first)
 {
     if (!s) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_readlen_hist: NULL handle");
+    if (s->header_only) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_readlen_hist: the file was opened for its header only");
     if (lengths && (cap < 0 || !counts || !first))
         return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_readlen_hist: NULL argument or cap < 0");
     if (!s->rl_valid || s->rl_mapq != mapq_min) {

@@ -43,6 +43,13 @@ def open_alignments(path, device_ingest: bool, device: int = 0, references=None,
     return sam.SamReader(path) if is_sam else bam.BamReader(path, index=index)
 
 
+def open_header(path):
+    """The host reader of an alignment file with its header read and no record: ``references`` / ``lengths``.  A BAM file's
+    open reads the header only (its records are read by ``feed``); a SAM file is opened with ``header_only``."""
+    from . import bam, sam
+    return sam.SamReader(path, header_only=True) if sam.is_sam(path) else bam.BamReader(path, index=False)
+
+
 def open_track(path, device_ingest: bool, device: int = 0):
     """The reader of a BigWig track: ``DeviceBigWigReader`` on ``device`` with ``device_ingest``, else ``BigWigReader``."""
     from . import bigwig, bigwig_device

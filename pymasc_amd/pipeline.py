@@ -7,17 +7,27 @@ tables and, with ``stats=True``, the `_stats.tab` of the fragment-length estimat
 Without READ_LEN the read length is estimated from the BAM file first (pymasc.py:187-227, handler/calc.py:74-98;
 pymasc_amd.readlen).  No CLI and no figures.
 Under `torch.distributed` (one process per GPU) the chromosomes are sharded over the ranks and rank 0 writes.
+`run_files` is the same for several files in one call, as `pymasc a.bam b.bam -n A B` runs them (pymasc.py:90-160):
+one read length, one mappable-length cache, one track reader and one context for all of them.
 """
 from __future__ import annotations
 
+import logging
 import os
+import pickle
+from collections import namedtuple
+from itertools import zip_longest
 from pathlib import Path
 from typing import List, Optional, Sequence
 
-from . import readlen, tables
-from .inputs import default_device_ingest, open_alignments, open_track
+from . import ffi, readlen, tables
+from .chromfilter import NoTargetChromosomesError, filter_references
+from .exceptions import ReadUnsortedError
+from .inputs import default_device_ingest, open_alignments, open_header, open_track
 from .mappability import MappabilityStats
 from .sharding import _collective_device_setup, on_rank0, rank_and_world, run_sharded
+
+logger = logging.getLogger(__name__)
 
 
 def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_criteria: int = 1, mappability_path=None,
@@ -111,11 +121,262 @@ def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path,
                          group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter)
     written: List[Path] = []
     if rank == 0:
-        out = Path(outdir)
-        out.mkdir(parents=True, exist_ok=True)
-        written = tables.write_tables(out / Path(bam_path).name, result)
-        if stat_opts is not None:   # every rank holds the same result: the statistics are rank 0's alone
-            from . import stats
-            written.append(stats.write_stats(out / Path(bam_path).stem,
-                                             stats.genome_wide_stats(result, read_len, **stat_opts)))
+        written = _write_outputs(outdir, Path(bam_path).stem, result, read_len, stat_opts)
     return result, written
+
+
+def _write_outputs(outdir, basename: str, result, read_len, stat_opts) -> List[Path]:
+    """``outdir/<basename>_{cc,mscc,nreads}.tab`` and, with ``stat_opts``, ``<basename>_stats.tab`` whose Name row is
+    ``basename``; the paths written."""
+    out = Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    # write_tables names the tables after the stem of its path (table.py:185-188): a suffix keeps a dotted base name whole
+    written = tables.write_tables(out / (basename + ".bam"), result)
+    if stat_opts is not None:       # every rank holds the same result: the statistics are rank 0's alone
+        from . import stats
+        written.append(stats.write_stats(out / basename, stats.genome_wide_stats(result, read_len, **stat_opts)))
+    return written
+
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Several files in one call: `pymasc a.bam b.bam -n A B` (pymasc.py:90-160)
+# ---------------------------------------------------------------------------------------------------------------------
+
+FileResult = namedtuple("FileResult", "path basename result written error")
+FileResult.__doc__ = """One input of run_files: ``basename`` names its outputs; a skipped file has ``result`` None, ``written``
+[] and in ``error`` the exception that skipped it."""
+
+
+def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, mapq_criteria: int = 1, mappability_path=None,
+              mappability_stats_path=None, skip_ncc: bool = False, references: Optional[Sequence[str]] = None,
+              device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
+              device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
+              library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
+              chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None) -> List[FileResult]:
+    """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
+    file, in input order.  Every keyword means what it means for ``run``.
+
+    ``names``: PyMaSC's -n, paired with the files by position (a missing or None name: ``Path(file).stem``, so that a file
+    without a name gets exactly what ``run`` writes for it); a name ``N`` gives ``N_cc.tab`` ... ``N_stats.tab``, whole even
+    when it holds a dot.  More names than files, an empty name or one with a path separator, and two files with the same base
+    name are a ValueError before any work, as bad options are.  Outputs that exist already are warned about first
+    (pymasc.py:178-182).
+
+    The steps, in the reference's order (pymasc.py:99-160, 187-250):
+
+    1. Every file's header is read on the host (``inputs.open_header``: no record is read) and the chromosome filter
+       applied; a file that fails -- missing, not BAM / SAM, a bad or empty header, no chromosome left by ``chromfilter`` --
+       is logged and skipped.
+    2. The read length: ``read_len``, or the estimate of every file left (on the device reader when the run ingests on the
+       device); a file whose estimate raises ValueError (no reads, longer than ``max_shift``) is logged and skipped, and the
+       others run with the LONGEST estimate, with PyMaSC's warning when they differ.  No file left: ValueError.  Only one device
+       reader is open at a time, so with several files and no ``read_len`` each file is inflated twice: once for its estimate,
+       once for its run; a single file is inflated once, as ``run`` does it.
+    3. The mappable-length cache, once: loaded, or computed with the common read length (and saved with
+       ``save_mappability_stats``); every file's calculator takes its lag tables from it.
+    4. The files one after the other, each sharded over the ranks as ``run`` shards it.  A file whose reads are not sorted
+       (ReadUnsortedError) is logged and skipped; any other error propagates.
+
+    One context (``context``, else one made here and closed at the end) serves every file and the cache: each file's
+    calculator gives its bit-vectors back to the context's pool and frees its result arena before the next file.  The track is
+    opened once per rank.  Several ranks: rank 0 alone takes steps 1 and 2 and broadcasts which files are left and the read
+    length; every rank then walks the same files, the skip of an unsorted file is decided from every rank's outcome, and
+    rank 0 writes (``written`` is [] on the other ranks)."""
+    paths = list(paths)
+    if not paths:
+        raise ValueError("no input files")
+    if references is not None and chromfilter is not None:
+        raise ValueError("give references or chromfilter, not both")
+    from .stats import check_params
+    check_params(None, library_length, smooth_window, max_shift)
+    if read_len is None:
+        readlen._check_esttype(readlen_estimator)
+    bases = _basenames(paths, names)
+    stat_opts = None
+    if stats:
+        stat_opts = dict(library_length=library_length, smooth_window=smooth_window, mask_size=mask_size,
+                         bg_avr_width=bg_avr_width, chi2_pval=chi2_pval)
+    on, rank, world = rank_and_world(group)
+    if device is None:
+        device = int(os.environ.get("LOCAL_RANK", "0")) if on else 0
+    _collective_device_setup(device, group)
+    if rank == 0:
+        _warn_existing(outdir, bases, mappability_path is not None, skip_ncc, stats)
+    ingest = bool(default_device_ingest(world, context) if device_ingest is None else device_ingest)
+    dev = context.device if (context is not None and ingest) else device         # the device readers' GPU
+
+    errors: List[Optional[BaseException]] = [None] * len(paths)
+    kept = None                     # (index, device reader) of the only file estimated: it feeds that file's run too
+    ctx, own_ctx, track = context, False, None
+    try:
+        if world == 1:
+            read_len, kept = _choose(paths, errors, read_len, chromfilter, readlen_estimator, mapq_criteria, max_shift,
+                                     dev if ingest else None)
+        else:                       # rank 0 decides, every rank learns the same (none waits for a value that never comes)
+            def choose():
+                errs: List[Optional[BaseException]] = [None] * len(paths)
+                rl, _k = _choose(paths, errs, read_len, chromfilter, readlen_estimator, mapq_criteria, max_shift, None)
+                return rl, [None if e is None else _portable(e) for e in errs]
+            read_len, errors = on_rank0(choose, group, "choosing the input files")
+        if read_len is None:
+            raise ValueError("no input file is left to run")
+        live = [i for i, e in enumerate(errors) if e is None]
+        if ctx is None:
+            ctx, own_ctx = ffi.Context(device), True
+        known = None
+        if mappability_path is not None:
+            track = open_track(mappability_path, ingest, dev)
+
+            def mappable_lengths():
+                ms = MappabilityStats(track, max_shift, read_len, map_path=mappability_stats_path,
+                                      track_path=mappability_path, device=device, context=ctx)
+                try:
+                    if not ms.is_called:                    # no valid cache: the lag tables of every file, computed once
+                        ms.calc_mappability()
+                        if save_mappability_stats:
+                            ms.save_mappability_stats()
+                    return ms.chrom2mappable_len
+                finally:
+                    ms.close()
+            known = on_rank0(mappable_lengths, group, "mappability statistics")
+        logger.info("Calculate cross-correlation between 0 to {} base shift with reads MAPQ >= {}"
+                    "".format(max_shift, mapq_criteria))
+        results = {}
+        for i in live:
+            logger.info("Process {}".format(paths[i]))
+            bam = None
+            if kept is not None and kept[0] == i:
+                bam, kept = kept[1], None
+            try:
+                result = run_sharded(paths[i], max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
+                                     references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
+                                     group=group, context=ctx, device_ingest=ingest, bam=bam, chromfilter=chromfilter,
+                                     track=track)
+            except Exception as e:
+                skip = _unsorted_on_every_rank(e, world)
+                if skip is None:
+                    raise
+                logger.error("Reads of '{}' are not sorted by position: the file is skipped ({})".format(paths[i], skip))
+                errors[i] = skip
+                continue
+            finally:
+                if bam is not None:
+                    bam.close()
+            written = on_rank0(lambda: _write_outputs(outdir, bases[i], result, read_len, stat_opts), group,
+                               "writing the outputs of '{}'".format(paths[i]))
+            results[i] = (result, list(written) if rank == 0 else [])
+    finally:
+        if kept is not None:
+            kept[1].close()
+        if track is not None:
+            track.close()
+        if own_ctx:
+            ctx.close()
+    return [FileResult(p, b, *results[i], None) if i in results else FileResult(p, b, None, [], errors[i])
+            for i, (p, b) in enumerate(zip(paths, bases))]
+
+
+def _basenames(paths, names) -> List[str]:
+    """The base name of every file's outputs (pymasc.py:172-177), checked."""
+    names = list(names or [])
+    if len(names) > len(paths):
+        raise ValueError("{} names for {} input files".format(len(names), len(paths)))
+    out = []
+    for f, n in zip_longest(paths, names):
+        if n is None:
+            n = Path(f).stem
+        elif not n or os.sep in n or (os.altsep and os.altsep in n) or n in (".", ".."):
+            raise ValueError("an output name is a file name: {!r}".format(n))
+        out.append(str(n))
+    seen = {}
+    for f, n in zip(paths, out):
+        if n in seen:
+            raise ValueError("'{}' and '{}' would both write '{}_*': give them different names".format(seen[n], f, n))
+        seen[n] = f
+    return out
+
+
+def _warn_existing(outdir, bases, has_track, skip_ncc, stats):
+    """prepare_output's warning (pymasc.py:178-182) for every output about to be replaced."""
+    suffixes = [s for s, on in (("_cc.tab", not (has_track and skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
+                                ("_stats.tab", stats)) if on]
+    for b in bases:
+        for suffix in suffixes:
+            path = Path(outdir) / (b + suffix)
+            if path.exists():
+                logger.warning("Existing file '{}' will be overwritten.".format(path))
+
+
+def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_shift, device):
+    """Steps 1 and 2 of run_files: the files that open and keep a chromosome, then the common read length.  Fills ``errors``
+    with the exception of every file skipped; returns (read length or None when no file is left, (index, device reader) or
+    None).  ``device``: the GPU of the device reader the estimates are made on, None for the host reader."""
+    for i, p in enumerate(paths):
+        try:
+            with open_header(p) as r:
+                if not r.references:
+                    raise ValueError("File has no sequences defined.")
+                filter_references(r.references, chromfilter)
+        except NoTargetChromosomesError as e:
+            logger.error("Check your -i/--include-chrom and/or -e/--exclude-chrom options.")
+            errors[i] = e
+        except (OSError, ValueError) as e:
+            logger.error("Failed to open file '{}'".format(p))
+            logger.error(str(e))
+            errors[i] = e
+    live = [i for i, e in enumerate(errors) if e is None]
+    if not live:
+        return None, None
+    if read_len is not None:
+        return int(read_len), None
+    logger.info("Check read length: Get {} from read length distribution".format(str(esttype).lower()))
+    lengths, kept = [], None
+    for i in live:
+        logger.info("Check read length... : {}".format(paths[i]))
+        if device is None:
+            r = open_alignments(paths[i], False, index=False)       # the whole file: the host reader without its index
+        else:
+            r = open_alignments(paths[i], True, device=device)
+        estimated = False
+        try:
+            lengths.append(readlen.estimate_from_reader(r, esttype, mapq_criteria, max_shift))
+            estimated = True
+        except ValueError as e:
+            logger.error(str(e))
+            errors[i] = e
+        finally:
+            if estimated and device is not None and len(live) == 1:
+                kept = (i, r)
+            else:
+                r.close()
+    if not lengths:
+        return None, None
+    if len(set(lengths)) != 1:
+        logger.warning("There are multiple read length candidates. Use max length "
+                       "({}) for MSCC calculation.".format(max(lengths)))
+    return max(lengths), kept
+
+
+def _portable(error: BaseException) -> BaseException:
+    """``error`` when it survives a pickle round trip (the ranks' broadcast), else a RuntimeError that says what it was."""
+    try:
+        back = pickle.loads(pickle.dumps(error))
+        if type(back) is type(error) and str(back) == str(error):
+            return error
+    except Exception:
+        pass
+    return RuntimeError("{}: {}".format(type(error).__name__, error))
+
+
+def _unsorted_on_every_rank(error: BaseException, world: int) -> Optional[ReadUnsortedError]:
+    """The ReadUnsortedError that skips a file on every rank, or None when ``error`` propagates on every rank.  Several ranks:
+    the decision is taken from ``failed_ranks``, which sharding.gather_chromosome_results attaches to what it raises on every
+    rank (the failing rank's own exception, a RuntimeError on the others) and which is the same list on every rank -- skip when
+    every failing rank's reads were unsorted.  An exception that did not come through that gather propagates."""
+    if world == 1:
+        return error if isinstance(error, ReadUnsortedError) else None
+    failed = getattr(error, "failed_ranks", None)
+    if not failed or any(kind != ReadUnsortedError.__name__ for _rank, kind, _msg in failed):
+        return None
+    return error if isinstance(error, ReadUnsortedError) else ReadUnsortedError(failed[0][2])

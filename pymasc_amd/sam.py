@@ -69,11 +69,16 @@ class SamReader(NativeReader):
     """A SAM file (plain or BGZF) as batches of filtered read arrays, like ``pymasc_amd.bam.BamReader``; no index."""
     _CLOSE = "pmx_sam_close"
 
-    def __init__(self, path, threads: int = 0):
+    def __init__(self, path, threads: int = 0, header_only: bool = False):
+        """``header_only``: read the header and no record (pmx_sam_open_header) -- ``references``, ``lengths`` and
+        ``header_text`` only; a plain file is read to its first record line, a BGZF one inflated until it."""
         self._L = load_io_library()
         self.path = os.fspath(path)
         h = ctypes.c_void_p()
-        rc = self._L.pmx_sam_open(self.path.encode(), int(threads), ctypes.byref(h))
+        if header_only:
+            rc = self._L.pmx_sam_open_header(self.path.encode(), ctypes.byref(h))
+        else:
+            rc = self._L.pmx_sam_open(self.path.encode(), int(threads), ctypes.byref(h))
         if rc:
             _raise(rc)
         self._h = h

@@ -163,22 +163,25 @@ def gather_chromosome_results(local: Dict[str, object], order: Sequence[str], gr
     worker.py:234); the fixed-shape tensor exchange used by the benchmark is ``exchange_results`` above.
     ``error``: this rank failed -- every rank learns about it from the same collective and raises, instead of the
     healthy ranks waiting for a peer that never arrives (the reference's '__ERROR__' report, worker.py:91-99 ->
-    handler/calc.py:205-206)."""
+    handler/calc.py:205-206).  Several ranks: the exception raised on every rank -- the failing rank's own, a RuntimeError
+    on the others -- carries ``failed_ranks``, the same list ``[(rank, exception type name, message), ...]`` on every rank,
+    so that callers can take one decision on all of them without another collective."""
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         if error is not None:
             raise error
-        parts = [(None, local)]
+        parts = [(None, local, None)]
     else:
         parts = [None] * dist.get_world_size(group)
-        mine = (None if error is None else "{}: {}".format(type(error).__name__, error), None if error else local)
+        mine = (None, local, None) if error is None else (str(error), None, type(error).__name__)
         dist.all_gather_object(parts, mine, group=group)
-    failed = [(r, p[0]) for r, p in enumerate(parts) if p[0] is not None]
+    failed = [(r, p[2], p[0]) for r, p in enumerate(parts) if p[2] is not None]
     if failed:
-        if error is not None:
-            raise error                                    # the failing rank re-raises its own exception (type kept)
-        raise RuntimeError("Worker error on rank(s): " + "; ".join("{} [{}]".format(r, msg) for r, msg in failed))
+        if error is None:
+            error = RuntimeError("Worker error on rank(s): " + "; ".join("{} [{}: {}]".format(*f) for f in failed))
+        error.failed_ranks = failed
+        raise error                                        # the failing rank re-raises its own exception (type kept)
     merged: Dict[str, object] = {}
-    for _err, p in parts:
+    for _err, p, _type in parts:
         for chrom, res in p.items():
             if chrom in merged:
                 raise RuntimeError("chromosome {} was calculated by two ranks".format(chrom))
@@ -209,7 +212,8 @@ def reconcile_chromosome_sizes(bam_sizes: Dict[str, int], external_sizes: Dict[s
 
 def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, bigwig_path=None,
                 references: Sequence[str] = None, skip_ncc: bool = False, device: int = None, context=None,
-                chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None, chromfilter=None):
+                chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None, chromfilter=None,
+                track=None):
     """BAM (+ BigWig) -> genome-wide result on every rank; chromosomes LPT-sharded over the ranks by length.
 
     Launch: one process per GPU under ``torch.distributed`` (torchrun, or pymasc_amd.launch.spawn_ranks), the process
@@ -233,7 +237,11 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     With the device reader and a .bai next to the BAM file, a rank of several -- or the only rank when ``references`` or
     ``chromfilter`` choose the chromosomes -- reads the header, takes its share and reads, copies and inflates only the BGZF
     members of that share (the device reader's ``select``); without an index, or with a ``bam`` given, the path
-    is the whole-file one above."""
+    is the whole-file one above.
+    ``track``: a reader of ``bigwig_path`` the caller has already opened (pipeline.run_files opens the track once for all its
+    files), used instead of opening one and left open, like ``bam``.
+    With a ``context`` given, the calculator still gives its bit-vectors back to the context's pool and frees its result arena
+    before this returns (``CCHipCalculator.close`` never closes a context it does not own)."""
     from .calculator import CCHipCalculator
     from .chromfilter import filter_references
     from .inputs import default_device_ingest, find_index, open_alignments, open_track
@@ -260,7 +268,7 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     # 
     indexed = (device_ingest and bam is None and (world > 1 or references is not None or chromfilter is not None)
                and not is_sam(bam_path) and find_index(bam_path) is not None)
-    reader, bw = bam, None          # the caller's reader is used, not closed
+    reader, bw = bam, None          # the caller's readers are used, not closed
     try:
         if reader is None:
             reader = open_alignments(bam_path, device_ingest, dev, references=[] if indexed else None)
@@ -270,7 +278,7 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
             names = [n for n in reader.references if references is None or n in set(references)]
         lengths = dict(zip(reader.references, reader.lengths))
         if bigwig_path is not None:     # with device ingest the track is decoded on the GPU too: its intervals stay in HBM
-            bw = open_track(bigwig_path, device_ingest, dev)
+            bw = track if track is not None else open_track(bigwig_path, device_ingest, dev)
             # the track's chromosome sizes win where they are longer (handler/calc.py:100-115)
             lengths.update(reconcile_chromosome_sizes({n: lengths[n] for n in names}, bw.chromsizes))
         mine = [names[i] for i in sorted(lpt_assign([lengths[n] for n in names], world)[rank])]
@@ -288,14 +296,13 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
                 reader.feed(calc, mapq_criteria, references=mine)
                 local = {c: calc.get_result(c) for c in mine}
             finally:
-                if context is None:
-                    calc.close()
+                calc.close()
     except Exception as e:              # surfaced on every rank by the gather below
         if not on or world == 1:
             raise
         error = e
     finally:
-        if bw is not None:
+        if bw is not None and bw is not track:
             bw.close()
         if reader is not bam:
             reader.close()
