@@ -1,0 +1,305 @@
+"""The ``pymasc`` command: ``python -m pymasc_amd reads... -m track.bw -d 1000 ...``.
+
+The options, their defaults and their checks are PyMaSC's (utils/parsearg.py ``get_pymasc_parser``, pymasc.py ``_parse_args``);
+the run is one ``pipeline.run_files`` call with ``stats=True``.  ``-p N`` is N ranks, one per GPU: without a
+launcher the command starts them itself (``launch.spawn_ranks``) and never touches a GPU; under torchrun (``WORLD_SIZE`` set)
+each process is one rank.
+
+Parsing, ``--help``, ``--version``, argument errors and the ``-p N`` parent import neither torch nor the native libraries:
+``pipeline`` is imported only in the process that does the work.
+"""
+from __future__ import annotations
+
+import argparse
+import logging
+import os
+import signal
+import sys
+from itertools import zip_longest
+from pathlib import Path
+
+from . import __version__, launch
+
+logger = logging.getLogger(__name__)
+
+READLEN_ESTIMATORS = ("MEAN", "MEDIAN", "MODE", "MIN", "MAX")     # pymasc_amd.readlen.ESTIMATORS
+LOG_LEVELS = ("DEBUG", "INFO", "WARNING", "ERROR", "CRITICAL")
+NO_FILE_LEFT = "no input file is left to run"                     # pipeline.run_files' ValueError after step 2
+TRACK_ERRORS = ("BWIOError", "JSONIOError")
+DIST_BACKEND_ENV = "PMX_DIST_BACKEND"
+_log_handler = None                 # the root handler setup_logging installed
+
+
+# ---- parser pieces shared with pymasc_amd.precalc ---------------------------------------------------------------------
+class _NaturalNumber(argparse.Action):
+    """An int option that must be at least 1: an argparse error (exit 2) otherwise."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        if values < 1:
+            parser.error("argument {} must be > 0.".format("/".join(self.option_strings)))
+        setattr(namespace, self.dest, values)
+
+
+class _LogLevel(argparse.Action):
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, getattr(logging, values))
+
+
+class _Color(argparse.Action):
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values == "TRUE")
+
+
+def _chromfilter_action(include: bool):
+    """-i / -e: append ``(include, [patterns])`` to the one ordered ``chromfilter`` list (pymasc_amd.chromfilter)."""
+    class _Append(argparse.Action):
+        def __call__(self, parser, namespace, values, option_string=None):
+            groups = list(getattr(namespace, self.dest) or [])
+            groups.append((include, list(values)))
+            setattr(namespace, self.dest, groups)
+    return _Append
+
+
+def shared_options(parser: argparse.ArgumentParser) -> None:
+    """-v, --disable-progress, --color and --version: the options both commands take."""
+    parser.add_argument("-v", "--log-level", type=str.upper, choices=LOG_LEVELS, default=logging.INFO, action=_LogLevel,
+                        help="lowest level of the messages printed on stderr (default INFO)")
+    parser.add_argument("--disable-progress", action="store_true", help="accepted for compatibility; nothing to disable")
+    parser.add_argument("--color", type=str.upper, choices=("TRUE", "FALSE"), default=True, action=_Color,
+                        help="accepted for compatibility; messages are printed without colour")
+    parser.add_argument("--version", action="version", version="pymasc_amd " + __version__)
+
+
+def ranks_option(group) -> None:
+    group.add_argument("-p", "--process", type=int, default=1, action=_NaturalNumber,
+                       help="how many ranks to run, each on a GPU of its own (default 1)")
+
+
+def track_options(group) -> None:
+    group.add_argument("-m", "--mappability", metavar="BIGWIG", type=Path,
+                       help="mappability track; positions with a value of at least 1 count as mappable")
+    group.add_argument("--mappability-stats", metavar="JSON", type=Path,
+                       help="where the mappable-length cache is read and written (default: the track's path with "
+                            "_mappability.json in place of its extension)")
+
+
+def shift_option(group) -> None:
+    group.add_argument("-d", "--max-shift", type=int, default=1000, action=_NaturalNumber,
+                       help="largest strand shift, in bases, the correlation is computed for (default 1000)")
+
+
+def setup_logging(level: int, rank: int = 0) -> None:
+    """One stderr handler on the root logger (replaced, not added to, when called again); ranks other than 0 log ERROR and
+    above only, so that a run over several ranks prints one set of messages."""
+    global _log_handler
+    root = logging.getLogger()
+    if _log_handler is not None:
+        root.removeHandler(_log_handler)
+    _log_handler = logging.StreamHandler(sys.stderr)
+    _log_handler.setFormatter(logging.Formatter("[%(asctime)s | %(levelname)s] %(name)s : %(message)s", "%Y-%m-%d %H:%M:%S"))
+    root.addHandler(_log_handler)
+    root.setLevel(level if rank == 0 else max(level, logging.ERROR))
+
+
+def log_version() -> None:
+    logger.info("pymasc_amd version {} with Python{}.{}.{}".format(__version__, *sys.version_info[:3]))
+
+
+def readable_track(path) -> bool:
+    """The -m file is a readable file; logged as the reference's BWIOError is when it is not."""
+    p = os.fspath(path)
+    if os.path.isfile(p) and os.access(p, os.R_OK):
+        return True
+    reason = "no such file" if not os.path.exists(p) else ("not a file" if not os.path.isfile(p) else "not readable")
+    logger.critical("Cannot read the mappability track '{}': {}".format(p, reason))
+    return False
+
+
+# ---- pymasc -----------------------------------------------------------------------------------------------------------
+def get_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(
+        prog="python -m pymasc_amd",
+        description="Strand cross-correlation of aligned reads, naive and mappability-masked, on AMD Instinct GPUs:\n"
+                    "the _cc, _mscc, _nreads and _stats tables of every input file.",
+        formatter_class=argparse.RawDescriptionHelpFormatter)
+    shared_options(parser)
+
+    run = parser.add_argument_group("how to run")
+    ranks_option(run)
+    run.add_argument("--successive", action="store_true",
+                     help="accepted for compatibility; the bit-vector path gives the same integers")
+    run.add_argument("--skip-ncc", action="store_true",
+                     help="write only the mappability-masked correlation (needs -m)")
+    run.add_argument("--skip-plots", action="store_true",
+                     help="do not log the missing figure of each file; no figure is ever drawn")
+
+    reads = parser.add_argument_group("reads")
+    reads.add_argument("reads", nargs="+", type=Path, help="BAM or SAM files (plain or bgzip'd), sorted by coordinate")
+    reads.add_argument("-r", "--read-length", type=int, action=_NaturalNumber,
+                       help="use this read length instead of estimating one from the files")
+    reads.add_argument("--readlen-estimator", type=str.upper, default="MEDIAN", choices=READLEN_ESTIMATORS,
+                       help="statistic of the observed read lengths taken as the estimate, in any case (default MEDIAN)")
+    reads.add_argument("-q", "--mapq", type=int, default=1,
+                       help="reads with a mapping quality below this are left out (default 1)")
+    reads.add_argument("-i", "--include-chrom", nargs="+", dest="chromfilter", metavar="PATTERN",
+                       action=_chromfilter_action(True),
+                       help="keep the chromosomes matching these fnmatch patterns (case-sensitive); -i and -e apply in "
+                            "the order given and may repeat")
+    reads.add_argument("-e", "--exclude-chrom", nargs="+", dest="chromfilter", metavar="PATTERN",
+                       action=_chromfilter_action(False),
+                       help="drop the chromosomes matching these fnmatch patterns (case-sensitive); see -i")
+
+    track_options(parser.add_argument_group("mappability"))
+
+    fit = parser.add_argument_group("correlation and statistics")
+    shift_option(fit)
+    fit.add_argument("-l", "--library-length", type=int, action=_NaturalNumber,
+                     help="fragment length you expect; _stats.tab reports the correlation there too")
+    fit.add_argument("--chi2-pval", type=float, default=0.05,
+                     help="significance level of the test for unequal forward and reverse read counts (default 0.05)")
+    fit.add_argument("-w", "--smooth-window", type=int, default=15, action=_NaturalNumber,
+                     help="width of the moving average applied to the masked curve before its peak is sought (default 15)")
+    fit.add_argument("--mask-size", type=int, default=5,
+                     help="when the peak lies this close to the read length, hide that neighbourhood and look again; "
+                          "below 1 turns it off (default 5)")
+    fit.add_argument("--bg-avr-width", type=int, default=50, action=_NaturalNumber,
+                     help="the background level is the median over this many of the largest shifts (default 50)")
+
+    out = parser.add_argument_group("outputs")
+    out.add_argument("-n", "--name", nargs="*", default=[],
+                     help="base names of the outputs, paired with the files in order (default: each file's stem)")
+    out.add_argument("-o", "--outdir", default=".", type=Path, help="directory the tables are written to (default .)")
+    return parser
+
+
+def check_names(paths, names) -> None:
+    """pipeline._basenames' rules, without importing pipeline (it brings torch): ValueError for more names than files, an
+    empty name or one with a path separator, and two files with the same base name."""
+    names = list(names or [])
+    if len(names) > len(paths):
+        raise ValueError("{} names for {} input files".format(len(names), len(paths)))
+    seen = {}
+    for f, n in zip_longest(paths, names):
+        if n is None:
+            n = Path(f).stem
+        elif not n or os.sep in n or (os.altsep and os.altsep in n) or n in (".", ".."):
+            raise ValueError("an output name is a file name: {!r}".format(n))
+        if n in seen:
+            raise ValueError("'{}' and '{}' would both write '{}_*': give them different names".format(seen[n], f, n))
+        seen[n] = f
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """The options, with every check that needs no file and no log (exit 2 on an error)."""
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    if args.skip_ncc and args.mappability is None:
+        parser.error("argument --skip-ncc: needs a track (-m/--mappability)")
+    try:
+        check_names([str(p) for p in args.reads], args.name)
+    except ValueError as e:
+        parser.error("argument -n/--name: {}".format(e))
+    return args
+
+
+def _raise_on_sigterm(signum, frame):
+    raise SystemExit(128 + signum)
+
+
+def main(argv=None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    try:
+        args = parse_args(argv)
+    except SystemExit as e:         # --help, --version, argument errors
+        return e.code if isinstance(e.code, int) else 2
+    rank = int(os.environ.get("RANK", "0"))
+    setup_logging(args.log_level, rank)
+    if args.mappability is not None and not readable_track(args.mappability):
+        return 1
+    if launch.needs_spawn(args.process):
+        # the ranks are this command again, in fresh processes; a SIGTERM here (a time limit) becomes SystemExit, and
+        # spawn_ranks' cleanup stops the ranks it started before the parent goes
+        signal.signal(signal.SIGTERM, _raise_on_sigterm)
+        return launch.spawn_ranks([sys.executable, "-m", "pymasc_amd", *argv], args.process)
+    return _rank_main(args, rank)
+
+
+def _rank_main(args, rank: int) -> int:
+    log_version()
+    if args.mappability_stats is not None and args.mappability_stats == args.mappability:
+        args.mappability_stats = None
+    if args.library_length is not None and args.library_length > args.max_shift:
+        logger.error("Specified expected library length > max shift. Ignore expected length setting.")
+        args.library_length = None
+    if args.successive:
+        logger.info("--successive: the bit-vector path computes the same integers as the successive algorithm; "
+                    "running it.")
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if "WORLD_SIZE" in os.environ and args.process != world:
+        logger.warning("-p {} but WORLD_SIZE={}: using WORLD_SIZE.".format(args.process, world))
+    if world <= 1:
+        return _run(args, None, rank)
+
+    backend = os.environ.get(DIST_BACKEND_ENV, "nccl")
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+    import torch
+    import torch.distributed as dist
+    ndev = torch.cuda.device_count()
+    need = local_world if backend == "nccl" else 1          # gloo: the ranks may share devices (LOCAL_RANK % count)
+    if ndev < need:                 # the same decision on every rank of the node, taken before the rendezvous
+        logger.error("{} ranks on this node with the {} backend need {} GPU(s); {} visible."
+                     "".format(local_world, backend, need, ndev))
+        return 1
+    device = local_rank if backend == "nccl" else local_rank % ndev
+    if backend == "nccl":
+        torch.cuda.set_device(device)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", device))
+    else:
+        dist.init_process_group(backend)
+    try:
+        return _run(args, device, rank)
+    finally:
+        dist.destroy_process_group()
+
+
+def _rank0_track_error(error: BaseException) -> bool:
+    """The RuntimeError that sharding.on_rank0 raises on the other ranks when rank 0's track or cache failed."""
+    return isinstance(error, RuntimeError) and any("failed on rank 0 [{}:".format(n) in str(error) for n in TRACK_ERRORS)
+
+
+def _run(args, device, rank: int) -> int:
+    from . import pipeline
+    from .mappability import BWIOError, JSONIOError
+    try:
+        results = pipeline.run_files(
+            [str(p) for p in args.reads], str(args.outdir), args.max_shift, read_len=args.read_length,
+            mapq_criteria=args.mapq,
+            mappability_path=None if args.mappability is None else str(args.mappability),
+            mappability_stats_path=None if args.mappability_stats is None else str(args.mappability_stats),
+            skip_ncc=args.skip_ncc, device=device, readlen_estimator=args.readlen_estimator,
+            chromfilter=args.chromfilter, stats=True, library_length=args.library_length,
+            smooth_window=args.smooth_window, mask_size=args.mask_size, bg_avr_width=args.bg_avr_width,
+            chi2_pval=args.chi2_pval, names=args.name or None)
+    except (BWIOError, JSONIOError):
+        return 1                    # logged where it was raised (mappability.MappabilityStats)
+    except RuntimeError as e:
+        if rank == 0 or not _rank0_track_error(e):
+            raise
+        logger.debug(str(e))        # rank 0 logged the cause and exits 1 too
+        return 1
+    except ValueError as e:
+        if str(e) != NO_FILE_LEFT:
+            raise
+        if rank == 0:               # (every rank raises it: one message)
+            logger.error("No input file could be run.")
+        return 1
+    if not args.skip_plots:
+        for f in results:
+            if f.written:           # rank 0, a file that ran
+                logger.error("Skip output plots '{}'".format(Path(args.outdir) / (f.basename + ".pdf")))
+    if not any(f.error is None for f in results):
+        if rank == 0:
+            logger.error("No input file could be run.")
+        return 1
+    return 0
