@@ -30,7 +30,7 @@ DIST_BACKEND_ENV = "PMX_DIST_BACKEND"
 _log_handler = None                 # the root handler setup_logging installed
 
 
-# ---- parser pieces shared with pymasc_amd.precalc ---------------------------------------------------------------------
+# ---- parser pieces shared with pymasc_amd.precalc and pymasc_amd.plot ------------------------------------------------
 class _NaturalNumber(argparse.Action):
     """An int option that must be at least 1: an argparse error (exit 2) otherwise."""
 
@@ -61,7 +61,7 @@ def _chromfilter_action(include: bool):
 
 
 def shared_options(parser: argparse.ArgumentParser) -> None:
-    """-v, --disable-progress, --color and --version: the options both commands take."""
+    """-v, --disable-progress, --color and --version: the options every command takes."""
     parser.add_argument("-v", "--log-level", type=str.upper, choices=LOG_LEVELS, default=logging.INFO, action=_LogLevel,
                         help="lowest level of the messages printed on stderr (default INFO)")
     parser.add_argument("--disable-progress", action="store_true", help="accepted for compatibility; nothing to disable")
@@ -86,6 +86,33 @@ def track_options(group) -> None:
 def shift_option(group) -> None:
     group.add_argument("-d", "--max-shift", type=int, default=1000, action=_NaturalNumber,
                        help="largest strand shift, in bases, the correlation is computed for (default 1000)")
+
+
+def stats_options(group) -> None:
+    """-l, --chi2-pval, -w, --mask-size and --bg-avr-width: the options of ``stats.genome_wide_stats``."""
+    group.add_argument("-l", "--library-length", type=int, action=_NaturalNumber,
+                       help="fragment length you expect; _stats.tab reports the correlation there too")
+    group.add_argument("--chi2-pval", type=float, default=0.05,
+                       help="significance level of the test for unequal forward and reverse read counts (default 0.05)")
+    group.add_argument("-w", "--smooth-window", type=int, default=15, action=_NaturalNumber,
+                       help="width of the moving average applied to the masked curve before its peak is sought "
+                            "(default 15)")
+    group.add_argument("--mask-size", type=int, default=5,
+                       help="when the peak lies this close to the read length, hide that neighbourhood and look again; "
+                            "below 1 turns it off (default 5)")
+    group.add_argument("--bg-avr-width", type=int, default=50, action=_NaturalNumber,
+                       help="the background level is the median over this many of the largest shifts (default 50)")
+
+
+def chromfilter_options(group) -> None:
+    """-i / -e, appending to one ordered ``chromfilter`` list."""
+    group.add_argument("-i", "--include-chrom", nargs="+", dest="chromfilter", metavar="PATTERN",
+                       action=_chromfilter_action(True),
+                       help="keep the chromosomes matching these fnmatch patterns (case-sensitive); -i and -e apply in "
+                            "the order given and may repeat")
+    group.add_argument("-e", "--exclude-chrom", nargs="+", dest="chromfilter", metavar="PATTERN",
+                       action=_chromfilter_action(False),
+                       help="drop the chromosomes matching these fnmatch patterns (case-sensitive); see -i")
 
 
 def setup_logging(level: int, rank: int = 0) -> None:
@@ -141,29 +168,13 @@ def get_parser() -> argparse.ArgumentParser:
                        help="statistic of the observed read lengths taken as the estimate, in any case (default MEDIAN)")
     reads.add_argument("-q", "--mapq", type=int, default=1,
                        help="reads with a mapping quality below this are left out (default 1)")
-    reads.add_argument("-i", "--include-chrom", nargs="+", dest="chromfilter", metavar="PATTERN",
-                       action=_chromfilter_action(True),
-                       help="keep the chromosomes matching these fnmatch patterns (case-sensitive); -i and -e apply in "
-                            "the order given and may repeat")
-    reads.add_argument("-e", "--exclude-chrom", nargs="+", dest="chromfilter", metavar="PATTERN",
-                       action=_chromfilter_action(False),
-                       help="drop the chromosomes matching these fnmatch patterns (case-sensitive); see -i")
+    chromfilter_options(reads)
 
     track_options(parser.add_argument_group("mappability"))
 
     fit = parser.add_argument_group("correlation and statistics")
     shift_option(fit)
-    fit.add_argument("-l", "--library-length", type=int, action=_NaturalNumber,
-                     help="fragment length you expect; _stats.tab reports the correlation there too")
-    fit.add_argument("--chi2-pval", type=float, default=0.05,
-                     help="significance level of the test for unequal forward and reverse read counts (default 0.05)")
-    fit.add_argument("-w", "--smooth-window", type=int, default=15, action=_NaturalNumber,
-                     help="width of the moving average applied to the masked curve before its peak is sought (default 15)")
-    fit.add_argument("--mask-size", type=int, default=5,
-                     help="when the peak lies this close to the read length, hide that neighbourhood and look again; "
-                          "below 1 turns it off (default 5)")
-    fit.add_argument("--bg-avr-width", type=int, default=50, action=_NaturalNumber,
-                     help="the background level is the median over this many of the largest shifts (default 50)")
+    stats_options(fit)
 
     out = parser.add_argument_group("outputs")
     out.add_argument("-n", "--name", nargs="*", default=[],

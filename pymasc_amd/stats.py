@@ -286,14 +286,17 @@ def _chrom_stats(kind, chroms, p: Params):
     return out, empty_len
 
 
-def _whole(kind, chroms: Mapping[str, CurveStats], empty_len: int, p: Params, warn: bool, est_lib_len=None):
+def _whole(kind, chroms: Mapping[str, CurveStats], empty_len: int, p: Params, warn: bool, est_lib_len=None, reads=None):
     if not chroms:
         return None
     rows = list(chroms.values())
     merged, lo, hi = merge_cc([s.genomelen_repr for s in rows], [s.cc for s in rows])
     glen = np.sum(np.asarray([s.genomelen for s in rows], dtype=np.int64), axis=0)
-    fw = np.sum(np.asarray([s.forward_reads for s in rows], dtype=np.int64), axis=0)
-    rv = np.sum(np.asarray([s.reverse_reads for s in rows], dtype=np.int64), axis=0)
+    if reads is not None:
+        fw, rv = (np.asarray(x, dtype=np.int64) for x in reads)
+    else:
+        fw = np.sum(np.asarray([s.forward_reads for s in rows], dtype=np.int64), axis=0)
+        rv = np.sum(np.asarray([s.reverse_reads for s in rows], dtype=np.int64), axis=0)
     if kind == "NCC":                # chromosomes without reads count towards NCC's genome length only
         glen, fw, rv = int(glen) + empty_len, int(fw), int(rv)
     return curve_stats(kind, merged, glen, fw, rv, p, warn, est_lib_len, (lo, hi))
@@ -330,12 +333,14 @@ def check_params(read_len, library_length=None, smooth_window=15, max_shift=None
 
 def genome_wide_stats(result, read_len: int, library_length: Optional[int] = None, smooth_window: int = 15,
                       bg_avr_width: int = 50, mask_size: int = 5, chi2_pval: float = 0.05,
-                      output_warnings: bool = True) -> GenomeStats:
+                      output_warnings: bool = True, mscc_reads=None) -> GenomeStats:
     """Statistics of a genome-wide result: ``NCCGenomeWideResult``, ``MSCCGenomeWideResult`` or ``BothGenomeWideResult``,
     the stand-alone dataclasses or the reference's own classes (pymasc_amd.result binds whichever is present).
     ``output_warnings``: the genome-wide curves' warnings (background above the first shifts, estimate near the read
     length); the per-chromosome curves never give them.  Raises ReadsTooFew when a genome-wide curve has no forward or
-    no reverse read (for MSCC only when there is no NCC curve; with one, it is a warning)."""
+    no reverse read (for MSCC only when there is no NCC curve; with one, it is a warning).  ``mscc_reads``: the genome-wide
+    (forward, reverse) mappable read counts by shift, in place of the sums over the chromosomes, for a result whose
+    per-chromosome counts are not known (a ``_nreads.tab`` written without MSCC columns, as ``--skip-ncc`` writes it)."""
     check_params(read_len, library_length, smooth_window)
     p = Params(int(read_len), None if library_length is None else int(library_length), int(smooth_window),
                int(bg_avr_width), int(mask_size), float(chi2_pval))
@@ -351,7 +356,7 @@ def genome_wide_stats(result, read_len: int, library_length: Optional[int] = Non
     mscc, whole_mscc = {}, None
     if mscc_rows is not None:
         mscc, empty = _chrom_stats("MSCC", mscc_rows, p)
-        whole_mscc = _whole("MSCC", mscc, empty, p, output_warnings)
+        whole_mscc = _whole("MSCC", mscc, empty, p, output_warnings, reads=mscc_reads)
     ncc, whole_ncc = {}, None
     if ncc_rows is not None:
         ncc, empty = _chrom_stats("NCC", ncc_rows, p)

@@ -234,8 +234,8 @@ def load_cc_table(path) -> Dict[str, List[float]]:
     return cols
 
 
-def load_nreads_table(path):
-    """(forward, reverse, mappable_forward, mappable_reverse) keyed by chromosome, ``whole`` removed
+def load_nreads_table(path, whole: bool = False):
+    """(forward, reverse, mappable_forward, mappable_reverse) keyed by chromosome, ``whole`` removed unless ``whole``
     (table.py:252-283, 336-366).  Raises KeyError when the file holds no pair at all."""
     with open(path, newline="") as fp:
         rows = list(csv.reader(fp, dialect="excel-tab"))
@@ -254,8 +254,9 @@ def load_nreads_table(path):
             else:
                 mfw.setdefault(key, []).append(f)
                 mrv.setdefault(key, []).append(r)
-    for d in (fw, rv, mfw, mrv):
-        d.pop("whole", None)
+    if not whole:
+        for d in (fw, rv, mfw, mrv):
+            d.pop("whole", None)
     if not (fw or rv or mfw or mrv):
         raise KeyError("nothing to load from {}".format(path))
     return fw, rv, mfw, mrv
