@@ -77,6 +77,29 @@ int pmx_dbam_select(pmx_dbam *b, const int32_t *refs, int32_t n);
  * [5] parse + the last filter) and inflated (the text) work on it; pmx_dbam_select returns PMX_DBAM_ERR_INVALID (no index). */
 int pmx_dsam_open(const char *path, int device, int nthreads, pmx_dbam **out);
 
+/* Stream reading (version >= 4): `fd` is read in BOUNDED WINDOWS -- a pipe, a FIFO, a socket, a character
+ * device or a regular file; it is never sized (fstat) or seeked, and the caller keeps it (it is not closed).  The format comes
+ * from the first bytes: BGZF whose first member inflates to "BAM\1" is BAM, to text is BGZF SAM; text starting with '@' is plain
+ * SAM; gzip that is not BGZF is PMX_DBAM_ERR_FORMAT.  The open reads and inflates the first window(s), as far as the header
+ * needs; nref / ref_name / ref_len / header_text work at once.  window_bytes: compressed bytes per window (0: 64 MiB); a window
+ * is whole BGZF members within window_bytes compressed AND 4 * window_bytes inflated (at least one member), or that many bytes
+ * of plain text.  nthreads is unused (one reader thread reads ahead).  Device memory depends on window_bytes only: the buffers
+ * grow only for a record or line longer than a window. */
+int pmx_dbam_open_stream(int fd, int device, int nthreads, uint64_t window_bytes, pmx_dbam **out);
+/* Makes the next window current: decode, device_arrays, runs, fetch, counters, readlen_hist and inflated then work on it (its
+ * records: from the record its first byte starts -- the first after the header, or the one the last window carried -- up to the
+ * last record that ends inside it; the rest is carried to the front of the next window by a device-to-device copy).  While the
+ * caller works on this window, a host thread reads the next one from fd.  Returns the window's record bytes (> 0), 0 at the end
+ * of the stream, or a negative error code: a stream that ends inside a member or a record, a CRC / ISIZE / DEFLATE error, a
+ * malformed record or SAM line are PMX_DBAM_ERR_FORMAT, with the messages of pmx_dbam_open / pmx_dsam_open; a read error is
+ * PMX_DBAM_ERR_OPEN.  readlen_hist's first-occurrence keys are offsets in the whole inflated stream. */
+int64_t pmx_dbam_stream_next(pmx_dbam *b);
+/* out = {windows made current, compressed bytes taken from fd, largest carried tail (bytes), peak device bytes the handle has
+ * held between calls (window buffers, compressed window, member table, record chain, kept-record arrays, histogram and SAM
+ * line tables; not pmx_dbam_runs' transient table), window_bytes, inflated budget}.  PMX_DBAM_ERR_INVALID for a handle that
+ * was not opened by pmx_dbam_open_stream. */
+int pmx_dbam_stream_info(const pmx_dbam *b, uint64_t out[6]);
+
 /* Reference dictionary = pysam's AlignmentFile.references / .lengths (reader/bam.py:137-153). */
 int32_t pmx_dbam_nref(const pmx_dbam *b);
 const char *pmx_dbam_ref_name(const pmx_dbam *b, int32_t i);

@@ -27,6 +27,7 @@ INGEST_EXPORTS = [
     "pmx_dbam_ref_len", "pmx_dbam_header_text", "pmx_dbam_decode", "pmx_dbam_device_arrays", "pmx_dbam_fetch",
     "pmx_dbam_runs", "pmx_dbam_counters", "pmx_dbam_timings", "pmx_dbam_inflated", "pmx_dbam_readlen_hist",
     "pmx_dbam_readlen_counters", "pmx_dbam_open_indexed", "pmx_dbam_select", "pmx_dsam_open",
+    "pmx_dbam_open_stream", "pmx_dbam_stream_next", "pmx_dbam_stream_info",
     "pmx_dbw_open", "pmx_dbw_close", "pmx_dbw_nchrom", "pmx_dbw_chrom_name", "pmx_dbw_chrom_len", "pmx_dbw_fetch", "pmx_dbw_device_arrays",
     "pmx_dbw_sorted", "pmx_dbw_copy",
 ]
@@ -56,6 +57,12 @@ def load_ingest_library():
     L.pmx_dbam_open_indexed.restype = ctypes.c_int
     L.pmx_dsam_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     L.pmx_dsam_open.restype = ctypes.c_int
+    L.pmx_dbam_open_stream.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, u64, ctypes.POINTER(vp)]
+    L.pmx_dbam_open_stream.restype = ctypes.c_int
+    L.pmx_dbam_stream_next.argtypes = [vp]
+    L.pmx_dbam_stream_next.restype = i64
+    L.pmx_dbam_stream_info.argtypes = [vp, ctypes.POINTER(u64)]
+    L.pmx_dbam_stream_info.restype = ctypes.c_int
     L.pmx_dbam_select.argtypes = [vp, ctypes.POINTER(i32), i32]
     L.pmx_dbam_select.restype = ctypes.c_int
     L.pmx_dbam_close.argtypes = [vp]

@@ -161,7 +161,8 @@ def get_parser() -> argparse.ArgumentParser:
                      help="do not log the missing figure of each file; no figure is ever drawn")
 
     reads = parser.add_argument_group("reads")
-    reads.add_argument("reads", nargs="+", type=Path, help="BAM or SAM files (plain or bgzip'd), sorted by coordinate")
+    reads.add_argument("reads", nargs="+", type=Path, help="BAM or SAM files (plain or bgzip'd), sorted by coordinate; '-' reads standard input, and a FIFO or /dev/fd/N "
+                            "is read as a stream too (both need -r/--read-length)")
     reads.add_argument("-r", "--read-length", type=int, action=_NaturalNumber,
                        help="use this read length instead of estimating one from the files")
     reads.add_argument("--readlen-estimator", type=str.upper, default="MEDIAN", choices=READLEN_ESTIMATORS,
@@ -206,6 +207,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = parser.parse_args(argv)
     if args.skip_ncc and args.mappability is None:
         parser.error("argument --skip-ncc: needs a track (-m/--mappability)")
+    stdin = sum(str(p) == "-" for p in args.reads)
+    if stdin > 1:
+        parser.error("argument reads: '-' (standard input) may be named once")
+    if stdin and args.process > 1:
+        parser.error("argument -p/--process: '-' (standard input) is read by one process: use -p 1")
     try:
         check_names([str(p) for p in args.reads], args.name)
     except ValueError as e:

@@ -22,6 +22,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <cerrno>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -1152,6 +1153,8 @@ const char *inf_err_text(u32 code)
     return "unknown inflate error";
 }
 
+struct StreamState;   // (stream_device.inc)
+
 }  // namespace
 
 struct pmx_dbam {
@@ -1207,6 +1210,12 @@ struct pmx_dbam {
     int *d_sref = nullptr, *d_spos = nullptr;
     u32 *d_sqlen = nullptr, *d_sfm = nullptr;   // query length; flag | mapq << 16
     double sam_parse_t = 0;          // seconds of the parse at open (timings [5] = it + the last filter)
+    u64 sam_nb_cap = 0;              // workgroups the decode's per-workgroup tables hold
+    // stream reading (pmx_dbam_open_stream, stream_device.inc): the stream is the current window
+    StreamState *st = nullptr;
+    u64 stream_base = 0;             // offset of d_out[0] in the whole inflated stream (the histogram's first-occurrence keys)
+    bool respec = false;             // a new window: the record chain is guessed again in the tables it has
+    u64 chain_cap = 0;               // pieces the chain's tables hold
 };
 
 namespace {
@@ -1569,6 +1578,8 @@ int free_chain(pmx_dbam &b)
     b.d_ref = b.d_pos = b.d_len = nullptr;
     b.d_rev = nullptr;
     b.out_cap = 0;
+    b.chain_cap = 0;
+    b.sam_nb_cap = 0;
     return 0;
 }
 
@@ -1753,7 +1764,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 3; }
+int pmx_dbam_version(void) { return 4; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1811,12 +1822,14 @@ static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam *
     return 0;
 }
 
+static void stream_free(pmx_dbam *b);   // stream_device.inc
 void pmx_dbam_close(pmx_dbam *b)
 {
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     if (b->kstream) (void)sync_kernels(*b);
+    stream_free(b);
     free_chain(*b);
     if (b->d_rl) (void)hipFree(b->d_rl);
     for (void *p : {(void *)b->d_nl, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
@@ -1863,7 +1876,9 @@ int64_t pmx_dbam_decode(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, i
 static int walk_chain(pmx_dbam *b, WalkArgs &A)
 {
     const u64 np = b->npieces;
-    if (!b->d_spec) {
+    const bool grow = !b->d_spec || np > b->chain_cap;   // (a stream's later window may have more pieces than the first)
+    if (grow) {
+        if (b->d_spec) free_chain(*b);
         // (all of the chain's tables or none: a failed allocation must not leave a handle that skips this block next time)
         struct Undo {
             pmx_dbam *b;
@@ -1882,10 +1897,14 @@ static int walk_chain(pmx_dbam *b, WalkArgs &A)
         HIPOK(hipMalloc((void **)&b->d_first_error, 8));
         HIPOK(hipMalloc((void **)&b->d_spec, 8 * np));
         undo.keep = true;
+        b->chain_cap = np;
+    }
+    if (grow || b->respec) {
         hipLaunchKernelGGL(k_bam_spec, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, b->stream, A.D, A.N, A.nref, np, b->d_spec);
         HIPOK(hipGetLastError());
         b->chain_ready = false;
         b->n_rewalked = 0;
+        b->respec = false;
     }
     A.npieces = np;
     A.spec = b->d_spec;
@@ -2122,7 +2141,7 @@ static int64_t dbam_readlen_impl(pmx_dbam *b, uint32_t mapq_min)
         RlArgs A;
         A.D = D;
         A.N = N;
-        A.base = b->data_beg;
+        A.base = b->stream_base + (b->sam ? 0 : b->data_beg);
         A.nref = (int)b->ref_names.size();
         A.mapq_min = mapq_min;
         A.npieces = np;
@@ -2197,8 +2216,8 @@ int pmx_dbam_counters(const pmx_dbam *b, uint64_t *records, uint64_t *kept, uint
     if (records) *records = b->n_records;
     if (kept) *kept = b->n_kept;
     if (bytes_out) *bytes_out = b->N;
-    if (bytes_in) *bytes_in = b->indexed ? b->bytes_read : b->fsize;
-    if (members) *members = b->indexed ? b->members_read : b->members.size();
+    if (bytes_in) *bytes_in = (b->indexed || b->st) ? b->bytes_read : b->fsize;
+    if (members) *members = (b->indexed || b->st) ? b->members_read : b->members.size();
     if (rewalked) *rewalked = b->n_rewalked;
     return 0;
 }
@@ -2504,3 +2523,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 
 #include "bigwig_device.inc"
 #include "sam_device.inc"
+#include "stream_device.inc"

@@ -184,7 +184,7 @@ __global__ void __launch_bounds__(256) k_sam_readlen(const RlArgs A, const int *
         const u64 hi = lo + SAM_RL_LINES < nrec ? lo + SAM_RL_LINES : nrec;
         for (u64 i = lo; i < hi; i++)
             if (ref[i] >= 0)
-                add(fm[i] & 0xffffu, fm[i] >> 16, [&]() { return qlen[i]; }, [&]() { return i ? nl[i - 1] + 1u : beg; });
+                add(fm[i] & 0xffffu, fm[i] >> 16, [&]() { return qlen[i]; }, [&]() { return A.base + (i ? nl[i - 1] + 1u : beg); });
     });
 }
 
@@ -320,10 +320,16 @@ static int64_t dsam_decode(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude
     if (n == 0) return 0;
     const double t0 = now_s();
     const u64 nb = (n + 255) / 256;
-    if (!b->d_kept) {                   // (the per-workgroup counts and bases; freed with the chain's tables)
+    if (!b->d_kept || nb > b->sam_nb_cap) {   // (the per-workgroup counts and bases; freed with the chain's tables)
+        for (void *p : {(void *)b->d_kept, (void *)b->d_kept_base, (void *)b->d_totals})
+            if (p) (void)hipFree(p);
+        b->d_kept = nullptr;
+        b->d_kept_base = b->d_totals = nullptr;
+        b->sam_nb_cap = 0;
         HIPOK(hipMalloc((void **)&b->d_kept, 4 * nb));
         HIPOK(hipMalloc((void **)&b->d_kept_base, 8 * nb));
         HIPOK(hipMalloc((void **)&b->d_totals, 16));
+        b->sam_nb_cap = nb;
     }
     hipLaunchKernelGGL(k_sam_keep, dim3((unsigned)nb), dim3(256), 0, b->stream, b->d_sref, b->d_sqlen, b->d_sfm, n, mapq_min, flag_exclude,
                        want_ref, b->d_kept);

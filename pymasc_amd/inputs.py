@@ -30,14 +30,49 @@ def default_device_ingest(world: int, context=None) -> bool:
         return False
 
 
+def is_stream(path) -> bool:
+    """An input read as a stream: ``-`` (standard input) or a path that is not a regular file -- a FIFO,
+    ``/dev/fd/N`` of a pipe, a character device."""
+    from .stream_device import is_stream_path
+    return is_stream_path(path)
+
+
+#: free device bytes kept back when the whole-file device reader is chosen (the calculator's pool and the track live there too)
+DEVICE_INGEST_MARGIN = 4 << 30
+
+
+def device_ingest_budget(device: int = 0) -> int:
+    """Free bytes of ``device`` (hipMemGetInfo through torch) that the whole-file device reader may use; a test replaces it."""
+    import torch
+    free, _total = torch.cuda.mem_get_info(device)
+    return int(free) - DEVICE_INGEST_MARGIN
+
+
+def whole_file_footprint(path) -> int:
+    """Device bytes the whole-file reader needs for a BAM file of this size: the compressed copy, the inflated stream at the
+    bound its output buffer is allocated for (6x), and the kept-record arrays (13 bytes per record of >= 36 bytes)."""
+    fsize = os.path.getsize(path)
+    inflated = 6 * fsize
+    return fsize + inflated + 13 * (inflated // 36)
+
+
 def open_alignments(path, device_ingest: bool, device: int = 0, references=None, index=None):
     """The reader of an alignment file: ``DeviceSamReader`` / ``DeviceBamReader`` on ``device`` with ``device_ingest``, else
     ``SamReader`` / ``BamReader``.  ``references`` and ``index`` as ``DeviceBamReader`` takes them (the host readers read the
     whole file and leave the choice of chromosomes to ``feed``); ``index=False`` also opens the host BAM reader without its
-    .bai, as a read-length estimate over the whole file wants it."""
-    from . import bam, bam_device, sam
+    .bai, as a read-length estimate over the whole file wants it.  A stream (``is_stream``) is read by
+    ``DeviceStreamReader`` and needs ``device_ingest``; so is a whole BAM file whose footprint (``whole_file_footprint``)
+    exceeds ``device_ingest_budget``, where the whole-file reader would fail to allocate."""
+    from . import bam, bam_device, sam, stream_device
+    if is_stream(path):
+        if not device_ingest:
+            raise ValueError("'{}' is a stream: it is read by the device reader only (one rank, a GPU)".format(os.fspath(path)))
+        return stream_device.DeviceStreamReader(path, device=device, references=references)
     is_sam = sam.is_sam(path)
     if device_ingest:
+        if not is_sam and (references is None or index is False or find_index(path) is None) \
+                and whole_file_footprint(path) > device_ingest_budget(device):
+            return stream_device.DeviceStreamReader(path, device=device, references=references)
         cls = sam.DeviceSamReader if is_sam else bam_device.DeviceBamReader
         return cls(path, device=device, references=references, index=index)
     return sam.SamReader(path) if is_sam else bam.BamReader(path, index=index)

@@ -22,8 +22,8 @@ from typing import List, Optional, Sequence
 
 from . import ffi, readlen, tables
 from .chromfilter import NoTargetChromosomesError, filter_references
-from .exceptions import ReadUnsortedError
-from .inputs import default_device_ingest, open_alignments, open_header, open_track
+from .exceptions import InputUnseekable, ReadUnsortedError
+from .inputs import default_device_ingest, is_stream, open_alignments, open_header, open_track
 from .mappability import MappabilityStats
 from .sharding import _collective_device_setup, on_rank0, rank_and_world, run_sharded
 
@@ -207,7 +207,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
     dev = context.device if (context is not None and ingest) else device         # the device readers' GPU
 
     errors: List[Optional[BaseException]] = [None] * len(paths)
-    kept = None                     # (index, device reader) of the only file estimated: it feeds that file's run too
+    kept = {}                       # index -> device reader opened in _choose that feeds that file's run too
     ctx, own_ctx, track = context, False, None
     try:
         if world == 1:
@@ -246,8 +246,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
         for i in live:
             logger.info("Process {}".format(paths[i]))
             bam = None
-            if kept is not None and kept[0] == i:
-                bam, kept = kept[1], None
+            bam = kept.pop(i, None)
             try:
                 result = run_sharded(paths[i], max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
                                      references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
@@ -267,8 +266,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
                                "writing the outputs of '{}'".format(paths[i]))
             results[i] = (result, list(written) if rank == 0 else [])
     finally:
-        if kept is not None:
-            kept[1].close()
+        for r in kept.values():
+            r.close()
         if track is not None:
             track.close()
         if own_ctx:
@@ -310,14 +309,35 @@ def _warn_existing(outdir, bases, has_track, skip_ncc, stats):
 
 def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_shift, device):
     """Steps 1 and 2 of run_files: the files that open and keep a chromosome, then the common read length.  Fills ``errors``
-    with the exception of every file skipped; returns (read length or None when no file is left, (index, device reader) or
-    None).  ``device``: the GPU of the device reader the estimates are made on, None for the host reader."""
+    with the exception of every file skipped; returns (read length or None when no file is left, {index: device reader} of
+    the readers opened here that feed their file's run).  ``device``: the GPU of the device reader the estimates are made on,
+    None for the host reader.  A stream (inputs.is_stream: ``-``, a FIFO) is opened once, here, by the stream reader, which
+    then feeds its run; without ``read_len`` it is skipped before a byte of it is read (PyMaSC: handler/calc.py:81,
+    pymasc.py:199-201), and without the device reader (``device`` None) too."""
+    kept = {}
     for i, p in enumerate(paths):
+        stream = is_stream(p)
+        if stream and read_len is None:
+            logger.error("Cannot execute read length checking for unseekable input.")
+            logger.error("If your input can't reread, specify read length using `-r` option.")
+            errors[i] = InputUnseekable("'{}' is not seekable: give the read length".format(p))
+            continue
+        if stream and device is None:
+            logger.error("Failed to open file '{}'".format(p))
+            logger.error("A stream input is read by the device reader only: one process on a GPU.")
+            errors[i] = ValueError("'{}' is a stream: it needs the device reader".format(p))
+            continue
         try:
-            with open_header(p) as r:
+            r = open_alignments(p, True, device=device) if stream else open_header(p)
+            try:
                 if not r.references:
                     raise ValueError("File has no sequences defined.")
                 filter_references(r.references, chromfilter)
+                if stream:
+                    kept[i], r = r, None
+            finally:
+                if r is not None:
+                    r.close()
         except NoTargetChromosomesError as e:
             logger.error("Check your -i/--include-chrom and/or -e/--exclude-chrom options.")
             errors[i] = e
@@ -327,11 +347,11 @@ def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_sh
             errors[i] = e
     live = [i for i, e in enumerate(errors) if e is None]
     if not live:
-        return None, None
+        return None, kept
     if read_len is not None:
-        return int(read_len), None
+        return int(read_len), kept
     logger.info("Check read length: Get {} from read length distribution".format(str(esttype).lower()))
-    lengths, kept = [], None
+    lengths = []
     for i in live:
         logger.info("Check read length... : {}".format(paths[i]))
         if device is None:
@@ -347,11 +367,11 @@ def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_sh
             errors[i] = e
         finally:
             if estimated and device is not None and len(live) == 1:
-                kept = (i, r)
+                kept[i] = r
             else:
                 r.close()
     if not lengths:
-        return None, None
+        return None, kept
     if len(set(lengths)) != 1:
         logger.warning("There are multiple read length candidates. Use max length "
                        "({}) for MSCC calculation.".format(max(lengths)))

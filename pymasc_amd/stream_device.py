@@ -1,0 +1,201 @@
+"""Alignments read from a STREAM on the device, in bounded windows: binding of pmx_dbam_open_stream /
+pmx_dbam_stream_next (include/pymasc_amd_ingest.h).
+
+``DeviceStreamReader`` has the surface of ``pymasc_amd.bam_device.DeviceBamReader`` for a source that cannot be read twice
+or is too large to hold in HBM: ``-`` (standard input), a pipe, a FIFO, ``/dev/fd/N``, or a regular file.  BAM, BGZF SAM and
+plain SAM are told apart from the first bytes.  The input is read window by window; every window is inflated, CRC-checked,
+walked and filtered by the kernels of the whole-file reader, and ``feed`` hands each window's runs to the calculator's device
+feeders before the next window overwrites them.  PyMaSC refuses to estimate a read length on an unseekable input
+(handler/calc.py:81, ``InputUnseekable``); so does ``read_length_histogram`` here.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import stat
+from typing import Iterator, Tuple
+
+import numpy as np
+
+from .bam import PMX_BAM_DEFAULT_EXCLUDE
+from .bam_device import DeviceBamReader, _raise, load_ingest_library
+from .exceptions import InputUnseekable
+
+STREAM_INFO_NAMES = ("windows", "bytes_in", "max_tail", "peak_device_bytes", "window_bytes", "inflated_budget")
+
+
+def is_stream_path(path) -> bool:
+    """True for an input that is read as a stream: ``-`` (standard input) or a path that is not a regular file (a FIFO,
+    ``/dev/fd/N``, a character device).  A path that does not exist is not a stream (its open reports it)."""
+    p = os.fspath(path)
+    if p == "-":
+        return True
+    try:
+        return not stat.S_ISREG(os.stat(p).st_mode)
+    except OSError:
+        return False
+
+
+class DeviceStreamReader(DeviceBamReader):
+    """An alignment stream read through the GPU one window at a time.
+
+    ``source``: ``"-"`` (fd 0), an int fd, an object with ``fileno()`` (the caller keeps these open), or a path (opened here,
+    closed by ``close``).  ``window_bytes``: compressed bytes per window (None: the library's 64 MiB).  ``references`` /
+    ``select`` choose records as for a BAM file without an index.  A source that is not a regular file is read once:
+    ``read_length_histogram`` raises ``InputUnseekable`` and a second ``feed`` / ``batches`` raises too."""
+
+    def __init__(self, source, device: int = 0, threads: int = 0, window_bytes=None, references=None):
+        self._L = load_ingest_library()
+        self._own_fd = False
+        if isinstance(source, int):
+            fd, self.path = source, "/dev/fd/{}".format(source)
+        elif isinstance(source, (str, bytes, os.PathLike)) and os.fspath(source) in ("-", b"-"):
+            fd, self.path = 0, "-"
+        elif hasattr(source, "fileno"):
+            fd, self.path = source.fileno(), getattr(source, "name", "<stream>")
+        else:
+            self.path = os.fspath(source)
+            fd = os.open(self.path, os.O_RDONLY)
+            self._own_fd = True
+        self._fd = fd
+        self.indexed = False
+        self._device, self._threads = int(device), int(threads)
+        self._window = 0 if window_bytes is None else int(window_bytes)
+        try:
+            self.seekable = stat.S_ISREG(os.fstat(fd).st_mode)
+            self._start = os.lseek(fd, 0, os.SEEK_CUR) if self.seekable else 0
+            self._consumed = False
+            self._attach(self._open(), references)
+        except BaseException:
+            self._close_fd()
+            raise
+
+    def _open(self):
+        h = ctypes.c_void_p()
+        rc = self._L.pmx_dbam_open_stream(self._fd, self._device, self._threads, self._window, ctypes.byref(h))
+        if rc:
+            _raise(rc)
+        return h
+
+    def _close_fd(self):
+        if self._own_fd and self._fd is not None:
+            os.close(self._fd)
+        self._fd = None
+
+    def close(self) -> None:
+        super().close()
+        if getattr(self, "_own_fd", False):
+            self._close_fd()
+
+    def stream_info(self) -> dict:
+        """pmx_dbam_stream_info: windows read, compressed bytes read, largest carried tail, peak device bytes, the budgets."""
+        v = (ctypes.c_uint64 * 6)()
+        rc = self._L.pmx_dbam_stream_info(self._h, v)
+        if rc:
+            _raise(rc)
+        return dict(zip(STREAM_INFO_NAMES, (int(x) for x in v)))
+
+    def _windows(self) -> Iterator[int]:
+        """Makes every window current in turn (the first pass reads the windows the open has begun; a regular file is opened
+        again for a later pass, any other source raises)."""
+        if self._h is None:
+            raise ValueError("I/O operation on closed BAM reader")
+        if self._consumed:
+            if not self.seekable:
+                raise InputUnseekable("'{}' cannot be read twice: it is not a regular file".format(self.path))
+            os.lseek(self._fd, self._start, os.SEEK_SET)
+            selected = self._selected
+            self._L.pmx_dbam_close(self._h)
+            self._h = None
+            self._h = self._open()
+            self._selected = selected
+        self._consumed = True
+        while True:
+            n = self._L.pmx_dbam_stream_next(self._h)
+            if n < 0:
+                _raise(n)
+            if n == 0:
+                return
+            yield int(n)
+
+    def _keep_mask(self):
+        if len(self._selected) == len(self.references):
+            return None
+        keep = np.zeros(max(len(self.references), 1), dtype=bool)
+        keep[list(self._selected)] = True
+        return keep
+
+    def read_length_histogram(self, mapq_criteria: int = 0):
+        """The histogram of ``DeviceBamReader.read_length_histogram`` summed over one pass of the windows (the first-occurrence
+        keys are offsets in the whole inflated stream); the next ``feed`` reads the file again.  A stream raises
+        ``InputUnseekable`` before reading anything, as PyMaSC refuses it (handler/calc.py:81)."""
+        from .readlen import COUNTER_NAMES, ReadLengthHistogram, histogram_from_library
+        if not self.seekable:
+            raise InputUnseekable("Cannot execute read length checking for unseekable input.")
+        acc, counters = {}, dict.fromkeys(COUNTER_NAMES, 0)
+        for _ in self._windows():
+            h = histogram_from_library(self._L.pmx_dbam_readlen_hist, self._L.pmx_dbam_readlen_counters, self._h, mapq_criteria,
+                                       _raise)
+            for ln, c, f in zip(h.lengths.tolist(), h.counts.tolist(), h.first.tolist()):
+                c0, f0 = acc.get(ln, (0, f))
+                acc[ln] = (c0 + c, min(f0, f))
+            for k, v in h.counters.items():
+                counters[k] += v
+        lens = sorted(acc)
+        return ReadLengthHistogram(np.array(lens, dtype=np.int64), np.array([acc[x][0] for x in lens], dtype=np.int64),
+                                   np.array([acc[x][1] for x in lens], dtype=np.uint64), counters, int(mapq_criteria))
+
+    def feed(self, calculator, mapq_criteria: int, references=None, finish: bool = True) -> int:
+        """``DeviceBamReader.feed`` window by window: every window's runs of one chromosome go to
+        ``calculator.feed_reads_device`` (a chromosome that spans windows arrives as several runs: the feeders' duplicate and
+        order rules, mscc.pyx:351-418, carry over from one call to the next), and the calculator's context is synchronised
+        before the next window overwrites the arrays.  A window with too many runs (unsorted input) goes through host arrays
+        and ``feed_reads``, which raises ``ReadUnsortedError`` as for the file.  Returns the number of reads fed."""
+        wanted = list(calculator.references if references is None else references)
+        self._check_selected(wanted)
+        wanted = set(wanted)
+        use = np.array([n in wanted for n in self.references] or [False], dtype=bool)
+        on_device = hasattr(calculator, "feed_reads_device")
+        ctx = getattr(calculator, "_ctx", None)
+        fed = 0
+        for _ in self._windows():
+            total = self.decode(mapq_criteria)
+            if total == 0:
+                continue
+            runs = self.device_runs() if on_device else None
+            if runs is None:
+                ref, pos, rlen, rev = self._fetch(0, total)
+                m = use[ref]
+                ref, pos, rlen, rev = ref[m], pos[m], rlen[m], rev[m]
+                cuts = np.flatnonzero(np.diff(ref)) + 1
+                for s, e in zip(np.concatenate(([0], cuts)).tolist(), np.concatenate((cuts, [ref.size])).tolist()):
+                    if e > s:
+                        calculator.feed_reads(self.references[int(ref[s])], pos[s:e], rlen[s:e], rev[s:e])
+                fed += int(ref.size)
+                continue
+            d_ref, d_pos, d_len, d_rev = self.device_arrays()
+            for ref, start, count, first, last in runs:
+                if self.references[ref] not in wanted:
+                    continue
+                calculator.feed_reads_device(self.references[ref], d_pos + 4 * start, d_len + 4 * start, d_rev + start, count,
+                                             first, last)
+                fed += count
+            if ctx is not None:
+                ctx.sync()              # the feeders read this window's arrays: done before the next window replaces them
+        if finish:
+            calculator.finishup_calculation()
+        return fed
+
+    def batches(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, batch: int = 1 << 22,
+                _reference: int = -1) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
+        """``DeviceBamReader.batches`` per window: (ref_id, pos_1based, read_len, is_reverse) of the reads that pass the
+        reference's filter, in stream order, at most ``batch`` per round."""
+        keep = self._keep_mask()
+        for _ in self._windows():
+            total = self.decode(mapq_criteria, flag_exclude, _reference)
+            for first in range(0, total, batch):
+                ref, pos, rlen, rev = self._fetch(first, min(batch, total - first))
+                if keep is not None:
+                    m = keep[ref]
+                    ref, pos, rlen, rev = ref[m], pos[m], rlen[m], rev[m]
+                yield ref, pos, rlen, rev
