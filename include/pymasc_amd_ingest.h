@@ -175,6 +175,17 @@ int pmx_dbw_device_arrays(const pmx_dbw *w, const uint32_t **d_begin, const uint
 int pmx_dbw_sorted(const pmx_dbw *w);
 int pmx_dbw_copy(pmx_dbw *w, int64_t first, int64_t n, uint32_t *begin, uint32_t *end, float *value);
 
+/* Text tracks on the device (version >= 5): `path` is a bedGraph, BED or WIG file, plain, BGZF or gzip, read by
+ * the rules of pmx_ttrack_open (pymasc_amd_io.h, its checker).  Plain text is copied to HBM through the staging buffers; BGZF goes
+ * through the member scan, k_bgzf_inflate and k_bgzf_crc; other gzip is inflated on the host with zlib (one DEFLATE stream
+ * cannot be split) and copied.  k_sam_count / k_bam_scan / k_sam_lines index the lines, k_tt_parse parses one line per lane
+ * (values by Clinger's fast path; the rest re-parsed with strtod on the host), WIG lines find their declaration by a scan over the
+ * line table, and the lines are put into per-chromosome order on the device.  A malformed line: PMX_DBAM_ERR_FORMAT with
+ * pmx_ttrack_open's message.  The handle is a pmx_dbw: nchrom / chrom_name / chrom_len (the chromosomes with lines, in the order
+ * of their first line; chrom_len = the largest end), fetch (the lines of a chromosome with value >= threshold, in file order),
+ * device_arrays, sorted, copy and close work on it. */
+int pmx_dtt_open(const char *path, int device, int nthreads, pmx_dbw **out);
+
 #ifdef __cplusplus
 }
 #endif

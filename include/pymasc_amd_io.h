@@ -143,6 +143,28 @@ int64_t pmx_bigwig_chrom_len(const pmx_bigwig *w, int32_t i);
 int64_t pmx_bigwig_fetch(pmx_bigwig *w, const char *chrom, float threshold, int64_t cap,
                          uint32_t *begin, uint32_t *end, float *value);
 
+/* ---- Text tracks: bedGraph, BED, WIG -------------------------------------------------------
+ * The host twin of pmx_dtt_open (pymasc_amd_ingest.h) and its checker.  `path` is plain text, BGZF or gzip (one or several
+ * members; told from the bytes).  The kind: a track line's type=bedGraph / type=wiggle_0, else a WIG declaration as the first
+ * data line, else a .bed suffix (after .gz / .bgz) means BED, else bedGraph.  The whole text is read and parsed at open by the
+ * rules of io/text_track_parse.h; values are (float)strtod of their text.  A malformed line, a bad number, a WIG data line
+ * before any declaration, a second track line or a truncated gzip stream: PMX_IO_ERR_FORMAT, "line N: <reason>" (1-based).
+ * nthreads is unused (one thread). */
+typedef struct pmx_ttrack pmx_ttrack;
+int pmx_ttrack_open(const char *path, int nthreads, pmx_ttrack **out);
+void pmx_ttrack_close(pmx_ttrack *t);
+/* The chromosomes that have lines, in the order of their first line; chrom_len = the largest end of its lines (an extent,
+ * not a chromosome size). */
+int32_t pmx_ttrack_nchrom(const pmx_ttrack *t);
+const char *pmx_ttrack_chrom_name(const pmx_ttrack *t, int32_t i);
+int64_t pmx_ttrack_chrom_len(const pmx_ttrack *t, int32_t i);
+/* The intervals of `chrom` whose value is >= threshold (threshold <= 0: every one), in file order, with
+ * pmx_bigwig_fetch's two-call protocol; PMX_IO_ERR_NOTFOUND for a chromosome without lines. */
+int64_t pmx_ttrack_fetch(pmx_ttrack *t, const char *chrom, float threshold, int64_t cap, uint32_t *begin, uint32_t *end,
+                         float *value);
+/* 1 when the intervals of the last fetch are ascending and disjoint (begin_(i+1) >= end_i), or there are none */
+int pmx_ttrack_sorted(const pmx_ttrack *t);
+
 #ifdef __cplusplus
 }
 #endif

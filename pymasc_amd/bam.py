@@ -39,6 +39,8 @@ IO_EXPORTS = [
     "pmx_sam_decode", "pmx_sam_fetch", "pmx_sam_counters", "pmx_sam_readlen_hist", "pmx_sam_readlen_counters",
     "pmx_bigwig_open", "pmx_bigwig_close", "pmx_bigwig_nchrom", "pmx_bigwig_chrom_name", "pmx_bigwig_chrom_len",
     "pmx_bigwig_fetch",
+    "pmx_ttrack_open", "pmx_ttrack_close", "pmx_ttrack_nchrom", "pmx_ttrack_chrom_name", "pmx_ttrack_chrom_len",
+    "pmx_ttrack_fetch", "pmx_ttrack_sorted",
 ]
 
 
@@ -135,6 +137,20 @@ def load_io_library():
     L.pmx_bigwig_chrom_len.restype = i64
     L.pmx_bigwig_fetch.argtypes = [vp, ctypes.c_char_p, ctypes.c_float, i64, vp, vp, vp]
     L.pmx_bigwig_fetch.restype = i64
+    L.pmx_ttrack_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(vp)]
+    L.pmx_ttrack_open.restype = ctypes.c_int
+    L.pmx_ttrack_close.argtypes = [vp]
+    L.pmx_ttrack_close.restype = None
+    L.pmx_ttrack_nchrom.argtypes = [vp]
+    L.pmx_ttrack_nchrom.restype = i32
+    L.pmx_ttrack_chrom_name.argtypes = [vp, i32]
+    L.pmx_ttrack_chrom_name.restype = ctypes.c_char_p
+    L.pmx_ttrack_chrom_len.argtypes = [vp, i32]
+    L.pmx_ttrack_chrom_len.restype = i64
+    L.pmx_ttrack_fetch.argtypes = [vp, ctypes.c_char_p, ctypes.c_float, i64, vp, vp, vp]
+    L.pmx_ttrack_fetch.restype = i64
+    L.pmx_ttrack_sorted.argtypes = [vp]
+    L.pmx_ttrack_sorted.restype = ctypes.c_int
     _lib = L
     return L
 

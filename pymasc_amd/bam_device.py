@@ -29,7 +29,7 @@ INGEST_EXPORTS = [
     "pmx_dbam_readlen_counters", "pmx_dbam_open_indexed", "pmx_dbam_select", "pmx_dsam_open",
     "pmx_dbam_open_stream", "pmx_dbam_stream_next", "pmx_dbam_stream_info",
     "pmx_dbw_open", "pmx_dbw_close", "pmx_dbw_nchrom", "pmx_dbw_chrom_name", "pmx_dbw_chrom_len", "pmx_dbw_fetch", "pmx_dbw_device_arrays",
-    "pmx_dbw_sorted", "pmx_dbw_copy",
+    "pmx_dbw_sorted", "pmx_dbw_copy", "pmx_dtt_open",
 ]
 
 _lib = None
@@ -95,6 +95,8 @@ def load_ingest_library():
     L.pmx_dbam_readlen_counters.restype = ctypes.c_int
     L.pmx_dbw_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     L.pmx_dbw_open.restype = ctypes.c_int
+    L.pmx_dtt_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+    L.pmx_dtt_open.restype = ctypes.c_int
     L.pmx_dbw_close.argtypes = [vp]
     L.pmx_dbw_close.restype = None
     L.pmx_dbw_nchrom.argtypes = [vp]

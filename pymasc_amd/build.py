@@ -82,11 +82,13 @@ def ingest_sources():
 
 
 def build_ingest(force=False, verbose=False):
-    """libpymasc_ingest.so (include/pymasc_amd_ingest.h): BGZF inflate + BAM record decode on the device, hipcc for gfx950.
+    """libpymasc_ingest.so (include/pymasc_amd_ingest.h): BGZF inflate + BAM record decode on the device, hipcc for gfx950
+    (zlib only for the host inflate of a plain-gzip text track).
     A library of its own: libpymasc_hip.so's build id (source_hash) covers the cross-correlation kernels only."""
     deps = ingest_sources() + glob.glob(os.path.join(CSRC, "ingest", "*.inc")) + [os.path.join(HERE, "..", "include", "pymasc_amd_ingest.h"),
                                                                                      os.path.join(CSRC, "io", "bai_index.h"),
                                                                                      os.path.join(CSRC, "io", "sam_parse.h"),
+                                                                                     os.path.join(CSRC, "io", "text_track_parse.h"),
                                                                                      os.path.abspath(__file__)]
     if not force and os.path.exists(INGEST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(INGEST_LIB) for d in deps):
         return INGEST_LIB
@@ -98,7 +100,7 @@ def build_ingest(force=False, verbose=False):
            # BAM-like members 28 -> 33 GB/s (same-box A/B, tools/ingest_paths.py; no effect on libpymasc_hip.so's kernels)
            "-mllvm", "-structurizecfg-skip-uniform-regions=1",
            "-Wall", "-Wno-unused-function", "-pthread",
-           "-o", INGEST_LIB] + ingest_sources()
+           "-o", INGEST_LIB] + ingest_sources() + ["-lz"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)

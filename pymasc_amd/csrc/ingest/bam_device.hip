@@ -13,7 +13,8 @@
 //   k_bgzf_crc      CRC-32 of a member's output: 64 slices, one per lane, combined with x^(8n) mod P.
 //   k_bam_spec / k_bam_walk / k_bam_scan   the record chain and the filter, see the comment above k_bam_spec.
 //
-// No zlib, no host inflate: a host that cannot launch these kernels gets an error, not a fallback.
+// No host inflate of BGZF: a host that cannot launch these kernels gets an error, not a fallback.  (zlib is linked for one
+// thing only: a text track in plain gzip, one DEFLATE stream that cannot be split, is inflated on the host -- DESIGN.md 7.10.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1764,7 +1765,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 4; }
+int pmx_dbam_version(void) { return 5; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -2524,3 +2525,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "bigwig_device.inc"
 #include "sam_device.inc"
 #include "stream_device.inc"
+#include "text_track_device.inc"

@@ -166,6 +166,12 @@ struct pmx_dbw {
     std::vector<std::pair<u64, u64>> range;   // per chromosome: its intervals in the arrays
     std::vector<int> order;         // per chromosome: -1 not asked yet, 1 ascending and disjoint, 0 not
     std::vector<void *> retired;    // arrays of an earlier threshold
+    // a text track (pmx_dtt_open, text_track_device.inc): every chromosome's lines in per-chromosome order, each in file order
+    bool text = false;
+    u32 *t_b = nullptr, *t_e = nullptr;
+    float *t_v = nullptr;
+    u64 *t_cbase = nullptr;         // [nchrom + 1]: where each chromosome's lines start
+    u64 t_n = 0, text_lines = 0, text_heads = 0, text_slow = 0;   // data lines, lines, chromosome blocks, values strtod decided
 };
 
 namespace {
@@ -365,7 +371,8 @@ void pmx_dbw_close(pmx_dbw *w)
     if (!w) return;
     (void)hipSetDevice(w->device);
     if (w->stream) (void)hipStreamSynchronize(w->stream);
-    for (void *p : {(void *)w->d_file, (void *)w->d_begin, (void *)w->d_end, (void *)w->d_value})
+    for (void *p : {(void *)w->d_file, (void *)w->d_begin, (void *)w->d_end, (void *)w->d_value, (void *)w->t_b, (void *)w->t_e,
+                    (void *)w->t_v, (void *)w->t_cbase})
         if (p) (void)hipFree(p);
     for (void *p : w->retired) (void)hipFree(p);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -551,6 +558,8 @@ int bw_decode_all(pmx_dbw *w, float threshold)
 
 }  // namespace
 
+static int tt_decode_all(pmx_dbw *w, float threshold);   // text_track_device.inc
+
 extern "C" {
 
 static int64_t dbw_fetch_impl(pmx_dbw *w, const char *chrom, float threshold);
@@ -572,7 +581,7 @@ static int64_t dbw_fetch_impl(pmx_dbw *w, const char *chrom, float threshold)
     if (!(threshold > 0.f)) threshold = 0.f;
     if (!w->have || w->have_threshold != threshold) {
         w->have = false;
-        const int rc = bw_decode_all(w, threshold);
+        const int rc = w->text ? tt_decode_all(w, threshold) : bw_decode_all(w, threshold);
         if (rc) return rc;
     }
     w->cur = k;

@@ -1,5 +1,5 @@
 """Which reader a run reads its input through: the one place that chooses between the host readers (libpymasc_io.so) and
-the device readers (libpymasc_ingest.so) of an alignment file -- BAM, or SAM (pymasc_amd.sam) -- and of a BigWig track.
+the device readers (libpymasc_ingest.so) of an alignment file -- BAM, or SAM (pymasc_amd.sam) -- and of a mappability track: BigWig, or text (pymasc_amd.text_track).
 
 The reader modules import ``find_index`` from here, so they are imported inside the openers, and the device classes are
 looked up through their module each time (a test may replace ``bam_device.DeviceBamReader``).
@@ -86,8 +86,14 @@ def open_header(path):
 
 
 def open_track(path, device_ingest: bool, device: int = 0):
-    """The reader of a BigWig track: ``DeviceBigWigReader`` on ``device`` with ``device_ingest``, else ``BigWigReader``."""
-    from . import bigwig, bigwig_device
+    """The reader of a mappability track: a BigWig file (``text_track.is_bigwig``: the bbi magic or a .bw / .bigwig name) is read
+    by ``DeviceBigWigReader`` on ``device`` with ``device_ingest``, else ``BigWigReader``; any other file is a text track
+    (bedGraph, BED, WIG; plain, BGZF or gzip) read by ``DeviceTextTrackReader`` / ``TextTrackReader``."""
+    from . import bigwig, bigwig_device, text_track
+    if text_track.is_bigwig(path):
+        if device_ingest:
+            return bigwig_device.DeviceBigWigReader(path, device=device)
+        return bigwig.BigWigReader(path)
     if device_ingest:
-        return bigwig_device.DeviceBigWigReader(path, device=device)
-    return bigwig.BigWigReader(path)
+        return text_track.DeviceTextTrackReader(path, device=device)
+    return text_track.TextTrackReader(path)

@@ -279,8 +279,12 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
         lengths = dict(zip(reader.references, reader.lengths))
         if bigwig_path is not None:     # with device ingest the track is decoded on the GPU too: its intervals stay in HBM
             bw = track if track is not None else open_track(bigwig_path, device_ingest, dev)
-            # the track's chromosome sizes win where they are longer (handler/calc.py:100-115)
-            lengths.update(reconcile_chromosome_sizes({n: lengths[n] for n in names}, bw.chromsizes))
+            # the track's chromosome sizes win where they are longer (handler/calc.py:100-115); a text track's sizes are the
+            # extents of its lines: one that stops short of the chromosome is normal and says nothing
+            ext = bw.chromsizes
+            if getattr(bw, "chromsizes_are_extents", False):
+                ext = {n: s for n, s in ext.items() if n in lengths and s > lengths[n]}
+            lengths.update(reconcile_chromosome_sizes({n: lengths[n] for n in names}, ext))
         mine = [names[i] for i in sorted(lpt_assign([lengths[n] for n in names], world)[rank])]
         if indexed:
             reader.select(mine)

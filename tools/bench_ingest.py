@@ -308,6 +308,73 @@ def time_bigwig(path_bw, chroms_per_call=None):
     return out
 
 
+def synth_text_track(path, kind, compress, nlines, seed=7):
+    """A seeded hg38-shaped text track of about `nlines` lines: alternating unmappable / mappable runs drawn from the golden
+    track's run and gap lengths (pymasc_amd.synth.fixture_run_lengths), over the 24 chromosomes in proportion to their length.
+    bedgraph: "chrom start end 0|1" for every run and gap; bed: the mappable runs; wig: one variableStep block per chromosome,
+    a "pos 1" line per mappable run (span 36: the read length of a Umap-style k36 track)."""
+    import gzip
+    from pymasc_amd import synth
+    runs, gaps = synth.fixture_run_lengths()
+    rng = np.random.default_rng(seed)
+    total = sum(l for _n, l in HG38)
+    out = []
+    t0 = time.time()
+    for n, l in HG38:
+        per = max(1, int(nlines * l / total) // (2 if kind == "bedgraph" else 1))
+        r = rng.choice(runs, per)
+        g = rng.choice(gaps, per)
+        b = int(rng.integers(0, 10000)) + np.cumsum(g + r) - r          # starts of the mappable runs
+        e = b + r
+        if kind == "bedgraph":
+            gb = np.concatenate(([0], e[:-1]))
+            z = np.char.add(np.char.add(n + "\t", gb.astype(str)), np.char.add("\t", b.astype(str)))
+            o = np.char.add(np.char.add(n + "\t", b.astype(str)), np.char.add("\t", e.astype(str)))
+            lines = np.empty(2 * per, dtype=object)
+            lines[0::2] = np.char.add(z, "\t0")
+            lines[1::2] = np.char.add(o, "\t1")
+            lines = lines[1:] if b[0] == 0 else lines
+        elif kind == "bed":
+            lines = np.char.add(np.char.add(n + "\t", b.astype(str)), np.char.add("\t", e.astype(str)))
+        else:
+            out.append("variableStep chrom={} span=36\n".format(n))
+            lines = np.char.add((b + 1).astype(str), " 1")
+        out.append("\n".join(lines.tolist()) + "\n")
+    data = "".join(out).encode()
+    if compress == "gzip":
+        data = gzip.compress(data, 6)
+    elif compress == "bgzf":
+        data = W.bgzf_compress(data)
+    with open(path, "wb") as fp:
+        fp.write(data)
+    return time.time() - t0
+
+
+def time_text_track(path, reps=3):
+    """Open + fetch of every chromosome at 1.0: the host reader against the device reader (intervals left in HBM)."""
+    from pymasc_amd.text_track import DeviceTextTrackReader, TextTrackReader
+    host = []
+    for _ in range(reps):
+        t0 = time.time()
+        with TextTrackReader(path) as r:
+            chk = [(a.size, int(a.sum()) + int(b.sum())) for a, b, _v in (r.fetch_arrays(1, c) for c in r.chromsizes)]
+            names = list(r.chromsizes)
+        host.append(round(time.time() - t0, 4))
+    dev, dev_open = [], []
+    for _ in range(reps):
+        t0 = time.time()
+        with DeviceTextTrackReader(path) as r:
+            t1 = time.time()
+            ns = [r.fetch_device(1, c)[2] for c in names]
+            dev.append(round(time.time() - t0, 4))
+            dev_open.append(round(t1 - t0, 4))
+    with DeviceTextTrackReader(path) as r:      # parity of the whole track
+        chk2 = [(a.size, int(a.sum()) + int(b.sum())) for a, b, _v in (r.fetch_arrays(1, c) for c in names)]
+    assert chk == chk2 and ns == [c[0] for c in chk]
+    return {"intervals_at_1": sum(c[0] for c in chk), "host_reader_s": host, "device_reader_s": dev, "device_open_s": dev_open,
+            "speedup": round(min(host) / min(dev), 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=5_000_000)
@@ -322,8 +389,28 @@ def main():
     ap.add_argument("--subsets", action="store_true", help="write a .bai and time indexed device reads of chromosome subsets")
     ap.add_argument("--sam", choices=["plain", "bgzf"], default=None,
                     help="write the synthetic reads as SAM text (plain or BGZF) and time SamReader against DeviceSamReader")
+    ap.add_argument("--track-text", choices=["bedgraph", "bed", "wig"], default=None,
+                    help="write a seeded hg38-shaped text track and time TextTrackReader against DeviceTextTrackReader")
+    ap.add_argument("--compress", choices=["none", "bgzf", "gzip"], default="none", help="compression of the --track-text file")
+    ap.add_argument("--lines", type=int, default=20_000_000, help="about how many lines the --track-text file has")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+
+    if a.track_text:
+        path = a.path + "." + a.track_text + {"none": "", "bgzf": ".gz", "gzip": ".gz"}[a.compress]
+        gen_s = synth_text_track(path, a.track_text, a.compress, a.lines)
+        res = {"kind": a.track_text, "compress": a.compress, "file_bytes": os.path.getsize(path), "generate_s": round(gen_s, 1)}
+        if a.compress == "none":
+            res["lines"] = sum(1 for _ in open(path, "rb"))
+        try:
+            res.update(time_text_track(path))
+        finally:
+            os.unlink(path)
+        print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "w") as fp:
+                json.dump(res, fp, indent=1)
+        return
 
     if a.sam:
         path = a.path + (".sam" if a.sam == "plain" else ".sam.gz")
