@@ -186,6 +186,18 @@ int pmx_dbw_copy(pmx_dbw *w, int64_t first, int64_t n, uint32_t *begin, uint32_t
  * device_arrays, sorted, copy and close work on it. */
 int pmx_dtt_open(const char *path, int device, int nthreads, pmx_dbw **out);
 
+/* BED read files on the device (version >= 6): `path` is a tagAlign / BED6 file with one read per line, plain,
+ * BGZF or gzip, read by the rules of pmx_bed_open (pymasc_amd_io.h, its checker) with the nref chromosome sizes given (their
+ * order is the reference order).  The text reaches HBM as a text track's does (pmx_dtt_open); k_sam_count / k_bam_scan /
+ * k_sam_lines index the lines, k_bed_parse parses one line per lane into the SAM parse table, and a file that is not in
+ * (reference, start) order is put in it by a stable LSD radix sort of the keys ref << 31 | start on the device (passes whose
+ * digit is the same in every key skipped), ties in file order.  A malformed line: PMX_DBAM_ERR_FORMAT with pmx_bed_open's
+ * message.  The handle is a pmx_dbam: nref / ref_name / ref_len (the sizes), header_text (empty), decode, device_arrays, fetch,
+ * runs, readlen_hist (first-occurrence keys: byte offsets of lines in the text), readlen_counters, counters (members 0) and
+ * timings work on it; pmx_dbam_select is PMX_DBAM_ERR_INVALID. */
+int pmx_dbed_open(const char *path, int device, int nthreads, int32_t nref, const char *const *names, const int64_t *lengths,
+                  pmx_dbam **out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,19 @@ int pmx_sam_counters(const pmx_sam *s, uint64_t *records, uint64_t *kept, uint64
 int64_t pmx_sam_readlen_hist(pmx_sam *s, uint32_t mapq_min, int64_t cap, int32_t *lengths, uint64_t *counts, uint64_t *first);
 int pmx_sam_readlen_counters(const pmx_sam *s, uint64_t c[6]);
 
+/* ---- BED read files: tagAlign / bedtools bamtobed, BED6 with one line per read (version >= 4) ----------
+ * The host twin of pmx_dbed_open (pymasc_amd_ingest.h) and its checker.  `path` is plain text, BGZF or gzip (one or several
+ * members; told from the bytes).  A BED file has no header: the references are the nref chromosome sizes given (names unique
+ * and non-empty, lengths in 1..2^31-1; their order is the reference order).  Every line is parsed by the rules of
+ * io/bed_reads_parse.h: "chrom start end name score strand" gives ref = chrom's index, pos1 = start + 1, query length =
+ * end - start, flag 16 for '-' (else 0), MAPQ = min(score, 255) ('.': 255); blank, '#', "browser" and one leading "track"
+ * line carry no read.  A malformed line: PMX_IO_ERR_FORMAT, "line N: <reason>" (1-based in the decompressed text).  The records
+ * are delivered sorted stably by (reference, start), ties in file order: a file out of that order is put in it with
+ * std::stable_sort.  The handle is a pmx_sam: nref / ref_name / ref_len (the sizes), header_text (empty), decode, fetch,
+ * counters (records = reads; members = BGZF members, 0 for plain text and other gzip), readlen_hist (first[i] = byte offset
+ * of the line of the first counted record, whatever the sort did), readlen_counters and close work on it. */
+int pmx_bed_open(const char *path, int nthreads, int32_t nref, const char *const *names, const int64_t *lengths, pmx_sam **out);
+
 /* ---- BigWig (bbi) ----------------------------------------------------------------------------------------- */
 typedef struct pmx_bigwig pmx_bigwig;
 

@@ -40,7 +40,7 @@ IO_EXPORTS = [
     "pmx_bigwig_open", "pmx_bigwig_close", "pmx_bigwig_nchrom", "pmx_bigwig_chrom_name", "pmx_bigwig_chrom_len",
     "pmx_bigwig_fetch",
     "pmx_ttrack_open", "pmx_ttrack_close", "pmx_ttrack_nchrom", "pmx_ttrack_chrom_name", "pmx_ttrack_chrom_len",
-    "pmx_ttrack_fetch", "pmx_ttrack_sorted",
+    "pmx_ttrack_fetch", "pmx_ttrack_sorted", "pmx_bed_open",
 ]
 
 
@@ -105,6 +105,9 @@ def load_io_library():
     L.pmx_sam_open.restype = ctypes.c_int
     L.pmx_sam_open_header.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pmx_sam_open_header.restype = ctypes.c_int
+    L.pmx_bed_open.argtypes = [ctypes.c_char_p, ctypes.c_int, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i64),
+                               ctypes.POINTER(vp)]
+    L.pmx_bed_open.restype = ctypes.c_int
     L.pmx_sam_close.argtypes = [vp]
     L.pmx_sam_close.restype = None
     L.pmx_sam_nref.argtypes = [vp]

@@ -29,7 +29,7 @@ INGEST_EXPORTS = [
     "pmx_dbam_readlen_counters", "pmx_dbam_open_indexed", "pmx_dbam_select", "pmx_dsam_open",
     "pmx_dbam_open_stream", "pmx_dbam_stream_next", "pmx_dbam_stream_info",
     "pmx_dbw_open", "pmx_dbw_close", "pmx_dbw_nchrom", "pmx_dbw_chrom_name", "pmx_dbw_chrom_len", "pmx_dbw_fetch", "pmx_dbw_device_arrays",
-    "pmx_dbw_sorted", "pmx_dbw_copy", "pmx_dtt_open",
+    "pmx_dbw_sorted", "pmx_dbw_copy", "pmx_dtt_open", "pmx_dbed_open",
 ]
 
 _lib = None
@@ -57,6 +57,9 @@ def load_ingest_library():
     L.pmx_dbam_open_indexed.restype = ctypes.c_int
     L.pmx_dsam_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     L.pmx_dsam_open.restype = ctypes.c_int
+    L.pmx_dbed_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, i32, ctypes.POINTER(ctypes.c_char_p),
+                                ctypes.POINTER(i64), ctypes.POINTER(vp)]
+    L.pmx_dbed_open.restype = ctypes.c_int
     L.pmx_dbam_open_stream.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, u64, ctypes.POINTER(vp)]
     L.pmx_dbam_open_stream.restype = ctypes.c_int
     L.pmx_dbam_stream_next.argtypes = [vp]

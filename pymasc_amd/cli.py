@@ -163,7 +163,11 @@ def get_parser() -> argparse.ArgumentParser:
 
     reads = parser.add_argument_group("reads")
     reads.add_argument("reads", nargs="+", type=Path, help="BAM or SAM files (plain or bgzip'd), sorted by coordinate; '-' reads standard input, and a FIFO or /dev/fd/N "
-                            "is read as a stream too (both need -r/--read-length)")
+                            "is read as a stream too (both need -r/--read-length); files named .tagAlign or .bed (optionally "
+                            ".gz / .bgz) are BED read files, sorted or not (need --chrom-sizes)")
+    reads.add_argument("--chrom-sizes", metavar="FILE", type=Path,
+                       help="chromosome names and lengths of the BED read files, in reference order: a .chrom.sizes or .fai "
+                            "file, or a BAM / SAM file whose header gives them (BAM and SAM inputs keep their own)")
     reads.add_argument("-r", "--read-length", type=int, action=_NaturalNumber,
                        help="use this read length instead of estimating one from the files")
     reads.add_argument("--readlen-estimator", type=str.upper, default="MEDIAN", choices=READLEN_ESTIMATORS,
@@ -217,6 +221,13 @@ def parse_args(argv=None) -> argparse.Namespace:
         check_names([str(p) for p in args.reads], args.name)
     except ValueError as e:
         parser.error("argument -n/--name: {}".format(e))
+    if args.chrom_sizes is not None and not os.path.isfile(args.chrom_sizes):
+        parser.error("argument --chrom-sizes: no such file: '{}'".format(args.chrom_sizes))
+    if args.chrom_sizes is None:
+        from .bed_reads import is_bed_reads     # (no torch, no native library)
+        bed = [str(p) for p in args.reads if is_bed_reads(p)]
+        if bed:
+            parser.error("argument --chrom-sizes: needed by the BED read file(s) {}".format(", ".join(bed)))
     return args
 
 
@@ -289,6 +300,7 @@ def _rank0_track_error(error: BaseException) -> bool:
 def _run(args, device, rank: int) -> int:
     from . import pipeline
     from .mappability import BWIOError, JSONIOError
+    extra = {} if args.chrom_sizes is None else {"chrom_sizes": str(args.chrom_sizes)}   # (BED read files only)
     try:
         results = pipeline.run_files(
             [str(p) for p in args.reads], str(args.outdir), args.max_shift, read_len=args.read_length,
@@ -298,7 +310,7 @@ def _run(args, device, rank: int) -> int:
             skip_ncc=args.skip_ncc, device=device, readlen_estimator=args.readlen_estimator,
             chromfilter=args.chromfilter, stats=True, library_length=args.library_length,
             smooth_window=args.smooth_window, mask_size=args.mask_size, bg_avr_width=args.bg_avr_width,
-            chi2_pval=args.chi2_pval, names=args.name or None)
+            chi2_pval=args.chi2_pval, names=args.name or None, **extra)
     except (BWIOError, JSONIOError):
         return 1                    # logged where it was raised (mappability.MappabilityStats)
     except RuntimeError as e:

@@ -839,8 +839,9 @@ struct RlArgs {
 
 // The body of the histogram kernels (k_bam_readlen; k_sam_readlen in sam_device.inc): the tables, a lane's counters and run,
 // the merge.  walk(add) calls add(flag, mapq, qlen, key) for every record with ref_id >= 0 of the lane's share, in file order;
-// qlen() and key() are evaluated only for a record that is counted.
-template <int PASS, class Walk>
+// qlen() and key() are evaluated only for a record that is counted.  MINKEY: the keys of a run are not ascending (a BED read file
+// put in order, bed_reads_device.inc), so each is compared with the run's first.
+template <int PASS, bool MINKEY = false, class Walk>
 __device__ __forceinline__ void readlen_lane(const RlArgs &A, Walk walk)
 {
     __shared__ u32 s_cnt[PASS == 0 ? RL_SHORT : 1];
@@ -898,6 +899,9 @@ __device__ __forceinline__ void readlen_lane(const RlArgs &A, Walk walk)
                     run_len = q;
                     run_cnt = 0;
                     run_first = key();
+                } else if (MINKEY) {
+                    const u64 k = key();
+                    if (k < run_first) run_first = k;
                 }
                 run_cnt++;
             }
@@ -1204,6 +1208,10 @@ struct pmx_dbam {
     std::vector<pmx_bai::RefRange> index;
     u64 hdr_end = 0;                 // file offset behind the last member that holds part of the header
     u64 bytes_read = 0, members_read = 0;   // compressed bytes and members behind the current stream (counters)
+    // BED reads (pmx_dbed_open, bed_reads_device.inc): a SAM handle whose table is in (reference, start) order, with the start
+    // of each record's line beside it; the line index is gone
+    bool bed = false;
+    u64 *d_ls = nullptr;
     // SAM text (pmx_dsam_open, sam_device.inc): the stream is the text, a table of its record lines replaces the record chain
     bool sam = false;
     u64 sam_lines = 0, sam_hdr_lines = 0;
@@ -1765,7 +1773,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 5; }
+int pmx_dbam_version(void) { return 6; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1833,7 +1841,7 @@ void pmx_dbam_close(pmx_dbam *b)
     stream_free(b);
     free_chain(*b);
     if (b->d_rl) (void)hipFree(b->d_rl);
-    for (void *p : {(void *)b->d_nl, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
+    for (void *p : {(void *)b->d_nl, (void *)b->d_ls, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
         if (p) (void)hipFree(p);
     for (hipStream_t x : b->kmore)
         if (x) (void)hipStreamDestroy(x);
@@ -2526,3 +2534,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "sam_device.inc"
 #include "stream_device.inc"
 #include "text_track_device.inc"
+#include "bed_reads_device.inc"

@@ -360,8 +360,10 @@ static int64_t dsam_decode(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude
     return (int64_t)b->n_kept;
 }
 
+static hipError_t dbed_launch_readlen(const pmx_dbam *b, int pass, const RlArgs &A);   // bed_reads_device.inc
 static hipError_t dsam_launch_readlen(const pmx_dbam *b, int pass, const RlArgs &A)
 {
+    if (b->bed) return dbed_launch_readlen(b, pass, A);
     const u64 lanes = (b->sam_lines + SAM_RL_LINES - 1) / SAM_RL_LINES;
     const dim3 wg((unsigned)((lanes + 255) / 256));
     if (pass == 0)

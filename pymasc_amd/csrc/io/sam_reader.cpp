@@ -7,11 +7,14 @@
 //   text per thread) --parse (one chunk of lines per task)--> per-record table (ref, pos1, qlen, flag | mapq << 16)
 //   --pmx_sam_decode: filter + compaction--> the kept arrays, copied out by pmx_sam_fetch
 #include "../../../include/pymasc_amd_io.h"
+#include "bed_reads_parse.h"
 #include "io_common.h"
 #include "sam_parse.h"
+#include "text_track_parse.h"
 
 #include <algorithm>
 #include <cstring>
+#include <numeric>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -25,6 +28,7 @@ struct pmx_sam {
     bool header_only = false;       // pmx_sam_open_header: no record was read
     samtext::Header h;
     std::vector<uint64_t> nl;       // end ('\n' or the end of the text) of every record line
+    std::vector<uint64_t> ls;       // a BED read file put in order (pmx_bed_open): the start of each record's line
     uint64_t nrec = 0;
     std::vector<int32_t> ref, pos;
     std::vector<uint32_t> qlen, fm;  // fm = flag | mapq << 16
@@ -40,7 +44,7 @@ struct pmx_sam {
     bool rl_valid = false;
     uint32_t rl_mapq = 0;
 
-    uint64_t line_start(uint64_t i) const { return i ? nl[i - 1] + 1 : h.data_beg; }
+    uint64_t line_start(uint64_t i) const { return !ls.empty() ? ls[i] : i ? nl[i - 1] + 1 : h.data_beg; }
 };
 
 namespace {
@@ -52,7 +56,8 @@ struct HostSrc {
 
 using pmx_io::parallel_for;
 
-void index_and_parse(pmx_sam &s)
+// s.nl: the end of every line after the header
+void index_lines(pmx_sam &s)
 {
     const uint64_t beg = s.h.data_beg, N = s.N;
     // line ends: one part of the text per thread
@@ -73,6 +78,11 @@ void index_and_parse(pmx_sam &s)
     s.nl.reserve(total + 1);
     for (auto &v : parts) s.nl.insert(s.nl.end(), v.begin(), v.end());
     if (N > beg && s.t[N - 1] != '\n') s.nl.push_back(N);    // the last line without its '\n'
+}
+
+void index_and_parse(pmx_sam &s)
+{
+    index_lines(s);
     uint64_t n = s.nl.size();
     if (n) {                                                  // one empty line at the very end is allowed
         const uint64_t a = s.line_start(n - 1);
@@ -114,9 +124,136 @@ inline bool keep(const pmx_sam &s, size_t i, uint32_t mapq_min, uint32_t flag_ex
     return !(flag & flag_exclude) && mapq >= mapq_min && s.ref[i] >= 0 && (want_ref < 0 || s.ref[i] == want_ref) && s.qlen[i] != 0;
 }
 
+// A BED read file (pmx_bed_open): every line parsed by io/bed_reads_parse.h, the track-line rules, then the table put in
+// (reference, start) order by std::stable_sort when the file is not in that order already; lines without a read sort last and
+// are dropped
+void bed_parse_sort(pmx_sam &s)
+{
+    index_lines(s);
+    const uint64_t n = s.nl.size();
+    if (n >= 0xffffffffull) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "more than 2^32 - 2 lines");
+    const uint32_t nref = (uint32_t)s.h.names.size();
+    s.ref.resize(n);
+    s.pos.resize(n);
+    s.qlen.resize(n);
+    s.fm.resize(n);
+    std::vector<uint64_t> key(n);
+    const size_t grain = 1 << 16, chunks = (n + grain - 1) / grain;
+    std::vector<uint64_t> first_err(chunks, ~0ull), first_read(chunks, ~0ull), unsorted(chunks, 0);
+    std::vector<std::vector<uint64_t>> tracks(chunks);
+    const samtext::Names nm = samtext::names_of(s.h);
+    parallel_for(s.nthreads, n, grain, [&](size_t lo, size_t hi, size_t c) {
+        HostSrc src{s.t};
+        for (size_t i = lo; i < hi; i++) {
+            samtext::Rec r;
+            r.ref = -1;
+            r.pos1 = 0;
+            r.qlen = r.flag = r.mapq = 0;
+            uint32_t type;
+            const uint32_t e = bedreads::parse_line(src, s.line_start(i), s.nl[i], nm, type, r);
+            if (type == bedreads::L_READ && first_read[c] == ~0ull) first_read[c] = i;
+            if (type == bedreads::L_TRACK) tracks[c].push_back(i);
+            if (e) {
+                first_err[c] = ((uint64_t)i << 8) | e;
+                return;
+            }
+            s.ref[i] = r.ref;
+            s.pos[i] = r.pos1;
+            s.qlen[i] = r.qlen;
+            s.fm[i] = r.flag | (r.mapq << 16);
+            key[i] = bedreads::sort_key(r.ref, r.pos1, nref);
+            if (i > lo && key[i] < key[i - 1]) unsorted[c] = 1;
+        }
+    });
+    uint64_t fe = chunks ? *std::min_element(first_err.begin(), first_err.end()) : ~0ull;
+    const uint64_t fr = chunks ? *std::min_element(first_read.begin(), first_read.end()) : ~0ull;
+    std::vector<uint64_t> tr;
+    for (const auto &v : tracks) tr.insert(tr.end(), v.begin(), v.end());
+    uint64_t tline = 0;
+    if (const uint32_t tc = bedreads::track_error(tr, fr, tline))
+        if ((tline << 8 | tc) < fe) fe = tline << 8 | tc;
+    if (fe != ~0ull) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bedreads::line_error(fe >> 8, (uint32_t)(fe & 255u)));
+    bool sorted = true;
+    for (size_t c = 0; c < chunks && sorted; c++)
+        sorted = !unsorted[c] && (c == 0 || key[c * grain] >= key[c * grain - 1]);
+    const uint64_t none = (uint64_t)nref << 31;
+    uint64_t reads = 0;
+    for (uint64_t k : key) reads += k < none;
+    if (!sorted) {
+        std::vector<std::pair<uint64_t, uint32_t>> kv(n);
+        for (uint64_t i = 0; i < n; i++) kv[i] = {key[i], (uint32_t)i};
+        std::stable_sort(kv.begin(), kv.end(), [](const std::pair<uint64_t, uint32_t> &x, const std::pair<uint64_t, uint32_t> &y) {
+            return x.first < y.first;
+        });
+        std::vector<int32_t> ref(reads), pos(reads);
+        std::vector<uint32_t> qlen(reads), fm(reads);
+        std::vector<uint64_t> ls(reads);
+        parallel_for(s.nthreads, reads, grain, [&](size_t lo, size_t hi, size_t) {
+            for (size_t i = lo; i < hi; i++) {
+                const uint32_t j = kv[i].second;
+                ref[i] = s.ref[j];
+                pos[i] = s.pos[j];
+                qlen[i] = s.qlen[j];
+                fm[i] = s.fm[j];
+                ls[i] = s.line_start(j);
+            }
+        });
+        s.ref.swap(ref);
+        s.pos.swap(pos);
+        s.qlen.swap(qlen);
+        s.fm.swap(fm);
+        s.ls.swap(ls);
+    }
+    s.nrec = reads;                 // (in order, the lines without a read are behind the reads)
+}
+
 }  // namespace
 
 extern "C" {
+
+int pmx_bed_open(const char *path, int nthreads, int32_t nref, const char *const *names, const int64_t *lengths, pmx_sam **out)
+{
+    if (!path || !out) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bed_open: NULL argument");
+    *out = nullptr;
+    pmx_sam *s = new pmx_sam();
+    try {
+        const std::string why = bedreads::check_sizes(nref, names, lengths, s->h.names, s->h.lens);
+        if (!why.empty()) throw pmx_io::Error(PMX_IO_ERR_INVALID, why);
+        bedreads::name_table(s->h.names, s->h.bytes, s->h.off, s->h.slot);
+        s->file.open(path);
+        s->nthreads = pmx_io::pick_threads(nthreads);
+        const uint8_t *d = s->file.data;
+        const size_t n = s->file.size;
+        const int comp = ttrack::detect_compression(d, n);
+        if (comp == ttrack::COMP_PLAIN) {
+            s->t = d;
+            s->N = n;
+        } else {
+            bool ok = false;
+            if (comp == ttrack::COMP_BGZF) {
+                try {
+                    pmx_io::bgzf_inflate_all(d, n, s->nthreads, s->inflated, s->members);
+                    ok = true;
+                } catch (const pmx_io::Error &) {   // the words of the gzip path below: where the text breaks off
+                }
+                s->members = 0;                     // (as the device reader counts: 0 for every BED file)
+            }
+            std::string err;
+            if (!ok && !ttrack::inflate_gzip(d, n, s->inflated, err)) throw pmx_io::Error(PMX_IO_ERR_FORMAT, err);
+            s->t = s->inflated.data();
+            s->N = s->inflated.size();
+        }
+        bed_parse_sort(*s);
+    } catch (const pmx_io::Error &e) {
+        delete s;
+        return pmx_io::fail(e.code, std::string(path) + ": " + e.msg);
+    } catch (const std::exception &e) {
+        delete s;
+        return pmx_io::fail(PMX_IO_ERR_OPEN, std::string(path) + ": " + e.what());
+    }
+    *out = s;
+    return PMX_IO_OK;
+}
 
 int pmx_sam_open(const char *path, int nthreads, pmx_sam **out)
 {
@@ -311,8 +448,10 @@ int64_t pmx_sam_readlen_hist(pmx_sam *s, uint32_t mapq_min, int64_t cap, int32_t
                         continue;
                     }
                     out.c[2]++;
-                    auto it = out.h.emplace((int32_t)q, std::make_pair((uint64_t)0, (uint64_t)s->line_start(i))).first;
+                    const uint64_t key = s->line_start(i);
+                    auto it = out.h.emplace((int32_t)q, std::make_pair((uint64_t)0, key)).first;
                     it->second.first++;
+                    it->second.second = std::min(it->second.second, key);   // (a BED file put in order: lines out of order)
                 }
             });
             std::unordered_map<int32_t, std::pair<uint64_t, uint64_t>> hist;

@@ -1,5 +1,6 @@
 """Which reader a run reads its input through: the one place that chooses between the host readers (libpymasc_io.so) and
-the device readers (libpymasc_ingest.so) of an alignment file -- BAM, or SAM (pymasc_amd.sam) -- and of a mappability track: BigWig, or text (pymasc_amd.text_track).
+the device readers (libpymasc_ingest.so) of an alignment file -- BAM, SAM (pymasc_amd.sam) or BED reads (pymasc_amd.bed_reads) -- and
+of a mappability track: BigWig, or text (pymasc_amd.text_track).
 
 The reader modules import ``find_index`` from here, so they are imported inside the openers, and the device classes are
 looked up through their module each time (a test may replace ``bam_device.DeviceBamReader``).
@@ -56,14 +57,32 @@ def whole_file_footprint(path) -> int:
     return fsize + inflated + 13 * (inflated // 36)
 
 
-def open_alignments(path, device_ingest: bool, device: int = 0, references=None, index=None):
+def bed_sizes(path, chrom_sizes):
+    """(references, lengths) of a BED read file (``bed_reads.is_bed_reads``) from ``chrom_sizes``; ValueError without them."""
+    from .bed_reads import chrom_sizes_of
+    if chrom_sizes is None:
+        raise ValueError("'{}' is a BED read file: give the chromosome sizes (chrom_sizes=, --chrom-sizes)".format(os.fspath(path)))
+    return chrom_sizes_of(chrom_sizes)
+
+
+def open_alignments(path, device_ingest: bool, device: int = 0, references=None, index=None, chrom_sizes=None):
     """The reader of an alignment file: ``DeviceSamReader`` / ``DeviceBamReader`` on ``device`` with ``device_ingest``, else
     ``SamReader`` / ``BamReader``.  ``references`` and ``index`` as ``DeviceBamReader`` takes them (the host readers read the
     whole file and leave the choice of chromosomes to ``feed``); ``index=False`` also opens the host BAM reader without its
     .bai, as a read-length estimate over the whole file wants it.  A stream (``is_stream``) is read by
     ``DeviceStreamReader`` and needs ``device_ingest``; so is a whole BAM file whose footprint (``whole_file_footprint``)
-    exceeds ``device_ingest_budget``, where the whole-file reader would fail to allocate."""
-    from . import bam, bam_device, sam, stream_device
+    exceeds ``device_ingest_budget``, where the whole-file reader would fail to allocate.  A BED read file
+    (``bed_reads.is_bed_reads``: named .tagAlign / .bed) is read by ``DeviceBedReadsReader`` / ``BedReadsReader`` with the
+    references of ``chrom_sizes`` (a path or an ordered ``{name: length}``; ValueError without them), never as a stream
+    (DESIGN.md 7.11); other files do not use ``chrom_sizes``."""
+    from . import bam, bam_device, bed_reads, sam, stream_device
+    if bed_reads.is_bed_reads(path):
+        names, lengths = bed_sizes(path, chrom_sizes)
+        if is_stream(path):
+            raise ValueError("'{}' is a BED read file: it is sorted whole, so it cannot be read as a stream".format(os.fspath(path)))
+        if device_ingest:
+            return bed_reads.DeviceBedReadsReader(path, names, lengths, device=device, select=references)
+        return bed_reads.BedReadsReader(path, names, lengths)
     if is_stream(path):
         if not device_ingest:
             raise ValueError("'{}' is a stream: it is read by the device reader only (one rank, a GPU)".format(os.fspath(path)))
@@ -78,10 +97,13 @@ def open_alignments(path, device_ingest: bool, device: int = 0, references=None,
     return sam.SamReader(path) if is_sam else bam.BamReader(path, index=index)
 
 
-def open_header(path):
+def open_header(path, chrom_sizes=None):
     """The host reader of an alignment file with its header read and no record: ``references`` / ``lengths``.  A BAM file's
-    open reads the header only (its records are read by ``feed``); a SAM file is opened with ``header_only``."""
-    from . import bam, sam
+    open reads the header only (its records are read by ``feed``); a SAM file is opened with ``header_only``; a BED read file
+    gives the references of ``chrom_sizes`` once it is found readable (``bed_reads.SizesHeader``; none of it is read)."""
+    from . import bam, bed_reads, sam
+    if bed_reads.is_bed_reads(path):
+        return bed_reads.SizesHeader(path, *bed_sizes(path, chrom_sizes))
     return sam.SamReader(path, header_only=True) if sam.is_sam(path) else bam.BamReader(path, index=False)
 
 

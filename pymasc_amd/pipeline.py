@@ -35,7 +35,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
         device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
         library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
-        chi2_pval: float = 0.05):
+        chi2_pval: float = 0.05, chrom_sizes=None):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -50,9 +50,12 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     ``stats``: rank 0 also writes ``<stem>_stats.tab`` (pymasc_amd.stats.genome_wide_stats / write_stats) with PyMaSC's
     options -l ``library_length``, -w ``smooth_window``, --mask-size ``mask_size``, --bg-avr-width ``bg_avr_width`` and
     --chi2-pval ``chi2_pval``.  A ``library_length`` longer than ``max_shift`` or below 1, or a ``smooth_window`` below 1, is
-    a ValueError before any GPU work (PyMaSC logs a too long ``library_length`` and ignores it)."""
+    a ValueError before any GPU work (PyMaSC logs a too long ``library_length`` and ignores it).
+    ``bam_path`` may also be a BED read file (tagAlign, ``pymasc_amd.bed_reads``); its references are ``chrom_sizes`` (a path or
+    an ordered ``{name: length}``), without which it is a ValueError; other inputs keep their header's."""
     if references is not None and chromfilter is not None:
         raise ValueError("give references or chromfilter, not both")
+    _check_bed_sizes(bam_path, chrom_sizes)
     from .stats import check_params
     check_params(None, library_length, smooth_window, max_shift)
     stat_opts = None
@@ -67,22 +70,31 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     try:
         if read_len is None:
             read_len, bam = _estimate_read_len(bam_path, max_shift, mapq_criteria, readlen_estimator, device, group,
-                                               context, device_ingest, world)
+                                               context, device_ingest, world, chrom_sizes)
         return _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path,
                     skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, rank,
-                    chromfilter, stat_opts)
+                    chromfilter, stat_opts, chrom_sizes)
     finally:
         if bam is not None:
             bam.close()
 
 
-def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, group, context, device_ingest, world):
+def _check_bed_sizes(path, chrom_sizes) -> None:
+    """A BED read file needs ``chrom_sizes``: ValueError before any work."""
+    from .bed_reads import is_bed_reads
+    if chrom_sizes is None and is_bed_reads(path):
+        raise ValueError("'{}' is a BED read file: give the chromosome sizes (chrom_sizes=, --chrom-sizes)".format(path))
+
+
+def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, group, context, device_ingest, world,
+                       chrom_sizes=None):
     """(read length, the device reader it was estimated on or None).  One rank: on the device reader that the run then
     feeds from when the BAM file goes through the GPU, on the host reader otherwise.  Several ranks: rank 0 estimates on the
     host reader and broadcasts the value or its error (sharding.on_rank0); every rank raises on an error, none waits."""
     readlen._check_esttype(esttype)                     # (every rank: a wrong name fails before any collective)
     if world == 1 and (default_device_ingest(world, context) if device_ingest is None else device_ingest):
-        bam = open_alignments(bam_path, True, device=(context.device if context is not None else device))
+        bam = open_alignments(bam_path, True, device=(context.device if context is not None else device),
+                              chrom_sizes=chrom_sizes)
         try:
             return readlen.estimate_from_reader(bam, esttype, mapq_criteria, max_shift), bam
         except BaseException:
@@ -90,14 +102,14 @@ def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, grou
             raise
 
     def estimate():                 # the whole file: the host reader without its index
-        with open_alignments(bam_path, False, index=False) as b:
+        with open_alignments(bam_path, False, index=False, chrom_sizes=chrom_sizes) as b:
             return readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift)
     return int(on_rank0(estimate, group, "read length estimation")), None
 
 
 def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path, skip_ncc,
          references, device, save_mappability_stats, group, context, device_ingest, bam, rank, chromfilter=None,
-         stat_opts=None):
+         stat_opts=None, chrom_sizes=None):
     # The mappable-length cache (handler/mappability.py:239-309): loaded when valid; otherwise computed ONCE, on rank 0,
     # written atomically, and broadcast -- the other ranks neither recompute it per chromosome nor read a file that is
     # being rewritten.
@@ -118,7 +130,8 @@ def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path,
     known = None if mappability_path is None else on_rank0(mappable_lengths, group, "mappability statistics")
     result = run_sharded(bam_path, max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
                          references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
-                         group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter)
+                         group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter,
+                         chrom_sizes=chrom_sizes)
     written: List[Path] = []
     if rank == 0:
         written = _write_outputs(outdir, Path(bam_path).stem, result, read_len, stat_opts)
@@ -153,13 +166,15 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
               device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
               library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
-              chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None) -> List[FileResult]:
+              chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``.
 
     ``names``: PyMaSC's -n, paired with the files by position (a missing or None name: ``Path(file).stem``, so that a file
     without a name gets exactly what ``run`` writes for it); a name ``N`` gives ``N_cc.tab`` ... ``N_stats.tab``, whole even
-    when it holds a dot.  More names than files, an empty name or one with a path separator, and two files with the same base
+    when it holds a dot.  ``chrom_sizes``: the references of every BED read file among ``paths`` (``run``); a BED read file
+    without them is skipped in step 1 with run's ValueError, and BAM / SAM files keep their header's lengths (logged once when
+    ``chrom_sizes`` is given beside them).  More names than files, an empty name or one with a path separator, and two files with the same base
     name are a ValueError before any work, as bad options are.  Outputs that exist already are warned about first
     (pymasc.py:178-182).
 
@@ -203,6 +218,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
     _collective_device_setup(device, group)
     if rank == 0:
         _warn_existing(outdir, bases, mappability_path is not None, skip_ncc, stats)
+        if chrom_sizes is not None and not all(_is_bed(p) for p in paths):
+            logger.info("The chromosome sizes are used for BED read files only: BAM and SAM files keep their header's lengths.")
     ingest = bool(default_device_ingest(world, context) if device_ingest is None else device_ingest)
     dev = context.device if (context is not None and ingest) else device         # the device readers' GPU
 
@@ -212,11 +229,12 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
     try:
         if world == 1:
             read_len, kept = _choose(paths, errors, read_len, chromfilter, readlen_estimator, mapq_criteria, max_shift,
-                                     dev if ingest else None)
+                                     dev if ingest else None, chrom_sizes)
         else:                       # rank 0 decides, every rank learns the same (none waits for a value that never comes)
             def choose():
                 errs: List[Optional[BaseException]] = [None] * len(paths)
-                rl, _k = _choose(paths, errs, read_len, chromfilter, readlen_estimator, mapq_criteria, max_shift, None)
+                rl, _k = _choose(paths, errs, read_len, chromfilter, readlen_estimator, mapq_criteria, max_shift, None,
+                                 chrom_sizes)
                 return rl, [None if e is None else _portable(e) for e in errs]
             read_len, errors = on_rank0(choose, group, "choosing the input files")
         if read_len is None:
@@ -251,7 +269,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
                 result = run_sharded(paths[i], max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
                                      references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
                                      group=group, context=ctx, device_ingest=ingest, bam=bam, chromfilter=chromfilter,
-                                     track=track)
+                                     track=track, chrom_sizes=chrom_sizes)
             except Exception as e:
                 skip = _unsorted_on_every_rank(e, world)
                 if skip is None:
@@ -307,13 +325,19 @@ def _warn_existing(outdir, bases, has_track, skip_ncc, stats):
                 logger.warning("Existing file '{}' will be overwritten.".format(path))
 
 
-def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_shift, device):
+def _is_bed(path) -> bool:
+    from .bed_reads import is_bed_reads
+    return is_bed_reads(path)
+
+
+def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_shift, device, chrom_sizes=None):
     """Steps 1 and 2 of run_files: the files that open and keep a chromosome, then the common read length.  Fills ``errors``
     with the exception of every file skipped; returns (read length or None when no file is left, {index: device reader} of
     the readers opened here that feed their file's run).  ``device``: the GPU of the device reader the estimates are made on,
     None for the host reader.  A stream (inputs.is_stream: ``-``, a FIFO) is opened once, here, by the stream reader, which
     then feeds its run; without ``read_len`` it is skipped before a byte of it is read (PyMaSC: handler/calc.py:81,
-    pymasc.py:199-201), and without the device reader (``device`` None) too."""
+    pymasc.py:199-201), and without the device reader (``device`` None) too.  A BED read file takes its references from
+    ``chrom_sizes`` (inputs.open_header); without them it is skipped here."""
     kept = {}
     for i, p in enumerate(paths):
         stream = is_stream(p)
@@ -328,7 +352,7 @@ def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_sh
             errors[i] = ValueError("'{}' is a stream: it needs the device reader".format(p))
             continue
         try:
-            r = open_alignments(p, True, device=device) if stream else open_header(p)
+            r = open_alignments(p, True, device=device) if stream else open_header(p, chrom_sizes)
             try:
                 if not r.references:
                     raise ValueError("File has no sequences defined.")
@@ -355,9 +379,9 @@ def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_sh
     for i in live:
         logger.info("Check read length... : {}".format(paths[i]))
         if device is None:
-            r = open_alignments(paths[i], False, index=False)       # the whole file: the host reader without its index
+            r = open_alignments(paths[i], False, index=False, chrom_sizes=chrom_sizes)   # the whole file, without its index
         else:
-            r = open_alignments(paths[i], True, device=device)
+            r = open_alignments(paths[i], True, device=device, chrom_sizes=chrom_sizes)
         estimated = False
         try:
             lengths.append(readlen.estimate_from_reader(r, esttype, mapq_criteria, max_shift))

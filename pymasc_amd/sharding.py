@@ -213,7 +213,7 @@ def reconcile_chromosome_sizes(bam_sizes: Dict[str, int], external_sizes: Dict[s
 def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, bigwig_path=None,
                 references: Sequence[str] = None, skip_ncc: bool = False, device: int = None, context=None,
                 chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None, chromfilter=None,
-                track=None):
+                track=None, chrom_sizes=None):
     """BAM (+ BigWig) -> genome-wide result on every rank; chromosomes LPT-sharded over the ranks by length.
 
     Launch: one process per GPU under ``torch.distributed`` (torchrun, or pymasc_amd.launch.spawn_ranks), the process
@@ -240,14 +240,20 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     is the whole-file one above.
     ``track``: a reader of ``bigwig_path`` the caller has already opened (pipeline.run_files opens the track once for all its
     files), used instead of opening one and left open, like ``bam``.
+    ``chrom_sizes``: the references of a BED read file (``pymasc_amd.bed_reads``; a path or an ordered ``{name: length}``),
+    which is read whole like SAM text -- by every rank of several through the host reader -- and is a ValueError without them.
     With a ``context`` given, the calculator still gives its bit-vectors back to the context's pool and frees its result arena
     before this returns (``CCHipCalculator.close`` never closes a context it does not own)."""
     from .calculator import CCHipCalculator
     from .chromfilter import filter_references
     from .inputs import default_device_ingest, find_index, open_alignments, open_track
     from .result import aggregate_results
+    from .bed_reads import is_bed_reads
     from .sam import is_sam
 
+    bed = is_bed_reads(bam_path)
+    if bed and chrom_sizes is None and bam is None:
+        raise ValueError("'{}' is a BED read file: give the chromosome sizes (chrom_sizes=, --chrom-sizes)".format(bam_path))
     on, rank, world = rank_and_world(group)
     if device is None and context is None and on:
         import os
@@ -267,11 +273,11 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     # indexed: the open reads the header only, the rank's share is selected below.  SAM text: the unindexed-BAM rules
     # 
     indexed = (device_ingest and bam is None and (world > 1 or references is not None or chromfilter is not None)
-               and not is_sam(bam_path) and find_index(bam_path) is not None)
+               and not bed and not is_sam(bam_path) and find_index(bam_path) is not None)
     reader, bw = bam, None          # the caller's readers are used, not closed
     try:
         if reader is None:
-            reader = open_alignments(bam_path, device_ingest, dev, references=[] if indexed else None)
+            reader = open_alignments(bam_path, device_ingest, dev, references=[] if indexed else None, chrom_sizes=chrom_sizes)
         if chromfilter is not None:
             names = filter_references(reader.references, chromfilter)
         else:

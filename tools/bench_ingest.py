@@ -375,6 +375,73 @@ def time_text_track(path, reps=3):
             "speedup": round(min(host) / min(dev), 2)}
 
 
+BED_FILES = [(order, comp) for order in ("sorted", "shuffled") for comp in ("none", "gzip", "bgzf")]
+
+
+def bed_file_name(directory, order, comp):
+    return os.path.join(directory, "reads.{}.tagAlign{}".format(order, {"none": "", "gzip": ".gz", "bgzf": ".bgz"}[comp]))
+
+
+def synth_bed_reads(directory, nlines, seed=11):
+    """A seeded tagAlign file of `nlines` 36-bp reads over the hg38 chromosomes in proportion to their length (ENCODE's layout:
+    "chrom start end N 1000 strand"), sorted and `shuf`-shuffled, each plain, gzip and BGZF: the six files of BED_FILES (made
+    once, reused when present).  Returns (sizes, seconds)."""
+    import gzip
+    t0 = time.time()
+    if all(os.path.exists(bed_file_name(directory, o, c)) for o, c in BED_FILES):
+        return HG38, 0.0
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    total = sum(l for _n, l in HG38)
+    lines = []
+    for n, l in HG38:
+        per = max(1, int(nlines * l / total))
+        b = np.sort(rng.integers(0, l - 36, per))
+        strand = np.where(rng.integers(0, 2, per) == 1, "\tN\t1000\t-", "\tN\t1000\t+")
+        lines.append(np.char.add(np.char.add(np.char.add(n + "\t", b.astype(str)), np.char.add("\t", (b + 36).astype(str))), strand))
+    lines = np.concatenate(lines)
+    for order in ("sorted", "shuffled"):
+        if order == "shuffled":
+            lines = lines[rng.permutation(lines.size)]
+        data = ("\n".join(lines.tolist()) + "\n").encode()
+        for comp in ("none", "gzip", "bgzf"):
+            out = data if comp == "none" else gzip.compress(data, 1) if comp == "gzip" else W.bgzf_compress(data, level=1)
+            with open(bed_file_name(directory, order, comp), "wb") as fp:
+                fp.write(out)
+    return HG38, time.time() - t0
+
+
+def time_bed_reads(path, sizes, mapq, reps=3, host=True):
+    """Open + decode at `mapq`: BedReadsReader on 16 threads against DeviceBedReadsReader (records left in HBM), best of `reps`
+    (the file is in the page cache after the first read); the same records from both."""
+    from pymasc_amd.bed_reads import BedReadsReader, DeviceBedReadsReader
+    names, lens = [n for n, _ in sizes], [l for _, l in sizes]
+    out = {}
+    if host:
+        hs = []
+        for _ in range(reps):
+            t0 = time.time()
+            with BedReadsReader(path, names, lens, threads=16) as r:
+                kept = r.decode(mapq)
+                ref, pos, _rl, rev = r._fetch(0, kept)
+            hs.append(round(time.time() - t0, 4))
+        out["host_reader_s"] = hs
+    ds, phases = [], None
+    for _ in range(reps):
+        t0 = time.time()
+        with DeviceBedReadsReader(path, names, lens) as r:
+            dk = r.decode(mapq)
+            ds.append(round(time.time() - t0, 4))
+            phases = r.timings()
+            if host and _ == 0:
+                dref, dpos, _drl, drev = r._fetch(0, dk)
+                assert dk == kept and (dref == ref).all() and (dpos == pos).all() and (drev == rev).all()
+    out.update({"kept": dk, "device_reader_s": ds, "device_phases_s": phases})
+    if host:
+        out["speedup"] = round(min(out["host_reader_s"]) / min(ds), 2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=5_000_000)
@@ -393,8 +460,30 @@ def main():
                     help="write a seeded hg38-shaped text track and time TextTrackReader against DeviceTextTrackReader")
     ap.add_argument("--compress", choices=["none", "bgzf", "gzip"], default="none", help="compression of the --track-text file")
     ap.add_argument("--lines", type=int, default=20_000_000, help="about how many lines the --track-text file has")
+    ap.add_argument("--bed", action="store_true",
+                    help="write a seeded tagAlign file of --lines reads, sorted and shuffled, plain / gzip / BGZF, and time "
+                         "BedReadsReader (16 threads) against DeviceBedReadsReader")
+    ap.add_argument("--bed-dir", default="/tmp/pymasc_bed_bench", help="where the --bed files are made (and kept)")
+    ap.add_argument("--bed-only", default=None, help="--bed: time only ORDER-COMP (e.g. shuffled-none), on the device only")
+    ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+
+    if a.bed:
+        sizes, gen_s = synth_bed_reads(a.bed_dir, a.lines)
+        res = {"lines": a.lines, "generate_s": round(gen_s, 1), "mapq": a.mapq, "files": []}
+        for order, comp in BED_FILES:
+            if a.bed_only and a.bed_only != "{}-{}".format(order, comp):
+                continue
+            path = bed_file_name(a.bed_dir, order, comp)
+            r = {"order": order, "compress": comp, "file_bytes": os.path.getsize(path)}
+            r.update(time_bed_reads(path, sizes, a.mapq, a.reps, host=a.bed_only is None))
+            res["files"].append(r)
+            print(json.dumps(r), flush=True)
+        if a.out:
+            with open(a.out, "w") as fp:
+                json.dump(res, fp, indent=1)
+        return
 
     if a.track_text:
         path = a.path + "." + a.track_text + {"none": "", "bgzf": ".gz", "gzip": ".gz"}[a.compress]
