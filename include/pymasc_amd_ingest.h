@@ -174,6 +174,11 @@ int pmx_dbw_device_arrays(const pmx_dbw *w, const uint32_t **d_begin, const uint
 /* 1 when the intervals of the last fetch are non-empty, ascending and disjoint (begin_i < end_i <= begin_(i+1): BigWig order) */
 int pmx_dbw_sorted(const pmx_dbw *w);
 int pmx_dbw_copy(pmx_dbw *w, int64_t first, int64_t n, uint32_t *begin, uint32_t *end, float *value);
+/* bigBed on the device (version >= 7): pmx_dbw_open also takes a bigBed file, read by the rules of pmx_bigwig_open
+ * (pymasc_amd_io.h, its checker).  Its blocks are inflated and Adler-32-checked as a BigWig's; k_bb_records walks each block's
+ * record chain (one wavefront per block) and writes [chromStart, chromEnd) with value 1.0.  pmx_dbw_kind: 0 BigWig (or a text
+ * track), 1 bigBed. */
+int pmx_dbw_kind(const pmx_dbw *w);
 
 /* Text tracks on the device (version >= 5): `path` is a bedGraph, BED or WIG file, plain, BGZF or gzip, read by
  * the rules of pmx_ttrack_open (pymasc_amd_io.h, its checker).  Plain text is copied to HBM through the staging buffers; BGZF goes

@@ -156,6 +156,12 @@ int64_t pmx_bigwig_chrom_len(const pmx_bigwig *w, int32_t i);
 int64_t pmx_bigwig_fetch(pmx_bigwig *w, const char *chrom, float threshold, int64_t cap,
                          uint32_t *begin, uint32_t *end, float *value);
 
+/* bigBed (version >= 5): pmx_bigwig_open also takes a bigBed file (magic 0x8789F2EB; fieldCount >= 3).  Its
+ * records, decoded by the rules of io/bigbed_parse.h, are the intervals [chromStart, chromEnd) with value 1.0 in index order;
+ * fetch keeps them as it keeps BigWig items.  A malformed record, end < start, a block of two chromosomes, a block that does not
+ * inflate or fails its Adler-32: PMX_IO_ERR_FORMAT with bigbed_parse.h's message.  pmx_bigwig_kind: 0 BigWig, 1 bigBed. */
+int pmx_bigwig_kind(const pmx_bigwig *w);
+
 /* ---- Text tracks: bedGraph, BED, WIG -------------------------------------------------------
  * The host twin of pmx_dtt_open (pymasc_amd_ingest.h) and its checker.  `path` is plain text, BGZF or gzip (one or several
  * members; told from the bytes).  The kind: a track line's type=bedGraph / type=wiggle_0, else a WIG declaration as the first

@@ -38,7 +38,7 @@ IO_EXPORTS = [
     "pmx_sam_open", "pmx_sam_open_header", "pmx_sam_close", "pmx_sam_nref", "pmx_sam_ref_name", "pmx_sam_ref_len", "pmx_sam_header_text",
     "pmx_sam_decode", "pmx_sam_fetch", "pmx_sam_counters", "pmx_sam_readlen_hist", "pmx_sam_readlen_counters",
     "pmx_bigwig_open", "pmx_bigwig_close", "pmx_bigwig_nchrom", "pmx_bigwig_chrom_name", "pmx_bigwig_chrom_len",
-    "pmx_bigwig_fetch",
+    "pmx_bigwig_fetch", "pmx_bigwig_kind",
     "pmx_ttrack_open", "pmx_ttrack_close", "pmx_ttrack_nchrom", "pmx_ttrack_chrom_name", "pmx_ttrack_chrom_len",
     "pmx_ttrack_fetch", "pmx_ttrack_sorted", "pmx_bed_open",
 ]
@@ -140,6 +140,8 @@ def load_io_library():
     L.pmx_bigwig_chrom_len.restype = i64
     L.pmx_bigwig_fetch.argtypes = [vp, ctypes.c_char_p, ctypes.c_float, i64, vp, vp, vp]
     L.pmx_bigwig_fetch.restype = i64
+    L.pmx_bigwig_kind.argtypes = [vp]
+    L.pmx_bigwig_kind.restype = ctypes.c_int
     L.pmx_ttrack_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(vp)]
     L.pmx_ttrack_open.restype = ctypes.c_int
     L.pmx_ttrack_close.argtypes = [vp]

@@ -5,6 +5,8 @@ Same surface as the reference's BigWigReader (PyMaSC/reader/bigwig.pyx:100-200):
 with value >= valfilter only when valfilter > 0), ``disable_progress_bar``, ``close`` -- so it drops into
 ``CCHipCalculator(bwfeeder=...)`` and ``MappabilityStats(feeder=...)`` where the reference passes its own reader.
 ``fetch_arrays`` is the bulk form the calculator prefers: numpy arrays straight into ``pmx_bits_set_regions``.
+A bigBed file (the same bbi container) is read by the same reader: its records are intervals of value 1 (DESIGN.md 7.12);
+``kind`` tells the two apart.
 """
 from __future__ import annotations
 
@@ -17,6 +19,7 @@ import numpy as np
 from .bam import NativeReader, PmxIOError, _raise, load_io_library  # noqa: F401  (PmxIOError re-exported)
 
 PMX_IO_ERR_NOTFOUND = -4
+KINDS = ("bigwig", "bigbed")
 
 
 class BigWigReader(NativeReader):
@@ -36,6 +39,13 @@ class BigWigReader(NativeReader):
         n = self._L.pmx_bigwig_nchrom(h)
         self.chromsizes: Dict[str, int] = {
             self._L.pmx_bigwig_chrom_name(h, i).decode(): int(self._L.pmx_bigwig_chrom_len(h, i)) for i in range(n)}
+        self.kind = KINDS[self._L.pmx_bigwig_kind(h)]
+        self._sorted = True
+
+    @property
+    def sorted(self) -> bool:
+        """The intervals of the last fetch are non-empty, ascending and disjoint (what pmx_dbw_sorted says on the device)."""
+        return self._sorted
 
     def fetch_arrays(self, valfilter: float, chrom: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(begin, end, value) arrays of the chromosome's intervals with value >= valfilter."""
@@ -58,6 +68,7 @@ class BigWigReader(NativeReader):
             if m < 0:
                 _raise(m)
             assert m == n
+        self._sorted = bool((begin < end).all() and (end[:-1] <= begin[1:]).all())
         return begin, end, value
 
     def fetch(self, valfilter: float, chrom: str) -> Iterator[Tuple[int, int, float]]:

@@ -4,7 +4,8 @@
 PyMaSC/reader/bigwig.pyx the calculation touches: ``chromsizes``, ``fetch(valfilter, chrom)``, ``fetch_arrays``, ``close`` -- plus
 ``fetch_device``, which leaves a chromosome's intervals in HBM for ``CCHipCalculator`` to build its mappability vector from
 (pmx_bits_set_regions_dev_ex).  The file is copied to the GPU once; data blocks are inflated (the BGZF kernel), Adler-32-checked and
-decoded by HIP kernels.  No host fallback: without a GPU the constructor raises.
+decoded by HIP kernels.  No host fallback: without a GPU the constructor raises.  A bigBed file is read by the same reader
+(``kind == "bigbed"``; k_bb_records decodes its records).
 """
 from __future__ import annotations
 
@@ -41,6 +42,15 @@ class DeviceBigWigReader(NativeReader):
         n = self._L.pmx_dbw_nchrom(h)
         self.chromsizes: Dict[str, int] = {self._L.pmx_dbw_chrom_name(h, i).decode(): int(self._L.pmx_dbw_chrom_len(h, i))
                                            for i in range(n)}
+
+    @property
+    def kind(self) -> str:
+        return ("bigwig", "bigbed")[self._L.pmx_dbw_kind(self._h)]
+
+    @property
+    def sorted(self) -> bool:
+        """The intervals of the last fetch are non-empty, ascending and disjoint."""
+        return bool(self._L.pmx_dbw_sorted(self._h))
 
     def fetch_device(self, valfilter: float, chrom: str) -> Tuple[int, int, int, bool]:
         """The chromosome's intervals with value >= valfilter, left in device memory: (address of uint32 begin[], address of

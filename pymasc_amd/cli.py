@@ -77,7 +77,8 @@ def ranks_option(group) -> None:
 
 def track_options(group) -> None:
     group.add_argument("-m", "--mappability", metavar="TRACK", type=Path,
-                       help="mappability track: BigWig, or bedGraph / BED / WIG text, plain or gzip / bgzip-compressed; "
+                       help="mappability track: BigWig, bigBed (every interval counts as 1), or bedGraph / BED / WIG text, "
+                            "plain or gzip / bgzip-compressed; "
                             "positions with a value of at least 1 count as mappable")
     group.add_argument("--mappability-stats", metavar="JSON", type=Path,
                        help="where the mappable-length cache is read and written (default: the track's path with "

@@ -1773,7 +1773,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 6; }
+int pmx_dbam_version(void) { return 7; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -2531,6 +2531,7 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 }  // extern "C"
 
 #include "bigwig_device.inc"
+#include "bigbed_device.inc"
 #include "sam_device.inc"
 #include "stream_device.inc"
 #include "text_track_device.inc"

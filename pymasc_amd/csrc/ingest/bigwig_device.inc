@@ -7,6 +7,11 @@
 // sections (bedGraph / variableStep / fixedStep items) decoded and filtered by k_bw_sections, and the intervals land in device
 // arrays in index order, where pmx_bits_set_regions_dev_ex (include/pymasc_amd.h) builds the mappability vector from them.
 // Same intervals as pmx_bigwig_fetch (libpymasc_io.so, the checker), bit for bit.
+//
+// A bigBed file (io/bigbed_parse.h, DESIGN.md 7.12) takes the same path up to the decode: its blocks hold BED records, walked by
+// k_bb_records (bigbed_device.inc) in place of k_bw_sections.
+
+#include "../io/bigbed_parse.h"
 
 enum { BW_OK = 0, BW_ERR_HEADER = 20, BW_ERR_TYPE = 21, BW_ERR_ITEMS = 22, BW_ERR_ADLER = 23 };
 
@@ -152,6 +157,7 @@ struct pmx_dbw {
     u8 *d_file = nullptr;
     u64 chrom_tree_off = 0, index_off = 0;
     u32 uncompress_buf = 0;
+    bool bigbed = false;            // a bigBed file: data blocks of BED records (k_bb_records)
     std::vector<std::string> names;
     std::vector<u32> ids;
     std::vector<int64_t> sizes;
@@ -186,7 +192,8 @@ struct BwCursor {
     const pmx_dbw &w;
     const u8 *at(u64 off, u64 n) const
     {
-        if (off > w.fsize || n > w.fsize - off) throw BwErr{PMX_DBAM_ERR_FORMAT, "BigWig structure points past the end of the file"};
+        if (off > w.fsize || n > w.fsize - off)
+            throw BwErr{PMX_DBAM_ERR_FORMAT, std::string(w.bigbed ? "bigBed" : "BigWig") + " structure points past the end of the file"};
         return w.host.data() + off;
     }
     u32 r8(u64 off) const { return *at(off, 1); }
@@ -276,7 +283,10 @@ int bw_open(pmx_dbw &w, const char *path, int nthreads)
         const BwCursor c{w};
         const u32 magic = c.r32(0);
         if (magic == __builtin_bswap32(BW_MAGIC)) throw BwErr{PMX_DBAM_ERR_FORMAT, "byte-swapped (big-endian) BigWig files are not supported"};
-        if (magic != BW_MAGIC) throw BwErr{PMX_DBAM_ERR_FORMAT, "not a BigWig file (bad magic)"};
+        if (magic == __builtin_bswap32(bigbed::MAGIC)) throw BwErr{PMX_DBAM_ERR_FORMAT, bigbed::ERR_SWAPPED};
+        if (magic != BW_MAGIC && magic != bigbed::MAGIC) throw BwErr{PMX_DBAM_ERR_FORMAT, "not a BigWig file (bad magic)"};
+        w.bigbed = magic == bigbed::MAGIC;
+        if (w.bigbed && c.r16(32) < 3) throw BwErr{PMX_DBAM_ERR_FORMAT, bigbed::ERR_FIELDS};
         w.chrom_tree_off = c.r64(8);
         w.index_off = c.r64(24);
         w.uncompress_buf = c.r32(52);
@@ -380,6 +390,7 @@ void pmx_dbw_close(pmx_dbw *w)
 }
 
 int32_t pmx_dbw_nchrom(const pmx_dbw *w) { return w ? (int32_t)w->names.size() : 0; }
+int pmx_dbw_kind(const pmx_dbw *w) { return (w && w->bigbed) ? 1 : 0; }
 const char *pmx_dbw_chrom_name(const pmx_dbw *w, int32_t i)
 {
     return (w && i >= 0 && (size_t)i < w->names.size()) ? w->names[(size_t)i].c_str() : nullptr;
@@ -394,22 +405,32 @@ int64_t pmx_dbw_chrom_len(const pmx_dbw *w, int32_t i) { return (w && i >= 0 && 
 // fetch -- 36 ms for the 24 chromosomes of an hg38-shaped track against 15 ms of the host reader on 16 threads.)
 namespace {
 
+// (ends on any input, as the host walk does: a child lies strictly after its parent and inside the file, and at most
+// file size / 32 leaf items are read -- io/bigbed_parse.h)
 void bw_walk_all(const BwCursor &c, u64 node, std::vector<BwBlock> &out, int depth)
 {
     if (depth > 64) throw BwErr{PMX_DBAM_ERR_FORMAT, "R-tree too deep"};
     const bool leaf = c.r8(node) != 0;
     const u32 count = c.r16(node + 2);
     u64 p = node + 4;
+    if (leaf && out.size() + count > c.w.fsize / 32) throw BwErr{PMX_DBAM_ERR_FORMAT, bigbed::ERR_RTREE_ITEMS};
     for (u32 i = 0; i < count; i++) {
         if (leaf) {
             out.push_back(BwBlock{c.r64(p + 16), c.r64(p + 24)});
             p += 32;
         } else {
-            bw_walk_all(c, c.r64(p + 16), out, depth + 1);
+            const u64 child = c.r64(p + 16);
+            if (child <= node || child >= c.w.fsize) throw BwErr{PMX_DBAM_ERR_FORMAT, bigbed::ERR_RTREE_CHILD};
+            bw_walk_all(c, child, out, depth + 1);
             p += 24;
         }
     }
 }
+
+// bigbed_device.inc: k_bb_records<write> over the blocks, launched on `s` (hipGetLastError tells whether the launch failed)
+void bb_launch_records(bool write, dim3 grid, hipStream_t s, const u8 *base, const BwSpan *spans, u32 nblk, const u32 *chrom_lens,
+                       u32 nlens, float threshold, u32 *status, u32 *cnt, u32 *blk_chrom, const u64 *place, u32 *o_begin, u32 *o_end,
+                       float *o_value);
 
 int bw_decode_all(pmx_dbw *w, float threshold)
 {
@@ -473,7 +494,7 @@ int bw_decode_all(pmx_dbw *w, float threshold)
             const u8 *p = w->host.data() + b.offset;
             // zlib wrapper (RFC 1950): CMF / FLG in front, Adler-32 (big-endian) behind the DEFLATE stream
             if (b.size < 6 || (p[0] & 15u) != 8u || ((u32)p[0] * 256u + p[1]) % 31u != 0u || (p[1] & 32u))
-                return fail(PMX_DBAM_ERR_FORMAT, "BigWig data block does not inflate");
+                return fail(PMX_DBAM_ERR_FORMAT, w->bigbed ? bigbed::ERR_INFLATE : "BigWig data block does not inflate");
             const u8 *q = p + b.size - 4;
             mem[i].in_off = b.offset + 2;
             mem[i].out_off = (u64)i * stride;
@@ -496,7 +517,8 @@ int bw_decode_all(pmx_dbw *w, float threshold)
     } else {
         sp.resize(nb);
         for (u32 i = 0; i < nb; i++) {
-            if (blocks[i].size > 0xffffffffull) return fail(PMX_DBAM_ERR_FORMAT, "BigWig data block larger than 4 GB");
+            if (blocks[i].size > 0xffffffffull)
+                return fail(PMX_DBAM_ERR_FORMAT, w->bigbed ? "bigBed data block larger than 4 GB" : "BigWig data block larger than 4 GB");
             sp[i].off = blocks[i].offset;
             sp[i].size = (u32)blocks[i].size;
             sp[i].pad = 0;
@@ -506,10 +528,14 @@ int bw_decode_all(pmx_dbw *w, float threshold)
     BW_STEP("adler / spans")
     const u8 *base = z ? d_out : w->d_file;
     const dim3 grid((nb + 3) / 4);
-    hipLaunchKernelGGL(k_bw_sections<false>, grid, dim3(256), 0, w->stream, base, d_spans, nb, d_lens, (u32)lens.size(), threshold, d_status,
-                       d_cnt, d_bchrom, d_place, (u32 *)nullptr, (u32 *)nullptr, (float *)nullptr);
+    if (w->bigbed)
+        bb_launch_records(false, grid, w->stream, base, d_spans, nb, d_lens, (u32)lens.size(), threshold, d_status, d_cnt, d_bchrom, d_place,
+                          nullptr, nullptr, nullptr);
+    else
+        hipLaunchKernelGGL(k_bw_sections<false>, grid, dim3(256), 0, w->stream, base, d_spans, nb, d_lens, (u32)lens.size(), threshold,
+                           d_status, d_cnt, d_bchrom, d_place, (u32 *)nullptr, (u32 *)nullptr, (float *)nullptr);
     HIPOK(hipGetLastError());
-    BW_STEP("sections (count)")
+    BW_STEP(w->bigbed ? "records (count)" : "sections (count)")
     hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, w->stream, d_cnt, d_cnt, (u64)nb, d_place, d_tot);
     HIPOK(hipGetLastError());
     std::vector<u32> status(nb), cnt(nb), bchrom(nb);
@@ -522,7 +548,12 @@ int bw_decode_all(pmx_dbw *w, float threshold)
     HIPOK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, w->stream));
     HIPOK(hipStreamSynchronize(w->stream));   // (mem / sp / lens are locals)
     for (u32 i = 0; i < nb; i++)
-        if (status[i]) return fail(PMX_DBAM_ERR_FORMAT, status[i] >= BW_ERR_HEADER ? bw_err_text(status[i]) : "BigWig data block does not inflate");
+        if (status[i]) {
+            if (w->bigbed)
+                return fail(PMX_DBAM_ERR_FORMAT, status[i] >= bigbed::BB_ERR_TRUNCATED ? bigbed::err_text(status[i])
+                                                 : status[i] == BW_ERR_ADLER ? bigbed::ERR_ADLER : bigbed::ERR_INFLATE);
+            return fail(PMX_DBAM_ERR_FORMAT, status[i] >= BW_ERR_HEADER ? bw_err_text(status[i]) : "BigWig data block does not inflate");
+        }
     // the range of every chromosome: its blocks are consecutive in index order (a chromosome whose blocks are not -- an index that is
     // not sorted by chromosome -- cannot be served from one range and is refused)
     std::vector<int> by_id((size_t)max_id + 1, -1);
@@ -535,7 +566,8 @@ int bw_decode_all(pmx_dbw *w, float threshold)
             if (cur >= 0) closed[(size_t)cur] = 1;
             cur = k;
             if (k >= 0) {
-                if (closed[(size_t)k]) return fail(PMX_DBAM_ERR_FORMAT, "BigWig index is not sorted by chromosome");
+                if (closed[(size_t)k])
+                    return fail(PMX_DBAM_ERR_FORMAT, w->bigbed ? "bigBed index is not sorted by chromosome" : "BigWig index is not sorted by chromosome");
                 w->range[(size_t)k].first = place[i];
                 w->range[(size_t)k].second = place[i];
             }
@@ -546,8 +578,12 @@ int bw_decode_all(pmx_dbw *w, float threshold)
         HIPOK(hipMalloc((void **)&w->d_begin, 4 * tot[0]));
         HIPOK(hipMalloc((void **)&w->d_end, 4 * tot[0]));
         HIPOK(hipMalloc((void **)&w->d_value, 4 * tot[0]));
-        hipLaunchKernelGGL(k_bw_sections<true>, grid, dim3(256), 0, w->stream, base, d_spans, nb, d_lens, (u32)lens.size(), threshold,
-                           d_status, d_cnt, d_bchrom, d_place, w->d_begin, w->d_end, w->d_value);
+        if (w->bigbed)
+            bb_launch_records(true, grid, w->stream, base, d_spans, nb, d_lens, (u32)lens.size(), threshold, d_status, d_cnt, d_bchrom,
+                              d_place, w->d_begin, w->d_end, w->d_value);
+        else
+            hipLaunchKernelGGL(k_bw_sections<true>, grid, dim3(256), 0, w->stream, base, d_spans, nb, d_lens, (u32)lens.size(), threshold,
+                               d_status, d_cnt, d_bchrom, d_place, w->d_begin, w->d_end, w->d_value);
         HIPOK(hipGetLastError());
         HIPOK(hipStreamSynchronize(w->stream));
     }

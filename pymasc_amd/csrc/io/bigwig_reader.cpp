@@ -11,7 +11,11 @@
 // The blocks of the wanted chromosome are found by walking the R-tree in order, inflated and decoded in parallel,
 // and concatenated in index order, which is ascending position for a valid file.  Parity is pinned on the
 // reference's own twin files tests/data/hg19_36mer-test.{bigwig,bedGraph}.
+//
+// bigBed files (the same container, magic 0x8789F2EB) are read by the same handle: their data blocks hold variable-length BED
+// records instead of sections, decoded by the rules of io/bigbed_parse.h into intervals of value 1.
 #include "../../../include/pymasc_amd_io.h"
+#include "bigbed_parse.h"
 #include "io_common.h"
 
 #include <zlib.h>
@@ -40,6 +44,7 @@ struct Interval {
 struct pmx_bigwig {
     pmx_io::MappedFile file;
     uint16_t version = 0;
+    bool bigbed = false;                // a bigBed file: data blocks of BED records
     uint64_t chrom_tree_off = 0, data_off = 0, index_off = 0;
     uint32_t uncompress_buf = 0;
     std::vector<std::string> names;     // in B+ tree order
@@ -60,7 +65,8 @@ struct Cursor {
     const uint8_t *at(uint64_t off, uint64_t n) const
     {
         if (off > w.file.size || n > w.file.size - off)
-            throw pmx_io::Error(PMX_IO_ERR_FORMAT, "BigWig structure points past the end of the file");
+            throw pmx_io::Error(PMX_IO_ERR_FORMAT, std::string(w.bigbed ? "bigBed" : "BigWig") +
+                                                       " structure points past the end of the file");
         return w.file.data + off;
     }
     uint8_t u8(uint64_t off) const { return *at(off, 1); }
@@ -90,13 +96,15 @@ void walk_chrom_tree(pmx_bigwig &w, const Cursor &c, uint64_t node, uint32_t key
     }
 }
 
-// Collects, in index order, the data blocks whose chromosome range includes chrom id `cid`.
-void walk_rtree(const Cursor &c, uint64_t node, uint32_t cid, std::vector<Span> &out, int depth)
+// Collects, in index order, the data blocks whose chromosome range includes chrom id `cid`.  Ends on any input
+// (bigbed_parse.h): a child lies strictly after its parent and inside the file, and at most file size / 32 leaf items are read.
+void walk_rtree(const Cursor &c, uint64_t node, uint32_t cid, std::vector<Span> &out, int depth, uint64_t &items)
 {
     if (depth > 64) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "R-tree too deep");
     const bool leaf = c.u8(node) != 0;
     const uint32_t count = c.u16(node + 2);
     uint64_t p = node + 4;
+    if (leaf && (items += count) > c.w.file.size / 32) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_RTREE_ITEMS);
     for (uint32_t i = 0; i < count; i++) {
         const uint32_t c0 = c.u32(p), c1 = c.u32(p + 8);
         const bool hit = c0 <= cid && cid <= c1;
@@ -104,10 +112,57 @@ void walk_rtree(const Cursor &c, uint64_t node, uint32_t cid, std::vector<Span> 
             if (hit) out.push_back(Span{c.u64(p + 16), c.u64(p + 24)});
             p += 32;
         } else {
-            if (hit) walk_rtree(c, c.u64(p + 16), cid, out, depth + 1);
+            if (hit) {
+                const uint64_t child = c.u64(p + 16);
+                if (child <= node || child >= c.w.file.size) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_RTREE_CHILD);
+                walk_rtree(c, child, cid, out, depth + 1, items);
+            }
             p += 24;
         }
     }
+}
+
+// A bigBed data block: zlib-checked like the device reader (header bytes, raw DEFLATE, then Adler-32, so both name the same
+// failure), then its records by bigbed::walk_block.  A block of another chromosome keeps nothing.
+void decode_bigbed_block(const pmx_bigwig &w, const Span &sp, uint32_t cid, int64_t chrom_len, float threshold,
+                         std::vector<Interval> &out)
+{
+    const Cursor c{w};
+    const uint8_t *raw = c.at(sp.offset, sp.size);
+    std::vector<uint8_t> tmp;
+    const uint8_t *d = raw;
+    uint64_t n = sp.size;
+    if (w.uncompress_buf > 0) {
+        if (sp.size < 6 || (raw[0] & 15u) != 8u || ((uint32_t)raw[0] * 256u + raw[1]) % 31u != 0u || (raw[1] & 32u))
+            throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_INFLATE);
+        tmp.resize(w.uncompress_buf);
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, -15) != Z_OK) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_INFLATE);
+        zs.next_in = const_cast<Bytef *>(raw + 2);
+        zs.avail_in = (uInt)(sp.size - 6);
+        zs.next_out = tmp.data();
+        zs.avail_out = (uInt)tmp.size();
+        const int rc = inflate(&zs, Z_FINISH);
+        n = zs.total_out;
+        inflateEnd(&zs);
+        if (rc != Z_STREAM_END) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_INFLATE);
+        const uint8_t *q = raw + sp.size - 4;
+        const uint32_t want = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
+        if ((uint32_t)adler32(adler32(0, nullptr, 0), tmp.data(), (uInt)n) != want)
+            throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_ADLER);
+        d = tmp.data();
+    }
+    const size_t first = out.size();
+    bool mine = true;
+    const uint32_t rc = bigbed::walk_block(d, n, [&](uint32_t chrom, uint32_t b, uint32_t e) {
+        if (out.size() == first && chrom != cid) mine = false;     // (the block's first record names its chromosome)
+        if (!mine) return;
+        if ((int64_t)b >= chrom_len || e == 0) return;
+        if (threshold > 0 && !(1.0f >= threshold)) return;
+        out.push_back(Interval{b, e, 1.0f});
+    });
+    if (rc) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::err_text(rc));
 }
 
 void decode_block(const pmx_bigwig &w, const Span &sp, uint32_t cid, int64_t chrom_len, float threshold,
@@ -169,7 +224,10 @@ void open_impl(pmx_bigwig &w, const char *path)
     const uint32_t magic = c.u32(0);
     if (magic == __builtin_bswap32(BIGWIG_MAGIC))
         throw pmx_io::Error(PMX_IO_ERR_FORMAT, "byte-swapped (big-endian) BigWig files are not supported");
-    if (magic != BIGWIG_MAGIC) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "not a BigWig file (bad magic)");
+    if (magic == __builtin_bswap32(bigbed::MAGIC)) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_SWAPPED);
+    if (magic != BIGWIG_MAGIC && magic != bigbed::MAGIC) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "not a BigWig file (bad magic)");
+    w.bigbed = magic == bigbed::MAGIC;
+    if (w.bigbed && c.u16(32) < 3) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_FIELDS);
     w.version = c.u16(4);
     w.chrom_tree_off = c.u64(8);
     w.data_off = c.u64(16);
@@ -211,6 +269,8 @@ int pmx_bigwig_open(const char *path, pmx_bigwig **out)
 
 void pmx_bigwig_close(pmx_bigwig *w) { delete w; }
 
+int pmx_bigwig_kind(const pmx_bigwig *w) { return (w && w->bigbed) ? 1 : 0; }
+
 int32_t pmx_bigwig_nchrom(const pmx_bigwig *w) { return w ? (int32_t)w->names.size() : 0; }
 
 const char *pmx_bigwig_chrom_name(const pmx_bigwig *w, int32_t i)
@@ -237,12 +297,16 @@ int64_t pmx_bigwig_fetch(pmx_bigwig *w, const char *chrom, float threshold, int6
         if (!(w->cache_valid && w->cache_chrom == chrom && w->cache_threshold == threshold)) {
             const Cursor c{*w};
             std::vector<Span> spans;
-            walk_rtree(c, w->index_off + 48, w->ids[k], spans, 0);
+            uint64_t items = 0;
+            walk_rtree(c, w->index_off + 48, w->ids[k], spans, 0, items);
             std::vector<std::vector<Interval>> parts(spans.size());
             const uint32_t cid = w->ids[k];
             const int64_t clen = w->sizes[k];
             pmx_io::parallel_for(w->nthreads, spans.size(), 8, [&](size_t lo, size_t hi, size_t) {
-                for (size_t i = lo; i < hi; i++) decode_block(*w, spans[i], cid, clen, threshold, parts[i]);
+                for (size_t i = lo; i < hi; i++) {
+                    if (w->bigbed) decode_bigbed_block(*w, spans[i], cid, clen, threshold, parts[i]);
+                    else decode_block(*w, spans[i], cid, clen, threshold, parts[i]);
+                }
             });
             size_t total = 0;
             for (auto &v : parts) total += v.size();

@@ -1,6 +1,6 @@
 """Which reader a run reads its input through: the one place that chooses between the host readers (libpymasc_io.so) and
 the device readers (libpymasc_ingest.so) of an alignment file -- BAM, SAM (pymasc_amd.sam) or BED reads (pymasc_amd.bed_reads) -- and
-of a mappability track: BigWig, or text (pymasc_amd.text_track).
+of a mappability track: BigWig or bigBed, or text (pymasc_amd.text_track).
 
 The reader modules import ``find_index`` from here, so they are imported inside the openers, and the device classes are
 looked up through their module each time (a test may replace ``bam_device.DeviceBamReader``).
@@ -108,11 +108,12 @@ def open_header(path, chrom_sizes=None):
 
 
 def open_track(path, device_ingest: bool, device: int = 0):
-    """The reader of a mappability track: a BigWig file (``text_track.is_bigwig``: the bbi magic or a .bw / .bigwig name) is read
-    by ``DeviceBigWigReader`` on ``device`` with ``device_ingest``, else ``BigWigReader``; any other file is a text track
+    """The reader of a mappability track: a BigWig file (``text_track.is_bigwig``: the bbi magic or a .bw / .bigwig name) or a
+    bigBed file (``text_track.is_bigbed``: the bigBed magic or a .bb / .bigbed name) is read by
+    ``DeviceBigWigReader`` on ``device`` with ``device_ingest``, else ``BigWigReader``; any other file is a text track
     (bedGraph, BED, WIG; plain, BGZF or gzip) read by ``DeviceTextTrackReader`` / ``TextTrackReader``."""
     from . import bigwig, bigwig_device, text_track
-    if text_track.is_bigwig(path):
+    if text_track.is_bigwig(path) or text_track.is_bigbed(path):
         if device_ingest:
             return bigwig_device.DeviceBigWigReader(path, device=device)
         return bigwig.BigWigReader(path)

@@ -4,7 +4,7 @@
 surface of ``BigWigReader`` / ``DeviceBigWigReader``: ``chromsizes``, ``fetch(valfilter, chrom)``, ``fetch_arrays`` (and, on the
 device, ``fetch_device``), ``close``.  A text track has no chromosome sizes: ``chromsizes`` holds the largest end of each
 chromosome's lines, and ``chromsizes_are_extents`` says so.  ``sorted``: the intervals of the last fetch are ascending and
-disjoint.  ``is_bigwig`` is the rule that sends a file to the BigWig readers instead.
+disjoint.  ``is_bigwig`` and ``is_bigbed`` are the rules that send a file to the bbi (BigWig) readers instead.
 """
 from __future__ import annotations
 
@@ -21,6 +21,7 @@ from .bigwig_device import _raise as _raise_device
 
 PMX_IO_ERR_NOTFOUND = -4
 BBI_MAGIC = (0x888FFC26).to_bytes(4, "little")
+BIGBED_MAGIC = (0x8789F2EB).to_bytes(4, "little")
 
 
 def is_bigwig(path) -> bool:
@@ -32,6 +33,19 @@ def is_bigwig(path) -> bool:
     try:
         with open(p, "rb") as fh:
             return fh.read(4) == BBI_MAGIC
+    except OSError:
+        return False
+
+
+def is_bigbed(path) -> bool:
+    """A bigBed file: its first four bytes are the bigBed magic, or its name ends in .bb / .bigbed (any case) -- read by the
+    BigWig readers, which take both kinds of bbi file."""
+    p = os.fspath(path)
+    if p.lower().endswith((".bb", ".bigbed")):
+        return True
+    try:
+        with open(p, "rb") as fh:
+            return fh.read(4) == BIGBED_MAGIC
     except OSError:
         return False
 

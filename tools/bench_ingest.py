@@ -375,6 +375,50 @@ def time_text_track(path, reps=3):
             "speedup": round(min(host) / min(dev), 2)}
 
 
+def synth_bigbed(path, nrec, seed=13):
+    """A seeded hg38-shaped bigBed of about `nrec` BED6 records over the 24 chromosomes (in proportion to their length), with
+    Umap-like rests (a name, a score, a strand: 20-30 bytes a record) in zlib blocks of 512 items (tests/bigbed_writers.py)."""
+    from tests import bigbed_writers as BB
+    t0 = time.time()
+    total = sum(l for _n, l in HG38)
+    recs = {}
+    for i, (n, l) in enumerate(HG38):
+        per = max(1, int(nrec * l / total))
+        recs[n] = BB.random_records(seed + i, per, [n])[n]
+    sizes = {n: max(l, int(recs[n][1][-1]) + 1) for n, l in HG38}
+    BB.write_bigbed(path, sizes, recs, items_per_block=512, rtree_block=256)
+    return sum(len(v[0]) for v in recs.values()), time.time() - t0
+
+
+def time_bigbed(path, reps=3):
+    """Open + fetch of every chromosome at 1.0: the host reader (zlib on threads) against the device reader (k_bb_records,
+    intervals left in HBM); the device arrays are compared with the host's, element for element."""
+    from pymasc_amd.bigwig import BigWigReader
+    from pymasc_amd.bigwig_device import DeviceBigWigReader
+    host = []
+    for _ in range(reps):
+        t0 = time.time()
+        with BigWigReader(path) as r:
+            assert r.kind == "bigbed"
+            arrays = {c: r.fetch_arrays(1, c) for c in r.chromsizes}
+        host.append(round(time.time() - t0, 4))
+    dev, dev_open = [], []
+    for _ in range(reps):
+        t0 = time.time()
+        with DeviceBigWigReader(path) as r:
+            t1 = time.time()
+            ns = [r.fetch_device(1, c)[2] for c in arrays]
+            dev.append(round(time.time() - t0, 4))
+            dev_open.append(round(t1 - t0, 4))
+    with DeviceBigWigReader(path) as r:         # parity of the whole track
+        for c, want in arrays.items():
+            for x, y in zip(r.fetch_arrays(1, c), want):
+                assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), c
+    assert ns == [a[0].size for a in arrays.values()]
+    return {"intervals_at_1": sum(ns), "host_reader_s": host, "device_reader_s": dev, "device_open_s": dev_open,
+            "speedup": round(min(host) / min(dev), 2)}
+
+
 BED_FILES = [(order, comp) for order in ("sorted", "shuffled") for comp in ("none", "gzip", "bgzf")]
 
 
@@ -465,6 +509,8 @@ def main():
                          "BedReadsReader (16 threads) against DeviceBedReadsReader")
     ap.add_argument("--bed-dir", default="/tmp/pymasc_bed_bench", help="where the --bed files are made (and kept)")
     ap.add_argument("--bed-only", default=None, help="--bed: time only ORDER-COMP (e.g. shuffled-none), on the device only")
+    ap.add_argument("--bigbed", action="store_true",
+                    help="time a bigBed track of about --lines BED6 records: host reader against device reader (DESIGN.md 7.12)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -480,6 +526,21 @@ def main():
             r.update(time_bed_reads(path, sizes, a.mapq, a.reps, host=a.bed_only is None))
             res["files"].append(r)
             print(json.dumps(r), flush=True)
+        if a.out:
+            with open(a.out, "w") as fp:
+                json.dump(res, fp, indent=1)
+        return
+
+    if a.bigbed:
+        path = a.path + ".bb"
+        nrec, gen_s = synth_bigbed(path, a.lines)
+        res = {"kind": "bigbed", "records": nrec, "items_per_block": 512, "file_bytes": os.path.getsize(path),
+               "generate_s": round(gen_s, 1)}
+        try:
+            res.update(time_bigbed(path, a.reps))
+        finally:
+            os.unlink(path)
+        print(json.dumps(res), flush=True)
         if a.out:
             with open(a.out, "w") as fp:
                 json.dump(res, fp, indent=1)
