@@ -177,7 +177,7 @@ int pmx_dbw_copy(pmx_dbw *w, int64_t first, int64_t n, uint32_t *begin, uint32_t
 /* bigBed on the device (version >= 7): pmx_dbw_open also takes a bigBed file, read by the rules of pmx_bigwig_open
  * (pymasc_amd_io.h, its checker).  Its blocks are inflated and Adler-32-checked as a BigWig's; k_bb_records walks each block's
  * record chain (one wavefront per block) and writes [chromStart, chromEnd) with value 1.0.  pmx_dbw_kind: 0 BigWig (or a text
- * track), 1 bigBed. */
+ * track), 1 bigBed, 2 a k-mer track of pmx_dkm_open (version >= 8). */
 int pmx_dbw_kind(const pmx_dbw *w);
 
 /* Text tracks on the device (version >= 5): `path` is a bedGraph, BED or WIG file, plain, BGZF or gzip, read by
@@ -202,6 +202,22 @@ int pmx_dtt_open(const char *path, int device, int nthreads, pmx_dbw **out);
  * timings work on it; pmx_dbam_select is PMX_DBAM_ERR_INVALID. */
 int pmx_dbed_open(const char *path, int device, int nthreads, int32_t nref, const char *const *names, const int64_t *lengths,
                   pmx_dbam **out);
+
+/* The k-mer uniqueness track of a genome FASTA on the device (version >= 8): `path` is a FASTA file, plain, BGZF
+ * or gzip, read by the rules of pmx_kmer_open (pymasc_amd_io.h, its checker), and the track is pmx_kmer_open's, interval for
+ * interval.  The text reaches HBM as a text track's does (pmx_dtt_open) and is indexed by k_sam_count / k_bam_scan / k_sam_lines;
+ * k_fa_class / k_fa_list / k_fa_pack pack the genome at 2 bits and a valid bit per position and the text is freed.  One lane per
+ * position hashes its k-mer strand-symmetrically (h = min(H(F), H(R)), any k in [16, 1024]; no k-mer or a palindrome: never
+ * unique, never sorted).  A histogram of the top 16 kept hash bits plans passes of at most budget_bytes / 24 k-mers (0: half of
+ * the free device memory less 4 GiB); each pass recomputes the hashes of its bins and LSD-radix-sorts (hash, position) with a
+ * multi-workgroup scan.  A run of equal hashes of one element is unique; in a longer run every element is compared with the
+ * run's first (a segmented max-scan finds it); a run with a mismatch is resolved exactly on the host by sorting the canonical
+ * packed k-mers of its elements.  hash_bits < 64 keeps only the low bits of the hash (a test knob that forces collisions).
+ * The handle is a pmx_dbw: nchrom / chrom_name / chrom_len (every record in file order, its length in bases), fetch (the
+ * record's unique runs, value 1.0; none above threshold 1), device_arrays, sorted, copy and close work on it; only the intervals
+ * (12 bytes each) stay in device memory.  k outside [16, 1024], hash_bits outside [1, 64]: PMX_DBAM_ERR_INVALID; a malformed
+ * file: PMX_DBAM_ERR_FORMAT with pmx_kmer_open's message; one hash bin larger than the budget: PMX_DBAM_ERR_OPEN. */
+int pmx_dkm_open(const char *path, int32_t k, int device, int nthreads, int64_t budget_bytes, int32_t hash_bits, pmx_dbw **out);
 
 #ifdef __cplusplus
 }

@@ -184,6 +184,24 @@ int64_t pmx_ttrack_fetch(pmx_ttrack *t, const char *chrom, float threshold, int6
 /* 1 when the intervals of the last fetch are ascending and disjoint (begin_(i+1) >= end_i), or there are none */
 int pmx_ttrack_sorted(const pmx_ttrack *t);
 
+/* ---- Genome FASTA -> k-mer uniqueness track (version >= 6) ------------------------------------------
+ * The host twin of pmx_dkm_open (pymasc_amd_ingest.h) and its checker, by another method: no hashing.  `path` is a genome
+ * FASTA, plain, BGZF or gzip (told from the bytes), read by the rules of io/fasta_parse.h.  Position p of record c is uniquely
+ * mappable when its k-mer F exists (p + k <= len(c), k valid bases A C G T of any case), F != revcomp(F), and no other existing
+ * position has F or revcomp(F) as its k-mer.  The positions are sorted on nthreads threads by the canonical packed k-mer
+ * (min(F, R), compared word by word) and the groups of size one are unique.  The track of a record is its maximal runs of
+ * unique positions, [p, q) with value 1.0, ascending and disjoint.  k outside [16, 1024]: PMX_IO_ERR_INVALID.  A malformed
+ * file: PMX_IO_ERR_FORMAT, "line N: <reason>" (1-based, in the decompressed text), or the genome-size message.
+ * nchrom / chrom_name / chrom_len: every record in file order with its length in bases; fetch / sorted as pmx_ttrack_*. */
+typedef struct pmx_kmer pmx_kmer;
+int pmx_kmer_open(const char *path, int32_t k, int nthreads, pmx_kmer **out);
+void pmx_kmer_close(pmx_kmer *t);
+int32_t pmx_kmer_nchrom(const pmx_kmer *t);
+const char *pmx_kmer_chrom_name(const pmx_kmer *t, int32_t i);
+int64_t pmx_kmer_chrom_len(const pmx_kmer *t, int32_t i);
+int64_t pmx_kmer_fetch(pmx_kmer *t, const char *chrom, float threshold, int64_t cap, uint32_t *begin, uint32_t *end, float *value);
+int pmx_kmer_sorted(const pmx_kmer *t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,8 @@ IO_EXPORTS = [
     "pmx_bigwig_fetch", "pmx_bigwig_kind",
     "pmx_ttrack_open", "pmx_ttrack_close", "pmx_ttrack_nchrom", "pmx_ttrack_chrom_name", "pmx_ttrack_chrom_len",
     "pmx_ttrack_fetch", "pmx_ttrack_sorted", "pmx_bed_open",
+    "pmx_kmer_open", "pmx_kmer_close", "pmx_kmer_nchrom", "pmx_kmer_chrom_name", "pmx_kmer_chrom_len", "pmx_kmer_fetch",
+    "pmx_kmer_sorted",
 ]
 
 
@@ -156,6 +158,20 @@ def load_io_library():
     L.pmx_ttrack_fetch.restype = i64
     L.pmx_ttrack_sorted.argtypes = [vp]
     L.pmx_ttrack_sorted.restype = ctypes.c_int
+    L.pmx_kmer_open.argtypes = [ctypes.c_char_p, i32, ctypes.c_int, ctypes.POINTER(vp)]
+    L.pmx_kmer_open.restype = ctypes.c_int
+    L.pmx_kmer_close.argtypes = [vp]
+    L.pmx_kmer_close.restype = None
+    L.pmx_kmer_nchrom.argtypes = [vp]
+    L.pmx_kmer_nchrom.restype = i32
+    L.pmx_kmer_chrom_name.argtypes = [vp, i32]
+    L.pmx_kmer_chrom_name.restype = ctypes.c_char_p
+    L.pmx_kmer_chrom_len.argtypes = [vp, i32]
+    L.pmx_kmer_chrom_len.restype = i64
+    L.pmx_kmer_fetch.argtypes = [vp, ctypes.c_char_p, ctypes.c_float, i64, vp, vp, vp]
+    L.pmx_kmer_fetch.restype = i64
+    L.pmx_kmer_sorted.argtypes = [vp]
+    L.pmx_kmer_sorted.restype = ctypes.c_int
     _lib = L
     return L
 

@@ -29,7 +29,7 @@ INGEST_EXPORTS = [
     "pmx_dbam_readlen_counters", "pmx_dbam_open_indexed", "pmx_dbam_select", "pmx_dsam_open",
     "pmx_dbam_open_stream", "pmx_dbam_stream_next", "pmx_dbam_stream_info",
     "pmx_dbw_open", "pmx_dbw_close", "pmx_dbw_nchrom", "pmx_dbw_chrom_name", "pmx_dbw_chrom_len", "pmx_dbw_fetch", "pmx_dbw_device_arrays",
-    "pmx_dbw_sorted", "pmx_dbw_copy", "pmx_dtt_open", "pmx_dbed_open", "pmx_dbw_kind",
+    "pmx_dbw_sorted", "pmx_dbw_copy", "pmx_dtt_open", "pmx_dbed_open", "pmx_dbw_kind", "pmx_dkm_open",
 ]
 
 _lib = None
@@ -118,6 +118,8 @@ def load_ingest_library():
     L.pmx_dbw_copy.restype = ctypes.c_int
     L.pmx_dbw_kind.argtypes = [vp]
     L.pmx_dbw_kind.restype = ctypes.c_int
+    L.pmx_dkm_open.argtypes = [ctypes.c_char_p, i32, ctypes.c_int, ctypes.c_int, i64, i32, ctypes.POINTER(vp)]
+    L.pmx_dkm_open.restype = ctypes.c_int
     _lib = L
     return L
 

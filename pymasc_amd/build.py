@@ -91,6 +91,7 @@ def build_ingest(force=False, verbose=False):
                                                                                      os.path.join(CSRC, "io", "text_track_parse.h"),
                                                                                      os.path.join(CSRC, "io", "bed_reads_parse.h"),
                                                                                      os.path.join(CSRC, "io", "bigbed_parse.h"),
+                                                                                     os.path.join(CSRC, "io", "fasta_parse.h"),
                                                                                      os.path.abspath(__file__)]
     if not force and os.path.exists(INGEST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(INGEST_LIB) for d in deps):
         return INGEST_LIB

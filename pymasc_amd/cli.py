@@ -79,7 +79,9 @@ def track_options(group) -> None:
     group.add_argument("-m", "--mappability", metavar="TRACK", type=Path,
                        help="mappability track: BigWig, bigBed (every interval counts as 1), or bedGraph / BED / WIG text, "
                             "plain or gzip / bgzip-compressed; "
-                            "positions with a value of at least 1 count as mappable")
+                            "positions with a value of at least 1 count as mappable; or a genome FASTA "
+                            "(.fa / .fasta / .fna / .fas, optionally .gz / .bgz), whose exact k-mer uniqueness track "
+                            "is computed with k = the read length")
     group.add_argument("--mappability-stats", metavar="JSON", type=Path,
                        help="where the mappable-length cache is read and written (default: the track's path with "
                             "_mappability.json in place of its extension)")

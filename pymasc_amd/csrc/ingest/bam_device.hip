@@ -1773,7 +1773,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 7; }
+int pmx_dbam_version(void) { return 8; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -2536,3 +2536,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "stream_device.inc"
 #include "text_track_device.inc"
 #include "bed_reads_device.inc"
+#include "kmer_track_device.inc"

@@ -178,6 +178,11 @@ struct pmx_dbw {
     float *t_v = nullptr;
     u64 *t_cbase = nullptr;         // [nchrom + 1]: where each chromosome's lines start
     u64 t_n = 0, text_lines = 0, text_heads = 0, text_slow = 0;   // data lines, lines, chromosome blocks, values strtod decided
+    // a k-mer track (pmx_dkm_open, kmer_track_device.inc): the runs of every record in d_begin / d_end / d_value, made at open
+    bool kmer = false;
+    std::vector<std::pair<u64, u64>> km_range;   // per record: its runs in the arrays
+    u64 km_kmers = 0, km_resolved = 0;           // k-mers sorted; elements of colliding runs resolved on the host
+    u32 km_passes = 0;
 };
 
 namespace {
@@ -390,7 +395,7 @@ void pmx_dbw_close(pmx_dbw *w)
 }
 
 int32_t pmx_dbw_nchrom(const pmx_dbw *w) { return w ? (int32_t)w->names.size() : 0; }
-int pmx_dbw_kind(const pmx_dbw *w) { return (w && w->bigbed) ? 1 : 0; }
+int pmx_dbw_kind(const pmx_dbw *w) { return !w ? 0 : w->kmer ? 2 : w->bigbed ? 1 : 0; }
 const char *pmx_dbw_chrom_name(const pmx_dbw *w, int32_t i)
 {
     return (w && i >= 0 && (size_t)i < w->names.size()) ? w->names[(size_t)i].c_str() : nullptr;
@@ -595,6 +600,7 @@ int bw_decode_all(pmx_dbw *w, float threshold)
 }  // namespace
 
 static int tt_decode_all(pmx_dbw *w, float threshold);   // text_track_device.inc
+static int km_select(pmx_dbw *w, float threshold);       // kmer_track_device.inc
 
 extern "C" {
 
@@ -617,7 +623,7 @@ static int64_t dbw_fetch_impl(pmx_dbw *w, const char *chrom, float threshold)
     if (!(threshold > 0.f)) threshold = 0.f;
     if (!w->have || w->have_threshold != threshold) {
         w->have = false;
-        const int rc = w->text ? tt_decode_all(w, threshold) : bw_decode_all(w, threshold);
+        const int rc = w->kmer ? km_select(w, threshold) : w->text ? tt_decode_all(w, threshold) : bw_decode_all(w, threshold);
         if (rc) return rc;
     }
     w->cur = k;

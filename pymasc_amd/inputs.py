@@ -107,12 +107,34 @@ def open_header(path, chrom_sizes=None):
     return sam.SamReader(path, header_only=True) if sam.is_sam(path) else bam.BamReader(path, index=False)
 
 
-def open_track(path, device_ingest: bool, device: int = 0):
+def track_on_device(path, device_ingest: bool, context=None) -> bool:
+    """Where a run's track is read: a genome FASTA (``kmer_track.is_fasta``) on the GPU whenever this rank has a GPU context
+    (``context`` None or a pymasc_amd.ffi.Context, and a device visible) -- uniqueness is genome-wide, so every rank generates
+    the whole track on its own device, never on the host; any other track where ``device_ingest`` says."""
+    from . import ffi, kmer_track
+    if not kmer_track.is_fasta(path):
+        return bool(device_ingest)
+    if not (context is None or isinstance(context, ffi.Context)):
+        return False
+    try:
+        return ffi.device_count() > 0
+    except Exception:
+        return False
+
+
+def open_track(path, device_ingest: bool, device: int = 0, k=None):
     """The reader of a mappability track: a BigWig file (``text_track.is_bigwig``: the bbi magic or a .bw / .bigwig name) or a
     bigBed file (``text_track.is_bigbed``: the bigBed magic or a .bb / .bigbed name) is read by
-    ``DeviceBigWigReader`` on ``device`` with ``device_ingest``, else ``BigWigReader``; any other file is a text track
-    (bedGraph, BED, WIG; plain, BGZF or gzip) read by ``DeviceTextTrackReader`` / ``TextTrackReader``."""
-    from . import bigwig, bigwig_device, text_track
+    ``DeviceBigWigReader`` on ``device`` with ``device_ingest``, else ``BigWigReader``; a genome FASTA (``kmer_track.is_fasta``:
+    .fa / .fasta / .fna / .fas, optionally .gz / .bgz) becomes its k-mer uniqueness track with ``k`` = the read length
+    (``DeviceKmerTrackReader`` / ``KmerTrackReader``; ValueError without ``k``); any other file is a text track
+    (bedGraph, BED, WIG; plain, BGZF or gzip) read by ``DeviceTextTrackReader`` / ``TextTrackReader``.  Tracks
+    other than FASTA ignore ``k``."""
+    from . import bigwig, bigwig_device, kmer_track, text_track
+    if kmer_track.is_fasta(path):
+        if k is None:
+            raise ValueError("'{}' is a genome FASTA: its track needs the k-mer length (the read length)".format(os.fspath(path)))
+        return kmer_track.open_kmer_track(path, k, device_ingest, device)
     if text_track.is_bigwig(path) or text_track.is_bigbed(path):
         if device_ingest:
             return bigwig_device.DeviceBigWigReader(path, device=device)

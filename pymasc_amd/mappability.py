@@ -65,9 +65,16 @@ def required_shift_size(readlen: int, max_shift: int) -> int:
     return max_shift - readlen + 1 if max_shift > 2 * readlen - 1 else readlen
 
 
-def default_stats_path(track_path) -> Path:
-    """``/dir/name.bw`` -> ``/dir/name_mappability.json`` (handler/mappability.py:196-199)."""
+def default_stats_path(track_path, k=None) -> Path:
+    """``/dir/name.bw`` -> ``/dir/name_mappability.json`` (handler/mappability.py:196-199).  A genome FASTA's track depends on
+    k: ``/dir/genome.fa.gz`` -> ``/dir/genome_k<K>_mappability.json``, so that a cache of another k is never picked up
+    (ValueError without ``k``)."""
+    from .kmer_track import fasta_stem, is_fasta
     p = Path(track_path)
+    if is_fasta(p):
+        if k is None:
+            raise ValueError("the cache of a genome FASTA's track is named after k: give k")
+        return p.parent / "{}_k{}_mappability.json".format(fasta_stem(p), int(k))
     return p.parent / (p.with_suffix("").name + "_mappability.json")
 
 
@@ -135,7 +142,7 @@ class MappabilityStats:
         if map_path is not None:
             self.map_path: Optional[Path] = Path(map_path)
         elif track_path is not None:
-            self.map_path = default_stats_path(track_path)
+            self.map_path = default_stats_path(track_path, getattr(feeder, "k", None))
         else:
             self.map_path = None
 

@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence
 from . import ffi, readlen, tables
 from .chromfilter import NoTargetChromosomesError, filter_references
 from .exceptions import InputUnseekable, ReadUnsortedError
-from .inputs import default_device_ingest, is_stream, open_alignments, open_header, open_track
+from .inputs import default_device_ingest, is_stream, open_alignments, open_header, open_track, track_on_device
 from .mappability import MappabilityStats
 from .sharding import _collective_device_setup, on_rank0, rank_and_world, run_sharded
 
@@ -113,8 +113,16 @@ def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path,
     # The mappable-length cache (handler/mappability.py:239-309): loaded when valid; otherwise computed ONCE, on rank 0,
     # written atomically, and broadcast -- the other ranks neither recompute it per chromosome nor read a file that is
     # being rewritten.
+    # A genome FASTA's track is generated once per rank (on its GPU when it has one, inputs.track_on_device) and that one
+    # reader serves the mappable lengths and the feed.
+    track = None
+    if mappability_path is not None and _is_fasta(mappability_path):
+        track = open_track(mappability_path, track_on_device(mappability_path, False, context),
+                           context.device if context is not None else device, k=read_len)
+
     def mappable_lengths():
-        with open_track(mappability_path, False) as bw:
+        bw = track if track is not None else open_track(mappability_path, False)
+        try:
             stats = MappabilityStats(bw, max_shift, read_len, map_path=mappability_stats_path, track_path=mappability_path,
                                      device=device, context=context)
             try:
@@ -127,11 +135,18 @@ def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path,
                 return None
             finally:
                 stats.close()
-    known = None if mappability_path is None else on_rank0(mappable_lengths, group, "mappability statistics")
-    result = run_sharded(bam_path, max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
-                         references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
-                         group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter,
-                         chrom_sizes=chrom_sizes)
+        finally:
+            if bw is not track:
+                bw.close()
+    try:
+        known = None if mappability_path is None else on_rank0(mappable_lengths, group, "mappability statistics")
+        result = run_sharded(bam_path, max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
+                             references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
+                             group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter,
+                             chrom_sizes=chrom_sizes, track=track)
+    finally:
+        if track is not None:
+            track.close()
     written: List[Path] = []
     if rank == 0:
         written = _write_outputs(outdir, Path(bam_path).stem, result, read_len, stat_opts)
@@ -243,8 +258,10 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
         if ctx is None:
             ctx, own_ctx = ffi.Context(device), True
         known = None
-        if mappability_path is not None:
-            track = open_track(mappability_path, ingest, dev)
+        if mappability_path is not None:        # (a genome FASTA: its k-mer track with k = the read length)
+            fasta = _is_fasta(mappability_path)
+            track = open_track(mappability_path, track_on_device(mappability_path, ingest, ctx),
+                               getattr(ctx, "device", dev) if fasta else dev, k=read_len)
 
             def mappable_lengths():
                 ms = MappabilityStats(track, max_shift, read_len, map_path=mappability_stats_path,
@@ -323,6 +340,11 @@ def _warn_existing(outdir, bases, has_track, skip_ncc, stats):
             path = Path(outdir) / (b + suffix)
             if path.exists():
                 logger.warning("Existing file '{}' will be overwritten.".format(path))
+
+
+def _is_fasta(path) -> bool:
+    from .kmer_track import is_fasta
+    return is_fasta(path)
 
 
 def _is_bed(path) -> bool:

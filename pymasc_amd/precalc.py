@@ -5,6 +5,9 @@ PyMaSC's calcmappablelen.py does: ``MappabilityStats`` computes the lag tables o
 is looked up with the host reader of the track (its header is all that takes); a valid cache that already covers the range
 is left as it is and no GPU is touched.  Otherwise the track is read by the device reader when there is a GPU.  ``-p`` is
 accepted and ignored: the lag tables come from one GPU.
+A genome FASTA (``kmer_track.is_fasta``) takes ``-r`` as the k of its k-mer track and needs it given: the default of 1000
+means nothing there (an argparse error, exit 2).  Its cache is ``<stem>_k<K>_mappability.json``; the names and lengths that
+check it come from ``<fasta>.fai`` or a scan of the header lines, so a valid cache costs no generation.
 """
 from __future__ import annotations
 
@@ -13,8 +16,17 @@ import logging
 import sys
 
 from . import cli
+from .kmer_track import is_fasta
 
 logger = logging.getLogger(__name__)
+
+
+class _Given(cli._NaturalNumber):
+    """-r: also notes that it was given (a genome FASTA has no use for the default)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        super().__call__(parser, namespace, values, option_string)
+        namespace.max_readlen_given = True
 
 
 def get_parser() -> argparse.ArgumentParser:
@@ -28,8 +40,9 @@ def get_parser() -> argparse.ArgumentParser:
     cli.track_options(parser.add_argument_group("mappability"))
     lags = parser.add_argument_group("lag range")
     cli.shift_option(lags)
-    lags.add_argument("-r", "--max-readlen", type=int, default=1000, action=cli._NaturalNumber,
-                      help="longest read length the cache has to serve (default 1000)")
+    lags.add_argument("-r", "--max-readlen", type=int, default=1000, action=_Given,
+                      help="longest read length the cache has to serve (default 1000); for a genome FASTA, the k-mer "
+                           "length of its track, which must be given")
     return parser
 
 
@@ -39,6 +52,8 @@ def main(argv=None) -> int:
         args = parser.parse_args(argv)
         if not args.mappability:
             parser.error("argument -m/--mappable: expected 1 argument(s)")
+        if is_fasta(args.mappability) and not getattr(args, "max_readlen_given", False):
+            parser.error("argument -r/--max-readlen: a genome FASTA needs it (the k of its k-mer track)")
     except SystemExit as e:         # --help, --version, argument errors
         return e.code if isinstance(e.code, int) else 2
     cli.setup_logging(args.log_level)
@@ -53,10 +68,11 @@ def main(argv=None) -> int:
     from .mappability import BWIOError, JSONIOError, MappabilityStats
     track_path = str(args.mappability)
     opened = []
+    fasta = is_fasta(track_path)
     try:
         try:
-            opened.append(inputs.open_track(track_path, False))
-        except OSError as e:
+            opened.append(_FastaSizes(track_path, args.max_readlen) if fasta else inputs.open_track(track_path, False))
+        except (OSError, ValueError) as e:
             logger.critical("Cannot open the mappability track '{}': {}".format(track_path, e))
             return 1
         stats = MappabilityStats(opened[0], max_shift=args.max_shift, readlen=args.max_readlen,
@@ -64,7 +80,14 @@ def main(argv=None) -> int:
                                  track_path=track_path)
         try:
             if not stats.is_called:             # no valid cache: the intervals are read on the GPU when there is one
-                if inputs.default_device_ingest(1):
+                if fasta:                       # the k-mer track, generated now (on the GPU when there is one)
+                    try:
+                        opened.append(inputs.open_track(track_path, inputs.default_device_ingest(1), k=args.max_readlen))
+                    except (OSError, ValueError) as e:
+                        logger.critical("Cannot open the mappability track '{}': {}".format(track_path, e))
+                        return 1
+                    stats.feeder = opened[-1]
+                elif inputs.default_device_ingest(1):
                     try:
                         opened.append(inputs.open_track(track_path, True))
                     except OSError as e:
@@ -81,6 +104,19 @@ def main(argv=None) -> int:
         for t in opened:
             t.close()
     return 0
+
+
+class _FastaSizes:
+    """The records of a genome FASTA (``kmer_track.fasta_sizes``) and the k of its track: what checking the cache needs."""
+    kind = "kmer"
+
+    def __init__(self, path, k):
+        from .kmer_track import _check_k, fasta_sizes
+        self.k = _check_k(k)
+        self.chromsizes = fasta_sizes(path)
+
+    def close(self):
+        pass
 
 
 if __name__ == "__main__":

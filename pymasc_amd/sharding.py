@@ -246,7 +246,7 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     before this returns (``CCHipCalculator.close`` never closes a context it does not own)."""
     from .calculator import CCHipCalculator
     from .chromfilter import filter_references
-    from .inputs import default_device_ingest, find_index, open_alignments, open_track
+    from .inputs import default_device_ingest, find_index, open_alignments, open_track, track_on_device
     from .result import aggregate_results
     from .bed_reads import is_bed_reads
     from .sam import is_sam
@@ -284,7 +284,12 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
             names = [n for n in reader.references if references is None or n in set(references)]
         lengths = dict(zip(reader.references, reader.lengths))
         if bigwig_path is not None:     # with device ingest the track is decoded on the GPU too: its intervals stay in HBM
-            bw = track if track is not None else open_track(bigwig_path, device_ingest, dev)
+            if track is None:           # (a genome FASTA: on this rank's GPU whenever it has one)
+                gpu_track = track_on_device(bigwig_path, device_ingest, context)
+                tdev = dev if (not gpu_track or device_ingest) else (context.device if context is not None else (device or 0))
+                bw = open_track(bigwig_path, gpu_track, tdev, k=read_len)
+            else:
+                bw = track
             # the track's chromosome sizes win where they are longer (handler/calc.py:100-115); a text track's sizes are the
             # extents of its lines: one that stops short of the chromosome is normal and says nothing
             ext = bw.chromsizes
