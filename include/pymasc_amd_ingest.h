@@ -155,8 +155,8 @@ int pmx_dbam_timings(const pmx_dbam *b, double t[6]);
 int pmx_dbam_inflated(pmx_dbam *b, uint64_t first, uint64_t n, uint8_t *dst);
 
 /* ---- BigWig (bbi) on the device -----------------------------------------------------------
- * What pmx_bigwig_* (pymasc_amd_io.h) does with zlib on host threads, with the data blocks inflated (the BGZF kernel, for zlib
- * streams of unknown length), Adler-32-checked and decoded by HIP kernels; the host reads the header, the chromosome B+ tree and
+ * What pmx_bigwig_open / pmx_track_fetch (pymasc_amd_io.h) do with zlib on host threads, with the data blocks inflated (the
+ * BGZF kernel, for zlib streams of unknown length), Adler-32-checked and decoded by HIP kernels; the host reads the header, the chromosome B+ tree and
  * the R-tree (a few KB per chromosome).  Replaces PyMaSC/reader/bigwig.pyx:129-177 (pyBigWig). */
 typedef struct pmx_dbw pmx_dbw;
 int pmx_dbw_open(const char *path, int device, int nthreads, pmx_dbw **out);
@@ -167,7 +167,7 @@ const char *pmx_dbw_chrom_name(const pmx_dbw *w, int32_t i);
 int64_t pmx_dbw_chrom_len(const pmx_dbw *w, int32_t i);
 /* All intervals of `chrom` in index order (ascending position for a valid file) whose float32 value is >= threshold
  * (threshold <= 0: every interval), as BigWigReader.fetch yields them (bigwig.pyx:147-177) -- the intervals, values and order
- * of pmx_bigwig_fetch.  They stay in device memory (begin[n], end[n] uint32, value[n] float32; every fetch has arrays of its own,
+ * of pmx_track_fetch.  They stay in device memory (begin[n], end[n] uint32, value[n] float32; every fetch has arrays of its own,
  * valid until close).  Returns n, PMX_DBAM_ERR_NOTFOUND for an unknown chromosome, or another negative error code. */
 int64_t pmx_dbw_fetch(pmx_dbw *w, const char *chrom, float threshold);
 int pmx_dbw_device_arrays(const pmx_dbw *w, const uint32_t **d_begin, const uint32_t **d_end, const float **d_value);

@@ -8,7 +8,7 @@
  *           Replaces the per-read pysam loop of PyMaSC/handler/calc.py:140-153 + handler/read.py:62-155.
  *   BigWig -> (begin, end, value) intervals of one chromosome with value >= threshold; consumed by
  *           pmx_bits_set_regions[_dev].  Replaces PyMaSC/reader/bigwig.pyx:147-177 (BigWigReader.fetch, itself a
- *           wrapper over the absent third-party libBigWig submodule).
+ *           wrapper over the absent third-party libBigWig submodule).  bigBed, text and k-mer tracks give the same.
  *
  * All functions return PMX_IO_OK (0) or a negative error code unless stated; the message of the last error of the
  * calling thread is pmx_io_last_error().  Handles are not thread-safe; the library runs its own worker threads.
@@ -87,7 +87,7 @@ int pmx_bam_counters(const pmx_bam *b, uint64_t *records, uint64_t *kept, uint64
  *                                     and QC-fail records included)                     (readlen.pyx:157-162)
  *   ... query length 0 or no CIGAR    nnoqlen instead (infer_query_length() is None; the reference fails on it)
  * One pass on the reader's threads with buffers of its own: a pmx_bam_next_batch iteration in progress is not disturbed.
- * Two-call protocol like pmx_bigwig_fetch: lengths == NULL returns the number of distinct counted lengths; otherwise fills up
+ * Two-call protocol like pmx_track_fetch: lengths == NULL returns the number of distinct counted lengths; otherwise fills up
  * to cap entries sorted by length -- counts[i], first[i] = offset in the uncompressed stream (header included) of the first
  * counted record of that length: the same key as pmx_dbam_readlen_hist's.  The result is kept for the next call with the same
  * mapq_min. */
@@ -137,30 +137,36 @@ int pmx_sam_readlen_counters(const pmx_sam *s, uint64_t c[6]);
  * of the line of the first counted record, whatever the sort did), readlen_counters and close work on it. */
 int pmx_bed_open(const char *path, int nthreads, int32_t nref, const char *const *names, const int64_t *lengths, pmx_sam **out);
 
-/* ---- BigWig (bbi) ----------------------------------------------------------------------------------------- */
-typedef struct pmx_bigwig pmx_bigwig;
+/* ---- Mappability tracks: one handle for every kind ------------------------------------------------------------------
+ * pmx_bigwig_open, pmx_ttrack_open and pmx_kmer_open each return a pmx_track (version >= 7; as pmx_dbw is the one track handle
+ * of pymasc_amd_ingest.h), read through the accessors below. */
+typedef struct pmx_track pmx_track;
+void pmx_track_close(pmx_track *t);
 
-int pmx_bigwig_open(const char *path, pmx_bigwig **out);
-void pmx_bigwig_close(pmx_bigwig *w);
+/* Chromosome dictionary = BigWigReader.chromsizes (reader/bigwig.pyx:60-75), in the order each open states. */
+int32_t pmx_track_nchrom(const pmx_track *t);
+const char *pmx_track_chrom_name(const pmx_track *t, int32_t i);
+int64_t pmx_track_chrom_len(const pmx_track *t, int32_t i);
 
-/* Chromosome dictionary = BigWigReader.chromsizes (reader/bigwig.pyx:60-75), in the file's B+ tree order. */
-int32_t pmx_bigwig_nchrom(const pmx_bigwig *w);
-const char *pmx_bigwig_chrom_name(const pmx_bigwig *w, int32_t i);
-int64_t pmx_bigwig_chrom_len(const pmx_bigwig *w, int32_t i);
-
-/* All intervals of `chrom` in ascending order whose float32 value is >= threshold (threshold <= 0: every interval),
- * as BigWigReader.fetch yields them (bigwig.pyx:147-177): begin 0-based inclusive, end exclusive.
+/* All intervals of `chrom`, in the order each open states, whose float32 value is >= threshold (threshold <= 0: every
+ * interval), as BigWigReader.fetch yields them (bigwig.pyx:147-177): begin 0-based inclusive, end exclusive.
  * Two-call protocol: with begin == NULL returns the number of intervals; otherwise fills up to cap entries and
- * returns the number written.  value may be NULL.  PMX_IO_ERR_NOTFOUND for an unknown chromosome (the
+ * returns the number written.  value may be NULL.  PMX_IO_ERR_NOTFOUND for a chromosome the dictionary does not hold (the
  * reference raises KeyError). */
-int64_t pmx_bigwig_fetch(pmx_bigwig *w, const char *chrom, float threshold, int64_t cap,
-                         uint32_t *begin, uint32_t *end, float *value);
+int64_t pmx_track_fetch(pmx_track *t, const char *chrom, float threshold, int64_t cap, uint32_t *begin, uint32_t *end,
+                        float *value);
+/* 1 when the intervals the last fetch delivered are non-empty, ascending and disjoint (begin_i < end_i, end_i <= begin_(i+1)),
+ * when there were none, and before the first fetch */
+int pmx_track_sorted(const pmx_track *t);
+/* 0 BigWig (a text track too, as on the device), 1 bigBed, 2 k-mer track: pmx_dbw_kind's numbering */
+int pmx_track_kind(const pmx_track *t);
 
-/* bigBed (version >= 5): pmx_bigwig_open also takes a bigBed file (magic 0x8789F2EB; fieldCount >= 3).  Its
+/* ---- BigWig (bbi): chromosomes in the file's B+ tree order, intervals in index order (ascending for a valid file) ------
+ * bigBed (version >= 5): pmx_bigwig_open also takes a bigBed file (magic 0x8789F2EB; fieldCount >= 3).  Its
  * records, decoded by the rules of io/bigbed_parse.h, are the intervals [chromStart, chromEnd) with value 1.0 in index order;
  * fetch keeps them as it keeps BigWig items.  A malformed record, end < start, a block of two chromosomes, a block that does not
- * inflate or fails its Adler-32: PMX_IO_ERR_FORMAT with bigbed_parse.h's message.  pmx_bigwig_kind: 0 BigWig, 1 bigBed. */
-int pmx_bigwig_kind(const pmx_bigwig *w);
+ * inflate or fails its Adler-32: PMX_IO_ERR_FORMAT with bigbed_parse.h's message. */
+int pmx_bigwig_open(const char *path, pmx_track **out);
 
 /* ---- Text tracks: bedGraph, BED, WIG -------------------------------------------------------
  * The host twin of pmx_dtt_open (pymasc_amd_ingest.h) and its checker.  `path` is plain text, BGZF or gzip (one or several
@@ -168,21 +174,9 @@ int pmx_bigwig_kind(const pmx_bigwig *w);
  * data line, else a .bed suffix (after .gz / .bgz) means BED, else bedGraph.  The whole text is read and parsed at open by the
  * rules of io/text_track_parse.h; values are (float)strtod of their text.  A malformed line, a bad number, a WIG data line
  * before any declaration, a second track line or a truncated gzip stream: PMX_IO_ERR_FORMAT, "line N: <reason>" (1-based).
- * nthreads is unused (one thread). */
-typedef struct pmx_ttrack pmx_ttrack;
-int pmx_ttrack_open(const char *path, int nthreads, pmx_ttrack **out);
-void pmx_ttrack_close(pmx_ttrack *t);
-/* The chromosomes that have lines, in the order of their first line; chrom_len = the largest end of its lines (an extent,
- * not a chromosome size). */
-int32_t pmx_ttrack_nchrom(const pmx_ttrack *t);
-const char *pmx_ttrack_chrom_name(const pmx_ttrack *t, int32_t i);
-int64_t pmx_ttrack_chrom_len(const pmx_ttrack *t, int32_t i);
-/* The intervals of `chrom` whose value is >= threshold (threshold <= 0: every one), in file order, with
- * pmx_bigwig_fetch's two-call protocol; PMX_IO_ERR_NOTFOUND for a chromosome without lines. */
-int64_t pmx_ttrack_fetch(pmx_ttrack *t, const char *chrom, float threshold, int64_t cap, uint32_t *begin, uint32_t *end,
-                         float *value);
-/* 1 when the intervals of the last fetch are ascending and disjoint (begin_(i+1) >= end_i), or there are none */
-int pmx_ttrack_sorted(const pmx_ttrack *t);
+ * nthreads is unused (one thread).  The chromosomes are those that have lines, in the order of their first line; chrom_len =
+ * the largest end of its lines (an extent, not a chromosome size); fetch delivers the lines in file order. */
+int pmx_ttrack_open(const char *path, int nthreads, pmx_track **out);
 
 /* ---- Genome FASTA -> k-mer uniqueness track (version >= 6) ------------------------------------------
  * The host twin of pmx_dkm_open (pymasc_amd_ingest.h) and its checker, by another method: no hashing.  `path` is a genome
@@ -192,15 +186,8 @@ int pmx_ttrack_sorted(const pmx_ttrack *t);
  * (min(F, R), compared word by word) and the groups of size one are unique.  The track of a record is its maximal runs of
  * unique positions, [p, q) with value 1.0, ascending and disjoint.  k outside [16, 1024]: PMX_IO_ERR_INVALID.  A malformed
  * file: PMX_IO_ERR_FORMAT, "line N: <reason>" (1-based, in the decompressed text), or the genome-size message.
- * nchrom / chrom_name / chrom_len: every record in file order with its length in bases; fetch / sorted as pmx_ttrack_*. */
-typedef struct pmx_kmer pmx_kmer;
-int pmx_kmer_open(const char *path, int32_t k, int nthreads, pmx_kmer **out);
-void pmx_kmer_close(pmx_kmer *t);
-int32_t pmx_kmer_nchrom(const pmx_kmer *t);
-const char *pmx_kmer_chrom_name(const pmx_kmer *t, int32_t i);
-int64_t pmx_kmer_chrom_len(const pmx_kmer *t, int32_t i);
-int64_t pmx_kmer_fetch(pmx_kmer *t, const char *chrom, float threshold, int64_t cap, uint32_t *begin, uint32_t *end, float *value);
-int pmx_kmer_sorted(const pmx_kmer *t);
+ * The chromosomes are every record in file order with its length in bases. */
+int pmx_kmer_open(const char *path, int32_t k, int nthreads, pmx_track **out);
 
 #ifdef __cplusplus
 }

@@ -15,124 +15,18 @@ from typing import Iterator, Tuple
 
 import numpy as np
 
-from .bam import PMX_BAM_DEFAULT_EXCLUDE, NativeReader, PmxIOError
 from .inputs import find_index
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_NAME = "libpymasc_ingest.so"
+from .native import INGEST_PROTOTYPES, PMX_BAM_DEFAULT_EXCLUDE, AlignmentReader, load_ingest_library
 
 #: every symbol include/pymasc_amd_ingest.h declares (tests/test_abi.py checks the built library against this list)
-INGEST_EXPORTS = [
-    "pmx_dbam_last_error", "pmx_dbam_version", "pmx_dbam_open", "pmx_dbam_close", "pmx_dbam_nref", "pmx_dbam_ref_name",
-    "pmx_dbam_ref_len", "pmx_dbam_header_text", "pmx_dbam_decode", "pmx_dbam_device_arrays", "pmx_dbam_fetch",
-    "pmx_dbam_runs", "pmx_dbam_counters", "pmx_dbam_timings", "pmx_dbam_inflated", "pmx_dbam_readlen_hist",
-    "pmx_dbam_readlen_counters", "pmx_dbam_open_indexed", "pmx_dbam_select", "pmx_dsam_open",
-    "pmx_dbam_open_stream", "pmx_dbam_stream_next", "pmx_dbam_stream_info",
-    "pmx_dbw_open", "pmx_dbw_close", "pmx_dbw_nchrom", "pmx_dbw_chrom_name", "pmx_dbw_chrom_len", "pmx_dbw_fetch", "pmx_dbw_device_arrays",
-    "pmx_dbw_sorted", "pmx_dbw_copy", "pmx_dtt_open", "pmx_dbed_open", "pmx_dbw_kind", "pmx_dkm_open",
-]
-
-_lib = None
-
-
-def ingest_library_path() -> str:
-    return os.environ.get("PYMASC_AMD_INGEST_LIB", os.path.join(_HERE, _LIB_NAME))
-
-
-def load_ingest_library():
-    """dlopen libpymasc_ingest.so (built by pymasc_amd/build.py:build_ingest) and declare its prototypes."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = ingest_library_path()
-    if not os.path.exists(path):
-        raise PmxIOError(-1, "{} not found: run `python pymasc_amd/build.py`".format(path))
-    L = ctypes.CDLL(path)
-    vp, i32, i64, u32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
-    L.pmx_dbam_last_error.restype = ctypes.c_char_p
-    L.pmx_dbam_version.restype = ctypes.c_int
-    L.pmx_dbam_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
-    L.pmx_dbam_open.restype = ctypes.c_int
-    L.pmx_dbam_open_indexed.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
-    L.pmx_dbam_open_indexed.restype = ctypes.c_int
-    L.pmx_dsam_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
-    L.pmx_dsam_open.restype = ctypes.c_int
-    L.pmx_dbed_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, i32, ctypes.POINTER(ctypes.c_char_p),
-                                ctypes.POINTER(i64), ctypes.POINTER(vp)]
-    L.pmx_dbed_open.restype = ctypes.c_int
-    L.pmx_dbam_open_stream.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, u64, ctypes.POINTER(vp)]
-    L.pmx_dbam_open_stream.restype = ctypes.c_int
-    L.pmx_dbam_stream_next.argtypes = [vp]
-    L.pmx_dbam_stream_next.restype = i64
-    L.pmx_dbam_stream_info.argtypes = [vp, ctypes.POINTER(u64)]
-    L.pmx_dbam_stream_info.restype = ctypes.c_int
-    L.pmx_dbam_select.argtypes = [vp, ctypes.POINTER(i32), i32]
-    L.pmx_dbam_select.restype = ctypes.c_int
-    L.pmx_dbam_close.argtypes = [vp]
-    L.pmx_dbam_close.restype = None
-    L.pmx_dbam_nref.argtypes = [vp]
-    L.pmx_dbam_nref.restype = i32
-    L.pmx_dbam_ref_name.argtypes = [vp, i32]
-    L.pmx_dbam_ref_name.restype = ctypes.c_char_p
-    L.pmx_dbam_ref_len.argtypes = [vp, i32]
-    L.pmx_dbam_ref_len.restype = i64
-    L.pmx_dbam_header_text.argtypes = [vp, ctypes.POINTER(u32)]
-    L.pmx_dbam_header_text.restype = ctypes.c_char_p
-    L.pmx_dbam_decode.argtypes = [vp, u32, u32, i32]
-    L.pmx_dbam_decode.restype = i64
-    L.pmx_dbam_device_arrays.argtypes = [vp] + [ctypes.POINTER(vp)] * 4
-    L.pmx_dbam_device_arrays.restype = ctypes.c_int
-    L.pmx_dbam_fetch.argtypes = [vp, i64, i64, vp, vp, vp, vp]
-    L.pmx_dbam_fetch.restype = ctypes.c_int
-    L.pmx_dbam_runs.argtypes = [vp, i64, vp, vp, vp, vp]
-    L.pmx_dbam_runs.restype = i64
-    L.pmx_dbam_counters.argtypes = [vp] + [ctypes.POINTER(u64)] * 6
-    L.pmx_dbam_counters.restype = ctypes.c_int
-    L.pmx_dbam_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-    L.pmx_dbam_timings.restype = ctypes.c_int
-    L.pmx_dbam_inflated.argtypes = [vp, u64, u64, vp]
-    L.pmx_dbam_inflated.restype = ctypes.c_int
-    L.pmx_dbam_readlen_hist.argtypes = [vp, u32, i64, vp, vp, vp]
-    L.pmx_dbam_readlen_hist.restype = i64
-    L.pmx_dbam_readlen_counters.argtypes = [vp, ctypes.POINTER(u64)]
-    L.pmx_dbam_readlen_counters.restype = ctypes.c_int
-    L.pmx_dbw_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
-    L.pmx_dbw_open.restype = ctypes.c_int
-    L.pmx_dtt_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
-    L.pmx_dtt_open.restype = ctypes.c_int
-    L.pmx_dbw_close.argtypes = [vp]
-    L.pmx_dbw_close.restype = None
-    L.pmx_dbw_nchrom.argtypes = [vp]
-    L.pmx_dbw_nchrom.restype = i32
-    L.pmx_dbw_chrom_name.argtypes = [vp, i32]
-    L.pmx_dbw_chrom_name.restype = ctypes.c_char_p
-    L.pmx_dbw_chrom_len.argtypes = [vp, i32]
-    L.pmx_dbw_chrom_len.restype = i64
-    L.pmx_dbw_fetch.argtypes = [vp, ctypes.c_char_p, ctypes.c_float]
-    L.pmx_dbw_fetch.restype = i64
-    L.pmx_dbw_device_arrays.argtypes = [vp] + [ctypes.POINTER(vp)] * 3
-    L.pmx_dbw_device_arrays.restype = ctypes.c_int
-    L.pmx_dbw_sorted.argtypes = [vp]
-    L.pmx_dbw_sorted.restype = ctypes.c_int
-    L.pmx_dbw_copy.argtypes = [vp, i64, i64, vp, vp, vp]
-    L.pmx_dbw_copy.restype = ctypes.c_int
-    L.pmx_dbw_kind.argtypes = [vp]
-    L.pmx_dbw_kind.restype = ctypes.c_int
-    L.pmx_dkm_open.argtypes = [ctypes.c_char_p, i32, ctypes.c_int, ctypes.c_int, i64, i32, ctypes.POINTER(vp)]
-    L.pmx_dkm_open.restype = ctypes.c_int
-    _lib = L
-    return L
-
-
-def _raise(code: int):
-    raise PmxIOError(int(code), load_ingest_library().pmx_dbam_last_error().decode("utf-8", "replace"))
+INGEST_EXPORTS = list(INGEST_PROTOTYPES)
 
 
 class UnknownReferenceError(ValueError, KeyError):
     """A reference name the BAM header does not hold (a ValueError; a KeyError too, as ``fetch`` raised before)."""
 
 
-class DeviceBamReader(NativeReader):
+class DeviceBamReader(AlignmentReader):
     """A BAM file inflated and decoded on the GPU; batches of filtered read arrays like ``BamReader``.
 
     ``references``: None reads the whole file (every reference selected).  A list of names with an index present (``index``:
@@ -140,7 +34,8 @@ class DeviceBamReader(NativeReader):
     (``pmx_dbam_open_indexed`` + ``pmx_dbam_select``); without an index the whole file is read and the selection is applied to
     the records.  ``select(names)`` replaces the selection (the two-step use: open with ``references=[]``, read the header,
     choose).  ``references`` / ``lengths`` always list the whole header; ``selected`` the chosen names in header order."""
-    _CLOSE = "pmx_dbam_close"
+    _P = "pmx_dbam"
+    _COUNTERS = ("records", "kept", "bytes_out", "bytes_in", "members", "rewalked")
 
     def __init__(self, path, device: int = 0, threads: int = 0, references=None, index=None):
         self._L = load_ingest_library()
@@ -150,22 +45,17 @@ class DeviceBamReader(NativeReader):
         else:
             index = None
         self.indexed = index is not None
-        h = ctypes.c_void_p()
         if self.indexed:
-            rc = self._L.pmx_dbam_open_indexed(self.path.encode(), index.encode(), int(device), int(threads), ctypes.byref(h))
+            h = self._open_handle("pmx_dbam_open_indexed", self.path.encode(), index.encode(), int(device), int(threads))
         else:
-            rc = self._L.pmx_dbam_open(self.path.encode(), int(device), int(threads), ctypes.byref(h))
-        if rc:
-            _raise(rc)
+            h = self._open_handle("pmx_dbam_open", self.path.encode(), int(device), int(threads))
         self._attach(h, references)
 
     def _attach(self, h, references) -> None:
         """The handle of an open: the header's references, then the selection."""
         self._h = h
-        n = self._L.pmx_dbam_nref(h)
-        self.references: Tuple[str, ...] = tuple(self._L.pmx_dbam_ref_name(h, i).decode() for i in range(n))
-        self.lengths: Tuple[int, ...] = tuple(int(self._L.pmx_dbam_ref_len(h, i)) for i in range(n))
-        self._selected = frozenset(range(n))
+        self._load_references()
+        self._selected = frozenset(range(len(self.references)))
         if references is not None:
             references = [references] if isinstance(references, str) else list(references)
             try:
@@ -190,15 +80,14 @@ class DeviceBamReader(NativeReader):
     def select(self, names) -> None:
         """Only the records of ``names`` from now on.  An indexed reader reads, copies and inflates just their BGZF members
         (the stream is replaced; ``counters()`` counts what was read); an unknown name raises ValueError."""
-        if self._h is None:
-            raise ValueError("I/O operation on closed BAM reader")
+        self._check_open()
         ids = sorted(set(self._ids(names)))
         if self.indexed:
             arr = (ctypes.c_int32 * max(len(ids), 1))(*ids)
             rc = self._L.pmx_dbam_select(self._h, arr, len(ids))
             if rc:
                 self._selected = frozenset()
-                _raise(rc)
+                self._raise(rc)
         self._selected = frozenset(ids)
 
     @property
@@ -214,24 +103,11 @@ class DeviceBamReader(NativeReader):
         """Every selected reference can be fetched on its own (its records are resident): no .bai needed for that."""
         return True
 
-    @property
-    def header_text(self) -> str:
-        ln = ctypes.c_uint32()
-        t = self._L.pmx_dbam_header_text(self._h, ctypes.byref(ln))
-        return (t or b"").decode("utf-8", "replace")
-
-    def counters(self) -> dict:
-        v = [ctypes.c_uint64() for _ in range(6)]
-        rc = self._L.pmx_dbam_counters(self._h, *[ctypes.byref(x) for x in v])
-        if rc:
-            _raise(rc)
-        return dict(zip(("records", "kept", "bytes_out", "bytes_in", "members", "rewalked"), (int(x.value) for x in v)))
-
     def timings(self) -> dict:
         t = (ctypes.c_double * 6)()
         rc = self._L.pmx_dbam_timings(self._h, t)
         if rc:
-            _raise(rc)
+            self._raise(rc)
         return dict(zip(("upload_s", "inflate_s", "crc_s", "header_s", "chain_s", "write_s"), (float(x) for x in t)))
 
     def inflated(self, first: int = 0, n: int = None) -> bytes:
@@ -241,34 +117,15 @@ class DeviceBamReader(NativeReader):
         buf = np.empty(max(n, 1), dtype=np.uint8)
         rc = self._L.pmx_dbam_inflated(self._h, int(first), int(n), buf.ctypes.data)
         if rc:
-            _raise(rc)
+            self._raise(rc)
         return buf[:n].tobytes()
-
-    def decode(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, reference: int = -1) -> int:
-        """Runs the record walk + filter on the device; returns the number of kept records (they stay in HBM)."""
-        if self._h is None:
-            raise ValueError("I/O operation on closed BAM reader")
-        n = self._L.pmx_dbam_decode(self._h, int(mapq_criteria), int(flag_exclude), int(reference))
-        if n < 0:
-            _raise(n)
-        return int(n)
-
-    def read_length_histogram(self, mapq_criteria: int = 0):
-        """The read-length histogram with the estimator's filter (PyMaSC core/readlen.pyx:estimate_readlen), built by one more
-        walk over the record chain already in HBM; the arrays of the last ``decode`` are left as they are.  Returns a
-        ``pymasc_amd.readlen.ReadLengthHistogram``; its first-occurrence keys are byte offsets in the inflated stream."""
-        from .readlen import histogram_from_library
-        if self._h is None:
-            raise ValueError("I/O operation on closed BAM reader")
-        return histogram_from_library(self._L.pmx_dbam_readlen_hist, self._L.pmx_dbam_readlen_counters, self._h, mapq_criteria,
-                                      _raise)
 
     def device_arrays(self) -> Tuple[int, int, int, int]:
         """Device addresses of (ref_id int32, pos1 int32, read_len int32, reverse uint8) of the last decode."""
         v = [ctypes.c_void_p() for _ in range(4)]
         rc = self._L.pmx_dbam_device_arrays(self._h, *[ctypes.byref(x) for x in v])
         if rc:
-            _raise(rc)
+            self._raise(rc)
         return tuple(int(x.value or 0) for x in v)
 
     def device_runs(self):
@@ -278,14 +135,14 @@ class DeviceBamReader(NativeReader):
         if n == -3:
             return None
         if n < 0:
-            _raise(n)
+            self._raise(n)
         start = np.empty(max(n, 1), dtype=np.int64)
         ref = np.empty(max(n, 1), dtype=np.int32)
         first = np.empty(max(n, 1), dtype=np.int32)
         last = np.empty(max(n, 1), dtype=np.int32)
         m = self._L.pmx_dbam_runs(self._h, n, start.ctypes.data, ref.ctypes.data, first.ctypes.data, last.ctypes.data)
         if m < 0:
-            _raise(m)
+            self._raise(m)
         total = self.counters()["kept"]
         ends = list(start[1:m]) + [total]
         return [(int(ref[r]), int(start[r]), int(ends[r] - start[r]), int(first[r]), int(last[r])) for r in range(m)]
@@ -318,16 +175,6 @@ class DeviceBamReader(NativeReader):
         else:
             calculator._ctx.sync()      # the feeders read this reader's arrays: they must be done before it may be closed
         return fed
-
-    def _fetch(self, first: int, n: int):
-        ref = np.empty(n, dtype=np.int32)
-        pos = np.empty(n, dtype=np.int32)
-        rlen = np.empty(n, dtype=np.int32)
-        rev = np.empty(n, dtype=np.uint8)
-        rc = self._L.pmx_dbam_fetch(self._h, first, n, ref.ctypes.data, pos.ctypes.data, rlen.ctypes.data, rev.ctypes.data)
-        if rc:
-            _raise(rc)
-        return ref, pos, rlen, rev.astype(bool)
 
     def batches(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, batch: int = 1 << 22,
                 _reference: int = -1) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:

@@ -19,8 +19,8 @@ import ctypes
 import os
 from typing import Tuple
 
-from .bam import PmxIOError, _raise, load_io_library
-from .bam_device import DeviceBamReader, _raise as _raise_device
+from .bam_device import DeviceBamReader
+from .native import PmxIOError, load_ingest_library, load_io_library
 from .sam import SamReader
 
 _SUFFIXES = (".tagalign", ".bed")
@@ -66,11 +66,7 @@ class BedReadsReader(SamReader):
     def __init__(self, path, references, lengths, threads: int = 0):
         self._L = load_io_library()
         self.path = os.fspath(path)
-        h = ctypes.c_void_p()
-        rc = self._L.pmx_bed_open(self.path.encode(), int(threads), *_c_sizes(references, lengths), ctypes.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
+        self._h = self._open_handle("pmx_bed_open", self.path.encode(), int(threads), *_c_sizes(references, lengths))
         self.references: Tuple[str, ...] = tuple(references)
         self.lengths: Tuple[int, ...] = tuple(int(v) for v in lengths)
 
@@ -84,15 +80,11 @@ class DeviceBedReadsReader(DeviceBamReader):
     an index."""
 
     def __init__(self, path, references, lengths, device: int = 0, threads: int = 0, select=None):
-        from .bam_device import load_ingest_library
         self._L = load_ingest_library()
         self.path = os.fspath(path)
         self.indexed = False
-        h = ctypes.c_void_p()
-        rc = self._L.pmx_dbed_open(self.path.encode(), int(device), int(threads), *_c_sizes(references, lengths), ctypes.byref(h))
-        if rc:
-            _raise_device(rc)
-        self._attach(h, select)
+        self._attach(self._open_handle("pmx_dbed_open", self.path.encode(), int(device), int(threads),
+                                       *_c_sizes(references, lengths)), select)
 
 
 class SizesHeader:

@@ -6,7 +6,7 @@
 // unknown length -- are inflated by k_bgzf_inflate (one wavefront each, `open_size`), their Adler-32 checked (k_bw_adler), their
 // sections (bedGraph / variableStep / fixedStep items) decoded and filtered by k_bw_sections, and the intervals land in device
 // arrays in index order, where pmx_bits_set_regions_dev_ex (include/pymasc_amd.h) builds the mappability vector from them.
-// Same intervals as pmx_bigwig_fetch (libpymasc_io.so, the checker), bit for bit.
+// Same intervals as pmx_track_fetch (libpymasc_io.so, the checker), bit for bit.
 //
 // A bigBed file (io/bigbed_parse.h, DESIGN.md 7.12) takes the same path up to the decode: its blocks hold BED records, walked by
 // k_bb_records (bigbed_device.inc) in place of k_bw_sections.

@@ -17,6 +17,7 @@
 #include "../../../include/pymasc_amd_io.h"
 #include "bigbed_parse.h"
 #include "io_common.h"
+#include "track.h"
 
 #include <zlib.h>
 
@@ -39,33 +40,27 @@ struct Interval {
     float value;
 };
 
-}  // namespace
-
-struct pmx_bigwig {
+struct BbiTrack : pmx_track {           // names / sizes in B+ tree order; kind 1: a bigBed file, data blocks of BED records
     pmx_io::MappedFile file;
     uint16_t version = 0;
-    bool bigbed = false;                // a bigBed file: data blocks of BED records
     uint64_t chrom_tree_off = 0, data_off = 0, index_off = 0;
     uint32_t uncompress_buf = 0;
-    std::vector<std::string> names;     // in B+ tree order
     std::vector<uint32_t> ids;
-    std::vector<int64_t> sizes;
     int nthreads = 1;
     // result of the last counting call, handed out by the filling call that follows it
     std::string cache_chrom;
     float cache_threshold = 0;
     bool cache_valid = false;
     std::vector<Interval> cache;
+    int64_t fetch(size_t k, float threshold, int64_t cap, uint32_t *begin, uint32_t *end, float *value) override;
 };
 
-namespace {
-
 struct Cursor {
-    const pmx_bigwig &w;
+    const BbiTrack &w;
     const uint8_t *at(uint64_t off, uint64_t n) const
     {
         if (off > w.file.size || n > w.file.size - off)
-            throw pmx_io::Error(PMX_IO_ERR_FORMAT, std::string(w.bigbed ? "bigBed" : "BigWig") +
+            throw pmx_io::Error(PMX_IO_ERR_FORMAT, std::string(w.kind ? "bigBed" : "BigWig") +
                                                        " structure points past the end of the file");
         return w.file.data + off;
     }
@@ -75,7 +70,7 @@ struct Cursor {
     uint64_t u64(uint64_t off) const { uint64_t v; memcpy(&v, at(off, 8), 8); return v; }
 };
 
-void walk_chrom_tree(pmx_bigwig &w, const Cursor &c, uint64_t node, uint32_t key_size, uint32_t val_size, int depth)
+void walk_chrom_tree(BbiTrack &w, const Cursor &c, uint64_t node, uint32_t key_size, uint32_t val_size, int depth)
 {
     if (depth > 32) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "chromosome tree too deep");
     const bool leaf = c.u8(node) != 0;
@@ -124,7 +119,7 @@ void walk_rtree(const Cursor &c, uint64_t node, uint32_t cid, std::vector<Span> 
 
 // A bigBed data block: zlib-checked like the device reader (header bytes, raw DEFLATE, then Adler-32, so both name the same
 // failure), then its records by bigbed::walk_block.  A block of another chromosome keeps nothing.
-void decode_bigbed_block(const pmx_bigwig &w, const Span &sp, uint32_t cid, int64_t chrom_len, float threshold,
+void decode_bigbed_block(const BbiTrack &w, const Span &sp, uint32_t cid, int64_t chrom_len, float threshold,
                          std::vector<Interval> &out)
 {
     const Cursor c{w};
@@ -165,7 +160,7 @@ void decode_bigbed_block(const pmx_bigwig &w, const Span &sp, uint32_t cid, int6
     if (rc) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::err_text(rc));
 }
 
-void decode_block(const pmx_bigwig &w, const Span &sp, uint32_t cid, int64_t chrom_len, float threshold,
+void decode_block(const BbiTrack &w, const Span &sp, uint32_t cid, int64_t chrom_len, float threshold,
                   std::vector<Interval> &out)
 {
     const Cursor c{w};
@@ -217,7 +212,7 @@ void decode_block(const pmx_bigwig &w, const Span &sp, uint32_t cid, int64_t chr
     }
 }
 
-void open_impl(pmx_bigwig &w, const char *path)
+void open_impl(BbiTrack &w, const char *path)
 {
     w.file.open(path);
     const Cursor c{w};
@@ -226,8 +221,8 @@ void open_impl(pmx_bigwig &w, const char *path)
         throw pmx_io::Error(PMX_IO_ERR_FORMAT, "byte-swapped (big-endian) BigWig files are not supported");
     if (magic == __builtin_bswap32(bigbed::MAGIC)) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_SWAPPED);
     if (magic != BIGWIG_MAGIC && magic != bigbed::MAGIC) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "not a BigWig file (bad magic)");
-    w.bigbed = magic == bigbed::MAGIC;
-    if (w.bigbed && c.u16(32) < 3) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_FIELDS);
+    w.kind = magic == bigbed::MAGIC ? 1 : 0;
+    if (w.kind && c.u16(32) < 3) throw pmx_io::Error(PMX_IO_ERR_FORMAT, bigbed::ERR_FIELDS);
     w.version = c.u16(4);
     w.chrom_tree_off = c.u64(8);
     w.data_off = c.u64(16);
@@ -245,93 +240,61 @@ void open_impl(pmx_bigwig &w, const char *path)
     w.nthreads = pmx_io::pick_threads(0);
 }
 
+// Decodes the chromosome's blocks on a counting call and keeps them for the filling call that follows it.
+int64_t BbiTrack::fetch(size_t k, float threshold, int64_t cap, uint32_t *begin, uint32_t *end, float *value)
+{
+    if (!(cache_valid && cache_chrom == names[k] && cache_threshold == threshold)) {
+        const Cursor c{*this};
+        std::vector<Span> spans;
+        uint64_t items = 0;
+        walk_rtree(c, index_off + 48, ids[k], spans, 0, items);
+        std::vector<std::vector<Interval>> parts(spans.size());
+        const uint32_t cid = ids[k];
+        const int64_t clen = sizes[k];
+        pmx_io::parallel_for(nthreads, spans.size(), 8, [&](size_t lo, size_t hi, size_t) {
+            for (size_t i = lo; i < hi; i++) {
+                if (kind) decode_bigbed_block(*this, spans[i], cid, clen, threshold, parts[i]);
+                else decode_block(*this, spans[i], cid, clen, threshold, parts[i]);
+            }
+        });
+        size_t total = 0;
+        for (auto &v : parts) total += v.size();
+        cache.clear();
+        cache.reserve(total);
+        for (auto &v : parts) cache.insert(cache.end(), v.begin(), v.end());
+        cache_chrom = names[k];
+        cache_threshold = threshold;
+        cache_valid = true;
+    }
+    const size_t n = begin ? std::min<size_t>((size_t)cap, cache.size()) : cache.size();
+    pmx_io::Sorted s;
+    for (size_t i = 0; i < n; i++) {
+        s.add(cache[i].begin, cache[i].end);
+        if (begin) {
+            begin[i] = cache[i].begin;
+            end[i] = cache[i].end;
+            if (value) value[i] = cache[i].value;
+        }
+    }
+    sorted = s.ok;
+    if (begin) {
+        cache_valid = false;
+        std::vector<Interval>().swap(cache);
+    }
+    return (int64_t)n;
+}
+
 }  // namespace
 
 extern "C" {
 
-int pmx_bigwig_open(const char *path, pmx_bigwig **out)
+int pmx_bigwig_open(const char *path, pmx_track **out)
 {
-    if (!path || !out) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bigwig_open: NULL argument");
-    *out = nullptr;
-    pmx_bigwig *w = new pmx_bigwig();
-    try {
+    return pmx_io::open_track("pmx_bigwig_open", path, out, [&]() {
+        std::unique_ptr<BbiTrack> w(new BbiTrack);
         open_impl(*w, path);
-    } catch (const pmx_io::Error &e) {
-        delete w;
-        return pmx_io::fail(e.code, std::string(path) + ": " + e.msg);
-    } catch (const std::exception &e) {
-        delete w;
-        return pmx_io::fail(PMX_IO_ERR_OPEN, std::string(path) + ": " + e.what());
-    }
-    *out = w;
-    return PMX_IO_OK;
-}
-
-void pmx_bigwig_close(pmx_bigwig *w) { delete w; }
-
-int pmx_bigwig_kind(const pmx_bigwig *w) { return (w && w->bigbed) ? 1 : 0; }
-
-int32_t pmx_bigwig_nchrom(const pmx_bigwig *w) { return w ? (int32_t)w->names.size() : 0; }
-
-const char *pmx_bigwig_chrom_name(const pmx_bigwig *w, int32_t i)
-{
-    if (!w || i < 0 || (size_t)i >= w->names.size()) return nullptr;
-    return w->names[i].c_str();
-}
-
-int64_t pmx_bigwig_chrom_len(const pmx_bigwig *w, int32_t i)
-{
-    if (!w || i < 0 || (size_t)i >= w->sizes.size()) return -1;
-    return w->sizes[i];
-}
-
-int64_t pmx_bigwig_fetch(pmx_bigwig *w, const char *chrom, float threshold, int64_t cap, uint32_t *begin,
-                         uint32_t *end, float *value)
-{
-    if (!w || !chrom) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bigwig_fetch: NULL argument");
-    if (begin && (!end || cap < 0)) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bigwig_fetch: end is NULL or cap < 0");
-    size_t k = 0;
-    while (k < w->names.size() && w->names[k] != chrom) k++;
-    if (k == w->names.size()) return pmx_io::fail(PMX_IO_ERR_NOTFOUND, std::string("unknown chromosome: ") + chrom);
-    try {
-        if (!(w->cache_valid && w->cache_chrom == chrom && w->cache_threshold == threshold)) {
-            const Cursor c{*w};
-            std::vector<Span> spans;
-            uint64_t items = 0;
-            walk_rtree(c, w->index_off + 48, w->ids[k], spans, 0, items);
-            std::vector<std::vector<Interval>> parts(spans.size());
-            const uint32_t cid = w->ids[k];
-            const int64_t clen = w->sizes[k];
-            pmx_io::parallel_for(w->nthreads, spans.size(), 8, [&](size_t lo, size_t hi, size_t) {
-                for (size_t i = lo; i < hi; i++) {
-                    if (w->bigbed) decode_bigbed_block(*w, spans[i], cid, clen, threshold, parts[i]);
-                    else decode_block(*w, spans[i], cid, clen, threshold, parts[i]);
-                }
-            });
-            size_t total = 0;
-            for (auto &v : parts) total += v.size();
-            w->cache.clear();
-            w->cache.reserve(total);
-            for (auto &v : parts) w->cache.insert(w->cache.end(), v.begin(), v.end());
-            w->cache_chrom = chrom;
-            w->cache_threshold = threshold;
-            w->cache_valid = true;
-        }
-        if (!begin) return (int64_t)w->cache.size();
-        const size_t n = std::min<size_t>((size_t)cap, w->cache.size());
-        for (size_t i = 0; i < n; i++) {
-            begin[i] = w->cache[i].begin;
-            end[i] = w->cache[i].end;
-            if (value) value[i] = w->cache[i].value;
-        }
-        w->cache_valid = false;
-        std::vector<Interval>().swap(w->cache);
-        return (int64_t)n;
-    } catch (const pmx_io::Error &e) {
-        return pmx_io::fail(e.code, e.msg);
-    } catch (const std::exception &e) {
-        return pmx_io::fail(PMX_IO_ERR_FORMAT, e.what());
-    }
+        return w;
+    });
 }
 
 }  // extern "C"

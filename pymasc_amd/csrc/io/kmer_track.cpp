@@ -1,28 +1,22 @@
-// The exact k-mer uniqueness track of a genome FASTA on host threads (include/pymasc_amd_io.h, pmx_kmer_*).
+// The exact k-mer uniqueness track of a genome FASTA on host threads (include/pymasc_amd_io.h, pmx_kmer_open).
 // The host twin of the device generator (ingest/kmer_track_device.inc) and its checker, by another method: no hashing.
 //
 //   file (mmap; gzip / BGZF: every member inflated with zlib) --the rules of io/fasta_parse.h, one line at a time--> the
 //   packed genome (2 bits and a valid bit per position, a separator in front of every record) --> every position whose k-mer
 //   exists and is no palindrome, with the strand of its canonical k-mer --> the positions sorted on nthreads threads by the
 //   canonical packed k-mer, compared word by word --> the groups of size one are the unique positions --> per record, its runs
-//   of unique positions as [p, q) with value 1.0
+//   of unique positions as [p, q) with value 1.0 (track.h's StoredTrack without a value vector)
 #include "../../../include/pymasc_amd_io.h"
 #include "fasta_parse.h"
 #include "io_common.h"
 #include "text_track_parse.h"
+#include "track.h"
 
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <unordered_set>
 #include <vector>
-
-struct pmx_kmer {
-    std::vector<std::string> names;          // in file order
-    std::vector<int64_t> sizes;              // the records' lengths in bases
-    std::vector<std::vector<uint32_t>> b, e;
-    bool sorted = true;
-};
 
 namespace {
 
@@ -46,7 +40,7 @@ void put(Genome &g, uint64_t q, uint32_t code)
     }
 }
 
-void parse_fasta(pmx_kmer &t, Genome &g, const uint8_t *text, uint64_t N)
+void parse_fasta(pmx_io::StoredTrack &t, Genome &g, const uint8_t *text, uint64_t N)
 {
     using namespace fasta;
     ttrack::PtrSrc s{text};
@@ -114,7 +108,7 @@ void parse_fasta(pmx_kmer &t, Genome &g, const uint8_t *text, uint64_t N)
     g.V.resize(words, 0);
 }
 
-void generate(pmx_kmer &t, const Genome &g, uint32_t k, int nthreads)
+void generate(pmx_io::StoredTrack &t, const Genome &g, uint32_t k, int nthreads)
 {
     using namespace fasta;
     const uint64_t npos = g.npos;
@@ -197,20 +191,20 @@ void generate(pmx_kmer &t, const Genome &g, uint32_t k, int nthreads)
 
 extern "C" {
 
-int pmx_kmer_open(const char *path, int32_t k, int nthreads, pmx_kmer **out)
+int pmx_kmer_open(const char *path, int32_t k, int nthreads, pmx_track **out)
 {
-    if (!path || !out) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_kmer_open: NULL argument");
-    *out = nullptr;
-    if (k < (int32_t)fasta::K_MIN || k > (int32_t)fasta::K_MAX) return pmx_io::fail(PMX_IO_ERR_INVALID, fasta::bad_k_text(k));
-    nthreads = pmx_io::pick_threads(nthreads);
-    pmx_kmer *t = new pmx_kmer;
-    try {
+    if (path && out && (k < (int32_t)fasta::K_MIN || k > (int32_t)fasta::K_MAX)) {
+        *out = nullptr;
+        return pmx_io::fail(PMX_IO_ERR_INVALID, fasta::bad_k_text(k));
+    }
+    return pmx_io::open_track("pmx_kmer_open", path, out, [&]() {
+        std::unique_ptr<pmx_io::StoredTrack> t(new pmx_io::StoredTrack);
+        t->kind = 2;
         Genome g;
         {
             pmx_io::MappedFile f;
             f.open(path);
-            const int comp = ttrack::detect_compression(f.data, f.size);
-            if (comp == ttrack::COMP_PLAIN) {
+            if (ttrack::detect_compression(f.data, f.size) == ttrack::COMP_PLAIN) {
                 parse_fasta(*t, g, f.data, f.size);
             } else {
                 std::vector<uint8_t> text;
@@ -220,54 +214,9 @@ int pmx_kmer_open(const char *path, int32_t k, int nthreads, pmx_kmer **out)
                 parse_fasta(*t, g, text.data(), text.size());
             }
         }
-        generate(*t, g, (uint32_t)k, nthreads);
-    } catch (const pmx_io::Error &e) {
-        delete t;
-        return pmx_io::fail(e.code, std::string(path) + ": " + e.msg);
-    } catch (const std::exception &e) {
-        delete t;
-        return pmx_io::fail(PMX_IO_ERR_OPEN, std::string(path) + ": " + e.what());
-    }
-    *out = t;
-    return PMX_IO_OK;
-}
-
-void pmx_kmer_close(pmx_kmer *t) { delete t; }
-
-int32_t pmx_kmer_nchrom(const pmx_kmer *t) { return t ? (int32_t)t->names.size() : 0; }
-
-const char *pmx_kmer_chrom_name(const pmx_kmer *t, int32_t i)
-{
-    if (!t || i < 0 || (size_t)i >= t->names.size()) return nullptr;
-    return t->names[(size_t)i].c_str();
-}
-
-int64_t pmx_kmer_chrom_len(const pmx_kmer *t, int32_t i)
-{
-    if (!t || i < 0 || (size_t)i >= t->sizes.size()) return -1;
-    return t->sizes[(size_t)i];
-}
-
-int pmx_kmer_sorted(const pmx_kmer *t) { return (t && t->sorted) ? 1 : 0; }
-
-int64_t pmx_kmer_fetch(pmx_kmer *t, const char *chrom, float threshold, int64_t cap, uint32_t *begin, uint32_t *end, float *value)
-{
-    if (!t || !chrom) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_kmer_fetch: NULL argument");
-    if (begin && (!end || cap < 0)) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_kmer_fetch: end is NULL or cap < 0");
-    size_t c = 0;
-    while (c < t->names.size() && t->names[c] != chrom) c++;
-    if (c == t->names.size()) return pmx_io::fail(PMX_IO_ERR_NOTFOUND, std::string("unknown chromosome: ") + chrom);
-    t->sorted = true;                         // (the runs are ascending and disjoint)
-    if (threshold > 1.0f) return 0;           // every value is 1.0
-    const int64_t n = (int64_t)t->b[c].size();
-    if (begin) {
-        const int64_t m = std::min(n, cap);
-        std::copy(t->b[c].begin(), t->b[c].begin() + m, begin);
-        std::copy(t->e[c].begin(), t->e[c].begin() + m, end);
-        if (value) std::fill(value, value + m, 1.0f);
-        return m;
-    }
-    return n;
+        generate(*t, g, (uint32_t)k, pmx_io::pick_threads(nthreads));
+        return t;
+    });
 }
 
 }  // extern "C"

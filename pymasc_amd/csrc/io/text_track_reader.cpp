@@ -1,5 +1,5 @@
 // Text mappability tracks -- bedGraph, BED, WIG; plain, BGZF or gzip -- -> the intervals a BigWig reader gives
-// (include/pymasc_amd_io.h, pmx_ttrack_*).  The host twin of the device reader (ingest/text_track_device.inc) and its
+// (include/pymasc_amd_io.h, pmx_ttrack_open; the handle is track.h's StoredTrack).  The host twin of the device reader (ingest/text_track_device.inc) and its
 // checker: the same rules (io/text_track_parse.h), every value through (float)strtod.  The whole text is read at open:
 //
 //   file (mmap; gzip / BGZF: every member inflated with zlib) --kind from the first lines (track type=, a WIG declaration,
@@ -8,6 +8,7 @@
 #include "../../../include/pymasc_amd_io.h"
 #include "io_common.h"
 #include "text_track_parse.h"
+#include "track.h"
 
 #include <algorithm>
 #include <cstring>
@@ -15,21 +16,13 @@
 #include <unordered_map>
 #include <vector>
 
-struct pmx_ttrack {
-    std::vector<std::string> names;          // in the order of their first data line
-    std::vector<int64_t> sizes;              // the largest end of each chromosome's lines
-    std::vector<std::vector<uint32_t>> b, e;
-    std::vector<std::vector<float>> v;
-    uint32_t kind = 0;
-    bool sorted = true;                      // the intervals of the last fetch are ascending and disjoint
-};
-
 namespace {
 
-void parse_text(pmx_ttrack &t, const uint8_t *text, uint64_t N, const std::string &path)
+void parse_text(pmx_io::StoredTrack &t, const uint8_t *text, uint64_t N, const std::string &path)
 {
     using namespace ttrack;
-    if (detect_kind(text, N, true, path, t.kind) != 0) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "cannot tell the kind of track");
+    uint32_t kind = 0;                   // bedGraph, BED or WIG (the handle's kind stays 0: a text track answers as a BigWig)
+    if (detect_kind(text, N, true, path, kind) != 0) throw pmx_io::Error(PMX_IO_ERR_FORMAT, "cannot tell the kind of track");
     PtrSrc s{text};
     std::unordered_map<std::string, uint32_t> ids;
     uint64_t line = 0, p = 0;
@@ -55,7 +48,7 @@ void parse_text(pmx_ttrack &t, const uint8_t *text, uint64_t N, const std::strin
         const uint8_t *q = (const uint8_t *)memchr(text + p, '\n', (size_t)(N - p));
         const uint64_t end = q ? (uint64_t)(q - text) : N;
         Line L;
-        uint32_t err = parse_line(s, p, end, t.kind, L);
+        uint32_t err = parse_line(s, p, end, kind, L);
         if (!err && L.type == L_TRACK) {
             if (seen_data) err = TT_ERR_LATE_TRACK;
             else if (seen_track) err = TT_ERR_TRACK;
@@ -74,7 +67,7 @@ void parse_text(pmx_ttrack &t, const uint8_t *text, uint64_t N, const std::strin
         } else if (!err && L.type == L_DATA) {
             seen_data = true;
             uint32_t c = 0, b = L.b, e = L.e;
-            if (t.kind == KIND_WIG) {
+            if (kind == KIND_WIG) {
                 if (decl == L_SKIP) err = TT_ERR_NODECL;
                 else err = wig_interval(decl, L.nfields, L.b, start, step, span, k++, b, e);
                 if (!err && !have_chrom) {
@@ -86,7 +79,7 @@ void parse_text(pmx_ttrack &t, const uint8_t *text, uint64_t N, const std::strin
                 c = chrom_of(L.name, L.nlen);
             }
             if (!err) {
-                const float v = (t.kind == KIND_BED) ? 1.0f : slow_value((const char *)text + L.voff, L.vlen);
+                const float v = (kind == KIND_BED) ? 1.0f : slow_value((const char *)text + L.voff, L.vlen);
                 t.b[c].push_back(b);
                 t.e[c].push_back(e);
                 t.v[c].push_back(v);
@@ -102,17 +95,14 @@ void parse_text(pmx_ttrack &t, const uint8_t *text, uint64_t N, const std::strin
 
 extern "C" {
 
-int pmx_ttrack_open(const char *path, int nthreads, pmx_ttrack **out)
+int pmx_ttrack_open(const char *path, int nthreads, pmx_track **out)
 {
     (void)nthreads;
-    if (!path || !out) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_ttrack_open: NULL argument");
-    *out = nullptr;
-    pmx_ttrack *t = new pmx_ttrack;
-    try {
+    return pmx_io::open_track("pmx_ttrack_open", path, out, [&]() {
+        std::unique_ptr<pmx_io::StoredTrack> t(new pmx_io::StoredTrack);
         pmx_io::MappedFile f;
         f.open(path);
-        const int comp = ttrack::detect_compression(f.data, f.size);
-        if (comp == ttrack::COMP_PLAIN) {
+        if (ttrack::detect_compression(f.data, f.size) == ttrack::COMP_PLAIN) {
             parse_text(*t, f.data, f.size, path);
         } else {
             std::vector<uint8_t> text;
@@ -121,62 +111,8 @@ int pmx_ttrack_open(const char *path, int nthreads, pmx_ttrack **out)
             f.close();
             parse_text(*t, text.data(), text.size(), path);
         }
-    } catch (const pmx_io::Error &e) {
-        delete t;
-        return pmx_io::fail(e.code, std::string(path) + ": " + e.msg);
-    } catch (const std::exception &e) {
-        delete t;
-        return pmx_io::fail(PMX_IO_ERR_OPEN, std::string(path) + ": " + e.what());
-    }
-    *out = t;
-    return PMX_IO_OK;
-}
-
-void pmx_ttrack_close(pmx_ttrack *t) { delete t; }
-
-int32_t pmx_ttrack_nchrom(const pmx_ttrack *t) { return t ? (int32_t)t->names.size() : 0; }
-
-const char *pmx_ttrack_chrom_name(const pmx_ttrack *t, int32_t i)
-{
-    if (!t || i < 0 || (size_t)i >= t->names.size()) return nullptr;
-    return t->names[(size_t)i].c_str();
-}
-
-int64_t pmx_ttrack_chrom_len(const pmx_ttrack *t, int32_t i)
-{
-    if (!t || i < 0 || (size_t)i >= t->sizes.size()) return -1;
-    return t->sizes[(size_t)i];
-}
-
-int pmx_ttrack_sorted(const pmx_ttrack *t) { return (t && t->sorted) ? 1 : 0; }
-
-int64_t pmx_ttrack_fetch(pmx_ttrack *t, const char *chrom, float threshold, int64_t cap, uint32_t *begin, uint32_t *end,
-                         float *value)
-{
-    if (!t || !chrom) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_ttrack_fetch: NULL argument");
-    if (begin && (!end || cap < 0)) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_ttrack_fetch: end is NULL or cap < 0");
-    size_t k = 0;
-    while (k < t->names.size() && t->names[k] != chrom) k++;
-    if (k == t->names.size()) return pmx_io::fail(PMX_IO_ERR_NOTFOUND, std::string("unknown chromosome: ") + chrom);
-    const std::vector<uint32_t> &B = t->b[k], &E = t->e[k];
-    const std::vector<float> &V = t->v[k];
-    int64_t n = 0;
-    bool sorted = true;
-    uint32_t prev_end = 0;
-    for (size_t i = 0; i < B.size(); i++) {
-        if (threshold > 0.f && !(V[i] >= threshold)) continue;    // (threshold <= 0: every interval, as pmx_bigwig_fetch)
-        if (n && B[i] < prev_end) sorted = false;
-        prev_end = E[i];
-        if (begin) {
-            if (n >= cap) break;
-            begin[n] = B[i];
-            end[n] = E[i];
-            if (value) value[n] = V[i];
-        }
-        n++;
-    }
-    t->sorted = sorted;
-    return n;
+        return t;
+    });
 }
 
 }  // extern "C"

@@ -18,19 +18,16 @@ Both readers report the records' true lengths as ``chromsizes`` (not extents) an
 """
 from __future__ import annotations
 
-import ctypes
 import gzip
 import os
-from typing import Dict, Iterator, Tuple
+from typing import Dict
 
 import numpy as np
 
-from .bam import NativeReader, PmxIOError, _raise, load_io_library  # noqa: F401  (PmxIOError re-exported)
-from .bam_device import load_ingest_library
 from .bigwig_device import DeviceBigWigReader
-from .bigwig_device import _raise as _raise_device
+from .native import (HostTrackReader, PmxIOError, existing_path, load_ingest_library,  # noqa: F401  (PmxIOError re-exported)
+                     load_io_library)
 
-PMX_IO_ERR_NOTFOUND = -4
 _SUFFIXES = (".fa", ".fasta", ".fna", ".fas")
 _COMPRESSED = (".gz", ".bgz")
 
@@ -100,60 +97,14 @@ def _check_k(k) -> int:
     return k
 
 
-class KmerTrackReader(NativeReader):
-    _CLOSE = "pmx_kmer_close"
+class KmerTrackReader(HostTrackReader):
     chromsizes_are_extents = False
-    kind = "kmer"
 
     def __init__(self, path, k: int, threads: int = 0):
-        path_str = os.fspath(path)
-        if not os.path.exists(path_str):
-            raise IOError("input file '{0}' dose not exist.".format(path_str))
+        self.path = existing_path(path)
         self.k = _check_k(k)
         self._L = load_io_library()
-        self.path = path_str
-        h = ctypes.c_void_p()
-        rc = self._L.pmx_kmer_open(path_str.encode(), self.k, int(threads), ctypes.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
-        n = self._L.pmx_kmer_nchrom(h)
-        self.chromsizes: Dict[str, int] = {
-            self._L.pmx_kmer_chrom_name(h, i).decode(): int(self._L.pmx_kmer_chrom_len(h, i)) for i in range(n)}
-
-    @property
-    def sorted(self) -> bool:
-        return bool(self._L.pmx_kmer_sorted(self._h))
-
-    def fetch_arrays(self, valfilter: float, chrom: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """(begin, end, value) arrays of the chromosome's unique runs (value 1.0; none when valfilter > 1)."""
-        if self.closed:
-            raise ValueError("I/O operation on closed track reader")
-        if chrom not in self.chromsizes:
-            raise KeyError(chrom)
-        name = chrom.encode()
-        n = self._L.pmx_kmer_fetch(self._h, name, float(valfilter), 0, None, None, None)
-        if n == PMX_IO_ERR_NOTFOUND:
-            raise KeyError(chrom)
-        if n < 0:
-            _raise(n)
-        begin = np.empty(n, dtype=np.uint32)
-        end = np.empty(n, dtype=np.uint32)
-        value = np.empty(n, dtype=np.float32)
-        if n:
-            m = self._L.pmx_kmer_fetch(self._h, name, float(valfilter), n, begin.ctypes.data, end.ctypes.data,
-                                       value.ctypes.data)
-            if m < 0:
-                _raise(m)
-            assert m == n
-        return begin, end, value
-
-    def fetch(self, valfilter: float, chrom: str) -> Iterator[Tuple[int, int, float]]:
-        begin, end, value = self.fetch_arrays(valfilter, chrom)
-        return iter(zip(begin.tolist(), end.tolist(), value.tolist()))
-
-    def disable_progress_bar(self) -> None:
-        pass
+        self._attach(self._open_handle("pmx_kmer_open", self.path.encode(), self.k, int(threads)))
 
 
 class DeviceKmerTrackReader(DeviceBigWigReader):
@@ -164,29 +115,11 @@ class DeviceKmerTrackReader(DeviceBigWigReader):
     chromsizes_are_extents = False
 
     def __init__(self, path, k: int, device: int = 0, budget_bytes: int = 0, hash_bits: int = 64, threads: int = 0):
-        path_str = os.fspath(path)
-        if not os.path.exists(path_str):
-            raise IOError("input file '{0}' dose not exist.".format(path_str))
+        self.path = existing_path(path)
         self.k = _check_k(k)
         self._L = load_ingest_library()
-        self.path = path_str
-        h = ctypes.c_void_p()
-        rc = self._L.pmx_dkm_open(path_str.encode(), self.k, int(device), int(threads), int(budget_bytes), int(hash_bits),
-                                  ctypes.byref(h))
-        if rc:
-            _raise_device(rc)
-        self._h = h
-        n = self._L.pmx_dbw_nchrom(h)
-        self.chromsizes: Dict[str, int] = {self._L.pmx_dbw_chrom_name(h, i).decode(): int(self._L.pmx_dbw_chrom_len(h, i))
-                                           for i in range(n)}
-
-    @property
-    def kind(self) -> str:
-        return ("bigwig", "bigbed", "kmer")[self._L.pmx_dbw_kind(self._h)]
-
-    @property
-    def sorted(self) -> bool:
-        return bool(self._L.pmx_dbw_sorted(self._h))
+        self._attach(self._open_handle("pmx_dkm_open", self.path.encode(), self.k, int(device), int(threads),
+                                       int(budget_bytes), int(hash_bits)))
 
 
 def open_kmer_track(path, k, device_ingest: bool, device: int = 0):

@@ -11,15 +11,15 @@ counters; only the first-occurrence keys differ (byte offsets of lines in the te
 """
 from __future__ import annotations
 
-import ctypes
 import os
 import zlib
 from typing import Iterator, Tuple
 
 import numpy as np
 
-from .bam import PMX_BAM_DEFAULT_EXCLUDE, NativeReader, PmxIOError, _raise, feed_bam, load_io_library
-from .bam_device import DeviceBamReader, _raise as _raise_device
+from .bam import feed_bam
+from .bam_device import DeviceBamReader
+from .native import PMX_BAM_DEFAULT_EXCLUDE, AlignmentReader, PmxIOError, load_ingest_library, load_io_library
 
 _PROBE = 65536
 
@@ -65,72 +65,32 @@ def is_sam(path) -> bool:
     return detect_format(path) != "bam"
 
 
-class SamReader(NativeReader):
+class SamReader(AlignmentReader):
     """A SAM file (plain or BGZF) as batches of filtered read arrays, like ``pymasc_amd.bam.BamReader``; no index."""
-    _CLOSE = "pmx_sam_close"
+    _P = "pmx_sam"
+    _WHAT = "SAM reader"
+    _COUNTERS = ("records", "kept", "bytes_out", "bytes_in", "members")
 
     def __init__(self, path, threads: int = 0, header_only: bool = False):
         """``header_only``: read the header and no record (pmx_sam_open_header) -- ``references``, ``lengths`` and
         ``header_text`` only; a plain file is read to its first record line, a BGZF one inflated until it."""
         self._L = load_io_library()
         self.path = os.fspath(path)
-        h = ctypes.c_void_p()
         if header_only:
-            rc = self._L.pmx_sam_open_header(self.path.encode(), ctypes.byref(h))
+            self._h = self._open_handle("pmx_sam_open_header", self.path.encode())
         else:
-            rc = self._L.pmx_sam_open(self.path.encode(), int(threads), ctypes.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
-        n = self._L.pmx_sam_nref(h)
-        self.references: Tuple[str, ...] = tuple(self._L.pmx_sam_ref_name(h, i).decode() for i in range(n))
-        self.lengths: Tuple[int, ...] = tuple(int(self._L.pmx_sam_ref_len(h, i)) for i in range(n))
+            self._h = self._open_handle("pmx_sam_open", self.path.encode(), int(threads))
+        self._load_references()
 
     def has_index(self) -> bool:
         return False
 
-    @property
-    def header_text(self) -> str:
-        ln = ctypes.c_uint32()
-        t = self._L.pmx_sam_header_text(self._h, ctypes.byref(ln))
-        return (t or b"").decode("utf-8", "replace")
-
     def counters(self) -> dict:
         """records (alignment lines), kept (last decode), bytes_out (text), bytes_in (file), members (BGZF), rewalked (0):
         the keys of ``DeviceBamReader.counters``."""
-        v = [ctypes.c_uint64() for _ in range(5)]
-        rc = self._L.pmx_sam_counters(self._h, *[ctypes.byref(x) for x in v])
-        if rc:
-            _raise(rc)
-        out = dict(zip(("records", "kept", "bytes_out", "bytes_in", "members"), (int(x.value) for x in v)))
+        out = super().counters()
         out["rewalked"] = 0
         return out
-
-    def read_length_histogram(self, mapq_criteria: int = 0):
-        """As ``BamReader.read_length_histogram``; the first-occurrence keys are byte offsets of lines in the text."""
-        from .readlen import histogram_from_library
-        if self._h is None:
-            raise ValueError("I/O operation on closed SAM reader")
-        return histogram_from_library(self._L.pmx_sam_readlen_hist, self._L.pmx_sam_readlen_counters, self._h, mapq_criteria,
-                                      _raise)
-
-    def decode(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, reference: int = -1) -> int:
-        if self._h is None:
-            raise ValueError("I/O operation on closed SAM reader")
-        n = self._L.pmx_sam_decode(self._h, int(mapq_criteria), int(flag_exclude), int(reference))
-        if n < 0:
-            _raise(n)
-        return int(n)
-
-    def _fetch(self, first: int, n: int):
-        ref = np.empty(n, dtype=np.int32)
-        pos = np.empty(n, dtype=np.int32)
-        rlen = np.empty(n, dtype=np.int32)
-        rev = np.empty(n, dtype=np.uint8)
-        rc = self._L.pmx_sam_fetch(self._h, first, n, ref.ctypes.data, pos.ctypes.data, rlen.ctypes.data, rev.ctypes.data)
-        if rc:
-            _raise(rc)
-        return ref, pos, rlen, rev.astype(bool)
 
     def feed(self, calculator, mapq_criteria: int, references=None, finish: bool = True) -> int:
         """``pymasc_amd.bam.feed_bam`` over this reader."""
@@ -152,12 +112,7 @@ class DeviceSamReader(DeviceBamReader):
     ``references`` selects records as for a BAM file without an index; ``select`` works the same way."""
 
     def __init__(self, path, device: int = 0, threads: int = 0, references=None, index=None):
-        from .bam_device import load_ingest_library
         self._L = load_ingest_library()
         self.path = os.fspath(path)
         self.indexed = False
-        h = ctypes.c_void_p()
-        rc = self._L.pmx_dsam_open(self.path.encode(), int(device), int(threads), ctypes.byref(h))
-        if rc:
-            _raise_device(rc)
-        self._attach(h, references)
+        self._attach(self._open_handle("pmx_dsam_open", self.path.encode(), int(device), int(threads)), references)

@@ -17,9 +17,9 @@ from typing import Iterator, Tuple
 
 import numpy as np
 
-from .bam import PMX_BAM_DEFAULT_EXCLUDE
-from .bam_device import DeviceBamReader, _raise, load_ingest_library
+from .bam_device import DeviceBamReader
 from .exceptions import InputUnseekable
+from .native import PMX_BAM_DEFAULT_EXCLUDE, load_ingest_library
 
 STREAM_INFO_NAMES = ("windows", "bytes_in", "max_tail", "peak_device_bytes", "window_bytes", "inflated_budget")
 
@@ -71,11 +71,7 @@ class DeviceStreamReader(DeviceBamReader):
             raise
 
     def _open(self):
-        h = ctypes.c_void_p()
-        rc = self._L.pmx_dbam_open_stream(self._fd, self._device, self._threads, self._window, ctypes.byref(h))
-        if rc:
-            _raise(rc)
-        return h
+        return self._open_handle("pmx_dbam_open_stream", self._fd, self._device, self._threads, self._window)
 
     def _close_fd(self):
         if self._own_fd and self._fd is not None:
@@ -92,14 +88,13 @@ class DeviceStreamReader(DeviceBamReader):
         v = (ctypes.c_uint64 * 6)()
         rc = self._L.pmx_dbam_stream_info(self._h, v)
         if rc:
-            _raise(rc)
+            self._raise(rc)
         return dict(zip(STREAM_INFO_NAMES, (int(x) for x in v)))
 
     def _windows(self) -> Iterator[int]:
         """Makes every window current in turn (the first pass reads the windows the open has begun; a regular file is opened
         again for a later pass, any other source raises)."""
-        if self._h is None:
-            raise ValueError("I/O operation on closed BAM reader")
+        self._check_open()
         if self._consumed:
             if not self.seekable:
                 raise InputUnseekable("'{}' cannot be read twice: it is not a regular file".format(self.path))
@@ -113,7 +108,7 @@ class DeviceStreamReader(DeviceBamReader):
         while True:
             n = self._L.pmx_dbam_stream_next(self._h)
             if n < 0:
-                _raise(n)
+                self._raise(n)
             if n == 0:
                 return
             yield int(n)
@@ -135,7 +130,7 @@ class DeviceStreamReader(DeviceBamReader):
         acc, counters = {}, dict.fromkeys(COUNTER_NAMES, 0)
         for _ in self._windows():
             h = histogram_from_library(self._L.pmx_dbam_readlen_hist, self._L.pmx_dbam_readlen_counters, self._h, mapq_criteria,
-                                       _raise)
+                                       self._raise)
             for ln, c, f in zip(h.lengths.tolist(), h.counts.tolist(), h.first.tolist()):
                 c0, f0 = acc.get(ln, (0, f))
                 acc[ln] = (c0 + c, min(f0, f))

@@ -16,6 +16,17 @@ def header_symbols(name="pymasc_amd.h"):
     return sorted(set(re.findall(r"\b(pmx_[a-z_0-9]+)\s*\(", text)))
 
 
+def _check_prototypes(table):
+    """Every entry of a reader library's table states both a restype and an argtypes list (the functions without arguments an
+    empty one)."""
+    for name, proto in table.items():
+        assert isinstance(proto, tuple) and len(proto) == 2, name
+        restype, argtypes = proto
+        assert restype is None or hasattr(restype, "from_param"), name
+        assert isinstance(argtypes, list) and all(hasattr(a, "from_param") for a in argtypes), name
+        assert (argtypes == []) == name.endswith(("_last_error", "_version")), name
+
+
 def test_library_builds_for_gfx950():
     path = build.build()
     assert os.path.exists(path)
@@ -35,7 +46,7 @@ def test_every_declared_symbol_is_exported():
 
 def test_io_library_builds_and_exports_its_header():
     """libpymasc_io.so (host readers, include/pymasc_amd_io.h): every declared symbol, nothing undeclared bound."""
-    from pymasc_amd import bam
+    from pymasc_amd import bam, native
     path = build.build_io()
     assert os.path.exists(path)
     L = bam.load_io_library()
@@ -44,6 +55,7 @@ def test_io_library_builds_and_exports_its_header():
     for s in syms:
         assert hasattr(L, s), s
     assert sorted(bam.IO_EXPORTS) == syms
+    _check_prototypes(native.IO_PROTOTYPES)
     assert L.pmx_io_version() >= 1
     text = open(os.path.join(ROOT, "include", "pymasc_amd_io.h")).read()
     consts = dict(re.findall(r"#define\s+(PMX_BAM_FLAG_[A-Z0-9]+)\s+(0x[0-9a-fA-F]+)u", text))
@@ -54,7 +66,7 @@ def test_io_library_builds_and_exports_its_header():
 def test_ingest_library_builds_and_exports_its_header(tmp_path):
     """libpymasc_ingest.so (device-side BGZF inflate + BAM decode, include/pymasc_amd_ingest.h): gfx950 code object, every
     declared symbol exported, nothing undeclared bound; without a GPU opening a file fails loudly (no host inflate in it)."""
-    from pymasc_amd import bam, bam_device
+    from pymasc_amd import bam, bam_device, native
     path = build.build_ingest()
     assert os.path.exists(path)
     assert b"gfx950" in open(path, "rb").read()
@@ -64,6 +76,7 @@ def test_ingest_library_builds_and_exports_its_header(tmp_path):
     for s in syms:
         assert hasattr(L, s), s
     assert sorted(bam_device.INGEST_EXPORTS) == syms
+    _check_prototypes(native.INGEST_PROTOTYPES)
     assert L.pmx_dbam_version() >= 1
     import torch
     if not torch.cuda.is_available():

@@ -1,4 +1,4 @@
-"""bigBed mappability tracks through the host reader (pymasc_amd.bigwig.BigWigReader, libpymasc_io.so pmx_bigwig_* with a bigBed
+"""bigBed mappability tracks through the host reader (pymasc_amd.bigwig.BigWigReader, libpymasc_io.so pmx_bigwig_open with a bigBed
 file): inputs.open_track's routing, the intervals of every input against its BED text twin read by
 TextTrackReader, the keep rule at the chromosome's end, and the error text of each corrupt case (a cyclic R-tree included, which
 must end).  The builders here are shared with tests/test_gpu_bigbed.py."""

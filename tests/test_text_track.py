@@ -1,14 +1,16 @@
-"""Text mappability tracks through the host reader (pymasc_amd.text_track.TextTrackReader, libpymasc_io.so pmx_ttrack_*): the
+"""Text mappability tracks through the host reader (pymasc_amd.text_track.TextTrackReader, libpymasc_io.so pmx_ttrack_open): the
 golden bedGraph in every compression and its BED / WIG twins give the golden BigWig's intervals; synthetic tracks agree with
 their BigWig twins; interleaved and overlapping lines, comments, spaces and CRLF; extents as chromsizes; value rounding as
 (float)strtod; the malformed cases and the line each names; and the reader inputs.open_track picks."""
 import numpy as np
 import pytest
 
-from pymasc_amd import bigwig, inputs
+from pymasc_amd import bigwig, inputs, kmer_track, native
 from pymasc_amd import text_track as T
 from pymasc_amd.bam import PmxIOError
+from . import bigbed_writers as BB
 from . import io_writers as W
+from . import kmer_cases as K
 from . import text_track_cases as C
 
 
@@ -160,3 +162,33 @@ def test_open_track_picks_the_reader(tmp_path):
     with pytest.raises(PmxIOError, match="magic"):
         inputs.open_track(zero, False)
     assert T.is_bigwig(zero) and T.is_bigwig(renamed) and not T.is_bigwig(v["plain"])
+
+
+def test_every_kind_of_host_track_through_the_one_base_class(tmp_path):
+    """A BigWig, a bigBed, a bedGraph and a genome FASTA are one pmx_track behind ``native.HostTrackReader``: ``kind``,
+    ``sorted`` before any fetch, KeyError for an unknown chromosome, ``fetch`` as the zip of ``fetch_arrays``, ValueError after
+    ``close``."""
+    bb = tmp_path / "twin.bb"
+    BB.write_bigbed(str(bb), {"chr1": 1000, "chr2": 500}, {"chr1": ([10, 30], [20, 45], b"r\t0\t+"), "chr2": ([0], [7], b"r\t0\t-")})
+    fasta, _recs = K.write_cases(str(tmp_path))[0]
+    opened = [(bigwig.BigWigReader(C.BIGWIG), "bigwig"), (bigwig.BigWigReader(bb), "bigbed"),
+              (T.TextTrackReader(C.BEDGRAPH), "bigwig"), (kmer_track.KmerTrackReader(fasta, 36), "kmer")]
+    for r, kind in opened:
+        assert isinstance(r, native.HostTrackReader) and type(r).fetch_arrays is native.HostTrackReader.fetch_arrays
+        assert r.kind == kind
+        assert r.sorted
+        with pytest.raises(KeyError):
+            r.fetch_arrays(1.0, "no-such-chromosome")
+        with pytest.raises(KeyError):
+            r.fetch(1.0, "no-such-chromosome")
+        for chrom in r.chromsizes:
+            b, e, v = r.fetch_arrays(0.5, chrom)
+            assert list(r.fetch(0.5, chrom)) == list(zip(b.tolist(), e.tolist(), v.tolist()))
+        assert sum(len(r.fetch_arrays(0.0, c)[0]) for c in r.chromsizes) > 0
+        r.disable_progress_bar()
+        r.close()
+        assert r.closed and r.kind == kind
+        with pytest.raises(ValueError, match="closed"):
+            r.fetch_arrays(1.0, next(iter(r.chromsizes)))
+        with pytest.raises(ValueError, match="closed"):
+            r.fetch(1.0, next(iter(r.chromsizes)))
