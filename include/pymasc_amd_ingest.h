@@ -141,6 +141,27 @@ int64_t pmx_dbam_readlen_hist(pmx_dbam *b, uint32_t mapq_min, int64_t cap, int32
 /* c = {nreads, nunmapped, ncounted, npaired, nread2, nnoqlen} of the last pmx_dbam_readlen_hist */
 int pmx_dbam_readlen_counters(const pmx_dbam *b, uint64_t c[6]);
 
+/* Library complexity (version >= 9): how often each key (ref_id, pos1, read_len, reverse) occurs among the
+ * records that pass mapq_min / flag_exclude (the filter of pmx_dbam_decode; ENCODE's NRF / PBC1 / PBC2 keep flagged duplicates:
+ * pass PMX_BAM_DEFAULT_EXCLUDE & ~PMX_BAM_FLAG_DUPLICATE).  The four fields are compared in full.  One more walk + filter over
+ * the record chain (or the SAM / BED parse table) already in HBM, with arrays of its own: the arrays of the last pmx_dbam_decode,
+ * its counters and pmx_dbam_runs are left as they are, and the order of the calls does not matter.  Equal keys are brought
+ * together by the stable LSD radix sort of pmx_dbed_open over the digits of the key (a digit that is the same in every key is
+ * skipped), so the input need not be sorted and a pile of reads on one position costs what any other reads cost.
+ * per_ref[4 * r + {0, 1, 2, 3}] = {reads, distinct keys, keys seen once, keys seen twice} of reference r (a key never spans two
+ * references: the whole is their sum); hist[k] = keys seen exactly k times for 1 <= k < PMX_COMPLEXITY_BINS - 1, the last bin =
+ * keys seen at least that often, hist[0] = the largest multiplicity.  use_ref: nref bytes, 0 = the reference is left out of every
+ * output; NULL = every reference.  Device memory: at most 40 bytes per kept read, transient (freed before the call returns).
+ * A stream handle: a call counts the current window, once (a second call for the same window reports zeros), except that the
+ * kept records of the window's last (ref_id, pos1) are held back in device memory (13 bytes each, part of pmx_dbam_stream_info's
+ * peak) and counted with the next window; a call after pmx_dbam_stream_next has returned 0 counts what is still held back, and
+ * the calls after it report zeros: the caller adds the calls up.  A stream must be in (ref_id, pos1) order: a kept record below
+ * its predecessor is PMX_DBAM_ERR_INVALID, "stream is not sorted by position".  Malformed records: the codes and messages of
+ * pmx_dbam_decode; a NULL output: PMX_DBAM_ERR_INVALID; 2^32 - 1 kept reads or more: PMX_DBAM_ERR_OPEN. */
+#define PMX_COMPLEXITY_BINS 32
+int pmx_dbam_complexity(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, const uint8_t *use_ref, uint64_t *per_ref,
+                        uint64_t hist[PMX_COMPLEXITY_BINS]);
+
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
  * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong.  An indexed
  * handle: bytes_out is the length of its stream (header + selected records), bytes_in and members count only the members

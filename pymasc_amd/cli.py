@@ -189,6 +189,10 @@ def get_parser() -> argparse.ArgumentParser:
     out.add_argument("-n", "--name", nargs="*", default=[],
                      help="base names of the outputs, paired with the files in order (default: each file's stem)")
     out.add_argument("-o", "--outdir", default=".", type=Path, help="directory the tables are written to (default .)")
+    out.add_argument("--complexity", action="store_true",
+                     help="also write <name>_complexity.tab for every file: the library complexity NRF, PBC1 and PBC2 (ENCODE) of "
+                          "the reads at -q on the chosen chromosomes, flagged duplicates kept, counted per "
+                          "(chromosome, position, read length, strand), with per-chromosome counts and the multiplicity histogram")
     return parser
 
 
@@ -304,6 +308,8 @@ def _run(args, device, rank: int) -> int:
     from . import pipeline
     from .mappability import BWIOError, JSONIOError
     extra = {} if args.chrom_sizes is None else {"chrom_sizes": str(args.chrom_sizes)}   # (BED read files only)
+    if args.complexity:
+        extra["complexity"] = True
     try:
         results = pipeline.run_files(
             [str(p) for p in args.reads], str(args.outdir), args.max_shift, read_len=args.read_length,

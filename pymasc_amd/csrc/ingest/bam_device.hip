@@ -1773,7 +1773,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 8; }
+int pmx_dbam_version(void) { return 9; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -2537,3 +2537,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "text_track_device.inc"
 #include "bed_reads_device.inc"
 #include "kmer_track_device.inc"
+#include "complexity_device.inc"

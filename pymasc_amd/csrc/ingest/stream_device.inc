@@ -47,6 +47,12 @@ struct StreamState {
     u64 sam_hdr_lines = 0, lines_before = 0;
     // stream_info
     u64 windows = 0, bytes_in = 0, max_tail = 0, peak = 0;
+    // pmx_dbam_complexity (complexity_device.inc): the kept records of the last counted window's last (ref_id, pos1), counted with
+    // the next window; the window counted last; whether pmx_dbam_stream_next has reported the end
+    int *cx_ref = nullptr, *cx_pos = nullptr, *cx_len = nullptr;
+    u8 *cx_rev = nullptr;
+    u64 cx_n = 0, cx_window = ~0ull;
+    bool cx_end = false;
 };
 
 // len bytes (or until the end of the stream) into hb[x] behind `have` bytes already there
@@ -90,6 +96,7 @@ u64 stream_held(const pmx_dbam &b)
     h += b.out_cap * 13;
     if (b.d_rl) h += 8 * (2u * RL_SHORT + RL_NCNT + 1u);
     if (b.sam) h += b.sam_lines * 24 + b.sam_nb_cap * 12 + 16;
+    h += s->cx_n * 13;
     return h;
 }
 void stream_note(pmx_dbam &b) { b.st->peak = std::max(b.st->peak, stream_held(b)); }
@@ -389,6 +396,8 @@ static void stream_free(pmx_dbam *b)
     }
     if (s->d_mem) (void)hipFree(s->d_mem);
     if (s->d_st) (void)hipFree(s->d_st);
+    for (void *p : {(void *)s->cx_ref, (void *)s->cx_pos, (void *)s->cx_len, (void *)s->cx_rev})
+        if (p) (void)hipFree(p);
     b->d_out = nullptr;   // (it pointed into d_win)
     delete s;
     b->st = nullptr;
@@ -455,9 +464,13 @@ int64_t pmx_dbam_stream_next(pmx_dbam *b)
         HIPOK(hipSetDevice(b->device));
         if (b->st->primed) {
             b->st->primed = false;
-            return b->N > b->data_beg ? (int64_t)(b->N - b->data_beg) : 0;
+            const int64_t r0 = b->N > b->data_beg ? (int64_t)(b->N - b->data_beg) : 0;
+            if (r0 == 0) b->st->cx_end = true;
+            return r0;
         }
-        return stream_advance(*b);
+        const int64_t r = stream_advance(*b);
+        if (r == 0) b->st->cx_end = true;
+        return r;
     } catch (const std::exception &e) {
         return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_stream_next: ") + e.what());
     }

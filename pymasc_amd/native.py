@@ -19,6 +19,7 @@ PMX_BAM_FLAG_REVERSE = 0x10
 PMX_BAM_FLAG_READ2 = 0x80
 PMX_BAM_FLAG_DUPLICATE = 0x400
 PMX_BAM_DEFAULT_EXCLUDE = PMX_BAM_FLAG_READ2 | PMX_BAM_FLAG_UNMAPPED | PMX_BAM_FLAG_DUPLICATE
+PMX_COMPLEXITY_BINS = 32        # (include/pymasc_amd_ingest.h)
 PMX_IO_ERR_NOTFOUND = -4        # (PMX_DBAM_ERR_NOTFOUND has the same value)
 TRACK_KINDS = ("bigwig", "bigbed", "kmer")      # pmx_track_kind / pmx_dbw_kind
 
@@ -114,6 +115,7 @@ INGEST_PROTOTYPES = {
     **_decode_protos("pmx_dbam"),
     "pmx_dbam_device_arrays": (_int, [_vp] + [_out] * 4),
     "pmx_dbam_runs": (_i64, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "pmx_dbam_complexity": (_int, [_vp, _u32, _u32, _vp, _vp, _vp]),
     "pmx_dbam_counters": (_int, [_vp] + [_pu64] * 6),
     "pmx_dbam_timings": (_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "pmx_dbam_inflated": (_int, [_vp, _u64, _u64, _vp]),
@@ -251,6 +253,14 @@ class AlignmentReader(NativeReader):
         self._check_open()
         return histogram_from_library(self._fn("readlen_hist"), self._fn("readlen_counters"), self._h, mapq_criteria,
                                       self._raise)
+
+    def library_complexity(self, mapq_criteria: int = 0, references=None):
+        """NRF / PBC1 / PBC2 of the reads at ``mapq_criteria`` over ``references`` (None: all the reader has selected), flagged
+        duplicates kept: a ``pymasc_amd.complexity.LibraryComplexity`` (``complexity.from_reader``).  A device reader counts on
+        the GPU with arrays of its own: the arrays of the last ``decode`` stay as they are."""
+        from .complexity import from_reader
+        self._check_open()
+        return from_reader(self, mapq_criteria, references)
 
     def decode(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, reference: int = -1) -> int:
         """Runs the record walk + filter; returns the number of kept records (they stay with the handle, for ``_fetch``)."""

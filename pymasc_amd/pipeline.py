@@ -35,7 +35,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
         device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
         library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
-        chi2_pval: float = 0.05, chrom_sizes=None):
+        chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -52,7 +52,12 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     --chi2-pval ``chi2_pval``.  A ``library_length`` longer than ``max_shift`` or below 1, or a ``smooth_window`` below 1, is
     a ValueError before any GPU work (PyMaSC logs a too long ``library_length`` and ignores it).
     ``bam_path`` may also be a BED read file (tagAlign, ``pymasc_amd.bed_reads``); its references are ``chrom_sizes`` (a path or
-    an ordered ``{name: length}``), without which it is a ValueError; other inputs keep their header's."""
+    an ordered ``{name: length}``), without which it is a ValueError; other inputs keep their header's.
+    ``complexity``: rank 0 also writes ``<stem>_complexity.tab`` (pymasc_amd.complexity: NRF, PBC1, PBC2 of the reads at
+    ``mapq_criteria`` on the chosen chromosomes, flagged duplicates kept).  One rank: counted on the reader
+    the run feeds from, so the file is inflated once (a stream is counted window by window while it is fed).  Several ranks:
+    rank 0 alone counts the chosen chromosomes on one more read of the file through ``inputs.open_alignments``, after the
+    run; no collective is added.  A run that raises (unsorted reads) writes no table."""
     if references is not None and chromfilter is not None:
         raise ValueError("give references or chromfilter, not both")
     _check_bed_sizes(bam_path, chrom_sizes)
@@ -73,7 +78,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
                                                context, device_ingest, world, chrom_sizes)
         return _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path,
                     skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, rank,
-                    chromfilter, stat_opts, chrom_sizes)
+                    chromfilter, stat_opts, chrom_sizes, complexity)
     finally:
         if bam is not None:
             bam.close()
@@ -109,7 +114,7 @@ def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, grou
 
 def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path, skip_ncc,
          references, device, save_mappability_stats, group, context, device_ingest, bam, rank, chromfilter=None,
-         stat_opts=None, chrom_sizes=None):
+         stat_opts=None, chrom_sizes=None, complexity=False):
     # The mappable-length cache (handler/mappability.py:239-309): loaded when valid; otherwise computed ONCE, on rank 0,
     # written atomically, and broadcast -- the other ranks neither recompute it per chromosome nor read a file that is
     # being rewritten.
@@ -138,19 +143,63 @@ def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path,
         finally:
             if bw is not track:
                 bw.close()
+    counted = _ComplexityCount(mapq_criteria) if complexity else None
     try:
         known = None if mappability_path is None else on_rank0(mappable_lengths, group, "mappability statistics")
         result = run_sharded(bam_path, max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
                              references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
                              group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter,
-                             chrom_sizes=chrom_sizes, track=track)
+                             chrom_sizes=chrom_sizes, track=track,
+                             reader_hook=counted.hook if counted is not None and rank_and_world(group)[2] == 1 else None)
     finally:
         if track is not None:
             track.close()
     written: List[Path] = []
     if rank == 0:
         written = _write_outputs(outdir, Path(bam_path).stem, result, read_len, stat_opts)
+        if counted is not None:
+            written.append(counted.write(outdir, Path(bam_path).stem, bam_path, references, chromfilter,
+                                         rank_and_world(group)[2], device_ingest, context, device, chrom_sizes))
     return result, written
+
+
+class _ComplexityCount:
+    """The library complexity of one file's run (pymasc_amd.complexity).  ``hook`` is run_sharded's ``reader_hook`` on one
+    rank: the count is taken on the reader that feeds the run (a stream: armed before the feed, summed window by window).
+    ``write`` writes the table; without a count so far (several ranks) it first counts the chosen chromosomes on one more
+    read of the file, through the reader ``inputs.open_alignments`` gives a run of that many ranks."""
+
+    def __init__(self, mapq_criteria: int):
+        self.mapq_criteria = int(mapq_criteria)
+        self.value = None
+
+    def hook(self, reader, names):
+        from . import complexity
+        if hasattr(reader, "arm_complexity"):
+            acc = reader.arm_complexity(self.mapq_criteria, names)
+
+            def after():
+                reader.disarm_complexity()
+                self.value = acc.result()
+            return after
+
+        def after():
+            self.value = complexity.from_reader(reader, self.mapq_criteria, names)
+        return after
+
+    def write(self, outdir, basename: str, path, references, chromfilter, world, device_ingest, context, device,
+              chrom_sizes) -> Path:
+        from . import complexity
+        if self.value is None:
+            ingest = bool(default_device_ingest(world, context) if device_ingest is None else device_ingest)
+            dev = context.device if (context is not None and ingest) else (device or 0)
+            with open_alignments(path, ingest, dev, chrom_sizes=chrom_sizes) as r:
+                if chromfilter is not None:
+                    names = filter_references(r.references, chromfilter)
+                else:
+                    names = [n for n in r.references if references is None or n in set(references)]
+                self.value = complexity.from_reader(r, self.mapq_criteria, names)
+        return complexity.write_complexity(Path(outdir) / basename, basename, self.value)
 
 
 def _write_outputs(outdir, basename: str, result, read_len, stat_opts) -> List[Path]:
@@ -181,9 +230,11 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
               device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
               library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
-              chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None) -> List[FileResult]:
+              chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None,
+              complexity: bool = False) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
-    file, in input order.  Every keyword means what it means for ``run``.
+    file, in input order.  Every keyword means what it means for ``run`` (``complexity``: ``<name>_complexity.tab`` for every
+    file that runs, counted as ``run`` counts it; a file that is skipped gets no table).
 
     ``names``: PyMaSC's -n, paired with the files by position (a missing or None name: ``Path(file).stem``, so that a file
     without a name gets exactly what ``run`` writes for it); a name ``N`` gives ``N_cc.tab`` ... ``N_stats.tab``, whole even
@@ -232,7 +283,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
         device = int(os.environ.get("LOCAL_RANK", "0")) if on else 0
     _collective_device_setup(device, group)
     if rank == 0:
-        _warn_existing(outdir, bases, mappability_path is not None, skip_ncc, stats)
+        _warn_existing(outdir, bases, mappability_path is not None, skip_ncc, stats, complexity)
         if chrom_sizes is not None and not all(_is_bed(p) for p in paths):
             logger.info("The chromosome sizes are used for BED read files only: BAM and SAM files keep their header's lengths.")
     ingest = bool(default_device_ingest(world, context) if device_ingest is None else device_ingest)
@@ -282,11 +333,13 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
             logger.info("Process {}".format(paths[i]))
             bam = None
             bam = kept.pop(i, None)
+            counted = _ComplexityCount(mapq_criteria) if complexity else None
             try:
                 result = run_sharded(paths[i], max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
                                      references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
                                      group=group, context=ctx, device_ingest=ingest, bam=bam, chromfilter=chromfilter,
-                                     track=track, chrom_sizes=chrom_sizes)
+                                     track=track, chrom_sizes=chrom_sizes,
+                                     reader_hook=counted.hook if counted is not None and world == 1 else None)
             except Exception as e:
                 skip = _unsorted_on_every_rank(e, world)
                 if skip is None:
@@ -297,8 +350,13 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
             finally:
                 if bam is not None:
                     bam.close()
-            written = on_rank0(lambda: _write_outputs(outdir, bases[i], result, read_len, stat_opts), group,
-                               "writing the outputs of '{}'".format(paths[i]))
+            def write_all():
+                out = _write_outputs(outdir, bases[i], result, read_len, stat_opts)
+                if counted is not None:
+                    out.append(counted.write(outdir, bases[i], paths[i], references, chromfilter, world, ingest, ctx, device,
+                                             chrom_sizes))
+                return out
+            written = on_rank0(write_all, group, "writing the outputs of '{}'".format(paths[i]))
             results[i] = (result, list(written) if rank == 0 else [])
     finally:
         for r in kept.values():
@@ -331,10 +389,10 @@ def _basenames(paths, names) -> List[str]:
     return out
 
 
-def _warn_existing(outdir, bases, has_track, skip_ncc, stats):
+def _warn_existing(outdir, bases, has_track, skip_ncc, stats, complexity=False):
     """prepare_output's warning (pymasc.py:178-182) for every output about to be replaced."""
     suffixes = [s for s, on in (("_cc.tab", not (has_track and skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
-                                ("_stats.tab", stats)) if on]
+                                ("_stats.tab", stats), ("_complexity.tab", complexity)) if on]
     for b in bases:
         for suffix in suffixes:
             path = Path(outdir) / (b + suffix)

@@ -213,7 +213,7 @@ def reconcile_chromosome_sizes(bam_sizes: Dict[str, int], external_sizes: Dict[s
 def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, bigwig_path=None,
                 references: Sequence[str] = None, skip_ncc: bool = False, device: int = None, context=None,
                 chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None, chromfilter=None,
-                track=None, chrom_sizes=None):
+                track=None, chrom_sizes=None, reader_hook=None):
     """BAM (+ BigWig) -> genome-wide result on every rank; chromosomes LPT-sharded over the ranks by length.
 
     Launch: one process per GPU under ``torch.distributed`` (torchrun, or pymasc_amd.launch.spawn_ranks), the process
@@ -243,7 +243,10 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     ``chrom_sizes``: the references of a BED read file (``pymasc_amd.bed_reads``; a path or an ordered ``{name: length}``),
     which is read whole like SAM text -- by every rank of several through the host reader -- and is a ValueError without them.
     With a ``context`` given, the calculator still gives its bit-vectors back to the context's pool and frees its result arena
-    before this returns (``CCHipCalculator.close`` never closes a context it does not own)."""
+    before this returns (``CCHipCalculator.close`` never closes a context it does not own).
+    ``reader_hook``: ``reader_hook(reader, names)`` is called with the open alignment reader and this rank's chromosomes just
+    before they are fed; what it returns, when not None, is called without arguments once the feed has succeeded, while the
+    reader is still open (pipeline.run counts the library complexity there: the file is inflated once)."""
     from .calculator import CCHipCalculator
     from .chromfilter import filter_references
     from .inputs import default_device_ingest, find_index, open_alignments, open_track, track_on_device
@@ -308,8 +311,11 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
             calc = CCHipCalculator(max_shift, read_len, mine, [lengths[n] for n in mine], bwfeeder=bw,
                                    skip_ncc=skip_ncc, chrom2mappable_len=chrom2mappable_len, **kw)
             try:
+                after_feed = reader_hook(reader, mine) if reader_hook is not None else None
                 reader.feed(calc, mapq_criteria, references=mine)
                 local = {c: calc.get_result(c) for c in mine}
+                if after_feed is not None:
+                    after_feed()
             finally:
                 calc.close()
     except Exception as e:              # surfaced on every rank by the gather below

@@ -110,8 +110,26 @@ class DeviceStreamReader(DeviceBamReader):
             if n < 0:
                 self._raise(n)
             if n == 0:
+                if self._complexity is not None:
+                    self._complexity.count(self)    # (what the library held back of the last window)
                 return
             yield int(n)
+            if self._complexity is not None:        # the caller is done with the window: its arrays stay as they are
+                self._complexity.count(self)
+
+    _complexity = None
+
+    def arm_complexity(self, mapq_criteria: int = 0, references=None):
+        """From now on every window a pass makes current (``feed``, ``batches``) is also counted for the library complexity
+        (``pmx_dbam_complexity``: the window's last position waits for the next window); returns the
+        ``pymasc_amd.complexity.WindowedCount`` whose ``result()`` is the whole stream's once the pass has ended.  A stream
+        that cannot be read twice is counted this way, in the pass that feeds it."""
+        from .complexity import WindowedCount
+        self._complexity = WindowedCount(self, mapq_criteria, references)
+        return self._complexity
+
+    def disarm_complexity(self) -> None:
+        self._complexity = None
 
     def _keep_mask(self):
         if len(self._selected) == len(self.references):
