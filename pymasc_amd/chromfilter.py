@@ -55,3 +55,11 @@ def filter_references(references: Sequence[str], chromfilter: Optional[ChromFilt
     if not out:
         raise NoTargetChromosomesError("the chromosome filter {!r} leaves no reference of the BAM file".format(list(chromfilter)))
     return out
+
+
+def kept_references(header: Sequence[str], references: Optional[Sequence[str]], chromfilter: Optional[ChromFilter]) -> List[str]:
+    """The names of a reader's ``header`` that a run keeps, in header order: what ``chromfilter`` leaves when one is given, else
+    the ones named in ``references`` (None: all of them)."""
+    if chromfilter is not None:
+        return filter_references(header, chromfilter)
+    return [n for n in header if references is None or n in set(references)]

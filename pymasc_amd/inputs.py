@@ -57,11 +57,25 @@ def whole_file_footprint(path) -> int:
     return fsize + inflated + 13 * (inflated // 36)
 
 
+def reader_device(context, device, device_ingest: bool = True) -> int:
+    """The GPU of a run's device readers: the one of ``context`` when the run has one and ingests on the device (a genome
+    FASTA's track goes there whatever the ingest: its callers leave ``device_ingest`` True), else ``device`` (None: 0)."""
+    if context is not None and device_ingest:
+        return context.device
+    return device or 0
+
+
+def check_bed_sizes(path, chrom_sizes) -> None:
+    """A BED read file (``bed_reads.is_bed_reads``) needs ``chrom_sizes``: ValueError without them, before any work."""
+    from .bed_reads import is_bed_reads
+    if chrom_sizes is None and is_bed_reads(path):
+        raise ValueError("'{}' is a BED read file: give the chromosome sizes (chrom_sizes=, --chrom-sizes)".format(os.fspath(path)))
+
+
 def bed_sizes(path, chrom_sizes):
     """(references, lengths) of a BED read file (``bed_reads.is_bed_reads``) from ``chrom_sizes``; ValueError without them."""
     from .bed_reads import chrom_sizes_of
-    if chrom_sizes is None:
-        raise ValueError("'{}' is a BED read file: give the chromosome sizes (chrom_sizes=, --chrom-sizes)".format(os.fspath(path)))
+    check_bed_sizes(path, chrom_sizes)
     return chrom_sizes_of(chrom_sizes)
 
 

@@ -16,14 +16,16 @@ import logging
 import os
 import pickle
 from collections import namedtuple
+from dataclasses import dataclass, fields, replace
 from itertools import zip_longest
 from pathlib import Path
 from typing import List, Optional, Sequence
 
 from . import ffi, readlen, tables
-from .chromfilter import NoTargetChromosomesError, filter_references
+from .chromfilter import NoTargetChromosomesError, filter_references, kept_references
 from .exceptions import InputUnseekable, ReadUnsortedError
-from .inputs import default_device_ingest, is_stream, open_alignments, open_header, open_track, track_on_device
+from .inputs import (check_bed_sizes, default_device_ingest, is_stream, open_alignments, open_header, open_track,
+                     reader_device, track_on_device)
 from .mappability import MappabilityStats
 from .sharding import _collective_device_setup, on_rank0, rank_and_world, run_sharded
 
@@ -58,109 +60,159 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     the run feeds from, so the file is inflated once (a stream is counted window by window while it is fed).  Several ranks:
     rank 0 alone counts the chosen chromosomes on one more read of the file through ``inputs.open_alignments``, after the
     run; no collective is added.  A run that raises (unsorted reads) writes no table."""
-    if references is not None and chromfilter is not None:
-        raise ValueError("give references or chromfilter, not both")
-    _check_bed_sizes(bam_path, chrom_sizes)
-    from .stats import check_params
-    check_params(None, library_length, smooth_window, max_shift)
-    stat_opts = None
-    if stats:
-        stat_opts = dict(library_length=library_length, smooth_window=smooth_window, mask_size=mask_size,
-                         bg_avr_width=bg_avr_width, chi2_pval=chi2_pval)
-    on, rank, world = rank_and_world(group)
-    if device is None:
-        device = int(os.environ.get("LOCAL_RANK", "0")) if on else 0
-    _collective_device_setup(device, group)
-    bam = None                      # a reader opened here for the estimate and handed on: the file is inflated once per run
+    check_bed_sizes(bam_path, chrom_sizes)
+    s = _settings(locals())
+    from .kmer_track import is_fasta
+    bam = track = None              # a reader opened here for the estimate and handed on: the file is inflated once per run
     try:
-        if read_len is None:
-            read_len, bam = _estimate_read_len(bam_path, max_shift, mapq_criteria, readlen_estimator, device, group,
-                                               context, device_ingest, world, chrom_sizes)
-        return _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path,
-                    skip_ncc, references, device, save_mappability_stats, group, context, device_ingest, bam, rank,
-                    chromfilter, stat_opts, chrom_sizes, complexity)
-    finally:
-        if bam is not None:
-            bam.close()
-
-
-def _check_bed_sizes(path, chrom_sizes) -> None:
-    """A BED read file needs ``chrom_sizes``: ValueError before any work."""
-    from .bed_reads import is_bed_reads
-    if chrom_sizes is None and is_bed_reads(path):
-        raise ValueError("'{}' is a BED read file: give the chromosome sizes (chrom_sizes=, --chrom-sizes)".format(path))
-
-
-def _estimate_read_len(bam_path, max_shift, mapq_criteria, esttype, device, group, context, device_ingest, world,
-                       chrom_sizes=None):
-    """(read length, the device reader it was estimated on or None).  One rank: on the device reader that the run then
-    feeds from when the BAM file goes through the GPU, on the host reader otherwise.  Several ranks: rank 0 estimates on the
-    host reader and broadcasts the value or its error (sharding.on_rank0); every rank raises on an error, none waits."""
-    readlen._check_esttype(esttype)                     # (every rank: a wrong name fails before any collective)
-    if world == 1 and (default_device_ingest(world, context) if device_ingest is None else device_ingest):
-        bam = open_alignments(bam_path, True, device=(context.device if context is not None else device),
-                              chrom_sizes=chrom_sizes)
-        try:
-            return readlen.estimate_from_reader(bam, esttype, mapq_criteria, max_shift), bam
-        except BaseException:
-            bam.close()
-            raise
-
-    def estimate():                 # the whole file: the host reader without its index
-        with open_alignments(bam_path, False, index=False, chrom_sizes=chrom_sizes) as b:
-            return readlen.estimate_from_reader(b, esttype, mapq_criteria, max_shift)
-    return int(on_rank0(estimate, group, "read length estimation")), None
-
-
-def _run(bam_path, outdir, max_shift, read_len, mapq_criteria, mappability_path, mappability_stats_path, skip_ncc,
-         references, device, save_mappability_stats, group, context, device_ingest, bam, rank, chromfilter=None,
-         stat_opts=None, chrom_sizes=None, complexity=False):
-    # The mappable-length cache (handler/mappability.py:239-309): loaded when valid; otherwise computed ONCE, on rank 0,
-    # written atomically, and broadcast -- the other ranks neither recompute it per chromosome nor read a file that is
-    # being rewritten.
-    # A genome FASTA's track is generated once per rank (on its GPU when it has one, inputs.track_on_device) and that one
-    # reader serves the mappable lengths and the feed (DESIGN.md 7.13).
-    track = None
-    if mappability_path is not None and _is_fasta(mappability_path):
-        track = open_track(mappability_path, track_on_device(mappability_path, False, context),
-                           context.device if context is not None else device, k=read_len)
-
-    def mappable_lengths():
-        bw = track if track is not None else open_track(mappability_path, False)
-        try:
-            stats = MappabilityStats(bw, max_shift, read_len, map_path=mappability_stats_path, track_path=mappability_path,
-                                     device=device, context=context)
-            try:
-                if stats.is_called:                          # a valid cache: the autocorrelation pass is skipped
-                    return stats.chrom2mappable_len
-                if save_mappability_stats:
-                    stats.calc_mappability()
-                    stats.save_mappability_stats()
-                    return stats.chrom2mappable_len
-                return None
-            finally:
-                stats.close()
-        finally:
-            if bw is not track:
-                bw.close()
-    counted = _ComplexityCount(mapq_criteria) if complexity else None
-    try:
-        known = None if mappability_path is None else on_rank0(mappable_lengths, group, "mappability statistics")
-        result = run_sharded(bam_path, max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
-                             references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
-                             group=group, context=context, device_ingest=device_ingest, bam=bam, chromfilter=chromfilter,
-                             chrom_sizes=chrom_sizes, track=track,
-                             reader_hook=counted.hook if counted is not None and rank_and_world(group)[2] == 1 else None)
+        if read_len is None:        # (one rank: on_rank0 is the call itself, and the reader comes back with the length)
+            read_len, bam = on_rank0(lambda: _estimate(s, bam_path, True), group, "read length estimation")
+        # A genome FASTA's track is generated once per rank (on its GPU when it has one, inputs.track_on_device) and that one
+        # reader serves the mappable lengths and the feed (DESIGN.md 7.13); any other track is opened where it is read.
+        if mappability_path is not None and is_fasta(mappability_path):
+            track = open_track(mappability_path, track_on_device(mappability_path, False, context),
+                               reader_device(context, s.device), k=read_len)
+        known = _mappable_lengths(s, read_len, track, False)
+        result, counted = _run_file(s, bam_path, read_len, known, bam, track)
     finally:
         if track is not None:
             track.close()
-    written: List[Path] = []
-    if rank == 0:
-        written = _write_outputs(outdir, Path(bam_path).stem, result, read_len, stat_opts)
-        if counted is not None:
-            written.append(counted.write(outdir, Path(bam_path).stem, bam_path, references, chromfilter,
-                                         rank_and_world(group)[2], device_ingest, context, device, chrom_sizes))
+        if bam is not None:
+            bam.close()
+    written = _write_file(s, bam_path, Path(bam_path).stem, result, read_len, counted) if s.rank == 0 else []
     return result, written
+
+
+_STAT_OPTS = ("library_length", "smooth_window", "mask_size", "bg_avr_width", "chi2_pval")
+
+
+@dataclass(frozen=True)
+class _Settings:
+    """What is constant over one call of run / run_files: its keywords under their own names, checked, with the defaults
+    resolved -- ``device`` (this rank's GPU), ``ingest`` (``device_ingest``), ``stat_opts`` (the keywords
+    of stats.genome_wide_stats with ``stats``, else None), ``rank`` and ``world``."""
+    outdir: object
+    max_shift: int
+    mapq_criteria: int
+    mappability_path: object
+    mappability_stats_path: object
+    skip_ncc: bool
+    references: Optional[Sequence[str]]
+    chromfilter: object
+    group: object
+    context: object
+    readlen_estimator: str
+    chrom_sizes: object
+    complexity: bool
+    save_mappability_stats: bool
+    device: int
+    ingest: bool
+    stat_opts: Optional[dict]
+    rank: int
+    world: int
+
+    @property
+    def estimate_gpu(self) -> Optional[int]:
+        """The GPU of the device reader that one rank estimates the read length on and then feeds the run from; None when the
+        host reader estimates (no device ingest, or several ranks: rank 0 estimates for all)."""
+        return reader_device(self.context, self.device) if self.world == 1 and self.ingest else None
+
+
+def _settings(kw: dict) -> _Settings:
+    """The settings of one call from the keywords of run / run_files (their ``locals()``).  Bad options raise ValueError
+    before any file, context or collective is touched."""
+    if kw["references"] is not None and kw["chromfilter"] is not None:
+        raise ValueError("give references or chromfilter, not both")
+    from .stats import check_params
+    check_params(None, kw["library_length"], kw["smooth_window"], kw["max_shift"])
+    if kw["read_len"] is None:
+        readlen._check_esttype(kw["readlen_estimator"])
+    on, rank, world = rank_and_world(kw["group"])
+    device = kw["device"]
+    if device is None:
+        device = int(os.environ.get("LOCAL_RANK", "0")) if on else 0
+    _collective_device_setup(device, kw["group"])
+    ingest = default_device_ingest(world, kw["context"]) if kw["device_ingest"] is None else kw["device_ingest"]
+    given = {f.name: kw[f.name] for f in fields(_Settings) if f.name in kw}
+    given.update(device=device, ingest=bool(ingest), rank=rank, world=world,
+                 stat_opts={k: kw[k] for k in _STAT_OPTS} if kw["stats"] else None)
+    return _Settings(**given)
+
+
+def _estimate(s: _Settings, path, keep: bool):
+    """(read length of ``path``, the reader it was estimated on or None): on the device reader on ``s.estimate_gpu``, handed
+    back open with ``keep`` to feed the run too, else on the host reader over the whole file, without its index.  A reader
+    that is not handed back is closed, after an error too."""
+    gpu = s.estimate_gpu
+    if gpu is None:
+        r = open_alignments(path, False, index=False, chrom_sizes=s.chrom_sizes)
+    else:
+        r = open_alignments(path, True, device=gpu, chrom_sizes=s.chrom_sizes)
+    back = None
+    try:
+        length = readlen.estimate_from_reader(r, s.readlen_estimator, s.mapq_criteria, s.max_shift)
+        back = r if keep and gpu is not None else None
+        return length, back
+    finally:
+        if back is None:
+            r.close()
+
+
+def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool):
+    """The mappable-length cache (handler/mappability.py:239-309) on every rank, None without a track: loaded when valid;
+    otherwise computed ONCE, on rank 0, written atomically with ``save_mappability_stats``, and broadcast -- the other ranks
+    neither recompute it per chromosome nor read a file that is being rewritten.  Not valid and not to be saved: computed all
+    the same with ``unsaved``, else None (each calculator computes its own in the fused pass).  ``track``: the track's open
+    reader, or None for rank 0 to open one on the host."""
+    if s.mappability_path is None:
+        return None
+
+    def lengths():
+        bw = track if track is not None else open_track(s.mappability_path, False)
+        try:
+            ms = MappabilityStats(bw, s.max_shift, read_len, map_path=s.mappability_stats_path,
+                                  track_path=s.mappability_path, device=s.device, context=s.context)
+            try:
+                if not ms.is_called:                        # no valid cache: the autocorrelation pass
+                    if not (s.save_mappability_stats or unsaved):
+                        return None
+                    ms.calc_mappability()
+                    if s.save_mappability_stats:
+                        ms.save_mappability_stats()
+                return ms.chrom2mappable_len
+            finally:
+                ms.close()
+        finally:
+            if bw is not track:
+                bw.close()
+    return on_rank0(lengths, s.group, "mappability statistics")
+
+
+def _run_file(s: _Settings, path, read_len: int, known, bam, track):
+    """One file sharded over the ranks: (its genome-wide result, its _ComplexityCount or None).  ``known``: the lag tables of
+    _mappable_lengths; ``bam`` / ``track``: the file's and the track's open readers, or None for run_sharded to open its own."""
+    counted = _ComplexityCount(s) if s.complexity else None
+    result = run_sharded(path, s.max_shift, read_len, s.mapq_criteria, bigwig_path=s.mappability_path,
+                         references=s.references, skip_ncc=s.skip_ncc, device=s.device, chrom2mappable_len=known,
+                         group=s.group, context=s.context, device_ingest=s.ingest, bam=bam, chromfilter=s.chromfilter,
+                         track=track, chrom_sizes=s.chrom_sizes,
+                         reader_hook=counted.hook if counted is not None and s.world == 1 else None)
+    return result, counted
+
+
+def _write_file(s: _Settings, path, basename: str, result, read_len: int, counted) -> List[Path]:
+    """Rank 0's part after _run_file: ``outdir/<basename>_{cc,mscc,nreads}.tab``, with ``stat_opts`` ``<basename>_stats.tab``
+    whose Name row is ``basename``, with ``counted`` ``<basename>_complexity.tab``; the paths written."""
+    out = Path(s.outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    # write_tables names the tables after the stem of its path (table.py:185-188): a suffix keeps a dotted base name whole
+    written = tables.write_tables(out / (basename + ".bam"), result)
+    if s.stat_opts is not None:     # every rank holds the same result: the statistics are rank 0's alone
+        from . import stats
+        written.append(stats.write_stats(out / basename, stats.genome_wide_stats(result, read_len, **s.stat_opts)))
+    if counted is not None:
+        written.append(counted.write(path, basename))
+    return written
 
 
 class _ComplexityCount:
@@ -169,14 +221,15 @@ class _ComplexityCount:
     ``write`` writes the table; without a count so far (several ranks) it first counts the chosen chromosomes on one more
     read of the file, through the reader ``inputs.open_alignments`` gives a run of that many ranks."""
 
-    def __init__(self, mapq_criteria: int):
-        self.mapq_criteria = int(mapq_criteria)
+    def __init__(self, s: _Settings):
+        self.s = s
         self.value = None
 
     def hook(self, reader, names):
         from . import complexity
+        mapq = int(self.s.mapq_criteria)
         if hasattr(reader, "arm_complexity"):
-            acc = reader.arm_complexity(self.mapq_criteria, names)
+            acc = reader.arm_complexity(mapq, names)
 
             def after():
                 reader.disarm_complexity()
@@ -184,36 +237,17 @@ class _ComplexityCount:
             return after
 
         def after():
-            self.value = complexity.from_reader(reader, self.mapq_criteria, names)
+            self.value = complexity.from_reader(reader, mapq, names)
         return after
 
-    def write(self, outdir, basename: str, path, references, chromfilter, world, device_ingest, context, device,
-              chrom_sizes) -> Path:
+    def write(self, path, basename: str) -> Path:
         from . import complexity
+        s = self.s
         if self.value is None:
-            ingest = bool(default_device_ingest(world, context) if device_ingest is None else device_ingest)
-            dev = context.device if (context is not None and ingest) else (device or 0)
-            with open_alignments(path, ingest, dev, chrom_sizes=chrom_sizes) as r:
-                if chromfilter is not None:
-                    names = filter_references(r.references, chromfilter)
-                else:
-                    names = [n for n in r.references if references is None or n in set(references)]
-                self.value = complexity.from_reader(r, self.mapq_criteria, names)
-        return complexity.write_complexity(Path(outdir) / basename, basename, self.value)
-
-
-def _write_outputs(outdir, basename: str, result, read_len, stat_opts) -> List[Path]:
-    """``outdir/<basename>_{cc,mscc,nreads}.tab`` and, with ``stat_opts``, ``<basename>_stats.tab`` whose Name row is
-    ``basename``; the paths written."""
-    out = Path(outdir)
-    out.mkdir(parents=True, exist_ok=True)
-    # write_tables names the tables after the stem of its path (table.py:185-188): a suffix keeps a dotted base name whole
-    written = tables.write_tables(out / (basename + ".bam"), result)
-    if stat_opts is not None:       # every rank holds the same result: the statistics are rank 0's alone
-        from . import stats
-        written.append(stats.write_stats(out / basename, stats.genome_wide_stats(result, read_len, **stat_opts)))
-    return written
-
+            with open_alignments(path, s.ingest, reader_device(s.context, s.device, s.ingest), chrom_sizes=s.chrom_sizes) as r:
+                names = kept_references(r.references, s.references, s.chromfilter)
+                self.value = complexity.from_reader(r, int(s.mapq_criteria), names)
+        return complexity.write_complexity(Path(s.outdir) / basename, basename, self.value)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -233,16 +267,14 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None,
               complexity: bool = False) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
-    file, in input order.  Every keyword means what it means for ``run`` (``complexity``: ``<name>_complexity.tab`` for every
-    file that runs, counted as ``run`` counts it; a file that is skipped gets no table).
+    file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
     ``names``: PyMaSC's -n, paired with the files by position (a missing or None name: ``Path(file).stem``, so that a file
     without a name gets exactly what ``run`` writes for it); a name ``N`` gives ``N_cc.tab`` ... ``N_stats.tab``, whole even
-    when it holds a dot.  ``chrom_sizes``: the references of every BED read file among ``paths`` (``run``); a BED read file
-    without them is skipped in step 1 with run's ValueError, and BAM / SAM files keep their header's lengths (logged once when
-    ``chrom_sizes`` is given beside them).  More names than files, an empty name or one with a path separator, and two files with the same base
-    name are a ValueError before any work, as bad options are.  Outputs that exist already are warned about first
-    (pymasc.py:178-182).
+    when it holds a dot.  A BED read file without ``chrom_sizes`` is skipped in step 1 with run's ValueError, and BAM / SAM
+    files keep their header's lengths (logged once when ``chrom_sizes`` is given beside them).  More names than files, an
+    empty name or one with a path separator, and two files with the same base name are a ValueError before any work, as bad
+    options are.  Outputs that exist already are warned about first (pymasc.py:178-182).
 
     The steps, in the reference's order (pymasc.py:99-160, 187-250):
 
@@ -263,85 +295,51 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
     calculator gives its bit-vectors back to the context's pool and frees its result arena before the next file.  The track is
     opened once per rank.  Several ranks: rank 0 alone takes steps 1 and 2 and broadcasts which files are left and the read
     length; every rank then walks the same files, the skip of an unsorted file is decided from every rank's outcome, and
-    rank 0 writes (``written`` is [] on the other ranks)."""
+    rank 0 writes inside ``sharding.on_rank0``, so that a write error reaches every rank (``written`` is [] on the others)."""
     paths = list(paths)
     if not paths:
         raise ValueError("no input files")
-    if references is not None and chromfilter is not None:
-        raise ValueError("give references or chromfilter, not both")
-    from .stats import check_params
-    check_params(None, library_length, smooth_window, max_shift)
-    if read_len is None:
-        readlen._check_esttype(readlen_estimator)
     bases = _basenames(paths, names)
-    stat_opts = None
-    if stats:
-        stat_opts = dict(library_length=library_length, smooth_window=smooth_window, mask_size=mask_size,
-                         bg_avr_width=bg_avr_width, chi2_pval=chi2_pval)
-    on, rank, world = rank_and_world(group)
-    if device is None:
-        device = int(os.environ.get("LOCAL_RANK", "0")) if on else 0
-    _collective_device_setup(device, group)
-    if rank == 0:
-        _warn_existing(outdir, bases, mappability_path is not None, skip_ncc, stats, complexity)
-        if chrom_sizes is not None and not all(_is_bed(p) for p in paths):
+    s = _settings(locals())
+    from .bed_reads import is_bed_reads
+    from .kmer_track import is_fasta
+    if s.rank == 0:
+        _warn_existing(s, bases)
+        if chrom_sizes is not None and not all(is_bed_reads(p) for p in paths):
             logger.info("The chromosome sizes are used for BED read files only: BAM and SAM files keep their header's lengths.")
-    ingest = bool(default_device_ingest(world, context) if device_ingest is None else device_ingest)
-    dev = context.device if (context is not None and ingest) else device         # the device readers' GPU
+    dev = reader_device(context, s.device, s.ingest)
 
     errors: List[Optional[BaseException]] = [None] * len(paths)
     kept = {}                       # index -> device reader opened in _choose that feeds that file's run too
-    ctx, own_ctx, track = context, False, None
+    own_ctx, track = False, None
     try:
-        if world == 1:
-            read_len, kept = _choose(paths, errors, read_len, chromfilter, readlen_estimator, mapq_criteria, max_shift,
-                                     dev if ingest else None, chrom_sizes)
+        if s.world == 1:
+            read_len, kept = _choose(s, paths, errors, read_len)
         else:                       # rank 0 decides, every rank learns the same (none waits for a value that never comes)
             def choose():
                 errs: List[Optional[BaseException]] = [None] * len(paths)
-                rl, _k = _choose(paths, errs, read_len, chromfilter, readlen_estimator, mapq_criteria, max_shift, None,
-                                 chrom_sizes)
+                rl, _k = _choose(s, paths, errs, read_len)
                 return rl, [None if e is None else _portable(e) for e in errs]
             read_len, errors = on_rank0(choose, group, "choosing the input files")
         if read_len is None:
             raise ValueError("no input file is left to run")
         live = [i for i, e in enumerate(errors) if e is None]
-        if ctx is None:
-            ctx, own_ctx = ffi.Context(device), True
-        known = None
+        if context is None:
+            s, own_ctx = replace(s, context=ffi.Context(s.device)), True
         if mappability_path is not None:        # (a genome FASTA: its k-mer track with k = the read length, DESIGN.md 7.13)
-            fasta = _is_fasta(mappability_path)
-            track = open_track(mappability_path, track_on_device(mappability_path, ingest, ctx),
-                               getattr(ctx, "device", dev) if fasta else dev, k=read_len)
-
-            def mappable_lengths():
-                ms = MappabilityStats(track, max_shift, read_len, map_path=mappability_stats_path,
-                                      track_path=mappability_path, device=device, context=ctx)
-                try:
-                    if not ms.is_called:                    # no valid cache: the lag tables of every file, computed once
-                        ms.calc_mappability()
-                        if save_mappability_stats:
-                            ms.save_mappability_stats()
-                    return ms.chrom2mappable_len
-                finally:
-                    ms.close()
-            known = on_rank0(mappable_lengths, group, "mappability statistics")
+            track = open_track(mappability_path, track_on_device(mappability_path, s.ingest, s.context),
+                               getattr(s.context, "device", dev) if is_fasta(mappability_path) else dev, k=read_len)
+        known = _mappable_lengths(s, read_len, track, True)     # the lag tables of every file, computed once
         logger.info("Calculate cross-correlation between 0 to {} base shift with reads MAPQ >= {}"
                     "".format(max_shift, mapq_criteria))
         results = {}
         for i in live:
             logger.info("Process {}".format(paths[i]))
-            bam = None
             bam = kept.pop(i, None)
-            counted = _ComplexityCount(mapq_criteria) if complexity else None
             try:
-                result = run_sharded(paths[i], max_shift, read_len, mapq_criteria, bigwig_path=mappability_path,
-                                     references=references, skip_ncc=skip_ncc, device=device, chrom2mappable_len=known,
-                                     group=group, context=ctx, device_ingest=ingest, bam=bam, chromfilter=chromfilter,
-                                     track=track, chrom_sizes=chrom_sizes,
-                                     reader_hook=counted.hook if counted is not None and world == 1 else None)
+                result, counted = _run_file(s, paths[i], read_len, known, bam, track)
             except Exception as e:
-                skip = _unsorted_on_every_rank(e, world)
+                skip = _unsorted_on_every_rank(e, s.world)
                 if skip is None:
                     raise
                 logger.error("Reads of '{}' are not sorted by position: the file is skipped ({})".format(paths[i], skip))
@@ -350,21 +348,16 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
             finally:
                 if bam is not None:
                     bam.close()
-            def write_all():
-                out = _write_outputs(outdir, bases[i], result, read_len, stat_opts)
-                if counted is not None:
-                    out.append(counted.write(outdir, bases[i], paths[i], references, chromfilter, world, ingest, ctx, device,
-                                             chrom_sizes))
-                return out
-            written = on_rank0(write_all, group, "writing the outputs of '{}'".format(paths[i]))
-            results[i] = (result, list(written) if rank == 0 else [])
+            written = on_rank0(lambda: _write_file(s, paths[i], bases[i], result, read_len, counted), group,
+                               "writing the outputs of '{}'".format(paths[i]))
+            results[i] = (result, list(written) if s.rank == 0 else [])
     finally:
         for r in kept.values():
             r.close()
         if track is not None:
             track.close()
         if own_ctx:
-            ctx.close()
+            s.context.close()
     return [FileResult(p, b, *results[i], None) if i in results else FileResult(p, b, None, [], errors[i])
             for i, (p, b) in enumerate(zip(paths, bases))]
 
@@ -389,35 +382,26 @@ def _basenames(paths, names) -> List[str]:
     return out
 
 
-def _warn_existing(outdir, bases, has_track, skip_ncc, stats, complexity=False):
+def _warn_existing(s: _Settings, bases):
     """prepare_output's warning (pymasc.py:178-182) for every output about to be replaced."""
-    suffixes = [s for s, on in (("_cc.tab", not (has_track and skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
-                                ("_stats.tab", stats), ("_complexity.tab", complexity)) if on]
+    has_track = s.mappability_path is not None
+    suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
+                                ("_stats.tab", s.stat_opts is not None), ("_complexity.tab", s.complexity)) if on]
     for b in bases:
         for suffix in suffixes:
-            path = Path(outdir) / (b + suffix)
+            path = Path(s.outdir) / (b + suffix)
             if path.exists():
                 logger.warning("Existing file '{}' will be overwritten.".format(path))
 
 
-def _is_fasta(path) -> bool:
-    from .kmer_track import is_fasta
-    return is_fasta(path)
-
-
-def _is_bed(path) -> bool:
-    from .bed_reads import is_bed_reads
-    return is_bed_reads(path)
-
-
-def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_shift, device, chrom_sizes=None):
+def _choose(s: _Settings, paths, errors, read_len):
     """Steps 1 and 2 of run_files: the files that open and keep a chromosome, then the common read length.  Fills ``errors``
     with the exception of every file skipped; returns (read length or None when no file is left, {index: device reader} of
-    the readers opened here that feed their file's run).  ``device``: the GPU of the device reader the estimates are made on,
-    None for the host reader.  A stream (inputs.is_stream: ``-``, a FIFO) is opened once, here, by the stream reader, which
-    then feeds its run; without ``read_len`` it is skipped before a byte of it is read (PyMaSC: handler/calc.py:81,
-    pymasc.py:199-201), and without the device reader (``device`` None) too.  A BED read file takes its references from
-    ``chrom_sizes`` (inputs.open_header); without them it is skipped here."""
+    the readers opened here that feed their file's run).  A stream (inputs.is_stream: ``-``, a FIFO) is opened once, here, by
+    the stream reader, which then feeds its run; without ``read_len`` it is skipped before a byte of it is read (PyMaSC:
+    handler/calc.py:81, pymasc.py:199-201), and without the device reader (``s.estimate_gpu`` None) too.  A BED read file
+    takes its references from ``chrom_sizes`` (inputs.open_header); without them it is skipped here."""
+    device = s.estimate_gpu
     kept = {}
     for i, p in enumerate(paths):
         stream = is_stream(p)
@@ -432,11 +416,11 @@ def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_sh
             errors[i] = ValueError("'{}' is a stream: it needs the device reader".format(p))
             continue
         try:
-            r = open_alignments(p, True, device=device) if stream else open_header(p, chrom_sizes)
+            r = open_alignments(p, True, device=device) if stream else open_header(p, s.chrom_sizes)
             try:
                 if not r.references:
                     raise ValueError("File has no sequences defined.")
-                filter_references(r.references, chromfilter)
+                filter_references(r.references, s.chromfilter)
                 if stream:
                     kept[i], r = r, None
             finally:
@@ -454,26 +438,19 @@ def _choose(paths, errors, read_len, chromfilter, esttype, mapq_criteria, max_sh
         return None, kept
     if read_len is not None:
         return int(read_len), kept
-    logger.info("Check read length: Get {} from read length distribution".format(str(esttype).lower()))
+    logger.info("Check read length: Get {} from read length distribution".format(str(s.readlen_estimator).lower()))
     lengths = []
     for i in live:
         logger.info("Check read length... : {}".format(paths[i]))
-        if device is None:
-            r = open_alignments(paths[i], False, index=False, chrom_sizes=chrom_sizes)   # the whole file, without its index
-        else:
-            r = open_alignments(paths[i], True, device=device, chrom_sizes=chrom_sizes)
-        estimated = False
-        try:
-            lengths.append(readlen.estimate_from_reader(r, esttype, mapq_criteria, max_shift))
-            estimated = True
+        try:                        # (one live file: its device reader feeds its run too)
+            length, r = _estimate(s, paths[i], len(live) == 1)
         except ValueError as e:
             logger.error(str(e))
             errors[i] = e
-        finally:
-            if estimated and device is not None and len(live) == 1:
-                kept[i] = r
-            else:
-                r.close()
+            continue
+        lengths.append(length)
+        if r is not None:
+            kept[i] = r
     if not lengths:
         return None, kept
     if len(set(lengths)) != 1:

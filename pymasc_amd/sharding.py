@@ -248,15 +248,15 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     before they are fed; what it returns, when not None, is called without arguments once the feed has succeeded, while the
     reader is still open (pipeline.run counts the library complexity there: the file is inflated once)."""
     from .calculator import CCHipCalculator
-    from .chromfilter import filter_references
-    from .inputs import default_device_ingest, find_index, open_alignments, open_track, track_on_device
+    from .chromfilter import kept_references
+    from .inputs import (check_bed_sizes, default_device_ingest, find_index, open_alignments, open_track, reader_device,
+                         track_on_device)
     from .result import aggregate_results
     from .bed_reads import is_bed_reads
     from .sam import is_sam
 
-    bed = is_bed_reads(bam_path)
-    if bed and chrom_sizes is None and bam is None:
-        raise ValueError("'{}' is a BED read file: give the chromosome sizes (chrom_sizes=, --chrom-sizes)".format(bam_path))
+    if bam is None:
+        check_bed_sizes(bam_path, chrom_sizes)
     on, rank, world = rank_and_world(group)
     if device is None and context is None and on:
         import os
@@ -272,24 +272,21 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
         device_ingest = default_device_ingest(world, context)
     if references is not None and chromfilter is not None:
         raise ValueError("give references or chromfilter, not both")
-    dev = (context.device if context is not None else (device or 0)) if device_ingest else 0     # the device readers' GPU
+    dev = reader_device(context, device) if device_ingest else 0
     # indexed: the open reads the header only, the rank's share is selected below.  SAM text: the unindexed-BAM rules
     # 
     indexed = (device_ingest and bam is None and (world > 1 or references is not None or chromfilter is not None)
-               and not bed and not is_sam(bam_path) and find_index(bam_path) is not None)
+               and not is_bed_reads(bam_path) and not is_sam(bam_path) and find_index(bam_path) is not None)
     reader, bw = bam, None          # the caller's readers are used, not closed
     try:
         if reader is None:
             reader = open_alignments(bam_path, device_ingest, dev, references=[] if indexed else None, chrom_sizes=chrom_sizes)
-        if chromfilter is not None:
-            names = filter_references(reader.references, chromfilter)
-        else:
-            names = [n for n in reader.references if references is None or n in set(references)]
+        names = kept_references(reader.references, references, chromfilter)
         lengths = dict(zip(reader.references, reader.lengths))
         if bigwig_path is not None:     # with device ingest the track is decoded on the GPU too: its intervals stay in HBM
             if track is None:           # (a genome FASTA: on this rank's GPU whenever it has one)
                 gpu_track = track_on_device(bigwig_path, device_ingest, context)
-                tdev = dev if (not gpu_track or device_ingest) else (context.device if context is not None else (device or 0))
+                tdev = dev if (not gpu_track or device_ingest) else reader_device(context, device)
                 bw = open_track(bigwig_path, gpu_track, tdev, k=read_len)
             else:
                 bw = track

@@ -287,6 +287,57 @@ def test_a_sam_file_is_probed_by_its_header(tmp_path, pair, monkeypatch):
     assert [v for _k, v in sorted(_bytes(got[1].written).items())] == [v for _k, v in sorted(want.items())]
 
 
+# What each entry point opens on the host readers, one rank, a BigWig track and no cache: the calls of the openers as pipeline
+# sees them ("p.") and as run_sharded looks them up in inputs ("i."), and for every run_sharded call whether ``bam=`` and
+# ``track=`` were handed on.  An extra open is an extra read of a file, so these counts are this layer's cost.
+_OPENS = {
+    ("run", 1, 36): {"p.open_alignments": 0, "p.open_track": 1, "p.open_header": 0, "i.open_alignments": 1, "i.open_track": 1,
+                     "run_sharded": [(False, False)]},
+    ("run", 1, None): {"p.open_alignments": 1, "p.open_track": 1, "p.open_header": 0, "i.open_alignments": 1,
+                       "i.open_track": 1, "run_sharded": [(False, False)]},
+    ("run_files", 1, 36): {"p.open_alignments": 0, "p.open_track": 1, "p.open_header": 1, "i.open_alignments": 1,
+                           "i.open_track": 0, "run_sharded": [(False, True)]},
+    ("run_files", 1, None): {"p.open_alignments": 1, "p.open_track": 1, "p.open_header": 1, "i.open_alignments": 1,
+                             "i.open_track": 0, "run_sharded": [(False, True)]},
+    ("run_files", 2, 36): {"p.open_alignments": 0, "p.open_track": 1, "p.open_header": 2, "i.open_alignments": 2,
+                           "i.open_track": 0, "run_sharded": [(False, True)] * 2},
+    ("run_files", 2, None): {"p.open_alignments": 2, "p.open_track": 1, "p.open_header": 2, "i.open_alignments": 2,
+                             "i.open_track": 0, "run_sharded": [(False, True)] * 2},
+}
+
+
+@pytest.mark.parametrize("entry,nfiles,read_len", sorted(_OPENS, key=str))
+def test_opens_per_call(tmp_path, pair, monkeypatch, entry, nfiles, read_len):
+    from pymasc_amd import inputs
+    seen = {k: 0 for k in _OPENS[entry, nfiles, read_len] if k != "run_sharded"}
+    seen["run_sharded"] = []
+
+    def counting(key, fn):
+        def call(*a, **k):
+            seen[key] += 1
+            return fn(*a, **k)
+        return call
+
+    for mod, tag in ((pipeline, "p."), (inputs, "i.")):
+        for name in ("open_alignments", "open_track", "open_header"):
+            if tag + name in seen:
+                monkeypatch.setattr(mod, name, counting(tag + name, getattr(mod, name)))
+    real_run = pipeline.run_sharded
+
+    def run_sharded(*a, **k):
+        seen["run_sharded"].append((k.get("bam") is not None, k.get("track") is not None))
+        return real_run(*a, **k)
+    monkeypatch.setattr(pipeline, "run_sharded", run_sharded)
+    bw = _track(tmp_path / "m.bw")
+    kw = dict(read_len=read_len, mapq_criteria=MAPQ, mappability_path=bw, device_ingest=False, context=FakeContext())
+    if entry == "run":
+        pipeline.run(pair[1], tmp_path / "out", SHIFT, **kw)
+    else:
+        got = pipeline.run_files(list(pair[:nfiles]), tmp_path / "out", SHIFT, **kw)
+        assert [g.error for g in got] == [None] * nfiles
+    assert seen == _OPENS[entry, nfiles, read_len]
+
+
 # ---- two gloo ranks -------------------------------------------------------------------------------------------------------
 def _rank_worker(rank, world, port, q, batches, tmp):
     import torch.distributed as dist

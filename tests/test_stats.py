@@ -264,12 +264,13 @@ def test_check_params_accepts_library_length_at_max_shift():
 @pytest.mark.parametrize("kw", [dict(library_length=301), dict(library_length=0), dict(smooth_window=0)])
 def test_pipeline_rejects_options_before_any_work(tmp_path, monkeypatch, kw):
     """pipeline.run raises the ValueError before it opens a file or touches torch.distributed."""
-    from pymasc_amd import pipeline
+    from pymasc_amd import ffi, pipeline, sharding
 
     def boom(*a, **k):
         raise AssertionError("work started")
-    monkeypatch.setattr(pipeline, "_run", boom)
-    monkeypatch.setattr(pipeline, "_estimate_read_len", boom)
+    for mod, name in ((pipeline, "open_alignments"), (pipeline, "open_track"), (pipeline, "run_sharded"), (ffi, "Context"),
+                      (pipeline, "rank_and_world"), (sharding, "rank_and_world")):
+        monkeypatch.setattr(mod, name, boom)
     with pytest.raises(ValueError):
         pipeline.run(tmp_path / "missing.bam", tmp_path / "out", 300, stats=True, **kw)
     assert not (tmp_path / "out").exists()
