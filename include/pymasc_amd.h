@@ -221,6 +221,19 @@ int pmx_bits_set_regions_ex(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits, con
  * PMX_REGIONS_CLEAR, PMX_REGIONS_SORTED (not PMX_REGIONS_SIDE: nothing is copied, the kernel runs on the context's stream). */
 int pmx_bits_set_regions_dev_ex(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits, const uint32_t *d_first, const uint32_t *d_last,
                                 uint64_t n, int64_t first_offset, uint64_t *d_state, uint32_t flags);
+/* The counterpart of pmx_bits_set_regions_dev_ex: CLEARS bits [d_first[i] + first_offset - left_pad, d_last[i]] for n intervals in
+ * device memory (uint32; ends inclusive).  The pad never reaches below bit 1 -- position 1 of a chromosome -- unless
+ * d_first[i] + first_offset does.  [d_first[i] + first_offset, d_last[i]] outside [0, nbits) is clipped and recorded in
+ * d_state[PMX_FEED_FIRST_OUT_OF_RANGE] as the setter records it (d_state may be NULL without flags); an interval whose end lies
+ * below its start is ignored.  With merged exclusion intervals (b, e) of a run of read length L -- first_offset 1, left_pad L - 1
+ * -- the cleared positions are max(1, b + 2 - L) .. e: those where a read of length L would touch (b, e).
+ * flags 0: any order, overlaps allowed (atomic AND on the edge words).  PMX_REGIONS_SORTED: the intervals are sorted and disjoint
+ * before padding -- d_first[i] + first_offset <= d_last[i] < d_first[i + 1] + first_offset -- and every workgroup ANDs the words
+ * it owns once, with plain loads and stores; the order is checked on the device and a violation recorded in
+ * d_state[PMX_FEED_REGIONS_UNSORTED] (the vector is then undefined).  Runs on the context's stream behind the side stream
+ * (pmx_bits_set_regions_ex with PMX_REGIONS_SIDE may be building the vector).  Asynchronous; n may be 0. */
+int pmx_bits_clear_regions_dev_ex(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits, const uint32_t *d_first, const uint32_t *d_last,
+                                  uint64_t n, int64_t first_offset, uint64_t left_pad, uint64_t *d_state, uint32_t flags);
 /* (The three feeders above and below stage their host arrays in one device slot, each array padded to 16 bytes.  Arrays
  * that lie in host memory in that same layout -- back to back in argument order, each padded to 16 bytes, ideally in
  * page-locked memory from pmx_host_alloc -- are copied in ONE piece; anything else array by array.) */

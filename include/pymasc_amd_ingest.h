@@ -162,6 +162,22 @@ int pmx_dbam_readlen_counters(const pmx_dbam *b, uint64_t c[6]);
 int pmx_dbam_complexity(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, const uint8_t *use_ref, uint64_t *per_ref,
                         uint64_t hist[PMX_COMPLEXITY_BINS]);
 
+/* Excluded regions (version >= 10): attaches a BED mask to the handle.  offsets[nref + 1] (host memory) delimit each
+ * reference's lines in begin[] / end[] (0-based, half-open; host OR device memory, the pointer decides): the lines of reference r are
+ * [offsets[r], offsets[r + 1]), in any order, overlapping or abutting.  They are clipped to the reference's length (a line that
+ * is empty then is dropped), sorted by begin within a reference and merged ON THE DEVICE (a line that overlaps or abuts the
+ * running maximum of the ends in front of it joins that group); the merged intervals stay in HBM with the handle.  From then on
+ * every pmx_dbam_decode -- of a BAM, indexed BAM, SAM or BED handle, and of every window of a stream -- leaves out, after its own
+ * filter, the records whose extent [pos1, pos1 + read_len - 1] overlaps a merged interval (b, e) of their reference:
+ * b + 1 <= pos1 + read_len - 1 and pos1 <= e.  The kept records are compacted in file order, so that device_arrays, fetch, runs and
+ * counters' `kept` describe the stream as if the dropped records had never been in the file; pmx_dbam_complexity counts the same
+ * records.  readlen_hist is not affected.  offsets = begin = end = NULL detaches the mask.  nref must be pmx_dbam_nref. */
+int pmx_dbam_set_exclude(pmx_dbam *b, int32_t nref, const int64_t *offsets, const uint32_t *begin, const uint32_t *end);
+/* The merged intervals in (reference, begin) order.  Two-call protocol like pmx_dbam_runs: ref_id == NULL returns their number. */
+int64_t pmx_dbam_exclude_intervals(pmx_dbam *b, int64_t cap, int32_t *ref_id, uint32_t *begin, uint32_t *end);
+/* *dropped = records the last pmx_dbam_decode left out because of the mask; *intervals = merged intervals attached. */
+int pmx_dbam_excluded(const pmx_dbam *b, uint64_t *dropped, uint64_t *intervals);
+
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
  * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong.  An indexed
  * handle: bytes_out is the length of its stream (header + selected records), bytes_in and members count only the members

@@ -72,6 +72,7 @@ class BamReader(AlignmentReader):
         (handler/read.py:62-90,131-141), in file order, at most ``batch`` per round."""
         self._check_open()
         if not _region:      # a plain pass always starts at the first record, whatever was fetched before
+            self._dropped = 0
             rc = self._L.pmx_bam_fetch_ref(self._h, -1)
             if rc:
                 self._raise(rc)
@@ -86,7 +87,7 @@ class BamReader(AlignmentReader):
                 self._raise(n)
             if n == 0:
                 return
-            yield ref[:n].copy(), pos[:n].copy(), rlen[:n].copy(), rev[:n].astype(bool)
+            yield self._drop_excluded(ref[:n].copy(), pos[:n].copy(), rlen[:n].copy(), rev[:n].astype(bool))
 
 
 def feed_bam(calculator, reader: BamReader, mapq_criteria: int, references: Optional[Sequence[str]] = None,
@@ -104,6 +105,7 @@ def feed_bam(calculator, reader: BamReader, mapq_criteria: int, references: Opti
     if use_index is None:
         use_index = reader.has_index() and not use.all()
     fed = 0
+    dropped = 0                                             # (a pass through the index restarts the reader's count per chromosome)
 
     def feed(ref, pos, rlen, rev):
         cuts = np.flatnonzero(np.diff(ref)) + 1           # runs of one chromosome, in file order
@@ -115,9 +117,12 @@ def feed_bam(calculator, reader: BamReader, mapq_criteria: int, references: Opti
 
     if use_index:
         for name in (n for n in names if n in wanted):    # file order = header order for a sorted BAM
+            reader._dropped = 0
             for ref, pos, rlen, rev in reader.fetch(name, mapq_criteria):
                 if ref.size:
                     fed += feed(ref, pos, rlen, rev)
+            dropped += reader.excluded()
+        reader._dropped = dropped
     else:
         for ref, pos, rlen, rev in reader.batches(mapq_criteria):
             if not use.all():

@@ -99,6 +99,44 @@ class DeviceBamReader(AlignmentReader):
             if i not in self._selected:
                 raise ValueError("reference {} was not selected".format(name))
 
+    def set_exclude(self, mask) -> None:
+        """``AlignmentReader.set_exclude`` on the device: the mask's lines go to ``pmx_dbam_set_exclude``, which clips, sorts and
+        merges them in HBM; every later ``decode`` (``feed``, ``batches``, each window of a stream) and ``library_complexity``
+        leaves the overlapping reads out on the GPU."""
+        self._check_open()
+        if mask is None:
+            rc = self._L.pmx_dbam_set_exclude(self._h, 0, None, None, None)
+        else:
+            offsets, begin, end = mask.csr()
+            rc = self._L.pmx_dbam_set_exclude(self._h, len(mask.references), offsets.ctypes.data, begin.ctypes.data if begin.size else None,
+                                              end.ctypes.data if end.size else None)
+        if rc:
+            self._raise(rc)
+        self._exclude = mask
+        self._dropped = 0
+
+    def exclude_intervals(self):
+        """(ref_id int32, begin uint32, end uint32) of the merged intervals the library holds, in (reference, begin) order."""
+        self._check_open()
+        n = self._L.pmx_dbam_exclude_intervals(self._h, 0, None, None, None)
+        if n < 0:
+            self._raise(n)
+        ref, begin, end = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.uint32), np.empty(max(n, 1), np.uint32)
+        m = self._L.pmx_dbam_exclude_intervals(self._h, n, ref.ctypes.data, begin.ctypes.data, end.ctypes.data)
+        if m < 0:
+            self._raise(m)
+        return ref[:m], begin[:m], end[:m]
+
+    def decode(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, reference: int = -1) -> int:
+        n = super().decode(mapq_criteria, flag_exclude, reference)
+        if self._exclude is not None:       # (the count of this decode: pmx_dbam_excluded; a stream's windows add up)
+            d = ctypes.c_uint64()
+            rc = self._L.pmx_dbam_excluded(self._h, ctypes.byref(d), None)
+            if rc:
+                self._raise(rc)
+            self._dropped += int(d.value)
+        return n
+
     def has_index(self) -> bool:
         """Every selected reference can be fetched on its own (its records are resident): no .bai needed for that."""
         return True
@@ -156,6 +194,7 @@ class DeviceBamReader(AlignmentReader):
         wanted = list(calculator.references if references is None else references)
         self._check_selected(wanted)
         wanted = set(wanted)
+        self._dropped = 0
         if not hasattr(calculator, "feed_reads_device"):
             return feed_bam(calculator, self, mapq_criteria, references, finish, use_index=False)
         self.decode(mapq_criteria)
@@ -180,6 +219,7 @@ class DeviceBamReader(AlignmentReader):
                 _reference: int = -1) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
         """Yields (ref_id, pos_1based, read_len, is_reverse) of the reads that pass the reference's filter
         (handler/read.py:62-90,131-141), in file order, at most ``batch`` per round -- as ``BamReader.batches``."""
+        self._dropped = 0
         total = self.decode(mapq_criteria, flag_exclude, _reference)
         keep = None
         if not self.indexed and len(self._selected) < len(self.references):

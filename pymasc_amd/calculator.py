@@ -113,7 +113,10 @@ class CCHipCalculator:
     def __init__(self, max_shift: int, read_len: int, references: Sequence[str], lengths: Sequence[int],
                  bwfeeder: Any = None, skip_ncc: bool = False, logger_lock: Any = None, progress_bar: Any = None,
                  device: int = 0, kernel_flags: int = 0, context: Optional[ffi.Context] = None,
-                 chrom2mappable_len: Optional[Dict[str, Sequence[int]]] = None):
+                 chrom2mappable_len: Optional[Dict[str, Sequence[int]]] = None, exclude: Any = None):
+        """``exclude``: the excluded regions of the run (``region_mask.ResolvedMask``) -- every chromosome's
+        mappability vector is cleared on ``max(1, b + 2 - read_len) .. e`` of each merged interval once it is built, before its
+        batch is queued.  The reads are the reader's to leave out (``set_exclude``)."""
         self.max_shift = int(max_shift)
         self.read_len = int(read_len)
         self.references = list(references)
@@ -130,6 +133,9 @@ class CCHipCalculator:
         # lag tables known beforehand (the *_mappability.json cache, pymasc_amd/mappability.py): chromosomes
         # found here skip the autocorrelation pass
         self._known_mlen: Dict[str, Sequence[int]] = dict(chrom2mappable_len or {})
+        self._exclude = exclude
+        self._excl_dev: Dict[str, Tuple[int, int, int]] = {}    # chromosome -> (d_first, d_last, n) of its merged intervals
+        self._excl_bufs: List[int] = []
 
         self._ncc: Dict[str, NCCResult] = {}
         self._mscc: Dict[str, MSCCResult] = {}
@@ -227,6 +233,9 @@ class CCHipCalculator:
         if self._arena:
             ctx.bits_free(self._arena)
             self._arena = 0
+        for p in getattr(self, "_excl_bufs", []):
+            ctx.bits_free(p)
+        self._excl_bufs, self._excl_dev = [], {}
         if self._own_ctx:
             ctx.close()
         self._ctx = None
@@ -387,6 +396,38 @@ class CCHipCalculator:
 
     # ---- per-chromosome calculation ---------------------------------------------------------------
     def _load_mappability(self, chrom: str, nbits: int, slot: int):
+        """``_build_mappability``, then the excluded regions cleared out of the vector: positions
+        ``max(1, b + 2 - L) .. e`` of every merged interval, where a read of length L would touch it.  The clear runs on the
+        context's stream behind the side stream that may be building the vector (pmx_bits_clear_regions_dev_ex)."""
+        vec = self._build_mappability(chrom, nbits, slot)
+        if vec is not None and self._exclude is not None:
+            d_first, d_last, n = self._exclude_intervals(chrom)
+            if n:
+                self._ctx.bits_clear_regions_dev_ex(vec[0], nbits, d_first, d_last, n, 1, self.read_len - 1, self._state_ptr(slot),
+                                                    sorted_disjoint=True)
+        return vec
+
+    def _exclude_intervals(self, chrom: str) -> Tuple[int, int, int]:
+        """(device address of the begins, of the ends, count) of the chromosome's merged excluded intervals (uint32), uploaded
+        once per chromosome: begins and ends in one allocation, the ends at the next 8-byte boundary."""
+        hit = self._excl_dev.get(chrom)
+        if hit is None:
+            mb, me = self._exclude.track_intervals(chrom)
+            n = int(mb.size)
+            hit = (0, 0, 0)
+            if n:
+                npad = (n + 1) & ~1
+                host = np.zeros(2 * npad, dtype=np.uint32)
+                host[:n], host[npad:npad + n] = mb, me
+                words = host.view(np.uint64)
+                p = self._ctx.bits_alloc(words.size * 64)
+                self._excl_bufs.append(p)
+                self._ctx.bits_upload(p, words, words.size * 64)
+                hit = (p, p + 4 * npad, n)
+            self._excl_dev[chrom] = hit
+        return hit
+
+    def _build_mappability(self, chrom: str, nbits: int, slot: int):
         """mscc.pyx:327-349 -> (device vector, pool capacity), queued, not waited for; None without a feeder; KeyError if
         the track is missing."""
         if not self._bwfeeder:

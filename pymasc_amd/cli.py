@@ -17,6 +17,7 @@ import signal
 import sys
 from itertools import zip_longest
 from pathlib import Path
+from typing import Optional
 
 from . import __version__, launch
 
@@ -85,6 +86,20 @@ def track_options(group) -> None:
     group.add_argument("--mappability-stats", metavar="JSON", type=Path,
                        help="where the mappable-length cache is read and written (default: the track's path with "
                             "_mappability.json in place of its extension)")
+
+
+def exclude_option(group) -> None:
+    group.add_argument("--exclude-regions", metavar="BED", type=Path,
+                       help="leave out the regions of this BED file (plain or gzip / bgzip-compressed; ENCODE's blacklist): reads "
+                            "that overlap one are dropped before the correlation, and the mappability track is cleared where a "
+                            "read would touch one; the mappable-length cache is then <track>_<BED name>_mappability.json")
+
+
+def missing_exclude_file(args) -> Optional[str]:
+    """The argparse message for an --exclude-regions file that does not exist, or None."""
+    if args.exclude_regions is not None and not os.path.isfile(args.exclude_regions):
+        return "argument --exclude-regions: no such file: '{}'".format(args.exclude_regions)
+    return None
 
 
 def shift_option(group) -> None:
@@ -179,7 +194,9 @@ def get_parser() -> argparse.ArgumentParser:
                        help="reads with a mapping quality below this are left out (default 1)")
     chromfilter_options(reads)
 
-    track_options(parser.add_argument_group("mappability"))
+    track = parser.add_argument_group("mappability")
+    track_options(track)
+    exclude_option(track)
 
     fit = parser.add_argument_group("correlation and statistics")
     shift_option(fit)
@@ -230,6 +247,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("argument -n/--name: {}".format(e))
     if args.chrom_sizes is not None and not os.path.isfile(args.chrom_sizes):
         parser.error("argument --chrom-sizes: no such file: '{}'".format(args.chrom_sizes))
+    if missing_exclude_file(args):
+        parser.error(missing_exclude_file(args))
     if args.chrom_sizes is None:
         from .bed_reads import is_bed_reads     # (no torch, no native library)
         bed = [str(p) for p in args.reads if is_bed_reads(p)]
@@ -310,6 +329,8 @@ def _run(args, device, rank: int) -> int:
     extra = {} if args.chrom_sizes is None else {"chrom_sizes": str(args.chrom_sizes)}   # (BED read files only)
     if args.complexity:
         extra["complexity"] = True
+    if args.exclude_regions is not None:
+        extra["exclude_regions"] = str(args.exclude_regions)
     try:
         results = pipeline.run_files(
             [str(p) for p in args.reads], str(args.outdir), args.max_shift, read_len=args.read_length,

@@ -1225,6 +1225,12 @@ struct pmx_dbam {
     u64 stream_base = 0;             // offset of d_out[0] in the whole inflated stream (the histogram's first-occurrence keys)
     bool respec = false;             // a new window: the record chain is guessed again in the tables it has
     u64 chain_cap = 0;               // pieces the chain's tables hold
+    // excluded regions (pmx_dbam_set_exclude, region_mask_device.inc): merged intervals in (reference, begin) order
+    u64 *d_xkey = nullptr;           // ref_id << 32 | begin (0-based)
+    u32 *d_xend = nullptr;           // end (exclusive), clipped to the reference's length
+    u64 x_n = 0, x_dropped = 0;      // merged intervals; reads the last decode left out because of them
+    u8 *d_xs = nullptr;              // the filter's scratch block (flags, block counts, compacted fields), grown, never shrunk
+    u64 xs_cap = 0;
 };
 
 namespace {
@@ -1773,7 +1779,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 9; }
+int pmx_dbam_version(void) { return 10; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1841,6 +1847,9 @@ void pmx_dbam_close(pmx_dbam *b)
     stream_free(b);
     free_chain(*b);
     if (b->d_rl) (void)hipFree(b->d_rl);
+    if (b->d_xkey) (void)hipFree(b->d_xkey);
+    if (b->d_xend) (void)hipFree(b->d_xend);
+    if (b->d_xs) (void)hipFree(b->d_xs);
     for (void *p : {(void *)b->d_nl, (void *)b->d_ls, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
         if (p) (void)hipFree(p);
     for (hipStream_t x : b->kmore)
@@ -1871,10 +1880,26 @@ const char *pmx_dbam_header_text(const pmx_dbam *b, uint32_t *len)
 }
 
 static int64_t dbam_decode_impl(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref);
+// region_mask_device.inc: the records of [0, n) that overlap no excluded region, compacted in place in file order; *n_out = how many
+static int rm_filter(pmx_dbam *b, int *ref, int *pos, int *len, u8 *rev, u64 n, u64 *n_out);
 int64_t pmx_dbam_decode(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref)
 {
     try {
-        return dbam_decode_impl(b, mapq_min, flag_exclude, want_ref);
+        const int64_t n = dbam_decode_impl(b, mapq_min, flag_exclude, want_ref);
+        if (b) b->x_dropped = 0;
+        if (n <= 0 || !b->x_n) return n;
+        // the excluded regions: one pass over the kept records of any decode (BAM walk, SAM / BED table, a stream's window);
+        // pmx_dbam_runs, fetch and the feeders then see the records as if the dropped ones had never been in the file
+        const double t0 = now_s();
+        u64 m = 0;
+        if (int rc = rm_filter(b, b->d_ref, b->d_pos, b->d_len, b->d_rev, (u64)n, &m)) {
+            b->n_kept = 0;
+            return rc;
+        }
+        b->x_dropped = (u64)n - m;
+        b->n_kept = m;
+        b->t[5] += now_s() - t0;
+        return (int64_t)m;
     } catch (const std::exception &e) {
         return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_decode: ") + e.what());
     }
@@ -2538,3 +2563,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "bed_reads_device.inc"
 #include "kmer_track_device.inc"
 #include "complexity_device.inc"
+#include "region_mask_device.inc"

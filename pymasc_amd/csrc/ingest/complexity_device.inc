@@ -242,7 +242,10 @@ int cx_filter(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, u64 front, bool curre
                            R.rev.as<u8>() + front);
         HIPOK(hipGetLastError());
         HIPOK(hipStreamSynchronize(st));
-        R.n = front + totals[0];
+        u64 m = totals[0];      // (an attached region mask: counted are the reads the run is fed)
+        if (int rc = rm_filter(b, R.ref.as<int>() + front, R.pos.as<int>() + front, R.len.as<int>() + front, R.rev.as<u8>() + front, m, &m))
+            return rc;
+        R.n = front + m;
         return 0;
     }
     if (current && !b->sam && b->npieces > 0) {
@@ -295,7 +298,10 @@ int cx_filter(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, u64 front, bool curre
         HIPOK(hipMemcpyAsync(&fe, d_err.p, 8, hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
         if (fe != ~0ull) return record_error(fe);
-        R.n = front + totals[0];
+        u64 m = totals[0];
+        if (int rc = rm_filter(b, R.ref.as<int>() + front, R.pos.as<int>() + front, R.len.as<int>() + front, R.rev.as<u8>() + front, m, &m))
+            return rc;
+        R.n = front + m;
         return 0;
     }
     if (front) {

@@ -413,6 +413,112 @@ __global__ void __launch_bounds__(256) k_regions_build(u64 *__restrict__ words, 
     }
 }
 
+// ---- clearing regions (pmx_bits_clear_regions_dev_ex): the counterpart of the two setters above ----
+// Interval i clears bits [a_i - left_pad, b_i] with a_i = first[i] + offset and b_i = last[i]; the pad stops at bit 1 (the first
+// position of a chromosome) unless a_i itself lies below it.  [a_i, b_i] outside [0, nbits) is clipped and recorded in err as the
+// setters record it.  The padded start of an interval: rc_start.
+__device__ __forceinline__ int64_t rc_start(int64_t a, int64_t pad)
+{
+    const int64_t floor1 = a < 1 ? a : 1;
+    return a - pad < floor1 ? floor1 : a - pad;
+}
+
+// Any order, overlaps allowed: one wavefront per interval, the two edge words AND-ed atomically, the words between stored as zero.
+__global__ void __launch_bounds__(256) k_clear_regions(u64 *__restrict__ words, uint64_t nbits, const u32 *__restrict__ from,
+                                                       const u32 *__restrict__ to, uint64_t n, int64_t offset, int64_t pad,
+                                                       u64 *__restrict__ err)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t i = wave; i < n; i += nwaves) {
+        int64_t a = (int64_t)from[i] + offset, b = (int64_t)to[i];
+        if (b < a) continue;
+        if (a < 0 || b >= (int64_t)nbits) {
+            if (err && lane == 0) atomicMax(err, FEED_ERR_BASE - i);
+            if (a < 0) a = 0;
+            if (b >= (int64_t)nbits) b = (int64_t)nbits - 1;
+            if (b < a) continue;
+        }
+        a = rc_start(a, pad);
+        const uint64_t wa = (uint64_t)a >> 6, wb = (uint64_t)b >> 6;
+        const u64 lo_mask = ~0ull << (a & 63);
+        const u64 hi_mask = ~0ull >> (63 - (b & 63));
+        if (wa == wb) {
+            if (lane == 0) atomicAnd(&words[wa], ~(lo_mask & hi_mask));
+            continue;
+        }
+        if (lane == 0) atomicAnd(&words[wa], ~lo_mask);
+        if (lane == 1) atomicAnd(&words[wb], ~hi_mask);
+        for (uint64_t w = wa + 1 + lane; w < wb; w += 64) words[w] = 0;
+    }
+}
+
+// Sorted, merged intervals (first ascending, last ascending, a_i <= b_i < a_(i+1)), owner-computes: the vector's words are dealt to
+// the workgroups, RB_WORDS each; a workgroup finds the intervals that reach into its bits with two searches (the padded starts
+// ascend with the starts), collects the bits to clear in LDS -- a wavefront per interval, its lanes over the interval's words in the
+// workgroup's range -- and ANDs every word that has any once, with a plain load and store: no atomics on the vector, and a
+// workgroup no interval reaches touches nothing.  The order is checked as k_regions_build checks it (err_order).
+__global__ void __launch_bounds__(256) k_regions_clear(u64 *__restrict__ words, uint64_t nbits, const u32 *__restrict__ from,
+                                                       const u32 *__restrict__ to, uint64_t n, int64_t offset, int64_t pad,
+                                                       u64 *__restrict__ err_range, u64 *__restrict__ err_order)
+{
+    __shared__ u64 clr[RB_WORDS];
+    __shared__ uint64_t s_idx[2];
+    const u32 tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint64_t nwords = (nbits + 63) / 64;
+    const uint64_t w0 = (uint64_t)blockIdx.x * RB_WORDS;
+    const uint64_t w1 = w0 + RB_WORDS < nwords ? w0 + RB_WORDS : nwords;
+    const int64_t lo = (int64_t)(w0 * 64), hi = (int64_t)(w1 * 64);
+    // every interval once, by index: order against its successor, emptiness, range
+    {
+        const uint64_t per = (n + gridDim.x - 1) / gridDim.x;
+        const uint64_t ia = (uint64_t)blockIdx.x * per, ib = ia + per < n ? ia + per : n;
+        u64 e_order = 0, e_range = 0;
+        for (uint64_t i = ia + tid; i < ib; i += 256) {
+            const int64_t a = (int64_t)from[i] + offset, b = (int64_t)to[i];
+            const bool bad = b < a || (i + 1 < n && (int64_t)from[i + 1] + offset <= b);
+            if (bad && FEED_ERR_BASE - i > e_order) e_order = FEED_ERR_BASE - i;
+            if (b >= a && (a < 0 || b >= (int64_t)nbits) && FEED_ERR_BASE - i > e_range) e_range = FEED_ERR_BASE - i;
+        }
+        if (e_order && err_order) atomicMax(err_order, e_order);
+        if (e_range && err_range) atomicMax(err_range, e_range);
+    }
+    // the intervals that reach into [lo, hi): from the first whose end is >= lo up to the first whose padded start is >= hi
+    // (a start - pad >= hi needs start >= hi + pad: the floor at bit 1 only matters below hi)
+    if (wv < 2) {
+        const uint64_t idx = wv == 0 ? feed_lower_bound(to, n, lo, false, lane) : feed_lower_bound(from, n, hi + pad - offset, false, lane);
+        if (lane == 0) s_idx[wv] = idx;
+    }
+    __syncthreads();
+    const uint64_t i_lo = s_idx[0], i_hi = s_idx[1];
+    if (i_lo >= i_hi) return;
+    for (u32 i = tid; i < RB_WORDS; i += 256) clr[i] = 0;
+    __syncthreads();
+    for (uint64_t i = i_lo + wv; i < i_hi; i += 4) {
+        int64_t a = (int64_t)from[i] + offset, b = (int64_t)to[i];
+        if (b < a) continue;
+        if (a < 0) a = 0;
+        if (b >= (int64_t)nbits) b = (int64_t)nbits - 1;
+        if (b < a) continue;
+        a = rc_start(a, pad);
+        const int64_t sa = a > lo ? a : lo, sb = b < hi - 1 ? b : hi - 1;      // bits [sa, sb] are this workgroup's
+        if (sb < sa) continue;
+        const uint64_t wa = (uint64_t)sa >> 6, wb = (uint64_t)sb >> 6;
+        for (uint64_t w = wa + lane; w <= wb; w += 64) {
+            u64 m = ~0ull;
+            if (w == wa) m &= ~0ull << (sa & 63);
+            if (w == wb) m &= ~0ull >> (63 - (sb & 63));
+            atomicOr(&clr[(u32)(w - w0)], m);          // (LDS: padded neighbours may share a word)
+        }
+    }
+    __syncthreads();
+    for (u32 k = tid; k < RB_WORDS; k += 256) {
+        const u64 m = clr[k];
+        if (m && w0 + k < w1) words[w0 + k] &= ~m;
+    }
+}
+
 // bitarray[pos] = 1 for positions of either width; out-of-range positions are dropped and recorded in err
 template <typename T>
 __global__ void __launch_bounds__(256) k_set_positions_t(u64 *__restrict__ words, uint64_t nbits, const T *__restrict__ pos,
@@ -782,6 +888,28 @@ int pmx_launch_regions_build_on(pmx_ctx *ctx, hipStream_t stream, uint64_t *d_wo
         return PMX_ERR_INVALID;
     }
     PMX_CHECK_LAUNCH("k_regions_build");
+    return PMX_OK;
+}
+
+int pmx_launch_clear_regions(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits, const uint32_t *d_from, const uint32_t *d_to, uint64_t n,
+                             int64_t offset, int64_t pad, bool sorted, uint64_t *d_err_range, uint64_t *d_err_order)
+{
+    const uint64_t nwords = (nbits + 63) / 64;
+    if (n == 0 || nwords == 0) return PMX_OK;
+    if (sorted) {
+        const uint64_t g = (nwords + RB_WORDS - 1) / RB_WORDS;
+        if (g > 0x7fffffffull) {
+            pmx_set_error("regions_clear: vector too long");
+            return PMX_ERR_INVALID;
+        }
+        hipLaunchKernelGGL(k_regions_clear, dim3((u32)g), dim3(256), 0, ctx->stream, (u64 *)d_words, nbits, d_from, d_to, n, offset, pad,
+                           (u64 *)d_err_range, (u64 *)d_err_order);
+        PMX_CHECK_LAUNCH("k_regions_clear");
+        return PMX_OK;
+    }
+    hipLaunchKernelGGL(k_clear_regions, dim3(feed_grid(ctx, n, 4)), dim3(256), 0, ctx->stream, (u64 *)d_words, nbits, d_from, d_to, n, offset,
+                       pad, (u64 *)d_err_range);
+    PMX_CHECK_LAUNCH("k_clear_regions");
     return PMX_OK;
 }
 

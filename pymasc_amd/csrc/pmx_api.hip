@@ -1092,6 +1092,20 @@ int pmx_bits_set_regions_dev_ex(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits,
                                     d_state ? d_state + PMX_FEED_FIRST_OUT_OF_RANGE : nullptr);
 }
 
+int pmx_bits_clear_regions_dev_ex(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits, const uint32_t *d_first, const uint32_t *d_last,
+                                  uint64_t n, int64_t first_offset, uint64_t left_pad, uint64_t *d_state, uint32_t flags)
+{
+    if (ctx) (void)hipSetDevice(ctx->device);
+    REQUIRE(ctx && d_words && ((d_first && d_last) || n == 0), "pmx_bits_clear_regions_dev_ex: NULL argument");
+    REQUIRE(!(flags & ~PMX_REGIONS_SORTED), "pmx_bits_clear_regions_dev_ex: unknown flag (only PMX_REGIONS_SORTED)");
+    REQUIRE(!(flags & PMX_REGIONS_SORTED) || d_state, "pmx_bits_clear_regions_dev_ex: PMX_REGIONS_SORTED needs d_state (order violations are recorded there)");
+    REQUIRE(left_pad < (1ull << 40), "pmx_bits_clear_regions_dev_ex: left_pad must be below 2^40");
+    PMX_JOIN_SIDE(ctx);      // (the vector may be in the making on the side stream)
+    return pmx_launch_clear_regions(ctx, d_words, nbits, d_first, d_last, n, first_offset, (int64_t)left_pad, (flags & PMX_REGIONS_SORTED) != 0,
+                                    d_state ? d_state + PMX_FEED_FIRST_OUT_OF_RANGE : nullptr,
+                                    d_state ? d_state + PMX_FEED_REGIONS_UNSORTED : nullptr);
+}
+
 int pmx_bits_set_regions_async(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits, const void *h_first, const void *h_last,
                                uint32_t width_bytes, uint64_t n, int64_t first_offset, uint64_t *d_state)
 {

@@ -180,6 +180,8 @@ int pmx_launch_feed_expand16(pmx_ctx *ctx, const void *d_words, const void *d_se
 int pmx_launch_set_regions_w(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits, const void *d_from, const void *d_to, uint32_t width,
                              uint64_t n, int64_t offset, uint64_t *d_err);
 // the whole vector from sorted, disjoint intervals (k_regions_build): no clear needed, violations recorded in d_err_order
+int pmx_launch_clear_regions(pmx_ctx *ctx, uint64_t *d_words, uint64_t nbits, const uint32_t *d_from, const uint32_t *d_to, uint64_t n,
+                             int64_t offset, int64_t pad, bool sorted, uint64_t *d_err_range, uint64_t *d_err_order);
 int pmx_launch_regions_build_on(pmx_ctx *ctx, hipStream_t stream, uint64_t *d_words, uint64_t nbits, const void *d_from, const void *d_to,
                                 uint32_t width, uint64_t n, int64_t offset, uint64_t *d_err_range, uint64_t *d_err_order);
 // (the same on an explicit stream: the side work never touches ctx->stream)

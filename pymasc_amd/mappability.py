@@ -46,6 +46,10 @@ class NeedUpdate(Exception):
     """The cache covers fewer lags than this run needs (handler/mappability.py:57-61)."""
 
 
+class _OtherMask(Exception):
+    """The cache was computed for another state of the excluded regions (none, or another read length)."""
+
+
 class _IntEncoder(json.JSONEncoder):
     """numpy scalars / arrays as plain JSON numbers / lists (handler/mappability.py:64-86)."""
 
@@ -100,7 +104,7 @@ def read_stats(path, need_shift: int, references: Iterable[str]) -> Dict[str, An
     return stats
 
 
-def write_stats(path, max_shift: int, whole: Sequence[int], per_chrom: Mapping[str, Sequence[int]]) -> None:
+def write_stats(path, max_shift: int, whole: Sequence[int], per_chrom: Mapping[str, Sequence[int]], extra: Optional[Mapping] = None) -> None:
     """The cache file, laid out like the reference's (handler/mappability.py:294-301).  Written to a temporary file in
     the same directory and renamed into place, so a concurrent reader (another rank, another run) sees either the old
     file or the complete new one, never a truncated one."""
@@ -109,7 +113,7 @@ def write_stats(path, max_shift: int, whole: Sequence[int], per_chrom: Mapping[s
     try:
         with open(tmp, "w") as fp:
             json.dump({"max_shift": max_shift, "__whole__": list(whole),
-                       "references": {c: list(v) for c, v in per_chrom.items()}},
+                       "references": {c: list(v) for c, v in per_chrom.items()}, **dict(extra or {})},
                       fp, indent=4, sort_keys=True, cls=_IntEncoder)
         os.replace(tmp, path)
     finally:
@@ -126,8 +130,13 @@ class MappabilityStats:
     """
 
     def __init__(self, feeder: Any, max_shift: int = 0, readlen: int = 0, map_path=None, track_path=None,
-                 device: int = 0, context: Optional[ffi.Context] = None):
+                 device: int = 0, context: Optional[ffi.Context] = None, masked_read_len: Optional[int] = None):
+        """``masked_read_len``: ``feeder`` is a track with excluded regions cut out for reads of this length
+        (``region_mask.MaskedTrack``).  Its cache holds that length under ``exclude_read_len`` and is valid for
+        that length only; a cache without the key -- an unmasked track's -- is never taken for it.  ``map_path`` must then be given
+        (``region_mask.stats_path``) or there is no cache: the unmasked default path is never derived."""
         self.feeder = feeder
+        self.masked_read_len = None if masked_read_len is None else int(masked_read_len)
         self.chromsizes: Dict[str, int] = dict(feeder.chromsizes)
         self.max_shift = required_shift_size(int(readlen), int(max_shift))
         self.chrom2is_called = {c: False for c in self.chromsizes}
@@ -141,7 +150,7 @@ class MappabilityStats:
 
         if map_path is not None:
             self.map_path: Optional[Path] = Path(map_path)
-        elif track_path is not None:
+        elif track_path is not None and self.masked_read_len is None:
             self.map_path = default_stats_path(track_path, getattr(feeder, "k", None))
         else:
             self.map_path = None
@@ -173,6 +182,8 @@ class MappabilityStats:
     def _try_load(self) -> None:
         try:
             stats = read_stats(self.map_path, self.max_shift, self.chromsizes)
+            if stats.get("exclude_read_len") != self.masked_read_len:
+                raise _OtherMask
         except IOError as e:
             logger.error("Failed to read '{}'".format(self.map_path))
             logger.error("[Errno {}] {}".format(e.errno, str(e)))
@@ -180,6 +191,10 @@ class MappabilityStats:
             logger.error("Failed to load json file: '{}'".format(self.map_path))
         except NeedUpdate:
             logger.info("Specified shift length longer than former analysis. The stats will be updated.")
+        except _OtherMask:
+            logger.info("'{}' was computed {}: the stats will be updated.".format(
+                self.map_path, "without excluded regions or for another read length" if self.masked_read_len is not None
+                else "with excluded regions"))
         else:
             n = self.max_shift + 1
             self.mappable_len = list(stats["__whole__"][:n])
@@ -198,7 +213,8 @@ class MappabilityStats:
             self.calc_mappability()
         logger.info("Save mappable length to '{}'".format(self.map_path))
         try:
-            write_stats(self.map_path, self.max_shift, self.mappable_len, self.chrom2mappable_len)
+            write_stats(self.map_path, self.max_shift, self.mappable_len, self.chrom2mappable_len,
+                        None if self.masked_read_len is None else {"exclude_read_len": self.masked_read_len})
         except IOError as e:
             logger.error("Faild to output: {}\n[Errno {}] {}".format(e.filename, e.errno, str(e)))
         self.need_save_stats = False

@@ -116,6 +116,9 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_device_arrays": (_int, [_vp] + [_out] * 4),
     "pmx_dbam_runs": (_i64, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "pmx_dbam_complexity": (_int, [_vp, _u32, _u32, _vp, _vp, _vp]),
+    "pmx_dbam_set_exclude": (_int, [_vp, _i32, _vp, _vp, _vp]),
+    "pmx_dbam_exclude_intervals": (_i64, [_vp, _i64, _vp, _vp, _vp]),
+    "pmx_dbam_excluded": (_int, [_vp, _pu64, _pu64]),
     "pmx_dbam_counters": (_int, [_vp] + [_pu64] * 6),
     "pmx_dbam_timings": (_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "pmx_dbam_inflated": (_int, [_vp, _u64, _u64, _vp]),
@@ -261,6 +264,30 @@ class AlignmentReader(NativeReader):
         from .complexity import from_reader
         self._check_open()
         return from_reader(self, mapq_criteria, references)
+
+    # ---- excluded regions (pymasc_amd.region_mask) ----
+    _exclude = None
+    _dropped = 0
+
+    def set_exclude(self, mask) -> None:
+        """From now on the reads that overlap ``mask`` (a ``region_mask.ResolvedMask`` of this reader's references; None: no
+        mask) are left out of ``batches`` / ``feed`` / ``library_complexity``, after the reader's own filter.  A host reader
+        applies ``mask.keep`` to every batch; a device reader hands the mask to the library."""
+        self._check_open()
+        self._exclude = mask
+        self._dropped = 0
+
+    def excluded(self) -> int:
+        """Reads left out because of the mask since the last pass (``feed`` / ``batches`` / ``decode``) began."""
+        return int(self._dropped)
+
+    def _drop_excluded(self, ref, pos, rlen, rev):
+        """A host batch less the reads the mask leaves out."""
+        if self._exclude is None or ref.size == 0:
+            return ref, pos, rlen, rev
+        keep = self._exclude.keep(ref, pos, rlen)
+        self._dropped += int(ref.size - keep.sum())
+        return ref[keep], pos[keep], rlen[keep], rev[keep]
 
     def decode(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, reference: int = -1) -> int:
         """Runs the record walk + filter; returns the number of kept records (they stay with the handle, for ``_fetch``)."""

@@ -37,7 +37,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
         device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
         library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
-        chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False):
+        chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -59,7 +59,14 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     ``mapq_criteria`` on the chosen chromosomes, flagged duplicates kept).  One rank: counted on the reader
     the run feeds from, so the file is inflated once (a stream is counted window by window while it is fed).  Several ranks:
     rank 0 alone counts the chosen chromosomes on one more read of the file through ``inputs.open_alignments``, after the
-    run; no collective is added.  A run that raises (unsorted reads) writes no table."""
+    run; no collective is added.  A run that raises (unsorted reads) writes no table.
+    ``exclude_regions``: a BED file (plain, gzip or bgzip) or an ordered ``{name: [(start, end), ...]}`` of regions to leave out,
+    as ENCODE leaves out its blacklist (pymasc_amd.region_mask): reads whose extent
+    ``[pos1, pos1 + read_len - 1]`` overlaps a merged region are removed before the feeders (on the GPU with device ingest), the
+    track is cleared where a read of the run's length would touch a region, ``complexity`` counts the reads that are left, and the
+    mappable-length cache is ``<track stem>_<mask file stem>_mappability.json`` (a dict: none) unless ``mappability_stats_path``
+    names it.  The read length is still estimated over the whole file.  No region's chromosome among the references: ValueError
+    before any table is written."""
     check_bed_sizes(bam_path, chrom_sizes)
     s = _settings(locals())
     from .kmer_track import is_fasta
@@ -72,8 +79,9 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         if mappability_path is not None and is_fasta(mappability_path):
             track = open_track(mappability_path, track_on_device(mappability_path, False, context),
                                reader_device(context, s.device), k=read_len)
-        known = _mappable_lengths(s, read_len, track, False)
-        result, counted = _run_file(s, bam_path, read_len, known, bam, track)
+        mask, bam = _resolve_mask(s, bam_path, bam)     # (no name in common: ValueError before the cache pass and any table)
+        known = _mappable_lengths(s, read_len, track, False, mask)
+        result, counted = _run_file(s, bam_path, read_len, known, bam, track, mask)
     finally:
         if track is not None:
             track.close()
@@ -104,6 +112,7 @@ class _Settings:
     readlen_estimator: str
     chrom_sizes: object
     complexity: bool
+    exclude_regions: object         # None, or the region_mask.ExcludeMask read once for the call
     save_mappability_stats: bool
     device: int
     ingest: bool
@@ -134,6 +143,9 @@ def _settings(kw: dict) -> _Settings:
     _collective_device_setup(device, kw["group"])
     ingest = default_device_ingest(world, kw["context"]) if kw["device_ingest"] is None else kw["device_ingest"]
     given = {f.name: kw[f.name] for f in fields(_Settings) if f.name in kw}
+    if kw.get("exclude_regions") is not None:      # read once (on the GPU with device ingest); each file resolves the names
+        from .region_mask import open_mask
+        given["exclude_regions"] = open_mask(kw["exclude_regions"], bool(ingest), reader_device(kw["context"], device, bool(ingest)))
     given.update(device=device, ingest=bool(ingest), rank=rank, world=world,
                  stat_opts={k: kw[k] for k in _STAT_OPTS} if kw["stats"] else None)
     return _Settings(**given)
@@ -158,26 +170,55 @@ def _estimate(s: _Settings, path, keep: bool):
             r.close()
 
 
-def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool):
+def _resolve_mask(s: _Settings, path, bam):
+    """(the run's excluded regions bound to the references of ``path`` -- a ``region_mask.ResolvedMask``, None without
+    ``exclude_regions`` --, the open reader of ``path``).  The references come from ``bam`` when the file is open already, else
+    from its header alone (``inputs.open_header``); a stream has no header to read apart, so its device reader is opened here
+    and handed back to feed the run.  ValueError when no name of the mask is a reference."""
+    if s.exclude_regions is None:
+        return None, bam
+    if bam is None and is_stream(path) and s.estimate_gpu is not None:
+        bam = open_alignments(path, True, device=s.estimate_gpu)
+    if bam is not None:
+        try:
+            return s.exclude_regions.resolve(bam.references, bam.lengths), bam
+        except BaseException:
+            bam.close()
+            raise
+    if is_stream(path):             # (no device reader: run_sharded says so)
+        return s.exclude_regions, bam
+    with open_header(path, s.chrom_sizes) as h:
+        return s.exclude_regions.resolve(h.references, h.lengths), bam
+
+
+def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool, mask=None):
     """The mappable-length cache (handler/mappability.py:239-309) on every rank, None without a track: loaded when valid;
     otherwise computed ONCE, on rank 0, written atomically with ``save_mappability_stats``, and broadcast -- the other ranks
     neither recompute it per chromosome nor read a file that is being rewritten.  Not valid and not to be saved: computed all
     the same with ``unsaved``, else None (each calculator computes its own in the fused pass).  ``track``: the track's open
-    reader, or None for rank 0 to open one on the host."""
+    reader, or None for rank 0 to open one on the host.  ``mask``: the excluded regions whose positions are cut out of the
+    track first (``_resolve_mask``), with a cache of their own."""
     if s.mappability_path is None:
         return None
 
     def lengths():
         bw = track if track is not None else open_track(s.mappability_path, False)
         try:
-            ms = MappabilityStats(bw, s.max_shift, read_len, map_path=s.mappability_stats_path,
-                                  track_path=s.mappability_path, device=s.device, context=s.context)
+            feeder, map_path, masked = bw, s.mappability_stats_path, None
+            if mask is not None:    # the track less the regions, with a cache of its own (DESIGN.md 7.15)
+                from .region_mask import MaskedTrack, stats_path
+                feeder, masked = MaskedTrack(bw, mask, read_len), read_len
+                if map_path is None:
+                    map_path = stats_path(s.mappability_path, s.exclude_regions, getattr(bw, "k", None))
+            save = s.save_mappability_stats and (masked is None or map_path is not None)
+            ms = MappabilityStats(feeder, s.max_shift, read_len, map_path=map_path,
+                                  track_path=s.mappability_path, device=s.device, context=s.context, masked_read_len=masked)
             try:
                 if not ms.is_called:                        # no valid cache: the autocorrelation pass
-                    if not (s.save_mappability_stats or unsaved):
+                    if not (save or unsaved):
                         return None
                     ms.calc_mappability()
-                    if s.save_mappability_stats:
+                    if save:
                         ms.save_mappability_stats()
                 return ms.chrom2mappable_len
             finally:
@@ -188,14 +229,14 @@ def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool):
     return on_rank0(lengths, s.group, "mappability statistics")
 
 
-def _run_file(s: _Settings, path, read_len: int, known, bam, track):
+def _run_file(s: _Settings, path, read_len: int, known, bam, track, mask=None):
     """One file sharded over the ranks: (its genome-wide result, its _ComplexityCount or None).  ``known``: the lag tables of
     _mappable_lengths; ``bam`` / ``track``: the file's and the track's open readers, or None for run_sharded to open its own."""
     counted = _ComplexityCount(s) if s.complexity else None
     result = run_sharded(path, s.max_shift, read_len, s.mapq_criteria, bigwig_path=s.mappability_path,
                          references=s.references, skip_ncc=s.skip_ncc, device=s.device, chrom2mappable_len=known,
                          group=s.group, context=s.context, device_ingest=s.ingest, bam=bam, chromfilter=s.chromfilter,
-                         track=track, chrom_sizes=s.chrom_sizes,
+                         track=track, chrom_sizes=s.chrom_sizes, exclude_regions=mask if mask is not None else s.exclude_regions,
                          reader_hook=counted.hook if counted is not None and s.world == 1 else None)
     return result, counted
 
@@ -246,6 +287,8 @@ class _ComplexityCount:
         if self.value is None:
             with open_alignments(path, s.ingest, reader_device(s.context, s.device, s.ingest), chrom_sizes=s.chrom_sizes) as r:
                 names = kept_references(r.references, s.references, s.chromfilter)
+                if s.exclude_regions is not None:
+                    r.set_exclude(s.exclude_regions.resolve(r.references, r.lengths))
                 self.value = complexity.from_reader(r, int(s.mapq_criteria), names)
         return complexity.write_complexity(Path(s.outdir) / basename, basename, self.value)
 
@@ -265,7 +308,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
               library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
               chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None,
-              complexity: bool = False) -> List[FileResult]:
+              complexity: bool = False, exclude_regions=None) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -329,7 +372,23 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
         if mappability_path is not None:        # (a genome FASTA: its k-mer track with k = the read length)
             track = open_track(mappability_path, track_on_device(mappability_path, s.ingest, s.context),
                                getattr(s.context, "device", dev) if is_fasta(mappability_path) else dev, k=read_len)
-        known = _mappable_lengths(s, read_len, track, True)     # the lag tables of every file, computed once
+        # the excluded regions are bound to every file's references before the cache pass: a file none of whose references the
+        # mask names is skipped like a file that cannot be opened; the cache is cut with the first file's clipped intervals
+        masks = {}
+        for i in list(live):
+            try:
+                masks[i], kept_i = _resolve_mask(s, paths[i], kept.get(i))
+                if kept_i is not None:
+                    kept[i] = kept_i
+            except ValueError as e:
+                kept.pop(i, None)
+                logger.error("Failed to open file '{}'".format(paths[i]))
+                logger.error(str(e))
+                errors[i] = _portable(e)
+                live.remove(i)
+        if not live:
+            raise ValueError("no input file is left to run")
+        known = _mappable_lengths(s, read_len, track, True, masks[live[0]])     # the lag tables of every file, computed once
         logger.info("Calculate cross-correlation between 0 to {} base shift with reads MAPQ >= {}"
                     "".format(max_shift, mapq_criteria))
         results = {}
@@ -337,7 +396,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
             logger.info("Process {}".format(paths[i]))
             bam = kept.pop(i, None)
             try:
-                result, counted = _run_file(s, paths[i], read_len, known, bam, track)
+                result, counted = _run_file(s, paths[i], read_len, known, bam, track, masks[i])
             except Exception as e:
                 skip = _unsorted_on_every_rank(e, s.world)
                 if skip is None:

@@ -5,6 +5,8 @@ PyMaSC's calcmappablelen.py does: ``MappabilityStats`` computes the lag tables o
 is looked up with the host reader of the track (its header is all that takes); a valid cache that already covers the range
 is left as it is and no GPU is touched.  Otherwise the track is read by the device reader when there is a GPU.  ``-p`` is
 accepted and ignored: the lag tables come from one GPU.
+``--exclude-regions BED`` writes the cache of the masked track, ``<track>_<BED name>_mappability.json``, for reads of exactly
+``-r`` bases: the cleared positions depend on the read length.
 A genome FASTA (``kmer_track.is_fasta``) takes ``-r`` as the k of its k-mer track and needs it given: the default of 1000
 means nothing there (an argparse error, exit 2).  Its cache is ``<stem>_k<K>_mappability.json``; the names and lengths that
 check it come from ``<fasta>.fai`` or a scan of the header lines, so a valid cache costs no generation.
@@ -37,7 +39,9 @@ def get_parser() -> argparse.ArgumentParser:
         formatter_class=argparse.RawDescriptionHelpFormatter)
     cli.shared_options(parser)
     cli.ranks_option(parser.add_argument_group("how to run"))
-    cli.track_options(parser.add_argument_group("mappability"))
+    track = parser.add_argument_group("mappability")
+    cli.track_options(track)
+    cli.exclude_option(track)
     lags = parser.add_argument_group("lag range")
     cli.shift_option(lags)
     lags.add_argument("-r", "--max-readlen", type=int, default=1000, action=_Given,
@@ -54,6 +58,8 @@ def main(argv=None) -> int:
             parser.error("argument -m/--mappable: expected 1 argument(s)")
         if is_fasta(args.mappability) and not getattr(args, "max_readlen_given", False):
             parser.error("argument -r/--max-readlen: a genome FASTA needs it (the k of its k-mer track)")
+        if cli.missing_exclude_file(args):
+            parser.error(cli.missing_exclude_file(args))
     except SystemExit as e:         # --help, --version, argument errors
         return e.code if isinstance(e.code, int) else 2
     cli.setup_logging(args.log_level)
@@ -75,9 +81,24 @@ def main(argv=None) -> int:
         except (OSError, ValueError) as e:
             logger.critical("Cannot open the mappability track '{}': {}".format(track_path, e))
             return 1
-        stats = MappabilityStats(opened[0], max_shift=args.max_shift, readlen=args.max_readlen,
-                                 map_path=None if args.mappability_stats is None else str(args.mappability_stats),
-                                 track_path=track_path)
+        map_path = None if args.mappability_stats is None else str(args.mappability_stats)
+        mask_path = None if args.exclude_regions is None else str(args.exclude_regions)
+        masked = None if mask_path is None else args.max_readlen
+        if mask_path is not None and map_path is None:      # the masked track's own cache, never the unmasked one
+            from .region_mask import stats_path
+            map_path = str(stats_path(track_path, mask_path, args.max_readlen if fasta else None))
+        mask = []
+
+        def feeder(t):
+            """``t`` less the excluded regions, which are read when the first track needs them: a valid cache reads no mask."""
+            if mask_path is None:
+                return t
+            from .region_mask import MaskedTrack, open_mask
+            if not mask:
+                mask.append(open_mask(mask_path, inputs.default_device_ingest(1)))
+            return MaskedTrack(t, mask[0], masked)
+        stats = MappabilityStats(opened[0], max_shift=args.max_shift, readlen=args.max_readlen, map_path=map_path,
+                                 track_path=track_path, masked_read_len=masked)
         try:
             if not stats.is_called:             # no valid cache: the intervals are read on the GPU when there is one
                 if fasta:                       # the k-mer track, generated now (on the GPU when there is one)
@@ -94,6 +115,11 @@ def main(argv=None) -> int:
                         logger.critical("Cannot open the mappability track '{}' on the GPU: {}".format(track_path, e))
                         return 1
                     stats.feeder = opened[-1]
+                try:
+                    stats.feeder = feeder(stats.feeder)
+                except (OSError, ValueError) as e:
+                    logger.critical("Cannot read the excluded regions '{}': {}".format(mask_path, e))
+                    return 1
                 stats.calc_mappability()
             stats.save_mappability_stats()
         finally:

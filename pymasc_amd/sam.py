@@ -100,8 +100,9 @@ class SamReader(AlignmentReader):
                 batch: int = 1 << 22) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
         """Yields (ref_id, pos_1based, read_len, is_reverse) of the reads that pass the reference's filter, in file order."""
         total = self.decode(mapq_criteria, flag_exclude)
+        self._dropped = 0
         for first in range(0, total, batch):
-            yield self._fetch(first, min(batch, total - first))
+            yield self._drop_excluded(*self._fetch(first, min(batch, total - first)))
 
     def fetch(self, reference: str, *args, **kwargs):
         raise ValueError("fetch() needs an index: {} is a SAM file".format(self.path))

@@ -213,7 +213,7 @@ def reconcile_chromosome_sizes(bam_sizes: Dict[str, int], external_sizes: Dict[s
 def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, bigwig_path=None,
                 references: Sequence[str] = None, skip_ncc: bool = False, device: int = None, context=None,
                 chrom2mappable_len=None, group=None, device_ingest: Optional[bool] = None, bam=None, chromfilter=None,
-                track=None, chrom_sizes=None, reader_hook=None):
+                track=None, chrom_sizes=None, reader_hook=None, exclude_regions=None):
     """BAM (+ BigWig) -> genome-wide result on every rank; chromosomes LPT-sharded over the ranks by length.
 
     Launch: one process per GPU under ``torch.distributed`` (torchrun, or pymasc_amd.launch.spawn_ranks), the process
@@ -246,7 +246,13 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
     before this returns (``CCHipCalculator.close`` never closes a context it does not own).
     ``reader_hook``: ``reader_hook(reader, names)`` is called with the open alignment reader and this rank's chromosomes just
     before they are fed; what it returns, when not None, is called without arguments once the feed has succeeded, while the
-    reader is still open (pipeline.run counts the library complexity there: the file is inflated once)."""
+    reader is still open (pipeline.run counts the library complexity there: the file is inflated once).
+    ``exclude_regions``: a BED file, an ordered ``{name: [(start, end), ...]}``, a ``region_mask.ExcludeMask`` or a ``ResolvedMask``
+    of this file's references:
+    the reads that overlap a region are left out by the reader (``set_exclude``, attached before ``reader_hook``; on the GPU with
+    the device reader) and every chromosome's mappability vector is cleared where a read of ``read_len`` would touch one.  Names
+    that are not references are skipped with one warning; none matching is a ValueError.  The count of the reads left out is
+    logged at INFO.  A caller's ``bam`` reader keeps the mask afterwards."""
     from .calculator import CCHipCalculator
     from .chromfilter import kept_references
     from .inputs import (check_bed_sizes, default_device_ingest, find_index, open_alignments, open_track, reader_device,
@@ -283,6 +289,14 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
             reader = open_alignments(bam_path, device_ingest, dev, references=[] if indexed else None, chrom_sizes=chrom_sizes)
         names = kept_references(reader.references, references, chromfilter)
         lengths = dict(zip(reader.references, reader.lengths))
+        mask = None
+        if exclude_regions is not None:
+            from .region_mask import ResolvedMask, open_mask
+            mask = exclude_regions      # (resolved by the caller against this file's header: taken as it is)
+            if not (isinstance(mask, ResolvedMask) and mask.references == tuple(reader.references)):
+                mask = getattr(mask, "mask", mask)
+                mask = open_mask(mask, device_ingest, dev).resolve(reader.references, reader.lengths)
+            reader.set_exclude(mask)
         if bigwig_path is not None:     # with device ingest the track is decoded on the GPU too: its intervals stay in HBM
             if track is None:           # (a genome FASTA: on this rank's GPU whenever it has one)
                 gpu_track = track_on_device(bigwig_path, device_ingest, context)
@@ -306,11 +320,14 @@ def run_sharded(bam_path, max_shift: int, read_len: int, mapq_criteria: int, big
             kw["device"] = device
         if mine:
             calc = CCHipCalculator(max_shift, read_len, mine, [lengths[n] for n in mine], bwfeeder=bw,
-                                   skip_ncc=skip_ncc, chrom2mappable_len=chrom2mappable_len, **kw)
+                                   skip_ncc=skip_ncc, chrom2mappable_len=chrom2mappable_len, exclude=mask, **kw)
             try:
                 after_feed = reader_hook(reader, mine) if reader_hook is not None else None
                 reader.feed(calc, mapq_criteria, references=mine)
                 local = {c: calc.get_result(c) for c in mine}
+                if mask is not None:
+                    import logging
+                    logging.getLogger(__name__).info("Excluded regions: {} reads of '{}' left out.".format(reader.excluded(), bam_path))
                 if after_feed is not None:
                     after_feed()
             finally:

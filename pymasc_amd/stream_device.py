@@ -104,6 +104,8 @@ class DeviceStreamReader(DeviceBamReader):
             self._h = None
             self._h = self._open()
             self._selected = selected
+            if self._exclude is not None:       # (the mask belongs to the handle: attached again)
+                self.set_exclude(self._exclude)
         self._consumed = True
         while True:
             n = self._L.pmx_dbam_stream_next(self._h)
@@ -171,6 +173,7 @@ class DeviceStreamReader(DeviceBamReader):
         on_device = hasattr(calculator, "feed_reads_device")
         ctx = getattr(calculator, "_ctx", None)
         fed = 0
+        self._dropped = 0
         for _ in self._windows():
             total = self.decode(mapq_criteria)
             if total == 0:
@@ -204,6 +207,7 @@ class DeviceStreamReader(DeviceBamReader):
         """``DeviceBamReader.batches`` per window: (ref_id, pos_1based, read_len, is_reverse) of the reads that pass the
         reference's filter, in stream order, at most ``batch`` per round."""
         keep = self._keep_mask()
+        self._dropped = 0
         for _ in self._windows():
             total = self.decode(mapq_criteria, flag_exclude, _reference)
             for first in range(0, total, batch):

@@ -486,6 +486,43 @@ def time_bed_reads(path, sizes, mapq, reps=3, host=True):
     return out
 
 
+def time_region_mask(path, refs, mapq, nmask, reps, seed=17):
+    """Open + decode + feed of the device reader with and without a mask of ``nmask`` random regions of 0.5-20 kb laid over the
+    references in proportion to their length: seconds of every repetition, the medians, the reads dropped."""
+    from pymasc_amd import bam_device as D
+    from pymasc_amd import region_mask
+    from pymasc_amd.calculator import CCHipCalculator
+    rng = np.random.default_rng(seed)
+    total = sum(l for _n, l in refs)
+    lines = {}
+    for name, length in refs:
+        k = max(1, round(nmask * length / total))
+        b = rng.integers(0, max(length - 20000, 1), k)
+        lines[name] = list(zip(b.tolist(), (b + rng.integers(500, 20000, k)).tolist()))
+    mask = region_mask.open_mask(lines)
+    out = {"regions": sum(len(v) for v in lines.values()), "unmasked_s": [], "masked_s": []}
+    for rep in range(reps + 1):             # (the first pair warms up: pinned staging buffers, code objects)
+        for key in ("unmasked_s", "masked_s"):
+            calc = CCHipCalculator(1000, 36, [n for n, _ in refs], [l for _, l in refs])
+            t0 = time.time()
+            with D.DeviceBamReader(path) as r:
+                if key == "masked_s":
+                    r.set_exclude(mask.resolve(r.references, r.lengths))
+                fed = r.feed(calc, mapq)
+                dropped = r.excluded()
+            dt = time.time() - t0
+            calc.close()
+            if rep:
+                out[key].append(round(dt, 4))
+                out["fed_" + key[:-2]] = fed
+                out["dropped_" + key[:-2]] = dropped
+    out["unmasked_median_s"] = float(np.median(out["unmasked_s"]))
+    out["masked_median_s"] = float(np.median(out["masked_s"]))
+    out["masked_over_unmasked"] = round(out["masked_median_s"] / out["unmasked_median_s"], 4)
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=5_000_000)
@@ -511,6 +548,9 @@ def main():
     ap.add_argument("--bed-only", default=None, help="--bed: time only ORDER-COMP (e.g. shuffled-none), on the device only")
     ap.add_argument("--bigbed", action="store_true",
                     help="time a bigBed track of about --lines BED6 records: host reader against device reader (DESIGN.md 7.12)")
+    ap.add_argument("--mask", type=int, default=0, metavar="N",
+                    help="time open + decode + feed of the device reader with and without N random excluded regions "
+                         "(--exclude-regions, DESIGN.md 7.15), --reps times each on the same file, and nothing else")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -577,6 +617,13 @@ def main():
 
     refs, gen_s = synth_bam(a.path, a.reads, chroms=a.chroms, index=a.subsets)
     res = {"reads": a.reads, "bam_bytes": os.path.getsize(a.path), "generate_s": round(gen_s, 1), "reader": []}
+    if a.mask:
+        res["region_mask"] = time_region_mask(a.path, refs, a.mapq, a.mask, a.reps)
+        if a.out:
+            with open(a.out, "w") as fp:
+                json.dump(res, fp, indent=1)
+        os.unlink(a.path)
+        return
     for t in a.threads:
         if t <= (os.cpu_count() or 1):
             res["reader"].append(time_reader(a.path, t, a.mapq))
