@@ -178,6 +178,34 @@ int64_t pmx_dbam_exclude_intervals(pmx_dbam *b, int64_t cap, int32_t *ref_id, ui
 /* *dropped = records the last pmx_dbam_decode left out because of the mask; *intervals = merged intervals attached. */
 int pmx_dbam_excluded(const pmx_dbam *b, uint64_t *dropped, uint64_t *intervals);
 
+/* Read counts per genome bin (version >= 11): the table behind the fingerprint and the Jensen-Shannon distance.
+ * A chosen reference of length len has floor(len / bin_size) bins; bin j (0-based) covers the 1-based positions
+ * j * bin_size + 1 .. (j + 1) * bin_size, the tail shorter than a bin has none; the chosen references' bins lie end to end in
+ * header order.  A read covers [pos1, pos1 + L - 1] when forward and [pos1 + read_len - L, pos1 + read_len - 1] when reverse (its
+ * 5' end stays put), with L = extend, or read_len when extend is 0; the extent is clipped to [1, len] and the read adds 1 to every
+ * bin it overlaps.
+ * pmx_dbam_bincount_begin allocates one zeroed uint32 per bin and 16 bytes per reference in device memory (part of
+ * pmx_dbam_stream_info's peak); they replace any earlier table and stay until the next begin or close.  use_ref: nref bytes, 0 =
+ * the reference has no bins; NULL = every reference.  bin_size 0, no bin at all, or 2^31 bins or more: PMX_DBAM_ERR_INVALID.
+ * pmx_dbam_bincount_add counts what the handle holds now -- the whole file, the selection of an indexed handle, the current
+ * window of a stream -- at mapq_min / flag_exclude (the filter of pmx_dbam_decode), less the reads an attached mask leaves out:
+ * the walk + filter of pmx_dbam_complexity, with arrays of its own (13 bytes per kept read, freed before the call returns), so
+ * the arrays, counters and runs of the last pmx_dbam_decode are left as they are.  Calls add up in the table: a stream is
+ * counted by one call per window (a read is counted in the window that decodes it, so nothing is held back and no order is
+ * asked for), and a second call on the same records doubles every bin.  *reads_added = the reads of this call that added to at
+ * least one bin.
+ * pmx_dbam_bincount_hist: hist[k] = bins that hold exactly k reads, for k < PMX_BINCOUNT_HIST; totals = {bins, the sum of all
+ * bins, reads that added to a bin since begin}.  The values of the bins at or above PMX_BINCOUNT_HIST come in `tail`, in any
+ * order (two-call protocol like pmx_dbam_runs: tail == NULL returns their number, else up to cap are written and their number
+ * is returned; hist and totals are filled by both calls).  The table is not cleared.
+ * pmx_dbam_bincount_copy: the bins [first, first + n) copied to the host.
+ * add / hist / copy before begin, a NULL output, and a range outside the table: PMX_DBAM_ERR_INVALID. */
+#define PMX_BINCOUNT_HIST 4096
+int pmx_dbam_bincount_begin(pmx_dbam *b, uint32_t bin_size, uint32_t extend, const uint8_t *use_ref);
+int pmx_dbam_bincount_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t *reads_added);
+int64_t pmx_dbam_bincount_hist(pmx_dbam *b, uint64_t hist[PMX_BINCOUNT_HIST], uint64_t totals[3], int64_t cap, uint32_t *tail);
+int pmx_dbam_bincount_copy(pmx_dbam *b, int64_t first, int64_t n, uint32_t *counts);
+
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
  * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong.  An indexed
  * handle: bytes_out is the length of its stream (header + selected records), bytes_in and members count only the members

@@ -210,6 +210,17 @@ def get_parser() -> argparse.ArgumentParser:
                      help="also write <name>_complexity.tab for every file: the library complexity NRF, PBC1 and PBC2 (ENCODE) of "
                           "the reads at -q on the chosen chromosomes, flagged duplicates kept, counted per "
                           "(chromosome, position, read length, strand), with per-chromosome counts and the multiplicity histogram")
+    out.add_argument("--fingerprint", action="store_true",
+                     help="also write <name>_fingerprint.tab for every file: the reads the correlation sees counted per genome bin, "
+                          "the fingerprint's AUC, X-intercept and elbow, the Jensen-Shannon distance to a Poisson model, and the "
+                          "number of bins at every count")
+    out.add_argument("--fingerprint-bin", metavar="N", type=int, action=_NaturalNumber,
+                     help="width of the genome bins, in bases (default 500); implies --fingerprint")
+    out.add_argument("--fingerprint-extend", metavar="N", type=int, action=_NaturalNumber,
+                     help="count every read as N bases from its 5' end instead of its own length; implies --fingerprint")
+    out.add_argument("--fingerprint-control", metavar="FILE", type=Path,
+                     help="an alignment file (a control / input sample) counted the same way: the table then holds the "
+                          "Jensen-Shannon distance between the two; implies --fingerprint")
     return parser
 
 
@@ -249,6 +260,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("argument --chrom-sizes: no such file: '{}'".format(args.chrom_sizes))
     if missing_exclude_file(args):
         parser.error(missing_exclude_file(args))
+    if args.fingerprint_control is not None and not os.path.isfile(args.fingerprint_control):
+        parser.error("argument --fingerprint-control: no such file: '{}'".format(args.fingerprint_control))
+    if args.fingerprint_bin is not None or args.fingerprint_extend is not None or args.fingerprint_control is not None:
+        args.fingerprint = True
     if args.chrom_sizes is None:
         from .bed_reads import is_bed_reads     # (no torch, no native library)
         bed = [str(p) for p in args.reads if is_bed_reads(p)]
@@ -331,6 +346,12 @@ def _run(args, device, rank: int) -> int:
         extra["complexity"] = True
     if args.exclude_regions is not None:
         extra["exclude_regions"] = str(args.exclude_regions)
+    if args.fingerprint:
+        extra["fingerprint"] = True
+        for key, value in (("fingerprint_bin", args.fingerprint_bin), ("fingerprint_extend", args.fingerprint_extend),
+                           ("fingerprint_control", args.fingerprint_control)):
+            if value is not None:
+                extra[key] = str(value) if key == "fingerprint_control" else value
     try:
         results = pipeline.run_files(
             [str(p) for p in args.reads], str(args.outdir), args.max_shift, read_len=args.read_length,

@@ -1231,6 +1231,11 @@ struct pmx_dbam {
     u64 x_n = 0, x_dropped = 0;      // merged intervals; reads the last decode left out because of them
     u8 *d_xs = nullptr;              // the filter's scratch block (flags, block counts, compacted fields), grown, never shrunk
     u64 xs_cap = 0;
+    // read counts per genome bin (pmx_dbam_bincount_*, bincount_device.inc): from begin to the next begin or close
+    u32 *d_bc = nullptr;             // one count per bin, the chosen references' bins end to end in header order
+    long long *d_bc_tab = nullptr;   // per reference: its first bin (-1: not chosen), its number of bins
+    u64 bc_bins = 0, bc_reads = 0;   // bins; reads that added to a bin since begin
+    u32 bc_bin = 0, bc_ext = 0;      // bin size, extend
 };
 
 namespace {
@@ -1779,7 +1784,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 10; }
+int pmx_dbam_version(void) { return 11; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1850,6 +1855,8 @@ void pmx_dbam_close(pmx_dbam *b)
     if (b->d_xkey) (void)hipFree(b->d_xkey);
     if (b->d_xend) (void)hipFree(b->d_xend);
     if (b->d_xs) (void)hipFree(b->d_xs);
+    if (b->d_bc) (void)hipFree(b->d_bc);
+    if (b->d_bc_tab) (void)hipFree(b->d_bc_tab);
     for (void *p : {(void *)b->d_nl, (void *)b->d_ls, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
         if (p) (void)hipFree(p);
     for (hipStream_t x : b->kmore)
@@ -2563,4 +2570,5 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "bed_reads_device.inc"
 #include "kmer_track_device.inc"
 #include "complexity_device.inc"
+#include "bincount_device.inc"
 #include "region_mask_device.inc"

@@ -208,6 +208,7 @@ void cx_drop_held(StreamState *s)
 }
 
 // The records of the current stream that pass the filter, behind `front` held-back ones, into R (arrays of this call).
+// Also the front half of pmx_dbam_bincount_add (bincount_device.inc), with front = 0.
 int cx_filter(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, u64 front, bool current, CxRecs &R)
 {
     hipStream_t st = b->stream;

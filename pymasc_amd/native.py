@@ -20,6 +20,7 @@ PMX_BAM_FLAG_READ2 = 0x80
 PMX_BAM_FLAG_DUPLICATE = 0x400
 PMX_BAM_DEFAULT_EXCLUDE = PMX_BAM_FLAG_READ2 | PMX_BAM_FLAG_UNMAPPED | PMX_BAM_FLAG_DUPLICATE
 PMX_COMPLEXITY_BINS = 32        # (include/pymasc_amd_ingest.h)
+PMX_BINCOUNT_HIST = 4096
 PMX_IO_ERR_NOTFOUND = -4        # (PMX_DBAM_ERR_NOTFOUND has the same value)
 TRACK_KINDS = ("bigwig", "bigbed", "kmer")      # pmx_track_kind / pmx_dbw_kind
 
@@ -116,6 +117,10 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_device_arrays": (_int, [_vp] + [_out] * 4),
     "pmx_dbam_runs": (_i64, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "pmx_dbam_complexity": (_int, [_vp, _u32, _u32, _vp, _vp, _vp]),
+    "pmx_dbam_bincount_begin": (_int, [_vp, _u32, _u32, _vp]),
+    "pmx_dbam_bincount_add": (_int, [_vp, _u32, _u32, _pu64]),
+    "pmx_dbam_bincount_hist": (_i64, [_vp, _vp, _vp, _i64, _vp]),
+    "pmx_dbam_bincount_copy": (_int, [_vp, _i64, _i64, _vp]),
     "pmx_dbam_set_exclude": (_int, [_vp, _i32, _vp, _vp, _vp]),
     "pmx_dbam_exclude_intervals": (_i64, [_vp, _i64, _vp, _vp, _vp]),
     "pmx_dbam_excluded": (_int, [_vp, _pu64, _pu64]),
@@ -264,6 +269,15 @@ class AlignmentReader(NativeReader):
         from .complexity import from_reader
         self._check_open()
         return from_reader(self, mapq_criteria, references)
+
+    def bin_counts(self, mapq_criteria: int = 0, references=None, bin_size: int = 500, extend: int = 0):
+        """The reads at ``mapq_criteria`` (flagged duplicates, read2 and unmapped reads dropped) counted per genome bin of
+        ``bin_size`` bases over ``references`` (None: all the reader has selected): a ``pymasc_amd.fingerprint.BinCounts``
+        (``fingerprint.from_reader``).  ``extend``: every read covers that many bases from its 5' end (0: its own
+        length).  A device reader counts on the GPU with arrays of its own: the arrays of the last ``decode`` stay as they are."""
+        from .fingerprint import from_reader
+        self._check_open()
+        return from_reader(self, mapq_criteria, references, bin_size, extend)
 
     # ---- excluded regions (pymasc_amd.region_mask; DESIGN.md 7.15) ----
     _exclude = None

@@ -37,7 +37,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         device: Optional[int] = None, save_mappability_stats: bool = True, group=None, context=None,
         device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
         library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
-        chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None):
+        chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None,
+        fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -66,7 +67,14 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     track is cleared where a read of the run's length would touch a region, ``complexity`` counts the reads that are left, and the
     mappable-length cache is ``<track stem>_<mask file stem>_mappability.json`` (a dict: none) unless ``mappability_stats_path``
     names it.  The read length is still estimated over the whole file.  No region's chromosome among the references: ValueError
-    before any table is written."""
+    before any table is written.
+    ``fingerprint``: rank 0 also writes ``<stem>_fingerprint.tab`` (pymasc_amd.fingerprint): the reads the
+    correlation sees -- ``mapq_criteria``, flagged duplicates dropped, the chosen chromosomes, less the excluded regions -- counted
+    per genome bin of ``fingerprint_bin`` bases, each read covering ``fingerprint_extend`` bases from its 5' end (0: its own
+    length); the table holds the fingerprint's AUC, X-intercept and elbow, the Jensen-Shannon distance to a Poisson model and the
+    number of bins at every count.  Counted where ``complexity`` is counted.  ``fingerprint_control``: an alignment file counted
+    the same way (once per call, never correlated), with the Jensen-Shannon distance to it in the table; it turns
+    ``fingerprint`` on.  Its chosen references must have the sample's names and lengths: ValueError before the run."""
     check_bed_sizes(bam_path, chrom_sizes)
     s = _settings(locals())
     from .kmer_track import is_fasta
@@ -80,6 +88,10 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
             track = open_track(mappability_path, track_on_device(mappability_path, False, context),
                                reader_device(context, s.device), k=read_len)
         mask, bam = _resolve_mask(s, bam_path, bam)     # (no name in common: ValueError before the cache pass and any table)
+        if s.fingerprint_control is not None:
+            if bam is None and is_stream(bam_path) and s.estimate_gpu is not None:      # (no header to read apart, as above)
+                bam = open_alignments(bam_path, True, device=s.estimate_gpu)
+            s.fingerprint_control.check(s, bam_path, bam)
         known = _mappable_lengths(s, read_len, track, False, mask)
         result, counted = _run_file(s, bam_path, read_len, known, bam, track, mask)
     finally:
@@ -113,6 +125,10 @@ class _Settings:
     chrom_sizes: object
     complexity: bool
     exclude_regions: object         # None, or the region_mask.ExcludeMask read once for the call
+    fingerprint: bool
+    fingerprint_bin: int
+    fingerprint_extend: int
+    fingerprint_control: object     # None, or the _FingerprintControl counted once for the call
     save_mappability_stats: bool
     device: int
     ingest: bool
@@ -146,6 +162,12 @@ def _settings(kw: dict) -> _Settings:
     if kw.get("exclude_regions") is not None:      # read once (on the GPU with device ingest); each file resolves the names
         from .region_mask import open_mask
         given["exclude_regions"] = open_mask(kw["exclude_regions"], bool(ingest), reader_device(kw["context"], device, bool(ingest)))
+    if int(kw["fingerprint_bin"]) < 1 or int(kw["fingerprint_extend"]) < 0:
+        raise ValueError("fingerprint_bin is at least 1 and fingerprint_extend at least 0")
+    control = kw["fingerprint_control"]
+    given.update(fingerprint=bool(kw["fingerprint"]) or control is not None, fingerprint_bin=int(kw["fingerprint_bin"]),
+                 fingerprint_extend=int(kw["fingerprint_extend"]),
+                 fingerprint_control=None if control is None else _FingerprintControl(control))
     given.update(device=device, ingest=bool(ingest), rank=rank, world=world,
                  stat_opts={k: kw[k] for k in _STAT_OPTS} if kw["stats"] else None)
     return _Settings(**given)
@@ -230,20 +252,36 @@ def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool, mask=No
 
 
 def _run_file(s: _Settings, path, read_len: int, known, bam, track, mask=None):
-    """One file sharded over the ranks: (its genome-wide result, its _ComplexityCount or None).  ``known``: the lag tables of
-    _mappable_lengths; ``bam`` / ``track``: the file's and the track's open readers, or None for run_sharded to open its own."""
-    counted = _ComplexityCount(s) if s.complexity else None
+    """One file sharded over the ranks: (its genome-wide result, the counts taken beside it: a _ComplexityCount and a
+    _FingerprintCount as asked for).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's and the
+    track's open readers, or None for run_sharded to open its own.  One rank: run_sharded's one ``reader_hook`` serves every
+    count (``_hooks``)."""
+    counted = [c(s) for c, on in ((_ComplexityCount, s.complexity), (_FingerprintCount, s.fingerprint)) if on]
     result = run_sharded(path, s.max_shift, read_len, s.mapq_criteria, bigwig_path=s.mappability_path,
                          references=s.references, skip_ncc=s.skip_ncc, device=s.device, chrom2mappable_len=known,
                          group=s.group, context=s.context, device_ingest=s.ingest, bam=bam, chromfilter=s.chromfilter,
                          track=track, chrom_sizes=s.chrom_sizes, exclude_regions=mask if mask is not None else s.exclude_regions,
-                         reader_hook=counted.hook if counted is not None and s.world == 1 else None)
+                         reader_hook=_hooks([c.hook for c in counted]) if counted and s.world == 1 else None)
     return result, counted
+
+
+def _hooks(hooks):
+    """One ``reader_hook`` of run_sharded out of several: each is called before the feed, and what they return after it, in order."""
+    def hook(reader, names):
+        after = [h(reader, names) for h in hooks]
+
+        def after_feed():
+            for a in after:
+                if a is not None:
+                    a()
+        return after_feed
+    return hook
 
 
 def _write_file(s: _Settings, path, basename: str, result, read_len: int, counted) -> List[Path]:
     """Rank 0's part after _run_file: ``outdir/<basename>_{cc,mscc,nreads}.tab``, with ``stat_opts`` ``<basename>_stats.tab``
-    whose Name row is ``basename``, with ``counted`` ``<basename>_complexity.tab``; the paths written."""
+    whose Name row is ``basename``, and the table of every count in ``counted`` (``<basename>_complexity.tab``,
+    ``<basename>_fingerprint.tab``); the paths written."""
     out = Path(s.outdir)
     out.mkdir(parents=True, exist_ok=True)
     # write_tables names the tables after the stem of its path (table.py:185-188): a suffix keeps a dotted base name whole
@@ -251,8 +289,8 @@ def _write_file(s: _Settings, path, basename: str, result, read_len: int, counte
     if s.stat_opts is not None:     # every rank holds the same result: the statistics are rank 0's alone
         from . import stats
         written.append(stats.write_stats(out / basename, stats.genome_wide_stats(result, read_len, **s.stat_opts)))
-    if counted is not None:
-        written.append(counted.write(path, basename))
+    for c in counted:
+        written.append(c.write(path, basename))
     return written
 
 
@@ -285,12 +323,95 @@ class _ComplexityCount:
         from . import complexity
         s = self.s
         if self.value is None:
-            with open_alignments(path, s.ingest, reader_device(s.context, s.device, s.ingest), chrom_sizes=s.chrom_sizes) as r:
-                names = kept_references(r.references, s.references, s.chromfilter)
-                if s.exclude_regions is not None:
-                    r.set_exclude(s.exclude_regions.resolve(r.references, r.lengths))
-                self.value = complexity.from_reader(r, int(s.mapq_criteria), names)
+            self.value = _count_again(s, path, lambda r, names: complexity.from_reader(r, int(s.mapq_criteria), names))
         return complexity.write_complexity(Path(s.outdir) / basename, basename, self.value)
+
+
+def _count_again(s: _Settings, path, count):
+    """``count(reader, names)`` on one more read of ``path`` through the reader ``inputs.open_alignments`` gives this run, with
+    the run's chosen chromosomes and excluded regions (several ranks: rank 0 counts alone and no collective is added)."""
+    with open_alignments(path, s.ingest, reader_device(s.context, s.device, s.ingest), chrom_sizes=s.chrom_sizes) as r:
+        names = kept_references(r.references, s.references, s.chromfilter)
+        if s.exclude_regions is not None:
+            r.set_exclude(s.exclude_regions.resolve(r.references, r.lengths))
+        return count(r, names)
+
+
+class _FingerprintCount:
+    """The bin counts of one file's run (pymasc_amd.fingerprint), taken where _ComplexityCount takes its own: ``hook`` on the
+    reader that feeds the run (a stream: armed before the feed, every window added), ``write`` on one more read when there is
+    no count so far."""
+
+    def __init__(self, s: _Settings):
+        self.s = s
+        self.value = None
+
+    def _args(self, names):
+        return int(self.s.mapq_criteria), names, self.s.fingerprint_bin, self.s.fingerprint_extend
+
+    def hook(self, reader, names):
+        from . import fingerprint
+        if hasattr(reader, "arm_fingerprint"):
+            acc = reader.arm_fingerprint(*self._args(names))
+
+            def after():
+                try:
+                    self.value = acc.result(reader)
+                finally:
+                    reader.disarm_fingerprint()
+            return after
+
+        def after():
+            self.value = fingerprint.from_reader(reader, *self._args(names))
+        return after
+
+    def write(self, path, basename: str) -> Path:
+        from . import fingerprint
+        s = self.s
+        if self.value is None:
+            self.value = _count_again(s, path, lambda r, names: fingerprint.from_reader(r, *self._args(names)))
+        control = s.fingerprint_control
+        return fingerprint.write_fingerprint(Path(s.outdir) / basename, basename, self.value,
+                                             None if control is None else control.counts(s), "" if control is None else control.path)
+
+
+class _FingerprintControl:
+    """``fingerprint_control``: the control file of a call's fingerprints.  ``check`` compares its chosen references with a
+    sample's from the headers alone; ``counts`` is its table, counted once per call (by rank 0, when the first table is written)
+    with the run's ``mapq_criteria``, chromosome filter, excluded regions and ``chrom_sizes``.  It is never correlated."""
+
+    def __init__(self, path):
+        self.path = os.fspath(path)
+        self._chosen = None
+        self._counts = None
+
+    def _chosen_of(self, s: _Settings, header):
+        names = set(kept_references(header.references, s.references, s.chromfilter))
+        return [(n, int(l)) for n, l in zip(header.references, header.lengths) if n in names]
+
+    def check(self, s: _Settings, path, reader=None) -> None:
+        """ValueError unless the chosen references of ``path`` (``reader``: its open reader, else its header is read) have the
+        names and lengths of the control's."""
+        if self._chosen is None:
+            with open_header(self.path, s.chrom_sizes) as h:
+                self._chosen = self._chosen_of(s, h)
+        if reader is not None:
+            mine = self._chosen_of(s, reader)
+        elif is_stream(path):       # (no device reader to read it: run_sharded says so)
+            return
+        else:
+            with open_header(path, s.chrom_sizes) as h:
+                mine = self._chosen_of(s, h)
+        if mine != self._chosen:
+            raise ValueError("the chosen references of the fingerprint control '{}' differ from those of '{}' in name or length"
+                             "".format(self.path, path))
+
+    def counts(self, s: _Settings):
+        from . import fingerprint
+        if self._counts is None:
+            self._counts = _count_again(s, self.path, lambda r, names: fingerprint.from_reader(
+                r, int(s.mapq_criteria), names, s.fingerprint_bin, s.fingerprint_extend))
+        return self._counts
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -308,7 +429,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
               library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
               chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None,
-              complexity: bool = False, exclude_regions=None) -> List[FileResult]:
+              complexity: bool = False, exclude_regions=None, fingerprint: bool = False, fingerprint_bin: int = 500,
+              fingerprint_extend: int = 0, fingerprint_control=None) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -395,6 +517,16 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
         for i in live:
             logger.info("Process {}".format(paths[i]))
             bam = kept.pop(i, None)
+            if s.fingerprint_control is not None:   # (from the headers, the same on every rank: skipped like a file that does not open)
+                try:
+                    s.fingerprint_control.check(s, paths[i], bam)
+                except ValueError as e:
+                    if bam is not None:
+                        bam.close()
+                    logger.error("Failed to open file '{}'".format(paths[i]))
+                    logger.error(str(e))
+                    errors[i] = _portable(e)
+                    continue
             try:
                 result, counted = _run_file(s, paths[i], read_len, known, bam, track, masks[i])
             except Exception as e:
@@ -445,7 +577,8 @@ def _warn_existing(s: _Settings, bases):
     """prepare_output's warning (pymasc.py:178-182) for every output about to be replaced."""
     has_track = s.mappability_path is not None
     suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
-                                ("_stats.tab", s.stat_opts is not None), ("_complexity.tab", s.complexity)) if on]
+                                ("_stats.tab", s.stat_opts is not None), ("_complexity.tab", s.complexity),
+                                ("_fingerprint.tab", s.fingerprint)) if on]
     for b in bases:
         for suffix in suffixes:
             path = Path(s.outdir) / (b + suffix)

@@ -106,6 +106,8 @@ class DeviceStreamReader(DeviceBamReader):
             self._selected = selected
             if self._exclude is not None:       # (the mask belongs to the handle: attached again)
                 self.set_exclude(self._exclude)
+            if self._fingerprint is not None:   # (so does the table of bins)
+                self._fingerprint.begin(self)
         self._consumed = True
         while True:
             n = self._L.pmx_dbam_stream_next(self._h)
@@ -118,6 +120,8 @@ class DeviceStreamReader(DeviceBamReader):
             yield int(n)
             if self._complexity is not None:        # the caller is done with the window: its arrays stay as they are
                 self._complexity.count(self)
+            if self._fingerprint is not None:
+                self._fingerprint.add(self)
 
     _complexity = None
 
@@ -132,6 +136,20 @@ class DeviceStreamReader(DeviceBamReader):
 
     def disarm_complexity(self) -> None:
         self._complexity = None
+
+    _fingerprint = None
+
+    def arm_fingerprint(self, mapq_criteria: int = 0, references=None, bin_size: int = 500, extend: int = 0):
+        """From now on every window a pass makes current is also counted per genome bin (``pmx_dbam_bincount_add``, into the
+        table ``pmx_dbam_bincount_begin`` allocates here); returns the ``pymasc_amd.fingerprint.DeviceCount`` whose
+        ``result(reader)`` is the whole stream's once the pass has ended.  A read is counted in the window that decodes it, so
+        nothing is held back and the stream need not be sorted."""
+        from .fingerprint import DeviceCount
+        self._fingerprint = DeviceCount(self, mapq_criteria, references, bin_size, extend)
+        return self._fingerprint
+
+    def disarm_fingerprint(self) -> None:
+        self._fingerprint = None
 
     def _keep_mask(self):
         if len(self._selected) == len(self.references):
