@@ -206,6 +206,29 @@ int pmx_dbam_bincount_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude,
 int64_t pmx_dbam_bincount_hist(pmx_dbam *b, uint64_t hist[PMX_BINCOUNT_HIST], uint64_t totals[3], int64_t cap, uint32_t *tail);
 int pmx_dbam_bincount_copy(pmx_dbam *b, int64_t first, int64_t n, uint32_t *counts);
 
+/* Reads per peak line and reads in peaks (version >= 12): FRiP's counts.  The lines come per reference as for
+ * pmx_dbam_set_exclude (offsets[nref + 1] in host memory; begin[] / end[] 0-based, half-open, in host OR device memory), in any
+ * order, overlapping, nested, abutting or repeated, and EVERY line keeps a count of its own.  A line is clipped to its reference's
+ * length; one that is empty then stays in the table with the count 0.  A read's extent is pmx_dbam_bincount's with `extend`,
+ * clipped to [1, len]: [lo, hi].  The read is IN the line (b, e) when b + 1 <= hi and lo <= e.
+ * pmx_dbam_peakcount_begin clips, sorts and scans the lines on the device with the mask's kernels and keeps, per line, the sorted
+ * key, the clipped end, the running maximum of the ends, the input place and one zeroed uint32 (28 bytes per line, part of
+ * pmx_dbam_stream_info's peak); they replace any earlier table and stay until the next begin or close.  use_ref: nref bytes, 0 =
+ * reads of that reference are not counted and its lines add nothing to the union; NULL = every reference.
+ * pmx_dbam_peakcount_add counts what the handle holds now -- the whole file, the selection of an indexed handle, the current
+ * window of a stream -- through the walk + filter of pmx_dbam_bincount_add (arrays of its own, an attached mask applied); calls
+ * add up.  out = {reads counted, reads in at least one line} of this call; a read on a chosen reference is counted whether or not
+ * it touches a line.
+ * pmx_dbam_peakcount_copy: the counts of the lines [first, first + n) in INPUT order.
+ * pmx_dbam_peakcount_totals: totals = {reads counted, reads in at least one line, bases of the clipped, merged lines on chosen
+ * references, lines} since begin; per_ref[2 * r + {0, 1}] = the first two for reference r (2 * nref values).
+ * add / copy / totals before begin, a NULL output, and a range outside the table: PMX_DBAM_ERR_INVALID. */
+int pmx_dbam_peakcount_begin(pmx_dbam *b, int32_t nref, const int64_t *offsets, const uint32_t *begin, const uint32_t *end,
+                             uint32_t extend, const uint8_t *use_ref);
+int pmx_dbam_peakcount_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t out[2]);
+int pmx_dbam_peakcount_copy(pmx_dbam *b, int64_t first, int64_t n, uint32_t *counts);
+int pmx_dbam_peakcount_totals(pmx_dbam *b, uint64_t totals[4], uint64_t *per_ref);
+
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
  * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong.  An indexed
  * handle: bytes_out is the length of its stream (header + selected records), bytes_in and members count only the members

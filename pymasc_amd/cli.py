@@ -221,6 +221,12 @@ def get_parser() -> argparse.ArgumentParser:
     out.add_argument("--fingerprint-control", metavar="FILE", type=Path,
                      help="an alignment file (a control / input sample) counted the same way: the table then holds the "
                           "Jensen-Shannon distance between the two; implies --fingerprint")
+    out.add_argument("--peaks", metavar="FILE", type=Path,
+                     help="also write <name>_peaks.tab for every file: the reads the correlation sees counted per line of this peak "
+                          "file (narrowPeak, broadPeak, gappedPeak or any BED3+; plain, gzip or bgzip; the first three columns), the "
+                          "fraction of reads in peaks (FRiP) and its enrichment over the share of the genome the peaks cover")
+    out.add_argument("--peaks-extend", metavar="N", type=int, action=_NaturalNumber,
+                     help="count every read as N bases from its 5' end instead of its own length; needs --peaks")
     return parser
 
 
@@ -264,6 +270,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("argument --fingerprint-control: no such file: '{}'".format(args.fingerprint_control))
     if args.fingerprint_bin is not None or args.fingerprint_extend is not None or args.fingerprint_control is not None:
         args.fingerprint = True
+    if args.peaks_extend is not None and args.peaks is None:
+        parser.error("argument --peaks-extend: needs a peak file (--peaks)")
+    if args.peaks is not None and not os.path.isfile(args.peaks):
+        parser.error("argument --peaks: no such file: '{}'".format(args.peaks))
     if args.chrom_sizes is None:
         from .bed_reads import is_bed_reads     # (no torch, no native library)
         bed = [str(p) for p in args.reads if is_bed_reads(p)]
@@ -352,6 +362,10 @@ def _run(args, device, rank: int) -> int:
                            ("fingerprint_control", args.fingerprint_control)):
             if value is not None:
                 extra[key] = str(value) if key == "fingerprint_control" else value
+    if args.peaks is not None:
+        extra["peaks"] = str(args.peaks)
+        if args.peaks_extend is not None:
+            extra["peaks_extend"] = args.peaks_extend
     try:
         results = pipeline.run_files(
             [str(p) for p in args.reads], str(args.outdir), args.max_shift, read_len=args.read_length,

@@ -1236,6 +1236,13 @@ struct pmx_dbam {
     long long *d_bc_tab = nullptr;   // per reference: its first bin (-1: not chosen), its number of bins
     u64 bc_bins = 0, bc_reads = 0;   // bins; reads that added to a bin since begin
     u32 bc_bin = 0, bc_ext = 0;      // bin size, extend
+    // reads per peak line (pmx_dbam_peakcount_*, peakcount_device.inc): from begin to the next begin or close
+    u8 *d_pk = nullptr;              // per line, in (reference, begin) order: key, pmax (8 bytes each), end, input line; counts by input line
+    long long *d_pk_tab = nullptr;   // per reference: its length, -1 when it is not chosen
+    bool pk_on = false;              // between a begin that succeeded and the next one
+    u64 pk_lines = 0, pk_union = 0;  // lines; bases of the merged lines on chosen references
+    u32 pk_ext = 0;                  // extend
+    std::vector<u64> pk_tot;         // N, n_in, then the same two per reference, summed over the calls of add
 };
 
 namespace {
@@ -1784,7 +1791,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 11; }
+int pmx_dbam_version(void) { return 12; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1857,6 +1864,8 @@ void pmx_dbam_close(pmx_dbam *b)
     if (b->d_xs) (void)hipFree(b->d_xs);
     if (b->d_bc) (void)hipFree(b->d_bc);
     if (b->d_bc_tab) (void)hipFree(b->d_bc_tab);
+    if (b->d_pk) (void)hipFree(b->d_pk);
+    if (b->d_pk_tab) (void)hipFree(b->d_pk_tab);
     for (void *p : {(void *)b->d_nl, (void *)b->d_ls, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
         if (p) (void)hipFree(p);
     for (hipStream_t x : b->kmore)
@@ -2572,3 +2581,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "complexity_device.inc"
 #include "bincount_device.inc"
 #include "region_mask_device.inc"
+#include "peakcount_device.inc"

@@ -16,6 +16,19 @@
 #define FP_BALLOT 4u                          // the counts 0 .. FP_BALLOT - 1 are tallied by ballot
 #define FP_HIST_GRID 2048u                    // workgroups of k_fp_hist at the most
 
+// The extent [lo, hi] of a read (1-based, inclusive; also k_pk_count's, peakcount_device.inc): L = ext, or the read's own length
+// when ext is 0; a forward read covers [pos1, pos1 + L - 1], a reverse read [pos1 + read_len - L, pos1 + read_len - 1] (its 5' end
+// stays put); both clipped to [1, top].  False: nothing is left of it.
+__device__ __forceinline__ bool fp_extent(long long p, long long rl, bool rev, u32 ext, long long top, long long &lo, long long &hi)
+{
+    const long long L = ext ? (long long)ext : rl;
+    lo = rev ? p + rl - L : p;
+    hi = rev ? p + rl - 1 : p + L - 1;
+    if (lo < 1) lo = 1;
+    if (hi > top) hi = top;
+    return lo <= hi;
+}
+
 // tab[2 * r] = the first bin of reference r in the table (-1: the reference is not chosen), tab[2 * r + 1] = its bins
 __global__ void __launch_bounds__(256) k_fp_count(const int *__restrict__ ref, const int *__restrict__ pos, const int *__restrict__ len,
                                                   const u8 *__restrict__ rev, u64 n, const long long *__restrict__ tab, u32 nref,
@@ -28,12 +41,9 @@ __global__ void __launch_bounds__(256) k_fp_count(const int *__restrict__ ref, c
     if (i < n && ref[i] >= 0 && (u32)ref[i] < nref) {
         const long long first = tab[2u * (u32)ref[i]], nb = tab[2u * (u32)ref[i] + 1u];
         if (first >= 0 && nb > 0) {
-            const long long p = pos[i], rl = len[i], L = ext ? (long long)ext : rl;
-            long long lo = rev[i] ? p + rl - L : p, hi = rev[i] ? p + rl - 1 : p + L - 1;
             const long long cover = nb * (long long)bin;     // (<= the reference's length: the clip to it and the binless tail in one)
-            if (lo < 1) lo = 1;
-            if (hi > cover) hi = cover;
-            if (lo <= hi) {
+            long long lo, hi;
+            if (fp_extent(pos[i], len[i], rev[i] != 0, ext, cover, lo, hi)) {
                 hit = true;
                 const long long j1 = (hi - 1) / bin;
                 for (long long j = (lo - 1) / bin; j <= j1; j++) atomicAdd(&counts[first + j], 1u);

@@ -14,6 +14,8 @@
 //   k_rm_keep     one lane per kept record of a decode: the last merged interval with begin + 1 <= pos1 + read_len - 1 (binary
 //                 search over the keys), dropped when it is of the read's reference and pos1 <= end; the keep flags and their
 //                 count per workgroup feed k_bam_scan and k_rm_compact (ranks by ballot, in record order)
+// rm_build runs the first three for pmx_dbam_set_exclude, which keeps the merged intervals, and for pmx_dbam_peakcount_begin
+// (peakcount_device.inc), which keeps the sorted lines, their ends, the running maximum and the sort's permutation as well.
 // The filter runs behind every decode (pmx_dbam_decode) and inside pmx_dbam_complexity; the runs (k_ref_runs) are taken
 // from the compacted arrays afterwards.
 
@@ -157,6 +159,16 @@ static int rm_to_device(hipStream_t st, const T *src, u64 n, DevAlloc &dst)
     return 0;
 }
 
+// What clipping, sorting and merging the lines of a region file leaves on the device (rm_build): the caller keeps what it needs
+// (pmx_dbam_set_exclude the merged intervals; pmx_dbam_peakcount_begin, peakcount_device.inc, the sorted lines as well) and the
+// rest is freed with the struct.
+struct RmBuilt {
+    DevAlloc key, endc, ka, kb, va, vb, pmax, okey, oend;
+    const u64 *skey = nullptr;      // the keys in (reference, begin) order, the empty lines (key nref << 32) at the tail
+    const u32 *perm = nullptr;      // sorted place -> input line; null: no pass moved a key, the order is the input's
+    u64 n = 0, merged = 0;          // lines; merged intervals (okey / oend)
+};
+
 extern "C" {
 
 static int rm_filter(pmx_dbam *b, int *ref, int *pos, int *len, u8 *rev, u64 n, u64 *n_out)
@@ -216,33 +228,32 @@ static void rm_detach(pmx_dbam *b)
     b->x_n = b->xs_cap = 0;
 }
 
-static int rm_set_exclude_impl(pmx_dbam *b, int32_t nref, const int64_t *offsets, const uint32_t *begin, const uint32_t *end)
+// The lines of reference r are [offsets[r], offsets[r + 1]) of begin / end (host or device memory): k_rm_keys, the radix sort with
+// the line index as payload, k_rm_merge.  B.n = 0: there is no line.  `who` names the caller in the messages.
+static int rm_build(pmx_dbam *b, const char *who, int32_t nref, const int64_t *offsets, const uint32_t *begin, const uint32_t *end,
+                    RmBuilt &B)
 {
-    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
-    HIPOK(hipSetDevice(b->device));
-    HIPOK(hipStreamSynchronize(b->stream));
-    rm_detach(b);
-    if (!offsets && !begin && !end) return 0;
+    const std::string w = std::string(who) + ": ";
     if (!offsets || nref != (int32_t)b->ref_names.size())
-        return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_set_exclude: nref offsets + 1 are needed, nref = the references of the header");
+        return fail(PMX_DBAM_ERR_INVALID, w + "nref offsets + 1 are needed, nref = the references of the header");
     if (nref == 0) return 0;
     for (int32_t r = 0; r < nref; r++)
-        if (offsets[r] < 0 || offsets[r + 1] < offsets[r]) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_set_exclude: offsets must ascend from 0");
-    if (offsets[0] != 0) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_set_exclude: offsets must ascend from 0");
+        if (offsets[r] < 0 || offsets[r + 1] < offsets[r]) return fail(PMX_DBAM_ERR_INVALID, w + "offsets must ascend from 0");
+    if (offsets[0] != 0) return fail(PMX_DBAM_ERR_INVALID, w + "offsets must ascend from 0");
     const u64 n = (u64)offsets[nref];
     if (n == 0) return 0;
-    if (!begin || !end) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_set_exclude: null interval arrays");
-    if (n >= 0xffffffffull) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_set_exclude: too many intervals");
+    if (!begin || !end) return fail(PMX_DBAM_ERR_INVALID, w + "null interval arrays");
+    if (n >= 0xffffffffull) return fail(PMX_DBAM_ERR_INVALID, w + "too many intervals");
     hipStream_t st = b->stream;
-    DevAlloc d_b, d_e, d_off, d_len, d_key, d_endc;
+    DevAlloc d_b, d_e, d_off, d_len;
     if (int rc = rm_to_device(st, begin, n, d_b)) return rc;
     if (int rc = rm_to_device(st, end, n, d_e)) return rc;
     if (int rc = rm_to_device(st, (const long long *)offsets, (u64)nref + 1, d_off)) return rc;
     if (int rc = rm_to_device(st, (const long long *)b->ref_lens.data(), (u64)nref, d_len)) return rc;
-    HIPOK(hipMalloc(&d_key.p, 8 * n));
-    HIPOK(hipMalloc(&d_endc.p, 4 * n));
+    HIPOK(hipMalloc(&B.key.p, 8 * n));
+    HIPOK(hipMalloc(&B.endc.p, 4 * n));
     hipLaunchKernelGGL(k_rm_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_b.as<u32>(), d_e.as<u32>(), d_off.as<long long>(),
-                       d_len.as<long long>(), (u32)nref, n, d_key.as<u64>(), d_endc.as<u32>());
+                       d_len.as<long long>(), (u32)nref, n, B.key.as<u64>(), B.endc.as<u32>());
     HIPOK(hipGetLastError());
     // sorted by (reference, begin): every bit of the begin, and the bits a reference id (or nref, the empty lines' key) can have
     u64 hb = 1;
@@ -250,35 +261,50 @@ static int rm_set_exclude_impl(pmx_dbam *b, int32_t nref, const int64_t *offsets
     const u64 differ = ((hb - 1) << 32) | 0xffffffffull;
     const u32 ntiles = (u32)((n + BED_RS_TILE - 1) / BED_RS_TILE);
     const u64 ncnt = 256ull * ntiles;
-    DevAlloc d_ka, d_kb, d_va, d_vb, d_cnt, d_base, d_tot;
-    HIPOK(hipMalloc(&d_ka.p, 8 * n));
-    HIPOK(hipMalloc(&d_kb.p, 8 * n));
-    HIPOK(hipMalloc(&d_va.p, 4 * n));
-    HIPOK(hipMalloc(&d_vb.p, 4 * n));
+    DevAlloc d_cnt, d_base, d_tot;
+    HIPOK(hipMalloc(&B.ka.p, 8 * n));
+    HIPOK(hipMalloc(&B.kb.p, 8 * n));
+    HIPOK(hipMalloc(&B.va.p, 4 * n));
+    HIPOK(hipMalloc(&B.vb.p, 4 * n));
     HIPOK(hipMalloc(&d_cnt.p, 4 * ncnt));
     HIPOK(hipMalloc(&d_base.p, 8 * ncnt));
     HIPOK(hipMalloc(&d_tot.p, 16));
-    const u64 *kin = d_key.as<u64>();
+    const u64 *kin = B.key.as<u64>();
     const u32 *vin = nullptr;
-    if (int rc = cx_sort(st, n, differ, kin, vin, d_ka.as<u64>(), d_kb.as<u64>(), d_va.as<u32>(), d_vb.as<u32>(), d_cnt.as<u32>(),
+    if (int rc = cx_sort(st, n, differ, kin, vin, B.ka.as<u64>(), B.kb.as<u64>(), B.va.as<u32>(), B.vb.as<u32>(), d_cnt.as<u32>(),
                          d_base.as<u64>(), d_tot.as<u64>()))
         return rc;
     // merged: the heads with the running maximum of the ends of their group
-    DevAlloc d_pmax, d_okey, d_oend;
-    HIPOK(hipMalloc(&d_pmax.p, 8 * n));
-    HIPOK(hipMalloc(&d_okey.p, 8 * n));
-    HIPOK(hipMalloc(&d_oend.p, 4 * n));
-    hipLaunchKernelGGL(k_rm_merge, dim3(1), dim3(1024), 0, st, kin, vin, d_endc.as<u32>(), n, (u32)nref, d_pmax.as<u64>(), d_okey.as<u64>(),
-                       d_oend.as<u32>(), d_tot.as<u64>());
+    HIPOK(hipMalloc(&B.pmax.p, 8 * n));
+    HIPOK(hipMalloc(&B.okey.p, 8 * n));
+    HIPOK(hipMalloc(&B.oend.p, 4 * n));
+    hipLaunchKernelGGL(k_rm_merge, dim3(1), dim3(1024), 0, st, kin, vin, B.endc.as<u32>(), n, (u32)nref, B.pmax.as<u64>(), B.okey.as<u64>(),
+                       B.oend.as<u32>(), d_tot.as<u64>());
     HIPOK(hipGetLastError());
     u64 merged = 0;
     HIPOK(hipMemcpyAsync(&merged, d_tot.p, 8, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    if (merged == 0) return 0;
-    b->d_xkey = d_okey.as<u64>();
-    b->d_xend = d_oend.as<u32>();
-    d_okey.p = d_oend.p = nullptr;
-    b->x_n = merged;
+    HIPOK(hipStreamSynchronize(st));      // (the copies of the lines and the scratch of the sort are locals)
+    B.skey = kin;
+    B.perm = vin;
+    B.n = n;
+    B.merged = merged;
+    return 0;
+}
+
+static int rm_set_exclude_impl(pmx_dbam *b, int32_t nref, const int64_t *offsets, const uint32_t *begin, const uint32_t *end)
+{
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    HIPOK(hipSetDevice(b->device));
+    HIPOK(hipStreamSynchronize(b->stream));
+    rm_detach(b);
+    if (!offsets && !begin && !end) return 0;
+    RmBuilt B;
+    if (int rc = rm_build(b, "pmx_dbam_set_exclude", nref, offsets, begin, end, B)) return rc;
+    if (B.merged == 0) return 0;
+    b->d_xkey = B.okey.as<u64>();
+    b->d_xend = B.oend.as<u32>();
+    B.okey.p = B.oend.p = nullptr;
+    b->x_n = B.merged;
     return 0;
 }
 

@@ -98,6 +98,7 @@ u64 stream_held(const pmx_dbam &b)
     if (b.sam) h += b.sam_lines * 24 + b.sam_nb_cap * 12 + 16;
     h += s->cx_n * 13;
     h += b.bc_bins * 4;
+    h += b.pk_lines * 28;
     return h;
 }
 void stream_note(pmx_dbam &b) { b.st->peak = std::max(b.st->peak, stream_held(b)); }

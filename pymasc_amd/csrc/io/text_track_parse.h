@@ -403,7 +403,9 @@ inline int detect_kind(const uint8_t *t, uint64_t n, bool complete, const std::s
     std::string name = path;
     if (iends_with(name, ".gz")) name.resize(name.size() - 3);
     else if (iends_with(name, ".bgz")) name.resize(name.size() - 4);
-    const uint32_t by_name = iends_with(name, ".bed") ? KIND_BED : KIND_BEDGRAPH;
+    // (ENCODE's peak formats are BED6+4 / BED6+3 / BED12+3: read as BED, by their first three columns)
+    const bool bed = iends_with(name, ".bed") || iends_with(name, ".narrowpeak") || iends_with(name, ".broadpeak") || iends_with(name, ".gappedpeak");
+    const uint32_t by_name = bed ? KIND_BED : KIND_BEDGRAPH;
     PtrSrc s{t};
     uint64_t p = 0;
     while (p < n) {

@@ -121,6 +121,10 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_bincount_add": (_int, [_vp, _u32, _u32, _pu64]),
     "pmx_dbam_bincount_hist": (_i64, [_vp, _vp, _vp, _i64, _vp]),
     "pmx_dbam_bincount_copy": (_int, [_vp, _i64, _i64, _vp]),
+    "pmx_dbam_peakcount_begin": (_int, [_vp, _i32, _vp, _vp, _vp, _u32, _vp]),
+    "pmx_dbam_peakcount_add": (_int, [_vp, _u32, _u32, _vp]),
+    "pmx_dbam_peakcount_copy": (_int, [_vp, _i64, _i64, _vp]),
+    "pmx_dbam_peakcount_totals": (_int, [_vp, _vp, _vp]),
     "pmx_dbam_set_exclude": (_int, [_vp, _i32, _vp, _vp, _vp]),
     "pmx_dbam_exclude_intervals": (_i64, [_vp, _i64, _vp, _vp, _vp]),
     "pmx_dbam_excluded": (_int, [_vp, _pu64, _pu64]),
@@ -278,6 +282,15 @@ class AlignmentReader(NativeReader):
         from .fingerprint import from_reader
         self._check_open()
         return from_reader(self, mapq_criteria, references, bin_size, extend)
+
+    def peak_counts(self, peaks, mapq_criteria: int = 0, references=None, extend: int = 0):
+        """The reads of ``bin_counts`` counted per line of ``peaks`` (a peak file's path, an ordered ``{name: [(start, end),
+        ...]}`` or ``peaks.open_peaks``' result) and in at least one line: a ``pymasc_amd.peaks.PeakCounts`` with ``frip`` and
+        ``enrichment`` (``peaks.from_reader``).  ``extend`` as for ``bin_counts``.  A device reader counts on the
+        GPU with arrays of its own: the arrays of the last ``decode`` stay as they are."""
+        from .peaks import from_reader
+        self._check_open()
+        return from_reader(self, peaks, mapq_criteria, references, extend)
 
     # ---- excluded regions (pymasc_amd.region_mask; DESIGN.md 7.15) ----
     _exclude = None

@@ -38,7 +38,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         device_ingest: Optional[bool] = None, readlen_estimator: str = "MEDIAN", chromfilter=None, stats: bool = False,
         library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
         chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None,
-        fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None):
+        fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None,
+        peaks=None, peaks_extend: int = 0):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -74,7 +75,13 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     length); the table holds the fingerprint's AUC, X-intercept and elbow, the Jensen-Shannon distance to a Poisson model and the
     number of bins at every count.  Counted where ``complexity`` is counted.  ``fingerprint_control``: an alignment file counted
     the same way (once per call, never correlated), with the Jensen-Shannon distance to it in the table; it turns
-    ``fingerprint`` on.  Its chosen references must have the sample's names and lengths: ValueError before the run."""
+    ``fingerprint`` on.  Its chosen references must have the sample's names and lengths: ValueError before the run.
+    ``peaks``: a peak file (narrowPeak, broadPeak, gappedPeak or any BED3+ file; plain, gzip or bgzip) or an ordered
+    ``{name: [(start, end), ...]}``: rank 0 also writes ``<stem>_peaks.tab`` (pymasc_amd.peaks): the reads the
+    fingerprint counts, each covering ``peaks_extend`` bases from its 5' end (0: its own length), counted per line of the file
+    and in at least one line -- FRiP, its enrichment over the share of the genome the lines cover, a row per chromosome and a
+    BED table of the reads per line.  Counted where ``complexity`` is counted.  No line's chromosome among the references:
+    ValueError before any table is written."""
     check_bed_sizes(bam_path, chrom_sizes)
     s = _settings(locals())
     from .kmer_track import is_fasta
@@ -88,6 +95,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
             track = open_track(mappability_path, track_on_device(mappability_path, False, context),
                                reader_device(context, s.device), k=read_len)
         mask, bam = _resolve_mask(s, bam_path, bam)     # (no name in common: ValueError before the cache pass and any table)
+        _lines, bam = _resolve_regions(s, s.peaks, bam_path, bam)
         if s.fingerprint_control is not None:
             if bam is None and is_stream(bam_path) and s.estimate_gpu is not None:      # (no header to read apart, as above)
                 bam = open_alignments(bam_path, True, device=s.estimate_gpu)
@@ -129,6 +137,8 @@ class _Settings:
     fingerprint_bin: int
     fingerprint_extend: int
     fingerprint_control: object     # None, or the _FingerprintControl counted once for the call
+    peaks: object                   # None, or the lines of the peak file, read once for the call (peaks.open_peaks)
+    peaks_extend: int
     save_mappability_stats: bool
     device: int
     ingest: bool
@@ -162,6 +172,14 @@ def _settings(kw: dict) -> _Settings:
     if kw.get("exclude_regions") is not None:      # read once (on the GPU with device ingest); each file resolves the names
         from .region_mask import open_mask
         given["exclude_regions"] = open_mask(kw["exclude_regions"], bool(ingest), reader_device(kw["context"], device, bool(ingest)))
+    if int(kw["peaks_extend"]) < 0:
+        raise ValueError("peaks_extend is at least 0")
+    if kw["peaks"] is None and int(kw["peaks_extend"]):
+        raise ValueError("peaks_extend needs peaks")
+    if kw["peaks"] is not None:
+        from .peaks import open_peaks
+        given["peaks"] = open_peaks(kw["peaks"], bool(ingest), reader_device(kw["context"], device, bool(ingest)))
+    given["peaks_extend"] = int(kw["peaks_extend"])
     if int(kw["fingerprint_bin"]) < 1 or int(kw["fingerprint_extend"]) < 0:
         raise ValueError("fingerprint_bin is at least 1 and fingerprint_extend at least 0")
     control = kw["fingerprint_control"]
@@ -194,23 +212,30 @@ def _estimate(s: _Settings, path, keep: bool):
 
 def _resolve_mask(s: _Settings, path, bam):
     """(the run's excluded regions bound to the references of ``path`` -- a ``region_mask.ResolvedMask``, None without
-    ``exclude_regions`` --, the open reader of ``path``).  The references come from ``bam`` when the file is open already, else
-    from its header alone (``inputs.open_header``); a stream has no header to read apart, so its device reader is opened here
-    and handed back to feed the run.  ValueError when no name of the mask is a reference."""
-    if s.exclude_regions is None:
+    ``exclude_regions`` --, the open reader of ``path``): ``_resolve_regions`` of ``s.exclude_regions``."""
+    return _resolve_regions(s, s.exclude_regions, path, bam)
+
+
+def _resolve_regions(s: _Settings, regions, path, bam):
+    """(``regions`` -- the run's excluded regions or its peak file, a ``region_mask.ExcludeMask`` or None -- bound to the
+    references of ``path``: a ``region_mask.ResolvedMask`` or None, the open reader of ``path``).  The references come from
+    ``bam`` when the file is open already, else from its header alone (``inputs.open_header``); a stream has no header to read
+    apart, so its device reader is opened here and handed back to feed the run.  ValueError when no name of ``regions`` is a
+    reference."""
+    if regions is None:
         return None, bam
     if bam is None and is_stream(path) and s.estimate_gpu is not None:
         bam = open_alignments(path, True, device=s.estimate_gpu)
     if bam is not None:
         try:
-            return s.exclude_regions.resolve(bam.references, bam.lengths), bam
+            return regions.resolve(bam.references, bam.lengths), bam
         except BaseException:
             bam.close()
             raise
     if is_stream(path):             # (no device reader: run_sharded says so)
-        return s.exclude_regions, bam
+        return regions, bam
     with open_header(path, s.chrom_sizes) as h:
-        return s.exclude_regions.resolve(h.references, h.lengths), bam
+        return regions.resolve(h.references, h.lengths), bam
 
 
 def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool, mask=None):
@@ -253,10 +278,11 @@ def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool, mask=No
 
 def _run_file(s: _Settings, path, read_len: int, known, bam, track, mask=None):
     """One file sharded over the ranks: (its genome-wide result, the counts taken beside it: a _ComplexityCount and a
-    _FingerprintCount as asked for).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's and the
+    _FingerprintCount and a _PeakCount as asked for).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's and the
     track's open readers, or None for run_sharded to open its own.  One rank: run_sharded's one ``reader_hook`` serves every
     count (``_hooks``)."""
-    counted = [c(s) for c, on in ((_ComplexityCount, s.complexity), (_FingerprintCount, s.fingerprint)) if on]
+    counted = [c(s) for c, on in ((_ComplexityCount, s.complexity), (_FingerprintCount, s.fingerprint),
+                                     (_PeakCount, s.peaks is not None)) if on]
     result = run_sharded(path, s.max_shift, read_len, s.mapq_criteria, bigwig_path=s.mappability_path,
                          references=s.references, skip_ncc=s.skip_ncc, device=s.device, chrom2mappable_len=known,
                          group=s.group, context=s.context, device_ingest=s.ingest, bam=bam, chromfilter=s.chromfilter,
@@ -281,7 +307,7 @@ def _hooks(hooks):
 def _write_file(s: _Settings, path, basename: str, result, read_len: int, counted) -> List[Path]:
     """Rank 0's part after _run_file: ``outdir/<basename>_{cc,mscc,nreads}.tab``, with ``stat_opts`` ``<basename>_stats.tab``
     whose Name row is ``basename``, and the table of every count in ``counted`` (``<basename>_complexity.tab``,
-    ``<basename>_fingerprint.tab``); the paths written."""
+    ``<basename>_fingerprint.tab``, ``<basename>_peaks.tab``); the paths written."""
     out = Path(s.outdir)
     out.mkdir(parents=True, exist_ok=True)
     # write_tables names the tables after the stem of its path (table.py:185-188): a suffix keeps a dotted base name whole
@@ -375,6 +401,40 @@ class _FingerprintCount:
                                              None if control is None else control.counts(s), "" if control is None else control.path)
 
 
+class _PeakCount:
+    """The reads per peak line of one file's run (pymasc_amd.peaks), taken where _FingerprintCount takes its own."""
+
+    def __init__(self, s: _Settings):
+        self.s = s
+        self.value = None
+
+    def _args(self, names):
+        return self.s.peaks, int(self.s.mapq_criteria), names, self.s.peaks_extend
+
+    def hook(self, reader, names):
+        from . import peaks
+        if hasattr(reader, "arm_peaks"):
+            acc = reader.arm_peaks(*self._args(names))
+
+            def after():
+                try:
+                    self.value = acc.result(reader)
+                finally:
+                    reader.disarm_peaks()
+            return after
+
+        def after():
+            self.value = peaks.from_reader(reader, *self._args(names))
+        return after
+
+    def write(self, path, basename: str) -> Path:
+        from . import peaks
+        s = self.s
+        if self.value is None:
+            self.value = _count_again(s, path, lambda r, names: peaks.from_reader(r, *self._args(names)))
+        return peaks.write_peaks(Path(s.outdir) / basename, basename, self.value, s.peaks.source or "")
+
+
 class _FingerprintControl:
     """``fingerprint_control``: the control file of a call's fingerprints.  ``check`` compares its chosen references with a
     sample's from the headers alone; ``counts`` is its table, counted once per call (by rank 0, when the first table is written)
@@ -430,7 +490,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
               chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None,
               complexity: bool = False, exclude_regions=None, fingerprint: bool = False, fingerprint_bin: int = 500,
-              fingerprint_extend: int = 0, fingerprint_control=None) -> List[FileResult]:
+              fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -495,11 +555,15 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
             track = open_track(mappability_path, track_on_device(mappability_path, s.ingest, s.context),
                                getattr(s.context, "device", dev) if is_fasta(mappability_path) else dev, k=read_len)
         # the excluded regions are bound to every file's references before the cache pass: a file none of whose references the
-        # mask names is skipped like a file that cannot be opened; the cache is cut with the first file's clipped intervals
+        # mask names is skipped like a file that cannot be opened; the cache is cut with the first file's clipped intervals.
+        # The peak file is bound the same way: a file none of whose references it names is skipped too.
         masks = {}
         for i in list(live):
             try:
                 masks[i], kept_i = _resolve_mask(s, paths[i], kept.get(i))
+                if kept_i is not None:
+                    kept[i] = kept_i
+                _lines, kept_i = _resolve_regions(s, s.peaks, paths[i], kept.get(i))
                 if kept_i is not None:
                     kept[i] = kept_i
             except ValueError as e:
@@ -578,7 +642,7 @@ def _warn_existing(s: _Settings, bases):
     has_track = s.mappability_path is not None
     suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
                                 ("_stats.tab", s.stat_opts is not None), ("_complexity.tab", s.complexity),
-                                ("_fingerprint.tab", s.fingerprint)) if on]
+                                ("_fingerprint.tab", s.fingerprint), ("_peaks.tab", s.peaks is not None)) if on]
     for b in bases:
         for suffix in suffixes:
             path = Path(s.outdir) / (b + suffix)

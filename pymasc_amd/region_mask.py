@@ -91,9 +91,10 @@ class ExcludeMask:
     """The lines of a mask by chromosome name, as they were read (``open_mask``); ``resolve`` binds them to an alignment's
     references.  ``source``: the path it was read from, None for a dict."""
 
-    def __init__(self, lines: Dict[str, Tuple[np.ndarray, np.ndarray]], source=None):
+    def __init__(self, lines: Dict[str, Tuple[np.ndarray, np.ndarray]], source=None, what: str = "excluded regions"):
         self.lines = lines
         self.source = source
+        self.what = what            # what the messages call the file (a peak file is read and resolved here too, DESIGN.md 7.17)
         self._merged: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
         self._warned = False        # the skipped names were reported (once per mask, however many files resolve it)
 
@@ -116,14 +117,14 @@ class ExcludeMask:
         known = set(refs)
         skipped = [n for n in self.lines if n not in known]
         if len(skipped) == len(self.lines):
-            raise ValueError("no chromosome of the excluded regions{} is among the alignment's references (e.g. {} vs {}): "
+            raise ValueError("no chromosome of the {}{} is among the alignment's references (e.g. {} vs {}): "
                              "check the naming ('chr1' vs '1')".format(
-                                 "" if self.source is None else " '{}'".format(self.source),
+                                 self.what, "" if self.source is None else " '{}'".format(self.source),
                                  ", ".join(repr(n) for n in skipped[:3]) or "none", ", ".join(repr(n) for n in refs[:3]) or "none"))
         if skipped and not self._warned:
             self._warned = True
-            logger.warning("Excluded regions: {} chromosome name(s) are not among the alignment's references and are skipped."
-                           "".format(len(skipped)))
+            logger.warning("{}: {} chromosome name(s) are not among the alignment's references and are skipped."
+                           "".format(self.what[:1].upper() + self.what[1:], len(skipped)))
         return ResolvedMask(self, refs, [int(x) for x in lengths])
 
 
@@ -135,10 +136,18 @@ class ResolvedMask:
         self.references = tuple(references)
         self.lengths = tuple(lengths)
 
-    def csr(self):
+    def lines(self, ref_id: int, clip: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """The lines of reference ``ref_id`` as they were read, one row per line in file order, unmerged (none for a reference
+        the file does not name); ``clip``: the ends clipped to the reference's length (a line may be empty then)."""
+        b, e = self.mask.lines.get(self.references[ref_id], (_EMPTY, _EMPTY))
+        return (b, np.minimum(e, min(max(self.lengths[ref_id], 0), 2**32 - 1)).astype(np.uint32)) if clip else (b, e)
+
+    def csr(self, use=None):
         """(offsets int64[nref + 1], begin uint32, end uint32): every reference's lines as read, in reference order -- the
-        arguments of ``pmx_dbam_set_exclude``, which clips, sorts and merges them on the device."""
-        parts = [self.mask.lines.get(n, (_EMPTY, _EMPTY)) for n in self.references]
+        arguments of ``pmx_dbam_set_exclude``, which clips, sorts and merges them on the device, and of
+        ``pmx_dbam_peakcount_begin``, which keeps them apart.  ``use`` (one flag per reference; None: all): a reference that is
+        not in it has no lines."""
+        parts = [self.lines(r) if use is None or use[r] else (_EMPTY, _EMPTY) for r in range(len(self.references))]
         offsets = np.zeros(len(parts) + 1, dtype=np.int64)
         if parts:
             offsets[1:] = np.cumsum([p[0].size for p in parts])
@@ -180,9 +189,10 @@ class ResolvedMask:
         return self.merged(self.references.index(name))
 
 
-def open_mask(source, device_ingest: bool = False, device: int = 0) -> ExcludeMask:
+def open_mask(source, device_ingest: bool = False, device: int = 0, what: str = "excluded regions") -> ExcludeMask:
     """The mask of ``source``: an ``ExcludeMask`` as it is, an ordered ``{name: [(start, end), ...]}``, or the path of a BED
-    file, read through ``inputs.open_track`` (on ``device`` with ``device_ingest``).  ValueError for a malformed dict interval."""
+    file, read through ``inputs.open_track`` (on ``device`` with ``device_ingest``).  ValueError for a malformed dict interval.
+    ``what``: what the messages call it (``pymasc_amd.peaks`` reads a peak file here: the first three columns of every line)."""
     if isinstance(source, ExcludeMask):
         return source
     if isinstance(source, dict):
@@ -190,19 +200,27 @@ def open_mask(source, device_ingest: bool = False, device: int = 0) -> ExcludeMa
         for name, ivs in source.items():
             arr = np.asarray(list(ivs), dtype=np.int64).reshape(-1, 2)
             if arr.size and (arr.min() < 0 or arr.max() >= 2**32):
-                raise ValueError("excluded regions of '{}': positions must lie in [0, 2^32)".format(name))
+                raise ValueError("{} of '{}': positions must lie in [0, 2^32)".format(what, name))
             lines[str(name)] = (arr[:, 0].astype(np.uint32), arr[:, 1].astype(np.uint32))
-        return ExcludeMask(lines)
+        return ExcludeMask(lines, what=what)
     from .inputs import open_track
     path = os.fspath(source)
     if not os.path.isfile(path):
-        raise FileNotFoundError("excluded regions: no such file: '{}'".format(path))
+        raise FileNotFoundError("{}: no such file: '{}'".format(what, path))
     lines = {}
     with open_track(path, device_ingest, device) as t:
         for name in t.chromsizes:
             b, e, _v = t.fetch_arrays(0.0, name)
             lines[name] = (np.asarray(b, dtype=np.uint32).copy(), np.asarray(e, dtype=np.uint32).copy())
-    return ExcludeMask(lines, source=path)
+    return ExcludeMask(lines, source=path, what=what)
+
+
+def resolve_lines(mask: ExcludeMask, references: Sequence[str], lengths: Sequence[int], use=None):
+    """``mask.resolve`` with the lines kept apart (a peak file): (the ``ResolvedMask``, its ``csr(use)``) -- one
+    row per line, in file order within a reference and the references in header order, unmerged and unclipped.  The names, the
+    warning and the ValueError are ``resolve``'s; the clipping is ``ResolvedMask.lines(r, clip=True)`` or the device's."""
+    resolved = mask.resolve(references, lengths)
+    return resolved, resolved.csr(use)
 
 
 def cut_intervals(begin, end, mb, me, read_len: int) -> Tuple[np.ndarray, np.ndarray]:

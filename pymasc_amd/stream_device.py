@@ -108,6 +108,8 @@ class DeviceStreamReader(DeviceBamReader):
                 self.set_exclude(self._exclude)
             if self._fingerprint is not None:   # (so does the table of bins)
                 self._fingerprint.begin(self)
+            if self._peaks is not None:         # (and the table of peak lines)
+                self._peaks.begin(self)
         self._consumed = True
         while True:
             n = self._L.pmx_dbam_stream_next(self._h)
@@ -122,6 +124,8 @@ class DeviceStreamReader(DeviceBamReader):
                 self._complexity.count(self)
             if self._fingerprint is not None:
                 self._fingerprint.add(self)
+            if self._peaks is not None:
+                self._peaks.add(self)
 
     _complexity = None
 
@@ -150,6 +154,20 @@ class DeviceStreamReader(DeviceBamReader):
 
     def disarm_fingerprint(self) -> None:
         self._fingerprint = None
+
+    _peaks = None
+
+    def arm_peaks(self, peaks, mapq_criteria: int = 0, references=None, extend: int = 0):
+        """From now on every window a pass makes current is also counted per line of ``peaks`` (``pmx_dbam_peakcount_add``, into
+        the table ``pmx_dbam_peakcount_begin`` builds here); returns the ``pymasc_amd.peaks.DeviceCount`` whose ``result(reader)``
+        is the whole stream's once the pass has ended.  A read is counted in the window that decodes it, as for
+        ``arm_fingerprint``."""
+        from .peaks import DeviceCount
+        self._peaks = DeviceCount(self, peaks, mapq_criteria, references, extend)
+        return self._peaks
+
+    def disarm_peaks(self) -> None:
+        self._peaks = None
 
     def _keep_mask(self):
         if len(self._selected) == len(self.references):
