@@ -229,6 +229,33 @@ int pmx_dbam_peakcount_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude
 int pmx_dbam_peakcount_copy(pmx_dbam *b, int64_t first, int64_t n, uint32_t *counts);
 int pmx_dbam_peakcount_totals(pmx_dbam *b, uint64_t totals[4], uint64_t *per_ref);
 
+/* The fragment pileup as a bedGraph track (version >= 13).  The reads are pmx_dbam_bincount_add's (the filter, the
+ * chosen references, less the reads an attached exclude mask drops) with its extent: L = extend, or the read's own length at 0; a
+ * forward read covers [pos1, pos1 + L - 1], a reverse read [pos1 + read_len - L, pos1 + read_len - 1], clipped to [1, len] of the
+ * reference; a read with nothing left adds nothing.  depth[r][p] = the kept reads whose clipped extent holds position p, a 32-bit
+ * count.  Per chosen reference, in header order, the maximal intervals of constant depth > 0 are the runs (start0, end0, depth),
+ * 0-based and half-open; reads that abut at equal depth form one run; depth 0 is no run.
+ * begin: one zeroed int32 slot per base of every chosen reference (use_ref[nref], NULL: all) plus one closing slot each (each
+ * reference begins on a multiple of 4 slots): 4 bytes per chosen base, 12.4 GB for hg38.  It replaces any earlier pileup and
+ * stays with the handle until finish, the next begin or close; it counts towards pmx_dbam_stream_info's peak.  No chosen reference:
+ * PMX_DBAM_ERR_INVALID; out of device memory: PMX_DBAM_ERR_OPEN, with the size asked for.
+ * add: the kept records of what the handle holds now (the arrays of the last decode stay untouched) each add +1 at the slot of
+ * their first position and -1 behind their last; *reads_added = the reads that added.  Calls add up (the windows of a stream);
+ * 2^31 reads or more since begin: PMX_DBAM_ERR_INVALID.
+ * finish: the table becomes the runs (tiles of PMX_COVERAGE_TILE slots: sums, scans, a compaction of the non-zero slots, a second
+ * one of the entries of depth > 0) and is freed; totals = reads, runs, covered bases = sum (end0 - start0), fragment bases =
+ * sum depth * (end0 - start0), the largest depth.  The runs (16 bytes each) stay until the next begin or close.
+ * runs: runs [first, first + n) copied to the host.  text: the bytes of their bedGraph lines "chrom\tstart0\tend0\tdepth\n",
+ * formatted on the device; with buf NULL only their number is returned (then call again with that much room, as for
+ * pmx_dbam_bincount_hist); a cap that is too small: PMX_DBAM_ERR_INVALID.  Returns the number of bytes.
+ * add / finish without a table, runs / text before finish, a NULL output and a range outside the runs: PMX_DBAM_ERR_INVALID. */
+#define PMX_COVERAGE_TILE 4096u
+int pmx_dbam_coverage_begin(pmx_dbam *b, uint32_t extend, const uint8_t *use_ref);
+int pmx_dbam_coverage_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t *reads_added);
+int pmx_dbam_coverage_finish(pmx_dbam *b, uint64_t totals[5]);
+int pmx_dbam_coverage_runs(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth);
+int64_t pmx_dbam_coverage_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap);
+
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
  * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong.  An indexed
  * handle: bytes_out is the length of its stream (header + selected records), bytes_in and members count only the members

@@ -41,6 +41,21 @@ class _NaturalNumber(argparse.Action):
         setattr(namespace, self.dest, values)
 
 
+class _Extend(_NaturalNumber):
+    """--coverage-extend: a natural number, or one of the words ``_extend`` lets through."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        if isinstance(values, str):
+            setattr(namespace, self.dest, values)
+        else:
+            super().__call__(parser, namespace, values, option_string)
+
+
+def _extend(text: str):
+    """``auto`` / ``read`` as they are, anything else as an int (argparse reports what is neither)."""
+    return text if text in ("auto", "read") else int(text)
+
+
 class _LogLevel(argparse.Action):
     def __call__(self, parser, namespace, values, option_string=None):
         setattr(namespace, self.dest, getattr(logging, values))
@@ -227,6 +242,15 @@ def get_parser() -> argparse.ArgumentParser:
                           "fraction of reads in peaks (FRiP) and its enrichment over the share of the genome the peaks cover")
     out.add_argument("--peaks-extend", metavar="N", type=int, action=_NaturalNumber,
                      help="count every read as N bases from its 5' end instead of its own length; needs --peaks")
+    out.add_argument("--coverage", action="store_true",
+                     help="also write <name>_coverage.bedGraph for every file: the reads the correlation sees, each extended from "
+                          "its 5' end to the estimated fragment length, piled up base by base on the GPU and written as runs of "
+                          "constant depth (plain text; no binning, no scaling).  The GPU table takes 4 bytes per base of the chosen "
+                          "chromosomes: 12.4 GB for hg38")
+    out.add_argument("--coverage-extend", metavar="N|auto|read", type=_extend, action=_Extend,
+                     help="extend every read to N bases from its 5' end; auto (the default): to the run's own fragment-length "
+                          "estimate, on one more read of the file, so not for '-' or a pipe; read: no extension, the read's own "
+                          "length; implies --coverage")
     return parser
 
 
@@ -274,6 +298,14 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("argument --peaks-extend: needs a peak file (--peaks)")
     if args.peaks is not None and not os.path.isfile(args.peaks):
         parser.error("argument --peaks: no such file: '{}'".format(args.peaks))
+    if args.coverage_extend is not None:
+        args.coverage = True
+    if args.coverage and args.coverage_extend in (None, "auto"):
+        from .stream_device import is_stream_path
+        streams = [str(p) for p in args.reads if is_stream_path(str(p))]
+        if streams:
+            parser.error("argument --coverage-extend: auto reads the file once more, which {} cannot be: give a number or 'read'"
+                         "".format(", ".join(streams)))
     if args.chrom_sizes is None:
         from .bed_reads import is_bed_reads     # (no torch, no native library)
         bed = [str(p) for p in args.reads if is_bed_reads(p)]
@@ -366,6 +398,10 @@ def _run(args, device, rank: int) -> int:
         extra["peaks"] = str(args.peaks)
         if args.peaks_extend is not None:
             extra["peaks_extend"] = args.peaks_extend
+    if args.coverage:
+        extra["coverage"] = True
+        if args.coverage_extend not in (None, "auto"):
+            extra["coverage_extend"] = 0 if args.coverage_extend == "read" else args.coverage_extend
     try:
         results = pipeline.run_files(
             [str(p) for p in args.reads], str(args.outdir), args.max_shift, read_len=args.read_length,

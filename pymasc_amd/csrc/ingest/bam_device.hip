@@ -1159,6 +1159,7 @@ const char *inf_err_text(u32 code)
 }
 
 struct StreamState;   // (stream_device.inc)
+struct CvSeg;         // (coverage_device.inc)
 
 }  // namespace
 
@@ -1243,6 +1244,17 @@ struct pmx_dbam {
     u64 pk_lines = 0, pk_union = 0;  // lines; bases of the merged lines on chosen references
     u32 pk_ext = 0;                  // extend
     std::vector<u64> pk_tot;         // N, n_in, then the same two per reference, summed over the calls of add
+    // fragment pileup (pmx_dbam_coverage_*, coverage_device.inc): the table from begin to finish, the runs from finish to the next begin or close
+    int *d_cv = nullptr;             // one slot per base of every chosen reference + a closing one: depth[p] - depth[p - 1]
+    long long *d_cv_tab = nullptr;   // per reference: its first slot (-1: not chosen), its length
+    CvSeg *d_cv_seg = nullptr;       // per chosen reference: first slot, first tile, slots, id; one more entry closes the tiles
+    u8 *d_cv_names = nullptr;        // per reference the offset of its name (u32, one more closes them), then the names
+    u8 *d_cv_runs = nullptr;         // reference, start, end, depth of every run (4 bytes each)
+    int cv_state = 0;                // nothing / a table / runs
+    u64 cv_slots = 0, cv_tiles = 0, cv_reads = 0, cv_runs = 0;   // slots; tiles; reads that added since begin; runs
+    u64 cv_held = 0;                 // device bytes the pileup holds now
+    u32 cv_nc = 0, cv_ext = 0;       // chosen references; extend
+    u64 cv_tot[5] = {0, 0, 0, 0, 0}; // reads, runs, covered bases, fragment bases, largest depth
 };
 
 namespace {
@@ -1791,7 +1803,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 12; }
+int pmx_dbam_version(void) { return 13; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1866,6 +1878,8 @@ void pmx_dbam_close(pmx_dbam *b)
     if (b->d_bc_tab) (void)hipFree(b->d_bc_tab);
     if (b->d_pk) (void)hipFree(b->d_pk);
     if (b->d_pk_tab) (void)hipFree(b->d_pk_tab);
+    for (void *p : {(void *)b->d_cv, (void *)b->d_cv_tab, (void *)b->d_cv_seg, (void *)b->d_cv_names, (void *)b->d_cv_runs})
+        if (p) (void)hipFree(p);
     for (void *p : {(void *)b->d_nl, (void *)b->d_ls, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
         if (p) (void)hipFree(p);
     for (hipStream_t x : b->kmore)
@@ -2582,3 +2596,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "bincount_device.inc"
 #include "region_mask_device.inc"
 #include "peakcount_device.inc"
+#include "coverage_device.inc"

@@ -1,0 +1,651 @@
+// The fragment pileup as runs of constant depth, and the text of its bedGraph track, on the device (pmx_dbam_coverage_*,
+// include/pymasc_amd_ingest.h; DESIGN.md 7.18).  Included at the end of bam_device.hip, behind peakcount_device.inc: the kept records
+// of a call come from cx_filter as in pmx_dbam_bincount_add, a read's extent is k_fp_count's (fp_extent), the scans over tiles,
+// workgroups and line lengths are k_bam_scan.
+//
+// The reads are the ones the correlation sees: the caller's filter, the chosen references, less the reads an attached exclude mask
+// drops.  L = extend, or the read's own length at 0; a forward read covers [pos1, pos1 + L - 1], a reverse read
+// [pos1 + read_len - L, pos1 + read_len - 1]; the extent is clipped to [1, len] of its reference, and a read with nothing left adds
+// nothing and is not in `reads`.  depth[r][p] = the kept reads whose clipped extent holds position p of reference r, a 32-bit count.
+// Per chosen reference, in header order, the maximal intervals of constant depth > 0 are the runs (start0, end0, depth), 0-based and
+// half-open; two reads that abut at equal depth form one run, depth 0 is not a run.  Totals: reads, runs, covered_bases =
+// sum (end0 - start0), fragment_bases = sum depth * (end0 - start0) (64-bit, = the sum of the clipped extents' lengths), max_depth.
+//
+// The table is one int32 slot per base of every chosen reference plus one closing slot behind its last base (the -1 of a read that
+// ends on the last base), the references end to end in header order, each beginning on a multiple of 4 slots (16-byte loads; up to
+// 3 slots of padding that nothing writes).  Slot p - 1 of a reference holds depth[p] - depth[p - 1]: a run boundary is exactly a
+// non-zero slot, and a +1 and a -1 that cancel leave none.  A reference's slots add up to 0, so no depth carries into the next.
+//
+//   k_cv_marks    one lane per kept read: atomicAdd(+1) at slot lo - 1 and atomicAdd(-1) at slot hi, neither with a return value;
+//                 the reads that added are reduced by ballot, one 64-bit atomic per workgroup
+//   k_cv_tiles    one workgroup per tile of CV_TILE slots (a reference's tiles begin at its first slot: no tile holds two
+//                 references), four 16-byte loads per lane: the tile's sum and its number of non-zero slots
+//   k_bam_scan    twice: the prefix of the tile sums (modulo 2^32: a depth is below 2^31) and of the tile counts.  The depth in
+//                 front of a tile is its prefix less that of its reference's first tile: the scan starts again at every reference
+//   k_cv_runs     per tile: the lanes' sums are scanned over the wave by shuffles and over the four loads and waves through LDS, on
+//                 top of the tile's prefix; the non-zero slots are compacted by ballots into entries (reference, position, depth
+//                 behind it) at the tile's offset, in position order
+//   k_cv_keep / k_bam_scan / k_cv_close   entry k's run ends at entry k + 1's position; the last non-zero slot of a reference
+//                 brings the depth to 0.  The entries of depth 0 are dropped by this second compaction (256 entries per
+//                 workgroup, ballots); the totals are reduced by wave sums, one atomic per wave and total
+//   k_cv_textlen  one lane per run: name length + the three decimal widths + 4, and the workgroup's sum
+//   k_bam_scan    the 64-bit exclusive prefix of the workgroups' sums
+//   k_cv_text     each lane writes its own line at the workgroup's prefix + a scan of the lengths within the workgroup
+// Bound: fewer than 2^31 reads between begin and finish (add fails above it), so every depth and prefix is below 2^31.
+// Device memory: 4 bytes per chosen base from begin to finish (12.4 GB for hg38) + 24 per tile, 12 per non-zero slot inside finish,
+// then 16 per run until the next begin or close; 13 bytes per kept read inside a call of add; 4 per run + the text inside text.
+
+#define CV_TILE PMX_COVERAGE_TILE             // slots per tile: 256 lanes x 4 loads x 4 slots
+#define CV_MAX_READS (1ull << 31)
+
+namespace {
+struct CvSeg {          // a chosen reference: its first slot, its first tile, its slots (length + 1), its id
+    u64 slot0;
+    u32 tile0, nslots;
+    int ref;
+    u32 pad;
+};
+}  // namespace
+
+// tab[2 * r] = the first slot of reference r (-1: the reference is not chosen), tab[2 * r + 1] = its length
+__global__ void __launch_bounds__(256) k_cv_marks(const int *__restrict__ ref, const int *__restrict__ pos, const int *__restrict__ len,
+                                                  const u8 *__restrict__ rev, u64 n, const long long *__restrict__ tab, u32 nref, u32 ext,
+                                                  int *__restrict__ slots, unsigned long long *__restrict__ added)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x;
+    const u64 i = (u64)blockIdx.x * 256u + t;
+    bool hit = false;
+    if (i < n && ref[i] >= 0 && (u32)ref[i] < nref) {
+        const long long first = tab[2u * (u32)ref[i]], top = tab[2u * (u32)ref[i] + 1u];
+        long long lo, hi;
+        if (first >= 0 && fp_extent(pos[i], len[i], rev[i] != 0, ext, top, lo, hi)) {      // (1 <= lo <= hi <= top: slots lo - 1 .. hi exist)
+            hit = true;
+            atomicAdd(&slots[first + lo - 1], 1);
+            atomicAdd(&slots[first + hi], -1);
+        }
+    }
+    const u64 m = __ballot(hit);
+    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (t == 0) {
+        const u32 c = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        if (c) atomicAdd(added, (unsigned long long)c);
+    }
+}
+
+// the last reference of seg[0, nc) whose first tile is not behind `tile` (the same in every lane)
+__device__ __forceinline__ u32 cv_seg_of(const CvSeg *__restrict__ seg, u32 nc, u32 tile)
+{
+    u32 a = 0, z = nc;
+    while (z - a > 1u) {
+        const u32 mid = (a + z) / 2u;
+        if (seg[mid].tile0 <= tile) a = mid;
+        else z = mid;
+    }
+    return a;
+}
+
+// load j of lane t holds the slots (j * 256 + t) * 4 .. + 3 of the tile; a reference's slots are padded with zeros to a multiple of 4
+__device__ __forceinline__ void cv_load(const int *__restrict__ slots, u64 base, u32 n, u32 t, int4 v[4])
+{
+#pragma unroll
+    for (u32 j = 0; j < 4u; j++) {
+        const u32 e = (j * 256u + t) * 4u;
+        v[j] = e < n ? *reinterpret_cast<const int4 *>(slots + base + e) : make_int4(0, 0, 0, 0);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_cv_tiles(const int *__restrict__ slots, const CvSeg *__restrict__ seg, u32 nc,
+                                                  u32 *__restrict__ tsum, u32 *__restrict__ tcnt)
+{
+    __shared__ u32 s_s[4], s_c[4];
+    const u32 t = threadIdx.x, tile = blockIdx.x;
+    const CvSeg S = seg[cv_seg_of(seg, nc, tile)];
+    const u32 off = (tile - S.tile0) * CV_TILE, n = S.nslots - off < CV_TILE ? S.nslots - off : CV_TILE;
+    int4 v[4];
+    cv_load(slots, S.slot0 + off, n, t, v);
+    u32 s = 0, c = 0;
+#pragma unroll
+    for (u32 j = 0; j < 4u; j++) {
+        s += (u32)v[j].x + (u32)v[j].y + (u32)v[j].z + (u32)v[j].w;
+        c += (v[j].x != 0) + (v[j].y != 0) + (v[j].z != 0) + (v[j].w != 0);
+    }
+    s = (u32)cx_wave_sum((u64)s);
+    c = (u32)cx_wave_sum((u64)c);
+    if ((t & 63u) == 0) {
+        s_s[t >> 6] = s;
+        s_c[t >> 6] = c;
+    }
+    __syncthreads();
+    if (t == 0) {
+        tsum[tile] = s_s[0] + s_s[1] + s_s[2] + s_s[3];
+        tcnt[tile] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+    }
+}
+
+// inclusive scan of x over the wave
+__device__ __forceinline__ u32 cv_wave_scan(u32 x, u32 lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 y = __shfl_up(x, o, 64);
+        if (lane >= (u32)o) x += y;
+    }
+    return x;
+}
+
+__global__ void __launch_bounds__(256) k_cv_runs(const int *__restrict__ slots, const CvSeg *__restrict__ seg, u32 nc,
+                                                 const u64 *__restrict__ psum, const u64 *__restrict__ pcnt, int *__restrict__ eref,
+                                                 u32 *__restrict__ epos, u32 *__restrict__ edep)
+{
+    __shared__ u32 s_s[4][4], s_c[4][4];          // [load][wave]
+    const u32 t = threadIdx.x, lane = t & 63u, w = t >> 6, tile = blockIdx.x;
+    const CvSeg S = seg[cv_seg_of(seg, nc, tile)];
+    const u32 off = (tile - S.tile0) * CV_TILE, n = S.nslots - off < CV_TILE ? S.nslots - off : CV_TILE;
+    const u32 carry = (u32)psum[tile] - (u32)psum[S.tile0];      // the depth in front of the tile: the scan starts again with the reference
+    int4 v[4];
+    cv_load(slots, S.slot0 + off, n, t, v);
+    const u64 below = (1ull << lane) - 1ull;
+    u32 own[4], incl[4], before[4];
+#pragma unroll
+    for (u32 j = 0; j < 4u; j++) {
+        own[j] = (u32)v[j].x + (u32)v[j].y + (u32)v[j].z + (u32)v[j].w;
+        incl[j] = cv_wave_scan(own[j], lane);
+        const u64 m0 = __ballot(v[j].x != 0), m1 = __ballot(v[j].y != 0), m2 = __ballot(v[j].z != 0), m3 = __ballot(v[j].w != 0);
+        before[j] = (u32)(__popcll(m0 & below) + __popcll(m1 & below) + __popcll(m2 & below) + __popcll(m3 & below));
+        if (lane == 63u) s_s[j][w] = incl[j];
+        if (lane == 0) s_c[j][w] = (u32)(__popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3));
+    }
+    __syncthreads();
+    const u64 out0 = pcnt[tile];
+#pragma unroll
+    for (u32 j = 0; j < 4u; j++) {
+        u32 bs = carry, bc = 0;
+        for (u32 k = 0; k < j * 4u + w; k++) {       // the loads and waves in front of this one
+            bs += s_s[k >> 2][k & 3u];
+            bc += s_c[k >> 2][k & 3u];
+        }
+        u32 run = bs + incl[j] - own[j];
+        u64 o = out0 + bc + before[j];
+        const u32 p0 = off + (j * 256u + t) * 4u;
+        const int x[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+        for (u32 e = 0; e < 4u; e++) {
+            run += (u32)x[e];
+            if (x[e] != 0) {
+                eref[o] = S.ref;
+                epos[o] = p0 + e;
+                edep[o] = run;
+                o++;
+            }
+        }
+    }
+}
+
+// entry k begins a run: its depth is above 0 and the next entry, of the same reference, ends it
+__device__ __forceinline__ bool cv_keeps(const int *__restrict__ eref, const u32 *__restrict__ edep, u64 k, u64 n)
+{
+    return k + 1u < n && (int)edep[k] > 0 && eref[k + 1u] == eref[k];
+}
+
+__global__ void __launch_bounds__(256) k_cv_keep(const int *__restrict__ eref, const u32 *__restrict__ edep, u64 n, u32 *__restrict__ kcnt)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x;
+    const u64 m = __ballot(cv_keeps(eref, edep, (u64)blockIdx.x * 256u + t, n));
+    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// tot[0] += covered bases, tot[1] += fragment bases, tot[2] = max(tot[2], depth)
+__global__ void __launch_bounds__(256) k_cv_close(const int *__restrict__ eref, const u32 *__restrict__ epos, const u32 *__restrict__ edep, u64 n,
+                                                  const u64 *__restrict__ kbase, int *__restrict__ rref, u32 *__restrict__ rstart,
+                                                  u32 *__restrict__ rend, u32 *__restrict__ rdepth, unsigned long long *__restrict__ tot)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x, lane = t & 63u;
+    const u64 k = (u64)blockIdx.x * 256u + t;
+    const bool keep = cv_keeps(eref, edep, k, n);
+    const u64 m = __ballot(keep);
+    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    u64 width = 0, area = 0;
+    u32 depth = 0;
+    if (keep) {
+        u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
+        for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
+        depth = edep[k];
+        const u32 a = epos[k], z = epos[k + 1u];
+        rref[o] = eref[k];
+        rstart[o] = a;
+        rend[o] = z;
+        rdepth[o] = depth;
+        width = (u64)(z - a);
+        area = width * depth;
+    }
+    width = cx_wave_sum(width);
+    area = cx_wave_sum(area);
+    for (int d = 32; d > 0; d >>= 1) {
+        const u32 y = __shfl_xor(depth, d, 64);
+        depth = y > depth ? y : depth;
+    }
+    if (lane == 0 && m) {
+        atomicAdd(&tot[0], (unsigned long long)width);
+        atomicAdd(&tot[1], (unsigned long long)area);
+        atomicMax(&tot[2], (unsigned long long)depth);
+    }
+}
+
+__device__ __forceinline__ u32 cv_width(u32 v)      // the decimal digits of v
+{
+    u32 w = 1;
+    for (; v >= 10u; v /= 10u) w++;
+    return w;
+}
+
+__global__ void __launch_bounds__(256) k_cv_textlen(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
+                                                    const u32 *__restrict__ rdepth, u64 n, const u32 *__restrict__ noff,
+                                                    u32 *__restrict__ len, u32 *__restrict__ wsum)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x;
+    const u64 i = (u64)blockIdx.x * 256u + t;
+    u32 l = 0;
+    if (i < n) {
+        const u32 r = (u32)rref[i];
+        l = noff[r + 1u] - noff[r] + cv_width(rstart[i]) + cv_width(rend[i]) + cv_width(rdepth[i]) + 4u;
+        len[i] = l;
+    }
+    l = (u32)cx_wave_sum((u64)l);
+    if ((t & 63u) == 0) s_w[t >> 6] = l;
+    __syncthreads();
+    if (t == 0) wsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// the digits of v in front of `end`; returns where they begin
+__device__ __forceinline__ u8 *cv_digits(u8 *end, u32 v)
+{
+    do {
+        *--end = (u8)('0' + v % 10u);
+        v /= 10u;
+    } while (v);
+    return end;
+}
+
+__global__ void __launch_bounds__(256) k_cv_text(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
+                                                 const u32 *__restrict__ rdepth, u64 n, const u32 *__restrict__ noff, const u8 *__restrict__ names,
+                                                 const u32 *__restrict__ len, const u64 *__restrict__ wbase, u8 *__restrict__ out)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x, lane = t & 63u;
+    const u64 i = (u64)blockIdx.x * 256u + t;
+    const u32 l = i < n ? len[i] : 0u;
+    const u32 incl = cv_wave_scan(l, lane);
+    if (lane == 63u) s_w[t >> 6] = incl;
+    __syncthreads();
+    if (i >= n) return;
+    u64 o = wbase[blockIdx.x] + incl - l;
+    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
+    const u32 r = (u32)rref[i];
+    u8 *p = out + o;
+    for (u32 c = noff[r]; c < noff[r + 1u]; c++) *p++ = names[c];
+    u8 *q = out + o + l;                // the line from its end: LF, depth, TAB, end, TAB, start, TAB
+    *--q = '\n';
+    q = cv_digits(q, rdepth[i]);
+    *--q = '\t';
+    q = cv_digits(q, rend[i]);
+    *--q = '\t';
+    q = cv_digits(q, rstart[i]);
+    *--q = '\t';                        // (q == p: the lengths are k_cv_textlen's)
+}
+
+namespace {
+
+enum { CV_NONE = 0, CV_TABLE = 1, CV_RUNS = 2 };
+
+void coverage_free(pmx_dbam *b)
+{
+    for (void *p : {(void *)b->d_cv, (void *)b->d_cv_tab, (void *)b->d_cv_seg, (void *)b->d_cv_names, (void *)b->d_cv_runs})
+        if (p) (void)hipFree(p);
+    b->d_cv = nullptr;
+    b->d_cv_tab = nullptr;
+    b->d_cv_seg = nullptr;
+    b->d_cv_names = nullptr;
+    b->d_cv_runs = nullptr;
+    b->cv_state = CV_NONE;
+    b->cv_slots = b->cv_tiles = b->cv_reads = b->cv_runs = b->cv_held = 0;
+    b->cv_nc = b->cv_ext = 0;
+    for (u64 &x : b->cv_tot) x = 0;
+}
+
+// the arrays of the runs in their one block: reference, start, end, depth (4 bytes per run each)
+struct CvRuns {
+    int *ref;
+    u32 *start, *end, *depth;
+    CvRuns(u8 *p, u64 n) : ref((int *)p), start((u32 *)(p + 4 * n)), end((u32 *)(p + 8 * n)), depth((u32 *)(p + 12 * n)) {}
+};
+
+int coverage_begin_impl(pmx_dbam *b, u32 extend, const uint8_t *use_ref)
+{
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    HIPOK(hipSetDevice(b->device));
+    HIPOK(hipStreamSynchronize(b->stream));
+    coverage_free(b);
+    const u64 nref = b->ref_names.size();
+    std::vector<long long> tab(2 * std::max<u64>(nref, 1), -1);
+    std::vector<CvSeg> seg;
+    std::vector<u32> noff(nref + 1, 0);
+    std::string names;
+    u64 slots = 0, tiles = 0;
+    for (u64 r = 0; r < nref; r++) {
+        noff[r] = (u32)names.size();
+        names += b->ref_names[r];
+        if (use_ref && use_ref[r] == 0) continue;
+        const u64 len = (u64)std::max<int64_t>(b->ref_lens[r], 0);
+        if (len >= 0xffffffffull) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_begin: a reference of 2^32 - 1 bases or more");
+        tab[2 * r] = (long long)slots;
+        tab[2 * r + 1] = (long long)len;
+        seg.push_back(CvSeg{slots, (u32)tiles, (u32)(len + 1), (int)r, 0u});
+        slots += (len + 1 + 3) / 4 * 4;
+        tiles += (len + 1 + CV_TILE - 1) / CV_TILE;
+        if (tiles >= (1ull << 31)) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_begin: 2^31 tiles or more");
+    }
+    noff[nref] = (u32)names.size();
+    if (seg.empty()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_begin: no chosen reference");
+    const u32 nc = (u32)seg.size();
+    seg.push_back(CvSeg{slots, (u32)tiles, 0u, -1, 0u});        // (the end of the last reference's tiles)
+    hipStream_t st = b->stream;
+    HIPOK(hipMalloc((void **)&b->d_cv_tab, 8 * tab.size()));
+    HIPOK(hipMalloc((void **)&b->d_cv_seg, sizeof(CvSeg) * seg.size()));
+    HIPOK(hipMalloc((void **)&b->d_cv_names, 4 * noff.size() + std::max<u64>(names.size(), 1)));
+    if (hipMalloc((void **)&b->d_cv, 4 * slots) != hipSuccess) {
+        (void)hipGetLastError();
+        coverage_free(b);
+        return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_coverage_begin: out of device memory for the table: " + std::to_string(4 * slots) +
+                                           " bytes asked for (4 per base of the chosen references)");
+    }
+    HIPOK(hipMemcpyAsync(b->d_cv_tab, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemcpyAsync(b->d_cv_seg, seg.data(), sizeof(CvSeg) * seg.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemcpyAsync(b->d_cv_names, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, st));
+    if (!names.empty()) HIPOK(hipMemcpyAsync(b->d_cv_names + 4 * noff.size(), names.data(), names.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemsetAsync(b->d_cv, 0, 4 * slots, st));
+    HIPOK(hipStreamSynchronize(st));       // (tab, seg, noff and names are locals)
+    b->cv_state = CV_TABLE;
+    b->cv_slots = slots;
+    b->cv_tiles = tiles;
+    b->cv_nc = nc;
+    b->cv_ext = extend;
+    b->cv_held = 4 * slots;
+    if (b->st) stream_note(*b);
+    return 0;
+}
+
+int coverage_add_impl(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, uint64_t *reads_added)
+{
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    if (!reads_added) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_add: null output");
+    *reads_added = 0;
+    if (b->cv_state != CV_TABLE) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_add: no table: call pmx_dbam_coverage_begin first");
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    CxRecs R;
+    if (int rc = cx_filter(b, mapq_min, flag_exclude, 0, true, R)) return rc;
+    if (R.n == 0) return 0;
+    if (b->cv_reads + R.n >= CV_MAX_READS)      // (before a mark is made: the table stays as it is)
+        return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_add: 2^31 reads or more: the depth is a 32-bit count");
+    DevAlloc d_added;
+    HIPOK(hipMalloc(&d_added.p, 8));
+    HIPOK(hipMemsetAsync(d_added.p, 0, 8, st));
+    hipLaunchKernelGGL(k_cv_marks, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
+                       R.rev.as<u8>(), R.n, b->d_cv_tab, (u32)b->ref_names.size(), b->cv_ext, b->d_cv, d_added.as<unsigned long long>());
+    HIPOK(hipGetLastError());
+    unsigned long long added = 0;
+    HIPOK(hipMemcpyAsync(&added, d_added.p, 8, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    b->cv_reads += added;
+    *reads_added = added;
+    return 0;
+}
+
+// device bytes a call holds for its own duration, counted into the handle's while it runs
+struct CvHold {
+    pmx_dbam *b;
+    u64 n = 0;
+    explicit CvHold(pmx_dbam *h) : b(h) {}
+    void add(u64 bytes)
+    {
+        n += bytes;
+        b->cv_held += bytes;
+        if (b->st) stream_note(*b);
+    }
+    ~CvHold() { b->cv_held -= std::min(n, b->cv_held); }       // (a pileup freed meanwhile holds nothing)
+};
+
+// the work of finish on a handle that holds a table; a failure leaves the handle for the caller to clear
+int coverage_finish_run(pmx_dbam *b, uint64_t *totals)
+{
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    const u64 nt = b->cv_tiles;
+    u64 tot[2] = {0, 0}, ne = 0, nruns = 0;
+    unsigned long long sums[3] = {0, 0, 0};
+    {
+        DevAlloc d_t, d_p, d_tot, d_e;      // tile sums and counts; their prefixes; totals; the entries
+        HIPOK(hipMalloc(&d_t.p, 8 * nt));
+        HIPOK(hipMalloc(&d_p.p, 16 * nt));
+        HIPOK(hipMalloc(&d_tot.p, 64));
+        HIPOK(hipMemsetAsync(d_tot.p, 0, 64, st));
+        u32 *tsum = d_t.as<u32>(), *tcnt = tsum + nt;
+        u64 *psum = d_p.as<u64>(), *pcnt = psum + nt, *dt = d_tot.as<u64>();
+        b->cv_held += 24 * nt;
+        if (b->st) stream_note(*b);
+        hipLaunchKernelGGL(k_cv_tiles, dim3((unsigned)nt), dim3(256), 0, st, b->d_cv, b->d_cv_seg, b->cv_nc, tsum, tcnt);
+        HIPOK(hipGetLastError());
+        hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, tsum, tcnt, nt, psum, dt);
+        HIPOK(hipGetLastError());
+        hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, tcnt, tcnt, nt, pcnt, dt + 2);
+        HIPOK(hipGetLastError());
+        HIPOK(hipMemcpyAsync(tot, dt, 16, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+        ne = tot[1];
+        if ((u32)tot[0] != 0) {             // (every read adds +1 and -1 to its reference)
+            coverage_free(b);
+            return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_finish: the table does not add up to 0");
+        }
+        if (ne) {
+            if (hipMalloc(&d_e.p, 12 * ne) != hipSuccess) {
+                (void)hipGetLastError();
+                coverage_free(b);
+                return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_coverage_finish: out of device memory for " + std::to_string(ne) + " run boundaries");
+            }
+            b->cv_held += 12 * ne;
+            if (b->st) stream_note(*b);
+            int *eref = d_e.as<int>();
+            u32 *epos = (u32 *)(eref + ne), *edep = epos + ne;
+            hipLaunchKernelGGL(k_cv_runs, dim3((unsigned)nt), dim3(256), 0, st, b->d_cv, b->d_cv_seg, b->cv_nc, psum, pcnt, eref, epos, edep);
+            HIPOK(hipGetLastError());
+            HIPOK(hipStreamSynchronize(st));
+        }
+        (void)hipFree(b->d_cv);             // the table has become entries
+        b->d_cv = nullptr;
+        b->cv_held -= 4 * b->cv_slots + 24 * nt;
+        if (ne) {
+            const u64 nwg = (ne + 255) / 256;
+            DevAlloc d_k, d_kb;
+            HIPOK(hipMalloc(&d_k.p, 4 * nwg));
+            HIPOK(hipMalloc(&d_kb.p, 8 * nwg));
+            const int *eref = d_e.as<int>();
+            const u32 *epos = (const u32 *)(eref + ne), *edep = epos + ne;
+            hipLaunchKernelGGL(k_cv_keep, dim3((unsigned)nwg), dim3(256), 0, st, eref, edep, ne, d_k.as<u32>());
+            HIPOK(hipGetLastError());
+            hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), nwg, d_kb.as<u64>(), dt + 4);
+            HIPOK(hipGetLastError());
+            HIPOK(hipMemcpyAsync(&nruns, dt + 4, 8, hipMemcpyDeviceToHost, st));
+            HIPOK(hipStreamSynchronize(st));
+            if (nruns) {
+                if (hipMalloc((void **)&b->d_cv_runs, 16 * nruns) != hipSuccess) {
+                    (void)hipGetLastError();
+                    coverage_free(b);
+                    return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_coverage_finish: out of device memory for " + std::to_string(nruns) + " runs");
+                }
+                b->cv_held += 16 * nruns;
+                if (b->st) stream_note(*b);
+                const CvRuns V(b->d_cv_runs, nruns);
+                HIPOK(hipMemsetAsync(dt, 0, 24, st));
+                hipLaunchKernelGGL(k_cv_close, dim3((unsigned)nwg), dim3(256), 0, st, eref, epos, edep, ne, d_kb.as<u64>(), V.ref, V.start, V.end,
+                                   V.depth, d_tot.as<unsigned long long>());
+                HIPOK(hipGetLastError());
+                HIPOK(hipMemcpyAsync(sums, dt, 24, hipMemcpyDeviceToHost, st));
+                HIPOK(hipStreamSynchronize(st));
+            }
+            b->cv_held -= 12 * ne;
+        }
+    }
+    b->cv_state = CV_RUNS;
+    b->cv_slots = 0;
+    b->cv_runs = nruns;
+    b->cv_tot[0] = b->cv_reads;
+    b->cv_tot[1] = nruns;
+    b->cv_tot[2] = sums[0];
+    b->cv_tot[3] = sums[1];
+    b->cv_tot[4] = sums[2];
+    for (int k = 0; k < 5; k++) totals[k] = b->cv_tot[k];
+    return 0;
+}
+
+// A failure past the state check clears the pileup: the table may be freed or half read by then, and no later add, finish, runs or
+// text may work on what is left of it.
+int coverage_finish_impl(pmx_dbam *b, uint64_t *totals)
+{
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    if (!totals) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_finish: null output");
+    for (int k = 0; k < 5; k++) totals[k] = 0;
+    if (b->cv_state != CV_TABLE) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_finish: no table: call pmx_dbam_coverage_begin first");
+    int rc = PMX_DBAM_ERR_OPEN;
+    try {
+        rc = coverage_finish_run(b, totals);
+    } catch (...) {
+        coverage_free(b);
+        throw;
+    }
+    if (rc) coverage_free(b);
+    return rc;
+}
+
+int coverage_range(pmx_dbam *b, const char *fn, int64_t first, int64_t n)
+{
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    if (b->cv_state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": no runs: call pmx_dbam_coverage_finish first");
+    if (first < 0 || n < 0 || (u64)first > b->cv_runs || (u64)n > b->cv_runs - (u64)first)
+        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": range outside the runs");
+    return 0;
+}
+
+int coverage_runs_impl(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth)
+{
+    if (int rc = coverage_range(b, "pmx_dbam_coverage_runs", first, n)) return rc;
+    if (!ref || !start || !end || !depth) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_runs: null output");
+    HIPOK(hipSetDevice(b->device));
+    HIPOK(hipStreamSynchronize(b->stream));
+    if (n == 0) return 0;
+    const CvRuns V(b->d_cv_runs, b->cv_runs);
+    HIPOK(hipMemcpy(ref, V.ref + first, 4 * (u64)n, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(start, V.start + first, 4 * (u64)n, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(end, V.end + first, 4 * (u64)n, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(depth, V.depth + first, 4 * (u64)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int64_t coverage_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
+{
+    if (int rc = coverage_range(b, "pmx_dbam_coverage_text", first, n)) return rc;
+    if (buf && cap < 0) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_text: a negative capacity");
+    if (n == 0) return 0;
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    const u64 m = (u64)n, nwg = (m + 255) / 256, nref = b->ref_names.size();
+    const CvRuns V(b->d_cv_runs, b->cv_runs);
+    const u32 *noff = (const u32 *)b->d_cv_names;
+    const u8 *names = b->d_cv_names + 4 * (nref + 1);
+    DevAlloc d_len, d_w, d_wb, d_tot, d_text;
+    CvHold held(b);
+    held.add(4 * m + 12 * nwg + 16);
+    HIPOK(hipMalloc(&d_len.p, 4 * m));
+    HIPOK(hipMalloc(&d_w.p, 4 * nwg));
+    HIPOK(hipMalloc(&d_wb.p, 8 * nwg));
+    HIPOK(hipMalloc(&d_tot.p, 16));
+    hipLaunchKernelGGL(k_cv_textlen, dim3((unsigned)nwg), dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff,
+                       d_len.as<u32>(), d_w.as<u32>());
+    HIPOK(hipGetLastError());
+    hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_w.as<u32>(), d_w.as<u32>(), nwg, d_wb.as<u64>(), d_tot.as<u64>());
+    HIPOK(hipGetLastError());
+    u64 bytes = 0;
+    HIPOK(hipMemcpyAsync(&bytes, d_tot.p, 8, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    if (!buf) return (int64_t)bytes;
+    if ((u64)cap < bytes) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_text: the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
+    if (hipMalloc(&d_text.p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_coverage_text: out of device memory for " + std::to_string(bytes) + " bytes of text");
+    }
+    held.add(bytes);
+    hipLaunchKernelGGL(k_cv_text, dim3((unsigned)nwg), dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff, names,
+                       d_len.as<u32>(), d_wb.as<u64>(), d_text.as<u8>());
+    HIPOK(hipGetLastError());
+    HIPOK(hipMemcpyAsync(buf, d_text.p, bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    return (int64_t)bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pmx_dbam_coverage_begin(pmx_dbam *b, uint32_t extend, const uint8_t *use_ref)
+{
+    try {
+        return coverage_begin_impl(b, extend, use_ref);
+    } catch (const std::exception &e) {
+        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_begin: ") + e.what());
+    }
+}
+
+int pmx_dbam_coverage_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t *reads_added)
+{
+    try {
+        return coverage_add_impl(b, mapq_min, flag_exclude, reads_added);
+    } catch (const std::exception &e) {
+        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_add: ") + e.what());
+    }
+}
+
+int pmx_dbam_coverage_finish(pmx_dbam *b, uint64_t totals[5])
+{
+    try {
+        return coverage_finish_impl(b, totals);
+    } catch (const std::exception &e) {
+        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_finish: ") + e.what());
+    }
+}
+
+int pmx_dbam_coverage_runs(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth)
+{
+    try {
+        return coverage_runs_impl(b, first, n, ref, start, end, depth);
+    } catch (const std::exception &e) {
+        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_runs: ") + e.what());
+    }
+}
+
+int64_t pmx_dbam_coverage_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
+{
+    try {
+        return coverage_text_impl(b, first, n, buf, cap);
+    } catch (const std::exception &e) {
+        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_text: ") + e.what());
+    }
+}
+
+}  // extern "C"

@@ -99,6 +99,7 @@ u64 stream_held(const pmx_dbam &b)
     h += s->cx_n * 13;
     h += b.bc_bins * 4;
     h += b.pk_lines * 28;
+    h += b.cv_held;
     return h;
 }
 void stream_note(pmx_dbam &b) { b.st->peak = std::max(b.st->peak, stream_held(b)); }

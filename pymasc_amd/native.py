@@ -125,6 +125,11 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_peakcount_add": (_int, [_vp, _u32, _u32, _vp]),
     "pmx_dbam_peakcount_copy": (_int, [_vp, _i64, _i64, _vp]),
     "pmx_dbam_peakcount_totals": (_int, [_vp, _vp, _vp]),
+    "pmx_dbam_coverage_begin": (_int, [_vp, _u32, _vp]),
+    "pmx_dbam_coverage_add": (_int, [_vp, _u32, _u32, _pu64]),
+    "pmx_dbam_coverage_finish": (_int, [_vp, _vp]),
+    "pmx_dbam_coverage_runs": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "pmx_dbam_coverage_text": (_i64, [_vp, _i64, _i64, _vp, _i64]),
     "pmx_dbam_set_exclude": (_int, [_vp, _i32, _vp, _vp, _vp]),
     "pmx_dbam_exclude_intervals": (_i64, [_vp, _i64, _vp, _vp, _vp]),
     "pmx_dbam_excluded": (_int, [_vp, _pu64, _pu64]),
@@ -291,6 +296,14 @@ class AlignmentReader(NativeReader):
         from .peaks import from_reader
         self._check_open()
         return from_reader(self, peaks, mapq_criteria, references, extend)
+
+    def coverage(self, mapq_criteria: int = 0, references=None, extend: int = 0):
+        """The reads of ``bin_counts`` piled up base by base into runs of constant depth: a ``pymasc_amd.coverage.Coverage``
+        (``coverage.from_reader``).  ``extend`` as for ``bin_counts``.  A device reader counts on the GPU with
+        arrays of its own: the arrays of the last ``decode`` stay as they are."""
+        from .coverage import from_reader
+        self._check_open()
+        return from_reader(self, mapq_criteria, references, extend)
 
     # ---- excluded regions (pymasc_amd.region_mask; DESIGN.md 7.15) ----
     _exclude = None

@@ -39,7 +39,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
         chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None,
         fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None,
-        peaks=None, peaks_extend: int = 0):
+        peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto"):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -81,9 +81,17 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     fingerprint counts, each covering ``peaks_extend`` bases from its 5' end (0: its own length), counted per line of the file
     and in at least one line -- FRiP, its enrichment over the share of the genome the lines cover, a row per chromosome and a
     BED table of the reads per line.  Counted where ``complexity`` is counted.  No line's chromosome among the references:
-    ValueError before any table is written."""
+    ValueError before any table is written.
+    ``coverage``: rank 0 also writes ``<stem>_coverage.bedGraph`` (pymasc_amd.coverage): the reads the
+    fingerprint counts, each covering ``coverage_extend`` bases from its 5' end (0: its own length), piled up base by base and
+    written as runs of constant depth above 0.  An integer ``coverage_extend`` is counted where ``complexity`` is counted.
+    ``"auto"`` (the default) extends to the run's own fragment-length estimate, ``stats.genome_wide_stats(...).est_lib_len``
+    with the run's statistics options, whether or not ``stats`` writes them; it exists only after the correlation, so rank 0
+    counts on one more read of the file, and a stream (``-``, a FIFO) with ``"auto"`` is a ValueError before anything runs.  The
+    device table is 4 bytes per chosen base (12.4 GB for hg38)."""
     check_bed_sizes(bam_path, chrom_sizes)
     s = _settings(locals())
+    _check_coverage_input(s, bam_path)
     from .kmer_track import is_fasta
     bam = track = None              # a reader opened here for the estimate and handed on: the file is inflated once per run
     try:
@@ -139,10 +147,13 @@ class _Settings:
     fingerprint_control: object     # None, or the _FingerprintControl counted once for the call
     peaks: object                   # None, or the lines of the peak file, read once for the call (peaks.open_peaks)
     peaks_extend: int
+    coverage: bool
+    coverage_extend: object         # an int (0: every read's own length), or "auto": the run's fragment-length estimate
     save_mappability_stats: bool
     device: int
     ingest: bool
     stat_opts: Optional[dict]
+    stat_kw: dict                   # the keywords of stats.genome_wide_stats, with ``stats`` or without
     rank: int
     world: int
 
@@ -180,15 +191,26 @@ def _settings(kw: dict) -> _Settings:
         from .peaks import open_peaks
         given["peaks"] = open_peaks(kw["peaks"], bool(ingest), reader_device(kw["context"], device, bool(ingest)))
     given["peaks_extend"] = int(kw["peaks_extend"])
+    extend = kw["coverage_extend"]
+    if extend != "auto" and (isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0):
+        raise ValueError("coverage_extend is \"auto\" or an integer of at least 0")
+    given.update(coverage=bool(kw["coverage"]), coverage_extend=extend if extend == "auto" else int(extend))
     if int(kw["fingerprint_bin"]) < 1 or int(kw["fingerprint_extend"]) < 0:
         raise ValueError("fingerprint_bin is at least 1 and fingerprint_extend at least 0")
     control = kw["fingerprint_control"]
     given.update(fingerprint=bool(kw["fingerprint"]) or control is not None, fingerprint_bin=int(kw["fingerprint_bin"]),
                  fingerprint_extend=int(kw["fingerprint_extend"]),
                  fingerprint_control=None if control is None else _FingerprintControl(control))
-    given.update(device=device, ingest=bool(ingest), rank=rank, world=world,
-                 stat_opts={k: kw[k] for k in _STAT_OPTS} if kw["stats"] else None)
+    stat_kw = {k: kw[k] for k in _STAT_OPTS}
+    given.update(device=device, ingest=bool(ingest), rank=rank, world=world, stat_opts=stat_kw if kw["stats"] else None,
+                 stat_kw=stat_kw)
     return _Settings(**given)
+
+
+def _check_coverage_input(s: _Settings, path) -> None:
+    """ValueError for a stream whose pileup would need the run's own estimate: it cannot be read a second time."""
+    if s.coverage and s.coverage_extend == "auto" and is_stream(path):
+        raise ValueError("'{}' is a stream and cannot be read twice: give coverage_extend an integer".format(path))
 
 
 def _estimate(s: _Settings, path, keep: bool):
@@ -278,16 +300,17 @@ def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool, mask=No
 
 def _run_file(s: _Settings, path, read_len: int, known, bam, track, mask=None):
     """One file sharded over the ranks: (its genome-wide result, the counts taken beside it: a _ComplexityCount and a
-    _FingerprintCount and a _PeakCount as asked for).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's and the
+    _FingerprintCount, a _PeakCount and a _CoverageCount as asked for).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's and the
     track's open readers, or None for run_sharded to open its own.  One rank: run_sharded's one ``reader_hook`` serves every
     count (``_hooks``)."""
     counted = [c(s) for c, on in ((_ComplexityCount, s.complexity), (_FingerprintCount, s.fingerprint),
-                                     (_PeakCount, s.peaks is not None)) if on]
+                                     (_PeakCount, s.peaks is not None), (_CoverageCount, s.coverage)) if on]
+    hooks = [c.hook for c in counted if c.hooked]
     result = run_sharded(path, s.max_shift, read_len, s.mapq_criteria, bigwig_path=s.mappability_path,
                          references=s.references, skip_ncc=s.skip_ncc, device=s.device, chrom2mappable_len=known,
                          group=s.group, context=s.context, device_ingest=s.ingest, bam=bam, chromfilter=s.chromfilter,
                          track=track, chrom_sizes=s.chrom_sizes, exclude_regions=mask if mask is not None else s.exclude_regions,
-                         reader_hook=_hooks([c.hook for c in counted]) if counted and s.world == 1 else None)
+                         reader_hook=_hooks(hooks) if hooks and s.world == 1 else None)
     return result, counted
 
 
@@ -307,16 +330,23 @@ def _hooks(hooks):
 def _write_file(s: _Settings, path, basename: str, result, read_len: int, counted) -> List[Path]:
     """Rank 0's part after _run_file: ``outdir/<basename>_{cc,mscc,nreads}.tab``, with ``stat_opts`` ``<basename>_stats.tab``
     whose Name row is ``basename``, and the table of every count in ``counted`` (``<basename>_complexity.tab``,
-    ``<basename>_fingerprint.tab``, ``<basename>_peaks.tab``); the paths written."""
+    ``<basename>_fingerprint.tab``, ``<basename>_peaks.tab``, ``<basename>_coverage.bedGraph``); the paths written.  The
+    statistics are computed once, for ``_stats.tab`` and for a pileup that extends to their estimate."""
     out = Path(s.outdir)
     out.mkdir(parents=True, exist_ok=True)
     # write_tables names the tables after the stem of its path (table.py:185-188): a suffix keeps a dotted base name whole
     written = tables.write_tables(out / (basename + ".bam"), result)
+    from . import stats
+    memo = []
+
+    def statistics():
+        if not memo:
+            memo.append(stats.genome_wide_stats(result, read_len, **s.stat_kw))
+        return memo[0]
     if s.stat_opts is not None:     # every rank holds the same result: the statistics are rank 0's alone
-        from . import stats
-        written.append(stats.write_stats(out / basename, stats.genome_wide_stats(result, read_len, **s.stat_opts)))
+        written.append(stats.write_stats(out / basename, statistics()))
     for c in counted:
-        written.append(c.write(path, basename))
+        written.append(c.write(path, basename, statistics))
     return written
 
 
@@ -324,7 +354,9 @@ class _ComplexityCount:
     """The library complexity of one file's run (pymasc_amd.complexity).  ``hook`` is run_sharded's ``reader_hook`` on one
     rank: the count is taken on the reader that feeds the run (a stream: armed before the feed, summed window by window).
     ``write`` writes the table; without a count so far (several ranks) it first counts the chosen chromosomes on one more
-    read of the file, through the reader ``inputs.open_alignments`` gives a run of that many ranks."""
+    read of the file, through the reader ``inputs.open_alignments`` gives a run of that many ranks.  ``hooked``: whether the
+    count is taken in ``hook``; ``statistics``: the run's statistics, computed when called (``_write_file``)."""
+    hooked = True
 
     def __init__(self, s: _Settings):
         self.s = s
@@ -345,7 +377,7 @@ class _ComplexityCount:
             self.value = complexity.from_reader(reader, mapq, names)
         return after
 
-    def write(self, path, basename: str) -> Path:
+    def write(self, path, basename: str, statistics=None) -> Path:
         from . import complexity
         s = self.s
         if self.value is None:
@@ -367,6 +399,7 @@ class _FingerprintCount:
     """The bin counts of one file's run (pymasc_amd.fingerprint), taken where _ComplexityCount takes its own: ``hook`` on the
     reader that feeds the run (a stream: armed before the feed, every window added), ``write`` on one more read when there is
     no count so far."""
+    hooked = True
 
     def __init__(self, s: _Settings):
         self.s = s
@@ -391,7 +424,7 @@ class _FingerprintCount:
             self.value = fingerprint.from_reader(reader, *self._args(names))
         return after
 
-    def write(self, path, basename: str) -> Path:
+    def write(self, path, basename: str, statistics=None) -> Path:
         from . import fingerprint
         s = self.s
         if self.value is None:
@@ -403,6 +436,7 @@ class _FingerprintCount:
 
 class _PeakCount:
     """The reads per peak line of one file's run (pymasc_amd.peaks), taken where _FingerprintCount takes its own."""
+    hooked = True
 
     def __init__(self, s: _Settings):
         self.s = s
@@ -427,12 +461,82 @@ class _PeakCount:
             self.value = peaks.from_reader(reader, *self._args(names))
         return after
 
-    def write(self, path, basename: str) -> Path:
+    def write(self, path, basename: str, statistics=None) -> Path:
         from . import peaks
         s = self.s
         if self.value is None:
             self.value = _count_again(s, path, lambda r, names: peaks.from_reader(r, *self._args(names)))
         return peaks.write_peaks(Path(s.outdir) / basename, basename, self.value, s.peaks.source or "")
+
+
+class _CoverageCount:
+    """The fragment pileup of one file's run (pymasc_amd.coverage).  An integer ``coverage_extend`` is counted where
+    _FingerprintCount takes its own: a host reader's ``Coverage`` is kept for ``write``; a device reader's lines are formatted on
+    the GPU while the reader is open and kept in an unnamed temporary file in the output directory until ``write`` names them.
+    ``"auto"`` needs the run's statistics, so it is not hooked: ``write`` counts with ``statistics().est_lib_len`` on one more
+    read of the file (``_count_again``), as several ranks do for an integer."""
+
+    def __init__(self, s: _Settings):
+        self.s = s
+        self.value = None           # (extend, reads, chunks of lines)
+
+    hooked = property(lambda self: self.s.coverage_extend != "auto")
+    _armed = None
+
+    def _take(self, reader, names, extend: int, spool: bool):
+        """(extend, reads, the lines) of ``reader``'s pileup; ``spool``: the reader closes before they are written."""
+        from . import coverage
+        from .bam_device import DeviceBamReader
+        mapq = int(self.s.mapq_criteria)
+        if not isinstance(reader, DeviceBamReader):
+            c = coverage.from_reader(reader, mapq, names, extend)
+            return extend, c.reads, c.text_chunks()
+        acc = self._armed if self._armed is not None else coverage.device_count_of(reader, mapq, names, extend)
+        reads = acc.finish(reader)["reads"]
+        if not spool:
+            return extend, reads, acc.text_chunks(reader)
+        import tempfile
+        Path(self.s.outdir).mkdir(parents=True, exist_ok=True)
+        fp = tempfile.TemporaryFile(dir=str(self.s.outdir))
+        for chunk in acc.text_chunks(reader):
+            fp.write(chunk)
+        return extend, reads, _spooled(fp)
+
+    def hook(self, reader, names):
+        extend = int(self.s.coverage_extend)
+        if hasattr(reader, "arm_coverage"):
+            self._armed = reader.arm_coverage(int(self.s.mapq_criteria), names, extend)
+
+        def after():
+            try:
+                self.value = self._take(reader, names, extend, True)
+            finally:
+                if self._armed is not None:
+                    reader.disarm_coverage()
+                    self._armed = None
+        return after
+
+    def write(self, path, basename: str, statistics=None) -> Path:
+        from . import coverage
+        s = self.s
+        base = Path(s.outdir) / basename
+        if self.value is not None:
+            return coverage.write_track(base, basename, *self.value)
+        extend = int(statistics().est_lib_len) if s.coverage_extend == "auto" else int(s.coverage_extend)
+        return _count_again(s, path, lambda r, names: coverage.write_track(base, basename, *self._take(r, names, extend, False)))
+
+
+def _spooled(fp, size: int = 1 << 22):
+    """The bytes of the temporary file ``fp`` from its beginning, ``size`` at a time; closes (and so removes) it at the end."""
+    try:
+        fp.seek(0)
+        while True:
+            chunk = fp.read(size)
+            if not chunk:
+                return
+            yield chunk
+    finally:
+        fp.close()
 
 
 class _FingerprintControl:
@@ -490,7 +594,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
               chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None,
               complexity: bool = False, exclude_regions=None, fingerprint: bool = False, fingerprint_bin: int = 500,
-              fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0) -> List[FileResult]:
+              fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0, coverage: bool = False,
+              coverage_extend="auto") -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -642,7 +747,8 @@ def _warn_existing(s: _Settings, bases):
     has_track = s.mappability_path is not None
     suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
                                 ("_stats.tab", s.stat_opts is not None), ("_complexity.tab", s.complexity),
-                                ("_fingerprint.tab", s.fingerprint), ("_peaks.tab", s.peaks is not None)) if on]
+                                ("_fingerprint.tab", s.fingerprint), ("_peaks.tab", s.peaks is not None),
+                                ("_coverage.bedGraph", s.coverage)) if on]
     for b in bases:
         for suffix in suffixes:
             path = Path(s.outdir) / (b + suffix)
@@ -665,6 +771,14 @@ def _choose(s: _Settings, paths, errors, read_len):
             logger.error("Cannot execute read length checking for unseekable input.")
             logger.error("If your input can't reread, specify read length using `-r` option.")
             errors[i] = InputUnseekable("'{}' is not seekable: give the read length".format(p))
+            continue
+        if stream and s.coverage and s.coverage_extend == "auto":
+            logger.error("Failed to open file '{}'".format(p))
+            logger.error("A stream cannot be read twice: give --coverage-extend a number or 'read'.")
+            try:
+                _check_coverage_input(s, p)
+            except ValueError as e:
+                errors[i] = e
             continue
         if stream and device is None:
             logger.error("Failed to open file '{}'".format(p))

@@ -110,6 +110,8 @@ class DeviceStreamReader(DeviceBamReader):
                 self._fingerprint.begin(self)
             if self._peaks is not None:         # (and the table of peak lines)
                 self._peaks.begin(self)
+            if self._coverage is not None:      # (and the pileup's table)
+                self._coverage.begin(self)
         self._consumed = True
         while True:
             n = self._L.pmx_dbam_stream_next(self._h)
@@ -126,6 +128,8 @@ class DeviceStreamReader(DeviceBamReader):
                 self._fingerprint.add(self)
             if self._peaks is not None:
                 self._peaks.add(self)
+            if self._coverage is not None:
+                self._coverage.add(self)
 
     _complexity = None
 
@@ -168,6 +172,20 @@ class DeviceStreamReader(DeviceBamReader):
 
     def disarm_peaks(self) -> None:
         self._peaks = None
+
+    _coverage = None
+
+    def arm_coverage(self, mapq_criteria: int = 0, references=None, extend: int = 0):
+        """From now on every window a pass makes current is also piled up base by base (``pmx_dbam_coverage_add``, into the table
+        ``pmx_dbam_coverage_begin`` allocates here); returns the ``pymasc_amd.coverage.DeviceCount`` whose ``finish(reader)`` /
+        ``result(reader)`` is the whole stream's once the pass has ended.  A read is marked in the window that decodes it, as
+        for ``arm_fingerprint``."""
+        from .coverage import DeviceCount
+        self._coverage = DeviceCount(self, mapq_criteria, references, extend)
+        return self._coverage
+
+    def disarm_coverage(self) -> None:
+        self._coverage = None
 
     def _keep_mask(self):
         if len(self._selected) == len(self.references):

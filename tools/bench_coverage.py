@@ -1,0 +1,82 @@
+"""Times the fragment pileup behind --coverage (pmx_dbam_coverage_begin + add + finish + the whole text pull) on the synthetic file of
+tools/bench_ingest.py, beside reading that file (open + decode on the device) in the same process and beside coverage.count_host on
+the same reads: python tools/bench_coverage.py --reads 20000000 --out profiles/coverage.json
+
+The times are wall-clock around the library calls (allocations, the zeroing of the table and the result copies included), medians
+after one warm-up round, split per call.  --reps 1 --no-open --no-host is the run to put under `rocprofv3 --kernel-trace --stats`
+for the split of the kernels; the trace is a run of its own."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from pymasc_amd import coverage  # noqa: E402
+from pymasc_amd.bam_device import DeviceBamReader  # noqa: E402
+from pymasc_amd.native import PMX_BAM_DEFAULT_EXCLUDE  # noqa: E402
+from tools.bench_ingest import synth_bam  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=20_000_000)
+    ap.add_argument("--path", default="/tmp/pymasc_complexity_bench.bam")
+    ap.add_argument("--mapq", type=int, default=10)
+    ap.add_argument("--extend", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-open", action="store_true", help="skip the timing of open + decode")
+    ap.add_argument("--no-host", action="store_true", help="skip coverage.count_host on the same reads")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not os.path.exists(a.path):
+        synth_bam(a.path, a.reads)
+    opens = []
+    for _ in range(0 if a.no_open else 3):
+        t0 = time.perf_counter()
+        with DeviceBamReader(a.path) as r:
+            r.decode(a.mapq, PMX_BAM_DEFAULT_EXCLUDE)
+            opens.append(time.perf_counter() - t0)
+    res = dict(file_reads=a.reads, mapq=a.mapq, extend=a.extend, file_to_records_s=sorted(opens))
+    with DeviceBamReader(a.path) as r:
+        res["kept"] = n = r.decode(a.mapq, PMX_BAM_DEFAULT_EXCLUDE)
+        res["library_version"] = int(r._L.pmx_dbam_version())
+        res["table_bytes"] = 4 * (sum(r.lengths) + len(r.lengths))
+        split = dict(begin=[], add=[], finish=[], text=[], whole=[])
+        for rep in range(a.reps + 1):               # (the first round warms up)
+            t = [time.perf_counter()]
+            acc = coverage.DeviceCount(r, a.mapq, None, a.extend)
+            t.append(time.perf_counter())
+            acc.add(r)
+            t.append(time.perf_counter())
+            totals = acc.finish(r)
+            t.append(time.perf_counter())
+            size = sum(len(chunk) for chunk in acc.text_chunks(r))
+            t.append(time.perf_counter())
+            if rep:
+                for k, name in enumerate(("begin", "add", "finish", "text")):
+                    split[name].append(t[k + 1] - t[k])
+                split["whole"].append(t[4] - t[0])
+        res.update(totals, text_bytes=size, text_chunk_runs=coverage.TEXT_CHUNK,
+                   **{k + "_s": v for k, v in split.items()},              # (every round, in the order they ran)
+                   **{k + "_median_s": statistics.median(v) for k, v in split.items()})
+        if not a.no_host:
+            cols = r._fetch(0, n)
+            t0 = time.perf_counter()
+            c = coverage.count_host(*cols, r.references, r.lengths, [1] * len(r.references), a.extend)
+            res["count_host_s"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            host_size = sum(len(chunk) for chunk in c.text_chunks())
+            res["host_text_s"] = time.perf_counter() - t0
+            assert c.totals == tuple(totals[k] for k in coverage.TOTALS) and host_size == size
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as fp:
+            json.dump(res, fp, indent=1)
+            fp.write("\n")
+
+
+if __name__ == "__main__":
+    main()
