@@ -58,7 +58,7 @@ enum {
     INF_OK = 0,
     INF_ERR_BTYPE = 1,      // reserved block type
     INF_ERR_STORED = 2,     // LEN / NLEN of a stored block
-    INF_ERR_TABLE = 3,      // over-subscribed or malformed Huffman code lengths
+    INF_ERR_TABLE = 3,      // over-subscribed, incomplete or otherwise malformed Huffman code lengths
     INF_ERR_CODE = 4,       // a bit pattern that is no code of the block's tables
     INF_ERR_DIST = 5,       // distance beyond the start of the member / too-large symbol
     INF_ERR_OUTPUT = 6,     // more output than ISIZE
@@ -159,7 +159,9 @@ __device__ __forceinline__ void inf_flush(const u8 *ring, u8 *__restrict__ ob, u
 
 // Canonical Huffman tables from code lengths (RFC 1951 3.2.2), built by the whole wavefront: counts per length with LDS
 // atomics, then every lane places its symbols -- the rank of a symbol among those of its length is a ballot + popcount.
-template <u32 P, bool LIT>
+// Refused is what zlib's inflate_table refuses: an over-subscribed set, and an incomplete one -- unless it is a literal / length
+// or distance set (not the code-length code, CL) without any code or with a single code of one bit.
+template <u32 P, bool LIT, bool CL = false>
 __device__ __forceinline__ bool inf_build(const u8 *lens, u32 n, u16 *T, u32 *cnt, u32 *fc, u32 *ix, u16 *syms, u32 lane)
 {
     for (u32 i = lane; i < (1u << P); i += 64u) T[i] = LIT ? 0x8000 : 0;
@@ -187,6 +189,7 @@ __device__ __forceinline__ bool inf_build(const u8 *lens, u32 n, u16 *T, u32 *cn
         if (left < 0) over = true;
     }
     if (over) return false;
+    if (left > 0 && (CL || !(idx == 0u || (idx == 1u && RFL(cnt[1]) == 1u)))) return false;   // (uniform)
     const u64 below = (1ull << lane) - 1ull;
     for (u32 b = 0; b < n; b += 64u) {
         const u32 s = b + lane;
@@ -300,10 +303,10 @@ k_bgzf_inflate(const u8 *__restrict__ in, u8 *__restrict__ out, const DMember *_
             __syncthreads();
             br_seek(r, bp + LEN);
         } else {
-            u32 hlit = 288u, hdist = 30u;
+            u32 hlit = 288u, hdist = 32u;
             if (btype == 1u) {
                 for (u32 s = lane; s < 288u; s += 64u) S.lens[s] = s < 144u ? 8 : s < 256u ? 9 : s < 280u ? 7 : 8;
-                if (lane < 30u) S.lens[288u + lane] = 5;
+                if (lane < 32u) S.lens[288u + lane] = 5;   // (RFC 1951 3.2.6: 32 codes, so the set is complete; 30 and 31 are refused below)
                 __syncthreads();
             } else {
                 INF_REFILL()
@@ -318,7 +321,7 @@ k_bgzf_inflate(const u8 *__restrict__ in, u8 *__restrict__ out, const DMember *_
                     S.cl[INF_CL_ORDER[i]] = (u8)br_take(r, 3);
                 }
                 __syncthreads();
-                if (!inf_build<7, false>(S.cl, 19u, S.distT, S.cntD, S.fcD, S.ixD, S.symD, lane)) INF_FAIL(INF_ERR_TABLE)
+                if (!inf_build<7, false, true>(S.cl, 19u, S.distT, S.cntD, S.fcD, S.ixD, S.symD, lane)) INF_FAIL(INF_ERR_TABLE)
                 const u32 total = hlit + hdist;
                 u32 i = 0, prev = 0;
                 while (i < total) {

@@ -133,7 +133,8 @@ def _bpt(chroms, block_size):
 def write_bigwig(path, chromsizes, tracks, kind="bedgraph", compress=True, items_per_block=64, rtree_block=4,
                  bpt_block=3, span=1, step=1):
     """tracks: {chrom: [(begin, end, value)]} ascending.  kind: bedgraph | varstep (end = begin + span) |
-    fixedstep (consecutive items at begin0 + i*step, width span; runs are split where the pattern breaks)."""
+    fixedstep (consecutive items at begin0 + i*step, width span; runs are split where the pattern breaks).
+    compress: True (zlib), False (none), or a callable payload -> zlib stream (RFC 1950) that takes zlib's place."""
     names = sorted(chromsizes)
     chroms = [(n, i, chromsizes[n]) for i, n in enumerate(names)]
     cid = {n: i for n, i, _ in chroms}
@@ -188,7 +189,7 @@ def write_bigwig(path, chromsizes, tracks, kind="bedgraph", compress=True, items
     data = struct.pack("<Q", len(blocks))
     leaves = []        # (c0, s0, c1, e1, offset, size)
     for c, b0, e1, payload in blocks:
-        z = zlib.compress(payload) if compress else payload
+        z = compress(payload) if callable(compress) else zlib.compress(payload) if compress else payload
         leaves.append((c, b0, c, e1, data_off + len(data), len(z)))
         data += z
     index_off = data_off + len(data)

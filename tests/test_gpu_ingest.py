@@ -194,6 +194,12 @@ def test_header_only_and_empty_cases(tmp_path):
 
 
 def test_corrupt_input_is_reported(tmp_path):
+    """Every error the host reader reports.  For the DEFLATE stream itself the device refuses what zlib's decoder refuses: reserved
+    block type, LEN != ~NLEN, HLIT > 286 / HDIST > 30, a bad repeat of a code length, no end-of-block code, over-subscribed code
+    lengths, incomplete ones (except a literal / length or distance set with no code or a single 1-bit code; the code-length code
+    never), a bit pattern that is no code, symbols 286 / 287 / distance 30 / 31, a distance beyond the member's start, and output or
+    input beyond the member's.  Here bit flips of zlib-written members probe that rule; tests/test_gpu_inflate_streams.py has one
+    crafted member per cause."""
     refs = [("c1", 100000)]
     recs, _ = W.synth_bam_records(np.random.default_rng(2), refs, 300)
     good = tmp_path / "g.bam"
@@ -212,7 +218,8 @@ def test_corrupt_input_is_reported(tmp_path):
     flipped[len(raw) // 2] ^= 0x55
     with pytest.raises(B.PmxIOError, match="CRC32|inflate|BGZF|DEFLATE|Huffman"):
         reading(flipped)
-    # single-bit flips inside a member: the device path reports an error exactly where the host reader (zlib) does -- a flip in
+    # single-bit flips inside a member: the device path reports an error exactly where the host reader (zlib) does (the rule in the
+    # docstring, incomplete code lengths included) -- a flip in
     # the gzip header's unused bytes or in the padding bits behind the last code changes nothing for either -- and none hangs
     rng = np.random.default_rng(3)
     raised = 0

@@ -4,7 +4,9 @@
 Every round writes one BGZF file of random members -- payload kinds (uniform bytes, skewed alphabets, text, repeats at
 random distances up to 32 KB, runs, BAM-like records), zlib level 0..9, strategy (default / filtered / Huffman-only / RLE /
 fixed), memLevel 1..9 (short blocks: several DEFLATE blocks per member), window 2^9..2^15, sync-flushed mixtures -- behind a
-BAM header, and checks the inflated stream byte for byte; every other round is a BAM file of random records (record sizes from
+BAM header, and checks the inflated stream byte for byte (every third round takes its members from tests/deflate_streams.encode
+instead: matches an encoder would not choose, blocks of random type, non-optimal code lengths up to 15 bits, the stream at any
+skew against a dword; same generator, same seed); every other round is a BAM file of random records (record sizes from
 tens of bytes to beyond a 16-KB piece, random flags / mapq / CIGARs / tags, member sizes 40 .. 65280) checked against the host
 reader's records for two filters, and a random BigWig track (device reader == host reader, three thresholds).  usage: tools/fuzz_ingest.py --seconds 300 --seed 1"""
 import argparse
@@ -20,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from pymasc_amd import bam as B  # noqa: E402
 from pymasc_amd import bam_device as D  # noqa: E402
+from tests import deflate_streams as S  # noqa: E402
 from tests import io_writers as W  # noqa: E402
 
 
@@ -78,13 +81,25 @@ def member(rng, p):
     raise AssertionError
 
 
-def round_members(rng, path):
+def crafted_member(rng, p, file_off):
+    """(member, payload) with the payload encoded by tests/deflate_streams.encode; shortened until it fits a member."""
+    for _ in range(8):
+        raw, _syms = S.encode(p, rng, long_lit=float(rng.random()), long_dist=float(rng.random()), literal_share=float(rng.random()) * 0.5)
+        if len(raw) <= S.MEMBER_CDATA_MAX - 8:
+            return S.bgzf_member(raw, p, extra=S.extra_for_skew(file_off, int(rng.integers(0, 4)))), p
+        p = p[:len(p) // 2]
+    raise AssertionError
+
+
+def round_members(rng, path, crafted=False):
     head = W.bam_header([("c1", 1000)])
     ms, want = [raw_member(zlib.compressobj(6, zlib.DEFLATED, -15).compress(head) + zlib.compressobj(6, zlib.DEFLATED, -15).flush(), head)], [head]
     co = zlib.compressobj(6, zlib.DEFLATED, -15)
     ms[0] = raw_member(co.compress(head) + co.flush(), head)
-    for _ in range(int(rng.integers(1, 400))):
-        m, p = member(rng, payload(rng))
+    off = len(ms[0])
+    for _ in range(int(rng.integers(1, 40 if crafted else 400))):      # (the Python encoder takes ~5 us per byte)
+        m, p = crafted_member(rng, payload(rng), off) if crafted else member(rng, payload(rng))
+        off += len(m)
         ms.append(m)
         want.append(p)
     with open(path, "wb") as fp:
@@ -173,7 +188,7 @@ def main():
     rounds = members = nbytes = nrecs = rewalked = nivs = 0
     last = t0
     while time.time() - t0 < a.seconds:
-        m, n = round_members(rng, path)
+        m, n = round_members(rng, path, crafted=rounds % 3 == 2)
         members += m
         nbytes += n
         k, rw = round_records(rng, path)
