@@ -334,6 +334,42 @@ int pmx_dbed_open(const char *path, int device, int nthreads, int32_t nref, cons
  * file: PMX_DBAM_ERR_FORMAT with pmx_kmer_open's message; one hash bin larger than the budget: PMX_DBAM_ERR_OPEN. */
 int pmx_dkm_open(const char *path, int32_t k, int device, int nthreads, int64_t budget_bytes, int32_t hash_bits, pmx_dbw **out);
 
+/* GC bias (version >= 14): the reads against the genome's windows, per G + C content of the window.
+ * The genome handle: pmx_dgc_open is the first stage of pmx_dkm_open and nothing else -- the FASTA (plain, BGZF, gzip) reaches HBM
+ * and is packed at 2 bits and a valid bit per position, with pmx_dkm_open's rules and error messages ("line N: <reason>", 2^32
+ * bases) -- and the handle keeps the packed genome with the records' names, lengths and first positions, in file order. */
+typedef struct pmx_dgc pmx_dgc;
+int pmx_dgc_open(const char *path, int device, int nthreads, pmx_dgc **out);
+void pmx_dgc_close(pmx_dgc *g);
+int32_t pmx_dgc_nrec(const pmx_dgc *g);
+const char *pmx_dgc_rec_name(const pmx_dgc *g, int32_t i);
+int64_t pmx_dgc_rec_len(const pmx_dgc *g, int32_t i);
+/* The window: W = `window`, 1 <= W <= 1024.  A chosen reference of length len has a window at every 1-based start s with
+ * s + W - 1 <= len, covering [s, s + W - 1].  A window is BLOCKED when any of its positions is not A C G T (either case) or lies
+ * inside a merged interval of the handle's attached mask (pmx_dbam_set_exclude: excluded regions act as runs of N).  g(s) = the
+ * G / C among the W bases of an unblocked window, an integer in 0 .. W.  N[g] = the unblocked windows of the chosen references
+ * with that g.
+ * The reads are pmx_dbam_bincount_add's (mapq_min / flag_exclude, the chosen references, less the reads an attached mask leaves
+ * out; reads on other references are ignored entirely).  A forward read is placed at s = pos1, a reverse read at
+ * s = pos1 + read_len - W (its window ends on its 5' base; it is not clipped).  s < 1 or s + W - 1 > len: the read counts in
+ * off_end; otherwise, a blocked window: in blocked; otherwise F[g(s)] += 1.
+ * pmx_dbam_gcbias_begin matches every chosen reference (use_ref[nref], NULL: all) to the record of the same name, which must
+ * have the same length (the FASTA's order is free, other records are ignored; the first reference without one:
+ * PMX_DBAM_ERR_INVALID, named); builds a GC bit and a blocked bit per position of the chosen references, laid end to end with one
+ * blocked separator behind each (0.25 bytes per chosen base, about 0.78 GB for hg38; part of pmx_dbam_stream_info's peak);
+ * computes N and zeroes F and the counters.  The genome is not referenced after begin returns: it may be closed, and one genome
+ * serves any number of handles.  The table replaces any earlier one and stays until the next begin or close; a mask attached
+ * later does not change it.  A chosen reference shorter than W has no windows, and all its reads are off_end.
+ * pmx_dbam_gcbias_add counts what the handle holds now (the arrays, counters and runs of the last pmx_dbam_decode stay
+ * untouched); out = {reads placed, off_end, blocked} of this call.  Calls add up in F (the windows of a stream); N never changes.
+ * pmx_dbam_gcbias_tables returns W + 1 and, with cap >= W + 1, fills windows[] = N and reads[] = F; totals = {sum N, sum F,
+ * off_end, blocked} since begin.
+ * add / tables without begin, a NULL output, window 0 or above 1024, a genome on another device, no chosen reference:
+ * PMX_DBAM_ERR_INVALID. */
+int pmx_dbam_gcbias_begin(pmx_dbam *b, const pmx_dgc *genome, uint32_t window, const uint8_t *use_ref);
+int pmx_dbam_gcbias_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t out[3]);
+int64_t pmx_dbam_gcbias_tables(pmx_dbam *b, uint64_t *windows, uint64_t *reads, int64_t cap, uint64_t totals[4]);
+
 #ifdef __cplusplus
 }
 #endif

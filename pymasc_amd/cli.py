@@ -251,6 +251,13 @@ def get_parser() -> argparse.ArgumentParser:
                      help="extend every read to N bases from its 5' end; auto (the default): to the run's own fragment-length "
                           "estimate, on one more read of the file, so not for '-' or a pipe; read: no extension, the read's own "
                           "length; implies --coverage")
+    out.add_argument("--gc-bias", metavar="FASTA", type=Path,
+                     help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
+                          "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
+                          "window beside the genome's windows of that content, with AT / GC dropout; windows with an N or inside "
+                          "--exclude-regions are left out")
+    out.add_argument("--gc-window", metavar="N", type=int, action=_NaturalNumber,
+                     help="length of the genome windows, 1 to 1024 bases (default 100); needs --gc-bias")
     return parser
 
 
@@ -306,6 +313,12 @@ def parse_args(argv=None) -> argparse.Namespace:
         if streams:
             parser.error("argument --coverage-extend: auto reads the file once more, which {} cannot be: give a number or 'read'"
                          "".format(", ".join(streams)))
+    if args.gc_window is not None and args.gc_bias is None:
+        parser.error("argument --gc-window: needs a genome (--gc-bias)")
+    if args.gc_window is not None and args.gc_window > 1024:
+        parser.error("argument --gc-window: the window is {}: it must lie in [1, 1024]".format(args.gc_window))
+    if args.gc_bias is not None and not os.path.isfile(args.gc_bias):
+        parser.error("argument --gc-bias: no such file: '{}'".format(args.gc_bias))
     if args.chrom_sizes is None:
         from .bed_reads import is_bed_reads     # (no torch, no native library)
         bed = [str(p) for p in args.reads if is_bed_reads(p)]
@@ -402,6 +415,10 @@ def _run(args, device, rank: int) -> int:
         extra["coverage"] = True
         if args.coverage_extend not in (None, "auto"):
             extra["coverage_extend"] = 0 if args.coverage_extend == "read" else args.coverage_extend
+    if args.gc_bias is not None:
+        extra["gc_bias"] = str(args.gc_bias)
+        if args.gc_window is not None:
+            extra["gc_window"] = args.gc_window
     try:
         results = pipeline.run_files(
             [str(p) for p in args.reads], str(args.outdir), args.max_shift, read_len=args.read_length,
@@ -412,8 +429,8 @@ def _run(args, device, rank: int) -> int:
             chromfilter=args.chromfilter, stats=True, library_length=args.library_length,
             smooth_window=args.smooth_window, mask_size=args.mask_size, bg_avr_width=args.bg_avr_width,
             chi2_pval=args.chi2_pval, names=args.name or None, **extra)
-    except (BWIOError, JSONIOError):
-        return 1                    # logged where it was raised (mappability.MappabilityStats)
+    except (BWIOError, JSONIOError, pipeline.GenomeError):
+        return 1                    # logged where it was raised (mappability.MappabilityStats, pipeline._GcGenome)
     except RuntimeError as e:
         if rank == 0 or not _rank0_track_error(e):
             raise

@@ -1258,6 +1258,14 @@ struct pmx_dbam {
     u64 cv_held = 0;                 // device bytes the pileup holds now
     u32 cv_nc = 0, cv_ext = 0;       // chosen references; extend
     u64 cv_tot[5] = {0, 0, 0, 0, 0}; // reads, runs, covered bases, fragment bases, largest depth
+    // GC bias (pmx_dbam_gcbias_*, gcbias_device.inc): from begin to the next begin or close
+    u64 *d_gc = nullptr, *d_gc_bl = nullptr;   // one GC and one blocked bit per position of the chosen references, laid end to end
+    long long *d_gc_tab = nullptr;   // per reference: its first position in the bit vectors (-1: not chosen), its length
+    unsigned long long *d_gc_f = nullptr;      // F[0 .. window]
+    u32 gc_w = 0;                    // the window (0: no table)
+    u64 gc_words = 0;                // words of each bit vector
+    std::vector<u64> gc_n;           // N[0 .. window], computed by begin
+    u64 gc_tot[3] = {0, 0, 0};       // reads placed, off_end, blocked since begin
 };
 
 namespace {
@@ -1806,7 +1814,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 13; }
+int pmx_dbam_version(void) { return 14; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1881,6 +1889,8 @@ void pmx_dbam_close(pmx_dbam *b)
     if (b->d_bc_tab) (void)hipFree(b->d_bc_tab);
     if (b->d_pk) (void)hipFree(b->d_pk);
     if (b->d_pk_tab) (void)hipFree(b->d_pk_tab);
+    for (void *p : {(void *)b->d_gc, (void *)b->d_gc_bl, (void *)b->d_gc_tab, (void *)b->d_gc_f})
+        if (p) (void)hipFree(p);
     for (void *p : {(void *)b->d_cv, (void *)b->d_cv_tab, (void *)b->d_cv_seg, (void *)b->d_cv_names, (void *)b->d_cv_runs})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->d_nl, (void *)b->d_ls, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
@@ -2600,3 +2610,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "region_mask_device.inc"
 #include "peakcount_device.inc"
 #include "coverage_device.inc"
+#include "gcbias_device.inc"

@@ -439,10 +439,10 @@ struct KmGenome {
 
 inline u64 km_parts(u64 n) { return n / KM_SCAN_TILE + 2; }
 
-// text -> records (names, lengths) and the packed genome; the first error by line
-int km_parse(pmx_dbw &w, const u8 *D, u64 N, TtDev &g, KmGenome &G)
+// text -> records (names, lengths) and the packed genome; the first error by line (also pmx_dgc_open's, gcbias_device.inc)
+int km_parse(hipStream_t st, std::vector<std::string> &rec_names, std::vector<int64_t> &rec_sizes, const u8 *D, u64 N, TtDev &g,
+             KmGenome &G)
 {
-    hipStream_t st = w.stream;
     TtDev t;                        // the line tables: freed when the genome is packed
     if (N == 0) return fail(PMX_DBAM_ERR_FORMAT, fasta::no_record_text());
     const u64 nch = (N + SAM_CHUNK - 1) / SAM_CHUNK;
@@ -540,8 +540,8 @@ int km_parse(pmx_dbw &w, const u8 *D, u64 N, TtDev &g, KmGenome &G)
         const u64 len = (h + 1 < nhdr ? hsep[h + 1] : total_pos) - hsep[h] - 1u;
         if (len == 0) fe = std::min<unsigned long long>(fe, ((u64)hline[h] << 8) | fasta::FA_ERR_EMPTY);
         if (hnlen[h] && !seen.emplace(nm, (u32)h).second) fe = std::min<unsigned long long>(fe, ((u64)hline[h] << 8) | fasta::FA_ERR_DUP);
-        w.names.push_back(nm);
-        w.sizes.push_back((int64_t)len);
+        rec_names.push_back(nm);
+        rec_sizes.push_back((int64_t)len);
     }
     const bool big = fasta::too_large(bases, nhdr);
     if (big || !nhdr) {
@@ -819,7 +819,7 @@ static int dkm_open_impl(const char *path, int32_t k, int device, int nthreads, 
         u8 *d_text = nullptr;
         u64 N = 0;
         rc = tt_upload(path, device, nthreads, &d_text, &N);
-        if (!rc) rc = km_parse(*w, d_text, N, g, G);
+        if (!rc) rc = km_parse(w->stream, w->names, w->sizes, d_text, N, g, G);
         if (d_text) {
             (void)hipStreamSynchronize(w->stream);
             (void)hipFree(d_text);  // (the genome is packed: the text is not needed any more)

@@ -100,6 +100,7 @@ u64 stream_held(const pmx_dbam &b)
     h += b.bc_bins * 4;
     h += b.pk_lines * 28;
     h += b.cv_held;
+    h += b.gc_words * 16;
     return h;
 }
 void stream_note(pmx_dbam &b) { b.st->peak = std::max(b.st->peak, stream_held(b)); }

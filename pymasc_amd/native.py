@@ -130,6 +130,14 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_coverage_finish": (_int, [_vp, _vp]),
     "pmx_dbam_coverage_runs": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pmx_dbam_coverage_text": (_i64, [_vp, _i64, _i64, _vp, _i64]),
+    "pmx_dbam_gcbias_begin": (_int, [_vp, _vp, _u32, _vp]),
+    "pmx_dbam_gcbias_add": (_int, [_vp, _u32, _u32, _vp]),
+    "pmx_dbam_gcbias_tables": (_i64, [_vp, _vp, _vp, _i64, _vp]),
+    "pmx_dgc_open": (_int, [_str, _int, _int, _out]),
+    "pmx_dgc_close": (None, [_vp]),
+    "pmx_dgc_nrec": (_i32, [_vp]),
+    "pmx_dgc_rec_name": (_str, [_vp, _i32]),
+    "pmx_dgc_rec_len": (_i64, [_vp, _i32]),
     "pmx_dbam_set_exclude": (_int, [_vp, _i32, _vp, _vp, _vp]),
     "pmx_dbam_exclude_intervals": (_i64, [_vp, _i64, _vp, _vp, _vp]),
     "pmx_dbam_excluded": (_int, [_vp, _pu64, _pu64]),
@@ -304,6 +312,15 @@ class AlignmentReader(NativeReader):
         from .coverage import from_reader
         self._check_open()
         return from_reader(self, mapq_criteria, references, extend)
+
+    def gc_bias(self, genome, mapq_criteria: int = 0, references=None, window: int = 100):
+        """The reads of ``bin_counts`` against the windows of ``genome`` per G + C content of the window: a
+        ``pymasc_amd.gcbias.GcBias`` (``gcbias.from_reader``).  ``genome``: a FASTA file's path, or for a device
+        reader an open ``gcbias.DeviceGenome``.  A device reader counts on the GPU with arrays of its own: the arrays of the last
+        ``decode`` stay as they are."""
+        from .gcbias import from_reader
+        self._check_open()
+        return from_reader(self, genome, mapq_criteria, references, window)
 
     # ---- excluded regions (pymasc_amd.region_mask; DESIGN.md 7.15) ----
     _exclude = None

@@ -39,7 +39,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
         chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None,
         fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None,
-        peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto"):
+        peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto", gc_bias=None, gc_window: int = 100):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -88,7 +88,13 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     ``"auto"`` (the default) extends to the run's own fragment-length estimate, ``stats.genome_wide_stats(...).est_lib_len``
     with the run's statistics options, whether or not ``stats`` writes them; it exists only after the correlation, so rank 0
     counts on one more read of the file, and a stream (``-``, a FIFO) with ``"auto"`` is a ValueError before anything runs.  The
-    device table is 4 bytes per chosen base (12.4 GB for hg38)."""
+    device table is 4 bytes per chosen base (12.4 GB for hg38).
+    ``gc_bias``: a genome FASTA (plain, gzip or bgzip): rank 0 also writes ``<stem>_gcbias.tab`` (pymasc_amd.gcbias, DESIGN.md
+    7.19): the reads the fingerprint counts, each placed on the genome window of ``gc_window`` bases (1 .. 1024) that begins at
+    its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
+    that is not A C G T or inside ``exclude_regions`` are left out.  Counted where ``complexity`` is counted.  The genome is
+    parsed once per call (on the GPU with device ingest).  A chosen reference without a record of its name and length:
+    ValueError before the run; a FASTA that cannot be parsed: ``GenomeError``."""
     check_bed_sizes(bam_path, chrom_sizes)
     s = _settings(locals())
     _check_coverage_input(s, bam_path)
@@ -108,9 +114,13 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
             if bam is None and is_stream(bam_path) and s.estimate_gpu is not None:      # (no header to read apart, as above)
                 bam = open_alignments(bam_path, True, device=s.estimate_gpu)
             s.fingerprint_control.check(s, bam_path, bam)
+        if s.gc_bias is not None:
+            s.gc_bias.check(s, bam_path, bam)
         known = _mappable_lengths(s, read_len, track, False, mask)
         result, counted = _run_file(s, bam_path, read_len, known, bam, track, mask)
     finally:
+        if s.gc_bias is not None:
+            s.gc_bias.close()
         if track is not None:
             track.close()
         if bam is not None:
@@ -149,6 +159,8 @@ class _Settings:
     peaks_extend: int
     coverage: bool
     coverage_extend: object         # an int (0: every read's own length), or "auto": the run's fragment-length estimate
+    gc_bias: object                 # None, or the _GcGenome parsed once for the call
+    gc_window: int
     save_mappability_stats: bool
     device: int
     ingest: bool
@@ -201,6 +213,12 @@ def _settings(kw: dict) -> _Settings:
     given.update(fingerprint=bool(kw["fingerprint"]) or control is not None, fingerprint_bin=int(kw["fingerprint_bin"]),
                  fingerprint_extend=int(kw["fingerprint_extend"]),
                  fingerprint_control=None if control is None else _FingerprintControl(control))
+    if kw["gc_bias"] is not None or int(kw["gc_window"]) != 100:
+        from .gcbias import check_window
+        if kw["gc_bias"] is None:
+            raise ValueError("gc_window needs gc_bias")
+        given.update(gc_bias=_GcGenome(kw["gc_bias"], bool(ingest), reader_device(kw["context"], device, bool(ingest))),
+                     gc_window=check_window(kw["gc_window"]))
     stat_kw = {k: kw[k] for k in _STAT_OPTS}
     given.update(device=device, ingest=bool(ingest), rank=rank, world=world, stat_opts=stat_kw if kw["stats"] else None,
                  stat_kw=stat_kw)
@@ -300,11 +318,12 @@ def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool, mask=No
 
 def _run_file(s: _Settings, path, read_len: int, known, bam, track, mask=None):
     """One file sharded over the ranks: (its genome-wide result, the counts taken beside it: a _ComplexityCount and a
-    _FingerprintCount, a _PeakCount and a _CoverageCount as asked for).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's and the
+    _FingerprintCount, a _PeakCount, a _CoverageCount and a _GcBiasCount as asked for).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's and the
     track's open readers, or None for run_sharded to open its own.  One rank: run_sharded's one ``reader_hook`` serves every
     count (``_hooks``)."""
     counted = [c(s) for c, on in ((_ComplexityCount, s.complexity), (_FingerprintCount, s.fingerprint),
-                                     (_PeakCount, s.peaks is not None), (_CoverageCount, s.coverage)) if on]
+                                     (_PeakCount, s.peaks is not None), (_CoverageCount, s.coverage),
+                                     (_GcBiasCount, s.gc_bias is not None)) if on]
     hooks = [c.hook for c in counted if c.hooked]
     result = run_sharded(path, s.max_shift, read_len, s.mapq_criteria, bigwig_path=s.mappability_path,
                          references=s.references, skip_ncc=s.skip_ncc, device=s.device, chrom2mappable_len=known,
@@ -330,7 +349,8 @@ def _hooks(hooks):
 def _write_file(s: _Settings, path, basename: str, result, read_len: int, counted) -> List[Path]:
     """Rank 0's part after _run_file: ``outdir/<basename>_{cc,mscc,nreads}.tab``, with ``stat_opts`` ``<basename>_stats.tab``
     whose Name row is ``basename``, and the table of every count in ``counted`` (``<basename>_complexity.tab``,
-    ``<basename>_fingerprint.tab``, ``<basename>_peaks.tab``, ``<basename>_coverage.bedGraph``); the paths written.  The
+    ``<basename>_fingerprint.tab``, ``<basename>_peaks.tab``, ``<basename>_coverage.bedGraph``, ``<basename>_gcbias.tab``); the
+    paths written.  The
     statistics are computed once, for ``_stats.tab`` and for a pileup that extends to their estimate."""
     out = Path(s.outdir)
     out.mkdir(parents=True, exist_ok=True)
@@ -539,6 +559,85 @@ def _spooled(fp, size: int = 1 << 22):
         fp.close()
 
 
+class _GcBiasCount:
+    """The GC bias of one file's run (pymasc_amd.gcbias), taken where _FingerprintCount takes its own, against the call's genome."""
+    hooked = True
+
+    def __init__(self, s: _Settings):
+        self.s = s
+        self.value = None
+
+    def _args(self, names):
+        return self.s.gc_bias.open(), int(self.s.mapq_criteria), names, self.s.gc_window
+
+    def hook(self, reader, names):
+        from . import gcbias
+        if hasattr(reader, "arm_gcbias"):
+            acc = reader.arm_gcbias(*self._args(names))
+
+            def after():
+                try:
+                    self.value = acc.result(reader)
+                finally:
+                    reader.disarm_gcbias()
+            return after
+
+        def after():
+            self.value = gcbias.from_reader(reader, *self._args(names))
+        return after
+
+    def write(self, path, basename: str, statistics=None) -> Path:
+        from . import gcbias
+        s = self.s
+        if self.value is None:
+            self.value = _count_again(s, path, lambda r, names: gcbias.from_reader(r, *self._args(names)))
+        return gcbias.write_gcbias(Path(s.outdir) / basename, basename, self.value)
+
+
+class GenomeError(RuntimeError):
+    """``gc_bias`` names a FASTA file that cannot be read or parsed: the call fails, as it does for a bad track."""
+
+
+class _GcGenome:
+    """``gc_bias``: the genome of a call's GC tables, parsed once, when the first file needs it (``open``: a
+    ``gcbias.DeviceGenome`` with device ingest, else a ``gcbias.HostGenome``) and closed with the call.  ``check`` compares a
+    file's chosen references with its records before the run: ValueError in ``pmx_dbam_gcbias_begin``'s words."""
+
+    def __init__(self, path, ingest: bool, device: int):
+        self.path, self.ingest, self.device = os.fspath(path), ingest, device
+        self._genome = None
+
+    def open(self):
+        if self._genome is None:
+            from . import gcbias
+            from .native import PmxIOError
+            try:
+                self._genome = gcbias.open_genome(self.path, self.ingest, self.device)
+            except (PmxIOError, OSError, ValueError) as e:
+                logger.error("Failed to read the genome '{}'".format(self.path))
+                logger.error(str(e))
+                raise GenomeError(str(e)) from e
+        return self._genome
+
+    def close(self) -> None:
+        if self._genome is not None and hasattr(self._genome, "close"):
+            self._genome.close()
+        self._genome = None
+
+    def check(self, s: _Settings, path, bam) -> None:
+        from .gcbias import match_references
+        genome = self.open()
+        if bam is not None:
+            refs, lengths = bam.references, bam.lengths
+        elif is_stream(path):       # (no header to read apart: pmx_dbam_gcbias_begin says the same when the stream is armed)
+            return
+        else:
+            with open_header(path, s.chrom_sizes) as h:
+                refs, lengths = h.references, h.lengths
+        chosen = set(kept_references(refs, s.references, s.chromfilter))
+        match_references(refs, lengths, [n in chosen for n in refs], dict(zip(genome.names, genome.lengths)))
+
+
 class _FingerprintControl:
     """``fingerprint_control``: the control file of a call's fingerprints.  ``check`` compares its chosen references with a
     sample's from the headers alone; ``counts`` is its table, counted once per call (by rank 0, when the first table is written)
@@ -595,7 +694,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None,
               complexity: bool = False, exclude_regions=None, fingerprint: bool = False, fingerprint_bin: int = 500,
               fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0, coverage: bool = False,
-              coverage_extend="auto") -> List[FileResult]:
+              coverage_extend="auto", gc_bias=None, gc_window: int = 100) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -625,7 +724,10 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
     calculator gives its bit-vectors back to the context's pool and frees its result arena before the next file.  The track is
     opened once per rank.  Several ranks: rank 0 alone takes steps 1 and 2 and broadcasts which files are left and the read
     length; every rank then walks the same files, the skip of an unsorted file is decided from every rank's outcome, and
-    rank 0 writes inside ``sharding.on_rank0``, so that a write error reaches every rank (``written`` is [] on the others)."""
+    rank 0 writes inside ``sharding.on_rank0``, so that a write error reaches every rank (``written`` is [] on the others).
+
+    ``gc_bias``: the genome is parsed once, before the first file runs, and serves every file; a file whose chosen references
+    have no record of their name and length in it is logged and skipped; a FASTA that cannot be parsed raises ``GenomeError``."""
     paths = list(paths)
     if not paths:
         raise ValueError("no input files")
@@ -696,6 +798,17 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
                     logger.error(str(e))
                     errors[i] = _portable(e)
                     continue
+            if s.gc_bias is not None:               # (from the headers too: a genome of another assembly skips the file)
+                s.gc_bias.open()
+                try:
+                    s.gc_bias.check(s, paths[i], bam)
+                except ValueError as e:
+                    if bam is not None:
+                        bam.close()
+                    logger.error("Failed to open file '{}'".format(paths[i]))
+                    logger.error(str(e))
+                    errors[i] = _portable(e)
+                    continue
             try:
                 result, counted = _run_file(s, paths[i], read_len, known, bam, track, masks[i])
             except Exception as e:
@@ -714,6 +827,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
     finally:
         for r in kept.values():
             r.close()
+        if s.gc_bias is not None:
+            s.gc_bias.close()
         if track is not None:
             track.close()
         if own_ctx:
@@ -748,7 +863,7 @@ def _warn_existing(s: _Settings, bases):
     suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
                                 ("_stats.tab", s.stat_opts is not None), ("_complexity.tab", s.complexity),
                                 ("_fingerprint.tab", s.fingerprint), ("_peaks.tab", s.peaks is not None),
-                                ("_coverage.bedGraph", s.coverage)) if on]
+                                ("_coverage.bedGraph", s.coverage), ("_gcbias.tab", s.gc_bias is not None)) if on]
     for b in bases:
         for suffix in suffixes:
             path = Path(s.outdir) / (b + suffix)

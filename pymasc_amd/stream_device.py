@@ -112,6 +112,8 @@ class DeviceStreamReader(DeviceBamReader):
                 self._peaks.begin(self)
             if self._coverage is not None:      # (and the pileup's table)
                 self._coverage.begin(self)
+            if self._gcbias is not None:        # (and the GC table: from the genome it was armed with)
+                self._gcbias.begin(self)
         self._consumed = True
         while True:
             n = self._L.pmx_dbam_stream_next(self._h)
@@ -130,6 +132,8 @@ class DeviceStreamReader(DeviceBamReader):
                 self._peaks.add(self)
             if self._coverage is not None:
                 self._coverage.add(self)
+            if self._gcbias is not None:
+                self._gcbias.add(self)
 
     _complexity = None
 
@@ -186,6 +190,20 @@ class DeviceStreamReader(DeviceBamReader):
 
     def disarm_coverage(self) -> None:
         self._coverage = None
+
+    _gcbias = None
+
+    def arm_gcbias(self, genome, mapq_criteria: int = 0, references=None, window: int = 100):
+        """From now on every window a pass makes current is also placed on the windows of ``genome`` (a FASTA path or an open
+        ``gcbias.DeviceGenome``) per G + C content (``pmx_dbam_gcbias_add``, into the table ``pmx_dbam_gcbias_begin`` builds
+        here); returns the ``pymasc_amd.gcbias.DeviceCount`` whose ``result(reader)`` is the whole stream's once the pass has
+        ended.  A read is counted in the window that decodes it, as for ``arm_fingerprint``."""
+        from .gcbias import DeviceCount
+        self._gcbias = DeviceCount(self, genome, mapq_criteria, references, window)
+        return self._gcbias
+
+    def disarm_gcbias(self) -> None:
+        self._gcbias = None
 
     def _keep_mask(self):
         if len(self._selected) == len(self.references):
