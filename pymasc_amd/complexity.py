@@ -14,7 +14,7 @@ from typing import Dict, Sequence, Tuple
 
 import numpy as np
 
-from .native import PMX_BAM_DEFAULT_EXCLUDE, PMX_BAM_FLAG_DUPLICATE, PMX_COMPLEXITY_BINS
+from .native import PMX_BAM_DEFAULT_EXCLUDE, PMX_BAM_FLAG_DUPLICATE, PMX_COMPLEXITY_BINS, SideAccumulator, count_over
 
 #: the filter of the complexity count: the run's, with flagged duplicates kept
 COMPLEXITY_EXCLUDE = PMX_BAM_DEFAULT_EXCLUDE & ~PMX_BAM_FLAG_DUPLICATE
@@ -126,9 +126,10 @@ def count_device(reader, mapq_criteria: int, use: np.ndarray) -> Tuple[np.ndarra
     return per_ref[:nref].astype(np.int64), hist.astype(np.int64)
 
 
-class WindowedCount:
+class WindowedCount(SideAccumulator):
     """The sum of a stream reader's ``pmx_dbam_complexity`` calls: ``DeviceStreamReader`` calls ``count`` when a window has
-    been worked on, and once more behind the last window (the records the library held back)."""
+    been worked on (``add``), and once more behind the last window (``flush``: the records the library held back).  The sums
+    live on the host: a new handle does not reset them (no ``begin``)."""
 
     def __init__(self, reader, mapq_criteria: int, references=None):
         self.mapq_criteria = int(mapq_criteria)
@@ -144,7 +145,9 @@ class WindowedCount:
         self.hist += hist
         self.hist[0] = top
 
-    def result(self) -> LibraryComplexity:
+    add = flush = count
+
+    def result(self, reader=None) -> LibraryComplexity:
         return _from_tables(self.names, self.use, self.per_ref, self.hist)
 
 
@@ -167,17 +170,7 @@ def from_reader(reader, mapq_criteria: int = 0, references=None) -> LibraryCompl
     when it is a regular file and raises ``InputUnseekable`` otherwise; a host reader through ``batches`` and ``count_host``."""
     from .bam_device import DeviceBamReader
     if isinstance(reader, DeviceBamReader):
-        if hasattr(reader, "_windows"):
-            acc = reader.arm_complexity(mapq_criteria, references)
-            try:
-                for _ in reader._windows():
-                    pass
-            finally:
-                reader.disarm_complexity()
-            return acc.result()
-        use = _selected_mask(reader, references)
-        per_ref, hist = count_device(reader, mapq_criteria, use)
-        return _from_tables(reader.references, use, per_ref, hist)
+        return count_over(reader, "complexity", lambda: WindowedCount(reader, mapq_criteria, references)).result()
     use = _selected_mask(reader, references)
     cols = [[], [], [], []]
     for batch in reader.batches(mapq_criteria, COMPLEXITY_EXCLUDE):

@@ -31,7 +31,7 @@ from typing import Dict, Iterator, Tuple
 import numpy as np
 
 from .complexity import _selected_mask
-from .native import PMX_BAM_DEFAULT_EXCLUDE
+from .native import PMX_BAM_DEFAULT_EXCLUDE, SideAccumulator, count_over
 
 COVERAGE_SUFFIX = "_coverage.bedGraph"
 TILE = 4096                 # slots per scan tile of the device code (PMX_COVERAGE_TILE of include/pymasc_amd_ingest.h)
@@ -145,7 +145,7 @@ def count_host(ref_id, pos1, read_len, reverse, names, lengths, use, extend: int
     return acc.result()
 
 
-class DeviceCount:
+class DeviceCount(SideAccumulator):
     """The pileup a device reader's handle holds between ``pmx_dbam_coverage_begin`` and the next one: ``add`` marks what the handle
     holds now (a stream reader calls it for every window), ``finish`` turns the table into runs, ``runs`` / ``text`` read them
     back, ``result`` is all of it as a ``Coverage``."""
@@ -235,16 +235,7 @@ def count_device(reader, mapq_criteria: int, references=None, extend: int = 0) -
 def device_count_of(reader, mapq_criteria: int = 0, references=None, extend: int = 0) -> DeviceCount:
     """The finished ``DeviceCount`` of everything a device reader reads: one ``add`` for a whole-file reader, every window of a
     stream reader (read once more when it is a regular file, ``InputUnseekable`` otherwise)."""
-    if hasattr(reader, "_windows"):
-        acc = reader.arm_coverage(mapq_criteria, references, extend)
-        try:
-            for _ in reader._windows():
-                pass
-        finally:
-            reader.disarm_coverage()
-    else:
-        acc = DeviceCount(reader, mapq_criteria, references, extend)
-        acc.add(reader)
+    acc = count_over(reader, "coverage", lambda: DeviceCount(reader, mapq_criteria, references, extend))
     acc.finish(reader)
     return acc
 

@@ -22,7 +22,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from .complexity import _ratio, _selected_mask
-from .native import PMX_BAM_DEFAULT_EXCLUDE, PMX_BINCOUNT_HIST
+from .native import PMX_BAM_DEFAULT_EXCLUDE, PMX_BINCOUNT_HIST, SideAccumulator, count_over
 
 FINGERPRINT_SUFFIX = "_fingerprint.tab"
 DEFAULT_BIN = 500
@@ -181,7 +181,7 @@ def _per_reference(names, use, nb) -> Dict[str, int]:
     return {n: int(nb[i]) for i, n in enumerate(names) if use[i]}
 
 
-class DeviceCount:
+class DeviceCount(SideAccumulator):
     """The table a device reader's handle holds between ``pmx_dbam_bincount_begin`` and the next one: ``add`` counts what the
     handle holds now (a stream reader calls it for every window), ``result`` reads ``H`` back."""
 
@@ -257,15 +257,8 @@ def from_reader(reader, mapq_criteria: int = 0, references=None, bin_size: int =
     when it is a regular file and raises ``InputUnseekable`` otherwise; a host reader through ``batches`` and ``count_host``."""
     from .bam_device import DeviceBamReader
     if isinstance(reader, DeviceBamReader):
-        if hasattr(reader, "_windows"):
-            acc = reader.arm_fingerprint(mapq_criteria, references, bin_size, extend)
-            try:
-                for _ in reader._windows():
-                    pass
-                return acc.result(reader)
-            finally:
-                reader.disarm_fingerprint()
-        return count_device(reader, mapq_criteria, references, bin_size, extend)
+        return count_over(reader, "fingerprint",
+                          lambda: DeviceCount(reader, mapq_criteria, references, bin_size, extend)).result(reader)
     if int(bin_size) < 0 or int(extend) < 0:
         raise ValueError("bin_size and extend are not negative")
     use = _selected_mask(reader, references)

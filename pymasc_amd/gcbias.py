@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .complexity import _selected_mask
-from .native import PMX_BAM_DEFAULT_EXCLUDE, NativeReader, load_ingest_library
+from .native import PMX_BAM_DEFAULT_EXCLUDE, NativeReader, SideAccumulator, count_over, load_ingest_library
 
 GCBIAS_SUFFIX = "_gcbias.tab"
 DEFAULT_WINDOW = 100
@@ -130,7 +130,7 @@ class DeviceGenome(NativeReader):
         self.lengths = tuple(int(self._L.pmx_dgc_rec_len(self._h, i)) for i in range(n))
 
 
-class DeviceCount:
+class DeviceCount(SideAccumulator):
     """The table a device reader's handle holds between ``pmx_dbam_gcbias_begin`` and the next one: ``add`` counts what the handle
     holds now (a stream reader calls it for every window), ``result`` reads ``N`` and ``F`` back.  ``genome``: an open
     ``DeviceGenome`` or a FASTA path (opened for the length of each ``begin``)."""
@@ -334,16 +334,9 @@ def from_reader(reader, genome, mapq_criteria: int = 0, references=None, window:
     otherwise; a host reader through ``count_host`` (``genome``: a FASTA path or a ``HostGenome``)."""
     from .bam_device import DeviceBamReader
     if isinstance(reader, DeviceBamReader):
-        window = check_window(window)
-        if hasattr(reader, "_windows"):
-            acc = reader.arm_gcbias(genome, mapq_criteria, references, window)
-            try:
-                for _ in reader._windows():
-                    pass
-                return acc.result(reader)
-            finally:
-                reader.disarm_gcbias()
-        return count_device(reader, genome, mapq_criteria, references, window)
+        window = check_window(window)       # (the host branch checks inside count_host)
+        return count_over(reader, "gcbias",
+                          lambda: DeviceCount(reader, genome, mapq_criteria, references, window)).result(reader)
     return count_host(reader, genome, mapq_criteria, references, window)
 
 

@@ -2,7 +2,8 @@
 (include/pymasc_amd_ingest.h, device) shares: the two libraries' prototypes as data and the one loader that declares them,
 ``PmxIOError`` / ``raise_last``, and the reader bases -- ``NativeReader`` (handle, close, context manager),
 ``AlignmentReader`` (the accessors of the pmx_bam / pmx_sam / pmx_dbam handle families) and ``TrackReader`` (``chromsizes``,
-``kind`` and ``sorted`` of the pmx_track / pmx_dbw handles).
+``kind`` and ``sorted`` of the pmx_track / pmx_dbw handles) --, and what the counts taken beside the correlation share on a device
+reader: ``SIDE_KINDS``, ``SideAccumulator`` and ``count_over``.
 """
 from __future__ import annotations
 
@@ -363,6 +364,39 @@ class AlignmentReader(NativeReader):
         if rc:
             self._raise(rc)
         return ref, pos, rlen, rev.astype(bool)
+
+
+#: the counts taken beside the correlation, in the order a stream reader serves them (it decides which error surfaces first)
+SIDE_KINDS = ("complexity", "fingerprint", "peaks", "coverage", "gcbias")
+
+
+class SideAccumulator:
+    """What a device reader's side count is to ``DeviceStreamReader._windows``: ``add(reader)`` counts what the handle holds now
+    (every window of a stream, the whole of any other device reader); ``begin(reader)`` starts again on a new handle (a regular
+    file opened for another pass); ``flush(reader)`` comes behind the last window.  Here the last two do nothing."""
+
+    def begin(self, reader) -> None:
+        pass
+
+    def flush(self, reader) -> None:
+        pass
+
+
+def count_over(reader, kind: str, make):
+    """The accumulator ``make()`` of ``kind`` (one of ``SIDE_KINDS``) over everything a device reader reads: armed for one pass
+    of a stream reader's windows (a regular file is read once more, any other source raises ``InputUnseekable``), one ``add``
+    for a whole-file reader."""
+    if not hasattr(reader, "_windows"):
+        acc = make()
+        acc.add(reader)
+        return acc
+    acc = reader._arm(kind, make())
+    try:
+        for _ in reader._windows():
+            pass
+    finally:
+        reader._disarm(kind)
+    return acc
 
 
 class TrackReader(NativeReader):

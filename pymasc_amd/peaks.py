@@ -33,7 +33,7 @@ from typing import Dict, Tuple
 import numpy as np
 
 from .complexity import _ratio, _selected_mask
-from .native import PMX_BAM_DEFAULT_EXCLUDE
+from .native import PMX_BAM_DEFAULT_EXCLUDE, SideAccumulator, count_over
 from .region_mask import ExcludeMask, merge, open_mask, resolve_lines
 
 PEAKS_SUFFIX = "_peaks.tab"
@@ -147,7 +147,7 @@ def count_host(ref_id, pos1, read_len, reverse, resolved, use, extend: int = 0) 
     return counts, per_ref
 
 
-class DeviceCount:
+class DeviceCount(SideAccumulator):
     """The table a device reader's handle holds between ``pmx_dbam_peakcount_begin`` and the next one: ``add`` counts what the
     handle holds now (a stream reader calls it for every window), ``result`` reads the counts back."""
 
@@ -214,15 +214,7 @@ def from_reader(reader, peaks, mapq_criteria: int = 0, references=None, extend: 
     and ``count_host``."""
     from .bam_device import DeviceBamReader
     if isinstance(reader, DeviceBamReader):
-        if hasattr(reader, "_windows"):
-            acc = reader.arm_peaks(peaks, mapq_criteria, references, extend)
-            try:
-                for _ in reader._windows():
-                    pass
-                return acc.result(reader)
-            finally:
-                reader.disarm_peaks()
-        return count_device(reader, peaks, mapq_criteria, references, extend)
+        return count_over(reader, "peaks", lambda: DeviceCount(reader, peaks, mapq_criteria, references, extend)).result(reader)
     if int(extend) < 0:
         raise ValueError("extend is not negative")
     lay = _Layout(reader, open_peaks(peaks), references)

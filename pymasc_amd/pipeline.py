@@ -21,7 +21,7 @@ from itertools import zip_longest
 from pathlib import Path
 from typing import List, Optional, Sequence
 
-from . import ffi, readlen, tables
+from . import complexity, coverage, ffi, fingerprint, gcbias, peaks, readlen, tables
 from .chromfilter import NoTargetChromosomesError, filter_references, kept_references
 from .exceptions import InputUnseekable, ReadUnsortedError
 from .inputs import (check_bed_sizes, default_device_ingest, is_stream, open_alignments, open_header, open_track,
@@ -108,14 +108,12 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         if mappability_path is not None and is_fasta(mappability_path):
             track = open_track(mappability_path, track_on_device(mappability_path, False, context),
                                reader_device(context, s.device), k=read_len)
-        mask, bam = _resolve_mask(s, bam_path, bam)     # (no name in common: ValueError before the cache pass and any table)
+        # (no name in common: ValueError before the cache pass and any table)
+        mask, bam = _resolve_regions(s, s.exclude_regions, bam_path, bam)
         _lines, bam = _resolve_regions(s, s.peaks, bam_path, bam)
-        if s.fingerprint_control is not None:
-            if bam is None and is_stream(bam_path) and s.estimate_gpu is not None:      # (no header to read apart, as above)
-                bam = open_alignments(bam_path, True, device=s.estimate_gpu)
-            s.fingerprint_control.check(s, bam_path, bam)
-        if s.gc_bias is not None:
-            s.gc_bias.check(s, bam_path, bam)
+        if s.fingerprint_control is not None and bam is None and is_stream(bam_path) and s.estimate_gpu is not None:
+            bam = open_alignments(bam_path, True, device=s.estimate_gpu)                # (no header to read apart, as above)
+        _check_inputs(s, bam_path, bam)
         known = _mappable_lengths(s, read_len, track, False, mask)
         result, counted = _run_file(s, bam_path, read_len, known, bam, track, mask)
     finally:
@@ -231,6 +229,15 @@ def _check_coverage_input(s: _Settings, path) -> None:
         raise ValueError("'{}' is a stream and cannot be read twice: give coverage_extend an integer".format(path))
 
 
+def _check_inputs(s: _Settings, path, bam) -> None:
+    """ValueError unless the chosen references of ``path`` (``bam``: its open reader, or None: its header is read) are those of
+    the fingerprint control and have their records in the genome of ``gc_bias``, where the call has either."""
+    if s.fingerprint_control is not None:
+        s.fingerprint_control.check(s, path, bam)
+    if s.gc_bias is not None:
+        s.gc_bias.check(s, path, bam)
+
+
 def _estimate(s: _Settings, path, keep: bool):
     """(read length of ``path``, the reader it was estimated on or None): on the device reader on ``s.estimate_gpu``, handed
     back open with ``keep`` to feed the run too, else on the host reader over the whole file, without its index.  A reader
@@ -248,12 +255,6 @@ def _estimate(s: _Settings, path, keep: bool):
     finally:
         if back is None:
             r.close()
-
-
-def _resolve_mask(s: _Settings, path, bam):
-    """(the run's excluded regions bound to the references of ``path`` -- a ``region_mask.ResolvedMask``, None without
-    ``exclude_regions`` --, the open reader of ``path``): ``_resolve_regions`` of ``s.exclude_regions``."""
-    return _resolve_regions(s, s.exclude_regions, path, bam)
 
 
 def _resolve_regions(s: _Settings, regions, path, bam):
@@ -284,7 +285,7 @@ def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool, mask=No
     neither recompute it per chromosome nor read a file that is being rewritten.  Not valid and not to be saved: computed all
     the same with ``unsaved``, else None (each calculator computes its own in the fused pass).  ``track``: the track's open
     reader, or None for rank 0 to open one on the host.  ``mask``: the excluded regions whose positions are cut out of the
-    track first (``_resolve_mask``), with a cache of their own."""
+    track first (``_resolve_regions`` of ``exclude_regions``), with a cache of their own."""
     if s.mappability_path is None:
         return None
 
@@ -317,13 +318,11 @@ def _mappable_lengths(s: _Settings, read_len: int, track, unsaved: bool, mask=No
 
 
 def _run_file(s: _Settings, path, read_len: int, known, bam, track, mask=None):
-    """One file sharded over the ranks: (its genome-wide result, the counts taken beside it: a _ComplexityCount and a
-    _FingerprintCount, a _PeakCount, a _CoverageCount and a _GcBiasCount as asked for).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's and the
-    track's open readers, or None for run_sharded to open its own.  One rank: run_sharded's one ``reader_hook`` serves every
-    count (``_hooks``)."""
-    counted = [c(s) for c, on in ((_ComplexityCount, s.complexity), (_FingerprintCount, s.fingerprint),
-                                     (_PeakCount, s.peaks is not None), (_CoverageCount, s.coverage),
-                                     (_GcBiasCount, s.gc_bias is not None)) if on]
+    """One file sharded over the ranks: (its genome-wide result, the counts taken beside it: the _SideCount of every row of
+    ``_SIDES`` that is asked for, in that order).  ``known``: the lag tables of _mappable_lengths; ``bam`` / ``track``: the file's
+    and the track's open readers, or None for run_sharded to open its own.  One rank: run_sharded's one ``reader_hook`` serves
+    every count (``_hooks``)."""
+    counted = [row.count(s, row) for row in _SIDES if row.enabled(s)]
     hooks = [c.hook for c in counted if c.hooked]
     result = run_sharded(path, s.max_shift, read_len, s.mapq_criteria, bigwig_path=s.mappability_path,
                          references=s.references, skip_ncc=s.skip_ncc, device=s.device, chrom2mappable_len=known,
@@ -348,10 +347,9 @@ def _hooks(hooks):
 
 def _write_file(s: _Settings, path, basename: str, result, read_len: int, counted) -> List[Path]:
     """Rank 0's part after _run_file: ``outdir/<basename>_{cc,mscc,nreads}.tab``, with ``stat_opts`` ``<basename>_stats.tab``
-    whose Name row is ``basename``, and the table of every count in ``counted`` (``<basename>_complexity.tab``,
-    ``<basename>_fingerprint.tab``, ``<basename>_peaks.tab``, ``<basename>_coverage.bedGraph``, ``<basename>_gcbias.tab``); the
-    paths written.  The
-    statistics are computed once, for ``_stats.tab`` and for a pileup that extends to their estimate."""
+    whose Name row is ``basename``, and the output of every count in ``counted`` (``<basename><suffix>`` of its row of
+    ``_SIDES``); the paths written.  The statistics are computed once, for ``_stats.tab`` and for a pileup that extends to their
+    estimate."""
     out = Path(s.outdir)
     out.mkdir(parents=True, exist_ok=True)
     # write_tables names the tables after the stem of its path (table.py:185-188): a suffix keeps a dotted base name whole
@@ -370,39 +368,42 @@ def _write_file(s: _Settings, path, basename: str, result, read_len: int, counte
     return written
 
 
-class _ComplexityCount:
-    """The library complexity of one file's run (pymasc_amd.complexity).  ``hook`` is run_sharded's ``reader_hook`` on one
-    rank: the count is taken on the reader that feeds the run (a stream: armed before the feed, summed window by window).
-    ``write`` writes the table; without a count so far (several ranks) it first counts the chosen chromosomes on one more
-    read of the file, through the reader ``inputs.open_alignments`` gives a run of that many ranks.  ``hooked``: whether the
+class _SideCount:
+    """One count taken beside one file's run, by its row of ``_SIDES``.  ``hook`` is run_sharded's ``reader_hook`` on one rank: the
+    count is taken on the reader that feeds the run -- a stream reader (it has the row's ``arm`` method) is armed before the feed
+    and counted window by window, any other reader is counted after the feed through the module's ``from_reader``.  ``write``
+    writes the table; without a count so far (several ranks) it first counts the chosen chromosomes on one more read of the file,
+    through the reader ``inputs.open_alignments`` gives a run of that many ranks (``_count_again``).  ``hooked``: whether the
     count is taken in ``hook``; ``statistics``: the run's statistics, computed when called (``_write_file``)."""
     hooked = True
 
-    def __init__(self, s: _Settings):
-        self.s = s
+    def __init__(self, s: _Settings, row):
+        self.s, self.row = s, row
         self.value = None
 
-    def hook(self, reader, names):
-        from . import complexity
-        mapq = int(self.s.mapq_criteria)
-        if hasattr(reader, "arm_complexity"):
-            acc = reader.arm_complexity(mapq, names)
+    def _take(self, reader, names, acc=None):
+        """The count of ``reader``: what ``acc``, armed before the feed, has summed, else counted now."""
+        if acc is not None:
+            return acc.result(reader)
+        return self.row.module.from_reader(reader, *self.row.args(self.s, names))
 
-            def after():
-                reader.disarm_complexity()
-                self.value = acc.result()
-            return after
+    def hook(self, reader, names):
+        arm = getattr(reader, self.row.arm, None)       # (a whole-file device reader has none: counted after the feed)
+        acc = None if arm is None else arm(*self.row.args(self.s, names))
 
         def after():
-            self.value = complexity.from_reader(reader, mapq, names)
+            try:
+                self.value = self._take(reader, names, acc)
+            finally:
+                if acc is not None:
+                    reader._disarm(self.row.kind)
         return after
 
     def write(self, path, basename: str, statistics=None) -> Path:
-        from . import complexity
         s = self.s
         if self.value is None:
-            self.value = _count_again(s, path, lambda r, names: complexity.from_reader(r, int(s.mapq_criteria), names))
-        return complexity.write_complexity(Path(s.outdir) / basename, basename, self.value)
+            self.value = _count_again(s, path, self._take)
+        return self.row.write(s, Path(s.outdir) / basename, basename, self.value)
 
 
 def _count_again(s: _Settings, path, count):
@@ -415,103 +416,26 @@ def _count_again(s: _Settings, path, count):
         return count(r, names)
 
 
-class _FingerprintCount:
-    """The bin counts of one file's run (pymasc_amd.fingerprint), taken where _ComplexityCount takes its own: ``hook`` on the
-    reader that feeds the run (a stream: armed before the feed, every window added), ``write`` on one more read when there is
-    no count so far."""
-    hooked = True
-
-    def __init__(self, s: _Settings):
-        self.s = s
-        self.value = None
-
-    def _args(self, names):
-        return int(self.s.mapq_criteria), names, self.s.fingerprint_bin, self.s.fingerprint_extend
-
-    def hook(self, reader, names):
-        from . import fingerprint
-        if hasattr(reader, "arm_fingerprint"):
-            acc = reader.arm_fingerprint(*self._args(names))
-
-            def after():
-                try:
-                    self.value = acc.result(reader)
-                finally:
-                    reader.disarm_fingerprint()
-            return after
-
-        def after():
-            self.value = fingerprint.from_reader(reader, *self._args(names))
-        return after
-
-    def write(self, path, basename: str, statistics=None) -> Path:
-        from . import fingerprint
-        s = self.s
-        if self.value is None:
-            self.value = _count_again(s, path, lambda r, names: fingerprint.from_reader(r, *self._args(names)))
-        control = s.fingerprint_control
-        return fingerprint.write_fingerprint(Path(s.outdir) / basename, basename, self.value,
-                                             None if control is None else control.counts(s), "" if control is None else control.path)
-
-
-class _PeakCount:
-    """The reads per peak line of one file's run (pymasc_amd.peaks), taken where _FingerprintCount takes its own."""
-    hooked = True
-
-    def __init__(self, s: _Settings):
-        self.s = s
-        self.value = None
-
-    def _args(self, names):
-        return self.s.peaks, int(self.s.mapq_criteria), names, self.s.peaks_extend
-
-    def hook(self, reader, names):
-        from . import peaks
-        if hasattr(reader, "arm_peaks"):
-            acc = reader.arm_peaks(*self._args(names))
-
-            def after():
-                try:
-                    self.value = acc.result(reader)
-                finally:
-                    reader.disarm_peaks()
-            return after
-
-        def after():
-            self.value = peaks.from_reader(reader, *self._args(names))
-        return after
-
-    def write(self, path, basename: str, statistics=None) -> Path:
-        from . import peaks
-        s = self.s
-        if self.value is None:
-            self.value = _count_again(s, path, lambda r, names: peaks.from_reader(r, *self._args(names)))
-        return peaks.write_peaks(Path(s.outdir) / basename, basename, self.value, s.peaks.source or "")
-
-
-class _CoverageCount:
-    """The fragment pileup of one file's run (pymasc_amd.coverage).  An integer ``coverage_extend`` is counted where
-    _FingerprintCount takes its own: a host reader's ``Coverage`` is kept for ``write``; a device reader's lines are formatted on
-    the GPU while the reader is open and kept in an unnamed temporary file in the output directory until ``write`` names them.
-    ``"auto"`` needs the run's statistics, so it is not hooked: ``write`` counts with ``statistics().est_lib_len`` on one more
-    read of the file (``_count_again``), as several ranks do for an integer."""
-
-    def __init__(self, s: _Settings):
-        self.s = s
-        self.value = None           # (extend, reads, chunks of lines)
-
+class _CoverageCount(_SideCount):
+    """The fragment pileup of one file's run (pymasc_amd.coverage); its value is (extend, reads, chunks of lines).  An integer
+    ``coverage_extend`` is counted where every _SideCount is: a host reader's ``Coverage`` is kept for ``write``; a device reader's
+    lines are formatted on the GPU while the reader is open and kept in an unnamed temporary file in the output directory until
+    ``write`` names them.  ``"auto"`` needs the run's statistics, so it is not hooked: ``write`` counts with
+    ``statistics().est_lib_len`` on one more read of the file (``_count_again``), as several ranks do for an integer, and writes
+    while that reader is open."""
     hooked = property(lambda self: self.s.coverage_extend != "auto")
-    _armed = None
 
-    def _take(self, reader, names, extend: int, spool: bool):
-        """(extend, reads, the lines) of ``reader``'s pileup; ``spool``: the reader closes before they are written."""
-        from . import coverage
+    def _take(self, reader, names, acc=None, extend=None):
+        """``extend`` None: the run's integer, and the reader closes before the lines are written: they are spooled."""
         from .bam_device import DeviceBamReader
-        mapq = int(self.s.mapq_criteria)
+        spool, mapq = extend is None, int(self.s.mapq_criteria)
+        if spool:
+            extend = int(self.s.coverage_extend)
         if not isinstance(reader, DeviceBamReader):
             c = coverage.from_reader(reader, mapq, names, extend)
             return extend, c.reads, c.text_chunks()
-        acc = self._armed if self._armed is not None else coverage.device_count_of(reader, mapq, names, extend)
+        if acc is None:             # (an armed count is not built again: its ``begin`` would zero the table)
+            acc = coverage.device_count_of(reader, mapq, names, extend)
         reads = acc.finish(reader)["reads"]
         if not spool:
             return extend, reads, acc.text_chunks(reader)
@@ -522,28 +446,13 @@ class _CoverageCount:
             fp.write(chunk)
         return extend, reads, _spooled(fp)
 
-    def hook(self, reader, names):
-        extend = int(self.s.coverage_extend)
-        if hasattr(reader, "arm_coverage"):
-            self._armed = reader.arm_coverage(int(self.s.mapq_criteria), names, extend)
-
-        def after():
-            try:
-                self.value = self._take(reader, names, extend, True)
-            finally:
-                if self._armed is not None:
-                    reader.disarm_coverage()
-                    self._armed = None
-        return after
-
     def write(self, path, basename: str, statistics=None) -> Path:
-        from . import coverage
         s = self.s
         base = Path(s.outdir) / basename
         if self.value is not None:
-            return coverage.write_track(base, basename, *self.value)
+            return self.row.write(s, base, basename, self.value)
         extend = int(statistics().est_lib_len) if s.coverage_extend == "auto" else int(s.coverage_extend)
-        return _count_again(s, path, lambda r, names: coverage.write_track(base, basename, *self._take(r, names, extend, False)))
+        return _count_again(s, path, lambda r, names: self.row.write(s, base, basename, self._take(r, names, None, extend)))
 
 
 def _spooled(fp, size: int = 1 << 22):
@@ -559,39 +468,35 @@ def _spooled(fp, size: int = 1 << 22):
         fp.close()
 
 
-class _GcBiasCount:
-    """The GC bias of one file's run (pymasc_amd.gcbias), taken where _FingerprintCount takes its own, against the call's genome."""
-    hooked = True
+def _write_fingerprint(s: _Settings, base, basename: str, value) -> Path:
+    control = s.fingerprint_control
+    return fingerprint.write_fingerprint(base, basename, value, None if control is None else control.counts(s),
+                                         "" if control is None else control.path)
 
-    def __init__(self, s: _Settings):
-        self.s = s
-        self.value = None
 
-    def _args(self, names):
-        return self.s.gc_bias.open(), int(self.s.mapq_criteria), names, self.s.gc_window
+_Side = namedtuple("_Side", "kind enabled suffix module args arm write count", defaults=(_SideCount,))
+_Side.__doc__ = """One count taken beside the correlation: ``kind`` (its name in ``native.SIDE_KINDS``), ``enabled(s)``, the
+``suffix`` of its output, its ``module`` (``from_reader``), ``args(s, names)`` -- what ``from_reader`` takes after the reader, and
+the stream reader's ``arm`` method (named here) takes --, ``write(s, base, basename, value)`` and the class that takes it."""
 
-    def hook(self, reader, names):
-        from . import gcbias
-        if hasattr(reader, "arm_gcbias"):
-            acc = reader.arm_gcbias(*self._args(names))
-
-            def after():
-                try:
-                    self.value = acc.result(reader)
-                finally:
-                    reader.disarm_gcbias()
-            return after
-
-        def after():
-            self.value = gcbias.from_reader(reader, *self._args(names))
-        return after
-
-    def write(self, path, basename: str, statistics=None) -> Path:
-        from . import gcbias
-        s = self.s
-        if self.value is None:
-            self.value = _count_again(s, path, lambda r, names: gcbias.from_reader(r, *self._args(names)))
-        return gcbias.write_gcbias(Path(s.outdir) / basename, basename, self.value)
+#: every side count, in the order the outputs are written and listed (that of ``native.SIDE_KINDS``)
+_SIDES = (
+    _Side("complexity", lambda s: s.complexity, complexity.COMPLEXITY_SUFFIX, complexity,
+          lambda s, names: (int(s.mapq_criteria), names), "arm_complexity",
+          lambda s, base, basename, value: complexity.write_complexity(base, basename, value)),
+    _Side("fingerprint", lambda s: s.fingerprint, fingerprint.FINGERPRINT_SUFFIX, fingerprint,
+          lambda s, names: (int(s.mapq_criteria), names, s.fingerprint_bin, s.fingerprint_extend), "arm_fingerprint",
+          _write_fingerprint),
+    _Side("peaks", lambda s: s.peaks is not None, peaks.PEAKS_SUFFIX, peaks,
+          lambda s, names: (s.peaks, int(s.mapq_criteria), names, s.peaks_extend), "arm_peaks",
+          lambda s, base, basename, value: peaks.write_peaks(base, basename, value, s.peaks.source or "")),
+    _Side("coverage", lambda s: s.coverage, coverage.COVERAGE_SUFFIX, coverage,
+          lambda s, names: (int(s.mapq_criteria), names, int(s.coverage_extend)), "arm_coverage",
+          lambda s, base, basename, value: coverage.write_track(base, basename, *value), _CoverageCount),
+    _Side("gcbias", lambda s: s.gc_bias is not None, gcbias.GCBIAS_SUFFIX, gcbias,      # (the genome is parsed when first needed)
+          lambda s, names: (s.gc_bias.open(), int(s.mapq_criteria), names, s.gc_window), "arm_gcbias",
+          lambda s, base, basename, value: gcbias.write_gcbias(base, basename, value)),
+)
 
 
 class GenomeError(RuntimeError):
@@ -626,6 +531,8 @@ class _GcGenome:
 
     def check(self, s: _Settings, path, bam) -> None:
         from .gcbias import match_references
+        # the genome is opened before anything here can raise ValueError: run_files takes a ValueError of this check as the
+        # file's (skipped) and relies on a FASTA that cannot be parsed raising GenomeError, the call's, whichever file is first
         genome = self.open()
         if bam is not None:
             refs, lengths = bam.references, bam.lengths
@@ -761,13 +668,21 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
         if mappability_path is not None:        # (a genome FASTA: its k-mer track with k = the read length)
             track = open_track(mappability_path, track_on_device(mappability_path, s.ingest, s.context),
                                getattr(s.context, "device", dev) if is_fasta(mappability_path) else dev, k=read_len)
+
+        def skip(i, e, bam=None):
+            """A file that fails a check before its run is logged and left out like one that cannot be opened."""
+            if bam is not None:
+                bam.close()
+            logger.error("Failed to open file '{}'".format(paths[i]))
+            logger.error(str(e))
+            errors[i] = _portable(e)
         # the excluded regions are bound to every file's references before the cache pass: a file none of whose references the
         # mask names is skipped like a file that cannot be opened; the cache is cut with the first file's clipped intervals.
         # The peak file is bound the same way: a file none of whose references it names is skipped too.
         masks = {}
         for i in list(live):
             try:
-                masks[i], kept_i = _resolve_mask(s, paths[i], kept.get(i))
+                masks[i], kept_i = _resolve_regions(s, s.exclude_regions, paths[i], kept.get(i))
                 if kept_i is not None:
                     kept[i] = kept_i
                 _lines, kept_i = _resolve_regions(s, s.peaks, paths[i], kept.get(i))
@@ -775,9 +690,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
                     kept[i] = kept_i
             except ValueError as e:
                 kept.pop(i, None)
-                logger.error("Failed to open file '{}'".format(paths[i]))
-                logger.error(str(e))
-                errors[i] = _portable(e)
+                skip(i, e)
                 live.remove(i)
         if not live:
             raise ValueError("no input file is left to run")
@@ -788,35 +701,21 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
         for i in live:
             logger.info("Process {}".format(paths[i]))
             bam = kept.pop(i, None)
-            if s.fingerprint_control is not None:   # (from the headers, the same on every rank: skipped like a file that does not open)
-                try:
-                    s.fingerprint_control.check(s, paths[i], bam)
-                except ValueError as e:
-                    if bam is not None:
-                        bam.close()
-                    logger.error("Failed to open file '{}'".format(paths[i]))
-                    logger.error(str(e))
-                    errors[i] = _portable(e)
-                    continue
-            if s.gc_bias is not None:               # (from the headers too: a genome of another assembly skips the file)
-                s.gc_bias.open()
-                try:
-                    s.gc_bias.check(s, paths[i], bam)
-                except ValueError as e:
-                    if bam is not None:
-                        bam.close()
-                    logger.error("Failed to open file '{}'".format(paths[i]))
-                    logger.error(str(e))
-                    errors[i] = _portable(e)
-                    continue
+            # from the headers, the same on every rank: a control or a genome of another assembly skips the file like one that
+            # does not open (ValueError); a FASTA that cannot be parsed is the call's error (GenomeError is none: it propagates)
+            try:
+                _check_inputs(s, paths[i], bam)
+            except ValueError as e:
+                skip(i, e, bam)
+                continue
             try:
                 result, counted = _run_file(s, paths[i], read_len, known, bam, track, masks[i])
             except Exception as e:
-                skip = _unsorted_on_every_rank(e, s.world)
-                if skip is None:
+                unsorted = _unsorted_on_every_rank(e, s.world)
+                if unsorted is None:
                     raise
-                logger.error("Reads of '{}' are not sorted by position: the file is skipped ({})".format(paths[i], skip))
-                errors[i] = skip
+                logger.error("Reads of '{}' are not sorted by position: the file is skipped ({})".format(paths[i], unsorted))
+                errors[i] = unsorted
                 continue
             finally:
                 if bam is not None:
@@ -861,9 +760,8 @@ def _warn_existing(s: _Settings, bases):
     """prepare_output's warning (pymasc.py:178-182) for every output about to be replaced."""
     has_track = s.mappability_path is not None
     suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
-                                ("_stats.tab", s.stat_opts is not None), ("_complexity.tab", s.complexity),
-                                ("_fingerprint.tab", s.fingerprint), ("_peaks.tab", s.peaks is not None),
-                                ("_coverage.bedGraph", s.coverage), ("_gcbias.tab", s.gc_bias is not None)) if on]
+                                ("_stats.tab", s.stat_opts is not None)) if on]
+    suffixes += [row.suffix for row in _SIDES if row.enabled(s)]
     for b in bases:
         for suffix in suffixes:
             path = Path(s.outdir) / (b + suffix)

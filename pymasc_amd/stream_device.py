@@ -19,7 +19,7 @@ import numpy as np
 
 from .bam_device import DeviceBamReader
 from .exceptions import InputUnseekable
-from .native import PMX_BAM_DEFAULT_EXCLUDE, load_ingest_library
+from .native import PMX_BAM_DEFAULT_EXCLUDE, SIDE_KINDS, load_ingest_library
 
 STREAM_INFO_NAMES = ("windows", "bytes_in", "max_tail", "peak_device_bytes", "window_bytes", "inflated_budget")
 
@@ -47,6 +47,7 @@ class DeviceStreamReader(DeviceBamReader):
     def __init__(self, source, device: int = 0, threads: int = 0, window_bytes=None, references=None):
         self._L = load_ingest_library()
         self._own_fd = False
+        self._armed = dict.fromkeys(SIDE_KINDS)     # kind -> the armed accumulator (native.SideAccumulator) or None
         if isinstance(source, int):
             fd, self.path = source, "/dev/fd/{}".format(source)
         elif isinstance(source, (str, bytes, os.PathLike)) and os.fspath(source) in ("-", b"-"):
@@ -106,36 +107,31 @@ class DeviceStreamReader(DeviceBamReader):
             self._selected = selected
             if self._exclude is not None:       # (the mask belongs to the handle: attached again)
                 self.set_exclude(self._exclude)
-            if self._fingerprint is not None:   # (so does the table of bins)
-                self._fingerprint.begin(self)
-            if self._peaks is not None:         # (and the table of peak lines)
-                self._peaks.begin(self)
-            if self._coverage is not None:      # (and the pileup's table)
-                self._coverage.begin(self)
-            if self._gcbias is not None:        # (and the GC table: from the genome it was armed with)
-                self._gcbias.begin(self)
+            for acc in self._each_armed():      # (so do the tables of the side counts: zeroed on the new handle)
+                acc.begin(self)
         self._consumed = True
         while True:
             n = self._L.pmx_dbam_stream_next(self._h)
             if n < 0:
                 self._raise(n)
             if n == 0:
-                if self._complexity is not None:
-                    self._complexity.count(self)    # (what the library held back of the last window)
+                for acc in self._each_armed():
+                    acc.flush(self)                 # (what the library held back of the last window)
                 return
             yield int(n)
-            if self._complexity is not None:        # the caller is done with the window: its arrays stay as they are
-                self._complexity.count(self)
-            if self._fingerprint is not None:
-                self._fingerprint.add(self)
-            if self._peaks is not None:
-                self._peaks.add(self)
-            if self._coverage is not None:
-                self._coverage.add(self)
-            if self._gcbias is not None:
-                self._gcbias.add(self)
+            for acc in self._each_armed():          # the caller is done with the window: its arrays stay as they are
+                acc.add(self)
 
-    _complexity = None
+    def _each_armed(self):
+        """The armed accumulators in the order of ``SIDE_KINDS``, whatever the order they were armed in."""
+        return [acc for acc in self._armed.values() if acc is not None]
+
+    def _arm(self, kind: str, acc):
+        self._armed[kind] = acc
+        return acc
+
+    def _disarm(self, kind: str) -> None:
+        self._armed[kind] = None
 
     def arm_complexity(self, mapq_criteria: int = 0, references=None):
         """From now on every window a pass makes current (``feed``, ``batches``) is also counted for the library complexity
@@ -143,13 +139,10 @@ class DeviceStreamReader(DeviceBamReader):
         ``pymasc_amd.complexity.WindowedCount`` whose ``result()`` is the whole stream's once the pass has ended.  A stream
         that cannot be read twice is counted this way, in the pass that feeds it."""
         from .complexity import WindowedCount
-        self._complexity = WindowedCount(self, mapq_criteria, references)
-        return self._complexity
+        return self._arm("complexity", WindowedCount(self, mapq_criteria, references))
 
     def disarm_complexity(self) -> None:
-        self._complexity = None
-
-    _fingerprint = None
+        self._disarm("complexity")
 
     def arm_fingerprint(self, mapq_criteria: int = 0, references=None, bin_size: int = 500, extend: int = 0):
         """From now on every window a pass makes current is also counted per genome bin (``pmx_dbam_bincount_add``, into the
@@ -157,13 +150,10 @@ class DeviceStreamReader(DeviceBamReader):
         ``result(reader)`` is the whole stream's once the pass has ended.  A read is counted in the window that decodes it, so
         nothing is held back and the stream need not be sorted."""
         from .fingerprint import DeviceCount
-        self._fingerprint = DeviceCount(self, mapq_criteria, references, bin_size, extend)
-        return self._fingerprint
+        return self._arm("fingerprint", DeviceCount(self, mapq_criteria, references, bin_size, extend))
 
     def disarm_fingerprint(self) -> None:
-        self._fingerprint = None
-
-    _peaks = None
+        self._disarm("fingerprint")
 
     def arm_peaks(self, peaks, mapq_criteria: int = 0, references=None, extend: int = 0):
         """From now on every window a pass makes current is also counted per line of ``peaks`` (``pmx_dbam_peakcount_add``, into
@@ -171,13 +161,10 @@ class DeviceStreamReader(DeviceBamReader):
         is the whole stream's once the pass has ended.  A read is counted in the window that decodes it, as for
         ``arm_fingerprint``."""
         from .peaks import DeviceCount
-        self._peaks = DeviceCount(self, peaks, mapq_criteria, references, extend)
-        return self._peaks
+        return self._arm("peaks", DeviceCount(self, peaks, mapq_criteria, references, extend))
 
     def disarm_peaks(self) -> None:
-        self._peaks = None
-
-    _coverage = None
+        self._disarm("peaks")
 
     def arm_coverage(self, mapq_criteria: int = 0, references=None, extend: int = 0):
         """From now on every window a pass makes current is also piled up base by base (``pmx_dbam_coverage_add``, into the table
@@ -185,13 +172,10 @@ class DeviceStreamReader(DeviceBamReader):
         ``result(reader)`` is the whole stream's once the pass has ended.  A read is marked in the window that decodes it, as
         for ``arm_fingerprint``."""
         from .coverage import DeviceCount
-        self._coverage = DeviceCount(self, mapq_criteria, references, extend)
-        return self._coverage
+        return self._arm("coverage", DeviceCount(self, mapq_criteria, references, extend))
 
     def disarm_coverage(self) -> None:
-        self._coverage = None
-
-    _gcbias = None
+        self._disarm("coverage")
 
     def arm_gcbias(self, genome, mapq_criteria: int = 0, references=None, window: int = 100):
         """From now on every window a pass makes current is also placed on the windows of ``genome`` (a FASTA path or an open
@@ -199,11 +183,10 @@ class DeviceStreamReader(DeviceBamReader):
         here); returns the ``pymasc_amd.gcbias.DeviceCount`` whose ``result(reader)`` is the whole stream's once the pass has
         ended.  A read is counted in the window that decodes it, as for ``arm_fingerprint``."""
         from .gcbias import DeviceCount
-        self._gcbias = DeviceCount(self, genome, mapq_criteria, references, window)
-        return self._gcbias
+        return self._arm("gcbias", DeviceCount(self, genome, mapq_criteria, references, window))
 
     def disarm_gcbias(self) -> None:
-        self._gcbias = None
+        self._disarm("gcbias")
 
     def _keep_mask(self):
         if len(self._selected) == len(self.references):

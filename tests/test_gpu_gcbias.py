@@ -180,6 +180,80 @@ def test_every_reader_gives_the_whole_file_table(case, genome, tmp_path, window,
         assert any(a[1] == b[0] and a[1] in piles for a, b in zip(edges, edges[1:])), edges
 
 
+PEAK_LINES = {"g0": [(100, 30_000)], "g2": [(5, 900)]}
+BIN, EXTEND = 500, 150
+
+
+@pytest.fixture(scope="module")
+def whole(case, genome):
+    """``{masked: the five side counts of the whole-file reader, each through its own method}``; counted once, left unchanged."""
+    out = {}
+    for masked in (False, True):
+        with DeviceBamReader(case["bam"]) as r:
+            if masked:
+                r.set_exclude(region_mask.open_mask(GC.MASK).resolve(r.references, r.lengths))
+            out[masked] = dict(complexity=r.library_complexity(GC.MAPQ), fingerprint=r.bin_counts(GC.MAPQ, None, BIN, EXTEND),
+                               peaks=r.peak_counts(PEAK_LINES, GC.MAPQ, None, EXTEND), coverage=r.coverage(GC.MAPQ, None, EXTEND),
+                               gcbias=r.gc_bias(genome, GC.MAPQ, None, 100))
+    return out
+
+
+@pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
+def test_all_five_counts_armed_on_one_stream(case, genome, whole, tmp_path, masked):
+    want = whole[masked]
+    assert want["complexity"].reads > want["fingerprint"].reads > 50_000 and want["peaks"].n_in > 0     # (flagged duplicates kept)
+    fifo = tmp_path / "fifo"
+    os.mkfifo(fifo)
+    blob = open(case["bam"], "rb").read()
+
+    def writer():
+        with open(fifo, "wb") as fp:
+            fp.write(blob)
+    t = threading.Thread(target=writer)
+    t.start()
+    try:
+        with DeviceStreamReader(str(fifo), window_bytes=WINDOW) as r:
+            assert not r.seekable
+            if masked:
+                r.set_exclude(region_mask.open_mask(GC.MASK).resolve(r.references, r.lengths))
+            acc = {}                # armed in another order than the reader serves them in
+            acc["gcbias"] = r.arm_gcbias(genome, GC.MAPQ, None, 100)
+            acc["coverage"] = r.arm_coverage(GC.MAPQ, None, EXTEND)
+            acc["complexity"] = r.arm_complexity(GC.MAPQ, None)
+            acc["peaks"] = r.arm_peaks(PEAK_LINES, GC.MAPQ, None, EXTEND)
+            acc["fingerprint"] = r.arm_fingerprint(GC.MAPQ, None, BIN, EXTEND)
+            for _ in r._windows():
+                pass
+            got = {k: a.result() if k == "complexity" else a.result(r) for k, a in acc.items()}
+            windows = r.stream_info()["windows"]
+    finally:
+        t.join(60)
+    os.unlink(fifo)
+    assert windows >= 4
+    for kind in want:
+        assert got[kind] == want[kind], kind
+
+
+def test_a_second_pass_over_a_file_begins_the_tables_again(case, genome, whole):
+    want = whole[False]
+    with DeviceStreamReader(case["bam"], window_bytes=WINDOW) as r:
+        assert r.seekable
+        acc = dict(fingerprint=r.arm_fingerprint(GC.MAPQ, None, BIN, EXTEND), peaks=r.arm_peaks(PEAK_LINES, GC.MAPQ, None, EXTEND),
+                   coverage=r.arm_coverage(GC.MAPQ, None, EXTEND), gcbias=r.arm_gcbias(genome, GC.MAPQ, None, 100))
+        for _pass in range(2):      # the second pass opens a new handle: its tables begin at zero, so nothing is doubled
+            for _ in r._windows():
+                pass
+        assert r.stream_info()["windows"] >= 4
+        for kind, a in acc.items():
+            assert a.result(r) == want[kind], kind
+        nrf = r.arm_complexity(GC.MAPQ, None)       # its sums live on the host and are never begun again: armed for one pass
+        for _ in r._windows():
+            pass
+        assert nrf.result() == want["complexity"]
+        for kind, a in acc.items():                 # the four were begun once more for the third pass
+            assert a.result(r) == want[kind], kind
+
+
 def test_table_lifetime_and_state(case):
     N, F, off_end, blocked = _want(case, 64)
     with DeviceBamReader(case["bam"]) as r, DeviceBamReader(case["bam"]) as other:

@@ -13,7 +13,9 @@ from pymasc_amd.calculator import CCHipCalculator
 from pymasc_amd.chromfilter import NoTargetChromosomesError
 from pymasc_amd.exceptions import ReadUnsortedError
 from pymasc_amd.mappability import MappabilityStats
+from tests import gcbias_cases as GC
 from tests import io_writers as W
+from tests import sam_writers as SW
 from tests.fake_context import FakeContext
 
 REFS = [("c1", 30000), ("c2", 20000)]
@@ -116,6 +118,50 @@ def test_existing_outputs_are_warned_about(tmp_path, pair, caplog):
     assert len([m for m in msgs if "_mappability.json" not in m]) == 6
 
 
+def test_all_five_side_counts_in_one_run(tmp_path, caplog):
+    """Every side count on in one run writes, file by file, the bytes a run with that count alone writes -- through run and through
+    run_files with two names -- in the order of the table of side counts; a second call warns about exactly these outputs."""
+    fasta = tmp_path / "genome.fa"
+    fasta.write_bytes(GC.fasta_text())
+    bam = SW.write_twins(tmp_path, "gc", GC.REFS, GC.alignment_records(GC.synthetic()))[1]
+    sides = (("_complexity.tab", dict(complexity=True)), ("_fingerprint.tab", dict(fingerprint=True)),
+             ("_peaks.tab", dict(peaks={"g0": [(100, 30_000)], "g2": [(5, 900)]})),
+             ("_coverage.bedGraph", dict(coverage=True, coverage_extend=150)), ("_gcbias.tab", dict(gc_bias=str(fasta))))
+    everything = {k: v for _suffix, options in sides for k, v in options.items()}
+    kw = dict(read_len=36, mapq_criteria=GC.MAPQ, device_ingest=False, exclude_regions=GC.MASK)
+    bases = ("gc", "B")
+
+    def files(out, paths=(bam, bam), **options):
+        got = pipeline.run_files(list(paths), tmp_path / out, SHIFT, names=[None, "B"][:len(paths)], context=FakeContext(),
+                                 **kw, **options)
+        assert [g.error for g in got] == [None] * len(paths)
+        return [g.written for g in got]
+
+    def overwritten():
+        return [r.getMessage() for r in caplog.records if "will be overwritten" in r.getMessage()]
+    alone = {}                      # output name -> the bytes of a call with that count alone
+    for suffix, options in sides:
+        for base, written in zip(bases, files("only" + suffix, **options)):
+            assert written[-1].name == base + suffix and not any(p.name.endswith(x) for p in written[:-1] for x, _o in sides)
+            alone[base + suffix] = written[-1].read_bytes()
+    _r, written = pipeline.run(bam, tmp_path / "all", SHIFT, context=FakeContext(), **kw, **everything)
+    plain = [p.name for p in written[:-5]]
+    assert plain and [p.name for p in written[-5:]] == ["gc" + suffix for suffix, _o in sides]
+    assert all(p.read_bytes() == alone[p.name] for p in written[-5:])
+    caplog.set_level(logging.WARNING)
+    again, = files("all", paths=(bam,), **everything)       # the same call once more, by the entry point that warns (run does not)
+    assert again == written and all(p.read_bytes() == alone[p.name] for p in again[-5:])
+    assert sorted(overwritten()) == sorted("Existing file '{}' will be overwritten.".format(p) for p in written)
+    caplog.clear()
+    many = files("many", **everything)
+    assert not overwritten()
+    for base, written in zip(bases, many):
+        assert [p.name for p in written] == [base + n[2:] for n in plain] + [base + suffix for suffix, _o in sides]
+        assert all(p.read_bytes() == alone[p.name] for p in written[-5:])
+    assert files("many", **everything) == many
+    assert sorted(overwritten()) == sorted("Existing file '{}' will be overwritten.".format(p) for w in many for p in w)
+
+
 @pytest.mark.parametrize("kw", [dict(names=["a", "b", "c"]), dict(names=["a", "a"]), dict(names=["x/y"]), dict(names=[""]),
                                 dict(library_length=0), dict(smooth_window=0), dict(readlen_estimator="AVERAGE"),
                                 dict(references=["c1"], chromfilter=[(True, ["c1"])]), dict(same_stem=True)])
@@ -174,6 +220,27 @@ def test_a_file_the_chromosome_filter_empties_is_skipped(tmp_path, caplog):
 def test_an_unsorted_file_is_skipped(tmp_path):
     got = _three(tmp_path, _bam(tmp_path / "unsorted.bam", 36, 6, unsorted=True))
     assert isinstance(got[1].error, ReadUnsortedError)
+
+
+@pytest.mark.parametrize("check", ["control", "genome"])
+def test_a_file_that_fails_a_check_after_an_unsorted_file_is_skipped_too(tmp_path, check):
+    """An unsorted file, then a file whose references are not the fingerprint control's / the genome's, then a good one: the first
+    two are skipped with their errors and the third is run and written."""
+    other = [REFS[0], ("c2", REFS[1][1] - 1000)]
+    paths = [_bam(tmp_path / "unsorted.bam", 36, 6, unsorted=True), _bam(tmp_path / "other.bam", 36, 7, refs=other),
+             _bam(tmp_path / "good.bam", 36, 8)]
+    if check == "control":
+        kw, table, said = dict(fingerprint_control=_bam(tmp_path / "control.bam", 36, 9)), "good_fingerprint.tab", "differ from those of"
+    else:
+        rng = np.random.default_rng(10)
+        fasta = tmp_path / "genome.fa"
+        fasta.write_text("".join(">{}\n{}\n".format(n, "".join(rng.choice(list("ACGT"), size=l))) for n, l in REFS))
+        kw, table, said = dict(gc_bias=str(fasta)), "good_gcbias.tab", "reference 'c2' is 19000 long in the alignment header"
+    got = _many(tmp_path, paths, read_len=36, **kw)
+    assert isinstance(got[0].error, ReadUnsortedError) and isinstance(got[1].error, ValueError) and said in str(got[1].error)
+    assert all(g.result is None and g.written == [] for g in got[:2])
+    assert got[2].error is None and [p.name for p in got[2].written] == ["good_cc.tab", "good_mscc.tab", "good_nreads.tab", table]
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(p.name for p in got[2].written)
 
 
 def test_a_file_whose_estimate_exceeds_max_shift_is_skipped(tmp_path, caplog):
