@@ -340,6 +340,49 @@ __device__ __forceinline__ u32 ev_below(u32 last_dword, u32 first)
     return (u32)__builtin_amdgcn_update_dpp((int)first, (int)last_dword, 0x138, 0xf, 0xf, false);   // wave_shr:1
 }
 
+// a, b := their sums over each quad of lanes, in every lane of the quad (two butterfly steps, one v_add_u32_dpp each; the
+// s_nop cover the two wait states of a DPP operand written by the VALU instruction before: see PMX_SCAN_STEP)
+__device__ __forceinline__ void ev_quad_sum2(u32 &a, u32 &b)
+{
+    asm volatile("s_nop 4\n\t"
+                 "v_add_u32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_add_u32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 0\n\t"
+                 "v_add_u32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_add_u32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+                 : "+v"(a), "+v"(b));
+}
+
+// index of the lowest / (from the top) of the highest set bit of a dword, ALL ONES for zero -- the plain instructions: the
+// builtins either leave zero undefined or add a v_min 32, and all ones is what the combination below wants
+__device__ __forceinline__ u32 ev_ffbl(u32 x)
+{
+    u32 r;
+    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+__device__ __forceinline__ u32 ev_ffbh(u32 x)
+{
+    u32 r;
+    asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+__device__ __forceinline__ u32 ev_min4(u32 a, u32 b, u32 c, u32 d) { return min(min(a, b), min(c, d)); }
+
+// The run edges of one quad WITHOUT a loop, for a quad that holds at most two (`cnt` = popcount of the edge words `e`; ~90 %
+// of the lanes hold none, nearly all others one or two): the first is the lowest set bit, the second the highest.  Lanes
+// without a first / second edge store to their dump slot.  The flag of an entry (bit 31: falling, M is 0 at the edge) needs no
+// look at M: below its first edge a quad continues the bit below it (`below` = the dword under the quad), and edges alternate.
+// `list_at`, `dump_at`: dword indices into `lds`; `base_bit`: a multiple of 128.
+__device__ __forceinline__ void ev_emit_edges2(const uint4 e, u32 below, u32 cnt, u32 list_at, u32 dump_at, u32 base_bit, u32 *lds)
+{
+    const u32 first = ev_min4(ev_ffbl(e.x), ev_ffbl(e.y) | 32u, ev_ffbl(e.z) | 64u, ev_ffbl(e.w) | 96u);
+    const u32 last = 127u - ev_min4(ev_ffbh(e.w), ev_ffbh(e.z) | 32u, ev_ffbh(e.y) | 64u, ev_ffbh(e.x) | 96u);
+    const u32 fall = below & 0x80000000u;
+    lds[cnt > 0 ? list_at : dump_at] = base_bit | first | fall;
+    lds[cnt > 1 ? list_at + 1 : dump_at] = (base_bit | last | 0x80000000u) ^ fall;
+}
+
 __device__ __forceinline__ u32 ev_mbit(const u32 *MT, u32 q) { return (MT[q >> 5] >> (q & 31u)) & 1u; }
 
 // signed add to cell `cell` of a GF / GR / EE row (see EvLds)
@@ -534,21 +577,43 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
         u32 gnext = g + NSG;
         if (act) {
             u32 bF = 0, bR = 0, bH = 0, bE = 0, bX = 0, tF = 0, tR = 0, tH = 0, tE = 0, tX = 0;
-#pragma unroll
-            for (u32 w = 0; w < 4; w++) {
-                const u32 xF = wt[w], xR = wt[4 + w], xH = wt[8 + w], xE = HAS_M ? wt[12 + w] : 0u, xX = HAS_M ? wt[16 + w] : 0u;
-                if (w < wave) {
-                    bF += xF;
-                    bR += xR;
-                    bH += xH;
-                    bE += xE;
-                    bX += xX;
+            if (!BIG) {
+                // wt is [field][wave]: ONE load puts its 20 words into lanes 0..19, a quad of lanes per field, and two butterfly
+                // steps inside the quads leave in every lane of quad f the field's total (from the words as they are) and this
+                // wave's base (from the words of the waves below it, the others zeroed).  Lanes 20.. hold whatever follows the
+                // totals in LDS (NCC-only: quads 3 and 4 too) and are not read.
+                const u32 x = wt[lane & 31u];
+                u32 t = x, b = (lane & 3u) < wave ? x : 0u;
+                ev_quad_sum2(t, b);
+                tF = (u32)__builtin_amdgcn_readlane((int)t, 0);
+                tR = (u32)__builtin_amdgcn_readlane((int)t, 4);
+                tH = (u32)__builtin_amdgcn_readlane((int)t, 8);
+                bF = (u32)__builtin_amdgcn_readlane((int)b, 0);
+                bR = (u32)__builtin_amdgcn_readlane((int)b, 4);
+                bH = (u32)__builtin_amdgcn_readlane((int)b, 8);
+                if (HAS_M) {
+                    tE = (u32)__builtin_amdgcn_readlane((int)t, 12);
+                    tX = (u32)__builtin_amdgcn_readlane((int)t, 16);
+                    bE = (u32)__builtin_amdgcn_readlane((int)b, 12);
+                    bX = (u32)__builtin_amdgcn_readlane((int)b, 16);
                 }
-                tF += xF;
-                tR += xR;
-                tH += xH;
-                tE += xE;
-                tX += xX;
+            } else {
+#pragma unroll
+                for (u32 w = 0; w < 4; w++) {
+                    const u32 xF = wt[w], xR = wt[4 + w], xH = wt[8 + w], xE = HAS_M ? wt[12 + w] : 0u, xX = HAS_M ? wt[16 + w] : 0u;
+                    if (w < wave) {
+                        bF += xF;
+                        bR += xR;
+                        bH += xH;
+                        bE += xE;
+                        bX += xX;
+                    }
+                    tF += xF;
+                    tR += xR;
+                    tH += xH;
+                    tE += xE;
+                    tX += xX;
+                }
             }
             const u32 TF0 = tF & 0xffffu, TR0 = tR & 0xffffu;
             TE0 = tE & 0xffffu;
@@ -623,21 +688,40 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                 // the run edges (+ those of the halos) in position order
                 const u32 eE = bE + sE - pE, eX = bX + sX - pH;
                 const u32 oE0 = TXb + (eE & 0xffffu), oE1 = TXb + TE0 + (eE >> 16);
+                // (uniform) the ordinary tile: no quad of this wave holds more than two edges, and every quad is listed in
+                // straight-line code (ev_emit_edges2); else the loops below take the whole wave
+                const u32 cmax = max(max(cE[0], cE[1]), cEh);
+                if (!BIG && !__ballot(cmax > 2)) {
+                    const u32 le_at = (u32)(LE - lds), dump_at = L::o_dump(HN) + lane;
 #pragma unroll
-                for (u32 q = 0; q < EV_NQ; q++) {
-                    const uint4 Eq = edge_words(er.m[q], ev_below(er.m[q].w, er.wb[q]));
-                    const u32 o = q ? oE1 : oE0;
-                    ap_emit(Eq, er.m[q], o, BIAS + q * SP_TB + 128u * tid, LE);
-                }
-                const uint4 Eh = edge_words(er.h, ev_below(er.h.w, er.hbw));
-                if (h_below) {
-                    ap_emit(Eh, er.h, eX & 0xffffu, 128u * hb, LE);
-                } else if (h_above) {
-                    const u32 oa = TXb + TE0 + TE1 + (eX >> 16);
-                    ap_emit(Eh, er.h, oa, BIAS + EV_TB + 128u * lane, LE);
-                    // (BIG with the mappable-length pairs: the run edges further above the tile than the read length are in
-                    // the list as PARTNERS of the pairs only; the edge events of fsum / rsum end in front of them)
-                    if (BIG && DO_MLEN && lane == EV_HI / 4u) sgb[L::MISC + 1] = oa;
+                    for (u32 q = 0; q < EV_NQ; q++) {
+                        const u32 bel = ev_below(er.m[q].w, er.wb[q]);
+                        ev_emit_edges2(edge_words(er.m[q], bel), bel, cE[q], le_at + (q ? oE1 : oE0), dump_at,
+                                       BIAS + q * SP_TB + 128u * tid, lds);
+                    }
+                    if (wave == 1 || wave == 2) {   // the halo quads of M: wave 1 below the tile, wave 2 above it (cEh: 0 beyond the role)
+                        const u32 hbel = ev_below(er.h.w, er.hbw);
+                        const u32 oh = wave == 1 ? (eX & 0xffffu) : TXb + TE0 + TE1 + (eX >> 16);
+                        ev_emit_edges2(edge_words(er.h, hbel), hbel, cEh, le_at + oh, dump_at,
+                                       (wave == 1 ? 0u : BIAS + EV_TB) + 128u * lane, lds);
+                    }
+                } else {
+#pragma unroll
+                    for (u32 q = 0; q < EV_NQ; q++) {
+                        const uint4 Eq = edge_words(er.m[q], ev_below(er.m[q].w, er.wb[q]));
+                        const u32 o = q ? oE1 : oE0;
+                        ap_emit(Eq, er.m[q], o, BIAS + q * SP_TB + 128u * tid, LE);
+                    }
+                    const uint4 Eh = edge_words(er.h, ev_below(er.h.w, er.hbw));
+                    if (h_below) {
+                        ap_emit(Eh, er.h, eX & 0xffffu, 128u * hb, LE);
+                    } else if (h_above) {
+                        const u32 oa = TXb + TE0 + TE1 + (eX >> 16);
+                        ap_emit(Eh, er.h, oa, BIAS + EV_TB + 128u * lane, LE);
+                        // (BIG with the mappable-length pairs: the run edges further above the tile than the read length are in
+                        // the list as PARTNERS of the pairs only; the edge events of fsum / rsum end in front of them)
+                        if (BIG && DO_MLEN && lane == EV_HI / 4u) sgb[L::MISC + 1] = oa;
+                    }
                 }
                 if (tid >= 2 * EV_PAD && tid < 2 * EV_PAD + 4) LE[nE + tid - 2 * EV_PAD] = EV_POS;   // sentinels
                 cntM += pendM;
