@@ -64,7 +64,20 @@ extern "C" {
                                    * up to ~1.5 % read starts per strand on an ordinary track).  Without ANY of the three
                                    * hints pmx_cc_batch_dev / pmx_calc_correlation take one from a sample of the vectors
                                    * themselves (16 tiles of each of the largest chromosomes: one small launch and ONE
-                                   * SYNCHRONISATION of the stream per call, ~20 us): pass a hint to stay asynchronous */
+                                   * SYNCHRONISATION of the stream per call, ~20 us): pass a hint to stay asynchronous.
+                                   * This hint and PMX_FLAG_DEEP_LISTS (and the sample's own choice of either) also select
+                                   * the event kernel WITHOUT its job-wide verdict on dense chromosomes (max_shift <= 1023):
+                                   * a tile beyond the lists is still found and handed to the window kernels, one by one,
+                                   * and the integers are the same, but a chromosome with 60 % of its tiles beyond them is
+                                   * no longer handed over as a whole after 16 tiles.  A hint from AVERAGES (as
+                                   * calculator.window_only_hint / deep_lists_hint) can be given to such a chromosome --
+                                   * an average tile at 1450..2053 of the pool's 2416 entries with the reads piled on 60 %
+                                   * of the tiles, the rest empty --: that call pays the event kernel's pass in front of
+                                   * the window kernels (0.21-0.28 ms per hg38 genome).  The ordinary route to it: a pass
+                                   * carries ONE hint, the one most of its positions ask for (calculator._run_cc, and the
+                                   * sample of pmx_cc_batch_dev): chromosomes whose own rule says PMX_FLAG_WINDOW_ONLY, with
+                                   * up to half of the pass's positions, ride under this hint and pay that pass for their
+                                   * tiles where the verdict handed them over after 16.  PMX_FLAG_FORCE_SPARSE keeps the verdict */
 #define PMX_FLAG_SKIP_MLEN    8u  /* the caller holds mappable_len already (the *_mappability.json cache,
                                    * handler/mappability.py:239-259): no autocorrelation pass; row 4 and
                                    * scalars[2] are written as zeros */

@@ -182,6 +182,13 @@ __device__ __forceinline__ u32 ev_role_mlo_index(u32 tid) { return BIG ? tid : (
 #define EV_BIG_NT 1
 #endif
 typedef u32 ev_v4u __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) const u32 ev_lds_cu32;   // a dword of LDS, addressed by its 32-bit byte address
+// entry k of a list behind position `at`: an index into `list`, or (BY_ADDRESS) the LDS byte address of the entry itself
+template <bool BY_ADDRESS>
+__device__ __forceinline__ u32 ev_list2(const u32 *list, u32 at, u32 k)
+{
+    return BY_ADDRESS ? ((ev_lds_cu32 *)(size_t)at)[k] : list[at + k];
+}
 template <bool GUARD, bool NT>
 __device__ __forceinline__ uint4 ev_ld_body(const u32 *__restrict__ p, int64_t j, uint64_t nbits)
 {
@@ -414,7 +421,11 @@ __device__ __forceinline__ void ev_zero_row5(u32 *__restrict__ slab, u32 segment
 // DEEP (max_shift <= 1023 with M only): a pool of EV_POOL_DEEP entries at four workgroups per CU, for callers that know their
 // data is deep (PMX_FLAG_DEEP_LISTS): between ~1.5 % and ~3.2 % read starts per strand the event formulation is still twice
 // as fast as the window kernels, but the five-per-CU instantiation would hand most tiles over.
-template <bool HAS_M, bool DO_NCC, bool DO_MLEN, u32 NSG, bool BIG, typename JT = SpJobTable, bool DEEP = false>
+// KNOWN_SPARSE (max_shift <= 1023): the caller's hint -- or the density probe -- says that the chromosomes fit the lists
+// (PMX_FLAG_EVENTS_HINT, PMX_FLAG_DEEP_LISTS).  Every tile is still tested against the list capacities and a dense one is
+// flagged on its own, but the job-wide verdict (job_mode below) and everything it carries from tile to tile is compiled out:
+// a chromosome whose tiles are mostly dense after all is flagged tile by tile instead of being handed over in one go.
+template <bool HAS_M, bool DO_NCC, bool DO_MLEN, u32 NSG, bool BIG, typename JT = SpJobTable, bool DEEP = false, bool KNOWN_SPARSE = false>
 __global__ void __launch_bounds__(256 * NSG, BIG ? 4 : (HAS_M ? (DEEP ? 4 : EV_WAVES) : EV_WAVES_NCC))
 k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, u32 S, u32 nhr, u32 max_lag,
             u32 hn_arg, u32 lo_arg, u32 hi_arg, u32 *__restrict__ slab, unsigned char *__restrict__ tile_flags,
@@ -423,6 +434,10 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
     typedef EvLds<HAS_M, BIG, DEEP> L;
     static_assert(!DEEP || (HAS_M && !BIG), "DEEP: the max_shift <= 1023 instantiations with a track");
     static_assert(BIG || NSG == 1, "the max_shift <= 1023 instantiations are one sub-group per workgroup");
+    static_assert(!KNOWN_SPARSE || !BIG, "KNOWN_SPARSE: the max_shift <= 1023 instantiations");
+    constexpr bool VERDICT = NSG == 1 && !KNOWN_SPARSE;   // the job-wide verdict on dense chromosomes (job_mode, below)
+    // the run starts of a tile from its edge totals instead of from every quad (see the listing of the run edges)
+    constexpr bool RUNS_PER_TILE = KNOWN_SPARSE && DO_MLEN;
     constexpr u32 NT = 256 * NSG;
     extern __shared__ __align__(16) u32 ev_dyn_lds[];
     __shared__ __align__(16) u32 ev_static_lds[BIG ? 4 : L::total(1024, EV_LO, 1)];
@@ -486,6 +501,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
     // per-workgroup rule the unlucky ones walked their whole range while the others had left (round 3, first try), and a
     // density right at a list capacity paid for both kernels (round 2: +30 % between 1.1 % and 2 % reads per strand).
     // Isolated dense tiles -- a pile-up, a repeat -- are flagged one by one whatever the verdict.
+    // (KNOWN_SPARSE: none of this; the five variables below stay what they are here)
     u32 job_mode = 0;                  // (uniform)
     u32 unreported = 0;                // (uniform) tiles of this job seen since my last report to jobstat
     bool had_dense = false;            // (uniform) a verdict may have been left in LDS since the job began
@@ -532,7 +548,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                     if (DO_MLEN) {
                         pendM += popc4(er.m[q]);
                         // run starts = rising edges; rising - falling = M[last bit of the quad] - M[bit before it]
-                        pendU += (cE[q] + (er.m[q].w >> 31) - (bel >> 31)) >> 1;
+                        if (!RUNS_PER_TILE) pendU += (cE[q] + (er.m[q].w >> 31) - (bel >> 31)) >> 1;
                     }
                 }
             }
@@ -628,7 +644,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
             // edge pairs of the mappable-length pass (DO_MLEN), so that deep data on an ordinary track does not push that pass onto
             // its window kernel as well.
             const bool dense_e = HAS_M && nE > EV_CAPE(BIG);
-            const bool dense_r = cur_skip || (BIG ? (nF > EV_CAPF || nR > EV_CAPR)
+            const bool dense_r = (VERDICT && cur_skip) || (BIG ? (nF > EV_CAPF || nR > EV_CAPR)
                                                   : nF + nR + ((HAS_M && !dense_e) ? nE : 0u) > L::POOL);
             dense = dense_e || dense_r;
             do_edges = HAS_M && !dense_e && (!dense || DO_MLEN);
@@ -657,12 +673,19 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                     if (tid == 255) {
                         idxF[128] = (unsigned short)nF;
                         idxR[128] = (unsigned short)nRt;
+                        if (RUNS_PER_TILE) xch[0] += er.m[EV_NQ - 1].w >> 31;   // M[last bit of the tile]
                     }
                 }
                 if (tid == 0) {
                     if (NSG == 1) {   // one thread between two barriers: plain adds (the atomic optimiser wraps an LDS atomic in a
                         xch[8 + 0] += nF;   // wave reduction of ~14 instructions, even under tid == 0)
                         xch[8 + 1] += nRt;
+                        // RUNS_PER_TILE: the quads' "rising - falling" telescope over the tile, and the rows' edge totals are
+                        // at hand: twice the run starts of the tile = its edges + M[its last bit] - M[the bit below it], the
+                        // first and the third term from this thread (er.wb[0]: the dword below the tile), the second from
+                        // thread 255 (above); xch[8 + 5] and xch[0] are added and halved at the flush.  (A tile that is not
+                        // dense lists its edges: do_edges holds here; the dense tile with listed edges: below)
+                        if (RUNS_PER_TILE) xch[8 + 5] += TE0 + TE1 - (er.wb[0] >> 31);
                     } else {          // (thread 0 of EVERY sub-group comes here)
                         atomicAdd(&xch[8 + 0], nF);
                         atomicAdd(&xch[8 + 1], nRt);
@@ -682,6 +705,10 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                 if (NSG == 1 && tid == 0) {      // (added to n_flagged when the workgroup leaves the job)
                     xch[14] += 1;
                     if (DO_MLEN && dense_e) xch[15] += 1;
+                }
+                if (RUNS_PER_TILE && do_edges) {   // (too many reads only: the run edges are listed)
+                    if (tid == 0) xch[8 + 5] += TE0 + TE1 - (er.wb[0] >> 31);
+                    if (tid == 255) xch[0] += er.m[EV_NQ - 1].w >> 31;
                 }
             }
             if (do_edges) {
@@ -725,9 +752,9 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                 }
                 if (tid >= 2 * EV_PAD && tid < 2 * EV_PAD + 4) LE[nE + tid - 2 * EV_PAD] = EV_POS;   // sentinels
                 cntM += pendM;
-                cntU += pendU;
+                if (!RUNS_PER_TILE) cntU += pendU;
             }
-            if (NSG == 1) {
+            if (VERDICT) {
                 // the job's counters.  A workgroup reports when it meets a dense tile -- that tile and the tiles it has seen since
                 // its last report, so every report is unbiased -- and leaves its verdict for everybody (read after B1): the
                 // ordinary tile costs no global atomic, and a workgroup that never sees a dense tile never asks for a verdict
@@ -787,13 +814,13 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                 if (gnext >= pj.tile_end) {   // rare: the next tile belongs to the next job
                     jn = ji + 1;
                     load_job(pj, jobs.j[jn]);
-                    next_skip = false;
+                    if (VERDICT) next_skip = false;
                 }
                 if (NSG > 1) {
                     const u32 lim = pj.tile_end < g1 ? pj.tile_end : g1;
                     act_var = gnext + sg < lim;
                 }
-                if (NSG == 1 || act_var) ev_fetch_job<HAS_M, BIG>(er, pj, gnext + sg - pj.tile0, tid, nhr, LO, NSG == 1 && next_skip, wave, HI);
+                if (NSG == 1 || act_var) ev_fetch_job<HAS_M, BIG>(er, pj, gnext + sg - pj.tile0, tid, nhr, LO, VERDICT && next_skip, wave, HI);
             } else if (NSG > 1) {
                 act_var = false;
             }
@@ -847,8 +874,8 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
             }
             prefetch_next();
         }
-        const bool fetched_skip = NSG == 1 && next_skip;
-        if (NSG == 1 && had_dense) {
+        const bool fetched_skip = VERDICT && next_skip;
+        if (VERDICT && had_dense) {
             const u32 v = __builtin_amdgcn_readfirstlane(sgb[L::MISC]);   // thread 0's verdict on the job (see job_mode)
             job_mode = v > job_mode ? v : job_mode;
         }
@@ -872,16 +899,21 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                 const u32 x = ent & EV_POS, xc = x + c;
                 const u32 flm = HAS_M ? (ent >> 31) << 16 : 0u;   // mappable: the increment of the cc half
                 if (HAS_M && flm) cntB += ev_mbit(MT, xc);   // Bf = sum of M[x + c]
-                u32 r = (ent >> 17) & ((1u << EV_RANK_BITS) - 1u);
-                u32 y0 = LR[r], y1 = LR[r + 1];
+                // KNOWN_SPARSE: the partner is carried as an LDS byte address, not as an index -- per trip an index costs a
+                // shift-and-add and the add of the list's offset, which is beyond the reach of the two-dword load's immediates
+                const u32 rk = (ent >> 17) & ((1u << EV_RANK_BITS) - 1u);
+                const u32 lr0 = KNOWN_SPARSE ? (u32)(size_t)(ev_lds_cu32 *)LR : 0u;
+                const u32 rstep = KNOWN_SPARSE ? 8u : 2u, rend = KNOWN_SPARSE ? lr0 + 4u * nR : nR;
+                u32 r = KNOWN_SPARSE ? lr0 + 4u * rk : rk;
+                u32 y0 = ev_list2<KNOWN_SPARSE>(LR, r, 0), y1 = ev_list2<KNOWN_SPARSE>(LR, r, 1);
                 u32 d0 = y0 - x, d1 = y1 - x;
                 bool h0 = d0 <= S, h1 = d1 <= S;   // sorted: h1 implies h0
                 // (a bottom-tested loop: one compare + one branch per trip; with the test in the middle the structurizer
                 // spends six scalar instructions per trip on the exit flag)
                 if (__ballot(h0)) do {
-                    r = h1 ? r + 2 : nR;
-                    y0 = LR[r];
-                    y1 = LR[r + 1];
+                    r = h1 ? r + rstep : rend;
+                    y0 = ev_list2<KNOWN_SPARSE>(LR, r, 0);
+                    y1 = ev_list2<KNOWN_SPARSE>(LR, r, 1);
                     const u32 a0 = h0 ? d0 : dumpN, a1 = h1 ? d1 : dumpN;
                     if (HAS_M) {
                         const u32 q0 = xc - (h0 ? d0 : 0u), q1 = xc - (h1 ? d1 : 0u);
@@ -1168,12 +1200,13 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                         if ((gt & 63u) == 0) {
 #pragma unroll
                             for (u32 k = 0; k < 4; k++)
-                                if (k < 2 || DO_MLEN) atomicAdd(&xch[8 + 2 + k], v[k]);
+                                if (k < 2 || (DO_MLEN && !(RUNS_PER_TILE && k == 3))) atomicAdd(&xch[8 + 2 + k], v[k]);   // (RUNS_PER_TILE: cntU is not used)
                         }
                         cntB = cnt0 = cntM = cntU = 0;
                     }
                     __syncthreads();
-                    const u32 a0 = xch[8 + 4], runs = xch[8 + 5];
+                    // (RUNS_PER_TILE: twice the run starts, in two parts: see the emit)
+                    const u32 a0 = xch[8 + 4], runs = RUNS_PER_TILE ? (xch[8 + 5] + xch[0]) >> 1 : xch[8 + 5];
                     // (b) cells 4 t .. 4 t + 3 of the three rows
                     const u32 k0 = 4 * gt;
                     const uint4 wgf = *reinterpret_cast<const uint4 *>(hGF + k0), wgr = *reinterpret_cast<const uint4 *>(hGF + 1024 + k0);
@@ -1250,13 +1283,14 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                     *reinterpret_cast<uint4 *>(hGF + 1024 + k0) = make_uint4(0, 0, 0, 0);
                     // (c) the scalar row of the segment and the chromosome's totals (k_events_finish reads six words per job)
                     if (gt < 6) {
-                        const u32 v = xch[8 + gt];
+                        const u32 v = (RUNS_PER_TILE && gt == 5) ? runs : xch[8 + gt];
                         u32 *ds = seg + 4 * HN + gt;
                         *ds = add ? *ds + v : v;
                         if (v) atomicAdd(EV_JOBSUM(jobstat) + 6 * ji + gt, (unsigned long long)v);
                     }
                     __syncthreads();
                     if (gt < 6) xch[8 + gt] = 0;
+                    if (RUNS_PER_TILE && gt == 6) xch[0] = 0;
                 }
             }
             accF = 0;
@@ -1297,13 +1331,15 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
         }
         if (jn != ji) {
             if (BIG && DO_MLEN && !EE_LDS) ev_zero_row5(slab, blockIdx.x + jn, HN, gt, NT);   // (the barrier at the top of the loop follows)
-            job_mode = 0;
-            next_skip = false;
-            unreported = 0;
-            if (had_dense && tid_ == 0) sgb[L::MISC] = 0;   // (read again after the next tile's B1 at the earliest)
-            had_dense = false;
+            if (VERDICT) {
+                job_mode = 0;
+                next_skip = false;
+                unreported = 0;
+                if (had_dense && tid_ == 0) sgb[L::MISC] = 0;   // (read again after the next tile's B1 at the earliest)
+                had_dense = false;
+            }
         }
-        cur_skip = fetched_skip;
+        if (VERDICT) cur_skip = fetched_skip;
         ji = jn;
         cur_tile0 = pj.tile0;
         cur_flag0 = pj.flag0;

@@ -2461,7 +2461,7 @@ static bool ev_big_plan(uint32_t max_shift, EvBigPlan *p, uint32_t fused_lag = 0
 // (cached per DEVICE: a process may hold one context per GPU, and both the occupancy answer and the function attribute of
 // ev_big_launch belong to the current device)
 #define EV_MAX_DEVICES 64
-template <bool HAS_M, bool DO_NCC, bool DO_MLEN, bool DEEP>
+template <bool HAS_M, bool DO_NCC, bool DO_MLEN, bool DEEP, bool KNOWN>
 static u32 ev_resident_per_cu(pmx_ctx *ctx, u32 built_for)
 {
     static int cached[EV_MAX_DEVICES];
@@ -2469,7 +2469,7 @@ static u32 ev_resident_per_cu(pmx_ctx *ctx, u32 built_for)
     const int dev = ctx->device >= 0 && ctx->device < EV_MAX_DEVICES ? ctx->device : -1;
     int n = dev >= 0 && known[dev] ? cached[dev] : -1;
     if (n < 0) {
-        auto kern = k_cc_events<HAS_M, DO_NCC, DO_MLEN, 1, false, SpJobTable, DEEP>;
+        auto kern = k_cc_events<HAS_M, DO_NCC, DO_MLEN, 1, false, SpJobTable, DEEP, KNOWN>;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(kern), 256, 0) != hipSuccess || n < 1) {
             (void)hipGetLastError();
             n = (int)built_for;
@@ -2838,11 +2838,13 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
             // (the next 32 jobs: their own flagged-tile counters and job statistics)
             if (lo) PMX_HIP(hipMemsetAsync(d_nflagged, 0, 16 + EV_STAT_BYTES, ctx->stream));
             const bool deep = has_m && ctx->deep_lists;   // PMX_FLAG_DEEP_LISTS: the larger list pool at four workgroups per CU
+            // the caller's hint, or the density probe's: the instantiations without the job-wide verdict on dense chromosomes
+            const bool known = ctx->known_sparse;
             // workgroups per CU: what the instantiation was built for (5 / 4 / 8), or fewer if this device takes fewer (the
             // grid is one round of resident workgroups: a sixth that does not fit would run as a tail behind the others)
             u32 per_cu = has_m ? (deep ? 4 : EV_WAVES) : EV_WAVES_NCC;
             {
-#define EV_OCC(HM, NC, ML, DP) ev_resident_per_cu<HM, NC, ML, DP>(ctx, per_cu)
+#define EV_OCC(HM, NC, ML, DP) (known ? ev_resident_per_cu<HM, NC, ML, DP, true>(ctx, per_cu) : ev_resident_per_cu<HM, NC, ML, DP, false>(ctx, per_cu))
                 if (has_m && do_ncc && fuse_mlen) per_cu = deep ? EV_OCC(true, true, true, true) : EV_OCC(true, true, true, false);
                 else if (has_m && do_ncc) per_cu = deep ? EV_OCC(true, true, false, true) : EV_OCC(true, true, false, false);
                 else if (has_m && fuse_mlen) per_cu = deep ? EV_OCC(true, false, true, true) : EV_OCC(true, false, true, false);
@@ -2860,9 +2862,14 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
             rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_EVENTS, &tl);
             if (rc) return rc;
             const u32 nhr = (max_shift + 1 + 127) / 128;   // quads of R above a tile that hold partners of its forward reads
-#define EV_LAUNCH_(HM, NC, ML, DP)                                                                                     \
-    hipLaunchKernelGGL((k_cc_events<HM, NC, ML, 1, false, SpJobTable, DP>), dim3(nwg), dim3(256), 0, ctx->stream, tab, n, total, tpw, \
+#define EV_LAUNCH__(HM, NC, ML, DP, KS)                                                                                \
+    hipLaunchKernelGGL((k_cc_events<HM, NC, ML, 1, false, SpJobTable, DP, KS>), dim3(nwg), dim3(256), 0, ctx->stream, tab, n, total, tpw, \
                        (u32)c, max_shift, nhr, fused_lag, 1024u, (u32)EV_LO, (u32)EV_HI, ctx->d_slab, d_flags, d_flags_ac, d_nflagged, d_jobstat)
+#define EV_LAUNCH_(HM, NC, ML, DP)                \
+    do {                                          \
+        if (known) EV_LAUNCH__(HM, NC, ML, DP, true); \
+        else EV_LAUNCH__(HM, NC, ML, DP, false);  \
+    } while (0)
 #define EV_LAUNCH(HM, NC, ML)                \
     do {                                     \
         if (deep) EV_LAUNCH_(HM, NC, ML, HM); \
@@ -2875,6 +2882,7 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
             else EV_LAUNCH_(false, true, false, false);
 #undef EV_LAUNCH
 #undef EV_LAUNCH_
+#undef EV_LAUNCH__
             PMX_CHECK_LAUNCH("k_cc_events");
             rc = pmx_prof_end(ctx, &tl);
             if (rc) return rc;

@@ -73,6 +73,7 @@ int pmx_ctx_create(int device, void *hip_stream, pmx_ctx **out)
     ctx->profiling = 0;
     ctx->window_only = false;
     ctx->deep_lists = false;
+    ctx->known_sparse = false;
     ctx->debug_max_wg = 0;
     ctx->d_scratch = nullptr;
     ctx->scratch_words = 0;
@@ -1515,6 +1516,10 @@ static int cc_batch_impl(pmx_ctx *ctx, uint32_t njobs, const uint64_t *const *d_
         // PMX_AUTOCORR_FORK=0 in the environment keeps everything on the caller's stream (per-kernel profiling)
         ctx->window_only = (flags & PMX_FLAG_WINDOW_ONLY) != 0;
         ctx->deep_lists = (flags & PMX_FLAG_DEEP_LISTS) != 0;
+        // PMX_FLAG_EVENTS_HINT / PMX_FLAG_DEEP_LISTS from the caller, or the probe's own choice of either (it ran and did not
+        // choose the window kernels): the event kernel without its job-wide verdict.  PMX_FLAG_FORCE_SPARSE keeps the verdict.
+        ctx->known_sparse = !(flags & PMX_FLAG_FORCE_SPARSE) && !ctx->window_only &&
+                            ((flags & (PMX_FLAG_EVENTS_HINT | PMX_FLAG_DEEP_LISTS)) != 0 || probed);
         static const bool fork_enabled = [] {
             const char *e = getenv("PMX_AUTOCORR_FORK");
             return !(e && e[0] == '0');
