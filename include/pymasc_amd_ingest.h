@@ -370,6 +370,40 @@ int pmx_dbam_gcbias_begin(pmx_dbam *b, const pmx_dgc *genome, uint32_t window, c
 int pmx_dbam_gcbias_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t out[3]);
 int64_t pmx_dbam_gcbias_tables(pmx_dbam *b, uint64_t *windows, uint64_t *reads, int64_t cap, uint64_t totals[4]);
 
+/* Paired-end fragment sizes and the pair pileup (version >= 15).  A pair is counted at its read1 record, from that
+ * record's own fields (flag, next_refID / RNEXT, next_pos / PNEXT, tlen / TLEN): nothing is matched, nothing is held back between
+ * a stream's windows.
+ * The pair rule.  A record that passes mapq_min / flag_exclude with ref_id >= 0, a query length > 0 and a chosen reference counts
+ * in `reads`; with flag 0x1 also in `paired`, and then in exactly one of (the first that holds): mate_unmapped (flag 0x8);
+ * mate_elsewhere (BAM: next_refID != refID; SAM: RNEXT is neither '=' nor byte-equal to RNAME); no_size (tlen 0 or -2^31, or
+ * mate_pos1 = next_pos + 1 = PNEXT <= 0); else it is a fragment of size = |tlen|, start1 = min(pos1, mate_pos1) and orientation
+ * TANDEM (2) when bits 0x10 and 0x20 agree, FR (0) when the read is forward and tlen > 0 or reverse and tlen < 0, RF (1) otherwise.
+ * size > max_size: over[orientation], and no further.  Otherwise a row (ref_id, start1, size, orientation), counted in `rows`; an
+ * attached mask (pmx_dbam_set_exclude) drops the rows whose extent [start1, start1 + size - 1] overlaps a region: `masked`.
+ * H[o][s - 1] = the rows left of orientation o and size s.  paired = mate_unmapped + mate_elsewhere + no_size + sum(over) + rows;
+ * rows - masked = sum(H).
+ * pmx_dbam_fragments_begin allocates and zeroes H (8 * 3 * max_size bytes) and the counters, 1 <= max_size <= 65536; use_ref[nref]
+ * chooses references (NULL: all).  They stay until the next begin or close.  pmx_dbam_fragments_add counts what the handle holds
+ * now (the arrays of the last pmx_dbam_decode stay untouched); *rows_added = the rows it added to H.  pmx_dbam_fragments_tables
+ * copies H (3 * max_size, [o][s - 1]) and the counters since begin.
+ * pmx_dbam_fragments_rows: the rows of what the handle holds now, after the mask, in record order; cap 0 returns their number, a
+ * cap >= it fills the arrays and returns it.
+ * pmx_dbam_coverage_add_fragments: between pmx_dbam_coverage_begin(b, 0, use_ref) and _finish, marks the FR rows at their own
+ * extent (clipped to the reference as a read's is); *added = the rows marked.
+ * A SAM handle parses PNEXT and TLEN the first time one of these is called: a field that is not a decimal integer (TLEN may be
+ * signed) is PMX_DBAM_ERR_FORMAT, "line N: <reason>".  A BED read handle: PMX_DBAM_ERR_INVALID, "the input has no mate fields".
+ * add / tables before begin, max_size out of range, a NULL output: PMX_DBAM_ERR_INVALID. */
+#define PMX_FRAGMENTS_MAX_SIZE 65536u
+#define PMX_FRAGMENTS_COUNTERS 10   /* reads, paired, mate_unmapped, mate_elsewhere, no_size, over FR / RF / TANDEM, rows, masked */
+int pmx_dbam_fragments_begin(pmx_dbam *b, uint32_t max_size, const uint8_t *use_ref);
+int pmx_dbam_fragments_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t *rows_added);
+int pmx_dbam_fragments_tables(pmx_dbam *b, uint64_t *hist, uint64_t counters[PMX_FRAGMENTS_COUNTERS]);
+/* seconds = {the row filter of the adds since begin (wall clock: walk, scan, write, mask), k_fr_hist of them (HIP events)} */
+int pmx_dbam_fragments_timings(pmx_dbam *b, double seconds[2]);
+int64_t pmx_dbam_fragments_rows(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint32_t max_size, const uint8_t *use_ref,
+                                int64_t cap, int32_t *ref_id, int32_t *start1, int32_t *size, uint8_t *orient);
+int pmx_dbam_coverage_add_fragments(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint32_t max_size, uint64_t *added);
+
 #ifdef __cplusplus
 }
 #endif

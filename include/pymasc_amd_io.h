@@ -64,6 +64,11 @@ const char *pmx_bam_header_text(const pmx_bam *b, uint32_t *len);
  * arguments must not change between calls on one handle. */
 int64_t pmx_bam_next_batch(pmx_bam *b, uint32_t mapq_min, uint32_t flag_exclude, int64_t cap,
                            int32_t *ref_id, int32_t *pos1, int32_t *read_len, uint8_t *reverse);
+/* pmx_bam_next_batch with four raw columns more (version >= 8): flag[i] = the record's flag, mate_ref[i] =
+ * next_refID, mate_pos1[i] = next_pos + 1, tlen[i] = tlen.  The checker of the device pair counts: the pair rule itself is applied
+ * by the caller.  A pass over the file is made of calls of one of the two functions only. */
+int64_t pmx_bam_next_mates(pmx_bam *b, uint32_t mapq_min, uint32_t flag_exclude, int64_t cap, int32_t *ref_id, int32_t *pos1,
+                           int32_t *read_len, uint8_t *reverse, uint16_t *flag, int32_t *mate_ref, int32_t *mate_pos1, int32_t *tlen);
 
 /* .bai index (SAM spec 5.2): what the reference's multi-process mode requires (reader/bam.py:246-262) and uses
  * through pysam's fetch(chrom) (handler/worker.py:106-132).  After pmx_bam_fetch_ref, pmx_bam_next_batch yields
@@ -117,6 +122,12 @@ const char *pmx_sam_header_text(const pmx_sam *s, uint32_t *len);
  * pmx_sam_fetch copies records [first, first + n) of them.  May be called again with another filter. */
 int64_t pmx_sam_decode(pmx_sam *s, uint32_t mapq_min, uint32_t flag_exclude, int32_t want_ref);
 int pmx_sam_fetch(pmx_sam *s, int64_t first, int64_t n, int32_t *ref_id, int32_t *pos1, int32_t *read_len, uint8_t *reverse);
+/* Parallel to pmx_sam_fetch (version >= 8): flag, and the mate fields of records [first, first + n) of the last
+ * decode by the rules of io/sam_parse.h (parse_mates): mate_ref = the record's own id when RNEXT is '=' or its own name, the named
+ * reference's id otherwise, -1 for '*' or a name no @SQ line has; mate_pos1 = PNEXT; tlen = TLEN.  The fields are parsed on the
+ * first call after a decode: a PNEXT or TLEN that is not a decimal integer is PMX_IO_ERR_FORMAT, "line N: <reason>".  A handle of
+ * pmx_bed_open: PMX_IO_ERR_INVALID, "the input has no mate fields". */
+int pmx_sam_fetch_mates(pmx_sam *s, int64_t first, int64_t n, uint16_t *flag, int32_t *mate_ref, int32_t *mate_pos1, int32_t *tlen);
 /* alignment lines, records kept by the last decode, text bytes, file bytes, BGZF members (0 for plain SAM) */
 int pmx_sam_counters(const pmx_sam *s, uint64_t *records, uint64_t *kept, uint64_t *bytes_out, uint64_t *bytes_in,
                      uint64_t *members);

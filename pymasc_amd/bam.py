@@ -89,6 +89,25 @@ class BamReader(AlignmentReader):
                 return
             yield self._drop_excluded(ref[:n].copy(), pos[:n].copy(), rlen[:n].copy(), rev[:n].astype(bool))
 
+    def mate_batches(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, batch: int = 1 << 22):
+        """``batches`` with four raw columns more (``pmx_bam_next_mates``): yields (ref_id, pos_1based, read_len, is_reverse, flag,
+        mate_ref_id, mate_pos_1based, tlen) of the reads that pass the filter, in file order.  The reader's mask is not applied:
+        a pair is masked by its fragment's extent (``fragments.rows_host``)."""
+        self._check_open()
+        rc = self._L.pmx_bam_fetch_ref(self._h, -1)
+        if rc:
+            self._raise(rc)
+        cols = [np.empty(batch, dtype=t) for t in (np.int32, np.int32, np.int32, np.uint8, np.uint16, np.int32, np.int32, np.int32)]
+        while True:
+            n = self._L.pmx_bam_next_mates(self._h, int(mapq_criteria), int(flag_exclude), batch, *[c.ctypes.data for c in cols])
+            if n < 0:
+                self._raise(n)
+            if n == 0:
+                return
+            out = [c[:n].copy() for c in cols]
+            out[3] = out[3].astype(bool)
+            yield tuple(out)
+
 
 def feed_bam(calculator, reader: BamReader, mapq_criteria: int, references: Optional[Sequence[str]] = None,
              finish: bool = True, use_index: Optional[bool] = None) -> int:

@@ -73,6 +73,9 @@ class BedReadsReader(SamReader):
     def fetch(self, reference: str, *args, **kwargs):
         raise ValueError("fetch() needs an index: {} is a BED read file".format(self.path))
 
+    def mate_batches(self, *args, **kwargs):
+        raise ValueError("{}: the input has no mate fields".format(self.path))
+
 
 class DeviceBedReadsReader(DeviceBamReader):
     """A BED read file copied to HBM, parsed and put in (reference, start) order there; the surface of ``DeviceBamReader``.

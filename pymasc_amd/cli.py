@@ -52,8 +52,8 @@ class _Extend(_NaturalNumber):
 
 
 def _extend(text: str):
-    """``auto`` / ``read`` as they are, anything else as an int (argparse reports what is neither)."""
-    return text if text in ("auto", "read") else int(text)
+    """``auto`` / ``read`` / ``pair`` as they are, anything else as an int (argparse reports what is neither)."""
+    return text if text in ("auto", "read", "pair") else int(text)
 
 
 class _LogLevel(argparse.Action):
@@ -247,10 +247,11 @@ def get_parser() -> argparse.ArgumentParser:
                           "its 5' end to the estimated fragment length, piled up base by base on the GPU and written as runs of "
                           "constant depth (plain text; no binning, no scaling).  The GPU table takes 4 bytes per base of the chosen "
                           "chromosomes: 12.4 GB for hg38")
-    out.add_argument("--coverage-extend", metavar="N|auto|read", type=_extend, action=_Extend,
+    out.add_argument("--coverage-extend", metavar="N|auto|read|pair", type=_extend, action=_Extend,
                      help="extend every read to N bases from its 5' end; auto (the default): to the run's own fragment-length "
                           "estimate, on one more read of the file, so not for '-' or a pipe; read: no extension, the read's own "
-                          "length; implies --coverage")
+                          "length; pair: instead of reads, every properly oriented (FR) pair at its own extent, from read1's mate "
+                          "fields, up to --fragments-max bases; implies --coverage")
     out.add_argument("--gc-bias", metavar="FASTA", type=Path,
                      help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
                           "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
@@ -258,6 +259,13 @@ def get_parser() -> argparse.ArgumentParser:
                           "--exclude-regions are left out")
     out.add_argument("--gc-window", metavar="N", type=int, action=_NaturalNumber,
                      help="length of the genome windows, 1 to 1024 bases (default 100); needs --gc-bias")
+    out.add_argument("--fragments", action="store_true",
+                     help="also write <name>_fragments.tab for every paired-end file: the fragment sizes of the pairs among the reads "
+                          "the correlation sees, each counted at its read1 record from that record's mate fields, with median, "
+                          "spread and the histogram per orientation (FR, RF, TANDEM); not for BED / tagAlign input")
+    out.add_argument("--fragments-max", metavar="N", type=int, action=_NaturalNumber,
+                     help="largest fragment size counted, 1 to 65536 bases (default 2000); larger pairs are only counted as over; "
+                          "implies --fragments")
     return parser
 
 
@@ -313,6 +321,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         if streams:
             parser.error("argument --coverage-extend: auto reads the file once more, which {} cannot be: give a number or 'read'"
                          "".format(", ".join(streams)))
+    if args.fragments_max is not None:
+        if args.fragments_max > 65536:
+            parser.error("argument --fragments-max: max_size is {}: it must lie in [1, 65536]".format(args.fragments_max))
+        args.fragments = True
     if args.gc_window is not None and args.gc_bias is None:
         parser.error("argument --gc-window: needs a genome (--gc-bias)")
     if args.gc_window is not None and args.gc_window > 1024:
@@ -415,6 +427,10 @@ def _run(args, device, rank: int) -> int:
         extra["coverage"] = True
         if args.coverage_extend not in (None, "auto"):
             extra["coverage_extend"] = 0 if args.coverage_extend == "read" else args.coverage_extend
+    if args.fragments:
+        extra["fragments"] = True
+    if args.fragments_max is not None:          # (it also bounds a pair pileup)
+        extra["fragments_max"] = args.fragments_max
     if args.gc_bias is not None:
         extra["gc_bias"] = str(args.gc_bias)
         if args.gc_window is not None:

@@ -8,6 +8,9 @@ They are this project's own: nothing here was compared with ``bedtools genomecov
 * The extent is the fingerprint's (7.16) with ``extend``: ``L = extend``, or the read's own length at 0; a forward read covers
   ``[pos1, pos1 + L - 1]``, a reverse read ``[pos1 + read_len - L, pos1 + read_len - 1]``; both clipped to ``[1, len]`` of the
   reference.  A read with nothing left after the clip adds nothing and is not in ``reads``.
+* With ``extend = "pair"`` (``PAIR``) the reads are replaced by the FR rows of ``pymasc_amd.fragments`` (pairs
+  counted at read1, ``size <= max_size``, masked by the fragment's extent): a row covers ``[start1, start1 + size - 1]``, clipped
+  the same way, and ``reads`` is the number of rows piled.
 * ``depth[r][p]`` is the number of kept reads whose clipped extent holds position ``p`` of reference ``r``, a 32-bit count.
 * Per chosen reference, in header order, the maximal intervals of constant depth greater than 0 are the runs
   ``(start0, end0, depth)``, 0-based and half-open as in bedGraph.  Two reads that abut at equal depth form one run; depth 0 is not
@@ -38,16 +41,26 @@ TILE = 4096                 # slots per scan tile of the device code (PMX_COVERA
 TEXT_CHUNK = 1 << 18        # runs per call of pmx_dbam_coverage_text when a file is written
 MAX_READS = 1 << 31
 TOTALS = ("reads", "runs", "covered_bases", "fragment_bases", "max_depth")
-_TRACK = re.compile(r'^track type=bedGraph name="(.*)" description="pymasc_amd fragment pileup extend=(\d+|read) reads=(\d+)"$')
+PAIR = "pair"               # ``extend``: the FR pairs at their own extent
+_TRACK = re.compile(r'^track type=bedGraph name="(.*)" description="pymasc_amd fragment pileup extend=(\d+|read|pair) reads=(\d+)"$')
+
+
+def check_extend(extend):
+    """``extend`` as the pileup takes it: ``"pair"`` or an integer of at least 0."""
+    if extend == PAIR:
+        return PAIR
+    if isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0:
+        raise ValueError("extend is \"pair\" or an integer that is not negative")
+    return int(extend)
 
 
 class Coverage:
     """``runs``: ``{name: (start0, end0, depth)}``, uint32, of the chosen references that have a run, in header order;
-    ``reads``: the reads that added; ``extend`` (0: every read's own length)."""
+    ``reads``: the reads that added; ``extend`` (0: every read's own length; ``"pair"``: the FR pairs at their own extent)."""
 
     def __init__(self, runs, reads: int, extend: int):
         self.runs = {str(k): tuple(np.asarray(x, dtype=np.uint32).ravel() for x in v) for k, v in runs.items()}
-        self.reads, self.extend = int(reads), int(extend)
+        self.reads, self.extend = int(reads), check_extend(extend)
         if any(len(v) != 3 or not (v[0].size == v[1].size == v[2].size > 0) for v in self.runs.values()):
             raise ValueError("every reference has as many starts as ends and depths, and at least one run")
 
@@ -91,9 +104,10 @@ class HostCount:
     slot per base and a closing one); ``add`` marks a batch of reads given as four columns with ``np.add.at``, ``result`` takes the running sum and
     cuts it into runs where a slot is not 0."""
 
-    def __init__(self, names, lengths, use, extend: int = 0):
-        if int(extend) < 0:
-            raise ValueError("extend is not negative")
+    def __init__(self, names, lengths, use, extend=0):
+        """``extend`` ``"pair"``: ``add`` is given the FR rows of ``fragments.rows_host`` as forward reads of ``size`` bases."""
+        self.label = check_extend(extend)
+        extend = 0 if self.label == PAIR else self.label
         self.names, self.lengths = tuple(names), tuple(max(int(x), 0) for x in lengths)
         self.use = np.asarray(use, dtype=bool)
         if not self.use.any():
@@ -135,7 +149,7 @@ class HostCount:
                 depth = np.cumsum(steps[at], dtype=np.int64)
                 keep = depth[:-1] > 0
                 runs[self.names[r]] = (at[:-1][keep], at[1:][keep], depth[:-1][keep])
-        return Coverage(runs, self.reads, self.extend)
+        return Coverage(runs, self.reads, self.label)
 
 
 def count_host(ref_id, pos1, read_len, reverse, names, lengths, use, extend: int = 0) -> Coverage:
@@ -150,11 +164,10 @@ class DeviceCount(SideAccumulator):
     holds now (a stream reader calls it for every window), ``finish`` turns the table into runs, ``runs`` / ``text`` read them
     back, ``result`` is all of it as a ``Coverage``."""
 
-    def __init__(self, reader, mapq_criteria: int, references=None, extend: int = 0):
+    def __init__(self, reader, mapq_criteria: int, references=None, extend=0, max_size: int = 2000):
+        """``extend`` ``"pair"``: ``add`` marks the FR rows of at most ``max_size`` bases (``pmx_dbam_coverage_add_fragments``)."""
         reader._check_open()
-        if int(extend) < 0:
-            raise ValueError("extend is not negative")
-        self.mapq_criteria, self.extend = int(mapq_criteria), int(extend)
+        self.mapq_criteria, self.extend, self.max_size = int(mapq_criteria), check_extend(extend), int(max_size)
         self.names = tuple(reader.references)
         self.use = _selected_mask(reader, references)
         self.totals = None
@@ -164,13 +177,17 @@ class DeviceCount(SideAccumulator):
         """A zeroed table on the reader's handle (a stream reader calls it again when a pass opens a new handle)."""
         mask = np.ascontiguousarray(self.use, dtype=np.uint8) if self.names else np.zeros(1, dtype=np.uint8)
         self.totals = None
-        rc = reader._L.pmx_dbam_coverage_begin(reader._h, self.extend, mask.ctypes.data)
+        rc = reader._L.pmx_dbam_coverage_begin(reader._h, 0 if self.extend == PAIR else self.extend, mask.ctypes.data)
         if rc:
             reader._raise(rc)
 
     def add(self, reader) -> int:
         added = ctypes.c_uint64()
-        rc = reader._L.pmx_dbam_coverage_add(reader._h, self.mapq_criteria, PMX_BAM_DEFAULT_EXCLUDE, ctypes.byref(added))
+        if self.extend == PAIR:
+            rc = reader._L.pmx_dbam_coverage_add_fragments(reader._h, self.mapq_criteria, PMX_BAM_DEFAULT_EXCLUDE, self.max_size,
+                                                           ctypes.byref(added))
+        else:
+            rc = reader._L.pmx_dbam_coverage_add(reader._h, self.mapq_criteria, PMX_BAM_DEFAULT_EXCLUDE, ctypes.byref(added))
         if rc:
             reader._raise(rc)
         return int(added.value)
@@ -225,40 +242,49 @@ class DeviceCount(SideAccumulator):
         return c
 
 
-def count_device(reader, mapq_criteria: int, references=None, extend: int = 0) -> Coverage:
+def count_device(reader, mapq_criteria: int, references=None, extend=0, max_size: int = 2000) -> Coverage:
     """``begin`` + ``add`` + ``finish`` + ``runs`` on a device reader's handle (what it holds now)."""
-    acc = DeviceCount(reader, mapq_criteria, references, extend)
+    acc = DeviceCount(reader, mapq_criteria, references, extend, max_size)
     acc.add(reader)
     return acc.result(reader)
 
 
-def device_count_of(reader, mapq_criteria: int = 0, references=None, extend: int = 0) -> DeviceCount:
+def device_count_of(reader, mapq_criteria: int = 0, references=None, extend=0, max_size: int = 2000) -> DeviceCount:
     """The finished ``DeviceCount`` of everything a device reader reads: one ``add`` for a whole-file reader, every window of a
     stream reader (read once more when it is a regular file, ``InputUnseekable`` otherwise)."""
-    acc = count_over(reader, "coverage", lambda: DeviceCount(reader, mapq_criteria, references, extend))
+    acc = count_over(reader, "coverage", lambda: DeviceCount(reader, mapq_criteria, references, extend, max_size))
     acc.finish(reader)
     return acc
 
 
-def from_reader(reader, mapq_criteria: int = 0, references=None, extend: int = 0) -> Coverage:
+def from_reader(reader, mapq_criteria: int = 0, references=None, extend=0, max_size: int = 2000) -> Coverage:
     """The pileup of the reads of ``reader`` at ``mapq_criteria`` over ``references`` (names; None: every reference the reader has
-    selected).  A device reader counts on the GPU (``device_count_of``); a host reader through ``batches`` and ``HostCount``."""
+    selected).  A device reader counts on the GPU (``device_count_of``); a host reader through ``batches`` and ``HostCount``.
+    ``extend`` ``"pair"``: the FR pairs of at most ``max_size`` bases at their own extent; a host reader through
+    ``fragments.rows_host``."""
     from .bam_device import DeviceBamReader
     if isinstance(reader, DeviceBamReader):
-        return device_count_of(reader, mapq_criteria, references, extend).result(reader)
+        return device_count_of(reader, mapq_criteria, references, extend, max_size).result(reader)
     acc = HostCount(reader.references, reader.lengths, _selected_mask(reader, references), extend)
+    if acc.label == PAIR:
+        from .fragments import FR, rows_host
+        for ref, start1, size, orient, _c in rows_host(reader, mapq_criteria, references, max_size):
+            fr = orient == FR
+            if fr.any():
+                acc.add(ref[fr], start1[fr], size[fr], np.zeros(int(fr.sum()), dtype=bool))
+        return acc.result()
     for batch in reader.batches(mapq_criteria, PMX_BAM_DEFAULT_EXCLUDE):
         if len(batch[0]):
             acc.add(*batch)
     return acc.result()
 
 
-def track_line(name: str, extend: int, reads: int) -> bytes:
+def track_line(name: str, extend, reads: int) -> bytes:
     return 'track type=bedGraph name="{}" description="pymasc_amd fragment pileup extend={} reads={}"\n'.format(
-        name, int(extend) if int(extend) else "read", int(reads)).encode()
+        name, PAIR if extend == PAIR else int(extend) if int(extend) else "read", int(reads)).encode()
 
 
-def write_track(path_base, name: str, extend: int, reads: int, chunks) -> Path:
+def write_track(path_base, name: str, extend, reads: int, chunks) -> Path:
     """Writes ``<path_base>_coverage.bedGraph`` (to a temporary file beside it, renamed into place) and returns its path: the
     track line, then the bytes of ``chunks`` (the lines of the runs)."""
     path = Path(str(path_base) + COVERAGE_SUFFIX)
@@ -294,4 +320,5 @@ def read_coverage(path) -> Tuple[str, Coverage]:
             chrom, s, e, d = ln.rstrip("\n").split("\t")
             cols.setdefault(chrom, []).append((int(s), int(e), int(d)))
     runs = {k: tuple(zip(*v)) for k, v in cols.items()}
-    return head.group(1), Coverage(runs, int(head.group(3)), 0 if head.group(2) == "read" else int(head.group(2)))
+    extend = head.group(2)
+    return head.group(1), Coverage(runs, int(head.group(3)), 0 if extend == "read" else PAIR if extend == PAIR else int(extend))

@@ -1266,6 +1266,16 @@ struct pmx_dbam {
     u64 gc_words = 0;                // words of each bit vector
     std::vector<u64> gc_n;           // N[0 .. window], computed by begin
     u64 gc_tot[3] = {0, 0, 0};       // reads placed, off_end, blocked since begin
+    // fragment sizes (pmx_dbam_fragments_*, fragments_device.inc): from begin to the next begin or close
+    unsigned long long *d_fr = nullptr;   // H[3][fr_max]
+    u8 *d_fr_use = nullptr;          // per reference: chosen (null: every reference)
+    u32 fr_max = 0;                  // max_size (0: no table)
+    u64 fr_c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // the counters since begin
+    double fr_t[2] = {0, 0};         // seconds since begin: the row filter (wall clock), k_fr_hist (HIP events)
+    // the mate fields of the SAM line table (k_sam_mates): built by the first pair call, freed with the table
+    int *d_smpos = nullptr, *d_stlen = nullptr;
+    u8 *d_ssame = nullptr;
+    u64 sam_line0 = 0;               // lines of the text in front of the table's first (the "line N" of an error)
 };
 
 namespace {
@@ -1814,7 +1824,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 14; }
+int pmx_dbam_version(void) { return 15; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -1894,6 +1904,8 @@ void pmx_dbam_close(pmx_dbam *b)
     for (void *p : {(void *)b->d_cv, (void *)b->d_cv_tab, (void *)b->d_cv_seg, (void *)b->d_cv_names, (void *)b->d_cv_runs})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)b->d_nl, (void *)b->d_ls, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)b->d_fr, (void *)b->d_fr_use, (void *)b->d_smpos, (void *)b->d_stlen, (void *)b->d_ssame})
         if (p) (void)hipFree(p);
     for (hipStream_t x : b->kmore)
         if (x) (void)hipStreamDestroy(x);
@@ -2611,3 +2623,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "peakcount_device.inc"
 #include "coverage_device.inc"
 #include "gcbias_device.inc"
+#include "fragments_device.inc"

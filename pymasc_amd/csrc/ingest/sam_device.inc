@@ -281,6 +281,7 @@ int sam_index_parse(pmx_dbam &b, const samtext::Header &h)
     }
     if (len == 0) n--;
     b.sam_lines = n;
+    b.sam_line0 = h.lines;
     double t1 = now_s();
     b.t[4] = t1 - t0;
     if (n == 0) return 0;

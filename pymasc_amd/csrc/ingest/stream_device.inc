@@ -101,6 +101,7 @@ u64 stream_held(const pmx_dbam &b)
     h += b.pk_lines * 28;
     h += b.cv_held;
     h += b.gc_words * 16;
+    h += 24ull * b.fr_max + (b.d_smpos ? b.sam_lines * 9 : 0);
     return h;
 }
 void stream_note(pmx_dbam &b) { b.st->peak = std::max(b.st->peak, stream_held(b)); }
@@ -177,8 +178,11 @@ int stream_carry_sam(pmx_dbam &b, u64 full, u64 &carry)
 
 void sam_free_table(pmx_dbam &b)
 {
-    for (void *p : {(void *)b.d_nl, (void *)b.d_sref, (void *)b.d_spos, (void *)b.d_sqlen, (void *)b.d_sfm})
+    for (void *p : {(void *)b.d_nl, (void *)b.d_sref, (void *)b.d_spos, (void *)b.d_sqlen, (void *)b.d_sfm, (void *)b.d_smpos,
+                    (void *)b.d_stlen, (void *)b.d_ssame})
         if (p) (void)hipFree(p);
+    b.d_smpos = b.d_stlen = nullptr;
+    b.d_ssame = nullptr;
     b.d_nl = nullptr;
     b.d_sref = b.d_spos = nullptr;
     b.d_sqlen = b.d_sfm = nullptr;

@@ -73,6 +73,8 @@ struct RawBuf {
 struct Window {
     std::vector<int32_t> ref, pos, len;
     std::vector<uint8_t> rev;
+    std::vector<uint16_t> flag;                  // (pmx_bam_next_mates only: the raw flag and the three mate fields)
+    std::vector<int32_t> mref, mpos, tlen;
 };
 
 inline uint16_t le16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
@@ -111,6 +113,7 @@ struct pmx_bam {
 
     bool filter_set = false;
     uint32_t mapq_min = 0, flag_exclude = 0;
+    bool mates = false;             // the pass was begun by pmx_bam_next_mates: the windows carry the mate columns
 
     // .bai index: per reference the virtual file offsets [beg, end) of its records (SAM spec 5.2)
     using RefRange = pmx_bai::RefRange;
@@ -290,10 +293,7 @@ bool long_cigar(const uint8_t *rec, uint32_t rec_len, uint32_t l_name, uint32_t 
     return false;
 }
 
-struct Decoded {
-    std::vector<int32_t> ref, pos, len;
-    std::vector<uint8_t> rev;
-};
+using Decoded = Window;
 
 void decode_range(const pmx_bam &b, size_t lo, size_t hi, Decoded &out)
 {
@@ -321,6 +321,12 @@ void decode_range(const pmx_bam &b, size_t lo, size_t hi, Decoded &out)
         out.pos.push_back(pos + 1);
         out.len.push_back((int32_t)q);
         out.rev.push_back((flag & PMX_BAM_FLAG_REVERSE) ? 1 : 0);
+        if (b.mates) {                                        // bytes 20-31 of the record: next_refID, next_pos, tlen
+            out.flag.push_back((uint16_t)flag);
+            out.mref.push_back(le32s(rec + 20));
+            out.mpos.push_back((int32_t)(le32(rec + 24) + 1u));
+            out.tlen.push_back(le32s(rec + 28));
+        }
     }
 }
 
@@ -355,6 +361,12 @@ void decode_window(pmx_bam &b, Window &w)
     w.pos.resize(kept);
     w.len.resize(kept);
     w.rev.resize(kept);
+    if (b.mates) {
+        w.flag.resize(kept);
+        w.mref.resize(kept);
+        w.mpos.resize(kept);
+        w.tlen.resize(kept);
+    }
     size_t o = 0;
     for (auto &d : parts) {
         const size_t k = d.ref.size();
@@ -363,6 +375,12 @@ void decode_window(pmx_bam &b, Window &w)
         memcpy(w.pos.data() + o, d.pos.data(), k * 4);
         memcpy(w.len.data() + o, d.len.data(), k * 4);
         memcpy(w.rev.data() + o, d.rev.data(), k);
+        if (b.mates) {
+            memcpy(w.flag.data() + o, d.flag.data(), k * 2);
+            memcpy(w.mref.data() + o, d.mref.data(), k * 4);
+            memcpy(w.mpos.data() + o, d.mpos.data(), k * 4);
+            memcpy(w.tlen.data() + o, d.tlen.data(), k * 4);
+        }
         o += k;
     }
     b.n_records += nrec;
@@ -675,16 +693,16 @@ const char *pmx_bam_header_text(const pmx_bam *b, uint32_t *len)
     return b->text.c_str();
 }
 
-int64_t pmx_bam_next_batch(pmx_bam *b, uint32_t mapq_min, uint32_t flag_exclude, int64_t cap,
-                           int32_t *ref_id, int32_t *pos1, int32_t *read_len, uint8_t *reverse)
+// pmx_bam_next_batch, and with `mates` pmx_bam_next_mates: the pass is one or the other from its first call on
+static int64_t next_batch(pmx_bam *b, bool mates, uint32_t mapq_min, uint32_t flag_exclude, int64_t cap, int32_t *ref_id, int32_t *pos1,
+                          int32_t *read_len, uint8_t *reverse, uint16_t *flag, int32_t *mate_ref, int32_t *mate_pos1, int32_t *tlen)
 {
-    if (!b || cap <= 0 || !ref_id || !pos1 || !read_len || !reverse)
-        return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bam_next_batch: NULL argument or cap <= 0");
     if (!b->filter_set) {
         b->mapq_min = mapq_min;
         b->flag_exclude = flag_exclude;
+        b->mates = mates;
         b->filter_set = true;
-    } else if (b->mapq_min != mapq_min || b->flag_exclude != flag_exclude) {
+    } else if (b->mapq_min != mapq_min || b->flag_exclude != flag_exclude || b->mates != mates) {
         return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bam_next_batch: the filter must not change between calls");
     }
     b->pristine = false;
@@ -707,8 +725,30 @@ int64_t pmx_bam_next_batch(pmx_bam *b, uint32_t mapq_min, uint32_t flag_exclude,
     memcpy(pos1, b->cur.pos.data() + c, n * 4);
     memcpy(read_len, b->cur.len.data() + c, n * 4);
     memcpy(reverse, b->cur.rev.data() + c, n);
+    if (mates) {
+        memcpy(flag, b->cur.flag.data() + c, n * 2);
+        memcpy(mate_ref, b->cur.mref.data() + c, n * 4);
+        memcpy(mate_pos1, b->cur.mpos.data() + c, n * 4);
+        memcpy(tlen, b->cur.tlen.data() + c, n * 4);
+    }
     b->w_cursor += n;
     return (int64_t)n;
+}
+
+int64_t pmx_bam_next_batch(pmx_bam *b, uint32_t mapq_min, uint32_t flag_exclude, int64_t cap,
+                           int32_t *ref_id, int32_t *pos1, int32_t *read_len, uint8_t *reverse)
+{
+    if (!b || cap <= 0 || !ref_id || !pos1 || !read_len || !reverse)
+        return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bam_next_batch: NULL argument or cap <= 0");
+    return next_batch(b, false, mapq_min, flag_exclude, cap, ref_id, pos1, read_len, reverse, nullptr, nullptr, nullptr, nullptr);
+}
+
+int64_t pmx_bam_next_mates(pmx_bam *b, uint32_t mapq_min, uint32_t flag_exclude, int64_t cap, int32_t *ref_id, int32_t *pos1,
+                           int32_t *read_len, uint8_t *reverse, uint16_t *flag, int32_t *mate_ref, int32_t *mate_pos1, int32_t *tlen)
+{
+    if (!b || cap <= 0 || !ref_id || !pos1 || !read_len || !reverse || !flag || !mate_ref || !mate_pos1 || !tlen)
+        return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bam_next_mates: NULL argument or cap <= 0");
+    return next_batch(b, true, mapq_min, flag_exclude, cap, ref_id, pos1, read_len, reverse, flag, mate_ref, mate_pos1, tlen);
 }
 
 int pmx_bam_index_load(pmx_bam *b, const char *bai_path)

@@ -64,5 +64,5 @@ void MappedFile::close()
 
 extern "C" {
 const char *pmx_io_last_error(void) { return pmx_io::g_last_error.c_str(); }
-int pmx_io_version(void) { return 7; }
+int pmx_io_version(void) { return 8; }
 }

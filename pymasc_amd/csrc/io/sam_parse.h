@@ -28,6 +28,8 @@ enum {
     SAM_ERR_CIGAR = 6,
     SAM_ERR_EMPTY = 7,       // an empty line before the end of the file
     SAM_ERR_LATE_HEADER = 8, // an '@' line after the first record
+    SAM_ERR_PNEXT = 9,       // (parse_mates)
+    SAM_ERR_TLEN = 10,       // (parse_mates)
     SAM_NERR
 };
 
@@ -42,6 +44,8 @@ inline const char *err_text(uint32_t code)
     case SAM_ERR_CIGAR: return "CIGAR is neither '*' nor (<length < 2^28><op in MIDNSHP=X>)+";
     case SAM_ERR_EMPTY: return "empty line";
     case SAM_ERR_LATE_HEADER: return "header line after the first alignment record";
+    case SAM_ERR_PNEXT: return "PNEXT is not a decimal in 0..2147483647";
+    case SAM_ERR_TLEN: return "TLEN is not a decimal in -2147483648..2147483647";
     }
     return "malformed alignment line";
 }
@@ -164,6 +168,61 @@ PMX_SAM_HD uint32_t parse_line(Src &s, uint64_t beg, uint64_t end, const Names &
         if (p == end) return SAM_ERR_FIELDS;
         p++;
     }
+    return SAM_OK;
+}
+
+// The mate fields of a line that parse_line accepted (fields 7-9: RNEXT, PNEXT, TLEN), read only by the pair counts
+// (DESIGN.md 7.21).  same: RNEXT is '=' or byte-equal to RNAME; [rnext, rnext + rnext_len) is RNEXT in the text.
+struct Mates {
+    int32_t mate_pos1;  // PNEXT (1-based; 0 when unavailable)
+    int32_t tlen;       // TLEN, signed
+    uint32_t same;
+    uint64_t rnext, rnext_len;
+};
+
+template <class Src>
+PMX_SAM_HD uint32_t parse_mates(Src &s, uint64_t beg, uint64_t end, Mates &m)
+{
+    if (end > beg && s.at(end - 1) == '\r') end--;
+    uint64_t p = beg, f[9];                                   // f[k]: the start of field k + 1; f[k + 1] - 1 its end
+    f[0] = beg;
+    for (int k = 1; k < 9; k++) {                             // (>= 11 fields: parse_line has seen them)
+        while (p < end && s.at(p) != '\t') p++;
+        if (p == end) return SAM_ERR_FIELDS;
+        f[k] = ++p;
+    }
+    uint64_t e9 = f[8];
+    while (e9 < end && s.at(e9) != '\t') e9++;
+    const uint64_t a2 = f[2], n2 = f[3] - 1 - a2, a6 = f[6], n6 = f[7] - 1 - a6;
+    m.rnext = a6;
+    m.rnext_len = n6;
+    m.same = n6 == 1 && s.at(a6) == '=';
+    if (!m.same && n6 == n2 && !(n6 == 1 && s.at(a6) == '*')) {
+        uint64_t i = 0;
+        while (i < n6 && s.at(a2 + i) == s.at(a6 + i)) i++;
+        m.same = i == n6;
+    }
+    // a decimal in [a, e): at most `lim`
+    auto dec = [&](uint64_t a, uint64_t e, uint64_t lim, uint64_t &v) -> bool {
+        if (a == e) return false;
+        uint64_t x = 0;
+        for (uint64_t i = a; i < e; i++) {
+            const uint8_t c = s.at(i);
+            if (c < '0' || c > '9') return false;
+            x = x * 10u + (uint32_t)(c - '0');
+            if (x > lim) return false;
+        }
+        v = x;
+        return true;
+    };
+    uint64_t v = 0;
+    if (!dec(f[7], f[8] - 1, 2147483647u, v)) return SAM_ERR_PNEXT;
+    m.mate_pos1 = (int32_t)v;
+    uint64_t a = f[8];
+    const bool neg = a < e9 && s.at(a) == '-';
+    if (neg || (a < e9 && s.at(a) == '+')) a++;
+    if (!dec(a, e9, neg ? 2147483648u : 2147483647u, v)) return SAM_ERR_TLEN;
+    m.tlen = neg ? (int32_t)(0u - (uint32_t)v) : (int32_t)v;
     return SAM_OK;
 }
 

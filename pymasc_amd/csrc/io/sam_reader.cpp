@@ -35,6 +35,12 @@ struct pmx_sam {
     std::vector<int32_t> o_ref, o_pos, o_len;
     std::vector<uint8_t> o_rev;
     uint64_t n_kept = 0;
+    // pmx_sam_fetch_mates: the last decode's filter, and the mate columns of its kept records, parsed when first asked for
+    uint32_t d_mapq = 0, d_flags = 0;
+    int32_t d_want = -1;
+    bool bed = false, mates_valid = false;
+    std::vector<uint16_t> m_flag;
+    std::vector<int32_t> m_ref, m_pos, m_tlen;
     struct LenBin {
         int32_t len;
         uint64_t count, first;
@@ -216,6 +222,7 @@ int pmx_bed_open(const char *path, int nthreads, int32_t nref, const char *const
     if (!path || !out) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_bed_open: NULL argument");
     *out = nullptr;
     pmx_sam *s = new pmx_sam();
+    s->bed = true;
     try {
         const std::string why = bedreads::check_sizes(nref, names, lengths, s->h.names, s->h.lens);
         if (!why.empty()) throw pmx_io::Error(PMX_IO_ERR_INVALID, why);
@@ -382,6 +389,10 @@ int64_t pmx_sam_decode(pmx_sam *s, uint32_t mapq_min, uint32_t flag_exclude, int
                 }
         });
         s->n_kept = kept;
+        s->d_mapq = mapq_min;
+        s->d_flags = flag_exclude;
+        s->d_want = want_ref;
+        s->mates_valid = false;
     } catch (const pmx_io::Error &e) {
         return pmx_io::fail(e.code, e.msg);
     } catch (const std::exception &e) {
@@ -398,6 +409,57 @@ int pmx_sam_fetch(pmx_sam *s, int64_t first, int64_t n, int32_t *ref_id, int32_t
     if (pos1) memcpy(pos1, s->o_pos.data() + first, 4 * (size_t)n);
     if (read_len) memcpy(read_len, s->o_len.data() + first, 4 * (size_t)n);
     if (reverse) memcpy(reverse, s->o_rev.data() + first, (size_t)n);
+    return PMX_IO_OK;
+}
+
+// the mate columns of the kept records of the last decode: fields 7-9 by samtext::parse_mates, RNEXT through the @SQ names
+static void parse_kept_mates(pmx_sam &s)
+{
+    const uint64_t kept = s.n_kept;
+    s.m_flag.resize(kept);
+    s.m_ref.resize(kept);
+    s.m_pos.resize(kept);
+    s.m_tlen.resize(kept);
+    std::unordered_map<std::string, int32_t> ids;
+    for (size_t r = 0; r < s.h.names.size(); r++) ids.emplace(s.h.names[r], (int32_t)r);
+    HostSrc src{s.t};
+    uint64_t o = 0;
+    for (size_t i = 0; i < s.nrec; i++) {
+        if (!keep(s, i, s.d_mapq, s.d_flags, s.d_want)) continue;
+        samtext::Mates m;
+        const uint32_t e = samtext::parse_mates(src, s.line_start(i), s.nl[i], m);
+        if (e) throw pmx_io::Error(PMX_IO_ERR_FORMAT, samtext::line_error(s.h, i, e));
+        int32_t mr = s.ref[i];
+        if (!m.same) {
+            const auto it = ids.find(std::string((const char *)s.t + m.rnext, (size_t)m.rnext_len));
+            mr = it == ids.end() ? -1 : it->second;
+        }
+        s.m_flag[o] = (uint16_t)(s.fm[i] & 0xffffu);
+        s.m_ref[o] = mr;
+        s.m_pos[o] = m.mate_pos1;
+        s.m_tlen[o] = m.tlen;
+        o++;
+    }
+    s.mates_valid = true;
+}
+
+int pmx_sam_fetch_mates(pmx_sam *s, int64_t first, int64_t n, uint16_t *flag, int32_t *mate_ref, int32_t *mate_pos1, int32_t *tlen)
+{
+    if (!s) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_fetch_mates: NULL handle");
+    if (s->bed) return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_fetch_mates: the input has no mate fields");
+    if (first < 0 || n < 0 || (uint64_t)(first + n) > s->n_kept)
+        return pmx_io::fail(PMX_IO_ERR_INVALID, "pmx_sam_fetch_mates: range outside the kept records");
+    try {
+        if (!s->mates_valid) parse_kept_mates(*s);
+    } catch (const pmx_io::Error &e) {
+        return pmx_io::fail(e.code, e.msg);
+    } catch (const std::exception &e) {
+        return pmx_io::fail(PMX_IO_ERR_OPEN, std::string("pmx_sam_fetch_mates: ") + e.what());
+    }
+    if (flag) memcpy(flag, s->m_flag.data() + first, 2 * (size_t)n);
+    if (mate_ref) memcpy(mate_ref, s->m_ref.data() + first, 4 * (size_t)n);
+    if (mate_pos1) memcpy(mate_pos1, s->m_pos.data() + first, 4 * (size_t)n);
+    if (tlen) memcpy(tlen, s->m_tlen.data() + first, 4 * (size_t)n);
     return PMX_IO_OK;
 }
 

@@ -22,6 +22,8 @@ PMX_BAM_FLAG_DUPLICATE = 0x400
 PMX_BAM_DEFAULT_EXCLUDE = PMX_BAM_FLAG_READ2 | PMX_BAM_FLAG_UNMAPPED | PMX_BAM_FLAG_DUPLICATE
 PMX_COMPLEXITY_BINS = 32        # (include/pymasc_amd_ingest.h)
 PMX_BINCOUNT_HIST = 4096
+PMX_FRAGMENTS_MAX_SIZE = 65536
+PMX_FRAGMENTS_COUNTERS = 10
 PMX_IO_ERR_NOTFOUND = -4        # (PMX_DBAM_ERR_NOTFOUND has the same value)
 TRACK_KINDS = ("bigwig", "bigbed", "kmer")      # pmx_track_kind / pmx_dbw_kind
 
@@ -84,6 +86,7 @@ IO_PROTOTYPES = {
     "pmx_bam_open": (_int, [_str, _int, _out]),
     **_alignment_protos("pmx_bam"),
     "pmx_bam_next_batch": (_i64, [_vp, _u32, _u32, _i64, _vp, _vp, _vp, _vp]),
+    "pmx_bam_next_mates": (_i64, [_vp, _u32, _u32, _i64] + [_vp] * 8),
     "pmx_bam_counters": (_int, [_vp] + [_pu64] * 4),
     "pmx_bam_index_load": (_int, [_vp, _str]),
     "pmx_bam_has_index": (_int, [_vp]),
@@ -93,6 +96,7 @@ IO_PROTOTYPES = {
     "pmx_bed_open": (_int, [_str, _int] + _sizes + [_out]),
     **_alignment_protos("pmx_sam"),
     **_decode_protos("pmx_sam"),
+    "pmx_sam_fetch_mates": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pmx_sam_counters": (_int, [_vp] + [_pu64] * 5),
     "pmx_bigwig_open": (_int, [_str, _out]),
     "pmx_ttrack_open": (_int, [_str, _int, _out]),
@@ -134,6 +138,12 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_gcbias_begin": (_int, [_vp, _vp, _u32, _vp]),
     "pmx_dbam_gcbias_add": (_int, [_vp, _u32, _u32, _vp]),
     "pmx_dbam_gcbias_tables": (_i64, [_vp, _vp, _vp, _i64, _vp]),
+    "pmx_dbam_fragments_begin": (_int, [_vp, _u32, _vp]),
+    "pmx_dbam_fragments_add": (_int, [_vp, _u32, _u32, _pu64]),
+    "pmx_dbam_fragments_tables": (_int, [_vp, _vp, _vp]),
+    "pmx_dbam_fragments_timings": (_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "pmx_dbam_fragments_rows": (_i64, [_vp, _u32, _u32, _u32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pmx_dbam_coverage_add_fragments": (_int, [_vp, _u32, _u32, _u32, _pu64]),
     "pmx_dgc_open": (_int, [_str, _int, _int, _out]),
     "pmx_dgc_close": (None, [_vp]),
     "pmx_dgc_nrec": (_i32, [_vp]),
@@ -323,6 +333,14 @@ class AlignmentReader(NativeReader):
         self._check_open()
         return from_reader(self, genome, mapq_criteria, references, window)
 
+    def fragment_sizes(self, mapq_criteria: int = 0, references=None, max_size: int = 2000):
+        """The paired-end fragment sizes of the reads of ``bin_counts`` that are paired, per orientation, from each read1 record's
+        own mate fields: a ``pymasc_amd.fragments.FragmentSizes`` (``fragments.from_reader``).  A device reader
+        counts on the GPU with arrays of its own: the arrays of the last ``decode`` stay as they are."""
+        from .fragments import from_reader
+        self._check_open()
+        return from_reader(self, mapq_criteria, references, max_size)
+
     # ---- excluded regions (pymasc_amd.region_mask; DESIGN.md 7.15) ----
     _exclude = None
     _dropped = 0
@@ -367,7 +385,7 @@ class AlignmentReader(NativeReader):
 
 
 #: the counts taken beside the correlation, in the order a stream reader serves them (it decides which error surfaces first)
-SIDE_KINDS = ("complexity", "fingerprint", "peaks", "coverage", "gcbias")
+SIDE_KINDS = ("complexity", "fingerprint", "peaks", "coverage", "gcbias", "fragments")
 
 
 class SideAccumulator:

@@ -21,7 +21,7 @@ from itertools import zip_longest
 from pathlib import Path
 from typing import List, Optional, Sequence
 
-from . import complexity, coverage, ffi, fingerprint, gcbias, peaks, readlen, tables
+from . import complexity, coverage, ffi, fingerprint, fragments, gcbias, peaks, readlen, tables
 from .chromfilter import NoTargetChromosomesError, filter_references, kept_references
 from .exceptions import InputUnseekable, ReadUnsortedError
 from .inputs import (check_bed_sizes, default_device_ingest, is_stream, open_alignments, open_header, open_track,
@@ -39,7 +39,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         library_length: Optional[int] = None, smooth_window: int = 15, mask_size: int = 5, bg_avr_width: int = 50,
         chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None,
         fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None,
-        peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto", gc_bias=None, gc_window: int = 100):
+        peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto", gc_bias=None, gc_window: int = 100,
+        fragments: bool = False, fragments_max: int = 2000):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -94,10 +95,17 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
     that is not A C G T or inside ``exclude_regions`` are left out.  Counted where ``complexity`` is counted.  The genome is
     parsed once per call (on the GPU with device ingest).  A chosen reference without a record of its name and length:
-    ValueError before the run; a FASTA that cannot be parsed: ``GenomeError``."""
+    ValueError before the run; a FASTA that cannot be parsed: ``GenomeError``.
+    ``fragments``: rank 0 also writes ``<stem>_fragments.tab`` (pymasc_amd.fragments): the paired-end fragment
+    sizes of the reads the fingerprint counts, each pair counted at its read1 record from that record's own mate fields, with
+    median and spread per orientation (FR, RF, TANDEM) and the histogram up to ``fragments_max`` bases (1 .. 65536); an excluded
+    region drops a pair whose fragment touches it.  Counted where ``complexity`` is counted.  ``coverage_extend="pair"`` piles the
+    FR pairs of at most ``fragments_max`` bases at their own extent instead of extended reads; it is known before the feed, so a
+    stream takes it.  A BED read file has no mate fields: ValueError before anything is read, with either."""
     check_bed_sizes(bam_path, chrom_sizes)
     s = _settings(locals())
     _check_coverage_input(s, bam_path)
+    _check_pairs_input(s, bam_path)
     from .kmer_track import is_fasta
     bam = track = None              # a reader opened here for the estimate and handed on: the file is inflated once per run
     try:
@@ -159,6 +167,8 @@ class _Settings:
     coverage_extend: object         # an int (0: every read's own length), or "auto": the run's fragment-length estimate
     gc_bias: object                 # None, or the _GcGenome parsed once for the call
     gc_window: int
+    fragments: bool
+    fragments_max: int              # the largest fragment size counted, and piled by a "pair" pileup
     save_mappability_stats: bool
     device: int
     ingest: bool
@@ -202,9 +212,10 @@ def _settings(kw: dict) -> _Settings:
         given["peaks"] = open_peaks(kw["peaks"], bool(ingest), reader_device(kw["context"], device, bool(ingest)))
     given["peaks_extend"] = int(kw["peaks_extend"])
     extend = kw["coverage_extend"]
-    if extend != "auto" and (isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0):
-        raise ValueError("coverage_extend is \"auto\" or an integer of at least 0")
-    given.update(coverage=bool(kw["coverage"]), coverage_extend=extend if extend == "auto" else int(extend))
+    if extend not in ("auto", coverage.PAIR) and (isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0):
+        raise ValueError("coverage_extend is \"auto\", \"pair\" or an integer of at least 0")
+    given.update(coverage=bool(kw["coverage"]), coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend))
+    given.update(fragments=bool(kw["fragments"]), fragments_max=fragments.check_max_size(kw["fragments_max"]))
     if int(kw["fingerprint_bin"]) < 1 or int(kw["fingerprint_extend"]) < 0:
         raise ValueError("fingerprint_bin is at least 1 and fingerprint_extend at least 0")
     control = kw["fingerprint_control"]
@@ -227,6 +238,13 @@ def _check_coverage_input(s: _Settings, path) -> None:
     """ValueError for a stream whose pileup would need the run's own estimate: it cannot be read a second time."""
     if s.coverage and s.coverage_extend == "auto" and is_stream(path):
         raise ValueError("'{}' is a stream and cannot be read twice: give coverage_extend an integer".format(path))
+
+
+def _check_pairs_input(s: _Settings, path) -> None:
+    """ValueError for a BED read file when the call counts pairs: it has no mate fields."""
+    from .bed_reads import is_bed_reads
+    if (s.fragments or (s.coverage and s.coverage_extend == coverage.PAIR)) and not is_stream(path) and is_bed_reads(path):
+        raise ValueError("'{}' is a BED read file: {}".format(path, fragments.NO_MATES))
 
 
 def _check_inputs(s: _Settings, path, bam) -> None:
@@ -430,12 +448,12 @@ class _CoverageCount(_SideCount):
         from .bam_device import DeviceBamReader
         spool, mapq = extend is None, int(self.s.mapq_criteria)
         if spool:
-            extend = int(self.s.coverage_extend)
+            extend = self.s.coverage_extend     # (an integer or "pair")
         if not isinstance(reader, DeviceBamReader):
-            c = coverage.from_reader(reader, mapq, names, extend)
+            c = coverage.from_reader(reader, mapq, names, extend, self.s.fragments_max)
             return extend, c.reads, c.text_chunks()
         if acc is None:             # (an armed count is not built again: its ``begin`` would zero the table)
-            acc = coverage.device_count_of(reader, mapq, names, extend)
+            acc = coverage.device_count_of(reader, mapq, names, extend, self.s.fragments_max)
         reads = acc.finish(reader)["reads"]
         if not spool:
             return extend, reads, acc.text_chunks(reader)
@@ -451,7 +469,7 @@ class _CoverageCount(_SideCount):
         base = Path(s.outdir) / basename
         if self.value is not None:
             return self.row.write(s, base, basename, self.value)
-        extend = int(statistics().est_lib_len) if s.coverage_extend == "auto" else int(s.coverage_extend)
+        extend = int(statistics().est_lib_len) if s.coverage_extend == "auto" else s.coverage_extend
         return _count_again(s, path, lambda r, names: self.row.write(s, base, basename, self._take(r, names, None, extend)))
 
 
@@ -491,11 +509,14 @@ _SIDES = (
           lambda s, names: (s.peaks, int(s.mapq_criteria), names, s.peaks_extend), "arm_peaks",
           lambda s, base, basename, value: peaks.write_peaks(base, basename, value, s.peaks.source or "")),
     _Side("coverage", lambda s: s.coverage, coverage.COVERAGE_SUFFIX, coverage,
-          lambda s, names: (int(s.mapq_criteria), names, int(s.coverage_extend)), "arm_coverage",
+          lambda s, names: (int(s.mapq_criteria), names, s.coverage_extend, s.fragments_max), "arm_coverage",
           lambda s, base, basename, value: coverage.write_track(base, basename, *value), _CoverageCount),
     _Side("gcbias", lambda s: s.gc_bias is not None, gcbias.GCBIAS_SUFFIX, gcbias,      # (the genome is parsed when first needed)
           lambda s, names: (s.gc_bias.open(), int(s.mapq_criteria), names, s.gc_window), "arm_gcbias",
           lambda s, base, basename, value: gcbias.write_gcbias(base, basename, value)),
+    _Side("fragments", lambda s: s.fragments, fragments.FRAGMENTS_SUFFIX, fragments,
+          lambda s, names: (int(s.mapq_criteria), names, s.fragments_max), "arm_fragments",
+          lambda s, base, basename, value: fragments.write_fragments(base, basename, value)),
 )
 
 
@@ -601,7 +622,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               chi2_pval: float = 0.05, names: Optional[Sequence[Optional[str]]] = None, chrom_sizes=None,
               complexity: bool = False, exclude_regions=None, fingerprint: bool = False, fingerprint_bin: int = 500,
               fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0, coverage: bool = False,
-              coverage_extend="auto", gc_bias=None, gc_window: int = 100) -> List[FileResult]:
+              coverage_extend="auto", gc_bias=None, gc_window: int = 100, fragments: bool = False,
+              fragments_max: int = 2000) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -634,7 +656,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
     rank 0 writes inside ``sharding.on_rank0``, so that a write error reaches every rank (``written`` is [] on the others).
 
     ``gc_bias``: the genome is parsed once, before the first file runs, and serves every file; a file whose chosen references
-    have no record of their name and length in it is logged and skipped; a FASTA that cannot be parsed raises ``GenomeError``."""
+    have no record of their name and length in it is logged and skipped; a FASTA that cannot be parsed raises ``GenomeError``.
+    ``fragments`` / ``coverage_extend="pair"``: a BED read file has no mate fields and is skipped in step 1 with run's ValueError."""
     paths = list(paths)
     if not paths:
         raise ValueError("no input files")
@@ -792,6 +815,13 @@ def _choose(s: _Settings, paths, errors, read_len):
                 _check_coverage_input(s, p)
             except ValueError as e:
                 errors[i] = e
+            continue
+        try:
+            _check_pairs_input(s, p)
+        except ValueError as e:
+            logger.error("Failed to open file '{}'".format(p))
+            logger.error(str(e))
+            errors[i] = e
             continue
         if stream and device is None:
             logger.error("Failed to open file '{}'".format(p))

@@ -104,6 +104,18 @@ class SamReader(AlignmentReader):
         for first in range(0, total, batch):
             yield self._drop_excluded(*self._fetch(first, min(batch, total - first)))
 
+    def mate_batches(self, mapq_criteria: int = 0, flag_exclude: int = PMX_BAM_DEFAULT_EXCLUDE, batch: int = 1 << 22):
+        """``BamReader.mate_batches`` for the text: (ref_id, pos_1based, read_len, is_reverse, flag, mate_ref_id, mate_pos_1based,
+        tlen) by ``pmx_sam_fetch_mates``; a PNEXT or TLEN that is no decimal integer raises ``PmxIOError`` with ``line N: ...``."""
+        total = self.decode(mapq_criteria, flag_exclude)
+        for first in range(0, total, batch):
+            n = min(batch, total - first)
+            flag, mref, mpos, tlen = (np.empty(n, dtype=t) for t in (np.uint16, np.int32, np.int32, np.int32))
+            rc = self._L.pmx_sam_fetch_mates(self._h, first, n, flag.ctypes.data, mref.ctypes.data, mpos.ctypes.data, tlen.ctypes.data)
+            if rc:
+                self._raise(rc)
+            yield self._fetch(first, n) + (flag, mref, mpos, tlen)
+
     def fetch(self, reference: str, *args, **kwargs):
         raise ValueError("fetch() needs an index: {} is a SAM file".format(self.path))
 

@@ -166,13 +166,13 @@ class DeviceStreamReader(DeviceBamReader):
     def disarm_peaks(self) -> None:
         self._disarm("peaks")
 
-    def arm_coverage(self, mapq_criteria: int = 0, references=None, extend: int = 0):
+    def arm_coverage(self, mapq_criteria: int = 0, references=None, extend=0, max_size: int = 2000):
         """From now on every window a pass makes current is also piled up base by base (``pmx_dbam_coverage_add``, into the table
         ``pmx_dbam_coverage_begin`` allocates here); returns the ``pymasc_amd.coverage.DeviceCount`` whose ``finish(reader)`` /
         ``result(reader)`` is the whole stream's once the pass has ended.  A read is marked in the window that decodes it, as
-        for ``arm_fingerprint``."""
+        for ``arm_fingerprint``.  ``extend`` ``"pair"``: the FR pairs of at most ``max_size`` bases at their own extent."""
         from .coverage import DeviceCount
-        return self._arm("coverage", DeviceCount(self, mapq_criteria, references, extend))
+        return self._arm("coverage", DeviceCount(self, mapq_criteria, references, extend, max_size))
 
     def disarm_coverage(self) -> None:
         self._disarm("coverage")
@@ -187,6 +187,17 @@ class DeviceStreamReader(DeviceBamReader):
 
     def disarm_gcbias(self) -> None:
         self._disarm("gcbias")
+
+    def arm_fragments(self, mapq_criteria: int = 0, references=None, max_size: int = 2000):
+        """From now on the pairs of every window a pass makes current are also counted by fragment size
+        (``pmx_dbam_fragments_add``, into the table ``pmx_dbam_fragments_begin`` allocates here); returns the
+        ``pymasc_amd.fragments.DeviceCount`` whose ``result(reader)`` is the whole stream's once the pass has ended.  A pair is
+        counted at its read1 record, in the window that decodes it: nothing is held back."""
+        from .fragments import DeviceCount
+        return self._arm("fragments", DeviceCount(self, mapq_criteria, references, max_size))
+
+    def disarm_fragments(self) -> None:
+        self._disarm("fragments")
 
     def _keep_mask(self):
         if len(self._selected) == len(self.references):
