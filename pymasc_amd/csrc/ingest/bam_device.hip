@@ -1164,6 +1164,8 @@ const char *inf_err_text(u32 code)
 struct StreamState;   // (stream_device.inc)
 struct CvSeg;         // (coverage_device.inc)
 
+#include "side_state.inc"
+
 }  // namespace
 
 struct pmx_dbam {
@@ -1235,43 +1237,12 @@ struct pmx_dbam {
     u64 x_n = 0, x_dropped = 0;      // merged intervals; reads the last decode left out because of them
     u8 *d_xs = nullptr;              // the filter's scratch block (flags, block counts, compacted fields), grown, never shrunk
     u64 xs_cap = 0;
-    // read counts per genome bin (pmx_dbam_bincount_*, bincount_device.inc): from begin to the next begin or close
-    u32 *d_bc = nullptr;             // one count per bin, the chosen references' bins end to end in header order
-    long long *d_bc_tab = nullptr;   // per reference: its first bin (-1: not chosen), its number of bins
-    u64 bc_bins = 0, bc_reads = 0;   // bins; reads that added to a bin since begin
-    u32 bc_bin = 0, bc_ext = 0;      // bin size, extend
-    // reads per peak line (pmx_dbam_peakcount_*, peakcount_device.inc): from begin to the next begin or close
-    u8 *d_pk = nullptr;              // per line, in (reference, begin) order: key, pmax (8 bytes each), end, input line; counts by input line
-    long long *d_pk_tab = nullptr;   // per reference: its length, -1 when it is not chosen
-    bool pk_on = false;              // between a begin that succeeded and the next one
-    u64 pk_lines = 0, pk_union = 0;  // lines; bases of the merged lines on chosen references
-    u32 pk_ext = 0;                  // extend
-    std::vector<u64> pk_tot;         // N, n_in, then the same two per reference, summed over the calls of add
-    // fragment pileup (pmx_dbam_coverage_*, coverage_device.inc): the table from begin to finish, the runs from finish to the next begin or close
-    int *d_cv = nullptr;             // one slot per base of every chosen reference + a closing one: depth[p] - depth[p - 1]
-    long long *d_cv_tab = nullptr;   // per reference: its first slot (-1: not chosen), its length
-    CvSeg *d_cv_seg = nullptr;       // per chosen reference: first slot, first tile, slots, id; one more entry closes the tiles
-    u8 *d_cv_names = nullptr;        // per reference the offset of its name (u32, one more closes them), then the names
-    u8 *d_cv_runs = nullptr;         // reference, start, end, depth of every run (4 bytes each)
-    int cv_state = 0;                // nothing / a table / runs
-    u64 cv_slots = 0, cv_tiles = 0, cv_reads = 0, cv_runs = 0;   // slots; tiles; reads that added since begin; runs
-    u64 cv_held = 0;                 // device bytes the pileup holds now
-    u32 cv_nc = 0, cv_ext = 0;       // chosen references; extend
-    u64 cv_tot[5] = {0, 0, 0, 0, 0}; // reads, runs, covered bases, fragment bases, largest depth
-    // GC bias (pmx_dbam_gcbias_*, gcbias_device.inc): from begin to the next begin or close
-    u64 *d_gc = nullptr, *d_gc_bl = nullptr;   // one GC and one blocked bit per position of the chosen references, laid end to end
-    long long *d_gc_tab = nullptr;   // per reference: its first position in the bit vectors (-1: not chosen), its length
-    unsigned long long *d_gc_f = nullptr;      // F[0 .. window]
-    u32 gc_w = 0;                    // the window (0: no table)
-    u64 gc_words = 0;                // words of each bit vector
-    std::vector<u64> gc_n;           // N[0 .. window], computed by begin
-    u64 gc_tot[3] = {0, 0, 0};       // reads placed, off_end, blocked since begin
-    // fragment sizes (pmx_dbam_fragments_*, fragments_device.inc): from begin to the next begin or close
-    unsigned long long *d_fr = nullptr;   // H[3][fr_max]
-    u8 *d_fr_use = nullptr;          // per reference: chosen (null: every reference)
-    u32 fr_max = 0;                  // max_size (0: no table)
-    u64 fr_c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // the counters since begin
-    double fr_t[2] = {0, 0};         // seconds since begin: the row filter (wall clock), k_fr_hist (HIP events)
+    // the side counts (side_state.inc): each from its begin to the next begin or close
+    Bincount bc;
+    Peakcount pk;
+    Coverage cv;
+    GcBias gc;
+    Fragments fr;
     // the mate fields of the SAM line table (k_sam_mates): built by the first pair call, freed with the table
     int *d_smpos = nullptr, *d_stlen = nullptr;
     u8 *d_ssame = nullptr;
@@ -1644,15 +1615,6 @@ int free_chain(pmx_dbam &b)
 }
 
 // ---- indexed reading: host helpers -----------------------------------------------------------------------------
-struct DevAlloc {   // a device allocation freed on every way out
-    void *p = nullptr;
-    ~DevAlloc()
-    {
-        if (p) (void)hipFree(p);
-    }
-    template <class T> T *as() const { return (T *)p; }
-};
-
 struct FileMember {
     u64 coff;          // file offset of the member
     u32 total, hlen;   // bytes of the whole member, of its gzip header (12 + XLEN)
@@ -1895,17 +1857,9 @@ void pmx_dbam_close(pmx_dbam *b)
     if (b->d_xkey) (void)hipFree(b->d_xkey);
     if (b->d_xend) (void)hipFree(b->d_xend);
     if (b->d_xs) (void)hipFree(b->d_xs);
-    if (b->d_bc) (void)hipFree(b->d_bc);
-    if (b->d_bc_tab) (void)hipFree(b->d_bc_tab);
-    if (b->d_pk) (void)hipFree(b->d_pk);
-    if (b->d_pk_tab) (void)hipFree(b->d_pk_tab);
-    for (void *p : {(void *)b->d_gc, (void *)b->d_gc_bl, (void *)b->d_gc_tab, (void *)b->d_gc_f})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->d_cv, (void *)b->d_cv_tab, (void *)b->d_cv_seg, (void *)b->d_cv_names, (void *)b->d_cv_runs})
-        if (p) (void)hipFree(p);
     for (void *p : {(void *)b->d_nl, (void *)b->d_ls, (void *)b->d_sref, (void *)b->d_spos, (void *)b->d_sqlen, (void *)b->d_sfm})
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)b->d_fr, (void *)b->d_fr_use, (void *)b->d_smpos, (void *)b->d_stlen, (void *)b->d_ssame})
+    for (void *p : {(void *)b->d_smpos, (void *)b->d_stlen, (void *)b->d_ssame})
         if (p) (void)hipFree(p);
     for (hipStream_t x : b->kmore)
         if (x) (void)hipStreamDestroy(x);
@@ -1915,7 +1869,7 @@ void pmx_dbam_close(pmx_dbam *b)
     if (b->d_out) (void)hipFree(b->d_out);
     if (b->d_status) (void)hipFree(b->d_status);
     if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
+    delete b;       // (the side counts' tables: hipFree needs no stream, and every stream was waited for above)
 }
 
 int32_t pmx_dbam_nref(const pmx_dbam *b) { return b ? (int32_t)b->ref_names.size() : 0; }

@@ -110,22 +110,12 @@ __global__ void __launch_bounds__(256) k_fp_hist(const u32 *__restrict__ counts,
 
 namespace {
 
-void bincount_free(pmx_dbam *b)
-{
-    if (b->d_bc) (void)hipFree(b->d_bc);
-    if (b->d_bc_tab) (void)hipFree(b->d_bc_tab);
-    b->d_bc = nullptr;
-    b->d_bc_tab = nullptr;
-    b->bc_bins = b->bc_reads = 0;
-    b->bc_bin = b->bc_ext = 0;
-}
-
 int bincount_begin_impl(pmx_dbam *b, u32 bin_size, u32 extend, const uint8_t *use_ref)
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
-    bincount_free(b);
+    b->bc = Bincount{};
     if (bin_size == 0) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_begin: the bin size is 0");
     const u64 nref = b->ref_names.size();
     std::vector<long long> tab(2 * std::max<u64>(nref, 1), 0);
@@ -139,17 +129,18 @@ int bincount_begin_impl(pmx_dbam *b, u32 bin_size, u32 extend, const uint8_t *us
     }
     if (bins == 0) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_begin: no chosen reference is as long as one bin");
     if (bins >= (1ull << 31)) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_begin: 2^31 bins or more: choose a larger bin size");
-    HIPOK(hipMalloc((void **)&b->d_bc_tab, 8 * tab.size()));
-    if (hipMalloc((void **)&b->d_bc, 4 * bins) != hipSuccess) {
-        bincount_free(b);
+    Bincount &c = b->bc;
+    HIPOK(hipMalloc(&c.tab.p, 8 * tab.size()));
+    if (hipMalloc(&c.counts.p, 4 * bins) != hipSuccess) {
+        c = Bincount{};
         return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_bincount_begin: out of device memory for the bins");
     }
-    HIPOK(hipMemcpyAsync(b->d_bc_tab, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, b->stream));
-    HIPOK(hipMemsetAsync(b->d_bc, 0, 4 * bins, b->stream));
+    HIPOK(hipMemcpyAsync(c.tab.p, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, b->stream));
+    HIPOK(hipMemsetAsync(c.counts.p, 0, 4 * bins, b->stream));
     HIPOK(hipStreamSynchronize(b->stream));       // (tab is a local)
-    b->bc_bins = bins;
-    b->bc_bin = bin_size;
-    b->bc_ext = extend;
+    c.bins = bins;
+    c.bin = bin_size;
+    c.ext = extend;
     if (b->st) stream_note(*b);
     return 0;
 }
@@ -159,23 +150,15 @@ int bincount_add_impl(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, uint64_t *rea
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!reads_added) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_add: null output");
     *reads_added = 0;
-    if (!b->d_bc) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_add: no table: call pmx_dbam_bincount_begin first");
-    HIPOK(hipSetDevice(b->device));
-    hipStream_t st = b->stream;
-    CxRecs R;
-    if (int rc = cx_filter(b, mapq_min, flag_exclude, 0, true, R)) return rc;
-    if (R.n == 0) return 0;
-    DevAlloc d_added;
-    HIPOK(hipMalloc(&d_added.p, 8));
-    HIPOK(hipMemsetAsync(d_added.p, 0, 8, st));
-    hipLaunchKernelGGL(k_fp_count, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
-                       R.rev.as<u8>(), R.n, b->d_bc_tab, (u32)b->ref_names.size(), b->bc_bin, b->bc_ext, b->d_bc,
-                       d_added.as<unsigned long long>());
-    HIPOK(hipGetLastError());
+    if (!b->bc.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_add: no table: call pmx_dbam_bincount_begin first");
+    Bincount &c = b->bc;
     unsigned long long added = 0;
-    HIPOK(hipMemcpyAsync(&added, d_added.p, 8, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    b->bc_reads += added;
+    const int rc = side_add(b, mapq_min, flag_exclude, 1, &added, [&](const CxRecs &R, hipStream_t st, unsigned long long *d_added) {
+        hipLaunchKernelGGL(k_fp_count, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
+                           R.rev.as<u8>(), R.n, c.tab.as<long long>(), (u32)b->ref_names.size(), c.bin, c.ext, c.counts.as<u32>(), d_added);
+    });
+    if (rc) return rc;
+    c.reads += added;
     *reads_added = added;
     return 0;
 }
@@ -184,7 +167,7 @@ int64_t bincount_hist_impl(pmx_dbam *b, uint64_t *hist, uint64_t *totals, int64_
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!hist || !totals || cap < 0) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_hist: null output");
-    if (!b->d_bc) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_hist: no table: call pmx_dbam_bincount_begin first");
+    if (!b->bc.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_hist: no table: call pmx_dbam_bincount_begin first");
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
     const u64 room = tail ? (u64)cap : 0, nres = FP_HIST + 3u;
@@ -192,8 +175,8 @@ int64_t bincount_hist_impl(pmx_dbam *b, uint64_t *hist, uint64_t *totals, int64_
     HIPOK(hipMalloc(&d_res.p, 8 * nres));
     HIPOK(hipMemsetAsync(d_res.p, 0, 8 * nres, st));
     if (room) HIPOK(hipMalloc(&d_tail.p, 4 * room));
-    const u64 nwg = std::min<u64>((b->bc_bins + 255) / 256, FP_HIST_GRID);
-    hipLaunchKernelGGL(k_fp_hist, dim3((unsigned)nwg), dim3(256), 0, st, b->d_bc, b->bc_bins, d_res.as<unsigned long long>(),
+    const u64 nwg = std::min<u64>((b->bc.bins + 255) / 256, FP_HIST_GRID);
+    hipLaunchKernelGGL(k_fp_hist, dim3((unsigned)nwg), dim3(256), 0, st, b->bc.counts.as<u32>(), b->bc.bins, d_res.as<unsigned long long>(),
                        d_res.as<unsigned long long>() + FP_HIST, d_tail.as<u32>(), room);
     HIPOK(hipGetLastError());
     std::vector<unsigned long long> res(nres);
@@ -204,7 +187,7 @@ int64_t bincount_hist_impl(pmx_dbam *b, uint64_t *hist, uint64_t *totals, int64_
     for (u32 k = 0; k < FP_HIST; k++) hist[k] = res[k];
     totals[0] = res[FP_HIST];
     totals[1] = res[FP_HIST + 1];
-    totals[2] = b->bc_reads;
+    totals[2] = b->bc.reads;
     return (int64_t)(tail ? got : above);
 }
 
@@ -212,12 +195,12 @@ int bincount_copy_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t *counts)
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!counts) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_copy: null output");
-    if (!b->d_bc) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_copy: no table: call pmx_dbam_bincount_begin first");
-    if (first < 0 || n < 0 || (u64)first > b->bc_bins || (u64)n > b->bc_bins - (u64)first)
+    if (!b->bc.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_copy: no table: call pmx_dbam_bincount_begin first");
+    if (first < 0 || n < 0 || (u64)first > b->bc.bins || (u64)n > b->bc.bins - (u64)first)
         return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_bincount_copy: range outside the table");
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
-    if (n) HIPOK(hipMemcpy(counts, b->d_bc + first, 4 * (u64)n, hipMemcpyDeviceToHost));
+    if (n) HIPOK(hipMemcpy(counts, b->bc.counts.as<u32>() + first, 4 * (u64)n, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -227,38 +210,22 @@ extern "C" {
 
 int pmx_dbam_bincount_begin(pmx_dbam *b, uint32_t bin_size, uint32_t extend, const uint8_t *use_ref)
 {
-    try {
-        return bincount_begin_impl(b, bin_size, extend, use_ref);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_bincount_begin: ") + e.what());
-    }
+    return guarded("pmx_dbam_bincount_begin", [&] { return bincount_begin_impl(b, bin_size, extend, use_ref); });
 }
 
 int pmx_dbam_bincount_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t *reads_added)
 {
-    try {
-        return bincount_add_impl(b, mapq_min, flag_exclude, reads_added);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_bincount_add: ") + e.what());
-    }
+    return guarded("pmx_dbam_bincount_add", [&] { return bincount_add_impl(b, mapq_min, flag_exclude, reads_added); });
 }
 
 int64_t pmx_dbam_bincount_hist(pmx_dbam *b, uint64_t hist[PMX_BINCOUNT_HIST], uint64_t totals[3], int64_t cap, uint32_t *tail)
 {
-    try {
-        return bincount_hist_impl(b, hist, totals, cap, tail);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_bincount_hist: ") + e.what());
-    }
+    return guarded("pmx_dbam_bincount_hist", [&] { return bincount_hist_impl(b, hist, totals, cap, tail); });
 }
 
 int pmx_dbam_bincount_copy(pmx_dbam *b, int64_t first, int64_t n, uint32_t *counts)
 {
-    try {
-        return bincount_copy_impl(b, first, n, counts);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_bincount_copy: ") + e.what());
-    }
+    return guarded("pmx_dbam_bincount_copy", [&] { return bincount_copy_impl(b, first, n, counts); });
 }
 
 }  // extern "C"

@@ -313,6 +313,30 @@ int cx_filter(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, u64 front, bool curre
     return 0;
 }
 
+inline int side_add_any(const CxRecs &) { return 0; }
+
+// What the add of bincount, peakcount, coverage and gcbias share behind their own entry checks: the kept records of what the handle
+// holds now (none: nothing is counted), `check` on them before anything is allocated or marked, n zeroed 64-bit counters on the
+// device, `launch` (the family's kernel over the records, on the stream, adding to the counters), the counters into counters[n].
+template <class Launch, class Check = int (*)(const CxRecs &)>
+int side_add(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, u64 n, unsigned long long *counters, Launch &&launch, Check &&check = side_add_any)
+{
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    CxRecs R;
+    if (int rc = cx_filter(b, mapq_min, flag_exclude, 0, true, R)) return rc;
+    if (R.n == 0) return 0;
+    if (int rc = check(R)) return rc;
+    DevAlloc d;
+    HIPOK(hipMalloc(&d.p, 8 * n));
+    HIPOK(hipMemsetAsync(d.p, 0, 8 * n, st));
+    launch(R, st, d.as<unsigned long long>());
+    HIPOK(hipGetLastError());
+    HIPOK(hipMemcpyAsync(counters, d.p, 8 * n, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    return 0;
+}
+
 // stable LSD radix passes over the digits of `differ`, from key_first (left as it is) through the buffers ka / kb, the payload
 // from vin (null: the key's index) through va / vb; afterwards kin / vin are the sorted keys and their payload
 int cx_sort(hipStream_t st, u64 n, u64 differ, const u64 *&kin, const u32 *&vin, u64 *ka, u64 *kb, u32 *va, u32 *vb, u32 *d_cnt,
@@ -488,11 +512,7 @@ extern "C" {
 int pmx_dbam_complexity(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, const uint8_t *use_ref, uint64_t *per_ref,
                         uint64_t hist[PMX_COMPLEXITY_BINS])
 {
-    try {
-        return dbam_complexity_impl(b, mapq_min, flag_exclude, use_ref, per_ref, hist);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_complexity: ") + e.what());
-    }
+    return guarded("pmx_dbam_complexity", [&] { return dbam_complexity_impl(b, mapq_min, flag_exclude, use_ref, per_ref, hist); });
 }
 
 }  // extern "C"

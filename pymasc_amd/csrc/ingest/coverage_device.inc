@@ -303,23 +303,6 @@ __global__ void __launch_bounds__(256) k_cv_text(const int *__restrict__ rref, c
 
 namespace {
 
-enum { CV_NONE = 0, CV_TABLE = 1, CV_RUNS = 2 };
-
-void coverage_free(pmx_dbam *b)
-{
-    for (void *p : {(void *)b->d_cv, (void *)b->d_cv_tab, (void *)b->d_cv_seg, (void *)b->d_cv_names, (void *)b->d_cv_runs})
-        if (p) (void)hipFree(p);
-    b->d_cv = nullptr;
-    b->d_cv_tab = nullptr;
-    b->d_cv_seg = nullptr;
-    b->d_cv_names = nullptr;
-    b->d_cv_runs = nullptr;
-    b->cv_state = CV_NONE;
-    b->cv_slots = b->cv_tiles = b->cv_reads = b->cv_runs = b->cv_held = 0;
-    b->cv_nc = b->cv_ext = 0;
-    for (u64 &x : b->cv_tot) x = 0;
-}
-
 // the arrays of the runs in their one block: reference, start, end, depth (4 bytes per run each)
 struct CvRuns {
     int *ref;
@@ -332,7 +315,7 @@ int coverage_begin_impl(pmx_dbam *b, u32 extend, const uint8_t *use_ref)
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
-    coverage_free(b);
+    b->cv = Coverage{};
     const u64 nref = b->ref_names.size();
     std::vector<long long> tab(2 * std::max<u64>(nref, 1), -1);
     std::vector<CvSeg> seg;
@@ -357,27 +340,28 @@ int coverage_begin_impl(pmx_dbam *b, u32 extend, const uint8_t *use_ref)
     const u32 nc = (u32)seg.size();
     seg.push_back(CvSeg{slots, (u32)tiles, 0u, -1, 0u});        // (the end of the last reference's tiles)
     hipStream_t st = b->stream;
-    HIPOK(hipMalloc((void **)&b->d_cv_tab, 8 * tab.size()));
-    HIPOK(hipMalloc((void **)&b->d_cv_seg, sizeof(CvSeg) * seg.size()));
-    HIPOK(hipMalloc((void **)&b->d_cv_names, 4 * noff.size() + std::max<u64>(names.size(), 1)));
-    if (hipMalloc((void **)&b->d_cv, 4 * slots) != hipSuccess) {
+    Coverage &c = b->cv;
+    HIPOK(hipMalloc(&c.tab.p, 8 * tab.size()));
+    HIPOK(hipMalloc(&c.seg.p, sizeof(CvSeg) * seg.size()));
+    HIPOK(hipMalloc(&c.names.p, 4 * noff.size() + std::max<u64>(names.size(), 1)));
+    if (hipMalloc(&c.table.p, 4 * slots) != hipSuccess) {
         (void)hipGetLastError();
-        coverage_free(b);
+        c = Coverage{};
         return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_coverage_begin: out of device memory for the table: " + std::to_string(4 * slots) +
                                            " bytes asked for (4 per base of the chosen references)");
     }
-    HIPOK(hipMemcpyAsync(b->d_cv_tab, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, st));
-    HIPOK(hipMemcpyAsync(b->d_cv_seg, seg.data(), sizeof(CvSeg) * seg.size(), hipMemcpyHostToDevice, st));
-    HIPOK(hipMemcpyAsync(b->d_cv_names, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, st));
-    if (!names.empty()) HIPOK(hipMemcpyAsync(b->d_cv_names + 4 * noff.size(), names.data(), names.size(), hipMemcpyHostToDevice, st));
-    HIPOK(hipMemsetAsync(b->d_cv, 0, 4 * slots, st));
+    HIPOK(hipMemcpyAsync(c.tab.p, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemcpyAsync(c.seg.p, seg.data(), sizeof(CvSeg) * seg.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemcpyAsync(c.names.p, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, st));
+    if (!names.empty()) HIPOK(hipMemcpyAsync(c.names.as<u8>() + 4 * noff.size(), names.data(), names.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemsetAsync(c.table.p, 0, 4 * slots, st));
     HIPOK(hipStreamSynchronize(st));       // (tab, seg, noff and names are locals)
-    b->cv_state = CV_TABLE;
-    b->cv_slots = slots;
-    b->cv_tiles = tiles;
-    b->cv_nc = nc;
-    b->cv_ext = extend;
-    b->cv_held = 4 * slots;
+    c.state = CV_TABLE;
+    c.slots = slots;
+    c.tiles = tiles;
+    c.nc = nc;
+    c.ext = extend;
+    c.bytes = 4 * slots;
     if (b->st) stream_note(*b);
     return 0;
 }
@@ -387,24 +371,22 @@ int coverage_add_impl(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, uint64_t *rea
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!reads_added) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_add: null output");
     *reads_added = 0;
-    if (b->cv_state != CV_TABLE) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_add: no table: call pmx_dbam_coverage_begin first");
-    HIPOK(hipSetDevice(b->device));
-    hipStream_t st = b->stream;
-    CxRecs R;
-    if (int rc = cx_filter(b, mapq_min, flag_exclude, 0, true, R)) return rc;
-    if (R.n == 0) return 0;
-    if (b->cv_reads + R.n >= CV_MAX_READS)      // (before a mark is made: the table stays as it is)
-        return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_add: 2^31 reads or more: the depth is a 32-bit count");
-    DevAlloc d_added;
-    HIPOK(hipMalloc(&d_added.p, 8));
-    HIPOK(hipMemsetAsync(d_added.p, 0, 8, st));
-    hipLaunchKernelGGL(k_cv_marks, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
-                       R.rev.as<u8>(), R.n, b->d_cv_tab, (u32)b->ref_names.size(), b->cv_ext, b->d_cv, d_added.as<unsigned long long>());
-    HIPOK(hipGetLastError());
+    if (!b->cv.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_add: no table: call pmx_dbam_coverage_begin first");
+    Coverage &c = b->cv;
     unsigned long long added = 0;
-    HIPOK(hipMemcpyAsync(&added, d_added.p, 8, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    b->cv_reads += added;
+    const int rc = side_add(
+        b, mapq_min, flag_exclude, 1, &added,
+        [&](const CxRecs &R, hipStream_t st, unsigned long long *d_added) {
+            hipLaunchKernelGGL(k_cv_marks, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
+                               R.rev.as<u8>(), R.n, c.tab.as<long long>(), (u32)b->ref_names.size(), c.ext, c.table.as<int>(), d_added);
+        },
+        [&](const CxRecs &R) {                  // (before a mark is made: the table stays as it is)
+            return c.reads + R.n >= CV_MAX_READS
+                       ? fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_add: 2^31 reads or more: the depth is a 32-bit count")
+                       : 0;
+        });
+    if (rc) return rc;
+    c.reads += added;
     *reads_added = added;
     return 0;
 }
@@ -417,10 +399,10 @@ struct CvHold {
     void add(u64 bytes)
     {
         n += bytes;
-        b->cv_held += bytes;
+        b->cv.bytes += bytes;
         if (b->st) stream_note(*b);
     }
-    ~CvHold() { b->cv_held -= std::min(n, b->cv_held); }       // (a pileup freed meanwhile holds nothing)
+    ~CvHold() { b->cv.bytes -= std::min(n, b->cv.bytes); }       // (a pileup freed meanwhile holds nothing)
 };
 
 // the work of finish on a handle that holds a table; a failure leaves the handle for the caller to clear
@@ -428,7 +410,8 @@ int coverage_finish_run(pmx_dbam *b, uint64_t *totals)
 {
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
-    const u64 nt = b->cv_tiles;
+    Coverage &c = b->cv;
+    const u64 nt = c.tiles;
     u64 tot[2] = {0, 0}, ne = 0, nruns = 0;
     unsigned long long sums[3] = {0, 0, 0};
     {
@@ -439,9 +422,9 @@ int coverage_finish_run(pmx_dbam *b, uint64_t *totals)
         HIPOK(hipMemsetAsync(d_tot.p, 0, 64, st));
         u32 *tsum = d_t.as<u32>(), *tcnt = tsum + nt;
         u64 *psum = d_p.as<u64>(), *pcnt = psum + nt, *dt = d_tot.as<u64>();
-        b->cv_held += 24 * nt;
+        c.bytes += 24 * nt;
         if (b->st) stream_note(*b);
-        hipLaunchKernelGGL(k_cv_tiles, dim3((unsigned)nt), dim3(256), 0, st, b->d_cv, b->d_cv_seg, b->cv_nc, tsum, tcnt);
+        hipLaunchKernelGGL(k_cv_tiles, dim3((unsigned)nt), dim3(256), 0, st, c.table.as<int>(), c.seg.as<CvSeg>(), c.nc, tsum, tcnt);
         HIPOK(hipGetLastError());
         hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, tsum, tcnt, nt, psum, dt);
         HIPOK(hipGetLastError());
@@ -451,26 +434,25 @@ int coverage_finish_run(pmx_dbam *b, uint64_t *totals)
         HIPOK(hipStreamSynchronize(st));
         ne = tot[1];
         if ((u32)tot[0] != 0) {             // (every read adds +1 and -1 to its reference)
-            coverage_free(b);
+            c = Coverage{};
             return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_finish: the table does not add up to 0");
         }
         if (ne) {
             if (hipMalloc(&d_e.p, 12 * ne) != hipSuccess) {
                 (void)hipGetLastError();
-                coverage_free(b);
+                c = Coverage{};
                 return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_coverage_finish: out of device memory for " + std::to_string(ne) + " run boundaries");
             }
-            b->cv_held += 12 * ne;
+            c.bytes += 12 * ne;
             if (b->st) stream_note(*b);
             int *eref = d_e.as<int>();
             u32 *epos = (u32 *)(eref + ne), *edep = epos + ne;
-            hipLaunchKernelGGL(k_cv_runs, dim3((unsigned)nt), dim3(256), 0, st, b->d_cv, b->d_cv_seg, b->cv_nc, psum, pcnt, eref, epos, edep);
+            hipLaunchKernelGGL(k_cv_runs, dim3((unsigned)nt), dim3(256), 0, st, c.table.as<int>(), c.seg.as<CvSeg>(), c.nc, psum, pcnt, eref, epos, edep);
             HIPOK(hipGetLastError());
             HIPOK(hipStreamSynchronize(st));
         }
-        (void)hipFree(b->d_cv);             // the table has become entries
-        b->d_cv = nullptr;
-        b->cv_held -= 4 * b->cv_slots + 24 * nt;
+        c.table = DevAlloc{};               // the table has become entries
+        c.bytes -= 4 * c.slots + 24 * nt;
         if (ne) {
             const u64 nwg = (ne + 255) / 256;
             DevAlloc d_k, d_kb;
@@ -485,14 +467,14 @@ int coverage_finish_run(pmx_dbam *b, uint64_t *totals)
             HIPOK(hipMemcpyAsync(&nruns, dt + 4, 8, hipMemcpyDeviceToHost, st));
             HIPOK(hipStreamSynchronize(st));
             if (nruns) {
-                if (hipMalloc((void **)&b->d_cv_runs, 16 * nruns) != hipSuccess) {
+                if (hipMalloc(&c.runs.p, 16 * nruns) != hipSuccess) {
                     (void)hipGetLastError();
-                    coverage_free(b);
+                    c = Coverage{};
                     return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_coverage_finish: out of device memory for " + std::to_string(nruns) + " runs");
                 }
-                b->cv_held += 16 * nruns;
+                c.bytes += 16 * nruns;
                 if (b->st) stream_note(*b);
-                const CvRuns V(b->d_cv_runs, nruns);
+                const CvRuns V(c.runs.as<u8>(), nruns);
                 HIPOK(hipMemsetAsync(dt, 0, 24, st));
                 hipLaunchKernelGGL(k_cv_close, dim3((unsigned)nwg), dim3(256), 0, st, eref, epos, edep, ne, d_kb.as<u64>(), V.ref, V.start, V.end,
                                    V.depth, d_tot.as<unsigned long long>());
@@ -500,18 +482,18 @@ int coverage_finish_run(pmx_dbam *b, uint64_t *totals)
                 HIPOK(hipMemcpyAsync(sums, dt, 24, hipMemcpyDeviceToHost, st));
                 HIPOK(hipStreamSynchronize(st));
             }
-            b->cv_held -= 12 * ne;
+            c.bytes -= 12 * ne;
         }
     }
-    b->cv_state = CV_RUNS;
-    b->cv_slots = 0;
-    b->cv_runs = nruns;
-    b->cv_tot[0] = b->cv_reads;
-    b->cv_tot[1] = nruns;
-    b->cv_tot[2] = sums[0];
-    b->cv_tot[3] = sums[1];
-    b->cv_tot[4] = sums[2];
-    for (int k = 0; k < 5; k++) totals[k] = b->cv_tot[k];
+    c.state = CV_RUNS;
+    c.slots = 0;
+    c.nruns = nruns;
+    c.tot[0] = c.reads;
+    c.tot[1] = nruns;
+    c.tot[2] = sums[0];
+    c.tot[3] = sums[1];
+    c.tot[4] = sums[2];
+    for (int k = 0; k < 5; k++) totals[k] = c.tot[k];
     return 0;
 }
 
@@ -522,23 +504,23 @@ int coverage_finish_impl(pmx_dbam *b, uint64_t *totals)
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!totals) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_finish: null output");
     for (int k = 0; k < 5; k++) totals[k] = 0;
-    if (b->cv_state != CV_TABLE) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_finish: no table: call pmx_dbam_coverage_begin first");
-    int rc = PMX_DBAM_ERR_OPEN;
-    try {
-        rc = coverage_finish_run(b, totals);
-    } catch (...) {
-        coverage_free(b);
-        throw;
-    }
-    if (rc) coverage_free(b);
-    return rc;
+    if (!b->cv.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_finish: no table: call pmx_dbam_coverage_begin first");
+    struct Clear {      // (on a return code and on an exception)
+        pmx_dbam *b;
+        int rc;
+        ~Clear()
+        {
+            if (rc) b->cv = Coverage{};
+        }
+    } run{b, PMX_DBAM_ERR_OPEN};
+    return run.rc = coverage_finish_run(b, totals);
 }
 
 int coverage_range(pmx_dbam *b, const char *fn, int64_t first, int64_t n)
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
-    if (b->cv_state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": no runs: call pmx_dbam_coverage_finish first");
-    if (first < 0 || n < 0 || (u64)first > b->cv_runs || (u64)n > b->cv_runs - (u64)first)
+    if (b->cv.state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": no runs: call pmx_dbam_coverage_finish first");
+    if (first < 0 || n < 0 || (u64)first > b->cv.nruns || (u64)n > b->cv.nruns - (u64)first)
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": range outside the runs");
     return 0;
 }
@@ -550,7 +532,7 @@ int coverage_runs_impl(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
     if (n == 0) return 0;
-    const CvRuns V(b->d_cv_runs, b->cv_runs);
+    const CvRuns V(b->cv.runs.as<u8>(), b->cv.nruns);
     HIPOK(hipMemcpy(ref, V.ref + first, 4 * (u64)n, hipMemcpyDeviceToHost));
     HIPOK(hipMemcpy(start, V.start + first, 4 * (u64)n, hipMemcpyDeviceToHost));
     HIPOK(hipMemcpy(end, V.end + first, 4 * (u64)n, hipMemcpyDeviceToHost));
@@ -566,9 +548,9 @@ int64_t coverage_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, 
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
     const u64 m = (u64)n, nwg = (m + 255) / 256, nref = b->ref_names.size();
-    const CvRuns V(b->d_cv_runs, b->cv_runs);
-    const u32 *noff = (const u32 *)b->d_cv_names;
-    const u8 *names = b->d_cv_names + 4 * (nref + 1);
+    const CvRuns V(b->cv.runs.as<u8>(), b->cv.nruns);
+    const u32 *noff = b->cv.names.as<u32>();
+    const u8 *names = b->cv.names.as<u8>() + 4 * (nref + 1);
     DevAlloc d_len, d_w, d_wb, d_tot, d_text;
     CvHold held(b);
     held.add(4 * m + 12 * nwg + 16);
@@ -605,47 +587,27 @@ extern "C" {
 
 int pmx_dbam_coverage_begin(pmx_dbam *b, uint32_t extend, const uint8_t *use_ref)
 {
-    try {
-        return coverage_begin_impl(b, extend, use_ref);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_begin: ") + e.what());
-    }
+    return guarded("pmx_dbam_coverage_begin", [&] { return coverage_begin_impl(b, extend, use_ref); });
 }
 
 int pmx_dbam_coverage_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t *reads_added)
 {
-    try {
-        return coverage_add_impl(b, mapq_min, flag_exclude, reads_added);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_add: ") + e.what());
-    }
+    return guarded("pmx_dbam_coverage_add", [&] { return coverage_add_impl(b, mapq_min, flag_exclude, reads_added); });
 }
 
 int pmx_dbam_coverage_finish(pmx_dbam *b, uint64_t totals[5])
 {
-    try {
-        return coverage_finish_impl(b, totals);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_finish: ") + e.what());
-    }
+    return guarded("pmx_dbam_coverage_finish", [&] { return coverage_finish_impl(b, totals); });
 }
 
 int pmx_dbam_coverage_runs(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth)
 {
-    try {
-        return coverage_runs_impl(b, first, n, ref, start, end, depth);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_runs: ") + e.what());
-    }
+    return guarded("pmx_dbam_coverage_runs", [&] { return coverage_runs_impl(b, first, n, ref, start, end, depth); });
 }
 
 int64_t pmx_dbam_coverage_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
 {
-    try {
-        return coverage_text_impl(b, first, n, buf, cap);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_text: ") + e.what());
-    }
+    return guarded("pmx_dbam_coverage_text", [&] { return coverage_text_impl(b, first, n, buf, cap); });
 }
 
 }  // extern "C"

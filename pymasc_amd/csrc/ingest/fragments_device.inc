@@ -240,17 +240,6 @@ __global__ void __launch_bounds__(1024) k_fr_hist(const int *__restrict__ len, c
 
 namespace {
 
-void fragments_free(pmx_dbam *b)
-{
-    if (b->d_fr) (void)hipFree(b->d_fr);
-    if (b->d_fr_use) (void)hipFree(b->d_fr_use);
-    b->d_fr = nullptr;
-    b->d_fr_use = nullptr;
-    b->fr_max = 0;
-    for (u64 &c : b->fr_c) c = 0;
-    b->fr_t[0] = b->fr_t[1] = 0;
-}
-
 struct FrEvents {
     hipEvent_t a = nullptr, z = nullptr;
     ~FrEvents()
@@ -421,16 +410,15 @@ int fragments_begin_impl(pmx_dbam *b, u32 max_size, const uint8_t *use_ref)
     if (int rc = fr_check_handle(b, who)) return rc;
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
-    fragments_free(b);
+    b->fr = Fragments{};
     if (int rc = fr_check_size(max_size, who)) return rc;
     DevAlloc use;
     if (int rc = fr_use_to_device(b, use_ref, use)) return rc;
-    HIPOK(hipMalloc((void **)&b->d_fr, 8ull * 3u * max_size));
-    HIPOK(hipMemsetAsync(b->d_fr, 0, 8ull * 3u * max_size, b->stream));
+    HIPOK(hipMalloc(&b->fr.hist.p, 8ull * 3u * max_size));
+    HIPOK(hipMemsetAsync(b->fr.hist.p, 0, 8ull * 3u * max_size, b->stream));
     HIPOK(hipStreamSynchronize(b->stream));
-    b->d_fr_use = use.as<u8>();
-    use.p = nullptr;
-    b->fr_max = max_size;
+    b->fr.use = std::move(use);
+    b->fr.max = max_size;
     if (b->st) stream_note(*b);
     return 0;
 }
@@ -441,29 +429,30 @@ int fragments_add_impl(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, uint64_t *ro
     if (int rc = fr_check_handle(b, who)) return rc;
     if (!rows_added) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": null output");
     *rows_added = 0;
-    if (!b->fr_max) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": no table: call pmx_dbam_fragments_begin first");
+    if (!b->fr.on()) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": no table: call pmx_dbam_fragments_begin first");
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
     CxRecs R;
     u64 c[PMX_FRAGMENTS_COUNTERS];
     const double t0 = now_s();
-    if (int rc = fr_filter(b, mapq_min, flag_exclude, b->fr_max, b->d_fr_use, false, R, c)) return rc;
-    b->fr_t[0] += now_s() - t0;
+    if (int rc = fr_filter(b, mapq_min, flag_exclude, b->fr.max, b->fr.use.as<u8>(), false, R, c)) return rc;
+    b->fr.t[0] += now_s() - t0;
     if (R.n) {
         FrEvents ev;                             // (HIP events around the one kernel: pmx_dbam_fragments_timings)
         HIPOK(hipEventCreate(&ev.a));
         HIPOK(hipEventCreate(&ev.z));
         HIPOK(hipEventRecord(ev.a, st));
         const u64 grid = std::max<u64>(std::min<u64>((R.n + 1023) / 1024, FR_GRID), (R.n >> 31) + 1u);
-        hipLaunchKernelGGL(k_fr_hist, dim3((unsigned)grid), dim3(1024), 0, st, R.len.as<int>(), R.rev.as<u8>(), R.n, b->fr_max, b->d_fr);
+        hipLaunchKernelGGL(k_fr_hist, dim3((unsigned)grid), dim3(1024), 0, st, R.len.as<int>(), R.rev.as<u8>(), R.n, b->fr.max,
+                           b->fr.hist.as<unsigned long long>());
         HIPOK(hipGetLastError());
         HIPOK(hipEventRecord(ev.z, st));
         HIPOK(hipStreamSynchronize(st));         // (R is freed on return)
         float ms = 0;
         HIPOK(hipEventElapsedTime(&ms, ev.a, ev.z));
-        b->fr_t[1] += 1e-3 * (double)ms;
+        b->fr.t[1] += 1e-3 * (double)ms;
     }
-    for (u32 k = 0; k < PMX_FRAGMENTS_COUNTERS; k++) b->fr_c[k] += c[k];
+    for (u32 k = 0; k < PMX_FRAGMENTS_COUNTERS; k++) b->fr.c[k] += c[k];
     *rows_added = R.n;
     return 0;
 }
@@ -473,11 +462,11 @@ int fragments_tables_impl(pmx_dbam *b, uint64_t *hist, uint64_t *counters)
     const char *who = "pmx_dbam_fragments_tables";
     if (int rc = fr_check_handle(b, who)) return rc;
     if (!hist || !counters) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": null output");
-    if (!b->fr_max) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": no table: call pmx_dbam_fragments_begin first");
+    if (!b->fr.on()) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": no table: call pmx_dbam_fragments_begin first");
     HIPOK(hipSetDevice(b->device));
-    HIPOK(hipMemcpyAsync(hist, b->d_fr, 8ull * 3u * b->fr_max, hipMemcpyDeviceToHost, b->stream));
+    HIPOK(hipMemcpyAsync(hist, b->fr.hist.p, 8ull * 3u * b->fr.max, hipMemcpyDeviceToHost, b->stream));
     HIPOK(hipStreamSynchronize(b->stream));
-    for (u32 k = 0; k < PMX_FRAGMENTS_COUNTERS; k++) counters[k] = b->fr_c[k];
+    for (u32 k = 0; k < PMX_FRAGMENTS_COUNTERS; k++) counters[k] = b->fr.c[k];
     return 0;
 }
 
@@ -512,25 +501,26 @@ int coverage_add_fragments_impl(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, u32
     if (!added_out) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": null output");
     *added_out = 0;
     if (int rc = fr_check_size(max_size, who)) return rc;
-    if (b->cv_state != CV_TABLE) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": no table: call pmx_dbam_coverage_begin first");
-    if (b->cv_ext) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": the table was begun with an extend: begin it with 0");
+    if (!b->cv.on()) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": no table: call pmx_dbam_coverage_begin first");
+    if (b->cv.ext) return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": the table was begun with an extend: begin it with 0");
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
     CxRecs R;
     if (int rc = fr_filter(b, mapq_min, flag_exclude, max_size, nullptr, true, R, nullptr)) return rc;
     if (R.n == 0) return 0;
-    if (b->cv_reads + R.n >= CV_MAX_READS)
+    if (b->cv.reads + R.n >= CV_MAX_READS)
         return fail(PMX_DBAM_ERR_INVALID, std::string(who) + ": 2^31 reads or more: the depth is a 32-bit count");
     DevAlloc d_added;
     HIPOK(hipMalloc(&d_added.p, 8));
     HIPOK(hipMemsetAsync(d_added.p, 0, 8, st));
     hipLaunchKernelGGL(k_cv_marks, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
-                       R.rev.as<u8>(), R.n, b->d_cv_tab, (u32)b->ref_names.size(), 0u, b->d_cv, d_added.as<unsigned long long>());
+                       R.rev.as<u8>(), R.n, b->cv.tab.as<long long>(), (u32)b->ref_names.size(), 0u, b->cv.table.as<int>(),
+                       d_added.as<unsigned long long>());
     HIPOK(hipGetLastError());
     unsigned long long added = 0;
     HIPOK(hipMemcpyAsync(&added, d_added.p, 8, hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
-    b->cv_reads += added;
+    b->cv.reads += added;
     *added_out = added;
     return 0;
 }
@@ -541,56 +531,37 @@ extern "C" {
 
 int pmx_dbam_fragments_begin(pmx_dbam *b, uint32_t max_size, const uint8_t *use_ref)
 {
-    try {
-        return fragments_begin_impl(b, max_size, use_ref);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_fragments_begin: ") + e.what());
-    }
+    return guarded("pmx_dbam_fragments_begin", [&] { return fragments_begin_impl(b, max_size, use_ref); });
 }
 
 int pmx_dbam_fragments_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t *rows_added)
 {
-    try {
-        return fragments_add_impl(b, mapq_min, flag_exclude, rows_added);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_fragments_add: ") + e.what());
-    }
+    return guarded("pmx_dbam_fragments_add", [&] { return fragments_add_impl(b, mapq_min, flag_exclude, rows_added); });
 }
 
 int pmx_dbam_fragments_timings(pmx_dbam *b, double seconds[2])
 {
     if (!b || !seconds) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_fragments_timings: null argument");
-    seconds[0] = b->fr_t[0];
-    seconds[1] = b->fr_t[1];
+    seconds[0] = b->fr.t[0];
+    seconds[1] = b->fr.t[1];
     return 0;
 }
 
 int pmx_dbam_fragments_tables(pmx_dbam *b, uint64_t *hist, uint64_t counters[PMX_FRAGMENTS_COUNTERS])
 {
-    try {
-        return fragments_tables_impl(b, hist, counters);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_fragments_tables: ") + e.what());
-    }
+    return guarded("pmx_dbam_fragments_tables", [&] { return fragments_tables_impl(b, hist, counters); });
 }
 
 int64_t pmx_dbam_fragments_rows(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint32_t max_size, const uint8_t *use_ref, int64_t cap,
                                 int32_t *ref_id, int32_t *start1, int32_t *size, uint8_t *orient)
 {
-    try {
-        return fragments_rows_impl(b, mapq_min, flag_exclude, max_size, use_ref, cap, ref_id, start1, size, orient);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_fragments_rows: ") + e.what());
-    }
+    return guarded("pmx_dbam_fragments_rows",
+                   [&] { return fragments_rows_impl(b, mapq_min, flag_exclude, max_size, use_ref, cap, ref_id, start1, size, orient); });
 }
 
 int pmx_dbam_coverage_add_fragments(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint32_t max_size, uint64_t *added)
 {
-    try {
-        return coverage_add_fragments_impl(b, mapq_min, flag_exclude, max_size, added);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_coverage_add_fragments: ") + e.what());
-    }
+    return guarded("pmx_dbam_coverage_add_fragments", [&] { return coverage_add_fragments_impl(b, mapq_min, flag_exclude, max_size, added); });
 }
 
 }  // extern "C"

@@ -228,19 +228,6 @@ __global__ void __launch_bounds__(256) k_gc_reads(const int *__restrict__ ref, c
 
 namespace {
 
-void gcbias_free(pmx_dbam *b)
-{
-    for (void *p : {(void *)b->d_gc, (void *)b->d_gc_bl, (void *)b->d_gc_tab, (void *)b->d_gc_f})
-        if (p) (void)hipFree(p);
-    b->d_gc = b->d_gc_bl = nullptr;
-    b->d_gc_tab = nullptr;
-    b->d_gc_f = nullptr;
-    b->gc_w = 0;
-    b->gc_words = 0;
-    b->gc_n.clear();
-    b->gc_tot[0] = b->gc_tot[1] = b->gc_tot[2] = 0;
-}
-
 int dgc_open_impl(const char *path, int device, int nthreads, pmx_dgc **out)
 {
     if (!path || !out) return fail(PMX_DBAM_ERR_INVALID, "null argument");
@@ -278,7 +265,7 @@ int gcbias_begin_impl(pmx_dbam *b, const pmx_dgc *genome, u32 window, const uint
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
-    gcbias_free(b);
+    b->gc = GcBias{};
     if (!genome) return fail(PMX_DBAM_ERR_INVALID, who + "null genome");
     if (window == 0 || window > GC_WINDOW_MAX)
         return fail(PMX_DBAM_ERR_INVALID, who + "the window is " + std::to_string(window) + ": it must lie in [1, " +
@@ -318,32 +305,33 @@ int gcbias_begin_impl(pmx_dbam *b, const pmx_dgc *genome, u32 window, const uint
     if (int rc = rm_to_device(st, T.data(), (u64)nc + 1, d_T)) return rc;
     if (int rc = rm_to_device(st, src.data(), (u64)nc, d_src)) return rc;
     if (int rc = rm_to_device(st, rid.data(), (u64)nc, d_rid)) return rc;
-    auto get = [&](void **p, u64 bytes) -> int {
-        if (hipMalloc(p, bytes) == hipSuccess) return 0;
-        gcbias_free(b);
+    GcBias &c = b->gc;
+    auto get = [&](DevAlloc &d, u64 bytes) -> int {
+        if (hipMalloc(&d.p, bytes) == hipSuccess) return 0;
+        c = GcBias{};
         return fail(PMX_DBAM_ERR_OPEN, who + "out of device memory for the bit vectors (" + std::to_string(2 * alloc) + " bytes)");
     };
-    if (int rc = get((void **)&b->d_gc, alloc)) return rc;
-    if (int rc = get((void **)&b->d_gc_bl, alloc)) return rc;
-    if (int rc = get((void **)&b->d_gc_tab, 8 * tab.size())) return rc;
-    if (int rc = get((void **)&b->d_gc_f, 8 * nf)) return rc;
+    if (int rc = get(c.gc, alloc)) return rc;
+    if (int rc = get(c.bl, alloc)) return rc;
+    if (int rc = get(c.tab, 8 * tab.size())) return rc;
+    if (int rc = get(c.f, 8 * nf)) return rc;
     DevAlloc d_hist;
     HIPOK(hipMalloc(&d_hist.p, 8 * ((u64)window + 1u)));
     HIPOK(hipMemsetAsync(d_hist.p, 0, 8 * ((u64)window + 1u), st));
-    HIPOK(hipMemsetAsync(b->d_gc_f, 0, 8 * nf, st));
-    HIPOK(hipMemcpyAsync(b->d_gc_tab, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemsetAsync(c.f.p, 0, 8 * nf, st));
+    HIPOK(hipMemcpyAsync(c.tab.p, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_gc_bits, dim3(km_grid(nwords + GC_PAD)), dim3(256), 0, st, genome->G.P, genome->G.V, d_T.as<u64>(), d_src.as<u64>(),
-                       d_rid.as<u32>(), nc, nwords, b->d_xkey, b->d_xend, b->x_n, b->d_gc, b->d_gc_bl);
+                       d_rid.as<u32>(), nc, nwords, b->d_xkey, b->d_xend, b->x_n, c.gc.as<u64>(), c.bl.as<u64>());
     HIPOK(hipGetLastError());
     const u64 nwg = std::min<u64>((nwords + 255) / 256, GC_GRID);
-    hipLaunchKernelGGL(k_gc_windows, dim3((unsigned)nwg), dim3(256), 0, st, b->d_gc, b->d_gc_bl, nwords, window,
+    hipLaunchKernelGGL(k_gc_windows, dim3((unsigned)nwg), dim3(256), 0, st, c.gc.as<u64>(), c.bl.as<u64>(), nwords, window,
                        d_hist.as<unsigned long long>());
     HIPOK(hipGetLastError());
-    b->gc_n.assign((u64)window + 1u, 0);
-    HIPOK(hipMemcpyAsync(b->gc_n.data(), d_hist.p, 8 * ((u64)window + 1u), hipMemcpyDeviceToHost, st));
+    c.n.assign((u64)window + 1u, 0);
+    HIPOK(hipMemcpyAsync(c.n.data(), d_hist.p, 8 * ((u64)window + 1u), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));             // (the genome is not read after this; the tables above are locals)
-    b->gc_w = window;
-    b->gc_words = nwords + GC_PAD;
+    c.w = window;
+    c.words = nwords + GC_PAD;
     if (b->st) stream_note(*b);
     return 0;
 }
@@ -353,25 +341,18 @@ int gcbias_add_impl(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, uint64_t *out)
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!out) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_gcbias_add: null output");
     out[0] = out[1] = out[2] = 0;
-    if (!b->gc_w) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_gcbias_add: no table: call pmx_dbam_gcbias_begin first");
-    HIPOK(hipSetDevice(b->device));
-    hipStream_t st = b->stream;
-    CxRecs R;
-    if (int rc = cx_filter(b, mapq_min, flag_exclude, 0, true, R)) return rc;
-    if (R.n == 0) return 0;
-    DevAlloc d_cnt;
-    HIPOK(hipMalloc(&d_cnt.p, 24));
-    HIPOK(hipMemsetAsync(d_cnt.p, 0, 24, st));
-    hipLaunchKernelGGL(k_gc_reads, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
-                       R.rev.as<u8>(), R.n, b->d_gc_tab, (u32)b->ref_names.size(), b->gc_w, b->d_gc, b->d_gc_bl, b->d_gc_f,
-                       d_cnt.as<unsigned long long>());
-    HIPOK(hipGetLastError());
-    unsigned long long c[3] = {0, 0, 0};
-    HIPOK(hipMemcpyAsync(c, d_cnt.p, 24, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
+    if (!b->gc.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_gcbias_add: no table: call pmx_dbam_gcbias_begin first");
+    GcBias &c = b->gc;
+    unsigned long long cnt[3] = {0, 0, 0};
+    const int rc = side_add(b, mapq_min, flag_exclude, 3, cnt, [&](const CxRecs &R, hipStream_t st, unsigned long long *d_cnt) {
+        hipLaunchKernelGGL(k_gc_reads, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
+                           R.rev.as<u8>(), R.n, c.tab.as<long long>(), (u32)b->ref_names.size(), c.w, c.gc.as<u64>(), c.bl.as<u64>(),
+                           c.f.as<unsigned long long>(), d_cnt);
+    });
+    if (rc) return rc;
     for (int k = 0; k < 3; k++) {
-        out[k] = c[k];
-        b->gc_tot[k] += c[k];
+        out[k] = cnt[k];
+        c.tot[k] += cnt[k];
     }
     return 0;
 }
@@ -380,18 +361,18 @@ int64_t gcbias_tables_impl(pmx_dbam *b, uint64_t *windows, uint64_t *reads, int6
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!totals || (cap > 0 && (!windows || !reads))) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_gcbias_tables: null output");
-    if (!b->gc_w) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_gcbias_tables: no table: call pmx_dbam_gcbias_begin first");
-    const u64 n = (u64)b->gc_w + 1u;
+    if (!b->gc.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_gcbias_tables: no table: call pmx_dbam_gcbias_begin first");
+    const u64 n = (u64)b->gc.w + 1u;
     totals[0] = 0;
-    for (u64 v : b->gc_n) totals[0] += v;
-    totals[1] = b->gc_tot[0];
-    totals[2] = b->gc_tot[1];
-    totals[3] = b->gc_tot[2];
+    for (u64 v : b->gc.n) totals[0] += v;
+    totals[1] = b->gc.tot[0];
+    totals[2] = b->gc.tot[1];
+    totals[3] = b->gc.tot[2];
     if (cap >= (int64_t)n) {
         HIPOK(hipSetDevice(b->device));
-        HIPOK(hipMemcpyAsync(reads, b->d_gc_f, 8 * n, hipMemcpyDeviceToHost, b->stream));
+        HIPOK(hipMemcpyAsync(reads, b->gc.f.p, 8 * n, hipMemcpyDeviceToHost, b->stream));
         HIPOK(hipStreamSynchronize(b->stream));
-        for (u64 k = 0; k < n; k++) windows[k] = b->gc_n[k];
+        for (u64 k = 0; k < n; k++) windows[k] = b->gc.n[k];
     }
     return (int64_t)n;
 }
@@ -402,11 +383,7 @@ extern "C" {
 
 int pmx_dgc_open(const char *path, int device, int nthreads, pmx_dgc **out)
 {
-    try {
-        return dgc_open_impl(path, device, nthreads, out);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dgc_open: ") + e.what());
-    }
+    return guarded("pmx_dgc_open", [&] { return dgc_open_impl(path, device, nthreads, out); });
 }
 
 void pmx_dgc_close(pmx_dgc *g)
@@ -426,29 +403,17 @@ int64_t pmx_dgc_rec_len(const pmx_dgc *g, int32_t i) { return g && i >= 0 && (si
 
 int pmx_dbam_gcbias_begin(pmx_dbam *b, const pmx_dgc *genome, uint32_t window, const uint8_t *use_ref)
 {
-    try {
-        return gcbias_begin_impl(b, genome, window, use_ref);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_gcbias_begin: ") + e.what());
-    }
+    return guarded("pmx_dbam_gcbias_begin", [&] { return gcbias_begin_impl(b, genome, window, use_ref); });
 }
 
 int pmx_dbam_gcbias_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t out[3])
 {
-    try {
-        return gcbias_add_impl(b, mapq_min, flag_exclude, out);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_gcbias_add: ") + e.what());
-    }
+    return guarded("pmx_dbam_gcbias_add", [&] { return gcbias_add_impl(b, mapq_min, flag_exclude, out); });
 }
 
 int64_t pmx_dbam_gcbias_tables(pmx_dbam *b, uint64_t *windows, uint64_t *reads, int64_t cap, uint64_t totals[4])
 {
-    try {
-        return gcbias_tables_impl(b, windows, reads, cap, totals);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_gcbias_tables: ") + e.what());
-    }
+    return guarded("pmx_dbam_gcbias_tables", [&] { return gcbias_tables_impl(b, windows, reads, cap, totals); });
 }
 
 }  // extern "C"

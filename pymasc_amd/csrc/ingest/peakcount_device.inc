@@ -91,18 +91,6 @@ __global__ void __launch_bounds__(256) k_pk_count(const int *__restrict__ ref, c
 
 namespace {
 
-void peakcount_free(pmx_dbam *b)
-{
-    if (b->d_pk) (void)hipFree(b->d_pk);
-    if (b->d_pk_tab) (void)hipFree(b->d_pk_tab);
-    b->d_pk = nullptr;
-    b->d_pk_tab = nullptr;
-    b->pk_on = false;
-    b->pk_lines = b->pk_union = 0;
-    b->pk_ext = 0;
-    b->pk_tot.clear();
-}
-
 // the arrays of the table in its one block: keys, pmax (8 bytes per line each), ends, places, counts (4 each)
 struct PkView {
     u64 *key, *pmax;
@@ -116,7 +104,7 @@ int peakcount_begin_impl(pmx_dbam *b, int32_t nref, const int64_t *offsets, cons
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
-    peakcount_free(b);
+    b->pk = Peakcount{};
     RmBuilt B;
     if (int rc = rm_build(b, "pmx_dbam_peakcount_begin", nref, offsets, begin, end, B)) return rc;
     hipStream_t st = b->stream;
@@ -135,25 +123,26 @@ int peakcount_begin_impl(pmx_dbam *b, int32_t nref, const int64_t *offsets, cons
         for (u64 i = 0; i < B.merged; i++)
             if (tab[mk[i] >> 32] >= 0) uni += (u64)me[i] - (u64)(u32)mk[i];
     }
-    HIPOK(hipMalloc((void **)&b->d_pk_tab, 8 * tab.size()));
-    if (n && hipMalloc((void **)&b->d_pk, 28 * n) != hipSuccess) {
-        peakcount_free(b);
+    Peakcount &c = b->pk;
+    HIPOK(hipMalloc(&c.tab.p, 8 * tab.size()));
+    if (n && hipMalloc(&c.lines.p, 28 * n) != hipSuccess) {
+        c = Peakcount{};
         return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_peakcount_begin: out of device memory for the lines");
     }
-    HIPOK(hipMemcpyAsync(b->d_pk_tab, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemcpyAsync(c.tab.p, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, st));
     if (n) {
-        const PkView V(b->d_pk, n);
+        const PkView V(c.lines.as<u8>(), n);
         hipLaunchKernelGGL(k_pk_keep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B.skey, B.perm, B.endc.as<u32>(), B.pmax.as<u64>(), n,
                            V.key, V.pmax, V.end, V.perm);
         HIPOK(hipGetLastError());
         HIPOK(hipMemsetAsync(V.cnt, 0, 4 * n, st));
     }
     HIPOK(hipStreamSynchronize(st));       // (tab and B are locals)
-    b->pk_on = true;
-    b->pk_lines = n;
-    b->pk_union = uni;
-    b->pk_ext = extend;
-    b->pk_tot.assign(2 + 2 * std::max<u64>(nr, 1), 0);
+    c.begun = true;
+    c.n = n;
+    c.uni = uni;
+    c.ext = extend;
+    c.tot.assign(2 + 2 * std::max<u64>(nr, 1), 0);
     if (b->st) stream_note(*b);
     return 0;
 }
@@ -163,25 +152,18 @@ int peakcount_add_impl(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, uint64_t *ou
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!out) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_add: null output");
     out[0] = out[1] = 0;
-    if (!b->pk_on) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_add: no table: call pmx_dbam_peakcount_begin first");
-    HIPOK(hipSetDevice(b->device));
-    hipStream_t st = b->stream;
-    CxRecs R;
-    if (int rc = cx_filter(b, mapq_min, flag_exclude, 0, true, R)) return rc;
-    if (R.n == 0) return 0;
-    const u64 nt = b->pk_tot.size();
-    DevAlloc d_tot;
-    HIPOK(hipMalloc(&d_tot.p, 8 * nt));
-    HIPOK(hipMemsetAsync(d_tot.p, 0, 8 * nt, st));
-    const PkView V(b->d_pk, b->pk_lines);
-    hipLaunchKernelGGL(k_pk_count, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
-                       R.rev.as<u8>(), R.n, b->d_pk_tab, (u32)b->ref_names.size(), b->pk_ext, V.key, V.end, V.pmax, V.perm, b->pk_lines,
-                       V.cnt, d_tot.as<unsigned long long>());
-    HIPOK(hipGetLastError());
-    std::vector<unsigned long long> tot(nt);
-    HIPOK(hipMemcpyAsync(tot.data(), d_tot.p, 8 * nt, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    for (u64 k = 0; k < nt; k++) b->pk_tot[k] += tot[k];
+    if (!b->pk.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_add: no table: call pmx_dbam_peakcount_begin first");
+    Peakcount &c = b->pk;
+    const u64 nt = c.tot.size();
+    std::vector<unsigned long long> tot(nt, 0);
+    const int rc = side_add(b, mapq_min, flag_exclude, nt, tot.data(), [&](const CxRecs &R, hipStream_t st, unsigned long long *d_tot) {
+        const PkView V(c.lines.as<u8>(), c.n);
+        hipLaunchKernelGGL(k_pk_count, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, R.ref.as<int>(), R.pos.as<int>(), R.len.as<int>(),
+                           R.rev.as<u8>(), R.n, c.tab.as<long long>(), (u32)b->ref_names.size(), c.ext, V.key, V.end, V.pmax, V.perm, c.n, V.cnt,
+                           d_tot);
+    });
+    if (rc) return rc;
+    for (u64 k = 0; k < nt; k++) c.tot[k] += tot[k];
     out[0] = tot[0];
     out[1] = tot[1];
     return 0;
@@ -191,12 +173,12 @@ int peakcount_copy_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t *counts)
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!counts) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_copy: null output");
-    if (!b->pk_on) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_copy: no table: call pmx_dbam_peakcount_begin first");
-    if (first < 0 || n < 0 || (u64)first > b->pk_lines || (u64)n > b->pk_lines - (u64)first)
+    if (!b->pk.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_copy: no table: call pmx_dbam_peakcount_begin first");
+    if (first < 0 || n < 0 || (u64)first > b->pk.n || (u64)n > b->pk.n - (u64)first)
         return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_copy: range outside the table");
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
-    if (n) HIPOK(hipMemcpy(counts, PkView(b->d_pk, b->pk_lines).cnt + first, 4 * (u64)n, hipMemcpyDeviceToHost));
+    if (n) HIPOK(hipMemcpy(counts, PkView(b->pk.lines.as<u8>(), b->pk.n).cnt + first, 4 * (u64)n, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -204,12 +186,12 @@ int peakcount_totals_impl(pmx_dbam *b, uint64_t *totals, uint64_t *per_ref)
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!totals || !per_ref) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_totals: null output");
-    if (!b->pk_on) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_totals: no table: call pmx_dbam_peakcount_begin first");
-    totals[0] = b->pk_tot[0];
-    totals[1] = b->pk_tot[1];
-    totals[2] = b->pk_union;
-    totals[3] = b->pk_lines;
-    for (u64 k = 0; k < 2 * b->ref_names.size(); k++) per_ref[k] = b->pk_tot[2 + k];
+    if (!b->pk.on()) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_peakcount_totals: no table: call pmx_dbam_peakcount_begin first");
+    totals[0] = b->pk.tot[0];
+    totals[1] = b->pk.tot[1];
+    totals[2] = b->pk.uni;
+    totals[3] = b->pk.n;
+    for (u64 k = 0; k < 2 * b->ref_names.size(); k++) per_ref[k] = b->pk.tot[2 + k];
     return 0;
 }
 
@@ -220,38 +202,22 @@ extern "C" {
 int pmx_dbam_peakcount_begin(pmx_dbam *b, int32_t nref, const int64_t *offsets, const uint32_t *begin, const uint32_t *end,
                              uint32_t extend, const uint8_t *use_ref)
 {
-    try {
-        return peakcount_begin_impl(b, nref, offsets, begin, end, extend, use_ref);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_peakcount_begin: ") + e.what());
-    }
+    return guarded("pmx_dbam_peakcount_begin", [&] { return peakcount_begin_impl(b, nref, offsets, begin, end, extend, use_ref); });
 }
 
 int pmx_dbam_peakcount_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t out[2])
 {
-    try {
-        return peakcount_add_impl(b, mapq_min, flag_exclude, out);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_peakcount_add: ") + e.what());
-    }
+    return guarded("pmx_dbam_peakcount_add", [&] { return peakcount_add_impl(b, mapq_min, flag_exclude, out); });
 }
 
 int pmx_dbam_peakcount_copy(pmx_dbam *b, int64_t first, int64_t n, uint32_t *counts)
 {
-    try {
-        return peakcount_copy_impl(b, first, n, counts);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_peakcount_copy: ") + e.what());
-    }
+    return guarded("pmx_dbam_peakcount_copy", [&] { return peakcount_copy_impl(b, first, n, counts); });
 }
 
 int pmx_dbam_peakcount_totals(pmx_dbam *b, uint64_t totals[4], uint64_t *per_ref)
 {
-    try {
-        return peakcount_totals_impl(b, totals, per_ref);
-    } catch (const std::exception &e) {
-        return fail(PMX_DBAM_ERR_OPEN, std::string("pmx_dbam_peakcount_totals: ") + e.what());
-    }
+    return guarded("pmx_dbam_peakcount_totals", [&] { return peakcount_totals_impl(b, totals, per_ref); });
 }
 
 }  // extern "C"
