@@ -335,6 +335,16 @@ int pmx_debug_poison(pmx_ctx *ctx, uint32_t pattern, uint32_t mask);
  * workgroup many tiles: the paths that depend on a workgroup's tile count (histogram flushes before a 16-bit cell can
  * overflow, job changes inside a range) are then checked against the oracle at sizes it finishes.  No effect on results. */
 int pmx_debug_set_max_workgroups(pmx_ctx *ctx, uint32_t n);
+/* How the hinted event kernel (max_shift <= 1023) hands the tiles of later launches to its workgroups.  0 (default): every
+ * workgroup draws the tiles of its own range and, at the end, tiles that others of its chromosome have not started; 1: the
+ * workgroups with an odd index draw nothing as owners, so that every tile of their ranges but the first per chromosome is
+ * taken through the helping path; 2: nobody helps -- the static walk.  No effect on results. */
+int pmx_debug_set_claim_mode(pmx_ctx *ctx, uint32_t mode);
+/* Copies what the last event pass of max_shift <= 1023 left in its flag area to host memory (after a synchronisation), at
+ * most `cap` bytes, and stores their number in *bytes: the dense-tile flags of the cross-correlation window kernel, those of
+ * the autocorrelation window kernel (equally long), 16 bytes of flagged-tile counters, the job statistics, and the claim
+ * counters -- (compute units x 8 + 32) words, rounded up to 16 bytes -- at the end. */
+int pmx_debug_read_flag_area(pmx_ctx *ctx, void *dst, uint64_t cap, uint64_t *bytes);
 /* Copies `bytes` from byte offset `off` of the event / window kernels' slab to host memory (phase stamps of the
  * diagnostic builds -DEV_STAMPS / -DSP_STAMPS). */
 int pmx_debug_read_slab(pmx_ctx *ctx, uint64_t off, void *dst, uint64_t bytes);

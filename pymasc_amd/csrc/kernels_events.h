@@ -458,6 +458,61 @@ __device__ __forceinline__ void ev_zero_row5(u32 *__restrict__ slab, u32 segment
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ---- claimed tiles (the KNOWN_SPARSE instantiations with a track, DEEP among them) -----------------------------------
+// The static cut of the tile sequence into ranges of tiles_per_wg stays, but a range is no longer walked: its tiles are CLAIMED,
+// so that a workgroup that has run out of its own can take tiles others have not started.  A PIECE is a workgroup's range
+// inside one job (v, job); it has one counter, claim[v + job] -- the injective index of the slab segments --, zero at launch.
+//   * the FIRST tile of a piece is its owner's without a claim: every (workgroup, job) pair of today processes a tile of its
+//     job, so it writes its slab segment exactly as it does today (k_events_finish sums wg_first .. wg_last of a job);
+//   * tile pstart + k, pstart = first tile + 1, belongs to whoever draws k = atomicAdd(&claim[v + job], 1) < plen;
+//   * the owner draws from its own pieces in job order -- the tiles it walks today, in today's order;
+//   * when the piece of its LAST job is exhausted the workgroup stays in that job (histograms, segment and flushes are what
+//     they were) and HELPS: wave 0 reads the counters of the job's pieces, 64 per load, from the piece behind its own round
+//     to its own, takes the first that has tiles left and draws from it; a scan that finds none ends the workgroup.
+// A helper never enters a job it holds no piece of: blockIdx + job stays injective, and a workgroup flushes as often as today.
+// Results are sums over tiles, so who takes a tile cannot change them.
+// mode (pmx_debug_set_claim_mode), read once per workgroup: 1 = workgroups with an odd index draw nothing as owners and
+// help in EVERY job of theirs (all tiles of their pieces but the first go through the helping path, whoever takes them);
+// 2 = nobody helps (the static walk, with the claims' bookkeeping).
+#define EV_NO_TILE 0xffffffffu
+#define EV_CLAIM_JOB_SHIFT 24u   // a claimed tile travels as tile | job << 24 (at most 32 jobs of < 2^16 tiles: 2^21 tiles)
+struct EvClaimer {
+    u32 cj, jl;                // job being drawn from, the last job of my range
+    u32 v, pstart, plen;       // the piece being drawn from: its workgroup, its first claimable tile, their number
+    bool valid;                // ... holds (else: look for another)
+    bool help_all, help_none;  // modes 1 (odd workgroups) and 2
+};
+
+// (wave 0, all lanes, uniform) the pieces of job c.cj with tiles left -> c.v / c.pstart / c.plen.  The counters are read past
+// the L1 (another CU's adds are made in the L2 / at the memory side: a line kept here would show an exhausted piece as open forever).
+// (the job's fields come by value: see FIRST_JOB on tables handed to helpers by reference)
+__device__ __forceinline__ bool ev_claim_scan(EvClaimer &c, u32 wf, u32 wl, u32 t0, u32 te, const u32 *claim, u32 tiles_per_wg, u32 lane)
+{
+    const u32 n = wl - wf + 1;
+    const u32 s = blockIdx.x + 1 > wl ? 0u : blockIdx.x + 1 - wf;   // the piece behind mine (round to the first)
+    for (u32 base = 0; base < n; base += 64) {
+        const u32 idx = base + lane;
+        const bool in = idx < n;
+        u32 u = s + idx;
+        u = u >= n ? u - n : u;
+        const u32 pv = wf + (in ? u : 0u);
+        const u32 lo = pv * tiles_per_wg > t0 ? pv * tiles_per_wg : t0;
+        const u32 hi = (pv + 1) * tiles_per_wg < te ? (pv + 1) * tiles_per_wg : te;
+        const u32 len = hi - lo - 1;   // (the piece's first tile is its owner's)
+        u32 cnt = EV_NO_TILE;
+        if (in) cnt = __hip_atomic_load(claim + pv + c.cj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long open = __ballot(in && cnt < len);
+        if (open) {
+            const int f = __builtin_ctzll(open);
+            c.v = (u32)__builtin_amdgcn_readlane((int)pv, f);
+            c.pstart = (u32)__builtin_amdgcn_readlane((int)lo, f) + 1u;
+            c.plen = (u32)__builtin_amdgcn_readlane((int)len, f);
+            return true;
+        }
+    }
+    return false;
+}
+
 // slab segment of a (workgroup, job) pair: EV_SEG_ROWS rows of `hn` u32: ncc, GF, cc, GR, scalars (|F|, |R|, Bf, R0,
 // popcount(M), runs), EE
 // DO_MLEN: also the pairs of run edges (the mappable-length autocorrelation, see k_autocorr_pairs): EE[k] = sum of
@@ -475,9 +530,15 @@ template <bool HAS_M, bool DO_NCC, bool DO_MLEN, u32 NSG, bool BIG, typename JT 
 __global__ void __launch_bounds__(256 * NSG, BIG ? 4 : (HAS_M ? (DEEP ? 4 : EV_WAVES) : EV_WAVES_NCC))
 k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, u32 S, u32 nhr, u32 max_lag,
             u32 hn_arg, u32 lo_arg, u32 hi_arg, u32 *__restrict__ slab, unsigned char *__restrict__ tile_flags,
-            unsigned char *__restrict__ tile_flags_ac, u32 *__restrict__ n_flagged, u32 *__restrict__ jobstat)
+            unsigned char *__restrict__ tile_flags_ac, u32 *__restrict__ n_flagged, u32 *__restrict__ jobstat,
+            u32 *__restrict__ claim, u32 claim_mode)
 {
     typedef EvLds<HAS_M, BIG, DEEP> L;
+    // tiles are claimed, not walked (see EvClaimer); `claim` and `claim_mode` are theirs alone.  With a track only: the NCC-only
+    // instantiation runs eight workgroups per CU at a throughput that hardly depends on how many of them are left (8.1: 0.202 /
+    // 0.197 ms at 7 / 8 per CU), so a workgroup that leaves hands its share to its neighbours anyway, and helping measured
+    // +5 % on `--mode ncc` (the bookkeeping alone +1 %): it keeps the walk.
+    constexpr bool CLAIMS = KNOWN_SPARSE && HAS_M;
     static_assert(!DEEP || (HAS_M && !BIG), "DEEP: the max_shift <= 1023 instantiations with a track");
     static_assert(BIG || NSG == 1, "the max_shift <= 1023 instantiations are one sub-group per workgroup");
     static_assert(!KNOWN_SPARSE || !BIG, "KNOWN_SPARSE: the max_shift <= 1023 instantiations");
@@ -515,12 +576,10 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
     const u32 g0 = blockIdx.x * tiles_per_wg;
     const u32 g1 = g0 + tiles_per_wg < total_tiles ? g0 + tiles_per_wg : total_tiles;
     if (g0 >= g1) return;
-    {
-#pragma nounroll
-        for (u32 i = gt; i < L::o_sg(HN); i += NT) lds[i] = 0;
-        if (EE_LDS)
-            for (u32 i = gt; i < HN / 2; i += NT) hEEb[i] = 0;
-    }
+#ifdef EV_STAMPS   // the workgroup's start on the constant 100 MHz clock, which the XCDs share (their shader clocks are their own)
+    unsigned long long stamp_t0;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_t0)::"memory");
+#endif
 
     FIRST_JOB(ji, JT, jobs, njobs, g0)
     u32 jn = ji;
@@ -536,6 +595,62 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
         act_var = g0 + sg < lim;
     }
     if (NSG == 1 || act_var) ev_fetch_job<HAS_M, BIG>(er, pj, g0 + sg - pj.tile0, tid_, nhr, LO, false, wave, HI);
+    {   // the histograms are cleared BEHIND the first tile's loads, while they are in flight (B0 follows)
+#pragma nounroll
+        for (u32 i = gt; i < L::o_sg(HN); i += NT) lds[i] = 0;
+        if (EE_LDS)
+            for (u32 i = gt; i < HN / 2; i += NT) hEEb[i] = 0;
+    }
+    // CLAIMS (see EvClaimer).  Wave 0 draws the next tile behind Bs, while the lists of tile g are emitted, and hands it over in
+    // xch[2] in front of B1: the draw's round trip has the emit.  The prefetch is issued behind B1, into
+    // the registers the emit has freed, and has the event loops to arrive.  A workgroup thus holds ONE tile beyond the one it
+    // works on: when a job's pieces run out, everybody is at most two tiles from its end (a draw a tile earlier, with the
+    // prefetch in front of B1, left three, and the tail of a job is what this is about).
+    EvClaimer cl;
+    u32 cl_next = EV_NO_TILE;                          // (uniform) tile | job << 24
+    u32 cl_draw = 0;                                   // wave 0, lane 0: the counter's value of the draw in flight
+    bool cl_drawn = false;                             // (uniform, wave 0) ... there is one
+    // (a lambda, not a helper with the table by reference: see FIRST_JOB)
+    auto claim_next = [&]() -> u32 {
+        const u32 lane0 = tid_ & 63u;
+        for (;;) {
+            if (cl.cj > cl.jl) return EV_NO_TILE;
+            if (cl.valid) {
+                u32 k = 0;
+                if (lane0 == 0) k = __hip_atomic_fetch_add(claim + cl.v + cl.cj, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                k = __builtin_amdgcn_readfirstlane(k);
+                if (k < cl.plen) return (cl.pstart + k) | (cl.cj << EV_CLAIM_JOB_SHIFT);
+                cl.valid = false;
+            }
+            if (!cl.help_none && (cl.help_all || cl.cj == cl.jl)) {
+                const u32 t0 = jobs.j[cl.cj].tile0;
+                if (ev_claim_scan(cl, jobs.j[cl.cj].wg_first, jobs.j[cl.cj].wg_last, t0, t0 + jobs.j[cl.cj].ntiles, claim, tiles_per_wg, lane0)) {
+                    cl.valid = true;
+                    continue;
+                }
+            }
+            // my piece of the next job: its first tile is mine as it stands
+            cl.cj++;
+            if (cl.cj > cl.jl) return EV_NO_TILE;
+            const u32 t0 = jobs.j[cl.cj].tile0, te = t0 + jobs.j[cl.cj].ntiles;
+            cl.v = blockIdx.x;
+            cl.pstart = t0 + 1;
+            cl.plen = (te < g1 ? te : g1) - t0 - 1;
+            cl.valid = !cl.help_all;
+            return t0 | (cl.cj << EV_CLAIM_JOB_SHIFT);
+        }
+    };
+    if (CLAIMS) {
+        cl.cj = ji;
+        cl.jl = ji;
+        while (cl.jl + 1 < njobs && jobs.j[cl.jl + 1].tile0 < g1) cl.jl++;
+        cl.help_all = claim_mode == 1 && (blockIdx.x & 1u);
+        cl.help_none = claim_mode == 2;
+        cl.v = blockIdx.x;             // my piece of the first job: tile g0 is mine as it stands
+        cl.pstart = g0 + 1;
+        cl.plen = (pj.tile_end < g1 ? pj.tile_end : g1) - g0 - 1;
+        cl.valid = !cl.help_all;
+    }
     // Read-dense stretches (deep data: every tile far above the list capacities): after two such tiles in a row the
     // workgroup hands the REST of its tile range in this chromosome to the window kernels in one go (flags only, nothing
     // staged): the event kernel then costs two tiles per workgroup instead of a wasted pass over everything.  (NSG == 1)
@@ -565,7 +680,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last)::"memory");
 #endif
 
-    for (u32 g = g0; g < g1;) {
+    for (u32 g = g0; CLAIMS ? g != EV_NO_TILE : g < g1;) {
         const bool act = NSG == 1 ? true : act_var;   // (uniform over the sub-group)
         EV_STAMP(9)
         __syncthreads();   // B0: every wave is done with the previous tile's lists and M words
@@ -633,10 +748,19 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
         EV_STAMP(1)
         __syncthreads();   // Bs
         EV_STAMP(2)
+        // The draw for the tile this iteration prefetches, resolved in front of B1.  Issued HERE, behind the last use of the
+        // prefetched registers: the vector memory counter is in order, and the waits for those loads are computed for the waves
+        // that issue no draw -- behind B0, wave 0 waited for its draw's round trip (1-3 us) at the first popcount of every tile,
+        // and the other waves for wave 0 at Bs (measured: +3.5 % on the step with helping off).
+        if (CLAIMS && wave == 0) {
+            cl_drawn = cl.valid;
+            if (cl_drawn && (tid_ & 63u) == 0)
+                cl_draw = __hip_atomic_fetch_add(claim + cl.v + cl.cj, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         u32 nF = 0, nRt = 0, nR = 0, nE = 0, TXb = 0, TE0 = 0, TE1 = 0;
         bool dense = false, do_edges = false;
         u32 *LR = LF, *LE = LF;
-        u32 gnext = g + NSG;
+        u32 gnext = CLAIMS ? EV_NO_TILE : g + NSG;   // (CLAIMS: known behind B1)
         if (act) {
             u32 bF = 0, bR = 0, bH = 0, bE = 0, bX = 0, tF = 0, tR = 0, tH = 0, tE = 0, tX = 0;
             if (!BIG) {
@@ -862,7 +986,16 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
         // later, at no cost; atomics queued behind the loads were waited for at every barrier of the next tile: +22 %)
         constexpr bool LATE_FETCH = BIG && DO_MLEN;
         auto prefetch_next = [&]() {
-            if (gnext < g1) {
+            if (CLAIMS) {   // the claimed tile and its job (one of mine: the same or a later one)
+                if (gnext != EV_NO_TILE) {
+                    const u32 j = cl_next >> EV_CLAIM_JOB_SHIFT;
+                    if (j != jn) {
+                        jn = j;
+                        load_job(pj, jobs.j[jn]);
+                    }
+                    ev_fetch_job<HAS_M, BIG>(er, pj, gnext - pj.tile0, tid, nhr, LO, false, wave, HI);
+                }
+            } else if (gnext < g1) {
                 if (gnext >= pj.tile_end) {   // rare: the next tile belongs to the next job
                     jn = ji + 1;
                     load_job(pj, jobs.j[jn]);
@@ -877,10 +1010,28 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                 act_var = false;
             }
         };
-        if (!LATE_FETCH) prefetch_next();
+        if (!LATE_FETCH && !CLAIMS) prefetch_next();
+        if (CLAIMS && wave == 0) {
+            // the draw issued behind Bs has had the emit
+            u32 t = EV_NO_TILE;
+            bool got = false;
+            if (cl_drawn) {
+                const u32 k = __builtin_amdgcn_readfirstlane(cl_draw);
+                got = k < cl.plen;
+                if (got) t = (cl.pstart + k) | (cl.cj << EV_CLAIM_JOB_SHIFT);
+                else cl.valid = false;   // the piece is exhausted
+            }
+            if (!got) t = claim_next();   // (rare) another piece, my next job, or the end
+            if ((tid_ & 63u) == 0) xch[2] = t;
+        }
         EV_STAMP(4)
         if (EV_PRIO_STAGE) __builtin_amdgcn_s_setprio(0);
         __syncthreads();   // B1: lists, M words and edge ranks visible
+        if (CLAIMS) {
+            cl_next = __builtin_amdgcn_readfirstlane(xch[2]);
+            gnext = cl_next == EV_NO_TILE ? EV_NO_TILE : cl_next & ((1u << EV_CLAIM_JOB_SHIFT) - 1u);
+            prefetch_next();
+        }
         // (tried on top, same-box A/B: the two waves with two pair blocks one level above the others: 0.400 -> 0.412; the two
         // priorities exchanged in every other "layer" of 256 / 8 / 1 workgroups: +-0)
         if (EV_PRIO_EVENTS) __builtin_amdgcn_s_setprio(EV_PRIO_EVENTS);
@@ -1138,7 +1289,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
             accR = __builtin_amdgcn_readfirstlane(accR);
             accE = __builtin_amdgcn_readfirstlane(accE);
         }
-        const bool leaving = jn != ji || gnext >= g1;
+        const bool leaving = jn != ji || (CLAIMS ? gnext == EV_NO_TILE : gnext >= g1);
         // another iteration could overflow a 16-bit cell (bounds in the comment of EvLds): flush now
         // (EE_LDS: a cell of the row of lags takes at most one pair per listed edge)
         const bool risk = HAS_M && (BIG ? (accF + NSG * EV_CAPF > 32767u || 3u * (accR + NSG * EV_CAPR) > 32767u ||
@@ -1398,6 +1549,8 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
         g = gnext;
     }
 #ifdef EV_STAMPS
+    stamp_acc[10] = stamp_t0;   // slots 10 and 11: the workgroup's start and end (tools_ev_stamps.py reads wave 0's)
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_acc[11])::"memory");
     if ((gt & 63) == 0) {
         unsigned long long *dbg = reinterpret_cast<unsigned long long *>(slab + (size_t)(gridDim.x + njobs) * EV_SEG_ROWS * HN);
         for (int i = 0; i < EV_NSTAMP; i++) dbg[((size_t)blockIdx.x * 4 * NSG + (gt >> 6)) * EV_NSTAMP + i] = stamp_acc[i];

@@ -2497,7 +2497,7 @@ static int ev_big_launch(pmx_ctx *ctx, const EvBigPlan &pl, const SpJobTableRef 
     }
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(256 * NSG), pl.lds_bytes, ctx->stream, tab, n, total, tpw, c, max_shift, nhr, fused_lag,
                        pl.hn, pl.lo, pl.hi | (DO_MLEN && pl.ee_lds ? 1u << 16 : 0u), ctx->d_slab, d_flags, d_flags_ac ? d_flags_ac : d_flags, d_nflagged,
-                       d_jobstat);
+                       d_jobstat, (u32 *)nullptr, 0u);
     PMX_CHECK_LAUNCH("k_cc_events (max_shift > 1023)");
     return PMX_OK;
 }
@@ -2795,7 +2795,11 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
             return PMX_ERR_INVALID;
         }
     unsigned char *d_flags = nullptr, *d_flags_ac = nullptr;
-    u32 *d_nflagged = nullptr, *d_plan_cc = nullptr, *d_plan_ac = nullptr, *d_jobstat = nullptr;
+    u32 *d_nflagged = nullptr, *d_plan_cc = nullptr, *d_plan_ac = nullptr, *d_jobstat = nullptr, *d_claim = nullptr;
+    // the claim counters of the event kernel's pieces (kernels_events.h, EvClaimer): one word per (workgroup, job) index, behind
+    // the job statistics in the flag area -- zero at launch like everything there, cleared by the next pass's k_events_finish
+    const size_t claim_words = (size_t)ctx->num_cus * 8 + SP_MAXJOBS;   // (a launch is at most EV_WAVES_NCC workgroups per CU)
+    const size_t claim_bytes = (claim_words * sizeof(u32) + 15) / 16 * 16;
     size_t flag_bytes_all = 0;     // raw length of a flag array (multiple of 16)
     unsigned char *d_other_area = nullptr;   // the context's other flag area: cleared by this pass's k_events_finish
     size_t other_dirty = 0;
@@ -2807,7 +2811,7 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
         }
         const size_t flag_bytes = (size_t)((total_flags + 15) / 16 * 16);
         const size_t stat_bytes = EV_STAT_BYTES;   // job statistics + the chromosomes' scalar totals
-        const size_t zero_bytes = 2 * flag_bytes + 16 + stat_bytes;   // (a multiple of 16)
+        const size_t zero_bytes = 2 * flag_bytes + 16 + stat_bytes + claim_bytes;   // (a multiple of 16)
         unsigned char *area = nullptr;
         int rc = ev_flag_area(ctx, zero_bytes + 2 * PLAN_WORDS * sizeof(u32), zero_bytes, &area, &d_other_area, &other_dirty);
         if (rc) return rc;
@@ -2816,7 +2820,8 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
         d_nflagged = (u32 *)(area + 2 * flag_bytes);
         d_jobstat = (u32 *)(area + 2 * flag_bytes + 16);   // per job: tiles seen / read-dense / edge-dense (k_cc_events)
         flag_bytes_all = flag_bytes;
-        d_plan_cc = (u32 *)((unsigned char *)d_jobstat + stat_bytes);   // work split of the two window launches (k_events_finish)
+        d_claim = (u32 *)((unsigned char *)d_jobstat + stat_bytes);
+        d_plan_cc = (u32 *)((unsigned char *)d_claim + claim_bytes);   // work split of the two window launches (k_events_finish)
         d_plan_ac = d_plan_cc + PLAN_WORDS;
         if (fuse_mlen) fused->done = true;   // row MLEN and scalar [2] are written by this call (k_events_finish)
     }
@@ -2836,7 +2841,7 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
         if (use_events) {
             memset(&tab, 0, sizeof tab);
             // (the next 32 jobs: their own flagged-tile counters and job statistics)
-            if (lo) PMX_HIP(hipMemsetAsync(d_nflagged, 0, 16 + EV_STAT_BYTES, ctx->stream));
+            if (lo) PMX_HIP(hipMemsetAsync(d_nflagged, 0, 16 + EV_STAT_BYTES + claim_bytes, ctx->stream));   // (and claim counters)
             const bool deep = has_m && ctx->deep_lists;   // PMX_FLAG_DEEP_LISTS: the larger list pool at four workgroups per CU
             // the caller's hint, or the density probe's: the instantiations without the job-wide verdict on dense chromosomes
             const bool known = ctx->known_sparse;
@@ -2859,12 +2864,17 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
             for (uint32_t i = 0; i < n; i++) vjobs[lo + i].ranged = false;
             rc = pmx_ensure_slab(ctx, (size_t)(nwg + n) * EV_SEG_ROWS * 1024 + (size_t)nwg * 4 * 12 * 2 + 64);
             if (rc) return rc;
+            if (known && has_m && ((size_t)nwg + n > claim_words || total >= (1u << EV_CLAIM_JOB_SHIFT))) {   // (the launches that claim)
+                pmx_set_error("k_cc_events: %u workgroups + %u jobs, %u tiles exceed the claim counters", nwg, n, total);
+                return PMX_ERR_INVALID;
+            }
             rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_EVENTS, &tl);
             if (rc) return rc;
             const u32 nhr = (max_shift + 1 + 127) / 128;   // quads of R above a tile that hold partners of its forward reads
 #define EV_LAUNCH__(HM, NC, ML, DP, KS)                                                                                \
     hipLaunchKernelGGL((k_cc_events<HM, NC, ML, 1, false, SpJobTable, DP, KS>), dim3(nwg), dim3(256), 0, ctx->stream, tab, n, total, tpw, \
-                       (u32)c, max_shift, nhr, fused_lag, 1024u, (u32)EV_LO, (u32)EV_HI, ctx->d_slab, d_flags, d_flags_ac, d_nflagged, d_jobstat)
+                       (u32)c, max_shift, nhr, fused_lag, 1024u, (u32)EV_LO, (u32)EV_HI, ctx->d_slab, d_flags, d_flags_ac, d_nflagged, d_jobstat, \
+                       d_claim, ctx->debug_claim_mode)
 #define EV_LAUNCH_(HM, NC, ML, DP)                \
     do {                                          \
         if (known) EV_LAUNCH__(HM, NC, ML, DP, true); \

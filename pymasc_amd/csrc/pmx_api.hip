@@ -75,6 +75,7 @@ int pmx_ctx_create(int device, void *hip_stream, pmx_ctx **out)
     ctx->deep_lists = false;
     ctx->known_sparse = false;
     ctx->debug_max_wg = 0;
+    ctx->debug_claim_mode = 0;
     ctx->d_scratch = nullptr;
     ctx->scratch_words = 0;
     ctx->d_slab = nullptr;
@@ -582,6 +583,27 @@ int pmx_debug_set_max_workgroups(pmx_ctx *ctx, uint32_t n)
 {
     REQUIRE(ctx, "pmx_debug_set_max_workgroups: ctx is NULL");
     ctx->debug_max_wg = n;
+    return PMX_OK;
+}
+
+int pmx_debug_set_claim_mode(pmx_ctx *ctx, uint32_t mode)
+{
+    REQUIRE(ctx, "pmx_debug_set_claim_mode: ctx is NULL");
+    REQUIRE(mode <= 2, "pmx_debug_set_claim_mode: mode is 0, 1 or 2");
+    ctx->debug_claim_mode = mode;
+    return PMX_OK;
+}
+
+int pmx_debug_read_flag_area(pmx_ctx *ctx, void *dst, uint64_t cap, uint64_t *bytes)
+{
+    REQUIRE(ctx && dst && bytes, "pmx_debug_read_flag_area: NULL argument");
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    const uint32_t used = (ctx->flags_cc_area ^ 1u) & 1u;   // (flags_cc_area names the NEXT pass's area)
+    const size_t n = ctx->d_flags_cc ? ctx->flags_cc_dirty[used] : 0;
+    REQUIRE(n <= cap, "pmx_debug_read_flag_area: the buffer is too small");
+    const size_t stride = (ctx->flags_cc_bytes / 2) & ~(size_t)255;
+    if (n) PMX_HIP(hipMemcpy(dst, ctx->d_flags_cc + used * stride, n, hipMemcpyDeviceToHost));
+    *bytes = n;
     return PMX_OK;
 }
 

@@ -69,6 +69,7 @@ struct pmx_ctx {
     bool deep_lists;             // PMX_FLAG_DEEP_LISTS of the call in progress
     bool known_sparse;           // ... its data is known to fit the event kernel's lists (a hint, or the density probe): no job-wide verdict
     uint32_t debug_max_wg;       // 0: off; tests: cap on the persistent workgroups of a launch (many tiles per workgroup on small inputs)
+    uint32_t debug_claim_mode;   // 0: off; tests and A/B runs: how the hinted event kernel hands out tiles (pmx_debug_set_claim_mode)
     int profiling;               // 0 off; 1: kernels that do work; 2: also the (usually empty) fallback launches behind the event kernel
     std::vector<pmx_timed_launch> timed;       // launches not yet folded into the totals
     std::vector<hipEvent_t> event_pool;

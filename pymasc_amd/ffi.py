@@ -62,7 +62,8 @@ EXPORTS = [
     "pmx_cc_dev", "pmx_cc_batch_dev", "pmx_cc_batch_ranges_dev", "pmx_calc_correlation", "pmx_mappable_len_dev", "pmx_mappable_len",
     "pmx_mappable_len_batch_dev",
     "pmx_ctx_set_profiling", "pmx_ctx_reset_kernel_times", "pmx_ctx_kernel_time", "pmx_kernel_name",
-    "pmx_debug_poison", "pmx_debug_read_slab", "pmx_debug_set_max_workgroups",
+    "pmx_debug_poison", "pmx_debug_read_slab", "pmx_debug_set_max_workgroups", "pmx_debug_set_claim_mode",
+    "pmx_debug_read_flag_area",
 ]
 
 
@@ -131,6 +132,8 @@ def load_library(path: Optional[str] = None):
     L.pmx_debug_poison.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
     L.pmx_debug_read_slab.argtypes = [vp, u64, vp, u64]
     L.pmx_debug_set_max_workgroups.argtypes = [vp, ctypes.c_uint32]
+    L.pmx_debug_set_claim_mode.argtypes = [vp, ctypes.c_uint32]
+    L.pmx_debug_read_flag_area.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("pmx_version",):
@@ -603,6 +606,18 @@ class Context:
     def debug_set_max_workgroups(self, n: int) -> None:
         """Diagnostic: cap the persistent workgroups of later launches (0: off), see include/pymasc_amd.h."""
         _check(self._L, self._L.pmx_debug_set_max_workgroups(self._h, int(n)))
+
+    def debug_set_claim_mode(self, mode: int) -> None:
+        """Diagnostic: how the hinted event kernel hands out tiles (0: claims + helping, 1: odd workgroups help only,
+        2: the static walk), see include/pymasc_amd.h."""
+        _check(self._L, self._L.pmx_debug_set_claim_mode(self._h, int(mode)))
+
+    def debug_read_flag_area(self, cap: int = 1 << 22) -> np.ndarray:
+        """Diagnostic: the bytes the last event pass of max_shift <= 1023 left in its flag area (see include/pymasc_amd.h)."""
+        buf = np.zeros(cap, dtype=np.uint8)
+        n = ctypes.c_uint64(0)
+        _check(self._L, self._L.pmx_debug_read_flag_area(self._h, buf.ctypes.data, cap, ctypes.byref(n)))
+        return buf[:int(n.value)].copy()
 
     def kernel_name(self, kernel_id: int) -> str:
         return self._L.pmx_kernel_name(int(kernel_id)).decode()

@@ -182,13 +182,17 @@ def main():
                                              full_range=full)
             skip_ncc = with_m and rng.random() < 0.2
             ref = oracle.calc_correlation(F, R, M, nbits, S, L, skip_ncc=skip_ncc)
+            # every other case: two to five workgroups, the odd ones drawing their tiles through the helping path (claim mode 1)
+            helping = (n & 1) == 1
+            ctx.debug_set_claim_mode(1 if helping else 0)
+            ctx.debug_set_max_workgroups(2 + (n >> 1) % 4 if helping else 0)
             for flags in (0, ffi.PMX_FLAG_FORCE_DENSE, ffi.PMX_FLAG_FORCE_SPARSE, ffi.PMX_FLAG_DEEP_LISTS, ffi.PMX_FLAG_EVENTS_HINT):
                 if flags == ffi.PMX_FLAG_FORCE_DENSE and (S + 1) * nbits > 3e8:
                     continue
                 if flags == ffi.PMX_FLAG_FORCE_SPARSE and L > 1024:
                     continue                       # reads longer than 1024 take the dense kernels
                 fl = flags | (ffi.PMX_FLAG_SKIP_NCC if skip_ncc else 0)
-                tag = f"seed={case_seed} S={S} L={L} clen={clen} fd={fd} rd={rd} m={with_m}/{mean_on}/{mean_off} full={full} flags={fl}"
+                tag = f"seed={case_seed} S={S} L={L} clen={clen} fd={fd} rd={rd} m={with_m}/{mean_on}/{mean_off} full={full} flags={fl} helping={helping}"
                 try:
                     out = ctx.calc_correlation(F, R, M, nbits, S, L, fl)
                 except ffi.PmxError as e:
@@ -197,6 +201,8 @@ def main():
                     continue
                 if not compare(out, ref, S, with_m, skip_ncc, tag):
                     bad += 1
+            ctx.debug_set_claim_mode(0)
+            ctx.debug_set_max_workgroups(0)
             if rng.random() < 0.15:
                 bad += fuzz_feed(ctx, rng, clen, S, L)
             if with_m and rng.random() < 0.25:

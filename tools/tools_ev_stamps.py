@@ -1,47 +1,82 @@
 #!/usr/bin/env python3
-"""GPU box diagnostic: builds the library with -DEV_STAMPS and prints where a tile's cycles go in k_cc_events."""
+"""GPU box diagnostic: builds the library with -DEV_STAMPS and prints where a tile's cycles go in k_cc_events, and when
+its workgroups start and end (their lifetimes: what the static tile ranges leave idle).
+
+usage: tools_ev_stamps.py [both|ncc] [extra hipcc flags ...]
+  EV_STAMPS_LIB=path   use a library already built with -DEV_STAMPS instead of compiling one
+  EV_TRACK=fixture     the fixture track's run lengths instead of the synthetic track (bench.py --track)
+  EV_CLAIM_MODE=n      pmx_debug_set_claim_mode (0: claims + helping, 2: the static walk)"""
 import ctypes, os, subprocess, sys, glob
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-lib = "/tmp/libevstamps.so"
-extra = [a for a in sys.argv[2:]]
-subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-mllvm", "-amdgpu-atomic-optimizer-strategy=DPP", "-fPIC", "-shared", "-DEV_STAMPS",
-                       "-o", lib] + extra + sorted(glob.glob(os.path.join(ROOT, "pymasc_amd/csrc/*.hip"))))
+lib = os.environ.get("EV_STAMPS_LIB")
+if not lib:
+    lib = "/tmp/libevstamps.so"
+    extra = [a for a in sys.argv[2:]]
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-mllvm", "-amdgpu-atomic-optimizer-strategy=DPP", "-fPIC", "-shared", "-DEV_STAMPS",
+                           "-o", lib] + extra + sorted(glob.glob(os.path.join(ROOT, "pymasc_amd/csrc/*.hip"))))
 os.environ["PYMASC_AMD_LIB"] = lib
 os.environ["PMX_AUTOCORR_FORK"] = "0"
 import torch
 from pymasc_amd import ffi, synth
 mode = sys.argv[1] if len(sys.argv) > 1 else "both"
+track = os.environ.get("EV_TRACK", "synthetic")
 with_m = mode == "both"
 ctx = ffi.Context(0)
 dev = torch.device("cuda", 0)
 S, L = 1000, 36
-vecs = [synth.make_chromosome(ctx, dev, n, ln, S, L, 0xC0FFEE + i, with_m=with_m) for i, (n, ln) in enumerate(synth.HG38)]
+vecs = [synth.make_chromosome(ctx, dev, n, ln, S, L, 0xC0FFEE + i, with_m=with_m, track=track) for i, (n, ln) in enumerate(synth.HG38)]
 out = torch.zeros((len(vecs), ffi.PMX_NROWS, S + 1), dtype=torch.int64, device=dev)
 args = ([v.F.data_ptr() for v in vecs], [v.R.data_ptr() for v in vecs], [v.M.data_ptr() for v in vecs] if with_m else None,
-        [v.nbits for v in vecs], S, L, 0, [out[i].data_ptr() for i in range(len(vecs))])
+        [v.nbits for v in vecs], S, L, ffi.PMX_FLAG_EVENTS_HINT, [out[i].data_ptr() for i in range(len(vecs))])
+Lb = ffi.load_library()
+if os.environ.get("EV_CLAIM_MODE"):
+    ctx.debug_set_claim_mode(int(os.environ["EV_CLAIM_MODE"]))
 for _ in range(3):
     ctx.cc_batch_dev(*args)
 ctx.sync()
 ntiles = sum((v.nbits + 65535) // 65536 for v in vecs)
-per_cu = int(os.environ.get("EV_PER_CU", 4 if with_m else 8))
+per_cu = int(os.environ.get("EV_PER_CU", 5 if with_m else 8))
 nwg = min(256 * per_cu, ntiles)
 tpw = -(-ntiles // nwg); nwg = -(-ntiles // tpw)
 off = (nwg + len(vecs)) * 6 * 1024 * 4   # EV_SEG_ROWS
 NS = 12
+NP = 10   # slots 0..9: phases of a tile, in shader cycles; slots 10, 11 of wave 0: start and end of the workgroup
 buf = np.zeros(nwg * 4 * NS, dtype=np.uint64)
-Lb = ffi.load_library()
 Lb.pmx_debug_read_slab.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
 rc = Lb.pmx_debug_read_slab(ctx._h, off, buf.ctypes.data, buf.nbytes)
 assert rc == 0
-a = buf.reshape(nwg, 4, NS).astype(np.float64)
+raw = buf.reshape(nwg, 4, NS)
+a = raw[:, :, :NP].astype(np.float64)
 tot = a.sum(axis=2).mean()
-print(f"mode={mode} nwg={nwg} tiles/wg={tpw} cycles per wave lifetime={tot:.0f}  per tile={tot / tpw:.0f}")
+print(f"mode={mode} track={track} nwg={nwg} tiles/wg={tpw} cycles per wave lifetime={tot:.0f}  per tile={tot / tpw:.0f}")
 lab = {0: "B0 barrier wait", 1: "counts + M store + scans", 2: "Bs barrier wait", 3: "totals + emit lists", 4: "prefetch issue",
        5: "B1 barrier wait", 6: "events: forward x reverse pairs", 8: "R0 (reverse reads: M[p] M[p+c])", 7: "events: edges x reads, edge pairs",
-       9: "flush / loop tail", 10: "-", 11: "-"}
-for i in range(NS):
+       9: "flush / loop tail"}
+for i in range(NP):
     print(f"  {lab[i]:32s} {a[:, :, i].mean() / tpw:9.0f} cyc/tile  {100 * a[:, :, i].sum() / a.sum():5.1f} %")
 for w in range(4):
-    print("  wave", w, " ".join(f"{a[:, w, i].mean() / tpw:7.0f}" for i in range(NS)))
+    print("  wave", w, " ".join(f"{a[:, w, i].mean() / tpw:7.0f}" for i in range(NP)))
+
+# ---- workgroup lifetimes.  The constant 100 MHz clock (s_memrealtime), one reading at kernel entry and one behind the last
+# flush: the shader clock (s_memtime) of one XCD says nothing about another's, and the question is who waits for whom.
+TICK_US = 0.01
+t0 = raw[:, 0, 10].astype(np.int64)
+t1 = raw[:, 0, 11].astype(np.int64)
+base = t0.min()
+st = (t0 - base) * TICK_US
+en = (t1 - base) * TICK_US
+life = en - st
+span = en.max() - st.min()
+idle = 1.0 - life.sum() / (nwg * span)
+print(f"workgroup lifetimes (us, from the first start): {nwg} workgroups")
+print(f"  first start {st.min():8.2f}   last start {st.max():8.2f}")
+print(f"  first end   {en.min():8.2f}   last end   {en.max():8.2f}")
+print(f"  mean lifetime {life.mean():8.2f}   shortest {life.min():8.2f}   longest {life.max():8.2f}")
+print(f"  idle share 1 - sum(lifetimes) / (workgroups x (last end - first start)) = {100 * idle:5.2f} %")
+print(f"    of which before the start {100 * (st - st.min()).sum() / (nwg * span):5.2f} %, behind the end {100 * (en.max() - en).sum() / (nwg * span):5.2f} %")
+hist, edges = np.histogram(en, bins=10, range=(en.min(), en.max()))
+print("  end times, ten bins from the first to the last end:")
+for k in range(10):
+    print(f"    {edges[k]:8.2f} .. {edges[k + 1]:8.2f} us  {hist[k]:5d}  {'#' * int(round(60 * hist[k] / max(1, hist.max())))}")
