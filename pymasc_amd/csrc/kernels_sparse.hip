@@ -2244,10 +2244,6 @@ __global__ void __launch_bounds__(1024) k_plan_flagged(const PlanLaunch a, const
 
 // ---- host side ----------------------------------------------------------------------------------------------
 
-static int launch_autocorr_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_lag, uint32_t mode, uint32_t read_len,
-                                 uint32_t max_shift, uint32_t out_stride, const uint32_t *pre_flag0, const unsigned char *pre_flags,
-                                 const u32 *pre_nflagged);
-
 static uint32_t lg_slot_lanes(uint32_t nshifts)   // nshifts = shifts handled per slot
 {
     const u32 need = (nshifts + 31) / 32;
@@ -2270,7 +2266,6 @@ struct VJob {
     const pmx_job *job;
     u32 d_off, d_n;
     u32 flag0;   // autocorrelation: index of the chromosome's first tile in the dense-tile flag array
-    bool ranged; // the event launch of a tile-range job: take job->tile_first / tile_count (every other launch sees the whole chromosome)
 };
 
 static void fill_plan_launch(PlanLaunch &p, const SpJobTable &tab, u32 n, u32 total, u32 nwg, u32 raw_lo, u32 raw_hi,
@@ -2285,9 +2280,14 @@ static void fill_plan_launch(PlanLaunch &p, const SpJobTable &tab, u32 n, u32 to
     p.flags_per_count = flags_per_count; p.flags = flags; p.n_flagged = n_flagged; p.plan = plan;
 }
 
+struct LaunchPlan {
+    uint32_t total, tiles_per_wg, nwg;   // tiles of the launch, tiles per workgroup, workgroups
+};
+
 // Cuts the global tile sequence of a launch into per-workgroup ranges and fills the device job table.
-static void plan_launch(pmx_ctx *ctx, const VJob *vj, uint32_t n, bool autocorr, uint32_t wg_per_cu, SpJobDev *out,
-                        uint32_t *total_tiles, uint32_t *tiles_per_wg, uint32_t *nwg, uint64_t tile_bits_override = 0)
+// ranged: the event launch of tile-range jobs takes job->tile_first / tile_count (every other launch sees whole chromosomes)
+static LaunchPlan plan_launch(pmx_ctx *ctx, const VJob *vj, uint32_t n, bool autocorr, uint32_t wg_per_cu, SpJobDev *out,
+                              uint64_t tile_bits_override = 0, bool ranged = false)
 {
     uint32_t t = 0;
     for (uint32_t i = 0; i < n; i++) {
@@ -2298,7 +2298,7 @@ static void plan_launch(pmx_ctx *ctx, const VJob *vj, uint32_t n, bool autocorr,
         uint64_t nt = (bits + tile_bits - 1) / tile_bits;
         if (nt < 1) nt = 1;
         uint32_t first = 0;
-        if (vj[i].ranged && jb.tile_count) {   // (validated by the caller: inside the chromosome, event tiles)
+        if (ranged && jb.tile_count) {   // (validated by the caller: inside the chromosome, event tiles)
             first = jb.tile_first;
             nt = jb.tile_count;
         }
@@ -2330,15 +2330,7 @@ static void plan_launch(pmx_ctx *ctx, const VJob *vj, uint32_t n, bool autocorr,
         d.wg_first = d.tile0 / tpw;
         d.wg_last = (d.tile0 + d.ntiles - 1) / tpw;
     }
-    *total_tiles = t;
-    *tiles_per_wg = tpw;
-    *nwg = nw;
-}
-
-static void plan_launch(pmx_ctx *ctx, const VJob *vj, uint32_t n, bool autocorr, uint32_t wg_per_cu, SpJobTable *tab,
-                        uint32_t *total_tiles, uint32_t *tiles_per_wg, uint32_t *nwg, uint64_t tile_bits_override = 0)
-{
-    plan_launch(ctx, vj, n, autocorr, wg_per_cu, tab->j, total_tiles, tiles_per_wg, nwg, tile_bits_override);
+    return LaunchPlan{t, tpw, nw};
 }
 
 // a launch's job table in device memory (any number of jobs)
@@ -2358,7 +2350,6 @@ static void expand_chunks(const pmx_job *jobs, uint32_t njobs, uint32_t nshifts,
     for (uint32_t i = 0; i < njobs; i++)
         for (uint32_t off = 0; off < nshifts; off += 1024) {
             VJob v;
-            v.ranged = false;
             v.job = &jobs[i];
             v.d_off = off;
             v.d_n = nshifts - off < 1024 ? nshifts - off : 1024;
@@ -2367,13 +2358,55 @@ static void expand_chunks(const pmx_job *jobs, uint32_t njobs, uint32_t nshifts,
         }
 }
 
+// the n jobs from jobs[lo] on, each whole: all its d_n shifts (or lags) in one piece
+static std::vector<VJob> whole_jobs(const pmx_job *jobs, uint32_t lo, uint32_t n, uint32_t d_n, const uint32_t *flag0)
+{
+    std::vector<VJob> v(n);
+    for (uint32_t i = 0; i < n; i++) {
+        v[i].job = &jobs[lo + i];
+        v[i].d_off = 0;
+        v[i].d_n = d_n;
+        v[i].flag0 = flag0 ? flag0[lo + i] : 0;
+    }
+    return v;
+}
+
+// Lays the jobs' entries out in one dense-tile flag array: a job has one entry per tile_bits of its vector (edges: of the
+// edge positions [0, nbits]) and `pad` more behind them; flag0[i] receives the index of job i's first entry.  Returns the
+// length of the array in bytes, a multiple of 16.
+static size_t flag_layout(const pmx_job *jobs, uint32_t njobs, uint64_t tile_bits, uint32_t pad, bool edges, uint32_t *flag0)
+{
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < njobs; i++) {
+        flag0[i] = (uint32_t)total;
+        total += (jobs[i].nbits + (edges ? 1 : 0) + tile_bits - 1) / tile_bits + pad;
+    }
+    return (size_t)((total + 15) / 16 * 16);
+}
+
+// What is done once per GPU of the process (a process may hold one context per GPU; occupancy answers and function
+// attributes belong to the current device): the flag of the context's device in flags[EV_MAX_DEVICES], or null for a
+// device beyond the table, for which it is done every time.
+#define EV_MAX_DEVICES 64
+static bool *once_per_device(const pmx_ctx *ctx, bool *flags)
+{
+    return ctx->device >= 0 && ctx->device < EV_MAX_DEVICES ? &flags[ctx->device] : nullptr;
+}
+
+// lets a kernel take up to 160 KB of dynamic LDS (set[]: done once per device for this kernel)
+static int allow_big_lds(const pmx_ctx *ctx, const void *kern, bool *set)
+{
+    bool *const done = once_per_device(ctx, set);
+    if (done && *done) return PMX_OK;
+    PMX_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
+    if (done) *done = true;
+    return PMX_OK;
+}
+
 static bool events_enabled()
 {
     // PMX_CC_EVENTS=0 in the environment keeps everything on the window kernel (A/B measurements, tests)
-    static const bool on = [] {
-        const char *e = getenv("PMX_CC_EVENTS");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pmx_env_enabled("PMX_CC_EVENTS");
     return on;
 }
 
@@ -2386,10 +2419,7 @@ struct EvBigPlan {
 static bool events_big_enabled()
 {
     // PMX_CC_EVENTS_BIG=0 in the environment keeps max_shift > 1023 on the window kernel in shift chunks (A/B, tests)
-    static const bool on = [] {
-        const char *e = getenv("PMX_CC_EVENTS_BIG");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = pmx_env_enabled("PMX_CC_EVENTS_BIG");
     return on;
 }
 
@@ -2437,10 +2467,7 @@ static bool ev_big_plan(uint32_t max_shift, EvBigPlan *p, uint32_t fused_lag = 0
     }
     // the row of lags of the fused mappable-length pairs (hn 16-bit cells) in LDS, if that costs no resident workgroup
     // (PMX_EV_EE_LDS=0 in the environment: always in the slab -- A/B, tests)
-    static const bool ee_ok = [] {
-        const char *e = getenv("PMX_EV_EE_LDS");
-        return !(e && e[0] == '0');
-    }();
+    static const bool ee_ok = pmx_env_enabled("PMX_EV_EE_LDS");
     if (best_waves && fused_lag && ee_ok) {
         const u32 bytes = p->lds_bytes + 16 + hn * 2;
         u32 per_cu = bytes <= lds_cu ? lds_cu / (bytes + 256) : 0;
@@ -2457,49 +2484,50 @@ static bool ev_big_plan(uint32_t max_shift, EvBigPlan *p, uint32_t fused_lag = 0
     return best_waves != 0;
 }
 
-// resident workgroups per CU of a max_shift <= 1023 instantiation on this device, at most `built_for` (asked once per instantiation)
-// (cached per DEVICE: a process may hold one context per GPU, and both the occupancy answer and the function attribute of
-// ev_big_launch belong to the current device)
-#define EV_MAX_DEVICES 64
-template <bool HAS_M, bool DO_NCC, bool DO_MLEN, bool DEEP, bool KNOWN>
-static u32 ev_resident_per_cu(pmx_ctx *ctx, u32 built_for)
+// ---- kernel choosers: the instantiations of a family over one job-table type share a pointer type ----
+template <typename JT>
+using EvKernelFn = void (*)(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, u32 S, u32 nhr, u32 max_lag, u32 hn,
+                            u32 lo, u32 hi, u32 *slab, unsigned char *tile_flags, unsigned char *tile_flags_ac, u32 *n_flagged,
+                            u32 *jobstat, u32 *claim, u32 claim_mode);
+template <typename JT>
+struct EvKernel {
+    EvKernelFn<JT> fn;
+    int index;   // of the instantiation in its chooser's table: with the device, the key of what is kept per instantiation
+};
+template <typename JT>
+using SpKernelFn = void (*)(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, int32_t c, u32 lgG, u32 *slab,
+                            const unsigned char *tile_flags, const u32 *n_flagged, const u32 *plan, u32 add_stride);
+
+// The window kernel.  CH (chunks of 1024 shifts) goes with the device-side table and only with it: each table type has the
+// three instantiations of its one CH.
+template <typename JT, bool CH>
+static SpKernelFn<JT> sp_kernel(bool has_m, bool do_ncc)
 {
-    static int cached[EV_MAX_DEVICES];
-    static bool known[EV_MAX_DEVICES];
-    const int dev = ctx->device >= 0 && ctx->device < EV_MAX_DEVICES ? ctx->device : -1;
-    int n = dev >= 0 && known[dev] ? cached[dev] : -1;
+    if (has_m && do_ncc) return k_cc_sparse<true, true, CH, JT>;
+    if (has_m) return k_cc_sparse<true, false, CH, JT>;
+    return k_cc_sparse<false, true, CH, JT>;
+}
+
+// resident workgroups per CU of a max_shift <= 1023 instantiation on this device, at most `built_for` (asked once per
+// instantiation and device)
+#define EV_KERNELS 18
+static u32 ev_resident_per_cu(pmx_ctx *ctx, const EvKernel<SpJobTable> &k, u32 built_for)
+{
+    static int cached[EV_KERNELS][EV_MAX_DEVICES];
+    static bool known[EV_KERNELS][EV_MAX_DEVICES];
+    bool *const have = once_per_device(ctx, known[k.index]);
+    int n = have && *have ? cached[k.index][ctx->device] : -1;
     if (n < 0) {
-        auto kern = k_cc_events<HAS_M, DO_NCC, DO_MLEN, 1, false, SpJobTable, DEEP, KNOWN>;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(kern), 256, 0) != hipSuccess || n < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(k.fn), 256, 0) != hipSuccess || n < 1) {
             (void)hipGetLastError();
             n = (int)built_for;
         }
-        if (dev >= 0) {
-            cached[dev] = n;
-            known[dev] = true;
+        if (have) {
+            cached[k.index][ctx->device] = n;
+            *have = true;
         }
     }
     return (u32)n < built_for ? (u32)n : built_for;
-}
-
-template <bool HAS_M, bool DO_NCC, u32 NSG, bool DO_MLEN = false>
-static int ev_big_launch(pmx_ctx *ctx, const EvBigPlan &pl, const SpJobTableRef &tab, u32 n, u32 total, u32 tpw, u32 nwg, u32 c,
-                         u32 max_shift, u32 nhr, unsigned char *d_flags, u32 *d_nflagged, u32 *d_jobstat, u32 fused_lag = 0,
-                         unsigned char *d_flags_ac = nullptr)
-{
-    auto kern = k_cc_events<HAS_M, DO_NCC, DO_MLEN, NSG, true, SpJobTableRef>;
-    static bool attr_set[EV_MAX_DEVICES];   // (per device function AND device: set once per GPU of the process, see ev_resident_per_cu)
-    const int dev = ctx->device >= 0 && ctx->device < EV_MAX_DEVICES ? ctx->device : -1;
-    if (dev < 0 || !attr_set[dev]) {
-        PMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024 - 64));
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256 * NSG), pl.lds_bytes, ctx->stream, tab, n, total, tpw, c, max_shift, nhr, fused_lag,
-                       pl.hn, pl.lo, pl.hi | (DO_MLEN && pl.ee_lds ? 1u << 16 : 0u), ctx->d_slab, d_flags, d_flags_ac ? d_flags_ac : d_flags, d_nflagged,
-                       d_jobstat, (u32 *)nullptr, 0u);
-    PMX_CHECK_LAUNCH("k_cc_events (max_shift > 1023)");
-    return PMX_OK;
 }
 
 // The window kernel in chunks of 1024 shifts over (chromosome x chunk) jobs with a device-side job table: every job of the
@@ -2507,16 +2535,15 @@ static int ev_big_launch(pmx_ctx *ctx, const EvBigPlan &pl, const SpJobTableRef 
 // event kernel flagged (the launch returns at once when there are none) and the sums are ADDED by a gated reduce;
 // null: every tile, rows written.
 static int launch_cc_window_chunks(pmx_ctx *ctx, const std::vector<VJob> &vjobs, bool has_m, bool do_ncc, int32_t c,
-                                   const ReduceSpec &rs, u32 nr, u32 nz, const unsigned char *d_flags, const u32 *d_nflagged)
+                                   const ReduceSpec &rs, const unsigned char *d_flags, const u32 *d_nflagged)
 {
     const bool behind_events = d_flags != nullptr;
+    const SpKernelFn<SpJobTableRef> kern = sp_kernel<SpJobTableRef, true>(has_m, do_ncc);
     for (size_t lo = 0; lo < vjobs.size(); lo += SP_MAXJOBS_REF) {
         const uint32_t n = (uint32_t)(vjobs.size() - lo < SP_MAXJOBS_REF ? vjobs.size() - lo : SP_MAXJOBS_REF);
         std::vector<SpJobDev> tab(n);
-        memset(tab.data(), 0, n * sizeof(SpJobDev));
-        uint32_t total, tpw, nwg;
-        plan_launch(ctx, &vjobs[lo], n, false, has_m ? SP_WAVES_CH : SP_WAVES_CH_NCC, tab.data(), &total, &tpw, &nwg);
-        const size_t wwords = (size_t)(nwg + n) * SP_SEG_ROWS * 1024 + (size_t)nwg * 4 * 12 * 2 + 64;
+        const LaunchPlan p = plan_launch(ctx, &vjobs[lo], n, false, has_m ? SP_WAVES_CH : SP_WAVES_CH_NCC, tab.data());
+        const size_t wwords = (size_t)(p.nwg + n) * SP_SEG_ROWS * 1024 + (size_t)p.nwg * 4 * 12 * 2 + 64;
         int rc = behind_events ? pmx_ensure_slab_fb(ctx, wwords) : pmx_ensure_slab(ctx, wwords);
         if (rc) return rc;
         u32 *const wslab = behind_events ? ctx->d_slab_fb : ctx->d_slab;
@@ -2526,35 +2553,181 @@ static int launch_cc_window_chunks(pmx_ctx *ctx, const std::vector<VJob> &vjobs,
         pmx_timed_launch tl;
         rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl, behind_events);
         if (rc) return rc;
-#define SP_LAUNCH(HM, NC)                                                                                                   \
-    hipLaunchKernelGGL((k_cc_sparse<HM, NC, true, SpJobTableRef>), dim3(nwg), dim3(256), 0, ctx->stream, ref, n, total, tpw, c, 5u, \
-                       wslab, d_flags, d_nflagged, (const u32 *)nullptr)
-        if (has_m && do_ncc) SP_LAUNCH(true, true);
-        else if (has_m) SP_LAUNCH(true, false);
-        else SP_LAUNCH(false, true);
-#undef SP_LAUNCH
+        hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(256), 0, ctx->stream, ref, n, p.total, p.tiles_per_wg, c, 5u, wslab, d_flags,
+                           d_nflagged, (const u32 *)nullptr, 0u);
         PMX_CHECK_LAUNCH("k_cc_sparse");
         rc = pmx_prof_end(ctx, &tl);
         if (rc) return rc;
         // (behind the event pass the launch is gated: normally 25 k blocks that return at once, 34 us of dispatch at 32 per row)
-        hipLaunchKernelGGL(k_reduce_segments<SpJobTableRef>, dim3(behind_events ? 8 : 32, nr + nz, n), dim3(256), 0, ctx->stream,
+        hipLaunchKernelGGL(k_reduce_segments<SpJobTableRef>, dim3(behind_events ? 8 : 32, rs.nrows + rs.nzero, n), dim3(256), 0, ctx->stream,
                            (const u32 *)wslab, ref, (u32)SP_SEG_ROWS, rs, d_nflagged);
         PMX_CHECK_LAUNCH("k_reduce_segments");
     }
     return PMX_OK;
 }
 
+// pre_flags != nullptr: the event kernel (max_shift > 1023, fused mappable-length pairs) has left the pair sums, popcount(M)
+// and the run count in the jobs' scratch and flagged the tiles whose run edges it could not list (pre_flag0[job]: index of
+// the job's first tile in pre_flags): only the window kernel for those tiles + the recurrence remain.
+static int launch_autocorr_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_lag, uint32_t mode,
+                                 uint32_t read_len, uint32_t max_shift, uint32_t out_stride, const uint32_t *pre_flag0,
+                                 const unsigned char *pre_flags, const u32 *pre_nflagged)
+{
+    if (njobs == 0) return PMX_OK;
+    const bool chunked = max_lag > 1023;
+    const u32 lagcap = (u32)(((size_t)max_lag + 1 + 1023) / 1024 * 1024);
+    const u32 lgG = chunked ? 5u : lg_slot_lanes(max_lag + 1);
+    typedef SpJobTableRef JT;   // job tables in device memory: every chromosome of the batch in one launch of each kernel
+
+    // Pass 1 (sparse-edge tiles): pair enumeration over every chromosome; tiles with more than AP_CAP edges are flagged.
+    // PMX_AUTOCORR_PAIRS=0 in the environment keeps everything on the window kernel (A/B measurements, tests).
+    static const bool pairs_enabled = pmx_env_enabled("PMX_AUTOCORR_PAIRS");
+    const bool use_pairs = !pre_flags && pairs_enabled && max_lag + 1 <= AP_MAX_LAGS;
+    std::vector<uint32_t> flag0(njobs, 0);
+    unsigned char *d_flags = const_cast<unsigned char *>(pre_flags);
+    u32 *d_nflagged = const_cast<u32 *>(pre_nflagged);
+    if (pre_flags)
+        for (uint32_t i = 0; i < njobs; i++) flag0[i] = pre_flag0[i];
+    const u32 nl = (max_lag + 1 + 63) / 64 * 64;
+    int rc;
+    if (use_pairs) {
+        const size_t flag_bytes = flag_layout(jobs, njobs, AC_TB, AP_NQ / AC_NQ, true, flag0.data());   // padding: a pair tile flags AP_NQ / AC_NQ window tiles
+        rc = pmx_ensure_flags(ctx, flag_bytes + 16);
+        if (rc) return rc;
+        d_flags = ctx->d_flags;
+        d_nflagged = (u32 *)(ctx->d_flags + flag_bytes);
+        PMX_HIP(hipMemsetAsync(ctx->d_flags, 0, flag_bytes + 16, ctx->stream));
+        const u32 nh = (max_lag + 1 + 127) / 128;   // quads above a tile that hold partners of its drivers
+        const size_t lds_bytes = (2 * (size_t)nl + 2 * AP_CAP + 32 + 16) * sizeof(u32);
+        const size_t seg_stride = 2 * (size_t)nl + 16;
+        // workgroups per CU: 8 by registers; the histograms may allow fewer
+        u32 per_cu = (u32)((160u * 1024u) / (lds_bytes + 512));
+        if (per_cu > AP_WAVES) per_cu = AP_WAVES;
+        if (per_cu < 1) per_cu = 1;
+        for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS_REF) {
+            const uint32_t n = njobs - lo < SP_MAXJOBS_REF ? njobs - lo : SP_MAXJOBS_REF;
+            const std::vector<VJob> vj = whole_jobs(jobs, lo, n, max_lag + 1, flag0.data());
+            std::vector<SpJobDev> tab(n);
+            const LaunchPlan p = plan_launch(ctx, vj.data(), n, true, per_cu, tab.data(), AP_TB);
+            rc = pmx_ensure_slab2(ctx, (size_t)(p.nwg + n) * seg_stride);
+            if (rc) return rc;
+            JT ref;
+            rc = upload_table(ctx, tab, &ref);
+            if (rc) return rc;
+            if (lds_bytes > 64 * 1024) {   // (max_lag above ~7870: the histograms alone pass 64 KB)
+                static bool attr_set[EV_MAX_DEVICES];
+                rc = allow_big_lds(ctx, reinterpret_cast<const void *>(k_autocorr_pairs<JT>), attr_set);
+                if (rc) return rc;
+            }
+            pmx_timed_launch tl;
+            rc = pmx_prof_begin(ctx, PMX_KERNEL_AUTOCORR, &tl);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_autocorr_pairs<JT>, dim3(p.nwg), dim3(256), lds_bytes, ctx->stream, ref, n, p.total, p.tiles_per_wg, max_lag, nl,
+                               nh, ctx->d_slab2, d_flags, d_nflagged);
+            PMX_CHECK_LAUNCH("k_autocorr_pairs");
+            rc = pmx_prof_end(ctx, &tl);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_reduce_pairs<JT>, dim3((max_lag + 1 + 31) / 32 < 64 ? (max_lag + 1 + 31) / 32 : 64, 3, n), dim3(256), 0,
+                               ctx->stream, (const u32 *)ctx->d_slab2, ref, nl, max_lag, lagcap, 0u);
+            PMX_CHECK_LAUNCH("k_reduce_pairs");
+        }
+    }
+
+    // Pass 2 (window kernel): every tile, or -- behind the pair pass -- only the tiles it flagged as dense (the whole
+    // grid returns at once when there are none); its sums are ADDED to what the pair pass left in the per-job scratch.
+    std::vector<VJob> vjobs;
+    expand_chunks(jobs, njobs, max_lag + 1, vjobs, flag0.data());
+
+    ReduceSpec rs;
+    memset(&rs, 0, sizeof rs);
+    rs.nrows = 3;
+    rs.src_row[0] = 0; rs.dst_row[0] = 0;            // P
+    rs.src_row[1] = 1; rs.dst_row[1] = lagcap;       // N
+    rs.src_row[2] = 2; rs.dst_row[2] = 2 * lagcap; rs.is_scalar[2] = 1;
+    rs.use_out2 = 1;
+    rs.accumulate = (use_pairs || pre_flags) ? 1 : 0;
+    rs.out_stride = out_stride;
+    const auto edges_kern = chunked ? k_autocorr_edges<true, JT> : k_autocorr_edges<false, JT>;
+
+    for (size_t lo = 0; lo < vjobs.size(); lo += SP_MAXJOBS_REF) {
+        const uint32_t n = (uint32_t)(vjobs.size() - lo < SP_MAXJOBS_REF ? vjobs.size() - lo : SP_MAXJOBS_REF);
+        std::vector<SpJobDev> tab(n);
+        const LaunchPlan p = plan_launch(ctx, &vjobs[lo], n, true, chunked ? AC_WAVES_CH : AC_WAVES, tab.data());
+        rc = pmx_ensure_slab_ac(ctx, (size_t)(p.nwg + n) * AC_SEG_ROWS * 1024);
+        if (rc) return rc;
+        JT ref;
+        rc = upload_table(ctx, tab, &ref);
+        if (rc) return rc;
+        pmx_timed_launch tl;
+        rc = pmx_prof_begin(ctx, PMX_KERNEL_AUTOCORR, &tl);
+        if (rc) return rc;
+        hipLaunchKernelGGL(edges_kern, dim3(p.nwg), dim3(256), 0, ctx->stream, ref, n, p.total, p.tiles_per_wg, lgG, ctx->d_slab_ac,
+                           (const unsigned char *)d_flags, (const u32 *)d_nflagged, (const u32 *)nullptr, 0u, (int32_t)0, 0u, 0u);
+        PMX_CHECK_LAUNCH("k_autocorr_edges");
+        rc = pmx_prof_end(ctx, &tl);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_reduce_segments<JT>, dim3(32, 3, n), dim3(256), 0, ctx->stream, (const u32 *)ctx->d_slab_ac, ref,
+                           (u32)AC_SEG_ROWS, rs, (const u32 *)d_nflagged);
+        PMX_CHECK_LAUNCH("k_reduce_segments");
+    }
+    // the recurrence needs every chunk of a chromosome: run it once all launches are queued (same stream)
+    for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS_REF) {
+        const uint32_t n = njobs - lo < SP_MAXJOBS_REF ? njobs - lo : SP_MAXJOBS_REF;
+        std::vector<SpJobDev> tab(n);
+        for (uint32_t i = 0; i < n; i++) {
+            tab[i].flags = 1;
+            tab[i].out = (u64 *)jobs[lo + i].d_out;
+            tab[i].out2 = (u64 *)jobs[lo + i].d_out2;
+        }
+        JT ref;
+        rc = upload_table(ctx, tab, &ref);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_autocorr_finish<JT>, dim3(n), dim3(AC_FINISH_THREADS), 0, ctx->stream, ref, max_lag, lagcap, mode,
+                           (int32_t)read_len - 1, max_shift, out_stride);
+        PMX_CHECK_LAUNCH("k_autocorr_finish");
+    }
+    return PMX_OK;
+}
+
+// The BIG instantiations of the event kernel (device-side table, nsg sub-groups of 256 threads); mlen: the mappable-length
+// pairs in the same launch (has_m only).  Without a track everything but nsg is ignored, as for ev_kernel.
+#define EV_BIG_KERNELS 15
+static EvKernel<SpJobTableRef> ev_big_kernel(bool has_m, bool do_ncc, bool mlen, u32 nsg)
+{
+    typedef SpJobTableRef JT;
+    static const EvKernelFn<JT> tab[EV_BIG_KERNELS] = {
+        // mlen: do_ncc, !do_ncc (x 1, 2, 4 sub-groups)
+        k_cc_events<true, true, true, 1, true, JT>,    k_cc_events<true, true, true, 2, true, JT>,    k_cc_events<true, true, true, 4, true, JT>,
+        k_cc_events<true, false, true, 1, true, JT>,   k_cc_events<true, false, true, 2, true, JT>,   k_cc_events<true, false, true, 4, true, JT>,
+        // !mlen: has_m with do_ncc, has_m without, !has_m
+        k_cc_events<true, true, false, 1, true, JT>,   k_cc_events<true, true, false, 2, true, JT>,   k_cc_events<true, true, false, 4, true, JT>,
+        k_cc_events<true, false, false, 1, true, JT>,  k_cc_events<true, false, false, 2, true, JT>,  k_cc_events<true, false, false, 4, true, JT>,
+        k_cc_events<false, true, false, 1, true, JT>,  k_cc_events<false, true, false, 2, true, JT>,  k_cc_events<false, true, false, 4, true, JT>,
+    };
+    const int i = (has_m ? (mlen ? 0 : 6) + (do_ncc ? 0 : 3) : 12) + (nsg == 1 ? 0 : nsg == 2 ? 1 : 2);
+    return {tab[i], i};
+}
+
+// the event kernels leave FSUM and RSUM in their slab rows as signed sums
+static ReduceSpec ev_reduce_spec(const ReduceSpec &rs, u32 rowlen)
+{
+    ReduceSpec rs_ev = rs;
+    for (u32 i = 0; i < rs.nrows; i++)
+        if (rs.dst_row[i] == PMX_ROW_MSCC_FSUM || rs.dst_row[i] == PMX_ROW_MSCC_RSUM) rs_ev.is_signed[i] = 1;
+    rs_ev.rowlen = rowlen;
+    return rs_ev;
+}
+
 // max_shift in [1024, EV_MAX_SHIFT]: the event kernel over every chromosome (one pass over the vectors whatever the
 // shift range), then -- for the tiles it flagged as dense only -- the window kernel in chunks of 1024 shifts, whose sums a
-// gated reduce adds to the rows.  The mappable-length pass is not fused here (the caller runs k_autocorr_pairs).
+// gated reduce adds to the rows.  The mappable-length pairs ride in the same launch when the caller asks for it (fused)
+// and the geometry allows it; otherwise the caller runs k_autocorr_pairs.
 static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_shift, uint32_t read_len,
-                                bool do_ncc, uint32_t out_stride, const ReduceSpec &rs, u32 nr, u32 nz, uint32_t fused_lag,
-                                pmx_fused_mlen *fused)
+                                bool do_ncc, uint32_t out_stride, const ReduceSpec &rs, uint32_t fused_lag, pmx_fused_mlen *fused)
 {
     const bool has_m = jobs[0].d_M != nullptr;
     const u32 c = read_len - 1;
     EvBigPlan pl;
-    // the mappable-length pairs in the same launch (round 4), when the caller asks for it and the geometry allows it
     bool fuse_mlen = has_m && fused && fused_lag && pmx_events_can_fuse_mlen(max_shift, fused_lag) && ev_big_plan<true>(max_shift, &pl, fused_lag);
     if (!fuse_mlen && !(has_m ? ev_big_plan<true>(max_shift, &pl) : ev_big_plan<false>(max_shift, &pl))) {
         pmx_set_error("k_cc_events: no launch geometry for max_shift %u", max_shift);
@@ -2562,12 +2735,7 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
     }
     if (fuse_mlen) fused->done = true;   // row MLEN and scalar [2] are written by this call
     std::vector<uint32_t> flag0(njobs);
-    uint64_t total_flags = 0;
-    for (uint32_t i = 0; i < njobs; i++) {
-        flag0[i] = (uint32_t)total_flags;
-        total_flags += (jobs[i].nbits + SP_TB - 1) / SP_TB + EV_NQ;   // padding: an event tile flags EV_NQ window tiles
-    }
-    const size_t flag_bytes = (size_t)((total_flags + 15) / 16 * 16);
+    const size_t flag_bytes = flag_layout(jobs, njobs, SP_TB, EV_NQ, false, flag0.data());   // padding: an event tile flags EV_NQ window tiles
     const uint32_t per_launch = njobs < SP_MAXJOBS_REF ? njobs : SP_MAXJOBS_REF;
     const size_t stat_bytes = 4 * (size_t)per_launch * sizeof(u32);
     // [flags of the cc window kernel][flags of the autocorrelation window kernel (fused pairs only)][counters][job statistics]
@@ -2581,27 +2749,16 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
     PMX_HIP(hipMemsetAsync(ctx->d_flags_cc, 0, nflag_arrays * flag_bytes + 16 + stat_bytes, ctx->stream));
     ctx->flags_cc_zeroed[0] = ctx->flags_cc_zeroed[1] = ctx->flags_cc_dirty[0] = ctx->flags_cc_dirty[1] = 0;   // (see ev_flag_area)
 
-    ReduceSpec rs_ev = rs;
-    for (u32 i = 0; i < nr; i++)
-        if (rs.dst_row[i] == PMX_ROW_MSCC_FSUM || rs.dst_row[i] == PMX_ROW_MSCC_RSUM) rs_ev.is_signed[i] = 1;
-    rs_ev.rowlen = pl.hn;
+    const EvKernel<SpJobTableRef> kern = ev_big_kernel(has_m, do_ncc, fuse_mlen, pl.nsg);
+    const ReduceSpec rs_ev = ev_reduce_spec(rs, pl.hn);
     const u32 nhr = (max_shift + 1 + 127) / 128;   // quads of R above a tile that hold partners of its forward reads
     for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS_REF) {
         const uint32_t n = njobs - lo < SP_MAXJOBS_REF ? njobs - lo : SP_MAXJOBS_REF;
-        std::vector<VJob> ev(n);
-        for (auto &v : ev) v.ranged = false;
-        for (uint32_t i = 0; i < n; i++) {
-            ev[i].job = &jobs[lo + i];
-            ev[i].d_off = 0;
-            ev[i].d_n = max_shift + 1;
-            ev[i].flag0 = flag0[lo + i];
-        }
+        const std::vector<VJob> ev = whole_jobs(jobs, lo, n, max_shift + 1, flag0.data());
         std::vector<SpJobDev> tab(n);
-        memset(tab.data(), 0, n * sizeof(SpJobDev));
-        uint32_t total, tpw, nwg;
         if (lo) PMX_HIP(hipMemsetAsync(d_jobstat, 0, stat_bytes, ctx->stream));   // (the next launch's jobs)
-        plan_launch(ctx, ev.data(), n, false, pl.wg_per_cu, tab.data(), &total, &tpw, &nwg, EV_TB);
-        rc = pmx_ensure_slab(ctx, (size_t)(nwg + n) * EV_SEG_ROWS * pl.hn + (size_t)nwg * 4 * pl.nsg * 12 * 2 + 64);
+        const LaunchPlan p = plan_launch(ctx, ev.data(), n, false, pl.wg_per_cu, tab.data(), EV_TB);
+        rc = pmx_ensure_slab(ctx, (size_t)(p.nwg + n) * EV_SEG_ROWS * pl.hn + (size_t)p.nwg * 4 * pl.nsg * 12 * 2 + 64);
         if (rc) return rc;
         SpJobTableRef ref;
         rc = upload_table(ctx, tab, &ref);
@@ -2609,20 +2766,16 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
         pmx_timed_launch tl;
         rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_EVENTS, &tl);
         if (rc) return rc;
-#define EVB(HM, NC, ML)                                                                                                                 \
-    (pl.nsg == 1   ? ev_big_launch<HM, NC, 1, ML>(ctx, pl, ref, n, total, tpw, nwg, c, max_shift, nhr, d_flags, d_nflagged, d_jobstat,  \
-                                                  ML ? fused_lag : 0u, d_flags_ac)                                                      \
-     : pl.nsg == 2 ? ev_big_launch<HM, NC, 2, ML>(ctx, pl, ref, n, total, tpw, nwg, c, max_shift, nhr, d_flags, d_nflagged, d_jobstat,  \
-                                                  ML ? fused_lag : 0u, d_flags_ac)                                                      \
-                   : ev_big_launch<HM, NC, 4, ML>(ctx, pl, ref, n, total, tpw, nwg, c, max_shift, nhr, d_flags, d_nflagged, d_jobstat,  \
-                                                  ML ? fused_lag : 0u, d_flags_ac))
-        if (fuse_mlen) rc = do_ncc ? EVB(true, true, true) : EVB(true, false, true);
-        else rc = has_m ? (do_ncc ? EVB(true, true, false) : EVB(true, false, false)) : EVB(false, true, false);
-#undef EVB
+        static bool attr_set[EV_BIG_KERNELS][EV_MAX_DEVICES];   // (per instantiation and device)
+        rc = allow_big_lds(ctx, reinterpret_cast<const void *>(kern.fn), attr_set[kern.index]);
         if (rc) return rc;
+        hipLaunchKernelGGL(kern.fn, dim3(p.nwg), dim3(256 * pl.nsg), pl.lds_bytes, ctx->stream, ref, n, p.total, p.tiles_per_wg, c,
+                           max_shift, nhr, fuse_mlen ? fused_lag : 0u, pl.hn, pl.lo, pl.hi | (fuse_mlen && pl.ee_lds ? 1u << 16 : 0u),
+                           ctx->d_slab, d_flags, d_flags_ac ? d_flags_ac : d_flags, d_nflagged, d_jobstat, (u32 *)nullptr, 0u);
+        PMX_CHECK_LAUNCH("k_cc_events (max_shift > 1023)");
         rc = pmx_prof_end(ctx, &tl);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_reduce_segments<SpJobTableRef>, dim3(32, nr + nz, n), dim3(256), 0, ctx->stream,
+        hipLaunchKernelGGL(k_reduce_segments<SpJobTableRef>, dim3(32, rs.nrows + rs.nzero, n), dim3(256), 0, ctx->stream,
                            (const u32 *)ctx->d_slab, ref, (u32)EV_SEG_ROWS, rs_ev, (const u32 *)nullptr);
         PMX_CHECK_LAUNCH("k_reduce_segments");
         if (fuse_mlen) {
@@ -2658,7 +2811,7 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
     expand_chunks(jobs, njobs, max_shift + 1, vjobs, flag0.data());
     ReduceSpec rs_w = rs;
     rs_w.accumulate = 1;
-    rc = launch_cc_window_chunks(ctx, vjobs, has_m, do_ncc, (int32_t)c, rs_w, nr, nz, d_flags, d_nflagged);
+    rc = launch_cc_window_chunks(ctx, vjobs, has_m, do_ncc, (int32_t)c, rs_w, d_flags, d_nflagged);
     if (rc || !fuse_mlen) return rc;
     // the window kernel of the mappable-length pass for the tiles whose run edges were not listed (normally none) and the
     // recurrence A(k+1) = 2 A(k) - A(k-1) - EE(k) -> row MLEN and scalar [2]
@@ -2676,18 +2829,12 @@ int pmx_events_take_big(uint32_t max_shift)
 
 int pmx_events_can_fuse_mlen(uint32_t max_shift, uint32_t max_lag)
 {
-    static const bool fuse = [] {   // PMX_CC_FUSE_MLEN=0: the mappable-length pass stays a pass of its own
-        const char *e = getenv("PMX_CC_FUSE_MLEN");
-        return !(e && e[0] == '0');
-    }();
+    static const bool fuse = pmx_env_enabled("PMX_CC_FUSE_MLEN");   // =0: the mappable-length pass stays a pass of its own
     if (!(events_enabled() && fuse)) return 0;
     if (max_shift <= 1023) return max_lag <= 1023;   // one histogram row of 1024 lags
     // beyond: the pairs go to the slab with global atomics (k_cc_events, BIG + DO_MLEN); the run edges up to max_lag bits above a
     // tile are staged by one wavefront (PMX_CC_FUSE_MLEN_BIG=0: the pair pass over M stays a pass of its own, A/B)
-    static const bool fuse_big = [] {
-        const char *e = getenv("PMX_CC_FUSE_MLEN_BIG");
-        return !(e && e[0] == '0');
-    }();
+    static const bool fuse_big = pmx_env_enabled("PMX_CC_FUSE_MLEN_BIG");
     EvBigPlan pl;
     return fuse_big && pmx_events_take_big(max_shift) && ev_big_plan<true>(max_shift, &pl, max_lag);
 }
@@ -2706,16 +2853,33 @@ int pmx_events_big_subgroups(uint32_t max_shift, int has_m)
     return (int)pl.nsg;
 }
 
-// The dense-tile flags, the flagged-tile counters and the job statistics of the event pass must be ZERO when k_cc_events
-// starts.  Until round 3 a memset in front of every pass did that (5 us of stream time per step); now the context keeps TWO
-// areas and uses them in turn: the pass in area A has its k_events_finish launch clear what the previous pass dirtied in area B
-// (nothing of the running pass touches B), so a pass finds its area clean without a launch of its own.  zeroed[]: prefix of
-// an idle area known to be zero; dirty[]: prefix a pass has used and nobody has cleared yet (cleared here if the pass that
-// should have done it never launched its k_events_finish: an error exit).
-static int ev_flag_area(pmx_ctx *ctx, size_t area_bytes, size_t zero_bytes, unsigned char **cur, unsigned char **other,
-                        size_t *other_dirty)
+// The flag area of an event pass of max_shift <= 1023, in this order:
+//   [cc flags][ac flags][counters][job statistics + totals][claim counters][plan cc][plan ac]
+// Everything in front of the plans must be ZERO when k_cc_events starts.  The context keeps TWO areas and uses them in turn:
+// the pass in area A has its k_events_finish launch clear what the previous pass dirtied in area B (nothing of the running
+// pass touches B), so a pass finds its area clean without a launch of its own.  zeroed[]: prefix of an idle area known to
+// be zero; dirty[]: prefix a pass has used and nobody has cleared yet (cleared here if the pass that should have done it
+// never launched its k_events_finish: an error exit).
+struct EvFlagArea {
+    unsigned char *flags;      // tiles of the cross-correlation window kernel (32 Kbit), flag_bytes long
+    unsigned char *flags_ac;   // tiles of the autocorrelation window kernel (64 Kbit), same flag0 per job, flag_bytes long
+    u32 *nflagged;             // flagged-tile counters of the two arrays (16 bytes)
+    u32 *jobstat;              // per job: tiles seen / read-dense / edge-dense (k_cc_events) + the chromosomes' scalar totals
+    u32 *claim;                // claim counters of the event kernel's pieces (kernels_events.h, EvClaimer): one word per
+                               // (workgroup, job) index; a launch is at most EV_WAVES_NCC workgroups per CU
+    u32 *plan_cc, *plan_ac;    // work split of the two window launches (k_events_finish), PLAN_WORDS each
+    size_t flag_bytes, claim_words, claim_bytes;
+    unsigned char *other;      // the context's other area, of which this pass's k_events_finish clears other_dirty bytes
+    size_t other_dirty;
+};
+
+static int ev_flag_area(pmx_ctx *ctx, size_t flag_bytes, EvFlagArea *fl)
 {
-    const size_t half = (area_bytes + 255) & ~(size_t)255;
+    fl->flag_bytes = flag_bytes;
+    fl->claim_words = (size_t)ctx->num_cus * 8 + SP_MAXJOBS;
+    fl->claim_bytes = (fl->claim_words * sizeof(u32) + 15) / 16 * 16;
+    const size_t zero_bytes = 2 * flag_bytes + 16 + EV_STAT_BYTES + fl->claim_bytes;   // (a multiple of 16)
+    const size_t half = (zero_bytes + 2 * PLAN_WORDS * sizeof(u32) + 255) & ~(size_t)255;
     const size_t before = ctx->flags_cc_bytes;
     int rc = pmx_ensure_flags_cc(ctx, 2 * half);
     if (rc) return rc;
@@ -2723,33 +2887,208 @@ static int ev_flag_area(pmx_ctx *ctx, size_t area_bytes, size_t zero_bytes, unsi
     const size_t stride = (ctx->flags_cc_bytes / 2) & ~(size_t)255;
     const u32 a = ctx->flags_cc_area & 1u;
     ctx->flags_cc_area = a ^ 1u;
-    *cur = ctx->d_flags_cc + a * stride;
-    *other = ctx->d_flags_cc + (a ^ 1u) * stride;
+    unsigned char *const area = ctx->d_flags_cc + a * stride;
+    fl->other = ctx->d_flags_cc + (a ^ 1u) * stride;
     if (ctx->flags_cc_dirty[a]) {
-        PMX_HIP(hipMemsetAsync(*cur, 0, ctx->flags_cc_dirty[a], ctx->stream));
+        PMX_HIP(hipMemsetAsync(area, 0, ctx->flags_cc_dirty[a], ctx->stream));
         ctx->flags_cc_dirty[a] = 0;
     }
     if (ctx->flags_cc_zeroed[a] < zero_bytes) {
-        PMX_HIP(hipMemsetAsync(*cur, 0, zero_bytes, ctx->stream));
+        PMX_HIP(hipMemsetAsync(area, 0, zero_bytes, ctx->stream));
         ctx->flags_cc_zeroed[a] = zero_bytes;
     }
     ctx->flags_cc_dirty[a] = zero_bytes;
-    *other_dirty = ctx->flags_cc_dirty[a ^ 1u];
+    fl->other_dirty = ctx->flags_cc_dirty[a ^ 1u];
+    fl->flags = area;
+    fl->flags_ac = area + flag_bytes;
+    fl->nflagged = (u32 *)(area + 2 * flag_bytes);
+    fl->jobstat = fl->nflagged + 4;
+    fl->claim = (u32 *)((unsigned char *)fl->jobstat + EV_STAT_BYTES);
+    fl->plan_cc = (u32 *)((unsigned char *)fl->claim + fl->claim_bytes);
+    fl->plan_ac = fl->plan_cc + PLAN_WORDS;
     return PMX_OK;
 }
 
-int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_shift,
-                               uint32_t read_len, bool do_ncc, uint32_t out_stride, bool zero_mlen,
-                               uint32_t fused_lag, pmx_fused_mlen *fused)
+// The event kernel of max_shift <= 1023 (table in the kernel arguments, one sub-group).  deep and fuse_mlen exist with
+// has_m only, and without has_m there is only do_ncc: 18 instantiations (without a track the other arguments are ignored).
+static EvKernel<SpJobTable> ev_kernel(bool has_m, bool do_ncc, bool fuse_mlen, bool deep, bool known)
 {
-    if (fused) fused->done = false;
-    if (njobs == 0) return PMX_OK;
-    const bool has_m = jobs[0].d_M != nullptr;
-    if (!has_m && !do_ncc) return PMX_OK;
-    const bool chunked = max_shift > 1023;
-    const int32_t c = (int32_t)read_len - 1;
-    const u32 lgG = chunked ? 5u : lg_slot_lanes(max_shift + 1);
+    typedef SpJobTable JT;
+    static const EvKernelFn<JT> tab[EV_KERNELS] = {
+        // has_m: (do_ncc, fuse_mlen) = (1, 1), (1, 0), (0, 1), (0, 0), each with (deep, known) = (1, 1), (1, 0), (0, 1), (0, 0)
+        k_cc_events<true, true, true, 1, false, JT, true, true>,     k_cc_events<true, true, true, 1, false, JT, true, false>,
+        k_cc_events<true, true, true, 1, false, JT, false, true>,    k_cc_events<true, true, true, 1, false, JT, false, false>,
+        k_cc_events<true, true, false, 1, false, JT, true, true>,    k_cc_events<true, true, false, 1, false, JT, true, false>,
+        k_cc_events<true, true, false, 1, false, JT, false, true>,   k_cc_events<true, true, false, 1, false, JT, false, false>,
+        k_cc_events<true, false, true, 1, false, JT, true, true>,    k_cc_events<true, false, true, 1, false, JT, true, false>,
+        k_cc_events<true, false, true, 1, false, JT, false, true>,   k_cc_events<true, false, true, 1, false, JT, false, false>,
+        k_cc_events<true, false, false, 1, false, JT, true, true>,   k_cc_events<true, false, false, 1, false, JT, true, false>,
+        k_cc_events<true, false, false, 1, false, JT, false, true>,  k_cc_events<true, false, false, 1, false, JT, false, false>,
+        // !has_m: known, !known
+        k_cc_events<false, true, false, 1, false, JT, false, true>,  k_cc_events<false, true, false, 1, false, JT, false, false>,
+    };
+    const int i = has_m ? (do_ncc ? 0 : 8) + (fuse_mlen ? 0 : 4) + (deep ? 0 : 2) + (known ? 0 : 1) : 16 + (known ? 0 : 1);
+    return {tab[i], i};
+}
 
+// max_shift <= 1023, pass 1 (sparse tiles): the event kernel over every chromosome; tiles whose lists would overflow are
+// flagged.  Pass 2: the window kernel for the tiles it flagged (the whole grid returns at once when there are none), which
+// adds its sums to the rows k_events_finish has written.  fuse != null: the mappable-length pairs up to fused_lag ride in
+// the event kernel and both window kernels share one launch (k_windows_flagged); row MLEN and scalar [2] are written here.
+static int launch_cc_events(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_shift, uint32_t read_len, bool do_ncc,
+                            uint32_t out_stride, bool zero_mlen, const ReduceSpec &rs, pmx_cc_options opt, uint32_t fused_lag,
+                            pmx_fused_mlen *fuse)
+{
+    const bool has_m = jobs[0].d_M != nullptr, fuse_mlen = fuse != nullptr;
+    const int32_t c = (int32_t)read_len - 1;
+    const u32 lgG = lg_slot_lanes(max_shift + 1);
+    std::vector<uint32_t> flag0(njobs);
+    EvFlagArea fl;
+    int rc = ev_flag_area(ctx, flag_layout(jobs, njobs, SP_TB, EV_NQ, false, flag0.data()), &fl);   // padding: an event tile flags EV_NQ window tiles
+    if (rc) return rc;
+    if (fuse_mlen) fuse->done = true;   // row MLEN and scalar [2] are written by this call (k_events_finish)
+    const bool deep = has_m && opt.deep_lists;   // PMX_FLAG_DEEP_LISTS: the larger list pool at four workgroups per CU
+    // the caller's hint, or the density probe's: the instantiations without the job-wide verdict on dense chromosomes
+    const bool known = opt.known_sparse;
+    const EvKernel<SpJobTable> kern = ev_kernel(has_m, do_ncc, fuse_mlen, deep, known);
+    // workgroups per CU: what the instantiation was built for (5 / 4 / 8), or fewer if this device takes fewer (the
+    // grid is one round of resident workgroups: a sixth that does not fit would run as a tail behind the others)
+    const u32 per_cu = ev_resident_per_cu(ctx, kern, has_m ? (deep ? 4 : EV_WAVES) : EV_WAVES_NCC);
+    const u32 nhr = (max_shift + 1 + 127) / 128;   // quads of R above a tile that hold partners of its forward reads
+    const SpKernelFn<SpJobTable> wkern = sp_kernel<SpJobTable, false>(has_m, do_ncc);   // (not launched when fuse_mlen)
+
+    for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS) {
+        const uint32_t n = njobs - lo < SP_MAXJOBS ? njobs - lo : SP_MAXJOBS;
+        const std::vector<VJob> vj = whole_jobs(jobs, lo, n, max_shift + 1, flag0.data());
+        // the flag entries of this launch's jobs
+        const u32 raw_lo = flag0[lo], raw_hi = lo + n < njobs ? flag0[lo + n] : (u32)fl.flag_bytes;
+        SpJobTable tab = {};
+        pmx_timed_launch tl;
+        // (the next 32 jobs: their own flagged-tile counters, job statistics and claim counters)
+        if (lo) PMX_HIP(hipMemsetAsync(fl.nflagged, 0, 16 + EV_STAT_BYTES + fl.claim_bytes, ctx->stream));
+        // (tile-range jobs -- a rank's share of a chromosome, pmx_cc_batch_ranges_dev -- exist for this launch only: the window
+        // launches behind it see whole chromosomes and take the tiles it flagged, which lie inside the ranges)
+        const LaunchPlan pe = plan_launch(ctx, vj.data(), n, false, per_cu, tab.j, EV_TB, true);
+        rc = pmx_ensure_slab(ctx, (size_t)(pe.nwg + n) * EV_SEG_ROWS * 1024 + (size_t)pe.nwg * 4 * 12 * 2 + 64);
+        if (rc) return rc;
+        if (known && has_m && ((size_t)pe.nwg + n > fl.claim_words || pe.total >= (1u << EV_CLAIM_JOB_SHIFT))) {   // (the launches that claim)
+            pmx_set_error("k_cc_events: %u workgroups + %u jobs, %u tiles exceed the claim counters", pe.nwg, n, pe.total);
+            return PMX_ERR_INVALID;
+        }
+        rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_EVENTS, &tl);
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern.fn, dim3(pe.nwg), dim3(256), 0, ctx->stream, tab, n, pe.total, pe.tiles_per_wg, (u32)c, max_shift, nhr,
+                           fused_lag, 1024u, (u32)EV_LO, (u32)EV_HI, ctx->d_slab, fl.flags, fl.flags_ac, fl.nflagged, fl.jobstat, fl.claim,
+                           ctx->debug_claim_mode);
+        PMX_CHECK_LAUNCH("k_cc_events");
+        rc = pmx_prof_end(ctx, &tl);
+        if (rc) return rc;
+
+        SpJobTable tabW = {}, tabA = {};
+        const LaunchPlan pw = plan_launch(ctx, vj.data(), n, false, has_m ? SP_WAVES : SP_WAVES_NCC, tabW.j);
+        rc = pmx_ensure_slab_fb(ctx, (size_t)(pw.nwg + n) * SP_SEG_ROWS * 1024 + (size_t)pw.nwg * 4 * 12 * 2 + 64);
+        if (rc) return rc;
+        // the flagged tiles in equal shares (one small block; returns at once when nothing was flagged)
+        if (pw.nwg > 2048) {
+            pmx_set_error("k_events_finish: %u workgroups exceed the planner's tables", pw.nwg);
+            return PMX_ERR_INVALID;
+        }
+        // (both window launches of this batch are planned in the same launch: the autocorrelation launch's shape is known here)
+        PlanLaunch pcc = {}, pac = {};
+        LaunchPlan pa = {};
+        fill_plan_launch(pcc, tabW, n, pw.total, pw.nwg, raw_lo, raw_hi, (u32)EV_NQ, fl.flags, fl.nflagged, fl.plan_cc);
+        if (fuse_mlen) {
+            const std::vector<VJob> va = whole_jobs(jobs, lo, n, fused_lag + 1, flag0.data());
+            pa = plan_launch(ctx, va.data(), n, true, AC_WAVES, tabA.j);
+            if (pa.nwg > 2048) {
+                pmx_set_error("k_events_finish: %u workgroups exceed the planner's tables", pa.nwg);
+                return PMX_ERR_INVALID;
+            }
+            fill_plan_launch(pac, tabA, n, pa.total, pa.nwg, raw_lo, raw_hi, 1u, fl.flags_ac, fl.nflagged + 1, fl.plan_ac);
+        }
+        // sums over the workgroups' segments, prefix sums, the mappable-length recurrence, the plan of the window launches
+        // and the clearing of the other flag area: ONE launch
+        EvFinishArgs fa = {};
+        fa.slab = ctx->d_slab;
+        fa.jobsum = EV_JOBSUM(fl.jobstat);
+        fa.S = max_shift;
+        fa.out_stride = out_stride;
+        fa.has_m = has_m ? 1u : 0u;
+        fa.do_ncc = do_ncc ? 1u : 0u;
+        fa.fused_mlen = fuse_mlen ? 1u : 0u;
+        fa.zero_mlen = zero_mlen ? 1u : 0u;
+        fa.keep_scalar2 = rs.keep_scalar2;
+        fa.zero_area = reinterpret_cast<uint4 *>(fl.other);
+        fa.zero_quads = (u32)(fl.other_dirty / 16);
+        hipLaunchKernelGGL(k_events_finish, dim3(EVF_CHUNKS, EVF_TASKS, n + 1), dim3(1024), 0, ctx->stream, tab, n, fa, pcc, pac);
+        PMX_CHECK_LAUNCH("k_events_finish");
+        ctx->flags_cc_dirty[(ctx->flags_cc_area & 1u)] = 0;   // (flags_cc_area already points at the other area: the next pass's)
+
+        if (fuse_mlen) {
+            // both window kernels for the flagged tiles in ONE launch (k_windows_flagged); each adds its shares to the rows
+            // itself, nothing is launched behind it.  Timed as the window kernel.
+            rc = pmx_ensure_slab_ac(ctx, (size_t)(pa.nwg + n) * AC_SEG_ROWS * 1024);
+            if (rc) return rc;
+            rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl, true);
+            if (rc) return rc;
+            WinCcArgs wa;
+            wa.total_tiles = pw.total; wa.tiles_per_wg = pw.tiles_per_wg; wa.lgG = lgG; wa.c = c;
+            wa.slab = ctx->d_slab_fb; wa.tile_flags = fl.flags; wa.plan = fl.plan_cc;
+            WinAcArgs aa;
+            aa.total_tiles = pa.total; aa.tiles_per_wg = pa.tiles_per_wg; aa.lgG = lg_slot_lanes(fused_lag + 1);
+            aa.add_shift = max_shift; aa.add_lag = fused_lag;
+            aa.slab = ctx->d_slab_ac; aa.tile_flags = fl.flags_ac; aa.plan = fl.plan_ac;
+            hipLaunchKernelGGL(do_ncc ? k_windows_flagged<true> : k_windows_flagged<false>, dim3(pw.nwg + pa.nwg), dim3(256), 0,
+                               ctx->stream, tabW, tabA, n, pw.nwg, wa, aa, (const u32 *)fl.nflagged, out_stride);
+            PMX_CHECK_LAUNCH("k_windows_flagged");
+            rc = pmx_prof_end(ctx, &tl);
+            if (rc) return rc;
+            continue;
+        }
+        rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl, true);
+        if (rc) return rc;
+        hipLaunchKernelGGL(wkern, dim3(pw.nwg), dim3(256), 0, ctx->stream, tabW, n, pw.total, pw.tiles_per_wg, c, lgG, ctx->d_slab_fb,
+                           (const unsigned char *)fl.flags, (const u32 *)fl.nflagged, (const u32 *)fl.plan_cc, out_stride);
+        PMX_CHECK_LAUNCH("k_cc_sparse");
+        rc = pmx_prof_end(ctx, &tl);
+        if (rc) return rc;
+    }
+    return PMX_OK;
+}
+
+// max_shift <= 1023, the window kernel alone over every tile (PMX_FLAG_WINDOW_ONLY, PMX_CC_EVENTS=0, vectors of 2^32 bits
+// and more); a reduce sums the per-workgroup slab segments into the result blocks.
+static int launch_cc_window(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_shift, uint32_t read_len, bool do_ncc,
+                            const ReduceSpec &rs)
+{
+    const bool has_m = jobs[0].d_M != nullptr;
+    const SpKernelFn<SpJobTable> kern = sp_kernel<SpJobTable, false>(has_m, do_ncc);
+    for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS) {
+        const uint32_t n = njobs - lo < SP_MAXJOBS ? njobs - lo : SP_MAXJOBS;
+        const std::vector<VJob> vj = whole_jobs(jobs, lo, n, max_shift + 1, nullptr);
+        SpJobTable tab = {};
+        const LaunchPlan p = plan_launch(ctx, vj.data(), n, false, has_m ? SP_WAVES : SP_WAVES_NCC, tab.j);
+        int rc = pmx_ensure_slab(ctx, (size_t)(p.nwg + n) * SP_SEG_ROWS * 1024 + (size_t)p.nwg * 4 * 12 * 2 + 64);
+        if (rc) return rc;
+        pmx_timed_launch tl;
+        rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl);
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(256), 0, ctx->stream, tab, n, p.total, p.tiles_per_wg, (int32_t)read_len - 1,
+                           lg_slot_lanes(max_shift + 1), ctx->d_slab, (const unsigned char *)nullptr, (const u32 *)nullptr,
+                           (const u32 *)nullptr, 0u);
+        PMX_CHECK_LAUNCH("k_cc_sparse");
+        rc = pmx_prof_end(ctx, &tl);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_reduce_segments, dim3(32, rs.nrows + rs.nzero, n), dim3(256), 0, ctx->stream, (const u32 *)ctx->d_slab, tab,
+                           (u32)SP_SEG_ROWS, rs, (const u32 *)nullptr);
+        PMX_CHECK_LAUNCH("k_reduce_segments");
+    }
+    return PMX_OK;
+}
+
+// which slab rows of the set-bit kernels go to which rows of the result blocks, and which rows are written as zeros
+static ReduceSpec cc_reduce_spec(bool has_m, bool do_ncc, bool zero_mlen, uint32_t out_stride)
+{
     ReduceSpec rs;
     memset(&rs, 0, sizeof rs);
     u32 nr = 0, nz = 0;
@@ -2770,23 +3109,32 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
     rs.nrows = nr;
     rs.nzero = nz;
     rs.out_stride = out_stride;
-    rs.use_out2 = 0;
     rs.keep_scalar2 = (has_m && !zero_mlen) ? 1 : 0;
+    return rs;
+}
 
-    if (!ctx->window_only && pmx_events_take_big(max_shift))
-        return launch_cc_events_big(ctx, jobs, njobs, max_shift, read_len, do_ncc, out_stride, rs, nr, nz, fused_lag, fused);
+int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_shift, uint32_t read_len,
+                               bool do_ncc, uint32_t out_stride, bool zero_mlen, pmx_cc_options opt, uint32_t fused_lag,
+                               pmx_fused_mlen *fused)
+{
+    if (fused) fused->done = false;
+    if (njobs == 0) return PMX_OK;
+    const bool has_m = jobs[0].d_M != nullptr;
+    if (!has_m && !do_ncc) return PMX_OK;
+    const ReduceSpec rs = cc_reduce_spec(has_m, do_ncc, zero_mlen, out_stride);
 
-    std::vector<VJob> vjobs;
-    expand_chunks(jobs, njobs, max_shift + 1, vjobs);
-    if (chunked)   // the window kernel alone over (chromosome x shift chunk) jobs (max_shift > 8191, or the event kernel disabled)
-        return launch_cc_window_chunks(ctx, vjobs, has_m, do_ncc, c, rs, nr, nz, nullptr, nullptr);
-
-    // Pass 1 (sparse tiles): the event kernel over every chromosome; tiles whose lists would overflow are flagged.
+    if (!opt.window_only && pmx_events_take_big(max_shift))
+        return launch_cc_events_big(ctx, jobs, njobs, max_shift, read_len, do_ncc, out_stride, rs, fused_lag, fused);
+    if (max_shift > 1023) {   // the window kernel alone over (chromosome x shift chunk) jobs (max_shift > 8191, or the event kernel disabled)
+        std::vector<VJob> vjobs;
+        expand_chunks(jobs, njobs, max_shift + 1, vjobs);
+        return launch_cc_window_chunks(ctx, vjobs, has_m, do_ncc, (int32_t)read_len - 1, rs, nullptr, nullptr);
+    }
     // (the event pass sums modulo 2^32 -- kernels_events.h, the transformed flush --: vectors of 2^32 bits and more, which no BAM
     // file can describe, stay on the window kernels)
     bool small_vectors = true;
     for (uint32_t i = 0; i < njobs; i++) small_vectors = small_vectors && jobs[i].nbits < (1ull << 32);
-    const bool use_events = events_enabled() && !ctx->window_only && !chunked && small_vectors;
+    const bool use_events = events_enabled() && !opt.window_only && small_vectors;
     const bool fuse_mlen = use_events && has_m && fused && njobs <= SP_MAXJOBS && pmx_events_can_fuse_mlen(max_shift, fused_lag);
     for (uint32_t i = 0; i < njobs; i++)
         if (jobs[i].tile_count && (!use_events || (has_m && fused && !fuse_mlen))) {
@@ -2794,220 +3142,10 @@ int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs
                           "PMX_FLAG_WINDOW_ONLY, PMX_CC_EVENTS=0 or vectors of 2^32 bits)");
             return PMX_ERR_INVALID;
         }
-    unsigned char *d_flags = nullptr, *d_flags_ac = nullptr;
-    u32 *d_nflagged = nullptr, *d_plan_cc = nullptr, *d_plan_ac = nullptr, *d_jobstat = nullptr, *d_claim = nullptr;
-    // the claim counters of the event kernel's pieces (kernels_events.h, EvClaimer): one word per (workgroup, job) index, behind
-    // the job statistics in the flag area -- zero at launch like everything there, cleared by the next pass's k_events_finish
-    const size_t claim_words = (size_t)ctx->num_cus * 8 + SP_MAXJOBS;   // (a launch is at most EV_WAVES_NCC workgroups per CU)
-    const size_t claim_bytes = (claim_words * sizeof(u32) + 15) / 16 * 16;
-    size_t flag_bytes_all = 0;     // raw length of a flag array (multiple of 16)
-    unsigned char *d_other_area = nullptr;   // the context's other flag area: cleared by this pass's k_events_finish
-    size_t other_dirty = 0;
-    if (use_events) {
-        uint64_t total_flags = 0;
-        for (size_t i = 0; i < vjobs.size(); i++) {
-            vjobs[i].flag0 = (uint32_t)total_flags;
-            total_flags += (vjobs[i].job->nbits + SP_TB - 1) / SP_TB + EV_NQ;   // padding: an event tile flags EV_NQ window tiles
-        }
-        const size_t flag_bytes = (size_t)((total_flags + 15) / 16 * 16);
-        const size_t stat_bytes = EV_STAT_BYTES;   // job statistics + the chromosomes' scalar totals
-        const size_t zero_bytes = 2 * flag_bytes + 16 + stat_bytes + claim_bytes;   // (a multiple of 16)
-        unsigned char *area = nullptr;
-        int rc = ev_flag_area(ctx, zero_bytes + 2 * PLAN_WORDS * sizeof(u32), zero_bytes, &area, &d_other_area, &other_dirty);
-        if (rc) return rc;
-        d_flags = area;                              // tiles of the cross-correlation window kernel (32 Kbit)
-        d_flags_ac = area + flag_bytes;              // tiles of the autocorrelation window kernel (64 Kbit), same flag0 per job
-        d_nflagged = (u32 *)(area + 2 * flag_bytes);
-        d_jobstat = (u32 *)(area + 2 * flag_bytes + 16);   // per job: tiles seen / read-dense / edge-dense (k_cc_events)
-        flag_bytes_all = flag_bytes;
-        d_claim = (u32 *)((unsigned char *)d_jobstat + stat_bytes);
-        d_plan_cc = (u32 *)((unsigned char *)d_claim + claim_bytes);   // work split of the two window launches (k_events_finish)
-        d_plan_ac = d_plan_cc + PLAN_WORDS;
-        if (fuse_mlen) fused->done = true;   // row MLEN and scalar [2] are written by this call (k_events_finish)
-    }
-    ReduceSpec rs_ev = rs;
-    for (u32 i = 0; i < nr; i++)
-        if (rs.dst_row[i] == PMX_ROW_MSCC_FSUM || rs.dst_row[i] == PMX_ROW_MSCC_RSUM) rs_ev.is_signed[i] = 1;
-
-    for (size_t lo = 0; lo < vjobs.size(); lo += SP_MAXJOBS) {
-        const uint32_t n = (uint32_t)(vjobs.size() - lo < SP_MAXJOBS ? vjobs.size() - lo : SP_MAXJOBS);
-        SpJobTable tab;
-        uint32_t total, tpw, nwg;
-        int rc;
-        pmx_timed_launch tl;
-        // the flag entries of this launch's jobs
-        const u32 raw_lo = use_events ? vjobs[lo].flag0 : 0u;
-        const u32 raw_hi = use_events ? (lo + n < vjobs.size() ? vjobs[lo + n].flag0 : (u32)flag_bytes_all) : 0u;
-        if (use_events) {
-            memset(&tab, 0, sizeof tab);
-            // (the next 32 jobs: their own flagged-tile counters and job statistics)
-            if (lo) PMX_HIP(hipMemsetAsync(d_nflagged, 0, 16 + EV_STAT_BYTES + claim_bytes, ctx->stream));   // (and claim counters)
-            const bool deep = has_m && ctx->deep_lists;   // PMX_FLAG_DEEP_LISTS: the larger list pool at four workgroups per CU
-            // the caller's hint, or the density probe's: the instantiations without the job-wide verdict on dense chromosomes
-            const bool known = ctx->known_sparse;
-            // workgroups per CU: what the instantiation was built for (5 / 4 / 8), or fewer if this device takes fewer (the
-            // grid is one round of resident workgroups: a sixth that does not fit would run as a tail behind the others)
-            u32 per_cu = has_m ? (deep ? 4 : EV_WAVES) : EV_WAVES_NCC;
-            {
-#define EV_OCC(HM, NC, ML, DP) (known ? ev_resident_per_cu<HM, NC, ML, DP, true>(ctx, per_cu) : ev_resident_per_cu<HM, NC, ML, DP, false>(ctx, per_cu))
-                if (has_m && do_ncc && fuse_mlen) per_cu = deep ? EV_OCC(true, true, true, true) : EV_OCC(true, true, true, false);
-                else if (has_m && do_ncc) per_cu = deep ? EV_OCC(true, true, false, true) : EV_OCC(true, true, false, false);
-                else if (has_m && fuse_mlen) per_cu = deep ? EV_OCC(true, false, true, true) : EV_OCC(true, false, true, false);
-                else if (has_m) per_cu = deep ? EV_OCC(true, false, false, true) : EV_OCC(true, false, false, false);
-                else per_cu = EV_OCC(false, true, false, false);
-#undef EV_OCC
-            }
-            // (tile-range jobs -- a rank's share of a chromosome, pmx_cc_batch_ranges_dev -- exist for this launch only: the window
-            // launches behind it see whole chromosomes and take the tiles it flagged, which lie inside the ranges)
-            for (uint32_t i = 0; i < n; i++) vjobs[lo + i].ranged = true;
-            plan_launch(ctx, &vjobs[lo], n, false, per_cu, &tab, &total, &tpw, &nwg, EV_TB);
-            for (uint32_t i = 0; i < n; i++) vjobs[lo + i].ranged = false;
-            rc = pmx_ensure_slab(ctx, (size_t)(nwg + n) * EV_SEG_ROWS * 1024 + (size_t)nwg * 4 * 12 * 2 + 64);
-            if (rc) return rc;
-            if (known && has_m && ((size_t)nwg + n > claim_words || total >= (1u << EV_CLAIM_JOB_SHIFT))) {   // (the launches that claim)
-                pmx_set_error("k_cc_events: %u workgroups + %u jobs, %u tiles exceed the claim counters", nwg, n, total);
-                return PMX_ERR_INVALID;
-            }
-            rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_EVENTS, &tl);
-            if (rc) return rc;
-            const u32 nhr = (max_shift + 1 + 127) / 128;   // quads of R above a tile that hold partners of its forward reads
-#define EV_LAUNCH__(HM, NC, ML, DP, KS)                                                                                \
-    hipLaunchKernelGGL((k_cc_events<HM, NC, ML, 1, false, SpJobTable, DP, KS>), dim3(nwg), dim3(256), 0, ctx->stream, tab, n, total, tpw, \
-                       (u32)c, max_shift, nhr, fused_lag, 1024u, (u32)EV_LO, (u32)EV_HI, ctx->d_slab, d_flags, d_flags_ac, d_nflagged, d_jobstat, \
-                       d_claim, ctx->debug_claim_mode)
-#define EV_LAUNCH_(HM, NC, ML, DP)                \
-    do {                                          \
-        if (known) EV_LAUNCH__(HM, NC, ML, DP, true); \
-        else EV_LAUNCH__(HM, NC, ML, DP, false);  \
-    } while (0)
-#define EV_LAUNCH(HM, NC, ML)                \
-    do {                                     \
-        if (deep) EV_LAUNCH_(HM, NC, ML, HM); \
-        else EV_LAUNCH_(HM, NC, ML, false);  \
-    } while (0)
-            if (has_m && do_ncc && fuse_mlen) EV_LAUNCH(true, true, true);
-            else if (has_m && do_ncc) EV_LAUNCH(true, true, false);
-            else if (has_m && fuse_mlen) EV_LAUNCH(true, false, true);
-            else if (has_m) EV_LAUNCH(true, false, false);
-            else EV_LAUNCH_(false, true, false, false);
-#undef EV_LAUNCH
-#undef EV_LAUNCH_
-#undef EV_LAUNCH__
-            PMX_CHECK_LAUNCH("k_cc_events");
-            rc = pmx_prof_end(ctx, &tl);
-            if (rc) return rc;
-        }
-        // Pass 2 (window kernel): every tile, or -- behind the event pass -- only the tiles it flagged (the whole grid returns
-        // at once when there are none).  Behind the event pass it adds its sums to the rows k_events_finish has written.
-        SpJobTable tabW, tabA;
-        std::vector<VJob> va(n);
-        for (auto &v : va) v.ranged = false;
-        uint32_t totalA = 0, tpwA = 0, nwgA = 0;
-        memset(&tabW, 0, sizeof tabW);
-        plan_launch(ctx, &vjobs[lo], n, false, chunked ? (has_m ? SP_WAVES_CH : SP_WAVES_CH_NCC) : (has_m ? SP_WAVES : SP_WAVES_NCC), &tabW, &total, &tpw, &nwg);
-        const size_t wwords = (size_t)(nwg + n) * SP_SEG_ROWS * 1024 + (size_t)nwg * 4 * 12 * 2 + 64;
-        rc = use_events ? pmx_ensure_slab_fb(ctx, wwords) : pmx_ensure_slab(ctx, wwords);
-        if (rc) return rc;
-        u32 *const wslab = use_events ? ctx->d_slab_fb : ctx->d_slab;
-        if (use_events) {
-            // the flagged tiles in equal shares (one small block; returns at once when nothing was flagged)
-            if (nwg > 2048) {
-                pmx_set_error("k_events_finish: %u workgroups exceed the planner's tables", nwg);
-                return PMX_ERR_INVALID;
-            }
-            // (both window launches of this batch are planned in the same launch: the autocorrelation launch's shape is known here)
-            PlanLaunch pcc, pac;
-            memset(&pcc, 0, sizeof pcc);
-            memset(&pac, 0, sizeof pac);
-            fill_plan_launch(pcc, tabW, n, total, nwg, raw_lo, raw_hi, (u32)EV_NQ, (const unsigned char *)d_flags, d_nflagged, d_plan_cc);
-            if (fuse_mlen) {
-                for (uint32_t i = 0; i < n; i++) {
-                    va[i].job = vjobs[lo + i].job;
-                    va[i].d_off = 0;
-                    va[i].d_n = fused_lag + 1;
-                    va[i].flag0 = vjobs[lo + i].flag0;
-                }
-                memset(&tabA, 0, sizeof tabA);
-                plan_launch(ctx, va.data(), n, true, AC_WAVES, &tabA, &totalA, &tpwA, &nwgA);
-                if (nwgA > 2048) {
-                    pmx_set_error("k_events_finish: %u workgroups exceed the planner's tables", nwgA);
-                    return PMX_ERR_INVALID;
-                }
-                fill_plan_launch(pac, tabA, n, totalA, nwgA, raw_lo, raw_hi, 1u, (const unsigned char *)d_flags_ac, d_nflagged + 1, d_plan_ac);
-            }
-            // sums over the workgroups' segments, prefix sums, the mappable-length recurrence, the plan of the window launches
-            // and the clearing of the other flag area: ONE launch (k_reduce_segments2 + k_plan_flagged + half of k_events_tail + a
-            // memset until round 3)
-            EvFinishArgs fa;
-            memset(&fa, 0, sizeof fa);
-            fa.slab = ctx->d_slab;
-            fa.jobsum = EV_JOBSUM(d_jobstat);
-            fa.S = max_shift;
-            fa.out_stride = out_stride;
-            fa.has_m = has_m ? 1u : 0u;
-            fa.do_ncc = do_ncc ? 1u : 0u;
-            fa.fused_mlen = fuse_mlen ? 1u : 0u;
-            fa.zero_mlen = zero_mlen ? 1u : 0u;
-            fa.keep_scalar2 = rs.keep_scalar2;
-            fa.zero_area = reinterpret_cast<uint4 *>(d_other_area);
-            fa.zero_quads = (u32)(other_dirty / 16);
-            hipLaunchKernelGGL(k_events_finish, dim3(EVF_CHUNKS, EVF_TASKS, n + 1), dim3(1024), 0, ctx->stream, tab, n, fa, pcc, pac);
-            PMX_CHECK_LAUNCH("k_events_finish");
-            ctx->flags_cc_dirty[(ctx->flags_cc_area & 1u)] = 0;   // (flags_cc_area already points at the other area: the next pass's)
-        }
-        if (use_events && fuse_mlen) {
-            // both window kernels for the flagged tiles in ONE launch (k_windows_flagged); each adds its shares to the rows
-            // itself, nothing is launched behind it (k_events_tail until round 3).  Timed as the window kernel.
-            rc = pmx_ensure_slab_ac(ctx, (size_t)(nwgA + n) * AC_SEG_ROWS * 1024);
-            if (rc) return rc;
-            rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl, true);
-            if (rc) return rc;
-            WinCcArgs wa;
-            wa.total_tiles = total; wa.tiles_per_wg = tpw; wa.lgG = lgG; wa.c = c;
-            wa.slab = wslab; wa.tile_flags = d_flags; wa.plan = d_plan_cc;
-            WinAcArgs aa;
-            aa.total_tiles = totalA; aa.tiles_per_wg = tpwA; aa.lgG = lg_slot_lanes(fused_lag + 1);
-            aa.add_shift = max_shift; aa.add_lag = fused_lag;
-            aa.slab = ctx->d_slab_ac; aa.tile_flags = d_flags_ac; aa.plan = d_plan_ac;
-            if (do_ncc)
-                hipLaunchKernelGGL(k_windows_flagged<true>, dim3(nwg + nwgA), dim3(256), 0, ctx->stream, tabW, tabA, n, nwg, wa, aa,
-                                   (const u32 *)d_nflagged, out_stride);
-            else
-                hipLaunchKernelGGL(k_windows_flagged<false>, dim3(nwg + nwgA), dim3(256), 0, ctx->stream, tabW, tabA, n, nwg, wa, aa,
-                                   (const u32 *)d_nflagged, out_stride);
-            PMX_CHECK_LAUNCH("k_windows_flagged");
-            rc = pmx_prof_end(ctx, &tl);
-            if (rc) return rc;
-            continue;
-        }
-        rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl, use_events);
-        if (rc) return rc;
-#define SP_LAUNCH(HM, NC, CK)                                                                                       \
-    hipLaunchKernelGGL((k_cc_sparse<HM, NC, CK>), dim3(nwg), dim3(256), 0, ctx->stream, tabW, n, total, tpw, c, lgG, \
-                       wslab, (const unsigned char *)d_flags, (const u32 *)d_nflagged, (const u32 *)(use_events ? d_plan_cc : nullptr), \
-                       use_events ? out_stride : 0u)
-        if (chunked) {
-            if (has_m && do_ncc) SP_LAUNCH(true, true, true);
-            else if (has_m) SP_LAUNCH(true, false, true);
-            else SP_LAUNCH(false, true, true);
-        } else {
-            if (has_m && do_ncc) SP_LAUNCH(true, true, false);
-            else if (has_m) SP_LAUNCH(true, false, false);
-            else SP_LAUNCH(false, true, false);
-        }
-#undef SP_LAUNCH
-        PMX_CHECK_LAUNCH("k_cc_sparse");
-        rc = pmx_prof_end(ctx, &tl);
-        if (rc) return rc;
-        if (!use_events) {
-            // sum the per-workgroup slab segments into the result blocks
-            hipLaunchKernelGGL(k_reduce_segments, dim3(32, nr + nz, n), dim3(256), 0, ctx->stream, (const u32 *)ctx->d_slab, tabW,
-                               (u32)SP_SEG_ROWS, rs, (const u32 *)nullptr);
-            PMX_CHECK_LAUNCH("k_reduce_segments");
-            continue;
-        }
-    }
-    return PMX_OK;
+    if (use_events)
+        return launch_cc_events(ctx, jobs, njobs, max_shift, read_len, do_ncc, out_stride, zero_mlen, rs, opt, fused_lag,
+                                fuse_mlen ? fused : nullptr);
+    return launch_cc_window(ctx, jobs, njobs, max_shift, read_len, do_ncc, rs);
 }
 
 size_t pmx_autocorr_scratch_words(uint32_t max_lag)
@@ -3023,154 +3161,4 @@ int pmx_launch_autocorr_edges_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t 
                                     uint32_t read_len, uint32_t max_shift, uint32_t out_stride)
 {
     return launch_autocorr_batch(ctx, jobs, njobs, max_lag, mode, read_len, max_shift, out_stride, nullptr, nullptr, nullptr);
-}
-
-// pre_flags != nullptr: the event kernel (max_shift > 1023, fused mappable-length pairs) has left the pair sums, popcount(M)
-// and the run count in the jobs' scratch and flagged the tiles whose run edges it could not list (pre_flag0[job]: index of
-// the job's first tile in pre_flags): only the window kernel for those tiles + the recurrence remain.
-static int launch_autocorr_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_lag, uint32_t mode,
-                                 uint32_t read_len, uint32_t max_shift, uint32_t out_stride, const uint32_t *pre_flag0,
-                                 const unsigned char *pre_flags, const u32 *pre_nflagged)
-{
-    if (njobs == 0) return PMX_OK;
-    const bool chunked = max_lag > 1023;
-    const u32 lagcap = (u32)(((size_t)max_lag + 1 + 1023) / 1024 * 1024);
-    const u32 lgG = chunked ? 5u : lg_slot_lanes(max_lag + 1);
-    typedef SpJobTableRef JT;   // job tables in device memory: every chromosome of the batch in one launch of each kernel
-
-    // Pass 1 (sparse-edge tiles): pair enumeration over every chromosome; tiles with more than AP_CAP edges are flagged.
-    // PMX_AUTOCORR_PAIRS=0 in the environment keeps everything on the window kernel (A/B measurements, tests).
-    static const bool pairs_enabled = [] {
-        const char *e = getenv("PMX_AUTOCORR_PAIRS");
-        return !(e && e[0] == '0');
-    }();
-    const bool use_pairs = !pre_flags && pairs_enabled && max_lag + 1 <= AP_MAX_LAGS;
-    std::vector<uint32_t> flag0(njobs, 0);
-    unsigned char *d_flags = const_cast<unsigned char *>(pre_flags);
-    u32 *d_nflagged = const_cast<u32 *>(pre_nflagged);
-    if (pre_flags)
-        for (uint32_t i = 0; i < njobs; i++) flag0[i] = pre_flag0[i];
-    const u32 nl = (max_lag + 1 + 63) / 64 * 64;
-    int rc;
-    if (use_pairs) {
-        uint64_t total_flags = 0;
-        for (uint32_t i = 0; i < njobs; i++) {
-            flag0[i] = (uint32_t)total_flags;
-            total_flags += (jobs[i].nbits + 1 + AC_TB - 1) / AC_TB + AP_NQ / AC_NQ;   // padding: a pair tile flags AP_NQ / AC_NQ window tiles
-        }
-        const size_t flag_bytes = (size_t)((total_flags + 15) / 16 * 16);
-        rc = pmx_ensure_flags(ctx, flag_bytes + 16);
-        if (rc) return rc;
-        d_flags = ctx->d_flags;
-        d_nflagged = (u32 *)(ctx->d_flags + flag_bytes);
-        PMX_HIP(hipMemsetAsync(ctx->d_flags, 0, flag_bytes + 16, ctx->stream));
-        const u32 nh = (max_lag + 1 + 127) / 128;   // quads above a tile that hold partners of its drivers
-        const size_t lds_bytes = (2 * (size_t)nl + 2 * AP_CAP + 32 + 16) * sizeof(u32);
-        const size_t seg_stride = 2 * (size_t)nl + 16;
-        // workgroups per CU: 8 by registers; the histograms may allow fewer
-        u32 per_cu = (u32)((160u * 1024u) / (lds_bytes + 512));
-        if (per_cu > AP_WAVES) per_cu = AP_WAVES;
-        if (per_cu < 1) per_cu = 1;
-        for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS_REF) {
-            const uint32_t n = njobs - lo < SP_MAXJOBS_REF ? njobs - lo : SP_MAXJOBS_REF;
-            std::vector<VJob> vj(n);
-            for (auto &v : vj) v.ranged = false;
-            for (uint32_t i = 0; i < n; i++) {
-                vj[i].job = &jobs[lo + i];
-                vj[i].d_off = 0;
-                vj[i].d_n = max_lag + 1;
-                vj[i].flag0 = flag0[lo + i];
-            }
-            std::vector<SpJobDev> tab(n);
-            memset(tab.data(), 0, n * sizeof(SpJobDev));
-            uint32_t total, tpw, nwg;
-            plan_launch(ctx, vj.data(), n, true, per_cu, tab.data(), &total, &tpw, &nwg, AP_TB);
-            rc = pmx_ensure_slab2(ctx, (size_t)(nwg + n) * seg_stride);
-            if (rc) return rc;
-            JT ref;
-            rc = upload_table(ctx, tab, &ref);
-            if (rc) return rc;
-            if (lds_bytes > 64 * 1024) {   // (max_lag above ~7870: the histograms alone pass 64 KB)
-                static bool attr_set[EV_MAX_DEVICES];   // (per device, see ev_big_launch)
-                const int dev = ctx->device >= 0 && ctx->device < EV_MAX_DEVICES ? ctx->device : -1;
-                if (dev < 0 || !attr_set[dev]) {
-                    PMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_autocorr_pairs<JT>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-                    if (dev >= 0) attr_set[dev] = true;
-                }
-            }
-            pmx_timed_launch tl;
-            rc = pmx_prof_begin(ctx, PMX_KERNEL_AUTOCORR, &tl);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_autocorr_pairs<JT>, dim3(nwg), dim3(256), lds_bytes, ctx->stream, ref, n, total, tpw, max_lag, nl,
-                               nh, ctx->d_slab2, d_flags, d_nflagged);
-            PMX_CHECK_LAUNCH("k_autocorr_pairs");
-            rc = pmx_prof_end(ctx, &tl);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_reduce_pairs<JT>, dim3((max_lag + 1 + 31) / 32 < 64 ? (max_lag + 1 + 31) / 32 : 64, 3, n), dim3(256), 0,
-                               ctx->stream, (const u32 *)ctx->d_slab2, ref, nl, max_lag, lagcap, 0u);
-            PMX_CHECK_LAUNCH("k_reduce_pairs");
-        }
-    }
-
-    // Pass 2 (window kernel): every tile, or -- behind the pair pass -- only the tiles it flagged as dense (the whole
-    // grid returns at once when there are none); its sums are ADDED to what the pair pass left in the per-job scratch.
-    std::vector<VJob> vjobs;
-    expand_chunks(jobs, njobs, max_lag + 1, vjobs, flag0.data());
-
-    ReduceSpec rs;
-    memset(&rs, 0, sizeof rs);
-    rs.nrows = 3;
-    rs.src_row[0] = 0; rs.dst_row[0] = 0;            // P
-    rs.src_row[1] = 1; rs.dst_row[1] = lagcap;       // N
-    rs.src_row[2] = 2; rs.dst_row[2] = 2 * lagcap; rs.is_scalar[2] = 1;
-    rs.use_out2 = 1;
-    rs.accumulate = (use_pairs || pre_flags) ? 1 : 0;
-    rs.out_stride = out_stride;
-
-    for (size_t lo = 0; lo < vjobs.size(); lo += SP_MAXJOBS_REF) {
-        const uint32_t n = (uint32_t)(vjobs.size() - lo < SP_MAXJOBS_REF ? vjobs.size() - lo : SP_MAXJOBS_REF);
-        std::vector<SpJobDev> tab(n);
-        memset(tab.data(), 0, n * sizeof(SpJobDev));
-        uint32_t total, tpw, nwg;
-        plan_launch(ctx, &vjobs[lo], n, true, chunked ? AC_WAVES_CH : AC_WAVES, tab.data(), &total, &tpw, &nwg);
-        rc = pmx_ensure_slab_ac(ctx, (size_t)(nwg + n) * AC_SEG_ROWS * 1024);
-        if (rc) return rc;
-        JT ref;
-        rc = upload_table(ctx, tab, &ref);
-        if (rc) return rc;
-        pmx_timed_launch tl;
-        rc = pmx_prof_begin(ctx, PMX_KERNEL_AUTOCORR, &tl);
-        if (rc) return rc;
-        if (chunked)
-            hipLaunchKernelGGL((k_autocorr_edges<true, JT>), dim3(nwg), dim3(256), 0, ctx->stream, ref, n, total, tpw, lgG,
-                               ctx->d_slab_ac, (const unsigned char *)d_flags, (const u32 *)d_nflagged, (const u32 *)nullptr);
-        else
-            hipLaunchKernelGGL((k_autocorr_edges<false, JT>), dim3(nwg), dim3(256), 0, ctx->stream, ref, n, total, tpw, lgG,
-                               ctx->d_slab_ac, (const unsigned char *)d_flags, (const u32 *)d_nflagged, (const u32 *)nullptr);
-        PMX_CHECK_LAUNCH("k_autocorr_edges");
-        rc = pmx_prof_end(ctx, &tl);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_reduce_segments<JT>, dim3(32, 3, n), dim3(256), 0, ctx->stream, (const u32 *)ctx->d_slab_ac, ref,
-                           (u32)AC_SEG_ROWS, rs, (const u32 *)d_nflagged);
-        PMX_CHECK_LAUNCH("k_reduce_segments");
-    }
-    // the recurrence needs every chunk of a chromosome: run it once all launches are queued (same stream)
-    for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS_REF) {
-        const uint32_t n = njobs - lo < SP_MAXJOBS_REF ? njobs - lo : SP_MAXJOBS_REF;
-        std::vector<SpJobDev> tab(n);
-        memset(tab.data(), 0, n * sizeof(SpJobDev));
-        for (uint32_t i = 0; i < n; i++) {
-            tab[i].flags = 1;
-            tab[i].out = (u64 *)jobs[lo + i].d_out;
-            tab[i].out2 = (u64 *)jobs[lo + i].d_out2;
-        }
-        JT ref;
-        rc = upload_table(ctx, tab, &ref);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_autocorr_finish<JT>, dim3(n), dim3(AC_FINISH_THREADS), 0, ctx->stream, ref, max_lag, lagcap, mode,
-                           (int32_t)read_len - 1, max_shift, out_stride);
-        PMX_CHECK_LAUNCH("k_autocorr_finish");
-    }
-    return PMX_OK;
 }

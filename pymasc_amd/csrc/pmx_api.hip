@@ -71,9 +71,6 @@ int pmx_ctx_create(int device, void *hip_stream, pmx_ctx **out)
     ctx->device = device;
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     ctx->profiling = 0;
-    ctx->window_only = false;
-    ctx->deep_lists = false;
-    ctx->known_sparse = false;
     ctx->debug_max_wg = 0;
     ctx->debug_claim_mode = 0;
     ctx->d_scratch = nullptr;
@@ -1501,10 +1498,7 @@ static int cc_batch_impl(pmx_ctx *ctx, uint32_t njobs, const uint64_t *const *d_
     }
     // no hint from the caller: take one from a sample of the vectors (one small launch, one synchronisation)
     bool probed = false;
-    static const bool probe_enabled = [] {   // PMX_DENSITY_PROBE=0: never (A/B, tests of the unhinted event path)
-        const char *e = getenv("PMX_DENSITY_PROBE");
-        return !(e && e[0] == '0');
-    }();
+    static const bool probe_enabled = pmx_env_enabled("PMX_DENSITY_PROBE");   // =0: never (A/B, tests of the unhinted event path)
     // (PMX_FLAG_FORCE_SPARSE: the set-bit path exactly as it is without a hint -- the event kernel finds dense tiles itself)
     if (probe_enabled && !(flags & (PMX_FLAG_WINDOW_ONLY | PMX_FLAG_DEEP_LISTS | PMX_FLAG_EVENTS_HINT | PMX_FLAG_FORCE_SPARSE)) &&
         pmx_events_used(max_shift)) {
@@ -1536,16 +1530,14 @@ static int cc_batch_impl(pmx_ctx *ctx, uint32_t njobs, const uint64_t *const *d_
         // fork: the mappable-length pass on the auxiliary stream, beside the set-bit kernel (they share no output word:
         // row MLEN and scalar [2] belong to the autocorrelation, everything else to the cross-correlation)
         // PMX_AUTOCORR_FORK=0 in the environment keeps everything on the caller's stream (per-kernel profiling)
-        ctx->window_only = (flags & PMX_FLAG_WINDOW_ONLY) != 0;
-        ctx->deep_lists = (flags & PMX_FLAG_DEEP_LISTS) != 0;
+        pmx_cc_options opt;
+        opt.window_only = (flags & PMX_FLAG_WINDOW_ONLY) != 0;
+        opt.deep_lists = (flags & PMX_FLAG_DEEP_LISTS) != 0;
         // PMX_FLAG_EVENTS_HINT / PMX_FLAG_DEEP_LISTS from the caller, or the probe's own choice of either (it ran and did not
         // choose the window kernels): the event kernel without its job-wide verdict.  PMX_FLAG_FORCE_SPARSE keeps the verdict.
-        ctx->known_sparse = !(flags & PMX_FLAG_FORCE_SPARSE) && !ctx->window_only &&
-                            ((flags & (PMX_FLAG_EVENTS_HINT | PMX_FLAG_DEEP_LISTS)) != 0 || probed);
-        static const bool fork_enabled = [] {
-            const char *e = getenv("PMX_AUTOCORR_FORK");
-            return !(e && e[0] == '0');
-        }();
+        opt.known_sparse = !(flags & PMX_FLAG_FORCE_SPARSE) && !opt.window_only &&
+                           ((flags & (PMX_FLAG_EVENTS_HINT | PMX_FLAG_DEEP_LISTS)) != 0 || probed);
+        static const bool fork_enabled = pmx_env_enabled("PMX_AUTOCORR_FORK");
         // beside the shift-chunked instantiation (max_shift > 1023) the fork does not pay (config 5 on one GPU: 17.4 ms
         // forked, 16.5 ms in sequence): the pair pass then holds 40 KB of histograms per workgroup
         static const bool fork_big = [] {   // PMX_AUTOCORR_FORK_BIG=1: also beside the event kernel of max_shift > 1023 (A/B)
@@ -1555,14 +1547,14 @@ static int cc_batch_impl(pmx_ctx *ctx, uint32_t njobs, const uint64_t *const *d_
         // (not behind the density probe either: its synchronisation has drained the stream, so the forked chain and the window
         // kernel would START together -- the window kernel's workgroups own fixed tile ranges, and the ones that find their CU
         // taken for the first 0.1 ms double up elsewhere for the whole launch: 6.6 -> 10.2 ms at 5 % reads per strand, measured)
-        const bool fork = fork_enabled && !probed && (max_shift <= 1023 || (pmx_events_take_big(max_shift) && !ctx->window_only &&
+        const bool fork = fork_enabled && !probed && (max_shift <= 1023 || (pmx_events_take_big(max_shift) && !opt.window_only &&
                                                                  (fork_big || pmx_events_big_subgroups(max_shift, has_m ? 1 : 0) == 1)));
         int rc;
-        if (do_mlen && !ctx->window_only && pmx_events_can_fuse_mlen(max_shift, max_lag)) {
+        if (do_mlen && !opt.window_only && pmx_events_can_fuse_mlen(max_shift, max_lag)) {
             // the event kernel stages M and lists its run edges anyway: it takes the edge pairs of the mappable-length pass
             // too, and only the window kernel for the tiles it flagged + the recurrence remain of that pass
             pmx_fused_mlen fm;
-            rc = pmx_launch_cc_sparse_batch(ctx, jobs.data(), n, max_shift, read_len, do_ncc, stride, false, max_lag, &fm);
+            rc = pmx_launch_cc_sparse_batch(ctx, jobs.data(), n, max_shift, read_len, do_ncc, stride, false, opt, max_lag, &fm);
             if (rc) return rc;
             if (!fm.done) {   // (not expected: the launcher declined the fusion)
                 rc = pmx_launch_autocorr_edges_batch(ctx, jobs.data(), n, max_lag, 1, read_len, max_shift, stride);
@@ -1575,7 +1567,7 @@ static int cc_batch_impl(pmx_ctx *ctx, uint32_t njobs, const uint64_t *const *d_
         // Behind the probe, window kernels alone: the chain is forked LATE -- queued on the auxiliary stream behind the window
         // kernel's launch (but not behind its completion: the mark is recorded in front of it).  The window kernel starts
         // alone and owns the CUs; the chain's kernels move in as its workgroups drain, under its tail.
-        const bool late_fork = fork_enabled && probed && do_mlen && ctx->window_only && max_shift <= 1023;
+        const bool late_fork = fork_enabled && probed && do_mlen && opt.window_only && max_shift <= 1023;
         if (late_fork) {
             PMX_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
         } else if (do_mlen && !fork) {
@@ -1602,7 +1594,7 @@ static int cc_batch_impl(pmx_ctx *ctx, uint32_t njobs, const uint64_t *const *d_
             if (forked) (void)join();
             return rc;
         }
-        rc = pmx_launch_cc_sparse_batch(ctx, jobs.data(), n, max_shift, read_len, do_ncc, stride, !do_mlen);
+        rc = pmx_launch_cc_sparse_batch(ctx, jobs.data(), n, max_shift, read_len, do_ncc, stride, !do_mlen, opt);
         if (late_fork && !rc) {
             PMX_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
             hipStream_t main_stream = ctx->stream;

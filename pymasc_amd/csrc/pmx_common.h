@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -12,6 +13,14 @@ typedef unsigned long long u64;   // what atomicAdd(unsigned long long*) wants; 
 typedef unsigned int u32;
 
 void pmx_set_error(const char *fmt, ...);
+
+// an on-by-default switch of the environment: false only when the variable is set and starts with '0'
+// (call sites read it once per process: static const bool x = pmx_env_enabled("..."))
+static inline bool pmx_env_enabled(const char *name)
+{
+    const char *e = getenv(name);
+    return !(e && e[0] == '0');
+}
 
 #define PMX_HIP(call)                                                                       \
     do {                                                                                    \
@@ -65,9 +74,6 @@ struct pmx_ctx {
     hipStream_t aux_stream;
     hipEvent_t ev_fork, ev_join;
     int num_cus;
-    bool window_only;            // PMX_FLAG_WINDOW_ONLY of the call in progress (pmx_cc_batch_dev)
-    bool deep_lists;             // PMX_FLAG_DEEP_LISTS of the call in progress
-    bool known_sparse;           // ... its data is known to fit the event kernel's lists (a hint, or the density probe): no job-wide verdict
     uint32_t debug_max_wg;       // 0: off; tests: cap on the persistent workgroups of a launch (many tiles per workgroup on small inputs)
     uint32_t debug_claim_mode;   // 0: off; tests and A/B runs: how the hinted event kernel hands out tiles (pmx_debug_set_claim_mode)
     int profiling;               // 0 off; 1: kernels that do work; 2: also the (usually empty) fallback launches behind the event kernel
@@ -221,10 +227,16 @@ int pmx_events_big_subgroups(uint32_t max_shift, int has_m);
 uint32_t pmx_sparse_max_jobs(void);
 uint32_t pmx_cc_batch_jobs(uint32_t max_shift);   // jobs per call of pmx_launch_cc_sparse_batch (device-side job tables beyond 1023 shifts)
 uint32_t pmx_autocorr_batch_jobs(void);           // ... of pmx_launch_autocorr_edges_batch
+// options of one call (pmx_cc_batch_dev fills them from its flags and the density probe)
+struct pmx_cc_options {
+    bool window_only;    // PMX_FLAG_WINDOW_ONLY: the window kernels alone
+    bool deep_lists;     // PMX_FLAG_DEEP_LISTS: the event kernel's larger list pool
+    bool known_sparse;   // the data is known to fit the event kernel's lists (a hint, or the density probe): no job-wide verdict
+};
 // Writes rows NCC_CCBINS / MSCC_FSUM / MSCC_CCBINS / MSCC_RSUM and the scalar row of every job's result block
 // (rows the batch does not produce are written as zeros, MLEN included when there is no mappability).
 int pmx_launch_cc_sparse_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, uint32_t max_shift,
-                               uint32_t read_len, bool do_ncc, uint32_t out_stride, bool zero_mlen,
+                               uint32_t read_len, bool do_ncc, uint32_t out_stride, bool zero_mlen, pmx_cc_options opt,
                                uint32_t fused_lag = 0xffffffffu, pmx_fused_mlen *fused = nullptr);
 // fused_lag / fused: let the event kernel enumerate the edge pairs up to that lag as well (njobs <= pmx_sparse_max_jobs())
 // zero_mlen == false: the autocorrelation pass (possibly running concurrently) owns row MLEN and scalar [2]: both are left alone
