@@ -16,7 +16,8 @@ Parity pin (see tests/test_oracle_golden.py): the reference's own goldens
 ``tests/golden/ENCFF000RMB-test_{cc,mscc,nreads}.tab`` and ``hg19_36mer-test_mappability.json``
 (copied as data fixtures into tests/golden/), plus vectors generated here by the reference's
 compiled ``successive`` NCC calculator (tests/golden/ref_successive_ncc.json, made by
-oracle/make_ref_vectors.py).  The BitArray C library the reference links is not in
+oracle/make_ref_vectors.py) and by its compiled ``successive`` MSCC calculator
+(tests/golden/ref_successive_mscc.json.gz, made by oracle/make_ref_mscc_vectors.py).  The BitArray C library the reference links is not in
 /root/reference (empty submodule), so the reference's bitarray extension itself cannot be built.
 """
 from __future__ import annotations

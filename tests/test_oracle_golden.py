@@ -1,15 +1,20 @@
 """Pins the CPU oracle (oracle/) to everything the reference's own tests hold for this path:
 the CLI goldens of tests/integration/test_golden_outputs.py:44-226 (-d 300 -q 10 -r 36 with the
 36-mer mappability track), the lag table JSON, and vectors produced by the reference's compiled
-`successive` NCC calculator (oracle/make_ref_vectors.py)."""
+`successive` NCC calculator (oracle/make_ref_vectors.py) and by its `successive` MSCC calculator
+(oracle/make_ref_mscc_vectors.py)."""
+import glob
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 from oracle import model as oracle
 from . import fixtures as fx
+from . import ref_mscc_cases as rm
 from .helpers import feed_all
 
 
@@ -87,6 +92,87 @@ def test_against_reference_successive_ncc(case):
         assert np.array_equal(np.isnan(ecc), np.isnan(ncc["cc"]))
         m = ~np.isnan(ecc)
         np.testing.assert_allclose(ncc["cc"][m], ecc[m], rtol=0, atol=1e-15)
+
+
+@pytest.fixture(scope="module")
+def mscc_oracle_runs():
+    """every case of the reference's successive MSCC vectors through the CPU oracle, once"""
+    cache = {}
+
+    def get(case):
+        if case["name"] not in cache:
+            calc = oracle.OracleCalculator(case["max_shift"], case["read_len"], [n for n, _ in case["chroms"]],
+                                           [g for _, g in case["chroms"]], mappability=rm.track_of(case))
+            rm.feed(calc, case)
+            calc.finishup_calculation()
+            cache[case["name"]] = calc
+        return cache[case["name"]]
+    return get
+
+
+@pytest.mark.parametrize("case", rm.CASES, ids=rm.IDS)
+def test_against_reference_successive_mscc(case, mscc_oracle_runs):
+    """The oracle restates the reference's BITARRAY calculator; its compiled SUCCESSIVE calculator is the second witness.
+    Integers exactly, the lag table over the lags both sides hold (the reference's feeder: max_shift + 1, the bitarray
+    calculator: max(L, S - L + 2)), cc within the tolerance used against the reference's tables.  The read-length sums: the
+    successive calculator leaves out the reads that contribute to no lag and keeps them genome-wide only
+    (oracle/make_ref_mscc_vectors.py, docstring, 3), so the oracle's sums less those reads must be its figures exactly."""
+    S, L = case["max_shift"], case["read_len"]
+    calc = mscc_oracle_runs(case)
+    exp = case["expected"]
+    # a chromosome absent from the track: no result in the successive calculator (mscc.pyx:213-216, :489-490), an empty
+    # placeholder with an all-zero lag table in the bitarray calculator (bitarray/mscc.pyx:196-205) -- and no MSCC row of it
+    assert sorted(exp["chroms"]) == sorted(n for n, _ in case["chroms"] if n in case["track"])
+    for n, _g in case["chroms"]:
+        if n not in case["track"]:
+            ph = calc.ref2mscc[n]
+            assert ph.get("empty") and not any(ph["mappable_len"]) and not np.any(ph["forward_sum"]) and np.isnan(ph["cc"]).all()
+    for ch, e in exp["chroms"].items():
+        mscc = calc.ref2mscc[ch]
+        for k in ("forward_sum", "reverse_sum", "ccbins"):
+            assert len(e[k]) == S + 1 and [int(x) for x in mscc[k]] == e[k], (ch, k)
+        mlen = list(mscc["mappable_len"])
+        assert len(mlen) == (S + 1 if mscc.get("empty") else max(L, S - L + 2)) and None not in mlen
+        assert mlen == e["mappable_len"][:len(mlen)], ch
+        ecc = rm.nan_array(e["cc"])
+        assert np.array_equal(np.isnan(ecc), np.isnan(mscc["cc"])), ch
+        m = ~np.isnan(ecc)
+        np.testing.assert_allclose(mscc["cc"][m], ecc[m], rtol=0, atol=1e-15)
+        assert (e["forward_read_len_sum"], e["reverse_read_len_sum"]) == (0, 0)     # (never incremented per chromosome there)
+    fdrop, rdrop = rm.read_len_sums_of_reads_in_no_lag(case)
+    assert calc.forward_read_len_sum - fdrop == exp["forward_read_len_sum"]
+    assert calc.reverse_read_len_sum - rdrop == exp["reverse_read_len_sum"]
+    # and the sums the bitarray rules give are what the kept reads add up to, chromosome by chromosome
+    for ch in case["reads"]:
+        _fp, flen, _re, rlen = rm.kept_reads(case, ch)
+        res = calc.ref2ncc[ch]
+        assert (res["forward_read_len_sum"], res["reverse_read_len_sum"]) == (int(flen.sum()), int(rlen.sum())), ch
+
+
+RECIPE_CHILD = (
+    "import gzip, os, sys\n"
+    "sys.path.insert(0, os.path.join(sys.argv[1], 'oracle'))\n"
+    "import make_ref_mscc_vectors as gen\n"
+    "assert gen.FIXTURE == sys.argv[2], gen.FIXTURE\n"
+    "data = open(os.path.join(sys.argv[1], 'tests', 'golden', gen.FIXTURE), 'rb').read()\n"
+    "assert len(data) <= gen.MAX_FIXTURE_BYTES\n"
+    "assert gen.dumps(gen.generate()) == gzip.decompress(data).decode(), 'the fixture is not what the recipe gives'\n"
+    "print('RECIPE_OK')\n"
+)
+
+
+def test_reference_successive_mscc_vectors_match_their_recipe():
+    """Re-runs oracle/make_ref_mscc_vectors.py in memory where the reference's modules were built (oracle/build_ref.sh):
+    the JSON text in the committed fixture is exactly what the recipe gives.  In a child process, because the generator puts the reference
+    tree on sys.path and loads its modules: processes that later tests of this run spawn would inherit both."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    reference = os.environ.get("PYMASC_REFERENCE", "/root/reference")
+    if not os.path.isdir(os.path.join(reference, "PyMaSC")):
+        pytest.skip("no reference tree here")
+    if not all(glob.glob(os.path.join(root, "oracle", "_ref", m + ".*so")) for m in ("mscc", "mappability", "bigwig")):
+        pytest.skip("oracle/_ref is not built (oracle/build_ref.sh)")
+    res = subprocess.run([sys.executable, "-c", RECIPE_CHILD, root, rm.FIXTURE], cwd=root, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and res.stdout.strip().endswith("RECIPE_OK"), res.stderr[-3000:]
 
 
 def test_bruteforce_definition_small():
