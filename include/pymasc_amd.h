@@ -345,6 +345,37 @@ int pmx_debug_set_claim_mode(pmx_ctx *ctx, uint32_t mode);
  * the autocorrelation window kernel (equally long), 16 bytes of flagged-tile counters, the job statistics, and the claim
  * counters -- (compute units x 8 + 32) words, rounded up to 16 bytes -- at the end. */
 int pmx_debug_read_flag_area(pmx_ctx *ctx, void *dst, uint64_t cap, uint64_t *bytes);
+/* The launch ledger: how often each template instantiation of the set-bit kernels (kernels_sparse.hip, kernels_events.h) has
+ * been launched on this context since the last reset -- host side only, one increment per launch; the kernel timers above
+ * count per kernel FAMILY.  An entry is (family, index in the family's table); the tables, in the order of their choosers:
+ *   PMX_LEDGER_CC_EVENTS      ev_kernel, max_shift <= 1023.  With a track 16: 8 * !do_ncc + 4 * !fused_mlen + 2 * !deep + !known
+ *                             (do_ncc: no PMX_FLAG_SKIP_NCC; fused_mlen: the mappable-length pairs ride in the launch; deep:
+ *                             PMX_FLAG_DEEP_LISTS; known: a hint or the density probe, not PMX_FLAG_FORCE_SPARSE); without: 16 + !known
+ *   PMX_LEDGER_CC_EVENTS_BIG  ev_big_kernel, max_shift 1024..8191.  With a track 12: 6 * !fused_mlen + 3 * !do_ncc + g, g = 0, 1, 2
+ *                             for 1, 2, 4 sub-groups per workgroup; without: 12 + g
+ *   PMX_LEDGER_CC_SPARSE      sp_kernel, job table in the arguments (max_shift <= 1023): 0 track and NCC, 1 track without NCC, 2 no track
+ *   PMX_LEDGER_CC_SPARSE_CH   sp_kernel in chunks of 1024 shifts, job table in device memory: the same three
+ *   PMX_LEDGER_WINDOWS_FLAGGED  k_windows_flagged: 0 with NCC, 1 without
+ *   PMX_LEDGER_AUTOCORR_EDGES   k_autocorr_edges: 0 lags <= 1023, 1 in chunks of 1024 lags
+ *   PMX_LEDGER_REDUCE_SEGMENTS  k_reduce_segments: 0 job table in the arguments, 1 in device memory
+ *   PMX_LEDGER_AUTOCORR_PAIRS, _REDUCE_PAIRS, _AUTOCORR_FINISH, _EVENTS_TAIL: one instantiation each (job table in device memory)
+ * pmx_debug_ledger_read copies min(cap, entries) counts of `family` to dst and stores that number in *written;
+ * pmx_debug_ledger_sizes needs no context (and no GPU): dst[f] = entries of family f, for min(cap, PMX_LEDGER_FAMILIES_) families. */
+#define PMX_LEDGER_CC_EVENTS        0
+#define PMX_LEDGER_CC_EVENTS_BIG    1
+#define PMX_LEDGER_CC_SPARSE        2
+#define PMX_LEDGER_CC_SPARSE_CH     3
+#define PMX_LEDGER_WINDOWS_FLAGGED  4
+#define PMX_LEDGER_AUTOCORR_EDGES   5
+#define PMX_LEDGER_REDUCE_SEGMENTS  6
+#define PMX_LEDGER_AUTOCORR_PAIRS   7
+#define PMX_LEDGER_REDUCE_PAIRS     8
+#define PMX_LEDGER_AUTOCORR_FINISH  9
+#define PMX_LEDGER_EVENTS_TAIL     10
+#define PMX_LEDGER_FAMILIES_       11
+int pmx_debug_ledger_reset(pmx_ctx *ctx);
+int pmx_debug_ledger_read(pmx_ctx *ctx, int family, uint64_t *dst, uint32_t cap, uint32_t *written);
+int pmx_debug_ledger_sizes(uint32_t *dst, uint32_t cap, uint32_t *written);
 /* Copies `bytes` from byte offset `off` of the event / window kernels' slab to host memory (phase stamps of the
  * diagnostic builds -DEV_STAMPS / -DSP_STAMPS). */
 int pmx_debug_read_slab(pmx_ctx *ctx, uint64_t off, void *dst, uint64_t bytes);

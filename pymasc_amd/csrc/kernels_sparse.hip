@@ -2498,19 +2498,52 @@ template <typename JT>
 using SpKernelFn = void (*)(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, int32_t c, u32 lgG, u32 *slab,
                             const unsigned char *tile_flags, const u32 *n_flagged, const u32 *plan, u32 add_stride);
 
+template <typename JT>
+struct SpKernel {
+    SpKernelFn<JT> fn;
+    int index;   // of the instantiation in sp_kernel's table
+};
+
 // The window kernel.  CH (chunks of 1024 shifts) goes with the device-side table and only with it: each table type has the
 // three instantiations of its one CH.
+#define SP_KERNELS 3
 template <typename JT, bool CH>
-static SpKernelFn<JT> sp_kernel(bool has_m, bool do_ncc)
+static SpKernel<JT> sp_kernel(bool has_m, bool do_ncc)
 {
-    if (has_m && do_ncc) return k_cc_sparse<true, true, CH, JT>;
-    if (has_m) return k_cc_sparse<true, false, CH, JT>;
-    return k_cc_sparse<false, true, CH, JT>;
+    static const SpKernelFn<JT> tab[SP_KERNELS] = {
+        // has_m with do_ncc, has_m without, !has_m
+        k_cc_sparse<true, true, CH, JT>, k_cc_sparse<true, false, CH, JT>, k_cc_sparse<false, true, CH, JT>,
+    };
+    const int i = has_m ? (do_ncc ? 0 : 1) : 2;
+    return {tab[i], i};
 }
+
+// Entries per family of the launch ledger (include/pymasc_amd.h: PMX_LEDGER_*): the choosers' tables, and the fixed indices
+// the launchers below give the other templated kernels.
+#define EV_KERNELS 18
+#define EV_BIG_KERNELS 15
+uint32_t pmx_ledger_family_size(int family)
+{
+    switch (family) {
+    case PMX_LEDGER_CC_EVENTS: return EV_KERNELS;
+    case PMX_LEDGER_CC_EVENTS_BIG: return EV_BIG_KERNELS;
+    case PMX_LEDGER_CC_SPARSE:
+    case PMX_LEDGER_CC_SPARSE_CH: return SP_KERNELS;
+    case PMX_LEDGER_WINDOWS_FLAGGED:    // <DO_NCC>: true, false
+    case PMX_LEDGER_AUTOCORR_EDGES:     // <CH, SpJobTableRef>: false, true
+    case PMX_LEDGER_REDUCE_SEGMENTS:    // <SpJobTable>, <SpJobTableRef>
+        return 2;
+    case PMX_LEDGER_AUTOCORR_PAIRS:     // <SpJobTableRef> each
+    case PMX_LEDGER_REDUCE_PAIRS:
+    case PMX_LEDGER_AUTOCORR_FINISH:
+    case PMX_LEDGER_EVENTS_TAIL: return 1;
+    default: return 0;
+    }
+}
+static_assert(EV_KERNELS <= PMX_LEDGER_MAX_ENTRIES && EV_BIG_KERNELS <= PMX_LEDGER_MAX_ENTRIES, "pmx_ctx::ledger");
 
 // resident workgroups per CU of a max_shift <= 1023 instantiation on this device, at most `built_for` (asked once per
 // instantiation and device)
-#define EV_KERNELS 18
 static u32 ev_resident_per_cu(pmx_ctx *ctx, const EvKernel<SpJobTable> &k, u32 built_for)
 {
     static int cached[EV_KERNELS][EV_MAX_DEVICES];
@@ -2538,7 +2571,7 @@ static int launch_cc_window_chunks(pmx_ctx *ctx, const std::vector<VJob> &vjobs,
                                    const ReduceSpec &rs, const unsigned char *d_flags, const u32 *d_nflagged)
 {
     const bool behind_events = d_flags != nullptr;
-    const SpKernelFn<SpJobTableRef> kern = sp_kernel<SpJobTableRef, true>(has_m, do_ncc);
+    const SpKernel<SpJobTableRef> kern = sp_kernel<SpJobTableRef, true>(has_m, do_ncc);
     for (size_t lo = 0; lo < vjobs.size(); lo += SP_MAXJOBS_REF) {
         const uint32_t n = (uint32_t)(vjobs.size() - lo < SP_MAXJOBS_REF ? vjobs.size() - lo : SP_MAXJOBS_REF);
         std::vector<SpJobDev> tab(n);
@@ -2553,12 +2586,14 @@ static int launch_cc_window_chunks(pmx_ctx *ctx, const std::vector<VJob> &vjobs,
         pmx_timed_launch tl;
         rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl, behind_events);
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(256), 0, ctx->stream, ref, n, p.total, p.tiles_per_wg, c, 5u, wslab, d_flags,
+        PMX_LEDGER(ctx, PMX_LEDGER_CC_SPARSE_CH, kern.index);
+        hipLaunchKernelGGL(kern.fn, dim3(p.nwg), dim3(256), 0, ctx->stream, ref, n, p.total, p.tiles_per_wg, c, 5u, wslab, d_flags,
                            d_nflagged, (const u32 *)nullptr, 0u);
         PMX_CHECK_LAUNCH("k_cc_sparse");
         rc = pmx_prof_end(ctx, &tl);
         if (rc) return rc;
         // (behind the event pass the launch is gated: normally 25 k blocks that return at once, 34 us of dispatch at 32 per row)
+        PMX_LEDGER(ctx, PMX_LEDGER_REDUCE_SEGMENTS, 1);
         hipLaunchKernelGGL(k_reduce_segments<SpJobTableRef>, dim3(behind_events ? 8 : 32, rs.nrows + rs.nzero, n), dim3(256), 0, ctx->stream,
                            (const u32 *)wslab, ref, (u32)SP_SEG_ROWS, rs, d_nflagged);
         PMX_CHECK_LAUNCH("k_reduce_segments");
@@ -2622,11 +2657,13 @@ static int launch_autocorr_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njo
             pmx_timed_launch tl;
             rc = pmx_prof_begin(ctx, PMX_KERNEL_AUTOCORR, &tl);
             if (rc) return rc;
+            PMX_LEDGER(ctx, PMX_LEDGER_AUTOCORR_PAIRS, 0);
             hipLaunchKernelGGL(k_autocorr_pairs<JT>, dim3(p.nwg), dim3(256), lds_bytes, ctx->stream, ref, n, p.total, p.tiles_per_wg, max_lag, nl,
                                nh, ctx->d_slab2, d_flags, d_nflagged);
             PMX_CHECK_LAUNCH("k_autocorr_pairs");
             rc = pmx_prof_end(ctx, &tl);
             if (rc) return rc;
+            PMX_LEDGER(ctx, PMX_LEDGER_REDUCE_PAIRS, 0);
             hipLaunchKernelGGL(k_reduce_pairs<JT>, dim3((max_lag + 1 + 31) / 32 < 64 ? (max_lag + 1 + 31) / 32 : 64, 3, n), dim3(256), 0,
                                ctx->stream, (const u32 *)ctx->d_slab2, ref, nl, max_lag, lagcap, 0u);
             PMX_CHECK_LAUNCH("k_reduce_pairs");
@@ -2661,11 +2698,13 @@ static int launch_autocorr_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njo
         pmx_timed_launch tl;
         rc = pmx_prof_begin(ctx, PMX_KERNEL_AUTOCORR, &tl);
         if (rc) return rc;
+        PMX_LEDGER(ctx, PMX_LEDGER_AUTOCORR_EDGES, chunked ? 1 : 0);
         hipLaunchKernelGGL(edges_kern, dim3(p.nwg), dim3(256), 0, ctx->stream, ref, n, p.total, p.tiles_per_wg, lgG, ctx->d_slab_ac,
                            (const unsigned char *)d_flags, (const u32 *)d_nflagged, (const u32 *)nullptr, 0u, (int32_t)0, 0u, 0u);
         PMX_CHECK_LAUNCH("k_autocorr_edges");
         rc = pmx_prof_end(ctx, &tl);
         if (rc) return rc;
+        PMX_LEDGER(ctx, PMX_LEDGER_REDUCE_SEGMENTS, 1);
         hipLaunchKernelGGL(k_reduce_segments<JT>, dim3(32, 3, n), dim3(256), 0, ctx->stream, (const u32 *)ctx->d_slab_ac, ref,
                            (u32)AC_SEG_ROWS, rs, (const u32 *)d_nflagged);
         PMX_CHECK_LAUNCH("k_reduce_segments");
@@ -2682,6 +2721,7 @@ static int launch_autocorr_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njo
         JT ref;
         rc = upload_table(ctx, tab, &ref);
         if (rc) return rc;
+        PMX_LEDGER(ctx, PMX_LEDGER_AUTOCORR_FINISH, 0);
         hipLaunchKernelGGL(k_autocorr_finish<JT>, dim3(n), dim3(AC_FINISH_THREADS), 0, ctx->stream, ref, max_lag, lagcap, mode,
                            (int32_t)read_len - 1, max_shift, out_stride);
         PMX_CHECK_LAUNCH("k_autocorr_finish");
@@ -2691,7 +2731,6 @@ static int launch_autocorr_batch(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njo
 
 // The BIG instantiations of the event kernel (device-side table, nsg sub-groups of 256 threads); mlen: the mappable-length
 // pairs in the same launch (has_m only).  Without a track everything but nsg is ignored, as for ev_kernel.
-#define EV_BIG_KERNELS 15
 static EvKernel<SpJobTableRef> ev_big_kernel(bool has_m, bool do_ncc, bool mlen, u32 nsg)
 {
     typedef SpJobTableRef JT;
@@ -2769,12 +2808,14 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
         static bool attr_set[EV_BIG_KERNELS][EV_MAX_DEVICES];   // (per instantiation and device)
         rc = allow_big_lds(ctx, reinterpret_cast<const void *>(kern.fn), attr_set[kern.index]);
         if (rc) return rc;
+        PMX_LEDGER(ctx, PMX_LEDGER_CC_EVENTS_BIG, kern.index);
         hipLaunchKernelGGL(kern.fn, dim3(p.nwg), dim3(256 * pl.nsg), pl.lds_bytes, ctx->stream, ref, n, p.total, p.tiles_per_wg, c,
                            max_shift, nhr, fuse_mlen ? fused_lag : 0u, pl.hn, pl.lo, pl.hi | (fuse_mlen && pl.ee_lds ? 1u << 16 : 0u),
                            ctx->d_slab, d_flags, d_flags_ac ? d_flags_ac : d_flags, d_nflagged, d_jobstat, (u32 *)nullptr, 0u);
         PMX_CHECK_LAUNCH("k_cc_events (max_shift > 1023)");
         rc = pmx_prof_end(ctx, &tl);
         if (rc) return rc;
+        PMX_LEDGER(ctx, PMX_LEDGER_REDUCE_SEGMENTS, 1);
         hipLaunchKernelGGL(k_reduce_segments<SpJobTableRef>, dim3(32, rs.nrows + rs.nzero, n), dim3(256), 0, ctx->stream,
                            (const u32 *)ctx->d_slab, ref, (u32)EV_SEG_ROWS, rs_ev, (const u32 *)nullptr);
         PMX_CHECK_LAUNCH("k_reduce_segments");
@@ -2793,6 +2834,7 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
             r2.n_override = fused_lag + 1;
             r2.out_stride = out_stride;
             r2.rowlen = pl.hn;
+            PMX_LEDGER(ctx, PMX_LEDGER_REDUCE_SEGMENTS, 1);
             hipLaunchKernelGGL(k_reduce_segments<SpJobTableRef>, dim3(32, 3, n), dim3(256), 0, ctx->stream, (const u32 *)ctx->d_slab, ref,
                                (u32)EV_SEG_ROWS, r2, (const u32 *)nullptr);
             PMX_CHECK_LAUNCH("k_reduce_segments (mappable-length pairs)");
@@ -2800,6 +2842,7 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
         if (has_m) {
             EvTailPlan tp;
             memset(&tp, 0, sizeof tp);
+            PMX_LEDGER(ctx, PMX_LEDGER_EVENTS_TAIL, 0);
             hipLaunchKernelGGL(k_events_tail<SpJobTableRef>, dim3(n, 1), dim3(EV_TAIL_THREADS), 0, ctx->stream, (const u32 *)ctx->d_slab,
                                ref, tp, (const u32 *)nullptr, (const u32 *)nullptr, (const u32 *)d_nflagged, max_shift, out_stride, 1u,
                                do_ncc ? 1u : 0u, 0u, 1024u, (int32_t)c, 0u, pl.hn, 0u, (const u32 *)nullptr, (const u32 *)nullptr, 0u);
@@ -2955,7 +2998,7 @@ static int launch_cc_events(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, u
     // grid is one round of resident workgroups: a sixth that does not fit would run as a tail behind the others)
     const u32 per_cu = ev_resident_per_cu(ctx, kern, has_m ? (deep ? 4 : EV_WAVES) : EV_WAVES_NCC);
     const u32 nhr = (max_shift + 1 + 127) / 128;   // quads of R above a tile that hold partners of its forward reads
-    const SpKernelFn<SpJobTable> wkern = sp_kernel<SpJobTable, false>(has_m, do_ncc);   // (not launched when fuse_mlen)
+    const SpKernel<SpJobTable> wkern = sp_kernel<SpJobTable, false>(has_m, do_ncc);   // (not launched when fuse_mlen)
 
     for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS) {
         const uint32_t n = njobs - lo < SP_MAXJOBS ? njobs - lo : SP_MAXJOBS;
@@ -2977,6 +3020,7 @@ static int launch_cc_events(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, u
         }
         rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_EVENTS, &tl);
         if (rc) return rc;
+        PMX_LEDGER(ctx, PMX_LEDGER_CC_EVENTS, kern.index);
         hipLaunchKernelGGL(kern.fn, dim3(pe.nwg), dim3(256), 0, ctx->stream, tab, n, pe.total, pe.tiles_per_wg, (u32)c, max_shift, nhr,
                            fused_lag, 1024u, (u32)EV_LO, (u32)EV_HI, ctx->d_slab, fl.flags, fl.flags_ac, fl.nflagged, fl.jobstat, fl.claim,
                            ctx->debug_claim_mode);
@@ -3038,6 +3082,7 @@ static int launch_cc_events(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, u
             aa.total_tiles = pa.total; aa.tiles_per_wg = pa.tiles_per_wg; aa.lgG = lg_slot_lanes(fused_lag + 1);
             aa.add_shift = max_shift; aa.add_lag = fused_lag;
             aa.slab = ctx->d_slab_ac; aa.tile_flags = fl.flags_ac; aa.plan = fl.plan_ac;
+            PMX_LEDGER(ctx, PMX_LEDGER_WINDOWS_FLAGGED, do_ncc ? 0 : 1);
             hipLaunchKernelGGL(do_ncc ? k_windows_flagged<true> : k_windows_flagged<false>, dim3(pw.nwg + pa.nwg), dim3(256), 0,
                                ctx->stream, tabW, tabA, n, pw.nwg, wa, aa, (const u32 *)fl.nflagged, out_stride);
             PMX_CHECK_LAUNCH("k_windows_flagged");
@@ -3047,7 +3092,8 @@ static int launch_cc_events(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, u
         }
         rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl, true);
         if (rc) return rc;
-        hipLaunchKernelGGL(wkern, dim3(pw.nwg), dim3(256), 0, ctx->stream, tabW, n, pw.total, pw.tiles_per_wg, c, lgG, ctx->d_slab_fb,
+        PMX_LEDGER(ctx, PMX_LEDGER_CC_SPARSE, wkern.index);
+        hipLaunchKernelGGL(wkern.fn, dim3(pw.nwg), dim3(256), 0, ctx->stream, tabW, n, pw.total, pw.tiles_per_wg, c, lgG, ctx->d_slab_fb,
                            (const unsigned char *)fl.flags, (const u32 *)fl.nflagged, (const u32 *)fl.plan_cc, out_stride);
         PMX_CHECK_LAUNCH("k_cc_sparse");
         rc = pmx_prof_end(ctx, &tl);
@@ -3062,7 +3108,7 @@ static int launch_cc_window(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, u
                             const ReduceSpec &rs)
 {
     const bool has_m = jobs[0].d_M != nullptr;
-    const SpKernelFn<SpJobTable> kern = sp_kernel<SpJobTable, false>(has_m, do_ncc);
+    const SpKernel<SpJobTable> kern = sp_kernel<SpJobTable, false>(has_m, do_ncc);
     for (uint32_t lo = 0; lo < njobs; lo += SP_MAXJOBS) {
         const uint32_t n = njobs - lo < SP_MAXJOBS ? njobs - lo : SP_MAXJOBS;
         const std::vector<VJob> vj = whole_jobs(jobs, lo, n, max_shift + 1, nullptr);
@@ -3073,12 +3119,14 @@ static int launch_cc_window(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, u
         pmx_timed_launch tl;
         rc = pmx_prof_begin(ctx, PMX_KERNEL_CC_SPARSE, &tl);
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(256), 0, ctx->stream, tab, n, p.total, p.tiles_per_wg, (int32_t)read_len - 1,
+        PMX_LEDGER(ctx, PMX_LEDGER_CC_SPARSE, kern.index);
+        hipLaunchKernelGGL(kern.fn, dim3(p.nwg), dim3(256), 0, ctx->stream, tab, n, p.total, p.tiles_per_wg, (int32_t)read_len - 1,
                            lg_slot_lanes(max_shift + 1), ctx->d_slab, (const unsigned char *)nullptr, (const u32 *)nullptr,
                            (const u32 *)nullptr, 0u);
         PMX_CHECK_LAUNCH("k_cc_sparse");
         rc = pmx_prof_end(ctx, &tl);
         if (rc) return rc;
+        PMX_LEDGER(ctx, PMX_LEDGER_REDUCE_SEGMENTS, 0);
         hipLaunchKernelGGL(k_reduce_segments, dim3(32, rs.nrows + rs.nzero, n), dim3(256), 0, ctx->stream, (const u32 *)ctx->d_slab, tab,
                            (u32)SP_SEG_ROWS, rs, (const u32 *)nullptr);
         PMX_CHECK_LAUNCH("k_reduce_segments");

@@ -31,7 +31,7 @@ static inline uint64_t words_for(uint64_t nbits) { return (nbits + 63) / 64; }
 extern "C" {
 
 const char *pmx_last_error(void) { return g_err; }
-int pmx_version(void) { return 100; }
+int pmx_version(void) { return 101; }   // 101: the launch ledger (pmx_debug_ledger_*)
 #ifndef PMX_SRC_SHA16
 #define PMX_SRC_SHA16 "unknown"
 #endif
@@ -601,6 +601,32 @@ int pmx_debug_read_flag_area(pmx_ctx *ctx, void *dst, uint64_t cap, uint64_t *by
     const size_t stride = (ctx->flags_cc_bytes / 2) & ~(size_t)255;
     if (n) PMX_HIP(hipMemcpy(dst, ctx->d_flags_cc + used * stride, n, hipMemcpyDeviceToHost));
     *bytes = n;
+    return PMX_OK;
+}
+
+int pmx_debug_ledger_reset(pmx_ctx *ctx)
+{
+    REQUIRE(ctx, "pmx_debug_ledger_reset: ctx is NULL");
+    memset(ctx->ledger, 0, sizeof ctx->ledger);
+    return PMX_OK;
+}
+
+int pmx_debug_ledger_read(pmx_ctx *ctx, int family, uint64_t *dst, uint32_t cap, uint32_t *written)
+{
+    REQUIRE(ctx && dst && written, "pmx_debug_ledger_read: NULL argument");
+    REQUIRE(family >= 0 && family < PMX_LEDGER_FAMILIES_, "pmx_debug_ledger_read: bad family");
+    const uint32_t size = pmx_ledger_family_size(family), n = size < cap ? size : cap;
+    for (uint32_t i = 0; i < n; i++) dst[i] = ctx->ledger[family][i];
+    *written = n;
+    return PMX_OK;
+}
+
+int pmx_debug_ledger_sizes(uint32_t *dst, uint32_t cap, uint32_t *written)
+{
+    REQUIRE(dst && written, "pmx_debug_ledger_sizes: NULL argument");
+    const uint32_t n = cap < (uint32_t)PMX_LEDGER_FAMILIES_ ? cap : (uint32_t)PMX_LEDGER_FAMILIES_;
+    for (uint32_t f = 0; f < n; f++) dst[f] = pmx_ledger_family_size((int)f);
+    *written = n;
     return PMX_OK;
 }
 

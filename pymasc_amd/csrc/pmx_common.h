@@ -64,6 +64,7 @@ struct pmx_side_task {
 #define PMX_FEED_SLOTS 6
 #endif
 #define PMX_JOBTAB_SLOTS 8
+#define PMX_LEDGER_MAX_ENTRIES 18   // the largest chooser table of the set-bit launch layer (kernels_sparse.hip: ev_kernel)
 
 struct pmx_ctx {
     int device;
@@ -81,6 +82,9 @@ struct pmx_ctx {
     std::vector<hipEvent_t> event_pool;
     double total_ms[PMX_KERNEL_COUNT_];
     uint64_t launches[PMX_KERNEL_COUNT_];
+    // launches per template instantiation of the set-bit kernels since the last pmx_debug_ledger_reset: [family][index in the
+    // family's table] (include/pymasc_amd.h: PMX_LEDGER_*), one increment in front of every launch (PMX_LEDGER)
+    uint64_t ledger[PMX_LEDGER_FAMILIES_][PMX_LEDGER_MAX_ENTRIES];
     // scratch (device): autocorrelation row + small flags
     u64 *d_scratch;
     size_t scratch_words;
@@ -224,6 +228,9 @@ int pmx_events_can_fuse_mlen(uint32_t max_shift, uint32_t max_lag);
 int pmx_events_take_big(uint32_t max_shift);
 int pmx_events_used(uint32_t max_shift);      // the event kernel takes this shift range (any of its instantiations)
 int pmx_events_big_subgroups(uint32_t max_shift, int has_m);
+// the launch ledger (pmx_ctx::ledger): entries of a family's table, 0 for an unknown family
+#define PMX_LEDGER(ctx, family, index) ((ctx)->ledger[family][index]++)
+uint32_t pmx_ledger_family_size(int family);
 uint32_t pmx_sparse_max_jobs(void);
 uint32_t pmx_cc_batch_jobs(uint32_t max_shift);   // jobs per call of pmx_launch_cc_sparse_batch (device-side job tables beyond 1023 shifts)
 uint32_t pmx_autocorr_batch_jobs(void);           // ... of pmx_launch_autocorr_edges_batch

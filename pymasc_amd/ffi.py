@@ -50,6 +50,19 @@ PMX_KERNEL_AUTOCORR = 2
 PMX_KERNEL_CC_EVENTS = 3
 PMX_KERNEL_COUNT = 4
 
+# families of the launch ledger (pmx_debug_ledger_*): one table of template instantiations each, see include/pymasc_amd.h
+PMX_LEDGER_CC_EVENTS = 0
+PMX_LEDGER_CC_EVENTS_BIG = 1
+PMX_LEDGER_CC_SPARSE = 2
+PMX_LEDGER_CC_SPARSE_CH = 3
+PMX_LEDGER_WINDOWS_FLAGGED = 4
+PMX_LEDGER_AUTOCORR_EDGES = 5
+PMX_LEDGER_REDUCE_SEGMENTS = 6
+PMX_LEDGER_AUTOCORR_PAIRS = 7
+PMX_LEDGER_REDUCE_PAIRS = 8
+PMX_LEDGER_AUTOCORR_FINISH = 9
+PMX_LEDGER_EVENTS_TAIL = 10
+
 # every symbol include/pymasc_amd.h declares (tests check the library exports all of them)
 EXPORTS = [
     "pmx_last_error", "pmx_version", "pmx_build_id", "pmx_device_count",
@@ -63,7 +76,7 @@ EXPORTS = [
     "pmx_mappable_len_batch_dev",
     "pmx_ctx_set_profiling", "pmx_ctx_reset_kernel_times", "pmx_ctx_kernel_time", "pmx_kernel_name",
     "pmx_debug_poison", "pmx_debug_read_slab", "pmx_debug_set_max_workgroups", "pmx_debug_set_claim_mode",
-    "pmx_debug_read_flag_area",
+    "pmx_debug_read_flag_area", "pmx_debug_ledger_reset", "pmx_debug_ledger_read", "pmx_debug_ledger_sizes",
 ]
 
 
@@ -134,6 +147,9 @@ def load_library(path: Optional[str] = None):
     L.pmx_debug_set_max_workgroups.argtypes = [vp, ctypes.c_uint32]
     L.pmx_debug_set_claim_mode.argtypes = [vp, ctypes.c_uint32]
     L.pmx_debug_read_flag_area.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.pmx_debug_ledger_reset.argtypes = [vp]
+    L.pmx_debug_ledger_read.argtypes = [vp, i32, vp, u32, ctypes.POINTER(u32)]
+    L.pmx_debug_ledger_sizes.argtypes = [vp, u32, ctypes.POINTER(u32)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("pmx_version",):
@@ -619,8 +635,31 @@ class Context:
         _check(self._L, self._L.pmx_debug_read_flag_area(self._h, buf.ctypes.data, cap, ctypes.byref(n)))
         return buf[:int(n.value)].copy()
 
+    def debug_ledger_reset(self) -> None:
+        """Diagnostic: clear the context's launch ledger (launches per template instantiation, include/pymasc_amd.h)."""
+        _check(self._L, self._L.pmx_debug_ledger_reset(self._h))
+
+    def debug_ledger(self) -> list:
+        """Diagnostic: the launch ledger since the last reset: per family (PMX_LEDGER_*) the launch counts of its table's entries."""
+        out = []
+        for family, size in enumerate(ledger_sizes()):
+            buf = np.zeros(size, dtype=np.uint64)
+            n = ctypes.c_uint32(0)
+            _check(self._L, self._L.pmx_debug_ledger_read(self._h, family, buf.ctypes.data, size, ctypes.byref(n)))
+            out.append([int(x) for x in buf[:int(n.value)]])
+        return out
+
     def kernel_name(self, kernel_id: int) -> str:
         return self._L.pmx_kernel_name(int(kernel_id)).decode()
+
+
+def ledger_sizes() -> list:
+    """Entries per family of the launch ledger, in the order of PMX_LEDGER_* (needs no context and no GPU)."""
+    L = load_library()
+    buf = (ctypes.c_uint32 * 64)()
+    n = ctypes.c_uint32(0)
+    _check(L, L.pmx_debug_ledger_sizes(buf, 64, ctypes.byref(n)))
+    return [int(buf[i]) for i in range(int(n.value))]
 
 
 def device_count() -> int:

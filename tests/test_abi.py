@@ -41,7 +41,7 @@ def test_every_declared_symbol_is_exported():
     for s in syms:
         assert hasattr(L, s), s
     assert sorted(ffi.EXPORTS) == syms
-    assert L.pmx_version() >= 100
+    assert L.pmx_version() >= 101
 
 
 def test_io_library_builds_and_exports_its_header():
@@ -91,6 +91,10 @@ def test_header_constants_match_binding():
                  "PMX_ROW_MLEN", "PMX_ROW_SCALARS", "PMX_NROWS", "PMX_FLAG_SKIP_NCC", "PMX_FLAG_FORCE_DENSE", "PMX_FLAG_SKIP_MLEN",
                  "PMX_FLAG_FORCE_SPARSE", "PMX_FLAG_WINDOW_ONLY", "PMX_FLAG_DEEP_LISTS", "PMX_PATH_DENSE", "PMX_PATH_SPARSE", "PMX_KERNEL_CC_DENSE",
                  "PMX_KERNEL_CC_SPARSE", "PMX_KERNEL_AUTOCORR", "PMX_KERNEL_CC_EVENTS"):
+        assert int(consts[name]) == getattr(ffi, name), name
+    ledger = [name for name in consts if name.startswith("PMX_LEDGER_") and not name.endswith("_")]
+    assert len(ledger) == int(consts["PMX_LEDGER_FAMILIES_"]) == len(ffi.ledger_sizes())
+    for name in ledger:
         assert int(consts[name]) == getattr(ffi, name), name
 
 
