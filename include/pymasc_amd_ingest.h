@@ -404,6 +404,33 @@ int64_t pmx_dbam_fragments_rows(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_ex
                                 int64_t cap, int32_t *ref_id, int32_t *start1, int32_t *size, uint8_t *orient);
 int pmx_dbam_coverage_add_fragments(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint32_t max_size, uint64_t *added);
 
+/* The strand-aware read profile around anchor sites (version >= 16): TSS enrichment's counts.  An anchor is
+ * (reference, a, s): a 1-based position a and a strand s (+ or -).  Anchors may repeat, and each counts separately.  The reads are
+ * pmx_dbam_bincount_add's (the filter, the chosen references, less the reads an attached exclude mask drops); N is their number.  A
+ * read's extent [lo, hi] is pmx_dbam_bincount's with `extend` (0: the read's own length; 1: its 5' base only), clipped to [1, len].
+ * With the flank F (1 .. PMX_TSS_MAX_FLANK) and W = 2F + 1, a read on an anchor's reference covers, for that anchor, the offsets
+ * o = s * (p - a) for p in [lo, hi] with |o| <= F.  For every such o, same[o + F] += 1 when the read's strand equals the anchor's,
+ * opposite[o + F] += 1 otherwise.  pairs = the (read, anchor) pairs with at least one such offset; n_near = the reads in at least
+ * one pair, once each.
+ * pmx_dbam_tss_begin takes n anchors in host memory (ref[] the reference's index, pos1[] = a, reverse[] non-zero for a - anchor),
+ * in any order.  A reference outside the header, a < 1, a beyond its reference's length, F outside 1 .. PMX_TSS_MAX_FLANK or more
+ * than PMX_TSS_MAX_ANCHORS anchors: PMX_DBAM_ERR_INVALID, and the handle holds no table of this family.  use_ref: nref bytes, 0 =
+ * reads of that reference are not counted and its anchors are dropped; NULL = every reference.  The kept anchors are sorted by
+ * (reference, a) on the device (12 bytes each) beside a zeroed table of signed 64-bit differences [2][W + 1] (part of
+ * pmx_dbam_stream_info's peak); they replace any earlier table and stay until the next begin or close.
+ * pmx_dbam_tss_add counts what the handle holds now, as pmx_dbam_peakcount_add does; calls add up.  out = {N, n_near} of this call.
+ * pmx_dbam_tss_copy: profile[0 .. W) = same, profile[W .. 2W) = opposite: the prefix sums of the differences.  A negative sum or a
+ * row that does not close at 0: PMX_DBAM_ERR_DEVICE, and nothing is written.
+ * pmx_dbam_tss_totals: totals = {N, n_near, anchors kept, pairs} since begin.
+ * add / copy / totals before begin and a NULL output: PMX_DBAM_ERR_INVALID. */
+#define PMX_TSS_MAX_FLANK 4095u
+#define PMX_TSS_MAX_ANCHORS (1u << 20)
+int pmx_dbam_tss_begin(pmx_dbam *b, int64_t n, const int32_t *ref, const uint32_t *pos1, const uint8_t *reverse, uint32_t flank,
+                       uint32_t extend, const uint8_t *use_ref);
+int pmx_dbam_tss_add(pmx_dbam *b, uint32_t mapq_min, uint32_t flag_exclude, uint64_t out[2]);
+int pmx_dbam_tss_copy(pmx_dbam *b, uint64_t *profile);
+int pmx_dbam_tss_totals(pmx_dbam *b, uint64_t totals[4]);
+
 #ifdef __cplusplus
 }
 #endif

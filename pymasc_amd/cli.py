@@ -266,6 +266,14 @@ def get_parser() -> argparse.ArgumentParser:
     out.add_argument("--fragments-max", metavar="N", type=int, action=_NaturalNumber,
                      help="largest fragment size counted, 1 to 65536 bases (default 2000); larger pairs are only counted as over; "
                           "implies --fragments")
+    out.add_argument("--tss", metavar="BED", type=Path,
+                     help="also write <name>_tss.tab for every file: the reads the correlation sees piled up around the anchor sites "
+                          "of this BED6 file (plain, gzip or bgzip; a + line anchors at start + 1, a - line at end: the TSS), by "
+                          "offset and by strand relative to the anchor's, with the TSS enrichment over the table's outer edges")
+    out.add_argument("--tss-flank", metavar="N", type=int, action=_NaturalNumber,
+                     help="bases either side of an anchor, 1 to 4095 (default 2000); needs --tss")
+    out.add_argument("--tss-extend", metavar="N", type=int, action=_NaturalNumber,
+                     help="count every read as N bases from its 5' end instead of its own length (1: the cut site); needs --tss")
     return parser
 
 
@@ -325,6 +333,14 @@ def parse_args(argv=None) -> argparse.Namespace:
         if args.fragments_max > 65536:
             parser.error("argument --fragments-max: max_size is {}: it must lie in [1, 65536]".format(args.fragments_max))
         args.fragments = True
+    if args.tss_flank is not None and args.tss is None:
+        parser.error("argument --tss-flank: needs an anchor file (--tss)")
+    if args.tss_extend is not None and args.tss is None:
+        parser.error("argument --tss-extend: needs an anchor file (--tss)")
+    if args.tss_flank is not None and args.tss_flank > 4095:
+        parser.error("argument --tss-flank: the flank is {}: it must lie in [1, 4095]".format(args.tss_flank))
+    if args.tss is not None and not os.path.isfile(args.tss):
+        parser.error("argument --tss: no such file: '{}'".format(args.tss))
     if args.gc_window is not None and args.gc_bias is None:
         parser.error("argument --gc-window: needs a genome (--gc-bias)")
     if args.gc_window is not None and args.gc_window > 1024:
@@ -431,6 +447,12 @@ def _run(args, device, rank: int) -> int:
         extra["fragments"] = True
     if args.fragments_max is not None:          # (it also bounds a pair pileup)
         extra["fragments_max"] = args.fragments_max
+    if args.tss is not None:
+        extra["tss"] = str(args.tss)
+        if args.tss_flank is not None:
+            extra["tss_flank"] = args.tss_flank
+        if args.tss_extend is not None:
+            extra["tss_extend"] = args.tss_extend
     if args.gc_bias is not None:
         extra["gc_bias"] = str(args.gc_bias)
         if args.gc_window is not None:

@@ -1243,6 +1243,7 @@ struct pmx_dbam {
     Coverage cv;
     GcBias gc;
     Fragments fr;
+    TssProfile ts;
     // the mate fields of the SAM line table (k_sam_mates): built by the first pair call, freed with the table
     int *d_smpos = nullptr, *d_stlen = nullptr;
     u8 *d_ssame = nullptr;
@@ -1786,7 +1787,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 15; }
+int pmx_dbam_version(void) { return 16; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -2578,3 +2579,4 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "coverage_device.inc"
 #include "gcbias_device.inc"
 #include "fragments_device.inc"
+#include "tss_device.inc"

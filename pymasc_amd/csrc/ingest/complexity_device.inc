@@ -315,7 +315,7 @@ int cx_filter(pmx_dbam *b, u32 mapq_min, u32 flag_exclude, u64 front, bool curre
 
 inline int side_add_any(const CxRecs &) { return 0; }
 
-// What the add of bincount, peakcount, coverage and gcbias share behind their own entry checks: the kept records of what the handle
+// What the add of bincount, peakcount, coverage, gcbias and tss share behind their own entry checks: the kept records of what the handle
 // holds now (none: nothing is counted), `check` on them before anything is allocated or marked, n zeroed 64-bit counters on the
 // device, `launch` (the family's kernel over the records, on the stream, adding to the counters), the counters into counters[n].
 template <class Launch, class Check = int (*)(const CxRecs &)>

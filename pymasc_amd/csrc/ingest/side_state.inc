@@ -88,6 +88,19 @@ struct Fragments {
     u64 held() const { return 24ull * max; }
 };
 
+// read profile around anchor sites (pmx_dbam_tss_*, tss_device.inc): from begin to the next begin or close
+struct TssProfile {
+    DevAlloc key, strand;            // per kept anchor, in (reference, a) order: u64 ref_id << 32 | a; u32 1 for a '-' anchor
+    DevAlloc tab;                    // long long, per reference: its length, -1 when it is not chosen
+    DevAlloc table;                  // long long [2][2 * flank + 2]: the differences of same / opposite, one closing entry per row
+    bool begun = false;              // between a begin that succeeded and the next one
+    u64 na = 0;                      // anchors on chosen references
+    u32 flank = 0, ext = 0;          // flank, extend
+    u64 tot[3] = {0, 0, 0};          // N, n_near, pairs, summed over the calls of add
+    bool on() const { return begun; }
+    u64 held() const { return begun ? na * 12 + 16ull * (2ull * flank + 2ull) : 0; }
+};
+
 // the body of an entry point: an exception (std::bad_alloc, ...) must not leave the C ABI
 template <class F> auto guarded(const char *name, F &&f) -> decltype(f())
 {

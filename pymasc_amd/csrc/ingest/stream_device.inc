@@ -97,7 +97,7 @@ u64 stream_held(const pmx_dbam &b)
     if (b.d_rl) h += 8 * (2u * RL_SHORT + RL_NCNT + 1u);
     if (b.sam) h += b.sam_lines * 24 + b.sam_nb_cap * 12 + 16;
     h += s->cx_n * 13;
-    h += b.bc.held() + b.pk.held() + b.cv.held() + b.gc.held() + b.fr.held();
+    h += b.bc.held() + b.pk.held() + b.cv.held() + b.gc.held() + b.fr.held() + b.ts.held();
     h += b.d_smpos ? b.sam_lines * 9 : 0;
     return h;
 }

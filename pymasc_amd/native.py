@@ -144,6 +144,10 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_fragments_timings": (_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "pmx_dbam_fragments_rows": (_i64, [_vp, _u32, _u32, _u32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pmx_dbam_coverage_add_fragments": (_int, [_vp, _u32, _u32, _u32, _pu64]),
+    "pmx_dbam_tss_begin": (_int, [_vp, _i64, _vp, _vp, _vp, _u32, _u32, _vp]),
+    "pmx_dbam_tss_add": (_int, [_vp, _u32, _u32, _vp]),
+    "pmx_dbam_tss_copy": (_int, [_vp, _vp]),
+    "pmx_dbam_tss_totals": (_int, [_vp, _vp]),
     "pmx_dgc_open": (_int, [_str, _int, _int, _out]),
     "pmx_dgc_close": (None, [_vp]),
     "pmx_dgc_nrec": (_i32, [_vp]),
@@ -341,6 +345,16 @@ class AlignmentReader(NativeReader):
         self._check_open()
         return from_reader(self, mapq_criteria, references, max_size)
 
+    def tss_profile(self, anchors, mapq_criteria: int = 0, references=None, flank: int = 2000, extend: int = 0):
+        """The reads of ``bin_counts`` piled up around ``anchors`` (a BED6 file's path, an ordered ``{name: [(a, "+" | "-"), ...]}``
+        or ``tss.open_anchors``' result) by offset and by strand relative to the anchor's, ``flank`` bases either side: a
+        ``pymasc_amd.tss.TssProfile`` with ``enrichment`` (``tss.from_reader``).  ``extend`` as for
+        ``bin_counts`` (1: the 5' base only).  A device reader counts on the GPU with arrays of its own: the arrays of the last
+        ``decode`` stay as they are."""
+        from .tss import from_reader
+        self._check_open()
+        return from_reader(self, anchors, mapq_criteria, references, flank, extend)
+
     # ---- excluded regions (pymasc_amd.region_mask; DESIGN.md 7.15) ----
     _exclude = None
     _dropped = 0
@@ -385,7 +399,7 @@ class AlignmentReader(NativeReader):
 
 
 #: the counts taken beside the correlation, in the order a stream reader serves them (it decides which error surfaces first)
-SIDE_KINDS = ("complexity", "fingerprint", "peaks", "coverage", "gcbias", "fragments")
+SIDE_KINDS = ("complexity", "fingerprint", "peaks", "coverage", "gcbias", "fragments", "tss")
 
 
 class SideAccumulator:

@@ -21,7 +21,7 @@ from itertools import zip_longest
 from pathlib import Path
 from typing import List, Optional, Sequence
 
-from . import complexity, coverage, ffi, fingerprint, fragments, gcbias, peaks, readlen, tables
+from . import complexity, coverage, ffi, fingerprint, fragments, gcbias, peaks, readlen, tables, tss
 from .chromfilter import NoTargetChromosomesError, filter_references, kept_references
 from .exceptions import InputUnseekable, ReadUnsortedError
 from .inputs import (check_bed_sizes, default_device_ingest, is_stream, open_alignments, open_header, open_track,
@@ -40,7 +40,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None,
         fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None,
         peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto", gc_bias=None, gc_window: int = 100,
-        fragments: bool = False, fragments_max: int = 2000):
+        fragments: bool = False, fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -101,7 +101,14 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     median and spread per orientation (FR, RF, TANDEM) and the histogram up to ``fragments_max`` bases (1 .. 65536); an excluded
     region drops a pair whose fragment touches it.  Counted where ``complexity`` is counted.  ``coverage_extend="pair"`` piles the
     FR pairs of at most ``fragments_max`` bases at their own extent instead of extended reads; it is known before the feed, so a
-    stream takes it.  A BED read file has no mate fields: ValueError before anything is read, with either."""
+    stream takes it.  A BED read file has no mate fields: ValueError before anything is read, with either.
+    ``tss``: anchor sites (transcription start sites, motif hits) as a BED6 file (plain, gzip or bgzip) or an ordered
+    ``{name: [(a, "+" | "-"), ...]}``: rank 0 also writes ``<stem>_tss.tab`` (pymasc_amd.tss): the reads the
+    fingerprint counts, each covering ``tss_extend`` bases from its 5' end (0: its own length; 1: the 5' base only), piled up by
+    their offset from every anchor within ``tss_flank`` bases (1 .. 4095) and by their strand relative to the anchor's, with the
+    TSS enrichment over the mean of the table's outer edges.  Counted where ``complexity`` is counted.  The anchors are read once
+    per call, against the alignment's own references: a line on a chromosome the alignment lacks, a strand of ``.`` or an anchor
+    beyond its chromosome's end is a ValueError before any table is written."""
     check_bed_sizes(bam_path, chrom_sizes)
     s = _settings(locals())
     _check_coverage_input(s, bam_path)
@@ -169,6 +176,9 @@ class _Settings:
     gc_window: int
     fragments: bool
     fragments_max: int              # the largest fragment size counted, and piled by a "pair" pileup
+    tss: object                     # None, or the tss.AnchorSource of the call: read once for every distinct header
+    tss_flank: int
+    tss_extend: int
     save_mappability_stats: bool
     device: int
     ingest: bool
@@ -216,6 +226,11 @@ def _settings(kw: dict) -> _Settings:
         raise ValueError("coverage_extend is \"auto\", \"pair\" or an integer of at least 0")
     given.update(coverage=bool(kw["coverage"]), coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend))
     given.update(fragments=bool(kw["fragments"]), fragments_max=fragments.check_max_size(kw["fragments_max"]))
+    if kw["tss"] is None and (int(kw["tss_flank"]) != tss.DEFAULT_FLANK or int(kw["tss_extend"])):
+        raise ValueError("tss_flank and tss_extend need tss")
+    given.update(tss_flank=tss.check_flank(kw["tss_flank"]), tss_extend=tss.check_extend(kw["tss_extend"]))
+    if kw["tss"] is not None:
+        given["tss"] = tss.AnchorSource(kw["tss"], bool(ingest), reader_device(kw["context"], device, bool(ingest)))
     if int(kw["fingerprint_bin"]) < 1 or int(kw["fingerprint_extend"]) < 0:
         raise ValueError("fingerprint_bin is at least 1 and fingerprint_extend at least 0")
     control = kw["fingerprint_control"]
@@ -249,11 +264,32 @@ def _check_pairs_input(s: _Settings, path) -> None:
 
 def _check_inputs(s: _Settings, path, bam) -> None:
     """ValueError unless the chosen references of ``path`` (``bam``: its open reader, or None: its header is read) are those of
-    the fingerprint control and have their records in the genome of ``gc_bias``, where the call has either."""
+    the fingerprint control and have their records in the genome of ``gc_bias``, and the anchors of ``tss`` can be bound to its
+    references, where the call has any of them."""
     if s.fingerprint_control is not None:
         s.fingerprint_control.check(s, path, bam)
     if s.gc_bias is not None:
         s.gc_bias.check(s, path, bam)
+    if s.tss is not None:
+        _bind_anchors(s, path, bam)
+
+
+def _bind_anchors(s: _Settings, path, bam) -> None:
+    """The anchors of ``tss`` bound to the references of ``path`` before its run (once per distinct header; the count finds them
+    bound).  What the BED read readers refuse -- a chromosome the alignment lacks, a strand of ``.`` -- is the file's ValueError, as
+    an anchor beyond its chromosome's end is."""
+    from .native import PmxIOError
+    if bam is not None:
+        refs, lengths = bam.references, bam.lengths
+    elif is_stream(path):           # (no header to read apart: the count binds them when the stream is armed)
+        return
+    else:
+        with open_header(path, s.chrom_sizes) as h:
+            refs, lengths = h.references, h.lengths
+    try:
+        s.tss.resolve(refs, lengths)
+    except PmxIOError as e:
+        raise ValueError("anchor file '{}': {}".format(s.tss.source, e.msg)) from e
 
 
 def _estimate(s: _Settings, path, keep: bool):
@@ -517,6 +553,9 @@ _SIDES = (
     _Side("fragments", lambda s: s.fragments, fragments.FRAGMENTS_SUFFIX, fragments,
           lambda s, names: (int(s.mapq_criteria), names, s.fragments_max), "arm_fragments",
           lambda s, base, basename, value: fragments.write_fragments(base, basename, value)),
+    _Side("tss", lambda s: s.tss is not None, tss.TSS_SUFFIX, tss,
+          lambda s, names: (s.tss, int(s.mapq_criteria), names, s.tss_flank, s.tss_extend), "arm_tss",
+          lambda s, base, basename, value: tss.write_tss(base, basename, value, s.tss.source)),
 )
 
 
@@ -623,7 +662,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               complexity: bool = False, exclude_regions=None, fingerprint: bool = False, fingerprint_bin: int = 500,
               fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0, coverage: bool = False,
               coverage_extend="auto", gc_bias=None, gc_window: int = 100, fragments: bool = False,
-              fragments_max: int = 2000) -> List[FileResult]:
+              fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -657,7 +696,9 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
 
     ``gc_bias``: the genome is parsed once, before the first file runs, and serves every file; a file whose chosen references
     have no record of their name and length in it is logged and skipped; a FASTA that cannot be parsed raises ``GenomeError``.
-    ``fragments`` / ``coverage_extend="pair"``: a BED read file has no mate fields and is skipped in step 1 with run's ValueError."""
+    ``fragments`` / ``coverage_extend="pair"``: a BED read file has no mate fields and is skipped in step 1 with run's ValueError.
+    ``tss``: the anchors are bound to every file's references before its run; a file whose references they do not match is logged
+    and skipped with its ValueError, and the other files go on."""
     paths = list(paths)
     if not paths:
         raise ValueError("no input files")

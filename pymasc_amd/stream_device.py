@@ -199,6 +199,16 @@ class DeviceStreamReader(DeviceBamReader):
     def disarm_fragments(self) -> None:
         self._disarm("fragments")
 
+    def arm_tss(self, anchors, mapq_criteria: int = 0, references=None, flank: int = 2000, extend: int = 0):
+        """From now on every window a pass makes current is also piled up around ``anchors`` (``pmx_dbam_tss_add``, into the table
+        ``pmx_dbam_tss_begin`` builds here); returns the ``pymasc_amd.tss.DeviceCount`` whose ``result(reader)`` is the whole
+        stream's once the pass has ended.  A read is counted in the window that decodes it, as for ``arm_fingerprint``."""
+        from .tss import DeviceCount
+        return self._arm("tss", DeviceCount(self, anchors, mapq_criteria, references, flank, extend))
+
+    def disarm_tss(self) -> None:
+        self._disarm("tss")
+
     def _keep_mask(self):
         if len(self._selected) == len(self.references):
             return None
