@@ -256,6 +256,37 @@ int pmx_dbam_coverage_finish(pmx_dbam *b, uint64_t totals[5]);
 int pmx_dbam_coverage_runs(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth);
 int64_t pmx_dbam_coverage_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap);
 
+/* The pileup as the parts of a bigWig file (version >= 17): the bytes of its data sections and of its zoom
+ * records, computed from the runs finish left, with a table per call that says where every section begins and ends, so that the
+ * host builds the R-trees without parsing a byte.  All four are legal only between finish and the next begin
+ * (PMX_DBAM_ERR_INVALID otherwise), and follow text: a NULL buffer returns the size, a cap that is too small is
+ * PMX_DBAM_ERR_INVALID, out of device memory is PMX_DBAM_ERR_OPEN with the bytes asked for.
+ * ranges: first[k] = the first run of the k-th chosen reference in header order (a reference without a run: that of the next),
+ * first[chosen] = the number of runs.  Returns chosen + 1; with first NULL only that.
+ * sections: runs [first, first + n), which must be runs of ONE reference, as bedGraph sections (type 1) of `items` runs (1 .. 65535;
+ * the last one shorter): a 24-byte header (chrom_id, start, end, 0, 0, type 1, 0, itemCount), then (start0, end0, float32 depth) per
+ * run; a depth is exact up to 2^24 and rounded to nearest above.  Returns the bytes, 24 per section + 12 per run;
+ * table[section][5] = chrom_id, start, chrom_id, end, bytes.
+ * zoom_begin: dense bins of z0 * 4^k bases for levels k < `levels` (at most PMX_COVERAGE_ZOOM_LEVELS) over every chosen
+ * reference; chrom_id[nref] gives every chosen reference its id, 0 .. chosen - 1 each once, and the bins lie in id order.  Bin j of
+ * a reference covers [j * z, min((j + 1) * z, len)).  Per bin, as integers: the covered bases (depth > 0), the smallest and
+ * largest depth, the sum of the depth and of its square over those bases.  Level 0 is filled from the runs, level k + 1 from four
+ * bins of level k.  out[0] = the sum of depth^2 over all covered bases, out[1] = the smallest depth (0 without a run).  28 bytes
+ * per bin of level 0 and about a third again, counted towards pmx_dbam_stream_info's peak, until the last level is pulled, the
+ * next zoom_begin, begin or close.  max_depth * fragment_bases >= 2^64 (a 64-bit sum of squares could be inexact):
+ * PMX_DBAM_ERR_INVALID and no bins.
+ * zoom_records: the bins of `level` with a covered base, in (id, start) order, as 32-byte records (chrom_id, start, end,
+ * validCount u32, then min, max, sum, sumSquares as float32, rounded to nearest even), in sections of `items` records that may
+ * hold two references; table[section][5] = first id, first start, last id, last end, bytes.  Returns the bytes.  Pulling
+ * the last level frees the bins. */
+#define PMX_COVERAGE_ZOOM_LEVELS 10u
+int64_t pmx_dbam_coverage_ranges(pmx_dbam *b, int64_t *first, int64_t cap);
+int64_t pmx_dbam_coverage_sections(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
+                                   uint32_t *table, int64_t table_cap);
+int pmx_dbam_coverage_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t out[2]);
+int64_t pmx_dbam_coverage_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
+                                       int64_t table_cap);
+
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
  * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong.  An indexed
  * handle: bytes_out is the length of its stream (header + selected records), bytes_in and members count only the members

@@ -252,6 +252,13 @@ def get_parser() -> argparse.ArgumentParser:
                           "estimate, on one more read of the file, so not for '-' or a pipe; read: no extension, the read's own "
                           "length; pair: instead of reads, every properly oriented (FR) pair at its own extent, from read1's mate "
                           "fields, up to --fragments-max bases; implies --coverage")
+    out.add_argument("--coverage-format", choices=("bedgraph", "bigwig"),
+                     help="bedgraph (the default): the text track; bigwig: <name>_coverage.bw instead, the same runs as a bigWig "
+                          "file a genome browser opens, with zoom levels (count, min, max, sum and sum of squares of the depth per "
+                          "bin), its sections and zoom records made on the GPU.  The depth is a 32-bit float there: exact up to "
+                          "2^24 and rounded to nearest above; implies --coverage")
+    out.add_argument("--coverage-compress", action="store_true",
+                     help="put every section of the bigWig file through zlib (on the host); needs --coverage-format bigwig")
     out.add_argument("--gc-bias", metavar="FASTA", type=Path,
                      help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
                           "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
@@ -321,8 +328,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("argument --peaks-extend: needs a peak file (--peaks)")
     if args.peaks is not None and not os.path.isfile(args.peaks):
         parser.error("argument --peaks: no such file: '{}'".format(args.peaks))
-    if args.coverage_extend is not None:
+    if args.coverage_extend is not None or args.coverage_format is not None:
         args.coverage = True
+    if args.coverage_compress and args.coverage_format != "bigwig":
+        parser.error("argument --coverage-compress: needs --coverage-format bigwig")
     if args.coverage and args.coverage_extend in (None, "auto"):
         from .stream_device import is_stream_path
         streams = [str(p) for p in args.reads if is_stream_path(str(p))]
@@ -443,6 +452,10 @@ def _run(args, device, rank: int) -> int:
         extra["coverage"] = True
         if args.coverage_extend not in (None, "auto"):
             extra["coverage_extend"] = 0 if args.coverage_extend == "read" else args.coverage_extend
+        if args.coverage_format is not None:
+            extra["coverage_format"] = args.coverage_format
+        if args.coverage_compress:
+            extra["coverage_compress"] = True
     if args.fragments:
         extra["fragments"] = True
     if args.fragments_max is not None:          # (it also bounds a pair pileup)

@@ -22,12 +22,17 @@ The file is ``<name>_coverage.bedGraph``: a ``track`` line, then ``chrom<TAB>sta
 
 A device reader counts on the GPU and formats the lines there (``pmx_dbam_coverage_*``, include/pymasc_amd_ingest.h); a host reader
 goes through its ``batches`` and ``HostCount`` (plain numpy), which is also the device's checker.
+
+The same runs as a bigWig file, ``<name>_coverage.bw`` (``write_bigwig``, ``read_bigwig``): see the second half of
+this module.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 import re
+import struct
+import zlib
 from pathlib import Path
 from typing import Dict, Iterator, Tuple
 
@@ -58,9 +63,12 @@ class Coverage:
     """``runs``: ``{name: (start0, end0, depth)}``, uint32, of the chosen references that have a run, in header order;
     ``reads``: the reads that added; ``extend`` (0: every read's own length; ``"pair"``: the FR pairs at their own extent)."""
 
-    def __init__(self, runs, reads: int, extend: int):
+    def __init__(self, runs, reads: int, extend: int, refs=None):
+        """``refs``: the chosen references as ``[(name, length), ...]`` in header order, where they are known (a count knows them, a
+        bedGraph file does not); ``write_bigwig`` needs them, and two pileups compare equal without them."""
         self.runs = {str(k): tuple(np.asarray(x, dtype=np.uint32).ravel() for x in v) for k, v in runs.items()}
         self.reads, self.extend = int(reads), check_extend(extend)
+        self.refs = None if refs is None else [(str(n), int(l)) for n, l in refs]
         if any(len(v) != 3 or not (v[0].size == v[1].size == v[2].size > 0) for v in self.runs.values()):
             raise ValueError("every reference has as many starts as ends and depths, and at least one run")
 
@@ -149,7 +157,7 @@ class HostCount:
                 depth = np.cumsum(steps[at], dtype=np.int64)
                 keep = depth[:-1] > 0
                 runs[self.names[r]] = (at[:-1][keep], at[1:][keep], depth[:-1][keep])
-        return Coverage(runs, self.reads, self.label)
+        return Coverage(runs, self.reads, self.label, [(self.names[r], self.lengths[r]) for r in self.steps])
 
 
 def count_host(ref_id, pos1, read_len, reverse, names, lengths, use, extend: int = 0) -> Coverage:
@@ -170,6 +178,7 @@ class DeviceCount(SideAccumulator):
         self.mapq_criteria, self.extend, self.max_size = int(mapq_criteria), check_extend(extend), int(max_size)
         self.names = tuple(reader.references)
         self.use = _selected_mask(reader, references)
+        self.refs = [(n, max(int(l), 0)) for n, l, u in zip(self.names, reader.lengths, self.use) if u]
         self.totals = None
         self.begin(reader)
 
@@ -230,13 +239,73 @@ class DeviceCount(SideAccumulator):
         for first in range(0, total, int(chunk)):
             yield self.text(reader, first, min(int(chunk), total - first))
 
+    def ranges(self, reader) -> np.ndarray:
+        """The first run of every chosen reference in header order, one more entry closing them (``pmx_dbam_coverage_ranges``)."""
+        self.finish(reader)
+        out = np.zeros(len(self.refs) + 1, dtype=np.int64)
+        got = reader._L.pmx_dbam_coverage_ranges(reader._h, out.ctypes.data, out.size)
+        if got < 0:
+            reader._raise(got)
+        assert got == out.size
+        return out
+
+    def sections(self, reader, first: int, n: int, chrom_id: int, items: int):
+        """(bytes, table) of the runs ``[first, first + n)`` of one reference as bedGraph sections of a bigWig file stamped with
+        ``chrom_id`` (``pmx_dbam_coverage_sections``: the size, then the bytes); ``table[section] = (id, start, id, end, bytes)``."""
+        L, h = reader._L, reader._h
+        size = L.pmx_dbam_coverage_sections(h, int(first), int(n), int(chrom_id), int(items), None, 0, None, 0)
+        if size < 0:
+            reader._raise(size)
+        buf = np.zeros(max(int(size), 1), dtype=np.uint8)
+        table = np.zeros((max(-(-int(n) // int(items)), 1), 5), dtype=np.uint32)
+        got = L.pmx_dbam_coverage_sections(h, int(first), int(n), int(chrom_id), int(items), buf.ctypes.data, int(size),
+                                           table.ctypes.data, len(table))
+        if got < 0:
+            reader._raise(got)
+        assert got == size
+        return buf[:int(size)].tobytes(), table[:-(-int(n) // int(items))]
+
+    def section_chunks(self, reader, k: int, chrom_id: int, items: int, chunk: int = TEXT_CHUNK):
+        """``sections`` of the ``k``-th chosen reference, about ``chunk`` runs at a time (whole sections)."""
+        ranges = self.ranges(reader)
+        step = max(int(chunk) // int(items), 1) * int(items)
+        for first in range(int(ranges[k]), int(ranges[k + 1]), step):
+            yield self.sections(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items)
+
+    def zoom_begin(self, reader, z0: int, levels: int, ids) -> Tuple[int, int]:
+        """Fills the zoom bins on the device (``pmx_dbam_coverage_zoom_begin``); ``ids[k]``: the chromosome id of the ``k``-th
+        chosen reference.  Returns (the sum of depth^2 over the covered bases, the smallest depth)."""
+        chrom_id = np.zeros(max(len(self.names), 1), dtype=np.uint32)
+        chrom_id[np.flatnonzero(self.use)] = np.asarray(ids, dtype=np.uint32)
+        out = np.zeros(2, dtype=np.uint64)
+        rc = reader._L.pmx_dbam_coverage_zoom_begin(reader._h, int(z0), int(levels), chrom_id.ctypes.data, out.ctypes.data)
+        if rc:
+            reader._raise(rc)
+        return int(out[0]), int(out[1])
+
+    def zoom_records(self, reader, level: int, items: int):
+        """(bytes, table) of a level's records, 32 bytes each, in sections of ``items`` (``pmx_dbam_coverage_zoom_records``);
+        ``table[section] = (first id, first start, last id, last end, bytes)``.  The last level frees the bins."""
+        L, h = reader._L, reader._h
+        size = L.pmx_dbam_coverage_zoom_records(h, int(level), int(items), None, 0, None, 0)
+        if size < 0:
+            reader._raise(size)
+        rows = -(-(int(size) // 32) // int(items))
+        buf = np.zeros(max(int(size), 1), dtype=np.uint8)
+        table = np.zeros((max(rows, 1), 5), dtype=np.uint32)
+        got = L.pmx_dbam_coverage_zoom_records(h, int(level), int(items), buf.ctypes.data, int(size), table.ctypes.data, len(table))
+        if got < 0:
+            reader._raise(got)
+        assert got == size
+        return buf[:int(size)].tobytes(), table[:rows]
+
     def result(self, reader) -> Coverage:
         totals = self.finish(reader)
         ref, start, end, depth = self.runs(reader)
         cut = np.flatnonzero(np.diff(ref)) + 1 if ref.size else np.zeros(0, dtype=np.int64)
         edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
         c = Coverage({self.names[int(ref[a])]: (start[a:z], end[a:z], depth[a:z]) for a, z in zip(edges[:-1], edges[1:])},
-                     totals["reads"], self.extend)
+                     totals["reads"], self.extend, self.refs)
         if c.totals != tuple(totals[k] for k in TOTALS):
             raise RuntimeError("pmx_dbam_coverage_finish: the runs do not add up to the totals")
         return c
@@ -322,3 +391,394 @@ def read_coverage(path) -> Tuple[str, Coverage]:
     runs = {k: tuple(zip(*v)) for k, v in cols.items()}
     extend = head.group(2)
     return head.group(1), Coverage(runs, int(head.group(3)), 0 if extend == "read" else PAIR if extend == PAIR else int(extend))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The pileup as a bigWig file: ``--coverage-format bigwig`` / ``coverage_format="bigwig"``
+# ---------------------------------------------------------------------------------------------------------------------------------
+#
+# bbi version 4, little-endian, in this one layout: the 64-byte header, the zoom headers (24 bytes each), the 40-byte total summary,
+# the chromosome B+ tree, the u64 section count, the data sections, their R-tree, then per zoom level a u32 record count, the
+# level's sections and their R-tree, and the magic again.  fieldCount, definedFieldCount, autoSqlOffset and extensionOffset are 0.
+#
+# * Chromosomes: the chosen references with their lengths, keyed in bytewise name order; a chromosome's id is its rank in that
+#   order, so the sections are written reference by reference in NAME order (``chr10`` before ``chr2``), each from its own range of
+#   the runs: no run is sorted.  A chosen reference without a run is in the tree and has no section.
+# * Data sections: type 1 (bedGraph), ``items_per_section`` runs each, the last one of a reference shorter, none holding two
+#   references; a depth is written as float32, exact up to 2^24 and rounded to nearest above.
+# * Zoom level ``k`` has the reduction ``z_k = z_0 * 4^k``: bin ``j`` of a reference covers ``[j * z, min((j + 1) * z, len))``; a bin
+#   with a covered base (depth > 0) gives one record (id, start, end, validCount = its covered bases, then min, max, sum and sum of
+#   squares of the depth over those bases as float32, each rounded to nearest even from the exact integer); empty bins are not
+#   written.  The records are packed ``items_per_section`` to a section in (id, start) order; such a section may hold the last
+#   records of one reference and the first of the next, which its R-tree item says with two ids.  ``z_0`` is ``zoom_base``, else the
+#   smallest power of two that is at least ``10 * covered_bases / runs`` and 32.  Levels exist for ``k < 10`` while ``z_k`` is at
+#   most half the longest chosen length; no run gives no level.
+# * Total summary: validCount = covered_bases, the smallest and largest depth, sum = fragment_bases, and the sum of squares.
+# * With ``compress`` every section goes through zlib on the host (a pool of at most ``min(16, cpus)`` threads) and
+#   ``uncompressBufSize`` is the largest raw section; otherwise it is 0.
+#
+# Sections, their tables and the zoom records come from a ``DeviceCount`` on its reader's handle (the GPU) or from ``HostParts``
+# (numpy); everything else is the code below, so the two files are the same byte for byte when nothing is compressed.
+
+BIGWIG_SUFFIX = "_coverage.bw"
+FORMATS = ("bedgraph", "bigwig")
+SUFFIXES = dict(zip(FORMATS, (COVERAGE_SUFFIX, BIGWIG_SUFFIX)))
+BW_MAGIC, BW_CHROM_MAGIC, BW_RTREE_MAGIC = 0x888FFC26, 0x78CA8C91, 0x2468ACE0
+ZOOM_LEVELS = 10            # at most (PMX_COVERAGE_ZOOM_LEVELS of include/pymasc_amd_ingest.h)
+CHROM_BLOCK = 256           # keys per node of the chromosome tree
+EXACT_DEPTH = 1 << 24       # below it a depth is exact as float32
+ZOOM_RECORD = np.dtype([("id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("valid", "<u4"), ("min", "<f4"), ("max", "<f4"), ("sum", "<f4"),
+                        ("sumsq", "<f4")])
+
+
+def check_format(fmt, compress=False) -> str:
+    """``coverage_format`` as the run takes it; ``compress`` only with ``"bigwig"``."""
+    if fmt not in FORMATS:
+        raise ValueError("coverage_format is \"bedgraph\" or \"bigwig\"")
+    if compress and fmt != "bigwig":
+        raise ValueError("coverage_compress needs coverage_format=\"bigwig\"")
+    return fmt
+
+
+def sumsq_fits(max_depth: int, fragment_bases: int) -> bool:
+    """Whether every sum of depth^2 over covered bases is exact in 64 bits: it is at most ``max_depth * fragment_bases``, which
+    must be below 2^64 (the check of ``pmx_dbam_coverage_zoom_begin``, made here for both paths before a byte is written)."""
+    return int(max_depth) * int(fragment_bases) < 1 << 64
+
+
+def zoom_plan(lengths, covered_bases: int, runs: int, zoom_base=None) -> Tuple[int, int]:
+    """(z_0, levels) of a pileup over references of ``lengths``."""
+    if zoom_base is not None and (isinstance(zoom_base, bool) or int(zoom_base) != zoom_base or not 1 <= int(zoom_base) < 1 << 31):
+        raise ValueError("zoom_base is an integer of at least 1 and below 2^31")
+    if not runs:
+        return 0, 0
+    z0 = 32
+    if zoom_base is not None:
+        z0 = int(zoom_base)
+    else:
+        while z0 * int(runs) < 10 * int(covered_bases):
+            z0 *= 2
+    longest, levels = max(lengths, default=0), 0
+    while levels < ZOOM_LEVELS and 2 * z0 * 4 ** levels <= longest:
+        levels += 1
+    return z0, levels
+
+
+def _section_table(ids, starts, ends, n: int, items: int, unit: int, head: int) -> np.ndarray:
+    """``table[section] = (first id, first start, last id, last end, bytes)`` of ``n`` rows packed ``items`` to a section."""
+    first = np.arange(0, n, items, dtype=np.int64)
+    last = np.minimum(first + items, n) - 1
+    t = np.zeros((first.size, 5), dtype=np.uint32)
+    if n:
+        t[:, 0], t[:, 1], t[:, 2], t[:, 3] = ids[first], starts[first], ids[last], ends[last]
+        t[:, 4] = head + unit * (last - first + 1)
+    return t
+
+
+class HostParts:
+    """The numpy twin of the device's bigWig entry points, over a ``Coverage`` that knows its chosen references: the path of host
+    readers and the device's checker.  It has what ``assemble_bigwig`` takes from a source: ``refs``, ``totals``,
+    ``section_chunks``, ``zoom_begin`` and ``zoom_records``."""
+
+    def __init__(self, c: Coverage):
+        if c.refs is None:
+            raise ValueError("the pileup does not know its chosen references' lengths (it was read from a bedGraph file)")
+        if any(n not in dict(c.refs) for n in c.runs):
+            raise ValueError("a run on a reference that is not among the chosen ones")
+        self.c, self.refs = c, list(c.refs)
+        self.totals = dict(zip(TOTALS, c.totals))
+        self._levels = []
+
+    def section_chunks(self, k: int, chrom_id: int, items: int, chunk: int = TEXT_CHUNK):
+        s, e, d = self.c.runs.get(self.refs[k][0], (np.zeros(0, dtype=np.uint32),) * 3)
+        step = max(int(chunk) // int(items), 1) * int(items)
+        for a in range(0, s.size, step):
+            sa, ea, da = s[a:a + step], e[a:a + step], d[a:a + step]
+            m = sa.size
+            i = np.arange(m, dtype=np.int64)
+            table = _section_table(np.full(m, chrom_id, dtype=np.uint32), sa, ea, m, items, 12, 24)
+            out = np.zeros(6 * len(table) + 3 * m, dtype="<u4")
+            at = 6 * (i // items + 1) + 3 * i
+            out[at], out[at + 1], out[at + 2] = sa, ea, da.astype(np.float32).view(np.uint32)
+            first = np.arange(0, m, items, dtype=np.int64)
+            head = 6 * (first // items) + 3 * first
+            out[head], out[head + 1], out[head + 2] = chrom_id, table[:, 1], table[:, 3]
+            out[head + 5] = 1 | ((table[:, 4] - 24) // 12 << 16)
+            yield out.tobytes(), table
+
+    @staticmethod
+    def _reduce(j, cnt, mn, mx, sm, sq):
+        """The bins ``j`` (ascending, with repeats) reduced to one row per distinct bin."""
+        at = np.flatnonzero(np.concatenate(([True], j[1:] != j[:-1]))) if j.size else np.zeros(0, dtype=np.int64)
+        if not j.size:
+            return j, cnt, mn, mx, sm, sq
+        return (j[at], np.add.reduceat(cnt, at), np.minimum.reduceat(mn, at), np.maximum.reduceat(mx, at), np.add.reduceat(sm, at),
+                np.add.reduceat(sq, at))
+
+    def zoom_begin(self, z0: int, levels: int, ids) -> Tuple[int, int]:
+        order = np.argsort(np.asarray(ids))                 # the chosen references in id order
+        empty = (np.zeros(0, dtype=np.uint32),) * 3
+        level, sumsq, low = [], 0, None
+        for k in order.tolist():
+            s, e, d = (x.astype(np.int64) for x in self.c.runs.get(self.refs[k][0], empty))
+            sumsq += int(((e - s).astype(np.uint64) * d.astype(np.uint64) * d.astype(np.uint64)).sum(dtype=np.uint64))
+            if d.size:
+                low = int(d.min()) if low is None else min(low, int(d.min()))
+            if not levels:
+                continue
+            j0, j1 = s // z0, (e - 1) // z0
+            n = j1 - j0 + 1                                 # the bins of every run
+            run = np.repeat(np.arange(s.size), n)
+            j = j0[run] + np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+            w = (np.minimum(e[run], (j + 1) * z0) - np.maximum(s[run], j * z0)).astype(np.uint64)
+            dd = d[run].astype(np.uint64)
+            level.append(self._reduce(j, w, dd, dd, w * dd, w * dd * dd))
+        self._ids, self._z0, self._levels = [int(ids[k]) for k in order.tolist()], int(z0), [level] if levels else []
+        self._lens = [self.refs[k][1] for k in order.tolist()]
+        for _ in range(1, levels):                          # four bins into one
+            self._levels.append([self._reduce(r[0] // 4, *r[1:]) for r in self._levels[-1]])
+        return sumsq, low or 0
+
+    def zoom_records(self, level: int, items: int):
+        z = self._z0 * 4 ** level
+        rows = self._levels[level]
+        rec = np.zeros(sum(r[0].size for r in rows), dtype=ZOOM_RECORD)
+        a = 0
+        for cid, length, (j, cnt, mn, mx, sm, sq) in zip(self._ids, self._lens, rows):
+            v = rec[a:a + j.size]
+            v["id"], v["start"], v["end"], v["valid"] = cid, j * z, np.minimum((j + 1) * z, length), cnt
+            v["min"], v["max"], v["sum"], v["sumsq"] = (x.astype(np.float32) for x in (mn, mx, sm, sq))
+            a += j.size
+        return rec.tobytes(), _section_table(rec["id"], rec["start"], rec["end"], rec.size, items, 32, 0)
+
+
+class _DeviceParts:
+    """A finished ``DeviceCount`` on its reader's handle as a source of ``assemble_bigwig``."""
+
+    def __init__(self, acc: "DeviceCount", reader):
+        self.acc, self.reader, self.refs = acc, reader, list(acc.refs)
+        self.totals = dict(acc.finish(reader))
+
+    def section_chunks(self, k, chrom_id, items):
+        return self.acc.section_chunks(self.reader, k, chrom_id, items)
+
+    def zoom_begin(self, z0, levels, ids):
+        return self.acc.zoom_begin(self.reader, z0, levels, ids)
+
+    def zoom_records(self, level, items):
+        return self.acc.zoom_records(self.reader, level, items)
+
+
+def _chrom_tree(names, ids, lengths, at: int) -> bytes:
+    """The chromosome B+ tree, which begins at ``at``: ``names`` (bytes, ascending) with their ids and lengths, ``CHROM_BLOCK`` keys
+    per node, a node's children behind it."""
+    key = max(len(n) for n in names)
+    tiers = [[(n, struct.pack("<II", i, l)) for n, i, l in zip(names, ids, lengths)]]      # (key, value) of every item, per tier
+    while len(tiers[-1]) > CHROM_BLOCK:
+        tiers.append([(tiers[-1][a][0], None) for a in range(0, len(tiers[-1]), CHROM_BLOCK)])
+    out = [struct.pack("<IIIIQQ", BW_CHROM_MAGIC, CHROM_BLOCK, key, 8, len(names), 0)]
+    pos, where = at + 32, {}
+    for t in reversed(range(len(tiers))):                                                   # where every tier's nodes begin
+        where[t] = pos
+        pos += 4 * -(-len(tiers[t]) // CHROM_BLOCK) + (key + 8) * len(tiers[t])
+    for t in reversed(range(len(tiers))):
+        for k in range(0, len(tiers[t]), CHROM_BLOCK):
+            items = tiers[t][k:k + CHROM_BLOCK]
+            out.append(struct.pack("<BBH", t == 0, 0, len(items)))
+            for x, (name, value) in enumerate(items, k):                                    # (item x of a tier points to node x of the one below)
+                out.append(name.ljust(key, b"\0") + (value if t == 0 else struct.pack("<Q", where[t - 1] + (4 + (key + 8) * CHROM_BLOCK) * x)))
+    return b"".join(out)
+
+
+_RT_LEAF = np.dtype([("c0", "<u4"), ("s0", "<u4"), ("c1", "<u4"), ("e1", "<u4"), ("off", "<u8"), ("size", "<u8")])
+_RT_NODE = np.dtype([("c0", "<u4"), ("s0", "<u4"), ("c1", "<u4"), ("e1", "<u4"), ("off", "<u8")])
+
+
+def _rtree(table: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, block: int, per_slot: int, at: int, data_end: int) -> bytes:
+    """The R-tree over the sections of ``table`` (rows ``(id, start, id, end, ...)`` in (id, start) order) that lie at ``offsets``
+    with ``sizes`` bytes; the index itself begins at ``at``.  Built bottom-up, ``block`` items per node, a node's children behind it;
+    a node's bounds are its first item's beginning and the largest (id, end) among its items.  No section: one empty leaf."""
+    n = len(table)
+    leaf = np.zeros(n, dtype=_RT_LEAF)
+    leaf["c0"], leaf["s0"], leaf["c1"], leaf["e1"], leaf["off"], leaf["size"] = table[:, 0], table[:, 1], table[:, 2], table[:, 3], offsets, sizes
+    tiers = [leaf]                                          # the items of every tier, bottom-up
+    while len(tiers[-1]) > block:
+        below = tiers[-1]
+        first = np.arange(0, len(below), block)
+        hi = np.maximum.reduceat((below["c1"].astype(np.uint64) << np.uint64(32)) | below["e1"].astype(np.uint64), first)
+        node = np.zeros(first.size, dtype=_RT_NODE)
+        node["c0"], node["s0"], node["c1"], node["e1"] = below["c0"][first], below["s0"][first], hi >> np.uint64(32), hi & np.uint64(0xffffffff)
+        tiers.append(node)
+    pos = at + 48
+    for t in reversed(range(len(tiers))):                   # the root first; every item above the leaves learns where its node is
+        items = tiers[t]
+        nodes = max(-(-len(items) // block), 1)
+        if t + 1 < len(tiers):
+            k = np.arange(len(tiers[t + 1]), dtype=np.uint64)
+            tiers[t + 1]["off"] = np.uint64(pos) + k * np.uint64(4 + items.dtype.itemsize * block)
+        pos += 4 * nodes + items.dtype.itemsize * len(items)
+    top = tiers[-1]
+    hi = int(((top["c1"].astype(np.uint64) << np.uint64(32)) | top["e1"].astype(np.uint64)).max()) if n else 0
+    out = [struct.pack("<IIQIIIIQII", BW_RTREE_MAGIC, block, n, int(top["c0"][0]) if n else 0, int(top["s0"][0]) if n else 0, hi >> 32,
+                       hi & 0xffffffff, data_end, per_slot, 0)]
+    for t in reversed(range(len(tiers))):
+        items = tiers[t]
+        for a in range(0, max(len(items), 1), block):
+            part = items[a:a + block]
+            out.append(struct.pack("<BBH", t == 0, 0, len(part)) + part.tobytes())
+    return b"".join(out)
+
+
+class _SectionWriter:
+    """Writes sections at the file's end and remembers where: raw, or each through zlib in a pool of threads."""
+
+    def __init__(self, fp, compress: bool):
+        self.fp, self.largest, self.pool = fp, 0, None
+        if compress:
+            from multiprocessing.pool import ThreadPool
+            self.pool = ThreadPool(max(min(16, os.cpu_count() or 1), 1))
+
+    def close(self) -> None:
+        if self.pool is not None:
+            self.pool.close()
+            self.pool.join()
+
+    def write(self, blob: bytes, table: np.ndarray):
+        """The sections of ``blob`` (``table[:, 4]``: their raw sizes); returns their (offsets, sizes) in the file."""
+        raw = table[:, 4].astype(np.int64)
+        ends = np.cumsum(raw)
+        assert (int(ends[-1]) if raw.size else 0) == len(blob)
+        self.largest = max(self.largest, int(raw.max()) if raw.size else 0)
+        at = self.fp.tell()
+        if self.pool is None:
+            self.fp.write(blob)
+            return at + ends - raw, raw
+        view = memoryview(blob)
+        parts = self.pool.map(zlib.compress, [view[int(z - r):int(z)] for z, r in zip(ends, raw)], chunksize=64)
+        sizes = np.array([len(p) for p in parts], dtype=np.int64)
+        self.fp.write(b"".join(parts))
+        return at + np.cumsum(sizes) - sizes, sizes
+
+
+def assemble_bigwig(fp, src, compress: bool = False, items_per_section: int = 1024, index_block: int = 256, zoom_base=None) -> None:
+    """Writes the bigWig file of the source ``src`` (``HostParts``, or a ``DeviceCount`` with its reader) into the seekable binary
+    file ``fp``, from its beginning."""
+    items, block = int(items_per_section), int(index_block)
+    if not 1 <= items <= 65535 or not 2 <= block <= 65535:
+        raise ValueError("items_per_section lies in [1, 65535] and index_block in [2, 65535]")
+    refs, tot = src.refs, src.totals
+    if not refs:
+        raise ValueError("no chosen reference")
+    if not sumsq_fits(tot["max_depth"], tot["fragment_bases"]):
+        raise ValueError("max_depth * fragment_bases is 2^64 or more: the zoom levels' sums of squares would not be exact")
+    z0, levels = zoom_plan([l for _n, l in refs], tot["covered_bases"], tot["runs"], zoom_base)
+    names = [n.encode() for n, _l in refs]
+    order = sorted(range(len(refs)), key=lambda k: names[k])           # bytewise name order: a chromosome's id is its rank
+    if any(names[a] == names[b] for a, b in zip(order, order[1:])):
+        raise ValueError("two chosen references have the same name")
+    ids = [0] * len(refs)
+    for rank, k in enumerate(order):
+        ids[k] = rank
+    sumsq, low = src.zoom_begin(z0, levels, ids)
+    # the pass over the runs against finish's totals: d <= d^2 <= max_depth * d for every covered base
+    if not (low <= tot["max_depth"] and tot["fragment_bases"] <= sumsq <= tot["max_depth"] * tot["fragment_bases"] and bool(low) == bool(tot["runs"])):
+        raise RuntimeError("the zoom pass does not agree with the pileup's totals")
+    writer = _SectionWriter(fp, compress)
+    try:
+        fp.seek(0)
+        fp.write(bytes(64 + 24 * levels))
+        summary_at = fp.tell()
+        fp.write(struct.pack("<Qdddd", tot["covered_bases"], float(low), float(tot["max_depth"]), float(tot["fragment_bases"]), float(sumsq)))
+        tree_at = fp.tell()
+        fp.write(_chrom_tree([names[k] for k in order], range(len(order)), [refs[k][1] for k in order], tree_at))
+        data_at = fp.tell()
+        fp.write(bytes(8))
+        tables, offsets, sizes, n_runs = [], [], [], 0
+        for rank, k in enumerate(order):
+            for blob, table in src.section_chunks(k, rank, items):
+                o, s = writer.write(blob, table)
+                tables.append(table)
+                offsets.append(o)
+                sizes.append(s)
+                n_runs += (len(blob) - 24 * len(table)) // 12
+        if n_runs != tot["runs"]:
+            raise RuntimeError("the sections hold {} runs, the pileup {}".format(n_runs, tot["runs"]))
+        table = np.concatenate(tables) if tables else np.zeros((0, 5), dtype=np.uint32)
+        index_at, n_sections = fp.tell(), len(table)
+        fp.write(_rtree(table, np.concatenate(offsets) if offsets else np.zeros(0), np.concatenate(sizes) if sizes else np.zeros(0),
+                        block, items, index_at, index_at))
+        zooms = []
+        for level in range(levels):
+            blob, table = src.zoom_records(level, items)
+            at = fp.tell()
+            fp.write(struct.pack("<I", len(blob) // 32))
+            o, s = writer.write(blob, table)
+            zindex_at = fp.tell()
+            fp.write(_rtree(table, o, s, block, items, zindex_at, zindex_at))
+            zooms.append((z0 * 4 ** level, at, zindex_at))
+        fp.write(struct.pack("<I", BW_MAGIC))
+        fp.seek(0)
+        fp.write(struct.pack("<IHHQQQHHQQIQ", BW_MAGIC, 4, levels, tree_at, data_at, index_at, 0, 0, 0, summary_at,
+                             writer.largest if compress else 0, 0))
+        for z, at, zindex_at in zooms:
+            fp.write(struct.pack("<IIQQ", z, 0, at, zindex_at))
+        fp.seek(data_at)
+        fp.write(struct.pack("<Q", n_sections))
+        fp.seek(0, os.SEEK_END)
+    finally:
+        writer.close()
+
+
+def bigwig_source(c, reader=None):
+    """What ``assemble_bigwig`` reads: ``HostParts`` of a ``Coverage``, or a finished ``DeviceCount`` on ``reader``'s handle."""
+    return HostParts(c) if reader is None else _DeviceParts(c, reader)
+
+
+def write_bigwig(path_base, name: str, c, reader=None, compress: bool = False, items_per_section: int = 1024, index_block: int = 256,
+                 zoom_base=None) -> Path:
+    """Writes ``<path_base>_coverage.bw`` (to a temporary file beside it, renamed into place) and returns its path: the pileup of
+    a ``Coverage`` that knows its chosen references (sections and zoom records made with numpy) or, with ``reader``, of a finished
+    ``DeviceCount`` on that reader's handle (made on the GPU).  A bigWig file has no place for ``name``, the reads or the extent.
+    A depth is exact as float32 up to 2^24 and rounded to nearest above."""
+    path = Path(str(path_base) + BIGWIG_SUFFIX)
+    tmp = "{}.tmp.{}".format(path, os.getpid())
+    try:
+        with open(tmp, "w+b") as fp:
+            assemble_bigwig(fp, bigwig_source(c, reader), compress, items_per_section, index_block, zoom_base)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+    return path
+
+
+def write_file(path, chunks) -> Path:
+    """Writes the bytes of ``chunks`` to ``path`` (through a temporary file beside it, renamed into place)."""
+    path = Path(path)
+    tmp = "{}.tmp.{}".format(path, os.getpid())
+    try:
+        with open(tmp, "wb") as fp:
+            for chunk in chunks:
+                fp.write(chunk)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+    return path
+
+
+def read_bigwig(path) -> Coverage:
+    """The pileup of a ``_coverage.bw``, read through the host ``BigWigReader``: the runs by reference in the file's (name) order
+    and ``refs`` from its chromosome tree.  The file does not hold the reads or the extent: both are 0.  A value that is not a whole
+    number from 1 to 2^24 - 1 is a ValueError (such a file is not a pileup this module wrote, or holds a depth float32 rounded)."""
+    from .bigwig import BigWigReader
+    with BigWigReader(path) as r:
+        refs = list(r.chromsizes.items())
+        runs = {}
+        for chrom, _length in refs:
+            s, e, v = r.fetch_arrays(0.0, chrom)
+            if v.size:
+                if not bool(np.all((v >= 1) & (v < EXACT_DEPTH) & (v == np.floor(v)))):
+                    raise ValueError("'{}': a value on '{}' is not a whole number from 1 to 2^24 - 1".format(path, chrom))
+                runs[chrom] = (s, e, v.astype(np.uint32))
+    return Coverage(runs, 0, 0, refs)

@@ -1,7 +1,7 @@
 // The fragment pileup as runs of constant depth, and the text of its bedGraph track, on the device (pmx_dbam_coverage_*,
 // include/pymasc_amd_ingest.h; DESIGN.md 7.18).  Included at the end of bam_device.hip, behind peakcount_device.inc: the kept records
 // of a call come from cx_filter as in pmx_dbam_bincount_add, a read's extent is k_fp_count's (fp_extent), the scans over tiles,
-// workgroups and line lengths are k_bam_scan.
+// workgroups and line lengths are k_bam_scan.  The second half of the file makes the parts of a bigWig file from the runs (7.18.1).
 //
 // The reads are the ones the correlation sees: the caller's filter, the chosen references, less the reads an attached exclude mask
 // drops.  L = extend, or the read's own length at 0; a forward read covers [pos1, pos1 + L - 1], a reverse read
@@ -361,6 +361,7 @@ int coverage_begin_impl(pmx_dbam *b, u32 extend, const uint8_t *use_ref)
     c.tiles = tiles;
     c.nc = nc;
     c.ext = extend;
+    for (u32 k = 0; k < nc; k++) c.chosen.push_back(seg[k].ref);
     c.bytes = 4 * slots;
     if (b->st) stream_note(*b);
     return 0;
@@ -608,6 +609,471 @@ int pmx_dbam_coverage_runs(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, 
 int64_t pmx_dbam_coverage_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
 {
     return guarded("pmx_dbam_coverage_text", [&] { return coverage_text_impl(b, first, n, buf, cap); });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The pileup as the parts of a bigWig file (DESIGN.md 7.18.1): pmx_dbam_coverage_ranges / _sections / _zoom_begin / _zoom_records,
+// all of them on the runs finish left.  The host puts the file together (pymasc_amd/coverage.py: assemble_bigwig); what it takes
+// from here are bytes it never parses and a table per pull that says where each section begins and ends.
+//
+//   k_cv_ranges      one lane per run: the first run of a reference writes its index (the host closes the references without one)
+//   k_cv_sections    one lane per run of a range of ONE reference: its 12-byte item (start0, end0, float32 depth) behind the 24-byte
+//                    header of its section; a section's first lane writes the header and the table row
+//   k_cv_zoom_fill   one lane per run: the bins of level 0 its run overlaps take its bases, depth, bases * depth and
+//                    bases * depth^2 by return-less integer atomics (add, min, max, 64-bit add); the sum of squares and the smallest
+//                    depth of the whole pileup are reduced over the wave, one atomic each per wave
+//   k_cv_zoom_fold   one lane per bin of level k + 1: its up to four bins of level k, no atomics
+//   k_cv_zoom_keep / k_bam_scan / k_cv_zoom_emit   the bins with a covered base, compacted by ballots into 32-byte records in
+//                    (id, start) order; integers become float32 by round-to-nearest-even; the table row of a section is written by
+//                    its first and its last record
+// Every accumulator is an integer, so the records do not depend on the order the atomics arrive in.  Bound: a u64 sum of squares is
+// exact while max_depth * fragment_bases < 2^64; zoom_begin refuses beyond it.  Device memory: 28 bytes per bin of level 0 and about a
+// third of that again for the higher levels, from zoom_begin until the last level is pulled; 12 bytes per run + 44 per section inside
+// sections; 12 per 256 bins + 32 per record + 20 per section inside zoom_records.
+
+namespace {
+
+struct ZmBins {         // the arrays of one level in its block
+    u64 *sum, *sq;
+    u32 *cnt, *mn, *mx;
+    __host__ __device__ ZmBins(u8 *p, u64 n)
+        : sum((u64 *)p), sq((u64 *)(p + 8 * n)), cnt((u32 *)(p + 16 * n)), mn((u32 *)(p + 20 * n)), mx((u32 *)(p + 24 * n))
+    {
+    }
+};
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_cv_ranges(const int *__restrict__ rref, u64 n, unsigned long long *__restrict__ first)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int r = rref[i];
+    if (i == 0 || rref[i - 1u] != r) first[r] = i;
+}
+
+// out: u32 words; run i of the range lies behind the headers of sections 0 .. i / ips: word 6 * (i / ips + 1) + 3 * i
+__global__ void __launch_bounds__(256) k_cv_sections(const u32 *__restrict__ rstart, const u32 *__restrict__ rend, const u32 *__restrict__ rdepth,
+                                                     u64 n, u32 ips, u32 id, u32 *__restrict__ out, u32 *__restrict__ table)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const u64 sec = i / ips;
+    u32 *p = out + 6u * (sec + 1u) + 3u * i;
+    const u32 a = rstart[i];
+    p[0] = a;
+    p[1] = rend[i];
+    p[2] = __float_as_uint(__uint2float_rn(rdepth[i]));
+    if (i == sec * ips) {
+        const u64 last = i + ips - 1u < n - 1u ? i + ips - 1u : n - 1u;
+        const u32 cnt = (u32)(last - i) + 1u, z = rend[last];
+        u32 *h = p - 6;
+        h[0] = id;
+        h[1] = a;
+        h[2] = z;
+        h[3] = 0;                           // itemStep
+        h[4] = 0;                           // itemSpan
+        h[5] = 1u | (cnt << 16);            // type 1 (bedGraph), a reserved byte, itemCount
+        u32 *T = table + 5u * sec;
+        T[0] = id;
+        T[1] = a;
+        T[2] = id;
+        T[3] = z;
+        T[4] = 24u + 12u * cnt;
+    }
+}
+
+// tot[0] += sum (end0 - start0) * depth^2, tot[1] = min(tot[1], depth); bins == nullptr: no level, the two totals alone
+__global__ void __launch_bounds__(256) k_cv_zoom_fill(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
+                                                      const u32 *__restrict__ rdepth, u64 n, const u32 *__restrict__ idof,
+                                                      const u64 *__restrict__ off0, u32 z, u64 nb, u8 *__restrict__ bins,
+                                                      unsigned long long *__restrict__ tot)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    u64 q = 0;
+    u32 dmin = 0xffffffffu;
+    if (i < n) {
+        const u32 s = rstart[i], e = rend[i], d = rdepth[i];
+        q = (u64)(e - s) * d * d;
+        dmin = d;
+        if (bins) {
+            const ZmBins B(bins, nb);
+            const u64 b0 = off0[idof[rref[i]]];
+            const u32 j1 = (e - 1u) / z;                      // (e > s >= 0 and e <= the reference's length: bin j1 exists)
+            for (u32 j = s / z; j <= j1; j++) {
+                const u64 lo = (u64)j * z, hi = lo + z;
+                const u64 w = (e < hi ? (u64)e : hi) - (s > lo ? (u64)s : lo);
+                const u64 b = b0 + j;
+                atomicAdd(&B.cnt[b], (u32)w);
+                atomicMin(&B.mn[b], d);
+                atomicMax(&B.mx[b], d);
+                atomicAdd((unsigned long long *)&B.sum[b], (unsigned long long)(w * d));
+                atomicAdd((unsigned long long *)&B.sq[b], (unsigned long long)(w * d * d));
+            }
+        }
+    }
+    q = cx_wave_sum(q);
+    for (int o = 32; o > 0; o >>= 1) {
+        const u32 y = __shfl_xor(dmin, o, 64);
+        dmin = y < dmin ? y : dmin;
+    }
+    if (lane == 0 && dmin != 0xffffffffu) {
+        atomicAdd(&tot[0], (unsigned long long)q);
+        atomicMin(&tot[1], (unsigned long long)dmin);
+    }
+}
+
+// the last id of off[0, nc] whose first bin is not behind `b` (b < off[nc]; an id without bins is never the answer)
+__device__ __forceinline__ u32 cv_zoom_id(const u64 *__restrict__ off, u32 nc, u64 b)
+{
+    u32 a = 0, z = nc;
+    while (z - a > 1u) {
+        const u32 mid = (a + z) / 2u;
+        if (off[mid] <= b) a = mid;
+        else z = mid;
+    }
+    return a;
+}
+
+__global__ void __launch_bounds__(256) k_cv_zoom_fold(u8 *__restrict__ src, u64 nsrc, u8 *__restrict__ dst, u64 ndst,
+                                                      const u64 *__restrict__ offs, const u64 *__restrict__ offd, u32 nc)
+{
+    const u64 b = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (b >= ndst) return;
+    const ZmBins S(src, nsrc), D(dst, ndst);
+    const u32 id = cv_zoom_id(offd, nc, b);
+    const u64 j = b - offd[id], ns = offs[id + 1u] - offs[id];
+    const u64 c0 = offs[id] + 4u * j, c1 = offs[id] + (4u * j + 4u < ns ? 4u * j + 4u : ns);     // (the last group may be short)
+    u64 sum = 0, sq = 0;
+    u32 cnt = 0, mn = 0xffffffffu, mx = 0;
+    for (u64 c = c0; c < c1; c++) {
+        sum += S.sum[c];
+        sq += S.sq[c];
+        cnt += S.cnt[c];
+        mn = S.mn[c] < mn ? S.mn[c] : mn;
+        mx = S.mx[c] > mx ? S.mx[c] : mx;
+    }
+    D.sum[b] = sum;
+    D.sq[b] = sq;
+    D.cnt[b] = cnt;
+    D.mn[b] = mn;
+    D.mx[b] = mx;
+}
+
+__global__ void __launch_bounds__(256) k_cv_zoom_keep(const u32 *__restrict__ cnt, u64 n, u32 *__restrict__ kcnt)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x;
+    const u64 b = (u64)blockIdx.x * 256u + t;
+    const u64 m = __ballot(b < n && cnt[b] != 0);
+    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// out: 8 u32 words per record; total[0]: the records of the level (k_bam_scan's total)
+__global__ void __launch_bounds__(256) k_cv_zoom_emit(u8 *__restrict__ bins, u64 n, const u64 *__restrict__ off, const u32 *__restrict__ lens,
+                                                      u32 nc, u32 z, u32 ips, const u64 *__restrict__ kbase, const u64 *__restrict__ total,
+                                                      u32 *__restrict__ out, u32 *__restrict__ table)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x, lane = t & 63u;
+    const u64 b = (u64)blockIdx.x * 256u + t;
+    const ZmBins B(bins, n);
+    const bool keep = b < n && B.cnt[b] != 0;
+    const u64 m = __ballot(keep);
+    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (!keep) return;
+    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
+    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
+    const u32 id = cv_zoom_id(off, nc, b);
+    const u64 a = (b - off[id]) * z;
+    const u32 start = (u32)a, end = a + z < (u64)lens[id] ? (u32)(a + z) : lens[id];
+    u32 *p = out + 8u * o;
+    p[0] = id;
+    p[1] = start;
+    p[2] = end;
+    p[3] = B.cnt[b];
+    p[4] = __float_as_uint(__uint2float_rn(B.mn[b]));
+    p[5] = __float_as_uint(__uint2float_rn(B.mx[b]));
+    p[6] = __float_as_uint(__ull2float_rn((unsigned long long)B.sum[b]));
+    p[7] = __float_as_uint(__ull2float_rn((unsigned long long)B.sq[b]));
+    const u64 sec = o / ips;
+    const u32 k = (u32)(o - sec * ips);
+    u32 *T = table + 5u * sec;
+    if (k == 0) {
+        T[0] = id;
+        T[1] = start;
+    }
+    if (k == ips - 1u || o + 1u == total[0]) {
+        T[2] = id;
+        T[3] = end;
+        T[4] = 32u * (k + 1u);
+    }
+}
+
+namespace {
+
+void zoom_drop(Coverage &c)
+{
+    c.zbins = DevAlloc{};
+    c.ztab = DevAlloc{};
+    c.bytes -= std::min(c.zbytes, c.bytes);
+    c.zbytes = 0;
+    c.zlevels = c.z0 = 0;
+    c.znb.clear();
+    c.zoff.clear();
+}
+
+// the first run of every chosen reference in header order, one more entry closing them; computed once per pileup
+int coverage_ranges_make(pmx_dbam *b)
+{
+    Coverage &c = b->cv;
+    if (!c.ranges.empty()) return 0;
+    const u64 nref = b->ref_names.size(), nc = c.chosen.size();
+    std::vector<u64> first(std::max<u64>(nref, 1), ~0ull);
+    HIPOK(hipSetDevice(b->device));
+    if (c.nruns) {
+        DevAlloc d_first;
+        CvHold held(b);
+        held.add(8 * first.size());
+        HIPOK(hipMalloc(&d_first.p, 8 * first.size()));
+        HIPOK(hipMemsetAsync(d_first.p, 0xff, 8 * first.size(), b->stream));
+        hipLaunchKernelGGL(k_cv_ranges, dim3((unsigned)((c.nruns + 255) / 256)), dim3(256), 0, b->stream, CvRuns(c.runs.as<u8>(), c.nruns).ref, c.nruns,
+                           d_first.as<unsigned long long>());
+        HIPOK(hipGetLastError());
+        HIPOK(hipMemcpyAsync(first.data(), d_first.p, 8 * first.size(), hipMemcpyDeviceToHost, b->stream));
+        HIPOK(hipStreamSynchronize(b->stream));
+    }
+    std::vector<u64> r(nc + 1, c.nruns);
+    for (u64 k = nc; k-- > 0;) r[k] = first[(u64)c.chosen[k]] != ~0ull ? first[(u64)c.chosen[k]] : r[k + 1];
+    for (u64 k = 0; k < nc; k++)
+        if (r[k] > r[k + 1]) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_ranges: the runs are not in header order");
+    c.ranges = std::move(r);
+    return 0;
+}
+
+int64_t coverage_ranges_impl(pmx_dbam *b, int64_t *first, int64_t cap)
+{
+    if (int rc = coverage_range(b, "pmx_dbam_coverage_ranges", 0, 0)) return rc;
+    const int64_t n = (int64_t)b->cv.chosen.size() + 1;
+    if (!first) return n;
+    if (cap < n) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_ranges: the buffer is too small: " + std::to_string(n) + " entries are needed");
+    if (int rc = coverage_ranges_make(b)) return rc;
+    for (int64_t k = 0; k < n; k++) first[k] = (int64_t)b->cv.ranges[(u64)k];
+    return n;
+}
+
+int64_t coverage_sections_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
+                               uint32_t *table, int64_t table_cap)
+{
+    const char *fn = "pmx_dbam_coverage_sections";
+    if (int rc = coverage_range(b, fn, first, n)) return rc;
+    if (items < 1 || items > 65535) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": 1 to 65535 items per section");
+    if (buf && (cap < 0 || table_cap < 0)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": a negative capacity");
+    if (n == 0) return 0;
+    if (int rc = coverage_ranges_make(b)) return rc;
+    Coverage &c = b->cv;
+    const auto it = std::upper_bound(c.ranges.begin(), c.ranges.end(), (u64)first);       // (the first reference that begins behind `first`)
+    if (it == c.ranges.end() || (u64)first + (u64)n > *it) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the range holds two references");
+    const u64 m = (u64)n, nsec = (m + items - 1) / items, bytes = 24 * nsec + 12 * m;
+    if (!buf) return (int64_t)bytes;
+    if ((u64)cap < bytes) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
+    if (!table || (u64)table_cap < nsec)
+        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the table is too small: " + std::to_string(nsec) + " rows are needed");
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    DevAlloc d_out;
+    CvHold held(b);
+    if (hipMalloc(&d_out.p, bytes + 20 * nsec) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PMX_DBAM_ERR_OPEN, std::string(fn) + ": out of device memory for " + std::to_string(bytes + 20 * nsec) + " bytes of sections");
+    }
+    held.add(bytes + 20 * nsec);
+    const CvRuns V(c.runs.as<u8>(), c.nruns);
+    u32 *d_table = (u32 *)(d_out.as<u8>() + bytes);
+    hipLaunchKernelGGL(k_cv_sections, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
+                       chrom_id, d_out.as<u32>(), d_table);
+    HIPOK(hipGetLastError());
+    HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipMemcpyAsync(table, d_table, 20 * nsec, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    return (int64_t)bytes;
+}
+
+int coverage_zoom_begin_impl(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t *out)
+{
+    const char *fn = "pmx_dbam_coverage_zoom_begin";
+    if (int rc = coverage_range(b, fn, 0, 0)) return rc;
+    if (!out || !chrom_id) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": null " + (out ? "chromosome ids" : "output"));
+    out[0] = out[1] = 0;
+    Coverage &c = b->cv;
+    if (levels > PMX_COVERAGE_ZOOM_LEVELS || (levels && z0 < 1)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at most 10 levels, and a reduction of at least 1");
+    if ((unsigned __int128)c.tot[4] * c.tot[3] >> 64)
+        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": max_depth * fragment_bases is 2^64 or more: the sums of squares would not be exact");
+    const u64 nref = b->ref_names.size(), nc = c.chosen.size();
+    std::vector<u32> idof(std::max<u64>(nref, 1), 0), lens(nc, 0);
+    std::vector<u8> seen(nc, 0);
+    for (u64 k = 0; k < nc; k++) {
+        const u32 id = chrom_id[c.chosen[k]];
+        if (id >= nc || seen[id]) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the chosen references' ids are not 0 .. n - 1, each once");
+        seen[id] = 1;
+        idof[(u64)c.chosen[k]] = id;
+        lens[id] = (u32)std::max<int64_t>(b->ref_lens[(u64)c.chosen[k]], 0);
+    }
+    zoom_drop(c);
+    std::vector<u64> off((u64)levels * (nc + 1), 0), znb(levels, 0), zoff(levels, 0);
+    u64 z = z0, bin_bytes = 0;
+    for (u32 k = 0; k < levels; k++, z *= 4) {
+        if (z > 0xffffffffull) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": a reduction of 2^32 or more");
+        u64 *o = off.data() + (u64)k * (nc + 1);
+        for (u64 id = 0; id < nc; id++) o[id + 1] = o[id] + ((u64)lens[id] + z - 1) / z;
+        znb[k] = o[nc];
+        zoff[k] = bin_bytes;
+        bin_bytes += (28 * znb[k] + 7) / 8 * 8;
+    }
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    const u64 tab_bytes = 8 * off.size() + 4 * idof.size() + 4 * std::max<u64>(nc, 1);
+    HIPOK(hipMalloc(&c.ztab.p, tab_bytes));
+    if (bin_bytes && hipMalloc(&c.zbins.p, bin_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c.ztab = DevAlloc{};
+        return fail(PMX_DBAM_ERR_OPEN, std::string(fn) + ": out of device memory for the zoom bins: " + std::to_string(bin_bytes) +
+                                           " bytes asked for (28 per bin of " + std::to_string(z0) + " bases, and a third again)");
+    }
+    c.zbytes = tab_bytes + bin_bytes;
+    c.bytes += c.zbytes;
+    if (b->st) stream_note(*b);
+    c.zlevels = levels;
+    c.z0 = z0;
+    c.znb = znb;
+    c.zoff = zoff;
+    struct Drop {       // a failure from here on leaves no bins
+        Coverage &c;
+        bool ok = false;
+        ~Drop()
+        {
+            if (!ok) zoom_drop(c);
+        }
+    } drop{c};
+    u64 *d_off = c.ztab.as<u64>();
+    u32 *d_idof = (u32 *)(d_off + off.size()), *d_lens = d_idof + idof.size();
+    if (!off.empty()) HIPOK(hipMemcpyAsync(d_off, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
+    HIPOK(hipMemcpyAsync(d_idof, idof.data(), 4 * idof.size(), hipMemcpyHostToDevice, st));
+    if (nc) HIPOK(hipMemcpyAsync(d_lens, lens.data(), 4 * nc, hipMemcpyHostToDevice, st));
+    unsigned long long tot[2] = {0, ~0ull};
+    DevAlloc d_tot;
+    HIPOK(hipMalloc(&d_tot.p, 16));
+    HIPOK(hipMemcpyAsync(d_tot.p, tot, 16, hipMemcpyHostToDevice, st));
+    if (levels && znb[0]) {
+        const ZmBins B(c.zbins.as<u8>(), znb[0]);
+        HIPOK(hipMemsetAsync(c.zbins.p, 0, 28 * znb[0], st));
+        HIPOK(hipMemsetAsync(B.mn, 0xff, 4 * znb[0], st));
+    }
+    if (c.nruns) {
+        const CvRuns V(c.runs.as<u8>(), c.nruns);
+        hipLaunchKernelGGL(k_cv_zoom_fill, dim3((unsigned)((c.nruns + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, c.nruns, d_idof,
+                           d_off, z0, levels ? znb[0] : 0, levels && znb[0] ? c.zbins.as<u8>() : (u8 *)nullptr, d_tot.as<unsigned long long>());
+        HIPOK(hipGetLastError());
+    }
+    for (u32 k = 0; k + 1 < levels; k++) {
+        if (!znb[k + 1]) continue;
+        hipLaunchKernelGGL(k_cv_zoom_fold, dim3((unsigned)((znb[k + 1] + 255) / 256)), dim3(256), 0, st, c.zbins.as<u8>() + zoff[k], znb[k],
+                           c.zbins.as<u8>() + zoff[k + 1], znb[k + 1], d_off + (u64)k * (nc + 1), d_off + (u64)(k + 1) * (nc + 1), (u32)nc);
+        HIPOK(hipGetLastError());
+    }
+    HIPOK(hipMemcpyAsync(tot, d_tot.p, 16, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));       // (off, idof and lens are locals)
+    out[0] = tot[0];
+    out[1] = c.nruns ? tot[1] : 0;
+    drop.ok = true;
+    if (!levels) zoom_drop(c);              // (nothing to pull)
+    return 0;
+}
+
+int64_t coverage_zoom_records_impl(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table, int64_t table_cap)
+{
+    const char *fn = "pmx_dbam_coverage_zoom_records";
+    if (int rc = coverage_range(b, fn, 0, 0)) return rc;
+    Coverage &c = b->cv;
+    if (level >= c.zlevels) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": no bins of that level: call pmx_dbam_coverage_zoom_begin first");
+    if (items < 1) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at least 1 item per section");
+    if (buf && (cap < 0 || table_cap < 0)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": a negative capacity");
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    const u64 nb = c.znb[level], nwg = (nb + 255) / 256, nc = c.chosen.size();
+    u8 *bins = c.zbins.as<u8>() + c.zoff[level];
+    u64 total = 0;
+    DevAlloc d_k, d_kb, d_tot, d_out;
+    CvHold held(b);
+    if (nwg) {
+        held.add(12 * nwg + 16);
+        HIPOK(hipMalloc(&d_k.p, 4 * nwg));
+        HIPOK(hipMalloc(&d_kb.p, 8 * nwg));
+        HIPOK(hipMalloc(&d_tot.p, 16));
+        hipLaunchKernelGGL(k_cv_zoom_keep, dim3((unsigned)nwg), dim3(256), 0, st, ZmBins(bins, nb).cnt, nb, d_k.as<u32>());
+        HIPOK(hipGetLastError());
+        hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), nwg, d_kb.as<u64>(), d_tot.as<u64>());
+        HIPOK(hipGetLastError());
+        HIPOK(hipMemcpyAsync(&total, d_tot.p, 8, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+    }
+    const u64 bytes = 32 * total, nsec = (total + items - 1) / items;
+    if (!buf) return (int64_t)bytes;
+    if ((u64)cap < bytes) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
+    if (!table || (u64)table_cap < nsec)
+        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the table is too small: " + std::to_string(nsec) + " rows are needed");
+    if (total) {
+        if (hipMalloc(&d_out.p, bytes + 20 * nsec) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PMX_DBAM_ERR_OPEN, std::string(fn) + ": out of device memory for " + std::to_string(bytes + 20 * nsec) + " bytes of records");
+        }
+        held.add(bytes + 20 * nsec);
+        const u64 *d_off = c.ztab.as<u64>() + (u64)level * (nc + 1);
+        const u32 *d_lens = (const u32 *)(c.ztab.as<u64>() + (u64)c.zlevels * (nc + 1)) + std::max<u64>(b->ref_names.size(), 1);
+        u64 z = c.z0;
+        for (u32 k = 0; k < level; k++) z *= 4;
+        u32 *d_table = (u32 *)(d_out.as<u8>() + bytes);
+        hipLaunchKernelGGL(k_cv_zoom_emit, dim3((unsigned)nwg), dim3(256), 0, st, bins, nb, d_off, d_lens, (u32)nc, (u32)z, items, d_kb.as<u64>(),
+                           d_tot.as<u64>(), d_out.as<u32>(), d_table);
+        HIPOK(hipGetLastError());
+        HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(table, d_table, 20 * nsec, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+    }
+    if (level + 1 == c.zlevels) zoom_drop(c);       // the last level is out: the bins are freed
+    return (int64_t)bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t pmx_dbam_coverage_ranges(pmx_dbam *b, int64_t *first, int64_t cap)
+{
+    return guarded("pmx_dbam_coverage_ranges", [&] { return coverage_ranges_impl(b, first, cap); });
+}
+
+int64_t pmx_dbam_coverage_sections(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
+                                   uint32_t *table, int64_t table_cap)
+{
+    return guarded("pmx_dbam_coverage_sections", [&] { return coverage_sections_impl(b, first, n, chrom_id, items, buf, cap, table, table_cap); });
+}
+
+int pmx_dbam_coverage_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t out[2])
+{
+    return guarded("pmx_dbam_coverage_zoom_begin", [&] { return coverage_zoom_begin_impl(b, z0, levels, chrom_id, out); });
+}
+
+int64_t pmx_dbam_coverage_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
+                                       int64_t table_cap)
+{
+    return guarded("pmx_dbam_coverage_zoom_records", [&] { return coverage_zoom_records_impl(b, level, items, buf, cap, table, table_cap); });
 }
 
 }  // extern "C"

@@ -60,6 +60,15 @@ struct Coverage {
     u64 bytes = 0;                   // device bytes the pileup holds now
     u32 nc = 0, ext = 0;             // chosen references; extend
     u64 tot[5] = {0, 0, 0, 0, 0};    // reads, runs, covered bases, fragment bases, largest depth
+    std::vector<int> chosen;         // the chosen references, in header order
+    std::vector<u64> ranges;         // runs state, once asked for: the first run of every chosen reference, one more entry closing them
+    // the zoom bins of a bigWig file (pmx_dbam_coverage_zoom_*; DESIGN.md 7.18.1): from zoom_begin until the last level is pulled
+    DevAlloc zbins;                  // per level: u64 sum, u64 sum of squares, u32 covered bases, u32 min, u32 max of every bin (28 bytes)
+    DevAlloc ztab;                   // u64 per level and chromosome id: its first bin (one more closes a level); u32 id of every
+                                     // reference; u32 length of every id
+    u32 zlevels = 0, z0 = 0;         // levels; the reduction of level 0
+    std::vector<u64> znb, zoff;      // per level: its bins; its first byte in zbins
+    u64 zbytes = 0;                  // device bytes of zbins and ztab, counted in `bytes`
     bool on() const { return state == CV_TABLE; }
     u64 held() const { return bytes; }
 };

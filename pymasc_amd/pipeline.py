@@ -40,7 +40,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         chi2_pval: float = 0.05, chrom_sizes=None, complexity: bool = False, exclude_regions=None,
         fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None,
         peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto", gc_bias=None, gc_window: int = 100,
-        fragments: bool = False, fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0):
+        fragments: bool = False, fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
+        coverage_format: str = "bedgraph", coverage_compress: bool = False):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -89,7 +90,10 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     ``"auto"`` (the default) extends to the run's own fragment-length estimate, ``stats.genome_wide_stats(...).est_lib_len``
     with the run's statistics options, whether or not ``stats`` writes them; it exists only after the correlation, so rank 0
     counts on one more read of the file, and a stream (``-``, a FIFO) with ``"auto"`` is a ValueError before anything runs.  The
-    device table is 4 bytes per chosen base (12.4 GB for hg38).
+    device table is 4 bytes per chosen base (12.4 GB for hg38).  ``coverage_format="bigwig"`` writes ``<stem>_coverage.bw`` instead
+    (DESIGN.md 7.18.1): the same runs as a bigWig file with zoom levels, its sections and zoom records made on the GPU with device
+    ingest; a depth is a float32 there, exact up to 2^24 and rounded to nearest above.  ``coverage_compress``: every section of
+    that file through zlib on the host; with ``"bedgraph"`` it is a ValueError.
     ``gc_bias``: a genome FASTA (plain, gzip or bgzip): rank 0 also writes ``<stem>_gcbias.tab`` (pymasc_amd.gcbias, DESIGN.md
     7.19): the reads the fingerprint counts, each placed on the genome window of ``gc_window`` bases (1 .. 1024) that begins at
     its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
@@ -172,6 +176,8 @@ class _Settings:
     peaks_extend: int
     coverage: bool
     coverage_extend: object         # an int (0: every read's own length), or "auto": the run's fragment-length estimate
+    coverage_format: str            # "bedgraph" or "bigwig"
+    coverage_compress: bool         # the sections of a bigWig file through zlib
     gc_bias: object                 # None, or the _GcGenome parsed once for the call
     gc_window: int
     fragments: bool
@@ -224,7 +230,9 @@ def _settings(kw: dict) -> _Settings:
     extend = kw["coverage_extend"]
     if extend not in ("auto", coverage.PAIR) and (isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0):
         raise ValueError("coverage_extend is \"auto\", \"pair\" or an integer of at least 0")
-    given.update(coverage=bool(kw["coverage"]), coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend))
+    given.update(coverage=bool(kw["coverage"]), coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend),
+                 coverage_format=coverage.check_format(kw["coverage_format"], kw["coverage_compress"]),
+                 coverage_compress=bool(kw["coverage_compress"]))
     given.update(fragments=bool(kw["fragments"]), fragments_max=fragments.check_max_size(kw["fragments_max"]))
     if kw["tss"] is None and (int(kw["tss_flank"]) != tss.DEFAULT_FLANK or int(kw["tss_extend"])):
         raise ValueError("tss_flank and tss_extend need tss")
@@ -471,34 +479,56 @@ def _count_again(s: _Settings, path, count):
 
 
 class _CoverageCount(_SideCount):
-    """The fragment pileup of one file's run (pymasc_amd.coverage); its value is (extend, reads, chunks of lines).  An integer
-    ``coverage_extend`` is counted where every _SideCount is: a host reader's ``Coverage`` is kept for ``write``; a device reader's
-    lines are formatted on the GPU while the reader is open and kept in an unnamed temporary file in the output directory until
-    ``write`` names them.  ``"auto"`` needs the run's statistics, so it is not hooked: ``write`` counts with
-    ``statistics().est_lib_len`` on one more read of the file (``_count_again``), as several ranks do for an integer, and writes
-    while that reader is open."""
+    """The fragment pileup of one file's run (pymasc_amd.coverage); its value is (extend, reads, chunks of lines), or the chunks of
+    the whole file for a bigWig.  An integer ``coverage_extend`` is counted where every _SideCount is: a host reader's
+    ``Coverage`` is kept for ``write``; a device reader's lines are formatted on the GPU while the reader is open and kept in an
+    unnamed temporary file in the output directory until ``write`` names them -- for a bigWig the sections, their tables and the
+    zoom records are pulled and the file is assembled there.  ``"auto"`` needs the run's statistics, so it is not hooked: ``write``
+    counts with ``statistics().est_lib_len`` on one more read of the file (``_count_again``), as several ranks do for an integer,
+    and writes while that reader is open."""
     hooked = property(lambda self: self.s.coverage_extend != "auto")
 
     def _take(self, reader, names, acc=None, extend=None):
         """``extend`` None: the run's integer, and the reader closes before the lines are written: they are spooled."""
         from .bam_device import DeviceBamReader
         spool, mapq = extend is None, int(self.s.mapq_criteria)
+        bigwig = self.s.coverage_format == "bigwig"
         if spool:
             extend = self.s.coverage_extend     # (an integer or "pair")
         if not isinstance(reader, DeviceBamReader):
             c = coverage.from_reader(reader, mapq, names, extend, self.s.fragments_max)
-            return extend, c.reads, c.text_chunks()
+            return self._bigwig(coverage.bigwig_source(c), False) if bigwig else (extend, c.reads, c.text_chunks())
         if acc is None:             # (an armed count is not built again: its ``begin`` would zero the table)
             acc = coverage.device_count_of(reader, mapq, names, extend, self.s.fragments_max)
         reads = acc.finish(reader)["reads"]
+        if bigwig:
+            return self._bigwig(coverage.bigwig_source(acc, reader), True)
         if not spool:
             return extend, reads, acc.text_chunks(reader)
-        import tempfile
-        Path(self.s.outdir).mkdir(parents=True, exist_ok=True)
-        fp = tempfile.TemporaryFile(dir=str(self.s.outdir))
+        fp = self._temporary()
         for chunk in acc.text_chunks(reader):
             fp.write(chunk)
         return extend, reads, _spooled(fp)
+
+    def _temporary(self):
+        import tempfile
+        Path(self.s.outdir).mkdir(parents=True, exist_ok=True)
+        return tempfile.TemporaryFile(dir=str(self.s.outdir))
+
+    def _bigwig(self, source, now: bool):
+        """The chunks of the bigWig file of ``source``; ``now``: assembled at once (the source's reader is open only now)."""
+        def chunks():
+            fp = self._temporary()
+            try:
+                coverage.assemble_bigwig(fp, source, self.s.coverage_compress)
+            except BaseException:
+                fp.close()
+                raise
+            return _spooled(fp)
+        if not now:
+            return _Later(chunks)
+        done = chunks()
+        return _Later(lambda: done)
 
     def write(self, path, basename: str, statistics=None) -> Path:
         s = self.s
@@ -507,6 +537,22 @@ class _CoverageCount(_SideCount):
             return self.row.write(s, base, basename, self.value)
         extend = int(statistics().est_lib_len) if s.coverage_extend == "auto" else s.coverage_extend
         return _count_again(s, path, lambda r, names: self.row.write(s, base, basename, self._take(r, names, None, extend)))
+
+
+class _Later:
+    """Chunks of bytes that are made when they are first asked for."""
+
+    def __init__(self, make):
+        self.make = make
+
+    def __iter__(self):
+        return iter(self.make())
+
+
+def _write_coverage(s: _Settings, base, basename: str, value) -> Path:
+    if s.coverage_format == "bigwig":
+        return coverage.write_file(str(base) + coverage.BIGWIG_SUFFIX, value)
+    return coverage.write_track(base, basename, *value)
 
 
 def _spooled(fp, size: int = 1 << 22):
@@ -530,7 +576,7 @@ def _write_fingerprint(s: _Settings, base, basename: str, value) -> Path:
 
 _Side = namedtuple("_Side", "kind enabled suffix module args arm write count", defaults=(_SideCount,))
 _Side.__doc__ = """One count taken beside the correlation: ``kind`` (its name in ``native.SIDE_KINDS``), ``enabled(s)``, the
-``suffix`` of its output, its ``module`` (``from_reader``), ``args(s, names)`` -- what ``from_reader`` takes after the reader, and
+``suffix`` of its output (or a function of the settings that gives it), its ``module`` (``from_reader``), ``args(s, names)`` -- what ``from_reader`` takes after the reader, and
 the stream reader's ``arm`` method (named here) takes --, ``write(s, base, basename, value)`` and the class that takes it."""
 
 #: every side count, in the order the outputs are written and listed (that of ``native.SIDE_KINDS``)
@@ -544,9 +590,9 @@ _SIDES = (
     _Side("peaks", lambda s: s.peaks is not None, peaks.PEAKS_SUFFIX, peaks,
           lambda s, names: (s.peaks, int(s.mapq_criteria), names, s.peaks_extend), "arm_peaks",
           lambda s, base, basename, value: peaks.write_peaks(base, basename, value, s.peaks.source or "")),
-    _Side("coverage", lambda s: s.coverage, coverage.COVERAGE_SUFFIX, coverage,
+    _Side("coverage", lambda s: s.coverage, lambda s: coverage.SUFFIXES[s.coverage_format], coverage,
           lambda s, names: (int(s.mapq_criteria), names, s.coverage_extend, s.fragments_max), "arm_coverage",
-          lambda s, base, basename, value: coverage.write_track(base, basename, *value), _CoverageCount),
+          _write_coverage, _CoverageCount),
     _Side("gcbias", lambda s: s.gc_bias is not None, gcbias.GCBIAS_SUFFIX, gcbias,      # (the genome is parsed when first needed)
           lambda s, names: (s.gc_bias.open(), int(s.mapq_criteria), names, s.gc_window), "arm_gcbias",
           lambda s, base, basename, value: gcbias.write_gcbias(base, basename, value)),
@@ -662,7 +708,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               complexity: bool = False, exclude_regions=None, fingerprint: bool = False, fingerprint_bin: int = 500,
               fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0, coverage: bool = False,
               coverage_extend="auto", gc_bias=None, gc_window: int = 100, fragments: bool = False,
-              fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0) -> List[FileResult]:
+              fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
+              coverage_format: str = "bedgraph", coverage_compress: bool = False) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -825,7 +872,7 @@ def _warn_existing(s: _Settings, bases):
     has_track = s.mappability_path is not None
     suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
                                 ("_stats.tab", s.stat_opts is not None)) if on]
-    suffixes += [row.suffix for row in _SIDES if row.enabled(s)]
+    suffixes += [row.suffix(s) if callable(row.suffix) else row.suffix for row in _SIDES if row.enabled(s)]
     for b in bases:
         for suffix in suffixes:
             path = Path(s.outdir) / (b + suffix)

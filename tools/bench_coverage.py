@@ -4,7 +4,12 @@ the same reads: python tools/bench_coverage.py --reads 20000000 --out profiles/c
 
 The times are wall-clock around the library calls (allocations, the zeroing of the table and the result copies included), medians
 after one warm-up round, split per call.  --reps 1 --no-open --no-host is the run to put under `rocprofv3 --kernel-trace --stats`
-for the split of the kernels; the trace is a run of its own."""
+for the split of the kernels; the trace is a run of its own.
+
+--format bigwig [--compress] also writes the bigWig file of the same runs in every round, behind the text pull, and
+splits its time into the section pulls, zoom begin (the fill and the folds), the record pulls and the rest, which is the host's
+assembly (R-trees, the file writes and, with --compress, zlib); profiles/coverage_bigwig.json is
+python tools/bench_coverage.py --reads 20000000 --format bigwig --no-host --out profiles/coverage_bigwig.json"""
 import argparse
 import json
 import os
@@ -20,6 +25,40 @@ from pymasc_amd.native import PMX_BAM_DEFAULT_EXCLUDE  # noqa: E402
 from tools.bench_ingest import synth_bam  # noqa: E402
 
 
+class _Timed:
+    """A source of coverage.assemble_bigwig that adds up the time spent in each of its three kinds of calls."""
+
+    def __init__(self, src):
+        self.src, self.refs, self.totals = src, src.refs, src.totals
+        self.t = dict(sections=0.0, zoom_begin=0.0, zoom_records=0.0)
+        self.pulled = dict(sections=0, zoom_records=0)
+
+    def section_chunks(self, k, chrom_id, items):
+        it = iter(self.src.section_chunks(k, chrom_id, items))
+        while True:
+            t0 = time.perf_counter()
+            got = next(it, None)
+            self.t["sections"] += time.perf_counter() - t0
+            if got is None:
+                return
+            self.pulled["sections"] += len(got[0]) + got[1].nbytes
+            yield got
+
+    def zoom_begin(self, z0, levels, ids):
+        t0 = time.perf_counter()
+        out = self.src.zoom_begin(z0, levels, ids)
+        self.t["zoom_begin"] += time.perf_counter() - t0
+        self.z0, self.levels = z0, levels
+        return out
+
+    def zoom_records(self, level, items):
+        t0 = time.perf_counter()
+        out = self.src.zoom_records(level, items)
+        self.t["zoom_records"] += time.perf_counter() - t0
+        self.pulled["zoom_records"] += len(out[0]) + out[1].nbytes
+        return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=20_000_000)
@@ -29,6 +68,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-open", action="store_true", help="skip the timing of open + decode")
     ap.add_argument("--no-host", action="store_true", help="skip coverage.count_host on the same reads")
+    ap.add_argument("--format", choices=coverage.FORMATS, default="bedgraph", help="bigwig: also time the bigWig file of the same runs")
+    ap.add_argument("--compress", action="store_true", help="the sections of the bigWig file through zlib")
+    ap.add_argument("--bigwig-path", default="/tmp/pymasc_coverage_bench.bw")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not os.path.exists(a.path):
@@ -45,6 +87,7 @@ def main():
         res["library_version"] = int(r._L.pmx_dbam_version())
         res["table_bytes"] = 4 * (sum(r.lengths) + len(r.lengths))
         split = dict(begin=[], add=[], finish=[], text=[], whole=[])
+        bw = dict(sections=[], zoom_begin=[], zoom_records=[], assembly=[], whole=[])
         for rep in range(a.reps + 1):               # (the first round warms up)
             t = [time.perf_counter()]
             acc = coverage.DeviceCount(r, a.mapq, None, a.extend)
@@ -55,6 +98,19 @@ def main():
             t.append(time.perf_counter())
             size = sum(len(chunk) for chunk in acc.text_chunks(r))
             t.append(time.perf_counter())
+            if a.format == "bigwig":
+                src = _Timed(coverage.bigwig_source(acc, r))
+                t0 = time.perf_counter()
+                with open(a.bigwig_path, "w+b") as fp:
+                    coverage.assemble_bigwig(fp, src, a.compress)
+                whole = time.perf_counter() - t0
+                if rep:
+                    for name in ("sections", "zoom_begin", "zoom_records"):
+                        bw[name].append(src.t[name])
+                    bw["assembly"].append(whole - sum(src.t.values()))
+                    bw["whole"].append(whole)
+                    res["bigwig"] = dict(bytes=os.path.getsize(a.bigwig_path), compress=a.compress, z0=src.z0, levels=src.levels,
+                                         section_bytes_pulled=src.pulled["sections"], record_bytes_pulled=src.pulled["zoom_records"])
             if rep:
                 for k, name in enumerate(("begin", "add", "finish", "text")):
                     split[name].append(t[k + 1] - t[k])
@@ -62,6 +118,9 @@ def main():
         res.update(totals, text_bytes=size, text_chunk_runs=coverage.TEXT_CHUNK,
                    **{k + "_s": v for k, v in split.items()},              # (every round, in the order they ran)
                    **{k + "_median_s": statistics.median(v) for k, v in split.items()})
+        if a.format == "bigwig":
+            res["bigwig"].update(**{k + "_s": v for k, v in bw.items()}, **{k + "_median_s": statistics.median(v) for k, v in bw.items()})
+            os.unlink(a.bigwig_path)
         if not a.no_host:
             cols = r._fetch(0, n)
             t0 = time.perf_counter()
