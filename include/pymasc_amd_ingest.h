@@ -287,6 +287,33 @@ int pmx_dbam_coverage_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, cons
 int64_t pmx_dbam_coverage_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
                                        int64_t table_cap);
 
+/* A DEFLATE encoder on the device (version >= 18): independent chunks of at most PMX_DEFLATE_MAX_CHUNK bytes, each
+ * turned into one complete zlib stream (RFC 1950 around RFC 1951): the header 0x78 with a 32-KB window and no dictionary, DEFLATE
+ * blocks of which the last is marked final, the big-endian Adler-32 of the raw bytes.  Matches have length 4 .. 258 and distance
+ * 1 .. 32768 (greedy parse, the nearest earlier position with the same four bytes); per chunk the smallest of one dynamic block
+ * (code lengths of at most 15 bits built on the device, 7 for the code-length alphabet), one fixed block and stored blocks is
+ * written, so a stream of n raw bytes is never longer than pmx_ddeflate_bound(n) = n + 5 * max(1, ceil(n / 65535)) + 6; n == 0 is
+ * a valid stream.  The same bytes give the same stream on every call.  The streams decode to the raw bytes; they are not the bytes
+ * zlib's own encoder writes.
+ * pmx_ddeflate: all pointers are host pointers; chunk i is src[offsets[i], offsets[i + 1]) for i < n.  The n streams are written end
+ * to end into dst[cap] and their lengths into sizes[n]; returns their total.  A NULL pointer, a negative n or cap, descending
+ * offsets, a chunk above the maximum (all before any launch) and a cap below the total: PMX_DBAM_ERR_INVALID; out of device
+ * memory: PMX_DBAM_ERR_OPEN with the bytes asked for.  Device memory: the raw bytes, 4 bytes of tokens per raw byte, a slot of
+ * `bound` per chunk, then the streams.
+ * sections_z / zoom_records_z: pmx_dbam_coverage_sections / _zoom_records with every section compressed before it leaves the device.
+ * `table` is exactly what the raw call gives (column 4 stays the RAW size of the section, what uncompressBufSize needs);
+ * zsizes[section] = the length of its stream, and buf holds the streams end to end.  With buf NULL the return value is an upper
+ * bound of the bytes (the sum of the sections' bounds), with a buffer the bytes written; a cap below them is PMX_DBAM_ERR_INVALID.
+ * A raw section must fit a chunk: more than 5459 items (sections_z) or 2048 items (zoom_records_z) is PMX_DBAM_ERR_INVALID.
+ * The scratch counts towards pmx_dbam_stream_info's peak and is freed with the call; pulling the last level frees the bins. */
+#define PMX_DEFLATE_MAX_CHUNK 65536u
+uint64_t pmx_ddeflate_bound(uint64_t n);
+int64_t pmx_ddeflate(int device, const uint8_t *src, const uint64_t *offsets, int64_t n, uint8_t *dst, int64_t cap, uint32_t *sizes);
+int64_t pmx_dbam_coverage_sections_z(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
+                                     uint32_t *table, int64_t table_cap, uint32_t *zsizes);
+int64_t pmx_dbam_coverage_zoom_records_z(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
+                                         int64_t table_cap, uint32_t *zsizes);
+
 /* Counters: alignment records walked and records kept by the last decode, uncompressed / compressed bytes of the file,
  * BGZF members, and how many 16-KB pieces had to be walked again because their guessed first record was wrong.  An indexed
  * handle: bytes_out is the length of its stream (header + selected records), bytes_in and members count only the members

@@ -259,6 +259,12 @@ def get_parser() -> argparse.ArgumentParser:
                           "2^24 and rounded to nearest above; implies --coverage")
     out.add_argument("--coverage-compress", action="store_true",
                      help="put every section of the bigWig file through zlib (on the host); needs --coverage-format bigwig")
+    out.add_argument("--coverage-deflate", choices=("host", "device"),
+                     help="where the sections of the bigWig file are compressed; implies --coverage-compress, so it needs "
+                          "--coverage-format bigwig.  host (what --coverage-compress alone does): zlib on host threads; device: the "
+                          "GPU's own DEFLATE encoder, before the sections leave it, for inputs read by device ingest.  A section "
+                          "holds 1024 items here; the device encoder takes at most 2048 items per section.  Its compressed bytes "
+                          "differ from zlib's; the decoded file does not")
     out.add_argument("--gc-bias", metavar="FASTA", type=Path,
                      help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
                           "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
@@ -330,6 +336,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("argument --peaks: no such file: '{}'".format(args.peaks))
     if args.coverage_extend is not None or args.coverage_format is not None:
         args.coverage = True
+    if args.coverage_deflate is not None:
+        if args.coverage_format != "bigwig":
+            parser.error("argument --coverage-deflate: needs --coverage-format bigwig")
+        args.coverage_compress = True
     if args.coverage_compress and args.coverage_format != "bigwig":
         parser.error("argument --coverage-compress: needs --coverage-format bigwig")
     if args.coverage and args.coverage_extend in (None, "auto"):
@@ -455,7 +465,7 @@ def _run(args, device, rank: int) -> int:
         if args.coverage_format is not None:
             extra["coverage_format"] = args.coverage_format
         if args.coverage_compress:
-            extra["coverage_compress"] = True
+            extra["coverage_compress"] = "device" if args.coverage_deflate == "device" else True
     if args.fragments:
         extra["fragments"] = True
     if args.fragments_max is not None:          # (it also bounds a pair pileup)

@@ -39,11 +39,12 @@ from typing import Dict, Iterator, Tuple
 import numpy as np
 
 from .complexity import _selected_mask
-from .native import PMX_BAM_DEFAULT_EXCLUDE, SideAccumulator, count_over
+from .native import PMX_BAM_DEFAULT_EXCLUDE, SideAccumulator, count_over, load_ingest_library, raise_last
 
 COVERAGE_SUFFIX = "_coverage.bedGraph"
 TILE = 4096                 # slots per scan tile of the device code (PMX_COVERAGE_TILE of include/pymasc_amd_ingest.h)
 TEXT_CHUNK = 1 << 18        # runs per call of pmx_dbam_coverage_text when a file is written
+DEFLATE_CHUNK = 1 << 20     # runs per call of pmx_dbam_coverage_sections_z: 1024 sections of 1024 runs, four workgroups on each of 256 CUs
 MAX_READS = 1 << 31
 TOTALS = ("reads", "runs", "covered_bases", "fragment_bases", "max_depth")
 PAIR = "pair"               # ``extend``: the FR pairs at their own extent
@@ -272,6 +273,30 @@ class DeviceCount(SideAccumulator):
         for first in range(int(ranges[k]), int(ranges[k + 1]), step):
             yield self.sections(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items)
 
+    def sections_z(self, reader, first: int, n: int, chrom_id: int, items: int):
+        """``sections`` with every section compressed on the device (``pmx_dbam_coverage_sections_z``): (the zlib
+        streams end to end, the table of ``sections`` -- column 4 stays the raw size --, the streams' lengths)."""
+        L, h = reader._L, reader._h
+        bound = L.pmx_dbam_coverage_sections_z(h, int(first), int(n), int(chrom_id), int(items), None, 0, None, 0, None)
+        if bound < 0:
+            reader._raise(bound)
+        rows = -(-int(n) // int(items))
+        buf = np.zeros(max(int(bound), 1), dtype=np.uint8)
+        table, zsizes = np.zeros((max(rows, 1), 5), dtype=np.uint32), np.zeros(max(rows, 1), dtype=np.uint32)
+        got = L.pmx_dbam_coverage_sections_z(h, int(first), int(n), int(chrom_id), int(items), buf.ctypes.data, int(bound),
+                                             table.ctypes.data, len(table), zsizes.ctypes.data)
+        if got < 0:
+            reader._raise(got)
+        assert got <= bound and got == int(zsizes[:rows].sum(dtype=np.int64))
+        return buf[:int(got)].tobytes(), table[:rows], zsizes[:rows]
+
+    def section_chunks_z(self, reader, k: int, chrom_id: int, items: int, chunk: int = DEFLATE_CHUNK):
+        """``sections_z`` of the ``k``-th chosen reference, about ``chunk`` runs at a time (whole sections)."""
+        ranges = self.ranges(reader)
+        step = max(int(chunk) // int(items), 1) * int(items)
+        for first in range(int(ranges[k]), int(ranges[k + 1]), step):
+            yield self.sections_z(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items)
+
     def zoom_begin(self, reader, z0: int, levels: int, ids) -> Tuple[int, int]:
         """Fills the zoom bins on the device (``pmx_dbam_coverage_zoom_begin``); ``ids[k]``: the chromosome id of the ``k``-th
         chosen reference.  Returns (the sum of depth^2 over the covered bases, the smallest depth)."""
@@ -298,6 +323,24 @@ class DeviceCount(SideAccumulator):
             reader._raise(got)
         assert got == size
         return buf[:int(size)].tobytes(), table[:rows]
+
+    def zoom_records_z(self, reader, level: int, items: int):
+        """``zoom_records`` with every section compressed on the device (``pmx_dbam_coverage_zoom_records_z``): (streams, table,
+        the streams' lengths).  The last level frees the bins."""
+        L, h = reader._L, reader._h
+        size = L.pmx_dbam_coverage_zoom_records(h, int(level), int(items), None, 0, None, 0)       # (the raw bytes: the rows)
+        bound = L.pmx_dbam_coverage_zoom_records_z(h, int(level), int(items), None, 0, None, 0, None)
+        if size < 0 or bound < 0:
+            reader._raise(min(size, bound))
+        rows = -(-(int(size) // 32) // int(items))
+        buf = np.zeros(max(int(bound), 1), dtype=np.uint8)
+        table, zsizes = np.zeros((max(rows, 1), 5), dtype=np.uint32), np.zeros(max(rows, 1), dtype=np.uint32)
+        got = L.pmx_dbam_coverage_zoom_records_z(h, int(level), int(items), buf.ctypes.data, int(bound), table.ctypes.data, len(table),
+                                                 zsizes.ctypes.data)
+        if got < 0:
+            reader._raise(got)
+        assert got <= bound and got == int(zsizes[:rows].sum(dtype=np.int64))
+        return buf[:int(got)].tobytes(), table[:rows], zsizes[:rows]
 
     def result(self, reader) -> Coverage:
         totals = self.finish(reader)
@@ -415,7 +458,9 @@ def read_coverage(path) -> Tuple[str, Coverage]:
 #   most half the longest chosen length; no run gives no level.
 # * Total summary: validCount = covered_bases, the smallest and largest depth, sum = fragment_bases, and the sum of squares.
 # * With ``compress`` every section goes through zlib on the host (a pool of at most ``min(16, cpus)`` threads) and
-#   ``uncompressBufSize`` is the largest raw section; otherwise it is 0.
+#   ``uncompressBufSize`` is the largest raw section; otherwise it is 0.  With ``compress="device"`` the sections
+#   are compressed by the GPU's own DEFLATE encoder before they leave it: the source hands zlib streams and their lengths, and the
+#   file differs from zlib's in its compressed bytes only.
 #
 # Sections, their tables and the zoom records come from a ``DeviceCount`` on its reader's handle (the GPU) or from ``HostParts``
 # (numpy); everything else is the code below, so the two files are the same byte for byte when nothing is compressed.
@@ -431,8 +476,23 @@ ZOOM_RECORD = np.dtype([("id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("valid
                         ("sumsq", "<f4")])
 
 
+DEVICE = "device"           # ``compress``: the sections are compressed on the GPU
+DEVICE_ITEMS = 2048         # items per section at most with it: a zoom section of 32-byte records must fit a chunk of the encoder
+DEFLATE_MAX_CHUNK = 1 << 16     # PMX_DEFLATE_MAX_CHUNK of include/pymasc_amd_ingest.h
+
+
+def check_compress(compress):
+    """``coverage_compress`` as the run takes it: False, True (zlib on the host) or ``"device"``."""
+    if compress == DEVICE or compress is True or compress is False:
+        return compress
+    if isinstance(compress, str):
+        raise ValueError("coverage_compress is False, True or \"device\"")
+    return bool(compress)
+
+
 def check_format(fmt, compress=False) -> str:
-    """``coverage_format`` as the run takes it; ``compress`` only with ``"bigwig"``."""
+    """``coverage_format`` as the run takes it; ``compress`` (``check_compress``) only with ``"bigwig"``."""
+    compress = check_compress(compress)
     if fmt not in FORMATS:
         raise ValueError("coverage_format is \"bedgraph\" or \"bigwig\"")
     if compress and fmt != "bigwig":
@@ -568,6 +628,12 @@ class _DeviceParts:
     def zoom_records(self, level, items):
         return self.acc.zoom_records(self.reader, level, items)
 
+    def section_chunks_z(self, k, chrom_id, items):
+        return self.acc.section_chunks_z(self.reader, k, chrom_id, items)
+
+    def zoom_records_z(self, level, items):
+        return self.acc.zoom_records_z(self.reader, level, items)
+
 
 def _chrom_tree(names, ids, lengths, at: int) -> bytes:
     """The chromosome B+ tree, which begins at ``at``: ``names`` (bytes, ascending) with their ids and lengths, ``CHROM_BLOCK`` keys
@@ -630,11 +696,12 @@ def _rtree(table: np.ndarray, offsets: np.ndarray, sizes: np.ndarray, block: int
 
 
 class _SectionWriter:
-    """Writes sections at the file's end and remembers where: raw, or each through zlib in a pool of threads."""
+    """Writes sections at the file's end and remembers where: raw, each through zlib in a pool of threads, or (``"device"``) as the
+    zlib streams the source made of them."""
 
-    def __init__(self, fp, compress: bool):
+    def __init__(self, fp, compress):
         self.fp, self.largest, self.pool = fp, 0, None
-        if compress:
+        if compress is True:
             from multiprocessing.pool import ThreadPool
             self.pool = ThreadPool(max(min(16, os.cpu_count() or 1), 1))
 
@@ -642,6 +709,15 @@ class _SectionWriter:
         if self.pool is not None:
             self.pool.close()
             self.pool.join()
+
+    def write_streams(self, blob: bytes, table: np.ndarray, zsizes: np.ndarray):
+        """The sections as the streams of ``blob``, ``zsizes`` bytes each, written as they are; ``table[:, 4]``: their raw sizes."""
+        sizes = np.asarray(zsizes).astype(np.int64)
+        assert len(sizes) == len(table) and int(sizes.sum()) == len(blob)
+        self.largest = max(self.largest, int(table[:, 4].max()) if len(table) else 0)
+        at = self.fp.tell()
+        self.fp.write(blob)
+        return at + np.cumsum(sizes) - sizes, sizes
 
     def write(self, blob: bytes, table: np.ndarray):
         """The sections of ``blob`` (``table[:, 4]``: their raw sizes); returns their (offsets, sizes) in the file."""
@@ -660,12 +736,20 @@ class _SectionWriter:
         return at + np.cumsum(sizes) - sizes, sizes
 
 
-def assemble_bigwig(fp, src, compress: bool = False, items_per_section: int = 1024, index_block: int = 256, zoom_base=None) -> None:
+def assemble_bigwig(fp, src, compress=False, items_per_section: int = 1024, index_block: int = 256, zoom_base=None) -> None:
     """Writes the bigWig file of the source ``src`` (``HostParts``, or a ``DeviceCount`` with its reader) into the seekable binary
-    file ``fp``, from its beginning."""
+    file ``fp``, from its beginning.  ``compress``: False, True (every section through zlib on the host) or ``"device"`` (the source
+    compresses them: it has ``section_chunks_z`` and ``zoom_records_z``, which hand ``(streams, table, lengths)``)."""
     items, block = int(items_per_section), int(index_block)
+    compress = check_compress(compress)
     if not 1 <= items <= 65535 or not 2 <= block <= 65535:
         raise ValueError("items_per_section lies in [1, 65535] and index_block in [2, 65535]")
+    device = compress == DEVICE
+    if device and items > DEVICE_ITEMS:
+        raise ValueError("compress=\"device\" takes at most {} items per section".format(DEVICE_ITEMS))
+    if device and not (hasattr(src, "section_chunks_z") and hasattr(src, "zoom_records_z")):
+        raise ValueError("compress=\"device\" needs a pileup counted by a device reader: this source has no section_chunks_z "
+                         "(a host reader or device_ingest=False; use compress=True for zlib on the host)")
     refs, tot = src.refs, src.totals
     if not refs:
         raise ValueError("no chosen reference")
@@ -695,12 +779,13 @@ def assemble_bigwig(fp, src, compress: bool = False, items_per_section: int = 10
         fp.write(bytes(8))
         tables, offsets, sizes, n_runs = [], [], [], 0
         for rank, k in enumerate(order):
-            for blob, table in src.section_chunks(k, rank, items):
-                o, s = writer.write(blob, table)
+            for part in (src.section_chunks_z if device else src.section_chunks)(k, rank, items):
+                table = part[1]
+                o, s = writer.write_streams(*part) if device else writer.write(*part)
                 tables.append(table)
                 offsets.append(o)
                 sizes.append(s)
-                n_runs += (len(blob) - 24 * len(table)) // 12
+                n_runs += (int(table[:, 4].sum(dtype=np.int64)) - 24 * len(table)) // 12
         if n_runs != tot["runs"]:
             raise RuntimeError("the sections hold {} runs, the pileup {}".format(n_runs, tot["runs"]))
         table = np.concatenate(tables) if tables else np.zeros((0, 5), dtype=np.uint32)
@@ -709,10 +794,11 @@ def assemble_bigwig(fp, src, compress: bool = False, items_per_section: int = 10
                         block, items, index_at, index_at))
         zooms = []
         for level in range(levels):
-            blob, table = src.zoom_records(level, items)
+            part = (src.zoom_records_z if device else src.zoom_records)(level, items)
+            table = part[1]
             at = fp.tell()
-            fp.write(struct.pack("<I", len(blob) // 32))
-            o, s = writer.write(blob, table)
+            fp.write(struct.pack("<I", int(table[:, 4].sum(dtype=np.int64)) // 32))
+            o, s = writer.write_streams(*part) if device else writer.write(*part)
             zindex_at = fp.tell()
             fp.write(_rtree(table, o, s, block, items, zindex_at, zindex_at))
             zooms.append((z0 * 4 ** level, at, zindex_at))
@@ -729,17 +815,41 @@ def assemble_bigwig(fp, src, compress: bool = False, items_per_section: int = 10
         writer.close()
 
 
+def deflate_bound(n: int) -> int:
+    """The longest zlib stream the device encoder writes for ``n`` raw bytes (``pmx_ddeflate_bound``)."""
+    return int(load_ingest_library().pmx_ddeflate_bound(int(n)))
+
+
+def deflate_device(chunks, device: int = 0):
+    """Every chunk (bytes of at most ``DEFLATE_MAX_CHUNK``) as one zlib stream made by the GPU's DEFLATE encoder (``pmx_ddeflate``;
+    DESIGN.md 7.18.2): a list of bytes that ``zlib.decompress`` turns back into the chunks."""
+    L = load_ingest_library()
+    chunks = [bytes(c) for c in chunks]
+    offsets = np.zeros(len(chunks) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(c) for c in chunks], dtype=np.uint64)
+    src = np.frombuffer(b"".join(chunks) or b"\0", dtype=np.uint8)
+    cap = sum(int(L.pmx_ddeflate_bound(len(c))) for c in chunks)
+    dst, sizes = np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(max(len(chunks), 1), dtype=np.uint32)
+    got = L.pmx_ddeflate(int(device), src.ctypes.data, offsets.ctypes.data, len(chunks), dst.ctypes.data, cap, sizes.ctypes.data)
+    if got < 0:
+        raise_last(L, got)
+    ends = np.cumsum(sizes[:len(chunks)], dtype=np.int64)
+    assert (int(ends[-1]) if len(chunks) else 0) == got
+    return [dst[int(z - n):int(z)].tobytes() for z, n in zip(ends, sizes)]
+
+
 def bigwig_source(c, reader=None):
     """What ``assemble_bigwig`` reads: ``HostParts`` of a ``Coverage``, or a finished ``DeviceCount`` on ``reader``'s handle."""
     return HostParts(c) if reader is None else _DeviceParts(c, reader)
 
 
-def write_bigwig(path_base, name: str, c, reader=None, compress: bool = False, items_per_section: int = 1024, index_block: int = 256,
+def write_bigwig(path_base, name: str, c, reader=None, compress=False, items_per_section: int = 1024, index_block: int = 256,
                  zoom_base=None) -> Path:
     """Writes ``<path_base>_coverage.bw`` (to a temporary file beside it, renamed into place) and returns its path: the pileup of
     a ``Coverage`` that knows its chosen references (sections and zoom records made with numpy) or, with ``reader``, of a finished
     ``DeviceCount`` on that reader's handle (made on the GPU).  A bigWig file has no place for ``name``, the reads or the extent.
-    A depth is exact as float32 up to 2^24 and rounded to nearest above."""
+    A depth is exact as float32 up to 2^24 and rounded to nearest above.  ``compress``: as for ``assemble_bigwig``; ``"device"`` needs
+    ``reader``."""
     path = Path(str(path_base) + BIGWIG_SUFFIX)
     tmp = "{}.tmp.{}".format(path, os.getpid())
     try:

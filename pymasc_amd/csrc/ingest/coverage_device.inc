@@ -818,6 +818,11 @@ __global__ void __launch_bounds__(256) k_cv_zoom_emit(u8 *__restrict__ bins, u64
 
 namespace {
 
+// deflate_device.inc: the upper bound of nsec sections (`full` raw bytes each, the last one `last`) as zlib streams, and the streams
+u64 df_sections_bound(u64 nsec, u64 full, u64 last);
+int64_t df_sections_out(pmx_dbam *b, CvHold &held, const std::string &fn, const u8 *d_raw, u64 nsec, u64 full, u64 last, uint8_t *buf,
+                        int64_t cap, uint32_t *zsizes);
+
 void zoom_drop(Coverage &c)
 {
     c.zbins = DevAlloc{};
@@ -868,12 +873,15 @@ int64_t coverage_ranges_impl(pmx_dbam *b, int64_t *first, int64_t cap)
     return n;
 }
 
+// z: every section as a zlib stream (pmx_dbam_coverage_sections_z), the streams' lengths in zsizes
 int64_t coverage_sections_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
-                               uint32_t *table, int64_t table_cap)
+                               uint32_t *table, int64_t table_cap, bool z = false, uint32_t *zsizes = nullptr)
 {
-    const char *fn = "pmx_dbam_coverage_sections";
+    const char *fn = z ? "pmx_dbam_coverage_sections_z" : "pmx_dbam_coverage_sections";
     if (int rc = coverage_range(b, fn, first, n)) return rc;
     if (items < 1 || items > 65535) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": 1 to 65535 items per section");
+    if (z && 24ull + 12ull * items > PMX_DEFLATE_MAX_CHUNK)
+        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at most 5459 items per section (a chunk of the encoder holds 65536 bytes)");
     if (buf && (cap < 0 || table_cap < 0)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": a negative capacity");
     if (n == 0) return 0;
     if (int rc = coverage_ranges_make(b)) return rc;
@@ -881,10 +889,13 @@ int64_t coverage_sections_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t c
     const auto it = std::upper_bound(c.ranges.begin(), c.ranges.end(), (u64)first);       // (the first reference that begins behind `first`)
     if (it == c.ranges.end() || (u64)first + (u64)n > *it) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the range holds two references");
     const u64 m = (u64)n, nsec = (m + items - 1) / items, bytes = 24 * nsec + 12 * m;
-    if (!buf) return (int64_t)bytes;
-    if ((u64)cap < bytes) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
+    const u64 full = 24 + 12ull * items, last = bytes - (nsec - 1) * full;
+    if (!buf) return (int64_t)(z ? df_sections_bound(nsec, full, last) : bytes);
+    if (!z && (u64)cap < bytes)
+        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
     if (!table || (u64)table_cap < nsec)
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the table is too small: " + std::to_string(nsec) + " rows are needed");
+    if (z && !zsizes) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": null output");
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
     DevAlloc d_out;
@@ -899,10 +910,10 @@ int64_t coverage_sections_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t c
     hipLaunchKernelGGL(k_cv_sections, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
                        chrom_id, d_out.as<u32>(), d_table);
     HIPOK(hipGetLastError());
-    HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
+    if (!z) HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
     HIPOK(hipMemcpyAsync(table, d_table, 20 * nsec, hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
-    return (int64_t)bytes;
+    return z ? df_sections_out(b, held, fn, d_out.as<u8>(), nsec, full, last, buf, cap, zsizes) : (int64_t)bytes;
 }
 
 int coverage_zoom_begin_impl(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t *out)
@@ -996,13 +1007,16 @@ int coverage_zoom_begin_impl(pmx_dbam *b, uint32_t z0, uint32_t levels, const ui
     return 0;
 }
 
-int64_t coverage_zoom_records_impl(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table, int64_t table_cap)
+int64_t coverage_zoom_records_impl(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table, int64_t table_cap,
+                                   bool zs = false, uint32_t *zsizes = nullptr)
 {
-    const char *fn = "pmx_dbam_coverage_zoom_records";
+    const char *fn = zs ? "pmx_dbam_coverage_zoom_records_z" : "pmx_dbam_coverage_zoom_records";
     if (int rc = coverage_range(b, fn, 0, 0)) return rc;
     Coverage &c = b->cv;
     if (level >= c.zlevels) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": no bins of that level: call pmx_dbam_coverage_zoom_begin first");
     if (items < 1) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at least 1 item per section");
+    if (zs && 32ull * items > PMX_DEFLATE_MAX_CHUNK)
+        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at most 2048 items per section (a chunk of the encoder holds 65536 bytes)");
     if (buf && (cap < 0 || table_cap < 0)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": a negative capacity");
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
@@ -1023,11 +1037,14 @@ int64_t coverage_zoom_records_impl(pmx_dbam *b, uint32_t level, uint32_t items, 
         HIPOK(hipMemcpyAsync(&total, d_tot.p, 8, hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
     }
-    const u64 bytes = 32 * total, nsec = (total + items - 1) / items;
-    if (!buf) return (int64_t)bytes;
-    if ((u64)cap < bytes) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
+    const u64 bytes = 32 * total, nsec = (total + items - 1) / items, full = 32ull * items, last = nsec ? bytes - (nsec - 1) * full : 0;
+    if (!buf) return (int64_t)(zs ? df_sections_bound(nsec, full, last) : bytes);
+    if (!zs && (u64)cap < bytes)
+        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
     if (!table || (u64)table_cap < nsec)
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the table is too small: " + std::to_string(nsec) + " rows are needed");
+    if (zs && !zsizes) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": null output");
+    int64_t written = (int64_t)bytes;
     if (total) {
         if (hipMalloc(&d_out.p, bytes + 20 * nsec) != hipSuccess) {
             (void)hipGetLastError();
@@ -1042,12 +1059,13 @@ int64_t coverage_zoom_records_impl(pmx_dbam *b, uint32_t level, uint32_t items, 
         hipLaunchKernelGGL(k_cv_zoom_emit, dim3((unsigned)nwg), dim3(256), 0, st, bins, nb, d_off, d_lens, (u32)nc, (u32)z, items, d_kb.as<u64>(),
                            d_tot.as<u64>(), d_out.as<u32>(), d_table);
         HIPOK(hipGetLastError());
-        HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
+        if (!zs) HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
         HIPOK(hipMemcpyAsync(table, d_table, 20 * nsec, hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
+        if (zs && (written = df_sections_out(b, held, fn, d_out.as<u8>(), nsec, full, last, buf, cap, zsizes)) < 0) return written;
     }
     if (level + 1 == c.zlevels) zoom_drop(c);       // the last level is out: the bins are freed
-    return (int64_t)bytes;
+    return written;
 }
 
 }  // namespace

@@ -139,6 +139,10 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_coverage_sections": (_i64, [_vp, _i64, _i64, _u32, _u32, _vp, _i64, _vp, _i64]),
     "pmx_dbam_coverage_zoom_begin": (_int, [_vp, _u32, _u32, _vp, _vp]),
     "pmx_dbam_coverage_zoom_records": (_i64, [_vp, _u32, _u32, _vp, _i64, _vp, _i64]),
+    "pmx_ddeflate_bound": (_u64, [_u64]),
+    "pmx_ddeflate": (_i64, [_int, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "pmx_dbam_coverage_sections_z": (_i64, [_vp, _i64, _i64, _u32, _u32, _vp, _i64, _vp, _i64, _vp]),
+    "pmx_dbam_coverage_zoom_records_z": (_i64, [_vp, _u32, _u32, _vp, _i64, _vp, _i64, _vp]),
     "pmx_dbam_gcbias_begin": (_int, [_vp, _vp, _u32, _vp]),
     "pmx_dbam_gcbias_add": (_int, [_vp, _u32, _u32, _vp]),
     "pmx_dbam_gcbias_tables": (_i64, [_vp, _vp, _vp, _i64, _vp]),

@@ -41,7 +41,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None,
         peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto", gc_bias=None, gc_window: int = 100,
         fragments: bool = False, fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
-        coverage_format: str = "bedgraph", coverage_compress: bool = False):
+        coverage_format: str = "bedgraph", coverage_compress=False):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -93,7 +93,9 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     device table is 4 bytes per chosen base (12.4 GB for hg38).  ``coverage_format="bigwig"`` writes ``<stem>_coverage.bw`` instead
     (DESIGN.md 7.18.1): the same runs as a bigWig file with zoom levels, its sections and zoom records made on the GPU with device
     ingest; a depth is a float32 there, exact up to 2^24 and rounded to nearest above.  ``coverage_compress``: every section of
-    that file through zlib on the host; with ``"bedgraph"`` it is a ValueError.
+    that file through zlib on the host (True), or (``"device"``) through the GPU's own DEFLATE encoder before it
+    leaves the device, which needs device ingest (a host reader is a ValueError, not zlib); the decoded file is the same, the
+    compressed bytes are not zlib's.  With ``"bedgraph"`` either is a ValueError.
     ``gc_bias``: a genome FASTA (plain, gzip or bgzip): rank 0 also writes ``<stem>_gcbias.tab`` (pymasc_amd.gcbias, DESIGN.md
     7.19): the reads the fingerprint counts, each placed on the genome window of ``gc_window`` bases (1 .. 1024) that begins at
     its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
@@ -177,7 +179,7 @@ class _Settings:
     coverage: bool
     coverage_extend: object         # an int (0: every read's own length), or "auto": the run's fragment-length estimate
     coverage_format: str            # "bedgraph" or "bigwig"
-    coverage_compress: bool         # the sections of a bigWig file through zlib
+    coverage_compress: object       # the sections of a bigWig file through zlib: False, True (on the host) or "device" (on the GPU)
     gc_bias: object                 # None, or the _GcGenome parsed once for the call
     gc_window: int
     fragments: bool
@@ -232,7 +234,10 @@ def _settings(kw: dict) -> _Settings:
         raise ValueError("coverage_extend is \"auto\", \"pair\" or an integer of at least 0")
     given.update(coverage=bool(kw["coverage"]), coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend),
                  coverage_format=coverage.check_format(kw["coverage_format"], kw["coverage_compress"]),
-                 coverage_compress=bool(kw["coverage_compress"]))
+                 coverage_compress=coverage.check_compress(kw["coverage_compress"]))
+    if given["coverage"] and given["coverage_compress"] == coverage.DEVICE and not ingest:     # (no silent fall-back to zlib)
+        raise ValueError("coverage_compress=\"device\" needs device ingest (device_ingest=False reads on the host); "
+                         "use coverage_compress=True for zlib on the host")
     given.update(fragments=bool(kw["fragments"]), fragments_max=fragments.check_max_size(kw["fragments_max"]))
     if kw["tss"] is None and (int(kw["tss_flank"]) != tss.DEFAULT_FLANK or int(kw["tss_extend"])):
         raise ValueError("tss_flank and tss_extend need tss")
@@ -496,6 +501,9 @@ class _CoverageCount(_SideCount):
         if spool:
             extend = self.s.coverage_extend     # (an integer or "pair")
         if not isinstance(reader, DeviceBamReader):
+            if bigwig and self.s.coverage_compress == coverage.DEVICE:      # (no silent fall-back to zlib)
+                raise ValueError("coverage_compress=\"device\" needs a device reader: this input is read on the host "
+                                 "(device_ingest=False or a host reader); use coverage_compress=True for zlib on the host")
             c = coverage.from_reader(reader, mapq, names, extend, self.s.fragments_max)
             return self._bigwig(coverage.bigwig_source(c), False) if bigwig else (extend, c.reads, c.text_chunks())
         if acc is None:             # (an armed count is not built again: its ``begin`` would zero the table)
@@ -709,7 +717,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0, coverage: bool = False,
               coverage_extend="auto", gc_bias=None, gc_window: int = 100, fragments: bool = False,
               fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
-              coverage_format: str = "bedgraph", coverage_compress: bool = False) -> List[FileResult]:
+              coverage_format: str = "bedgraph", coverage_compress=False) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 

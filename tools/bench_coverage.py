@@ -6,9 +6,10 @@ The times are wall-clock around the library calls (allocations, the zeroing of t
 after one warm-up round, split per call.  --reps 1 --no-open --no-host is the run to put under `rocprofv3 --kernel-trace --stats`
 for the split of the kernels; the trace is a run of its own.
 
---format bigwig [--compress] also writes the bigWig file of the same runs in every round, behind the text pull, and
-splits its time into the section pulls, zoom begin (the fill and the folds), the record pulls and the rest, which is the host's
-assembly (R-trees, the file writes and, with --compress, zlib); profiles/coverage_bigwig.json is
+--format bigwig [--compress [host|device]] also writes the bigWig file of the same runs in every round, behind the
+text pull, and splits its time into the section pulls, zoom begin (the fill and the folds), the record pulls and the rest, which is
+the host's assembly (R-trees, the file writes and, with --compress host, zlib); with --compress device the pulls
+are the compressed ones, pmx_dbam_coverage_sections_z / _zoom_records_z.  profiles/coverage_bigwig.json is
 python tools/bench_coverage.py --reads 20000000 --format bigwig --no-host --out profiles/coverage_bigwig.json"""
 import argparse
 import json
@@ -31,17 +32,19 @@ class _Timed:
     def __init__(self, src):
         self.src, self.refs, self.totals = src, src.refs, src.totals
         self.t = dict(sections=0.0, zoom_begin=0.0, zoom_records=0.0)
-        self.pulled = dict(sections=0, zoom_records=0)
+        self.pulled = dict(sections=0, zoom_records=0)      # bytes copied from the device
+        self.raw = dict(sections=0, zoom_records=0)         # raw bytes of the sections they hold
 
-    def section_chunks(self, k, chrom_id, items):
-        it = iter(self.src.section_chunks(k, chrom_id, items))
+    def section_chunks(self, k, chrom_id, items, z=False):
+        it = iter((self.src.section_chunks_z if z else self.src.section_chunks)(k, chrom_id, items))
         while True:
             t0 = time.perf_counter()
             got = next(it, None)
             self.t["sections"] += time.perf_counter() - t0
             if got is None:
                 return
-            self.pulled["sections"] += len(got[0]) + got[1].nbytes
+            self.pulled["sections"] += len(got[0]) + sum(x.nbytes for x in got[1:])
+            self.raw["sections"] += int(got[1][:, 4].sum(dtype="int64"))
             yield got
 
     def zoom_begin(self, z0, levels, ids):
@@ -51,12 +54,19 @@ class _Timed:
         self.z0, self.levels = z0, levels
         return out
 
-    def zoom_records(self, level, items):
+    def zoom_records(self, level, items, z=False):
         t0 = time.perf_counter()
-        out = self.src.zoom_records(level, items)
+        out = (self.src.zoom_records_z if z else self.src.zoom_records)(level, items)
         self.t["zoom_records"] += time.perf_counter() - t0
-        self.pulled["zoom_records"] += len(out[0]) + out[1].nbytes
+        self.pulled["zoom_records"] += len(out[0]) + sum(x.nbytes for x in out[1:])
+        self.raw["zoom_records"] += int(out[1][:, 4].sum(dtype="int64"))
         return out
+
+    def section_chunks_z(self, k, chrom_id, items):
+        return self.section_chunks(k, chrom_id, items, True)
+
+    def zoom_records_z(self, level, items):
+        return self.zoom_records(level, items, True)
 
 
 def main():
@@ -69,7 +79,8 @@ def main():
     ap.add_argument("--no-open", action="store_true", help="skip the timing of open + decode")
     ap.add_argument("--no-host", action="store_true", help="skip coverage.count_host on the same reads")
     ap.add_argument("--format", choices=coverage.FORMATS, default="bedgraph", help="bigwig: also time the bigWig file of the same runs")
-    ap.add_argument("--compress", action="store_true", help="the sections of the bigWig file through zlib")
+    ap.add_argument("--compress", nargs="?", const="host", default=None, choices=("host", "device"),
+                    help="the sections of the bigWig file compressed: host (the bare flag): zlib on the host; device: on the GPU")
     ap.add_argument("--bigwig-path", default="/tmp/pymasc_coverage_bench.bw")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -102,7 +113,7 @@ def main():
                 src = _Timed(coverage.bigwig_source(acc, r))
                 t0 = time.perf_counter()
                 with open(a.bigwig_path, "w+b") as fp:
-                    coverage.assemble_bigwig(fp, src, a.compress)
+                    coverage.assemble_bigwig(fp, src, {None: False, "host": True, "device": "device"}[a.compress])
                 whole = time.perf_counter() - t0
                 if rep:
                     for name in ("sections", "zoom_begin", "zoom_records"):
@@ -110,7 +121,8 @@ def main():
                     bw["assembly"].append(whole - sum(src.t.values()))
                     bw["whole"].append(whole)
                     res["bigwig"] = dict(bytes=os.path.getsize(a.bigwig_path), compress=a.compress, z0=src.z0, levels=src.levels,
-                                         section_bytes_pulled=src.pulled["sections"], record_bytes_pulled=src.pulled["zoom_records"])
+                                         section_bytes_pulled=src.pulled["sections"], record_bytes_pulled=src.pulled["zoom_records"],
+                                         section_bytes_raw=src.raw["sections"], record_bytes_raw=src.raw["zoom_records"])
             if rep:
                 for k, name in enumerate(("begin", "add", "finish", "text")):
                     split[name].append(t[k + 1] - t[k])
