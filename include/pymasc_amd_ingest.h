@@ -287,6 +287,48 @@ int pmx_dbam_coverage_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, cons
 int64_t pmx_dbam_coverage_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
                                        int64_t table_cap);
 
+/* The pileup as a signal track (version >= 19): the mean depth per bin of B bases times a scale factor, float32,
+ * equal neighbours merged; made of the runs finish left, so every call here is legal only between finish and the next begin
+ * (PMX_DBAM_ERR_INVALID otherwise), and all but `signal` only after a `signal`.
+ * The definitions.  Reference r of length len has the bins j = 0 .. ceil(len / B) - 1; bin j covers [j * B, min((j + 1) * B, len)) and
+ * has the width w_j (only the last bin can be short); S_j is the integer sum of the depth over its bases (below 2^47: exact as u64
+ * and as float64); B is 1 .. 65536.  v_j = f32((f64(S_j) * scale) / f64(w_j)): one float64 multiply, one float64 divide, one
+ * conversion to float32, each rounded to nearest even.  Consecutive bins of one reference are one run when they have the same S and
+ * the same width (the rule is on S, not on v: two S that round to one float32 stay two runs); bins with S = 0 are in no run; a run
+ * is (ref, start0, end0, v), in header order.  With B = 1 the signal runs are the depth runs with v = f32(f64(depth) * scale).
+ * signal: makes the signal runs, kept on the handle beside the depth runs (16 bytes each) and replaced by the next signal, begin or
+ * close; totals = runs, covered bases (the runs' widths summed), the smallest and the largest v (0 without a run).  scale must be
+ * finite and at least 2^-64 (no value is a float32 denormal) with scale * max_depth < 2^40 (v * 10^6 < 2^63), bin 1 .. 65536:
+ * PMX_DBAM_ERR_INVALID otherwise.  For B > 1 a dense u64 table, 8 bytes per bin of every chosen reference, is held inside the call
+ * and counted towards pmx_dbam_stream_info's peak; out of device memory: PMX_DBAM_ERR_OPEN with the bytes asked for.  A failure
+ * leaves no signal.
+ * signal_runs / _text / _ranges / _sections / _zoom_begin / _zoom_records / _sections_z / _zoom_records_z: their depth twins over the
+ * signal runs, with the same rules for a NULL buffer, a short cap and out of memory.  What differs:
+ * - runs: the fourth column is the float32 v.
+ * - text: the value is the decimal expansion of the exact value of v rounded to six decimals, ties to even, without trailing zeros
+ *   and without a trailing '.' ("0.0000004" is "0"); made in integers.  With scale 1 and B = 1 the lines equal pmx_dbam_coverage_text's.
+ * - sections: the third word of an item is v; sums[section][2] = the section's runs in order, acc += f64(ov) * f64(v) and
+ *   acc += f64(ov) * (f64(v) * f64(v)) from 0.0, ov = end0 - start0 (what the total summary adds up, in file order, on the host).
+ * - zoom_begin: a bin of level 0 takes the signal runs that overlap it in ascending start order, each by ov bases: validCount =
+ *   sum ov, min and max over v, and the two sums above as float64; a bin of level k + 1 adds its up to four bins of level k in
+ *   index order the same way.  Every multiply and add is rounded on its own (no fused multiply-add), so the records do not depend
+ *   on scheduling.  out[0] = out[1] = 0: the signal's summary needs nothing from here.  The bins replace the depth's, and the
+ *   depth's zoom_begin replaces these; zoom_records of the other kind: PMX_DBAM_ERR_INVALID.
+ * - zoom_records: min and max as they are, the two sums rounded to float32. */
+int pmx_dbam_coverage_signal(pmx_dbam *b, uint32_t bin, double scale, double totals[4]);
+int pmx_dbam_coverage_signal_runs(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, float *value);
+int64_t pmx_dbam_coverage_signal_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap);
+int64_t pmx_dbam_coverage_signal_ranges(pmx_dbam *b, int64_t *first, int64_t cap);
+int64_t pmx_dbam_coverage_signal_sections(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
+                                          uint32_t *table, int64_t table_cap, double *sums);
+int pmx_dbam_coverage_signal_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t out[2]);
+int64_t pmx_dbam_coverage_signal_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
+                                              int64_t table_cap);
+int64_t pmx_dbam_coverage_signal_sections_z(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
+                                            uint32_t *table, int64_t table_cap, uint32_t *zsizes, double *sums);
+int64_t pmx_dbam_coverage_signal_zoom_records_z(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
+                                                int64_t table_cap, uint32_t *zsizes);
+
 /* A DEFLATE encoder on the device (version >= 18): independent chunks of at most PMX_DEFLATE_MAX_CHUNK bytes, each
  * turned into one complete zlib stream (RFC 1950 around RFC 1951): the header 0x78 with a 32-KB window and no dictionary, DEFLATE
  * blocks of which the last is marked final, the big-endian Adler-32 of the raw bytes.  Matches have length 4 .. 258 and distance

@@ -245,7 +245,7 @@ def get_parser() -> argparse.ArgumentParser:
     out.add_argument("--coverage", action="store_true",
                      help="also write <name>_coverage.bedGraph for every file: the reads the correlation sees, each extended from "
                           "its 5' end to the estimated fragment length, piled up base by base on the GPU and written as runs of "
-                          "constant depth (plain text; no binning, no scaling).  The GPU table takes 4 bytes per base of the chosen "
+                          "constant depth (plain text; binning and scaling: --coverage-bin, --coverage-normalize).  The GPU table takes 4 bytes per base of the chosen "
                           "chromosomes: 12.4 GB for hg38")
     out.add_argument("--coverage-extend", metavar="N|auto|read|pair", type=_extend, action=_Extend,
                      help="extend every read to N bases from its 5' end; auto (the default): to the run's own fragment-length "
@@ -265,6 +265,17 @@ def get_parser() -> argparse.ArgumentParser:
                           "GPU's own DEFLATE encoder, before the sections leave it, for inputs read by device ingest.  A section "
                           "holds 1024 items here; the device encoder takes at most 2048 items per section.  Its compressed bytes "
                           "differ from zlib's; the decoded file does not")
+    out.add_argument("--coverage-bin", metavar="N", type=int, action=_NaturalNumber,
+                     help="write the pileup as a signal track: the mean depth per bin of N bases (1 to 65536; default 1), a 32-bit "
+                          "float, equal neighbouring bins merged into one run, made on the GPU; implies --coverage")
+    out.add_argument("--coverage-normalize", choices=("none", "cpm", "rpgc"),
+                     help="scale the signal track: cpm: by 10^6 / the reads piled up; rpgc: by the genome size / the bases piled up, so "
+                          "that the mean depth over the genome is 1 (the genome size: --coverage-genome-size, else the chosen "
+                          "chromosomes' lengths); none (the default); implies --coverage")
+    out.add_argument("--coverage-scale", metavar="X", type=float,
+                     help="multiply the signal track by X (above 0; default 1) on top of --coverage-normalize; implies --coverage")
+    out.add_argument("--coverage-genome-size", metavar="N", type=int, action=_NaturalNumber,
+                     help="the genome size of --coverage-normalize rpgc, which it needs; implies --coverage")
     out.add_argument("--gc-bias", metavar="FASTA", type=Path,
                      help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
                           "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
@@ -334,7 +345,14 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("argument --peaks-extend: needs a peak file (--peaks)")
     if args.peaks is not None and not os.path.isfile(args.peaks):
         parser.error("argument --peaks: no such file: '{}'".format(args.peaks))
-    if args.coverage_extend is not None or args.coverage_format is not None:
+    if args.coverage_bin is not None and args.coverage_bin > 65536:
+        parser.error("argument --coverage-bin: the bin is {}: it must lie in [1, 65536]".format(args.coverage_bin))
+    if args.coverage_scale is not None and not 0.0 < args.coverage_scale < float("inf"):
+        parser.error("argument --coverage-scale: must be a finite number above 0")
+    if args.coverage_genome_size is not None and args.coverage_normalize != "rpgc":
+        parser.error("argument --coverage-genome-size: needs --coverage-normalize rpgc")
+    signal = (args.coverage_bin, args.coverage_normalize, args.coverage_scale, args.coverage_genome_size)
+    if args.coverage_extend is not None or args.coverage_format is not None or any(x is not None for x in signal):
         args.coverage = True
     if args.coverage_deflate is not None:
         if args.coverage_format != "bigwig":
@@ -466,6 +484,9 @@ def _run(args, device, rank: int) -> int:
             extra["coverage_format"] = args.coverage_format
         if args.coverage_compress:
             extra["coverage_compress"] = "device" if args.coverage_deflate == "device" else True
+        for key in ("coverage_bin", "coverage_normalize", "coverage_scale", "coverage_genome_size"):
+            if getattr(args, key) is not None:
+                extra[key] = getattr(args, key)
     if args.fragments:
         extra["fragments"] = True
     if args.fragments_max is not None:          # (it also bounds a pair pileup)

@@ -25,6 +25,35 @@ goes through its ``batches`` and ``HostCount`` (plain numpy), which is also the 
 
 The same runs as a bigWig file, ``<name>_coverage.bw`` (``write_bigwig``, ``read_bigwig``): see the second half of
 this module.
+
+The pileup as a signal track (``--coverage-bin`` / ``--coverage-normalize``; ``Signal``, ``Coverage.signal``,
+``DeviceCount.signal``): the mean depth per bin of ``B`` bases times a scale factor, float32, equal neighbours merged.
+
+* Reference ``r`` of length ``len`` has the bins ``j = 0 .. ceil(len / B) - 1``; bin ``j`` covers ``[j * B, min((j + 1) * B, len))``
+  and has the width ``w_j`` (only the last bin can be short); ``S_j`` is the integer sum of the depth over its bases (below 2^47:
+  exact as a u64 and as a float64); ``B`` is an integer from 1 to 65536.
+* ``v_j = f32((f64(S_j) * scale) / f64(w_j))``: one float64 multiply, one float64 divide, one conversion to float32, each rounded
+  to nearest even: ``np.float32((float(S) * scale) / float(w))``.
+* ``scale`` is a finite float64 of at least 2^-64 (no value is a float32 denormal) with ``scale * max_depth < 2^40`` (so
+  ``v * 10^6 < 2^63`` and the device's text is integer arithmetic); anything else is a ``ValueError`` (``check_scale``).
+* Consecutive bins of one reference are one run when they have the same ``S`` and the same width -- the rule is on ``S``, not on
+  ``v``: two different ``S`` that round to one float32 stay two runs --; bins with ``S = 0`` are in no run.  A run is ``(ref,
+  start0, end0, v)``, in header order.  With ``B = 1`` the signal runs are the depth runs with ``v = f32(f64(depth) * scale)``.
+  Totals: ``runs``, ``covered_bases`` (the runs' widths summed), the smallest and the largest ``v``.
+* Normalisation (``scale_of``, float64): ``none``: 1.0; ``cpm``: ``1e6 / reads``; ``rpgc``: ``genome_size / fragment_bases``
+  (``genome_size``: ``coverage_genome_size``, else the sum of the chosen references' lengths); times ``coverage_scale``, one
+  multiplication.  With no kept read the factor is 1.0 and the track is empty.
+* bedGraph text: ``value`` is the decimal expansion of the exact value of ``v`` rounded to six decimals, ties to even, without
+  trailing zeros and without a trailing ``.`` (``format_value``: ``'%.6f' % float(v)``, stripped); with scale 1 and ``B = 1`` the
+  lines equal the depth track's.  The track line is the depth track's followed by `` bin=<B> normalize=<word> scale=<repr>``.
+* bigWig: the layout of 7.18.1 with ``v`` as an item's third word.  ``z_0`` is ``zoom_base`` (a multiple of ``B``), else ``B * p``
+  with ``p`` the smallest power of two with ``B * p >= max(32, 10 * covered_bases / runs)`` (the signal's counts).  A zoom bin of
+  level 0 takes the signal runs that overlap it in ascending start order, each by ``ov`` bases: ``validCount = sum ov``, min and max
+  over ``v``, ``sum``: ``acc += f64(ov) * f64(v)``, ``sumSquares``: ``acc += f64(ov) * (f64(v) * f64(v))``, both float64 from 0.0,
+  every multiply and add rounded on its own (no fused multiply-add).  A bin of level ``k + 1`` adds its up to four bins of level
+  ``k`` in index order the same way.  The records hold the four floats as float32, rounded to nearest.  Total summary:
+  ``validCount = covered_bases``, min, max, then ``sum`` and ``sumSquares`` as float64: per data section its runs in order with the
+  two products above from 0.0, the sections' partial sums then added in file order on the host from 0.0.
 """
 from __future__ import annotations
 
@@ -48,6 +77,10 @@ DEFLATE_CHUNK = 1 << 20     # runs per call of pmx_dbam_coverage_sections_z: 102
 MAX_READS = 1 << 31
 TOTALS = ("reads", "runs", "covered_bases", "fragment_bases", "max_depth")
 PAIR = "pair"               # ``extend``: the FR pairs at their own extent
+NORMALIZE = ("none", "cpm", "rpgc")
+MAX_BIN = 1 << 16           # the widest bin of a signal track
+MIN_SCALE, MAX_VALUE = 2.0 ** -64, 2.0 ** 40       # scale >= MIN_SCALE and scale * max_depth < MAX_VALUE
+SIGNAL_TOTALS = ("runs", "covered_bases", "min", "max")
 _TRACK = re.compile(r'^track type=bedGraph name="(.*)" description="pymasc_amd fragment pileup extend=(\d+|read|pair) reads=(\d+)"$')
 
 
@@ -58,6 +91,127 @@ def check_extend(extend):
     if isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0:
         raise ValueError("extend is \"pair\" or an integer that is not negative")
     return int(extend)
+
+
+def check_bin(b) -> int:
+    """``coverage_bin`` as the signal takes it: an integer from 1 to 65536."""
+    try:
+        ok = not isinstance(b, (str, bool)) and int(b) == b and 1 <= int(b) <= MAX_BIN
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("coverage_bin is an integer from 1 to 65536")
+    return int(b)
+
+
+def check_scale(scale, max_depth: int = 0) -> float:
+    """The signal's scale factor: a finite float64 of at least 2^-64 with ``scale * max_depth`` below 2^40 (the refusals of
+    ``pmx_dbam_coverage_signal``, made here for both paths)."""
+    if isinstance(scale, (str, bool)):
+        raise ValueError("the scale is a number")
+    scale = float(scale)
+    if not np.isfinite(scale) or scale < MIN_SCALE:
+        raise ValueError("the scale is a finite number of at least 2^-64 (below it a value could be a float32 denormal)")
+    if scale * float(int(max_depth)) >= MAX_VALUE:
+        raise ValueError("scale * max_depth is 2^40 or more (a value's text is made in 64-bit integers)")
+    return scale
+
+
+def check_factor(scale) -> float:
+    """``coverage_scale`` as the run takes it: a finite number above 0 (the final factor is checked by ``check_scale``)."""
+    if isinstance(scale, (str, bool)) or not np.isfinite(float(scale)) or float(scale) <= 0.0:
+        raise ValueError("coverage_scale is a finite number above 0")
+    return float(scale)
+
+
+def check_genome_size(size, normalize: str = "rpgc"):
+    """``coverage_genome_size``: None or a positive integer, and only with ``rpgc``."""
+    if size is None:
+        return None
+    if isinstance(size, (str, bool)) or int(size) != size or int(size) < 1:
+        raise ValueError("coverage_genome_size is a positive integer")
+    if normalize != "rpgc":
+        raise ValueError("coverage_genome_size needs coverage_normalize=\"rpgc\"")
+    return int(size)
+
+
+def check_normalize(normalize) -> str:
+    if normalize not in NORMALIZE:
+        raise ValueError("coverage_normalize is \"none\", \"cpm\" or \"rpgc\"")
+    return normalize
+
+
+def scale_of(normalize: str, reads: int, fragment_bases: int, lengths, coverage_scale: float = 1.0, genome_size=None) -> float:
+    """The final scale factor, float64: ``none``: 1.0; ``cpm``: ``1e6 / reads``; ``rpgc``: ``genome_size / fragment_bases``
+    (``genome_size`` None: the sum of the chosen references' ``lengths``); times ``coverage_scale``, one multiplication.  With no
+    kept read the normalisation is 1.0 (the track is empty)."""
+    check_normalize(normalize)
+    genome_size = check_genome_size(genome_size, normalize)
+    coverage_scale = check_factor(coverage_scale)
+    factor = 1.0
+    if normalize == "cpm" and int(reads):
+        factor = 1e6 / float(int(reads))
+    elif normalize == "rpgc" and int(fragment_bases):
+        factor = float(sum(int(l) for l in lengths) if genome_size is None else genome_size) / float(int(fragment_bases))
+    return factor * coverage_scale
+
+
+def format_value(v) -> str:
+    """A value as the bedGraph text holds it: the exact value of the float32 rounded to six decimals (ties to even), without
+    trailing zeros and without a trailing ``.``."""
+    return ("%.6f" % float(v)).rstrip("0").rstrip(".")
+
+
+def signal_tail(bin: int, normalize: str, scale: float) -> str:
+    """What a signal's track line has behind the depth track's."""
+    return " bin={} normalize={} scale={!r}".format(int(bin), normalize, float(scale))
+
+
+class Signal:
+    """A signal track: ``runs``: ``{name: (start0, end0, value)}`` (uint32, uint32, float32) of the chosen references that have a
+    run, in header order; ``bin``, ``scale``; ``refs`` as for ``Coverage``; ``reads``, ``extend`` and ``normalize`` (the word) are
+    what the track line says.  Two signals are equal when their runs are, bit for bit, with ``bin`` and ``scale``."""
+
+    def __init__(self, runs, bin: int, scale: float, refs=None, reads: int = 0, extend=0, normalize: str = "none"):
+        self.runs = {str(k): (np.asarray(v[0], dtype=np.uint32).ravel(), np.asarray(v[1], dtype=np.uint32).ravel(),
+                              np.asarray(v[2], dtype=np.float32).ravel()) for k, v in runs.items()}
+        self.bin, self.scale = check_bin(bin), float(scale)
+        self.refs = None if refs is None else [(str(n), int(l)) for n, l in refs]
+        self.reads, self.extend, self.normalize = int(reads), check_extend(extend), check_normalize(normalize)
+        if any(not (v[0].size == v[1].size == v[2].size > 0) for v in self.runs.values()):
+            raise ValueError("every reference has as many starts as ends and values, and at least one run")
+
+    n_runs = property(lambda self: sum(int(v[0].size) for v in self.runs.values()))
+    covered_bases = property(lambda self: sum(int((e.astype(np.int64) - s.astype(np.int64)).sum()) for s, e, _v in self.runs.values()))
+    min = property(lambda self: min((float(v.min()) for _s, _e, v in self.runs.values()), default=0.0))
+    max = property(lambda self: max((float(v.max()) for _s, _e, v in self.runs.values()), default=0.0))
+
+    @property
+    def totals(self):
+        """(runs, covered_bases, the smallest value, the largest value), the order of ``pmx_dbam_coverage_signal``."""
+        return self.n_runs, self.covered_bases, self.min, self.max
+
+    def rows(self):
+        """Every run as a plain tuple (name, start0, end0, value), in file order."""
+        return [(n, *r) for n, v in self.runs.items() for r in zip(*(x.tolist() for x in v))]
+
+    def text_chunks(self, chunk: int = 1 << 16) -> Iterator[bytes]:
+        """The bedGraph lines, ``chunk`` runs at a time."""
+        for name, (s, e, v) in self.runs.items():
+            for a in range(0, s.size, chunk):
+                yield "".join("{}\t{}\t{}\t{}\n".format(name, x, y, format_value(z))
+                               for x, y, z in zip(s[a:a + chunk].tolist(), e[a:a + chunk].tolist(), v[a:a + chunk])).encode()
+
+    tail = property(lambda self: signal_tail(self.bin, self.normalize, self.scale))
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, Signal) and (self.bin, self.scale) == (other.bin, other.scale) and list(self.runs) == list(other.runs)
+                and all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for k in self.runs for a, b in zip(self.runs[k], other.runs[k])))
+
+    __hash__ = None
+
+    def __repr__(self) -> str:
+        return "Signal(bin={}, scale={!r}, runs={}, covered_bases={}, min={!r}, max={!r})".format(self.bin, self.scale, *self.totals)
 
 
 class Coverage:
@@ -96,6 +250,40 @@ class Coverage:
                 cols = [x[a:a + chunk].astype("U10") for x in (s, e, d)]
                 lines = np.char.add(np.char.add(np.char.add(np.char.add(np.char.add(head, cols[0]), "\t"), cols[1]), "\t"), cols[2])
                 yield ("\n".join(lines.tolist()) + "\n").encode()
+
+    def signal(self, bin: int = 1, scale: float = 1.0, normalize: str = "none") -> Signal:
+        """The signal track of the pileup, in numpy: the runs are split at the bin edges and their ``overlap * depth`` added per
+        bin (``np.add.at``); a bin begins a run where ``S`` or the width differs from the bin before.  ``bin`` above 1 needs
+        ``refs`` (the last bin of a reference is clipped to its length).  ``normalize``: the word the track line says."""
+        bin, scale = check_bin(bin), check_scale(scale, self.max_depth)
+        if bin > 1 and self.refs is None:
+            raise ValueError("the pileup does not know its chosen references' lengths (it was read from a bedGraph file)")
+        lengths = dict(self.refs or [])
+        out = {}
+        for name, (s, e, d) in self.runs.items():
+            if bin == 1:
+                out[name] = (s, e, ((d.astype(np.float64) * scale) / 1.0).astype(np.float32))
+                continue
+            length = lengths[name]
+            s, e, d = (x.astype(np.int64) for x in (s, e, d))
+            j0, j1 = s // bin, (e - 1) // bin
+            n = j1 - j0 + 1                                 # the bins of every run
+            run = np.repeat(np.arange(s.size), n)
+            j = j0[run] + np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+            w = np.minimum(e[run], (j + 1) * bin) - np.maximum(s[run], j * bin)
+            total = np.zeros(-(-length // bin), dtype=np.int64)
+            np.add.at(total, j, w * d[run])
+            width = np.full(total.size, bin, dtype=np.int64)
+            width[-1] = length - (total.size - 1) * bin
+            begins = np.ones(total.size, dtype=bool)
+            begins[1:] = (total[1:] != total[:-1]) | (width[1:] != width[:-1])
+            at = np.flatnonzero(begins)
+            ends = np.append(at[1:] * bin, length)
+            keep = total[at] != 0
+            if keep.any():
+                at, ends = at[keep], ends[keep]
+                out[name] = (at * bin, ends, ((total[at].astype(np.float64) * scale) / width[at].astype(np.float64)).astype(np.float32))
+        return Signal(out, bin, scale, self.refs, self.reads, self.extend, normalize)
 
     def __eq__(self, other) -> bool:
         return (isinstance(other, Coverage) and (self.reads, self.extend) == (other.reads, other.extend)
@@ -183,10 +371,15 @@ class DeviceCount(SideAccumulator):
         self.totals = None
         self.begin(reader)
 
+    @staticmethod
+    def _fn(reader, what: str, signal: bool):
+        """The entry point ``what`` over the depth runs or, with ``signal``, its twin over the signal runs."""
+        return getattr(reader._L, ("pmx_dbam_coverage_signal_" if signal else "pmx_dbam_coverage_") + what)
+
     def begin(self, reader) -> None:
         """A zeroed table on the reader's handle (a stream reader calls it again when a pass opens a new handle)."""
         mask = np.ascontiguousarray(self.use, dtype=np.uint8) if self.names else np.zeros(1, dtype=np.uint8)
-        self.totals = None
+        self.totals = self.sig = None
         rc = reader._L.pmx_dbam_coverage_begin(reader._h, 0 if self.extend == PAIR else self.extend, mask.ctypes.data)
         if rc:
             reader._raise(rc)
@@ -212,131 +405,156 @@ class DeviceCount(SideAccumulator):
             self.totals = dict(zip(TOTALS, (int(x) for x in out)))
         return self.totals
 
-    def runs(self, reader, first: int = 0, n=None):
-        """(reference int32, start0, end0, depth uint32) of the runs ``[first, first + n)`` (``pmx_dbam_coverage_runs``)."""
-        n = self.finish(reader)["runs"] - int(first) if n is None else int(n)
-        out = [np.zeros(max(n, 1), dtype=t) for t in (np.int32, np.uint32, np.uint32, np.uint32)]
-        rc = reader._L.pmx_dbam_coverage_runs(reader._h, int(first), n, *(x.ctypes.data for x in out))
+    def signal(self, reader, bin: int = 1, scale: float = 1.0, normalize: str = "none") -> Dict[str, float]:
+        """Makes the signal runs on the handle (``pmx_dbam_coverage_signal``), beside the depth runs and in place of an earlier
+        signal, and returns their totals by name (``SIGNAL_TOTALS``).  Every method below takes ``signal=True`` to work on them.
+        ``normalize``: the word the track line says."""
+        bin, scale = check_bin(bin), check_scale(scale, self.finish(reader)["max_depth"])
+        out = np.zeros(4, dtype=np.float64)
+        self.sig = None
+        rc = reader._L.pmx_dbam_coverage_signal(reader._h, bin, scale, out.ctypes.data)
+        if rc:
+            reader._raise(rc)
+        self.sig = dict(bin=bin, scale=scale, normalize=check_normalize(normalize),
+                        totals=dict(runs=int(out[0]), covered_bases=int(out[1]), min=float(out[2]), max=float(out[3])))
+        return self.sig["totals"]
+
+    def _count(self, reader, signal: bool) -> int:
+        if signal and self.sig is None:
+            raise ValueError("no signal: call signal first")
+        return self.sig["totals"]["runs"] if signal else self.finish(reader)["runs"]
+
+    def runs(self, reader, first: int = 0, n=None, signal: bool = False):
+        """(reference int32, start0, end0, depth uint32) of the runs ``[first, first + n)`` (``pmx_dbam_coverage_runs``); with
+        ``signal`` the last column is the float32 value."""
+        n = self._count(reader, signal) - int(first) if n is None else int(n)
+        out = [np.zeros(max(n, 1), dtype=t) for t in (np.int32, np.uint32, np.uint32, np.float32 if signal else np.uint32)]
+        rc = self._fn(reader, "runs", signal)(reader._h, int(first), n, *(x.ctypes.data for x in out))
         if rc:
             reader._raise(rc)
         return tuple(x[:n] for x in out)
 
-    def text(self, reader, first: int = 0, n=None) -> bytes:
+    def text(self, reader, first: int = 0, n=None, signal: bool = False) -> bytes:
         """The bedGraph lines of the runs ``[first, first + n)``, formatted on the device (``pmx_dbam_coverage_text``: the size,
         then the bytes)."""
-        n = self.finish(reader)["runs"] - int(first) if n is None else int(n)
-        size = reader._L.pmx_dbam_coverage_text(reader._h, int(first), n, None, 0)
+        n = self._count(reader, signal) - int(first) if n is None else int(n)
+        fn = self._fn(reader, "text", signal)
+        size = fn(reader._h, int(first), n, None, 0)
         if size < 0:
             reader._raise(size)
         buf = np.zeros(max(int(size), 1), dtype=np.uint8)
-        got = reader._L.pmx_dbam_coverage_text(reader._h, int(first), n, buf.ctypes.data, int(size))
+        got = fn(reader._h, int(first), n, buf.ctypes.data, int(size))
         if got < 0:
             reader._raise(got)
         assert got == size
         return buf[:int(size)].tobytes()
 
-    def text_chunks(self, reader, chunk: int = TEXT_CHUNK) -> Iterator[bytes]:
-        total = self.finish(reader)["runs"]
+    def text_chunks(self, reader, chunk: int = TEXT_CHUNK, signal: bool = False) -> Iterator[bytes]:
+        total = self._count(reader, signal)
         for first in range(0, total, int(chunk)):
-            yield self.text(reader, first, min(int(chunk), total - first))
+            yield self.text(reader, first, min(int(chunk), total - first), signal)
 
-    def ranges(self, reader) -> np.ndarray:
+    def ranges(self, reader, signal: bool = False) -> np.ndarray:
         """The first run of every chosen reference in header order, one more entry closing them (``pmx_dbam_coverage_ranges``)."""
         self.finish(reader)
         out = np.zeros(len(self.refs) + 1, dtype=np.int64)
-        got = reader._L.pmx_dbam_coverage_ranges(reader._h, out.ctypes.data, out.size)
+        got = self._fn(reader, "ranges", signal)(reader._h, out.ctypes.data, out.size)
         if got < 0:
             reader._raise(got)
         assert got == out.size
         return out
 
-    def sections(self, reader, first: int, n: int, chrom_id: int, items: int):
+    def sections(self, reader, first: int, n: int, chrom_id: int, items: int, signal: bool = False):
         """(bytes, table) of the runs ``[first, first + n)`` of one reference as bedGraph sections of a bigWig file stamped with
-        ``chrom_id`` (``pmx_dbam_coverage_sections``: the size, then the bytes); ``table[section] = (id, start, id, end, bytes)``."""
-        L, h = reader._L, reader._h
-        size = L.pmx_dbam_coverage_sections(h, int(first), int(n), int(chrom_id), int(items), None, 0, None, 0)
+        ``chrom_id`` (``pmx_dbam_coverage_sections``: the size, then the bytes); ``table[section] = (id, start, id, end, bytes)``.
+        With ``signal`` (bytes, table, sums): ``sums[section] = (sum, sum of squares)``, float64."""
+        h, fn = reader._h, self._fn(reader, "sections", signal)
+        rows = -(-int(n) // int(items))
+        sums = np.zeros((max(rows, 1), 2), dtype=np.float64)
+        more = (sums.ctypes.data,) if signal else ()
+        size = fn(h, int(first), int(n), int(chrom_id), int(items), None, 0, None, 0, *((None,) if signal else ()))
         if size < 0:
             reader._raise(size)
         buf = np.zeros(max(int(size), 1), dtype=np.uint8)
-        table = np.zeros((max(-(-int(n) // int(items)), 1), 5), dtype=np.uint32)
-        got = L.pmx_dbam_coverage_sections(h, int(first), int(n), int(chrom_id), int(items), buf.ctypes.data, int(size),
-                                           table.ctypes.data, len(table))
+        table = np.zeros((max(rows, 1), 5), dtype=np.uint32)
+        got = fn(h, int(first), int(n), int(chrom_id), int(items), buf.ctypes.data, int(size), table.ctypes.data, len(table), *more)
         if got < 0:
             reader._raise(got)
         assert got == size
-        return buf[:int(size)].tobytes(), table[:-(-int(n) // int(items))]
+        return (buf[:int(size)].tobytes(), table[:rows]) + ((sums[:rows],) if signal else ())
 
-    def section_chunks(self, reader, k: int, chrom_id: int, items: int, chunk: int = TEXT_CHUNK):
+    def section_chunks(self, reader, k: int, chrom_id: int, items: int, chunk: int = TEXT_CHUNK, signal: bool = False):
         """``sections`` of the ``k``-th chosen reference, about ``chunk`` runs at a time (whole sections)."""
-        ranges = self.ranges(reader)
+        ranges = self.ranges(reader, signal)
         step = max(int(chunk) // int(items), 1) * int(items)
         for first in range(int(ranges[k]), int(ranges[k + 1]), step):
-            yield self.sections(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items)
+            yield self.sections(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items, signal)
 
-    def sections_z(self, reader, first: int, n: int, chrom_id: int, items: int):
+    def sections_z(self, reader, first: int, n: int, chrom_id: int, items: int, signal: bool = False):
         """``sections`` with every section compressed on the device (``pmx_dbam_coverage_sections_z``): (the zlib
-        streams end to end, the table of ``sections`` -- column 4 stays the raw size --, the streams' lengths)."""
-        L, h = reader._L, reader._h
-        bound = L.pmx_dbam_coverage_sections_z(h, int(first), int(n), int(chrom_id), int(items), None, 0, None, 0, None)
+        streams end to end, the table of ``sections`` -- column 4 stays the raw size --, the streams' lengths); with ``signal``
+        the sums of ``sections`` behind them."""
+        h, fn = reader._h, self._fn(reader, "sections_z", signal)
+        rows = -(-int(n) // int(items))
+        sums = np.zeros((max(rows, 1), 2), dtype=np.float64)
+        bound = fn(h, int(first), int(n), int(chrom_id), int(items), None, 0, None, 0, None, *((None,) if signal else ()))
         if bound < 0:
             reader._raise(bound)
-        rows = -(-int(n) // int(items))
         buf = np.zeros(max(int(bound), 1), dtype=np.uint8)
         table, zsizes = np.zeros((max(rows, 1), 5), dtype=np.uint32), np.zeros(max(rows, 1), dtype=np.uint32)
-        got = L.pmx_dbam_coverage_sections_z(h, int(first), int(n), int(chrom_id), int(items), buf.ctypes.data, int(bound),
-                                             table.ctypes.data, len(table), zsizes.ctypes.data)
+        got = fn(h, int(first), int(n), int(chrom_id), int(items), buf.ctypes.data, int(bound), table.ctypes.data, len(table),
+                 zsizes.ctypes.data, *((sums.ctypes.data,) if signal else ()))
         if got < 0:
             reader._raise(got)
         assert got <= bound and got == int(zsizes[:rows].sum(dtype=np.int64))
-        return buf[:int(got)].tobytes(), table[:rows], zsizes[:rows]
+        return (buf[:int(got)].tobytes(), table[:rows], zsizes[:rows]) + ((sums[:rows],) if signal else ())
 
-    def section_chunks_z(self, reader, k: int, chrom_id: int, items: int, chunk: int = DEFLATE_CHUNK):
+    def section_chunks_z(self, reader, k: int, chrom_id: int, items: int, chunk: int = DEFLATE_CHUNK, signal: bool = False):
         """``sections_z`` of the ``k``-th chosen reference, about ``chunk`` runs at a time (whole sections)."""
-        ranges = self.ranges(reader)
+        ranges = self.ranges(reader, signal)
         step = max(int(chunk) // int(items), 1) * int(items)
         for first in range(int(ranges[k]), int(ranges[k + 1]), step):
-            yield self.sections_z(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items)
+            yield self.sections_z(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items, signal)
 
-    def zoom_begin(self, reader, z0: int, levels: int, ids) -> Tuple[int, int]:
+    def zoom_begin(self, reader, z0: int, levels: int, ids, signal: bool = False) -> Tuple[int, int]:
         """Fills the zoom bins on the device (``pmx_dbam_coverage_zoom_begin``); ``ids[k]``: the chromosome id of the ``k``-th
-        chosen reference.  Returns (the sum of depth^2 over the covered bases, the smallest depth)."""
+        chosen reference.  Returns (the sum of depth^2 over the covered bases, the smallest depth); (0, 0) with ``signal``."""
         chrom_id = np.zeros(max(len(self.names), 1), dtype=np.uint32)
         chrom_id[np.flatnonzero(self.use)] = np.asarray(ids, dtype=np.uint32)
         out = np.zeros(2, dtype=np.uint64)
-        rc = reader._L.pmx_dbam_coverage_zoom_begin(reader._h, int(z0), int(levels), chrom_id.ctypes.data, out.ctypes.data)
+        rc = self._fn(reader, "zoom_begin", signal)(reader._h, int(z0), int(levels), chrom_id.ctypes.data, out.ctypes.data)
         if rc:
             reader._raise(rc)
         return int(out[0]), int(out[1])
 
-    def zoom_records(self, reader, level: int, items: int):
+    def zoom_records(self, reader, level: int, items: int, signal: bool = False):
         """(bytes, table) of a level's records, 32 bytes each, in sections of ``items`` (``pmx_dbam_coverage_zoom_records``);
         ``table[section] = (first id, first start, last id, last end, bytes)``.  The last level frees the bins."""
-        L, h = reader._L, reader._h
-        size = L.pmx_dbam_coverage_zoom_records(h, int(level), int(items), None, 0, None, 0)
+        h, fn = reader._h, self._fn(reader, "zoom_records", signal)
+        size = fn(h, int(level), int(items), None, 0, None, 0)
         if size < 0:
             reader._raise(size)
         rows = -(-(int(size) // 32) // int(items))
         buf = np.zeros(max(int(size), 1), dtype=np.uint8)
         table = np.zeros((max(rows, 1), 5), dtype=np.uint32)
-        got = L.pmx_dbam_coverage_zoom_records(h, int(level), int(items), buf.ctypes.data, int(size), table.ctypes.data, len(table))
+        got = fn(h, int(level), int(items), buf.ctypes.data, int(size), table.ctypes.data, len(table))
         if got < 0:
             reader._raise(got)
         assert got == size
         return buf[:int(size)].tobytes(), table[:rows]
 
-    def zoom_records_z(self, reader, level: int, items: int):
+    def zoom_records_z(self, reader, level: int, items: int, signal: bool = False):
         """``zoom_records`` with every section compressed on the device (``pmx_dbam_coverage_zoom_records_z``): (streams, table,
         the streams' lengths).  The last level frees the bins."""
-        L, h = reader._L, reader._h
-        size = L.pmx_dbam_coverage_zoom_records(h, int(level), int(items), None, 0, None, 0)       # (the raw bytes: the rows)
-        bound = L.pmx_dbam_coverage_zoom_records_z(h, int(level), int(items), None, 0, None, 0, None)
+        h, fn = reader._h, self._fn(reader, "zoom_records_z", signal)
+        size = self._fn(reader, "zoom_records", signal)(h, int(level), int(items), None, 0, None, 0)       # (the raw bytes: the rows)
+        bound = fn(h, int(level), int(items), None, 0, None, 0, None)
         if size < 0 or bound < 0:
             reader._raise(min(size, bound))
         rows = -(-(int(size) // 32) // int(items))
         buf = np.zeros(max(int(bound), 1), dtype=np.uint8)
         table, zsizes = np.zeros((max(rows, 1), 5), dtype=np.uint32), np.zeros(max(rows, 1), dtype=np.uint32)
-        got = L.pmx_dbam_coverage_zoom_records_z(h, int(level), int(items), buf.ctypes.data, int(bound), table.ctypes.data, len(table),
-                                                 zsizes.ctypes.data)
+        got = fn(h, int(level), int(items), buf.ctypes.data, int(bound), table.ctypes.data, len(table), zsizes.ctypes.data)
         if got < 0:
             reader._raise(got)
         assert got <= bound and got == int(zsizes[:rows].sum(dtype=np.int64))
@@ -352,6 +570,17 @@ class DeviceCount(SideAccumulator):
         if c.totals != tuple(totals[k] for k in TOTALS):
             raise RuntimeError("pmx_dbam_coverage_finish: the runs do not add up to the totals")
         return c
+
+    def signal_result(self, reader) -> Signal:
+        """The signal runs on the handle as a ``Signal``."""
+        ref, start, end, value = self.runs(reader, signal=True)
+        cut = np.flatnonzero(np.diff(ref)) + 1 if ref.size else np.zeros(0, dtype=np.int64)
+        edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
+        g = Signal({self.names[int(ref[a])]: (start[a:z], end[a:z], value[a:z]) for a, z in zip(edges[:-1], edges[1:])},
+                   self.sig["bin"], self.sig["scale"], self.refs, self.finish(reader)["reads"], self.extend, self.sig["normalize"])
+        if g.totals != tuple(self.sig["totals"][k] for k in SIGNAL_TOTALS):
+            raise RuntimeError("pmx_dbam_coverage_signal: the runs do not add up to the totals")
+        return g
 
 
 def count_device(reader, mapq_criteria: int, references=None, extend=0, max_size: int = 2000) -> Coverage:
@@ -391,19 +620,20 @@ def from_reader(reader, mapq_criteria: int = 0, references=None, extend=0, max_s
     return acc.result()
 
 
-def track_line(name: str, extend, reads: int) -> bytes:
-    return 'track type=bedGraph name="{}" description="pymasc_amd fragment pileup extend={} reads={}"\n'.format(
-        name, PAIR if extend == PAIR else int(extend) if int(extend) else "read", int(reads)).encode()
+def track_line(name: str, extend, reads: int, tail: str = "") -> bytes:
+    """``tail``: what a signal track says behind the depth track's line (``signal_tail``)."""
+    return 'track type=bedGraph name="{}" description="pymasc_amd fragment pileup extend={} reads={}"{}\n'.format(
+        name, PAIR if extend == PAIR else int(extend) if int(extend) else "read", int(reads), tail).encode()
 
 
-def write_track(path_base, name: str, extend, reads: int, chunks) -> Path:
+def write_track(path_base, name: str, extend, reads: int, chunks, tail: str = "") -> Path:
     """Writes ``<path_base>_coverage.bedGraph`` (to a temporary file beside it, renamed into place) and returns its path: the
-    track line, then the bytes of ``chunks`` (the lines of the runs)."""
+    track line (with ``tail`` behind it), then the bytes of ``chunks`` (the lines of the runs)."""
     path = Path(str(path_base) + COVERAGE_SUFFIX)
     tmp = "{}.tmp.{}".format(path, os.getpid())
     try:
         with open(tmp, "wb") as fp:
-            fp.write(track_line(name, extend, reads))
+            fp.write(track_line(name, extend, reads, tail))
             for chunk in chunks:
                 fp.write(chunk)
         os.replace(tmp, path)
@@ -413,12 +643,16 @@ def write_track(path_base, name: str, extend, reads: int, chunks) -> Path:
     return path
 
 
-def write_coverage(path_base, name: str, c, reader=None) -> Path:
-    """``write_track`` of a ``Coverage`` (the lines formatted with numpy) or, with ``reader``, of a finished ``DeviceCount`` on that
-    reader's handle: the lines are formatted on the device and pulled ``TEXT_CHUNK`` runs at a time."""
+def write_coverage(path_base, name: str, c, reader=None, signal: bool = False) -> Path:
+    """``write_track`` of a ``Coverage`` or a ``Signal`` (the lines formatted on the host) or, with ``reader``, of a finished
+    ``DeviceCount`` on that reader's handle: the lines are formatted on the device and pulled ``TEXT_CHUNK`` runs at a time;
+    ``signal``: the lines of the signal it made last (``DeviceCount.signal``)."""
     if reader is None:
-        return write_track(path_base, name, c.extend, c.reads, c.text_chunks())
-    return write_track(path_base, name, c.extend, c.finish(reader)["reads"], c.text_chunks(reader))
+        return write_track(path_base, name, c.extend, c.reads, c.text_chunks(), c.tail if isinstance(c, Signal) else "")
+    if signal and c.sig is None:
+        raise ValueError("no signal: call signal first")
+    tail = signal_tail(c.sig["bin"], c.sig["normalize"], c.sig["scale"]) if signal else ""
+    return write_track(path_base, name, c.extend, c.finish(reader)["reads"], c.text_chunks(reader, signal=signal), tail)
 
 
 def read_coverage(path) -> Tuple[str, Coverage]:
@@ -506,17 +740,21 @@ def sumsq_fits(max_depth: int, fragment_bases: int) -> bool:
     return int(max_depth) * int(fragment_bases) < 1 << 64
 
 
-def zoom_plan(lengths, covered_bases: int, runs: int, zoom_base=None) -> Tuple[int, int]:
-    """(z_0, levels) of a pileup over references of ``lengths``."""
+def zoom_plan(lengths, covered_bases: int, runs: int, zoom_base=None, bin: int = 1) -> Tuple[int, int]:
+    """(z_0, levels) of a pileup over references of ``lengths``; ``bin`` above 1 (a signal's): ``zoom_base`` is a multiple of it,
+    and without one ``z_0 = bin * p`` with the smallest power of two ``p`` that makes it at least ``10 * covered_bases / runs`` and
+    32."""
     if zoom_base is not None and (isinstance(zoom_base, bool) or int(zoom_base) != zoom_base or not 1 <= int(zoom_base) < 1 << 31):
         raise ValueError("zoom_base is an integer of at least 1 and below 2^31")
+    if zoom_base is not None and int(zoom_base) % int(bin):
+        raise ValueError("zoom_base is a multiple of the signal's bin")
     if not runs:
         return 0, 0
-    z0 = 32
+    z0 = 32 if int(bin) == 1 else int(bin)
     if zoom_base is not None:
         z0 = int(zoom_base)
     else:
-        while z0 * int(runs) < 10 * int(covered_bases):
+        while z0 * int(runs) < 10 * int(covered_bases) or z0 < 32:
             z0 *= 2
     longest, levels = max(lengths, default=0), 0
     while levels < ZOOM_LEVELS and 2 * z0 * 4 ** levels <= longest:
@@ -540,13 +778,16 @@ class HostParts:
     readers and the device's checker.  It has what ``assemble_bigwig`` takes from a source: ``refs``, ``totals``,
     ``section_chunks``, ``zoom_begin`` and ``zoom_records``."""
 
-    def __init__(self, c: Coverage):
+    def __init__(self, c):
+        """``c``: a ``Coverage``, or a ``Signal`` (then ``bin`` is its bin, ``section_chunks`` also hands the sections' sums and the
+        zoom levels are summed in float64 in the stated order)."""
         if c.refs is None:
             raise ValueError("the pileup does not know its chosen references' lengths (it was read from a bedGraph file)")
         if any(n not in dict(c.refs) for n in c.runs):
             raise ValueError("a run on a reference that is not among the chosen ones")
         self.c, self.refs = c, list(c.refs)
-        self.totals = dict(zip(TOTALS, c.totals))
+        self.bin = c.bin if isinstance(c, Signal) else None
+        self.totals = dict(zip(TOTALS if self.bin is None else SIGNAL_TOTALS, c.totals))
         self._levels = []
 
     def section_chunks(self, k: int, chrom_id: int, items: int, chunk: int = TEXT_CHUNK):
@@ -564,7 +805,14 @@ class HostParts:
             head = 6 * (first // items) + 3 * first
             out[head], out[head + 1], out[head + 2] = chrom_id, table[:, 1], table[:, 3]
             out[head + 5] = 1 | ((table[:, 4] - 24) // 12 << 16)
-            yield out.tobytes(), table
+            if self.bin is None:
+                yield out.tobytes(), table
+                continue
+            ov, v = (ea.astype(np.int64) - sa.astype(np.int64)).astype(np.float64), da.astype(np.float64)
+            sums = np.zeros((len(table), 2), dtype=np.float64)
+            np.add.at(sums[:, 0], i // items, ov * v)               # (np.add.at adds one element after the other, in order)
+            np.add.at(sums[:, 1], i // items, ov * (v * v))
+            yield out.tobytes(), table, sums
 
     @staticmethod
     def _reduce(j, cnt, mn, mx, sm, sq):
@@ -575,7 +823,43 @@ class HostParts:
         return (j[at], np.add.reduceat(cnt, at), np.minimum.reduceat(mn, at), np.maximum.reduceat(mx, at), np.add.reduceat(sm, at),
                 np.add.reduceat(sq, at))
 
+    @staticmethod
+    def _reduce_signal(j, cnt, mn, mx, sm, sq):
+        """``_reduce`` for a signal: the two float64 sums are added one after the other, in order, from 0.0."""
+        if not j.size:
+            return j, cnt, mn, mx, sm, sq
+        first = np.concatenate(([True], j[1:] != j[:-1]))
+        at, g = np.flatnonzero(first), np.cumsum(first) - 1
+        a, b = np.zeros(at.size, dtype=np.float64), np.zeros(at.size, dtype=np.float64)
+        np.add.at(a, g, sm)
+        np.add.at(b, g, sq)
+        return j[at], np.add.reduceat(cnt, at), np.minimum.reduceat(mn, at), np.maximum.reduceat(mx, at), a, b
+
+    def _zoom_begin_signal(self, z0: int, levels: int, ids) -> Tuple[int, int]:
+        order = np.argsort(np.asarray(ids))
+        empty = (np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float32))
+        level = []
+        for k in order.tolist():
+            s, e, v = self.c.runs.get(self.refs[k][0], empty)
+            s, e = s.astype(np.int64), e.astype(np.int64)
+            if not levels:
+                continue
+            j0, j1 = s // z0, (e - 1) // z0
+            n = j1 - j0 + 1
+            run = np.repeat(np.arange(s.size), n)
+            j = j0[run] + np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+            w = np.minimum(e[run], (j + 1) * z0) - np.maximum(s[run], j * z0)
+            ov, vv = w.astype(np.float64), v[run].astype(np.float64)
+            level.append(self._reduce_signal(j, w.astype(np.uint64), v[run], v[run], ov * vv, ov * (vv * vv)))
+        self._ids, self._z0, self._levels = [int(ids[k]) for k in order.tolist()], int(z0), [level] if levels else []
+        self._lens = [self.refs[k][1] for k in order.tolist()]
+        for _ in range(1, levels):
+            self._levels.append([self._reduce_signal(r[0] // 4, *r[1:]) for r in self._levels[-1]])
+        return 0, 0
+
     def zoom_begin(self, z0: int, levels: int, ids) -> Tuple[int, int]:
+        if self.bin is not None:
+            return self._zoom_begin_signal(z0, levels, ids)
         order = np.argsort(np.asarray(ids))                 # the chosen references in id order
         empty = (np.zeros(0, dtype=np.uint32),) * 3
         level, sumsq, low = [], 0, None
@@ -613,26 +897,29 @@ class HostParts:
 
 
 class _DeviceParts:
-    """A finished ``DeviceCount`` on its reader's handle as a source of ``assemble_bigwig``."""
+    """A finished ``DeviceCount`` on its reader's handle as a source of ``assemble_bigwig``; ``signal``: the signal it made last."""
 
-    def __init__(self, acc: "DeviceCount", reader):
-        self.acc, self.reader, self.refs = acc, reader, list(acc.refs)
-        self.totals = dict(acc.finish(reader))
+    def __init__(self, acc: "DeviceCount", reader, signal: bool = False):
+        self.acc, self.reader, self.refs, self.sg = acc, reader, list(acc.refs), bool(signal)
+        if self.sg and acc.sig is None:
+            raise ValueError("no signal: call signal first")
+        self.bin = acc.sig["bin"] if self.sg else None
+        self.totals = dict(acc.sig["totals"]) if self.sg else dict(acc.finish(reader))
 
     def section_chunks(self, k, chrom_id, items):
-        return self.acc.section_chunks(self.reader, k, chrom_id, items)
+        return self.acc.section_chunks(self.reader, k, chrom_id, items, signal=self.sg)
 
     def zoom_begin(self, z0, levels, ids):
-        return self.acc.zoom_begin(self.reader, z0, levels, ids)
+        return self.acc.zoom_begin(self.reader, z0, levels, ids, self.sg)
 
     def zoom_records(self, level, items):
-        return self.acc.zoom_records(self.reader, level, items)
+        return self.acc.zoom_records(self.reader, level, items, self.sg)
 
     def section_chunks_z(self, k, chrom_id, items):
-        return self.acc.section_chunks_z(self.reader, k, chrom_id, items)
+        return self.acc.section_chunks_z(self.reader, k, chrom_id, items, signal=self.sg)
 
     def zoom_records_z(self, level, items):
-        return self.acc.zoom_records_z(self.reader, level, items)
+        return self.acc.zoom_records_z(self.reader, level, items, self.sg)
 
 
 def _chrom_tree(names, ids, lengths, at: int) -> bytes:
@@ -751,11 +1038,12 @@ def assemble_bigwig(fp, src, compress=False, items_per_section: int = 1024, inde
         raise ValueError("compress=\"device\" needs a pileup counted by a device reader: this source has no section_chunks_z "
                          "(a host reader or device_ingest=False; use compress=True for zlib on the host)")
     refs, tot = src.refs, src.totals
+    sbin = getattr(src, "bin", None)                                   # a signal's bin; None: the depth runs
     if not refs:
         raise ValueError("no chosen reference")
-    if not sumsq_fits(tot["max_depth"], tot["fragment_bases"]):
+    if sbin is None and not sumsq_fits(tot["max_depth"], tot["fragment_bases"]):
         raise ValueError("max_depth * fragment_bases is 2^64 or more: the zoom levels' sums of squares would not be exact")
-    z0, levels = zoom_plan([l for _n, l in refs], tot["covered_bases"], tot["runs"], zoom_base)
+    z0, levels = zoom_plan([l for _n, l in refs], tot["covered_bases"], tot["runs"], zoom_base, sbin or 1)
     names = [n.encode() for n, _l in refs]
     order = sorted(range(len(refs)), key=lambda k: names[k])           # bytewise name order: a chromosome's id is its rank
     if any(names[a] == names[b] for a, b in zip(order, order[1:])):
@@ -765,14 +1053,19 @@ def assemble_bigwig(fp, src, compress=False, items_per_section: int = 1024, inde
         ids[k] = rank
     sumsq, low = src.zoom_begin(z0, levels, ids)
     # the pass over the runs against finish's totals: d <= d^2 <= max_depth * d for every covered base
-    if not (low <= tot["max_depth"] and tot["fragment_bases"] <= sumsq <= tot["max_depth"] * tot["fragment_bases"] and bool(low) == bool(tot["runs"])):
+    if sbin is None and not (low <= tot["max_depth"] and tot["fragment_bases"] <= sumsq <= tot["max_depth"] * tot["fragment_bases"]
+                             and bool(low) == bool(tot["runs"])):
         raise RuntimeError("the zoom pass does not agree with the pileup's totals")
     writer = _SectionWriter(fp, compress)
     try:
         fp.seek(0)
         fp.write(bytes(64 + 24 * levels))
         summary_at = fp.tell()
-        fp.write(struct.pack("<Qdddd", tot["covered_bases"], float(low), float(tot["max_depth"]), float(tot["fragment_bases"]), float(sumsq)))
+        if sbin is None:
+            fp.write(struct.pack("<Qdddd", tot["covered_bases"], float(low), float(tot["max_depth"]), float(tot["fragment_bases"]), float(sumsq)))
+        else:
+            fp.write(bytes(40))                                         # (a signal's two sums are known behind its sections)
+        total, squares = 0.0, 0.0
         tree_at = fp.tell()
         fp.write(_chrom_tree([names[k] for k in order], range(len(order)), [refs[k][1] for k in order], tree_at))
         data_at = fp.tell()
@@ -781,6 +1074,11 @@ def assemble_bigwig(fp, src, compress=False, items_per_section: int = 1024, inde
         for rank, k in enumerate(order):
             for part in (src.section_chunks_z if device else src.section_chunks)(k, rank, items):
                 table = part[1]
+                if sbin is not None:                                    # the sections' partial sums, added in file order
+                    part, sums = part[:-1], part[-1]
+                    for a, b in sums.tolist():
+                        total += a
+                        squares += b
                 o, s = writer.write_streams(*part) if device else writer.write(*part)
                 tables.append(table)
                 offsets.append(o)
@@ -808,6 +1106,9 @@ def assemble_bigwig(fp, src, compress=False, items_per_section: int = 1024, inde
                              writer.largest if compress else 0, 0))
         for z, at, zindex_at in zooms:
             fp.write(struct.pack("<IIQQ", z, 0, at, zindex_at))
+        if sbin is not None:
+            fp.seek(summary_at)
+            fp.write(struct.pack("<Qdddd", tot["covered_bases"], float(tot["min"]), float(tot["max"]), total, squares))
         fp.seek(data_at)
         fp.write(struct.pack("<Q", n_sections))
         fp.seek(0, os.SEEK_END)
@@ -838,23 +1139,24 @@ def deflate_device(chunks, device: int = 0):
     return [dst[int(z - n):int(z)].tobytes() for z, n in zip(ends, sizes)]
 
 
-def bigwig_source(c, reader=None):
-    """What ``assemble_bigwig`` reads: ``HostParts`` of a ``Coverage``, or a finished ``DeviceCount`` on ``reader``'s handle."""
-    return HostParts(c) if reader is None else _DeviceParts(c, reader)
+def bigwig_source(c, reader=None, signal: bool = False):
+    """What ``assemble_bigwig`` reads: ``HostParts`` of a ``Coverage`` or a ``Signal``, or a finished ``DeviceCount`` on ``reader``'s
+    handle (``signal``: the signal it made last)."""
+    return HostParts(c) if reader is None else _DeviceParts(c, reader, signal)
 
 
 def write_bigwig(path_base, name: str, c, reader=None, compress=False, items_per_section: int = 1024, index_block: int = 256,
-                 zoom_base=None) -> Path:
+                 zoom_base=None, signal: bool = False) -> Path:
     """Writes ``<path_base>_coverage.bw`` (to a temporary file beside it, renamed into place) and returns its path: the pileup of
     a ``Coverage`` that knows its chosen references (sections and zoom records made with numpy) or, with ``reader``, of a finished
     ``DeviceCount`` on that reader's handle (made on the GPU).  A bigWig file has no place for ``name``, the reads or the extent.
     A depth is exact as float32 up to 2^24 and rounded to nearest above.  ``compress``: as for ``assemble_bigwig``; ``"device"`` needs
-    ``reader``."""
+    ``reader``.  ``c`` may be a ``Signal``; with ``reader``, ``signal`` writes the signal the count made last."""
     path = Path(str(path_base) + BIGWIG_SUFFIX)
     tmp = "{}.tmp.{}".format(path, os.getpid())
     try:
         with open(tmp, "w+b") as fp:
-            assemble_bigwig(fp, bigwig_source(c, reader), compress, items_per_section, index_block, zoom_base)
+            assemble_bigwig(fp, bigwig_source(c, reader, signal), compress, items_per_section, index_block, zoom_base)
         os.replace(tmp, path)
     finally:
         if os.path.exists(tmp):

@@ -517,23 +517,41 @@ int coverage_finish_impl(pmx_dbam *b, uint64_t *totals)
     return run.rc = coverage_finish_run(b, totals);
 }
 
-int coverage_range(pmx_dbam *b, const char *fn, int64_t first, int64_t n)
+// The runs an entry point works on, and the kernels that read their fourth column: the depth runs finish left (CV_DEPTH) or the
+// signal runs pmx_dbam_coverage_signal made of them (SG_KIND, signal_device.inc), whose fourth column is a float32.  The host code
+// below is the same for both.
+struct CvKind {
+    bool sg;
+    const char *stem;                       // what the entry points' names begin with
+    decltype(&k_cv_textlen) textlen;
+    decltype(&k_cv_text) text;
+    std::string fn(const char *what) const { return std::string(stem) + what; }
+    u8 *runs(Coverage &c) const { return sg ? c.sruns.as<u8>() : c.runs.as<u8>(); }
+    u64 count(const Coverage &c) const { return sg ? c.snruns : c.nruns; }
+    std::vector<u64> &ranges(Coverage &c) const { return sg ? c.sranges : c.ranges; }
+};
+const CvKind CV_DEPTH = {false, "pmx_dbam_coverage_", k_cv_textlen, k_cv_text};
+
+int coverage_range(pmx_dbam *b, const CvKind &K, const std::string &fn, int64_t first, int64_t n)
 {
     if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
-    if (b->cv.state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": no runs: call pmx_dbam_coverage_finish first");
-    if (first < 0 || n < 0 || (u64)first > b->cv.nruns || (u64)n > b->cv.nruns - (u64)first)
-        return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": range outside the runs");
+    if (b->cv.state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, fn + ": no runs: call pmx_dbam_coverage_finish first");
+    if (K.sg && !b->cv.shave) return fail(PMX_DBAM_ERR_INVALID, fn + ": no signal: call pmx_dbam_coverage_signal first");
+    const u64 nruns = K.count(b->cv);
+    if (first < 0 || n < 0 || (u64)first > nruns || (u64)n > nruns - (u64)first) return fail(PMX_DBAM_ERR_INVALID, fn + ": range outside the runs");
     return 0;
 }
 
-int coverage_runs_impl(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth)
+// depth: the fourth column as it is kept, a u32 depth or the bits of a float32 value
+int coverage_runs_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth)
 {
-    if (int rc = coverage_range(b, "pmx_dbam_coverage_runs", first, n)) return rc;
-    if (!ref || !start || !end || !depth) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_runs: null output");
+    const std::string fn = K.fn("runs");
+    if (int rc = coverage_range(b, K, fn, first, n)) return rc;
+    if (!ref || !start || !end || !depth) return fail(PMX_DBAM_ERR_INVALID, fn + ": null output");
     HIPOK(hipSetDevice(b->device));
     HIPOK(hipStreamSynchronize(b->stream));
     if (n == 0) return 0;
-    const CvRuns V(b->cv.runs.as<u8>(), b->cv.nruns);
+    const CvRuns V(K.runs(b->cv), K.count(b->cv));
     HIPOK(hipMemcpy(ref, V.ref + first, 4 * (u64)n, hipMemcpyDeviceToHost));
     HIPOK(hipMemcpy(start, V.start + first, 4 * (u64)n, hipMemcpyDeviceToHost));
     HIPOK(hipMemcpy(end, V.end + first, 4 * (u64)n, hipMemcpyDeviceToHost));
@@ -541,15 +559,16 @@ int coverage_runs_impl(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint
     return 0;
 }
 
-int64_t coverage_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
+int64_t coverage_text_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
 {
-    if (int rc = coverage_range(b, "pmx_dbam_coverage_text", first, n)) return rc;
-    if (buf && cap < 0) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_text: a negative capacity");
+    const std::string fn = K.fn("text");
+    if (int rc = coverage_range(b, K, fn, first, n)) return rc;
+    if (buf && cap < 0) return fail(PMX_DBAM_ERR_INVALID, fn + ": a negative capacity");
     if (n == 0) return 0;
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
     const u64 m = (u64)n, nwg = (m + 255) / 256, nref = b->ref_names.size();
-    const CvRuns V(b->cv.runs.as<u8>(), b->cv.nruns);
+    const CvRuns V(K.runs(b->cv), K.count(b->cv));
     const u32 *noff = b->cv.names.as<u32>();
     const u8 *names = b->cv.names.as<u8>() + 4 * (nref + 1);
     DevAlloc d_len, d_w, d_wb, d_tot, d_text;
@@ -559,7 +578,7 @@ int64_t coverage_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, 
     HIPOK(hipMalloc(&d_w.p, 4 * nwg));
     HIPOK(hipMalloc(&d_wb.p, 8 * nwg));
     HIPOK(hipMalloc(&d_tot.p, 16));
-    hipLaunchKernelGGL(k_cv_textlen, dim3((unsigned)nwg), dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff,
+    hipLaunchKernelGGL(K.textlen, dim3((unsigned)nwg), dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff,
                        d_len.as<u32>(), d_w.as<u32>());
     HIPOK(hipGetLastError());
     hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_w.as<u32>(), d_w.as<u32>(), nwg, d_wb.as<u64>(), d_tot.as<u64>());
@@ -568,13 +587,13 @@ int64_t coverage_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, 
     HIPOK(hipMemcpyAsync(&bytes, d_tot.p, 8, hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     if (!buf) return (int64_t)bytes;
-    if ((u64)cap < bytes) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_text: the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
+    if ((u64)cap < bytes) return fail(PMX_DBAM_ERR_INVALID, fn + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
     if (hipMalloc(&d_text.p, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(PMX_DBAM_ERR_OPEN, "pmx_dbam_coverage_text: out of device memory for " + std::to_string(bytes) + " bytes of text");
+        return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(bytes) + " bytes of text");
     }
     held.add(bytes);
-    hipLaunchKernelGGL(k_cv_text, dim3((unsigned)nwg), dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff, names,
+    hipLaunchKernelGGL(K.text, dim3((unsigned)nwg), dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff, names,
                        d_len.as<u32>(), d_wb.as<u64>(), d_text.as<u8>());
     HIPOK(hipGetLastError());
     HIPOK(hipMemcpyAsync(buf, d_text.p, bytes, hipMemcpyDeviceToHost, st));
@@ -603,12 +622,12 @@ int pmx_dbam_coverage_finish(pmx_dbam *b, uint64_t totals[5])
 
 int pmx_dbam_coverage_runs(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *depth)
 {
-    return guarded("pmx_dbam_coverage_runs", [&] { return coverage_runs_impl(b, first, n, ref, start, end, depth); });
+    return guarded("pmx_dbam_coverage_runs", [&] { return coverage_runs_impl(b, CV_DEPTH, first, n, ref, start, end, depth); });
 }
 
 int64_t pmx_dbam_coverage_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
 {
-    return guarded("pmx_dbam_coverage_text", [&] { return coverage_text_impl(b, first, n, buf, cap); });
+    return guarded("pmx_dbam_coverage_text", [&] { return coverage_text_impl(b, CV_DEPTH, first, n, buf, cap); });
 }
 
 }  // extern "C"
@@ -823,6 +842,17 @@ u64 df_sections_bound(u64 nsec, u64 full, u64 last);
 int64_t df_sections_out(pmx_dbam *b, CvHold &held, const std::string &fn, const u8 *d_raw, u64 nsec, u64 full, u64 last, uint8_t *buf,
                         int64_t cap, uint32_t *zsizes);
 
+// the kernels of the second half for a kind of runs (CvKind): the sections, the optional sums per section, the zoom levels
+struct CvParts {
+    decltype(&k_cv_sections) sections;
+    void (*sums)(const u32 *, const u32 *, const u32 *, u64, u32, double *);      // (signal only) per section: sum and sum of squares
+    // level 0; h_idof / d_idof: the id of every reference on the host and on the device, d_off: the first bin of every id, d_lens
+    int (*fill)(pmx_dbam *b, const u32 *h_idof, const u32 *d_idof, const u64 *d_off, const u32 *d_lens, u32 z0, u64 nb0, u8 *bins,
+                unsigned long long *d_tot);
+    decltype(&k_cv_zoom_fold) fold;
+    decltype(&k_cv_zoom_emit) emit;
+};
+
 void zoom_drop(Coverage &c)
 {
     c.zbins = DevAlloc{};
@@ -835,59 +865,65 @@ void zoom_drop(Coverage &c)
 }
 
 // the first run of every chosen reference in header order, one more entry closing them; computed once per pileup
-int coverage_ranges_make(pmx_dbam *b)
+int coverage_ranges_make(pmx_dbam *b, const CvKind &K)
 {
     Coverage &c = b->cv;
-    if (!c.ranges.empty()) return 0;
+    std::vector<u64> &ranges = K.ranges(c);
+    const u64 nruns = K.count(c);
+    if (!ranges.empty()) return 0;
     const u64 nref = b->ref_names.size(), nc = c.chosen.size();
     std::vector<u64> first(std::max<u64>(nref, 1), ~0ull);
     HIPOK(hipSetDevice(b->device));
-    if (c.nruns) {
+    if (nruns) {
         DevAlloc d_first;
         CvHold held(b);
         held.add(8 * first.size());
         HIPOK(hipMalloc(&d_first.p, 8 * first.size()));
         HIPOK(hipMemsetAsync(d_first.p, 0xff, 8 * first.size(), b->stream));
-        hipLaunchKernelGGL(k_cv_ranges, dim3((unsigned)((c.nruns + 255) / 256)), dim3(256), 0, b->stream, CvRuns(c.runs.as<u8>(), c.nruns).ref, c.nruns,
+        hipLaunchKernelGGL(k_cv_ranges, dim3((unsigned)((nruns + 255) / 256)), dim3(256), 0, b->stream, CvRuns(K.runs(c), nruns).ref, nruns,
                            d_first.as<unsigned long long>());
         HIPOK(hipGetLastError());
         HIPOK(hipMemcpyAsync(first.data(), d_first.p, 8 * first.size(), hipMemcpyDeviceToHost, b->stream));
         HIPOK(hipStreamSynchronize(b->stream));
     }
-    std::vector<u64> r(nc + 1, c.nruns);
+    std::vector<u64> r(nc + 1, nruns);
     for (u64 k = nc; k-- > 0;) r[k] = first[(u64)c.chosen[k]] != ~0ull ? first[(u64)c.chosen[k]] : r[k + 1];
     for (u64 k = 0; k < nc; k++)
-        if (r[k] > r[k + 1]) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_ranges: the runs are not in header order");
-    c.ranges = std::move(r);
+        if (r[k] > r[k + 1]) return fail(PMX_DBAM_ERR_INVALID, K.fn("ranges") + ": the runs are not in header order");
+    ranges = std::move(r);
     return 0;
 }
 
-int64_t coverage_ranges_impl(pmx_dbam *b, int64_t *first, int64_t cap)
+int64_t coverage_ranges_impl(pmx_dbam *b, const CvKind &K, int64_t *first, int64_t cap)
 {
-    if (int rc = coverage_range(b, "pmx_dbam_coverage_ranges", 0, 0)) return rc;
+    const std::string fn = K.fn("ranges");
+    if (int rc = coverage_range(b, K, fn, 0, 0)) return rc;
     const int64_t n = (int64_t)b->cv.chosen.size() + 1;
     if (!first) return n;
-    if (cap < n) return fail(PMX_DBAM_ERR_INVALID, "pmx_dbam_coverage_ranges: the buffer is too small: " + std::to_string(n) + " entries are needed");
-    if (int rc = coverage_ranges_make(b)) return rc;
-    for (int64_t k = 0; k < n; k++) first[k] = (int64_t)b->cv.ranges[(u64)k];
+    if (cap < n) return fail(PMX_DBAM_ERR_INVALID, fn + ": the buffer is too small: " + std::to_string(n) + " entries are needed");
+    if (int rc = coverage_ranges_make(b, K)) return rc;
+    for (int64_t k = 0; k < n; k++) first[k] = (int64_t)K.ranges(b->cv)[(u64)k];
     return n;
 }
 
-// z: every section as a zlib stream (pmx_dbam_coverage_sections_z), the streams' lengths in zsizes
-int64_t coverage_sections_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
-                               uint32_t *table, int64_t table_cap, bool z = false, uint32_t *zsizes = nullptr)
+// z: every section as a zlib stream (pmx_dbam_coverage_sections_z), the streams' lengths in zsizes; sums (a kind that has them):
+// sums[section][2], the section's sum and sum of squares
+int64_t coverage_sections_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items,
+                               uint8_t *buf, int64_t cap, uint32_t *table, int64_t table_cap, bool z = false, uint32_t *zsizes = nullptr,
+                               double *sums = nullptr)
 {
-    const char *fn = z ? "pmx_dbam_coverage_sections_z" : "pmx_dbam_coverage_sections";
-    if (int rc = coverage_range(b, fn, first, n)) return rc;
+    const std::string fn = K.fn(z ? "sections_z" : "sections");
+    if (int rc = coverage_range(b, K, fn, first, n)) return rc;
     if (items < 1 || items > 65535) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": 1 to 65535 items per section");
     if (z && 24ull + 12ull * items > PMX_DEFLATE_MAX_CHUNK)
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at most 5459 items per section (a chunk of the encoder holds 65536 bytes)");
     if (buf && (cap < 0 || table_cap < 0)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": a negative capacity");
     if (n == 0) return 0;
-    if (int rc = coverage_ranges_make(b)) return rc;
+    if (int rc = coverage_ranges_make(b, K)) return rc;
     Coverage &c = b->cv;
-    const auto it = std::upper_bound(c.ranges.begin(), c.ranges.end(), (u64)first);       // (the first reference that begins behind `first`)
-    if (it == c.ranges.end() || (u64)first + (u64)n > *it) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the range holds two references");
+    const std::vector<u64> &ranges = K.ranges(c);
+    const auto it = std::upper_bound(ranges.begin(), ranges.end(), (u64)first);       // (the first reference that begins behind `first`)
+    if (it == ranges.end() || (u64)first + (u64)n > *it) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the range holds two references");
     const u64 m = (u64)n, nsec = (m + items - 1) / items, bytes = 24 * nsec + 12 * m;
     const u64 full = 24 + 12ull * items, last = bytes - (nsec - 1) * full;
     if (!buf) return (int64_t)(z ? df_sections_bound(nsec, full, last) : bytes);
@@ -895,19 +931,27 @@ int64_t coverage_sections_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t c
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
     if (!table || (u64)table_cap < nsec)
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the table is too small: " + std::to_string(nsec) + " rows are needed");
-    if (z && !zsizes) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": null output");
+    if ((z && !zsizes) || (P.sums && !sums)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": null output");
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
-    DevAlloc d_out;
+    DevAlloc d_out, d_sums;
     CvHold held(b);
     if (hipMalloc(&d_out.p, bytes + 20 * nsec) != hipSuccess) {
         (void)hipGetLastError();
         return fail(PMX_DBAM_ERR_OPEN, std::string(fn) + ": out of device memory for " + std::to_string(bytes + 20 * nsec) + " bytes of sections");
     }
     held.add(bytes + 20 * nsec);
-    const CvRuns V(c.runs.as<u8>(), c.nruns);
+    const CvRuns V(K.runs(c), K.count(c));
     u32 *d_table = (u32 *)(d_out.as<u8>() + bytes);
-    hipLaunchKernelGGL(k_cv_sections, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
+    if (P.sums) {
+        HIPOK(hipMalloc(&d_sums.p, 16 * nsec));
+        held.add(16 * nsec);
+        hipLaunchKernelGGL(P.sums, dim3((unsigned)((nsec + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
+                           d_sums.as<double>());
+        HIPOK(hipGetLastError());
+        HIPOK(hipMemcpyAsync(sums, d_sums.p, 16 * nsec, hipMemcpyDeviceToHost, st));
+    }
+    hipLaunchKernelGGL(P.sections, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
                        chrom_id, d_out.as<u32>(), d_table);
     HIPOK(hipGetLastError());
     if (!z) HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
@@ -916,15 +960,29 @@ int64_t coverage_sections_impl(pmx_dbam *b, int64_t first, int64_t n, uint32_t c
     return z ? df_sections_out(b, held, fn, d_out.as<u8>(), nsec, full, last, buf, cap, zsizes) : (int64_t)bytes;
 }
 
-int coverage_zoom_begin_impl(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t *out)
+// level 0 of the depth runs: k_cv_zoom_fill, which also reduces the two totals
+int cv_zoom_fill(pmx_dbam *b, const u32 *, const u32 *d_idof, const u64 *d_off, const u32 *, u32 z0, u64 nb0, u8 *bins, unsigned long long *d_tot)
 {
-    const char *fn = "pmx_dbam_coverage_zoom_begin";
-    if (int rc = coverage_range(b, fn, 0, 0)) return rc;
+    const Coverage &c = b->cv;
+    if (!c.nruns) return 0;
+    const CvRuns V(c.runs.as<u8>(), c.nruns);
+    hipLaunchKernelGGL(k_cv_zoom_fill, dim3((unsigned)((c.nruns + 255) / 256)), dim3(256), 0, b->stream, V.ref, V.start, V.end, V.depth, c.nruns, d_idof,
+                       d_off, z0, nb0, bins, d_tot);
+    HIPOK(hipGetLastError());
+    return 0;
+}
+const CvParts CV_DEPTH_PARTS = {k_cv_sections, nullptr, cv_zoom_fill, k_cv_zoom_fold, k_cv_zoom_emit};
+
+// out: the depth's two totals (the signal has none: its summary comes from signal's totals and the sections' sums; 0, 0)
+int coverage_zoom_begin_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t *out)
+{
+    const std::string fn = K.fn("zoom_begin");
+    if (int rc = coverage_range(b, K, fn, 0, 0)) return rc;
     if (!out || !chrom_id) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": null " + (out ? "chromosome ids" : "output"));
     out[0] = out[1] = 0;
     Coverage &c = b->cv;
     if (levels > PMX_COVERAGE_ZOOM_LEVELS || (levels && z0 < 1)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at most 10 levels, and a reduction of at least 1");
-    if ((unsigned __int128)c.tot[4] * c.tot[3] >> 64)
+    if (!K.sg && (unsigned __int128)c.tot[4] * c.tot[3] >> 64)
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": max_depth * fragment_bases is 2^64 or more: the sums of squares would not be exact");
     const u64 nref = b->ref_names.size(), nc = c.chosen.size();
     std::vector<u32> idof(std::max<u64>(nref, 1), 0), lens(nc, 0);
@@ -961,6 +1019,7 @@ int coverage_zoom_begin_impl(pmx_dbam *b, uint32_t z0, uint32_t levels, const ui
     c.bytes += c.zbytes;
     if (b->st) stream_note(*b);
     c.zlevels = levels;
+    c.zsg = K.sg;
     c.z0 = z0;
     c.znb = znb;
     c.zoff = zoff;
@@ -986,34 +1045,30 @@ int coverage_zoom_begin_impl(pmx_dbam *b, uint32_t z0, uint32_t levels, const ui
         HIPOK(hipMemsetAsync(c.zbins.p, 0, 28 * znb[0], st));
         HIPOK(hipMemsetAsync(B.mn, 0xff, 4 * znb[0], st));
     }
-    if (c.nruns) {
-        const CvRuns V(c.runs.as<u8>(), c.nruns);
-        hipLaunchKernelGGL(k_cv_zoom_fill, dim3((unsigned)((c.nruns + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, c.nruns, d_idof,
-                           d_off, z0, levels ? znb[0] : 0, levels && znb[0] ? c.zbins.as<u8>() : (u8 *)nullptr, d_tot.as<unsigned long long>());
-        HIPOK(hipGetLastError());
-    }
+    if (int rc = P.fill(b, idof.data(), d_idof, d_off, d_lens, z0, levels ? znb[0] : 0, levels && znb[0] ? c.zbins.as<u8>() : (u8 *)nullptr, d_tot.as<unsigned long long>()))
+        return rc;
     for (u32 k = 0; k + 1 < levels; k++) {
         if (!znb[k + 1]) continue;
-        hipLaunchKernelGGL(k_cv_zoom_fold, dim3((unsigned)((znb[k + 1] + 255) / 256)), dim3(256), 0, st, c.zbins.as<u8>() + zoff[k], znb[k],
+        hipLaunchKernelGGL(P.fold, dim3((unsigned)((znb[k + 1] + 255) / 256)), dim3(256), 0, st, c.zbins.as<u8>() + zoff[k], znb[k],
                            c.zbins.as<u8>() + zoff[k + 1], znb[k + 1], d_off + (u64)k * (nc + 1), d_off + (u64)(k + 1) * (nc + 1), (u32)nc);
         HIPOK(hipGetLastError());
     }
     HIPOK(hipMemcpyAsync(tot, d_tot.p, 16, hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));       // (off, idof and lens are locals)
-    out[0] = tot[0];
-    out[1] = c.nruns ? tot[1] : 0;
+    out[0] = K.sg ? 0 : tot[0];
+    out[1] = !K.sg && c.nruns ? tot[1] : 0;
     drop.ok = true;
     if (!levels) zoom_drop(c);              // (nothing to pull)
     return 0;
 }
 
-int64_t coverage_zoom_records_impl(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table, int64_t table_cap,
-                                   bool zs = false, uint32_t *zsizes = nullptr)
+int64_t coverage_zoom_records_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap,
+                                   uint32_t *table, int64_t table_cap, bool zs = false, uint32_t *zsizes = nullptr)
 {
-    const char *fn = zs ? "pmx_dbam_coverage_zoom_records_z" : "pmx_dbam_coverage_zoom_records";
-    if (int rc = coverage_range(b, fn, 0, 0)) return rc;
+    const std::string fn = K.fn(zs ? "zoom_records_z" : "zoom_records");
+    if (int rc = coverage_range(b, K, fn, 0, 0)) return rc;
     Coverage &c = b->cv;
-    if (level >= c.zlevels) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": no bins of that level: call pmx_dbam_coverage_zoom_begin first");
+    if (level >= c.zlevels || c.zsg != K.sg) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": no bins of that level: call " + K.fn("zoom_begin") + " first");
     if (items < 1) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at least 1 item per section");
     if (zs && 32ull * items > PMX_DEFLATE_MAX_CHUNK)
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": at most 2048 items per section (a chunk of the encoder holds 65536 bytes)");
@@ -1056,7 +1111,7 @@ int64_t coverage_zoom_records_impl(pmx_dbam *b, uint32_t level, uint32_t items, 
         u64 z = c.z0;
         for (u32 k = 0; k < level; k++) z *= 4;
         u32 *d_table = (u32 *)(d_out.as<u8>() + bytes);
-        hipLaunchKernelGGL(k_cv_zoom_emit, dim3((unsigned)nwg), dim3(256), 0, st, bins, nb, d_off, d_lens, (u32)nc, (u32)z, items, d_kb.as<u64>(),
+        hipLaunchKernelGGL(P.emit, dim3((unsigned)nwg), dim3(256), 0, st, bins, nb, d_off, d_lens, (u32)nc, (u32)z, items, d_kb.as<u64>(),
                            d_tot.as<u64>(), d_out.as<u32>(), d_table);
         HIPOK(hipGetLastError());
         if (!zs) HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
@@ -1074,24 +1129,24 @@ extern "C" {
 
 int64_t pmx_dbam_coverage_ranges(pmx_dbam *b, int64_t *first, int64_t cap)
 {
-    return guarded("pmx_dbam_coverage_ranges", [&] { return coverage_ranges_impl(b, first, cap); });
+    return guarded("pmx_dbam_coverage_ranges", [&] { return coverage_ranges_impl(b, CV_DEPTH, first, cap); });
 }
 
 int64_t pmx_dbam_coverage_sections(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
                                    uint32_t *table, int64_t table_cap)
 {
-    return guarded("pmx_dbam_coverage_sections", [&] { return coverage_sections_impl(b, first, n, chrom_id, items, buf, cap, table, table_cap); });
+    return guarded("pmx_dbam_coverage_sections", [&] { return coverage_sections_impl(b, CV_DEPTH, CV_DEPTH_PARTS, first, n, chrom_id, items, buf, cap, table, table_cap); });
 }
 
 int pmx_dbam_coverage_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t out[2])
 {
-    return guarded("pmx_dbam_coverage_zoom_begin", [&] { return coverage_zoom_begin_impl(b, z0, levels, chrom_id, out); });
+    return guarded("pmx_dbam_coverage_zoom_begin", [&] { return coverage_zoom_begin_impl(b, CV_DEPTH, CV_DEPTH_PARTS, z0, levels, chrom_id, out); });
 }
 
 int64_t pmx_dbam_coverage_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
                                        int64_t table_cap)
 {
-    return guarded("pmx_dbam_coverage_zoom_records", [&] { return coverage_zoom_records_impl(b, level, items, buf, cap, table, table_cap); });
+    return guarded("pmx_dbam_coverage_zoom_records", [&] { return coverage_zoom_records_impl(b, CV_DEPTH, CV_DEPTH_PARTS, level, items, buf, cap, table, table_cap); });
 }
 
 }  // extern "C"

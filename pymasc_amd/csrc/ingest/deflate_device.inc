@@ -466,14 +466,14 @@ int64_t pmx_dbam_coverage_sections_z(pmx_dbam *b, int64_t first, int64_t n, uint
                                      uint32_t *table, int64_t table_cap, uint32_t *zsizes)
 {
     return guarded("pmx_dbam_coverage_sections_z",
-                   [&] { return coverage_sections_impl(b, first, n, chrom_id, items, buf, cap, table, table_cap, true, zsizes); });
+                   [&] { return coverage_sections_impl(b, CV_DEPTH, CV_DEPTH_PARTS, first, n, chrom_id, items, buf, cap, table, table_cap, true, zsizes); });
 }
 
 int64_t pmx_dbam_coverage_zoom_records_z(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
                                          int64_t table_cap, uint32_t *zsizes)
 {
     return guarded("pmx_dbam_coverage_zoom_records_z",
-                   [&] { return coverage_zoom_records_impl(b, level, items, buf, cap, table, table_cap, true, zsizes); });
+                   [&] { return coverage_zoom_records_impl(b, CV_DEPTH, CV_DEPTH_PARTS, level, items, buf, cap, table, table_cap, true, zsizes); });
 }
 
 }  // extern "C"

@@ -69,6 +69,14 @@ struct Coverage {
     u32 zlevels = 0, z0 = 0;         // levels; the reduction of level 0
     std::vector<u64> znb, zoff;      // per level: its bins; its first byte in zbins
     u64 zbytes = 0;                  // device bytes of zbins and ztab, counted in `bytes`
+    bool zsg = false;                // the bins are the signal's: f64 sums and f32 bounds in the same 28 bytes
+    // the signal track (pmx_dbam_coverage_signal, signal_device.inc; DESIGN.md 7.18.3): from signal until the next signal, begin or close
+    DevAlloc sruns;                  // u8: reference, start, end, float32 value of every signal run (the layout of `runs`)
+    bool shave = false;              // a signal has been made of these runs
+    u64 snruns = 0;                  // its runs
+    u32 sbin = 0;                    // its bin
+    double stot[4] = {0, 0, 0, 0};   // runs, covered bases, smallest and largest value
+    std::vector<u64> sranges;        // `ranges` of the signal runs
     bool on() const { return state == CV_TABLE; }
     u64 held() const { return bytes; }
 };

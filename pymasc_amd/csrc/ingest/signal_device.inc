@@ -1,0 +1,701 @@
+// The pileup as a signal track: the mean depth per bin times a scale factor, float32 (pmx_dbam_coverage_signal*,
+// include/pymasc_amd_ingest.h; DESIGN.md 7.18.3).  Included in bam_device.hip behind coverage_device.inc and deflate_device.inc: the
+// host code of every consumer is coverage_device.inc's, run with SG_KIND / SG_PARTS in place of CV_DEPTH / CV_DEPTH_PARTS.
+//
+// The definitions.  Reference r of length len has the bins j = 0 .. ceil(len / B) - 1; bin j covers [j * B, min((j + 1) * B, len)) and
+// has the width w_j (only the last bin can be short); S_j is the integer sum of the depth over its bases (below 2^47: exact as u64 and
+// as float64); B is 1 .. 65536.  v_j = f32((f64(S_j) * scale) / f64(w_j)): one float64 multiply, one float64 divide, one conversion
+// to float32, each rounded to nearest even.  scale is a finite float64 of at least 2^-64 (no value is a float32 denormal) with
+// scale * max_depth < 2^40 (v * 10^6 < 2^63: the text is integer arithmetic).  Consecutive bins of one reference are one run when
+// they have the same S and the same width -- the rule is on S, not on v --, bins with S = 0 are in no run; a run is (ref, start0, end0,
+// v), in header order.  With B = 1 the signal runs are the depth runs with v = f32(f64(depth) * scale).  Totals: runs, covered bases
+// (the runs' widths summed), the smallest and the largest v.
+// The text of a value is the decimal expansion of the exact value of v rounded to six decimals, ties to even, without trailing
+// zeros and without a trailing '.': a float32 is m * 2^e with m < 2^24, so m * 10^6 fits 64 bits and the rounding is a shift, a
+// remainder and a comparison with half.
+// A zoom bin of level 0 takes the signal runs that overlap it in ascending start order, each by ov bases: validCount = sum ov, min
+// and max over v, sum: acc += f64(ov) * f64(v), sumSquares: acc += f64(ov) * (f64(v) * f64(v)), both from 0.0, every multiply and
+// add rounded on its own (no fused multiply-add); a bin of level k + 1 adds its up to four bins of level k in index order the same
+// way.  The two sums of a data section: its runs in order with the same two products, from 0.0.
+//
+//   k_sg_convert     B = 1: one lane per depth run
+//   k_cv_bin_fill    B > 1: one lane per depth run; the bins it overlaps take overlap * depth by a return-less 64-bit atomic add into a
+//                    dense u64 table, one slot per bin of every chosen reference, the references end to end (integers: no order)
+//   k_sg_mark / k_bam_scan / k_sg_entries   a bin begins an entry where S differs from the bin before, where its width does (the
+//                    short last bin) or where its reference begins; compacted by ballots (256 bins per workgroup) into (reference,
+//                    bin, S)
+//   k_sg_keep / k_bam_scan / k_sg_close     entry k ends where entry k + 1 of its reference begins, the last at the reference's
+//                    end; the entries with S = 0 are dropped by this second compaction; the totals are reduced over the wave, one
+//                    atomic each per wave, min and max of the non-negative float32 through their bits as u32
+//   k_sg_textlen / k_sg_text                k_cv_textlen / k_cv_text with the value formatted as above
+//   k_sg_sections / k_sg_secsums            one lane per run: its item; one lane per section: its two sums over its runs in order
+//   k_sg_zoom_fill   one lane per bin of level 0: a binary search for the first run of its reference that ends behind the bin's
+//                    beginning, then forward in order; no atomics
+//   k_sg_zoom_fold / k_sg_zoom_emit         over (u32 valid, f32 min, f32 max, f64 sum, f64 sq), in ZmBins' 28 bytes
+// Device memory: 8 bytes per bin + 16 per entry inside signal (counted in the handle's bytes while it runs), then 16 per signal run
+// until the next signal, begin or close.
+
+#define SG_MAX_BIN 65536u
+
+namespace {
+struct SgGeo {          // the bins of the chosen references k = 0 .. nc - 1 in header order
+    const u64 *boff;    // [nc + 1]: the first bin of k
+    const u32 *lens;    // [nc]
+    const int *cref;    // [nc]: the reference id of k
+    u32 nc, B;
+};
+}  // namespace
+
+__device__ __forceinline__ u32 sg_value(u64 S, double scale, u32 w)
+{
+#pragma clang fp contract(off)
+    const double x = (double)S * scale;
+    const double q = x / (double)w;
+    return __float_as_uint(__double2float_rn(q));
+}
+
+// covered bases, and the bits of the smallest and largest value, of the lanes that `have` a run: tot[0] +=, tot[1] = min, tot[2] = max
+__device__ __forceinline__ void sg_totals(u32 lane, bool have, u64 width, u32 bits, unsigned long long *__restrict__ tot)
+{
+    u32 lo = have ? bits : 0xffffffffu, hi = have ? bits : 0u;
+    width = cx_wave_sum(have ? width : 0ull);
+    for (int d = 32; d > 0; d >>= 1) {
+        const u32 x = __shfl_xor(lo, d, 64), y = __shfl_xor(hi, d, 64);
+        lo = x < lo ? x : lo;
+        hi = y > hi ? y : hi;
+    }
+    if (lane == 0 && lo != 0xffffffffu) {
+        atomicAdd(&tot[0], (unsigned long long)width);
+        atomicMin(&tot[1], (unsigned long long)lo);
+        atomicMax(&tot[2], (unsigned long long)hi);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_sg_convert(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
+                                                    const u32 *__restrict__ rdepth, u64 n, double scale, int *__restrict__ oref,
+                                                    u32 *__restrict__ ostart, u32 *__restrict__ oend, u32 *__restrict__ oval,
+                                                    unsigned long long *__restrict__ tot)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    u32 bits = 0;
+    u64 width = 0;
+    if (i < n) {
+        const u32 s = rstart[i], e = rend[i];
+        bits = sg_value((u64)rdepth[i], scale, 1u);
+        oref[i] = rref[i];
+        ostart[i] = s;
+        oend[i] = e;
+        oval[i] = bits;
+        width = (u64)(e - s);
+    }
+    sg_totals(threadIdx.x & 63u, i < n, width, bits, tot);
+}
+
+// bof[r]: the first bin of reference r (every run lies on a chosen reference)
+__global__ void __launch_bounds__(256) k_cv_bin_fill(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
+                                                     const u32 *__restrict__ rdepth, u64 n, const u64 *__restrict__ bof, u32 B,
+                                                     unsigned long long *__restrict__ tab)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const u32 s = rstart[i], e = rend[i], d = rdepth[i];
+    const u64 b0 = bof[rref[i]];
+    const u32 j1 = (e - 1u) / B;                          // (e > s and e <= the reference's length: bin j1 exists)
+    for (u32 j = s / B; j <= j1; j++) {
+        const u64 lo = (u64)j * B, hi = lo + B;
+        const u64 w = (e < hi ? (u64)e : hi) - (s > lo ? (u64)s : lo);
+        atomicAdd(&tab[b0 + j], (unsigned long long)(w * d));
+    }
+}
+
+// whether bin b begins an entry; k: its reference, j: its bin there
+__device__ __forceinline__ bool sg_begins(const unsigned long long *__restrict__ tab, u64 b, const SgGeo &G, u32 &k, u32 &j)
+{
+    k = cv_zoom_id(G.boff, G.nc, b);
+    j = (u32)(b - G.boff[k]);
+    if (j == 0) return true;
+    return ((u64)j + 1u) * G.B > (u64)G.lens[k] || tab[b - 1u] != tab[b];        // the short last bin; another S
+}
+
+__global__ void __launch_bounds__(256) k_sg_mark(const unsigned long long *__restrict__ tab, u64 nb, SgGeo G, u32 *__restrict__ kcnt)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x;
+    const u64 b = (u64)blockIdx.x * 256u + t;
+    u32 k, j;
+    const u64 m = __ballot(b < nb && sg_begins(tab, b, G, k, j));
+    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ void __launch_bounds__(256) k_sg_entries(const unsigned long long *__restrict__ tab, u64 nb, SgGeo G, const u64 *__restrict__ kbase,
+                                                    u32 *__restrict__ eid, u32 *__restrict__ ej, unsigned long long *__restrict__ eS)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x, lane = t & 63u;
+    const u64 b = (u64)blockIdx.x * 256u + t;
+    u32 k = 0, j = 0;
+    const bool keep = b < nb && sg_begins(tab, b, G, k, j);
+    const u64 m = __ballot(keep);
+    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (!keep) return;
+    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
+    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
+    eid[o] = k;
+    ej[o] = j;
+    eS[o] = tab[b];
+}
+
+__global__ void __launch_bounds__(256) k_sg_keep(const unsigned long long *__restrict__ eS, u64 n, u32 *__restrict__ kcnt)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x;
+    const u64 k = (u64)blockIdx.x * 256u + t;
+    const u64 m = __ballot(k < n && eS[k] != 0);
+    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ void __launch_bounds__(256) k_sg_close(const u32 *__restrict__ eid, const u32 *__restrict__ ej, const unsigned long long *__restrict__ eS,
+                                                  u64 n, const u64 *__restrict__ kbase, SgGeo G, double scale, int *__restrict__ oref,
+                                                  u32 *__restrict__ ostart, u32 *__restrict__ oend, u32 *__restrict__ oval,
+                                                  unsigned long long *__restrict__ tot)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x, lane = t & 63u;
+    const u64 k = (u64)blockIdx.x * 256u + t;
+    const bool keep = k < n && eS[k] != 0;
+    const u64 m = __ballot(keep);
+    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    u64 width = 0;
+    u32 bits = 0;
+    if (keep) {
+        u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
+        for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
+        const u32 id = eid[k], len = G.lens[id];
+        const u32 a = ej[k] * G.B;                                                         // (below len < 2^32)
+        const u32 z = k + 1u < n && eid[k + 1u] == id ? ej[k + 1u] * G.B : len;
+        const u32 w = len - a < G.B ? len - a : G.B;                                       // the width of the run's bins
+        bits = sg_value((u64)eS[k], scale, w);
+        oref[o] = G.cref[id];
+        ostart[o] = a;
+        oend[o] = z;
+        oval[o] = bits;
+        width = (u64)(z - a);
+    }
+    sg_totals(lane, keep, width, bits, tot);
+}
+
+// round(v * 10^6), ties to even, of the float32 with these bits (0 <= v < 2^40), in integers
+__device__ __forceinline__ u64 sg_micro(u32 bits)
+{
+    const u32 ex = (bits >> 23) & 255u;
+    const u64 P = (u64)((bits & 0x7fffffu) | (ex ? 0x800000u : 0u)) * 1000000ull;          // m * 10^6 < 2^44; v = m * 2^e
+    const int e = (int)(ex ? ex : 1u) - 150;
+    if (e >= 0) return P << (e < 19 ? e : 19);                                             // (v < 2^40: e <= 16)
+    const u32 sh = (u32)-e;
+    if (sh >= 46u) return 0;                                                               // P is below half of 2^sh
+    const u64 q = P >> sh, r = P & ((1ull << sh) - 1ull), half = 1ull << (sh - 1u);
+    return q + (u64)(r > half || (r == half && (q & 1ull)));
+}
+
+__device__ __forceinline__ u32 sg_width(u64 v)      // the decimal digits of v
+{
+    u32 w = 1;
+    for (; v >= 10u; v /= 10u) w++;
+    return w;
+}
+
+// N = round(v * 10^6) as whole part and fraction: the fraction's digits without trailing zeros (nd of them, 0 .. 6)
+__device__ __forceinline__ void sg_split(u64 N, u64 &whole, u32 &frac, u32 &nd)
+{
+    whole = N / 1000000ull;
+    frac = (u32)(N - whole * 1000000ull);
+    nd = frac ? 6u : 0u;
+    while (nd && frac % 10u == 0) {
+        frac /= 10u;
+        nd--;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_sg_textlen(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
+                                                    const u32 *__restrict__ rval, u64 n, const u32 *__restrict__ noff,
+                                                    u32 *__restrict__ len, u32 *__restrict__ wsum)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x;
+    const u64 i = (u64)blockIdx.x * 256u + t;
+    u32 l = 0;
+    if (i < n) {
+        const u32 r = (u32)rref[i];
+        u64 whole;
+        u32 frac, nd;
+        sg_split(sg_micro(rval[i]), whole, frac, nd);
+        l = noff[r + 1u] - noff[r] + cv_width(rstart[i]) + cv_width(rend[i]) + sg_width(whole) + (nd ? nd + 1u : 0u) + 4u;
+        len[i] = l;
+    }
+    l = (u32)cx_wave_sum((u64)l);
+    if ((t & 63u) == 0) s_w[t >> 6] = l;
+    __syncthreads();
+    if (t == 0) wsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ void __launch_bounds__(256) k_sg_text(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
+                                                 const u32 *__restrict__ rval, u64 n, const u32 *__restrict__ noff, const u8 *__restrict__ names,
+                                                 const u32 *__restrict__ len, const u64 *__restrict__ wbase, u8 *__restrict__ out)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x, lane = t & 63u;
+    const u64 i = (u64)blockIdx.x * 256u + t;
+    const u32 l = i < n ? len[i] : 0u;
+    const u32 incl = cv_wave_scan(l, lane);
+    if (lane == 63u) s_w[t >> 6] = incl;
+    __syncthreads();
+    if (i >= n) return;
+    u64 o = wbase[blockIdx.x] + incl - l;
+    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
+    const u32 r = (u32)rref[i];
+    u8 *p = out + o;
+    for (u32 c = noff[r]; c < noff[r + 1u]; c++) *p++ = names[c];
+    u64 whole;
+    u32 frac, nd;
+    sg_split(sg_micro(rval[i]), whole, frac, nd);
+    u8 *q = out + o + l;                // the line from its end: LF, fraction, '.', whole part, TAB, end, TAB, start, TAB
+    *--q = '\n';
+    if (nd) {
+        for (u32 c = 0; c < nd; c++) {  // (nd digits, leading zeros among them)
+            *--q = (u8)('0' + frac % 10u);
+            frac /= 10u;
+        }
+        *--q = '.';
+    }
+    do {
+        *--q = (u8)('0' + (u32)(whole % 10u));
+        whole /= 10u;
+    } while (whole);
+    *--q = '\t';
+    q = cv_digits(q, rend[i]);
+    *--q = '\t';
+    q = cv_digits(q, rstart[i]);
+    *--q = '\t';                        // (q == p: the lengths are k_sg_textlen's)
+}
+
+// k_cv_sections with the value as it is kept
+__global__ void __launch_bounds__(256) k_sg_sections(const u32 *__restrict__ rstart, const u32 *__restrict__ rend, const u32 *__restrict__ rval,
+                                                     u64 n, u32 ips, u32 id, u32 *__restrict__ out, u32 *__restrict__ table)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const u64 sec = i / ips;
+    u32 *p = out + 6u * (sec + 1u) + 3u * i;
+    const u32 a = rstart[i];
+    p[0] = a;
+    p[1] = rend[i];
+    p[2] = rval[i];
+    if (i == sec * ips) {
+        const u64 last = i + ips - 1u < n - 1u ? i + ips - 1u : n - 1u;
+        const u32 cnt = (u32)(last - i) + 1u, z = rend[last];
+        u32 *h = p - 6;
+        h[0] = id;
+        h[1] = a;
+        h[2] = z;
+        h[3] = 0;                           // itemStep
+        h[4] = 0;                           // itemSpan
+        h[5] = 1u | (cnt << 16);            // type 1 (bedGraph), a reserved byte, itemCount
+        u32 *T = table + 5u * sec;
+        T[0] = id;
+        T[1] = a;
+        T[2] = id;
+        T[3] = z;
+        T[4] = 24u + 12u * cnt;
+    }
+}
+
+// sums[2 * section], [2 * section + 1]: the section's runs in order, acc += f64(ov) * f64(v) and acc += f64(ov) * (f64(v) * f64(v))
+__global__ void __launch_bounds__(256) k_sg_secsums(const u32 *rstart, const u32 *rend, const u32 *rval, u64 n, u32 ips, double *sums)
+{
+#pragma clang fp contract(off)
+    const u64 sec = (u64)blockIdx.x * 256u + threadIdx.x;
+    const u64 i0 = sec * ips;
+    if (i0 >= n) return;
+    const u64 i1 = i0 + ips < n ? i0 + ips : n;
+    double sum = 0.0, sq = 0.0;
+    for (u64 i = i0; i < i1; i++) {
+        const double ov = (double)(rend[i] - rstart[i]), v = (double)__uint_as_float(rval[i]);
+        const double a = ov * v, vv = v * v;
+        const double q = ov * vv;
+        sum = sum + a;
+        sq = sq + q;
+    }
+    sums[2u * sec] = sum;
+    sums[2u * sec + 1u] = sq;
+}
+
+// rng[2 * id], rng[2 * id + 1]: the runs of the reference with that id; off0, lens: by id
+__global__ void __launch_bounds__(256) k_sg_zoom_fill(const u32 *__restrict__ rstart, const u32 *__restrict__ rend, const u32 *__restrict__ rval,
+                                                      const u64 *__restrict__ rng, const u64 *__restrict__ off0, const u32 *__restrict__ lens,
+                                                      u32 nc, u32 z, u64 nb, u8 *__restrict__ bins)
+{
+#pragma clang fp contract(off)
+    const u64 b = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (b >= nb) return;
+    const ZmBins B(bins, nb);
+    const u32 id = cv_zoom_id(off0, nc, b);
+    const u64 lo = (b - off0[id]) * z, hi = lo + z < (u64)lens[id] ? lo + z : (u64)lens[id];
+    u64 a = rng[2u * id], top = rng[2u * id + 1u], zz = top;
+    while (a < zz) {                        // the first run that ends behind lo
+        const u64 mid = a + (zz - a) / 2u;
+        if ((u64)rend[mid] > lo) zz = mid;
+        else a = mid + 1u;
+    }
+    u32 cnt = 0;
+    float mn = 0.0f, mx = 0.0f;
+    double sum = 0.0, sq = 0.0;
+    for (u64 i = a; i < top && (u64)rstart[i] < hi; i++) {
+        const u64 s = rstart[i], e = rend[i];
+        const u32 w = (u32)((e < hi ? e : hi) - (s > lo ? s : lo));
+        const float f = __uint_as_float(rval[i]);
+        const double ov = (double)w, v = (double)f;
+        const double p = ov * v, vv = v * v;
+        const double q = ov * vv;
+        sum = sum + p;
+        sq = sq + q;
+        mn = cnt == 0 || f < mn ? f : mn;
+        mx = f > mx ? f : mx;
+        cnt += w;
+    }
+    B.sum[b] = (u64)__double_as_longlong(sum);
+    B.sq[b] = (u64)__double_as_longlong(sq);
+    B.cnt[b] = cnt;
+    B.mn[b] = __float_as_uint(mn);
+    B.mx[b] = __float_as_uint(mx);
+}
+
+__global__ void __launch_bounds__(256) k_sg_zoom_fold(u8 *__restrict__ src, u64 nsrc, u8 *__restrict__ dst, u64 ndst,
+                                                      const u64 *__restrict__ offs, const u64 *__restrict__ offd, u32 nc)
+{
+#pragma clang fp contract(off)
+    const u64 b = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (b >= ndst) return;
+    const ZmBins S(src, nsrc), D(dst, ndst);
+    const u32 id = cv_zoom_id(offd, nc, b);
+    const u64 j = b - offd[id], ns = offs[id + 1u] - offs[id];
+    const u64 c0 = offs[id] + 4u * j, c1 = offs[id] + (4u * j + 4u < ns ? 4u * j + 4u : ns);     // (the last group may be short)
+    double sum = 0.0, sq = 0.0;
+    u32 cnt = 0;
+    float mn = 0.0f, mx = 0.0f;
+    for (u64 c = c0; c < c1; c++) {                 // in index order; an empty child adds 0.0
+        sum = sum + __longlong_as_double((long long)S.sum[c]);
+        sq = sq + __longlong_as_double((long long)S.sq[c]);
+        if (S.cnt[c]) {
+            const float lo = __uint_as_float(S.mn[c]), hi = __uint_as_float(S.mx[c]);
+            mn = cnt == 0 || lo < mn ? lo : mn;
+            mx = hi > mx ? hi : mx;
+            cnt += S.cnt[c];
+        }
+    }
+    D.sum[b] = (u64)__double_as_longlong(sum);
+    D.sq[b] = (u64)__double_as_longlong(sq);
+    D.cnt[b] = cnt;
+    D.mn[b] = __float_as_uint(mn);
+    D.mx[b] = __float_as_uint(mx);
+}
+
+// k_cv_zoom_emit over the signal's bins: min and max as they are kept, the two float64 sums rounded to float32
+__global__ void __launch_bounds__(256) k_sg_zoom_emit(u8 *__restrict__ bins, u64 n, const u64 *__restrict__ off, const u32 *__restrict__ lens,
+                                                      u32 nc, u32 z, u32 ips, const u64 *__restrict__ kbase, const u64 *__restrict__ total,
+                                                      u32 *__restrict__ out, u32 *__restrict__ table)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x, lane = t & 63u;
+    const u64 b = (u64)blockIdx.x * 256u + t;
+    const ZmBins B(bins, n);
+    const bool keep = b < n && B.cnt[b] != 0;
+    const u64 m = __ballot(keep);
+    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (!keep) return;
+    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
+    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
+    const u32 id = cv_zoom_id(off, nc, b);
+    const u64 a = (b - off[id]) * z;
+    const u32 start = (u32)a, end = a + z < (u64)lens[id] ? (u32)(a + z) : lens[id];
+    u32 *p = out + 8u * o;
+    p[0] = id;
+    p[1] = start;
+    p[2] = end;
+    p[3] = B.cnt[b];
+    p[4] = B.mn[b];
+    p[5] = B.mx[b];
+    p[6] = __float_as_uint(__double2float_rn(__longlong_as_double((long long)B.sum[b])));
+    p[7] = __float_as_uint(__double2float_rn(__longlong_as_double((long long)B.sq[b])));
+    const u64 sec = o / ips;
+    const u32 k = (u32)(o - sec * ips);
+    u32 *T = table + 5u * sec;
+    if (k == 0) {
+        T[0] = id;
+        T[1] = start;
+    }
+    if (k == ips - 1u || o + 1u == total[0]) {
+        T[2] = id;
+        T[3] = end;
+        T[4] = 32u * (k + 1u);
+    }
+}
+
+namespace {
+
+const CvKind SG_KIND = {true, "pmx_dbam_coverage_signal_", k_sg_textlen, k_sg_text};
+
+// level 0 of the signal runs: the runs of every id from the signal's ranges, then one lane per bin
+int sg_zoom_fill(pmx_dbam *b, const u32 *h_idof, const u32 *, const u64 *d_off, const u32 *d_lens, u32 z0, u64 nb0, u8 *bins, unsigned long long *)
+{
+    Coverage &c = b->cv;
+    if (!bins || !nb0) return 0;
+    if (int rc = coverage_ranges_make(b, SG_KIND)) return rc;
+    const u64 nc = c.chosen.size();
+    std::vector<u64> rng(2 * std::max<u64>(nc, 1), 0);
+    for (u64 k = 0; k < nc; k++) {
+        const u32 id = h_idof[(u64)c.chosen[k]];
+        rng[2 * id] = c.sranges[k];
+        rng[2 * id + 1] = c.sranges[k + 1];
+    }
+    DevAlloc d_rng;
+    CvHold held(b);
+    held.add(8 * rng.size());
+    HIPOK(hipMalloc(&d_rng.p, 8 * rng.size()));
+    HIPOK(hipMemcpyAsync(d_rng.p, rng.data(), 8 * rng.size(), hipMemcpyHostToDevice, b->stream));
+    const CvRuns V(c.sruns.as<u8>(), c.snruns);
+    hipLaunchKernelGGL(k_sg_zoom_fill, dim3((unsigned)((nb0 + 255) / 256)), dim3(256), 0, b->stream, V.start, V.end, V.depth, d_rng.as<u64>(), d_off, d_lens,
+                       (u32)nc, z0, nb0, bins);
+    HIPOK(hipGetLastError());
+    HIPOK(hipStreamSynchronize(b->stream));        // (rng and d_rng are locals)
+    return 0;
+}
+const CvParts SG_PARTS = {k_sg_sections, k_sg_secsums, sg_zoom_fill, k_sg_zoom_fold, k_sg_zoom_emit};
+
+void signal_drop(Coverage &c)
+{
+    if (c.zsg) zoom_drop(c);
+    c.zsg = false;
+    c.bytes -= std::min<u64>(16 * c.snruns, c.bytes);
+    c.sruns = DevAlloc{};
+    c.shave = false;
+    c.snruns = 0;
+    c.sbin = 0;
+    c.sranges.clear();
+    for (double &x : c.stot) x = 0;
+}
+
+// the work of signal behind its checks; a failure leaves no signal
+int coverage_signal_run(pmx_dbam *b, const std::string &fn, u32 bin, double scale)
+{
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    Coverage &c = b->cv;
+    const u64 n = c.nruns;
+    unsigned long long tot[3] = {0, ~0ull, 0};
+    u64 nout = 0;
+    if (n) {
+        const CvRuns V(c.runs.as<u8>(), n);
+        DevAlloc d_tot;
+        HIPOK(hipMalloc(&d_tot.p, 64));
+        HIPOK(hipMemcpyAsync(d_tot.p, tot, 24, hipMemcpyHostToDevice, st));
+        u64 *dt = d_tot.as<u64>();
+        auto out_alloc = [&](u64 m) {
+            if (hipMalloc(&c.sruns.p, 16 * m) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(m) + " runs");
+            }
+            c.snruns = m;           // (counted from here on: signal_drop takes them off again)
+            c.bytes += 16 * m;
+            if (b->st) stream_note(*b);
+            return 0;
+        };
+        if (bin == 1) {
+            if (int rc = out_alloc(n)) return rc;
+            const CvRuns O(c.sruns.as<u8>(), n);
+            hipLaunchKernelGGL(k_sg_convert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, n, scale, O.ref, O.start,
+                               O.end, O.depth, d_tot.as<unsigned long long>());
+            HIPOK(hipGetLastError());
+            nout = n;
+        } else {
+            const u64 nref = b->ref_names.size(), nc = c.chosen.size();
+            std::vector<u64> boff(nc + 1, 0), bof(std::max<u64>(nref, 1), 0);
+            std::vector<u32> lens(nc, 0);
+            std::vector<int> cref(nc, 0);
+            for (u64 k = 0; k < nc; k++) {
+                lens[k] = (u32)std::max<int64_t>(b->ref_lens[(u64)c.chosen[k]], 0);
+                cref[k] = c.chosen[k];
+                bof[(u64)c.chosen[k]] = boff[k];
+                boff[k + 1] = boff[k] + ((u64)lens[k] + bin - 1) / bin;
+            }
+            const u64 nb = boff[nc], nwg = (nb + 255) / 256;
+            if (nwg >= (1ull << 31)) return fail(PMX_DBAM_ERR_INVALID, fn + ": 2^39 bins or more");
+            DevAlloc d_geo, d_tab, d_k, d_kb, d_e;
+            CvHold held(b);
+            const u64 geo_bytes = 8 * boff.size() + 8 * bof.size() + 8 * std::max<u64>(nc, 1);
+            HIPOK(hipMalloc(&d_geo.p, geo_bytes));
+            if (hipMalloc(&d_tab.p, 8 * nb) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for the bin table: " + std::to_string(8 * nb) +
+                                                   " bytes asked for (8 per bin of " + std::to_string(bin) + " bases)");
+            }
+            held.add(geo_bytes + 8 * nb + 12 * nwg);
+            HIPOK(hipMalloc(&d_k.p, 4 * nwg));
+            HIPOK(hipMalloc(&d_kb.p, 8 * nwg));
+            u64 *d_boff = d_geo.as<u64>(), *d_bof = d_boff + boff.size();
+            u32 *d_lens = (u32 *)(d_bof + bof.size());
+            int *d_cref = (int *)(d_lens + std::max<u64>(nc, 1));
+            HIPOK(hipMemcpyAsync(d_boff, boff.data(), 8 * boff.size(), hipMemcpyHostToDevice, st));
+            HIPOK(hipMemcpyAsync(d_bof, bof.data(), 8 * bof.size(), hipMemcpyHostToDevice, st));
+            HIPOK(hipMemcpyAsync(d_lens, lens.data(), 4 * nc, hipMemcpyHostToDevice, st));
+            HIPOK(hipMemcpyAsync(d_cref, cref.data(), 4 * nc, hipMemcpyHostToDevice, st));
+            HIPOK(hipMemsetAsync(d_tab.p, 0, 8 * nb, st));
+            const SgGeo G{d_boff, d_lens, d_cref, (u32)nc, bin};
+            unsigned long long *tab = d_tab.as<unsigned long long>();
+            hipLaunchKernelGGL(k_cv_bin_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, n, d_bof, bin, tab);
+            HIPOK(hipGetLastError());
+            hipLaunchKernelGGL(k_sg_mark, dim3((unsigned)nwg), dim3(256), 0, st, tab, nb, G, d_k.as<u32>());
+            HIPOK(hipGetLastError());
+            hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), nwg, d_kb.as<u64>(), dt + 4);
+            HIPOK(hipGetLastError());
+            u64 ne = 0;
+            HIPOK(hipMemcpyAsync(&ne, dt + 4, 8, hipMemcpyDeviceToHost, st));
+            HIPOK(hipStreamSynchronize(st));       // (boff, bof, lens and cref are locals)
+            if (hipMalloc(&d_e.p, 16 * ne) != hipSuccess) {      // (ne >= 1: the first bin of the first reference that has one)
+                (void)hipGetLastError();
+                return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(ne) + " bin boundaries");
+            }
+            held.add(16 * ne);
+            unsigned long long *eS = d_e.as<unsigned long long>();
+            u32 *eid = (u32 *)(eS + ne), *ej = eid + ne;
+            hipLaunchKernelGGL(k_sg_entries, dim3((unsigned)nwg), dim3(256), 0, st, tab, nb, G, d_kb.as<u64>(), eid, ej, eS);
+            HIPOK(hipGetLastError());
+            const u64 ewg = (ne + 255) / 256;          // (ewg <= nwg: d_k and d_kb are used again)
+            hipLaunchKernelGGL(k_sg_keep, dim3((unsigned)ewg), dim3(256), 0, st, eS, ne, d_k.as<u32>());
+            HIPOK(hipGetLastError());
+            hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), ewg, d_kb.as<u64>(), dt + 6);
+            HIPOK(hipGetLastError());
+            HIPOK(hipMemcpyAsync(&nout, dt + 6, 8, hipMemcpyDeviceToHost, st));
+            HIPOK(hipStreamSynchronize(st));
+            if (nout) {
+                if (int rc = out_alloc(nout)) return rc;
+                const CvRuns O(c.sruns.as<u8>(), nout);
+                hipLaunchKernelGGL(k_sg_close, dim3((unsigned)ewg), dim3(256), 0, st, eid, ej, eS, ne, d_kb.as<u64>(), G, scale, O.ref, O.start, O.end, O.depth,
+                                   d_tot.as<unsigned long long>());
+                HIPOK(hipGetLastError());
+            }
+        }
+        HIPOK(hipMemcpyAsync(tot, d_tot.p, 24, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));            // (the table, the entries and the scans are freed behind it)
+    }
+    float lo = 0.0f, hi = 0.0f;
+    if (nout) {
+        const u32 l = (u32)tot[1], h = (u32)tot[2];
+        memcpy(&lo, &l, 4);
+        memcpy(&hi, &h, 4);
+    }
+    c.shave = true;
+    c.sbin = bin;
+    c.stot[0] = (double)nout;
+    c.stot[1] = (double)(nout ? tot[0] : 0);
+    c.stot[2] = (double)lo;
+    c.stot[3] = (double)hi;
+    return 0;
+}
+
+int coverage_signal_impl(pmx_dbam *b, uint32_t bin, double scale, double *totals)
+{
+    const std::string fn = "pmx_dbam_coverage_signal";
+    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    if (!totals) return fail(PMX_DBAM_ERR_INVALID, fn + ": null output");
+    for (int k = 0; k < 4; k++) totals[k] = 0;
+    Coverage &c = b->cv;
+    if (c.state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, fn + ": no runs: call pmx_dbam_coverage_finish first");
+    if (bin < 1 || bin > SG_MAX_BIN) return fail(PMX_DBAM_ERR_INVALID, fn + ": a bin of 1 to 65536 bases");
+    if (!std::isfinite(scale) || scale < 0x1p-64)
+        return fail(PMX_DBAM_ERR_INVALID, fn + ": the scale is a finite number of at least 2^-64 (below it a value could be a float32 denormal)");
+    if (scale * (double)c.tot[4] >= 0x1p40)
+        return fail(PMX_DBAM_ERR_INVALID, fn + ": scale * max_depth is 2^40 or more (a value's text is made in 64-bit integers)");
+    HIPOK(hipSetDevice(b->device));
+    HIPOK(hipStreamSynchronize(b->stream));
+    signal_drop(c);
+    struct Drop {       // a failure from here on leaves no signal
+        Coverage &c;
+        bool ok = false;
+        ~Drop()
+        {
+            if (!ok) signal_drop(c);
+        }
+    } drop{c};
+    if (int rc = coverage_signal_run(b, fn, bin, scale)) return rc;
+    drop.ok = true;
+    for (int k = 0; k < 4; k++) totals[k] = c.stot[k];
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pmx_dbam_coverage_signal(pmx_dbam *b, uint32_t bin, double scale, double totals[4])
+{
+    return guarded("pmx_dbam_coverage_signal", [&] { return coverage_signal_impl(b, bin, scale, totals); });
+}
+
+int pmx_dbam_coverage_signal_runs(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, float *value)
+{
+    return guarded("pmx_dbam_coverage_signal_runs", [&] { return coverage_runs_impl(b, SG_KIND, first, n, ref, start, end, (uint32_t *)value); });
+}
+
+int64_t pmx_dbam_coverage_signal_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
+{
+    return guarded("pmx_dbam_coverage_signal_text", [&] { return coverage_text_impl(b, SG_KIND, first, n, buf, cap); });
+}
+
+int64_t pmx_dbam_coverage_signal_ranges(pmx_dbam *b, int64_t *first, int64_t cap)
+{
+    return guarded("pmx_dbam_coverage_signal_ranges", [&] { return coverage_ranges_impl(b, SG_KIND, first, cap); });
+}
+
+int64_t pmx_dbam_coverage_signal_sections(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
+                                          uint32_t *table, int64_t table_cap, double *sums)
+{
+    return guarded("pmx_dbam_coverage_signal_sections", [&] {
+        return coverage_sections_impl(b, SG_KIND, SG_PARTS, first, n, chrom_id, items, buf, cap, table, table_cap, false, nullptr, sums);
+    });
+}
+
+int pmx_dbam_coverage_signal_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t out[2])
+{
+    return guarded("pmx_dbam_coverage_signal_zoom_begin", [&] { return coverage_zoom_begin_impl(b, SG_KIND, SG_PARTS, z0, levels, chrom_id, out); });
+}
+
+int64_t pmx_dbam_coverage_signal_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
+                                              int64_t table_cap)
+{
+    return guarded("pmx_dbam_coverage_signal_zoom_records",
+                   [&] { return coverage_zoom_records_impl(b, SG_KIND, SG_PARTS, level, items, buf, cap, table, table_cap); });
+}
+
+int64_t pmx_dbam_coverage_signal_sections_z(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
+                                            uint32_t *table, int64_t table_cap, uint32_t *zsizes, double *sums)
+{
+    return guarded("pmx_dbam_coverage_signal_sections_z", [&] {
+        return coverage_sections_impl(b, SG_KIND, SG_PARTS, first, n, chrom_id, items, buf, cap, table, table_cap, true, zsizes, sums);
+    });
+}
+
+int64_t pmx_dbam_coverage_signal_zoom_records_z(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
+                                                int64_t table_cap, uint32_t *zsizes)
+{
+    return guarded("pmx_dbam_coverage_signal_zoom_records_z",
+                   [&] { return coverage_zoom_records_impl(b, SG_KIND, SG_PARTS, level, items, buf, cap, table, table_cap, true, zsizes); });
+}
+
+}  // extern "C"

@@ -41,7 +41,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         fingerprint: bool = False, fingerprint_bin: int = 500, fingerprint_extend: int = 0, fingerprint_control=None,
         peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto", gc_bias=None, gc_window: int = 100,
         fragments: bool = False, fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
-        coverage_format: str = "bedgraph", coverage_compress=False):
+        coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
+        coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -96,6 +97,11 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     that file through zlib on the host (True), or (``"device"``) through the GPU's own DEFLATE encoder before it
     leaves the device, which needs device ingest (a host reader is a ValueError, not zlib); the decoded file is the same, the
     compressed bytes are not zlib's.  With ``"bedgraph"`` either is a ValueError.
+    ``coverage_bin`` (1 .. 65536), ``coverage_normalize`` (``"none"``, ``"cpm"``, ``"rpgc"``), ``coverage_scale`` and
+    ``coverage_genome_size`` (a positive integer, with ``"rpgc"`` only): when any is not its default, the file holds the signal
+    track made of the pileup -- the mean depth per bin times ``coverage.scale_of(...)``, float32, equal
+    neighbours merged, made on the GPU with device ingest -- in either format; with the defaults the file is the depth track, byte
+    for byte.
     ``gc_bias``: a genome FASTA (plain, gzip or bgzip): rank 0 also writes ``<stem>_gcbias.tab`` (pymasc_amd.gcbias, DESIGN.md
     7.19): the reads the fingerprint counts, each placed on the genome window of ``gc_window`` bases (1 .. 1024) that begins at
     its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
@@ -180,6 +186,10 @@ class _Settings:
     coverage_extend: object         # an int (0: every read's own length), or "auto": the run's fragment-length estimate
     coverage_format: str            # "bedgraph" or "bigwig"
     coverage_compress: object       # the sections of a bigWig file through zlib: False, True (on the host) or "device" (on the GPU)
+    coverage_bin: int               # the signal track: its bin, the normalisation's word, the caller's factor and
+    coverage_normalize: str         # the genome size of "rpgc" (None: the chosen references' lengths); all at their defaults: the
+    coverage_scale: float           # depth track
+    coverage_genome_size: object
     gc_bias: object                 # None, or the _GcGenome parsed once for the call
     gc_window: int
     fragments: bool
@@ -238,6 +248,10 @@ def _settings(kw: dict) -> _Settings:
     if given["coverage"] and given["coverage_compress"] == coverage.DEVICE and not ingest:     # (no silent fall-back to zlib)
         raise ValueError("coverage_compress=\"device\" needs device ingest (device_ingest=False reads on the host); "
                          "use coverage_compress=True for zlib on the host")
+    normalize = coverage.check_normalize(kw["coverage_normalize"])
+    given.update(coverage_bin=coverage.check_bin(kw["coverage_bin"]), coverage_normalize=normalize,
+                 coverage_scale=coverage.check_factor(kw["coverage_scale"]),
+                 coverage_genome_size=coverage.check_genome_size(kw["coverage_genome_size"], normalize))
     given.update(fragments=bool(kw["fragments"]), fragments_max=fragments.check_max_size(kw["fragments_max"]))
     if kw["tss"] is None and (int(kw["tss_flank"]) != tss.DEFAULT_FLANK or int(kw["tss_extend"])):
         raise ValueError("tss_flank and tss_extend need tss")
@@ -493,6 +507,18 @@ class _CoverageCount(_SideCount):
     and writes while that reader is open."""
     hooked = property(lambda self: self.s.coverage_extend != "auto")
 
+    @property
+    def signal(self) -> bool:
+        """Whether the file holds the signal track: any of its four settings is not the default."""
+        s = self.s
+        return (s.coverage_bin, s.coverage_normalize, s.coverage_scale, s.coverage_genome_size) != (1, "none", 1.0, None)
+
+    def _scale(self, totals, refs) -> float:
+        """The final scale factor from a pileup's totals (by name) and its chosen references."""
+        s = self.s
+        return coverage.scale_of(s.coverage_normalize, totals["reads"], totals["fragment_bases"], [l for _n, l in refs], s.coverage_scale,
+                                 s.coverage_genome_size)
+
     def _take(self, reader, names, acc=None, extend=None):
         """``extend`` None: the run's integer, and the reader closes before the lines are written: they are spooled."""
         from .bam_device import DeviceBamReader
@@ -505,18 +531,26 @@ class _CoverageCount(_SideCount):
                 raise ValueError("coverage_compress=\"device\" needs a device reader: this input is read on the host "
                                  "(device_ingest=False or a host reader); use coverage_compress=True for zlib on the host")
             c = coverage.from_reader(reader, mapq, names, extend, self.s.fragments_max)
-            return self._bigwig(coverage.bigwig_source(c), False) if bigwig else (extend, c.reads, c.text_chunks())
+            tail = ()
+            if self.signal:
+                c = c.signal(self.s.coverage_bin, self._scale(dict(zip(coverage.TOTALS, c.totals)), c.refs), self.s.coverage_normalize)
+                tail = (c.tail,)
+            return self._bigwig(coverage.bigwig_source(c), False) if bigwig else (extend, c.reads, c.text_chunks()) + tail
         if acc is None:             # (an armed count is not built again: its ``begin`` would zero the table)
             acc = coverage.device_count_of(reader, mapq, names, extend, self.s.fragments_max)
-        reads = acc.finish(reader)["reads"]
+        totals = acc.finish(reader)
+        reads, signal, tail = totals["reads"], self.signal, ()
+        if signal:                  # the signal runs are made on the handle, beside the depth runs
+            acc.signal(reader, self.s.coverage_bin, self._scale(totals, acc.refs), self.s.coverage_normalize)
+            tail = (coverage.signal_tail(acc.sig["bin"], acc.sig["normalize"], acc.sig["scale"]),)
         if bigwig:
-            return self._bigwig(coverage.bigwig_source(acc, reader), True)
+            return self._bigwig(coverage.bigwig_source(acc, reader, signal), True)
         if not spool:
-            return extend, reads, acc.text_chunks(reader)
+            return (extend, reads, acc.text_chunks(reader, signal=signal)) + tail
         fp = self._temporary()
-        for chunk in acc.text_chunks(reader):
+        for chunk in acc.text_chunks(reader, signal=signal):
             fp.write(chunk)
-        return extend, reads, _spooled(fp)
+        return (extend, reads, _spooled(fp)) + tail
 
     def _temporary(self):
         import tempfile
@@ -717,7 +751,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               fingerprint_extend: int = 0, fingerprint_control=None, peaks=None, peaks_extend: int = 0, coverage: bool = False,
               coverage_extend="auto", gc_bias=None, gc_window: int = 100, fragments: bool = False,
               fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
-              coverage_format: str = "bedgraph", coverage_compress=False) -> List[FileResult]:
+              coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
+              coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 

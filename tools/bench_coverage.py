@@ -10,7 +10,10 @@ for the split of the kernels; the trace is a run of its own.
 text pull, and splits its time into the section pulls, zoom begin (the fill and the folds), the record pulls and the rest, which is
 the host's assembly (R-trees, the file writes and, with --compress host, zlib); with --compress device the pulls
 are the compressed ones, pmx_dbam_coverage_sections_z / _zoom_records_z.  profiles/coverage_bigwig.json is
-python tools/bench_coverage.py --reads 20000000 --format bigwig --no-host --out profiles/coverage_bigwig.json"""
+python tools/bench_coverage.py --reads 20000000 --format bigwig --no-host --out profiles/coverage_bigwig.json
+
+--bin N / --normalize none|cpm|rpgc: with a bin above 1 or a normalisation every round also makes the signal track
+behind finish (pmx_dbam_coverage_signal, timed as "signal"), and the text pull and the bigWig file are the signal's."""
 import argparse
 import json
 import os
@@ -30,7 +33,7 @@ class _Timed:
     """A source of coverage.assemble_bigwig that adds up the time spent in each of its three kinds of calls."""
 
     def __init__(self, src):
-        self.src, self.refs, self.totals = src, src.refs, src.totals
+        self.src, self.refs, self.totals, self.bin = src, src.refs, src.totals, getattr(src, "bin", None)
         self.t = dict(sections=0.0, zoom_begin=0.0, zoom_records=0.0)
         self.pulled = dict(sections=0, zoom_records=0)      # bytes copied from the device
         self.raw = dict(sections=0, zoom_records=0)         # raw bytes of the sections they hold
@@ -81,6 +84,8 @@ def main():
     ap.add_argument("--format", choices=coverage.FORMATS, default="bedgraph", help="bigwig: also time the bigWig file of the same runs")
     ap.add_argument("--compress", nargs="?", const="host", default=None, choices=("host", "device"),
                     help="the sections of the bigWig file compressed: host (the bare flag): zlib on the host; device: on the GPU")
+    ap.add_argument("--bin", type=int, default=1, help="the signal track's bin (1 .. 65536)")
+    ap.add_argument("--normalize", choices=coverage.NORMALIZE, default="none", help="the signal track's normalisation")
     ap.add_argument("--bigwig-path", default="/tmp/pymasc_coverage_bench.bw")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -93,11 +98,12 @@ def main():
             r.decode(a.mapq, PMX_BAM_DEFAULT_EXCLUDE)
             opens.append(time.perf_counter() - t0)
     res = dict(file_reads=a.reads, mapq=a.mapq, extend=a.extend, file_to_records_s=sorted(opens))
+    signal = a.bin != 1 or a.normalize != "none"
     with DeviceBamReader(a.path) as r:
         res["kept"] = n = r.decode(a.mapq, PMX_BAM_DEFAULT_EXCLUDE)
         res["library_version"] = int(r._L.pmx_dbam_version())
         res["table_bytes"] = 4 * (sum(r.lengths) + len(r.lengths))
-        split = dict(begin=[], add=[], finish=[], text=[], whole=[])
+        split = dict(begin=[], add=[], finish=[], signal=[], text=[], whole=[])
         bw = dict(sections=[], zoom_begin=[], zoom_records=[], assembly=[], whole=[])
         for rep in range(a.reps + 1):               # (the first round warms up)
             t = [time.perf_counter()]
@@ -107,10 +113,14 @@ def main():
             t.append(time.perf_counter())
             totals = acc.finish(r)
             t.append(time.perf_counter())
-            size = sum(len(chunk) for chunk in acc.text_chunks(r))
+            if signal:
+                scale = coverage.scale_of(a.normalize, totals["reads"], totals["fragment_bases"], [l for _n, l in acc.refs])
+                res["signal"] = dict(acc.signal(r, a.bin, scale, a.normalize), bin=a.bin, normalize=a.normalize, scale=scale)
+            t.append(time.perf_counter())
+            size = sum(len(chunk) for chunk in acc.text_chunks(r, signal=signal))
             t.append(time.perf_counter())
             if a.format == "bigwig":
-                src = _Timed(coverage.bigwig_source(acc, r))
+                src = _Timed(coverage.bigwig_source(acc, r, signal))
                 t0 = time.perf_counter()
                 with open(a.bigwig_path, "w+b") as fp:
                     coverage.assemble_bigwig(fp, src, {None: False, "host": True, "device": "device"}[a.compress])
@@ -124,9 +134,9 @@ def main():
                                          section_bytes_pulled=src.pulled["sections"], record_bytes_pulled=src.pulled["zoom_records"],
                                          section_bytes_raw=src.raw["sections"], record_bytes_raw=src.raw["zoom_records"])
             if rep:
-                for k, name in enumerate(("begin", "add", "finish", "text")):
+                for k, name in enumerate(("begin", "add", "finish", "signal", "text")):
                     split[name].append(t[k + 1] - t[k])
-                split["whole"].append(t[4] - t[0])
+                split["whole"].append(t[5] - t[0])
         res.update(totals, text_bytes=size, text_chunk_runs=coverage.TEXT_CHUNK,
                    **{k + "_s": v for k, v in split.items()},              # (every round, in the order they ran)
                    **{k + "_median_s": statistics.median(v) for k, v in split.items()})
@@ -141,7 +151,7 @@ def main():
             t0 = time.perf_counter()
             host_size = sum(len(chunk) for chunk in c.text_chunks())
             res["host_text_s"] = time.perf_counter() - t0
-            assert c.totals == tuple(totals[k] for k in coverage.TOTALS) and host_size == size
+            assert c.totals == tuple(totals[k] for k in coverage.TOTALS) and (signal or host_size == size)
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as fp:
