@@ -329,6 +329,40 @@ int64_t pmx_dbam_coverage_signal_sections_z(pmx_dbam *b, int64_t first, int64_t 
 int64_t pmx_dbam_coverage_signal_zoom_records_z(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
                                                 int64_t table_cap, uint32_t *zsizes);
 
+/* Treatment against control (version >= 20): two pileups as one signal track.  `b` (the treatment) and `c` (the
+ * control) must both be in the runs state (between finish and the next begin), on the same device, with equal chosen references (the
+ * same names and lengths in the same order): PMX_DBAM_ERR_INVALID otherwise, with the condition that failed.  c == b is legal: with
+ * a_t == a_c it gives a track of zeros (ones, for ratio) over b's covered bins.
+ * The definitions.  S_t[j] and S_c[j] are the integer depth sums per bin of B bases, with the bins, the widths w_j and the bound on S
+ * of pmx_dbam_coverage_signal; B is 1 .. 65536.  Per bin, in float64, each operation rounded to nearest even on its own (no fused
+ * multiply-add):
+ *   t = (f64(S_t) * a_t) / f64(w)        c = (f64(S_c) * a_c) / f64(w)
+ *   op 2, subtract: v = f32(t - c)
+ *   op 1, ratio:    v = f32((t + p) / (c + p))
+ *   op 0, log2:     v = f32(lg2((t + p) / (c + p)))
+ * lg2(x) of a positive normal float64 is a stated algorithm, not a library call:
+ *   1. (m, e) = frexp(x), with m in [0.5, 1) (the exponent field, taken with integer operations).
+ *   2. If m < C, with C = 0.7071067811865476 (the float64 of sqrt(1/2)), then m = 2 m and e = e - 1.
+ *   3. f = m - 1.0; s = f / (2.0 + f); z = s * s.
+ *   4. P = c_10; for k = 9 .. 0: P = P * z + c_k, with c_k = 1.0 / (2 k + 1) computed as a float64 division (c_0 = 1.0); the
+ *      multiply and the add are rounded separately.
+ *   5. ln = (2.0 * s) * P; lg2 = f64(e) + ln * 1.4426950408889634.
+ * Consecutive bins of one reference are one run when they have the same S_t, the same S_c and the same width (the rule is on the
+ * sums, not on v: (3, 3) and (5, 5) both give log2 = 0 and stay two runs); bins with S_t = 0 and S_c = 0 are in no run; a bin that
+ * only the control covers is in a run.  A run is (ref, start0, end0, v), in header order.  totals = runs, covered bases, the smallest
+ * and the largest v as signed floats (0 without a run).
+ * Refused with PMX_DBAM_ERR_INVALID: an op other than 0, 1, 2; a bin outside 1 .. 65536; a factor, or for log2 / ratio p, below
+ * 2^-64 or not finite; a * max_depth >= 2^40 for either track; p >= 2^40; for ratio (a_t * max_depth_t + p) / p >= 2^40 (below that
+ * |v| * 10^6 < 2^63 and the text is integer arithmetic).  subtract ignores p.
+ * The call waits for c's stream, then works on b's.  The runs are kept on b in the signal slot -- the same four columns, replaced by
+ * the next signal, compare, begin or close -- and all eight pmx_dbam_coverage_signal_* consumers serve them: the text of a negative v
+ * is '-' followed by the text of |v|, written only when round(|v| * 10^6) is not 0 ("0", never "-0"); min and max of a zoom record
+ * are signed.  c is not changed.  Two dense u64 tables, 16 bytes per bin of every chosen reference, are held inside the call for
+ * B = 1 as for any other bin (two run lists do not line up), counted towards pmx_dbam_stream_info's peak and freed before the call
+ * returns: B = 1 on a large genome (hg38: 49 GB) runs out of device memory and returns PMX_DBAM_ERR_OPEN with the bytes asked for;
+ * the table is not tiled.  A failure leaves no signal. */
+int pmx_dbam_coverage_compare(pmx_dbam *b, pmx_dbam *c, uint32_t bin, int op, double a_t, double a_c, double pseudo, double totals[4]);
+
 /* A DEFLATE encoder on the device (version >= 18): independent chunks of at most PMX_DEFLATE_MAX_CHUNK bytes, each
  * turned into one complete zlib stream (RFC 1950 around RFC 1951): the header 0x78 with a 32-KB window and no dictionary, DEFLATE
  * blocks of which the last is marked final, the big-endian Adler-32 of the raw bytes.  Matches have length 4 .. 258 and distance

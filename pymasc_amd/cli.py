@@ -276,6 +276,16 @@ def get_parser() -> argparse.ArgumentParser:
                      help="multiply the signal track by X (above 0; default 1) on top of --coverage-normalize; implies --coverage")
     out.add_argument("--coverage-genome-size", metavar="N", type=int, action=_NaturalNumber,
                      help="the genome size of --coverage-normalize rpgc, which it needs; implies --coverage")
+    out.add_argument("--coverage-control", metavar="FILE",
+                     help="an alignment file (a regular file, not a stream) with the control's reads: the track is every input "
+                          "against it, bin by bin (--coverage-compare), both scaled by --coverage-normalize (none: the control to "
+                          "the input's number of reads), made on the GPU; its chromosomes must be the input's; implies --coverage")
+    out.add_argument("--coverage-compare", choices=("log2", "ratio", "subtract"),
+                     help="what the track holds with --coverage-control, which it needs: log2 (the default) or ratio of "
+                          "(input + pseudocount) / (control + pseudocount), or input - control")
+    out.add_argument("--coverage-pseudocount", metavar="X", type=float,
+                     help="the pseudocount of --coverage-compare log2 and ratio (at least 2^-64 and below 2^40; default 1); needs "
+                          "--coverage-control")
     out.add_argument("--gc-bias", metavar="FASTA", type=Path,
                      help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
                           "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
@@ -351,7 +361,15 @@ def parse_args(argv=None) -> argparse.Namespace:
         parser.error("argument --coverage-scale: must be a finite number above 0")
     if args.coverage_genome_size is not None and args.coverage_normalize != "rpgc":
         parser.error("argument --coverage-genome-size: needs --coverage-normalize rpgc")
-    signal = (args.coverage_bin, args.coverage_normalize, args.coverage_scale, args.coverage_genome_size)
+    if args.coverage_control is None and (args.coverage_compare is not None or args.coverage_pseudocount is not None):
+        parser.error("argument --coverage-compare / --coverage-pseudocount: needs --coverage-control")
+    if args.coverage_control is not None:
+        if args.coverage_control == "-" or not os.path.isfile(args.coverage_control):
+            parser.error("argument --coverage-control: '{}' is not a regular file".format(args.coverage_control))
+        if (args.coverage_pseudocount is not None and args.coverage_compare != "subtract"
+                and not 2.0 ** -64 <= args.coverage_pseudocount < 2.0 ** 40):
+            parser.error("argument --coverage-pseudocount: must be a finite number of at least 2^-64 and below 2^40")
+    signal = (args.coverage_bin, args.coverage_normalize, args.coverage_scale, args.coverage_genome_size, args.coverage_control)
     if args.coverage_extend is not None or args.coverage_format is not None or any(x is not None for x in signal):
         args.coverage = True
     if args.coverage_deflate is not None:
@@ -484,7 +502,8 @@ def _run(args, device, rank: int) -> int:
             extra["coverage_format"] = args.coverage_format
         if args.coverage_compress:
             extra["coverage_compress"] = "device" if args.coverage_deflate == "device" else True
-        for key in ("coverage_bin", "coverage_normalize", "coverage_scale", "coverage_genome_size"):
+        for key in ("coverage_bin", "coverage_normalize", "coverage_scale", "coverage_genome_size", "coverage_control", "coverage_compare",
+                    "coverage_pseudocount"):
             if getattr(args, key) is not None:
                 extra[key] = getattr(args, key)
     if args.fragments:

@@ -54,6 +54,30 @@ The pileup as a signal track (``--coverage-bin`` / ``--coverag
   ``k`` in index order the same way.  The records hold the four floats as float32, rounded to nearest.  Total summary:
   ``validCount = covered_bases``, min, max, then ``sum`` and ``sumSquares`` as float64: per data section its runs in order with the
   two products above from 0.0, the sections' partial sums then added in file order on the host from 0.0.
+
+Treatment against control (``--coverage-control``; ``Coverage.compare``, ``DeviceCount.compare``): two pileups
+over the same chosen references as one signal track.
+
+* ``S_t[j]`` and ``S_c[j]`` are the integer depth sums per bin of ``B`` bases of the two pileups, with the bins, the widths ``w_j``
+  and the bound on ``S`` above; ``B`` is 1 .. 65536.  ``a_t``, ``a_c`` and the pseudocount ``p`` are float64.
+* Per bin, in float64, each operation rounded to nearest even on its own (no fused multiply-add): ``t = (f64(S_t) * a_t) /
+  f64(w)``, ``c = (f64(S_c) * a_c) / f64(w)``; ``subtract``: ``v = f32(t - c)``; ``ratio``: ``v = f32((t + p) / (c + p))``;
+  ``log2``: ``v = f32(lg2((t + p) / (c + p)))``.
+* ``lg2(x)`` of a positive normal float64 is a stated algorithm (``lg2``): ``(m, e) = frexp(x)`` with ``m`` in [0.5, 1); if ``m <
+  0.7071067811865476`` (the float64 of sqrt(1/2)): ``m = 2 m``, ``e = e - 1``; ``f = m - 1.0``; ``s = f / (2.0 + f)``; ``z = s * s``;
+  ``P = c_10``, then for ``k = 9 .. 0``: ``P = P * z + c_k`` with ``c_k = 1.0 / (2 k + 1)`` as a float64 division, the multiply and
+  the add rounded separately; ``ln = (2.0 * s) * P``; ``lg2 = f64(e) + ln * 1.4426950408889634``.
+* Consecutive bins of one reference are one run when they have the same ``S_t``, the same ``S_c`` and the same width (the rule is
+  on the sums, not on ``v``); bins with both sums 0 are in no run; a bin only the control covers is in one.  Totals: ``runs``,
+  ``covered_bases``, the smallest and the largest ``v`` as signed floats.
+* Factors (``factors_of``, float64): with ``cpm`` or ``rpgc`` each track takes ``scale_of`` of its own totals; with ``none``
+  ``a_t = 1.0`` and ``a_c = reads_t / reads_c`` (both 1.0 when either has no kept read); ``coverage_scale`` then multiplies both.
+* Refused (``check_factors``, a ``ValueError``): a factor or, for ``log2`` / ``ratio``, ``p`` below 2^-64 or not finite;
+  ``a * max_depth >= 2^40`` for either track; ``p >= 2^40``; for ``ratio`` ``(a_t * max_depth_t + p) / p >= 2^40``.  ``subtract``
+  ignores ``p``.
+* bedGraph text: a negative ``v`` is ``-`` followed by the text of ``|v|``, unless that is ``0`` (never ``-0``); the track line
+  is the signal's (``scale=`` is ``a_t``) followed by `` control=<the control's basename> compare=<op> pseudocount=<repr>``.
+  bigWig: the layout and sum orders above; min and max are signed.
 """
 from __future__ import annotations
 
@@ -81,6 +105,7 @@ NORMALIZE = ("none", "cpm", "rpgc")
 MAX_BIN = 1 << 16           # the widest bin of a signal track
 MIN_SCALE, MAX_VALUE = 2.0 ** -64, 2.0 ** 40       # scale >= MIN_SCALE and scale * max_depth < MAX_VALUE
 SIGNAL_TOTALS = ("runs", "covered_bases", "min", "max")
+COMPARE = ("log2", "ratio", "subtract")     # ``coverage_compare``; an operation's index is its ``op`` of pmx_dbam_coverage_compare
 _TRACK = re.compile(r'^track type=bedGraph name="(.*)" description="pymasc_amd fragment pileup extend=(\d+|read|pair) reads=(\d+)"$')
 
 
@@ -158,8 +183,10 @@ def scale_of(normalize: str, reads: int, fragment_bases: int, lengths, coverage_
 
 def format_value(v) -> str:
     """A value as the bedGraph text holds it: the exact value of the float32 rounded to six decimals (ties to even), without
-    trailing zeros and without a trailing ``.``."""
-    return ("%.6f" % float(v)).rstrip("0").rstrip(".")
+    trailing zeros and without a trailing ``.``.  A negative value is ``-`` followed by the text of ``|v|``, unless that is ``0``
+    (never ``-0``)."""
+    text = ("%.6f" % abs(float(v))).rstrip("0").rstrip(".")
+    return "-" + text if float(v) < 0 and text != "0" else text
 
 
 def signal_tail(bin: int, normalize: str, scale: float) -> str:
@@ -167,12 +194,98 @@ def signal_tail(bin: int, normalize: str, scale: float) -> str:
     return " bin={} normalize={} scale={!r}".format(int(bin), normalize, float(scale))
 
 
+def compare_tail(control, op: str, pseudo: float) -> str:
+    """What a compared track's line has behind a signal's: the control's basename, the operation and the pseudocount."""
+    return " control={} compare={} pseudocount={!r}".format(os.path.basename(os.fspath(control)), check_compare(op), float(pseudo))
+
+
+def check_compare(op) -> str:
+    if op not in COMPARE:
+        raise ValueError("coverage_compare is \"log2\", \"ratio\" or \"subtract\"")
+    return op
+
+
+def check_pseudocount(p, op: str = "log2") -> float:
+    """``coverage_pseudocount``: for ``log2`` and ``ratio`` a finite number of at least 2^-64 and below 2^40; ``subtract`` ignores
+    it (any number)."""
+    if isinstance(p, (str, bool)):
+        raise ValueError("coverage_pseudocount is a number")
+    p = float(p)
+    if check_compare(op) == "subtract":
+        return p
+    if not np.isfinite(p) or p < MIN_SCALE:
+        raise ValueError("coverage_pseudocount is a finite number of at least 2^-64")
+    if p >= MAX_VALUE:
+        raise ValueError("coverage_pseudocount is 2^40 or more")
+    return p
+
+
+def check_factors(op: str, a_t, a_c, pseudo, max_depth_t: int = 0, max_depth_c: int = 0):
+    """(a_t, a_c, p) as ``pmx_dbam_coverage_compare`` takes them, its refusals made here for both paths: each factor by
+    ``check_scale`` with its own track's ``max_depth``, ``p`` by ``check_pseudocount``, and for ``ratio``
+    ``(a_t * max_depth_t + p) / p`` below 2^40."""
+    a_t, a_c, p = check_scale(a_t, max_depth_t), check_scale(a_c, max_depth_c), check_pseudocount(pseudo, op)
+    if op == "ratio" and (a_t * float(int(max_depth_t)) + p) / p >= MAX_VALUE:
+        raise ValueError("(factor * max_depth + pseudocount) / pseudocount is 2^40 or more (a value's text is made in 64-bit integers)")
+    return a_t, a_c, p
+
+
+def factors_of(normalize: str, totals_t, totals_c, lengths, scale: float = 1.0, genome_size=None) -> Tuple[float, float]:
+    """(a_t, a_c), float64, from the two pileups' totals by name (``reads``, ``fragment_bases``): with ``cpm`` or ``rpgc`` each
+    track takes ``scale_of`` of its own totals; with ``none`` ``a_t = 1.0`` and ``a_c = reads_t / reads_c`` (one division: the
+    control is scaled to the treatment's library size), both 1.0 when either file has no kept read; ``scale`` then multiplies
+    both."""
+    if check_normalize(normalize) != "none":
+        return tuple(scale_of(normalize, t["reads"], t["fragment_bases"], lengths, scale, genome_size) for t in (totals_t, totals_c))
+    check_genome_size(genome_size, normalize)
+    scale = check_factor(scale)
+    rt, rc = int(totals_t["reads"]), int(totals_c["reads"])
+    a_c = float(rt) / float(rc) if rt and rc else 1.0
+    return 1.0 * scale, a_c * scale
+
+
+_LG2_C = [1.0 / (2 * k + 1) for k in range(11)]
+
+
+def lg2(x):
+    """The base-2 logarithm of positive normal float64 values as the compared track states it, in numpy: every
+    operation is one float64 operation rounded on its own, so the device, this and the tests' restatement agree to the bit.
+    ``(m, e) = frexp(x)``; ``m < 0.7071067811865476``: ``m = 2 m, e = e - 1``; ``f = m - 1``; ``s = f / (2 + f)``; ``z = s * s``;
+    ``P = c_10``, ``P = P * z + c_k`` for ``k = 9 .. 0`` with ``c_k = 1 / (2 k + 1)``; ``lg2 = e + ((2 s) * P) * 1.4426950408889634``."""
+    m, e = np.frexp(np.asarray(x, dtype=np.float64))
+    low = m < 0.7071067811865476
+    m = np.where(low, 2.0 * m, m)
+    e = np.where(low, e - 1, e)
+    f = m - 1.0
+    s = f / (2.0 + f)
+    z = s * s
+    P = np.full_like(z, _LG2_C[10])
+    for k in range(9, -1, -1):
+        P = P * z
+        P = P + _LG2_C[k]
+    ln = (2.0 * s) * P
+    return e.astype(np.float64) + ln * 1.4426950408889634
+
+
+def compare_values(S_t, S_c, w, op: str, a_t: float, a_c: float, pseudo: float) -> np.ndarray:
+    """``v`` (float32) of bins with the sums ``S_t``, ``S_c`` and the widths ``w``, in the stated order of operations."""
+    w = np.asarray(w, dtype=np.float64)
+    t = (np.asarray(S_t, dtype=np.float64) * a_t) / w
+    c = (np.asarray(S_c, dtype=np.float64) * a_c) / w
+    if op == "subtract":
+        return (t - c).astype(np.float32)
+    x = (t + pseudo) / (c + pseudo)
+    return (x if op == "ratio" else lg2(x)).astype(np.float32)
+
+
 class Signal:
     """A signal track: ``runs``: ``{name: (start0, end0, value)}`` (uint32, uint32, float32) of the chosen references that have a
     run, in header order; ``bin``, ``scale``; ``refs`` as for ``Coverage``; ``reads``, ``extend`` and ``normalize`` (the word) are
     what the track line says.  Two signals are equal when their runs are, bit for bit, with ``bin`` and ``scale``."""
 
-    def __init__(self, runs, bin: int, scale: float, refs=None, reads: int = 0, extend=0, normalize: str = "none"):
+    def __init__(self, runs, bin: int, scale: float, refs=None, reads: int = 0, extend=0, normalize: str = "none", more: str = ""):
+        """``more``: what the track line says behind a signal's (``compare_tail`` of a compared track)."""
+        self.more = str(more)
         self.runs = {str(k): (np.asarray(v[0], dtype=np.uint32).ravel(), np.asarray(v[1], dtype=np.uint32).ravel(),
                               np.asarray(v[2], dtype=np.float32).ravel()) for k, v in runs.items()}
         self.bin, self.scale = check_bin(bin), float(scale)
@@ -202,7 +315,7 @@ class Signal:
                 yield "".join("{}\t{}\t{}\t{}\n".format(name, x, y, format_value(z))
                                for x, y, z in zip(s[a:a + chunk].tolist(), e[a:a + chunk].tolist(), v[a:a + chunk])).encode()
 
-    tail = property(lambda self: signal_tail(self.bin, self.normalize, self.scale))
+    tail = property(lambda self: signal_tail(self.bin, self.normalize, self.scale) + self.more)
 
     def __eq__(self, other) -> bool:
         return (isinstance(other, Signal) and (self.bin, self.scale) == (other.bin, other.scale) and list(self.runs) == list(other.runs)
@@ -265,16 +378,7 @@ class Coverage:
                 out[name] = (s, e, ((d.astype(np.float64) * scale) / 1.0).astype(np.float32))
                 continue
             length = lengths[name]
-            s, e, d = (x.astype(np.int64) for x in (s, e, d))
-            j0, j1 = s // bin, (e - 1) // bin
-            n = j1 - j0 + 1                                 # the bins of every run
-            run = np.repeat(np.arange(s.size), n)
-            j = j0[run] + np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
-            w = np.minimum(e[run], (j + 1) * bin) - np.maximum(s[run], j * bin)
-            total = np.zeros(-(-length // bin), dtype=np.int64)
-            np.add.at(total, j, w * d[run])
-            width = np.full(total.size, bin, dtype=np.int64)
-            width[-1] = length - (total.size - 1) * bin
+            total, width = self._bin_sums(name, bin, length)
             begins = np.ones(total.size, dtype=bool)
             begins[1:] = (total[1:] != total[:-1]) | (width[1:] != width[:-1])
             at = np.flatnonzero(begins)
@@ -284,6 +388,52 @@ class Coverage:
                 at, ends = at[keep], ends[keep]
                 out[name] = (at * bin, ends, ((total[at].astype(np.float64) * scale) / width[at].astype(np.float64)).astype(np.float32))
         return Signal(out, bin, scale, self.refs, self.reads, self.extend, normalize)
+
+    def _bin_sums(self, name: str, bin: int, length: int):
+        """(S, width) of every bin of ``bin`` bases of the reference ``name`` of ``length`` bases, int64: the runs are split at the
+        bin edges and their ``overlap * depth`` added per bin."""
+        total = np.zeros(-(-length // bin), dtype=np.int64)
+        width = np.full(total.size, bin, dtype=np.int64)
+        if total.size:
+            width[-1] = length - (total.size - 1) * bin
+        if name in self.runs:
+            s, e, d = (x.astype(np.int64) for x in self.runs[name])
+            j0, j1 = s // bin, (e - 1) // bin
+            n = j1 - j0 + 1                                 # the bins of every run
+            run = np.repeat(np.arange(s.size), n)
+            j = j0[run] + np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+            w = np.minimum(e[run], (j + 1) * bin) - np.maximum(s[run], j * bin)
+            np.add.at(total, j, w * d[run])
+        return total, width
+
+    def compare(self, other: "Coverage", bin: int = 1, op: str = "log2", a_t: float = 1.0, a_c: float = 1.0, pseudo: float = 1.0,
+                normalize: str = "none", control="") -> Signal:
+        """This pileup (the treatment) against ``other`` (the control) as one signal track, in numpy: the path of
+        host readers and the checker of ``pmx_dbam_coverage_compare``.  Both know the same chosen references.  Per bin ``t = (S_t *
+        a_t) / w``, ``c = (S_c * a_c) / w`` and ``v`` by ``op`` (``compare_values``); a bin begins a run where ``S_t``, ``S_c`` or
+        the width differs from the bin before; the bins with both sums 0 are in no run.  The result's ``scale`` is ``a_t``;
+        ``normalize`` and ``control`` are what the track line says."""
+        bin = check_bin(bin)
+        a_t, a_c, pseudo = check_factors(op, a_t, a_c, pseudo, self.max_depth, other.max_depth)
+        if self.refs is None or other.refs is None:
+            raise ValueError("a pileup does not know its chosen references' lengths (it was read from a bedGraph file)")
+        if self.refs != other.refs:
+            raise ValueError("the chosen references of the control differ in name, length or order")
+        out = {}
+        for name, length in self.refs:
+            if name not in self.runs and name not in other.runs:
+                continue
+            St, width = self._bin_sums(name, bin, length)
+            Sc, _w = other._bin_sums(name, bin, length)
+            begins = np.ones(St.size, dtype=bool)
+            begins[1:] = (St[1:] != St[:-1]) | (Sc[1:] != Sc[:-1]) | (width[1:] != width[:-1])
+            at = np.flatnonzero(begins)
+            ends = np.append(at[1:] * bin, length)
+            keep = (St[at] != 0) | (Sc[at] != 0)
+            at, ends = at[keep], ends[keep]
+            if at.size:
+                out[name] = (at * bin, ends, compare_values(St[at], Sc[at], width[at], op, a_t, a_c, pseudo))
+        return Signal(out, bin, a_t, self.refs, self.reads, self.extend, normalize, compare_tail(control, op, pseudo))
 
     def __eq__(self, other) -> bool:
         return (isinstance(other, Coverage) and (self.reads, self.extend) == (other.reads, other.extend)
@@ -416,6 +566,25 @@ class DeviceCount(SideAccumulator):
         if rc:
             reader._raise(rc)
         self.sig = dict(bin=bin, scale=scale, normalize=check_normalize(normalize),
+                        totals=dict(runs=int(out[0]), covered_bases=int(out[1]), min=float(out[2]), max=float(out[3])))
+        return self.sig["totals"]
+
+    def compare(self, reader, control_acc: "DeviceCount", control_reader, bin: int = 1, op: str = "log2", a_t: float = 1.0,
+                a_c: float = 1.0, pseudo: float = 1.0, normalize: str = "none", control="") -> Dict[str, float]:
+        """Makes the compared track of this pileup (the treatment) and the finished pileup ``control_acc`` on
+        ``control_reader``'s handle (``pmx_dbam_coverage_compare``) in this handle's signal slot and returns
+        its totals by name (``SIGNAL_TOTALS``): ``signal=True`` on every method below serves it.  The control's handle is
+        not changed and may be closed afterwards.  ``normalize`` and ``control``: what the track line says."""
+        bin = check_bin(bin)
+        a_t, a_c, pseudo = check_factors(op, a_t, a_c, pseudo, self.finish(reader)["max_depth"], control_acc.finish(control_reader)["max_depth"])
+        if self.refs != control_acc.refs:
+            raise ValueError("the chosen references of the control differ in name, length or order")
+        out = np.zeros(4, dtype=np.float64)
+        self.sig = None
+        rc = reader._L.pmx_dbam_coverage_compare(reader._h, control_reader._h, bin, COMPARE.index(op), a_t, a_c, pseudo, out.ctypes.data)
+        if rc:
+            reader._raise(rc)
+        self.sig = dict(bin=bin, scale=a_t, normalize=check_normalize(normalize), more=compare_tail(control, op, pseudo),
                         totals=dict(runs=int(out[0]), covered_bases=int(out[1]), min=float(out[2]), max=float(out[3])))
         return self.sig["totals"]
 
@@ -577,7 +746,8 @@ class DeviceCount(SideAccumulator):
         cut = np.flatnonzero(np.diff(ref)) + 1 if ref.size else np.zeros(0, dtype=np.int64)
         edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
         g = Signal({self.names[int(ref[a])]: (start[a:z], end[a:z], value[a:z]) for a, z in zip(edges[:-1], edges[1:])},
-                   self.sig["bin"], self.sig["scale"], self.refs, self.finish(reader)["reads"], self.extend, self.sig["normalize"])
+                   self.sig["bin"], self.sig["scale"], self.refs, self.finish(reader)["reads"], self.extend, self.sig["normalize"],
+                   self.sig.get("more", ""))
         if g.totals != tuple(self.sig["totals"][k] for k in SIGNAL_TOTALS):
             raise RuntimeError("pmx_dbam_coverage_signal: the runs do not add up to the totals")
         return g
@@ -651,7 +821,7 @@ def write_coverage(path_base, name: str, c, reader=None, signal: bool = False) -
         return write_track(path_base, name, c.extend, c.reads, c.text_chunks(), c.tail if isinstance(c, Signal) else "")
     if signal and c.sig is None:
         raise ValueError("no signal: call signal first")
-    tail = signal_tail(c.sig["bin"], c.sig["normalize"], c.sig["scale"]) if signal else ""
+    tail = signal_tail(c.sig["bin"], c.sig["normalize"], c.sig["scale"]) + c.sig.get("more", "") if signal else ""
     return write_track(path_base, name, c.extend, c.finish(reader)["reads"], c.text_chunks(reader, signal=signal), tail)
 
 

@@ -70,7 +70,8 @@ struct Coverage {
     std::vector<u64> znb, zoff;      // per level: its bins; its first byte in zbins
     u64 zbytes = 0;                  // device bytes of zbins and ztab, counted in `bytes`
     bool zsg = false;                // the bins are the signal's: f64 sums and f32 bounds in the same 28 bytes
-    // the signal track (pmx_dbam_coverage_signal, signal_device.inc; DESIGN.md 7.18.3): from signal until the next signal, begin or close
+    // the signal track (pmx_dbam_coverage_signal, signal_device.inc; DESIGN.md 7.18.3) or the compared track (pmx_dbam_coverage_compare,
+    // compare_device.inc; 7.18.4): from signal / compare until the next signal, compare, begin or close
     DevAlloc sruns;                  // u8: reference, start, end, float32 value of every signal run (the layout of `runs`)
     bool shave = false;              // a signal has been made of these runs
     u64 snruns = 0;                  // its runs

@@ -26,7 +26,7 @@
 //                    bin, S)
 //   k_sg_keep / k_bam_scan / k_sg_close     entry k ends where entry k + 1 of its reference begins, the last at the reference's
 //                    end; the entries with S = 0 are dropped by this second compaction; the totals are reduced over the wave, one
-//                    atomic each per wave, min and max of the non-negative float32 through their bits as u32
+//                    atomic each per wave, min and max of the float32 through the order-preserving map of their bits to u32
 //   k_sg_textlen / k_sg_text                k_cv_textlen / k_cv_text with the value formatted as above
 //   k_sg_sections / k_sg_secsums            one lane per run: its item; one lane per section: its two sums over its runs in order
 //   k_sg_zoom_fill   one lane per bin of level 0: a binary search for the first run of its reference that ends behind the bin's
@@ -54,10 +54,15 @@ __device__ __forceinline__ u32 sg_value(u64 S, double scale, u32 w)
     return __float_as_uint(__double2float_rn(q));
 }
 
-// covered bases, and the bits of the smallest and largest value, of the lanes that `have` a run: tot[0] +=, tot[1] = min, tot[2] = max
+// the order-preserving map of a float32's bits to u32 (all bits of a negative flipped, the top bit of a non-negative set), and back
+__host__ __device__ __forceinline__ u32 sg_key(u32 bits) { return bits & 0x80000000u ? ~bits : bits | 0x80000000u; }
+__host__ __device__ __forceinline__ u32 sg_unkey(u32 key) { return key & 0x80000000u ? key & 0x7fffffffu : ~key; }
+
+// covered bases, and the keys (sg_key) of the smallest and largest value, of the lanes that `have` a run: tot[0] +=, tot[1] = min,
+// tot[2] = max (no value is a NaN: the keys 0 and 0xffffffff stand for no lane)
 __device__ __forceinline__ void sg_totals(u32 lane, bool have, u64 width, u32 bits, unsigned long long *__restrict__ tot)
 {
-    u32 lo = have ? bits : 0xffffffffu, hi = have ? bits : 0u;
+    u32 lo = have ? sg_key(bits) : 0xffffffffu, hi = have ? sg_key(bits) : 0u;
     width = cx_wave_sum(have ? width : 0ull);
     for (int d = 32; d > 0; d >>= 1) {
         const u32 x = __shfl_xor(lo, d, 64), y = __shfl_xor(hi, d, 64);
@@ -190,9 +195,10 @@ __global__ void __launch_bounds__(256) k_sg_close(const u32 *__restrict__ eid, c
     sg_totals(lane, keep, width, bits, tot);
 }
 
-// round(v * 10^6), ties to even, of the float32 with these bits (0 <= v < 2^40), in integers
+// round(|v| * 10^6), ties to even, of the float32 with these bits (|v| < 2^40), in integers; the sign is the caller's (sg_minus)
 __device__ __forceinline__ u64 sg_micro(u32 bits)
 {
+    bits &= 0x7fffffffu;
     const u32 ex = (bits >> 23) & 255u;
     const u64 P = (u64)((bits & 0x7fffffu) | (ex ? 0x800000u : 0u)) * 1000000ull;          // m * 10^6 < 2^44; v = m * 2^e
     const int e = (int)(ex ? ex : 1u) - 150;
@@ -202,6 +208,9 @@ __device__ __forceinline__ u64 sg_micro(u32 bits)
     const u64 q = P >> sh, r = P & ((1ull << sh) - 1ull), half = 1ull << (sh - 1u);
     return q + (u64)(r > half || (r == half && (q & 1ull)));
 }
+
+// whether the text of the value begins with '-': a negative whose micro-count N is not 0 ("0", never "-0")
+__device__ __forceinline__ u32 sg_minus(u32 bits, u64 N) { return (bits >> 31) & (u32)(N != 0); }
 
 __device__ __forceinline__ u32 sg_width(u64 v)      // the decimal digits of v
 {
@@ -234,8 +243,9 @@ __global__ void __launch_bounds__(256) k_sg_textlen(const int *__restrict__ rref
         const u32 r = (u32)rref[i];
         u64 whole;
         u32 frac, nd;
-        sg_split(sg_micro(rval[i]), whole, frac, nd);
-        l = noff[r + 1u] - noff[r] + cv_width(rstart[i]) + cv_width(rend[i]) + sg_width(whole) + (nd ? nd + 1u : 0u) + 4u;
+        const u64 N = sg_micro(rval[i]);
+        sg_split(N, whole, frac, nd);
+        l = noff[r + 1u] - noff[r] + cv_width(rstart[i]) + cv_width(rend[i]) + sg_minus(rval[i], N) + sg_width(whole) + (nd ? nd + 1u : 0u) + 4u;
         len[i] = l;
     }
     l = (u32)cx_wave_sum((u64)l);
@@ -263,8 +273,9 @@ __global__ void __launch_bounds__(256) k_sg_text(const int *__restrict__ rref, c
     for (u32 c = noff[r]; c < noff[r + 1u]; c++) *p++ = names[c];
     u64 whole;
     u32 frac, nd;
-    sg_split(sg_micro(rval[i]), whole, frac, nd);
-    u8 *q = out + o + l;                // the line from its end: LF, fraction, '.', whole part, TAB, end, TAB, start, TAB
+    const u64 N = sg_micro(rval[i]);
+    sg_split(N, whole, frac, nd);
+    u8 *q = out + o + l;                // the line from its end: LF, fraction, '.', whole part, '-', TAB, end, TAB, start, TAB
     *--q = '\n';
     if (nd) {
         for (u32 c = 0; c < nd; c++) {  // (nd digits, leading zeros among them)
@@ -277,6 +288,7 @@ __global__ void __launch_bounds__(256) k_sg_text(const int *__restrict__ rref, c
         *--q = (u8)('0' + (u32)(whole % 10u));
         whole /= 10u;
     } while (whole);
+    if (sg_minus(rval[i], N)) *--q = '-';
     *--q = '\t';
     q = cv_digits(q, rend[i]);
     *--q = '\t';
@@ -365,7 +377,7 @@ __global__ void __launch_bounds__(256) k_sg_zoom_fill(const u32 *__restrict__ rs
         sum = sum + p;
         sq = sq + q;
         mn = cnt == 0 || f < mn ? f : mn;
-        mx = f > mx ? f : mx;
+        mx = cnt == 0 || f > mx ? f : mx;
         cnt += w;
     }
     B.sum[b] = (u64)__double_as_longlong(sum);
@@ -394,7 +406,7 @@ __global__ void __launch_bounds__(256) k_sg_zoom_fold(u8 *__restrict__ src, u64 
         if (S.cnt[c]) {
             const float lo = __uint_as_float(S.mn[c]), hi = __uint_as_float(S.mx[c]);
             mn = cnt == 0 || lo < mn ? lo : mn;
-            mx = hi > mx ? hi : mx;
+            mx = cnt == 0 || hi > mx ? hi : mx;
             cnt += S.cnt[c];
         }
     }
@@ -596,7 +608,7 @@ int coverage_signal_run(pmx_dbam *b, const std::string &fn, u32 bin, double scal
     }
     float lo = 0.0f, hi = 0.0f;
     if (nout) {
-        const u32 l = (u32)tot[1], h = (u32)tot[2];
+        const u32 l = sg_unkey((u32)tot[1]), h = sg_unkey((u32)tot[2]);
         memcpy(&lo, &l, 4);
         memcpy(&hi, &h, 4);
     }

@@ -42,7 +42,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         peaks=None, peaks_extend: int = 0, coverage: bool = False, coverage_extend="auto", gc_bias=None, gc_window: int = 100,
         fragments: bool = False, fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
         coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
-        coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None):
+        coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None, coverage_control=None,
+        coverage_compare: str = "log2", coverage_pseudocount: float = 1.0):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -102,6 +103,12 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     track made of the pileup -- the mean depth per bin times ``coverage.scale_of(...)``, float32, equal
     neighbours merged, made on the GPU with device ingest -- in either format; with the defaults the file is the depth track, byte
     for byte.
+    ``coverage_control``: an alignment file (a regular file, not a stream; it implies ``coverage``): the file holds the treatment
+    against the control instead -- ``coverage_compare`` ``"log2"``, ``"ratio"`` or ``"subtract"`` of the two scaled
+    mean depths per bin, with ``coverage_pseudocount`` added to both for the first two; the factors are ``coverage.factors_of``.
+    The control is piled up with the run's ``mapq_criteria``, chromosome filter, excluded regions and ``chrom_sizes`` and the
+    treatment's extend (``"pair"``: its own pairs), once for every file; its chosen references must be the treatment's
+    (ValueError).  A compare setting without a control is a ValueError.
     ``gc_bias``: a genome FASTA (plain, gzip or bgzip): rank 0 also writes ``<stem>_gcbias.tab`` (pymasc_amd.gcbias, DESIGN.md
     7.19): the reads the fingerprint counts, each placed on the genome window of ``gc_window`` bases (1 .. 1024) that begins at
     its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
@@ -138,7 +145,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         # (no name in common: ValueError before the cache pass and any table)
         mask, bam = _resolve_regions(s, s.exclude_regions, bam_path, bam)
         _lines, bam = _resolve_regions(s, s.peaks, bam_path, bam)
-        if s.fingerprint_control is not None and bam is None and is_stream(bam_path) and s.estimate_gpu is not None:
+        if ((s.fingerprint_control is not None or s.coverage_control is not None) and bam is None and is_stream(bam_path)
+                and s.estimate_gpu is not None):
             bam = open_alignments(bam_path, True, device=s.estimate_gpu)                # (no header to read apart, as above)
         _check_inputs(s, bam_path, bam)
         known = _mappable_lengths(s, read_len, track, False, mask)
@@ -190,6 +198,9 @@ class _Settings:
     coverage_normalize: str         # the genome size of "rpgc" (None: the chosen references' lengths); all at their defaults: the
     coverage_scale: float           # depth track
     coverage_genome_size: object
+    coverage_control: object        # None, or the _CoverageControl of the call: the track is the treatment against it
+    coverage_compare: str           # "log2", "ratio" or "subtract"
+    coverage_pseudocount: float
     gc_bias: object                 # None, or the _GcGenome parsed once for the call
     gc_window: int
     fragments: bool
@@ -242,7 +253,8 @@ def _settings(kw: dict) -> _Settings:
     extend = kw["coverage_extend"]
     if extend not in ("auto", coverage.PAIR) and (isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0):
         raise ValueError("coverage_extend is \"auto\", \"pair\" or an integer of at least 0")
-    given.update(coverage=bool(kw["coverage"]), coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend),
+    given.update(coverage=bool(kw["coverage"]) or kw["coverage_control"] is not None,
+                 coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend),
                  coverage_format=coverage.check_format(kw["coverage_format"], kw["coverage_compress"]),
                  coverage_compress=coverage.check_compress(kw["coverage_compress"]))
     if given["coverage"] and given["coverage_compress"] == coverage.DEVICE and not ingest:     # (no silent fall-back to zlib)
@@ -252,6 +264,14 @@ def _settings(kw: dict) -> _Settings:
     given.update(coverage_bin=coverage.check_bin(kw["coverage_bin"]), coverage_normalize=normalize,
                  coverage_scale=coverage.check_factor(kw["coverage_scale"]),
                  coverage_genome_size=coverage.check_genome_size(kw["coverage_genome_size"], normalize))
+    control, op = kw["coverage_control"], coverage.check_compare(kw["coverage_compare"])
+    if control is None and (op != "log2" or kw["coverage_pseudocount"] != 1.0):
+        raise ValueError("coverage_compare and coverage_pseudocount need coverage_control")
+    if control is not None:
+        if is_stream(control):
+            raise ValueError("coverage_control '{}' is a stream: the control is a regular file, read once per input file".format(control))
+        given.update(coverage_control=_CoverageControl(control))
+    given.update(coverage_compare=op, coverage_pseudocount=coverage.check_pseudocount(kw["coverage_pseudocount"], op))
     given.update(fragments=bool(kw["fragments"]), fragments_max=fragments.check_max_size(kw["fragments_max"]))
     if kw["tss"] is None and (int(kw["tss_flank"]) != tss.DEFAULT_FLANK or int(kw["tss_extend"])):
         raise ValueError("tss_flank and tss_extend need tss")
@@ -295,6 +315,8 @@ def _check_inputs(s: _Settings, path, bam) -> None:
     references, where the call has any of them."""
     if s.fingerprint_control is not None:
         s.fingerprint_control.check(s, path, bam)
+    if s.coverage_control is not None:
+        s.coverage_control.check(s, path, bam)
     if s.gc_bias is not None:
         s.gc_bias.check(s, path, bam)
     if s.tss is not None:
@@ -532,7 +554,10 @@ class _CoverageCount(_SideCount):
                                  "(device_ingest=False or a host reader); use coverage_compress=True for zlib on the host")
             c = coverage.from_reader(reader, mapq, names, extend, self.s.fragments_max)
             tail = ()
-            if self.signal:
+            if self.s.coverage_control is not None:
+                c = self._against(lambda r, chosen: self._compare_host(c, coverage.from_reader(r, mapq, chosen, extend, self.s.fragments_max)))
+                tail = (c.tail,)
+            elif self.signal:
                 c = c.signal(self.s.coverage_bin, self._scale(dict(zip(coverage.TOTALS, c.totals)), c.refs), self.s.coverage_normalize)
                 tail = (c.tail,)
             return self._bigwig(coverage.bigwig_source(c), False) if bigwig else (extend, c.reads, c.text_chunks()) + tail
@@ -540,7 +565,11 @@ class _CoverageCount(_SideCount):
             acc = coverage.device_count_of(reader, mapq, names, extend, self.s.fragments_max)
         totals = acc.finish(reader)
         reads, signal, tail = totals["reads"], self.signal, ()
-        if signal:                  # the signal runs are made on the handle, beside the depth runs
+        if self.s.coverage_control is not None:     # the control is piled up on a handle of its own; the track stays on this one
+            self._against(lambda r, chosen: self._compare_device(acc, reader, r, coverage.device_count_of(
+                r, mapq, chosen, extend, self.s.fragments_max)))
+            signal, tail = True, (coverage.signal_tail(acc.sig["bin"], acc.sig["normalize"], acc.sig["scale"]) + acc.sig["more"],)
+        elif signal:                # the signal runs are made on the handle, beside the depth runs
             acc.signal(reader, self.s.coverage_bin, self._scale(totals, acc.refs), self.s.coverage_normalize)
             tail = (coverage.signal_tail(acc.sig["bin"], acc.sig["normalize"], acc.sig["scale"]),)
         if bigwig:
@@ -551,6 +580,29 @@ class _CoverageCount(_SideCount):
         for chunk in acc.text_chunks(reader, signal=signal):
             fp.write(chunk)
         return (extend, reads, _spooled(fp)) + tail
+
+    def _against(self, make):
+        """``make(reader, names)`` on the control, opened as ``_count_again`` opens a file of this run and closed behind it."""
+        return _count_again(self.s, self.s.coverage_control.path, make)
+
+    def _factors(self, totals_t, totals_c, refs):
+        s = self.s
+        return coverage.factors_of(s.coverage_normalize, totals_t, totals_c, [l for _n, l in refs], s.coverage_scale, s.coverage_genome_size)
+
+    def _compare_host(self, c, control):
+        s = self.s
+        a_t, a_c = self._factors(dict(zip(coverage.TOTALS, c.totals)), dict(zip(coverage.TOTALS, control.totals)), c.refs)
+        return c.compare(control, s.coverage_bin, s.coverage_compare, a_t, a_c, s.coverage_pseudocount, s.coverage_normalize,
+                         s.coverage_control.path)
+
+    def _compare_device(self, acc, reader, control_reader, control_acc):
+        from .bam_device import DeviceBamReader
+        s = self.s
+        if not isinstance(control_reader, DeviceBamReader):
+            raise ValueError("the coverage control '{}' is read on the host and the input on the device".format(s.coverage_control.path))
+        a_t, a_c = self._factors(acc.finish(reader), control_acc.finish(control_reader), acc.refs)
+        acc.compare(reader, control_acc, control_reader, s.coverage_bin, s.coverage_compare, a_t, a_c, s.coverage_pseudocount,
+                    s.coverage_normalize, s.coverage_control.path)
 
     def _temporary(self):
         import tempfile
@@ -697,6 +749,7 @@ class _FingerprintControl:
     """``fingerprint_control``: the control file of a call's fingerprints.  ``check`` compares its chosen references with a
     sample's from the headers alone; ``counts`` is its table, counted once per call (by rank 0, when the first table is written)
     with the run's ``mapq_criteria``, chromosome filter, excluded regions and ``chrom_sizes``.  It is never correlated."""
+    label = "fingerprint control"       # what ``check`` calls the file
 
     def __init__(self, path):
         self.path = os.fspath(path)
@@ -721,8 +774,8 @@ class _FingerprintControl:
             with open_header(path, s.chrom_sizes) as h:
                 mine = self._chosen_of(s, h)
         if mine != self._chosen:
-            raise ValueError("the chosen references of the fingerprint control '{}' differ from those of '{}' in name or length"
-                             "".format(self.path, path))
+            raise ValueError("the chosen references of the {} '{}' differ from those of '{}' in name or length"
+                             "".format(self.label, self.path, path))
 
     def counts(self, s: _Settings):
         from . import fingerprint
@@ -730,6 +783,12 @@ class _FingerprintControl:
             self._counts = _count_again(s, self.path, lambda r, names: fingerprint.from_reader(
                 r, int(s.mapq_criteria), names, s.fingerprint_bin, s.fingerprint_extend))
         return self._counts
+
+
+class _CoverageControl(_FingerprintControl):
+    """``coverage_control``: the control file of a call's compared tracks, checked from the headers as the
+    fingerprint's is.  It is piled up again for every file (``_CoverageCount._against``): nothing of it is kept between files."""
+    label = "coverage control"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -752,7 +811,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               coverage_extend="auto", gc_bias=None, gc_window: int = 100, fragments: bool = False,
               fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
               coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
-              coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None) -> List[FileResult]:
+              coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None, coverage_control=None,
+              coverage_compare: str = "log2", coverage_pseudocount: float = 1.0) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 

@@ -13,8 +13,14 @@ are the compressed ones, pmx_dbam_coverage_sections_z / _zoom_records_z.  profil
 python tools/bench_coverage.py --reads 20000000 --format bigwig --no-host --out profiles/coverage_bigwig.json
 
 --bin N / --normalize none|cpm|rpgc: with a bin above 1 or a normalisation every round also makes the signal track
-behind finish (pmx_dbam_coverage_signal, timed as "signal"), and the text pull and the bigWig file are the signal's."""
+behind finish (pmx_dbam_coverage_signal, timed as "signal"), and the text pull and the bigWig file are the signal's.
+
+--control FILE [--compare log2|ratio|subtract]: a second synthetic file (made with another seed and
+--control-reads reads when it does not exist) is decoded once; every round then piles it up on its own handle behind the signal (begin
++ add + finish, timed as "control") and makes the compared track (pmx_dbam_coverage_compare, timed as "compare") in place of the
+signal, so "compare" stands beside "signal" on the same pileup, and the text pull and the bigWig file are the compared track's."""
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -86,11 +92,16 @@ def main():
                     help="the sections of the bigWig file compressed: host (the bare flag): zlib on the host; device: on the GPU")
     ap.add_argument("--bin", type=int, default=1, help="the signal track's bin (1 .. 65536)")
     ap.add_argument("--normalize", choices=coverage.NORMALIZE, default="none", help="the signal track's normalisation")
+    ap.add_argument("--control", default=None, help="a control file: every round also makes the treatment against it")
+    ap.add_argument("--control-reads", type=int, default=None, help="the reads of a control made here (default: half of --reads)")
+    ap.add_argument("--compare", choices=coverage.COMPARE, default="log2", help="the operation with --control")
     ap.add_argument("--bigwig-path", default="/tmp/pymasc_coverage_bench.bw")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not os.path.exists(a.path):
         synth_bam(a.path, a.reads)
+    if a.control is not None and not os.path.exists(a.control):
+        synth_bam(a.control, a.control_reads or a.reads // 2, seed=2)
     opens = []
     for _ in range(0 if a.no_open else 3):
         t0 = time.perf_counter()
@@ -98,12 +109,17 @@ def main():
             r.decode(a.mapq, PMX_BAM_DEFAULT_EXCLUDE)
             opens.append(time.perf_counter() - t0)
     res = dict(file_reads=a.reads, mapq=a.mapq, extend=a.extend, file_to_records_s=sorted(opens))
-    signal = a.bin != 1 or a.normalize != "none"
-    with DeviceBamReader(a.path) as r:
+    signal = a.bin != 1 or a.normalize != "none" or a.control is not None
+    with contextlib.ExitStack() as stack:
+        r = stack.enter_context(DeviceBamReader(a.path))
+        rc = None if a.control is None else stack.enter_context(DeviceBamReader(a.control))
+        if rc is not None:
+            res["control_kept"] = rc.decode(a.mapq, PMX_BAM_DEFAULT_EXCLUDE)
         res["kept"] = n = r.decode(a.mapq, PMX_BAM_DEFAULT_EXCLUDE)
         res["library_version"] = int(r._L.pmx_dbam_version())
         res["table_bytes"] = 4 * (sum(r.lengths) + len(r.lengths))
         split = dict(begin=[], add=[], finish=[], signal=[], text=[], whole=[])
+        versus = dict(control=[], compare=[])
         bw = dict(sections=[], zoom_begin=[], zoom_records=[], assembly=[], whole=[])
         for rep in range(a.reps + 1):               # (the first round warms up)
             t = [time.perf_counter()]
@@ -117,6 +133,18 @@ def main():
                 scale = coverage.scale_of(a.normalize, totals["reads"], totals["fragment_bases"], [l for _n, l in acc.refs])
                 res["signal"] = dict(acc.signal(r, a.bin, scale, a.normalize), bin=a.bin, normalize=a.normalize, scale=scale)
             t.append(time.perf_counter())
+            if rc is not None:                      # the control's pileup on its own handle, then the compared track in the signal's place
+                cacc = coverage.DeviceCount(rc, a.mapq, None, a.extend)
+                cacc.add(rc)
+                ctotals = cacc.finish(rc)
+                t1 = time.perf_counter()
+                a_t, a_c = coverage.factors_of(a.normalize, totals, ctotals, [l for _n, l in acc.refs])
+                res["compare"] = dict(acc.compare(r, cacc, rc, a.bin, a.compare, a_t, a_c, 1.0, a.normalize, a.control), bin=a.bin, op=a.compare,
+                                      normalize=a.normalize, a_t=a_t, a_c=a_c, control_totals=ctotals)
+                t2 = time.perf_counter()
+                if rep:
+                    versus["control"].append(t1 - t[4])
+                    versus["compare"].append(t2 - t1)
             size = sum(len(chunk) for chunk in acc.text_chunks(r, signal=signal))
             t.append(time.perf_counter())
             if a.format == "bigwig":
@@ -137,6 +165,10 @@ def main():
                 for k, name in enumerate(("begin", "add", "finish", "signal", "text")):
                     split[name].append(t[k + 1] - t[k])
                 split["whole"].append(t[5] - t[0])
+                if rc is not None:                  # (the text pull begins behind compare)
+                    split["text"][-1] -= versus["control"][-1] + versus["compare"][-1]
+        if rc is not None:
+            split.update(versus)
         res.update(totals, text_bytes=size, text_chunk_runs=coverage.TEXT_CHUNK,
                    **{k + "_s": v for k, v in split.items()},              # (every round, in the order they ran)
                    **{k + "_median_s": statistics.median(v) for k, v in split.items()})
