@@ -363,6 +363,40 @@ int64_t pmx_dbam_coverage_signal_zoom_records_z(pmx_dbam *b, uint32_t level, uin
  * the table is not tiled.  A failure leaves no signal. */
 int pmx_dbam_coverage_compare(pmx_dbam *b, pmx_dbam *c, uint32_t bin, int op, double a_t, double a_c, double pseudo, double totals[4]);
 
+/* Peaks called from the signal track (version >= 21): a threshold caller over the signal runs on the handle, the
+ * result of pmx_dbam_coverage_signal or pmx_dbam_coverage_compare.  The definitions are this project's own; nothing here was
+ * compared with MACS2.
+ * The input.  The signal runs (ref, start0, end0, v), in header order; within a reference they ascend and do not overlap, and the
+ * bases in no run are uncovered.  cutoff is a finite float64 (negative is legal), max_gap an integer 0 .. 2^31 - 1, min_length an
+ * integer 1 .. 2^31 - 1: PMX_DBAM_ERR_INVALID otherwise.  Values compare as floats: f64(v) against cutoff and f64(v) against f64(v');
+ * -0.0 equals 0.0.
+ * Passing.  A run passes when f64(v) >= cutoff.  Equality passes.
+ * Chains.  Take the passing runs of one reference in order.  Two consecutive passing runs a, b are linked when
+ * b.start0 - a.end0 <= max_gap, whatever lies between them (failing runs or uncovered bases).  Runs of different references are never
+ * linked.  A candidate is a maximal chain: its start is the first run's start0, its end the last run's end0.
+ * Peaks.  A candidate is a peak when end - start >= min_length.  Peaks are in header order, then ascending.
+ * Per peak.  value: the largest v of its passing runs, float32.  summit = s + (e - s) / 2 (integer division), where (s, e) is the
+ * FIRST passing run with that value; the position is 0-based.  runs: the number of its passing runs.  Only integers, a maximum and a
+ * first-argmax appear, so every reduction is associative and the result does not depend on scheduling; a mean or an area over the
+ * peak would be a float sum in some order and is left out.
+ * totals = passing runs, candidates, peaks, peak bases (end - start summed over the peaks), passing bases (the widths of the passing
+ * runs inside peaks).
+ * The narrowPeak line of peak number n, 1-based in file order (first + i + 1 of a pull), no header line:
+ *   chrom TAB start TAB end TAB peak_<n> TAB score TAB . TAB value TAB -1 TAB -1 TAB (summit - start) LF
+ * score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0)), the product exact in float64; value is written as the signal's text
+ * writes it: six decimals, ties to even, '-' only when the rounded micro-count is not 0.
+ * call without a signal on the handle is PMX_DBAM_ERR_INVALID (call signal or compare first).  The peak table (reference, start, end,
+ * summit, value, runs: 24 bytes per peak) is kept on the handle, counted towards pmx_dbam_stream_info's peak, and dropped by the next
+ * call, signal, compare, begin or close; call_rows and call_text after one of those are PMX_DBAM_ERR_INVALID.  The signal runs and
+ * the depth runs are not changed.  Inside call 12 bytes per 256 signal runs and 4 per passing run, candidate and peak are held and
+ * freed before it returns; a failure leaves no peak table and the signal as it was.  Refused: 2^32 signal runs or more.
+ * call_rows copies the peaks [first, first + n); call_text formats their lines on the device (buf NULL: the size; a cap below it:
+ * PMX_DBAM_ERR_INVALID), with the range rules of pmx_dbam_coverage_signal_runs / _text. */
+int pmx_dbam_coverage_call(pmx_dbam *b, double cutoff, uint32_t max_gap, uint32_t min_length, uint64_t totals[5]);
+int pmx_dbam_coverage_call_rows(pmx_dbam *b, int64_t first, int64_t n, int32_t *ref, uint32_t *start, uint32_t *end, uint32_t *summit,
+                                float *value, uint32_t *runs);
+int64_t pmx_dbam_coverage_call_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap);
+
 /* A DEFLATE encoder on the device (version >= 18): independent chunks of at most PMX_DEFLATE_MAX_CHUNK bytes, each
  * turned into one complete zlib stream (RFC 1950 around RFC 1951): the header 0x78 with a 32-KB window and no dictionary, DEFLATE
  * blocks of which the last is marked final, the big-endian Adler-32 of the raw bytes.  Matches have length 4 .. 258 and distance

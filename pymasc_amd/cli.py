@@ -286,6 +286,15 @@ def get_parser() -> argparse.ArgumentParser:
     out.add_argument("--coverage-pseudocount", metavar="X", type=float,
                      help="the pseudocount of --coverage-compare log2 and ratio (at least 2^-64 and below 2^40; default 1); needs "
                           "--coverage-control")
+    out.add_argument("--coverage-call", metavar="X", type=float,
+                     help="also write <name>_coverage_peaks.narrowPeak: the peaks of the track the coverage file holds (depth, signal or "
+                          "treatment against control), called on the GPU -- runs of at least X (any finite number), linked over gaps "
+                          "of at most --coverage-call-gap bases and kept from --coverage-call-length bases; the score is the track's "
+                          "value, no p-value is computed, and --peaks reads the file in a second run; implies --coverage")
+    out.add_argument("--coverage-call-gap", metavar="N", type=int,
+                     help="the largest gap between two runs of one peak (0 .. 2^31 - 1; default 30); needs --coverage-call")
+    out.add_argument("--coverage-call-length", metavar="N", type=int,
+                     help="the smallest peak (1 .. 2^31 - 1; default 200); needs --coverage-call")
     out.add_argument("--gc-bias", metavar="FASTA", type=Path,
                      help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
                           "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
@@ -369,7 +378,17 @@ def parse_args(argv=None) -> argparse.Namespace:
         if (args.coverage_pseudocount is not None and args.coverage_compare != "subtract"
                 and not 2.0 ** -64 <= args.coverage_pseudocount < 2.0 ** 40):
             parser.error("argument --coverage-pseudocount: must be a finite number of at least 2^-64 and below 2^40")
-    signal = (args.coverage_bin, args.coverage_normalize, args.coverage_scale, args.coverage_genome_size, args.coverage_control)
+    if args.coverage_call is None and (args.coverage_call_gap is not None or args.coverage_call_length is not None):
+        parser.error("argument --coverage-call-gap / --coverage-call-length: needs --coverage-call")
+    if args.coverage_call is not None:
+        if not float("-inf") < args.coverage_call < float("inf"):
+            parser.error("argument --coverage-call: must be a finite number")
+        if args.coverage_call_gap is not None and not 0 <= args.coverage_call_gap < 1 << 31:
+            parser.error("argument --coverage-call-gap: must lie in [0, 2^31 - 1]")
+        if args.coverage_call_length is not None and not 1 <= args.coverage_call_length < 1 << 31:
+            parser.error("argument --coverage-call-length: must lie in [1, 2^31 - 1]")
+    signal = (args.coverage_bin, args.coverage_normalize, args.coverage_scale, args.coverage_genome_size, args.coverage_control,
+              args.coverage_call)
     if args.coverage_extend is not None or args.coverage_format is not None or any(x is not None for x in signal):
         args.coverage = True
     if args.coverage_deflate is not None:
@@ -503,7 +522,7 @@ def _run(args, device, rank: int) -> int:
         if args.coverage_compress:
             extra["coverage_compress"] = "device" if args.coverage_deflate == "device" else True
         for key in ("coverage_bin", "coverage_normalize", "coverage_scale", "coverage_genome_size", "coverage_control", "coverage_compare",
-                    "coverage_pseudocount"):
+                    "coverage_pseudocount", "coverage_call", "coverage_call_gap", "coverage_call_length"):
             if getattr(args, key) is not None:
                 extra[key] = getattr(args, key)
     if args.fragments:

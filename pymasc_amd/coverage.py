@@ -78,6 +78,28 @@ over the same chosen references as one signal track.
 * bedGraph text: a negative ``v`` is ``-`` followed by the text of ``|v|``, unless that is ``0`` (never ``-0``); the track line
   is the signal's (``scale=`` is ``a_t``) followed by `` control=<the control's basename> compare=<op> pseudocount=<repr>``.
   bigWig: the layout and sum orders above; min and max are signed.
+
+Peaks called from the track (``--coverage-call``; ``Signal.call``, ``DeviceCount.call``, ``Peaks``): a threshold
+caller over the signal runs, whichever of the above made them.  The definitions are this project's own: nothing here was compared
+with MACS2.
+
+* The input is the runs ``(ref, start0, end0, v)`` of a track: within a reference they ascend and do not overlap, and the bases in
+  no run are uncovered.  ``cutoff`` is a finite float64 (negative is legal), ``max_gap`` an integer 0 .. 2^31 - 1, ``min_length`` an
+  integer 1 .. 2^31 - 1 (``check_call``).  Values compare as floats: ``f64(v)`` against ``cutoff`` and ``f64(v)`` against
+  ``f64(v')``; ``-0.0`` equals ``0.0``.
+* A run passes when ``f64(v) >= cutoff``; equality passes.
+* Take the passing runs of one reference in order.  Two consecutive passing runs ``a``, ``b`` are linked when ``b.start0 - a.end0
+  <= max_gap``, whatever lies between them (failing runs or uncovered bases); runs of different references are never linked.  A
+  candidate is a maximal chain: ``start`` is its first run's ``start0``, ``end`` its last run's ``end0``.
+* A candidate is a peak when ``end - start >= min_length``.  Peaks are in header order, then ascending.
+* Per peak: ``value``, the largest ``v`` of its passing runs, float32; ``summit = s + (e - s) // 2``, 0-based, where ``(s, e)`` is
+  the first passing run with that value; ``runs``, the number of its passing runs.  Only integers, a maximum and a first-argmax
+  appear, so the result does not depend on any order; a mean or an area over a peak would be a float sum and is left out.
+* Totals (``CALL_TOTALS``): ``passing_runs``, ``candidates``, ``peaks``, ``peak_bases`` (``end - start`` over the peaks),
+  ``passing_bases`` (the widths of the passing runs inside peaks).
+* The file is ``<name>_coverage_peaks.narrowPeak``, without a header line, one line per peak: ``chrom``, ``start``, ``end``,
+  ``peak_<n>`` (``n`` 1-based in file order), ``score``, ``.``, ``value``, ``-1``, ``-1``, ``summit - start``, TAB-separated.
+  ``score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0))`` (``call_score``); ``value`` is written by ``format_value``.
 """
 from __future__ import annotations
 
@@ -106,6 +128,10 @@ MAX_BIN = 1 << 16           # the widest bin of a signal track
 MIN_SCALE, MAX_VALUE = 2.0 ** -64, 2.0 ** 40       # scale >= MIN_SCALE and scale * max_depth < MAX_VALUE
 SIGNAL_TOTALS = ("runs", "covered_bases", "min", "max")
 COMPARE = ("log2", "ratio", "subtract")     # ``coverage_compare``; an operation's index is its ``op`` of pmx_dbam_coverage_compare
+CALL_SUFFIX = "_coverage_peaks.narrowPeak"
+CALL_TOTALS = ("passing_runs", "candidates", "peaks", "peak_bases", "passing_bases")
+CALL_GAP, CALL_LENGTH = 30, 200             # the defaults of ``coverage_call_gap`` and ``coverage_call_length``
+MAX_CALL_INT = (1 << 31) - 1                # the largest ``max_gap`` and ``min_length``
 _TRACK = re.compile(r'^track type=bedGraph name="(.*)" description="pymasc_amd fragment pileup extend=(\d+|read|pair) reads=(\d+)"$')
 
 
@@ -278,6 +304,77 @@ def compare_values(S_t, S_c, w, op: str, a_t: float, a_c: float, pseudo: float) 
     return (x if op == "ratio" else lg2(x)).astype(np.float32)
 
 
+def check_call(cutoff, max_gap=30, min_length=200) -> Tuple[float, int, int]:
+    """(cutoff, max_gap, min_length) as the peak caller takes them (the refusals of ``pmx_dbam_coverage_call``, made here for both
+    paths): a finite number (negative is legal), an integer from 0 to 2^31 - 1, an integer from 1 to 2^31 - 1."""
+    if isinstance(cutoff, (str, bool)) or cutoff is None:
+        raise ValueError("coverage_call (the cutoff) is a number")
+    try:
+        cutoff = float(cutoff)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("coverage_call (the cutoff) is a number") from None
+    if not np.isfinite(cutoff):
+        raise ValueError("coverage_call (the cutoff) is a finite number")
+    for what, x, low in (("coverage_call_gap", max_gap, 0), ("coverage_call_length", min_length, 1)):
+        try:
+            ok = not isinstance(x, (str, bool)) and int(x) == x and low <= int(x) <= MAX_CALL_INT
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("{} is an integer from {} to 2^31 - 1".format(what, low))
+    return cutoff, int(max_gap), int(min_length)
+
+
+def call_score(value) -> np.ndarray:
+    """The narrowPeak score of float32 values: ``trunc(min(max(f64(value) * 10.0, 0.0), 1000.0))``, int64."""
+    x = np.asarray(value, dtype=np.float32).astype(np.float64) * 10.0
+    return np.trunc(np.minimum(np.maximum(x, 0.0), 1000.0)).astype(np.int64)
+
+
+class Peaks:
+    """The peaks called from a signal track: ``rows``: ``{name: (start, end, summit, value, runs)}`` (uint32,
+    uint32, uint32, float32, uint32) of the references that have a peak, in header order; ``cutoff``, ``max_gap``, ``min_length``;
+    ``totals``: by name (``CALL_TOTALS``).  Two are equal when their rows are, bit for bit, with the three parameters and the
+    totals."""
+
+    def __init__(self, rows, cutoff: float, max_gap: int, min_length: int, totals):
+        types = (np.uint32, np.uint32, np.uint32, np.float32, np.uint32)
+        self.rows = {str(k): tuple(np.asarray(x, dtype=t).ravel() for x, t in zip(v, types)) for k, v in rows.items()}
+        self.cutoff, self.max_gap, self.min_length = check_call(cutoff, max_gap, min_length)
+        self.totals = {k: int(totals[k]) for k in CALL_TOTALS}
+        if any(len(v) != 5 or not (v[0].size == v[1].size == v[2].size == v[3].size == v[4].size > 0) for v in self.rows.values()):
+            raise ValueError("every reference has five columns of one length, and at least one peak")
+
+    n_peaks = property(lambda self: sum(int(v[0].size) for v in self.rows.values()))
+    peak_bases = property(lambda self: sum(int((e.astype(np.int64) - s.astype(np.int64)).sum()) for s, e, *_x in self.rows.values()))
+
+    def lines(self):
+        """``{name: [(start, end), ...]}`` of the peaks, in file order: what ``peaks.open_peaks`` takes."""
+        return {n: list(zip(v[0].tolist(), v[1].tolist())) for n, v in self.rows.items()}
+
+    def text_chunks(self, chunk: int = 1 << 16) -> Iterator[bytes]:
+        """The narrowPeak lines, ``chunk`` peaks at a time; the peak numbers run through the file."""
+        no = 0
+        for name, (s, e, m, v, _r) in self.rows.items():
+            for a in range(0, s.size, chunk):
+                z = slice(a, a + chunk)
+                yield "".join("{}\t{}\t{}\tpeak_{}\t{}\t.\t{}\t-1\t-1\t{}\n".format(name, x, y, no + a + i + 1, sc, format_value(val), c - x)
+                               for i, (x, y, c, val, sc) in enumerate(zip(s[z].tolist(), e[z].tolist(), m[z].tolist(), v[z],
+                                                                          call_score(v[z]).tolist()))).encode()
+            no += s.size
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, Peaks) and (self.cutoff, self.max_gap, self.min_length) == (other.cutoff, other.max_gap, other.min_length)
+                and self.totals == other.totals and list(self.rows) == list(other.rows)
+                and all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for k in self.rows for a, b in zip(self.rows[k], other.rows[k])))
+
+    __hash__ = None
+
+    def __repr__(self) -> str:
+        return "Peaks(cutoff={!r}, max_gap={}, min_length={}, {})".format(self.cutoff, self.max_gap, self.min_length,
+                                                                          ", ".join("{}={}".format(k, v) for k, v in self.totals.items()))
+
+
 class Signal:
     """A signal track: ``runs``: ``{name: (start0, end0, value)}`` (uint32, uint32, float32) of the chosen references that have a
     run, in header order; ``bin``, ``scale``; ``refs`` as for ``Coverage``; ``reads``, ``extend`` and ``normalize`` (the word) are
@@ -316,6 +413,41 @@ class Signal:
                                for x, y, z in zip(s[a:a + chunk].tolist(), e[a:a + chunk].tolist(), v[a:a + chunk])).encode()
 
     tail = property(lambda self: signal_tail(self.bin, self.normalize, self.scale) + self.more)
+
+    def call(self, cutoff, max_gap: int = CALL_GAP, min_length: int = CALL_LENGTH) -> Peaks:
+        """The peaks of the track, in numpy: the path of host readers and the checker of
+        ``pmx_dbam_coverage_call``.  A run passes when ``f64(v) >= cutoff``; consecutive passing runs of a reference are linked
+        when the second begins at most ``max_gap`` bases behind the first's end; a maximal chain of at least ``min_length`` bases
+        from its first start to its last end is a peak, with the largest ``v`` of its passing runs, the middle ``s + (e - s) // 2``
+        of the first run that has it, and the number of its passing runs."""
+        cutoff, max_gap, min_length = check_call(cutoff, max_gap, min_length)
+        rows, tot = {}, dict.fromkeys(CALL_TOTALS, 0)
+        for name, (s, e, v) in self.runs.items():
+            at = np.flatnonzero(v.astype(np.float64) >= cutoff)
+            if not at.size:
+                continue
+            ps, pe, pv = s[at].astype(np.int64), e[at].astype(np.int64), v[at]
+            begins = np.ones(at.size, dtype=bool)
+            begins[1:] = ps[1:] - pe[:-1] > max_gap
+            first = np.flatnonzero(begins)
+            count = np.diff(np.append(first, at.size))
+            start, end = ps[first], pe[first + count - 1]
+            tot["passing_runs"] += int(at.size)
+            tot["candidates"] += int(first.size)
+            keep = end - start >= min_length
+            if not keep.any():
+                continue
+            f64 = pv.astype(np.float64)
+            top = np.repeat(np.maximum.reduceat(f64, first), count)
+            hit = np.flatnonzero(f64 == top)                     # (-0.0 == 0.0; every chain has one)
+            chain = np.repeat(np.arange(first.size), count)
+            _c, where = np.unique(chain[hit], return_index=True)    # the first hit of every chain
+            arg = hit[where][keep]
+            rows[name] = (start[keep], end[keep], ps[arg] + (pe[arg] - ps[arg]) // 2, pv[arg], count[keep])
+            tot["peaks"] += int(keep.sum())
+            tot["peak_bases"] += int((end - start)[keep].sum())
+            tot["passing_bases"] += int(np.add.reduceat(pe - ps, first)[keep].sum())
+        return Peaks(rows, cutoff, max_gap, min_length, tot)
 
     def __eq__(self, other) -> bool:
         return (isinstance(other, Signal) and (self.bin, self.scale) == (other.bin, other.scale) and list(self.runs) == list(other.runs)
@@ -435,6 +567,10 @@ class Coverage:
                 out[name] = (at * bin, ends, compare_values(St[at], Sc[at], width[at], op, a_t, a_c, pseudo))
         return Signal(out, bin, a_t, self.refs, self.reads, self.extend, normalize, compare_tail(control, op, pseudo))
 
+    def call(self, cutoff, max_gap: int = CALL_GAP, min_length: int = CALL_LENGTH) -> Peaks:
+        """The peaks of the depth track: ``Signal.call`` of the signal at bin 1 and scale 1.0."""
+        return self.signal(1, 1.0).call(cutoff, max_gap, min_length)
+
     def __eq__(self, other) -> bool:
         return (isinstance(other, Coverage) and (self.reads, self.extend) == (other.reads, other.extend)
                 and list(self.runs) == list(other.runs)
@@ -529,7 +665,7 @@ class DeviceCount(SideAccumulator):
     def begin(self, reader) -> None:
         """A zeroed table on the reader's handle (a stream reader calls it again when a pass opens a new handle)."""
         mask = np.ascontiguousarray(self.use, dtype=np.uint8) if self.names else np.zeros(1, dtype=np.uint8)
-        self.totals = self.sig = None
+        self.totals = self.sig = self.called = None
         rc = reader._L.pmx_dbam_coverage_begin(reader._h, 0 if self.extend == PAIR else self.extend, mask.ctypes.data)
         if rc:
             reader._raise(rc)
@@ -561,7 +697,7 @@ class DeviceCount(SideAccumulator):
         ``normalize``: the word the track line says."""
         bin, scale = check_bin(bin), check_scale(scale, self.finish(reader)["max_depth"])
         out = np.zeros(4, dtype=np.float64)
-        self.sig = None
+        self.sig = self.called = None
         rc = reader._L.pmx_dbam_coverage_signal(reader._h, bin, scale, out.ctypes.data)
         if rc:
             reader._raise(rc)
@@ -580,7 +716,7 @@ class DeviceCount(SideAccumulator):
         if self.refs != control_acc.refs:
             raise ValueError("the chosen references of the control differ in name, length or order")
         out = np.zeros(4, dtype=np.float64)
-        self.sig = None
+        self.sig = self.called = None
         rc = reader._L.pmx_dbam_coverage_compare(reader._h, control_reader._h, bin, COMPARE.index(op), a_t, a_c, pseudo, out.ctypes.data)
         if rc:
             reader._raise(rc)
@@ -751,6 +887,70 @@ class DeviceCount(SideAccumulator):
         if g.totals != tuple(self.sig["totals"][k] for k in SIGNAL_TOTALS):
             raise RuntimeError("pmx_dbam_coverage_signal: the runs do not add up to the totals")
         return g
+
+    def call(self, reader, cutoff, max_gap: int = CALL_GAP, min_length: int = CALL_LENGTH) -> Dict[str, int]:
+        """Calls the peaks of the signal runs on the handle (``pmx_dbam_coverage_call``) and returns the totals by
+        name (``CALL_TOTALS``); the peak table stays on the handle until the next ``call``, ``signal``, ``compare`` or ``begin``.
+        A handle without a signal gets ``signal(reader, 1, 1.0)`` first: the peaks of the depth track."""
+        cutoff, max_gap, min_length = check_call(cutoff, max_gap, min_length)
+        if self.sig is None:
+            self.signal(reader, 1, 1.0)
+        out = np.zeros(5, dtype=np.uint64)
+        self.called = None
+        rc = reader._L.pmx_dbam_coverage_call(reader._h, cutoff, max_gap, min_length, out.ctypes.data)
+        if rc:
+            reader._raise(rc)
+        self.called = dict(cutoff=cutoff, max_gap=max_gap, min_length=min_length, totals=dict(zip(CALL_TOTALS, (int(x) for x in out))))
+        return self.called["totals"]
+
+    def _peaks(self) -> int:
+        if self.called is None:
+            raise ValueError("no peaks: call call first")
+        return self.called["totals"]["peaks"]
+
+    def call_rows(self, reader, first: int = 0, n=None):
+        """(reference int32, start, end, summit uint32, value float32, runs uint32) of the peaks ``[first, first + n)``
+        (``pmx_dbam_coverage_call_rows``)."""
+        n = self._peaks() - int(first) if n is None else int(n)
+        out = [np.zeros(max(n, 1), dtype=t) for t in (np.int32, np.uint32, np.uint32, np.uint32, np.float32, np.uint32)]
+        rc = reader._L.pmx_dbam_coverage_call_rows(reader._h, int(first), n, *(x.ctypes.data for x in out))
+        if rc:
+            reader._raise(rc)
+        return tuple(x[:n] for x in out)
+
+    def call_text(self, reader, first: int = 0, n=None) -> bytes:
+        """The narrowPeak lines of the peaks ``[first, first + n)``, formatted on the device (``pmx_dbam_coverage_call_text``: the
+        size, then the bytes); peak ``first + i`` is ``peak_<first + i + 1>``."""
+        n = self._peaks() - int(first) if n is None else int(n)
+        fn = reader._L.pmx_dbam_coverage_call_text
+        size = fn(reader._h, int(first), n, None, 0)
+        if size < 0:
+            reader._raise(size)
+        buf = np.zeros(max(int(size), 1), dtype=np.uint8)
+        got = fn(reader._h, int(first), n, buf.ctypes.data, int(size))
+        if got < 0:
+            reader._raise(got)
+        assert got == size
+        return buf[:int(size)].tobytes()
+
+    def call_text_chunks(self, reader, chunk: int = TEXT_CHUNK) -> Iterator[bytes]:
+        total = self._peaks()
+        for first in range(0, total, int(chunk)):
+            yield self.call_text(reader, first, min(int(chunk), total - first))
+
+    def call_result(self, reader) -> Peaks:
+        """The peak table on the handle as a ``Peaks``."""
+        ref, start, end, summit, value, runs = self.call_rows(reader)
+        cut = np.flatnonzero(np.diff(ref)) + 1 if ref.size else np.zeros(0, dtype=np.int64)
+        edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
+        tot = self.called["totals"]
+        p = Peaks({self.names[int(ref[a])]: tuple(x[a:z] for x in (start, end, summit, value, runs)) for a, z in zip(edges[:-1], edges[1:])},
+                  self.called["cutoff"], self.called["max_gap"], self.called["min_length"], tot)
+        inside = int(runs.sum(dtype=np.int64))
+        if (p.n_peaks, p.peak_bases) != (tot["peaks"], tot["peak_bases"]) or not (tot["peaks"] <= tot["candidates"] <= tot["passing_runs"]) \
+                or inside > tot["passing_runs"] or not (inside <= tot["passing_bases"] <= tot["peak_bases"]):
+            raise RuntimeError("pmx_dbam_coverage_call: the peaks do not add up to the totals")
+        return p
 
 
 def count_device(reader, mapq_criteria: int, references=None, extend=0, max_size: int = 2000) -> Coverage:
@@ -1347,6 +1547,13 @@ def write_file(path, chunks) -> Path:
         if os.path.exists(tmp):
             os.unlink(tmp)
     return path
+
+
+def write_called(path_base, chunks) -> Path:
+    """Writes ``<path_base>_coverage_peaks.narrowPeak`` (through a temporary file, renamed into place) and returns its path: the
+    bytes of ``chunks`` -- ``Peaks.text_chunks()`` or ``DeviceCount.call_text_chunks(reader)`` --, no header line, so that
+    ``peaks.open_peaks`` reads the file as it is."""
+    return write_file(str(path_base) + CALL_SUFFIX, chunks)
 
 
 def read_bigwig(path) -> Coverage:

@@ -559,16 +559,14 @@ int coverage_runs_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t n, i
     return 0;
 }
 
-int64_t coverage_text_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
+// The text of m >= 1 lines, one lane per line (`fn`: the entry point, its range checked): lengths(grid, noff, len, wsum) launches the
+// kernel that measures them, write(grid, noff, names, len, wbase, out) the one that writes them.  buf NULL: the size.
+template <class Lengths, class Write>
+int64_t coverage_text_pull(pmx_dbam *b, const std::string &fn, u64 m, uint8_t *buf, int64_t cap, Lengths lengths, Write write)
 {
-    const std::string fn = K.fn("text");
-    if (int rc = coverage_range(b, K, fn, first, n)) return rc;
-    if (buf && cap < 0) return fail(PMX_DBAM_ERR_INVALID, fn + ": a negative capacity");
-    if (n == 0) return 0;
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
-    const u64 m = (u64)n, nwg = (m + 255) / 256, nref = b->ref_names.size();
-    const CvRuns V(K.runs(b->cv), K.count(b->cv));
+    const u64 nwg = (m + 255) / 256, nref = b->ref_names.size();
     const u32 *noff = b->cv.names.as<u32>();
     const u8 *names = b->cv.names.as<u8>() + 4 * (nref + 1);
     DevAlloc d_len, d_w, d_wb, d_tot, d_text;
@@ -578,8 +576,7 @@ int64_t coverage_text_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t 
     HIPOK(hipMalloc(&d_w.p, 4 * nwg));
     HIPOK(hipMalloc(&d_wb.p, 8 * nwg));
     HIPOK(hipMalloc(&d_tot.p, 16));
-    hipLaunchKernelGGL(K.textlen, dim3((unsigned)nwg), dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff,
-                       d_len.as<u32>(), d_w.as<u32>());
+    lengths(dim3((unsigned)nwg), noff, d_len.as<u32>(), d_w.as<u32>());
     HIPOK(hipGetLastError());
     hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_w.as<u32>(), d_w.as<u32>(), nwg, d_wb.as<u64>(), d_tot.as<u64>());
     HIPOK(hipGetLastError());
@@ -593,12 +590,31 @@ int64_t coverage_text_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t 
         return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(bytes) + " bytes of text");
     }
     held.add(bytes);
-    hipLaunchKernelGGL(K.text, dim3((unsigned)nwg), dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff, names,
-                       d_len.as<u32>(), d_wb.as<u64>(), d_text.as<u8>());
+    write(dim3((unsigned)nwg), noff, names, d_len.as<u32>(), d_wb.as<u64>(), d_text.as<u8>());
     HIPOK(hipGetLastError());
     HIPOK(hipMemcpyAsync(buf, d_text.p, bytes, hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     return (int64_t)bytes;
+}
+
+int64_t coverage_text_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
+{
+    const std::string fn = K.fn("text");
+    if (int rc = coverage_range(b, K, fn, first, n)) return rc;
+    if (buf && cap < 0) return fail(PMX_DBAM_ERR_INVALID, fn + ": a negative capacity");
+    if (n == 0) return 0;
+    hipStream_t st = b->stream;
+    const u64 m = (u64)n;
+    const CvRuns V(K.runs(b->cv), K.count(b->cv));
+    return coverage_text_pull(
+        b, fn, m, buf, cap,
+        [&](dim3 grid, const u32 *noff, u32 *len, u32 *wsum) {
+            hipLaunchKernelGGL(K.textlen, grid, dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff, len, wsum);
+        },
+        [&](dim3 grid, const u32 *noff, const u8 *names, const u32 *len, const u64 *wbase, u8 *out) {
+            hipLaunchKernelGGL(K.text, grid, dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff, names, len, wbase,
+                               out);
+        });
 }
 
 }  // namespace

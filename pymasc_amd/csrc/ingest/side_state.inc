@@ -78,6 +78,12 @@ struct Coverage {
     u32 sbin = 0;                    // its bin
     double stot[4] = {0, 0, 0, 0};   // runs, covered bases, smallest and largest value
     std::vector<u64> sranges;        // `ranges` of the signal runs
+    // the peaks called from the signal runs (pmx_dbam_coverage_call, call_device.inc; DESIGN.md 7.18.5): from call until the next
+    // call, signal, compare, begin or close
+    DevAlloc peaks;                  // u8: reference, start, end, summit, float32 value, passing runs of every peak (4 bytes each)
+    bool phave = false;              // peaks have been called from these signal runs
+    u64 npeaks = 0;                  // the peaks
+    u64 ptot[5] = {0, 0, 0, 0, 0};   // passing runs, candidates, peaks, peak bases, passing bases
     bool on() const { return state == CV_TABLE; }
     u64 held() const { return bytes; }
 };

@@ -490,8 +490,19 @@ int sg_zoom_fill(pmx_dbam *b, const u32 *h_idof, const u32 *, const u64 *d_off, 
 }
 const CvParts SG_PARTS = {k_sg_sections, k_sg_secsums, sg_zoom_fill, k_sg_zoom_fold, k_sg_zoom_emit};
 
+// the peaks called from the signal runs (call_device.inc) go with them
+void call_drop(Coverage &c)
+{
+    c.bytes -= std::min<u64>(24 * c.npeaks, c.bytes);
+    c.peaks = DevAlloc{};
+    c.phave = false;
+    c.npeaks = 0;
+    for (u64 &x : c.ptot) x = 0;
+}
+
 void signal_drop(Coverage &c)
 {
+    call_drop(c);
     if (c.zsg) zoom_drop(c);
     c.zsg = false;
     c.bytes -= std::min<u64>(16 * c.snruns, c.bytes);

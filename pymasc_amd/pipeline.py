@@ -43,7 +43,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         fragments: bool = False, fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
         coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
         coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None, coverage_control=None,
-        coverage_compare: str = "log2", coverage_pseudocount: float = 1.0):
+        coverage_compare: str = "log2", coverage_pseudocount: float = 1.0, coverage_call=None, coverage_call_gap: int = 30,
+        coverage_call_length: int = 200):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -109,6 +110,11 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     The control is piled up with the run's ``mapq_criteria``, chromosome filter, excluded regions and ``chrom_sizes`` and the
     treatment's extend (``"pair"``: its own pairs), once for every file; its chosen references must be the treatment's
     (ValueError).  A compare setting without a control is a ValueError.
+    ``coverage_call``: a cutoff (any finite number; it implies ``coverage``): rank 0 also writes
+    ``<stem>_coverage_peaks.narrowPeak``, the peaks of exactly the track the coverage file holds -- the compared
+    track, the signal track or the depth --: runs of at least the cutoff, linked over gaps of at most ``coverage_call_gap`` bases
+    and kept from ``coverage_call_length`` bases, called on the GPU with device ingest (``coverage.DeviceCount.call``) and in numpy
+    otherwise (``coverage.Signal.call``).  No p-value is computed; ``peaks=`` reads the file in a second run.
     ``gc_bias``: a genome FASTA (plain, gzip or bgzip): rank 0 also writes ``<stem>_gcbias.tab`` (pymasc_amd.gcbias, DESIGN.md
     7.19): the reads the fingerprint counts, each placed on the genome window of ``gc_window`` bases (1 .. 1024) that begins at
     its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
@@ -201,6 +207,9 @@ class _Settings:
     coverage_control: object        # None, or the _CoverageControl of the call: the track is the treatment against it
     coverage_compare: str           # "log2", "ratio" or "subtract"
     coverage_pseudocount: float
+    coverage_call: object           # None, or the cutoff: the peaks of the file's track are written beside it
+    coverage_call_gap: int          # the largest gap inside a peak, and the smallest peak
+    coverage_call_length: int
     gc_bias: object                 # None, or the _GcGenome parsed once for the call
     gc_window: int
     fragments: bool
@@ -253,7 +262,13 @@ def _settings(kw: dict) -> _Settings:
     extend = kw["coverage_extend"]
     if extend not in ("auto", coverage.PAIR) and (isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0):
         raise ValueError("coverage_extend is \"auto\", \"pair\" or an integer of at least 0")
-    given.update(coverage=bool(kw["coverage"]) or kw["coverage_control"] is not None,
+    cutoff, gap, length = kw["coverage_call"], kw["coverage_call_gap"], kw["coverage_call_length"]
+    if cutoff is None and (gap != coverage.CALL_GAP or length != coverage.CALL_LENGTH):
+        raise ValueError("coverage_call_gap and coverage_call_length need coverage_call")
+    if cutoff is not None:
+        cutoff, gap, length = coverage.check_call(cutoff, gap, length)
+    given.update(coverage_call=cutoff, coverage_call_gap=gap, coverage_call_length=length)
+    given.update(coverage=bool(kw["coverage"]) or kw["coverage_control"] is not None or cutoff is not None,
                  coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend),
                  coverage_format=coverage.check_format(kw["coverage_format"], kw["coverage_compress"]),
                  coverage_compress=coverage.check_compress(kw["coverage_compress"]))
@@ -467,7 +482,8 @@ def _write_file(s: _Settings, path, basename: str, result, read_len: int, counte
     if s.stat_opts is not None:     # every rank holds the same result: the statistics are rank 0's alone
         written.append(stats.write_stats(out / basename, statistics()))
     for c in counted:
-        written.append(c.write(path, basename, statistics))
+        paths = c.write(path, basename, statistics)     # (the coverage side may write two files)
+        written.extend(paths if isinstance(paths, list) else [paths])
     return written
 
 
@@ -526,7 +542,10 @@ class _CoverageCount(_SideCount):
     unnamed temporary file in the output directory until ``write`` names them -- for a bigWig the sections, their tables and the
     zoom records are pulled and the file is assembled there.  ``"auto"`` needs the run's statistics, so it is not hooked: ``write``
     counts with ``statistics().est_lib_len`` on one more read of the file (``_count_again``), as several ranks do for an integer,
-    and writes while that reader is open."""
+    and writes while that reader is open.  With ``coverage_call`` the peaks of the track the file holds are called where the pileup
+    is taken (``called``: the chunks of their lines; a device reader's are spooled like the track's) and ``write`` returns two
+    paths, the coverage file's and ``<basename>_coverage_peaks.narrowPeak``'s."""
+    called = None
     hooked = property(lambda self: self.s.coverage_extend != "auto")
 
     @property
@@ -560,6 +579,8 @@ class _CoverageCount(_SideCount):
             elif self.signal:
                 c = c.signal(self.s.coverage_bin, self._scale(dict(zip(coverage.TOTALS, c.totals)), c.refs), self.s.coverage_normalize)
                 tail = (c.tail,)
+            if self.s.coverage_call is not None:    # (of the depth track: through its signal at bin 1 and scale 1.0)
+                self.called = _Later(c.call(*self._call).text_chunks)
             return self._bigwig(coverage.bigwig_source(c), False) if bigwig else (extend, c.reads, c.text_chunks()) + tail
         if acc is None:             # (an armed count is not built again: its ``begin`` would zero the table)
             acc = coverage.device_count_of(reader, mapq, names, extend, self.s.fragments_max)
@@ -572,6 +593,12 @@ class _CoverageCount(_SideCount):
         elif signal:                # the signal runs are made on the handle, beside the depth runs
             acc.signal(reader, self.s.coverage_bin, self._scale(totals, acc.refs), self.s.coverage_normalize)
             tail = (coverage.signal_tail(acc.sig["bin"], acc.sig["normalize"], acc.sig["scale"]),)
+        if self.s.coverage_call is not None:        # on the track the file holds; the depth track through signal(1, 1.0), and the
+            acc.call(reader, *self._call)           # file is still written from the depth runs.  The lines are few: always spooled
+            fp = self._temporary()
+            for chunk in acc.call_text_chunks(reader):
+                fp.write(chunk)
+            self.called = _spooled(fp)
         if bigwig:
             return self._bigwig(coverage.bigwig_source(acc, reader, signal), True)
         if not spool:
@@ -624,13 +651,22 @@ class _CoverageCount(_SideCount):
         done = chunks()
         return _Later(lambda: done)
 
-    def write(self, path, basename: str, statistics=None) -> Path:
+    _call = property(lambda self: (self.s.coverage_call, self.s.coverage_call_gap, self.s.coverage_call_length))
+
+    def _write(self, base, basename: str, value):
+        """The coverage file; with ``coverage_call`` [it, ``<basename>_coverage_peaks.narrowPeak``] (the lines ``_take`` left)."""
+        track = self.row.write(self.s, base, basename, value)
+        if self.s.coverage_call is None:
+            return track
+        return [track, coverage.write_called(base, self.called)]
+
+    def write(self, path, basename: str, statistics=None):
         s = self.s
         base = Path(s.outdir) / basename
         if self.value is not None:
-            return self.row.write(s, base, basename, self.value)
+            return self._write(base, basename, self.value)
         extend = int(statistics().est_lib_len) if s.coverage_extend == "auto" else s.coverage_extend
-        return _count_again(s, path, lambda r, names: self.row.write(s, base, basename, self._take(r, names, None, extend)))
+        return _count_again(s, path, lambda r, names: self._write(base, basename, self._take(r, names, None, extend)))
 
 
 class _Later:
@@ -812,7 +848,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               fragments_max: int = 2000, tss=None, tss_flank: int = 2000, tss_extend: int = 0,
               coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
               coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None, coverage_control=None,
-              coverage_compare: str = "log2", coverage_pseudocount: float = 1.0) -> List[FileResult]:
+              coverage_compare: str = "log2", coverage_pseudocount: float = 1.0, coverage_call=None, coverage_call_gap: int = 30,
+              coverage_call_length: int = 200) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -976,6 +1013,8 @@ def _warn_existing(s: _Settings, bases):
     suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
                                 ("_stats.tab", s.stat_opts is not None)) if on]
     suffixes += [row.suffix(s) if callable(row.suffix) else row.suffix for row in _SIDES if row.enabled(s)]
+    if s.coverage_call is not None:
+        suffixes.append(coverage.CALL_SUFFIX)
     for b in bases:
         for suffix in suffixes:
             path = Path(s.outdir) / (b + suffix)

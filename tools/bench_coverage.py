@@ -18,7 +18,14 @@ behind finish (pmx_dbam_coverage_signal, timed as "signal"), and the text pull a
 --control FILE [--compare log2|ratio|subtract]: a second synthetic file (made with another seed and
 --control-reads reads when it does not exist) is decoded once; every round then piles it up on its own handle behind the signal (begin
 + add + finish, timed as "control") and makes the compared track (pmx_dbam_coverage_compare, timed as "compare") in place of the
-signal, so "compare" stands beside "signal" on the same pileup, and the text pull and the bigWig file are the compared track's."""
+signal, so "compare" stands beside "signal" on the same pileup, and the text pull and the bigWig file are the compared track's.
+
+--call X [--call-gap N] [--call-length N]: every round also calls the peaks of the track the text pull read
+(pmx_dbam_coverage_call, timed as "call") and pulls their narrowPeak lines (timed as "call_text"), behind the text pull and outside
+"whole"; the depth track is first made a signal at bin 1 and scale 1.0 (timed as "call_signal").  The totals and the longest peak, in
+runs and in bases, are recorded under "call".  profiles/coverage_call.json is
+python tools/bench_coverage.py --reads 20000000 --format bigwig --bin 50 --normalize cpm --control /tmp/pymasc_coverage_control.bam \
+    --control-reads 10000000 --call 1 --no-host --no-open --reps 3 --out profiles/coverage_call.json"""
 import argparse
 import contextlib
 import json
@@ -95,6 +102,9 @@ def main():
     ap.add_argument("--control", default=None, help="a control file: every round also makes the treatment against it")
     ap.add_argument("--control-reads", type=int, default=None, help="the reads of a control made here (default: half of --reads)")
     ap.add_argument("--compare", choices=coverage.COMPARE, default="log2", help="the operation with --control")
+    ap.add_argument("--call", type=float, default=None, help="a cutoff: every round also calls the peaks of the track and pulls their lines")
+    ap.add_argument("--call-gap", type=int, default=coverage.CALL_GAP, help="the largest gap inside a peak")
+    ap.add_argument("--call-length", type=int, default=coverage.CALL_LENGTH, help="the smallest peak")
     ap.add_argument("--bigwig-path", default="/tmp/pymasc_coverage_bench.bw")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -120,6 +130,7 @@ def main():
         res["table_bytes"] = 4 * (sum(r.lengths) + len(r.lengths))
         split = dict(begin=[], add=[], finish=[], signal=[], text=[], whole=[])
         versus = dict(control=[], compare=[])
+        called = dict(call_signal=[], call=[], call_text=[])
         bw = dict(sections=[], zoom_begin=[], zoom_records=[], assembly=[], whole=[])
         for rep in range(a.reps + 1):               # (the first round warms up)
             t = [time.perf_counter()]
@@ -147,6 +158,22 @@ def main():
                     versus["compare"].append(t2 - t1)
             size = sum(len(chunk) for chunk in acc.text_chunks(r, signal=signal))
             t.append(time.perf_counter())
+            if a.call is not None:                  # the peaks of the track the text pull read, and their lines
+                tc = [time.perf_counter()]
+                if acc.sig is None:
+                    acc.signal(r, 1, 1.0)
+                tc.append(time.perf_counter())
+                ctotals = acc.call(r, a.call, a.call_gap, a.call_length)
+                tc.append(time.perf_counter())
+                csize = sum(len(chunk) for chunk in acc.call_text_chunks(r))
+                tc.append(time.perf_counter())
+                if rep:
+                    for k, name in enumerate(called):
+                        called[name].append(tc[k + 1] - tc[k])
+                rows = acc.call_rows(r)
+                res["call"] = dict(ctotals, cutoff=a.call, max_gap=a.call_gap, min_length=a.call_length, text_bytes=csize,
+                                   signal_runs=acc.sig["totals"]["runs"], longest_peak_runs=int(rows[5].max()) if rows[5].size else 0,
+                                   longest_peak_bases=int((rows[2] - rows[1]).max()) if rows[5].size else 0)
             if a.format == "bigwig":
                 src = _Timed(coverage.bigwig_source(acc, r, signal))
                 t0 = time.perf_counter()
@@ -169,6 +196,8 @@ def main():
                     split["text"][-1] -= versus["control"][-1] + versus["compare"][-1]
         if rc is not None:
             split.update(versus)
+        if a.call is not None:
+            split.update(called)
         res.update(totals, text_bytes=size, text_chunk_runs=coverage.TEXT_CHUNK,
                    **{k + "_s": v for k, v in split.items()},              # (every round, in the order they ran)
                    **{k + "_median_s": statistics.median(v) for k, v in split.items()})
