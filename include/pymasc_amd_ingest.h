@@ -363,6 +363,42 @@ int64_t pmx_dbam_coverage_signal_zoom_records_z(pmx_dbam *b, uint32_t level, uin
  * the table is not tiled.  A failure leaves no signal. */
 int pmx_dbam_coverage_compare(pmx_dbam *b, pmx_dbam *c, uint32_t bin, int op, double a_t, double a_c, double pseudo, double totals[4]);
 
+/* The treatment scored against the control (version >= 22): -log10 of a Poisson upper tail per bin against a local
+ * lambda, as one signal track.  The definitions are this project's own; nothing here was compared with MACS2.  `b` and `c` are
+ * checked as pmx_dbam_coverage_compare checks them (both in the runs state, one device, equal chosen references; c == b is legal).
+ * The definitions.  Everything is integer arithmetic or float64, each float64 operation rounded to nearest even on its own (no
+ * fused multiply-add).  S_t[j] and S_c[j] are the integer depth sums per bin of B bases (1 .. 65536) with the bins and the widths w_j
+ * of pmx_dbam_coverage_signal; reference r has the bins 0 .. n_r - 1 and the length len_r.  a_c is a float64 factor; the treatment is
+ * not scaled, because the score counts reads.  small (W_s) and large (W_l) are two window sizes in bases, each 0 (off) .. 2^31 - 1.
+ *   k        k[j] = S_t[j] / w_j, an integer division.
+ *   window   For W > 0: h = (W / B) / 2 bins; lo = max(0, j - h) and hi = min(n_r - 1, j + h), inside the bin range of j's own
+ *            reference (a window never crosses into another reference); N = sum S_c[lo .. hi] as u64;
+ *            D = min(len_r, (hi + 1) * B) - lo * B; c_W = (f64(N) * a_c) / f64(D).  h = 0 gives the bin's own value; a window that is
+ *            off contributes nothing.
+ *   lambda   c_0 = (f64(S_c[j]) * a_c) / f64(w_j); l_bg = (f64(sum of every S_c) * a_c) / f64(sum of the chosen lengths);
+ *            l[j] = max(l_bg, c_0, c_Ws, c_Wl).  A control without a covered base is refused, so l > 0 and normal everywhere.
+ *   ln, F    ln(x) = lg2(x) * 0.6931471805599453 with lg2 the stated algorithm of pmx_dbam_coverage_compare.  F[0] = F[1] = 0.0,
+ *            F[i] = F[i - 1] + ln(f64(i)), a sequential sum: the caller computes it once for max_depth_t + 1 entries and hands it in
+ *            as lnfact[n_lnfact] (more entries are legal; only the first max_depth_t + 1 are read).
+ *   score    If f64(k) <= l then v = 0.0: the bin is not enriched, and equality counts as not enriched.  Otherwise S = 1.0, T = 1.0
+ *            and for i = 1, 2, ...: r = l / f64(k + i); T = T * r; S' = S + T; stop when S' == S, else S = S' (the ratio is below
+ *            1 and falling, so the loop ends).  Then A = f64(k) * ln(l); C = (l - A) + F[k];
+ *            v = f32(C * 0.4342944819032518 - lg2(S) * 0.3010299956639812): -log10 of P(X >= k | l), with 0 <= v < 2^40.
+ *   runs     A bin with S_t = 0 is in no run.  A kept bin begins a run when it is the first bin of its reference, when the bin
+ *            before it is not kept, or when k or the bits of l differ from the bin before: the rule is on (k, l), not on v and not
+ *            on the width.  A run is (ref, start0, end0, v), in header order.  totals: as pmx_dbam_coverage_signal's four.
+ * Refused with PMX_DBAM_ERR_INVALID: a bin outside 1 .. 65536; a window above 2^31 - 1; n_lnfact <= max_depth_t (or lnfact NULL);
+ * max_depth_t > 2^20; a_c below 2^-64, not finite, or a_c * max_depth_c >= 2^40; a control without a covered base.
+ * The call waits for c's stream, then works on b's.  The runs are kept on b in the signal slot, marked as a p-score track until the
+ * next signal, compare, poisson, begin or close, and all eight pmx_dbam_coverage_signal_* consumers and pmx_dbam_coverage_call serve
+ * them; pmx_dbam_coverage_call_text on a p-score track writes the peak's value text in column 8 as well, in place of -1.  c is not
+ * changed.  Inside the call 24 bytes per bin of every chosen reference (S_t, the inclusive u64 prefix sum of S_c, l), 12 per 256
+ * bins, 8 per entry of F read and 20 per boundary of a run are held, counted towards pmx_dbam_stream_info's peak and freed before
+ * the call returns; out of memory for the tables is PMX_DBAM_ERR_OPEN with the bytes asked for (B = 1 on a large genome: the table
+ * is not tiled).  A failure leaves no signal. */
+int pmx_dbam_coverage_poisson(pmx_dbam *b, pmx_dbam *c, uint32_t bin, double a_c, uint32_t small, uint32_t large, const double *lnfact,
+                              uint64_t n_lnfact, double totals[4]);
+
 /* Peaks called from the signal track (version >= 21): a threshold caller over the signal runs on the handle, the
  * result of pmx_dbam_coverage_signal or pmx_dbam_coverage_compare.  The definitions are this project's own; nothing here was
  * compared with MACS2.
@@ -384,7 +420,8 @@ int pmx_dbam_coverage_compare(pmx_dbam *b, pmx_dbam *c, uint32_t bin, int op, do
  * The narrowPeak line of peak number n, 1-based in file order (first + i + 1 of a pull), no header line:
  *   chrom TAB start TAB end TAB peak_<n> TAB score TAB . TAB value TAB -1 TAB -1 TAB (summit - start) LF
  * score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0)), the product exact in float64; value is written as the signal's text
- * writes it: six decimals, ties to even, '-' only when the rounded micro-count is not 0.
+ * writes it: six decimals, ties to even, '-' only when the rounded micro-count is not 0.  On a p-score track (the signal slot filled
+ * by pmx_dbam_coverage_poisson, version >= 22) the first -1, column 8, is the value's text as well.
  * call without a signal on the handle is PMX_DBAM_ERR_INVALID (call signal or compare first).  The peak table (reference, start, end,
  * summit, value, runs: 24 bytes per peak) is kept on the handle, counted towards pmx_dbam_stream_info's peak, and dropped by the next
  * call, signal, compare, begin or close; call_rows and call_text after one of those are PMX_DBAM_ERR_INVALID.  The signal runs and

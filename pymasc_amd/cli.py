@@ -295,6 +295,16 @@ def get_parser() -> argparse.ArgumentParser:
                      help="the largest gap between two runs of one peak (0 .. 2^31 - 1; default 30); needs --coverage-call")
     out.add_argument("--coverage-call-length", metavar="N", type=int,
                      help="the smallest peak (1 .. 2^31 - 1; default 200); needs --coverage-call")
+    out.add_argument("--coverage-poisson", action="store_true",
+                     help="with --coverage-control, which it needs: the track holds -log10 of the Poisson upper tail P(X >= k | lambda) "
+                          "per bin instead of a compare operation, made on the GPU: k is the input's mean depth per bin as a whole "
+                          "number (the input is not scaled), lambda the largest of the control's mean over the genome, at the bin "
+                          "and over the two windows of --coverage-lambda, the control scaled to the input's number of reads; "
+                          "--coverage-call then thresholds the score and writes it in column 8 too.  Not with --coverage-compare, "
+                          "--coverage-pseudocount, --coverage-normalize other than none or --coverage-scale other than 1")
+    out.add_argument("--coverage-lambda", metavar=("S", "L"), type=int, nargs=2,
+                     help="the small and the large window of --coverage-poisson around every bin, in bases (each 0 .. 2^31 - 1, 0: "
+                          "off; default 1000 10000); needs --coverage-poisson")
     out.add_argument("--gc-bias", metavar="FASTA", type=Path,
                      help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
                           "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
@@ -378,6 +388,19 @@ def parse_args(argv=None) -> argparse.Namespace:
         if (args.coverage_pseudocount is not None and args.coverage_compare != "subtract"
                 and not 2.0 ** -64 <= args.coverage_pseudocount < 2.0 ** 40):
             parser.error("argument --coverage-pseudocount: must be a finite number of at least 2^-64 and below 2^40")
+    if args.coverage_lambda is not None and not args.coverage_poisson:
+        parser.error("argument --coverage-lambda: needs --coverage-poisson")
+    if args.coverage_poisson:
+        if args.coverage_control is None:
+            parser.error("argument --coverage-poisson: needs --coverage-control")
+        if args.coverage_compare is not None or args.coverage_pseudocount is not None:
+            parser.error("argument --coverage-poisson: not with --coverage-compare / --coverage-pseudocount (the score is not a compare "
+                         "operation)")
+        if args.coverage_normalize not in (None, "none") or args.coverage_scale not in (None, 1.0):
+            parser.error("argument --coverage-poisson: not with --coverage-normalize other than none or --coverage-scale other than 1 "
+                         "(the input is not scaled: the score counts reads)")
+        if args.coverage_lambda is not None and not all(0 <= x < 1 << 31 for x in args.coverage_lambda):
+            parser.error("argument --coverage-lambda: each window must lie in [0, 2^31 - 1]")
     if args.coverage_call is None and (args.coverage_call_gap is not None or args.coverage_call_length is not None):
         parser.error("argument --coverage-call-gap / --coverage-call-length: needs --coverage-call")
     if args.coverage_call is not None:
@@ -525,6 +548,10 @@ def _run(args, device, rank: int) -> int:
                     "coverage_pseudocount", "coverage_call", "coverage_call_gap", "coverage_call_length"):
             if getattr(args, key) is not None:
                 extra[key] = getattr(args, key)
+        if args.coverage_poisson:
+            extra["coverage_poisson"] = True
+            if args.coverage_lambda is not None:
+                extra["coverage_lambda"] = tuple(args.coverage_lambda)
     if args.fragments:
         extra["fragments"] = True
     if args.fragments_max is not None:          # (it also bounds a pair pileup)

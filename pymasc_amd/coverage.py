@@ -99,7 +99,40 @@ with MACS2.
   ``passing_bases`` (the widths of the passing runs inside peaks).
 * The file is ``<name>_coverage_peaks.narrowPeak``, without a header line, one line per peak: ``chrom``, ``start``, ``end``,
   ``peak_<n>`` (``n`` 1-based in file order), ``score``, ``.``, ``value``, ``-1``, ``-1``, ``summit - start``, TAB-separated.
-  ``score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0))`` (``call_score``); ``value`` is written by ``format_value``.
+  ``score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0))`` (``call_score``); ``value`` is written by ``format_value``.  On a
+  p-score track (below) column 8 holds the text of ``value`` as well, in place of ``-1``.
+
+The treatment scored against the control (``--coverage-poisson``; ``Coverage.poisson``, ``DeviceCount.poisson``):
+-log10 of a Poisson upper tail per bin against a local lambda, as one signal track.  The definitions are this project's own: nothing
+here was compared with MACS2.  Everything is integer arithmetic or float64, each float64 operation rounded to nearest even on its
+own (no fused multiply-add).
+
+* Two pileups over the same chosen references (``compare``'s check); ``B`` (1 .. 65536) with the bins, the widths ``w_j`` and the
+  sums ``S_t[j]``, ``S_c[j]`` above; reference ``r`` has the bins ``0 .. n_r - 1`` and the length ``len_r``.  ``a_c`` is a float64
+  factor checked by ``check_scale`` against the control's ``max_depth``; the treatment is not scaled, because the score counts reads
+  (``a_c = factors_of("none", ...)[1]`` scales the control to the treatment's library size).  ``W_s`` and ``W_l`` are two window
+  sizes in bases, each 0 (off) .. 2^31 - 1 (``check_lambda_windows``; the defaults are 1000 and 10000).
+* ``k[j] = S_t[j] // w_j``, an integer division.
+* Window mean, for ``W > 0``: ``h = (W // B) // 2`` bins; ``lo = max(0, j - h)`` and ``hi = min(n_r - 1, j + h)``, inside the bin
+  range of ``j``'s own reference (a window never crosses into another reference); ``N = sum S_c[lo .. hi]`` as u64;
+  ``D = min(len_r, (hi + 1) * B) - lo * B``; ``c_W = (f64(N) * a_c) / f64(D)``.  ``h = 0`` gives the bin's own value; a window that is
+  off contributes nothing.
+* Lambda: ``c_0 = (f64(S_c[j]) * a_c) / f64(w_j)``; ``l_bg = (f64(sum of every S_c) * a_c) / f64(sum of the chosen lengths)``;
+  ``l[j] = max(l_bg, c_0, c_Ws, c_Wl)`` (``poisson_lambda``).  A control without a covered base is refused, so ``l > 0`` and normal
+  everywhere.
+* ``ln(x) = lg2(x) * 0.6931471805599453`` with ``lg2`` the stated algorithm above; ``F[0] = F[1] = 0.0``,
+  ``F[i] = F[i - 1] + ln(f64(i))``, a sequential sum (``lnfact(n)``), computed here for ``n = max_depth_t + 1`` entries and handed
+  to the library as an array.  A ``max_depth_t`` above 2^20 is refused.
+* Score (``poisson_values``): if ``f64(k) <= l`` then ``v = 0.0`` -- the bin is not enriched, and equality counts as not enriched.
+  Otherwise ``S = 1.0``, ``T = 1.0`` and for ``i = 1, 2, ...``: ``r = l / f64(k + i)``; ``T = T * r``; ``S' = S + T``; stop when
+  ``S' == S``, else ``S = S'`` (the ratio is below 1 and falling, so the loop ends).  Then ``A = f64(k) * ln(l)``;
+  ``C = (l - A) + F[k]``; ``v = f32(C * 0.4342944819032518 - lg2(S) * 0.3010299956639812)``: -log10 of ``P(X >= k | l)``, with
+  ``0 <= v < 2^40``.
+* Runs: a bin with ``S_t = 0`` is in no run.  A kept bin begins a run when it is the first bin of its reference, when the bin before
+  it is not kept, or when ``k`` or the bits of ``l`` differ from the bin before: the rule is on ``(k, l)``, not on ``v`` and not on
+  the width.  Rows are ``(ref, start0, end0, v)`` in header order; the totals are the signal's four.
+* The track line is the signal's (``normalize=none scale=1.0``) followed by `` control=<the control's basename>
+  poisson=<W_s>,<W_l>`` (``poisson_tail``).
 """
 from __future__ import annotations
 
@@ -132,6 +165,10 @@ CALL_SUFFIX = "_coverage_peaks.narrowPeak"
 CALL_TOTALS = ("passing_runs", "candidates", "peaks", "peak_bases", "passing_bases")
 CALL_GAP, CALL_LENGTH = 30, 200             # the defaults of ``coverage_call_gap`` and ``coverage_call_length``
 MAX_CALL_INT = (1 << 31) - 1                # the largest ``max_gap`` and ``min_length``
+LAMBDA_WINDOWS = (1000, 10000)              # the defaults of ``coverage_lambda``: the small and the large window of the p-score track
+MAX_WINDOW = (1 << 31) - 1                  # the largest window
+MAX_POISSON_DEPTH = 1 << 20                 # the largest ``max_depth`` of a treatment that is scored
+LN_2, LOG10_E, LOG10_2 = 0.6931471805599453, 0.4342944819032518, 0.3010299956639812
 _TRACK = re.compile(r'^track type=bedGraph name="(.*)" description="pymasc_amd fragment pileup extend=(\d+|read|pair) reads=(\d+)"$')
 
 
@@ -304,6 +341,101 @@ def compare_values(S_t, S_c, w, op: str, a_t: float, a_c: float, pseudo: float) 
     return (x if op == "ratio" else lg2(x)).astype(np.float32)
 
 
+def check_lambda_windows(windows=LAMBDA_WINDOWS) -> Tuple[int, int]:
+    """``coverage_lambda`` as the p-score track takes it: (small, large), two integers from 0 (off) to 2^31 - 1."""
+    try:
+        small, large = windows
+        ok = all(not isinstance(x, (str, bool)) and int(x) == x and 0 <= int(x) <= MAX_WINDOW for x in (small, large))
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("coverage_lambda is two integers, each from 0 (off) to 2^31 - 1")
+    return int(small), int(large)
+
+
+def poisson_tail(control, small: int, large: int) -> str:
+    """What a p-score track's line has behind a signal's: the control's basename and the two windows."""
+    small, large = check_lambda_windows((small, large))
+    return " control={} poisson={},{}".format(os.path.basename(os.fspath(control)), small, large)
+
+
+def lnfact(n) -> np.ndarray:
+    """``F[0 .. n - 1]``, float64, of the p-score track: ``F[0] = F[1] = 0.0``, ``F[i] = F[i - 1] + ln(f64(i))``
+    with ``ln(x) = lg2(x) * 0.6931471805599453``, a sequential sum (``np.cumsum`` adds one element after the other).  ``n`` is
+    ``max_depth + 1`` of the treatment: 1 to 2^20 + 1."""
+    if isinstance(n, (str, bool)) or int(n) != n or not 1 <= int(n) <= MAX_POISSON_DEPTH + 1:
+        raise ValueError("the table of ln(i!) has 1 to 2^20 + 1 entries (the treatment's max_depth is at most 2^20)")
+    terms = np.zeros(int(n), dtype=np.float64)
+    if n > 2:
+        terms[2:] = lg2(np.arange(2, int(n), dtype=np.float64)) * LN_2
+    return np.cumsum(terms)
+
+
+def poisson_series(k, lam) -> Tuple[np.ndarray, np.ndarray]:
+    """(S, steps) of the series of pairs with ``f64(k) > lam``: ``S = T = 1.0``; for ``i = 1, 2, ...``: ``T = T * (lam / f64(k + i))``,
+    ``S' = S + T``, stop when ``S' == S``, else ``S = S'``.  A masked loop: the pairs that have stopped are left out."""
+    k, lam = np.asarray(k, dtype=np.int64).ravel(), np.asarray(lam, dtype=np.float64).ravel()
+    S, T, steps = np.ones(k.size, dtype=np.float64), np.ones(k.size, dtype=np.float64), np.zeros(k.size, dtype=np.int64)
+    live, i = np.arange(k.size), 0
+    while live.size:
+        i += 1
+        T[live] = T[live] * (lam[live] / (k[live] + i).astype(np.float64))
+        S2 = S[live] + T[live]
+        go = S2 > S[live]                                   # (T >= 0: S' >= S, so this is S' != S)
+        steps[live] = i
+        S[live[go]] = S2[go]
+        live = live[go]
+    return S, steps
+
+
+def poisson_values(k, lam, F) -> np.ndarray:
+    """``v`` (float32) of pairs ``(k, lam)`` with the table ``F`` (``lnfact``; ``F[k]`` exists for every ``k``), in the stated order
+    of operations: 0.0 where ``f64(k) <= lam``; elsewhere ``f32(((lam - f64(k) * ln(lam)) + F[k]) * 0.4342944819032518 - lg2(S) *
+    0.3010299956639812)`` with ``S`` of ``poisson_series``."""
+    k, lam = np.asarray(k, dtype=np.int64).ravel(), np.asarray(lam, dtype=np.float64).ravel()
+    F = np.asarray(F, dtype=np.float64)
+    out = np.zeros(k.size, dtype=np.float32)
+    at = np.flatnonzero(k.astype(np.float64) > lam)
+    if at.size:
+        kk, ll = k[at], lam[at]
+        S, _steps = poisson_series(kk, ll)
+        A = kk.astype(np.float64) * (lg2(ll) * LN_2)
+        C = (ll - A) + F[kk]
+        out[at] = (C * LOG10_E - lg2(S) * LOG10_2).astype(np.float32)
+    return out
+
+
+def poisson_lambda(S_c, width, bin: int, length: int, a_c: float, lam_bg: float, small: int, large: int) -> np.ndarray:
+    """``l[j]`` (float64) of the bins of one reference of ``length`` bases from the control's sums ``S_c`` and the widths: the
+    largest of ``lam_bg``, ``c_0`` and the means over the windows that are on, each ``(f64(N) * a_c) / f64(D)``."""
+    S_c, width = np.asarray(S_c, dtype=np.int64), np.asarray(width, dtype=np.int64)
+    n = S_c.size
+    P = np.concatenate(([0], np.cumsum(S_c, dtype=np.int64)))      # P[i]: the sum of the bins in front of i
+    lam = np.maximum(lam_bg, (S_c.astype(np.float64) * a_c) / width.astype(np.float64))
+    j = np.arange(n, dtype=np.int64)
+    for W in (small, large):
+        if W:
+            h = (int(W) // int(bin)) // 2
+            lo, hi = np.maximum(j - h, 0), np.minimum(j + h, n - 1)
+            N = P[hi + 1] - P[lo]
+            D = np.minimum(int(length), (hi + 1) * int(bin)) - lo * int(bin)
+            lam = np.maximum(lam, (N.astype(np.float64) * a_c) / D.astype(np.float64))
+    return lam
+
+
+def check_poisson(a_c, small, large, max_depth_t: int, max_depth_c: int, control_bases: int):
+    """(a_c, small, large) as ``pmx_dbam_coverage_poisson`` takes them, its refusals made here for both paths: the windows by
+    ``check_lambda_windows``, a treatment's ``max_depth`` above 2^20, ``a_c`` by ``check_scale`` with the control's ``max_depth``,
+    a control without a covered base."""
+    small, large = check_lambda_windows((small, large))
+    if int(max_depth_t) > MAX_POISSON_DEPTH:
+        raise ValueError("the treatment's max_depth is above 2^20")
+    a_c = check_scale(a_c, max_depth_c)
+    if not int(control_bases):
+        raise ValueError("the control has no covered base: there is no background to score against")
+    return a_c, small, large
+
+
 def check_call(cutoff, max_gap=30, min_length=200) -> Tuple[float, int, int]:
     """(cutoff, max_gap, min_length) as the peak caller takes them (the refusals of ``pmx_dbam_coverage_call``, made here for both
     paths): a finite number (negative is legal), an integer from 0 to 2^31 - 1, an integer from 1 to 2^31 - 1."""
@@ -337,7 +469,9 @@ class Peaks:
     ``totals``: by name (``CALL_TOTALS``).  Two are equal when their rows are, bit for bit, with the three parameters and the
     totals."""
 
-    def __init__(self, rows, cutoff: float, max_gap: int, min_length: int, totals):
+    def __init__(self, rows, cutoff: float, max_gap: int, min_length: int, totals, pscore: bool = False):
+        """``pscore``: the track is a p-score track: column 8 of a line holds the value's text, not ``-1``."""
+        self.pscore = bool(pscore)
         types = (np.uint32, np.uint32, np.uint32, np.float32, np.uint32)
         self.rows = {str(k): tuple(np.asarray(x, dtype=t).ravel() for x, t in zip(v, types)) for k, v in rows.items()}
         self.cutoff, self.max_gap, self.min_length = check_call(cutoff, max_gap, min_length)
@@ -358,13 +492,15 @@ class Peaks:
         for name, (s, e, m, v, _r) in self.rows.items():
             for a in range(0, s.size, chunk):
                 z = slice(a, a + chunk)
-                yield "".join("{}\t{}\t{}\tpeak_{}\t{}\t.\t{}\t-1\t-1\t{}\n".format(name, x, y, no + a + i + 1, sc, format_value(val), c - x)
+                yield "".join("{}\t{}\t{}\tpeak_{}\t{}\t.\t{}\t{}\t-1\t{}\n".format(name, x, y, no + a + i + 1, sc, format_value(val),
+                                                                                 format_value(val) if self.pscore else "-1", c - x)
                                for i, (x, y, c, val, sc) in enumerate(zip(s[z].tolist(), e[z].tolist(), m[z].tolist(), v[z],
                                                                           call_score(v[z]).tolist()))).encode()
             no += s.size
 
     def __eq__(self, other) -> bool:
-        return (isinstance(other, Peaks) and (self.cutoff, self.max_gap, self.min_length) == (other.cutoff, other.max_gap, other.min_length)
+        return (isinstance(other, Peaks) and (self.cutoff, self.max_gap, self.min_length, self.pscore) == (other.cutoff, other.max_gap,
+                                                                                                            other.min_length, other.pscore)
                 and self.totals == other.totals and list(self.rows) == list(other.rows)
                 and all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for k in self.rows for a, b in zip(self.rows[k], other.rows[k])))
 
@@ -380,9 +516,11 @@ class Signal:
     run, in header order; ``bin``, ``scale``; ``refs`` as for ``Coverage``; ``reads``, ``extend`` and ``normalize`` (the word) are
     what the track line says.  Two signals are equal when their runs are, bit for bit, with ``bin`` and ``scale``."""
 
-    def __init__(self, runs, bin: int, scale: float, refs=None, reads: int = 0, extend=0, normalize: str = "none", more: str = ""):
-        """``more``: what the track line says behind a signal's (``compare_tail`` of a compared track)."""
-        self.more = str(more)
+    def __init__(self, runs, bin: int, scale: float, refs=None, reads: int = 0, extend=0, normalize: str = "none", more: str = "",
+                 pscore: bool = False):
+        """``more``: what the track line says behind a signal's (``compare_tail`` of a compared track); ``pscore``: the values are
+        p-scores (``Coverage.poisson``), which ``call`` hands on to its ``Peaks``."""
+        self.more, self.pscore = str(more), bool(pscore)
         self.runs = {str(k): (np.asarray(v[0], dtype=np.uint32).ravel(), np.asarray(v[1], dtype=np.uint32).ravel(),
                               np.asarray(v[2], dtype=np.float32).ravel()) for k, v in runs.items()}
         self.bin, self.scale = check_bin(bin), float(scale)
@@ -447,10 +585,11 @@ class Signal:
             tot["peaks"] += int(keep.sum())
             tot["peak_bases"] += int((end - start)[keep].sum())
             tot["passing_bases"] += int(np.add.reduceat(pe - ps, first)[keep].sum())
-        return Peaks(rows, cutoff, max_gap, min_length, tot)
+        return Peaks(rows, cutoff, max_gap, min_length, tot, self.pscore)
 
     def __eq__(self, other) -> bool:
-        return (isinstance(other, Signal) and (self.bin, self.scale) == (other.bin, other.scale) and list(self.runs) == list(other.runs)
+        return (isinstance(other, Signal) and (self.bin, self.scale, self.pscore) == (other.bin, other.scale, other.pscore)
+                and list(self.runs) == list(other.runs)
                 and all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for k in self.runs for a, b in zip(self.runs[k], other.runs[k])))
 
     __hash__ = None
@@ -566,6 +705,42 @@ class Coverage:
             if at.size:
                 out[name] = (at * bin, ends, compare_values(St[at], Sc[at], width[at], op, a_t, a_c, pseudo))
         return Signal(out, bin, a_t, self.refs, self.reads, self.extend, normalize, compare_tail(control, op, pseudo))
+
+    def poisson(self, other: "Coverage", bin: int = 1, a_c: float = 1.0, small: int = LAMBDA_WINDOWS[0], large: int = LAMBDA_WINDOWS[1],
+                control="") -> Signal:
+        """This pileup (the treatment) scored against ``other`` (the control) as one signal track of p-scores,
+        in numpy: the path of host readers and the checker of ``pmx_dbam_coverage_poisson``.  Per bin ``k = S_t // w`` and ``l``
+        (``poisson_lambda``); a bin with ``S_t = 0`` is in no run, a kept bin begins a run where its reference begins, where the
+        bin before is not kept or where ``k`` or the bits of ``l`` differ from it; ``v`` by ``poisson_values``.  The result's
+        ``scale`` is 1.0 (the treatment is not scaled) and its ``pscore`` is set; ``control`` is what the track line says."""
+        bin = check_bin(bin)
+        a_c, small, large = check_poisson(a_c, small, large, self.max_depth, other.max_depth, other.fragment_bases)
+        if self.refs is None or other.refs is None:
+            raise ValueError("a pileup does not know its chosen references' lengths (it was read from a bedGraph file)")
+        if self.refs != other.refs:
+            raise ValueError("the chosen references of the control differ in name, length or order")
+        F = lnfact(self.max_depth + 1)
+        out = {name: (start, end, poisson_values(k, lam, F)) for name, start, end, k, lam in self.poisson_pairs(other, bin, a_c, small, large)}
+        return Signal(out, bin, 1.0, self.refs, self.reads, self.extend, "none", poisson_tail(control, small, large), True)
+
+    def poisson_pairs(self, other: "Coverage", bin: int, a_c: float, small: int, large: int):
+        """(name, start0, end0, k, l) of the runs of ``poisson``, reference by reference: the pairs ``poisson_values`` scores."""
+        lam_bg = (float(other.fragment_bases) * a_c) / float(sum(l for _n, l in self.refs))
+        for name, length in self.refs:
+            if name not in self.runs:
+                continue
+            St, width = self._bin_sums(name, bin, length)
+            Sc, _w = other._bin_sums(name, bin, length)
+            k, lam = St // width, poisson_lambda(Sc, width, bin, length, a_c, lam_bg, small, large)
+            kept, bits = St != 0, lam.view(np.uint64)
+            begins = np.ones(St.size, dtype=bool)
+            begins[1:] = (kept[1:] != kept[:-1]) | (kept[1:] & ((k[1:] != k[:-1]) | (bits[1:] != bits[:-1])))
+            at = np.flatnonzero(begins)
+            ends = np.append(at[1:] * bin, length)
+            keep = kept[at]
+            at, ends = at[keep], ends[keep]
+            if at.size:
+                yield name, at * bin, ends, k[at], lam[at]
 
     def call(self, cutoff, max_gap: int = CALL_GAP, min_length: int = CALL_LENGTH) -> Peaks:
         """The peaks of the depth track: ``Signal.call`` of the signal at bin 1 and scale 1.0."""
@@ -721,6 +896,27 @@ class DeviceCount(SideAccumulator):
         if rc:
             reader._raise(rc)
         self.sig = dict(bin=bin, scale=a_t, normalize=check_normalize(normalize), more=compare_tail(control, op, pseudo),
+                        totals=dict(runs=int(out[0]), covered_bases=int(out[1]), min=float(out[2]), max=float(out[3])))
+        return self.sig["totals"]
+
+    def poisson(self, reader, control_acc: "DeviceCount", control_reader, bin: int = 1, a_c: float = 1.0, small: int = LAMBDA_WINDOWS[0],
+                large: int = LAMBDA_WINDOWS[1], control="") -> Dict[str, float]:
+        """Makes the p-score track of this pileup (the treatment) against the finished pileup ``control_acc`` on
+        ``control_reader``'s handle (``pmx_dbam_coverage_poisson``) in this handle's signal slot and returns its
+        totals by name (``SIGNAL_TOTALS``): ``signal=True`` on every method below serves it, and ``call`` writes column 8.  The
+        table ``lnfact`` is computed here.  The control's handle is not changed and may be closed afterwards."""
+        bin = check_bin(bin)
+        mine, theirs = self.finish(reader), control_acc.finish(control_reader)
+        a_c, small, large = check_poisson(a_c, small, large, mine["max_depth"], theirs["max_depth"], theirs["fragment_bases"])
+        if self.refs != control_acc.refs:
+            raise ValueError("the chosen references of the control differ in name, length or order")
+        F = np.ascontiguousarray(lnfact(mine["max_depth"] + 1))
+        out = np.zeros(4, dtype=np.float64)
+        self.sig = self.called = None
+        rc = reader._L.pmx_dbam_coverage_poisson(reader._h, control_reader._h, bin, a_c, small, large, F.ctypes.data, F.size, out.ctypes.data)
+        if rc:
+            reader._raise(rc)
+        self.sig = dict(bin=bin, scale=1.0, normalize="none", more=poisson_tail(control, small, large), pscore=True,
                         totals=dict(runs=int(out[0]), covered_bases=int(out[1]), min=float(out[2]), max=float(out[3])))
         return self.sig["totals"]
 
@@ -883,7 +1079,7 @@ class DeviceCount(SideAccumulator):
         edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
         g = Signal({self.names[int(ref[a])]: (start[a:z], end[a:z], value[a:z]) for a, z in zip(edges[:-1], edges[1:])},
                    self.sig["bin"], self.sig["scale"], self.refs, self.finish(reader)["reads"], self.extend, self.sig["normalize"],
-                   self.sig.get("more", ""))
+                   self.sig.get("more", ""), self.sig.get("pscore", False))
         if g.totals != tuple(self.sig["totals"][k] for k in SIGNAL_TOTALS):
             raise RuntimeError("pmx_dbam_coverage_signal: the runs do not add up to the totals")
         return g
@@ -900,7 +1096,8 @@ class DeviceCount(SideAccumulator):
         rc = reader._L.pmx_dbam_coverage_call(reader._h, cutoff, max_gap, min_length, out.ctypes.data)
         if rc:
             reader._raise(rc)
-        self.called = dict(cutoff=cutoff, max_gap=max_gap, min_length=min_length, totals=dict(zip(CALL_TOTALS, (int(x) for x in out))))
+        self.called = dict(cutoff=cutoff, max_gap=max_gap, min_length=min_length, pscore=bool(self.sig.get("pscore", False)),
+                           totals=dict(zip(CALL_TOTALS, (int(x) for x in out))))
         return self.called["totals"]
 
     def _peaks(self) -> int:
@@ -945,7 +1142,7 @@ class DeviceCount(SideAccumulator):
         edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
         tot = self.called["totals"]
         p = Peaks({self.names[int(ref[a])]: tuple(x[a:z] for x in (start, end, summit, value, runs)) for a, z in zip(edges[:-1], edges[1:])},
-                  self.called["cutoff"], self.called["max_gap"], self.called["min_length"], tot)
+                  self.called["cutoff"], self.called["max_gap"], self.called["min_length"], tot, self.called["pscore"])
         inside = int(runs.sum(dtype=np.int64))
         if (p.n_peaks, p.peak_bases) != (tot["peaks"], tot["peak_bases"]) or not (tot["peaks"] <= tot["candidates"] <= tot["passing_runs"]) \
                 or inside > tot["passing_runs"] or not (inside <= tot["passing_bases"] <= tot["peak_bases"]):

@@ -18,7 +18,8 @@
 // The narrowPeak line of peak number n (1-based in file order: first + i + 1 of a pull):
 //   chrom TAB start TAB end TAB peak_<n> TAB score TAB . TAB value TAB -1 TAB -1 TAB (summit - start) LF
 // score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0)), the product exact in float64; value by sg_micro / sg_minus / sg_split of
-// signal_device.inc.  No header line.
+// signal_device.inc.  No header line.  When the signal slot holds a p-score track (pmx_dbam_coverage_poisson, poisson_device.inc; DESIGN.md
+// 7.18.6) the first -1 (column 8) is the value's text as well; on every other track each byte is as above.
 //
 //   k_cl_count<0> / k_bam_scan / k_cl_list<0>   the passing runs, compacted by ballots (256 per workgroup) into the list P of run indices
 //   k_cl_count<1> / k_bam_scan / k_cl_list<1>   over P: an element begins a candidate when it is the first, when its reference differs
@@ -180,9 +181,27 @@ __device__ __forceinline__ u32 cl_score(u32 bits)
     return (u32)x;
 }
 
-// no0: the number of the first peak of the pull
+// the text of a value (sg_split of its micro-count N) in front of `end`; returns where it begins
+__device__ __forceinline__ u8 *cl_value(u8 *q, u32 bits, u64 N, u64 whole, u32 frac, u32 nd)
+{
+    if (nd) {
+        for (u32 c = 0; c < nd; c++) {  // (nd digits, leading zeros among them)
+            *--q = (u8)('0' + frac % 10u);
+            frac /= 10u;
+        }
+        *--q = '.';
+    }
+    do {
+        *--q = (u8)('0' + (u32)(whole % 10u));
+        whole /= 10u;
+    } while (whole);
+    if (sg_minus(bits, N)) *--q = '-';
+    return q;
+}
+
+// no0: the number of the first peak of the pull; ps: the signal is a p-score track (poisson_device.inc): column 8 holds the value too
 __global__ void __launch_bounds__(256) k_cl_textlen(const int *__restrict__ pref, const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
-                                                    const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0,
+                                                    const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0, int ps,
                                                     const u32 *__restrict__ noff, u32 *__restrict__ len, u32 *__restrict__ wsum)
 {
     __shared__ u32 s_w[4];
@@ -195,8 +214,9 @@ __global__ void __launch_bounds__(256) k_cl_textlen(const int *__restrict__ pref
         u32 frac, nd;
         const u64 N = sg_micro(pval[i]);
         sg_split(N, whole, frac, nd);
-        l = noff[r + 1u] - noff[r] + cv_width(pstart[i]) + cv_width(pend[i]) + 5u + sg_width(no0 + i) + cv_width(cl_score(pval[i])) + 1u +
-            sg_minus(pval[i], N) + sg_width(whole) + (nd ? nd + 1u : 0u) + 4u + cv_width(psummit[i] - pstart[i]) + 10u;
+        const u32 vl = sg_minus(pval[i], N) + sg_width(whole) + (nd ? nd + 1u : 0u);          // the value's text
+        l = noff[r + 1u] - noff[r] + cv_width(pstart[i]) + cv_width(pend[i]) + 5u + sg_width(no0 + i) + cv_width(cl_score(pval[i])) + 1u + vl +
+            (ps ? vl + 2u : 4u) + cv_width(psummit[i] - pstart[i]) + 10u;
         len[i] = l;
     }
     l = (u32)cx_wave_sum((u64)l);
@@ -206,7 +226,7 @@ __global__ void __launch_bounds__(256) k_cl_textlen(const int *__restrict__ pref
 }
 
 __global__ void __launch_bounds__(256) k_cl_text(const int *__restrict__ pref, const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
-                                                 const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0,
+                                                 const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0, int ps,
                                                  const u32 *__restrict__ noff, const u8 *__restrict__ names, const u32 *__restrict__ len,
                                                  const u64 *__restrict__ wbase, u8 *__restrict__ out)
 {
@@ -230,24 +250,18 @@ __global__ void __launch_bounds__(256) k_cl_text(const int *__restrict__ pref, c
     u8 *q = out + o + l;                // the line from its end: LF, summit - start, TAB -1 TAB -1 TAB, the value, TAB . TAB, ...
     *--q = '\n';
     q = cv_digits(q, psummit[i] - pstart[i]);
-    for (int c = 0; c < 2; c++) {
-        *--q = '\t';
+    *--q = '\t';
+    *--q = '1';
+    *--q = '-';
+    *--q = '\t';
+    if (ps) {                           // (a p-score track: column 8 is the value's text as well)
+        q = cl_value(q, pval[i], N, whole, frac, nd);
+    } else {
         *--q = '1';
         *--q = '-';
     }
     *--q = '\t';
-    if (nd) {
-        for (u32 c = 0; c < nd; c++) {  // (nd digits, leading zeros among them)
-            *--q = (u8)('0' + frac % 10u);
-            frac /= 10u;
-        }
-        *--q = '.';
-    }
-    do {
-        *--q = (u8)('0' + (u32)(whole % 10u));
-        whole /= 10u;
-    } while (whole);
-    if (sg_minus(pval[i], N)) *--q = '-';
+    q = cl_value(q, pval[i], N, whole, frac, nd);
     *--q = '\t';
     *--q = '.';
     *--q = '\t';
@@ -440,16 +454,17 @@ int64_t coverage_call_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *
     if (n == 0) return 0;
     hipStream_t st = b->stream;
     const u64 m = (u64)n, no0 = (u64)first + 1u;
+    const int ps = (int)b->cv.spscore;
     const ClPeaks K(b->cv.peaks.as<u8>(), b->cv.npeaks);
     return coverage_text_pull(
         b, fn, m, buf, cap,
         [&](dim3 grid, const u32 *noff, u32 *len, u32 *wsum) {
             hipLaunchKernelGGL(k_cl_textlen, grid, dim3(256), 0, st, K.ref + first, K.start + first, K.end + first, K.summit + first, K.value + first, m,
-                               no0, noff, len, wsum);
+                               no0, ps, noff, len, wsum);
         },
         [&](dim3 grid, const u32 *noff, const u8 *names, const u32 *len, const u64 *wbase, u8 *out) {
             hipLaunchKernelGGL(k_cl_text, grid, dim3(256), 0, st, K.ref + first, K.start + first, K.end + first, K.summit + first, K.value + first, m, no0,
-                               noff, names, len, wbase, out);
+                               ps, noff, names, len, wbase, out);
         });
 }
 

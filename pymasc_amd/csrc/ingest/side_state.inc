@@ -74,6 +74,7 @@ struct Coverage {
     // compare_device.inc; 7.18.4): from signal / compare until the next signal, compare, begin or close
     DevAlloc sruns;                  // u8: reference, start, end, float32 value of every signal run (the layout of `runs`)
     bool shave = false;              // a signal has been made of these runs
+    bool spscore = false;            // its values are p-scores (pmx_dbam_coverage_poisson, poisson_device.inc; 7.18.6): call writes column 8
     u64 snruns = 0;                  // its runs
     u32 sbin = 0;                    // its bin
     double stot[4] = {0, 0, 0, 0};   // runs, covered bases, smallest and largest value

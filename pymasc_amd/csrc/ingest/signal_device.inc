@@ -508,6 +508,7 @@ void signal_drop(Coverage &c)
     c.bytes -= std::min<u64>(16 * c.snruns, c.bytes);
     c.sruns = DevAlloc{};
     c.shave = false;
+    c.spscore = false;
     c.snruns = 0;
     c.sbin = 0;
     c.sranges.clear();

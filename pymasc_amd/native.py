@@ -145,6 +145,7 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_coverage_zoom_records_z": (_i64, [_vp, _u32, _u32, _vp, _i64, _vp, _i64, _vp]),
     "pmx_dbam_coverage_signal": (_int, [_vp, _u32, ctypes.c_double, _vp]),
     "pmx_dbam_coverage_compare": (_int, [_vp, _vp, _u32, _int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),
+    "pmx_dbam_coverage_poisson": (_int, [_vp, _vp, _u32, ctypes.c_double, _u32, _u32, _vp, ctypes.c_uint64, _vp]),
     "pmx_dbam_coverage_call": (_int, [_vp, ctypes.c_double, _u32, _u32, _vp]),
     "pmx_dbam_coverage_call_rows": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmx_dbam_coverage_call_text": (_i64, [_vp, _i64, _i64, _vp, _i64]),

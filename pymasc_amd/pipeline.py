@@ -44,7 +44,7 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
         coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None, coverage_control=None,
         coverage_compare: str = "log2", coverage_pseudocount: float = 1.0, coverage_call=None, coverage_call_gap: int = 30,
-        coverage_call_length: int = 200):
+        coverage_call_length: int = 200, coverage_poisson: bool = False, coverage_lambda=(1000, 10000)):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -114,7 +114,15 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     ``<stem>_coverage_peaks.narrowPeak``, the peaks of exactly the track the coverage file holds -- the compared
     track, the signal track or the depth --: runs of at least the cutoff, linked over gaps of at most ``coverage_call_gap`` bases
     and kept from ``coverage_call_length`` bases, called on the GPU with device ingest (``coverage.DeviceCount.call``) and in numpy
-    otherwise (``coverage.Signal.call``).  No p-value is computed; ``peaks=`` reads the file in a second run.
+    otherwise (``coverage.Signal.call``).  The caller itself computes no p-value; ``peaks=`` reads the file in a second run.
+    ``coverage_poisson``: with ``coverage_control``, which it needs (ValueError): the file holds -log10 of the Poisson upper tail
+    ``P(X >= k | lambda)`` per bin instead of a compare operation -- ``k`` the treatment's mean depth per bin as
+    an integer, ``lambda`` the largest of the control's mean over the genome, at the bin and over the two windows
+    ``coverage_lambda = (small, large)`` in bases (each 0 .. 2^31 - 1, 0: off), the control scaled to the treatment's library size
+    (``coverage.factors_of("none", ...)[1]``) --, made on the GPU with device ingest (``coverage.DeviceCount.poisson``) and in numpy
+    otherwise (``coverage.Coverage.poisson``); with ``coverage_call`` the narrowPeak holds the score in column 8 as well.  It
+    excludes a given ``coverage_compare`` or ``coverage_pseudocount`` and a ``coverage_normalize`` / ``coverage_scale`` other than
+    ``"none"`` / 1 (ValueError: the treatment is not scaled, the score counts reads); ``coverage_lambda`` without it is a ValueError.
     ``gc_bias``: a genome FASTA (plain, gzip or bgzip): rank 0 also writes ``<stem>_gcbias.tab`` (pymasc_amd.gcbias, DESIGN.md
     7.19): the reads the fingerprint counts, each placed on the genome window of ``gc_window`` bases (1 .. 1024) that begins at
     its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
@@ -210,6 +218,8 @@ class _Settings:
     coverage_call: object           # None, or the cutoff: the peaks of the file's track are written beside it
     coverage_call_gap: int          # the largest gap inside a peak, and the smallest peak
     coverage_call_length: int
+    coverage_poisson: bool          # the track is the Poisson -log10 p of the treatment against coverage_control
+    coverage_lambda: tuple          # its small and its large window in bases (0: off)
     gc_bias: object                 # None, or the _GcGenome parsed once for the call
     gc_window: int
     fragments: bool
@@ -287,6 +297,18 @@ def _settings(kw: dict) -> _Settings:
             raise ValueError("coverage_control '{}' is a stream: the control is a regular file, read once per input file".format(control))
         given.update(coverage_control=_CoverageControl(control))
     given.update(coverage_compare=op, coverage_pseudocount=coverage.check_pseudocount(kw["coverage_pseudocount"], op))
+    windows = coverage.check_lambda_windows(kw["coverage_lambda"])
+    if not kw["coverage_poisson"] and windows != coverage.LAMBDA_WINDOWS:
+        raise ValueError("coverage_lambda needs coverage_poisson")
+    if kw["coverage_poisson"]:
+        if control is None:
+            raise ValueError("coverage_poisson needs coverage_control")
+        if op != "log2" or kw["coverage_pseudocount"] != 1.0:
+            raise ValueError("coverage_poisson excludes coverage_compare and coverage_pseudocount: the score is not a compare operation")
+        if normalize != "none" or given["coverage_scale"] != 1.0:
+            raise ValueError("coverage_poisson excludes coverage_normalize and coverage_scale: the treatment is not scaled (the score "
+                             "counts reads), the control is scaled to the treatment's library size")
+    given.update(coverage_poisson=bool(kw["coverage_poisson"]), coverage_lambda=windows)
     given.update(fragments=bool(kw["fragments"]), fragments_max=fragments.check_max_size(kw["fragments_max"]))
     if kw["tss"] is None and (int(kw["tss_flank"]) != tss.DEFAULT_FLANK or int(kw["tss_extend"])):
         raise ValueError("tss_flank and tss_extend need tss")
@@ -619,6 +641,8 @@ class _CoverageCount(_SideCount):
     def _compare_host(self, c, control):
         s = self.s
         a_t, a_c = self._factors(dict(zip(coverage.TOTALS, c.totals)), dict(zip(coverage.TOTALS, control.totals)), c.refs)
+        if s.coverage_poisson:
+            return c.poisson(control, s.coverage_bin, a_c, *s.coverage_lambda, s.coverage_control.path)
         return c.compare(control, s.coverage_bin, s.coverage_compare, a_t, a_c, s.coverage_pseudocount, s.coverage_normalize,
                          s.coverage_control.path)
 
@@ -628,6 +652,9 @@ class _CoverageCount(_SideCount):
         if not isinstance(control_reader, DeviceBamReader):
             raise ValueError("the coverage control '{}' is read on the host and the input on the device".format(s.coverage_control.path))
         a_t, a_c = self._factors(acc.finish(reader), control_acc.finish(control_reader), acc.refs)
+        if s.coverage_poisson:
+            acc.poisson(reader, control_acc, control_reader, s.coverage_bin, a_c, *s.coverage_lambda, s.coverage_control.path)
+            return
         acc.compare(reader, control_acc, control_reader, s.coverage_bin, s.coverage_compare, a_t, a_c, s.coverage_pseudocount,
                     s.coverage_normalize, s.coverage_control.path)
 
@@ -849,7 +876,7 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
               coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None, coverage_control=None,
               coverage_compare: str = "log2", coverage_pseudocount: float = 1.0, coverage_call=None, coverage_call_gap: int = 30,
-              coverage_call_length: int = 200) -> List[FileResult]:
+              coverage_call_length: int = 200, coverage_poisson: bool = False, coverage_lambda=(1000, 10000)) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 

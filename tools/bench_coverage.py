@@ -25,7 +25,15 @@ signal, so "compare" stands beside "signal" on the same pileup, and the text pul
 "whole"; the depth track is first made a signal at bin 1 and scale 1.0 (timed as "call_signal").  The totals and the longest peak, in
 runs and in bases, are recorded under "call".  profiles/coverage_call.json is
 python tools/bench_coverage.py --reads 20000000 --format bigwig --bin 50 --normalize cpm --control /tmp/pymasc_coverage_control.bam \
-    --control-reads 10000000 --call 1 --no-host --no-open --reps 3 --out profiles/coverage_call.json"""
+    --control-reads 10000000 --call 1 --no-host --no-open --reps 3 --out profiles/coverage_call.json
+
+--poisson [--lambda S L] (needs --control): every round also makes the p-score track behind the compared one on the
+same two pileups (pmx_dbam_coverage_poisson, timed as "poisson", so it stands beside "compare"), and the text pull, the peaks and the
+bigWig file are the p-score track's.  Recorded under "poisson": its totals, the bytes the call holds per bin (24 per bin, 12 per 256
+bins, 8 per entry of F, 20 per boundary, 16 per run), and -- from the two pileups pulled to the host once, outside the timing -- the
+longest series of a run.  profiles/coverage_poisson.json is
+python tools/bench_coverage.py --reads 20000000 --format bigwig --bin 50 --control /tmp/pymasc_coverage_control.bam \
+    --control-reads 10000000 --poisson --no-host --no-open --reps 3 --out profiles/coverage_poisson.json"""
 import argparse
 import contextlib
 import json
@@ -102,12 +110,16 @@ def main():
     ap.add_argument("--control", default=None, help="a control file: every round also makes the treatment against it")
     ap.add_argument("--control-reads", type=int, default=None, help="the reads of a control made here (default: half of --reads)")
     ap.add_argument("--compare", choices=coverage.COMPARE, default="log2", help="the operation with --control")
+    ap.add_argument("--poisson", action="store_true", help="with --control: every round also makes the p-score track, behind the compared one")
+    ap.add_argument("--lambda", dest="windows", type=int, nargs=2, default=list(coverage.LAMBDA_WINDOWS), help="the two windows of --poisson")
     ap.add_argument("--call", type=float, default=None, help="a cutoff: every round also calls the peaks of the track and pulls their lines")
     ap.add_argument("--call-gap", type=int, default=coverage.CALL_GAP, help="the largest gap inside a peak")
     ap.add_argument("--call-length", type=int, default=coverage.CALL_LENGTH, help="the smallest peak")
     ap.add_argument("--bigwig-path", default="/tmp/pymasc_coverage_bench.bw")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.poisson and (a.control is None or a.normalize != "none"):
+        ap.error("--poisson needs --control and --normalize none")
     if not os.path.exists(a.path):
         synth_bam(a.path, a.reads)
     if a.control is not None and not os.path.exists(a.control):
@@ -129,7 +141,7 @@ def main():
         res["library_version"] = int(r._L.pmx_dbam_version())
         res["table_bytes"] = 4 * (sum(r.lengths) + len(r.lengths))
         split = dict(begin=[], add=[], finish=[], signal=[], text=[], whole=[])
-        versus = dict(control=[], compare=[])
+        versus = dict(control=[], compare=[], poisson=[]) if a.poisson else dict(control=[], compare=[])
         called = dict(call_signal=[], call=[], call_text=[])
         bw = dict(sections=[], zoom_begin=[], zoom_records=[], assembly=[], whole=[])
         for rep in range(a.reps + 1):               # (the first round warms up)
@@ -153,9 +165,14 @@ def main():
                 res["compare"] = dict(acc.compare(r, cacc, rc, a.bin, a.compare, a_t, a_c, 1.0, a.normalize, a.control), bin=a.bin, op=a.compare,
                                       normalize=a.normalize, a_t=a_t, a_c=a_c, control_totals=ctotals)
                 t2 = time.perf_counter()
+                if a.poisson:                       # on the same two pileups, in the compared track's place
+                    res["poisson"] = dict(acc.poisson(r, cacc, rc, a.bin, a_c, *a.windows, a.control), bin=a.bin, a_c=a_c, windows=a.windows)
+                t3 = time.perf_counter()
                 if rep:
                     versus["control"].append(t1 - t[4])
                     versus["compare"].append(t2 - t1)
+                    if a.poisson:
+                        versus["poisson"].append(t3 - t2)
             size = sum(len(chunk) for chunk in acc.text_chunks(r, signal=signal))
             t.append(time.perf_counter())
             if a.call is not None:                  # the peaks of the track the text pull read, and their lines
@@ -193,7 +210,7 @@ def main():
                     split[name].append(t[k + 1] - t[k])
                 split["whole"].append(t[5] - t[0])
                 if rc is not None:                  # (the text pull begins behind compare)
-                    split["text"][-1] -= versus["control"][-1] + versus["compare"][-1]
+                    split["text"][-1] -= sum(v[-1] for v in versus.values())
         if rc is not None:
             split.update(versus)
         if a.call is not None:
@@ -204,6 +221,23 @@ def main():
         if a.format == "bigwig":
             res["bigwig"].update(**{k + "_s": v for k, v in bw.items()}, **{k + "_median_s": statistics.median(v) for k, v in bw.items()})
             os.unlink(a.bigwig_path)
+        if a.poisson:                               # what the call held, and the longest series: from the pileups, outside the timing
+            t_host, c_host = acc.result(r), cacc.result(rc)
+            nb = sum(-(-l // a.bin) for _n, l in acc.refs)
+            ne = runs = longest = 0
+            lengths = dict(acc.refs)
+            seen = set()
+            for name, s0, e0, k, lam in t_host.poisson_pairs(c_host, a.bin, res["poisson"]["a_c"], *a.windows):
+                gaps = int((s0[1:] > e0[:-1]).sum()) + int(s0[0] > 0) + int(e0[-1] < lengths[name])
+                ne, runs = ne + int(s0.size) + gaps, runs + int(s0.size)
+                seen.add(name)
+                up = k.astype("float64") > lam
+                if up.any():
+                    longest = max(longest, int(coverage.poisson_series(k[up], lam[up])[1].max()))
+            ne += sum(1 for name, l in acc.refs if name not in seen and l > 0)
+            assert runs == res["poisson"]["runs"]
+            held = 24 * nb + 12 * (-(-nb // 256)) + 8 * (totals["max_depth"] + 1) + 20 * ne + 16 * runs
+            res["poisson"].update(bins=nb, boundaries=ne, longest_series=longest, held_bytes=held, held_bytes_per_bin=held / nb)
         if not a.no_host:
             cols = r._fetch(0, n)
             t0 = time.perf_counter()
