@@ -103,8 +103,9 @@
 #define EV_WAVES_NCC 8
 #endif
 
+#define EV_STAMP_SLOTS 16u   // u64 per wave behind the slab's segments: room for the stamps of the diagnostic build
 #ifdef EV_STAMPS   // diagnostic build: where does a tile's time go (never defined in the shipped library)
-#define EV_NSTAMP 12
+#define EV_NSTAMP EV_STAMP_SLOTS   // 0..9 phases of a tile, 10 / 11 start and end of the workgroup, 12 / 13 flushes (cycles, count), 14 / 15 guarded fetches
 #define EV_STAMP(i)                                                                                    \
     {                                                                                                  \
         unsigned long long t_;                                                                         \
@@ -114,8 +115,17 @@
         stamp_acc[i] += t_ - stamp_last;                                                               \
         stamp_last = t_;                                                                               \
     }
+// the fetch of the next tile, waits included: slot 4 for an interior tile, slots 14 (cycles) and 15 (count) for a guarded one
+#define EV_STAMP_FETCH(guarded)                                                                        \
+    if (guarded) {                                                                                     \
+        EV_STAMP(14)                                                                                   \
+        stamp_acc[15]++;                                                                               \
+    } else {                                                                                           \
+        EV_STAMP(4)                                                                                    \
+    }
 #else
 #define EV_STAMP(i)
+#define EV_STAMP_FETCH(guarded) (void)(guarded);
 #endif
 
 // ---- LDS (dwords) -------------------------------------------------------------------------------------------------
@@ -283,8 +293,9 @@ __device__ __forceinline__ void ev_fetch_fast(EvRegs &er, const SpJobRegs &jb, u
     er.hbw = HAS_M ? *reinterpret_cast<const u32 *>(hb - 4) : 0u;
 }
 
+// (returns whether the tile took a guarded fetch: read by the -DEV_STAMPS build alone)
 template <bool HAS_M, bool BIG>
-__device__ __forceinline__ void ev_fetch_job(EvRegs &er, const SpJobRegs &jb, u32 local_tile, u32 tid, u32 nhr, u32 lo,
+__device__ __forceinline__ bool ev_fetch_job(EvRegs &er, const SpJobRegs &jb, u32 local_tile, u32 tid, u32 nhr, u32 lo,
                                              bool skip_reads = false, u32 wave = 0, u32 hi_dwords = EV_HI)
 {
     const int64_t d0 = (int64_t)local_tile * EV_TBW;
@@ -303,6 +314,7 @@ __device__ __forceinline__ void ev_fetch_job(EvRegs &er, const SpJobRegs &jb, u3
         ev_fetch<HAS_M, false, BIG>(er, jb.F, jb.R, jb.M, d0, jb.nbits, tid, nhr, lo, skip_reads, hi_dwords / 4u);
     else
         ev_fetch<HAS_M, true, BIG>(er, jb.F, jb.R, jb.M, d0, jb.nbits, tid, nhr, lo, skip_reads, hi_dwords / 4u);
+    return !interior;
 }
 
 // forward list entry: bits 0..16 biased position, 17..29 index of the first reverse read at or above it, 31 = M[x]
@@ -675,7 +687,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
     bool seg_written = false;                     // (uniform) this (workgroup, job) segment already holds a flush
     bool seg_gr_written = false;                  // (uniform) ... and its GR row (BIG: that row is also flushed alone, below)
 #ifdef EV_STAMPS
-    unsigned long long stamp_acc[EV_NSTAMP] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long stamp_acc[EV_NSTAMP] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stamp_last;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last)::"memory");
 #endif
@@ -993,7 +1005,9 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                         jn = j;
                         load_job(pj, jobs.j[jn]);
                     }
-                    ev_fetch_job<HAS_M, BIG>(er, pj, gnext - pj.tile0, tid, nhr, LO, false, wave, HI);
+                    EV_STAMP(5)
+                    const bool guarded = ev_fetch_job<HAS_M, BIG>(er, pj, gnext - pj.tile0, tid, nhr, LO, false, wave, HI);
+                    EV_STAMP_FETCH(guarded)
                 }
             } else if (gnext < g1) {
                 if (gnext >= pj.tile_end) {   // rare: the next tile belongs to the next job
@@ -1005,7 +1019,11 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                     const u32 lim = pj.tile_end < g1 ? pj.tile_end : g1;
                     act_var = gnext + sg < lim;
                 }
-                if (NSG == 1 || act_var) ev_fetch_job<HAS_M, BIG>(er, pj, gnext + sg - pj.tile0, tid, nhr, LO, VERDICT && next_skip, wave, HI);
+                if (NSG == 1 || act_var) {
+                    EV_STAMP(4)
+                    const bool guarded = ev_fetch_job<HAS_M, BIG>(er, pj, gnext + sg - pj.tile0, tid, nhr, LO, VERDICT && next_skip, wave, HI);
+                    EV_STAMP_FETCH(guarded)
+                }
             } else if (NSG > 1) {
                 act_var = false;
             }
@@ -1336,19 +1354,36 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
             seg_gr_written = true;
         } else if (leaving || risk) {
             // histograms of this (workgroup, job) -> its slab segment (added to it from the second flush on); cleared
+            EV_STAMP(9)
             __syncthreads();
             u32 *seg = slab + (size_t)(blockIdx.x + ji) * EV_SEG_ROWS * HN;
             const bool add = seg_written;
+            if (!BIG) {
+                // max_shift <= 1023: thread t owns cells 4 t .. 4 t + 3 of EVERY row.  Without a track that is row 0; with one the
+                // rows are finished on chip first and leave in one block of 16-byte stores (the !BIG arm below)
+                if (!HAS_M) {
+                    const uint4 w = *reinterpret_cast<const uint4 *>(hN + 4 * gt);
+                    *reinterpret_cast<uint4 *>(hN + 4 * gt) = make_uint4(0, 0, 0, 0);
+                    uint4 *d0 = reinterpret_cast<uint4 *>(seg + 4 * gt);
+                    uint4 v = w;
+                    if (add) {
+                        const uint4 o = *d0;
+                        v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
+                    }
+                    *d0 = v;
+                }
+            } else {
 #pragma nounroll   // (unrolled, its index registers are hoisted out of the tile loop and spill)
-            for (u32 i = gt; i < HN; i += NT) {
-                const u32 w = hN[i];
-                hN[i] = 0;
-                if (HAS_M) {
-                    const u32 lo16 = w & 0xffffu, hi16 = w >> 16;
-                    seg[i] = add ? seg[i] + lo16 : lo16;
-                    seg[2 * HN + i] = add ? seg[2 * HN + i] + hi16 : hi16;
-                } else {
-                    seg[i] = add ? seg[i] + w : w;
+                for (u32 i = gt; i < HN; i += NT) {
+                    const u32 w = hN[i];
+                    hN[i] = 0;
+                    if (HAS_M) {
+                        const u32 lo16 = w & 0xffffu, hi16 = w >> 16;
+                        seg[i] = add ? seg[i] + lo16 : lo16;
+                        seg[2 * HN + i] = add ? seg[2 * HN + i] + hi16 : hi16;
+                    } else {
+                        seg[i] = add ? seg[i] + w : w;
+                    }
                 }
             }
             if (HAS_M) {
@@ -1394,25 +1429,39 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                     // remains for k_events_finish is a column sum, which any number of workgroups can share (one workgroup per row
                     // read chromosome 1's 103 segments at ~30 GB/s: 17 us).  Arithmetic modulo 2^32: every total is below 2^32
                     // (the launcher keeps vectors of 2^32 bits and more off this path).
+                    // Every row is FINISHED ON CHIP first and the segment is then written in one straight block of 16-byte stores
+                    // per thread, the scalar row and the chromosome's totals behind it.  (Row by row, where each was finished, the
+                    // addresses the compiler had spilled came back from scratch in front of each later store, and a scratch load
+                    // waits on vmcnt, which counts stores too: six store round trips one after the other at the end of every
+                    // workgroup)  Thread t owns cells 4 t .. 4 t + 3 of every row.  Five barriers: the recurrence
+                    // row A is gathered from the list pool (dead between the event loops and the next tile's emit), so nobody waits
+                    // before clearing GF; the scan totals of the Deltas have slots of their own; and the scalars are cleared behind
+                    // the second barrier, when everybody has read them.
                     // (a) the scalars of this flush: the recurrence starts from them
+                    u32 ft = gt;
+                    u32 z = 0;
+                    asm volatile("" : "+v"(ft), "+v"(z));   // (opaque: addresses derived from gt, and a quad of zeros, are hoisted out of
+                    const uint4 zq = make_uint4(z, z, z, z);   // the tile loop, live across it, and spill)
                     {
                         u32 v[4] = {cntB, cnt0, cntM, cntU};
 #pragma unroll
                         for (u32 k = 0; k < 4; k++)
                             for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-                        if ((gt & 63u) == 0) {
+                        if ((ft & 63u) == 0) {
 #pragma unroll
                             for (u32 k = 0; k < 4; k++)
                                 if (k < 2 || (DO_MLEN && !(RUNS_PER_TILE && k == 3))) atomicAdd(&xch[8 + 2 + k], v[k]);   // (RUNS_PER_TILE: cntU is not used)
                         }
                         cntB = cnt0 = cntM = cntU = 0;
                     }
-                    __syncthreads();
-                    // (RUNS_PER_TILE: twice the run starts, in two parts: see the emit)
+                    __syncthreads();   // F1: the scalars of this flush
                     const u32 a0 = xch[8 + 4], runs = RUNS_PER_TILE ? (xch[8 + 5] + xch[0]) >> 1 : xch[8 + 5];
-                    // (b) cells 4 t .. 4 t + 3 of the three rows
-                    const u32 k0 = 4 * gt;
+                    u32 vs = 0;        // the scalar row's word of threads 0 .. 5
+                    if (ft < 6) vs = (RUNS_PER_TILE && ft == 5) ? runs : xch[8 + ft];
+                    const u32 k0 = 4 * ft;
                     const uint4 wgf = *reinterpret_cast<const uint4 *>(hGF + k0), wgr = *reinterpret_cast<const uint4 *>(hGF + 1024 + k0);
+                    *reinterpret_cast<uint4 *>(hGF + k0) = zq;
+                    *reinterpret_cast<uint4 *>(hGF + 1024 + k0) = zq;
                     const u32 cgf[4] = {wgf.x, wgf.y, wgf.z, wgf.w}, cgr[4] = {wgr.x, wgr.y, wgr.z, wgr.w};
                     u32 pgf[4], pgr[4], dl[4], tGF = 0, tGR = 0, tX = 0;
 #pragma unroll
@@ -1428,14 +1477,16 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                     }
                     u32 sGF = tGF, sGR = tGR, sX = tX;
                     wave_inclusive_scan3(sGF, sGR, sX);
-                    if ((gt & 63u) == 63u) {
-                        wt[0 + (gt >> 6)] = sGF;
-                        wt[4 + (gt >> 6)] = sGR;
-                        wt[8 + (gt >> 6)] = sX;
+                    if ((ft & 63u) == 63u) {
+                        wt[0 + (ft >> 6)] = sGF;
+                        wt[4 + (ft >> 6)] = sGR;
+                        wt[8 + (ft >> 6)] = sX;
                     }
-                    __syncthreads();
+                    __syncthreads();   // F2: the waves' totals
+                    if (ft < 6) xch[8 + ft] = 0;   // (a0, runs and vs were read between F1 and F2; added to again behind the next tile's B0)
+                    if (RUNS_PER_TILE && ft == 6) xch[0] = 0;
                     u32 bGF = sGF - tGF, bGR = sGR - tGR, bX = sX - tX;
-                    for (u32 w = 0; w < (gt >> 6); w++) {
+                    for (u32 w = 0; w < (ft >> 6); w++) {
                         bGF += wt[w];
                         bGR += wt[4 + w];
                         bX += wt[8 + w];
@@ -1449,51 +1500,69 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                         ex[j] = tD;           // ... and the sum of the Deltas below k inside the thread
                         tD += dl[j];
                     }
-                    {
-                        uint4 *d1 = reinterpret_cast<uint4 *>(seg + 1 * 1024 + k0), *d3 = reinterpret_cast<uint4 *>(seg + 3 * 1024 + k0);
-                        uint4 v1 = make_uint4(pgf[0], pgf[1], pgf[2], pgf[3]), v3 = make_uint4(pgr[0], pgr[1], pgr[2], pgr[3]);
-                        if (add) {
-                            const uint4 o1 = *d1, o3 = *d3;
-                            v1.x += o1.x; v1.y += o1.y; v1.z += o1.z; v1.w += o1.w;
-                            v3.x += o3.x; v3.y += o3.y; v3.z += o3.z; v3.w += o3.w;
-                        }
-                        *d1 = v1;
-                        *d3 = v3;
-                    }
+                    ev_v4u v1 = {pgf[0], pgf[1], pgf[2], pgf[3]}, v3 = {pgr[0], pgr[1], pgr[2], pgr[3]}, v5 = {0, 0, 0, 0};
                     if (DO_MLEN) {
-                        // A(k) = a0 + the sum of Delta(t) over t < k, then row 5 holds A(|c - d|) for the shifts d = 0 .. S
+                        // A(k) = a0 + the sum of Delta(t) over t < k, then row 5 holds A(|c - d|) for the shifts d = 0 .. S (zeros
+                        // above S, which nothing reads: a quad is stored whole)
                         u32 sD = wave_inclusive_scan(tD);
-                        __syncthreads();                    // (wt was read above)
-                        if ((gt & 63u) == 63u) wt[12 + (gt >> 6)] = sD;
-                        __syncthreads();
+                        if ((ft & 63u) == 63u) wt[12 + (ft >> 6)] = sD;
+                        __syncthreads();   // F3
                         u32 bD = sD - tD;
-                        for (u32 w = 0; w < (gt >> 6); w++) bD += wt[12 + w];
-                        *reinterpret_cast<uint4 *>(hGF + k0) = make_uint4(a0 + bD + ex[0], a0 + bD + ex[1], a0 + bD + ex[2], a0 + bD + ex[3]);
-                        __syncthreads();
+                        for (u32 w = 0; w < (ft >> 6); w++) bD += wt[12 + w];
+                        static_assert(L::POOL >= 1024 && L::LF % 4 == 0, "the recurrence row in the list pool");
+                        *reinterpret_cast<uint4 *>(LF + k0) = make_uint4(a0 + bD + ex[0], a0 + bD + ex[1], a0 + bD + ex[2], a0 + bD + ex[3]);
+                        __syncthreads();   // F4
 #pragma unroll
                         for (u32 j = 0; j < 4; j++) {
                             const u32 d = k0 + j;
-                            if (d <= S) {
-                                const int32_t k = (int32_t)c - (int32_t)d;
-                                const u32 av = hGF[k < 0 ? -k : k];
-                                u32 *de = seg + (size_t)5 * 1024 + d;
-                                *de = add ? *de + av : av;
-                            }
+                            const int32_t k = (int32_t)c - (int32_t)d;
+                            v5[j] = d <= S ? LF[k < 0 ? -k : k] : 0u;
                         }
-                        __syncthreads();
                     }
-                    *reinterpret_cast<uint4 *>(hGF + k0) = make_uint4(0, 0, 0, 0);
-                    *reinterpret_cast<uint4 *>(hGF + 1024 + k0) = make_uint4(0, 0, 0, 0);
-                    // (c) the scalar row of the segment and the chromosome's totals (k_events_finish reads six words per job)
-                    if (gt < 6) {
-                        const u32 v = (RUNS_PER_TILE && gt == 5) ? runs : xch[8 + gt];
-                        u32 *ds = seg + 4 * HN + gt;
-                        *ds = add ? *ds + v : v;
-                        if (v) atomicAdd(EV_JOBSUM(jobstat) + 6 * ji + gt, (unsigned long long)v);
+                    const uint4 wn = *reinterpret_cast<const uint4 *>(hN + k0);
+                    *reinterpret_cast<uint4 *>(hN + k0) = zq;
+                    ev_v4u v0 = {wn.x & 0xffffu, wn.y & 0xffffu, wn.z & 0xffffu, wn.w & 0xffffu}, v2 = {wn.x >> 16, wn.y >> 16, wn.z >> 16, wn.w >> 16};
+                    // the segment: a uniform base (in scalar registers) + one 32-bit byte offset per thread and row
+                    char *const sb = reinterpret_cast<char *>(slab + (size_t)__builtin_amdgcn_readfirstlane(blockIdx.x + ji) * (EV_SEG_ROWS * 1024u));
+                    // (each row's base made opaque: folded into one 64-bit address per thread and row, they cost ten registers more)
+                    char *rb[EV_SEG_ROWS];
+#pragma unroll
+                    for (u32 r = 0; r < EV_SEG_ROWS; r++) {
+                        u32 ro = r * 4096u;
+                        asm volatile("" : "+s"(ro));
+                        rb[r] = sb + ro;
                     }
-                    __syncthreads();
-                    if (gt < 6) xch[8 + gt] = 0;
-                    if (RUNS_PER_TILE && gt == 6) xch[0] = 0;
+                    const u32 vo = 16u * ft;
+                    ev_v4u *const d0 = reinterpret_cast<ev_v4u *>(rb[0] + vo), *const d1 = reinterpret_cast<ev_v4u *>(rb[1] + vo),
+                                 *const d2 = reinterpret_cast<ev_v4u *>(rb[2] + vo), *const d3 = reinterpret_cast<ev_v4u *>(rb[3] + vo),
+                                 *const d5 = reinterpret_cast<ev_v4u *>(rb[5] + vo);
+                    u32 *const ds = reinterpret_cast<u32 *>(rb[4] + 4u * (ft < 6 ? ft : 0u));
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (!add) {
+                        *d0 = v0;
+                        *d1 = v1;
+                        *d2 = v2;
+                        *d3 = v3;
+                        if (DO_MLEN) *d5 = v5;
+                        if (ft < 6) *ds = vs;
+                    } else {
+                        // a later flush of this segment (its cells are this thread's own, and were written by it): added in the L2, by
+                        // atomics without a return value -- no load of the old values, no wait, and no registers for them (21 more
+                        // here, next to the prefetched tile's 31, pushed the claimer's draw into scratch inside the tile loop)
+#pragma unroll
+                        for (u32 j = 0; j < 4; j++) {
+                            __hip_atomic_fetch_add(reinterpret_cast<u32 *>(d0) + j, v0[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            __hip_atomic_fetch_add(reinterpret_cast<u32 *>(d1) + j, v1[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            __hip_atomic_fetch_add(reinterpret_cast<u32 *>(d2) + j, v2[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            __hip_atomic_fetch_add(reinterpret_cast<u32 *>(d3) + j, v3[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (DO_MLEN) __hip_atomic_fetch_add(reinterpret_cast<u32 *>(d5) + j, v5[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        if (ft < 6) __hip_atomic_fetch_add(ds, vs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    // the chromosome's totals (k_events_finish reads six words per job): THIS flush's scalars, behind the stores
+                    if (ft < 6) {
+                        if (vs) atomicAdd(EV_JOBSUM(jobstat) + 6 * ji + ft, (unsigned long long)vs);
+                    }
                 }
             }
             accF = 0;
@@ -1531,6 +1600,10 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                 seg_written = false;
                 seg_gr_written = false;
             }
+#ifdef EV_STAMPS   // a flush, its entry barrier included (what is left in the store queue is in the end stamp, slot 11)
+            EV_STAMP(12)
+            stamp_acc[13]++;
+#endif
         }
         if (jn != ji) {
             if (BIG && DO_MLEN && !EE_LDS) ev_zero_row5(slab, blockIdx.x + jn, HN, gt, NT);   // (the barrier at the top of the loop follows)

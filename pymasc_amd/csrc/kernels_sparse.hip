@@ -2797,7 +2797,7 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
         std::vector<SpJobDev> tab(n);
         if (lo) PMX_HIP(hipMemsetAsync(d_jobstat, 0, stat_bytes, ctx->stream));   // (the next launch's jobs)
         const LaunchPlan p = plan_launch(ctx, ev.data(), n, false, pl.wg_per_cu, tab.data(), EV_TB);
-        rc = pmx_ensure_slab(ctx, (size_t)(p.nwg + n) * EV_SEG_ROWS * pl.hn + (size_t)p.nwg * 4 * pl.nsg * 12 * 2 + 64);
+        rc = pmx_ensure_slab(ctx, (size_t)(p.nwg + n) * EV_SEG_ROWS * pl.hn + (size_t)p.nwg * 4 * pl.nsg * EV_STAMP_SLOTS * 2 + 64);
         if (rc) return rc;
         SpJobTableRef ref;
         rc = upload_table(ctx, tab, &ref);
@@ -3012,7 +3012,7 @@ static int launch_cc_events(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, u
         // (tile-range jobs -- a rank's share of a chromosome, pmx_cc_batch_ranges_dev -- exist for this launch only: the window
         // launches behind it see whole chromosomes and take the tiles it flagged, which lie inside the ranges)
         const LaunchPlan pe = plan_launch(ctx, vj.data(), n, false, per_cu, tab.j, EV_TB, true);
-        rc = pmx_ensure_slab(ctx, (size_t)(pe.nwg + n) * EV_SEG_ROWS * 1024 + (size_t)pe.nwg * 4 * 12 * 2 + 64);
+        rc = pmx_ensure_slab(ctx, (size_t)(pe.nwg + n) * EV_SEG_ROWS * 1024 + (size_t)pe.nwg * 4 * EV_STAMP_SLOTS * 2 + 64);
         if (rc) return rc;
         if (known && has_m && ((size_t)pe.nwg + n > fl.claim_words || pe.total >= (1u << EV_CLAIM_JOB_SHIFT))) {   // (the launches that claim)
             pmx_set_error("k_cc_events: %u workgroups + %u jobs, %u tiles exceed the claim counters", pe.nwg, n, pe.total);

@@ -41,23 +41,33 @@ per_cu = int(os.environ.get("EV_PER_CU", 5 if with_m else 8))
 nwg = min(256 * per_cu, ntiles)
 tpw = -(-ntiles // nwg); nwg = -(-ntiles // tpw)
 off = (nwg + len(vecs)) * 6 * 1024 * 4   # EV_SEG_ROWS
-NS = 12
-NP = 10   # slots 0..9: phases of a tile, in shader cycles; slots 10, 11 of wave 0: start and end of the workgroup
+NS = 16   # EV_STAMP_SLOTS
+NP = 10   # slots 0..9: phases of a tile, in shader cycles; slots 10, 11 of wave 0: start and end of the workgroup;
+          # 12, 13: cycles and number of flushes; 14, 15: cycles and number of guarded fetches (slot 4: the interior ones)
 buf = np.zeros(nwg * 4 * NS, dtype=np.uint64)
 Lb.pmx_debug_read_slab.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
 rc = Lb.pmx_debug_read_slab(ctx._h, off, buf.ctypes.data, buf.nbytes)
 assert rc == 0
 raw = buf.reshape(nwg, 4, NS)
 a = raw[:, :, :NP].astype(np.float64)
-tot = a.sum(axis=2).mean()
+tot = (a.sum(axis=2) + raw[:, :, 12] + raw[:, :, 14]).mean()
 print(f"mode={mode} track={track} nwg={nwg} tiles/wg={tpw} cycles per wave lifetime={tot:.0f}  per tile={tot / tpw:.0f}")
 lab = {0: "B0 barrier wait", 1: "counts + M store + scans", 2: "Bs barrier wait", 3: "totals + emit lists", 4: "prefetch issue",
        5: "B1 barrier wait", 6: "events: forward x reverse pairs", 8: "R0 (reverse reads: M[p] M[p+c])", 7: "events: edges x reads, edge pairs",
-       9: "flush / loop tail"}
+       9: "loop tail (without the flushes)"}
 for i in range(NP):
     print(f"  {lab[i]:32s} {a[:, :, i].mean() / tpw:9.0f} cyc/tile  {100 * a[:, :, i].sum() / a.sum():5.1f} %")
 for w in range(4):
     print("  wave", w, " ".join(f"{a[:, w, i].mean() / tpw:7.0f}" for i in range(NP)))
+
+# ---- the cold path of a workgroup: flushes and guarded fetches (boundary tiles), per occurrence and wave
+fl_c, fl_n = raw[:, :, 12].astype(np.float64), raw[:, :, 13].astype(np.float64)
+gf_c, gf_n = raw[:, :, 14].astype(np.float64), raw[:, :, 15].astype(np.float64)
+tiles_w = a[:, :, 4] * 0 + tpw   # (claimed tiles move between workgroups: the static share stands in for the count)
+print(f"  flushes: {fl_n.sum() / 4:.0f} in {nwg} workgroups, {fl_c.sum() / max(1.0, fl_n.sum()):9.0f} cycles per flush and wave"
+      f" (longest wave mean {np.max(fl_c / np.maximum(1, fl_n)):9.0f})")
+print(f"  guarded fetches: {gf_n.sum() / 4:.0f}, {gf_c.sum() / max(1.0, gf_n.sum()):9.0f} cycles per fetch and wave;"
+      f" interior fetches: {a[:, :, 4].sum() / max(1.0, (tiles_w - gf_n).sum()):9.0f} cycles per fetch and wave")
 
 # ---- workgroup lifetimes.  The constant 100 MHz clock (s_memrealtime), one reading at kernel entry and one behind the last
 # flush: the shader clock (s_memtime) of one XCD says nothing about another's, and the question is who waits for whom.
@@ -76,6 +86,14 @@ print(f"  first end   {en.min():8.2f}   last end   {en.max():8.2f}")
 print(f"  mean lifetime {life.mean():8.2f}   shortest {life.min():8.2f}   longest {life.max():8.2f}")
 print(f"  idle share 1 - sum(lifetimes) / (workgroups x (last end - first start)) = {100 * idle:5.2f} %")
 print(f"    of which before the start {100 * (st - st.min()).sum() / (nwg * span):5.2f} %, behind the end {100 * (en.max() - en).sum() / (nwg * span):5.2f} %")
+# the workgroups that hold a guarded tile, or flush more than once (two jobs), against the rest
+cold = (raw[:, 0, 15] > 0) | (raw[:, 0, 13] > 1)
+for name, sel in (("with a guarded tile or two jobs", cold), ("the rest", ~cold)):
+    if sel.any():
+        print(f"  {name:32s} {int(sel.sum()):5d} workgroups  mean lifetime {life[sel].mean():8.2f}  mean end {en[sel].mean():8.2f}  last end {en[sel].max():8.2f}")
+order = np.argsort(en)[::-1][:20]
+print("  the last twenty to end (workgroup: end us, guarded fetches, flushes): " +
+      ", ".join(f"{int(w)}: {en[w]:.2f} {int(raw[w, 0, 15])} {int(raw[w, 0, 13])}" for w in order))
 hist, edges = np.histogram(en, bins=10, range=(en.min(), en.max()))
 print("  end times, ten bins from the first to the last end:")
 for k in range(10):
