@@ -340,6 +340,15 @@ int pmx_debug_set_max_workgroups(pmx_ctx *ctx, uint32_t n);
  * workgroups with an odd index draw nothing as owners, so that every tile of their ranges but the first per chromosome is
  * taken through the helping path; 2: nobody helps -- the static walk.  No effect on results. */
 int pmx_debug_set_claim_mode(pmx_ctx *ctx, uint32_t mode);
+/* The order in which the hinted event kernel with a track (the instantiations that claim tiles) gives tile ranges to its
+ * workgroups in later launches.  The device is filled in layers of `width` workgroups in launch order, one per compute unit
+ * and layer; range v goes to the workgroup pmx_debug_wg_order names, so that neighbouring ranges -- a chromosome's group --
+ * come from different layers.  0 (default): width = the device's compute units; 1: ranges in launch order.  No effect on
+ * results. */
+int pmx_debug_set_wg_layer(pmx_ctx *ctx, uint32_t width);
+/* out[b] = the range workgroup b of a launch of nwg workgroups owns at layer width `width` >= 1: a permutation of 0 .. nwg - 1,
+ * the identity for width 1 and for nwg <= width.  Host only. */
+int pmx_debug_wg_order(uint32_t nwg, uint32_t width, uint32_t *out);
 /* Copies what the last event pass of max_shift <= 1023 left in its flag area to host memory (after a synchronisation), at
  * most `cap` bytes, and stores their number in *bytes: the dense-tile flags of the cross-correlation window kernel, those of
  * the autocorrelation window kernel (equally long), 16 bytes of flagged-tile counters, the job statistics, and the claim

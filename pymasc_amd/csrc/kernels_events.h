@@ -105,7 +105,7 @@
 
 #define EV_STAMP_SLOTS 16u   // u64 per wave behind the slab's segments: room for the stamps of the diagnostic build
 #ifdef EV_STAMPS   // diagnostic build: where does a tile's time go (never defined in the shipped library)
-#define EV_NSTAMP EV_STAMP_SLOTS   // 0..9 phases of a tile, 10 / 11 start and end of the workgroup, 12 / 13 flushes (cycles, count), 14 / 15 guarded fetches
+#define EV_NSTAMP EV_STAMP_SLOTS   // 0..9 phases of a tile, 10 / 11 start and end of the workgroup (wave 1's 10: HW_ID | XCC_ID << 32), 12 / 13 flushes (cycles, count), 14 / 15 guarded fetches
 #define EV_STAMP(i)                                                                                    \
     {                                                                                                  \
         unsigned long long t_;                                                                         \
@@ -488,6 +488,20 @@ __device__ __forceinline__ void ev_zero_row5(u32 *__restrict__ slab, u32 segment
 // 2 = nobody helps (the static walk, with the claims' bookkeeping).
 #define EV_NO_TILE 0xffffffffu
 #define EV_CLAIM_JOB_SHIFT 24u   // a claimed tile travels as tile | job << 24 (at most 32 jobs of < 2^16 tiles: 2^21 tiles)
+
+// The range a physical block owns.  The dispatcher fills the device in LAYERS of `width` blocks in blockIdx
+// order -- one block per CU and layer --, and ranges handed out in that order give a chromosome's group the blocks of one
+// layer only.  Here block b of layer b / width, at position b % width in it, owns range v, with the positions' ranges
+// laid side by side: logical neighbours v, v + 1 come from different layers, and every stretch of `layers` ranges holds
+// one block of each.  The last layer may be partial (r blocks): positions below r have nl layers, the others nl - 1.
+// A bijection on [0, nwg); the identity for width == 1 and for nwg <= width.  (width >= 1)
+__host__ __device__ __forceinline__ u32 ev_wg_virtual(u32 b, u32 nwg, u32 width)
+{
+    const u32 nl = (nwg + width - 1) / width;
+    const u32 r = nwg - (nl - 1) * width;
+    const u32 layer = b / width, pos = b - layer * width;
+    return pos < r ? pos * nl + layer : r * nl + (pos - r) * (nl - 1) + layer;
+}
 struct EvClaimer {
     u32 cj, jl;                // job being drawn from, the last job of my range
     u32 v, pstart, plen;       // the piece being drawn from: its workgroup, its first claimable tile, their number
@@ -498,10 +512,11 @@ struct EvClaimer {
 // (wave 0, all lanes, uniform) the pieces of job c.cj with tiles left -> c.v / c.pstart / c.plen.  The counters are read past
 // the L1 (another CU's adds are made in the L2 / at the memory side: a line kept here would show an exhausted piece as open forever).
 // (the job's fields come by value: see FIRST_JOB on tables handed to helpers by reference)
-__device__ __forceinline__ bool ev_claim_scan(EvClaimer &c, u32 wf, u32 wl, u32 t0, u32 te, const u32 *claim, u32 tiles_per_wg, u32 lane)
+// (me: the range the calling workgroup owns, see ev_wg_virtual)
+__device__ __forceinline__ bool ev_claim_scan(EvClaimer &c, u32 me, u32 wf, u32 wl, u32 t0, u32 te, const u32 *claim, u32 tiles_per_wg, u32 lane)
 {
     const u32 n = wl - wf + 1;
-    const u32 s = blockIdx.x + 1 > wl ? 0u : blockIdx.x + 1 - wf;   // the piece behind mine (round to the first)
+    const u32 s = me + 1 > wl ? 0u : me + 1 - wf;   // the piece behind mine (round to the first)
     for (u32 base = 0; base < n; base += 64) {
         const u32 idx = base + lane;
         const bool in = idx < n;
@@ -543,7 +558,7 @@ __global__ void __launch_bounds__(256 * NSG, BIG ? 4 : (HAS_M ? (DEEP ? 4 : EV_W
 k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, u32 S, u32 nhr, u32 max_lag,
             u32 hn_arg, u32 lo_arg, u32 hi_arg, u32 *__restrict__ slab, unsigned char *__restrict__ tile_flags,
             unsigned char *__restrict__ tile_flags_ac, u32 *__restrict__ n_flagged, u32 *__restrict__ jobstat,
-            u32 *__restrict__ claim, u32 claim_mode)
+            u32 *__restrict__ claim, u32 claim_mode, u32 wg_layer)
 {
     typedef EvLds<HAS_M, BIG, DEEP> L;
     // tiles are claimed, not walked (see EvClaimer); `claim` and `claim_mode` are theirs alone.  With a track only: the NCC-only
@@ -585,17 +600,24 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
     const u32 gt = threadIdx.x;              // thread of the workgroup (histogram clears / flushes)
     const u32 tid_ = NSG > 1 ? (threadIdx.x & 255u) : threadIdx.x;   // thread of the sub-group
     const u32 wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);      // wave of the sub-group
-    const u32 g0 = blockIdx.x * tiles_per_wg;
+    // the range this block owns: under CLAIMS the blocks of a CU's dispatch layers are interleaved (ev_wg_virtual; wg_layer is the
+    // layers' width, 1 = the order of blockIdx); everything below that is indexed by range -- tiles, pieces, slab segments, claim
+    // counters -- takes wv.  The other instantiations keep blockIdx: without helping the order of the ranges gains nothing.
+    const u32 wv = CLAIMS ? __builtin_amdgcn_readfirstlane(ev_wg_virtual(blockIdx.x, gridDim.x, wg_layer)) : blockIdx.x;
+    const u32 g0 = wv * tiles_per_wg;
     const u32 g1 = g0 + tiles_per_wg < total_tiles ? g0 + tiles_per_wg : total_tiles;
     if (g0 >= g1) return;
 #ifdef EV_STAMPS   // the workgroup's start on the constant 100 MHz clock, which the XCDs share (their shader clocks are their own)
     unsigned long long stamp_t0;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_t0)::"memory");
+    // ... and where the dispatcher placed it: HW_ID (CU 8..11, SH 12, SE 13..15) and the XCC's number
+    u32 stamp_hw, stamp_xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(stamp_hw), "=s"(stamp_xcc));
 #endif
 
     FIRST_JOB(ji, JT, jobs, njobs, g0)
     u32 jn = ji;
-    if (BIG && DO_MLEN && !EE_LDS) ev_zero_row5(slab, blockIdx.x + ji, HN, gt, NT);
+    if (BIG && DO_MLEN && !EE_LDS) ev_zero_row5(slab, wv + ji, HN, gt, NT);
     EvRegs er;
     SpJobRegs pj;   // job of the tiles being prefetched (index jn), held in scalar registers
     load_job(pj, jobs.j[ji]);
@@ -636,7 +658,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
             }
             if (!cl.help_none && (cl.help_all || cl.cj == cl.jl)) {
                 const u32 t0 = jobs.j[cl.cj].tile0;
-                if (ev_claim_scan(cl, jobs.j[cl.cj].wg_first, jobs.j[cl.cj].wg_last, t0, t0 + jobs.j[cl.cj].ntiles, claim, tiles_per_wg, lane0)) {
+                if (ev_claim_scan(cl, wv, jobs.j[cl.cj].wg_first, jobs.j[cl.cj].wg_last, t0, t0 + jobs.j[cl.cj].ntiles, claim, tiles_per_wg, lane0)) {
                     cl.valid = true;
                     continue;
                 }
@@ -645,7 +667,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
             cl.cj++;
             if (cl.cj > cl.jl) return EV_NO_TILE;
             const u32 t0 = jobs.j[cl.cj].tile0, te = t0 + jobs.j[cl.cj].ntiles;
-            cl.v = blockIdx.x;
+            cl.v = wv;
             cl.pstart = t0 + 1;
             cl.plen = (te < g1 ? te : g1) - t0 - 1;
             cl.valid = !cl.help_all;
@@ -656,9 +678,9 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
         cl.cj = ji;
         cl.jl = ji;
         while (cl.jl + 1 < njobs && jobs.j[cl.jl + 1].tile0 < g1) cl.jl++;
-        cl.help_all = claim_mode == 1 && (blockIdx.x & 1u);
+        cl.help_all = claim_mode == 1 && (wv & 1u);
         cl.help_none = claim_mode == 2;
-        cl.v = blockIdx.x;             // my piece of the first job: tile g0 is mine as it stands
+        cl.v = wv;                     // my piece of the first job: tile g0 is mine as it stands
         cl.pstart = g0 + 1;
         cl.plen = (pj.tile_end < g1 ? pj.tile_end : g1) - g0 - 1;
         cl.valid = !cl.help_all;
@@ -1060,7 +1082,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                 // workgroups), and the pairs are few -- ~60 edges per tile, ~4 partners each --: they are added straight to row 5
                 // of the (workgroup, job) segment in the slab with device-scope atomics (zeroed when the workgroup entered
                 // the job).  This replaces the pair pass over M (k_autocorr_pairs: 0.44 ms of config 5's 3.7, M read twice).
-                u32 *const gEE = slab + ((size_t)(blockIdx.x + ji) * EV_SEG_ROWS + 5u) * HN;
+                u32 *const gEE = slab + ((size_t)(wv + ji) * EV_SEG_ROWS + 5u) * HN;
                 const u32 nEt = TE0 + TE1;
                 // (one wave per block of 64 edges.  Tried: every wave walking all edges and taking every fourth partner, as in the
                 // edge events -- four times the atomic instructions with a quarter of the lanes each: 3.45 -> 3.5-3.8 ms, unstable)
@@ -1333,7 +1355,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
 #endif
         if (risk_gr_only) {
             __syncthreads();
-            u32 *seg = slab + (size_t)(blockIdx.x + ji) * EV_SEG_ROWS * HN;
+            u32 *seg = slab + (size_t)(wv + ji) * EV_SEG_ROWS * HN;
             const bool add = seg_gr_written;
 #pragma nounroll
             for (u32 k = gt; k < (HN >> 1); k += NT) {
@@ -1356,7 +1378,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
             // histograms of this (workgroup, job) -> its slab segment (added to it from the second flush on); cleared
             EV_STAMP(9)
             __syncthreads();
-            u32 *seg = slab + (size_t)(blockIdx.x + ji) * EV_SEG_ROWS * HN;
+            u32 *seg = slab + (size_t)(wv + ji) * EV_SEG_ROWS * HN;
             const bool add = seg_written;
             if (!BIG) {
                 // max_shift <= 1023: thread t owns cells 4 t .. 4 t + 3 of EVERY row.  Without a track that is row 0; with one the
@@ -1523,7 +1545,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
                     *reinterpret_cast<uint4 *>(hN + k0) = zq;
                     ev_v4u v0 = {wn.x & 0xffffu, wn.y & 0xffffu, wn.z & 0xffffu, wn.w & 0xffffu}, v2 = {wn.x >> 16, wn.y >> 16, wn.z >> 16, wn.w >> 16};
                     // the segment: a uniform base (in scalar registers) + one 32-bit byte offset per thread and row
-                    char *const sb = reinterpret_cast<char *>(slab + (size_t)__builtin_amdgcn_readfirstlane(blockIdx.x + ji) * (EV_SEG_ROWS * 1024u));
+                    char *const sb = reinterpret_cast<char *>(slab + (size_t)__builtin_amdgcn_readfirstlane(wv + ji) * (EV_SEG_ROWS * 1024u));
                     // (each row's base made opaque: folded into one 64-bit address per thread and row, they cost ten registers more)
                     char *rb[EV_SEG_ROWS];
 #pragma unroll
@@ -1606,7 +1628,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
 #endif
         }
         if (jn != ji) {
-            if (BIG && DO_MLEN && !EE_LDS) ev_zero_row5(slab, blockIdx.x + jn, HN, gt, NT);   // (the barrier at the top of the loop follows)
+            if (BIG && DO_MLEN && !EE_LDS) ev_zero_row5(slab, wv + jn, HN, gt, NT);   // (the barrier at the top of the loop follows)
             if (VERDICT) {
                 job_mode = 0;
                 next_skip = false;
@@ -1624,6 +1646,7 @@ k_cc_events(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, 
 #ifdef EV_STAMPS
     stamp_acc[10] = stamp_t0;   // slots 10 and 11: the workgroup's start and end (tools_ev_stamps.py reads wave 0's)
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_acc[11])::"memory");
+    if ((gt >> 6) == 1) stamp_acc[10] = (unsigned long long)stamp_hw | ((unsigned long long)stamp_xcc << 32);   // wave 1's slot 10: the placement
     if ((gt & 63) == 0) {
         unsigned long long *dbg = reinterpret_cast<unsigned long long *>(slab + (size_t)(gridDim.x + njobs) * EV_SEG_ROWS * HN);
         for (int i = 0; i < EV_NSTAMP; i++) dbg[((size_t)blockIdx.x * 4 * NSG + (gt >> 6)) * EV_NSTAMP + i] = stamp_acc[i];

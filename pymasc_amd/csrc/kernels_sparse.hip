@@ -2333,6 +2333,17 @@ static LaunchPlan plan_launch(pmx_ctx *ctx, const VJob *vj, uint32_t n, bool aut
     return LaunchPlan{t, tpw, nw};
 }
 
+// the range each block of a claiming launch owns (ev_wg_virtual), filled on the host: out[b], b < nwg
+int pmx_debug_wg_order(uint32_t nwg, uint32_t width, uint32_t *out)
+{
+    if (!out || !width) {
+        pmx_set_error("pmx_debug_wg_order: out is NULL or width is 0");
+        return PMX_ERR_INVALID;
+    }
+    for (uint32_t b = 0; b < nwg; b++) out[b] = ev_wg_virtual(b, nwg, width);
+    return PMX_OK;
+}
+
 // a launch's job table in device memory (any number of jobs)
 static int upload_table(pmx_ctx *ctx, const std::vector<SpJobDev> &v, SpJobTableRef *ref)
 {
@@ -2488,7 +2499,7 @@ static bool ev_big_plan(uint32_t max_shift, EvBigPlan *p, uint32_t fused_lag = 0
 template <typename JT>
 using EvKernelFn = void (*)(const JT jobs, u32 njobs, u32 total_tiles, u32 tiles_per_wg, u32 c, u32 S, u32 nhr, u32 max_lag, u32 hn,
                             u32 lo, u32 hi, u32 *slab, unsigned char *tile_flags, unsigned char *tile_flags_ac, u32 *n_flagged,
-                            u32 *jobstat, u32 *claim, u32 claim_mode);
+                            u32 *jobstat, u32 *claim, u32 claim_mode, u32 wg_layer);
 template <typename JT>
 struct EvKernel {
     EvKernelFn<JT> fn;
@@ -2811,7 +2822,7 @@ static int launch_cc_events_big(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njob
         PMX_LEDGER(ctx, PMX_LEDGER_CC_EVENTS_BIG, kern.index);
         hipLaunchKernelGGL(kern.fn, dim3(p.nwg), dim3(256 * pl.nsg), pl.lds_bytes, ctx->stream, ref, n, p.total, p.tiles_per_wg, c,
                            max_shift, nhr, fuse_mlen ? fused_lag : 0u, pl.hn, pl.lo, pl.hi | (fuse_mlen && pl.ee_lds ? 1u << 16 : 0u),
-                           ctx->d_slab, d_flags, d_flags_ac ? d_flags_ac : d_flags, d_nflagged, d_jobstat, (u32 *)nullptr, 0u);
+                           ctx->d_slab, d_flags, d_flags_ac ? d_flags_ac : d_flags, d_nflagged, d_jobstat, (u32 *)nullptr, 0u, 1u);
         PMX_CHECK_LAUNCH("k_cc_events (max_shift > 1023)");
         rc = pmx_prof_end(ctx, &tl);
         if (rc) return rc;
@@ -3023,7 +3034,7 @@ static int launch_cc_events(pmx_ctx *ctx, const pmx_job *jobs, uint32_t njobs, u
         PMX_LEDGER(ctx, PMX_LEDGER_CC_EVENTS, kern.index);
         hipLaunchKernelGGL(kern.fn, dim3(pe.nwg), dim3(256), 0, ctx->stream, tab, n, pe.total, pe.tiles_per_wg, (u32)c, max_shift, nhr,
                            fused_lag, 1024u, (u32)EV_LO, (u32)EV_HI, ctx->d_slab, fl.flags, fl.flags_ac, fl.nflagged, fl.jobstat, fl.claim,
-                           ctx->debug_claim_mode);
+                           ctx->debug_claim_mode, ctx->debug_wg_layer ? ctx->debug_wg_layer : (u32)ctx->num_cus);
         PMX_CHECK_LAUNCH("k_cc_events");
         rc = pmx_prof_end(ctx, &tl);
         if (rc) return rc;

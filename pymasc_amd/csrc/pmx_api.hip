@@ -73,6 +73,7 @@ int pmx_ctx_create(int device, void *hip_stream, pmx_ctx **out)
     ctx->profiling = 0;
     ctx->debug_max_wg = 0;
     ctx->debug_claim_mode = 0;
+    ctx->debug_wg_layer = 0;
     ctx->d_scratch = nullptr;
     ctx->scratch_words = 0;
     ctx->d_slab = nullptr;
@@ -588,6 +589,13 @@ int pmx_debug_set_claim_mode(pmx_ctx *ctx, uint32_t mode)
     REQUIRE(ctx, "pmx_debug_set_claim_mode: ctx is NULL");
     REQUIRE(mode <= 2, "pmx_debug_set_claim_mode: mode is 0, 1 or 2");
     ctx->debug_claim_mode = mode;
+    return PMX_OK;
+}
+
+int pmx_debug_set_wg_layer(pmx_ctx *ctx, uint32_t width)
+{
+    REQUIRE(ctx, "pmx_debug_set_wg_layer: ctx is NULL");
+    ctx->debug_wg_layer = width;
     return PMX_OK;
 }
 

@@ -76,6 +76,7 @@ struct pmx_ctx {
     hipEvent_t ev_fork, ev_join;
     int num_cus;
     uint32_t debug_max_wg;       // 0: off; tests: cap on the persistent workgroups of a launch (many tiles per workgroup on small inputs)
+    uint32_t debug_wg_layer;     // 0: the device's CUs; width of the dispatch layers the claiming event kernel interleaves (pmx_debug_set_wg_layer)
     uint32_t debug_claim_mode;   // 0: off; tests and A/B runs: how the hinted event kernel hands out tiles (pmx_debug_set_claim_mode)
     int profiling;               // 0 off; 1: kernels that do work; 2: also the (usually empty) fallback launches behind the event kernel
     std::vector<pmx_timed_launch> timed;       // launches not yet folded into the totals

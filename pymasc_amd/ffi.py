@@ -76,6 +76,7 @@ EXPORTS = [
     "pmx_mappable_len_batch_dev",
     "pmx_ctx_set_profiling", "pmx_ctx_reset_kernel_times", "pmx_ctx_kernel_time", "pmx_kernel_name",
     "pmx_debug_poison", "pmx_debug_read_slab", "pmx_debug_set_max_workgroups", "pmx_debug_set_claim_mode",
+    "pmx_debug_set_wg_layer", "pmx_debug_wg_order",
     "pmx_debug_read_flag_area", "pmx_debug_ledger_reset", "pmx_debug_ledger_read", "pmx_debug_ledger_sizes",
 ]
 
@@ -146,6 +147,8 @@ def load_library(path: Optional[str] = None):
     L.pmx_debug_read_slab.argtypes = [vp, u64, vp, u64]
     L.pmx_debug_set_max_workgroups.argtypes = [vp, ctypes.c_uint32]
     L.pmx_debug_set_claim_mode.argtypes = [vp, ctypes.c_uint32]
+    L.pmx_debug_set_wg_layer.argtypes = [vp, ctypes.c_uint32]
+    L.pmx_debug_wg_order.argtypes = [u32, u32, vp]
     L.pmx_debug_read_flag_area.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
     L.pmx_debug_ledger_reset.argtypes = [vp]
     L.pmx_debug_ledger_read.argtypes = [vp, i32, vp, u32, ctypes.POINTER(u32)]
@@ -628,6 +631,11 @@ class Context:
         2: the static walk), see include/pymasc_amd.h."""
         _check(self._L, self._L.pmx_debug_set_claim_mode(self._h, int(mode)))
 
+    def debug_set_wg_layer(self, width: int) -> None:
+        """Diagnostic: the layer width at which the claiming event kernel interleaves its tile ranges (0: the device's
+        compute units, 1: ranges in launch order), see include/pymasc_amd.h."""
+        _check(self._L, self._L.pmx_debug_set_wg_layer(self._h, int(width)))
+
     def debug_read_flag_area(self, cap: int = 1 << 22) -> np.ndarray:
         """Diagnostic: the bytes the last event pass of max_shift <= 1023 left in its flag area (see include/pymasc_amd.h)."""
         buf = np.zeros(cap, dtype=np.uint8)
@@ -660,6 +668,14 @@ def ledger_sizes() -> list:
     n = ctypes.c_uint32(0)
     _check(L, L.pmx_debug_ledger_sizes(buf, 64, ctypes.byref(n)))
     return [int(buf[i]) for i in range(int(n.value))]
+
+
+def wg_order(nwg: int, width: int) -> np.ndarray:
+    """The tile range each workgroup of a claiming launch of `nwg` workgroups owns at layer width `width` (needs no GPU)."""
+    L = load_library()
+    out = np.zeros(int(nwg), dtype=np.uint32)
+    _check(L, L.pmx_debug_wg_order(int(nwg), int(width), out.ctypes.data))
+    return out
 
 
 def device_count() -> int:

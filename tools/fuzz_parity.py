@@ -186,13 +186,17 @@ def main():
             helping = (n & 1) == 1
             ctx.debug_set_claim_mode(1 if helping else 0)
             ctx.debug_set_max_workgroups(2 + (n >> 1) % 4 if helping else 0)
+            # ... and every other of those with the tile ranges interleaved over layers of two or three workgroups (the default
+            # width, the device's compute units, is the identity on so few)
+            width = (2 + (n >> 3) % 2) if helping and (n & 4) else 0
+            ctx.debug_set_wg_layer(width)
             for flags in (0, ffi.PMX_FLAG_FORCE_DENSE, ffi.PMX_FLAG_FORCE_SPARSE, ffi.PMX_FLAG_DEEP_LISTS, ffi.PMX_FLAG_EVENTS_HINT):
                 if flags == ffi.PMX_FLAG_FORCE_DENSE and (S + 1) * nbits > 3e8:
                     continue
                 if flags == ffi.PMX_FLAG_FORCE_SPARSE and L > 1024:
                     continue                       # reads longer than 1024 take the dense kernels
                 fl = flags | (ffi.PMX_FLAG_SKIP_NCC if skip_ncc else 0)
-                tag = f"seed={case_seed} S={S} L={L} clen={clen} fd={fd} rd={rd} m={with_m}/{mean_on}/{mean_off} full={full} flags={fl} helping={helping}"
+                tag = f"seed={case_seed} S={S} L={L} clen={clen} fd={fd} rd={rd} m={with_m}/{mean_on}/{mean_off} full={full} flags={fl} helping={helping} width={width}"
                 try:
                     out = ctx.calc_correlation(F, R, M, nbits, S, L, fl)
                 except ffi.PmxError as e:
@@ -203,6 +207,7 @@ def main():
                     bad += 1
             ctx.debug_set_claim_mode(0)
             ctx.debug_set_max_workgroups(0)
+            ctx.debug_set_wg_layer(0)
             if rng.random() < 0.15:
                 bad += fuzz_feed(ctx, rng, clen, S, L)
             if with_m and rng.random() < 0.25:
