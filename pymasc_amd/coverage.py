@@ -598,6 +598,44 @@ class Signal:
         return "Signal(bin={}, scale={!r}, runs={}, covered_bases={}, min={!r}, max={!r})".format(self.bin, self.scale, *self.totals)
 
 
+def _same_refs(mine, theirs) -> None:
+    """Both pileups of a compared or scored track know their chosen references, and they are the same."""
+    if mine is None or theirs is None:
+        raise ValueError("a pileup does not know its chosen references' lengths (it was read from a bedGraph file)")
+    if mine != theirs:
+        raise ValueError("the chosen references of the control differ in name, length or order")
+
+
+def _entries(begins, keep_of, bin: int, length: int):
+    """(at, ends) of the kept entries of a reference: the bins where ``begins`` is set begin an entry, which ends where the next one
+    begins, the last at ``length``; ``keep_of(at)``: which of them are kept."""
+    at = np.flatnonzero(begins)
+    ends = np.append(at[1:] * bin, length)
+    keep = keep_of(at)
+    return at[keep], ends[keep]
+
+
+def _by_reference(names, ref, *cols):
+    """``{name: columns}`` of rows given as columns: split where the reference column ``ref`` (ids into ``names``) changes."""
+    cut = np.flatnonzero(np.diff(ref)) + 1 if ref.size else np.zeros(0, dtype=np.int64)
+    edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
+    return {names[int(ref[a])]: tuple(x[a:z] for x in cols) for a, z in zip(edges[:-1], edges[1:])}
+
+
+def _pull(reader, fn, head, rest_none=(), rest_of=lambda size: ()) -> bytes:
+    """The bytes of an entry point that is called twice: ``fn(handle, *head, None, 0, *rest_none)`` gives their number,
+    ``fn(handle, *head, buffer, size, *rest_of(size))`` fills a buffer of it."""
+    size = fn(reader._h, *head, None, 0, *rest_none)
+    if size < 0:
+        reader._raise(size)
+    buf = np.zeros(max(int(size), 1), dtype=np.uint8)
+    got = fn(reader._h, *head, buf.ctypes.data, int(size), *rest_of(int(size)))
+    if got < 0:
+        reader._raise(got)
+    assert got == size
+    return buf[:int(size)].tobytes()
+
+
 class Coverage:
     """``runs``: ``{name: (start0, end0, depth)}``, uint32, of the chosen references that have a run, in header order;
     ``reads``: the reads that added; ``extend`` (0: every read's own length; ``"pair"``: the FR pairs at their own extent)."""
@@ -652,11 +690,8 @@ class Coverage:
             total, width = self._bin_sums(name, bin, length)
             begins = np.ones(total.size, dtype=bool)
             begins[1:] = (total[1:] != total[:-1]) | (width[1:] != width[:-1])
-            at = np.flatnonzero(begins)
-            ends = np.append(at[1:] * bin, length)
-            keep = total[at] != 0
-            if keep.any():
-                at, ends = at[keep], ends[keep]
+            at, ends = _entries(begins, lambda at: total[at] != 0, bin, length)
+            if at.size:
                 out[name] = (at * bin, ends, ((total[at].astype(np.float64) * scale) / width[at].astype(np.float64)).astype(np.float32))
         return Signal(out, bin, scale, self.refs, self.reads, self.extend, normalize)
 
@@ -686,10 +721,7 @@ class Coverage:
         ``normalize`` and ``control`` are what the track line says."""
         bin = check_bin(bin)
         a_t, a_c, pseudo = check_factors(op, a_t, a_c, pseudo, self.max_depth, other.max_depth)
-        if self.refs is None or other.refs is None:
-            raise ValueError("a pileup does not know its chosen references' lengths (it was read from a bedGraph file)")
-        if self.refs != other.refs:
-            raise ValueError("the chosen references of the control differ in name, length or order")
+        _same_refs(self.refs, other.refs)
         out = {}
         for name, length in self.refs:
             if name not in self.runs and name not in other.runs:
@@ -698,10 +730,7 @@ class Coverage:
             Sc, _w = other._bin_sums(name, bin, length)
             begins = np.ones(St.size, dtype=bool)
             begins[1:] = (St[1:] != St[:-1]) | (Sc[1:] != Sc[:-1]) | (width[1:] != width[:-1])
-            at = np.flatnonzero(begins)
-            ends = np.append(at[1:] * bin, length)
-            keep = (St[at] != 0) | (Sc[at] != 0)
-            at, ends = at[keep], ends[keep]
+            at, ends = _entries(begins, lambda at: (St[at] != 0) | (Sc[at] != 0), bin, length)
             if at.size:
                 out[name] = (at * bin, ends, compare_values(St[at], Sc[at], width[at], op, a_t, a_c, pseudo))
         return Signal(out, bin, a_t, self.refs, self.reads, self.extend, normalize, compare_tail(control, op, pseudo))
@@ -715,10 +744,7 @@ class Coverage:
         ``scale`` is 1.0 (the treatment is not scaled) and its ``pscore`` is set; ``control`` is what the track line says."""
         bin = check_bin(bin)
         a_c, small, large = check_poisson(a_c, small, large, self.max_depth, other.max_depth, other.fragment_bases)
-        if self.refs is None or other.refs is None:
-            raise ValueError("a pileup does not know its chosen references' lengths (it was read from a bedGraph file)")
-        if self.refs != other.refs:
-            raise ValueError("the chosen references of the control differ in name, length or order")
+        _same_refs(self.refs, other.refs)
         F = lnfact(self.max_depth + 1)
         out = {name: (start, end, poisson_values(k, lam, F)) for name, start, end, k, lam in self.poisson_pairs(other, bin, a_c, small, large)}
         return Signal(out, bin, 1.0, self.refs, self.reads, self.extend, "none", poisson_tail(control, small, large), True)
@@ -735,10 +761,7 @@ class Coverage:
             kept, bits = St != 0, lam.view(np.uint64)
             begins = np.ones(St.size, dtype=bool)
             begins[1:] = (kept[1:] != kept[:-1]) | (kept[1:] & ((k[1:] != k[:-1]) | (bits[1:] != bits[:-1])))
-            at = np.flatnonzero(begins)
-            ends = np.append(at[1:] * bin, length)
-            keep = kept[at]
-            at, ends = at[keep], ends[keep]
+            at, ends = _entries(begins, lambda at: kept[at], bin, length)
             if at.size:
                 yield name, at * bin, ends, k[at], lam[at]
 
@@ -871,12 +894,17 @@ class DeviceCount(SideAccumulator):
         signal, and returns their totals by name (``SIGNAL_TOTALS``).  Every method below takes ``signal=True`` to work on them.
         ``normalize``: the word the track line says."""
         bin, scale = check_bin(bin), check_scale(scale, self.finish(reader)["max_depth"])
+        return self._track(reader, "signal", (bin, scale), bin, scale, check_normalize(normalize))
+
+    def _track(self, reader, what: str, args, bin: int, scale: float, normalize: str, more: str = "", pscore: bool = False) -> Dict[str, float]:
+        """A track into the handle's signal slot by ``pmx_dbam_coverage_<what>(handle, *args, totals)``, in place of the one before
+        and its peaks; what a ``Signal`` of it says beside its runs is kept in ``sig``.  Returns the totals by name."""
         out = np.zeros(4, dtype=np.float64)
         self.sig = self.called = None
-        rc = reader._L.pmx_dbam_coverage_signal(reader._h, bin, scale, out.ctypes.data)
+        rc = getattr(reader._L, "pmx_dbam_coverage_" + what)(reader._h, *args, out.ctypes.data)
         if rc:
             reader._raise(rc)
-        self.sig = dict(bin=bin, scale=scale, normalize=check_normalize(normalize),
+        self.sig = dict(bin=bin, scale=scale, normalize=normalize, more=more, pscore=pscore,
                         totals=dict(runs=int(out[0]), covered_bases=int(out[1]), min=float(out[2]), max=float(out[3])))
         return self.sig["totals"]
 
@@ -888,16 +916,9 @@ class DeviceCount(SideAccumulator):
         not changed and may be closed afterwards.  ``normalize`` and ``control``: what the track line says."""
         bin = check_bin(bin)
         a_t, a_c, pseudo = check_factors(op, a_t, a_c, pseudo, self.finish(reader)["max_depth"], control_acc.finish(control_reader)["max_depth"])
-        if self.refs != control_acc.refs:
-            raise ValueError("the chosen references of the control differ in name, length or order")
-        out = np.zeros(4, dtype=np.float64)
-        self.sig = self.called = None
-        rc = reader._L.pmx_dbam_coverage_compare(reader._h, control_reader._h, bin, COMPARE.index(op), a_t, a_c, pseudo, out.ctypes.data)
-        if rc:
-            reader._raise(rc)
-        self.sig = dict(bin=bin, scale=a_t, normalize=check_normalize(normalize), more=compare_tail(control, op, pseudo),
-                        totals=dict(runs=int(out[0]), covered_bases=int(out[1]), min=float(out[2]), max=float(out[3])))
-        return self.sig["totals"]
+        _same_refs(self.refs, control_acc.refs)
+        return self._track(reader, "compare", (control_reader._h, bin, COMPARE.index(op), a_t, a_c, pseudo), bin, a_t, check_normalize(normalize),
+                           compare_tail(control, op, pseudo))
 
     def poisson(self, reader, control_acc: "DeviceCount", control_reader, bin: int = 1, a_c: float = 1.0, small: int = LAMBDA_WINDOWS[0],
                 large: int = LAMBDA_WINDOWS[1], control="") -> Dict[str, float]:
@@ -908,17 +929,10 @@ class DeviceCount(SideAccumulator):
         bin = check_bin(bin)
         mine, theirs = self.finish(reader), control_acc.finish(control_reader)
         a_c, small, large = check_poisson(a_c, small, large, mine["max_depth"], theirs["max_depth"], theirs["fragment_bases"])
-        if self.refs != control_acc.refs:
-            raise ValueError("the chosen references of the control differ in name, length or order")
+        _same_refs(self.refs, control_acc.refs)
         F = np.ascontiguousarray(lnfact(mine["max_depth"] + 1))
-        out = np.zeros(4, dtype=np.float64)
-        self.sig = self.called = None
-        rc = reader._L.pmx_dbam_coverage_poisson(reader._h, control_reader._h, bin, a_c, small, large, F.ctypes.data, F.size, out.ctypes.data)
-        if rc:
-            reader._raise(rc)
-        self.sig = dict(bin=bin, scale=1.0, normalize="none", more=poisson_tail(control, small, large), pscore=True,
-                        totals=dict(runs=int(out[0]), covered_bases=int(out[1]), min=float(out[2]), max=float(out[3])))
-        return self.sig["totals"]
+        return self._track(reader, "poisson", (control_reader._h, bin, a_c, small, large, F.ctypes.data, F.size), bin, 1.0, "none",
+                           poisson_tail(control, small, large), True)
 
     def _count(self, reader, signal: bool) -> int:
         if signal and self.sig is None:
@@ -939,16 +953,7 @@ class DeviceCount(SideAccumulator):
         """The bedGraph lines of the runs ``[first, first + n)``, formatted on the device (``pmx_dbam_coverage_text``: the size,
         then the bytes)."""
         n = self._count(reader, signal) - int(first) if n is None else int(n)
-        fn = self._fn(reader, "text", signal)
-        size = fn(reader._h, int(first), n, None, 0)
-        if size < 0:
-            reader._raise(size)
-        buf = np.zeros(max(int(size), 1), dtype=np.uint8)
-        got = fn(reader._h, int(first), n, buf.ctypes.data, int(size))
-        if got < 0:
-            reader._raise(got)
-        assert got == size
-        return buf[:int(size)].tobytes()
+        return _pull(reader, self._fn(reader, "text", signal), (int(first), n))
 
     def text_chunks(self, reader, chunk: int = TEXT_CHUNK, signal: bool = False) -> Iterator[bytes]:
         total = self._count(reader, signal)
@@ -969,20 +974,11 @@ class DeviceCount(SideAccumulator):
         """(bytes, table) of the runs ``[first, first + n)`` of one reference as bedGraph sections of a bigWig file stamped with
         ``chrom_id`` (``pmx_dbam_coverage_sections``: the size, then the bytes); ``table[section] = (id, start, id, end, bytes)``.
         With ``signal`` (bytes, table, sums): ``sums[section] = (sum, sum of squares)``, float64."""
-        h, fn = reader._h, self._fn(reader, "sections", signal)
         rows = -(-int(n) // int(items))
-        sums = np.zeros((max(rows, 1), 2), dtype=np.float64)
-        more = (sums.ctypes.data,) if signal else ()
-        size = fn(h, int(first), int(n), int(chrom_id), int(items), None, 0, None, 0, *((None,) if signal else ()))
-        if size < 0:
-            reader._raise(size)
-        buf = np.zeros(max(int(size), 1), dtype=np.uint8)
-        table = np.zeros((max(rows, 1), 5), dtype=np.uint32)
-        got = fn(h, int(first), int(n), int(chrom_id), int(items), buf.ctypes.data, int(size), table.ctypes.data, len(table), *more)
-        if got < 0:
-            reader._raise(got)
-        assert got == size
-        return (buf[:int(size)].tobytes(), table[:rows]) + ((sums[:rows],) if signal else ())
+        sums, table = np.zeros((max(rows, 1), 2), dtype=np.float64), np.zeros((max(rows, 1), 5), dtype=np.uint32)
+        blob = _pull(reader, self._fn(reader, "sections", signal), (int(first), int(n), int(chrom_id), int(items)),
+                     (None, 0) + ((None,) if signal else ()), lambda size: (table.ctypes.data, len(table)) + ((sums.ctypes.data,) if signal else ()))
+        return (blob, table[:rows]) + ((sums[:rows],) if signal else ())
 
     def section_chunks(self, reader, k: int, chrom_id: int, items: int, chunk: int = TEXT_CHUNK, signal: bool = False):
         """``sections`` of the ``k``-th chosen reference, about ``chunk`` runs at a time (whole sections)."""
@@ -1031,18 +1027,13 @@ class DeviceCount(SideAccumulator):
     def zoom_records(self, reader, level: int, items: int, signal: bool = False):
         """(bytes, table) of a level's records, 32 bytes each, in sections of ``items`` (``pmx_dbam_coverage_zoom_records``);
         ``table[section] = (first id, first start, last id, last end, bytes)``.  The last level frees the bins."""
-        h, fn = reader._h, self._fn(reader, "zoom_records", signal)
-        size = fn(h, int(level), int(items), None, 0, None, 0)
-        if size < 0:
-            reader._raise(size)
-        rows = -(-(int(size) // 32) // int(items))
-        buf = np.zeros(max(int(size), 1), dtype=np.uint8)
-        table = np.zeros((max(rows, 1), 5), dtype=np.uint32)
-        got = fn(h, int(level), int(items), buf.ctypes.data, int(size), table.ctypes.data, len(table))
-        if got < 0:
-            reader._raise(got)
-        assert got == size
-        return buf[:int(size)].tobytes(), table[:rows]
+        tables = []
+
+        def table_of(size):         # (the rows follow from the size)
+            tables.append(np.zeros((max(-(-(size // 32) // int(items)), 1), 5), dtype=np.uint32))
+            return tables[0].ctypes.data, len(tables[0])
+        blob = _pull(reader, self._fn(reader, "zoom_records", signal), (int(level), int(items)), (None, 0), table_of)
+        return blob, tables[0][:-(-(len(blob) // 32) // int(items))]
 
     def zoom_records_z(self, reader, level: int, items: int, signal: bool = False):
         """``zoom_records`` with every section compressed on the device (``pmx_dbam_coverage_zoom_records_z``): (streams, table,
@@ -1063,23 +1054,15 @@ class DeviceCount(SideAccumulator):
 
     def result(self, reader) -> Coverage:
         totals = self.finish(reader)
-        ref, start, end, depth = self.runs(reader)
-        cut = np.flatnonzero(np.diff(ref)) + 1 if ref.size else np.zeros(0, dtype=np.int64)
-        edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
-        c = Coverage({self.names[int(ref[a])]: (start[a:z], end[a:z], depth[a:z]) for a, z in zip(edges[:-1], edges[1:])},
-                     totals["reads"], self.extend, self.refs)
+        c = Coverage(_by_reference(self.names, *self.runs(reader)), totals["reads"], self.extend, self.refs)
         if c.totals != tuple(totals[k] for k in TOTALS):
             raise RuntimeError("pmx_dbam_coverage_finish: the runs do not add up to the totals")
         return c
 
     def signal_result(self, reader) -> Signal:
         """The signal runs on the handle as a ``Signal``."""
-        ref, start, end, value = self.runs(reader, signal=True)
-        cut = np.flatnonzero(np.diff(ref)) + 1 if ref.size else np.zeros(0, dtype=np.int64)
-        edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
-        g = Signal({self.names[int(ref[a])]: (start[a:z], end[a:z], value[a:z]) for a, z in zip(edges[:-1], edges[1:])},
-                   self.sig["bin"], self.sig["scale"], self.refs, self.finish(reader)["reads"], self.extend, self.sig["normalize"],
-                   self.sig.get("more", ""), self.sig.get("pscore", False))
+        g = Signal(_by_reference(self.names, *self.runs(reader, signal=True)), self.sig["bin"], self.sig["scale"], self.refs, self.finish(reader)["reads"], self.extend, self.sig["normalize"],
+                   self.sig["more"], self.sig["pscore"])
         if g.totals != tuple(self.sig["totals"][k] for k in SIGNAL_TOTALS):
             raise RuntimeError("pmx_dbam_coverage_signal: the runs do not add up to the totals")
         return g
@@ -1096,7 +1079,7 @@ class DeviceCount(SideAccumulator):
         rc = reader._L.pmx_dbam_coverage_call(reader._h, cutoff, max_gap, min_length, out.ctypes.data)
         if rc:
             reader._raise(rc)
-        self.called = dict(cutoff=cutoff, max_gap=max_gap, min_length=min_length, pscore=bool(self.sig.get("pscore", False)),
+        self.called = dict(cutoff=cutoff, max_gap=max_gap, min_length=min_length, pscore=self.sig["pscore"],
                            totals=dict(zip(CALL_TOTALS, (int(x) for x in out))))
         return self.called["totals"]
 
@@ -1119,16 +1102,7 @@ class DeviceCount(SideAccumulator):
         """The narrowPeak lines of the peaks ``[first, first + n)``, formatted on the device (``pmx_dbam_coverage_call_text``: the
         size, then the bytes); peak ``first + i`` is ``peak_<first + i + 1>``."""
         n = self._peaks() - int(first) if n is None else int(n)
-        fn = reader._L.pmx_dbam_coverage_call_text
-        size = fn(reader._h, int(first), n, None, 0)
-        if size < 0:
-            reader._raise(size)
-        buf = np.zeros(max(int(size), 1), dtype=np.uint8)
-        got = fn(reader._h, int(first), n, buf.ctypes.data, int(size))
-        if got < 0:
-            reader._raise(got)
-        assert got == size
-        return buf[:int(size)].tobytes()
+        return _pull(reader, reader._L.pmx_dbam_coverage_call_text, (int(first), n))
 
     def call_text_chunks(self, reader, chunk: int = TEXT_CHUNK) -> Iterator[bytes]:
         total = self._peaks()
@@ -1138,11 +1112,8 @@ class DeviceCount(SideAccumulator):
     def call_result(self, reader) -> Peaks:
         """The peak table on the handle as a ``Peaks``."""
         ref, start, end, summit, value, runs = self.call_rows(reader)
-        cut = np.flatnonzero(np.diff(ref)) + 1 if ref.size else np.zeros(0, dtype=np.int64)
-        edges = np.concatenate(([0], cut, [ref.size])).astype(np.int64) if ref.size else np.zeros(1, dtype=np.int64)
         tot = self.called["totals"]
-        p = Peaks({self.names[int(ref[a])]: tuple(x[a:z] for x in (start, end, summit, value, runs)) for a, z in zip(edges[:-1], edges[1:])},
-                  self.called["cutoff"], self.called["max_gap"], self.called["min_length"], tot, self.called["pscore"])
+        p = Peaks(_by_reference(self.names, ref, start, end, summit, value, runs), self.called["cutoff"], self.called["max_gap"], self.called["min_length"], tot, self.called["pscore"])
         inside = int(runs.sum(dtype=np.int64))
         if (p.n_peaks, p.peak_bases) != (tot["peaks"], tot["peak_bases"]) or not (tot["peaks"] <= tot["candidates"] <= tot["passing_runs"]) \
                 or inside > tot["passing_runs"] or not (inside <= tot["passing_bases"] <= tot["peak_bases"]):
@@ -1218,7 +1189,7 @@ def write_coverage(path_base, name: str, c, reader=None, signal: bool = False) -
         return write_track(path_base, name, c.extend, c.reads, c.text_chunks(), c.tail if isinstance(c, Signal) else "")
     if signal and c.sig is None:
         raise ValueError("no signal: call signal first")
-    tail = signal_tail(c.sig["bin"], c.sig["normalize"], c.sig["scale"]) + c.sig.get("more", "") if signal else ""
+    tail = signal_tail(c.sig["bin"], c.sig["normalize"], c.sig["scale"]) + c.sig["more"] if signal else ""
     return write_track(path_base, name, c.extend, c.finish(reader)["reads"], c.text_chunks(reader, signal=signal), tail)
 
 

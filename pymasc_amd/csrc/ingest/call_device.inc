@@ -75,23 +75,7 @@ template <int S> __device__ __forceinline__ bool cl_keeps(const ClIn &A, u64 k)
 template <int S> __global__ void __launch_bounds__(256) k_cl_count(ClIn A, u32 *__restrict__ kcnt)
 {
     __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 m = __ballot(cl_keeps<S>(A, (u64)blockIdx.x * 256u + t));
-    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// where a kept element of a workgroup goes: kbase of the workgroup + the kept ones in front of it
-__device__ __forceinline__ u64 cl_slot(bool keep, const u64 *__restrict__ kbase, u32 *s_w)
-{
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 m = __ballot(keep);
-    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
-    return o;
+    cv_count(cl_keeps<S>(A, (u64)blockIdx.x * 256u + threadIdx.x), kcnt, s_w);
 }
 
 template <int S> __global__ void __launch_bounds__(256) k_cl_list(ClIn A, const u64 *__restrict__ kbase, u32 *__restrict__ out)
@@ -99,7 +83,7 @@ template <int S> __global__ void __launch_bounds__(256) k_cl_list(ClIn A, const 
     __shared__ u32 s_w[4];
     const u64 k = (u64)blockIdx.x * 256u + threadIdx.x;
     const bool keep = cl_keeps<S>(A, k);
-    const u64 o = cl_slot(keep, kbase, s_w);
+    const u64 o = cv_slot(keep, kbase, s_w);
     if (keep) out[o] = (u32)k;                  // (below 2^32 runs)
 }
 
@@ -111,7 +95,7 @@ __global__ void __launch_bounds__(256) k_cl_close(ClIn A, const u64 *__restrict_
     __shared__ u32 s_w[4];
     const u64 k = (u64)blockIdx.x * 256u + threadIdx.x;
     const bool keep = cl_keeps<2>(A, k);
-    const u64 o = cl_slot(keep, kbase, s_w);
+    const u64 o = cv_slot(keep, kbase, s_w);
     u64 width = 0;
     if (keep) {
         u32 first, last;

@@ -20,9 +20,11 @@
 // Refused: a factor, or for log2 / ratio p, below 2^-64 or not finite; a * max_depth >= 2^40 of either track; p >= 2^40; for ratio
 // (a_t * max_depth_t + p) / p >= 2^40 (|v| < 2^40: the text stays integer arithmetic).  subtract ignores p.
 //
+// signal_device.inc's pipeline (bintrack_run) with the kind CpTrack:
 //   k_cv_bin_fill    once per handle into its own dense u64 table, for B = 1 as for any other bin (two run lists do not line up)
-//   k_cp_mark / k_bam_scan / k_cp_entries   sg_begins extended to both sums; compacted into (reference, bin, S_t, S_c)
-//   k_cp_keep / k_bam_scan / k_cp_close     the (0, 0) entries dropped, v by op, the totals through sg_totals
+//   k_bt_count<CpTrack, false> / k_bam_scan / k_bt_entries<CpTrack>   SgTrack's rule extended to both sums; compacted into
+//                    (reference, bin, S_t, S_c)
+//   k_bt_count<CpTrack, true> / k_bam_scan / k_bt_close<CpTrack>      the (0, 0) entries dropped, v by op, the totals through sg_totals
 // Device memory: 16 bytes per bin + 24 per entry inside compare (counted in the handle's bytes while it runs, freed before it
 // returns), then 16 per run in the signal slot.
 
@@ -74,228 +76,46 @@ __device__ __forceinline__ u32 cp_value(u64 St, u64 Sc, u32 w, int op, double at
     return __float_as_uint(__double2float_rn(v));
 }
 
-// sg_begins over both tables
-__device__ __forceinline__ bool cp_begins(const unsigned long long *__restrict__ tt, const unsigned long long *__restrict__ tc, u64 b,
-                                          const SgGeo &G, u32 &k, u32 &j)
-{
-    k = cv_zoom_id(G.boff, G.nc, b);
-    j = (u32)(b - G.boff[k]);
-    if (j == 0) return true;
-    return ((u64)j + 1u) * G.B > (u64)G.lens[k] || tt[b - 1u] != tt[b] || tc[b - 1u] != tc[b];
-}
-
-__global__ void __launch_bounds__(256) k_cp_mark(const unsigned long long *__restrict__ tt, const unsigned long long *__restrict__ tc, u64 nb,
-                                                 SgGeo G, u32 *__restrict__ kcnt)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 b = (u64)blockIdx.x * 256u + t;
-    u32 k, j;
-    const u64 m = __ballot(b < nb && cp_begins(tt, tc, b, G, k, j));
-    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ void __launch_bounds__(256) k_cp_entries(const unsigned long long *__restrict__ tt, const unsigned long long *__restrict__ tc, u64 nb,
-                                                    SgGeo G, const u64 *__restrict__ kbase, u32 *__restrict__ eid, u32 *__restrict__ ej,
-                                                    unsigned long long *__restrict__ eSt, unsigned long long *__restrict__ eSc)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 b = (u64)blockIdx.x * 256u + t;
-    u32 k = 0, j = 0;
-    const bool keep = b < nb && cp_begins(tt, tc, b, G, k, j);
-    const u64 m = __ballot(keep);
-    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    if (!keep) return;
-    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
-    eid[o] = k;
-    ej[o] = j;
-    eSt[o] = tt[b];
-    eSc[o] = tc[b];
-}
-
-__global__ void __launch_bounds__(256) k_cp_keep(const unsigned long long *__restrict__ eSt, const unsigned long long *__restrict__ eSc, u64 n,
-                                                 u32 *__restrict__ kcnt)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 k = (u64)blockIdx.x * 256u + t;
-    const u64 m = __ballot(k < n && (eSt[k] | eSc[k]) != 0);
-    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ void __launch_bounds__(256) k_cp_close(const u32 *__restrict__ eid, const u32 *__restrict__ ej, const unsigned long long *__restrict__ eSt,
-                                                  const unsigned long long *__restrict__ eSc, u64 n, const u64 *__restrict__ kbase, SgGeo G,
-                                                  int op, double at, double ac, double p, int *__restrict__ oref, u32 *__restrict__ ostart,
-                                                  u32 *__restrict__ oend, u32 *__restrict__ oval, unsigned long long *__restrict__ tot)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 k = (u64)blockIdx.x * 256u + t;
-    const bool keep = k < n && (eSt[k] | eSc[k]) != 0;
-    const u64 m = __ballot(keep);
-    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    u64 width = 0;
-    u32 bits = 0;
-    if (keep) {
-        u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-        for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
-        const u32 id = eid[k], len = G.lens[id];
-        const u32 a = ej[k] * G.B;                                                         // (below len < 2^32)
-        const u32 z = k + 1u < n && eid[k + 1u] == id ? ej[k + 1u] * G.B : len;
-        const u32 w = len - a < G.B ? len - a : G.B;                                       // the width of the run's bins
-        bits = cp_value((u64)eSt[k], (u64)eSc[k], w, op, at, ac, p);
-        oref[o] = G.cref[id];
-        ostart[o] = a;
-        oend[o] = z;
-        oval[o] = bits;
-        width = (u64)(z - a);
-    }
-    sg_totals(lane, keep, width, bits, tot);
-}
-
 namespace {
 
-// the work of compare behind its checks; a failure leaves no signal.  The control's stream has been waited for.
-int coverage_compare_run(pmx_dbam *b, pmx_dbam *ctl, const std::string &fn, u32 bin, int op, double at, double ac, double p)
-{
-    HIPOK(hipSetDevice(b->device));
-    hipStream_t st = b->stream;
-    Coverage &c = b->cv;
-    const Coverage &cc = ctl->cv;
-    unsigned long long tot[3] = {0, ~0ull, 0};
-    u64 nout = 0;
-    if (c.nruns || cc.nruns) {
-        const u64 nc = c.chosen.size();
-        std::vector<u64> boff(nc + 1, 0), boft(std::max<u64>(b->ref_names.size(), 1), 0), bofc(std::max<u64>(ctl->ref_names.size(), 1), 0);
-        std::vector<u32> lens(nc, 0);
-        std::vector<int> cref(nc, 0);
-        for (u64 k = 0; k < nc; k++) {
-            lens[k] = (u32)std::max<int64_t>(b->ref_lens[(u64)c.chosen[k]], 0);
-            cref[k] = c.chosen[k];
-            boft[(u64)c.chosen[k]] = boff[k];
-            bofc[(u64)cc.chosen[k]] = boff[k];
-            boff[k + 1] = boff[k] + ((u64)lens[k] + bin - 1) / bin;
-        }
-        const u64 nb = boff[nc], nwg = (nb + 255) / 256;
-        if (nwg >= (1ull << 31)) return fail(PMX_DBAM_ERR_INVALID, fn + ": 2^39 bins or more");
-        DevAlloc d_tot, d_geo, d_tab, d_k, d_kb, d_e;
-        CvHold held(b);
-        HIPOK(hipMalloc(&d_tot.p, 64));
-        HIPOK(hipMemcpyAsync(d_tot.p, tot, 24, hipMemcpyHostToDevice, st));
-        u64 *dt = d_tot.as<u64>();
-        const u64 geo_bytes = 8 * boff.size() + 8 * boft.size() + 8 * bofc.size() + 8 * std::max<u64>(nc, 1);
-        HIPOK(hipMalloc(&d_geo.p, geo_bytes));
-        if (hipMalloc(&d_tab.p, 16 * std::max<u64>(nb, 1)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for the bin tables: " + std::to_string(16 * nb) +
-                                               " bytes asked for (16 per bin of " + std::to_string(bin) + " bases)");
-        }
-        held.add(geo_bytes + 16 * nb + 12 * nwg);
-        HIPOK(hipMalloc(&d_k.p, 4 * std::max<u64>(nwg, 1)));
-        HIPOK(hipMalloc(&d_kb.p, 8 * std::max<u64>(nwg, 1)));
-        u64 *d_boff = d_geo.as<u64>(), *d_boft = d_boff + boff.size(), *d_bofc = d_boft + boft.size();
-        u32 *d_lens = (u32 *)(d_bofc + bofc.size());
-        int *d_cref = (int *)(d_lens + std::max<u64>(nc, 1));
-        HIPOK(hipMemcpyAsync(d_boff, boff.data(), 8 * boff.size(), hipMemcpyHostToDevice, st));
-        HIPOK(hipMemcpyAsync(d_boft, boft.data(), 8 * boft.size(), hipMemcpyHostToDevice, st));
-        HIPOK(hipMemcpyAsync(d_bofc, bofc.data(), 8 * bofc.size(), hipMemcpyHostToDevice, st));
-        HIPOK(hipMemcpyAsync(d_lens, lens.data(), 4 * nc, hipMemcpyHostToDevice, st));
-        HIPOK(hipMemcpyAsync(d_cref, cref.data(), 4 * nc, hipMemcpyHostToDevice, st));
-        HIPOK(hipMemsetAsync(d_tab.p, 0, 16 * nb, st));
-        const SgGeo G{d_boff, d_lens, d_cref, (u32)nc, bin};
-        unsigned long long *tt = d_tab.as<unsigned long long>(), *tc = tt + nb;
-        if (c.nruns) {
-            const CvRuns V(c.runs.as<u8>(), c.nruns);
-            hipLaunchKernelGGL(k_cv_bin_fill, dim3((unsigned)((c.nruns + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, c.nruns, d_boft,
-                               bin, tt);
-            HIPOK(hipGetLastError());
-        }
-        if (cc.nruns) {
-            const CvRuns V((u8 *)cc.runs.p, cc.nruns);
-            hipLaunchKernelGGL(k_cv_bin_fill, dim3((unsigned)((cc.nruns + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, cc.nruns,
-                               d_bofc, bin, tc);
-            HIPOK(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_cp_mark, dim3((unsigned)nwg), dim3(256), 0, st, tt, tc, nb, G, d_k.as<u32>());
-        HIPOK(hipGetLastError());
-        hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), nwg, d_kb.as<u64>(), dt + 4);
-        HIPOK(hipGetLastError());
-        u64 ne = 0;
-        HIPOK(hipMemcpyAsync(&ne, dt + 4, 8, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));       // (boff, boft, bofc, lens and cref are locals)
-        if (hipMalloc(&d_e.p, 24 * ne) != hipSuccess) {      // (ne >= 1: a run lies in a bin, so a reference has one)
-            (void)hipGetLastError();
-            return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(ne) + " bin boundaries");
-        }
-        held.add(24 * ne);
-        unsigned long long *eSt = d_e.as<unsigned long long>(), *eSc = eSt + ne;
-        u32 *eid = (u32 *)(eSc + ne), *ej = eid + ne;
-        hipLaunchKernelGGL(k_cp_entries, dim3((unsigned)nwg), dim3(256), 0, st, tt, tc, nb, G, d_kb.as<u64>(), eid, ej, eSt, eSc);
-        HIPOK(hipGetLastError());
-        const u64 ewg = (ne + 255) / 256;          // (ewg <= nwg: d_k and d_kb are used again)
-        hipLaunchKernelGGL(k_cp_keep, dim3((unsigned)ewg), dim3(256), 0, st, eSt, eSc, ne, d_k.as<u32>());
-        HIPOK(hipGetLastError());
-        hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), ewg, d_kb.as<u64>(), dt + 6);
-        HIPOK(hipGetLastError());
-        HIPOK(hipMemcpyAsync(&nout, dt + 6, 8, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        if (nout) {
-            if (hipMalloc(&c.sruns.p, 16 * nout) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(nout) + " runs");
-            }
-            c.snruns = nout;        // (counted from here on: signal_drop takes them off again)
-            c.bytes += 16 * nout;
-            if (b->st) stream_note(*b);
-            const CvRuns O(c.sruns.as<u8>(), nout);
-            hipLaunchKernelGGL(k_cp_close, dim3((unsigned)ewg), dim3(256), 0, st, eid, ej, eSt, eSc, ne, d_kb.as<u64>(), G, op, at, ac, p, O.ref, O.start,
-                               O.end, O.depth, d_tot.as<unsigned long long>());
-            HIPOK(hipGetLastError());
-        }
-        HIPOK(hipMemcpyAsync(tot, d_tot.p, 24, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));            // (the tables, the entries and the scans are freed behind it)
+struct CpTrack {        // compare: an entry is (reference, bin, S_t, S_c); SgTrack's rule over both tables
+    static constexpr u64 TABLES = 2, ENTRY = 24;
+    int op;
+    double at, ac, p;
+    const unsigned long long *tt, *tc;
+    unsigned long long *eSt, *eSc;
+    u32 *eid, *ej;
+    void tables(const unsigned long long *t, u64 nb)
+    {
+        tt = t;
+        tc = t + nb;
     }
-    float lo = 0.0f, hi = 0.0f;
-    if (nout) {
-        const u32 l = sg_unkey((u32)tot[1]), h = sg_unkey((u32)tot[2]);
-        memcpy(&lo, &l, 4);
-        memcpy(&hi, &h, 4);
+    void entries(u8 *q, u64 ne)
+    {
+        eSt = (unsigned long long *)q;
+        eSc = eSt + ne;
+        eid = (u32 *)(eSc + ne);
+        ej = eid + ne;
     }
-    c.shave = true;
-    c.sbin = bin;
-    c.stot[0] = (double)nout;
-    c.stot[1] = (double)(nout ? tot[0] : 0);
-    c.stot[2] = (double)lo;
-    c.stot[3] = (double)hi;
-    return 0;
-}
+    __device__ __forceinline__ bool begins(u64 b, const SgGeo &G, u32 id, u32 j, u32 &) const
+    {
+        if (j == 0) return true;
+        return ((u64)j + 1u) * G.B > (u64)G.lens[id] || tt[b - 1u] != tt[b] || tc[b - 1u] != tc[b];
+    }
+    __device__ __forceinline__ void put(u64 o, u64 b, u32) const
+    {
+        eSt[o] = tt[b];
+        eSc[o] = tc[b];
+    }
+    __device__ __forceinline__ bool kept(u64 e) const { return (eSt[e] | eSc[e]) != 0; }
+    __device__ __forceinline__ u32 value(u64 e, u32 w) const { return cp_value((u64)eSt[e], (u64)eSc[e], w, op, at, ac, p); }
+};
 
 int coverage_compare_impl(pmx_dbam *b, pmx_dbam *ctl, uint32_t bin, int op, double at, double ac, double p, double *totals)
 {
     const std::string fn = "pmx_dbam_coverage_compare";
-    if (!b || !ctl) return fail(PMX_DBAM_ERR_INVALID, "null handle");
-    if (!totals) return fail(PMX_DBAM_ERR_INVALID, fn + ": null output");
-    for (int k = 0; k < 4; k++) totals[k] = 0;
-    Coverage &c = b->cv;
-    const Coverage &cc = ctl->cv;
-    if (c.state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, fn + ": no runs: call pmx_dbam_coverage_finish first");
-    if (cc.state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, fn + ": the control has no runs: call pmx_dbam_coverage_finish on it first");
-    if (b->device != ctl->device) return fail(PMX_DBAM_ERR_INVALID, fn + ": the control is on another device");
-    bool same = c.chosen.size() == cc.chosen.size();
-    for (u64 k = 0; same && k < c.chosen.size(); k++) {
-        const u64 x = (u64)c.chosen[k], y = (u64)cc.chosen[k];
-        same = b->ref_names[x] == ctl->ref_names[y] && std::max<int64_t>(b->ref_lens[x], 0) == std::max<int64_t>(ctl->ref_lens[y], 0);
-    }
-    if (!same) return fail(PMX_DBAM_ERR_INVALID, fn + ": the chosen references of the control differ in name, length or order");
-    if (bin < 1 || bin > SG_MAX_BIN) return fail(PMX_DBAM_ERR_INVALID, fn + ": a bin of 1 to 65536 bases");
+    if (int rc = track_checks(b, ctl, true, fn, bin, totals)) return rc;
+    const Coverage &c = b->cv, &cc = ctl->cv;
     if (op != CP_LOG2 && op != CP_RATIO && op != CP_SUBTRACT)
         return fail(PMX_DBAM_ERR_INVALID, fn + ": the operation is 0 (log2), 1 (ratio) or 2 (subtract)");
     if (!std::isfinite(at) || at < 0x1p-64 || !std::isfinite(ac) || ac < 0x1p-64)
@@ -311,22 +131,7 @@ int coverage_compare_impl(pmx_dbam *b, pmx_dbam *ctl, uint32_t bin, int op, doub
     } else {
         p = 0.0;
     }
-    HIPOK(hipSetDevice(b->device));
-    if (ctl != b) HIPOK(hipStreamSynchronize(ctl->stream));
-    HIPOK(hipStreamSynchronize(b->stream));
-    signal_drop(c);
-    struct Drop {       // a failure from here on leaves no signal
-        Coverage &c;
-        bool ok = false;
-        ~Drop()
-        {
-            if (!ok) signal_drop(c);
-        }
-    } drop{c};
-    if (int rc = coverage_compare_run(b, ctl, fn, bin, op, at, ac, p)) return rc;
-    drop.ok = true;
-    for (int k = 0; k < 4; k++) totals[k] = c.stot[k];
-    return 0;
+    return track_make(b, ctl, totals, [&] { return bintrack_run(b, ctl, fn, bin, CpTrack{op, at, ac, p}, bt_no_stage); });
 }
 
 }  // namespace

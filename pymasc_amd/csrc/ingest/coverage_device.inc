@@ -189,14 +189,34 @@ __device__ __forceinline__ bool cv_keeps(const int *__restrict__ eref, const u32
     return k + 1u < n && (int)edep[k] > 0 && eref[k + 1u] == eref[k];
 }
 
-__global__ void __launch_bounds__(256) k_cv_keep(const int *__restrict__ eref, const u32 *__restrict__ edep, u64 n, u32 *__restrict__ kcnt)
+// kcnt[workgroup] = its kept elements (s_w: four words of LDS)
+__device__ __forceinline__ void cv_count(bool keep, u32 *__restrict__ kcnt, u32 *s_w)
 {
-    __shared__ u32 s_w[4];
     const u32 t = threadIdx.x;
-    const u64 m = __ballot(cv_keeps(eref, edep, (u64)blockIdx.x * 256u + t, n));
+    const u64 m = __ballot(keep);
     if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
     __syncthreads();
     if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// where a kept element of a workgroup goes: kbase (k_bam_scan over cv_count's counts) of the workgroup + the kept ones in front of it
+// (only the kept lanes do the arithmetic: done by every lane it costs k_bt_close two more VGPRs)
+__device__ __forceinline__ u64 cv_slot(bool keep, const u64 *__restrict__ kbase, u32 *s_w)
+{
+    const u32 t = threadIdx.x, lane = t & 63u;
+    const u64 m = __ballot(keep);
+    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
+    __syncthreads();
+    if (!keep) return 0;
+    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
+    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
+    return o;
+}
+
+__global__ void __launch_bounds__(256) k_cv_keep(const int *__restrict__ eref, const u32 *__restrict__ edep, u64 n, u32 *__restrict__ kcnt)
+{
+    __shared__ u32 s_w[4];
+    cv_count(cv_keeps(eref, edep, (u64)blockIdx.x * 256u + threadIdx.x, n), kcnt, s_w);
 }
 
 // tot[0] += covered bases, tot[1] += fragment bases, tot[2] = max(tot[2], depth)
@@ -205,17 +225,12 @@ __global__ void __launch_bounds__(256) k_cv_close(const int *__restrict__ eref, 
                                                   u32 *__restrict__ rend, u32 *__restrict__ rdepth, unsigned long long *__restrict__ tot)
 {
     __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 k = (u64)blockIdx.x * 256u + t;
+    const u64 k = (u64)blockIdx.x * 256u + threadIdx.x;
     const bool keep = cv_keeps(eref, edep, k, n);
-    const u64 m = __ballot(keep);
-    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
+    const u64 o = cv_slot(keep, kbase, s_w);
     u64 width = 0, area = 0;
     u32 depth = 0;
     if (keep) {
-        u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-        for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
         depth = edep[k];
         const u32 a = epos[k], z = epos[k + 1u];
         rref[o] = eref[k];
@@ -231,7 +246,7 @@ __global__ void __launch_bounds__(256) k_cv_close(const int *__restrict__ eref, 
         const u32 y = __shfl_xor(depth, d, 64);
         depth = y > depth ? y : depth;
     }
-    if (lane == 0 && m) {
+    if ((threadIdx.x & 63u) == 0 && width) {       // (a run is a base wide at least)
         atomicAdd(&tot[0], (unsigned long long)width);
         atomicAdd(&tot[1], (unsigned long long)area);
         atomicMax(&tot[2], (unsigned long long)depth);
@@ -801,12 +816,8 @@ __global__ void __launch_bounds__(256) k_cv_zoom_fold(u8 *__restrict__ src, u64 
 __global__ void __launch_bounds__(256) k_cv_zoom_keep(const u32 *__restrict__ cnt, u64 n, u32 *__restrict__ kcnt)
 {
     __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 b = (u64)blockIdx.x * 256u + t;
-    const u64 m = __ballot(b < n && cnt[b] != 0);
-    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const u64 b = (u64)blockIdx.x * 256u + threadIdx.x;
+    cv_count(b < n && cnt[b] != 0, kcnt, s_w);
 }
 
 // out: 8 u32 words per record; total[0]: the records of the level (k_bam_scan's total)
@@ -815,16 +826,11 @@ __global__ void __launch_bounds__(256) k_cv_zoom_emit(u8 *__restrict__ bins, u64
                                                       u32 *__restrict__ out, u32 *__restrict__ table)
 {
     __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 b = (u64)blockIdx.x * 256u + t;
+    const u64 b = (u64)blockIdx.x * 256u + threadIdx.x;
     const ZmBins B(bins, n);
     const bool keep = b < n && B.cnt[b] != 0;
-    const u64 m = __ballot(keep);
-    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
+    const u64 o = cv_slot(keep, kbase, s_w);
     if (!keep) return;
-    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
     const u32 id = cv_zoom_id(off, nc, b);
     const u64 a = (b - off[id]) * z;
     const u32 start = (u32)a, end = a + z < (u64)lens[id] ? (u32)(a + z) : lens[id];

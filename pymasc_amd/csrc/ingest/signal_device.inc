@@ -21,12 +21,13 @@
 //   k_sg_convert     B = 1: one lane per depth run
 //   k_cv_bin_fill    B > 1: one lane per depth run; the bins it overlaps take overlap * depth by a return-less 64-bit atomic add into a
 //                    dense u64 table, one slot per bin of every chosen reference, the references end to end (integers: no order)
-//   k_sg_mark / k_bam_scan / k_sg_entries   a bin begins an entry where S differs from the bin before, where its width does (the
-//                    short last bin) or where its reference begins; compacted by ballots (256 bins per workgroup) into (reference,
-//                    bin, S)
-//   k_sg_keep / k_bam_scan / k_sg_close     entry k ends where entry k + 1 of its reference begins, the last at the reference's
-//                    end; the entries with S = 0 are dropped by this second compaction; the totals are reduced over the wave, one
-//                    atomic each per wave, min and max of the float32 through the order-preserving map of their bits to u32
+//   k_bt_count<K, false> / k_bam_scan / k_bt_entries<K>   the bins-to-runs pipeline every kind of track K shares (SgTrack here,
+//                    CpTrack, PsTrack; bintrack_run).  SgTrack: a bin begins an entry where S differs from the bin before, where
+//                    its width does (the short last bin) or where its reference begins; compacted by ballots (256 bins per
+//                    workgroup; cv_count, cv_slot) into (reference, bin, S)
+//   k_bt_count<K, true> / k_bam_scan / k_bt_close<K>      entry k ends where entry k + 1 of its reference begins, the last at the
+//                    reference's end; the entries with S = 0 are dropped by this second compaction; the totals are reduced over the
+//                    wave, one atomic each per wave, min and max of the float32 through the order-preserving map of their bits to u32
 //   k_sg_textlen / k_sg_text                k_cv_textlen / k_cv_text with the value formatted as above
 //   k_sg_sections / k_sg_secsums            one lane per run: its item; one lane per section: its two sums over its runs in order
 //   k_sg_zoom_fill   one lane per bin of level 0: a binary search for the first run of its reference that ends behind the bin's
@@ -113,87 +114,93 @@ __global__ void __launch_bounds__(256) k_cv_bin_fill(const int *__restrict__ rre
     }
 }
 
-// whether bin b begins an entry; k: its reference, j: its bin there
-__device__ __forceinline__ bool sg_begins(const unsigned long long *__restrict__ tab, u64 b, const SgGeo &G, u32 &k, u32 &j)
+// From the bin tables to runs, once for every kind of track (signal below, compare_device.inc, poisson_device.inc).  A kind is a small
+// struct K that the kernels take by value:
+//   TABLES, ENTRY     its u64 tables per bin (the depth sums of k_cv_bin_fill in front) and its bytes per entry: what the call holds
+//   tables, entries   where they lie in the call's two blocks (host)
+//   eid, ej           the reference and the bin of every entry, written here; the rest of an entry is the kind's
+//   begins(b, G, id, j, x)    whether bin b = bin j of reference id begins an entry; x: a word of the kind's own for put
+//   put(o, b, x)      the kind's part of entry o, which begins at bin b
+//   kept(e)           whether entry e becomes a run
+//   value(e, w)       the bits of v of entry e, whose bins are w bases wide
+template <class K> __device__ __forceinline__ bool bt_begins(const K &T, u64 b, const SgGeo &G, u32 &id, u32 &j, u32 &x)
 {
-    k = cv_zoom_id(G.boff, G.nc, b);
-    j = (u32)(b - G.boff[k]);
-    if (j == 0) return true;
-    return ((u64)j + 1u) * G.B > (u64)G.lens[k] || tab[b - 1u] != tab[b];        // the short last bin; another S
+    id = cv_zoom_id(G.boff, G.nc, b);
+    j = (u32)(b - G.boff[id]);
+    return T.begins(b, G, id, j, x);
 }
 
-__global__ void __launch_bounds__(256) k_sg_mark(const unsigned long long *__restrict__ tab, u64 nb, SgGeo G, u32 *__restrict__ kcnt)
+// the bins that begin an entry, or with ENTRIES the entries that are kept, per workgroup of 256
+template <class K, bool ENTRIES> __global__ void __launch_bounds__(256) k_bt_count(K T, u64 n, SgGeo G, u32 *__restrict__ kcnt)
 {
     __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 b = (u64)blockIdx.x * 256u + t;
-    u32 k, j;
-    const u64 m = __ballot(b < nb && sg_begins(tab, b, G, k, j));
-    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    u32 id, j, x;
+    cv_count(i < n && (ENTRIES ? T.kept(i) : bt_begins(T, i, G, id, j, x)), kcnt, s_w);
 }
 
-__global__ void __launch_bounds__(256) k_sg_entries(const unsigned long long *__restrict__ tab, u64 nb, SgGeo G, const u64 *__restrict__ kbase,
-                                                    u32 *__restrict__ eid, u32 *__restrict__ ej, unsigned long long *__restrict__ eS)
+template <class K> __global__ void __launch_bounds__(256) k_bt_entries(K T, u64 nb, SgGeo G, const u64 *__restrict__ kbase)
 {
     __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 b = (u64)blockIdx.x * 256u + t;
-    u32 k = 0, j = 0;
-    const bool keep = b < nb && sg_begins(tab, b, G, k, j);
-    const u64 m = __ballot(keep);
-    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
+    const u64 b = (u64)blockIdx.x * 256u + threadIdx.x;
+    u32 id = 0, j = 0, x = 0;
+    const bool keep = b < nb && bt_begins(T, b, G, id, j, x);
+    const u64 o = cv_slot(keep, kbase, s_w);
     if (!keep) return;
-    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
-    eid[o] = k;
-    ej[o] = j;
-    eS[o] = tab[b];
+    T.eid[o] = id;
+    T.ej[o] = j;
+    T.put(o, b, x);
 }
 
-__global__ void __launch_bounds__(256) k_sg_keep(const unsigned long long *__restrict__ eS, u64 n, u32 *__restrict__ kcnt)
+// entry e ends where entry e + 1 of its reference begins, the last at the reference's end
+template <class K> __global__ void __launch_bounds__(256) k_bt_close(K T, u64 n, const u64 *__restrict__ kbase, SgGeo G, int *__restrict__ oref,
+                                                                     u32 *__restrict__ ostart, u32 *__restrict__ oend, u32 *__restrict__ oval,
+                                                                     unsigned long long *__restrict__ tot)
 {
     __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 k = (u64)blockIdx.x * 256u + t;
-    const u64 m = __ballot(k < n && eS[k] != 0);
-    if ((t & 63u) == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
-    if (t == 0) kcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ void __launch_bounds__(256) k_sg_close(const u32 *__restrict__ eid, const u32 *__restrict__ ej, const unsigned long long *__restrict__ eS,
-                                                  u64 n, const u64 *__restrict__ kbase, SgGeo G, double scale, int *__restrict__ oref,
-                                                  u32 *__restrict__ ostart, u32 *__restrict__ oend, u32 *__restrict__ oval,
-                                                  unsigned long long *__restrict__ tot)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 k = (u64)blockIdx.x * 256u + t;
-    const bool keep = k < n && eS[k] != 0;
-    const u64 m = __ballot(keep);
-    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
+    const u64 e = (u64)blockIdx.x * 256u + threadIdx.x;
+    const bool keep = e < n && T.kept(e);
+    const u64 o = cv_slot(keep, kbase, s_w);
     u64 width = 0;
     u32 bits = 0;
     if (keep) {
-        u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-        for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
-        const u32 id = eid[k], len = G.lens[id];
-        const u32 a = ej[k] * G.B;                                                         // (below len < 2^32)
-        const u32 z = k + 1u < n && eid[k + 1u] == id ? ej[k + 1u] * G.B : len;
-        const u32 w = len - a < G.B ? len - a : G.B;                                       // the width of the run's bins
-        bits = sg_value((u64)eS[k], scale, w);
+        const u32 id = T.eid[e], len = G.lens[id];
+        const u32 a = T.ej[e] * G.B;                                                       // (below len < 2^32)
+        const u32 z = e + 1u < n && T.eid[e + 1u] == id ? T.ej[e + 1u] * G.B : len;
+        bits = T.value(e, len - a < G.B ? len - a : G.B);                                  // the width of the run's bins
         oref[o] = G.cref[id];
         ostart[o] = a;
         oend[o] = z;
         oval[o] = bits;
         width = (u64)(z - a);
     }
-    sg_totals(lane, keep, width, bits, tot);
+    sg_totals(threadIdx.x & 63u, keep, width, bits, tot);
 }
+
+namespace {
+struct SgTrack {        // signal: an entry is (reference, bin, S)
+    static constexpr u64 TABLES = 1, ENTRY = 16;
+    double scale;
+    const unsigned long long *tab;
+    unsigned long long *eS;
+    u32 *eid, *ej;
+    void tables(const unsigned long long *t, u64) { tab = t; }
+    void entries(u8 *p, u64 ne)
+    {
+        eS = (unsigned long long *)p;
+        eid = (u32 *)(eS + ne);
+        ej = eid + ne;
+    }
+    __device__ __forceinline__ bool begins(u64 b, const SgGeo &G, u32 id, u32 j, u32 &) const
+    {
+        if (j == 0) return true;
+        return ((u64)j + 1u) * G.B > (u64)G.lens[id] || tab[b - 1u] != tab[b];         // the short last bin; another S
+    }
+    __device__ __forceinline__ void put(u64 o, u64 b, u32) const { eS[o] = tab[b]; }
+    __device__ __forceinline__ bool kept(u64 e) const { return eS[e] != 0; }
+    __device__ __forceinline__ u32 value(u64 e, u32 w) const { return sg_value((u64)eS[e], scale, w); }
+};
+}  // namespace
 
 // round(|v| * 10^6), ties to even, of the float32 with these bits (|v| < 2^40), in integers; the sign is the caller's (sg_minus)
 __device__ __forceinline__ u64 sg_micro(u32 bits)
@@ -423,16 +430,11 @@ __global__ void __launch_bounds__(256) k_sg_zoom_emit(u8 *__restrict__ bins, u64
                                                       u32 *__restrict__ out, u32 *__restrict__ table)
 {
     __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 b = (u64)blockIdx.x * 256u + t;
+    const u64 b = (u64)blockIdx.x * 256u + threadIdx.x;
     const ZmBins B(bins, n);
     const bool keep = b < n && B.cnt[b] != 0;
-    const u64 m = __ballot(keep);
-    if (lane == 0) s_w[t >> 6] = (u32)__popcll(m);
-    __syncthreads();
+    const u64 o = cv_slot(keep, kbase, s_w);
     if (!keep) return;
-    u64 o = kbase[blockIdx.x] + (u64)__popcll(m & ((1ull << lane) - 1ull));
-    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
     const u32 id = cv_zoom_id(off, nc, b);
     const u64 a = (b - off[id]) * z;
     const u32 start = (u32)a, end = a + z < (u64)lens[id] ? (u32)(a + z) : lens[id];
@@ -515,109 +517,23 @@ void signal_drop(Coverage &c)
     for (double &x : c.stot) x = 0;
 }
 
-// the work of signal behind its checks; a failure leaves no signal
-int coverage_signal_run(pmx_dbam *b, const std::string &fn, u32 bin, double scale)
+// the signal slot for m runs, counted from here on: signal_drop takes them off again
+int signal_alloc(pmx_dbam *b, const std::string &fn, u64 m)
 {
-    HIPOK(hipSetDevice(b->device));
-    hipStream_t st = b->stream;
     Coverage &c = b->cv;
-    const u64 n = c.nruns;
-    unsigned long long tot[3] = {0, ~0ull, 0};
-    u64 nout = 0;
-    if (n) {
-        const CvRuns V(c.runs.as<u8>(), n);
-        DevAlloc d_tot;
-        HIPOK(hipMalloc(&d_tot.p, 64));
-        HIPOK(hipMemcpyAsync(d_tot.p, tot, 24, hipMemcpyHostToDevice, st));
-        u64 *dt = d_tot.as<u64>();
-        auto out_alloc = [&](u64 m) {
-            if (hipMalloc(&c.sruns.p, 16 * m) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(m) + " runs");
-            }
-            c.snruns = m;           // (counted from here on: signal_drop takes them off again)
-            c.bytes += 16 * m;
-            if (b->st) stream_note(*b);
-            return 0;
-        };
-        if (bin == 1) {
-            if (int rc = out_alloc(n)) return rc;
-            const CvRuns O(c.sruns.as<u8>(), n);
-            hipLaunchKernelGGL(k_sg_convert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, n, scale, O.ref, O.start,
-                               O.end, O.depth, d_tot.as<unsigned long long>());
-            HIPOK(hipGetLastError());
-            nout = n;
-        } else {
-            const u64 nref = b->ref_names.size(), nc = c.chosen.size();
-            std::vector<u64> boff(nc + 1, 0), bof(std::max<u64>(nref, 1), 0);
-            std::vector<u32> lens(nc, 0);
-            std::vector<int> cref(nc, 0);
-            for (u64 k = 0; k < nc; k++) {
-                lens[k] = (u32)std::max<int64_t>(b->ref_lens[(u64)c.chosen[k]], 0);
-                cref[k] = c.chosen[k];
-                bof[(u64)c.chosen[k]] = boff[k];
-                boff[k + 1] = boff[k] + ((u64)lens[k] + bin - 1) / bin;
-            }
-            const u64 nb = boff[nc], nwg = (nb + 255) / 256;
-            if (nwg >= (1ull << 31)) return fail(PMX_DBAM_ERR_INVALID, fn + ": 2^39 bins or more");
-            DevAlloc d_geo, d_tab, d_k, d_kb, d_e;
-            CvHold held(b);
-            const u64 geo_bytes = 8 * boff.size() + 8 * bof.size() + 8 * std::max<u64>(nc, 1);
-            HIPOK(hipMalloc(&d_geo.p, geo_bytes));
-            if (hipMalloc(&d_tab.p, 8 * nb) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for the bin table: " + std::to_string(8 * nb) +
-                                                   " bytes asked for (8 per bin of " + std::to_string(bin) + " bases)");
-            }
-            held.add(geo_bytes + 8 * nb + 12 * nwg);
-            HIPOK(hipMalloc(&d_k.p, 4 * nwg));
-            HIPOK(hipMalloc(&d_kb.p, 8 * nwg));
-            u64 *d_boff = d_geo.as<u64>(), *d_bof = d_boff + boff.size();
-            u32 *d_lens = (u32 *)(d_bof + bof.size());
-            int *d_cref = (int *)(d_lens + std::max<u64>(nc, 1));
-            HIPOK(hipMemcpyAsync(d_boff, boff.data(), 8 * boff.size(), hipMemcpyHostToDevice, st));
-            HIPOK(hipMemcpyAsync(d_bof, bof.data(), 8 * bof.size(), hipMemcpyHostToDevice, st));
-            HIPOK(hipMemcpyAsync(d_lens, lens.data(), 4 * nc, hipMemcpyHostToDevice, st));
-            HIPOK(hipMemcpyAsync(d_cref, cref.data(), 4 * nc, hipMemcpyHostToDevice, st));
-            HIPOK(hipMemsetAsync(d_tab.p, 0, 8 * nb, st));
-            const SgGeo G{d_boff, d_lens, d_cref, (u32)nc, bin};
-            unsigned long long *tab = d_tab.as<unsigned long long>();
-            hipLaunchKernelGGL(k_cv_bin_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, n, d_bof, bin, tab);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_sg_mark, dim3((unsigned)nwg), dim3(256), 0, st, tab, nb, G, d_k.as<u32>());
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), nwg, d_kb.as<u64>(), dt + 4);
-            HIPOK(hipGetLastError());
-            u64 ne = 0;
-            HIPOK(hipMemcpyAsync(&ne, dt + 4, 8, hipMemcpyDeviceToHost, st));
-            HIPOK(hipStreamSynchronize(st));       // (boff, bof, lens and cref are locals)
-            if (hipMalloc(&d_e.p, 16 * ne) != hipSuccess) {      // (ne >= 1: the first bin of the first reference that has one)
-                (void)hipGetLastError();
-                return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(ne) + " bin boundaries");
-            }
-            held.add(16 * ne);
-            unsigned long long *eS = d_e.as<unsigned long long>();
-            u32 *eid = (u32 *)(eS + ne), *ej = eid + ne;
-            hipLaunchKernelGGL(k_sg_entries, dim3((unsigned)nwg), dim3(256), 0, st, tab, nb, G, d_kb.as<u64>(), eid, ej, eS);
-            HIPOK(hipGetLastError());
-            const u64 ewg = (ne + 255) / 256;          // (ewg <= nwg: d_k and d_kb are used again)
-            hipLaunchKernelGGL(k_sg_keep, dim3((unsigned)ewg), dim3(256), 0, st, eS, ne, d_k.as<u32>());
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), ewg, d_kb.as<u64>(), dt + 6);
-            HIPOK(hipGetLastError());
-            HIPOK(hipMemcpyAsync(&nout, dt + 6, 8, hipMemcpyDeviceToHost, st));
-            HIPOK(hipStreamSynchronize(st));
-            if (nout) {
-                if (int rc = out_alloc(nout)) return rc;
-                const CvRuns O(c.sruns.as<u8>(), nout);
-                hipLaunchKernelGGL(k_sg_close, dim3((unsigned)ewg), dim3(256), 0, st, eid, ej, eS, ne, d_kb.as<u64>(), G, scale, O.ref, O.start, O.end, O.depth,
-                                   d_tot.as<unsigned long long>());
-                HIPOK(hipGetLastError());
-            }
-        }
-        HIPOK(hipMemcpyAsync(tot, d_tot.p, 24, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));            // (the table, the entries and the scans are freed behind it)
+    if (hipMalloc(&c.sruns.p, 16 * m) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(m) + " runs");
     }
+    c.snruns = m;
+    c.bytes += 16 * m;
+    if (b->st) stream_note(*b);
+    return 0;
+}
+
+// the totals of the nout runs in the slot; tot: sg_totals' three words
+void signal_have(Coverage &c, u32 bin, u64 nout, const unsigned long long *tot)
+{
     float lo = 0.0f, hi = 0.0f;
     if (nout) {
         const u32 l = sg_unkey((u32)tot[1]), h = sg_unkey((u32)tot[2]);
@@ -630,26 +546,176 @@ int coverage_signal_run(pmx_dbam *b, const std::string &fn, u32 bin, double scal
     c.stot[1] = (double)(nout ? tot[0] : 0);
     c.stot[2] = (double)lo;
     c.stot[3] = (double)hi;
+}
+
+struct BtStage {        // what a kind's own stage between the fills and the marks is given (poisson's lambda)
+    hipStream_t st;
+    CvHold &held;
+    SgGeo G;
+    unsigned long long *tab;        // the kind's tables, TABLES * nb words
+    u64 nb, nwg, L;                 // bins, workgroups of 256 bins, the sum of the chosen lengths
+    u64 *kb;                        // nwg words, free until the marks
+};
+
+// The work of a track of kind K behind its checks, from the depth runs of b (and of the control, where the kind has one, whose
+// stream has been waited for) to the runs in b's signal slot and their totals; a failure leaves no signal.  stage(T, BtStage) runs
+// between the fills and the marks.
+template <class K, class Stage> int bintrack_run(pmx_dbam *b, pmx_dbam *ctl, const std::string &fn, u32 bin, K T, Stage stage)
+{
+    HIPOK(hipSetDevice(b->device));
+    hipStream_t st = b->stream;
+    Coverage &c = b->cv;
+    pmx_dbam *const src[2] = {b, ctl};
+    const u32 ns = ctl ? 2u : 1u;
+    unsigned long long tot[3] = {0, ~0ull, 0};
+    u64 nout = 0;
+    if (c.nruns || (ctl && ctl->cv.nruns)) {
+        const u64 nc = c.chosen.size();
+        std::vector<u64> boff(nc + 1, 0), bof[2];       // bof[h][r]: the first bin of reference r of src[h] (every run lies on a chosen one)
+        std::vector<u32> lens(nc, 0);
+        std::vector<int> cref(nc, 0);
+        u64 L = 0, geo_bytes = 8 * boff.size() + 8 * std::max<u64>(nc, 1);
+        for (u32 h = 0; h < ns; h++) {
+            bof[h].assign(std::max<u64>(src[h]->ref_names.size(), 1), 0);
+            geo_bytes += 8 * bof[h].size();
+        }
+        for (u64 k = 0; k < nc; k++) {
+            lens[k] = (u32)std::max<int64_t>(b->ref_lens[(u64)c.chosen[k]], 0);
+            cref[k] = c.chosen[k];
+            for (u32 h = 0; h < ns; h++) bof[h][(u64)src[h]->cv.chosen[k]] = boff[k];
+            boff[k + 1] = boff[k] + ((u64)lens[k] + bin - 1) / bin;
+            L += lens[k];
+        }
+        const u64 nb = boff[nc], nwg = (nb + 255) / 256, tab_bytes = 8 * K::TABLES * nb;      // (nb >= 1: a run lies in a bin)
+        if (nwg >= (1ull << 31)) return fail(PMX_DBAM_ERR_INVALID, fn + ": 2^39 bins or more");
+        DevAlloc d_tot, d_geo, d_tab, d_k, d_kb, d_e;
+        CvHold held(b);
+        HIPOK(hipMalloc(&d_tot.p, 64));
+        HIPOK(hipMemcpyAsync(d_tot.p, tot, 24, hipMemcpyHostToDevice, st));
+        u64 *dt = d_tot.as<u64>();
+        HIPOK(hipMalloc(&d_geo.p, geo_bytes));
+        if (hipMalloc(&d_tab.p, tab_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for the bin table" + (K::TABLES > 1 ? "s" : "") + ": " + std::to_string(tab_bytes) +
+                                               " bytes asked for (" + std::to_string(8 * K::TABLES) + " per bin of " + std::to_string(bin) + " bases)");
+        }
+        held.add(geo_bytes + tab_bytes + 12 * nwg);
+        HIPOK(hipMalloc(&d_k.p, 4 * nwg));
+        HIPOK(hipMalloc(&d_kb.p, 8 * nwg));
+        u64 *d_boff = d_geo.as<u64>(), *d_bof[2] = {d_boff + boff.size(), d_boff + boff.size() + bof[0].size()};
+        u32 *d_lens = (u32 *)(d_bof[ns - 1] + bof[ns - 1].size());
+        int *d_cref = (int *)(d_lens + std::max<u64>(nc, 1));
+        HIPOK(hipMemcpyAsync(d_boff, boff.data(), 8 * boff.size(), hipMemcpyHostToDevice, st));
+        for (u32 h = 0; h < ns; h++) HIPOK(hipMemcpyAsync(d_bof[h], bof[h].data(), 8 * bof[h].size(), hipMemcpyHostToDevice, st));
+        HIPOK(hipMemcpyAsync(d_lens, lens.data(), 4 * nc, hipMemcpyHostToDevice, st));
+        HIPOK(hipMemcpyAsync(d_cref, cref.data(), 4 * nc, hipMemcpyHostToDevice, st));
+        HIPOK(hipMemsetAsync(d_tab.p, 0, 8 * ns * nb, st));            // (the depth sums; a kind fills its further tables itself)
+        const SgGeo G{d_boff, d_lens, d_cref, (u32)nc, bin};
+        unsigned long long *tab = d_tab.as<unsigned long long>();
+        for (u32 h = 0; h < ns; h++) {      // once per handle into its own table, for B = 1 as for any other bin (two run lists do not line up)
+            const Coverage &s = src[h]->cv;
+            if (!s.nruns) continue;
+            const CvRuns V((u8 *)s.runs.p, s.nruns);
+            hipLaunchKernelGGL(k_cv_bin_fill, dim3((unsigned)((s.nruns + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, s.nruns, d_bof[h],
+                               bin, tab + h * nb);
+            HIPOK(hipGetLastError());
+        }
+        T.tables(tab, nb);
+        if (int rc = stage(T, BtStage{st, held, G, tab, nb, nwg, L, d_kb.as<u64>()})) return rc;
+        hipLaunchKernelGGL((k_bt_count<K, false>), dim3((unsigned)nwg), dim3(256), 0, st, T, nb, G, d_k.as<u32>());
+        HIPOK(hipGetLastError());
+        hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), nwg, d_kb.as<u64>(), dt + 4);
+        HIPOK(hipGetLastError());
+        u64 ne = 0;
+        HIPOK(hipMemcpyAsync(&ne, dt + 4, 8, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));       // (the geometry is of locals, and a stage's host arrays have been read)
+        if (hipMalloc(&d_e.p, K::ENTRY * ne) != hipSuccess) {        // (ne >= 1: the first bin begins an entry)
+            (void)hipGetLastError();
+            return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(ne) + " bin boundaries");
+        }
+        held.add(K::ENTRY * ne);
+        T.entries(d_e.as<u8>(), ne);
+        hipLaunchKernelGGL(k_bt_entries<K>, dim3((unsigned)nwg), dim3(256), 0, st, T, nb, G, d_kb.as<u64>());
+        HIPOK(hipGetLastError());
+        const u64 ewg = (ne + 255) / 256;          // (ewg <= nwg: d_k and d_kb are used again)
+        hipLaunchKernelGGL((k_bt_count<K, true>), dim3((unsigned)ewg), dim3(256), 0, st, T, ne, G, d_k.as<u32>());
+        HIPOK(hipGetLastError());
+        hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_k.as<u32>(), d_k.as<u32>(), ewg, d_kb.as<u64>(), dt + 6);
+        HIPOK(hipGetLastError());
+        HIPOK(hipMemcpyAsync(&nout, dt + 6, 8, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+        if (nout) {
+            if (int rc = signal_alloc(b, fn, nout)) return rc;
+            const CvRuns O(c.sruns.as<u8>(), nout);
+            hipLaunchKernelGGL(k_bt_close<K>, dim3((unsigned)ewg), dim3(256), 0, st, T, ne, d_kb.as<u64>(), G, O.ref, O.start, O.end, O.depth,
+                               d_tot.as<unsigned long long>());
+            HIPOK(hipGetLastError());
+        }
+        HIPOK(hipMemcpyAsync(tot, d_tot.p, 24, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));            // (the tables, the entries and the scans are freed behind it)
+    }
+    signal_have(c, bin, nout, tot);
     return 0;
 }
 
-int coverage_signal_impl(pmx_dbam *b, uint32_t bin, double scale, double *totals)
+const auto bt_no_stage = [](auto &, const BtStage &) { return 0; };
+
+// the work of signal behind its checks; a failure leaves no signal
+int coverage_signal_run(pmx_dbam *b, const std::string &fn, u32 bin, double scale)
 {
-    const std::string fn = "pmx_dbam_coverage_signal";
-    if (!b) return fail(PMX_DBAM_ERR_INVALID, "null handle");
+    Coverage &c = b->cv;
+    const u64 n = c.nruns;
+    if (bin > 1 || !n) return bintrack_run(b, nullptr, fn, bin, SgTrack{scale}, bt_no_stage);
+    HIPOK(hipSetDevice(b->device));         // B = 1: the signal runs are the depth runs
+    hipStream_t st = b->stream;
+    unsigned long long tot[3] = {0, ~0ull, 0};
+    const CvRuns V(c.runs.as<u8>(), n);
+    DevAlloc d_tot;
+    HIPOK(hipMalloc(&d_tot.p, 64));
+    HIPOK(hipMemcpyAsync(d_tot.p, tot, 24, hipMemcpyHostToDevice, st));
+    if (int rc = signal_alloc(b, fn, n)) return rc;
+    const CvRuns O(c.sruns.as<u8>(), n);
+    hipLaunchKernelGGL(k_sg_convert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, V.ref, V.start, V.end, V.depth, n, scale, O.ref, O.start, O.end,
+                       O.depth, d_tot.as<unsigned long long>());
+    HIPOK(hipGetLastError());
+    HIPOK(hipMemcpyAsync(tot, d_tot.p, 24, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    signal_have(c, bin, n, tot);
+    return 0;
+}
+
+// The checks every track call begins with, in the order the calls have always made them; two: the kind has a control (ctl).
+int track_checks(pmx_dbam *b, pmx_dbam *ctl, bool two, const std::string &fn, uint32_t bin, double *totals)
+{
+    if (!b || (two && !ctl)) return fail(PMX_DBAM_ERR_INVALID, "null handle");
     if (!totals) return fail(PMX_DBAM_ERR_INVALID, fn + ": null output");
     for (int k = 0; k < 4; k++) totals[k] = 0;
-    Coverage &c = b->cv;
+    const Coverage &c = b->cv;
     if (c.state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, fn + ": no runs: call pmx_dbam_coverage_finish first");
+    if (two) {          // the same device, the same chosen references in name, length and order
+        const Coverage &cc = ctl->cv;
+        if (cc.state != CV_RUNS) return fail(PMX_DBAM_ERR_INVALID, fn + ": the control has no runs: call pmx_dbam_coverage_finish on it first");
+        if (b->device != ctl->device) return fail(PMX_DBAM_ERR_INVALID, fn + ": the control is on another device");
+        bool same = c.chosen.size() == cc.chosen.size();
+        for (u64 k = 0; same && k < c.chosen.size(); k++) {
+            const u64 x = (u64)c.chosen[k], y = (u64)cc.chosen[k];
+            same = b->ref_names[x] == ctl->ref_names[y] && std::max<int64_t>(b->ref_lens[x], 0) == std::max<int64_t>(ctl->ref_lens[y], 0);
+        }
+        if (!same) return fail(PMX_DBAM_ERR_INVALID, fn + ": the chosen references of the control differ in name, length or order");
+    }
     if (bin < 1 || bin > SG_MAX_BIN) return fail(PMX_DBAM_ERR_INVALID, fn + ": a bin of 1 to 65536 bases");
-    if (!std::isfinite(scale) || scale < 0x1p-64)
-        return fail(PMX_DBAM_ERR_INVALID, fn + ": the scale is a finite number of at least 2^-64 (below it a value could be a float32 denormal)");
-    if (scale * (double)c.tot[4] >= 0x1p40)
-        return fail(PMX_DBAM_ERR_INVALID, fn + ": scale * max_depth is 2^40 or more (a value's text is made in 64-bit integers)");
+    return 0;
+}
+
+// run() behind the checks: both streams waited for, the signal before dropped, and none left by a failure; then the totals
+template <class Run> int track_make(pmx_dbam *b, pmx_dbam *ctl, double *totals, Run run)
+{
+    Coverage &c = b->cv;
     HIPOK(hipSetDevice(b->device));
+    if (ctl && ctl != b) HIPOK(hipStreamSynchronize(ctl->stream));
     HIPOK(hipStreamSynchronize(b->stream));
     signal_drop(c);
-    struct Drop {       // a failure from here on leaves no signal
+    struct Drop {
         Coverage &c;
         bool ok = false;
         ~Drop()
@@ -657,10 +723,21 @@ int coverage_signal_impl(pmx_dbam *b, uint32_t bin, double scale, double *totals
             if (!ok) signal_drop(c);
         }
     } drop{c};
-    if (int rc = coverage_signal_run(b, fn, bin, scale)) return rc;
+    if (int rc = run()) return rc;
     drop.ok = true;
     for (int k = 0; k < 4; k++) totals[k] = c.stot[k];
     return 0;
+}
+
+int coverage_signal_impl(pmx_dbam *b, uint32_t bin, double scale, double *totals)
+{
+    const std::string fn = "pmx_dbam_coverage_signal";
+    if (int rc = track_checks(b, nullptr, false, fn, bin, totals)) return rc;
+    if (!std::isfinite(scale) || scale < 0x1p-64)
+        return fail(PMX_DBAM_ERR_INVALID, fn + ": the scale is a finite number of at least 2^-64 (below it a value could be a float32 denormal)");
+    if (scale * (double)b->cv.tot[4] >= 0x1p40)
+        return fail(PMX_DBAM_ERR_INVALID, fn + ": scale * max_depth is 2^40 or more (a value's text is made in 64-bit integers)");
+    return track_make(b, nullptr, totals, [&] { return coverage_signal_run(b, fn, bin, scale); });
 }
 
 }  // namespace

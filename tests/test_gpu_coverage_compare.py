@@ -243,6 +243,38 @@ def test_a_reference_with_reads_in_one_file_only(tmp_path):
         assert none.ranges(rc, signal=True).tolist() == [0] * 5
 
 
+def test_subtracting_an_empty_control_makes_the_signal_track(tmp_path):
+    """compare with "subtract" against a control without a run on the chosen references is signal, bit for bit: t - 0.0 is t, and
+    with S_c = 0 everywhere compare's runs begin where signal's do.  On the host classes too, over an empty pileup."""
+    refs = [("s0", 1000), ("s1", 257), ("s2", 64)]
+    rnd = random.Random(11)
+    reads = []
+    for k, (_n, length) in enumerate(refs):
+        for _ in range((240, 80, 30)[k]):
+            l = rnd.randint(1, 40)
+            reads.append((k, rnd.randint(1, length - l + 1), l, rnd.randint(0, 1)))
+    reads.sort(key=lambda x: (x[0], x[1]))
+    crefs = refs + [("s3", 500)]
+    creads = sorted((3, rnd.randint(1, 460), 36, 0) for _ in range(50))
+    names = [n for n, _l in refs]
+    t, none = _host_count(reads, refs, [1] * 3, 0), _host_count(creads, crefs, [1, 1, 1, 0], 0)
+    assert t.n_runs > 100 and none.n_runs == 0 and none.reads == 0 and none.refs == t.refs
+    scales = (1.0, 0.37, 2.0 ** -64)
+    for B in (1, 2, 7, 50, 64, 65536):
+        for s in scales:
+            assert t.compare(none, B, "subtract", s, 1.0, 1.0) == t.signal(B, s)
+    with DeviceBamReader(_bam_of(tmp_path, "t", refs, reads)) as r, DeviceBamReader(_bam_of(tmp_path, "c", crefs, creads)) as rc:
+        acc, cacc = coverage.device_count_of(r, FC.MAPQ, None, 0), coverage.device_count_of(rc, FC.MAPQ, names, 0)
+        assert cacc.finish(rc)["runs"] == 0 and acc.result(r) == t
+        for B in (1, 2, 7, 64):
+            for s in scales:
+                want = acc.signal(r, B, s)
+                plain = acc.signal_result(r)
+                assert plain == t.signal(B, s) and want["runs"] > 0
+                assert acc.compare(r, cacc, rc, B, "subtract", s, 1.0, 1.0) == want
+                assert acc.signal_result(r) == plain
+
+
 def test_the_pair_pileup(tmp_path):
     def pairs(seed, n):
         recs = [r for _l, r in FR.planted()] + FR.random_pairs(random.Random(seed), n)
