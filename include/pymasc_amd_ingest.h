@@ -434,6 +434,44 @@ int pmx_dbam_coverage_call_rows(pmx_dbam *b, int64_t first, int64_t n, int32_t *
                                 float *value, uint32_t *runs);
 int64_t pmx_dbam_coverage_call_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *buf, int64_t cap);
 
+/* Benjamini-Hochberg q-scores for the p-score track (version >= 23): the correction over every base of the chosen
+ * genome, made on the device from the runs pmx_dbam_coverage_poisson left in the signal slot.  The definitions are this project's own;
+ * nothing here was compared with MACS2.  Everything is integer arithmetic or float64, and every float64 operation is rounded to nearest
+ * even on its own (no fused multiply-add).
+ *   input      The runs (ref, start0, end0, v) of a p-score track, v float32: +0.0 or the float32 of a positive number, so v >= 0 and
+ *              never a NaN.  A track whose smallest value is negative is refused.
+ *   tests      N = the sum of the lengths of the chosen references, u64 (the L of pmx_dbam_coverage_poisson's l_bg).  Every base of
+ *              the chosen genome is one test; a base in no run has p = 1 and counts in N only.
+ *   distinct   u_1 > u_2 > ... > u_m are the distinct values of the runs, compared as floats.  W_i = the sum of end0 - start0 over
+ *              the runs with the value u_i, u64.
+ *   rank       r_1 = 1, r_i = 1 + W_1 + ... + W_(i-1), u64.  r_i <= N always.
+ *   raw score  x_i = f64(u_i) + (lg2(f64(r_i)) - lg2(f64(N))) * 0.3010299956639812, with lg2 the stated algorithm of
+ *              pmx_dbam_coverage_compare.  r_i and N are below 2^53, so the conversions are exact.
+ *   monotone   Q_i = max(0.0, min(x_1 .. x_i)) and q_i = f32(Q_i).  min and max are associative and exact and the sums are integers,
+ *              so no result depends on scheduling or on the order of the sort.  q is non-increasing in i, hence non-decreasing in the
+ *              p-score.
+ *   table      m rows (u_i, W_i, q_i), descending in u.
+ *   cutoff     pcut(X) for a finite float64 X: f64(u_i) of the largest i with f64(q_i) >= X, the smallest p-score whose q-score
+ *              reaches X; 2^40 when no row reaches X (v < 2^40, so pmx_dbam_coverage_call then finds nothing); X <= 0 gives f64(u_m).
+ *   lookup     The q-score of a peak is q_i of the row with u_i == its value.  A peak's value is the value of one of its runs, so the
+ *              row exists: a miss is an internal error (PMX_DBAM_ERR_DEVICE), not a -1.
+ * pmx_dbam_coverage_qvalue builds the table: totals = m, N, the covered bases (the sum of every W), the bases with q > 0.  The runs go
+ * through one key pass, a stable radix sort over the 8-bit digits that differ, a u64 prefix sum, a compaction of the heads and a
+ * prefix minimum.  PMX_DBAM_ERR_INVALID: no signal, a signal that is not a p-score track, 2^32 runs or more.  A track with 0 runs
+ * gives an empty table and is legal.  The table (16 bytes per row) is kept on the handle beside the signal runs, counted towards
+ * pmx_dbam_stream_info's peak, and dropped with them by the next signal, compare, poisson, begin or close; qvalue again replaces it.
+ * qvalue drops a peak table that is there: call again.  Inside the call 40 bytes per run, 3072 per 8192 runs, 64, and 16 per row are
+ * held besides, counted the same way and freed before it returns; out of memory is PMX_DBAM_ERR_OPEN with the bytes asked for.  A
+ * failure leaves no table and the signal as it was.
+ * qvalue_rows copies the rows [first, first + n) (p = u, bases = W, q), with the range rules of pmx_dbam_coverage_signal_runs.
+ * qvalue_cutoff gives pcut(X) by a search on the device; a non-finite X is PMX_DBAM_ERR_INVALID.  Both without a table:
+ * PMX_DBAM_ERR_INVALID.
+ * While the handle holds a table, pmx_dbam_coverage_call_text writes the text of the peak's q-score in column 9, in place of the
+ * second -1; column 8 is as above.  Without a table every byte is as above; call and call_rows are the same either way. */
+int pmx_dbam_coverage_qvalue(pmx_dbam *b, uint64_t totals[4]);
+int pmx_dbam_coverage_qvalue_rows(pmx_dbam *b, int64_t first, int64_t n, float *p, uint64_t *bases, float *q);
+int pmx_dbam_coverage_qvalue_cutoff(pmx_dbam *b, double X, double *pcut);
+
 /* A DEFLATE encoder on the device (version >= 18): independent chunks of at most PMX_DEFLATE_MAX_CHUNK bytes, each
  * turned into one complete zlib stream (RFC 1950 around RFC 1951): the header 0x78 with a 32-KB window and no dictionary, DEFLATE
  * blocks of which the last is marked final, the big-endian Adler-32 of the raw bytes.  Matches have length 4 .. 258 and distance

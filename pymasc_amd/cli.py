@@ -305,6 +305,14 @@ def get_parser() -> argparse.ArgumentParser:
     out.add_argument("--coverage-lambda", metavar=("S", "L"), type=int, nargs=2,
                      help="the small and the large window of --coverage-poisson around every bin, in bases (each 0 .. 2^31 - 1, 0: "
                           "off; default 1000 10000); needs --coverage-poisson")
+    out.add_argument("--coverage-qvalue", action="store_true",
+                     help="with --coverage-poisson and one of --coverage-call / --coverage-call-q, which it needs: the "
+                          "Benjamini-Hochberg q-scores of the p-score track over every base of the chosen chromosomes, made on the "
+                          "GPU; column 9 of the narrowPeak holds -log10 q of every peak.  The coverage file stays the p-score track")
+    out.add_argument("--coverage-call-q", metavar="X", type=float,
+                     help="call the peaks at the smallest p-score whose q-score (-log10 q) reaches X (any finite number; 2: q <= "
+                          "0.01) and write both scores; needs --coverage-poisson, not with --coverage-call, implies --coverage-qvalue; "
+                          "--coverage-call-gap and --coverage-call-length apply")
     out.add_argument("--gc-bias", metavar="FASTA", type=Path,
                      help="also write <name>_gcbias.tab for every file: the reads the correlation sees, each placed on the window "
                           "of this genome (FASTA; plain, gzip or bgzip) that begins at its 5' end, counted per G + C content of the "
@@ -401,10 +409,22 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "(the input is not scaled: the score counts reads)")
         if args.coverage_lambda is not None and not all(0 <= x < 1 << 31 for x in args.coverage_lambda):
             parser.error("argument --coverage-lambda: each window must lie in [0, 2^31 - 1]")
-    if args.coverage_call is None and (args.coverage_call_gap is not None or args.coverage_call_length is not None):
+    if args.coverage_call_q is not None:
+        if args.coverage_call is not None:
+            parser.error("argument --coverage-call-q: not with --coverage-call (the cutoff is the p-score whose q-score reaches X)")
+        if not args.coverage_poisson:
+            parser.error("argument --coverage-call-q: needs --coverage-poisson")
+        if not float("-inf") < args.coverage_call_q < float("inf"):
+            parser.error("argument --coverage-call-q: must be a finite number")
+    if args.coverage_qvalue:
+        if not args.coverage_poisson:
+            parser.error("argument --coverage-qvalue: needs --coverage-poisson")
+        if args.coverage_call is None and args.coverage_call_q is None:
+            parser.error("argument --coverage-qvalue: needs --coverage-call or --coverage-call-q")
+    if args.coverage_call is None and args.coverage_call_q is None and (args.coverage_call_gap is not None or args.coverage_call_length is not None):
         parser.error("argument --coverage-call-gap / --coverage-call-length: needs --coverage-call")
-    if args.coverage_call is not None:
-        if not float("-inf") < args.coverage_call < float("inf"):
+    if args.coverage_call is not None or args.coverage_call_q is not None:
+        if args.coverage_call is not None and not float("-inf") < args.coverage_call < float("inf"):
             parser.error("argument --coverage-call: must be a finite number")
         if args.coverage_call_gap is not None and not 0 <= args.coverage_call_gap < 1 << 31:
             parser.error("argument --coverage-call-gap: must lie in [0, 2^31 - 1]")
@@ -545,13 +565,15 @@ def _run(args, device, rank: int) -> int:
         if args.coverage_compress:
             extra["coverage_compress"] = "device" if args.coverage_deflate == "device" else True
         for key in ("coverage_bin", "coverage_normalize", "coverage_scale", "coverage_genome_size", "coverage_control", "coverage_compare",
-                    "coverage_pseudocount", "coverage_call", "coverage_call_gap", "coverage_call_length"):
+                    "coverage_pseudocount", "coverage_call", "coverage_call_gap", "coverage_call_length", "coverage_call_q"):
             if getattr(args, key) is not None:
                 extra[key] = getattr(args, key)
         if args.coverage_poisson:
             extra["coverage_poisson"] = True
             if args.coverage_lambda is not None:
                 extra["coverage_lambda"] = tuple(args.coverage_lambda)
+        if args.coverage_qvalue:
+            extra["coverage_qvalue"] = True
     if args.fragments:
         extra["fragments"] = True
     if args.fragments_max is not None:          # (it also bounds a pair pileup)

@@ -133,6 +133,31 @@ own (no fused multiply-add).
   the width.  Rows are ``(ref, start0, end0, v)`` in header order; the totals are the signal's four.
 * The track line is the signal's (``normalize=none scale=1.0``) followed by `` control=<the control's basename>
   poisson=<W_s>,<W_l>`` (``poisson_tail``).
+
+Benjamini-Hochberg q-scores for the p-score track (DESIGN.md 7.18.7; ``--coverage-qvalue``, ``--coverage-call-q``;
+``Signal.qvalues``, ``DeviceCount.qvalue``, ``QTable``): the correction over every base of the chosen genome.  The definitions are
+this project's own: nothing here was compared with MACS2.  Everything is integer arithmetic or float64, each float64 operation
+rounded to nearest even on its own (no fused multiply-add).
+
+* Input: the runs ``(ref, start0, end0, v)`` of a p-score track, ``v`` float32: ``+0.0`` or the float32 of a positive number, so
+  ``v >= 0`` and never a NaN.  A track whose smallest value is negative is refused.
+* Tests: ``N`` = the sum of the lengths of the chosen references, u64 (the ``L`` of ``l_bg`` above).  Every base of the chosen
+  genome is one test; a base in no run has p = 1 and counts in ``N`` only.
+* Distinct values: ``u_1 > u_2 > ... > u_m`` are the distinct values of the runs, compared as floats.  ``W_i`` = the sum of
+  ``end0 - start0`` over the runs with the value ``u_i``, u64.
+* Rank: ``r_1 = 1``, ``r_i = 1 + W_1 + ... + W_(i-1)``, u64.  ``r_i <= N`` always.
+* Raw score: ``x_i = f64(u_i) + (lg2(f64(r_i)) - lg2(f64(N))) * 0.3010299956639812`` with ``lg2`` the stated algorithm above.
+  ``r_i`` and ``N`` are below 2^53, so the conversions are exact.
+* Monotone, clamped: ``Q_i = max(0.0, min(x_1 .. x_i))`` and ``q_i = f32(Q_i)``.  ``min`` and ``max`` are associative and exact
+  and the sums are integers, so no result depends on any order.  ``q`` is non-increasing in ``i``, hence non-decreasing in the
+  p-score.
+* Table: ``m`` rows ``(u_i, W_i, q_i)``, descending in ``u`` (``QTable``).
+* Cutoff: ``pcut(X)`` for a finite float64 ``X`` is ``f64(u_i)`` of the largest ``i`` with ``f64(q_i) >= X``, the smallest
+  p-score whose q-score reaches ``X``; ``2^40`` when no row reaches ``X`` (``v < 2^40``, so ``call`` then finds nothing);
+  ``X <= 0`` gives ``f64(u_m)``.
+* Lookup: the q-score of a peak is ``q_i`` of the row with ``u_i == value``.  A peak's value is the value of one of its runs, so
+  the row exists: a miss is an internal error, not a ``-1``.  With a table, column 9 of a narrowPeak line is the text of the
+  peak's q-score (``format_value``); the coverage file itself stays the p-score track.
 """
 from __future__ import annotations
 
@@ -163,6 +188,7 @@ SIGNAL_TOTALS = ("runs", "covered_bases", "min", "max")
 COMPARE = ("log2", "ratio", "subtract")     # ``coverage_compare``; an operation's index is its ``op`` of pmx_dbam_coverage_compare
 CALL_SUFFIX = "_coverage_peaks.narrowPeak"
 CALL_TOTALS = ("passing_runs", "candidates", "peaks", "peak_bases", "passing_bases")
+QVALUE_TOTALS = ("rows", "tests", "covered_bases", "positive_bases")
 CALL_GAP, CALL_LENGTH = 30, 200             # the defaults of ``coverage_call_gap`` and ``coverage_call_length``
 MAX_CALL_INT = (1 << 31) - 1                # the largest ``max_gap`` and ``min_length``
 LAMBDA_WINDOWS = (1000, 10000)              # the defaults of ``coverage_lambda``: the small and the large window of the p-score track
@@ -463,14 +489,77 @@ def call_score(value) -> np.ndarray:
     return np.trunc(np.minimum(np.maximum(x, 0.0), 1000.0)).astype(np.int64)
 
 
+def check_q(x, what: str = "coverage_call_q") -> float:
+    """``X`` of ``pcut(X)``: a finite number."""
+    if isinstance(x, (str, bool)) or x is None:
+        raise ValueError("{} is a number".format(what))
+    try:
+        x = float(x)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("{} is a number".format(what)) from None
+    if not np.isfinite(x):
+        raise ValueError("{} is a finite number".format(what))
+    return x
+
+
+class QTable:
+    """The q-scores of a p-score track: ``p`` the distinct values ``u_i`` (float32, descending), ``bases`` their
+    covered bases ``W_i`` (uint64), ``q`` their q-scores (float32, non-increasing), ``tests`` the number ``N`` of tests.  Two are
+    equal when their columns are, bit for bit, with ``tests``."""
+
+    def __init__(self, p, bases, q, tests: int):
+        self.p = np.asarray(p, dtype=np.float32).ravel()
+        self.bases = np.asarray(bases, dtype=np.uint64).ravel()
+        self.q = np.asarray(q, dtype=np.float32).ravel()
+        self.tests = int(tests)
+        if not (self.p.size == self.bases.size == self.q.size):
+            raise ValueError("the three columns have one length")
+        if self.p.size and (self.p.min() < 0 or np.any(np.diff(self.p.view(np.uint32).astype(np.int64)) >= 0)):
+            raise ValueError("the values are not negative and descend")
+
+    @property
+    def totals(self):
+        """(rows, tests, covered bases, bases with q > 0), the order of ``pmx_dbam_coverage_qvalue``."""
+        return int(self.p.size), self.tests, int(self.bases.sum(dtype=np.uint64)), int(self.bases[self.q > 0].sum(dtype=np.uint64))
+
+    def lookup(self, values) -> np.ndarray:
+        """``q_i`` (float32) of the rows with ``u_i == value``; a value without a row is an internal error."""
+        bits = np.asarray(values, dtype=np.float32).ravel().view(np.uint32)
+        asc = self.p.view(np.uint32)[::-1]                      # (v >= +0.0: the bits order as the floats do)
+        at = np.searchsorted(asc, bits)
+        if bits.size and (np.any(at >= asc.size) or np.any(asc[np.minimum(at, max(asc.size - 1, 0))] != bits)):
+            raise RuntimeError("a value has no row in the q-score table")
+        return self.q[::-1][at] if bits.size else np.zeros(0, dtype=np.float32)
+
+    def cutoff(self, X) -> float:
+        """``pcut(X)``: the smallest p-score whose q-score reaches ``X``, ``2^40`` when none does."""
+        X = check_q(X, "X")
+        n = int(np.count_nonzero(self.q.astype(np.float64) >= X))       # (q is non-increasing: the rows that reach X are the first n)
+        return float(self.p[n - 1]) if n else MAX_VALUE
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, QTable) and self.tests == other.tests and self.p.size == other.p.size
+                and np.array_equal(self.p.view(np.uint32), other.p.view(np.uint32)) and np.array_equal(self.bases, other.bases)
+                and np.array_equal(self.q.view(np.uint32), other.q.view(np.uint32)))
+
+    __hash__ = None
+
+    def __repr__(self) -> str:
+        return "QTable(rows={}, tests={}, covered_bases={}, positive_bases={})".format(*self.totals)
+
+
 class Peaks:
     """The peaks called from a signal track: ``rows``: ``{name: (start, end, summit, value, runs)}`` (uint32,
     uint32, uint32, float32, uint32) of the references that have a peak, in header order; ``cutoff``, ``max_gap``, ``min_length``;
-    ``totals``: by name (``CALL_TOTALS``).  Two are equal when their rows are, bit for bit, with the three parameters and the
-    totals."""
+    ``totals``: by name (``CALL_TOTALS``).  Two are equal when their rows are, bit for bit, with the three parameters, the
+    totals and the q-score table."""
 
-    def __init__(self, rows, cutoff: float, max_gap: int, min_length: int, totals, pscore: bool = False):
-        """``pscore``: the track is a p-score track: column 8 of a line holds the value's text, not ``-1``."""
+    def __init__(self, rows, cutoff: float, max_gap: int, min_length: int, totals, pscore: bool = False, qtable=None):
+        """``pscore``: the track is a p-score track: column 8 of a line holds the value's text, not ``-1``.
+        ``qtable``: its ``QTable`` (7.18.7): column 9 holds the text of the peak's q-score, not ``-1``."""
+        if qtable is not None and not (isinstance(qtable, QTable) and pscore):
+            raise ValueError("qtable is the QTable of a p-score track")
+        self.qtable = qtable
         self.pscore = bool(pscore)
         types = (np.uint32, np.uint32, np.uint32, np.float32, np.uint32)
         self.rows = {str(k): tuple(np.asarray(x, dtype=t).ravel() for x, t in zip(v, types)) for k, v in rows.items()}
@@ -492,16 +581,18 @@ class Peaks:
         for name, (s, e, m, v, _r) in self.rows.items():
             for a in range(0, s.size, chunk):
                 z = slice(a, a + chunk)
-                yield "".join("{}\t{}\t{}\tpeak_{}\t{}\t.\t{}\t{}\t-1\t{}\n".format(name, x, y, no + a + i + 1, sc, format_value(val),
-                                                                                 format_value(val) if self.pscore else "-1", c - x)
-                               for i, (x, y, c, val, sc) in enumerate(zip(s[z].tolist(), e[z].tolist(), m[z].tolist(), v[z],
-                                                                          call_score(v[z]).tolist()))).encode()
+                q9 = ["-1"] * int(v[z].size) if self.qtable is None else [format_value(x) for x in self.qtable.lookup(v[z])]
+                yield "".join("{}\t{}\t{}\tpeak_{}\t{}\t.\t{}\t{}\t{}\t{}\n".format(name, x, y, no + a + i + 1, sc, format_value(val),
+                                                                                 format_value(val) if self.pscore else "-1", q, c - x)
+                               for i, (x, y, c, val, sc, q) in enumerate(zip(s[z].tolist(), e[z].tolist(), m[z].tolist(), v[z],
+                                                                             call_score(v[z]).tolist(), q9))).encode()
             no += s.size
 
     def __eq__(self, other) -> bool:
         return (isinstance(other, Peaks) and (self.cutoff, self.max_gap, self.min_length, self.pscore) == (other.cutoff, other.max_gap,
                                                                                                             other.min_length, other.pscore)
                 and self.totals == other.totals and list(self.rows) == list(other.rows)
+                and (self.qtable is None) == (other.qtable is None) and (self.qtable is None or self.qtable == other.qtable)
                 and all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for k in self.rows for a, b in zip(self.rows[k], other.rows[k])))
 
     __hash__ = None
@@ -552,12 +643,40 @@ class Signal:
 
     tail = property(lambda self: signal_tail(self.bin, self.normalize, self.scale) + self.more)
 
-    def call(self, cutoff, max_gap: int = CALL_GAP, min_length: int = CALL_LENGTH) -> Peaks:
+    def qvalues(self) -> QTable:
+        """The q-scores of a p-score track, in numpy: the path of host readers and the checker of
+        ``pmx_dbam_coverage_qvalue``.  ``N`` is the sum of ``refs``' lengths; the distinct values descend, ``W`` their covered
+        bases, ``r = 1 +`` the bases in front, ``x = f64(u) + (lg2(f64(r)) - lg2(f64(N))) * 0.3010299956639812``,
+        ``q = f32(max(0.0, the running minimum of x))``."""
+        if not self.pscore:
+            raise ValueError("the track is not a p-score track (Coverage.poisson makes one)")
+        if self.refs is None:
+            raise ValueError("the track does not know its chosen references' lengths: the number of tests is their sum")
+        tests = sum(l for _n, l in self.refs)
+        if not self.runs:
+            return QTable([], [], [], tests)
+        v = np.concatenate([x for _s, _e, x in self.runs.values()])
+        w = np.concatenate([e.astype(np.uint64) - s.astype(np.uint64) for s, e, _x in self.runs.values()])
+        if v.min() < 0:
+            raise ValueError("the smallest value of the track is negative: not a p-score")
+        bits = v.view(np.uint32)
+        order = np.argsort(bits, kind="stable")[::-1]           # (v >= +0.0: the bits order as the floats do)
+        sb, sw = bits[order], w[order]
+        heads = np.flatnonzero(np.concatenate(([True], sb[1:] != sb[:-1])))
+        u, W = sb[heads].view(np.float32), np.add.reduceat(sw, heads)
+        r = np.uint64(1) + np.concatenate((np.zeros(1, dtype=np.uint64), np.cumsum(W, dtype=np.uint64)[:-1]))
+        d = lg2(r.astype(np.float64)) - lg2(np.full(1, tests, dtype=np.float64))[0]
+        x = u.astype(np.float64) + d * LOG10_2
+        mn = np.minimum.accumulate(x)
+        return QTable(u, W, np.where(mn > 0.0, mn, 0.0).astype(np.float32), tests)
+
+    def call(self, cutoff, max_gap: int = CALL_GAP, min_length: int = CALL_LENGTH, qtable=None) -> Peaks:
         """The peaks of the track, in numpy: the path of host readers and the checker of
         ``pmx_dbam_coverage_call``.  A run passes when ``f64(v) >= cutoff``; consecutive passing runs of a reference are linked
         when the second begins at most ``max_gap`` bases behind the first's end; a maximal chain of at least ``min_length`` bases
         from its first start to its last end is a peak, with the largest ``v`` of its passing runs, the middle ``s + (e - s) // 2``
-        of the first run that has it, and the number of its passing runs."""
+        of the first run that has it, and the number of its passing runs.  ``qtable``: the track's ``QTable``, handed on to
+        the ``Peaks`` for column 9."""
         cutoff, max_gap, min_length = check_call(cutoff, max_gap, min_length)
         rows, tot = {}, dict.fromkeys(CALL_TOTALS, 0)
         for name, (s, e, v) in self.runs.items():
@@ -585,7 +704,7 @@ class Signal:
             tot["peaks"] += int(keep.sum())
             tot["peak_bases"] += int((end - start)[keep].sum())
             tot["passing_bases"] += int(np.add.reduceat(pe - ps, first)[keep].sum())
-        return Peaks(rows, cutoff, max_gap, min_length, tot, self.pscore)
+        return Peaks(rows, cutoff, max_gap, min_length, tot, self.pscore, qtable)
 
     def __eq__(self, other) -> bool:
         return (isinstance(other, Signal) and (self.bin, self.scale, self.pscore) == (other.bin, other.scale, other.pscore)
@@ -863,7 +982,7 @@ class DeviceCount(SideAccumulator):
     def begin(self, reader) -> None:
         """A zeroed table on the reader's handle (a stream reader calls it again when a pass opens a new handle)."""
         mask = np.ascontiguousarray(self.use, dtype=np.uint8) if self.names else np.zeros(1, dtype=np.uint8)
-        self.totals = self.sig = self.called = None
+        self.totals = self.sig = self.called = self.qtab = None
         rc = reader._L.pmx_dbam_coverage_begin(reader._h, 0 if self.extend == PAIR else self.extend, mask.ctypes.data)
         if rc:
             reader._raise(rc)
@@ -900,7 +1019,7 @@ class DeviceCount(SideAccumulator):
         """A track into the handle's signal slot by ``pmx_dbam_coverage_<what>(handle, *args, totals)``, in place of the one before
         and its peaks; what a ``Signal`` of it says beside its runs is kept in ``sig``.  Returns the totals by name."""
         out = np.zeros(4, dtype=np.float64)
-        self.sig = self.called = None
+        self.sig = self.called = self.qtab = None
         rc = getattr(reader._L, "pmx_dbam_coverage_" + what)(reader._h, *args, out.ctypes.data)
         if rc:
             reader._raise(rc)
@@ -1109,11 +1228,52 @@ class DeviceCount(SideAccumulator):
         for first in range(0, total, int(chunk)):
             yield self.call_text(reader, first, min(int(chunk), total - first))
 
+    def qvalue(self, reader) -> Dict[str, int]:
+        """Builds the q-score table of the p-score track on the handle (``pmx_dbam_coverage_qvalue``) and returns
+        its totals by name (``QVALUE_TOTALS``).  The table stays on the handle until the next ``signal``, ``compare``, ``poisson``
+        or ``begin``; while it is there ``call_text`` writes column 9.  A peak table that is there is dropped: ``call`` again."""
+        out = np.zeros(4, dtype=np.uint64)
+        self.called = self.qtab = None
+        rc = reader._L.pmx_dbam_coverage_qvalue(reader._h, out.ctypes.data)
+        if rc:
+            reader._raise(rc)
+        self.qtab = dict(zip(QVALUE_TOTALS, (int(x) for x in out)))
+        return self.qtab
+
+    def qvalue_rows(self, reader, first: int = 0, n=None):
+        """(p float32, bases uint64, q float32) of the rows ``[first, first + n)`` (``pmx_dbam_coverage_qvalue_rows``)."""
+        if n is None:
+            if self.qtab is None:
+                raise ValueError("no table: call qvalue first")
+            n = self.qtab["rows"] - int(first)
+        n = int(n)
+        out = [np.zeros(max(n, 1), dtype=t) for t in (np.float32, np.uint64, np.float32)]
+        rc = reader._L.pmx_dbam_coverage_qvalue_rows(reader._h, int(first), n, *(x.ctypes.data for x in out))
+        if rc:
+            reader._raise(rc)
+        return tuple(x[:n] for x in out)
+
+    def qvalue_cutoff(self, reader, X) -> float:
+        """``pcut(X)`` of the table on the handle, searched on the device (``pmx_dbam_coverage_qvalue_cutoff``)."""
+        out = ctypes.c_double()
+        rc = reader._L.pmx_dbam_coverage_qvalue_cutoff(reader._h, check_q(X, "X"), ctypes.byref(out))
+        if rc:
+            reader._raise(rc)
+        return float(out.value)
+
+    def qvalue_result(self, reader) -> QTable:
+        """The table on the handle as a ``QTable``."""
+        t = QTable(*self.qvalue_rows(reader), self.qtab["tests"])
+        if t.totals != tuple(self.qtab[k] for k in QVALUE_TOTALS):
+            raise RuntimeError("pmx_dbam_coverage_qvalue: the rows do not add up to the totals")
+        return t
+
     def call_result(self, reader) -> Peaks:
-        """The peak table on the handle as a ``Peaks``."""
+        """The peak table on the handle as a ``Peaks``, with the q-score table when the handle holds one."""
         ref, start, end, summit, value, runs = self.call_rows(reader)
         tot = self.called["totals"]
-        p = Peaks(_by_reference(self.names, ref, start, end, summit, value, runs), self.called["cutoff"], self.called["max_gap"], self.called["min_length"], tot, self.called["pscore"])
+        p = Peaks(_by_reference(self.names, ref, start, end, summit, value, runs), self.called["cutoff"], self.called["max_gap"], self.called["min_length"], tot, self.called["pscore"],
+                  None if self.qtab is None else self.qvalue_result(reader))
         inside = int(runs.sum(dtype=np.int64))
         if (p.n_peaks, p.peak_bases) != (tot["peaks"], tot["peak_bases"]) or not (tot["peaks"] <= tot["candidates"] <= tot["passing_runs"]) \
                 or inside > tot["passing_runs"] or not (inside <= tot["passing_bases"] <= tot["peak_bases"]):

@@ -1787,7 +1787,7 @@ void reset_stream(pmx_dbam &b)
 extern "C" {
 
 const char *pmx_dbam_last_error(void) { return g_err.c_str(); }
-int pmx_dbam_version(void) { return 22; }
+int pmx_dbam_version(void) { return 23; }
 
 static int dbam_open_impl(const char *path, int device, int nthreads, pmx_dbam **out);
 int pmx_dbam_open(const char *path, int device, int nthreads, pmx_dbam **out)
@@ -2581,6 +2581,7 @@ static int select_body(pmx_dbam *b, const std::vector<u8> &chosen)
 #include "signal_device.inc"
 #include "compare_device.inc"
 #include "poisson_device.inc"
+#include "qvalue_device.inc"
 #include "call_device.inc"
 #include "gcbias_device.inc"
 #include "fragments_device.inc"

@@ -19,7 +19,9 @@
 //   chrom TAB start TAB end TAB peak_<n> TAB score TAB . TAB value TAB -1 TAB -1 TAB (summit - start) LF
 // score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0)), the product exact in float64; value by sg_micro / sg_minus / sg_split of
 // signal_device.inc.  No header line.  When the signal slot holds a p-score track (pmx_dbam_coverage_poisson, poisson_device.inc; DESIGN.md
-// 7.18.6) the first -1 (column 8) is the value's text as well; on every other track each byte is as above.
+// 7.18.6) the first -1 (column 8) is the value's text as well; on every other track each byte is as above.  When the handle also holds a
+// q-score table (pmx_dbam_coverage_qvalue, qvalue_device.inc; DESIGN.md 7.18.7) the second -1 (column 9) is the text of the peak's
+// q-score, found by a binary search of the table by the value's bits; without a table each byte is as above.
 //
 //   k_cl_count<0> / k_bam_scan / k_cl_list<0>   the passing runs, compacted by ballots (256 per workgroup) into the list P of run indices
 //   k_cl_count<1> / k_bam_scan / k_cl_list<1>   over P: an element begins a candidate when it is the first, when its reference differs
@@ -183,9 +185,28 @@ __device__ __forceinline__ u8 *cl_value(u8 *q, u32 bits, u64 N, u64 whole, u32 f
     return q;
 }
 
-// no0: the number of the first peak of the pull; ps: the signal is a p-score track (poisson_device.inc): column 8 holds the value too
+namespace {
+struct ClQ {            // the q-score table of the handle for column 9 (m = 0 and null pointers: there is none); miss: set on a value without a row
+    const u32 *u, *q;
+    u64 m;
+    u32 *miss;
+};
+}  // namespace
+
+// the length of the text of the float32 with these bits
+__device__ __forceinline__ u32 cl_value_len(u32 bits)
+{
+    u64 whole;
+    u32 frac, nd;
+    const u64 N = sg_micro(bits);
+    sg_split(N, whole, frac, nd);
+    return sg_minus(bits, N) + sg_width(whole) + (nd ? nd + 1u : 0u);
+}
+
+// no0: the number of the first peak of the pull; ps: the signal is a p-score track (poisson_device.inc): column 8 holds the value too;
+// Q: the q-score table, when there is one: column 9 holds the peak's q-score
 __global__ void __launch_bounds__(256) k_cl_textlen(const int *__restrict__ pref, const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
-                                                    const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0, int ps,
+                                                    const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0, int ps, ClQ Q,
                                                     const u32 *__restrict__ noff, u32 *__restrict__ len, u32 *__restrict__ wsum)
 {
     __shared__ u32 s_w[4];
@@ -200,7 +221,7 @@ __global__ void __launch_bounds__(256) k_cl_textlen(const int *__restrict__ pref
         sg_split(N, whole, frac, nd);
         const u32 vl = sg_minus(pval[i], N) + sg_width(whole) + (nd ? nd + 1u : 0u);          // the value's text
         l = noff[r + 1u] - noff[r] + cv_width(pstart[i]) + cv_width(pend[i]) + 5u + sg_width(no0 + i) + cv_width(cl_score(pval[i])) + 1u + vl +
-            (ps ? vl + 2u : 4u) + cv_width(psummit[i] - pstart[i]) + 10u;
+            (ps ? vl + (Q.u ? cl_value_len(qv_lookup(Q.u, Q.q, Q.m, pval[i], Q.miss)) : 2u) : 4u) + cv_width(psummit[i] - pstart[i]) + 10u;
         len[i] = l;
     }
     l = (u32)cx_wave_sum((u64)l);
@@ -210,7 +231,7 @@ __global__ void __launch_bounds__(256) k_cl_textlen(const int *__restrict__ pref
 }
 
 __global__ void __launch_bounds__(256) k_cl_text(const int *__restrict__ pref, const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
-                                                 const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0, int ps,
+                                                 const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0, int ps, ClQ Q,
                                                  const u32 *__restrict__ noff, const u8 *__restrict__ names, const u32 *__restrict__ len,
                                                  const u64 *__restrict__ wbase, u8 *__restrict__ out)
 {
@@ -235,8 +256,17 @@ __global__ void __launch_bounds__(256) k_cl_text(const int *__restrict__ pref, c
     *--q = '\n';
     q = cv_digits(q, psummit[i] - pstart[i]);
     *--q = '\t';
-    *--q = '1';
-    *--q = '-';
+    if (Q.u) {                          // (a q-score table: column 9 is the text of the peak's q-score)
+        const u32 qb = qv_lookup(Q.u, Q.q, Q.m, pval[i], Q.miss);
+        u64 qwhole;
+        u32 qfrac, qnd;
+        const u64 qN = sg_micro(qb);
+        sg_split(qN, qwhole, qfrac, qnd);
+        q = cl_value(q, qb, qN, qwhole, qfrac, qnd);
+    } else {
+        *--q = '1';
+        *--q = '-';
+    }
     *--q = '\t';
     if (ps) {                           // (a p-score track: column 8 is the value's text as well)
         q = cl_value(q, pval[i], N, whole, frac, nd);
@@ -440,16 +470,33 @@ int64_t coverage_call_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *
     const u64 m = (u64)n, no0 = (u64)first + 1u;
     const int ps = (int)b->cv.spscore;
     const ClPeaks K(b->cv.peaks.as<u8>(), b->cv.npeaks);
-    return coverage_text_pull(
+    ClQ Q{nullptr, nullptr, 0, nullptr};
+    DevAlloc d_miss;
+    CvHold held(b);
+    if (b->cv.qhave && ps) {            // (a table of 0 rows goes with 0 runs and 0 peaks: n == 0 has returned)
+        const QvTable T(b->cv.qtab.as<u8>(), b->cv.qrows);
+        held.add(4);
+        HIPOK(hipSetDevice(b->device));
+        HIPOK(hipMalloc(&d_miss.p, 4));
+        HIPOK(hipMemsetAsync(d_miss.p, 0, 4, st));
+        Q = ClQ{T.u, T.q, b->cv.qrows, d_miss.as<u32>()};
+    }
+    const int64_t got = coverage_text_pull(
         b, fn, m, buf, cap,
         [&](dim3 grid, const u32 *noff, u32 *len, u32 *wsum) {
             hipLaunchKernelGGL(k_cl_textlen, grid, dim3(256), 0, st, K.ref + first, K.start + first, K.end + first, K.summit + first, K.value + first, m,
-                               no0, ps, noff, len, wsum);
+                               no0, ps, Q, noff, len, wsum);
         },
         [&](dim3 grid, const u32 *noff, const u8 *names, const u32 *len, const u64 *wbase, u8 *out) {
             hipLaunchKernelGGL(k_cl_text, grid, dim3(256), 0, st, K.ref + first, K.start + first, K.end + first, K.summit + first, K.value + first, m, no0,
-                               ps, noff, names, len, wbase, out);
+                               ps, Q, noff, names, len, wbase, out);
         });
+    if (got >= 0 && Q.u) {
+        u32 miss = 0;
+        HIPOK(hipMemcpy(&miss, d_miss.p, 4, hipMemcpyDeviceToHost));
+        if (miss) return fail(PMX_DBAM_ERR_DEVICE, fn + ": a peak's value has no row in the q-score table");
+    }
+    return got;
 }
 
 }  // namespace

@@ -85,6 +85,12 @@ struct Coverage {
     bool phave = false;              // peaks have been called from these signal runs
     u64 npeaks = 0;                  // the peaks
     u64 ptot[5] = {0, 0, 0, 0, 0};   // passing runs, candidates, peaks, peak bases, passing bases
+    // the q-scores of a p-score track (pmx_dbam_coverage_qvalue, qvalue_device.inc; DESIGN.md 7.18.7): from qvalue until the next
+    // qvalue, signal, compare, poisson, begin or close
+    DevAlloc qtab;                   // u8: per distinct value its covered bases (8 bytes), its float32 p-score, its float32 q-score
+    bool qhave = false;              // the table has been made of these signal runs
+    u64 qrows = 0;                   // its rows
+    u64 qtot[4] = {0, 0, 0, 0};      // rows, tests, covered bases, bases with q > 0
     bool on() const { return state == CV_TABLE; }
     u64 held() const { return bytes; }
 };

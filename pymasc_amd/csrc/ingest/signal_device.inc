@@ -502,9 +502,27 @@ void call_drop(Coverage &c)
     for (u64 &x : c.ptot) x = 0;
 }
 
+// the arrays of the q-score table (qvalue_device.inc) in its one block: covered bases (8 bytes per row), p-score, q-score (4 each)
+struct QvTable {
+    u64 *W;
+    u32 *u, *q;
+    QvTable(u8 *p, u64 m) : W((u64 *)p), u((u32 *)(p + 8 * m)), q((u32 *)(p + 12 * m)) {}
+};
+
+// the q-scores of a p-score track go with its runs
+void qvalue_drop(Coverage &c)
+{
+    c.bytes -= std::min<u64>(16 * c.qrows, c.bytes);
+    c.qtab = DevAlloc{};
+    c.qhave = false;
+    c.qrows = 0;
+    for (u64 &x : c.qtot) x = 0;
+}
+
 void signal_drop(Coverage &c)
 {
     call_drop(c);
+    qvalue_drop(c);
     if (c.zsg) zoom_drop(c);
     c.zsg = false;
     c.bytes -= std::min<u64>(16 * c.snruns, c.bytes);

@@ -149,6 +149,9 @@ INGEST_PROTOTYPES = {
     "pmx_dbam_coverage_call": (_int, [_vp, ctypes.c_double, _u32, _u32, _vp]),
     "pmx_dbam_coverage_call_rows": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmx_dbam_coverage_call_text": (_i64, [_vp, _i64, _i64, _vp, _i64]),
+    "pmx_dbam_coverage_qvalue": (_int, [_vp, _vp]),
+    "pmx_dbam_coverage_qvalue_rows": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "pmx_dbam_coverage_qvalue_cutoff": (_int, [_vp, ctypes.c_double, _vp]),
     "pmx_dbam_coverage_signal_runs": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pmx_dbam_coverage_signal_text": (_i64, [_vp, _i64, _i64, _vp, _i64]),
     "pmx_dbam_coverage_signal_ranges": (_i64, [_vp, _vp, _i64]),

@@ -44,7 +44,8 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
         coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
         coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None, coverage_control=None,
         coverage_compare: str = "log2", coverage_pseudocount: float = 1.0, coverage_call=None, coverage_call_gap: int = 30,
-        coverage_call_length: int = 200, coverage_poisson: bool = False, coverage_lambda=(1000, 10000)):
+        coverage_call_length: int = 200, coverage_poisson: bool = False, coverage_lambda=(1000, 10000),
+        coverage_qvalue: bool = False, coverage_call_q=None):
     """Returns (genome-wide result, [paths written]).  ``outdir/<bam stem>_{cc,mscc,nreads}.tab`` are written by
     rank 0 (every rank holds the result).  ``context``: an existing pymasc_amd.ffi.Context to run on (default: one per
     call on ``device``).  ``device_ingest``: see sharding.run_sharded (default: the BAM file is inflated and decoded on the GPU
@@ -123,6 +124,13 @@ def run(bam_path, outdir, max_shift: int, read_len: Optional[int] = None, mapq_c
     otherwise (``coverage.Coverage.poisson``); with ``coverage_call`` the narrowPeak holds the score in column 8 as well.  It
     excludes a given ``coverage_compare`` or ``coverage_pseudocount`` and a ``coverage_normalize`` / ``coverage_scale`` other than
     ``"none"`` / 1 (ValueError: the treatment is not scaled, the score counts reads); ``coverage_lambda`` without it is a ValueError.
+    ``coverage_qvalue``: with ``coverage_poisson`` and one of ``coverage_call`` / ``coverage_call_q``, which it needs (ValueError):
+    the Benjamini-Hochberg q-scores of the p-score track over every base of the chosen references, made on the
+    GPU with device ingest (``coverage.DeviceCount.qvalue``) and in numpy otherwise (``coverage.Signal.qvalues``); column 9 of the
+    narrowPeak holds the q-score of every peak.  ``coverage_call_q``: a finite number ``X``: the peaks are called at ``pcut(X)``,
+    the smallest p-score whose q-score reaches ``X`` (``X = 2``: q <= 0.01); it needs ``coverage_poisson``, excludes
+    ``coverage_call`` and implies ``coverage_qvalue`` (ValueError otherwise); ``coverage_call_gap`` / ``coverage_call_length``
+    apply as with ``coverage_call``.  The coverage file itself stays the p-score track.
     ``gc_bias``: a genome FASTA (plain, gzip or bgzip): rank 0 also writes ``<stem>_gcbias.tab`` (pymasc_amd.gcbias, DESIGN.md
     7.19): the reads the fingerprint counts, each placed on the genome window of ``gc_window`` bases (1 .. 1024) that begins at
     its 5' end, counted per G + C content of the window beside the number of genome windows of that content; windows with a base
@@ -220,6 +228,8 @@ class _Settings:
     coverage_call_length: int
     coverage_poisson: bool          # the track is the Poisson -log10 p of the treatment against coverage_control
     coverage_lambda: tuple          # its small and its large window in bases (0: off)
+    coverage_qvalue: bool           # the narrowPeak holds the Benjamini-Hochberg q-score of every peak in column 9
+    coverage_call_q: object         # None, or X: the peaks are called at pcut(X), the smallest p-score whose q-score reaches X
     gc_bias: object                 # None, or the _GcGenome parsed once for the call
     gc_window: int
     fragments: bool
@@ -273,12 +283,26 @@ def _settings(kw: dict) -> _Settings:
     if extend not in ("auto", coverage.PAIR) and (isinstance(extend, (str, bool)) or int(extend) != extend or int(extend) < 0):
         raise ValueError("coverage_extend is \"auto\", \"pair\" or an integer of at least 0")
     cutoff, gap, length = kw["coverage_call"], kw["coverage_call_gap"], kw["coverage_call_length"]
-    if cutoff is None and (gap != coverage.CALL_GAP or length != coverage.CALL_LENGTH):
-        raise ValueError("coverage_call_gap and coverage_call_length need coverage_call")
     if cutoff is not None:
         cutoff, gap, length = coverage.check_call(cutoff, gap, length)
-    given.update(coverage_call=cutoff, coverage_call_gap=gap, coverage_call_length=length)
-    given.update(coverage=bool(kw["coverage"]) or kw["coverage_control"] is not None or cutoff is not None,
+    call_q = kw["coverage_call_q"]
+    if call_q is not None:
+        if cutoff is not None:
+            raise ValueError("coverage_call_q excludes coverage_call: the cutoff is pcut(coverage_call_q)")
+        if not kw["coverage_poisson"]:
+            raise ValueError("coverage_call_q needs coverage_poisson: q-scores are made of a p-score track")
+        call_q = coverage.check_q(call_q)
+        _c, gap, length = coverage.check_call(0.0, gap, length)
+    elif cutoff is None and (gap != coverage.CALL_GAP or length != coverage.CALL_LENGTH):
+        raise ValueError("coverage_call_gap and coverage_call_length need coverage_call")
+    if kw["coverage_qvalue"]:
+        if not kw["coverage_poisson"]:
+            raise ValueError("coverage_qvalue needs coverage_poisson: q-scores are made of a p-score track")
+        if cutoff is None and call_q is None:
+            raise ValueError("coverage_qvalue needs coverage_call or coverage_call_q: the q-scores are written with the peaks")
+    given.update(coverage_call=cutoff, coverage_call_gap=gap, coverage_call_length=length, coverage_call_q=call_q,
+                 coverage_qvalue=bool(kw["coverage_qvalue"]) or call_q is not None)
+    given.update(coverage=bool(kw["coverage"]) or kw["coverage_control"] is not None or cutoff is not None or call_q is not None,
                  coverage_extend=extend if extend in ("auto", coverage.PAIR) else int(extend),
                  coverage_format=coverage.check_format(kw["coverage_format"], kw["coverage_compress"]),
                  coverage_compress=coverage.check_compress(kw["coverage_compress"]))
@@ -601,8 +625,13 @@ class _CoverageCount(_SideCount):
             elif self.signal:
                 c = c.signal(self.s.coverage_bin, self._scale(dict(zip(coverage.TOTALS, c.totals)), c.refs), self.s.coverage_normalize)
                 tail = (c.tail,)
-            if self.s.coverage_call is not None:    # (of the depth track: through its signal at bin 1 and scale 1.0)
-                self.called = _Later(c.call(*self._call).text_chunks)
+            if self.calls:                          # (of the depth track: through its signal at bin 1 and scale 1.0)
+                if self.s.coverage_qvalue:          # (a p-score track: the table, and with coverage_call_q the cutoff from it)
+                    qtable = c.qvalues()
+                    cutoff = self.s.coverage_call if self.s.coverage_call_q is None else qtable.cutoff(self.s.coverage_call_q)
+                    self.called = _Later(c.call(cutoff, *self._call[1:], qtable).text_chunks)
+                else:
+                    self.called = _Later(c.call(*self._call).text_chunks)
             return self._bigwig(coverage.bigwig_source(c), False) if bigwig else (extend, c.reads, c.text_chunks()) + tail
         if acc is None:             # (an armed count is not built again: its ``begin`` would zero the table)
             acc = coverage.device_count_of(reader, mapq, names, extend, self.s.fragments_max)
@@ -615,8 +644,13 @@ class _CoverageCount(_SideCount):
         elif signal:                # the signal runs are made on the handle, beside the depth runs
             acc.signal(reader, self.s.coverage_bin, self._scale(totals, acc.refs), self.s.coverage_normalize)
             tail = (coverage.signal_tail(acc.sig["bin"], acc.sig["normalize"], acc.sig["scale"]),)
-        if self.s.coverage_call is not None:        # on the track the file holds; the depth track through signal(1, 1.0), and the
-            acc.call(reader, *self._call)           # file is still written from the depth runs.  The lines are few: always spooled
+        if self.calls:                              # on the track the file holds; the depth track through signal(1, 1.0), and the
+            cutoff = self.s.coverage_call           # file is still written from the depth runs.  The lines are few: always spooled
+            if self.s.coverage_qvalue:              # (the table beside the p-score runs; with coverage_call_q the cutoff from it)
+                acc.qvalue(reader)
+                if self.s.coverage_call_q is not None:
+                    cutoff = acc.qvalue_cutoff(reader, self.s.coverage_call_q)
+            acc.call(reader, cutoff, *self._call[1:])
             fp = self._temporary()
             for chunk in acc.call_text_chunks(reader):
                 fp.write(chunk)
@@ -679,11 +713,12 @@ class _CoverageCount(_SideCount):
         return _Later(lambda: done)
 
     _call = property(lambda self: (self.s.coverage_call, self.s.coverage_call_gap, self.s.coverage_call_length))
+    calls = property(lambda self: self.s.coverage_call is not None or self.s.coverage_call_q is not None)
 
     def _write(self, base, basename: str, value):
         """The coverage file; with ``coverage_call`` [it, ``<basename>_coverage_peaks.narrowPeak``] (the lines ``_take`` left)."""
         track = self.row.write(self.s, base, basename, value)
-        if self.s.coverage_call is None:
+        if not self.calls:
             return track
         return [track, coverage.write_called(base, self.called)]
 
@@ -876,7 +911,8 @@ def run_files(paths, outdir, max_shift: int, read_len: Optional[int] = None, map
               coverage_format: str = "bedgraph", coverage_compress=False, coverage_bin: int = 1, coverage_normalize: str = "none",
               coverage_scale: float = 1.0, coverage_genome_size: Optional[int] = None, coverage_control=None,
               coverage_compare: str = "log2", coverage_pseudocount: float = 1.0, coverage_call=None, coverage_call_gap: int = 30,
-              coverage_call_length: int = 200, coverage_poisson: bool = False, coverage_lambda=(1000, 10000)) -> List[FileResult]:
+              coverage_call_length: int = 200, coverage_poisson: bool = False, coverage_lambda=(1000, 10000),
+              coverage_qvalue: bool = False, coverage_call_q=None) -> List[FileResult]:
     """``run`` over several alignment files in one call, as ``pymasc a.bam b.bam -n A B`` runs them; returns one FileResult per
     file, in input order.  Every keyword means what it means for ``run``; a file that is skipped gets no table.
 
@@ -1040,7 +1076,7 @@ def _warn_existing(s: _Settings, bases):
     suffixes = [x for x, on in (("_cc.tab", not (has_track and s.skip_ncc)), ("_mscc.tab", has_track), ("_nreads.tab", True),
                                 ("_stats.tab", s.stat_opts is not None)) if on]
     suffixes += [row.suffix(s) if callable(row.suffix) else row.suffix for row in _SIDES if row.enabled(s)]
-    if s.coverage_call is not None:
+    if s.coverage_call is not None or s.coverage_call_q is not None:
         suffixes.append(coverage.CALL_SUFFIX)
     for b in bases:
         for suffix in suffixes:

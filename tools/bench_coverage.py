@@ -33,7 +33,16 @@ bigWig file are the p-score track's.  Recorded under "poisson": its totals, the 
 bins, 8 per entry of F, 20 per boundary, 16 per run), and -- from the two pileups pulled to the host once, outside the timing -- the
 longest series of a run.  profiles/coverage_poisson.json is
 python tools/bench_coverage.py --reads 20000000 --format bigwig --bin 50 --control /tmp/pymasc_coverage_control.bam \
-    --control-reads 10000000 --poisson --no-host --no-open --reps 3 --out profiles/coverage_poisson.json"""
+    --control-reads 10000000 --poisson --no-host --no-open --reps 3 --out profiles/coverage_poisson.json
+
+--qvalue [--call-q X] (needs --poisson): every round also builds the q-score table of the p-score track behind the text
+pull (pmx_dbam_coverage_qvalue, timed as "qvalue"), takes pcut(X) on the device (timed as "qvalue_cutoff"; X defaults to 2, q <= 0.01)
+and calls the peaks at it (at --call's cutoff when that is given), so "qvalue" stands beside "poisson" and "call" of the same run, and
+the narrowPeak lines carry column 9.  Recorded under "qvalue": the four totals, the runs, pcut, the 8-bit digits in which the keys
+differ (the radix passes that ran) and the bytes the call holds (40 per run, 3072 per 8192 runs, 64, 32 per row, the table's 16 per
+row among them).  profiles/coverage_qvalue.json is
+python tools/bench_coverage.py --reads 20000000 --format bigwig --bin 50 --control /tmp/pymasc_coverage_control.bam \
+    --control-reads 10000000 --poisson --qvalue --no-host --no-open --reps 3 --out profiles/coverage_qvalue.json"""
 import argparse
 import contextlib
 import json
@@ -41,6 +50,8 @@ import os
 import statistics
 import sys
 import time
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -112,6 +123,8 @@ def main():
     ap.add_argument("--compare", choices=coverage.COMPARE, default="log2", help="the operation with --control")
     ap.add_argument("--poisson", action="store_true", help="with --control: every round also makes the p-score track, behind the compared one")
     ap.add_argument("--lambda", dest="windows", type=int, nargs=2, default=list(coverage.LAMBDA_WINDOWS), help="the two windows of --poisson")
+    ap.add_argument("--qvalue", action="store_true", help="with --poisson: every round also builds the q-score table and calls the peaks with it")
+    ap.add_argument("--call-q", type=float, default=2.0, help="with --qvalue and no --call: the peaks are called at pcut(X)")
     ap.add_argument("--call", type=float, default=None, help="a cutoff: every round also calls the peaks of the track and pulls their lines")
     ap.add_argument("--call-gap", type=int, default=coverage.CALL_GAP, help="the largest gap inside a peak")
     ap.add_argument("--call-length", type=int, default=coverage.CALL_LENGTH, help="the smallest peak")
@@ -120,6 +133,8 @@ def main():
     a = ap.parse_args()
     if a.poisson and (a.control is None or a.normalize != "none"):
         ap.error("--poisson needs --control and --normalize none")
+    if a.qvalue and not a.poisson:
+        ap.error("--qvalue needs --poisson")
     if not os.path.exists(a.path):
         synth_bam(a.path, a.reads)
     if a.control is not None and not os.path.exists(a.control):
@@ -143,6 +158,7 @@ def main():
         split = dict(begin=[], add=[], finish=[], signal=[], text=[], whole=[])
         versus = dict(control=[], compare=[], poisson=[]) if a.poisson else dict(control=[], compare=[])
         called = dict(call_signal=[], call=[], call_text=[])
+        qtimes = dict(qvalue=[], qvalue_cutoff=[])
         bw = dict(sections=[], zoom_begin=[], zoom_records=[], assembly=[], whole=[])
         for rep in range(a.reps + 1):               # (the first round warms up)
             t = [time.perf_counter()]
@@ -175,12 +191,24 @@ def main():
                         versus["poisson"].append(t3 - t2)
             size = sum(len(chunk) for chunk in acc.text_chunks(r, signal=signal))
             t.append(time.perf_counter())
-            if a.call is not None:                  # the peaks of the track the text pull read, and their lines
+            cutoff = a.call
+            if a.qvalue:                            # the table of the p-score track, and the cutoff from it
+                tq = [time.perf_counter()]
+                qtot = acc.qvalue(r)
+                tq.append(time.perf_counter())
+                pcut = acc.qvalue_cutoff(r, a.call_q)
+                tq.append(time.perf_counter())
+                cutoff = pcut if a.call is None else a.call
+                if rep:
+                    qtimes["qvalue"].append(tq[1] - tq[0])
+                    qtimes["qvalue_cutoff"].append(tq[2] - tq[1])
+                res["qvalue"] = dict(qtot, call_q=a.call_q, pcut=pcut, cutoff=cutoff, runs=acc.sig["totals"]["runs"])
+            if cutoff is not None:                  # the peaks of the track the text pull read, and their lines
                 tc = [time.perf_counter()]
                 if acc.sig is None:
                     acc.signal(r, 1, 1.0)
                 tc.append(time.perf_counter())
-                ctotals = acc.call(r, a.call, a.call_gap, a.call_length)
+                ctotals = acc.call(r, cutoff, a.call_gap, a.call_length)
                 tc.append(time.perf_counter())
                 csize = sum(len(chunk) for chunk in acc.call_text_chunks(r))
                 tc.append(time.perf_counter())
@@ -188,7 +216,7 @@ def main():
                     for k, name in enumerate(called):
                         called[name].append(tc[k + 1] - tc[k])
                 rows = acc.call_rows(r)
-                res["call"] = dict(ctotals, cutoff=a.call, max_gap=a.call_gap, min_length=a.call_length, text_bytes=csize,
+                res["call"] = dict(ctotals, cutoff=cutoff, max_gap=a.call_gap, min_length=a.call_length, text_bytes=csize,
                                    signal_runs=acc.sig["totals"]["runs"], longest_peak_runs=int(rows[5].max()) if rows[5].size else 0,
                                    longest_peak_bases=int((rows[2] - rows[1]).max()) if rows[5].size else 0)
             if a.format == "bigwig":
@@ -213,8 +241,15 @@ def main():
                     split["text"][-1] -= sum(v[-1] for v in versus.values())
         if rc is not None:
             split.update(versus)
-        if a.call is not None:
+        if a.call is not None or a.qvalue:
             split.update(called)
+        if a.qvalue:
+            split.update(qtimes)
+            n_runs, m = res["qvalue"]["runs"], res["qvalue"]["rows"]
+            keys = ~acc.qvalue_rows(r)[0].view("uint32")            # (the distinct values' keys differ where the runs' do)
+            differ = int(np.bitwise_or.reduce(keys) ^ np.bitwise_and.reduce(keys)) if m else 0
+            held = 40 * n_runs + 3072 * (-(-n_runs // 8192)) + 64 + 32 * m if n_runs else 0
+            res["qvalue"].update(radix_passes=[d for d in range(8) if (differ >> (8 * d)) & 255], held_bytes=held, table_bytes=16 * m)
         res.update(totals, text_bytes=size, text_chunk_runs=coverage.TEXT_CHUNK,
                    **{k + "_s": v for k, v in split.items()},              # (every round, in the order they ran)
                    **{k + "_median_s": statistics.median(v) for k, v in split.items()})
