@@ -741,9 +741,10 @@ def _by_reference(names, ref, *cols):
     return {names[int(ref[a])]: tuple(x[a:z] for x in cols) for a, z in zip(edges[:-1], edges[1:])}
 
 
-def _pull(reader, fn, head, rest_none=(), rest_of=lambda size: ()) -> bytes:
+def _pull(reader, fn, head, rest_none=(), rest_of=lambda size: (), bound: bool = False) -> bytes:
     """The bytes of an entry point that is called twice: ``fn(handle, *head, None, 0, *rest_none)`` gives their number,
-    ``fn(handle, *head, buffer, size, *rest_of(size))`` fills a buffer of it."""
+    ``fn(handle, *head, buffer, size, *rest_of(size))`` fills a buffer of it.  ``bound``: the number is an upper bound (a compressed
+    pull), and the second call says how many bytes it wrote."""
     size = fn(reader._h, *head, None, 0, *rest_none)
     if size < 0:
         reader._raise(size)
@@ -751,8 +752,8 @@ def _pull(reader, fn, head, rest_none=(), rest_of=lambda size: ()) -> bytes:
     got = fn(reader._h, *head, buf.ctypes.data, int(size), *rest_of(int(size)))
     if got < 0:
         reader._raise(got)
-    assert got == size
-    return buf[:int(size)].tobytes()
+    assert got <= size if bound else got == size
+    return buf[:int(got)].tobytes()
 
 
 class Coverage:
@@ -1093,44 +1094,38 @@ class DeviceCount(SideAccumulator):
         """(bytes, table) of the runs ``[first, first + n)`` of one reference as bedGraph sections of a bigWig file stamped with
         ``chrom_id`` (``pmx_dbam_coverage_sections``: the size, then the bytes); ``table[section] = (id, start, id, end, bytes)``.
         With ``signal`` (bytes, table, sums): ``sums[section] = (sum, sum of squares)``, float64."""
-        rows = -(-int(n) // int(items))
-        sums, table = np.zeros((max(rows, 1), 2), dtype=np.float64), np.zeros((max(rows, 1), 5), dtype=np.uint32)
-        blob = _pull(reader, self._fn(reader, "sections", signal), (int(first), int(n), int(chrom_id), int(items)),
-                     (None, 0) + ((None,) if signal else ()), lambda size: (table.ctypes.data, len(table)) + ((sums.ctypes.data,) if signal else ()))
-        return (blob, table[:rows]) + ((sums[:rows],) if signal else ())
+        return self._sections(reader, first, n, chrom_id, items, signal, False)
 
-    def section_chunks(self, reader, k: int, chrom_id: int, items: int, chunk: int = TEXT_CHUNK, signal: bool = False):
-        """``sections`` of the ``k``-th chosen reference, about ``chunk`` runs at a time (whole sections)."""
+    def _sections(self, reader, first, n, chrom_id, items, signal, z):
+        """``sections``, or with ``z`` ``sections_z``: what an entry point writes behind the table is the streams' lengths (``z``), then
+        the sums (``signal``), a row per section each."""
+        rows = -(-int(n) // int(items))
+        table = np.zeros((max(rows, 1), 5), dtype=np.uint32)
+        more = [np.zeros(max(rows, 1), dtype=np.uint32)] * bool(z) + [np.zeros((max(rows, 1), 2), dtype=np.float64)] * bool(signal)
+        blob = _pull(reader, self._fn(reader, "sections_z" if z else "sections", signal), (int(first), int(n), int(chrom_id), int(items)),
+                     (None, 0) + (None,) * len(more), lambda size: (table.ctypes.data, len(table)) + tuple(x.ctypes.data for x in more), z)
+        assert not z or len(blob) == int(more[0][:rows].sum(dtype=np.int64))
+        return (blob, table[:rows]) + tuple(x[:rows] for x in more)
+
+    def _section_chunks(self, pull, reader, k, chrom_id, items, chunk, signal):
         ranges = self.ranges(reader, signal)
         step = max(int(chunk) // int(items), 1) * int(items)
         for first in range(int(ranges[k]), int(ranges[k + 1]), step):
-            yield self.sections(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items, signal)
+            yield pull(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items, signal)
+
+    def section_chunks(self, reader, k: int, chrom_id: int, items: int, chunk: int = TEXT_CHUNK, signal: bool = False):
+        """``sections`` of the ``k``-th chosen reference, about ``chunk`` runs at a time (whole sections)."""
+        return self._section_chunks(self.sections, reader, k, chrom_id, items, chunk, signal)
 
     def sections_z(self, reader, first: int, n: int, chrom_id: int, items: int, signal: bool = False):
         """``sections`` with every section compressed on the device (``pmx_dbam_coverage_sections_z``): (the zlib
         streams end to end, the table of ``sections`` -- column 4 stays the raw size --, the streams' lengths); with ``signal``
         the sums of ``sections`` behind them."""
-        h, fn = reader._h, self._fn(reader, "sections_z", signal)
-        rows = -(-int(n) // int(items))
-        sums = np.zeros((max(rows, 1), 2), dtype=np.float64)
-        bound = fn(h, int(first), int(n), int(chrom_id), int(items), None, 0, None, 0, None, *((None,) if signal else ()))
-        if bound < 0:
-            reader._raise(bound)
-        buf = np.zeros(max(int(bound), 1), dtype=np.uint8)
-        table, zsizes = np.zeros((max(rows, 1), 5), dtype=np.uint32), np.zeros(max(rows, 1), dtype=np.uint32)
-        got = fn(h, int(first), int(n), int(chrom_id), int(items), buf.ctypes.data, int(bound), table.ctypes.data, len(table),
-                 zsizes.ctypes.data, *((sums.ctypes.data,) if signal else ()))
-        if got < 0:
-            reader._raise(got)
-        assert got <= bound and got == int(zsizes[:rows].sum(dtype=np.int64))
-        return (buf[:int(got)].tobytes(), table[:rows], zsizes[:rows]) + ((sums[:rows],) if signal else ())
+        return self._sections(reader, first, n, chrom_id, items, signal, True)
 
     def section_chunks_z(self, reader, k: int, chrom_id: int, items: int, chunk: int = DEFLATE_CHUNK, signal: bool = False):
         """``sections_z`` of the ``k``-th chosen reference, about ``chunk`` runs at a time (whole sections)."""
-        ranges = self.ranges(reader, signal)
-        step = max(int(chunk) // int(items), 1) * int(items)
-        for first in range(int(ranges[k]), int(ranges[k + 1]), step):
-            yield self.sections_z(reader, first, min(step, int(ranges[k + 1]) - first), chrom_id, items, signal)
+        return self._section_chunks(self.sections_z, reader, k, chrom_id, items, chunk, signal)
 
     def zoom_begin(self, reader, z0: int, levels: int, ids, signal: bool = False) -> Tuple[int, int]:
         """Fills the zoom bins on the device (``pmx_dbam_coverage_zoom_begin``); ``ids[k]``: the chromosome id of the ``k``-th
@@ -1157,19 +1152,13 @@ class DeviceCount(SideAccumulator):
     def zoom_records_z(self, reader, level: int, items: int, signal: bool = False):
         """``zoom_records`` with every section compressed on the device (``pmx_dbam_coverage_zoom_records_z``): (streams, table,
         the streams' lengths).  The last level frees the bins."""
-        h, fn = reader._h, self._fn(reader, "zoom_records_z", signal)
-        size = self._fn(reader, "zoom_records", signal)(h, int(level), int(items), None, 0, None, 0)       # (the raw bytes: the rows)
-        bound = fn(h, int(level), int(items), None, 0, None, 0, None)
-        if size < 0 or bound < 0:
-            reader._raise(min(size, bound))
-        rows = -(-(int(size) // 32) // int(items))
-        buf = np.zeros(max(int(bound), 1), dtype=np.uint8)
+        size = self._fn(reader, "zoom_records", signal)(reader._h, int(level), int(items), None, 0, None, 0)     # (the raw bytes: the rows)
+        rows = -(-(max(int(size), 0) // 32) // int(items))      # (what fails there fails in the pull, which raises it)
         table, zsizes = np.zeros((max(rows, 1), 5), dtype=np.uint32), np.zeros(max(rows, 1), dtype=np.uint32)
-        got = fn(h, int(level), int(items), buf.ctypes.data, int(bound), table.ctypes.data, len(table), zsizes.ctypes.data)
-        if got < 0:
-            reader._raise(got)
-        assert got <= bound and got == int(zsizes[:rows].sum(dtype=np.int64))
-        return buf[:int(got)].tobytes(), table[:rows], zsizes[:rows]
+        blob = _pull(reader, self._fn(reader, "zoom_records_z", signal), (int(level), int(items)), (None, 0, None),
+                     lambda size: (table.ctypes.data, len(table), zsizes.ctypes.data), True)
+        assert len(blob) == int(zsizes[:rows].sum(dtype=np.int64))
+        return blob, table[:rows], zsizes[:rows]
 
     def result(self, reader) -> Coverage:
         totals = self.finish(reader)

@@ -17,7 +17,7 @@
 // an area over a peak would be a float sum in some order and is left out on purpose.
 // The narrowPeak line of peak number n (1-based in file order: first + i + 1 of a pull):
 //   chrom TAB start TAB end TAB peak_<n> TAB score TAB . TAB value TAB -1 TAB -1 TAB (summit - start) LF
-// score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0)), the product exact in float64; value by sg_micro / sg_minus / sg_split of
+// score = trunc(min(max(f64(value) * 10.0, 0.0), 1000.0)), the product exact in float64; value by ValueText of
 // signal_device.inc.  No header line.  When the signal slot holds a p-score track (pmx_dbam_coverage_poisson, poisson_device.inc; DESIGN.md
 // 7.18.6) the first -1 (column 8) is the value's text as well; on every other track each byte is as above.  When the handle also holds a
 // q-score table (pmx_dbam_coverage_qvalue, qvalue_device.inc; DESIGN.md 7.18.7) the second -1 (column 9) is the text of the peak's
@@ -32,7 +32,7 @@
 //   k_cl_summit      one lane per peak.  A peak of fewer than CL_LONG runs is walked by its lane; the longer ones of a wave are taken
 //                    one after the other by all 64 lanes, which reduce (key, index) by shuffles: the larger key wins, on a tie the
 //                    smaller index.  key = sg_key of v with zero made canonical, so that the u32 order is the float order
-//   k_cl_textlen / k_cl_text                    k_sg_textlen / k_sg_text over the peak table
+//   k_ln_len<LnPeak> / k_ln_text<LnPeak>        coverage_device.inc's line writer over the peak table
 // Device memory: 12 bytes per 256 runs + 4 per passing run + 4 per candidate + 4 per peak inside call (counted in the handle's bytes
 // while it runs, freed before it returns), then 24 per peak until the next call, signal, compare, begin or close.
 
@@ -167,136 +167,73 @@ __device__ __forceinline__ u32 cl_score(u32 bits)
     return (u32)x;
 }
 
-// the text of a value (sg_split of its micro-count N) in front of `end`; returns where it begins
-__device__ __forceinline__ u8 *cl_value(u8 *q, u32 bits, u64 N, u64 whole, u32 frac, u32 nd)
-{
-    if (nd) {
-        for (u32 c = 0; c < nd; c++) {  // (nd digits, leading zeros among them)
-            *--q = (u8)('0' + frac % 10u);
-            frac /= 10u;
-        }
-        *--q = '.';
-    }
-    do {
-        *--q = (u8)('0' + (u32)(whole % 10u));
-        whole /= 10u;
-    } while (whole);
-    if (sg_minus(bits, N)) *--q = '-';
-    return q;
-}
-
 namespace {
 struct ClQ {            // the q-score table of the handle for column 9 (m = 0 and null pointers: there is none); miss: set on a value without a row
     const u32 *u, *q;
     u64 m;
     u32 *miss;
 };
+
+// A peak's line (k_ln_len, coverage_device.inc).  no0: the number of the first peak of the pull; ps: the signal is a p-score track
+// (poisson_device.inc): column 8 holds the value too; Q: the q-score table, when there is one: column 9 holds the peak's q-score
+struct LnPeak {
+    const int *pref;
+    const u32 *start, *end, *summit, *val;
+    u64 no0;
+    int ps;
+    ClQ Q;
+    __device__ __forceinline__ u32 ref(u64 i) const { return (u32)pref[i]; }
+    __device__ __forceinline__ u32 len(u64 i) const
+    {
+        const u32 vl = ValueText(val[i]).len();
+        return ln_width(start[i]) + ln_width(end[i]) + 5u + ln_width(no0 + i) + ln_width(cl_score(val[i])) + 1u + vl +
+               (ps ? vl + (Q.u ? ValueText(qv_lookup(Q.u, Q.q, Q.m, val[i], Q.miss)).len() : 2u) : 4u) + ln_width(summit[i] - start[i]) + 10u;
+    }
+    __device__ __forceinline__ void put(u64 i, u8 *q) const
+    {
+        const u32 s = start[i], e = end[i], bits = val[i];
+        const ValueText v(bits);
+        *--q = '\n';                    // from the line's end: LF, summit - start, TAB -1 TAB -1 TAB, the value, TAB . TAB, ...
+        q = cv_digits(q, summit[i] - s);
+        *--q = '\t';
+        if (Q.u) {                      // (a q-score table: column 9 is the text of the peak's q-score)
+            q = ValueText(qv_lookup(Q.u, Q.q, Q.m, bits, Q.miss)).put(q);
+        } else {
+            *--q = '1';
+            *--q = '-';
+        }
+        *--q = '\t';
+        if (ps) {                       // (a p-score track: column 8 is the value's text as well)
+            q = v.put(q);
+        } else {
+            *--q = '1';
+            *--q = '-';
+        }
+        *--q = '\t';
+        q = v.put(q);
+        *--q = '\t';
+        *--q = '.';
+        *--q = '\t';
+        q = cv_digits(q, cl_score(bits));
+        *--q = '\t';
+        u64 no = no0 + i;               // ... the score, TAB, peak_<n>, TAB, end, TAB, start, TAB
+        do {
+            *--q = (u8)('0' + (u32)(no % 10u));
+            no /= 10u;
+        } while (no);
+        *--q = '_';
+        *--q = 'k';
+        *--q = 'a';
+        *--q = 'e';
+        *--q = 'p';
+        *--q = '\t';
+        q = cv_digits(q, e);
+        *--q = '\t';
+        q = cv_digits(q, s);
+        *--q = '\t';
+    }
+};
 }  // namespace
-
-// the length of the text of the float32 with these bits
-__device__ __forceinline__ u32 cl_value_len(u32 bits)
-{
-    u64 whole;
-    u32 frac, nd;
-    const u64 N = sg_micro(bits);
-    sg_split(N, whole, frac, nd);
-    return sg_minus(bits, N) + sg_width(whole) + (nd ? nd + 1u : 0u);
-}
-
-// no0: the number of the first peak of the pull; ps: the signal is a p-score track (poisson_device.inc): column 8 holds the value too;
-// Q: the q-score table, when there is one: column 9 holds the peak's q-score
-__global__ void __launch_bounds__(256) k_cl_textlen(const int *__restrict__ pref, const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
-                                                    const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0, int ps, ClQ Q,
-                                                    const u32 *__restrict__ noff, u32 *__restrict__ len, u32 *__restrict__ wsum)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 i = (u64)blockIdx.x * 256u + t;
-    u32 l = 0;
-    if (i < n) {
-        const u32 r = (u32)pref[i];
-        u64 whole;
-        u32 frac, nd;
-        const u64 N = sg_micro(pval[i]);
-        sg_split(N, whole, frac, nd);
-        const u32 vl = sg_minus(pval[i], N) + sg_width(whole) + (nd ? nd + 1u : 0u);          // the value's text
-        l = noff[r + 1u] - noff[r] + cv_width(pstart[i]) + cv_width(pend[i]) + 5u + sg_width(no0 + i) + cv_width(cl_score(pval[i])) + 1u + vl +
-            (ps ? vl + (Q.u ? cl_value_len(qv_lookup(Q.u, Q.q, Q.m, pval[i], Q.miss)) : 2u) : 4u) + cv_width(psummit[i] - pstart[i]) + 10u;
-        len[i] = l;
-    }
-    l = (u32)cx_wave_sum((u64)l);
-    if ((t & 63u) == 0) s_w[t >> 6] = l;
-    __syncthreads();
-    if (t == 0) wsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ void __launch_bounds__(256) k_cl_text(const int *__restrict__ pref, const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
-                                                 const u32 *__restrict__ psummit, const u32 *__restrict__ pval, u64 n, u64 no0, int ps, ClQ Q,
-                                                 const u32 *__restrict__ noff, const u8 *__restrict__ names, const u32 *__restrict__ len,
-                                                 const u64 *__restrict__ wbase, u8 *__restrict__ out)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 i = (u64)blockIdx.x * 256u + t;
-    const u32 l = i < n ? len[i] : 0u;
-    const u32 incl = cv_wave_scan(l, lane);
-    if (lane == 63u) s_w[t >> 6] = incl;
-    __syncthreads();
-    if (i >= n) return;
-    u64 o = wbase[blockIdx.x] + incl - l;
-    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
-    const u32 r = (u32)pref[i];
-    u8 *p = out + o;
-    for (u32 c = noff[r]; c < noff[r + 1u]; c++) *p++ = names[c];
-    u64 whole;
-    u32 frac, nd;
-    const u64 N = sg_micro(pval[i]);
-    sg_split(N, whole, frac, nd);
-    u8 *q = out + o + l;                // the line from its end: LF, summit - start, TAB -1 TAB -1 TAB, the value, TAB . TAB, ...
-    *--q = '\n';
-    q = cv_digits(q, psummit[i] - pstart[i]);
-    *--q = '\t';
-    if (Q.u) {                          // (a q-score table: column 9 is the text of the peak's q-score)
-        const u32 qb = qv_lookup(Q.u, Q.q, Q.m, pval[i], Q.miss);
-        u64 qwhole;
-        u32 qfrac, qnd;
-        const u64 qN = sg_micro(qb);
-        sg_split(qN, qwhole, qfrac, qnd);
-        q = cl_value(q, qb, qN, qwhole, qfrac, qnd);
-    } else {
-        *--q = '1';
-        *--q = '-';
-    }
-    *--q = '\t';
-    if (ps) {                           // (a p-score track: column 8 is the value's text as well)
-        q = cl_value(q, pval[i], N, whole, frac, nd);
-    } else {
-        *--q = '1';
-        *--q = '-';
-    }
-    *--q = '\t';
-    q = cl_value(q, pval[i], N, whole, frac, nd);
-    *--q = '\t';
-    *--q = '.';
-    *--q = '\t';
-    q = cv_digits(q, cl_score(pval[i]));
-    *--q = '\t';
-    u64 no = no0 + i;                   // ... the score, TAB, peak_<n>, TAB, end, TAB, start, TAB
-    do {
-        *--q = (u8)('0' + (u32)(no % 10u));
-        no /= 10u;
-    } while (no);
-    *--q = '_';
-    *--q = 'k';
-    *--q = 'a';
-    *--q = 'e';
-    *--q = 'p';
-    *--q = '\t';
-    q = cv_digits(q, pend[i]);
-    *--q = '\t';
-    q = cv_digits(q, pstart[i]);
-    *--q = '\t';                        // (q == p: the lengths are k_cl_textlen's)
-}
 
 namespace {
 
@@ -467,7 +404,7 @@ int64_t coverage_call_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *
     if (buf && cap < 0) return fail(PMX_DBAM_ERR_INVALID, fn + ": a negative capacity");
     if (n == 0) return 0;
     hipStream_t st = b->stream;
-    const u64 m = (u64)n, no0 = (u64)first + 1u;
+    const u64 no0 = (u64)first + 1u;
     const int ps = (int)b->cv.spscore;
     const ClPeaks K(b->cv.peaks.as<u8>(), b->cv.npeaks);
     ClQ Q{nullptr, nullptr, 0, nullptr};
@@ -482,15 +419,7 @@ int64_t coverage_call_text_impl(pmx_dbam *b, int64_t first, int64_t n, uint8_t *
         Q = ClQ{T.u, T.q, b->cv.qrows, d_miss.as<u32>()};
     }
     const int64_t got = coverage_text_pull(
-        b, fn, m, buf, cap,
-        [&](dim3 grid, const u32 *noff, u32 *len, u32 *wsum) {
-            hipLaunchKernelGGL(k_cl_textlen, grid, dim3(256), 0, st, K.ref + first, K.start + first, K.end + first, K.summit + first, K.value + first, m,
-                               no0, ps, Q, noff, len, wsum);
-        },
-        [&](dim3 grid, const u32 *noff, const u8 *names, const u32 *len, const u64 *wbase, u8 *out) {
-            hipLaunchKernelGGL(k_cl_text, grid, dim3(256), 0, st, K.ref + first, K.start + first, K.end + first, K.summit + first, K.value + first, m, no0,
-                               ps, Q, noff, names, len, wbase, out);
-        });
+        b, fn, (u64)n, buf, cap, LnPeak{K.ref + first, K.start + first, K.end + first, K.summit + first, K.value + first, no0, ps, Q});
     if (got >= 0 && Q.u) {
         u32 miss = 0;
         HIPOK(hipMemcpy(&miss, d_miss.p, 4, hipMemcpyDeviceToHost));

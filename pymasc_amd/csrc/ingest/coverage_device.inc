@@ -28,9 +28,9 @@
 //   k_cv_keep / k_bam_scan / k_cv_close   entry k's run ends at entry k + 1's position; the last non-zero slot of a reference
 //                 brings the depth to 0.  The entries of depth 0 are dropped by this second compaction (256 entries per
 //                 workgroup, ballots); the totals are reduced by wave sums, one atomic per wave and total
-//   k_cv_textlen  one lane per run: name length + the three decimal widths + 4, and the workgroup's sum
+//   k_ln_len<LnDepth>   one lane per run: name length + the three decimal widths + 4, and the workgroup's sum
 //   k_bam_scan    the 64-bit exclusive prefix of the workgroups' sums
-//   k_cv_text     each lane writes its own line at the workgroup's prefix + a scan of the lengths within the workgroup
+//   k_ln_text<LnDepth>  each lane writes its own line at the workgroup's prefix + a scan of the lengths within the workgroup
 // Bound: fewer than 2^31 reads between begin and finish (add fails above it), so every depth and prefix is below 2^31.
 // Device memory: 4 bytes per chosen base from begin to finish (12.4 GB for hg38) + 24 per tile, 12 per non-zero slot inside finish,
 // then 16 per run until the next begin or close; 13 bytes per kept read inside a call of add; 4 per run + the text inside text.
@@ -253,30 +253,11 @@ __global__ void __launch_bounds__(256) k_cv_close(const int *__restrict__ eref, 
     }
 }
 
-__device__ __forceinline__ u32 cv_width(u32 v)      // the decimal digits of v
+template <class T> __device__ __forceinline__ u32 ln_width(T v)      // the decimal digits of v (a u32 divides in 32 bits)
 {
     u32 w = 1;
     for (; v >= 10u; v /= 10u) w++;
     return w;
-}
-
-__global__ void __launch_bounds__(256) k_cv_textlen(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
-                                                    const u32 *__restrict__ rdepth, u64 n, const u32 *__restrict__ noff,
-                                                    u32 *__restrict__ len, u32 *__restrict__ wsum)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 i = (u64)blockIdx.x * 256u + t;
-    u32 l = 0;
-    if (i < n) {
-        const u32 r = (u32)rref[i];
-        l = noff[r + 1u] - noff[r] + cv_width(rstart[i]) + cv_width(rend[i]) + cv_width(rdepth[i]) + 4u;
-        len[i] = l;
-    }
-    l = (u32)cx_wave_sum((u64)l);
-    if ((t & 63u) == 0) s_w[t >> 6] = l;
-    __syncthreads();
-    if (t == 0) wsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
 
 // the digits of v in front of `end`; returns where they begin
@@ -289,9 +270,33 @@ __device__ __forceinline__ u8 *cv_digits(u8 *end, u32 v)
     return end;
 }
 
-__global__ void __launch_bounds__(256) k_cv_text(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
-                                                 const u32 *__restrict__ rdepth, u64 n, const u32 *__restrict__ noff, const u8 *__restrict__ names,
-                                                 const u32 *__restrict__ len, const u64 *__restrict__ wbase, u8 *__restrict__ out)
+// The text of m lines, one lane per line, once for every kind of line (LnDepth below, LnSignal in signal_device.inc, LnPeak in
+// call_device.inc).  A line is its reference's name and the columns behind it; a kind is a small struct L that the two kernels take by
+// value, its column pointers already at the first line of the pull:
+//   ref(i)       the reference of line i
+//   len(i)       the bytes behind the name, from the TAB that follows it to the LF
+//   put(i, q)    writes those bytes backwards from q, the line's end
+template <class L> __global__ void __launch_bounds__(256) k_ln_len(L P, u64 n, const u32 *__restrict__ noff, u32 *__restrict__ len,
+                                                                   u32 *__restrict__ wsum)
+{
+    __shared__ u32 s_w[4];
+    const u32 t = threadIdx.x;
+    const u64 i = (u64)blockIdx.x * 256u + t;
+    u32 l = 0;
+    if (i < n) {
+        const u32 r = P.ref(i);
+        l = noff[r + 1u] - noff[r] + P.len(i);
+        len[i] = l;
+    }
+    l = (u32)cx_wave_sum((u64)l);
+    if ((t & 63u) == 0) s_w[t >> 6] = l;
+    __syncthreads();
+    if (t == 0) wsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+template <class L> __global__ void __launch_bounds__(256) k_ln_text(L P, u64 n, const u32 *__restrict__ noff, const u8 *__restrict__ names,
+                                                                    const u32 *__restrict__ len, const u64 *__restrict__ wbase,
+                                                                    u8 *__restrict__ out)
 {
     __shared__ u32 s_w[4];
     const u32 t = threadIdx.x, lane = t & 63u;
@@ -303,18 +308,31 @@ __global__ void __launch_bounds__(256) k_cv_text(const int *__restrict__ rref, c
     if (i >= n) return;
     u64 o = wbase[blockIdx.x] + incl - l;
     for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
-    const u32 r = (u32)rref[i];
+    const u32 r = P.ref(i);
     u8 *p = out + o;
     for (u32 c = noff[r]; c < noff[r + 1u]; c++) *p++ = names[c];
-    u8 *q = out + o + l;                // the line from its end: LF, depth, TAB, end, TAB, start, TAB
-    *--q = '\n';
-    q = cv_digits(q, rdepth[i]);
-    *--q = '\t';
-    q = cv_digits(q, rend[i]);
-    *--q = '\t';
-    q = cv_digits(q, rstart[i]);
-    *--q = '\t';                        // (q == p: the lengths are k_cv_textlen's)
+    P.put(i, out + o + l);              // (it ends at p: the lengths are k_ln_len's)
 }
+
+namespace {
+struct LnDepth {        // a depth run: name TAB start TAB end TAB depth LF
+    const int *rref;
+    const u32 *start, *end, *depth;
+    __device__ __forceinline__ u32 ref(u64 i) const { return (u32)rref[i]; }
+    __device__ __forceinline__ u32 len(u64 i) const { return ln_width(start[i]) + ln_width(end[i]) + ln_width(depth[i]) + 4u; }
+    __device__ __forceinline__ void put(u64 i, u8 *q) const
+    {
+        const u32 s = start[i], e = end[i], d = depth[i];
+        *--q = '\n';
+        q = cv_digits(q, d);
+        *--q = '\t';
+        q = cv_digits(q, e);
+        *--q = '\t';
+        q = cv_digits(q, s);
+        *--q = '\t';
+    }
+};
+}  // namespace
 
 namespace {
 
@@ -532,20 +550,27 @@ int coverage_finish_impl(pmx_dbam *b, uint64_t *totals)
     return run.rc = coverage_finish_run(b, totals);
 }
 
-// The runs an entry point works on, and the kernels that read their fourth column: the depth runs finish left (CV_DEPTH) or the
-// signal runs pmx_dbam_coverage_signal made of them (SG_KIND, signal_device.inc), whose fourth column is a float32.  The host code
-// below is the same for both.
+// The runs an entry point works on, and everything that reads their fourth column: the depth runs finish left (CV_DEPTH, defined
+// behind its kernels below) or the signal runs pmx_dbam_coverage_signal made of them (SG_KIND, signal_device.inc), whose fourth
+// column is a float32.  The host code below is the same for both.
 struct CvKind {
     bool sg;
     const char *stem;                       // what the entry points' names begin with
-    decltype(&k_cv_textlen) textlen;
-    decltype(&k_cv_text) text;
+    // coverage_lines<L>: the text of the runs [first, first + m) through the kind's line policy
+    int64_t (*text)(pmx_dbam *b, const std::string &fn, const CvRuns &V, int64_t first, u64 m, uint8_t *buf, int64_t cap);
+    void (*sections)(const u32 *, const u32 *, const u32 *, u64, u32, u32, u32 *, u32 *);       // k_tr_sections<V>
+    void (*sums)(const u32 *, const u32 *, const u32 *, u64, u32, double *);      // (signal only) per section: sum and sum of squares
+    // level 0; h_idof / d_idof: the id of every reference on the host and on the device, d_off: the first bin of every id, d_lens
+    int (*fill)(pmx_dbam *b, const u32 *h_idof, const u32 *d_idof, const u64 *d_off, const u32 *d_lens, u32 z0, u64 nb0, u8 *bins,
+                unsigned long long *d_tot);
+    void (*fold)(u8 *, u64, u8 *, u64, const u64 *, const u64 *, u32);             // k_cv_zoom_fold, k_sg_zoom_fold
+    void (*emit)(u8 *, u64, const u64 *, const u32 *, u32, u32, u32, const u64 *, const u64 *, u32 *, u32 *);      // k_tr_zoom_emit<V>
     std::string fn(const char *what) const { return std::string(stem) + what; }
     u8 *runs(Coverage &c) const { return sg ? c.sruns.as<u8>() : c.runs.as<u8>(); }
     u64 count(const Coverage &c) const { return sg ? c.snruns : c.nruns; }
     std::vector<u64> &ranges(Coverage &c) const { return sg ? c.sranges : c.ranges; }
 };
-const CvKind CV_DEPTH = {false, "pmx_dbam_coverage_", k_cv_textlen, k_cv_text};
+extern const CvKind CV_DEPTH;
 
 int coverage_range(pmx_dbam *b, const CvKind &K, const std::string &fn, int64_t first, int64_t n)
 {
@@ -574,10 +599,9 @@ int coverage_runs_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t n, i
     return 0;
 }
 
-// The text of m >= 1 lines, one lane per line (`fn`: the entry point, its range checked): lengths(grid, noff, len, wsum) launches the
-// kernel that measures them, write(grid, noff, names, len, wbase, out) the one that writes them.  buf NULL: the size.
-template <class Lengths, class Write>
-int64_t coverage_text_pull(pmx_dbam *b, const std::string &fn, u64 m, uint8_t *buf, int64_t cap, Lengths lengths, Write write)
+// The text of m >= 1 lines, one lane per line (`fn`: the entry point, its range checked; `lines`: their policy, k_ln_len).
+// buf NULL: the size.
+template <class L> int64_t coverage_text_pull(pmx_dbam *b, const std::string &fn, u64 m, uint8_t *buf, int64_t cap, L lines)
 {
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
@@ -591,7 +615,7 @@ int64_t coverage_text_pull(pmx_dbam *b, const std::string &fn, u64 m, uint8_t *b
     HIPOK(hipMalloc(&d_w.p, 4 * nwg));
     HIPOK(hipMalloc(&d_wb.p, 8 * nwg));
     HIPOK(hipMalloc(&d_tot.p, 16));
-    lengths(dim3((unsigned)nwg), noff, d_len.as<u32>(), d_w.as<u32>());
+    hipLaunchKernelGGL(k_ln_len<L>, dim3((unsigned)nwg), dim3(256), 0, st, lines, m, noff, d_len.as<u32>(), d_w.as<u32>());
     HIPOK(hipGetLastError());
     hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, d_w.as<u32>(), d_w.as<u32>(), nwg, d_wb.as<u64>(), d_tot.as<u64>());
     HIPOK(hipGetLastError());
@@ -605,11 +629,17 @@ int64_t coverage_text_pull(pmx_dbam *b, const std::string &fn, u64 m, uint8_t *b
         return fail(PMX_DBAM_ERR_OPEN, fn + ": out of device memory for " + std::to_string(bytes) + " bytes of text");
     }
     held.add(bytes);
-    write(dim3((unsigned)nwg), noff, names, d_len.as<u32>(), d_wb.as<u64>(), d_text.as<u8>());
+    hipLaunchKernelGGL(k_ln_text<L>, dim3((unsigned)nwg), dim3(256), 0, st, lines, m, noff, names, d_len.as<u32>(), d_wb.as<u64>(), d_text.as<u8>());
     HIPOK(hipGetLastError());
     HIPOK(hipMemcpyAsync(buf, d_text.p, bytes, hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     return (int64_t)bytes;
+}
+
+// CvKind::text: the line policy L (LnDepth, LnSignal) over the four columns of the runs from `first`
+template <class L> int64_t coverage_lines(pmx_dbam *b, const std::string &fn, const CvRuns &V, int64_t first, u64 m, uint8_t *buf, int64_t cap)
+{
+    return coverage_text_pull(b, fn, m, buf, cap, L{V.ref + first, V.start + first, V.end + first, V.depth + first});
 }
 
 int64_t coverage_text_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t n, uint8_t *buf, int64_t cap)
@@ -618,18 +648,7 @@ int64_t coverage_text_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t 
     if (int rc = coverage_range(b, K, fn, first, n)) return rc;
     if (buf && cap < 0) return fail(PMX_DBAM_ERR_INVALID, fn + ": a negative capacity");
     if (n == 0) return 0;
-    hipStream_t st = b->stream;
-    const u64 m = (u64)n;
-    const CvRuns V(K.runs(b->cv), K.count(b->cv));
-    return coverage_text_pull(
-        b, fn, m, buf, cap,
-        [&](dim3 grid, const u32 *noff, u32 *len, u32 *wsum) {
-            hipLaunchKernelGGL(K.textlen, grid, dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff, len, wsum);
-        },
-        [&](dim3 grid, const u32 *noff, const u8 *names, const u32 *len, const u64 *wbase, u8 *out) {
-            hipLaunchKernelGGL(K.text, grid, dim3(256), 0, st, V.ref + first, V.start + first, V.end + first, V.depth + first, m, noff, names, len, wbase,
-                               out);
-        });
+    return K.text(b, fn, CvRuns(K.runs(b->cv), K.count(b->cv)), first, (u64)n, buf, cap);
 }
 
 }  // namespace
@@ -669,13 +688,14 @@ int64_t pmx_dbam_coverage_text(pmx_dbam *b, int64_t first, int64_t n, uint8_t *b
 // from here are bytes it never parses and a table per pull that says where each section begins and ends.
 //
 //   k_cv_ranges      one lane per run: the first run of a reference writes its index (the host closes the references without one)
-//   k_cv_sections    one lane per run of a range of ONE reference: its 12-byte item (start0, end0, float32 depth) behind the 24-byte
-//                    header of its section; a section's first lane writes the header and the table row
+//   k_tr_sections<V> one lane per run of a range of ONE reference: its 12-byte item (start0, end0, float32 depth) behind the 24-byte
+//                    header of its section; a section's first lane writes the header and the table row.  V (TrDepth here, TrSignal in
+//                    signal_device.inc) says what the kept fourth column and a zoom slot hold: it is all the two kinds differ in
 //   k_cv_zoom_fill   one lane per run: the bins of level 0 its run overlaps take its bases, depth, bases * depth and
 //                    bases * depth^2 by return-less integer atomics (add, min, max, 64-bit add); the sum of squares and the smallest
 //                    depth of the whole pileup are reduced over the wave, one atomic each per wave
 //   k_cv_zoom_fold   one lane per bin of level k + 1: its up to four bins of level k, no atomics
-//   k_cv_zoom_keep / k_bam_scan / k_cv_zoom_emit   the bins with a covered base, compacted by ballots into 32-byte records in
+//   k_cv_zoom_keep / k_bam_scan / k_tr_zoom_emit<V>   the bins with a covered base, compacted by ballots into 32-byte records in
 //                    (id, start) order; integers become float32 by round-to-nearest-even; the table row of a section is written by
 //                    its first and its last record
 // Every accumulator is an integer, so the records do not depend on the order the atomics arrive in.  Bound: a u64 sum of squares is
@@ -694,6 +714,17 @@ struct ZmBins {         // the arrays of one level in its block
     }
 };
 
+struct TrDepth {        // the depth runs: a u32 depth, and a slot of integers that become float32 by round-to-nearest-even
+    static __device__ __forceinline__ u32 item(u32 depth) { return __float_as_uint(__uint2float_rn(depth)); }
+    static __device__ __forceinline__ void stats(const ZmBins &B, u64 b, u32 *p)      // min, max, sum, sum of squares
+    {
+        p[0] = __float_as_uint(__uint2float_rn(B.mn[b]));
+        p[1] = __float_as_uint(__uint2float_rn(B.mx[b]));
+        p[2] = __float_as_uint(__ull2float_rn((unsigned long long)B.sum[b]));
+        p[3] = __float_as_uint(__ull2float_rn((unsigned long long)B.sq[b]));
+    }
+};
+
 }  // namespace
 
 __global__ void __launch_bounds__(256) k_cv_ranges(const int *__restrict__ rref, u64 n, unsigned long long *__restrict__ first)
@@ -705,7 +736,8 @@ __global__ void __launch_bounds__(256) k_cv_ranges(const int *__restrict__ rref,
 }
 
 // out: u32 words; run i of the range lies behind the headers of sections 0 .. i / ips: word 6 * (i / ips + 1) + 3 * i
-__global__ void __launch_bounds__(256) k_cv_sections(const u32 *__restrict__ rstart, const u32 *__restrict__ rend, const u32 *__restrict__ rdepth,
+template <class V>
+__global__ void __launch_bounds__(256) k_tr_sections(const u32 *__restrict__ rstart, const u32 *__restrict__ rend, const u32 *__restrict__ rval,
                                                      u64 n, u32 ips, u32 id, u32 *__restrict__ out, u32 *__restrict__ table)
 {
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -715,7 +747,7 @@ __global__ void __launch_bounds__(256) k_cv_sections(const u32 *__restrict__ rst
     const u32 a = rstart[i];
     p[0] = a;
     p[1] = rend[i];
-    p[2] = __float_as_uint(__uint2float_rn(rdepth[i]));
+    p[2] = V::item(rval[i]);
     if (i == sec * ips) {
         const u64 last = i + ips - 1u < n - 1u ? i + ips - 1u : n - 1u;
         const u32 cnt = (u32)(last - i) + 1u, z = rend[last];
@@ -821,7 +853,8 @@ __global__ void __launch_bounds__(256) k_cv_zoom_keep(const u32 *__restrict__ cn
 }
 
 // out: 8 u32 words per record; total[0]: the records of the level (k_bam_scan's total)
-__global__ void __launch_bounds__(256) k_cv_zoom_emit(u8 *__restrict__ bins, u64 n, const u64 *__restrict__ off, const u32 *__restrict__ lens,
+template <class V>
+__global__ void __launch_bounds__(256) k_tr_zoom_emit(u8 *__restrict__ bins, u64 n, const u64 *__restrict__ off, const u32 *__restrict__ lens,
                                                       u32 nc, u32 z, u32 ips, const u64 *__restrict__ kbase, const u64 *__restrict__ total,
                                                       u32 *__restrict__ out, u32 *__restrict__ table)
 {
@@ -839,10 +872,7 @@ __global__ void __launch_bounds__(256) k_cv_zoom_emit(u8 *__restrict__ bins, u64
     p[1] = start;
     p[2] = end;
     p[3] = B.cnt[b];
-    p[4] = __float_as_uint(__uint2float_rn(B.mn[b]));
-    p[5] = __float_as_uint(__uint2float_rn(B.mx[b]));
-    p[6] = __float_as_uint(__ull2float_rn((unsigned long long)B.sum[b]));
-    p[7] = __float_as_uint(__ull2float_rn((unsigned long long)B.sq[b]));
+    V::stats(B, b, p + 4);
     const u64 sec = o / ips;
     const u32 k = (u32)(o - sec * ips);
     u32 *T = table + 5u * sec;
@@ -863,17 +893,6 @@ namespace {
 u64 df_sections_bound(u64 nsec, u64 full, u64 last);
 int64_t df_sections_out(pmx_dbam *b, CvHold &held, const std::string &fn, const u8 *d_raw, u64 nsec, u64 full, u64 last, uint8_t *buf,
                         int64_t cap, uint32_t *zsizes);
-
-// the kernels of the second half for a kind of runs (CvKind): the sections, the optional sums per section, the zoom levels
-struct CvParts {
-    decltype(&k_cv_sections) sections;
-    void (*sums)(const u32 *, const u32 *, const u32 *, u64, u32, double *);      // (signal only) per section: sum and sum of squares
-    // level 0; h_idof / d_idof: the id of every reference on the host and on the device, d_off: the first bin of every id, d_lens
-    int (*fill)(pmx_dbam *b, const u32 *h_idof, const u32 *d_idof, const u64 *d_off, const u32 *d_lens, u32 z0, u64 nb0, u8 *bins,
-                unsigned long long *d_tot);
-    decltype(&k_cv_zoom_fold) fold;
-    decltype(&k_cv_zoom_emit) emit;
-};
 
 void zoom_drop(Coverage &c)
 {
@@ -930,7 +949,7 @@ int64_t coverage_ranges_impl(pmx_dbam *b, const CvKind &K, int64_t *first, int64
 
 // z: every section as a zlib stream (pmx_dbam_coverage_sections_z), the streams' lengths in zsizes; sums (a kind that has them):
 // sums[section][2], the section's sum and sum of squares
-int64_t coverage_sections_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items,
+int64_t coverage_sections_impl(pmx_dbam *b, const CvKind &K, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items,
                                uint8_t *buf, int64_t cap, uint32_t *table, int64_t table_cap, bool z = false, uint32_t *zsizes = nullptr,
                                double *sums = nullptr)
 {
@@ -953,7 +972,7 @@ int64_t coverage_sections_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, i
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the buffer is too small: " + std::to_string(bytes) + " bytes are needed");
     if (!table || (u64)table_cap < nsec)
         return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": the table is too small: " + std::to_string(nsec) + " rows are needed");
-    if ((z && !zsizes) || (P.sums && !sums)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": null output");
+    if ((z && !zsizes) || (K.sums && !sums)) return fail(PMX_DBAM_ERR_INVALID, std::string(fn) + ": null output");
     HIPOK(hipSetDevice(b->device));
     hipStream_t st = b->stream;
     DevAlloc d_out, d_sums;
@@ -965,15 +984,15 @@ int64_t coverage_sections_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, i
     held.add(bytes + 20 * nsec);
     const CvRuns V(K.runs(c), K.count(c));
     u32 *d_table = (u32 *)(d_out.as<u8>() + bytes);
-    if (P.sums) {
+    if (K.sums) {
         HIPOK(hipMalloc(&d_sums.p, 16 * nsec));
         held.add(16 * nsec);
-        hipLaunchKernelGGL(P.sums, dim3((unsigned)((nsec + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
+        hipLaunchKernelGGL(K.sums, dim3((unsigned)((nsec + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
                            d_sums.as<double>());
         HIPOK(hipGetLastError());
         HIPOK(hipMemcpyAsync(sums, d_sums.p, 16 * nsec, hipMemcpyDeviceToHost, st));
     }
-    hipLaunchKernelGGL(P.sections, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
+    hipLaunchKernelGGL(K.sections, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, V.start + first, V.end + first, V.depth + first, m, items,
                        chrom_id, d_out.as<u32>(), d_table);
     HIPOK(hipGetLastError());
     if (!z) HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
@@ -993,10 +1012,11 @@ int cv_zoom_fill(pmx_dbam *b, const u32 *, const u32 *d_idof, const u64 *d_off, 
     HIPOK(hipGetLastError());
     return 0;
 }
-const CvParts CV_DEPTH_PARTS = {k_cv_sections, nullptr, cv_zoom_fill, k_cv_zoom_fold, k_cv_zoom_emit};
+const CvKind CV_DEPTH = {false, "pmx_dbam_coverage_", coverage_lines<LnDepth>, k_tr_sections<TrDepth>, nullptr, cv_zoom_fill,
+                         k_cv_zoom_fold, k_tr_zoom_emit<TrDepth>};
 
 // out: the depth's two totals (the signal has none: its summary comes from signal's totals and the sections' sums; 0, 0)
-int coverage_zoom_begin_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t *out)
+int coverage_zoom_begin_impl(pmx_dbam *b, const CvKind &K, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t *out)
 {
     const std::string fn = K.fn("zoom_begin");
     if (int rc = coverage_range(b, K, fn, 0, 0)) return rc;
@@ -1067,11 +1087,11 @@ int coverage_zoom_begin_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, uin
         HIPOK(hipMemsetAsync(c.zbins.p, 0, 28 * znb[0], st));
         HIPOK(hipMemsetAsync(B.mn, 0xff, 4 * znb[0], st));
     }
-    if (int rc = P.fill(b, idof.data(), d_idof, d_off, d_lens, z0, levels ? znb[0] : 0, levels && znb[0] ? c.zbins.as<u8>() : (u8 *)nullptr, d_tot.as<unsigned long long>()))
+    if (int rc = K.fill(b, idof.data(), d_idof, d_off, d_lens, z0, levels ? znb[0] : 0, levels && znb[0] ? c.zbins.as<u8>() : (u8 *)nullptr, d_tot.as<unsigned long long>()))
         return rc;
     for (u32 k = 0; k + 1 < levels; k++) {
         if (!znb[k + 1]) continue;
-        hipLaunchKernelGGL(P.fold, dim3((unsigned)((znb[k + 1] + 255) / 256)), dim3(256), 0, st, c.zbins.as<u8>() + zoff[k], znb[k],
+        hipLaunchKernelGGL(K.fold, dim3((unsigned)((znb[k + 1] + 255) / 256)), dim3(256), 0, st, c.zbins.as<u8>() + zoff[k], znb[k],
                            c.zbins.as<u8>() + zoff[k + 1], znb[k + 1], d_off + (u64)k * (nc + 1), d_off + (u64)(k + 1) * (nc + 1), (u32)nc);
         HIPOK(hipGetLastError());
     }
@@ -1084,7 +1104,7 @@ int coverage_zoom_begin_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, uin
     return 0;
 }
 
-int64_t coverage_zoom_records_impl(pmx_dbam *b, const CvKind &K, const CvParts &P, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap,
+int64_t coverage_zoom_records_impl(pmx_dbam *b, const CvKind &K, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap,
                                    uint32_t *table, int64_t table_cap, bool zs = false, uint32_t *zsizes = nullptr)
 {
     const std::string fn = K.fn(zs ? "zoom_records_z" : "zoom_records");
@@ -1133,7 +1153,7 @@ int64_t coverage_zoom_records_impl(pmx_dbam *b, const CvKind &K, const CvParts &
         u64 z = c.z0;
         for (u32 k = 0; k < level; k++) z *= 4;
         u32 *d_table = (u32 *)(d_out.as<u8>() + bytes);
-        hipLaunchKernelGGL(P.emit, dim3((unsigned)nwg), dim3(256), 0, st, bins, nb, d_off, d_lens, (u32)nc, (u32)z, items, d_kb.as<u64>(),
+        hipLaunchKernelGGL(K.emit, dim3((unsigned)nwg), dim3(256), 0, st, bins, nb, d_off, d_lens, (u32)nc, (u32)z, items, d_kb.as<u64>(),
                            d_tot.as<u64>(), d_out.as<u32>(), d_table);
         HIPOK(hipGetLastError());
         if (!zs) HIPOK(hipMemcpyAsync(buf, d_out.p, bytes, hipMemcpyDeviceToHost, st));
@@ -1157,18 +1177,18 @@ int64_t pmx_dbam_coverage_ranges(pmx_dbam *b, int64_t *first, int64_t cap)
 int64_t pmx_dbam_coverage_sections(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
                                    uint32_t *table, int64_t table_cap)
 {
-    return guarded("pmx_dbam_coverage_sections", [&] { return coverage_sections_impl(b, CV_DEPTH, CV_DEPTH_PARTS, first, n, chrom_id, items, buf, cap, table, table_cap); });
+    return guarded("pmx_dbam_coverage_sections", [&] { return coverage_sections_impl(b, CV_DEPTH, first, n, chrom_id, items, buf, cap, table, table_cap); });
 }
 
 int pmx_dbam_coverage_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t out[2])
 {
-    return guarded("pmx_dbam_coverage_zoom_begin", [&] { return coverage_zoom_begin_impl(b, CV_DEPTH, CV_DEPTH_PARTS, z0, levels, chrom_id, out); });
+    return guarded("pmx_dbam_coverage_zoom_begin", [&] { return coverage_zoom_begin_impl(b, CV_DEPTH, z0, levels, chrom_id, out); });
 }
 
 int64_t pmx_dbam_coverage_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
                                        int64_t table_cap)
 {
-    return guarded("pmx_dbam_coverage_zoom_records", [&] { return coverage_zoom_records_impl(b, CV_DEPTH, CV_DEPTH_PARTS, level, items, buf, cap, table, table_cap); });
+    return guarded("pmx_dbam_coverage_zoom_records", [&] { return coverage_zoom_records_impl(b, CV_DEPTH, level, items, buf, cap, table, table_cap); });
 }
 
 }  // extern "C"

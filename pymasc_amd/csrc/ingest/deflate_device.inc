@@ -23,7 +23,7 @@
 //               is written from the chunk itself, in blocks of at most 65535 bytes.
 //   k_bam_scan  the exclusive prefix of the streams' sizes
 //   k_df_pack   one workgroup per chunk: its stream from its slot to its place among the others
-// Device memory inside a call: the raw bytes (pmx_ddeflate; the coverage calls compress what k_cv_sections / k_cv_zoom_emit wrote),
+// Device memory inside a call: the raw bytes (pmx_ddeflate; the coverage calls compress what k_tr_sections / k_tr_zoom_emit wrote),
 // 4 bytes per raw byte of tokens, a slot of pmx_ddeflate_bound rounded up to 16 per chunk, 36 per chunk of tables, then the packed
 // streams.  LDS per workgroup: 37 / 62 / 119 KB for chunks up to 16 / 32 / 64 KB, so 4 / 2 / 1 workgroups per CU.
 
@@ -466,14 +466,14 @@ int64_t pmx_dbam_coverage_sections_z(pmx_dbam *b, int64_t first, int64_t n, uint
                                      uint32_t *table, int64_t table_cap, uint32_t *zsizes)
 {
     return guarded("pmx_dbam_coverage_sections_z",
-                   [&] { return coverage_sections_impl(b, CV_DEPTH, CV_DEPTH_PARTS, first, n, chrom_id, items, buf, cap, table, table_cap, true, zsizes); });
+                   [&] { return coverage_sections_impl(b, CV_DEPTH, first, n, chrom_id, items, buf, cap, table, table_cap, true, zsizes); });
 }
 
 int64_t pmx_dbam_coverage_zoom_records_z(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
                                          int64_t table_cap, uint32_t *zsizes)
 {
     return guarded("pmx_dbam_coverage_zoom_records_z",
-                   [&] { return coverage_zoom_records_impl(b, CV_DEPTH, CV_DEPTH_PARTS, level, items, buf, cap, table, table_cap, true, zsizes); });
+                   [&] { return coverage_zoom_records_impl(b, CV_DEPTH, level, items, buf, cap, table, table_cap, true, zsizes); });
 }
 
 }  // extern "C"

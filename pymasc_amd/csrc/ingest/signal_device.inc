@@ -1,6 +1,6 @@
 // The pileup as a signal track: the mean depth per bin times a scale factor, float32 (pmx_dbam_coverage_signal*,
 // include/pymasc_amd_ingest.h; DESIGN.md 7.18.3).  Included in bam_device.hip behind coverage_device.inc and deflate_device.inc: the
-// host code of every consumer is coverage_device.inc's, run with SG_KIND / SG_PARTS in place of CV_DEPTH / CV_DEPTH_PARTS.
+// host code of every consumer is coverage_device.inc's, run with SG_KIND in place of CV_DEPTH.
 //
 // The definitions.  Reference r of length len has the bins j = 0 .. ceil(len / B) - 1; bin j covers [j * B, min((j + 1) * B, len)) and
 // has the width w_j (only the last bin can be short); S_j is the integer sum of the depth over its bases (below 2^47: exact as u64 and
@@ -28,11 +28,11 @@
 //   k_bt_count<K, true> / k_bam_scan / k_bt_close<K>      entry k ends where entry k + 1 of its reference begins, the last at the
 //                    reference's end; the entries with S = 0 are dropped by this second compaction; the totals are reduced over the
 //                    wave, one atomic each per wave, min and max of the float32 through the order-preserving map of their bits to u32
-//   k_sg_textlen / k_sg_text                k_cv_textlen / k_cv_text with the value formatted as above
-//   k_sg_sections / k_sg_secsums            one lane per run: its item; one lane per section: its two sums over its runs in order
+//   k_ln_len<LnSignal> / k_ln_text<LnSignal>   coverage_device.inc's line writer with the value formatted as above (ValueText)
+//   k_tr_sections<TrSignal> / k_sg_secsums  one lane per run: its item; one lane per section: its two sums over its runs in order
 //   k_sg_zoom_fill   one lane per bin of level 0: a binary search for the first run of its reference that ends behind the bin's
 //                    beginning, then forward in order; no atomics
-//   k_sg_zoom_fold / k_sg_zoom_emit         over (u32 valid, f32 min, f32 max, f64 sum, f64 sq), in ZmBins' 28 bytes
+//   k_sg_zoom_fold / k_tr_zoom_emit<TrSignal>   over (u32 valid, f32 min, f32 max, f64 sum, f64 sq), in ZmBins' 28 bytes
 // Device memory: 8 bytes per bin + 16 per entry inside signal (counted in the handle's bytes while it runs), then 16 per signal run
 // until the next signal, begin or close.
 
@@ -219,13 +219,6 @@ __device__ __forceinline__ u64 sg_micro(u32 bits)
 // whether the text of the value begins with '-': a negative whose micro-count N is not 0 ("0", never "-0")
 __device__ __forceinline__ u32 sg_minus(u32 bits, u64 N) { return (bits >> 31) & (u32)(N != 0); }
 
-__device__ __forceinline__ u32 sg_width(u64 v)      // the decimal digits of v
-{
-    u32 w = 1;
-    for (; v >= 10u; v /= 10u) w++;
-    return w;
-}
-
 // N = round(v * 10^6) as whole part and fraction: the fraction's digits without trailing zeros (nd of them, 0 .. 6)
 __device__ __forceinline__ void sg_split(u64 N, u64 &whole, u32 &frac, u32 &nd)
 {
@@ -238,101 +231,62 @@ __device__ __forceinline__ void sg_split(u64 N, u64 &whole, u32 &frac, u32 &nd)
     }
 }
 
-__global__ void __launch_bounds__(256) k_sg_textlen(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
-                                                    const u32 *__restrict__ rval, u64 n, const u32 *__restrict__ noff,
-                                                    u32 *__restrict__ len, u32 *__restrict__ wsum)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x;
-    const u64 i = (u64)blockIdx.x * 256u + t;
-    u32 l = 0;
-    if (i < n) {
-        const u32 r = (u32)rref[i];
-        u64 whole;
-        u32 frac, nd;
-        const u64 N = sg_micro(rval[i]);
-        sg_split(N, whole, frac, nd);
-        l = noff[r + 1u] - noff[r] + cv_width(rstart[i]) + cv_width(rend[i]) + sg_minus(rval[i], N) + sg_width(whole) + (nd ? nd + 1u : 0u) + 4u;
-        len[i] = l;
-    }
-    l = (u32)cx_wave_sum((u64)l);
-    if ((t & 63u) == 0) s_w[t >> 6] = l;
-    __syncthreads();
-    if (t == 0) wsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ void __launch_bounds__(256) k_sg_text(const int *__restrict__ rref, const u32 *__restrict__ rstart, const u32 *__restrict__ rend,
-                                                 const u32 *__restrict__ rval, u64 n, const u32 *__restrict__ noff, const u8 *__restrict__ names,
-                                                 const u32 *__restrict__ len, const u64 *__restrict__ wbase, u8 *__restrict__ out)
-{
-    __shared__ u32 s_w[4];
-    const u32 t = threadIdx.x, lane = t & 63u;
-    const u64 i = (u64)blockIdx.x * 256u + t;
-    const u32 l = i < n ? len[i] : 0u;
-    const u32 incl = cv_wave_scan(l, lane);
-    if (lane == 63u) s_w[t >> 6] = incl;
-    __syncthreads();
-    if (i >= n) return;
-    u64 o = wbase[blockIdx.x] + incl - l;
-    for (u32 x = 0; x < (t >> 6); x++) o += s_w[x];
-    const u32 r = (u32)rref[i];
-    u8 *p = out + o;
-    for (u32 c = noff[r]; c < noff[r + 1u]; c++) *p++ = names[c];
-    u64 whole;
-    u32 frac, nd;
-    const u64 N = sg_micro(rval[i]);
-    sg_split(N, whole, frac, nd);
-    u8 *q = out + o + l;                // the line from its end: LF, fraction, '.', whole part, '-', TAB, end, TAB, start, TAB
-    *--q = '\n';
-    if (nd) {
-        for (u32 c = 0; c < nd; c++) {  // (nd digits, leading zeros among them)
-            *--q = (u8)('0' + frac % 10u);
-            frac /= 10u;
+namespace {
+struct ValueText {      // the text of the float32 with these bits: '-', whole part, '.', fraction
+    u32 bits, frac, nd;
+    u64 N, whole;
+    __device__ __forceinline__ explicit ValueText(u32 b) : bits(b), N(sg_micro(b)) { sg_split(N, whole, frac, nd); }
+    __device__ __forceinline__ u32 len() const { return sg_minus(bits, N) + ln_width(whole) + (nd ? nd + 1u : 0u); }
+    __device__ __forceinline__ u8 *put(u8 *q) const     // in front of q; returns where it begins
+    {
+        u64 wh = whole;
+        u32 fr = frac;
+        if (nd) {
+            for (u32 c = 0; c < nd; c++) {  // (nd digits, leading zeros among them)
+                *--q = (u8)('0' + fr % 10u);
+                fr /= 10u;
+            }
+            *--q = '.';
         }
-        *--q = '.';
+        do {
+            *--q = (u8)('0' + (u32)(wh % 10u));
+            wh /= 10u;
+        } while (wh);
+        if (sg_minus(bits, N)) *--q = '-';
+        return q;
     }
-    do {
-        *--q = (u8)('0' + (u32)(whole % 10u));
-        whole /= 10u;
-    } while (whole);
-    if (sg_minus(rval[i], N)) *--q = '-';
-    *--q = '\t';
-    q = cv_digits(q, rend[i]);
-    *--q = '\t';
-    q = cv_digits(q, rstart[i]);
-    *--q = '\t';                        // (q == p: the lengths are k_sg_textlen's)
-}
+};
 
-// k_cv_sections with the value as it is kept
-__global__ void __launch_bounds__(256) k_sg_sections(const u32 *__restrict__ rstart, const u32 *__restrict__ rend, const u32 *__restrict__ rval,
-                                                     u64 n, u32 ips, u32 id, u32 *__restrict__ out, u32 *__restrict__ table)
-{
-    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const u64 sec = i / ips;
-    u32 *p = out + 6u * (sec + 1u) + 3u * i;
-    const u32 a = rstart[i];
-    p[0] = a;
-    p[1] = rend[i];
-    p[2] = rval[i];
-    if (i == sec * ips) {
-        const u64 last = i + ips - 1u < n - 1u ? i + ips - 1u : n - 1u;
-        const u32 cnt = (u32)(last - i) + 1u, z = rend[last];
-        u32 *h = p - 6;
-        h[0] = id;
-        h[1] = a;
-        h[2] = z;
-        h[3] = 0;                           // itemStep
-        h[4] = 0;                           // itemSpan
-        h[5] = 1u | (cnt << 16);            // type 1 (bedGraph), a reserved byte, itemCount
-        u32 *T = table + 5u * sec;
-        T[0] = id;
-        T[1] = a;
-        T[2] = id;
-        T[3] = z;
-        T[4] = 24u + 12u * cnt;
+struct LnSignal {       // a signal run (k_ln_len): name TAB start TAB end TAB value LF
+    const int *rref;
+    const u32 *start, *end, *val;
+    __device__ __forceinline__ u32 ref(u64 i) const { return (u32)rref[i]; }
+    __device__ __forceinline__ u32 len(u64 i) const { return ln_width(start[i]) + ln_width(end[i]) + ValueText(val[i]).len() + 4u; }
+    __device__ __forceinline__ void put(u64 i, u8 *q) const
+    {
+        const u32 s = start[i], e = end[i];
+        const ValueText v(val[i]);
+        *--q = '\n';
+        q = v.put(q);
+        *--q = '\t';
+        q = cv_digits(q, e);
+        *--q = '\t';
+        q = cv_digits(q, s);
+        *--q = '\t';
     }
-}
+};
+
+struct TrSignal {       // the signal runs (k_tr_sections): the bits of a float32, and a slot of float32 min / max and float64 sums
+    static __device__ __forceinline__ u32 item(u32 bits) { return bits; }
+    static __device__ __forceinline__ void stats(const ZmBins &B, u64 b, u32 *p)
+    {
+        p[0] = B.mn[b];
+        p[1] = B.mx[b];
+        p[2] = __float_as_uint(__double2float_rn(__longlong_as_double((long long)B.sum[b])));
+        p[3] = __float_as_uint(__double2float_rn(__longlong_as_double((long long)B.sq[b])));
+    }
+};
+}  // namespace
 
 // sums[2 * section], [2 * section + 1]: the section's runs in order, acc += f64(ov) * f64(v) and acc += f64(ov) * (f64(v) * f64(v))
 __global__ void __launch_bounds__(256) k_sg_secsums(const u32 *rstart, const u32 *rend, const u32 *rval, u64 n, u32 ips, double *sums)
@@ -424,46 +378,9 @@ __global__ void __launch_bounds__(256) k_sg_zoom_fold(u8 *__restrict__ src, u64 
     D.mx[b] = __float_as_uint(mx);
 }
 
-// k_cv_zoom_emit over the signal's bins: min and max as they are kept, the two float64 sums rounded to float32
-__global__ void __launch_bounds__(256) k_sg_zoom_emit(u8 *__restrict__ bins, u64 n, const u64 *__restrict__ off, const u32 *__restrict__ lens,
-                                                      u32 nc, u32 z, u32 ips, const u64 *__restrict__ kbase, const u64 *__restrict__ total,
-                                                      u32 *__restrict__ out, u32 *__restrict__ table)
-{
-    __shared__ u32 s_w[4];
-    const u64 b = (u64)blockIdx.x * 256u + threadIdx.x;
-    const ZmBins B(bins, n);
-    const bool keep = b < n && B.cnt[b] != 0;
-    const u64 o = cv_slot(keep, kbase, s_w);
-    if (!keep) return;
-    const u32 id = cv_zoom_id(off, nc, b);
-    const u64 a = (b - off[id]) * z;
-    const u32 start = (u32)a, end = a + z < (u64)lens[id] ? (u32)(a + z) : lens[id];
-    u32 *p = out + 8u * o;
-    p[0] = id;
-    p[1] = start;
-    p[2] = end;
-    p[3] = B.cnt[b];
-    p[4] = B.mn[b];
-    p[5] = B.mx[b];
-    p[6] = __float_as_uint(__double2float_rn(__longlong_as_double((long long)B.sum[b])));
-    p[7] = __float_as_uint(__double2float_rn(__longlong_as_double((long long)B.sq[b])));
-    const u64 sec = o / ips;
-    const u32 k = (u32)(o - sec * ips);
-    u32 *T = table + 5u * sec;
-    if (k == 0) {
-        T[0] = id;
-        T[1] = start;
-    }
-    if (k == ips - 1u || o + 1u == total[0]) {
-        T[2] = id;
-        T[3] = end;
-        T[4] = 32u * (k + 1u);
-    }
-}
-
 namespace {
 
-const CvKind SG_KIND = {true, "pmx_dbam_coverage_signal_", k_sg_textlen, k_sg_text};
+extern const CvKind SG_KIND;
 
 // level 0 of the signal runs: the runs of every id from the signal's ranges, then one lane per bin
 int sg_zoom_fill(pmx_dbam *b, const u32 *h_idof, const u32 *, const u64 *d_off, const u32 *d_lens, u32 z0, u64 nb0, u8 *bins, unsigned long long *)
@@ -490,7 +407,8 @@ int sg_zoom_fill(pmx_dbam *b, const u32 *h_idof, const u32 *, const u64 *d_off, 
     HIPOK(hipStreamSynchronize(b->stream));        // (rng and d_rng are locals)
     return 0;
 }
-const CvParts SG_PARTS = {k_sg_sections, k_sg_secsums, sg_zoom_fill, k_sg_zoom_fold, k_sg_zoom_emit};
+const CvKind SG_KIND = {true, "pmx_dbam_coverage_signal_", coverage_lines<LnSignal>, k_tr_sections<TrSignal>, k_sg_secsums, sg_zoom_fill,
+                        k_sg_zoom_fold, k_tr_zoom_emit<TrSignal>};
 
 // the peaks called from the signal runs (call_device.inc) go with them
 void call_drop(Coverage &c)
@@ -786,27 +704,27 @@ int64_t pmx_dbam_coverage_signal_sections(pmx_dbam *b, int64_t first, int64_t n,
                                           uint32_t *table, int64_t table_cap, double *sums)
 {
     return guarded("pmx_dbam_coverage_signal_sections", [&] {
-        return coverage_sections_impl(b, SG_KIND, SG_PARTS, first, n, chrom_id, items, buf, cap, table, table_cap, false, nullptr, sums);
+        return coverage_sections_impl(b, SG_KIND, first, n, chrom_id, items, buf, cap, table, table_cap, false, nullptr, sums);
     });
 }
 
 int pmx_dbam_coverage_signal_zoom_begin(pmx_dbam *b, uint32_t z0, uint32_t levels, const uint32_t *chrom_id, uint64_t out[2])
 {
-    return guarded("pmx_dbam_coverage_signal_zoom_begin", [&] { return coverage_zoom_begin_impl(b, SG_KIND, SG_PARTS, z0, levels, chrom_id, out); });
+    return guarded("pmx_dbam_coverage_signal_zoom_begin", [&] { return coverage_zoom_begin_impl(b, SG_KIND, z0, levels, chrom_id, out); });
 }
 
 int64_t pmx_dbam_coverage_signal_zoom_records(pmx_dbam *b, uint32_t level, uint32_t items, uint8_t *buf, int64_t cap, uint32_t *table,
                                               int64_t table_cap)
 {
     return guarded("pmx_dbam_coverage_signal_zoom_records",
-                   [&] { return coverage_zoom_records_impl(b, SG_KIND, SG_PARTS, level, items, buf, cap, table, table_cap); });
+                   [&] { return coverage_zoom_records_impl(b, SG_KIND, level, items, buf, cap, table, table_cap); });
 }
 
 int64_t pmx_dbam_coverage_signal_sections_z(pmx_dbam *b, int64_t first, int64_t n, uint32_t chrom_id, uint32_t items, uint8_t *buf, int64_t cap,
                                             uint32_t *table, int64_t table_cap, uint32_t *zsizes, double *sums)
 {
     return guarded("pmx_dbam_coverage_signal_sections_z", [&] {
-        return coverage_sections_impl(b, SG_KIND, SG_PARTS, first, n, chrom_id, items, buf, cap, table, table_cap, true, zsizes, sums);
+        return coverage_sections_impl(b, SG_KIND, first, n, chrom_id, items, buf, cap, table, table_cap, true, zsizes, sums);
     });
 }
 
@@ -814,7 +732,7 @@ int64_t pmx_dbam_coverage_signal_zoom_records_z(pmx_dbam *b, uint32_t level, uin
                                                 int64_t table_cap, uint32_t *zsizes)
 {
     return guarded("pmx_dbam_coverage_signal_zoom_records_z",
-                   [&] { return coverage_zoom_records_impl(b, SG_KIND, SG_PARTS, level, items, buf, cap, table, table_cap, true, zsizes); });
+                   [&] { return coverage_zoom_records_impl(b, SG_KIND, level, items, buf, cap, table, table_cap, true, zsizes); });
 }
 
 }  // extern "C"

@@ -184,3 +184,34 @@ def check_situations(reads, want, extend):
     assert "f3" not in want["runs"]                                             # a reference without reads has no run
     assert MASKED_READ in reads and MASKED_READ not in FC.masked(reads, REFS, MASK)        # a read the mask leaves out
     assert want["fragment_bases"] == want["extents"]                            # the identity of the totals
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the shapes of the output kernels (the line writer, the sections, the zoom records): isolated short reads a few
+# bases apart, a few hundred runs
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+OUT_REFS = [("c", 400), ("chromosome12", 2400)]                 # names of 1 and of 12 characters
+OUT_SHORT, OUT_LONG = 43, 490                                   # their runs: the reference changes at run 43
+OUT_READS = sorted([(0, 1 + 8 * k, 3, 0) for k in range(OUT_SHORT) for _d in range(1 + k % 3)] +
+                   [(1, 1 + 4 * k, 2, 0) for k in range(OUT_LONG) for _d in range(1 + k % 4)])
+OUT_FIRST = 3                                                   # a pull begins at the fourth row ...
+OUT_COUNTS = (1, 63, 64, 65, 255, 256, 257, 513)                # ... and ends on lane 63, on a workgroup's edge, in the third workgroup
+OUT_SECTION_COUNTS, OUT_ITEMS = (1, 255, 256, 257), (1, 3, 256, 257, 1024)
+OUT_ZOOM, OUT_KEPT = 16, (1, 256, 257)                          # the bins of a zoom level that hold a base: every other bin of 16
+
+
+def check_line_pulls(pull, whole: bytes, names=OUT_REFS) -> None:
+    """``pull(first, n)`` against the same lines of ``whole`` for every count of ``OUT_COUNTS``; the reference changes on line 43,
+    which is lane 40 of a pull's first wave."""
+    lines = whole.splitlines(True)
+    assert len(lines) >= OUT_FIRST + max(OUT_COUNTS)
+    assert lines[OUT_SHORT - 1].startswith(names[0][0].encode() + b"\t") and lines[OUT_SHORT].startswith(names[1][0].encode() + b"\t")
+    for n in OUT_COUNTS:
+        assert pull(OUT_FIRST, n) == b"".join(lines[OUT_FIRST:OUT_FIRST + n]), n
+
+
+def zoom_reads(kept: int):
+    """Reads on ``OUT_REFS[1]`` lengthened to hold them: ``kept`` bins of ``OUT_ZOOM`` bases hold one, an empty bin between two."""
+    refs = [OUT_REFS[0], (OUT_REFS[1][0], 2 * OUT_ZOOM * kept + 5)]
+    return refs, [(1, 4 + 2 * OUT_ZOOM * k, 2, 0) for k in range(kept) for _d in range(1 + k % 3)]

@@ -19,6 +19,7 @@ from pymasc_amd.native import PmxIOError
 from pymasc_amd.sam import DeviceSamReader
 from pymasc_amd.stream_device import DeviceStreamReader
 from tests import call_cases as KC
+from tests import coverage_cases as CC
 from tests import fixtures as fx
 from tests import fragments_cases as FR
 from tests import io_writers as W
@@ -186,6 +187,38 @@ def test_the_text_in_chunks(tmp_path):
             with pytest.raises(PmxIOError, match="pmx_dbam_coverage_call_(text|rows): " + what):
                 r._raise(rc_)
         assert L.pmx_dbam_coverage_call_text(h, 0, 699, buf.ctypes.data, size) == size and buf.tobytes() == whole
+
+
+@pytest.mark.parametrize("kind", ["depth", "signal", "peaks", "p-score peaks", "p- and q-score peaks"])
+def test_pulls_of_lines_from_the_fourth_on(tmp_path, kind):
+    """Every kind of line through the one line writer: pulls that end on lane 63, on a workgroup's edge and in the third workgroup,
+    over two references whose names have 1 and 12 characters, against the same lines of the host path's text."""
+    c = _host(CC.OUT_READS, CC.OUT_REFS)
+    with DeviceBamReader(_bam_of(tmp_path, "t", CC.OUT_REFS, CC.OUT_READS)) as r, \
+            DeviceBamReader(_bam_of(tmp_path, "c", CC.OUT_REFS, [(1, 2301, 40, 0)])) as rc:
+        acc = coverage.device_count_of(r, MAPQ, None, 0)
+        if kind == "depth":
+            assert acc.finish(r)["runs"] == CC.OUT_SHORT + CC.OUT_LONG
+            return CC.check_line_pulls(lambda first, n: acc.text(r, first, n), b"".join(c.text_chunks()))
+        if kind == "signal":
+            acc.signal(r, 1, 0.37)
+            return CC.check_line_pulls(lambda first, n: acc.text(r, first, n, signal=True), b"".join(c.signal(1, 0.37).text_chunks()))
+        if kind == "peaks":                                 # every run a peak: peak_9 / peak_10 and peak_99 / peak_100 inside the pulls
+            acc.signal(r, 1, 0.37)
+            acc.call(r, 0.3, 0, 1)
+            whole = b"".join(c.signal(1, 0.37).call(0.3, 0, 1).text_chunks())
+            assert all(ln.split(b"\t")[7:9] == [b"-1", b"-1"] for ln in whole.splitlines())
+        else:                                               # column 8, and with the table column 9, are a value's text as well
+            acc.poisson(r, coverage.device_count_of(rc, MAPQ, None, 0), rc, 1, 1.0, 0, 0)
+            g = acc.signal_result(r)
+            table = g.qvalues() if kind == "p- and q-score peaks" else None
+            if table is not None:
+                acc.qvalue(r)
+            acc.call(r, 0.0, 0, 1)
+            whole = b"".join(g.call(0.0, 0, 1, qtable=table).text_chunks())
+            assert all((ln.split(b"\t")[7] != b"-1") and (ln.split(b"\t")[8] == b"-1") == (table is None) for ln in whole.splitlines())
+        assert whole.splitlines()[8].split(b"\t")[3] == b"peak_9" and whole.splitlines()[99].split(b"\t")[3] == b"peak_100"
+        CC.check_line_pulls(lambda first, n: acc.call_text(r, first, n), whole)
 
 
 def test_the_tables_life_on_the_handle(tmp_path):

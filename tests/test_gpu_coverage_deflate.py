@@ -99,6 +99,67 @@ def test_the_compressed_pulls_against_the_raw_ones(case, items):
             assert [zlib.decompress(s) for s in _split(zblob, zsizes)] == _split(blob, table[:, 4])
 
 
+def _out_bam(d, refs, reads):
+    recs = [SW.rec("q%d" % i, 16 if s else 0, refs[r][0], p, 40, (("M", l),)) for i, (r, p, l, s) in enumerate(reads)]
+    return SW.write_twins(d, "out", refs, recs)[1]
+
+
+def _out_host(refs, reads, signal):
+    c = coverage.count_host(*(np.array(x, dtype=np.int64) for x in zip(*reads)), [n for n, _l in refs], [l for _n, l in refs], [1] * len(refs), 0)
+    return c.signal(1, 0.37) if signal else c
+
+
+def _same_parts(got, z, want):
+    """A raw pull and its compressed twin against the host's: the bytes, the table, and a signal's sums bit for bit."""
+    assert got[0] == want[0] and np.array_equal(got[1], want[1]) and np.array_equal(z[1], want[1]) and len(got) == len(want) == len(z) - 1
+    assert [zlib.decompress(s) for s in _split(z[0], z[2])] == _split(want[0], want[1][:, 4])
+    for sums in got[2:] + z[3:]:
+        assert np.array_equal(sums.view(np.uint64), want[2].view(np.uint64))
+
+
+@pytest.mark.parametrize("signal", [False, True], ids=["depth", "signal"])
+@pytest.mark.parametrize("items", CC.OUT_ITEMS)
+def test_sections_of_a_pull_from_a_references_fourth_run_on(tmp_path, items, signal):
+    """k_tr_sections of both kinds, raw and compressed: a lane, a workgroup and one run more, in sections of every size around them,
+    against ``HostParts.section_chunks`` over the same runs."""
+    name = CC.OUT_REFS[1][0]
+    host = _out_host(CC.OUT_REFS, CC.OUT_READS, signal)
+    with DeviceBamReader(_out_bam(tmp_path, CC.OUT_REFS, CC.OUT_READS)) as r:
+        acc = coverage.device_count_of(r, FC.MAPQ, None, 0)
+        if signal:
+            acc.signal(r, 1, 0.37)
+        first = int(acc.ranges(r, signal)[1]) + CC.OUT_FIRST
+        assert first == CC.OUT_SHORT + CC.OUT_FIRST
+        for n in CC.OUT_SECTION_COUNTS:
+            cut = {name: tuple(x[CC.OUT_FIRST:CC.OUT_FIRST + n] for x in host.runs[name])}
+            part = coverage.Signal(cut, 1, 0.37, CC.OUT_REFS) if signal else coverage.Coverage(cut, 0, 0, CC.OUT_REFS)
+            want, = coverage.HostParts(part).section_chunks(1, 5, items, 1 << 30)
+            assert len(want[1]) == -(-n // items)
+            _same_parts(acc.sections(r, first, n, 5, items, signal), acc.sections_z(r, first, n, 5, items, signal), want)
+
+
+@pytest.mark.parametrize("signal", [False, True], ids=["depth", "signal"])
+@pytest.mark.parametrize("kept", CC.OUT_KEPT)
+def test_zoom_records_of_a_level_with_empty_bins_between(tmp_path, kept, signal):
+    """k_tr_zoom_emit of both kinds, raw and compressed: 1, 256 and 257 records, each in another slot than its bin's, in sections
+    of 1 and of 3 (the last one short), against ``HostParts.zoom_records``."""
+    refs, reads = CC.zoom_reads(kept)
+    parts = coverage.HostParts(_out_host(refs, reads, signal))
+    parts.zoom_begin(CC.OUT_ZOOM, 1, [0, 1])
+    with DeviceBamReader(_out_bam(tmp_path, refs, reads)) as r:
+        acc = coverage.device_count_of(r, FC.MAPQ, None, 0)
+        if signal:
+            acc.signal(r, 1, 0.37)
+        for items in (1, 3):
+            want = parts.zoom_records(0, items)
+            assert len(want[0]) == 32 * kept and len(want[1]) == -(-kept // items)
+            got = []
+            for pull in (acc.zoom_records, acc.zoom_records_z):         # (the only level is the last one: it frees the bins)
+                acc.zoom_begin(r, CC.OUT_ZOOM, 1, [0, 1], signal)
+                got.append(pull(r, 0, items, signal))
+            _same_parts(got[0], got[1], want)
+
+
 @pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
 def test_every_input_writes_a_file_every_reader_takes(case, tmp_path, masked):
     mask = region_mask.open_mask(BC.MASK) if masked else None
